@@ -17,9 +17,13 @@ Multi-GPU: one process per GPU. `python bench.py --gpus N` launches itself under
 running under it (WORLD_SIZE unset); RCCL (backend "nccl") broadcasts the prompt ids / voice latent from rank 0 and gathers
 the audio on rank 0. No collective sits inside the data path: candidates never interact.
 
-Prints ONE JSON line (rank 0): `roofline` = the dominant kernel family (fp16 MFMA GEMMs of the diffusion stage, HIP-event timed on the
-engine's stream inside the timed region), `roofline_decode` = the HBM-bound decode step (one event pair per hipGraph replay),
-`cpu_baseline` = the oracle (CPU restatement of the reference path) on a bounded sample at 4 threads and at all host cores.
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps steps, writes the last timed step's outputs when
+--dump-outputs DIR is given and prints the headline (`value`, `ms_per_step`, `stage_ms_per_step`, `load_ms`, `per_rank`, ...).
+With --full the line also carries: `roofline` = the dominant kernel family (fp16 MFMA GEMMs of the diffusion stage, HIP-event timed on
+the engine's stream inside the timed region), `roofline_decode` = the HBM-bound decode step (one event pair per hipGraph replay),
+`cpu_baseline` = the oracle (CPU restatement of the reference path) on a bounded sample at 4 threads and at all host cores, and the
+A/B passes after the timed region (other share_uncond setting, reference precision, AR weight modes, ragged batch, one utterance,
+first audio, CLVP).
 """
 import argparse
 import json
@@ -75,6 +79,52 @@ def synthetic_prompt(p=0):
     # SURVEY §8d: ids 255, (3 + 7j mod 250) for j < 64, 0  -> n = 66 text ids, P = 68 prompt positions; p > 0: the distinct
     # prompts of config 5 (same length, shifted ids)
     return np.array([255] + [3 + (7 * j + 11 * p) % 250 for j in range(64)] + [0], np.int32)
+
+
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000  # --dump-outputs: under 64 MB however a megabyte is counted
+
+
+def _stack_padded(arrs, dtype):
+    """[n, max shape...] with every array of the list in its leading corner, zeros elsewhere (candidates may differ in length)."""
+    shp = tuple(max(x.shape[d] for x in arrs) for d in range(arrs[0].ndim))
+    out = np.zeros((len(arrs),) + shp, dtype)
+    for i, x in enumerate(arrs):
+        out[(i,) + tuple(slice(0, n) for n in x.shape)] = x
+    return out
+
+
+def dump_outputs(path, pass_out):
+    """--dump-outputs: what the stages returned in the last timed pass, every prompt's candidates in order, as DIR/<name>.npy (float32 for the
+    computed values, float64 for ids and lengths). Above DUMP_LIMIT_BYTES in all, every array of more than 1 MB is replaced by a fixed sample
+    of its flattened elements (seed 0, sorted indices) so that the files stay within the limit. Returns {name: description} for the JSON line."""
+    arrays = {"codes": np.concatenate([np.asarray(o["codes"]).reshape(len(o["audio"]), -1) for o in pass_out]).astype(np.float64)}
+    if "latents" in pass_out[0]:
+        lats = [np.asarray(x, np.float32) for o in pass_out for x in o["latents"]]
+        mels = [np.asarray(x, np.float32) for o in pass_out for x in o["mel"]]
+        arrays["latent_rows"] = np.concatenate([np.asarray(o["latent_rows"]) for o in pass_out]).astype(np.float64)
+        arrays["latents"] = _stack_padded(lats, np.float32)
+        arrays["mel_frames"] = np.array([m.shape[1] for m in mels], np.float64)
+        arrays["mel"] = _stack_padded(mels, np.float32)
+    audio = [np.asarray(x, np.float32) for o in pass_out for x in o["audio"]]
+    arrays["audio_samples"] = np.array([len(x) for x in audio], np.float64)
+    arrays["audio"] = _stack_padded(audio, np.float32)
+    total = sum(v.nbytes for v in arrays.values())
+    big = {k for k, v in arrays.items() if v.nbytes > 1000 * 1000}
+    keep = 1.0
+    if total > DUMP_LIMIT_BYTES:
+        small = sum(v.nbytes for k, v in arrays.items() if k not in big)
+        keep = 0.99 * (DUMP_LIMIT_BYTES - small) / sum(arrays[k].nbytes for k in big)
+    os.makedirs(path, exist_ok=True)
+    info = {}
+    for k, v in arrays.items():
+        desc = {"shape": list(v.shape), "dtype": str(v.dtype)}
+        if keep < 1.0 and k in big:
+            idx = np.sort(np.random.default_rng(0).choice(v.size, int(v.size * keep), replace=False, shuffle=False))
+            v = v.reshape(-1)[idx]
+            desc = {"shape": list(v.shape), "dtype": str(v.dtype), "sample_of_shape": desc["shape"], "sample": "flat indices: sorted numpy default_rng(0).choice"}
+        np.save(os.path.join(path, k + ".npy"), v)
+        info[k] = desc
+    return info
 
 
 def ensure_models(path, quick, rank_is_writer, wait_s=1800):
@@ -194,10 +244,14 @@ def main():
     ap.add_argument("--diff-steps", type=int, default=None)
     ap.add_argument("--decode-steps", type=int, default=192, help="sampled codes per candidate (stop token masked) -> L=200, T=870")
     ap.add_argument("--quick", action="store_true", help="tiny layer counts (plumbing check only; NOT the benchmark)")
-    ap.add_argument("--prof-stride", type=int, default=13, help="1 GEMM launch in N (hashed decimation per shape class) is bracketed by a HIP event pair (roofline timing)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline event timing inside the timed region, "
+                                                          "the A/B passes after it and the CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed (codes, latents, "
+                                                                        "mels, audio; float32 / float64) as DIR/<name>.npy, under 64 MB in all (rank 0's own outputs)")
+    ap.add_argument("--prof-stride", type=int, default=13, help="with --full: 1 GEMM launch in N (hashed decimation per shape class) is bracketed by a HIP event pair (roofline timing)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-share-uncond", action="store_true", help="headline pass with the unconditioned integrator layers evaluated per candidate")
-    ap.add_argument("--no-ab", action="store_true", help="skip the extra pass that measures the other share_uncond setting")
+    ap.add_argument("--no-ab", action="store_true", help="with --full: skip the extra passes after the timed region (other share_uncond setting, option A/Bs)")
     ap.add_argument("--latency-mode", action="store_true", help="option latency_mode for the headline pass too (it only acts on diffusion batches of <= 2 048 packed rows: "
                     "--candidates 1); the single-utterance A/B below always measures both settings")
     ap.add_argument("--engine-option", action="append", default=[], metavar="KEY=VALUE", help="tts_set_option on every rank's engine before the run (A/B of an option, e.g. hoist_integrator=0)")
@@ -211,6 +265,8 @@ def main():
                                                        "runs two real engines on one GPU (test of the N > 1 path on a one-GPU box; RCCL needs one GPU per rank)")
     ap.add_argument("--allow-shared-device", action="store_true", help="let two ranks create their engine on ONE GPU (unsupported form; one-GPU test boxes only)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(self_launch(a))
@@ -318,10 +374,12 @@ def main():
 
     stage_ms = {"ar": 0.0, "diffusion": 0.0, "vocoder": 0.0}
     shape = {}
+    last_pass = []  # per prompt: what the stages of the latest pass returned (--dump-outputs)
 
     def one_pass(it, record=True):
         audio_s, n_audio = 0.0, 0
         chunks = []
+        pass_out = []
         for p in my_prompts:
             # config 3: distinct candidates per rank and per pass; configs 4/5: one seed for the whole (sharded) batch
             eng.seed(1000 * it + (rank if a.config == 3 else 17 * p))
@@ -333,6 +391,7 @@ def main():
                 shape.update(L=200, T=870, ids=[int(i) for i in ids])
                 # one os.write per line: the ranks share stderr, and print() may split a line into several writes that interleave with the other rank's
                 os.write(2, ("DRY_IDS rank %d prompt %d pass %d: %s\n" % (rank, p, it, " ".join(str(int(i)) for i in ids))).encode())
+                pass_out.append({"codes": ids, "audio": audio})
             else:
                 t_a = time.time()
                 codes, rows, lats, steps = eng.autoregressive(prompts[p], voice, B, S, mask_stop=True)
@@ -345,9 +404,11 @@ def main():
                     stage_ms["ar"] += 1e3 * (t_b - t_a); stage_ms["diffusion"] += 1e3 * (t_c - t_b); stage_ms["vocoder"] += 1e3 * (t_d - t_c)
                 Ts = [m.shape[1] for m in mels]
                 shape.update(L=int(rows[0]), T=int(Ts[0]))
+                pass_out.append({"codes": codes, "latent_rows": rows, "latents": lats, "mel": mels, "audio": audio})
             audio_s += sum(t * 256 for t in Ts) / 24000.0  # T*256/24000 per candidate (the 10 pad frames are not counted)
             n_audio += sum(len(x) for x in audio)
             chunks += audio
+        last_pass[:] = pass_out
         if dist:
             import torch
             flat = torch.from_numpy(np.concatenate(chunks) if chunks else np.zeros(0, np.float32)).to(dev)
@@ -403,7 +464,7 @@ def main():
     share = not a.no_share_uncond
     for w in range(a.warmup):
         one_pass(-1 - w, record=False)
-    if not a.dry_engine:
+    if a.full and not a.dry_engine:
         # 1 GEMM launch in 13 is bracketed by a HIP event pair (a hash of each shape class's launch counter decides: every launch position is sampled
         # equally often whatever the number of launches per step — round 5: with exactly 13 QKV launches per step a plain stride of 13 bracketed the same
         # layer every time). An event pair drains the pipeline around its launch: bracketing all ~9 600 launches of the timed region cost 5 % of the pass,
@@ -414,9 +475,10 @@ def main():
         eng.set_option("prof_stride", a.prof_stride)
         eng.prof_reset(True)
     audio_s, dt, stages = timed(a.steps, share)
+    dumped = dump_outputs(a.dump_outputs, last_pass) if a.dump_outputs and rank == 0 else None
     g_ms = g_n = g_flops = d_ms = d_n = d_bytes = 0.0
     per_kernel = {}
-    if not a.dry_engine:
+    if a.full and not a.dry_engine:
         per_kernel = {fam: eng.prof_get(fam) for fam in GEMM_FAMILIES}
         g_ms, g_n, g_flops = (sum(v[i] for v in per_kernel.values()) for i in range(3))
         d_ms, d_n, d_bytes = eng.prof_get("ar_decode_step")
@@ -424,17 +486,17 @@ def main():
     # because the masked stop token gives every candidate the same length) — under the SAME profiling setting as the headline pass
     # (event pairs on every 13th GEMM launch, every 8th diffusion step eager), so the two values are comparable
     other = None
-    if not a.no_ab and not a.dry_engine:
+    if a.full and not a.no_ab and not a.dry_engine:
         o_audio, o_dt, o_stages = timed(1, not share)
         other = {"uncond_integrator_shared": not share, "value": round(o_audio / o_dt, 3), "ms_per_step": round(1000.0 * o_dt, 2),
                  "stage_ms_per_step": o_stages}
         eng.set_option("share_uncond", 1 if share else 0)  # (rounds 1-4 left the other setting on for the option passes below)
-    if not a.dry_engine:
+    if a.full and not a.dry_engine:
         eng.prof_reset(False)
     # the reference-precision mode of the diffusion stage (option attn_f32 = 1: F32 AttentionBlock as main.cpp:3848-3875 on split-fp16 MFMA
     # operands + exact SiLU; the parity tests' mode), one pass outside the timed region: what the mode costs
     ref_prec = None
-    if world == 1 and not a.no_ab and not a.dry_engine:
+    if world == 1 and a.full and not a.no_ab and not a.dry_engine:
         eng.seed(99)
         _, _, lats_rp, _ = eng.autoregressive(prompts[0], voice, B, S, mask_stop=True)
         times = {}
@@ -456,7 +518,7 @@ def main():
     # power-of-two scale per output column: 0.39 GB), measured beside the default f32 mode on the same prompt and seed:
     # AR stage time, decode-step bandwidth, first sampled id that differs from the f32 run
     f16 = fp8 = f32_rerun = topk = None
-    if world == 1 and not a.no_ab and not a.dry_engine:
+    if world == 1 and a.full and not a.no_ab and not a.dry_engine:
         eng.seed(4242)
         t0 = time.time()
         c32, _, _, _ = eng.autoregressive(prompts[0], voice, B, S, mask_stop=True)
@@ -510,7 +572,7 @@ def main():
         f16, fp8 = reports["f16"], reports["fp8"]
     # ---- what a real batch looks like, outside the headline's timed region like the other A/B passes -------------------------
     ragged = single_ms = single_lat = first_audio = clvp = None
-    if world == 1 and not a.no_ab and not a.dry_engine and a.config == 3:
+    if world == 1 and a.full and not a.no_ab and not a.dry_engine and a.config == 3:
         eng.set_option("share_uncond", 1)
         # (a) RAGGED batch: trained weights stop every candidate at its own step (main.cpp:5188-5249); random-init ones never stop, so a stop SCHEDULE
         # (tts_ar_set_stop_schedule) ends candidate b after 0.61 S .. S codes. Decode steps then carry retired candidates (TTS_AR_RETIRE), the latent pass,
@@ -596,40 +658,6 @@ def main():
         if dist:
             dist.destroy_process_group()
         return
-    achieved = g_flops / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
-    dec_gbs = d_bytes / (d_ms * 1e-3) / 1e9 if d_ms > 0 else 0.0
-    # HBM bytes per GEMM launch from the committed PMC profile (FETCH_SIZE + WRITE_SIZE, separate rocprofv3 passes, calibration in the
-    # file's note); null when the profile is absent. bench.py does not run rocprofv3 itself.
-    traffic, traffic_src = None, None
-    for prof_name in ("r6_pmc_hbm_traffic.json", "r5_pmc_hbm_traffic.json", "r4_pmc_hbm_traffic.json", "r3_pmc_hbm_traffic.json", "r2_pmc_hbm_traffic.json", "r1_pmc_hbm_traffic.json"):
-        try:
-            prof = json.load(open(os.path.join(ROOT, "profiles", prof_name)))["kernels"]
-            gk = [v for k, v in prof.items() if "gemm_f16" in k]
-            traffic = int(sum(v["dispatches"] * v["hbm_bytes_per_launch"] for v in gk) / max(1, sum(v["dispatches"] for v in gk)))
-            traffic_src = "profiles/" + prof_name
-            break
-        except Exception:
-            pass
-    # second denominator: the fp16 MFMA peak at the shader clock the chip actually sustains under these kernels (PMC pass: GRBM_GUI_ACTIVE
-    # over the kernel's duration; 1.95-2.2 GHz under MFMA load against the 2.4 GHz the 2.5 PF figure assumes), launch-weighted over the GEMM kernels
-    sus_clk, sus_src = None, None
-    for prof_name in ("r6_pmc_mfma_util.json", "r5_pmc_mfma_util.json", "r4_pmc_mfma_util.json"):
-        try:
-            prof = json.load(open(os.path.join(ROOT, "profiles", prof_name)))["kernels"]
-            gk = [v for k, v in prof.items() if "gemm_f16" in k and v.get("dispatches", 0) >= 20]
-            sus_clk = sum(v["dispatches"] * v["avg_us"] * v["shader_clock_MHz"] for v in gk) / max(1e-9, sum(v["dispatches"] * v["avg_us"] for v in gk))
-            sus_src = "profiles/" + prof_name
-            break
-        except Exception:
-            pass
-    dec_traffic, dec_traffic_src = None, None  # L2-miss bytes fetched per decode step (PMC FETCH_SIZE pass over the decode launches, committed profile)
-    for prof_name, what in (("r6_pmc_decode_traffic.json", "round-6 pass"), ("r5_pmc_decode_traffic.json", "round-5 pass"), ("r4_pmc_decode_traffic.json", "round-4 kernels"), ("r2_pmc_decode_traffic.json", "round-2 pass: the same slabs are streamed")):
-        try:
-            dec_traffic = int(json.load(open(os.path.join(ROOT, "profiles", prof_name)))["fetch_bytes_per_step"])
-            dec_traffic_src = "profiles/%s (%s)" % (prof_name, what)
-            break
-        except Exception:
-            pass
     L, T = shape.get("L", 0), shape.get("T", 0)
     n_prompts = len(my_prompts) if a.config != 5 else 8
     out = {
@@ -653,40 +681,80 @@ def main():
                    "audio_seconds": "T*256/24000 per candidate = %.3f s (SURVEY 8d; the vocoder also emits 10 silent pad frames: %.3f s of samples)"
                                     % (T * 256 / 24000.0, ((T + 10) * 256 - 6) / 24000.0)},
         "stage_ms_per_step": stages,
-        "other_share_uncond_setting": other,
-        "ar_f32_default_rerun": f32_rerun,
-        "ar_device_topk_option": topk,
         # evaluations of the diffusion timestep MLP that disagreed with their repetition (the evaluate-twice guard): 0 unless another
         # process shares this GPU
         "diffusion_time_mlp_retries": (None if a.dry_engine else int(eng.time_mlp_retries())),
-        "ar_weights_f16_option": f16,
-        "ar_weights_fp8_option": fp8,
-        "reference_precision_option": ref_prec,
-        "ragged_batch": ragged, "single_utterance_ms": single_ms, "single_utterance_latency_mode": single_lat, "first_audio_ms": first_audio, "clvp_ms": clvp, "load_ms": load_ms,
+        "load_ms": load_ms,
         # the collective backend has seen this many ranks (all_reduce of ones) and rank 0 has gathered this many audio samples in the last pass
         "per_rank": (per_rank if per_rank else [{"rank": 0, "ms_per_step": None, "numa_node": placement["node"], "pinned_cpus": placement["cpus"]}]),
         "collective_ranks": collective_ranks, "collective_backend": (a.backend if dist else None), "gathered_samples": shape.get("gathered_samples"),
-        "roofline": {"kernel": "gemm_f16_vh_kernel + gemm_f16_conv3_vh_kernel (diffusion convs/projections)", "bound": "mfma",
-                     "achieved": round(achieved, 1), "peak": MFMA_F16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / MFMA_F16_DENSE_PEAK_TFLOPS, 4),
-                     "sustained_shader_clock_MHz": (round(sus_clk) if sus_clk else None), "sustained_clock_source": sus_src,
-                     "frac_of_sustained_clock_peak": (round(achieved / (MFMA_F16_DENSE_PEAK_TFLOPS * sus_clk / 2400.0), 4) if sus_clk else None),
-                     "sustained_clock_caveat": "the clock comes from a rocprofv3 PMC pass (GRBM_GUI_ACTIVE / kernel time), and a chip under counter collection clocks "
-                                               "LOWER than in the un-profiled run this line times (1.89-1.95 vs ~2.02 GHz in the guide's DVFS note): this fraction is biased high "
-                                               "by a few per cent; `frac` (against the 2.4 GHz peak) is the figure to quote",
-                     "traffic": traffic, "traffic_source": traffic_src, "launches_timed": int(g_n),
-                     "launch_sampling": "1 launch in %d of every shape class (hashed decimation of the class's launch counter: no period to resonate with the "
-                                        "13 / 16 launches per sampling step) is bracketed by HIP events" % a.prof_stride,
-                     "avg_launch_us": round(1000.0 * g_ms / max(g_n, 1), 2), "algorithmic_gflop_per_launch": round(g_flops / max(g_n, 1) / 1e9, 2),
-                     # per shape class: its own bound = max(MFMA floor at 2.5 PF, algorithmic bytes at the 6.29 TB/s a streaming kernel reaches)
-                     "kernels": gemm_kernel_table(per_kernel)},
-        "roofline_decode": {"kernel": "AR decode step (one hipGraph replay: 151 kernels streaming every weight once)", "bound": "hbm",
-                            "achieved": round(dec_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(dec_gbs / HBM_PEAK_GBS, 4),
-                            "traffic": dec_traffic, "traffic_source": dec_traffic_src, "steps_timed": int(d_n), "avg_step_us": round(1000.0 * d_ms / max(d_n, 1), 1),
-                            "algorithmic_mb_per_step": round(d_bytes / max(d_n, 1) / 1e6, 1)},
     }
+    if a.full:
+        achieved = g_flops / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
+        dec_gbs = d_bytes / (d_ms * 1e-3) / 1e9 if d_ms > 0 else 0.0
+        # HBM bytes per GEMM launch from the committed PMC profile (FETCH_SIZE + WRITE_SIZE, separate rocprofv3 passes, calibration in the
+        # file's note); null when the profile is absent. bench.py does not run rocprofv3 itself.
+        traffic, traffic_src = None, None
+        for prof_name in ("r6_pmc_hbm_traffic.json", "r5_pmc_hbm_traffic.json", "r4_pmc_hbm_traffic.json", "r3_pmc_hbm_traffic.json", "r2_pmc_hbm_traffic.json", "r1_pmc_hbm_traffic.json"):
+            try:
+                prof = json.load(open(os.path.join(ROOT, "profiles", prof_name)))["kernels"]
+                gk = [v for k, v in prof.items() if "gemm_f16" in k]
+                traffic = int(sum(v["dispatches"] * v["hbm_bytes_per_launch"] for v in gk) / max(1, sum(v["dispatches"] for v in gk)))
+                traffic_src = "profiles/" + prof_name
+                break
+            except Exception:
+                pass
+        # second denominator: the fp16 MFMA peak at the shader clock the chip actually sustains under these kernels (PMC pass: GRBM_GUI_ACTIVE
+        # over the kernel's duration; 1.95-2.2 GHz under MFMA load against the 2.4 GHz the 2.5 PF figure assumes), launch-weighted over the GEMM kernels
+        sus_clk, sus_src = None, None
+        for prof_name in ("r6_pmc_mfma_util.json", "r5_pmc_mfma_util.json", "r4_pmc_mfma_util.json"):
+            try:
+                prof = json.load(open(os.path.join(ROOT, "profiles", prof_name)))["kernels"]
+                gk = [v for k, v in prof.items() if "gemm_f16" in k and v.get("dispatches", 0) >= 20]
+                sus_clk = sum(v["dispatches"] * v["avg_us"] * v["shader_clock_MHz"] for v in gk) / max(1e-9, sum(v["dispatches"] * v["avg_us"] for v in gk))
+                sus_src = "profiles/" + prof_name
+                break
+            except Exception:
+                pass
+        dec_traffic, dec_traffic_src = None, None  # L2-miss bytes fetched per decode step (PMC FETCH_SIZE pass over the decode launches, committed profile)
+        for prof_name, what in (("r6_pmc_decode_traffic.json", "round-6 pass"), ("r5_pmc_decode_traffic.json", "round-5 pass"), ("r4_pmc_decode_traffic.json", "round-4 kernels"), ("r2_pmc_decode_traffic.json", "round-2 pass: the same slabs are streamed")):
+            try:
+                dec_traffic = int(json.load(open(os.path.join(ROOT, "profiles", prof_name)))["fetch_bytes_per_step"])
+                dec_traffic_src = "profiles/%s (%s)" % (prof_name, what)
+                break
+            except Exception:
+                pass
+        out.update({
+            "other_share_uncond_setting": other,
+            "ar_f32_default_rerun": f32_rerun,
+            "ar_device_topk_option": topk,
+            "ar_weights_f16_option": f16,
+            "ar_weights_fp8_option": fp8,
+            "reference_precision_option": ref_prec,
+            "ragged_batch": ragged, "single_utterance_ms": single_ms, "single_utterance_latency_mode": single_lat, "first_audio_ms": first_audio, "clvp_ms": clvp,
+            "roofline": {"kernel": "gemm_f16_vh_kernel + gemm_f16_conv3_vh_kernel (diffusion convs/projections)", "bound": "mfma",
+                         "achieved": round(achieved, 1), "peak": MFMA_F16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(achieved / MFMA_F16_DENSE_PEAK_TFLOPS, 4),
+                         "sustained_shader_clock_MHz": (round(sus_clk) if sus_clk else None), "sustained_clock_source": sus_src,
+                         "frac_of_sustained_clock_peak": (round(achieved / (MFMA_F16_DENSE_PEAK_TFLOPS * sus_clk / 2400.0), 4) if sus_clk else None),
+                         "sustained_clock_caveat": "the clock comes from a rocprofv3 PMC pass (GRBM_GUI_ACTIVE / kernel time), and a chip under counter collection clocks "
+                                                   "LOWER than in the un-profiled run this line times (1.89-1.95 vs ~2.02 GHz without counters): this fraction is biased high "
+                                                   "by a few per cent; `frac` (against the 2.4 GHz peak) is the figure to quote",
+                         "traffic": traffic, "traffic_source": traffic_src, "launches_timed": int(g_n),
+                         "launch_sampling": "1 launch in %d of every shape class (hashed decimation of the class's launch counter: no period to resonate with the "
+                                            "13 / 16 launches per sampling step) is bracketed by HIP events" % a.prof_stride,
+                         "avg_launch_us": round(1000.0 * g_ms / max(g_n, 1), 2), "algorithmic_gflop_per_launch": round(g_flops / max(g_n, 1) / 1e9, 2),
+                         # per shape class: its own bound = max(MFMA floor at 2.5 PF, algorithmic bytes at the 6.29 TB/s a streaming kernel reaches)
+                         "kernels": gemm_kernel_table(per_kernel)},
+            "roofline_decode": {"kernel": "AR decode step (one hipGraph replay: 151 kernels streaming every weight once)", "bound": "hbm",
+                                "achieved": round(dec_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(dec_gbs / HBM_PEAK_GBS, 4),
+                                "traffic": dec_traffic, "traffic_source": dec_traffic_src, "steps_timed": int(d_n), "avg_step_us": round(1000.0 * d_ms / max(d_n, 1), 1),
+                                "algorithmic_mb_per_step": round(d_bytes / max(d_n, 1) / 1e6, 1)},
+        })
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if a.dry_engine:
         out["dry_engine"] = {"ids": shape.get("ids"), "gathered_samples": shape.get("gathered_samples")}
-    if world == 1 and not a.no_cpu_baseline and not a.dry_engine:
+    if world == 1 and a.full and not a.no_cpu_baseline and not a.dry_engine:
         out["cpu_baseline"] = cpu_baseline(model_dir, voice, prompts[0], S, L, n_diff, a.quick)
     print(json.dumps(out))
     if dist:

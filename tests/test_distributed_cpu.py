@@ -169,6 +169,40 @@ def test_bench_force_dist_one_rank_gloo():
     assert out["gathered_samples"] == out["dry_engine"]["gathered_samples"] > 0
 
 
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps passes, carries none of the --full figures, and --dump-outputs writes what the
+    LAST timed pass returned as float .npy files; two runs with the same arguments write identical files (host-only contexts, --dry-engine)."""
+    import json
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("dump%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--dry-engine", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        for k in ("roofline", "roofline_decode", "cpu_baseline", "other_share_uncond_setting", "ragged_batch", "clvp_ms"):
+            assert k not in out, k
+        passes = [int(l.split("pass ")[1].split(":")[0]) for l in r.stderr.splitlines() if l.startswith("DRY_IDS")]
+        assert passes == [-1, 0, 1, 2]  # one warm-up pass, then exactly --steps timed passes
+        last_ids = [int(x) for x in [l for l in r.stderr.splitlines() if l.startswith("DRY_IDS")][-1].split(": ")[1].split()]
+        files = sorted(os.listdir(d))
+        assert files == ["audio.npy", "audio_samples.npy", "codes.npy"] and set(out["dump_outputs"]) == {f[:-4] for f in files}
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(os.path.getsize(d / f) for f in files) < 64 * 1000 * 1000
+        assert arrs["codes"][:, 0].tolist() == last_ids == out["dry_engine"]["ids"]
+        n = arrs["audio_samples"].astype(int)
+        assert arrs["audio"].shape == (16, n.max()) and all((arrs["audio"][i, :n[i]] == float(last_ids[i])).all() for i in range(16))
+        dumps.append(arrs)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
 def test_cli_devices_worker_bookkeeping_without_a_gpu(tmp_path):
     """`tortoise --devices 2 --exchange files` on a machine without a GPU (--dry-run 1: host-only contexts, the host sampler on fixed synthetic
     logits stands in for the stages): the parent re-executes itself once per shard with --shard r/2 and ONE seed, worker r draws exactly its

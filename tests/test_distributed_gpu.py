@@ -110,7 +110,7 @@ def test_bench_two_ranks_share_one_gpu():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--device-map", "0,0", "--allow-shared-device", "--quick", "--config", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--backend", "gloo", "--device-map", "0,0", "--allow-shared-device", "--quick", "--config", "4",
            "--candidates", "4", "--steps", "1", "--warmup", "0", "--decode-steps", "8", "--diff-steps", "4", "--no-cpu-baseline", "--no-ab"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]

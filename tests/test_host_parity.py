@@ -1,6 +1,6 @@
-"""CPU tests: the product's host logic (C ABI on a host-only context) against the real reference code
-(oracle/_ref/libref.so, when /root/reference was available at build time) and against the committed
-golden vectors. No device compute happens here."""
+"""CPU tests: the product's host logic (C ABI on a host-only context) against the real reference code's answers
+(stored under tests/golden/, and live from oracle/_ref/libref.so where the reference checkout was available at build
+time) and against the committed golden vectors. No device compute happens here."""
 import ctypes as C
 import json
 import os
@@ -59,12 +59,19 @@ def test_tokenizer_golden(host):
         assert list(host.tokenize(msg)) == ids, msg
 
 
+def _fuzz_golden():
+    """The reference's own answers to the seeded fuzz inputs below (tests/golden/make_fuzz_golden.py, from oracle/_ref/libref.so)."""
+    return np.load(os.path.join(GOLDEN, "reference_fuzz_golden.npz"))
+
+
 def test_tokenizer_fuzz_vs_reference(host, oracle):
+    """300 random messages: the product's and the oracle's tokenizer against the reference's (stored answers; and live, where libref.so was built)."""
     R = oracle.ref()
-    if R is None:
-        pytest.skip("oracle/_ref/libref.so not built (no /root/reference)")
+    g = _fuzz_golden()
+    stored = np.split(g["tok_ids"], np.cumsum(g["tok_len"])[:-1])
     host.tokenizer_load(os.path.join(MODELS, "tokenizer.json"))
-    R.ref_tokenizer_init(os.path.join(MODELS, "tokenizer.json").encode())
+    if R is not None:
+        R.ref_tokenizer_init(os.path.join(MODELS, "tokenizer.json").encode())
     tk = oracle.Tokenizer(os.path.join(MODELS, "tokenizer.json"))
     rs = np.random.RandomState(0)
     alphabet = list("abcdefghijklmnopqrstuvwxyz     .,!?'-\"[]0123456789ABCXYZ;:()\t\n") + ["[SPACE]", "[STOP]", "'s", "'re", "é", "ß"]
@@ -72,11 +79,13 @@ def test_tokenizer_fuzz_vs_reference(host, oracle):
     saved = os.dup(2)
     os.dup2(devnull, 2)  # both sides print "unknown token" to stderr
     try:
-        for _ in range(300):
+        for i in range(300):
             msg = "".join(rs.choice(alphabet) for _ in range(rs.randint(0, 60)))
-            out = np.empty(2048, np.int32)
-            n = R.ref_tokenize(msg.encode("utf-8"), out, 2048)
-            want = list(out[:n])
+            want = list(stored[i])
+            if R is not None:
+                out = np.empty(2048, np.int32)
+                n = R.ref_tokenize(msg.encode("utf-8"), out, 2048)
+                assert list(out[:n]) == want, repr(msg)
             assert list(host.tokenize(msg)) == want, repr(msg)
             assert list(tk.encode(msg)) == want, repr(msg)
     finally:
@@ -96,9 +105,10 @@ def test_sampler_golden(host, oracle):
 
 
 def test_sampler_fuzz_vs_reference(host, oracle):
+    """150 random logit batches: the product's sampler against the reference's (stored answers; and live, where libref.so was built)."""
     R = oracle.ref()
-    if R is None:
-        pytest.skip("oracle/_ref/libref.so not built (no /root/reference)")
+    g = _fuzz_golden()
+    at = 0
     rs = np.random.RandomState(1)
     for trial in range(150):
         B = 16 if trial % 10 == 9 else rs.randint(1, 6)  # B >= 4 runs on the sampler thread pool
@@ -112,13 +122,18 @@ def test_sampler_fuzz_vs_reference(host, oracle):
             ids[:, :-1] = 1
             ids[:, -1] = 8192
         seed = int(rs.randint(1 << 30))
-        R.ref_seed(seed)
+        want, want_u = g["samp_ids"][at:at + B], g["samp_next_uniform"][trial]
+        at += B
+        if R is not None:
+            R.ref_seed(seed)
+            live = np.empty(B, np.int32)
+            R.ref_process_logits_and_sample(logits.reshape(-1), ids.reshape(-1), ids.size, B, live, None)
+            assert (live == want).all() and R.ref_uniform() == want_u, trial
         host.seed(seed)
-        want = np.empty(B, np.int32)
-        R.ref_process_logits_and_sample(logits.reshape(-1), ids.reshape(-1), ids.size, B, want, None)
         got = host.sample(logits, ids)
         assert (got == want).all(), (trial, got, want)
-        assert host.rng_uniform() == R.ref_uniform()
+        assert host.rng_uniform() == want_u
+    assert at == len(g["samp_ids"])
 
 
 def test_sampler_from_prefiltered_list_equals_full_row(pkg, host):
@@ -314,13 +329,20 @@ def test_bulk_normal_draws_equal_single_draws(pkg, host, oracle):
             assert (x.view(np.uint32) == y.view(np.uint32)).all(), (seed, n)
             assert host.rng_uniform() == slow.rng_uniform(), (seed, n)
     slow.close()
-    R = oracle.ref()
-    if R is None:
-        pytest.skip("oracle/_ref/libref.so not built (no /root/reference): the comparison with the single-draw form above has run")
+    R = oracle.ref()  # the reference's answers are stored (tests/golden/make_fuzz_golden.py); compared live as well where libref.so was built
+    g = _fuzz_golden()
     host.seed(77)
-    R.ref_seed(77)
+    if R is not None:
+        R.ref_seed(77)
+    at = 0
     for n in (87000, 4097, 5, 20000):
-        want = np.empty(n, np.float32)
-        R.ref_normal_fill(want, n)
+        want = g["normal_seed77"][at:at + n]
+        at += n
+        if R is not None:
+            live = np.empty(n, np.float32)
+            R.ref_normal_fill(live, n)
+            assert (live.view(np.uint32) == want.view(np.uint32)).all(), n
         assert (host.rng_normal(n).view(np.uint32) == want.view(np.uint32)).all(), n
-    assert host.rng_uniform() == R.ref_uniform()
+    assert host.rng_uniform() == g["normal_seed77_next_uniform"][0]
+    if R is not None:
+        assert R.ref_uniform() == g["normal_seed77_next_uniform"][0]

@@ -62,21 +62,26 @@ def test_padding_and_trim(oracle):
     assert p[0] == 8192 and p[501] == 8193 and list(p[1:6]) == [5, 6, 83, 83, 7]
     assert list(p[498:501]) == [45, 45, 248] and (p[6:498] == 83).all()
     assert oracle.trimmed_rows(p) == 5 + 8  # rows kept until MORE than 8 consecutive 83s
-    R = oracle.ref()
-    if R is not None:
-        rs = np.random.RandomState(3)
-        for _ in range(20):
-            n = rs.randint(1, 400)
-            c = rs.choice([83, 83, 17, 4000, 8193, 8139], n).astype(np.int32)
-            want = np.empty(502, np.int32)
-            R.ref_apply_padding(c, n, want)
-            got = oracle.apply_padding(c)
-            assert (got == want).all()
-            lat = rs.randn(1, 500, 1024).astype(np.float32)
+    R = oracle.ref()  # the reference's answers are stored (tests/golden/make_fuzz_golden.py); compared live as well where libref.so was built
+    g = np.load(os.path.join(GOLDEN, "reference_fuzz_golden.npz"))
+    rs = np.random.RandomState(3)
+    for i in range(20):
+        n = rs.randint(1, 400)
+        c = rs.choice([83, 83, 17, 4000, 8193, 8139], n).astype(np.int32)
+        want = g["pad_want"][i]
+        if R is not None:
+            live = np.empty(502, np.int32)
+            R.ref_apply_padding(c, n, live)
+            assert (live == want).all()
+        got = oracle.apply_padding(c)
+        assert (got == want).all()
+        lat = rs.randn(1, 500, 1024).astype(np.float32)
+        if R is not None:
             out = np.empty(500 * 1024, np.float32)
             rows = np.empty(1, np.int32)
-            R.ref_trim_latents(lat.reshape(-1), want, 1, out, rows)
-            assert rows[0] == oracle.trimmed_rows(got)
+            R.ref_trim_latents(lat.reshape(-1), np.ascontiguousarray(want), 1, out, rows)
+            assert rows[0] == g["trim_rows"][i]
+        assert g["trim_rows"][i] == oracle.trimmed_rows(got)
 
 
 def test_oracle_stages_run_and_are_consistent(oracle, small_models, voice):

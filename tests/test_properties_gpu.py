@@ -175,13 +175,13 @@ def test_cli_end_to_end(small_models, tmp_path):
 
 
 def test_bench_contract_quick():
-    """bench.py prints ONE JSON line with the contract's keys (tiny layer counts: plumbing only, not a measurement)."""
+    """bench.py --full prints ONE JSON line with the contract's keys (tiny layer counts: plumbing only, not a measurement)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--quick", "--steps", "1", "--warmup", "1", "--candidates", "4",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--quick", "--steps", "1", "--warmup", "1", "--candidates", "4",
                         "--decode-steps", "24", "--diff-steps", "4"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -197,3 +197,32 @@ def test_bench_contract_quick():
     assert abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3 and "traffic" in rf
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["unit"] == d["unit"] and cb["sample"]
+
+
+def test_bench_plain_quick_dumps_outputs(tmp_path):
+    """A plain bench.py run (no --full): the headline keys only, and --dump-outputs writes the last timed pass's codes, latents, mels and audio
+    (tiny layer counts: plumbing only, not a measurement)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--quick", "--steps", "2", "--warmup", "1", "--candidates", "4",
+                        "--decode-steps", "24", "--diff-steps", "4", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "stage_ms_per_step", "load_ms"):
+        assert k in out, k
+    for k in ("roofline", "roofline_decode", "cpu_baseline", "other_share_uncond_setting", "ragged_batch", "clvp_ms"):
+        assert k not in out, k
+    assert out["steps"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0 and out["diffusion_time_mlp_retries"] == 0
+    a = {k: np.load(d / (k + ".npy")) for k in ("codes", "latent_rows", "latents", "mel_frames", "mel", "audio_samples", "audio")}
+    assert sorted(os.listdir(d)) == sorted(k + ".npy" for k in a) and set(out["dump_outputs"]) == set(a)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert a["codes"].shape[0] == 4 and (a["codes"] >= 0).all() and (a["codes"] < 8194).all()
+    rows, T, n = (a[k].astype(int) for k in ("latent_rows", "mel_frames", "audio_samples"))
+    assert a["latents"].shape == (4, rows.max(), 1024) and a["mel"].shape == (4, 100, T.max()) and a["audio"].shape == (4, n.max())
+    assert all(np.abs(a["audio"][i, :n[i]]).max() > 0 and np.abs(a["mel"][i, :, :T[i]]).max() > 0 for i in range(4))
