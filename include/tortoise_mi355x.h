@@ -47,8 +47,10 @@ enum { TTS_VOCAB_MEL = 8194, TTS_DMODEL = 1024, TTS_MEL_CH = 100, TTS_CODES = 50
  *   6 = round 6: options "latency_mode", "fp16_check"; tts_diffusion_fp16_check, tts_device_numa_node, tts_pin_to_device_numa_node; the split proj_out weight is
  *       scaled per tensor
  *   5 = round 5: tts_ar_set_stop_schedule, tts_version; option "attn_proj_f16"; the default AttentionBlock multiplies proj_out on an F32-accurate
- *       (split fp16 pair) weight. */
-#define TTS_API_VERSION 6
+ *       (split fp16 pair) weight.
+ *   7 = several prompts in one autoregressive pass: tts_ar_begin_multi, tts_autoregressive_multi, tts_split_text, tts_host_ar_stop_run (after
+ *       tts_ar_begin_multi, tts_ar_prefill / tts_ar_step / tts_ar_step_sample / tts_ar_latents work on the whole batch of all prompts). */
+#define TTS_API_VERSION 7
 int tts_version(void);
 
 /* replaces ggml_backend_cuda_init(0) (main.cpp:651, 1213, 1777). device = HIP ordinal; returns NULL
@@ -218,6 +220,37 @@ int tts_ar_set_stop_schedule(tts_ctx *ctx, const int32_t *stop_at, int n_candida
  * waits for), 0 = it was cut at max_steps (TTS_AR_RETIRE / TTS_AR_MASK_STOP) and padded like a finished one. */
 int tts_ar_stop_status(tts_ctx *ctx, int32_t *stopped_out, int n_candidates);
 
+/* ---- several prompts in one autoregressive pass (API version 7; the reference runs one prompt per call) ------------------------ */
+/* A batch of G PROMPT GROUPS: text_ids holds the G prompts back to back, prompt g has n_text[g] ids (1 .. 404, each < 256) and n_cand[g] >= 1 candidates,
+ * which are the contiguous range [c0_g, c0_g + n_cand[g]) of the B = sum n_cand candidates (c0_g = n_cand[0] + .. + n_cand[g-1]). One voice latent for all
+ * (the diffusion stage's voice is a weight of the loaded model). The decode steps of all groups run in lock-step — mel position id step_i + 2 for every row —
+ * and only the context length differs per row: n_past = n_text[g] + 2 + step_i. Every argument is checked before any device work (TTS_ERR_ARG: G < 1,
+ * n_cand < 1, n_text < 1, an id >= 256; TTS_ERR_LIMIT: a prompt > 404 ids, max_steps + 2 > 608, longest prompt + 2 + max_steps + 1 > 1024 positions).
+ * After tts_ar_begin_multi: tts_ar_prefill / tts_ar_step return [B][8194] in global candidate order (a group's prefill rows are its prompt's logits),
+ * tts_ar_step_sample works as after tts_ar_begin, tts_ar_latents takes n_candidates = B and evaluates every candidate against its own prompt. Every row is
+ * bit-identical to the same prompt run alone through tts_ar_begin (the decode step is batch-invariant). G = 1 is tts_ar_begin. */
+int tts_ar_begin_multi(tts_ctx *ctx, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voice1024, const int32_t *n_cand,
+                       int max_steps);
+/* autoregressive() per group inside ONE decode loop. Outputs in global candidate order as tts_autoregressive's: codes_out [B][502], rows_out [B], latents_out
+ * the trimmed latents of all candidates back to back (capacity B*500*1024 floats), steps_out: sampling iterations run.
+ *   Stop rule, strict mode: per group — a candidate's sequence freezes at its first 8193, and a group ENDS in the first iteration where all of its candidates
+ *   sample 8193; from then on its rows are fed 8193 and their samples ignored (their uniforms are still drawn). The loop ends when every group has ended;
+ *   reaching max_steps fails with TTS_ERR_LIMIT. TTS_AR_MASK_STOP / TTS_AR_RETIRE as in tts_autoregressive. tts_ar_set_stop_schedule and tts_ar_stop_status
+ *   take global candidate indices.
+ *   RNG: the uniforms are those of one batch of B candidates, so group g's codes equal a tts_autoregressive of prompt g alone with options
+ *   rng_shard_offset = c0_g, rng_shard_total = B and the same seed. n_prompts = 1 is tts_autoregressive, byte for byte (RNG state afterwards included). */
+int tts_autoregressive_multi(tts_ctx *ctx, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voice1024, const int32_t *n_cand,
+                             int max_steps, unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out);
+/* Splits a message into chunks that each tokenize (tts_tokenize, the 255 ... 0 wrapper included) to at most max_ids (3 .. 404) ids. Host only (works on a
+ * device = -1 context with a tokenizer loaded). The rule (ours; the reference reads one message):
+ *   - a sentence ends after '.', '!' or '?' followed by whitespace or the end of the text;
+ *   - whole sentences are packed greedily into a chunk while the chunk's id count is <= max_ids;
+ *   - a sentence that does not fit alone is cut after the last ',', ';', ':' or whitespace at which the piece still fits, or — with no such place — at the
+ *     longest prefix that fits (a hard cut between two UTF-8 characters);
+ *   - chunks are trimmed of whitespace; no chunk is empty (an empty or all-whitespace message gives 0 chunks).
+ * starts_out[k] / lens_out[k]: byte range of chunk k in `message`. Returns the number of chunks (only the first `cap` are written) or a negative status. */
+int tts_split_text(tts_ctx *ctx, const char *message, int max_ids, int32_t *starts_out, int32_t *lens_out, int cap);
+
 /* ---- candidate re-ranking (not in the reference) -------------------------------------------- */
 /* Score of every candidate = cosine similarity of the text latent and the candidate's speech-code latent x exp(temperature); the
  * caller keeps the arg-max (upstream tortoise-tts api.py; the reference keeps candidate 0, main.cpp:6575).
@@ -300,6 +333,12 @@ int tts_host_sample_row(const float *row8194, const int32_t *penalty_ids, int n_
 int tts_host_sample_prefiltered(const float *row8194, const int32_t *penalty_ids, int n_ids, float uniform, int keep);
 int tts_host_pad_codes(const int32_t *codes, int n, int32_t *out502);
 int tts_host_trimmed_rows(const int32_t *codes502);
+/* tts_autoregressive_multi's stop bookkeeping on scripted samples (random-init weights never sample the stop token): samples [max_steps][B] = what the
+ * sampler returns at each iteration, n_cand [G] the groups, flags and stop_at [B] (or NULL) as in tts_autoregressive_multi. codes_out [B][502] (padded like the
+ * driver's), stopped_out [B] (tts_ar_stop_status), *steps_out; inputs_out [max_steps][B] (may be NULL): the token fed to the decode step after each
+ * iteration. Returns TTS_OK, or TTS_ERR_LIMIT when strict mode reaches max_steps. */
+int tts_host_ar_stop_run(const int32_t *n_cand, int G, const int32_t *samples, int max_steps, unsigned flags, const int32_t *stop_at, int32_t *codes_out,
+                         int32_t *stopped_out, int32_t *steps_out, int32_t *inputs_out);
 /* Mel front-end of the two voice-conditioning encoders (host arithmetic, f64 inside; no counterpart in the reference, which has no audio input):
  * STFT n_fft = win = 1024, hop 256, periodic Hann, centre = true with reflect padding, frames = n / 256 + 1 (tts_host_mel_frames); n > 512.
  * tts_host_mel_diffusion100: 24 kHz audio -> [100][frames], upstream TacotronSTFT(1024, 256, 1024, 100, 24000, 0, 12000) magnitude mel (librosa

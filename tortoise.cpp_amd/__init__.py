@@ -64,6 +64,10 @@ def lib():
         "tts_host_sample_row": (ci, [_f32p, _i32p, ci, cf]), "tts_host_sample_prefiltered": (ci, [_f32p, _i32p, ci, cf, ci]),
         "tts_autoregressive": (ci, [vp, _i32p, ci, _f32p, ci, ci, C.c_uint, _i32p, _i32p, vp, _i32p]),
         "tts_ar_stop_status": (ci, [vp, _i32p, ci]), "tts_ar_set_stop_schedule": (ci, [vp, C.c_void_p, ci]),
+        "tts_ar_begin_multi": (ci, [vp, _i32p, _i32p, ci, _f32p, _i32p, ci]),
+        "tts_autoregressive_multi": (ci, [vp, _i32p, _i32p, ci, _f32p, _i32p, ci, C.c_uint, _i32p, _i32p, vp, _i32p]),
+        "tts_split_text": (ci, [vp, C.c_char_p, ci, _i32p, _i32p, ci]),
+        "tts_host_ar_stop_run": (ci, [_i32p, ci, _i32p, ci, C.c_uint, vp, _i32p, _i32p, _i32p, vp]),
         "tts_diffusion_frames": (ci, [ci]),
         "tts_diffusion_forward": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p]),
         "tts_diffusion": (ci, [vp, _f32p, _i32p, ci, ci, vp, ci, _f32p]),
@@ -246,6 +250,46 @@ class Engine:
                 off += r
         return codes, rows, lats, int(steps[0])
 
+    def ar_begin_multi(self, prompts, voice, n_cand, max_steps):
+        """Several prompts in one batch: prompt g (text ids) gets n_cand[g] candidates, candidates in prompt order. ar_prefill / ar_step / ar_step_sample /
+        ar_latents then work on all sum(n_cand) rows."""
+        ids, lens, nc = _prompt_args(prompts, n_cand)
+        self.B = int(nc.sum())
+        self._ck(self.L.tts_ar_begin_multi(self.h, ids, lens, len(lens), np.ascontiguousarray(voice, np.float32), nc, max_steps))
+
+    def autoregressive_multi(self, prompts, voice, n_cand, max_steps, mask_stop=False, retire=False, want_latents=True):
+        """autoregressive() of every prompt inside one decode loop. Returns (codes, rows, latents, steps): per prompt g codes [n_cand[g], 502], rows
+        [n_cand[g]] and the list of its candidates' trimmed latents (None without want_latents); steps = sampling iterations of the shared loop."""
+        ids, lens, nc = _prompt_args(prompts, n_cand)
+        B = int(nc.sum())
+        codes = np.empty((B, 502), np.int32)
+        rows = np.empty(B, np.int32)
+        steps = np.zeros(1, np.int32)
+        lat = np.empty((B * 500, DMODEL), np.float32) if want_latents else None
+        self._ck(self.L.tts_autoregressive_multi(self.h, ids, lens, len(lens), np.ascontiguousarray(voice, np.float32), nc, max_steps,
+                                                 (AR_MASK_STOP if mask_stop else 0) | (AR_RETIRE if retire else 0), codes.reshape(-1), rows, _ptr(lat), steps))
+        c0 = np.concatenate([[0], np.cumsum(nc)])
+        out_codes = [codes[c0[g]:c0[g + 1]].copy() for g in range(len(nc))]
+        out_rows = [rows[c0[g]:c0[g + 1]].copy() for g in range(len(nc))]
+        out_lats = None
+        if want_latents:
+            out_lats, off = [], 0
+            for g in range(len(nc)):
+                lg = []
+                for r in out_rows[g]:
+                    lg.append(lat[off:off + r].copy())
+                    off += r
+                out_lats.append(lg)
+        return out_codes, out_rows, out_lats, int(steps[0])
+
+    def split_text(self, message, max_ids):
+        """Chunks of `message` that each tokenize to at most max_ids ids (tts_split_text's rule): a list of strings."""
+        raw = message.encode("utf-8")
+        cap = len(raw) + 1
+        starts, lens = np.empty(cap, np.int32), np.empty(cap, np.int32)
+        n = self._ck(self.L.tts_split_text(self.h, raw, max_ids, starts, lens, cap))
+        return [raw[starts[k]:starts[k] + lens[k]].decode("utf-8") for k in range(n)]
+
     def ar_stop_status(self, B):
         """Per candidate of the last autoregressive() call: 1 = ended in a sampled stop token, 0 = cut at max_steps."""
         out = np.zeros(B, np.int32)
@@ -403,6 +447,28 @@ def host_pad_codes(codes):
     if rc:
         raise TtsError("tts_host_pad_codes failed (%d)" % rc)
     return out
+
+
+def _prompt_args(prompts, n_cand):
+    lens = np.array([len(p) for p in prompts], np.int32)
+    ids = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32).reshape(-1) for p in prompts]) if len(prompts) else np.zeros(0, np.int32), np.int32)
+    nc = np.ascontiguousarray(np.broadcast_to(np.asarray(n_cand, np.int32), lens.shape) if np.ndim(n_cand) == 0 else np.asarray(n_cand, np.int32), np.int32)
+    return ids, lens, nc
+
+
+def host_ar_stop_run(n_cand, samples, max_steps, flags=0, stop_at=None):
+    """tts_autoregressive_multi's stop bookkeeping on scripted samples [max_steps, B] (no device). Returns (status, codes [B,502], stopped [B], steps,
+    inputs [max_steps, B]: the tokens fed to the decode step after each iteration)."""
+    nc = np.ascontiguousarray(n_cand, np.int32)
+    B = int(nc.sum())
+    smp = np.ascontiguousarray(samples, np.int32).reshape(max_steps, B)
+    sa = None if stop_at is None else np.ascontiguousarray(stop_at, np.int32)
+    codes = np.zeros((B, 502), np.int32)
+    stopped = np.zeros(B, np.int32)
+    steps = np.zeros(1, np.int32)
+    inputs = np.full((max_steps, B), -1, np.int32)
+    rc = lib().tts_host_ar_stop_run(nc, len(nc), smp.reshape(-1), max_steps, flags, _ptr(sa), codes.reshape(-1), stopped, steps, _ptr(inputs))
+    return rc, codes, stopped, int(steps[0]), inputs
 
 
 def host_trimmed_rows(codes502):

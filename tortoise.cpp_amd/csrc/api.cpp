@@ -9,6 +9,8 @@
 
 namespace tts {
 int ar_begin(tts_ctx *, const int32_t *, int, const float *, int, int);
+int ar_begin_groups(tts_ctx *, const int32_t *, const int *, int, const float *, const int *, int);
+int ar_latents_group(tts_ctx *, int, const int32_t *, int, float *);
 int ar_prefill(tts_ctx *, float *);
 int ar_step(tts_ctx *, const int32_t *, int, float *, int mode);
 const int32_t *ar_host_lists(tts_ctx *);
@@ -355,13 +357,17 @@ int tts_sample(tts_ctx *c, const float *logits, const int32_t *ids, int ids_per_
   return guarded(c, [&] { sample_candidates(c, logits, ids, ids_per_cand, B, out); return (int)TTS_OK; });
 }
 
-// autoregressive(), main.cpp:5042-5367.
-static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, int B, int max_steps,
+// autoregressive(), main.cpp:5042-5367, for G prompt groups in one decode loop (tts_autoregressive: G = 1; tts_autoregressive_multi). Group g's
+// prompt is text_ids[t0_g .. + n_text[g]), its candidates [c0_g, c0_g + n_cand[g]) of the batch.
+static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n_text, int G, const float *voice, const int *n_cand, int max_steps,
                                unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
   static const bool timing = getenv("TTS_TIMING") != nullptr; // developer aid: host-side breakdown of the stage on stderr
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_begin = now(), t_sample = 0, t_step = 0;
   if (!codes_out || !rows_out) return fail(c, TTS_ERR_ARG, "tts_autoregressive: null output");
+  if (G < 1 || !n_text || !n_cand) return fail(c, TTS_ERR_ARG, "tts_autoregressive: bad argument");
+  int B = 0, P_max = 0;
+  for (int g = 0; g < G; g++) { B += n_cand[g] > 0 ? n_cand[g] : 0; P_max = std::max(P_max, n_text[g] + 2); }
   if (max_steps > 500) return fail(c, TTS_ERR_LIMIT, "max_steps %d exceeds the 500 codes apply_padding accepts", max_steps);
   // The stop schedule (tts_ar_set_stop_schedule: a bench / test device, not a reference feature) is checked BEFORE any device work, applies only to calls that pass
   // TTS_AR_MASK_STOP | TTS_AR_RETIRE (the combination it is documented for: a strict call is never truncated by a forgotten schedule) and says so on stderr once.
@@ -371,7 +377,7 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, int n_text, 
     if (!warned) { fprintf(stderr, "tts_autoregressive: a stop schedule is set but the call does not pass TTS_AR_MASK_STOP | TTS_AR_RETIRE: ignored\n"); warned = true; }
   }
   if (sched && (int)c->stop_schedule.size() != B) return fail(c, TTS_ERR_ARG, "tts_autoregressive: the stop schedule holds %d candidates, the call %d", (int)c->stop_schedule.size(), B);
-  int rc = ar_begin(c, text_ids, n_text, voice, B, max_steps);
+  int rc = ar_begin_groups(c, text_ids, n_text, G, voice, n_cand, max_steps);
   if (rc) return rc;
   const int V = TTS_VOCAB_MEL;
   std::vector<float> logits0((size_t)B * V);
@@ -380,22 +386,24 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, int n_text, 
   float *logits = logits0.data(); // after the first step: the pinned buffer the decode graph copies into (no extra host copy)
   const double t_after_prefill = now();
   // mel_transformer_inputs_vector: [1 ... 1, 8192] per candidate at step 0 (5095-5105), afterwards
-  // the previous samples (5208-5217).
-  const int P = n_text + 2;
+  // the previous samples (5208-5217). Several prompts: every row is padded to the longest prompt's P with more 1s — the penalty is applied once per
+  // DISTINCT id (sample_one / sample_one_list skip repeated ids; the literal form recomputes l[id] from the unpenalised logit), so the padded row
+  // penalises exactly what the group's own row does (tests/test_multi_prompt_cpu.py checks it on the sampler).
+  const int P = P_max;
   std::vector<int32_t> ids((size_t)P * B, 1);
   for (int b = 0; b < B; b++) ids[(size_t)b * P + P - 1] = 8192;
   int ids_per_cand = P;
-  std::vector<std::vector<int>> seq(B);
   std::vector<int32_t> samples(B);
-  // Stop rule. Reference (strict, always for B == 1): the loop ends only in an iteration where ALL B samples are 8193
-  // (main.cpp:5214-5222), a candidate's sequence freezes at its first 8193 (5210-5213). TTS_AR_RETIRE (throughput mode,
-  // SURVEY 8e): a candidate retires at its first 8193 — from then on its input token is forced to 8193 and its samples are
-  // ignored — the loop ends when every candidate has retired, and reaching max_steps pads and returns instead of failing.
+  // Stop rule (ArStopBook, host_logic.cpp). Reference (strict, always for B == 1): the loop ends only in an iteration where ALL B samples are 8193
+  // (main.cpp:5214-5222), a candidate's sequence freezes at its first 8193 (5210-5213); several prompts: that rule per group, and an ended group's rows
+  // are fed 8193. TTS_AR_RETIRE (throughput mode): a candidate retires at its first 8193 — from then on its input token is forced to 8193
+  // and its samples are ignored — the loop ends when every candidate has retired, and reaching max_steps pads and returns instead of failing.
   // The uniforms are consumed exactly as in strict mode (two per candidate and step, candidate order), so every
   // sequence is the one strict mode would have produced.
   const bool retire = (flags & TTS_AR_RETIRE) != 0;
   if ((rc = shard_check(c, B))) return rc;
-  std::vector<char> done(B, 0);
+  ArStopBook book;
+  book.init(n_cand, G);
   std::vector<int32_t> next; // the samples of the coming iteration when the device-top-k step already produced them
   bool have_next = false;
   c->topk_fallbacks = 0;
@@ -409,17 +417,11 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, int n_text, 
       sample_candidates(c, logits, ids.data(), ids_per_cand, B, samples.data());
       t_sample += now() - t0;
     }
-    int stops = 0;
-    for (int b = 0; b < B; b++) {
-      if (sched && i == c->stop_schedule[b]) samples[b] = 8193; // tts_ar_set_stop_schedule
-      if (retire && done[b]) { samples[b] = 8193; stops++; continue; }
-      if (!(seq[b].size() > 0 && seq[b].back() == 8193)) seq[b].push_back(samples[b]);
-      if (samples[b] == 8193) { stops++; done[b] = 1; }
-    }
+    const bool all_ended = book.step(samples.data(), i, retire, sched ? c->stop_schedule.data() : nullptr);
     ids.assign(samples.begin(), samples.end());
     ids_per_cand = 1;
     i++;
-    if (stops == B) break;
+    if (all_ended) break;
     if (i >= max_steps) {
       if ((flags & TTS_AR_MASK_STOP) || retire) break;
       return fail(c, TTS_ERR_LIMIT, "no stop token within %d steps", max_steps);
@@ -437,40 +439,44 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, int n_text, 
     t0 = now();
     next.resize(B);
     if (sample_candidates_list(c, ar_host_lists(c), ids.data(), 1, B, next.data(), [&](int b) { return ar_fetch_logits_row(c, b); }, &c->topk_fallbacks,
-                               retire ? done.data() : nullptr))
+                               book.retired.data()))
       return fail(c, TTS_ERR_HIP, "tts_autoregressive: fetching a logits row failed");
     t_sample += now() - t0;
     have_next = true;
   }
   const double t_after_loop = now();
   if (steps_out) *steps_out = i;
+  std::vector<std::vector<int>> &seq = book.seq;
   c->ar_stopped.assign(B, 0); // who was cut at max_steps (TTS_AR_RETIRE / TTS_AR_MASK_STOP): tts_ar_stop_status
   for (int b = 0; b < B; b++) c->ar_stopped[b] = (!seq[b].empty() && seq[b].back() == 8193) ? 1 : 0;
-  int max_rows = 0;
-  for (int b = 0; b < B; b++) {
-    if (seq[b].size() > 500) seq[b].resize(500); // the reference asserts (main.cpp:4517)
-    pad_codes(seq[b]);
-    std::copy(seq[b].begin(), seq[b].end(), codes_out + (size_t)b * 502);
-    rows_out[b] = trimmed_latent_rows(codes_out + (size_t)b * 502);
-    max_rows = std::max(max_rows, rows_out[b]);
-  }
+  std::vector<int> max_rows(G, 0);
+  for (int g = 0; g < G; g++)
+    for (int b = book.c0[g]; b < book.c0[g] + n_cand[g]; b++) {
+      if (seq[b].size() > 500) seq[b].resize(500); // the reference asserts (main.cpp:4517)
+      pad_codes(seq[b]);
+      std::copy(seq[b].begin(), seq[b].end(), codes_out + (size_t)b * 502);
+      rows_out[b] = trimmed_latent_rows(codes_out + (size_t)b * 502);
+      max_rows[g] = std::max(max_rows[g], rows_out[b]);
+    }
   if (!latents_out) return TTS_OK;
-  // latent pass over the mel prefix that trim_latents keeps (causal: rows beyond it cannot matter)
-  const int n_mel = std::min(502, max_rows + 1);
-  const int n_out = std::min(500, n_mel);
-  std::vector<float> lat((size_t)B * n_out * TTS_DMODEL);
+  // latent pass over the mel prefix that trim_latents keeps (causal: rows beyond it cannot matter), per group over its own prompt and rows
   const double t_before_lat = now();
-  if ((rc = ar_latents(c, codes_out, B, n_mel, lat.data()))) return rc;
+  size_t off = 0;
+  for (int g = 0; g < G; g++) {
+    const int n_mel = std::min(502, max_rows[g] + 1);
+    const int n_out = std::min(500, n_mel);
+    std::vector<float> lat((size_t)n_cand[g] * n_out * TTS_DMODEL);
+    if ((rc = ar_latents_group(c, g, codes_out + (size_t)book.c0[g] * 502, n_mel, lat.data()))) return rc;
+    for (int k = 0; k < n_cand[g]; k++) {
+      const int b = book.c0[g] + k;
+      std::copy(lat.begin() + (size_t)k * n_out * TTS_DMODEL, lat.begin() + ((size_t)k * n_out + rows_out[b]) * TTS_DMODEL, latents_out + off);
+      off += (size_t)rows_out[b] * TTS_DMODEL;
+    }
+  }
   if (timing)
     fprintf(stderr, "[tts timing] AR: begin %.1f ms, prefill %.1f, loop %.1f (steps %.1f in %d, sampler %.1f), latents %.1f, total %.1f\n",
             t_after_begin - t_begin, t_after_prefill - t_after_begin, t_after_loop - t_after_prefill, t_step, i - 1, t_sample,
             now() - t_before_lat, now() - t_begin);
-  size_t off = 0;
-  for (int b = 0; b < B; b++) {
-    std::copy(lat.begin() + (size_t)b * n_out * TTS_DMODEL, lat.begin() + ((size_t)b * n_out + rows_out[b]) * TTS_DMODEL,
-              latents_out + off);
-    off += (size_t)rows_out[b] * TTS_DMODEL;
-  }
   return TTS_OK;
 }
 
@@ -478,7 +484,34 @@ int tts_autoregressive(tts_ctx *c, const int32_t *text_ids, int n_text, const fl
                        unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
   NEED_CTX(c);
   return guarded(c, [&] {
-    return autoregressive_impl(c, text_ids, n_text, voice, B, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
+    return autoregressive_impl(c, text_ids, &n_text, 1, voice, &B, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
+  });
+}
+
+int tts_autoregressive_multi(tts_ctx *c, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voice, const int32_t *n_cand, int max_steps,
+                             unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
+  NEED_CTX(c);
+  if (n_prompts < 1 || !n_text || !n_cand) return fail(c, TTS_ERR_ARG, "tts_autoregressive_multi: bad argument");
+  return guarded(c, [&] {
+    return autoregressive_impl(c, text_ids, n_text, n_prompts, voice, n_cand, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
+  });
+}
+
+int tts_ar_begin_multi(tts_ctx *c, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voice, const int32_t *n_cand, int max_steps) {
+  NEED_CTX(c);
+  if (n_prompts < 1 || !n_text || !n_cand) return fail(c, TTS_ERR_ARG, "tts_ar_begin_multi: bad argument");
+  return guarded(c, [&] { return ar_begin_groups(c, text_ids, n_text, n_prompts, voice, n_cand, max_steps); });
+}
+
+int tts_split_text(tts_ctx *c, const char *message, int max_ids, int32_t *starts_out, int32_t *lens_out, int cap) {
+  if (!c) return TTS_ERR_ARG;
+  if (!c->tok) return fail(c, TTS_ERR_STATE, "tokenizer not loaded");
+  if (!message || max_ids < 3 || max_ids > 404 || cap < 0 || (cap > 0 && (!starts_out || !lens_out)))
+    return fail(c, TTS_ERR_ARG, "tts_split_text: bad argument (max_ids %d: 3 .. 404)", max_ids);
+  return guarded(c, [&] {
+    const std::vector<std::pair<int, int>> ch = split_text(*c->tok, message, max_ids);
+    for (int k = 0; k < (int)ch.size() && k < cap; k++) { starts_out[k] = ch[k].first; lens_out[k] = ch[k].second; }
+    return (int)ch.size();
   });
 }
 

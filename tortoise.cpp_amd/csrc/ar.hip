@@ -577,6 +577,7 @@ struct DecLnArgs {
   const StepState *ss;
   int max_pos, lut;
   const float *wscale;       // SPLIT 3: per-output-column scale (a power of two) of the fp8 weights
+  const int *row_off = nullptr; // RO (multi-prompt decode): per-row context offset added to the step's n_past (ArState::row_off)
 };
 
 // sum over the four 16-lane rows of a wave (lanes l, l^16, l^32, l^48): gfx950 half/row swap instructions
@@ -628,7 +629,9 @@ __device__ __forceinline__ void dec_layernorm(float4 (&x)[16], const float *__re
 // half the bytes streamed; the activations keep their hi + lo split) — the throughput mode of SURVEY 8d, option "ar_weights";
 // 3 = OCP fp8 (e4m3) WEIGHTS with a power-of-two scale per output column (a quarter of the bytes): converted to fp16 in
 // registers (exact: every e4m3 value is an fp16 value), multiplied on the fp16 MFMA against the hi + lo split activations.
-template <int EPI, int SPLIT = 0, bool NTW = false, bool HT = false> // HT: a.h is in the h4 layout (decode step); otherwise [row][1024] (prompt pass)
+// RO (DEC_QKV decode only): the K/V store position of row r is n_past + a.row_off[r] — a batch of several prompts (tts_ar_begin_multi); false = the
+// single-prompt kernel unchanged.
+template <int EPI, int SPLIT = 0, bool NTW = false, bool HT = false, bool RO = false> // HT: a.h is in the h4 layout (decode step); otherwise [row][1024] (prompt pass)
 __global__ __launch_bounds__(256) void dec_ln_gemv_kernel(DecLnArgs a_in) {
   constexpr int SP = SPLIT ? 1 : 0;
   constexpr int TSLOT = EPI == DEC_QKV ? 0 : EPI == DEC_GELU ? 3 : 5; (void)TSLOT;
@@ -647,6 +650,7 @@ __global__ __launch_bounds__(256) void dec_ln_gemv_kernel(DecLnArgs a_in) {
   //  become generic pointers and every load a flat_load, which also counts on lgkmcnt)
   asm volatile("" ::"s"(a.h), "s"(a.g1), "s"(a.b1), "s"(a.W), "s"(a.Wh), "s"(a.bias), "s"(a.out), "s"(a.kc), "s"(a.vc), "s"(a.ss), "s"(a.wscale));
   asm volatile("" ::"s"(a.rows), "s"(a.n_valid), "s"(a.ldo), "s"(a.prefill_B), "s"(a.max_pos), "s"(a.lut));
+  if (RO) asm volatile("" ::"s"(a.row_off));
   // Everything the epilogue reads (bias, the step's n_past) is requested FIRST: loaded after the reduction they were one or two
   // dependent L2 round trips (~0.5 us each) at the end of every launch. n_past goes through the VECTOR memory path (a zero offset the
   // compiler cannot see through): as a scalar load it is a dependent round trip that every later s_waitcnt lgkmcnt(0) waits for; as the
@@ -661,6 +665,9 @@ __global__ __launch_bounds__(256) void dec_ln_gemv_kernel(DecLnArgs a_in) {
     const int *np_ptr = a.prefill_B == 0 ? &a.ss->n_past : (const int *)a.bias; // the prompt pass has no step state (ss may be null): read a valid dummy, drop it
     n_past = *(const int *)((const char *)np_ptr + zero);
     n_past = a.prefill_B == 0 ? n_past : 0;
+    // the row's own context offset: a vector load issued beside n_past's (same queue position, no extra round trip). The array is padded to whole
+    // tiles of 16 rows (zeros), so the rows of the last tile past the batch read inside it; their results are never stored.
+    if (RO) n_past += a.row_off[row];
   }
   // activations next (L2 hits), then the weight slab (HBM): vmcnt retires in order, so the LayerNorm runs on
   // the activations while the 16 x 1 KB-per-wave weight loads are still streaming in
@@ -1001,9 +1008,11 @@ __device__ __forceinline__ void attn_decode_chunk(const __half *__restrict__ kb,
 // Decode attention for one (candidate, head), the default (non-LUT) path: softmax(q.K/8) V over n_past+1 keys with the
 // hardware exp2 (relative error ~1e-6 on a weight). Up to 288 keys go through one chunk = one memory round trip
 // (attn_decode_chunk); the four waves keep separate online-softmax states that are merged once at the end.
+// RO: row c sees ss->n_past + row_off[c] + 1 keys (a batch of several prompts, tts_ar_begin_multi); false: row_off is not read.
+template <bool RO = false>
 __global__ __launch_bounds__(256) void attn_decode_fast_kernel(const float *__restrict__ qbuf, const __half *__restrict__ kc,
                                                                const __half *__restrict__ vc, const StepState *__restrict__ ss,
-                                                               int max_pos, float *__restrict__ out) {
+                                                               int max_pos, float *__restrict__ out, const int *__restrict__ row_off) {
   constexpr float L2E = 1.4426950408889634f;
   constexpr int TSLOT = 1; (void)TSLOT;
   __shared__ float red[4][HD];
@@ -1014,7 +1023,8 @@ __global__ __launch_bounds__(256) void attn_decode_fast_kernel(const float *__re
   // all arguments in one batch of scalar loads (see dec_ln_gemv_kernel) and the one dependent fetch this kernel cannot avoid: n_past.
   // (the load of n_past stays IN FRONT of the asm: behind a volatile asm hipcc no longer proves the memory unclobbered and fetches it through
   //  the vector path, which makes the loop bounds divergent)
-  const int nk = ss->n_past + 1;
+  // (RO: the row's offset is a second scalar load from a kernel argument, issued beside n_past's: the same single round trip)
+  const int nk = ss->n_past + 1 + (RO ? row_off[c] : 0);
   asm volatile("" ::"s"(qbuf), "s"(kc), "s"(vc), "s"(max_pos), "s"(out)); // input-only: the pointers keep their address space
   const __half *kb = kc + (size_t)c * max_pos * D + h * HD;
   const __half *vb = vc + (size_t)c * max_pos * D + h * HD;
@@ -1070,15 +1080,16 @@ __global__ __launch_bounds__(256) void attn_decode_fast_kernel(const float *__re
 // Decode attention for one (candidate, head): q is this step's (fp16-rounded) query, K/V of the new position
 // are already in the fp16 cache; softmax(q.K/8) V over n_past+1 keys. 4 waves: keys are spread over all 256
 // threads for the scores and over 16 groups for PV.
+template <bool RO = false> // as attn_decode_fast_kernel
 __global__ __launch_bounds__(256) void attn_decode_kernel(const float *__restrict__ qbuf, const __half *__restrict__ kc,
                                                           const __half *__restrict__ vc, const StepState *__restrict__ ss,
-                                                          int max_pos, float *__restrict__ out, int lut) {
+                                                          int max_pos, float *__restrict__ out, int lut, const int *__restrict__ row_off) {
   __shared__ float sc[1024];
   __shared__ float qs[HD];
   __shared__ float red[16 * HD];
   __shared__ float wred[8];
   const int c = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nk = ss->n_past + 1;
+  const int nk = ss->n_past + 1 + (RO ? row_off[c] : 0);
   const __half *kb = kc + (size_t)c * max_pos * D + h * HD;
   const __half *vb = vc + (size_t)c * max_pos * D + h * HD;
   if (tid < HD) qs[tid] = qbuf[(size_t)c * D + h * HD + tid];
@@ -1262,9 +1273,14 @@ struct ArState {
   bool f32_mfma = false;   // option "dec_f32_mfma" at load: LayerNorm-GEMVs on v_mfma_f32_16x16x4_f32 (exact f32 products) instead of split fp16
   std::vector<void *> owned;
   // run state
-  int B = 0, n_text = 0, P = 0, max_pos = 0;
+  int B = 0, n_text = 0, P = 0, max_pos = 0; // several prompts (tts_ar_begin_multi): n_text / P of the LONGEST prompt
   bool prefill_done = false; // the prompt's K/V rows are in the decode cache (set by ar_prefill, cleared by ar_begin)
-  std::vector<int> tokens;
+  std::vector<int> tokens;   // the prompts back to back
+  // Prompt groups: group g holds candidates [g_c0[g], g_c0[g] + g_n[g]) and the prompt tokens[g_t0[g] .. + g_ntext[g]). One group = the single-prompt
+  // path of rounds 1-6 (multi = false); several: the decode step reads every row's context length from row_off (multi = true).
+  std::vector<int> g_c0, g_n, g_t0, g_ntext;
+  bool multi = false;
+  DevBuf row_off;            // multi: [tiles * 16] ints, P of the row's group (0 past the batch); the step state's n_past is then the step index
   DevBuf voice, kcache, vcache, lat_k, lat_v;
   DevBuf h, xn, qkv, att, ff, part, desc, logits, hn, a_hi, a_lo;
   // decode-step graph
@@ -1280,17 +1296,17 @@ struct ArState {
   hipGraphExec_t graph_execs[3] = {};
   // everything the captured step bakes into its nodes: the graph of the previous utterance is replayed when nothing moved
   struct GraphSig {
-    int B = 0, max_pos = 0, lut = 0, wmode = 0, mode = 0;
-    const void *p[11] = {};
+    int B = 0, max_pos = 0, lut = 0, wmode = 0, mode = 0, multi = 0;
+    const void *p[12] = {};
     bool operator==(const GraphSig &o) const {
-      return B == o.B && max_pos == o.max_pos && lut == o.lut && wmode == o.wmode && mode == o.mode && std::equal(p, p + 11, o.p);
+      return B == o.B && max_pos == o.max_pos && lut == o.lut && wmode == o.wmode && mode == o.mode && multi == o.multi && std::equal(p, p + 12, o.p);
     }
   } graph_sigs[3];
   GraphSig current_sig(int lut, int wmode) const {
     GraphSig g;
-    g.B = B; g.max_pos = max_pos; g.lut = lut; g.wmode = wmode; g.mode = step_mode;
-    const void *q[11] = {h.p, qkv.p, att.p, ff.p, kcache.p, vcache.p, d_toks.p, logits.p, h_toks, h_logits, h_pf};
-    std::copy(q, q + 11, g.p);
+    g.B = B; g.max_pos = max_pos; g.lut = lut; g.wmode = wmode; g.mode = step_mode; g.multi = multi;
+    const void *q[12] = {h.p, qkv.p, att.p, ff.p, kcache.p, vcache.p, d_toks.p, logits.p, h_toks, h_logits, h_pf, multi ? row_off.p : nullptr};
+    std::copy(q, q + 12, g.p);
     return g;
   }
   void drop_graph(int m) {
@@ -1952,19 +1968,33 @@ static int embed(tts_ctx *ctx, ArState *st, const std::vector<int4> &desc) {
   return TTS_OK;
 }
 
-int ar_begin(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice, int B, int max_steps) {
+// tts_ar_begin (one prompt, G = 1) and tts_ar_begin_multi (G prompts back to back in text_ids, group g with n_text[g] ids and n_cand[g] candidates).
+// Every argument is checked before anything changes.
+int ar_begin_groups(tts_ctx *ctx, const int32_t *text_ids, const int *n_text, int G, const float *voice, const int *n_cand, int max_steps) {
   ArState *st = ctx->ar;
   if (!st) return fail(ctx, TTS_ERR_STATE, "AR model not loaded");
-  if (n_text < 1 || B < 1 || max_steps < 1 || !text_ids || !voice) return fail(ctx, TTS_ERR_ARG, "tts_ar_begin: bad argument");
-  if (n_text > 404) return fail(ctx, TTS_ERR_LIMIT, "text has %d ids; the model has 404 text positions", n_text);
+  if (G < 1 || !n_text || !n_cand || max_steps < 1 || !text_ids || !voice) return fail(ctx, TTS_ERR_ARG, "tts_ar_begin: bad argument");
+  int B = 0, P_max = 0, T = 0;
+  for (int g = 0; g < G; g++) {
+    if (n_text[g] < 1 || n_cand[g] < 1) return fail(ctx, TTS_ERR_ARG, "tts_ar_begin: bad argument (prompt %d: %d ids, %d candidates)", g, n_text[g], n_cand[g]);
+    if (n_text[g] > 404) return fail(ctx, TTS_ERR_LIMIT, "text has %d ids; the model has 404 text positions", n_text[g]);
+    if (n_cand[g] > (1 << 24) - B) return fail(ctx, TTS_ERR_LIMIT, "more than 2^24 candidates");
+    B += n_cand[g]; T += n_text[g];
+    P_max = std::max(P_max, n_text[g] + 2);
+  }
   if (max_steps + 2 > 608) return fail(ctx, TTS_ERR_LIMIT, "max_steps %d exceeds the 608 mel positions", max_steps);
-  for (int i = 0; i < n_text; i++)
+  for (int i = 0; i < T; i++)
     if (text_ids[i] < 0 || text_ids[i] >= 256) return fail(ctx, TTS_ERR_ARG, "text id %d out of range", text_ids[i]);
-  st->B = B; st->n_text = n_text; st->P = n_text + 2;
+  const int max_pos = P_max + max_steps + 1;
+  if (max_pos > 1024) return fail(ctx, TTS_ERR_LIMIT, "context of %d positions exceeds 1024", max_pos);
+  st->B = 0; // (a failure below leaves no half-begun state behind)
+  st->g_c0.assign(G, 0); st->g_n.assign(n_cand, n_cand + G); st->g_t0.assign(G, 0); st->g_ntext.assign(n_text, n_text + G);
+  for (int g = 1; g < G; g++) { st->g_c0[g] = st->g_c0[g - 1] + n_cand[g - 1]; st->g_t0[g] = st->g_t0[g - 1] + n_text[g - 1]; }
+  st->multi = G > 1;
+  st->n_text = P_max - 2; st->P = P_max;
   st->prefill_done = false;
-  st->max_pos = st->P + max_steps + 1;
-  if (st->max_pos > 1024) return fail(ctx, TTS_ERR_LIMIT, "context of %d positions exceeds 1024", st->max_pos);
-  st->tokens.assign(text_ids, text_ids + n_text);
+  st->max_pos = max_pos;
+  st->tokens.assign(text_ids, text_ids + T);
   TTS_HIP(ctx, st->voice.reserve(D * 4));
   TTS_HIP(ctx, hipMemcpy(st->voice.p, voice, D * 4, hipMemcpyHostToDevice));
   size_t cache = (size_t)st->n_layers * B * st->max_pos * D * sizeof(__half);
@@ -1972,6 +2002,13 @@ int ar_begin(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voi
   TTS_HIP(ctx, st->vcache.reserve(cache));
   TTS_HIP(ctx, st->d_toks.reserve((size_t)(B + 2) * 4)); // [tokens | n_past, pos_id]
   TTS_HIP(ctx, st->logits.reserve((size_t)B * V * 4));
+  if (st->multi) { // every row's context offset, once per begin (outside the graph: the step state's n_past becomes the step index)
+    std::vector<int> off((size_t)(B + 15) / 16 * 16, 0);
+    for (int g = 0; g < G; g++)
+      for (int c = 0; c < n_cand[g]; c++) off[(size_t)st->g_c0[g] + c] = n_text[g] + 2;
+    TTS_HIP(ctx, st->row_off.reserve(off.size() * sizeof(int)));
+    TTS_HIP(ctx, hipMemcpy(st->row_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
   if (B > st->h_cap_B) { // pinned allocations are slow (milliseconds): keep them across utterances
     if (st->h_toks) (void)hipHostFree(st->h_toks);
     if (st->h_logits) (void)hipHostFree(st->h_logits);
@@ -1986,30 +2023,35 @@ int ar_begin(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voi
   // the decode step's h4 layout holds whole tiles of 16 candidates: the padding rows of the last tile are read (never stored), keep them finite
   CHECK(reserve_rows(ctx, st, std::max((B + 15) / 16 * 16, st->P)));
   TTS_HIP(ctx, hipMemsetAsync(st->h.p, 0, st->h.cap, ctx->stream));
+  st->B = B;
   return TTS_OK;
+}
+
+int ar_begin(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice, int B, int max_steps) {
+  return ar_begin_groups(ctx, text_ids, &n_text, 1, voice, &B, max_steps);
 }
 
 // Prefill (main.cpp:2586-2665): [voice | text_emb+pos | mel_emb(8192)+mel_pos(0)] — identical for all
 // candidates, so it is evaluated once and its K/V rows are written into every candidate's cache.
-int ar_prefill(tts_ctx *ctx, float *logits_out) {
-  ArState *st = ctx->ar;
-  if (!st || st->B == 0) return fail(ctx, TTS_ERR_STATE, "tts_ar_begin not called");
-  const int P = st->P;
+// Several prompts (tts_ar_begin_multi): one such pass per group, its K/V rows written into the caches of the group's candidates only.
+static int prefill_group(tts_ctx *ctx, ArState *st, int g) {
+  const int n_text = st->g_ntext[g], P = n_text + 2, c0 = st->g_c0[g];
+  const int *tok = st->tokens.data() + st->g_t0[g];
   std::vector<int4> desc(P);
   desc[0] = make_int4(0, 0, -1, 0);
-  for (int i = 0; i < st->n_text; i++) desc[1 + i] = make_int4(1, st->tokens[i], 0, i);
+  for (int i = 0; i < n_text; i++) desc[1 + i] = make_int4(1, tok[i], 0, i);
   desc[P - 1] = make_int4(2, 8192, 1, 0);
   CHECK(embed(ctx, st, desc));
-  const size_t layer_stride = (size_t)st->B * st->max_pos * D;
+  const size_t layer_stride = (size_t)st->B * st->max_pos * D, cand0 = (size_t)c0 * st->max_pos * D;
   // The prompt pass runs on the decode-step kernels, tiled over 16 positions (exact f32, weights re-read from L2 per
   // tile): rows are positions of the one shared prompt, the QKV epilogue replicates K/V into every candidate's cache.
   const int tiles = (P + 15) / 16;
   float *h = st->h.as<float>(), *qkv = st->qkv.as<float>(), *att = st->att.as<float>(), *ff = st->ff.as<float>();
   for (int l = 0; l < st->n_layers; l++) {
     const ArLayerDev &w = st->L[l];
-    __half *kc = st->kcache.as<__half>() + l * layer_stride, *vc = st->vcache.as<__half>() + l * layer_stride;
+    __half *kc = st->kcache.as<__half>() + l * layer_stride + cand0, *vc = st->vcache.as<__half>() + l * layer_stride + cand0;
     { ProfScope ps(ctx, "ar_gemv", 3.0 * D * D * 4.0 * tiles);
-      DecLnArgs a{h, nullptr, nullptr, w.d_attn, w.dh_attn, w.db_attn, P, 3 * D, 3 * D, st->B, qkv, kc, vc, nullptr, st->max_pos, ctx->ggml_lut};
+      DecLnArgs a{h, nullptr, nullptr, w.d_attn, w.dh_attn, w.db_attn, P, 3 * D, 3 * D, st->g_n[g], qkv, kc, vc, nullptr, st->max_pos, ctx->ggml_lut};
       DEC_LN_LAUNCH(DEC_QKV, dim3(3 * D / 16, tiles), false); }
     { ProfScope ps(ctx, "ar_attention");
       attention_kernel<<<dim3(P, NH), 64, 0, ctx->stream>>>(qkv, kc, vc, att, P, 0, st->max_pos, ctx->ggml_lut); }
@@ -2021,21 +2063,42 @@ int ar_prefill(tts_ctx *ctx, float *logits_out) {
     { ProfScope ps(ctx, "ar_gemv", 4.0 * D * D * 4.0 * tiles);
       dec_gemv_resid_kernel<4, 512><<<dim3(D / 4, tiles), 512, 0, ctx->stream>>>(ff, P, w.d_fc2, w.b_fc2, h); }
   }
-  TTS_HIP(ctx, st->logits.reserve((size_t)V * 4));
+  // the group's logits go to the row of its first candidate
   { ProfScope ps(ctx, "ar_gemv", (double)D * VPAD * 4.0);
-    DecLnArgs a{h + (size_t)(P - 1) * D, st->lnf_g, st->lnf_b, st->d_lm, st->dh_lm, st->d_lmb, 1, V, V, 0, st->logits.as<float>(),
+    DecLnArgs a{h + (size_t)(P - 1) * D, st->lnf_g, st->lnf_b, st->d_lm, st->dh_lm, st->d_lmb, 1, V, V, 0, st->logits.as<float>() + (size_t)c0 * V,
                 nullptr, nullptr, nullptr, 0, ctx->ggml_lut};
     DEC_LN_LAUNCH(DEC_LOGITS, dim3(VPAD / 16, 1), false); }
   TTS_HIP(ctx, hipGetLastError());
+  return TTS_OK;
+}
+
+int ar_prefill(tts_ctx *ctx, float *logits_out) {
+  ArState *st = ctx->ar;
+  if (!st || st->B == 0) return fail(ctx, TTS_ERR_STATE, "tts_ar_begin not called");
+  TTS_HIP(ctx, st->logits.reserve((size_t)st->B * V * 4));
+  const int G = (int)st->g_n.size();
+  for (int g = 0; g < G; g++) CHECK(prefill_group(ctx, st, g));
   if (logits_out) {
-    TTS_HIP(ctx, hipMemcpyAsync(logits_out, st->logits.p, (size_t)V * 4, hipMemcpyDeviceToHost, ctx->stream));
+    for (int g = 0; g < G; g++)
+      TTS_HIP(ctx, hipMemcpyAsync(logits_out + (size_t)st->g_c0[g] * V, st->logits.as<float>() + (size_t)st->g_c0[g] * V, (size_t)V * 4, hipMemcpyDeviceToHost,
+                                  ctx->stream));
     TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int c = 1; c < st->B; c++) memcpy(logits_out + (size_t)c * V, logits_out, (size_t)V * 4);
+    for (int g = 0; g < G; g++)
+      for (int c = 1; c < st->g_n[g]; c++) memcpy(logits_out + (size_t)(st->g_c0[g] + c) * V, logits_out + (size_t)st->g_c0[g] * V, (size_t)V * 4);
   } else {
     TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   st->prefill_done = true;
   return TTS_OK;
+}
+
+// The decode step's LN1 + QKV launch. RO: several prompts, every row stores its K/V at its own position (a.row_off).
+template <bool RO>
+static void launch_dec_qkv(tts_ctx *ctx, const ArState *st, int wm, dim3 grid, const DecLnArgs &a) {
+  if (wm == 2) dec_ln_gemv_kernel<DEC_QKV, 3, true, true, RO><<<grid, 256, 0, ctx->stream>>>(a);
+  else if (wm == 1) dec_ln_gemv_kernel<DEC_QKV, 2, false, true, RO><<<grid, 256, 0, ctx->stream>>>(a);
+  else if (st->f32_mfma) dec_ln_gemv_kernel<DEC_QKV, 0, false, true, RO><<<grid, 256, 0, ctx->stream>>>(a);
+  else dec_ln_gemv_kernel<DEC_QKV, 1, true, true, RO><<<grid, 256, 0, ctx->stream>>>(a);
 }
 
 // One decode step for all candidates, enqueued on the ctx stream (captured once into a hipGraph): five
@@ -2048,19 +2111,24 @@ static int enqueue_decode_step(tts_ctx *ctx, ArState *st) {
   const size_t layer_stride = (size_t)B * st->max_pos * D;
   const int wm = ctx->ar_weights; // 1 / 2: fp16 / fp8 weights, a half / a quarter of the bytes per step (throughput modes, not f32-exact); checked by ar_step
   const double wb = wm == 2 ? 1.0 : wm == 1 ? 2.0 : 4.0;
+  const int *ro = st->multi ? st->row_off.as<int>() : nullptr; // several prompts: the rows' context offsets (n_past = step index + row_off[row])
   embed_step_kernel<<<B, 256, 0, ctx->stream>>>(st->mel_emb, st->mel_pos, st->h_toks, B, (StepState *)(st->d_toks.as<int>() + B), h);
   for (int l = 0; l < st->n_layers; l++) {
     const ArLayerDev &w = st->L[l];
     __half *kc = st->kcache.as<__half>() + l * layer_stride, *vc = st->vcache.as<__half>() + l * layer_stride;
     { ProfScope ps(ctx, "ar_gemv", 3.0 * D * D * wb * tiles);
       DecLnArgs a{h, nullptr, nullptr, w.d_attn, wm == 2 ? (const __half *)w.o_attn : wm == 1 ? w.q_attn : w.dh_attn, w.db_attn, B, 3 * D, D, 0, q, kc, vc, ss,
-                  st->max_pos, ctx->ggml_lut, w.os_attn};
-      if (wm == 2) dec_ln_gemv_kernel<DEC_QKV, 3, true, true><<<dim3(3 * D / 16, tiles), 256, 0, ctx->stream>>>(a);
-      else if (wm == 1) dec_ln_gemv_kernel<DEC_QKV, 2, false, true><<<dim3(3 * D / 16, tiles), 256, 0, ctx->stream>>>(a);
-      else DEC_LN_LAUNCH(DEC_QKV, dim3(3 * D / 16, tiles), true); }
+                  st->max_pos, ctx->ggml_lut, w.os_attn, ro};
+      if (st->multi) launch_dec_qkv<true>(ctx, st, wm, dim3(3 * D / 16, tiles), a);
+      else launch_dec_qkv<false>(ctx, st, wm, dim3(3 * D / 16, tiles), a); }
     { ProfScope ps(ctx, "ar_attention");
-      if (ctx->ggml_lut) attn_decode_kernel<<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, 1);
-      else attn_decode_fast_kernel<<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att); }
+      if (ctx->ggml_lut) {
+        if (st->multi) attn_decode_kernel<true><<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, 1, ro);
+        else attn_decode_kernel<false><<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, 1, nullptr);
+      } else {
+        if (st->multi) attn_decode_fast_kernel<true><<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, ro);
+        else attn_decode_fast_kernel<false><<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, nullptr);
+      } }
     { ProfScope ps(ctx, "ar_gemv", 1.0 * D * D * wb * tiles);
       if (wm == 2) dec_gemv_resid_kernel<1, 256, 2, false, true><<<dim3(D / 4, tiles), 256, 0, ctx->stream>>>(att, B, (const float *)w.o_proj, w.b_proj, h, w.os_proj);
       else if (wm == 1) dec_gemv_resid_kernel<1, 256, 1, false, true><<<dim3(D / 4, tiles), 256, 0, ctx->stream>>>(att, B, (const float *)w.q_proj, w.b_proj, h);
@@ -2101,12 +2169,12 @@ int ar_step(tts_ctx *ctx, const int32_t *prev_ids, int step_i, float *logits_out
   if (!st || st->B == 0) return fail(ctx, TTS_ERR_STATE, "tts_ar_begin not called");
   if (mode < 0 || mode > 2 || (mode && logits_out)) return fail(ctx, TTS_ERR_ARG, "ar_step: bad mode");
   st->step_mode = mode;
-  if (step_i < 0 || st->P + step_i >= st->max_pos) return fail(ctx, TTS_ERR_LIMIT, "step %d beyond the KV cache", step_i);
+  if (step_i < 0 || st->P + step_i >= st->max_pos) return fail(ctx, TTS_ERR_LIMIT, "step %d beyond the KV cache", step_i); // (P: the longest prompt's)
   for (int c = 0; c < st->B; c++) {
     if (prev_ids[c] < 0 || prev_ids[c] >= V) return fail(ctx, TTS_ERR_ARG, "mel token %d out of range", prev_ids[c]);
     st->h_toks[c] = prev_ids[c];
   }
-  st->h_toks[st->B] = st->P + step_i; // n_past
+  st->h_toks[st->B] = st->multi ? step_i : st->P + step_i; // n_past (several prompts: the kernels add the row's P, ArState::row_off)
   st->h_toks[st->B + 1] = step_i + 2; // mel position id (main.cpp:5244)
   // checked here, not inside enqueue_decode_step: that runs between hipStreamBeginCapture and hipStreamEndCapture
   if (ctx->ar_weights != 0 && ctx->ar_weights != st->loaded_wmode)
@@ -2171,25 +2239,28 @@ __global__ __launch_bounds__(256) void copy_prompt_kv_kernel(const __half *__res
 // Latent pass (main.cpp:2053-2519): the full stack over [voice | text | mel codes at mel positions 0..] without the
 // decode cache's position quirk. The 1 + n_text prompt rows are the same for every candidate and do not depend on the
 // mel rows (causal mask): their K/V rows are taken from the decode cache (written by the prompt pass), so the stack runs
-// over the mel rows only, with n_past = 1 + n_text.
-int ar_latents(tts_ctx *ctx, const int32_t *codes502, int nb, int n_mel, float *out) {
-  ArState *st = ctx->ar;
-  if (!st || st->n_text == 0) return fail(ctx, TTS_ERR_STATE, "tts_ar_begin not called");
-  if (nb < 1 || n_mel < 1 || n_mel > 502) return fail(ctx, TTS_ERR_ARG, "tts_ar_latents: bad argument");
-  const int Sp = 1 + st->n_text, S = Sp + n_mel, rows = nb * n_mel;
-  if (S > 1024) return fail(ctx, TTS_ERR_LIMIT, "latent pass of %d positions exceeds 1024", S);
+// over the mel rows only, with n_past = 1 + n_text. Several prompts: one such pass per group, over the group's own prompt (its first
+// candidate's cache rows) and n_mel.
+static int latents_check(tts_ctx *ctx, const ArState *st, int n_text, const int32_t *codes502, int nb, int n_mel) {
+  if (nb < 1 || n_mel < 1 || n_mel > 502 || !codes502) return fail(ctx, TTS_ERR_ARG, "tts_ar_latents: bad argument");
+  if (1 + n_text + n_mel > 1024) return fail(ctx, TTS_ERR_LIMIT, "latent pass of %d positions exceeds 1024", 1 + n_text + n_mel);
   for (int c = 0; c < nb; c++)
     for (int j = 0; j < n_mel; j++) {
       const int code = codes502[c * 502 + j];
       if (code < 0 || code >= V) return fail(ctx, TTS_ERR_ARG, "mel code %d out of range", code);
     }
-  if (!st->prefill_done) CHECK(ar_prefill(ctx, nullptr));
+  return TTS_OK;
+}
+
+static int latents_group(tts_ctx *ctx, ArState *st, int g, const int32_t *codes502, int nb, int n_mel, float *out) {
+  const int Sp = 1 + st->g_ntext[g], S = Sp + n_mel, rows = nb * n_mel;
   CHECK(reserve_rows(ctx, st, rows));
   const size_t lat_stride = (size_t)nb * S * D; // per layer: [cand][S][1024]
   TTS_HIP(ctx, st->lat_k.reserve(st->n_layers * lat_stride * sizeof(__half)));
   TTS_HIP(ctx, st->lat_v.reserve(st->n_layers * lat_stride * sizeof(__half)));
+  const size_t src0 = (size_t)st->g_c0[g] * st->max_pos * D; // the group's first candidate holds its prompt rows
   copy_prompt_kv_kernel<<<dim3(Sp, nb, 2 * st->n_layers), 256, 0, ctx->stream>>>(
-      st->kcache.as<__half>(), st->vcache.as<__half>(), (size_t)st->B * st->max_pos * D, st->lat_k.as<__half>(), st->lat_v.as<__half>(),
+      st->kcache.as<__half>() + src0, st->vcache.as<__half>() + src0, (size_t)st->B * st->max_pos * D, st->lat_k.as<__half>(), st->lat_v.as<__half>(),
       lat_stride, S, st->n_layers);
   std::vector<int4> desc(rows);
   for (int c = 0; c < nb; c++)
@@ -2206,6 +2277,29 @@ int ar_latents(tts_ctx *ctx, const int32_t *codes502, int nb, int n_mel, float *
                                 ctx->stream));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return TTS_OK;
+}
+
+// tts_ar_latents. Several prompts: nb must be the whole batch, every candidate is evaluated against its own prompt (out [B][min(500, n_mel)][1024]).
+int ar_latents(tts_ctx *ctx, const int32_t *codes502, int nb, int n_mel, float *out) {
+  ArState *st = ctx->ar;
+  if (!st || st->B == 0) return fail(ctx, TTS_ERR_STATE, "tts_ar_begin not called");
+  if (st->multi && nb != st->B) return fail(ctx, TTS_ERR_ARG, "tts_ar_latents: %d candidates, the batch of several prompts has %d", nb, st->B);
+  CHECK(latents_check(ctx, st, st->n_text, codes502, nb, n_mel));
+  if (!st->prefill_done) CHECK(ar_prefill(ctx, nullptr));
+  if (!st->multi) return latents_group(ctx, st, 0, codes502, nb, n_mel, out);
+  const size_t n_out = std::min(500, n_mel);
+  for (int g = 0; g < (int)st->g_n.size(); g++)
+    CHECK(latents_group(ctx, st, g, codes502 + (size_t)st->g_c0[g] * 502, st->g_n[g], n_mel, out + (size_t)st->g_c0[g] * n_out * D));
+  return TTS_OK;
+}
+
+// The latent pass of group g alone (the driver's per-group n_mel): codes502 / out hold the group's candidates only.
+int ar_latents_group(tts_ctx *ctx, int g, const int32_t *codes502, int n_mel, float *out) {
+  ArState *st = ctx->ar;
+  if (!st || st->B == 0 || g < 0 || g >= (int)st->g_n.size()) return fail(ctx, TTS_ERR_STATE, "tts_ar_begin not called");
+  CHECK(latents_check(ctx, st, st->g_ntext[g], codes502, st->g_n[g], n_mel));
+  if (!st->prefill_done) CHECK(ar_prefill(ctx, nullptr));
+  return latents_group(ctx, st, g, codes502, st->g_n[g], n_mel, out);
 }
 
 int ar_layers(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->n_layers : 0; }

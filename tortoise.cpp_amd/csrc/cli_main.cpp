@@ -24,6 +24,10 @@
 //   files (<output> for candidate 0, <output>.<c>.wav for the others, c = global candidate index).
 //   --exchange rccl: the workers form one RCCL communicator (cli_rccl.h; distinct GPUs per worker): rank 0 broadcasts the conditioning
 //   (text ids + voice latent), the result sizes / CLVP scores are all-gathered, the audio is sent to rank 0, which writes every WAV file.
+// --split-text <N> (0 = off, the default): a message longer than one prompt. It is split into chunks of at most N text ids (tts_split_text: whole sentences
+//   packed greedily, include/tortoise_mi355x.h states the rule); all chunks run through ONE tts_autoregressive_multi call (--candidates per chunk), each
+//   chunk keeps candidate 0 (or the CLVP best with --clvp), one tts_diffusion and one tts_vocoder call run over the kept candidates, and their audio is
+//   written to --output one after the other as ONE file. A message that fits one chunk takes the path without the flag. Not with --devices > 1.
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -52,7 +56,7 @@ int main(int argc, char **argv) {
   std::string outputPath = "./output.wav";
   std::string modelsDir = "../models";
   bool have_seed = false;
-  int seed = 0, candidates = 1, steps = 80, device = 0, fixed_codes = 0, devices = 1, shard = -1, nshards = 1;
+  int seed = 0, candidates = 1, steps = 80, device = 0, fixed_codes = 0, devices = 1, shard = -1, nshards = 1, split_ids = 0;
   std::string device_map, clvpPath, exchange = "files", rccl_id, diffLatentPath;
   bool dry = false, allow_shared = false;
   bool timing = false;
@@ -85,6 +89,7 @@ int main(int argc, char **argv) {
       engine_options.emplace_back(kv.substr(0, eq), std::atof(kv.c_str() + eq + 1));
     }
     else if (a == "--diffusion-latent") diffLatentPath = argv[i + 1];
+    else if (a == "--split-text") split_ids = std::stoi(argv[i + 1]);
     else if (a == "--rccl-id") rccl_id = argv[i + 1]; // worker mode (set by the parent)
     else if (a == "--shard") { // worker mode (set by the parent): "r/N"
       std::string v(argv[i + 1]);
@@ -93,6 +98,11 @@ int main(int argc, char **argv) {
     }
   }
   if (exchange != "files" && exchange != "rccl") { fprintf(stderr, "--exchange %s: files or rccl\n", exchange.c_str()); return 1; }
+  if (split_ids != 0 && (devices > 1 || exchange == "rccl" || shard >= 0)) {
+    fprintf(stderr, "--split-text cannot be combined with --devices > 1 or --exchange rccl (one process runs all chunks)\n");
+    return 1;
+  }
+  if (split_ids < 0 || split_ids > 404) { fprintf(stderr, "--split-text %d: 0 (off) or 3 .. 404 text ids per chunk\n", split_ids); return 1; }
   if ((devices > 1 || exchange == "rccl") && shard < 0) { // parent: one worker process per GPU
     if (candidates % devices) { fprintf(stderr, "--candidates %d does not divide over --devices %d\n", candidates, devices); return 1; }
     std::vector<int> map;
@@ -222,6 +232,21 @@ int main(int argc, char **argv) {
   int n = tts_tokenize(ctx, message.c_str(), tokens.data(), (int)tokens.size());
   if (n < 0) return die(ctx, "tokenize");
   tokens.resize(n);
+  // --split-text: the chunks' text ids (a message that fits one chunk keeps the path without the flag)
+  std::vector<std::vector<int32_t>> chunk_tokens;
+  if (split_ids > 0) {
+    std::vector<int32_t> starts(message.size() + 1), lens(message.size() + 1);
+    const int k = tts_split_text(ctx, message.c_str(), split_ids, starts.data(), lens.data(), (int)starts.size());
+    if (k < 0) return die(ctx, "split-text");
+    for (int c = 0; k > 1 && c < k; c++) {
+      std::vector<int32_t> t(4096);
+      const int m = tts_tokenize(ctx, message.substr(starts[c], lens[c]).c_str(), t.data(), (int)t.size());
+      if (m < 0) return die(ctx, "tokenize");
+      t.resize(m);
+      chunk_tokens.push_back(t);
+    }
+  }
+  const int n_chunks = (int)chunk_tokens.size(); // 0: one prompt
 
   std::vector<float> voice(1024);
   {
@@ -294,49 +319,87 @@ int main(int argc, char **argv) {
   });
   if (tts_load_ar(ctx, (modelsDir + "/ggml-model.bin").c_str())) return die(ctx, "autoregressive_model_load");
   mark("load autoregressive");
-  std::vector<int32_t> codes((size_t)B_ar * 502), rows(B_ar);
-  std::vector<float> latents((size_t)B_ar * 500 * 1024);
-  int32_t nsteps = 0;
-  // More than one candidate (in this process or across --devices shards): the throughput stop rule. The reference's "all B samples of ONE
-  // step are 8193" practically never fires for B > 1 (and would need a per-step exchange between shards); every sequence is the same.
-  const unsigned ar_flags = (fixed_codes > 0 ? TTS_AR_MASK_STOP : 0) | (total_candidates > 1 ? TTS_AR_RETIRE : 0);
-  if (tts_autoregressive(ctx, tokens.data(), n, voice.data(), B_ar, fixed_codes > 0 ? fixed_codes : 500, ar_flags,
-                         codes.data(), rows.data(), latents.data(), &nsteps))
-    return die(ctx, "autoregressive");
-  mark("autoregressive");
-  printf("tokens sampled: %d\n", nsteps);
-  if (fixed_codes <= 0) {
-    std::vector<int32_t> stopped(B_ar);
-    if (tts_ar_stop_status(ctx, stopped.data(), B_ar) == 0)
-      for (int c = 0; c < B_ar; c++)
-        if (!stopped[c]) fprintf(stderr, "warning: candidate %d sampled no stop token within 500 codes (sequence cut)\n", (shard >= 0 ? shard * B_ar : 0) + c);
-  }
-
-  // CLVP re-ranking (extension): keep the candidate whose codes (the rows the diffusion stage would consume) score best against the text
-  B = B_ar;
+  const int B_all = B_ar * std::max(1, n_chunks); // --split-text: candidates of all chunks
+  std::vector<int32_t> codes((size_t)B_all * 502), rows(B_all);
+  std::vector<float> latents((size_t)B_all * 500 * 1024);
   const float *lat_in = latents.data();
-  if (!clvpPath.empty()) {
-    if (tts_load_clvp(ctx, clvpPath.c_str())) return die(ctx, "clvp_model_load");
-    std::vector<float> scores(B_ar);
-    if (tts_clvp_score(ctx, tokens.data(), n, codes.data() + 1, rows.data(), B_ar, 502, scores.data())) return die(ctx, "clvp");
-    int best = 0;
-    for (int c = 1; c < B_ar; c++)
-      if (scores[c] > scores[best]) best = c;
-    printf("clvp scores:");
-    for (int c = 0; c < B_ar; c++) printf(" %.5f", scores[c]);
-    printf("\n");
-    size_t off_rows = 0;
-    for (int c = 0; c < best; c++) off_rows += (size_t)rows[c];
-    lat_in = latents.data() + off_rows * 1024;
-    rows[0] = rows[best];
-    B = 1;
-    kept_gc = (shard >= 0 ? shard * B_ar : 0) + best;
-    kept_score = scores[best];
-    if (total_candidates > 1) { // device noise stays keyed by the kept candidate's global id
-      tts_set_option(ctx, "rng_shard_offset", (double)kept_gc);
-      tts_set_option(ctx, "rng_shard_total", (double)total_candidates);
+  if (n_chunks > 1) {
+    // all chunks in one autoregressive pass (chunk c: candidates [c B_ar, (c + 1) B_ar)), then candidate 0 or the CLVP best of every chunk
+    std::vector<int32_t> ids, n_text(n_chunks), n_cand(n_chunks, B_ar);
+    for (int c = 0; c < n_chunks; c++) { ids.insert(ids.end(), chunk_tokens[c].begin(), chunk_tokens[c].end()); n_text[c] = (int)chunk_tokens[c].size(); }
+    int32_t nsteps = 0;
+    const unsigned ar_flags = (fixed_codes > 0 ? TTS_AR_MASK_STOP : 0) | (B_ar > 1 ? TTS_AR_RETIRE : 0);
+    if (tts_autoregressive_multi(ctx, ids.data(), n_text.data(), n_chunks, voice.data(), n_cand.data(), fixed_codes > 0 ? fixed_codes : 500, ar_flags,
+                                 codes.data(), rows.data(), latents.data(), &nsteps))
+      return die(ctx, "autoregressive");
+    mark("autoregressive");
+    printf("tokens sampled: %d (%d chunks)\n", nsteps, n_chunks);
+    if (!clvpPath.empty() && tts_load_clvp(ctx, clvpPath.c_str())) return die(ctx, "clvp_model_load");
+    std::vector<size_t> lat_off(B_all + 1, 0);
+    for (int b = 0; b < B_all; b++) lat_off[b + 1] = lat_off[b] + (size_t)rows[b];
+    std::vector<float> kept;
+    std::vector<int32_t> kept_rows(n_chunks);
+    for (int c = 0; c < n_chunks; c++) {
+      int best = 0;
+      if (!clvpPath.empty()) {
+        std::vector<float> scores(B_ar);
+        if (tts_clvp_score(ctx, chunk_tokens[c].data(), n_text[c], codes.data() + (size_t)c * B_ar * 502 + 1, rows.data() + (size_t)c * B_ar, B_ar, 502,
+                           scores.data()))
+          return die(ctx, "clvp");
+        for (int k = 1; k < B_ar; k++)
+          if (scores[k] > scores[best]) best = k;
+      }
+      const int b = c * B_ar + best;
+      kept_rows[c] = rows[b];
+      kept.insert(kept.end(), latents.begin() + lat_off[b] * 1024, latents.begin() + lat_off[b + 1] * 1024);
+      printf("chunk %d: %d text ids, candidate %d kept, %d latent rows, %d mel frames\n", c, n_text[c], best, rows[b], tts_diffusion_frames(rows[b]));
     }
-    if (shard < 0) printf("clvp: candidate %d kept (score %.5f)\n", kept_gc, kept_score);
+    latents.swap(kept);
+    rows = kept_rows;
+    lat_in = latents.data();
+    B = n_chunks;
+  } else {
+    int32_t nsteps = 0;
+    // More than one candidate (in this process or across --devices shards): the throughput stop rule. The reference's "all B samples of ONE
+    // step are 8193" practically never fires for B > 1 (and would need a per-step exchange between shards); every sequence is the same.
+    const unsigned ar_flags = (fixed_codes > 0 ? TTS_AR_MASK_STOP : 0) | (total_candidates > 1 ? TTS_AR_RETIRE : 0);
+    if (tts_autoregressive(ctx, tokens.data(), n, voice.data(), B_ar, fixed_codes > 0 ? fixed_codes : 500, ar_flags,
+                           codes.data(), rows.data(), latents.data(), &nsteps))
+      return die(ctx, "autoregressive");
+    mark("autoregressive");
+    printf("tokens sampled: %d\n", nsteps);
+    if (fixed_codes <= 0) {
+      std::vector<int32_t> stopped(B_ar);
+      if (tts_ar_stop_status(ctx, stopped.data(), B_ar) == 0)
+        for (int c = 0; c < B_ar; c++)
+          if (!stopped[c]) fprintf(stderr, "warning: candidate %d sampled no stop token within 500 codes (sequence cut)\n", (shard >= 0 ? shard * B_ar : 0) + c);
+    }
+
+    // CLVP re-ranking (extension): keep the candidate whose codes (the rows the diffusion stage would consume) score best against the text
+    B = B_ar;
+    if (!clvpPath.empty()) {
+      if (tts_load_clvp(ctx, clvpPath.c_str())) return die(ctx, "clvp_model_load");
+      std::vector<float> scores(B_ar);
+      if (tts_clvp_score(ctx, tokens.data(), n, codes.data() + 1, rows.data(), B_ar, 502, scores.data())) return die(ctx, "clvp");
+      int best = 0;
+      for (int c = 1; c < B_ar; c++)
+        if (scores[c] > scores[best]) best = c;
+      printf("clvp scores:");
+      for (int c = 0; c < B_ar; c++) printf(" %.5f", scores[c]);
+      printf("\n");
+      size_t off_rows = 0;
+      for (int c = 0; c < best; c++) off_rows += (size_t)rows[c];
+      lat_in = latents.data() + off_rows * 1024;
+      rows[0] = rows[best];
+      B = 1;
+      kept_gc = (shard >= 0 ? shard * B_ar : 0) + best;
+      kept_score = scores[best];
+      if (total_candidates > 1) { // device noise stays keyed by the kept candidate's global id
+        tts_set_option(ctx, "rng_shard_offset", (double)kept_gc);
+        tts_set_option(ctx, "rng_shard_total", (double)total_candidates);
+      }
+      if (shard < 0) printf("clvp: candidate %d kept (score %.5f)\n", kept_gc, kept_score);
+    }
   }
 
   bg.t.join();
@@ -412,6 +475,8 @@ int main(int argc, char **argv) {
         }
       }
     }
+  } else if (n_chunks > 1) { // --split-text: the chunks' audio one after the other, one file
+    write_one(audio.data(), (int64_t)audio.size(), 0, true);
   } else {
     size_t off = 0;
     for (int c = 0; c < B; c++) {

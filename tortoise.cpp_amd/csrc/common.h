@@ -319,6 +319,23 @@ int host_prefilter_row(const float *row, int keep, int32_t *list);
 int sample_one_row(const float *row, const int32_t *ids, int ids_per_cand, float uniform);
 int sample_one_from_list(const int32_t *list, const int32_t *ids, int ids_per_cand, float uniform);
 void pad_codes(std::vector<int> &codes);            // apply_padding
+// Stop rule of the decode loop (main.cpp:5188-5249) for a batch of prompt groups: group g holds candidates [c0[g], c0[g] + n[g]).
+// Strict (the reference's rule, per group): a candidate's sequence freezes at its first 8193 and the group ENDS in the first iteration where all
+// of its candidates sample 8193. retire (TTS_AR_RETIRE): a candidate retires at its first 8193. A retired candidate (retire mode) or a
+// candidate of an ended group is fed 8193 and its samples are ignored; its uniforms are still drawn by the caller.
+struct ArStopBook {
+  std::vector<int> c0, n;
+  std::vector<char> done;     // per candidate: has sampled 8193 (its sequence is frozen)
+  std::vector<char> retired;  // per candidate: input forced to 8193, samples ignored (sample_candidates_list skips it)
+  std::vector<char> ended;    // per group
+  std::vector<std::vector<int>> seq;
+  void init(const int *n_cand, int G);
+  // Applies iteration i's samples [B] in place (stop schedule stop_at [B] or null, retired rows -> 8193): afterwards `samples` are the next step's
+  // input tokens. Returns true when every group has ended.
+  bool step(int32_t *samples, int i, bool retire, const int32_t *stop_at);
+};
+// tts_split_text's rule on a tokenizer: byte ranges {start, length} of the chunks of `message`
+std::vector<std::pair<int, int>> split_text(const Tokenizer &tok, const std::string &message, int max_ids);
 int trimmed_latent_rows(const int32_t *codes502);   // trim_latents row count
 struct DiffSchedule {
   int n = 0;

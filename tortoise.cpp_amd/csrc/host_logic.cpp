@@ -690,6 +690,35 @@ void pad_codes(std::vector<int> &codes) {
   codes.insert(codes.begin(), 8192);
 }
 
+void ArStopBook::init(const int *n_cand, int G) {
+  c0.assign(G, 0); n.assign(n_cand, n_cand + G);
+  for (int g = 1; g < G; g++) c0[g] = c0[g - 1] + n[g - 1];
+  const int B = G ? c0[G - 1] + n[G - 1] : 0;
+  done.assign(B, 0); retired.assign(B, 0); ended.assign(G, 0);
+  seq.assign(B, {});
+}
+
+// One prompt (G = 1) is the loop of rounds 1-6 exactly: strict mode ends when all B samples of one iteration are 8193, retire mode when every
+// candidate has retired.
+bool ArStopBook::step(int32_t *samples, int i, bool retire, const int32_t *stop_at) {
+  bool all = true;
+  for (size_t g = 0; g < n.size(); g++) {
+    int stops = 0;
+    for (int b = c0[g]; b < c0[g] + n[g]; b++) {
+      if (stop_at && i == stop_at[b]) samples[b] = 8193; // tts_ar_set_stop_schedule
+      if (retired[b]) { samples[b] = 8193; stops++; continue; }
+      if (!(seq[b].size() > 0 && seq[b].back() == 8193)) seq[b].push_back(samples[b]);
+      if (samples[b] == 8193) { stops++; done[b] = 1; if (retire) retired[b] = 1; }
+    }
+    if (stops == n[g] && !ended[g]) {
+      ended[g] = 1;
+      for (int b = c0[g]; b < c0[g] + n[g]; b++) retired[b] = 1; // the group's rows are fed 8193 from now on
+    }
+    all = all && ended[g];
+  }
+  return all;
+}
+
 // trim_latents, main.cpp:4873-4915: rows kept until more than 8 consecutive 83s.
 int trimmed_latent_rows(const int32_t *codes502) {
   int run = 0;
@@ -765,6 +794,76 @@ void DiffSchedule::build(int n_steps) {
   }
 }
 
+// Text splitter (tts_split_text; our own rule, stated in include/tortoise_mi355x.h). Chunks are byte ranges of the message; every chunk tokenizes to
+// at most max_ids ids. Token counts are those of Tokenizer::encode on the chunk's bytes (255 ... 0 included).
+std::vector<std::pair<int, int>> split_text(const Tokenizer &tok, const std::string &msg, int max_ids) {
+  auto ws = [&](int i) { return isspace((unsigned char)msg[i]) != 0; };
+  auto fits = [&](int a, int b) { // the trimmed piece, as it would be emitted
+    while (a < b && ws(a)) a++;
+    while (b > a && ws(b - 1)) b--;
+    return (int)tok.encode(msg.substr(a, b - a)).size() <= max_ids;
+  };
+  const int n = (int)msg.size();
+  // sentences: [a, b) trimmed, ending after '.', '!' or '?' followed by whitespace or the end of the text
+  std::vector<std::pair<int, int>> sent;
+  for (int i = 0; i < n;) {
+    while (i < n && ws(i)) i++;
+    if (i >= n) break;
+    int j = i;
+    while (j < n && !((msg[j] == '.' || msg[j] == '!' || msg[j] == '?') && (j + 1 == n || ws(j + 1)))) j++;
+    j = std::min(n, j + 1);
+    int e = j;
+    while (e > i && ws(e - 1)) e--;
+    sent.push_back({i, e});
+    i = j;
+  }
+  std::vector<std::pair<int, int>> out;
+  auto emit = [&](int a, int b) { // trimmed, never empty
+    while (a < b && ws(a)) a++;
+    while (b > a && ws(b - 1)) b--;
+    if (b > a) out.push_back({a, b - a});
+  };
+  // an over-long sentence [a, b): cut after the last ',', ';', ':' or space whose piece fits, else at the longest fitting prefix (whole UTF-8 characters)
+  auto split_long = [&](int a, int b) {
+    while (a < b) {
+      while (a < b && ws(a)) a++;
+      if (a >= b) break;
+      if (fits(a, b)) { emit(a, b); break; }
+      int best = -1;
+      for (int k = a + 1; k < b; k++) { // break points in order; the token count grows with the piece, so stop at the first that does not fit
+        const char ch = msg[k - 1];
+        if (!(ch == ',' || ch == ';' || ch == ':' || ws(k - 1))) continue;
+        if (!fits(a, k)) break;
+        best = k;
+      }
+      if (best < 0) { // hard cut: the longest prefix that fits (bisection over character starts, then checked downwards)
+        int lo = a + 1, hi = b; // lo: fits (one character is at most one id, max_ids >= 3), hi: does not
+        while (lo < b && ((unsigned char)msg[lo] & 0xC0) == 0x80) lo++;
+        auto cstart = [&](int k) { while (k > a && k < b && ((unsigned char)msg[k] & 0xC0) == 0x80) k--; return k; };
+        while (hi - lo > 1) {
+          const int mid = cstart(lo + (hi - lo) / 2);
+          if (mid <= lo) break;
+          if (fits(a, mid)) lo = mid; else hi = mid;
+        }
+        while (lo > a + 1 && !fits(a, lo)) lo = cstart(lo - 1);
+        best = lo;
+        while (best < b && ((unsigned char)msg[best] & 0xC0) == 0x80) best++; // never split a character
+      }
+      emit(a, best);
+      a = best;
+    }
+  };
+  for (size_t s0 = 0; s0 < sent.size();) {
+    const int a = sent[s0].first;
+    if (!fits(a, sent[s0].second)) { split_long(a, sent[s0].second); s0++; continue; }
+    size_t s1 = s0 + 1; // greedy: whole sentences while the chunk fits
+    while (s1 < sent.size() && fits(a, sent[s1].second)) s1++;
+    emit(a, sent[s1 - 1].second);
+    s0 = s1;
+  }
+  return out;
+}
+
 } // namespace tts
 
 // ---- host-logic probes: the host-side pieces of the stage drivers, callable without a GPU (tests/test_host_parity.py) ----
@@ -792,6 +891,41 @@ extern "C" int tts_host_pad_codes(const int32_t *codes, int n, int32_t *out502) 
   return TTS_OK;
 }
 extern "C" int tts_host_trimmed_rows(const int32_t *codes502) { return tts::trimmed_latent_rows(codes502); }
+// The decode loop's stop bookkeeping (tts::ArStopBook, the one tts_autoregressive_multi runs) on scripted samples: samples [max_steps][B] are what the
+// sampler returns at each iteration. Outputs as the driver's: codes [B][502] (padded), stopped [B], *steps; inputs [max_steps][B] (may be null): the tokens fed to
+// the decode step after each iteration. TTS_ERR_LIMIT when strict mode reaches max_steps.
+extern "C" int tts_host_ar_stop_run(const int32_t *n_cand, int G, const int32_t *samples, int max_steps, unsigned flags, const int32_t *stop_at,
+                                    int32_t *codes_out, int32_t *stopped_out, int32_t *steps_out, int32_t *inputs_out) {
+  if (!n_cand || G < 1 || !samples || max_steps < 1 || max_steps > 500 || !codes_out || !stopped_out || !steps_out) return TTS_ERR_ARG;
+  int B = 0;
+  for (int g = 0; g < G; g++) { if (n_cand[g] < 1) return TTS_ERR_ARG; B += n_cand[g]; }
+  const bool retire = (flags & TTS_AR_RETIRE) != 0, sched = stop_at && (flags & TTS_AR_MASK_STOP) && retire;
+  tts::ArStopBook book;
+  book.init(n_cand, G);
+  std::vector<int32_t> s(B);
+  int i = 0;
+  for (;;) {
+    std::copy(samples + (size_t)i * B, samples + (size_t)(i + 1) * B, s.begin());
+    const bool end = book.step(s.data(), i, retire, sched ? stop_at : nullptr);
+    if (inputs_out) std::copy(s.begin(), s.end(), inputs_out + (size_t)i * B);
+    i++;
+    if (end) break;
+    if (i >= max_steps) {
+      if ((flags & TTS_AR_MASK_STOP) || retire) break;
+      *steps_out = i;
+      return TTS_ERR_LIMIT;
+    }
+  }
+  *steps_out = i;
+  for (int b = 0; b < B; b++) {
+    stopped_out[b] = (!book.seq[b].empty() && book.seq[b].back() == 8193) ? 1 : 0;
+    std::vector<int> v = book.seq[b];
+    if (v.size() > 500) v.resize(500);
+    tts::pad_codes(v);
+    std::copy(v.begin(), v.end(), codes_out + (size_t)b * 502);
+  }
+  return TTS_OK;
+}
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Mel front-end of the two voice-conditioning encoders (upstream tortoise-tts; the reference has no audio INPUT path at all).
