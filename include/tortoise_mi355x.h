@@ -49,8 +49,10 @@ enum { TTS_VOCAB_MEL = 8194, TTS_DMODEL = 1024, TTS_MEL_CH = 100, TTS_CODES = 50
  *   5 = round 5: tts_ar_set_stop_schedule, tts_version; option "attn_proj_f16"; the default AttentionBlock multiplies proj_out on an F32-accurate
  *       (split fp16 pair) weight.
  *   7 = several prompts in one autoregressive pass: tts_ar_begin_multi, tts_autoregressive_multi, tts_split_text, tts_host_ar_stop_run (after
- *       tts_ar_begin_multi, tts_ar_prefill / tts_ar_step / tts_ar_step_sample / tts_ar_latents work on the whole batch of all prompts). */
-#define TTS_API_VERSION 7
+ *       tts_ar_begin_multi, tts_ar_prefill / tts_ar_step / tts_ar_step_sample / tts_ar_latents work on the whole batch of all prompts).
+ *   8 = several voices in one batch: tts_ar_begin_multi_voice, tts_autoregressive_multi_voice, tts_diffusion_multi_voice, tts_split_turns (every earlier
+ *       prototype, option and default keeps its meaning and its bits). */
+#define TTS_API_VERSION 8
 int tts_version(void);
 
 /* replaces ggml_backend_cuda_init(0) (main.cpp:651, 1213, 1777). device = HIP ordinal; returns NULL
@@ -223,7 +225,7 @@ int tts_ar_stop_status(tts_ctx *ctx, int32_t *stopped_out, int n_candidates);
 /* ---- several prompts in one autoregressive pass (API version 7; the reference runs one prompt per call) ------------------------ */
 /* A batch of G PROMPT GROUPS: text_ids holds the G prompts back to back, prompt g has n_text[g] ids (1 .. 404, each < 256) and n_cand[g] >= 1 candidates,
  * which are the contiguous range [c0_g, c0_g + n_cand[g]) of the B = sum n_cand candidates (c0_g = n_cand[0] + .. + n_cand[g-1]). One voice latent for all
- * (the diffusion stage's voice is a weight of the loaded model). The decode steps of all groups run in lock-step — mel position id step_i + 2 for every row —
+ * (a voice per prompt: tts_ar_begin_multi_voice below). The decode steps of all groups run in lock-step — mel position id step_i + 2 for every row —
  * and only the context length differs per row: n_past = n_text[g] + 2 + step_i. Every argument is checked before any device work (TTS_ERR_ARG: G < 1,
  * n_cand < 1, n_text < 1, an id >= 256; TTS_ERR_LIMIT: a prompt > 404 ids, max_steps + 2 > 608, longest prompt + 2 + max_steps + 1 > 1024 positions).
  * After tts_ar_begin_multi: tts_ar_prefill / tts_ar_step return [B][8194] in global candidate order (a group's prefill rows are its prompt's logits),
@@ -250,6 +252,40 @@ int tts_autoregressive_multi(tts_ctx *ctx, const int32_t *text_ids, const int32_
  *   - chunks are trimmed of whitespace; no chunk is empty (an empty or all-whitespace message gives 0 chunks).
  * starts_out[k] / lens_out[k]: byte range of chunk k in `message`. Returns the number of chunks (only the first `cap` are written) or a negative status. */
 int tts_split_text(tts_ctx *ctx, const char *message, int max_ids, int32_t *starts_out, int32_t *lens_out, int cap);
+
+/* ---- several voices in one batch (API version 8; the reference has one voice per run, main.cpp:5179-5184, 1557-1560) ------------------------------ */
+/* The engine reads a voice at two places only: the 1024-float autoregressive latent is position 0 of every prompt pass (and, through the prompt's cache rows,
+ * of every latent pass), the 2048-float diffusion conditioning latent is the scale / shift of the code norm that ends the latent conditioner. Both become a
+ * table with one row index per prompt group / per candidate; everything downstream (decode steps, guidance, sampling steps, vocoder) is per sequence already.
+ * Every row of such a batch is bit-identical to the same row run alone with its voice through the single-voice entry points.
+ * Argument checks, before any device work, for all three device calls: TTS_ERR_ARG for n_voices < 1, a null pointer, an index outside [0, n_voices), a
+ * non-finite latent value. A call refused by these checks changes nothing; one that fails later leaves no half-begun state (as tts_ar_begin_multi). */
+/* tts_ar_begin_multi with voices [n_voices][1024]: prompt group g's prefill and latent pass read voices[voice_of_prompt[g]]. Afterwards tts_ar_prefill /
+ * tts_ar_step / tts_ar_step_sample / tts_ar_latents work on the whole batch as after tts_ar_begin_multi. */
+int tts_ar_begin_multi_voice(tts_ctx *ctx, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voices, int n_voices,
+                             const int32_t *voice_of_prompt, const int32_t *n_cand, int max_steps);
+/* tts_autoregressive_multi with a voice per prompt group. Stop rule, RNG order, TTS_AR_MASK_STOP, TTS_AR_RETIRE, stop schedules and outputs are exactly
+ * those of tts_autoregressive_multi: group g's codes, rows, latents and stop status equal a tts_autoregressive of prompt g alone with voices[voice_of_prompt[g]],
+ * options rng_shard_offset = c0_g, rng_shard_total = B and the same seed. n_voices = 1 with all indices 0 is tts_autoregressive_multi, byte for byte (RNG
+ * state afterwards included). */
+int tts_autoregressive_multi_voice(tts_ctx *ctx, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voices, int n_voices,
+                                   const int32_t *voice_of_prompt, const int32_t *n_cand, int max_steps, unsigned flags, int32_t *codes_out,
+                                   int32_t *rows_out, float *latents_out, int32_t *steps_out);
+/* tts_diffusion (declared below: latents, rows, noise, noise_mode, mel_out as there) with candidate c conditioned on voice_latents[voice_of_candidate[c]]
+ * ([n_voices][2048], what tts_diffusion_conditioning_latent returns) instead of the loaded model's `diffusion_conditioning_latent`, which is neither read
+ * nor modified: a later tts_diffusion returns what it returned before. Candidate c's mel equals tts_set_diffusion_conditioning_latent(its voice) +
+ * tts_diffusion of that candidate alone on the same noise. One small upload per call, no additional kernel launch. tts_diffusion_forward stays single-voice. */
+int tts_diffusion_multi_voice(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates, const float *voice_latents, int n_voices,
+                              const int32_t *voice_of_candidate, int n_steps, const float *noise, int noise_mode, float *mel_out);
+/* Splits a multi-speaker message into chunks (tts_split_text's byte ranges) with a voice index each. Host only (works on a device = -1 context with a
+ * tokenizer loaded). The rule (ours):
+ *   - turns are separated by '\n';
+ *   - a turn that begins with "<decimal index>|" (blanks before the digits are allowed) speaks with that voice; the prefix is not part of the text;
+ *   - a turn without a prefix keeps the previous turn's voice; the first turn defaults to voice 0;
+ *   - each turn's text is split by the tts_split_text rule with max_ids; an empty turn gives no chunk (a prefix on it still sets the voice).
+ * starts_out[k] / lens_out[k]: byte range of chunk k in `message` (never inside a prefix), voice_out[k] its voice. Returns the number of chunks (only the
+ * first `cap` are written) or a negative status: TTS_ERR_ARG for n_voices < 1, max_ids outside 3 .. 404 or an index >= n_voices. */
+int tts_split_turns(tts_ctx *ctx, const char *message, int n_voices, int max_ids, int32_t *starts_out, int32_t *lens_out, int32_t *voice_out, int cap);
 
 /* ---- candidate re-ranking (not in the reference) -------------------------------------------- */
 /* Score of every candidate = cosine similarity of the text latent and the candidate's speech-code latent x exp(temperature); the

@@ -67,6 +67,10 @@ def lib():
         "tts_ar_begin_multi": (ci, [vp, _i32p, _i32p, ci, _f32p, _i32p, ci]),
         "tts_autoregressive_multi": (ci, [vp, _i32p, _i32p, ci, _f32p, _i32p, ci, C.c_uint, _i32p, _i32p, vp, _i32p]),
         "tts_split_text": (ci, [vp, C.c_char_p, ci, _i32p, _i32p, ci]),
+        "tts_ar_begin_multi_voice": (ci, [vp, _i32p, _i32p, ci, vp, ci, vp, _i32p, ci]),
+        "tts_autoregressive_multi_voice": (ci, [vp, _i32p, _i32p, ci, vp, ci, vp, _i32p, ci, C.c_uint, _i32p, _i32p, vp, _i32p]),
+        "tts_diffusion_multi_voice": (ci, [vp, _f32p, _i32p, ci, vp, ci, vp, ci, vp, ci, _f32p]),
+        "tts_split_turns": (ci, [vp, C.c_char_p, ci, ci, _i32p, _i32p, _i32p, ci]),
         "tts_host_ar_stop_run": (ci, [_i32p, ci, _i32p, ci, C.c_uint, vp, _i32p, _i32p, _i32p, vp]),
         "tts_diffusion_frames": (ci, [ci]),
         "tts_diffusion_forward": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p]),
@@ -250,24 +254,35 @@ class Engine:
                 off += r
         return codes, rows, lats, int(steps[0])
 
-    def ar_begin_multi(self, prompts, voice, n_cand, max_steps):
+    def ar_begin_multi(self, prompts, voice=None, n_cand=1, max_steps=1, voices=None, voice_of_prompt=None):
         """Several prompts in one batch: prompt g (text ids) gets n_cand[g] candidates, candidates in prompt order. ar_prefill / ar_step / ar_step_sample /
-        ar_latents then work on all sum(n_cand) rows."""
+        ar_latents then work on all sum(n_cand) rows. One `voice` [1024] for all, or `voices` [V, 1024] with `voice_of_prompt` [G] (tts_ar_begin_multi_voice)."""
         ids, lens, nc = _prompt_args(prompts, n_cand)
         self.B = int(nc.sum())
-        self._ck(self.L.tts_ar_begin_multi(self.h, ids, lens, len(lens), np.ascontiguousarray(voice, np.float32), nc, max_steps))
+        if voices is None and voice_of_prompt is None:
+            self._ck(self.L.tts_ar_begin_multi(self.h, ids, lens, len(lens), np.ascontiguousarray(voice, np.float32), nc, max_steps))
+            return
+        tab, nv, idx = _voice_args(voice, voices, voice_of_prompt, DMODEL)
+        self._ck(self.L.tts_ar_begin_multi_voice(self.h, ids, lens, len(lens), _ptr(tab), nv, _ptr(idx), nc, max_steps))
 
-    def autoregressive_multi(self, prompts, voice, n_cand, max_steps, mask_stop=False, retire=False, want_latents=True):
+    def autoregressive_multi(self, prompts, voice=None, n_cand=1, max_steps=1, mask_stop=False, retire=False, want_latents=True, voices=None, voice_of_prompt=None):
         """autoregressive() of every prompt inside one decode loop. Returns (codes, rows, latents, steps): per prompt g codes [n_cand[g], 502], rows
-        [n_cand[g]] and the list of its candidates' trimmed latents (None without want_latents); steps = sampling iterations of the shared loop."""
+        [n_cand[g]] and the list of its candidates' trimmed latents (None without want_latents); steps = sampling iterations of the shared loop.
+        One `voice` [1024] for all, or `voices` [V, 1024] with `voice_of_prompt` [G] (tts_autoregressive_multi_voice)."""
         ids, lens, nc = _prompt_args(prompts, n_cand)
         B = int(nc.sum())
         codes = np.empty((B, 502), np.int32)
         rows = np.empty(B, np.int32)
         steps = np.zeros(1, np.int32)
         lat = np.empty((B * 500, DMODEL), np.float32) if want_latents else None
-        self._ck(self.L.tts_autoregressive_multi(self.h, ids, lens, len(lens), np.ascontiguousarray(voice, np.float32), nc, max_steps,
-                                                 (AR_MASK_STOP if mask_stop else 0) | (AR_RETIRE if retire else 0), codes.reshape(-1), rows, _ptr(lat), steps))
+        flags = (AR_MASK_STOP if mask_stop else 0) | (AR_RETIRE if retire else 0)
+        if voices is None and voice_of_prompt is None:
+            self._ck(self.L.tts_autoregressive_multi(self.h, ids, lens, len(lens), np.ascontiguousarray(voice, np.float32), nc, max_steps, flags,
+                                                     codes.reshape(-1), rows, _ptr(lat), steps))
+        else:
+            tab, nv, idx = _voice_args(voice, voices, voice_of_prompt, DMODEL)
+            self._ck(self.L.tts_autoregressive_multi_voice(self.h, ids, lens, len(lens), _ptr(tab), nv, _ptr(idx), nc, max_steps, flags, codes.reshape(-1), rows,
+                                                           _ptr(lat), steps))
         c0 = np.concatenate([[0], np.cumsum(nc)])
         out_codes = [codes[c0[g]:c0[g + 1]].copy() for g in range(len(nc))]
         out_rows = [rows[c0[g]:c0[g + 1]].copy() for g in range(len(nc))]
@@ -289,6 +304,15 @@ class Engine:
         starts, lens = np.empty(cap, np.int32), np.empty(cap, np.int32)
         n = self._ck(self.L.tts_split_text(self.h, raw, max_ids, starts, lens, cap))
         return [raw[starts[k]:starts[k] + lens[k]].decode("utf-8") for k in range(n)]
+
+    def split_turns(self, message, n_voices, max_ids=404):
+        """Chunks of a multi-speaker message (tts_split_turns' rule: one turn per line, "<index>|" in front of a turn names its voice): a list of
+        (text, voice index)."""
+        raw = message.encode("utf-8")
+        cap = len(raw) + 1
+        starts, lens, vo = np.empty(cap, np.int32), np.empty(cap, np.int32), np.empty(cap, np.int32)
+        n = self._ck(self.L.tts_split_turns(self.h, raw, n_voices, max_ids, starts, lens, vo, cap))
+        return [(raw[starts[k]:starts[k] + lens[k]].decode("utf-8"), int(vo[k])) for k in range(n)]
 
     def ar_stop_status(self, B):
         """Per candidate of the last autoregressive() call: 1 = ended in a sampled stop token, 0 = cut at max_steps."""
@@ -351,8 +375,10 @@ class Engine:
                                               timestep, 1 if conditioning_free else 0, out.reshape(-1)))
         return out
 
-    def diffusion(self, latents_list, n_steps=80, noise=None, noise_mode=NOISE_REFERENCE):
-        """latents_list: list of [L_c,1024]. noise: list of [(n_steps+1), 100*T_c] or None. Returns list of mel [100,T_c]."""
+    def diffusion(self, latents_list, n_steps=80, noise=None, noise_mode=NOISE_REFERENCE, voice_latents=None, voice_of_candidate=None):
+        """latents_list: list of [L_c,1024]. noise: list of [(n_steps+1), 100*T_c] or None. Returns list of mel [100,T_c].
+        voice_latents [V, 2048] + voice_of_candidate [B]: candidate c is conditioned on voice_latents[voice_of_candidate[c]] instead of the loaded model's
+        latent (tts_diffusion_multi_voice)."""
         rows = np.array([len(l) for l in latents_list], np.int32)
         lat = np.ascontiguousarray(np.concatenate([np.asarray(l, np.float32).reshape(-1, DMODEL) for l in latents_list]))
         Ts = [self.frames(int(r)) for r in rows]
@@ -360,7 +386,11 @@ class Engine:
         nz = None
         if noise is not None:
             nz = np.ascontiguousarray(np.concatenate([np.asarray(n, np.float32).reshape(-1) for n in noise]))
-        self._ck(self.L.tts_diffusion(self.h, lat.reshape(-1), rows, len(rows), n_steps, _ptr(nz), noise_mode, mel))
+        if voice_latents is None and voice_of_candidate is None:
+            self._ck(self.L.tts_diffusion(self.h, lat.reshape(-1), rows, len(rows), n_steps, _ptr(nz), noise_mode, mel))
+        else:
+            tab, nv, idx = _voice_args(None, voice_latents, voice_of_candidate, 2 * DMODEL)
+            self._ck(self.L.tts_diffusion_multi_voice(self.h, lat.reshape(-1), rows, len(rows), _ptr(tab), nv, _ptr(idx), n_steps, _ptr(nz), noise_mode, mel))
         out, off = [], 0
         for t in Ts:
             out.append(mel[off:off + 100 * t].reshape(100, t).copy())
@@ -454,6 +484,16 @@ def _prompt_args(prompts, n_cand):
     ids = np.ascontiguousarray(np.concatenate([np.asarray(p, np.int32).reshape(-1) for p in prompts]) if len(prompts) else np.zeros(0, np.int32), np.int32)
     nc = np.ascontiguousarray(np.broadcast_to(np.asarray(n_cand, np.int32), lens.shape) if np.ndim(n_cand) == 0 else np.asarray(n_cand, np.int32), np.int32)
     return ids, lens, nc
+
+
+def _voice_args(voice, voices, index, width):
+    """(table [V, width] or None, V, indices or None) for the multi-voice entry points. Nothing is checked here beyond the row width: a missing table or index
+    list, an index out of range and a non-finite value are the library's to refuse (TTS_ERR_ARG)."""
+    if voices is None and voice is not None:
+        voices = np.asarray(voice, np.float32).reshape(1, -1)
+    tab = None if voices is None else np.ascontiguousarray(voices, np.float32).reshape(-1, width)
+    idx = None if index is None else np.ascontiguousarray(index, np.int32).reshape(-1)
+    return tab, (0 if tab is None else tab.shape[0]), idx
 
 
 def host_ar_stop_run(n_cand, samples, max_steps, flags=0, stop_at=None):

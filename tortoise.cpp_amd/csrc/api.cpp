@@ -9,7 +9,7 @@
 
 namespace tts {
 int ar_begin(tts_ctx *, const int32_t *, int, const float *, int, int);
-int ar_begin_groups(tts_ctx *, const int32_t *, const int *, int, const float *, const int *, int);
+int ar_begin_groups(tts_ctx *, const int32_t *, const int *, int, const float *, int n_voices, const int *voice_of, const int *, int);
 int ar_latents_group(tts_ctx *, int, const int32_t *, int, float *);
 int ar_prefill(tts_ctx *, float *);
 int ar_step(tts_ctx *, const int32_t *, int, float *, int mode);
@@ -22,6 +22,7 @@ float *ar_host_logits(tts_ctx *);
 int diff_layers(const tts_ctx *);
 int diff_forward(tts_ctx *, const float *, int, const float *, int, int, float *);
 int diff_sample(tts_ctx *, const float *, const int32_t *, int, int, const float *, int, float *);
+int diff_sample_voices(tts_ctx *, const float *, const int32_t *, int, const float *, int, const int32_t *, int, const float *, int, float *);
 int voc_run(tts_ctx *, const float *, const int32_t *, int, const float *, int, float *);
 } // namespace tts
 
@@ -358,9 +359,10 @@ int tts_sample(tts_ctx *c, const float *logits, const int32_t *ids, int ids_per_
 }
 
 // autoregressive(), main.cpp:5042-5367, for G prompt groups in one decode loop (tts_autoregressive: G = 1; tts_autoregressive_multi). Group g's
-// prompt is text_ids[t0_g .. + n_text[g]), its candidates [c0_g, c0_g + n_cand[g]) of the batch.
-static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n_text, int G, const float *voice, const int *n_cand, int max_steps,
-                               unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
+// prompt is text_ids[t0_g .. + n_text[g]), its candidates [c0_g, c0_g + n_cand[g]) of the batch. voice: [n_voices][1024], group g reads row voice_of[g]
+// (tts_autoregressive_multi_voice; voice_of == nullptr: one voice for all). Nothing after ar_begin_groups depends on the voices.
+static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n_text, int G, const float *voice, int n_voices, const int *voice_of,
+                               const int *n_cand, int max_steps, unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
   static const bool timing = getenv("TTS_TIMING") != nullptr; // developer aid: host-side breakdown of the stage on stderr
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_begin = now(), t_sample = 0, t_step = 0;
@@ -377,7 +379,7 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
     if (!warned) { fprintf(stderr, "tts_autoregressive: a stop schedule is set but the call does not pass TTS_AR_MASK_STOP | TTS_AR_RETIRE: ignored\n"); warned = true; }
   }
   if (sched && (int)c->stop_schedule.size() != B) return fail(c, TTS_ERR_ARG, "tts_autoregressive: the stop schedule holds %d candidates, the call %d", (int)c->stop_schedule.size(), B);
-  int rc = ar_begin_groups(c, text_ids, n_text, G, voice, n_cand, max_steps);
+  int rc = ar_begin_groups(c, text_ids, n_text, G, voice, n_voices, voice_of, n_cand, max_steps);
   if (rc) return rc;
   const int V = TTS_VOCAB_MEL;
   std::vector<float> logits0((size_t)B * V);
@@ -484,7 +486,7 @@ int tts_autoregressive(tts_ctx *c, const int32_t *text_ids, int n_text, const fl
                        unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
   NEED_CTX(c);
   return guarded(c, [&] {
-    return autoregressive_impl(c, text_ids, &n_text, 1, voice, &B, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
+    return autoregressive_impl(c, text_ids, &n_text, 1, voice, 1, nullptr, &B, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
   });
 }
 
@@ -493,14 +495,48 @@ int tts_autoregressive_multi(tts_ctx *c, const int32_t *text_ids, const int32_t 
   NEED_CTX(c);
   if (n_prompts < 1 || !n_text || !n_cand) return fail(c, TTS_ERR_ARG, "tts_autoregressive_multi: bad argument");
   return guarded(c, [&] {
-    return autoregressive_impl(c, text_ids, n_text, n_prompts, voice, n_cand, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
+    return autoregressive_impl(c, text_ids, n_text, n_prompts, voice, 1, nullptr, n_cand, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
   });
 }
 
 int tts_ar_begin_multi(tts_ctx *c, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voice, const int32_t *n_cand, int max_steps) {
   NEED_CTX(c);
   if (n_prompts < 1 || !n_text || !n_cand) return fail(c, TTS_ERR_ARG, "tts_ar_begin_multi: bad argument");
-  return guarded(c, [&] { return ar_begin_groups(c, text_ids, n_text, n_prompts, voice, n_cand, max_steps); });
+  return guarded(c, [&] { return ar_begin_groups(c, text_ids, n_text, n_prompts, voice, 1, nullptr, n_cand, max_steps); });
+}
+
+// Several voices in one batch (API version 8): the voice table and the groups' rows of it are checked by ar_begin_groups before any device work.
+int tts_ar_begin_multi_voice(tts_ctx *c, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voices, int n_voices,
+                             const int32_t *voice_of_prompt, const int32_t *n_cand, int max_steps) {
+  NEED_CTX(c);
+  if (n_prompts < 1 || !n_text || !n_cand || !voices || !voice_of_prompt || n_voices < 1) return fail(c, TTS_ERR_ARG, "tts_ar_begin_multi_voice: bad argument");
+  return guarded(c, [&] { return ar_begin_groups(c, text_ids, n_text, n_prompts, voices, n_voices, voice_of_prompt, n_cand, max_steps); });
+}
+
+int tts_autoregressive_multi_voice(tts_ctx *c, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voices, int n_voices,
+                                   const int32_t *voice_of_prompt, const int32_t *n_cand, int max_steps, unsigned flags, int32_t *codes_out, int32_t *rows_out,
+                                   float *latents_out, int32_t *steps_out) {
+  NEED_CTX(c);
+  if (n_prompts < 1 || !n_text || !n_cand || !voices || !voice_of_prompt || n_voices < 1)
+    return fail(c, TTS_ERR_ARG, "tts_autoregressive_multi_voice: bad argument");
+  return guarded(c, [&] {
+    return autoregressive_impl(c, text_ids, n_text, n_prompts, voices, n_voices, voice_of_prompt, n_cand, max_steps, flags, codes_out, rows_out, latents_out,
+                               steps_out);
+  });
+}
+
+int tts_split_turns(tts_ctx *c, const char *message, int n_voices, int max_ids, int32_t *starts_out, int32_t *lens_out, int32_t *voice_out, int cap) {
+  if (!c) return TTS_ERR_ARG;
+  if (!c->tok) return fail(c, TTS_ERR_STATE, "tokenizer not loaded");
+  if (!message || n_voices < 1 || max_ids < 3 || max_ids > 404 || cap < 0 || (cap > 0 && (!starts_out || !lens_out || !voice_out)))
+    return fail(c, TTS_ERR_ARG, "tts_split_turns: bad argument (n_voices %d: >= 1, max_ids %d: 3 .. 404)", n_voices, max_ids);
+  return guarded(c, [&] {
+    std::vector<TurnChunk> ch;
+    long bad = 0;
+    if (!split_turns(*c->tok, message, n_voices, max_ids, ch, &bad)) return fail(c, TTS_ERR_ARG, "tts_split_turns: a turn names voice %ld of %d", bad, n_voices);
+    for (int k = 0; k < (int)ch.size() && k < cap; k++) { starts_out[k] = ch[k].start; lens_out[k] = ch[k].len; voice_out[k] = ch[k].voice; }
+    return (int)ch.size();
+  });
 }
 
 int tts_split_text(tts_ctx *c, const char *message, int max_ids, int32_t *starts_out, int32_t *lens_out, int cap) {
@@ -544,6 +580,12 @@ int tts_diffusion(tts_ctx *c, const float *latents, const int32_t *rows, int B, 
   // the DEVICE noise streams are keyed by the global candidate id; host / reference noise does not look at the shard options
   if (B >= 1 && !noise && noise_mode == TTS_NOISE_DEVICE) if (int rc = shard_check(c, B)) return rc;
   return guarded(c, [&] { return diff_sample(c, latents, rows, B, n_steps, noise, noise_mode, mel_out); });
+}
+int tts_diffusion_multi_voice(tts_ctx *c, const float *latents, const int32_t *rows, int B, const float *voice_latents, int n_voices,
+                              const int32_t *voice_of_candidate, int n_steps, const float *noise, int noise_mode, float *mel_out) {
+  NEED_CTX(c);
+  if (B >= 1 && !noise && noise_mode == TTS_NOISE_DEVICE) if (int rc = shard_check(c, B)) return rc;
+  return guarded(c, [&] { return diff_sample_voices(c, latents, rows, B, voice_latents, n_voices, voice_of_candidate, n_steps, noise, noise_mode, mel_out); });
 }
 int tts_vocoder_samples(int T) { return (T + 10) * 256 - 6; }
 int tts_vocoder(tts_ctx *c, const float *mel, const int32_t *frames, int B, const float *noise, int noise_mode, float *audio) {

@@ -52,7 +52,7 @@ __device__ __forceinline__ float gelu_tanh(float x, int lut) {
 }
 
 // rows of the transformer input: out[r] = tabA[ia[r]] + tabB[ib[r]]  (ib < 0: no second term).
-// tables: 0 voice(1 row), 1 text_emb, 2 mel_emb ; 0 text_pos, 1 mel_pos.
+// tables: 0 voice(one row per voice of the batch), 1 text_emb, 2 mel_emb ; 0 text_pos, 1 mel_pos.
 struct EmbedTables { const float *a[3]; const float *b[2]; };
 __global__ __launch_bounds__(256) void embed_rows_kernel(EmbedTables t, const int4 *__restrict__ desc,
                                                          float *__restrict__ out) {
@@ -1279,6 +1279,7 @@ struct ArState {
   // Prompt groups: group g holds candidates [g_c0[g], g_c0[g] + g_n[g]) and the prompt tokens[g_t0[g] .. + g_ntext[g]). One group = the single-prompt
   // path of rounds 1-6 (multi = false); several: the decode step reads every row's context length from row_off (multi = true).
   std::vector<int> g_c0, g_n, g_t0, g_ntext;
+  std::vector<int> g_voice;  // group g's row of the voice table `voice` ([n_voices][1024]; the single-voice entry points: one row, all 0)
   bool multi = false;
   DevBuf row_off;            // multi: [tiles * 16] ints, P of the row's group (0 past the batch); the step state's n_past is then the step index
   DevBuf voice, kcache, vcache, lat_k, lat_v;
@@ -1969,11 +1970,20 @@ static int embed(tts_ctx *ctx, ArState *st, const std::vector<int4> &desc) {
 }
 
 // tts_ar_begin (one prompt, G = 1) and tts_ar_begin_multi (G prompts back to back in text_ids, group g with n_text[g] ids and n_cand[g] candidates).
-// Every argument is checked before anything changes.
-int ar_begin_groups(tts_ctx *ctx, const int32_t *text_ids, const int *n_text, int G, const float *voice, const int *n_cand, int max_steps) {
+// tts_ar_begin_multi_voice: `voice` is a table [n_voices][1024] and group g reads row voice_of[g] (voice_of == nullptr: row 0 for every group — the
+// single-voice entry points, n_voices = 1). Every argument is checked before anything changes.
+int ar_begin_groups(tts_ctx *ctx, const int32_t *text_ids, const int *n_text, int G, const float *voice, int n_voices, const int *voice_of, const int *n_cand,
+                    int max_steps) {
   ArState *st = ctx->ar;
   if (!st) return fail(ctx, TTS_ERR_STATE, "AR model not loaded");
   if (G < 1 || !n_text || !n_cand || max_steps < 1 || !text_ids || !voice) return fail(ctx, TTS_ERR_ARG, "tts_ar_begin: bad argument");
+  if (n_voices < 1 || n_voices > (1 << 20)) return fail(ctx, TTS_ERR_ARG, "tts_ar_begin: %d voices", n_voices);
+  if (voice_of) {
+    for (int g = 0; g < G; g++)
+      if (voice_of[g] < 0 || voice_of[g] >= n_voices) return fail(ctx, TTS_ERR_ARG, "tts_ar_begin: prompt %d names voice %d of %d", g, voice_of[g], n_voices);
+    for (size_t i = 0; i < (size_t)n_voices * D; i++)
+      if (!std::isfinite(voice[i])) return fail(ctx, TTS_ERR_ARG, "tts_ar_begin: voice %d holds a non-finite value", (int)(i / D));
+  }
   int B = 0, P_max = 0, T = 0;
   for (int g = 0; g < G; g++) {
     if (n_text[g] < 1 || n_cand[g] < 1) return fail(ctx, TTS_ERR_ARG, "tts_ar_begin: bad argument (prompt %d: %d ids, %d candidates)", g, n_text[g], n_cand[g]);
@@ -1989,14 +1999,16 @@ int ar_begin_groups(tts_ctx *ctx, const int32_t *text_ids, const int *n_text, in
   if (max_pos > 1024) return fail(ctx, TTS_ERR_LIMIT, "context of %d positions exceeds 1024", max_pos);
   st->B = 0; // (a failure below leaves no half-begun state behind)
   st->g_c0.assign(G, 0); st->g_n.assign(n_cand, n_cand + G); st->g_t0.assign(G, 0); st->g_ntext.assign(n_text, n_text + G);
+  st->g_voice.assign(G, 0);
+  if (voice_of) st->g_voice.assign(voice_of, voice_of + G);
   for (int g = 1; g < G; g++) { st->g_c0[g] = st->g_c0[g - 1] + n_cand[g - 1]; st->g_t0[g] = st->g_t0[g - 1] + n_text[g - 1]; }
   st->multi = G > 1;
   st->n_text = P_max - 2; st->P = P_max;
   st->prefill_done = false;
   st->max_pos = max_pos;
   st->tokens.assign(text_ids, text_ids + T);
-  TTS_HIP(ctx, st->voice.reserve(D * 4));
-  TTS_HIP(ctx, hipMemcpy(st->voice.p, voice, D * 4, hipMemcpyHostToDevice));
+  TTS_HIP(ctx, st->voice.reserve((size_t)n_voices * D * 4));
+  TTS_HIP(ctx, hipMemcpy(st->voice.p, voice, (size_t)n_voices * D * 4, hipMemcpyHostToDevice));
   size_t cache = (size_t)st->n_layers * B * st->max_pos * D * sizeof(__half);
   TTS_HIP(ctx, st->kcache.reserve(cache));
   TTS_HIP(ctx, st->vcache.reserve(cache));
@@ -2028,7 +2040,7 @@ int ar_begin_groups(tts_ctx *ctx, const int32_t *text_ids, const int *n_text, in
 }
 
 int ar_begin(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice, int B, int max_steps) {
-  return ar_begin_groups(ctx, text_ids, &n_text, 1, voice, &B, max_steps);
+  return ar_begin_groups(ctx, text_ids, &n_text, 1, voice, 1, nullptr, &B, max_steps);
 }
 
 // Prefill (main.cpp:2586-2665): [voice | text_emb+pos | mel_emb(8192)+mel_pos(0)] — identical for all
@@ -2038,7 +2050,7 @@ static int prefill_group(tts_ctx *ctx, ArState *st, int g) {
   const int n_text = st->g_ntext[g], P = n_text + 2, c0 = st->g_c0[g];
   const int *tok = st->tokens.data() + st->g_t0[g];
   std::vector<int4> desc(P);
-  desc[0] = make_int4(0, 0, -1, 0);
+  desc[0] = make_int4(0, st->g_voice[g], -1, 0); // the group's row of the voice table
   for (int i = 0; i < n_text; i++) desc[1 + i] = make_int4(1, tok[i], 0, i);
   desc[P - 1] = make_int4(2, 8192, 1, 0);
   CHECK(embed(ctx, st, desc));
@@ -2240,7 +2252,8 @@ __global__ __launch_bounds__(256) void copy_prompt_kv_kernel(const __half *__res
 // decode cache's position quirk. The 1 + n_text prompt rows are the same for every candidate and do not depend on the
 // mel rows (causal mask): their K/V rows are taken from the decode cache (written by the prompt pass), so the stack runs
 // over the mel rows only, with n_past = 1 + n_text. Several prompts: one such pass per group, over the group's own prompt (its first
-// candidate's cache rows) and n_mel.
+// candidate's cache rows) and n_mel. Several voices: position 0 of those cache rows was embedded from the group's own voice by its prompt pass, so the
+// latent pass reads the right voice without naming it.
 static int latents_check(tts_ctx *ctx, const ArState *st, int n_text, const int32_t *codes502, int nb, int n_mel) {
   if (nb < 1 || n_mel < 1 || n_mel > 502 || !codes502) return fail(ctx, TTS_ERR_ARG, "tts_ar_latents: bad argument");
   if (1 + n_text + n_mel > 1024) return fail(ctx, TTS_ERR_LIMIT, "latent pass of %d positions exceeds 1024", 1 + n_text + n_mel);

@@ -28,6 +28,13 @@
 //   packed greedily, include/tortoise_mi355x.h states the rule); all chunks run through ONE tts_autoregressive_multi call (--candidates per chunk), each
 //   chunk keeps candidate 0 (or the CLVP best with --clvp), one tts_diffusion and one tts_vocoder call run over the kept candidates, and their audio is
 //   written to --output one after the other as ONE file. A message that fits one chunk takes the path without the flag. Not with --devices > 1.
+// Several speakers: --voice (and --diffusion-latent) may be repeated, the k-th occurrence is voice k; one occurrence is the behaviour above. With more than one
+//   --voice the message is a dialogue (tts_split_turns: one turn per line, "<index>|" in front of a turn names its voice, a turn without it keeps the voice of the
+//   turn before, the first defaults to voice 0; --split-text N = ids per chunk inside a turn, default 404). Every chunk is a prompt group with its voice in ONE
+//   tts_autoregressive_multi_voice call (--candidates per chunk, --clvp per chunk), the kept candidates run through one tts_diffusion_multi_voice and one
+//   tts_vocoder call and their audio is written to --output in message order as ONE file. --diffusion-latent: none (every speaker uses the model's own latent)
+//   or one per --voice; anything else is a usage error (exit 1) before a model is loaded. Not with --devices > 1: the conditioning broadcast carries one voice.
+//   --dry-run 1 prints one line per chunk ("chunk k: voice v, n text ids") and exits 0.
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -62,9 +69,10 @@ int main(int argc, char **argv) {
   bool timing = false;
   int test_fail_shard = -1, test_slow_shard = -1;
   std::vector<std::pair<std::string, double>> engine_options; // --option key=value (repeatable): tts_set_option before the models are loaded
+  std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
   for (int i = 1; i < argc - 1; ++i) {
     std::string a(argv[i]);
-    if (a == "--voice") voicePath = argv[i + 1];
+    if (a == "--voice") { voicePath = argv[i + 1]; voicePaths.push_back(voicePath); }
     else if (a == "--message") message = argv[i + 1];
     else if (a == "--output") outputPath = argv[i + 1];
     else if (a == "--seed") { seed = std::stoi(argv[i + 1]); have_seed = true; }
@@ -88,7 +96,7 @@ int main(int argc, char **argv) {
       if (eq == std::string::npos) { fprintf(stderr, "--option %s: expected key=value\n", kv.c_str()); return 1; }
       engine_options.emplace_back(kv.substr(0, eq), std::atof(kv.c_str() + eq + 1));
     }
-    else if (a == "--diffusion-latent") diffLatentPath = argv[i + 1];
+    else if (a == "--diffusion-latent") { diffLatentPath = argv[i + 1]; diffLatentPaths.push_back(diffLatentPath); }
     else if (a == "--split-text") split_ids = std::stoi(argv[i + 1]);
     else if (a == "--rccl-id") rccl_id = argv[i + 1]; // worker mode (set by the parent)
     else if (a == "--shard") { // worker mode (set by the parent): "r/N"
@@ -103,6 +111,19 @@ int main(int argc, char **argv) {
     return 1;
   }
   if (split_ids < 0 || split_ids > 404) { fprintf(stderr, "--split-text %d: 0 (off) or 3 .. 404 text ids per chunk\n", split_ids); return 1; }
+  // several voices (usage errors before any model is loaded / any worker is started)
+  const int n_voices = std::max<int>(1, (int)voicePaths.size());
+  const bool multi_voice = n_voices > 1;
+  if (!diffLatentPaths.empty() && (int)diffLatentPaths.size() != n_voices) {
+    fprintf(stderr, "%d --diffusion-latent for %d --voice: give none (every speaker uses the model's own latent) or one per voice, in the same order\n",
+            (int)diffLatentPaths.size(), n_voices);
+    return 1;
+  }
+  if (multi_voice && (devices > 1 || exchange == "rccl" || shard >= 0)) {
+    fprintf(stderr, "several --voice cannot be combined with --devices > 1 or --exchange rccl (the conditioning broadcast carries one voice; one process runs all turns)\n");
+    return 1;
+  }
+  if (multi_voice && split_ids != 0 && split_ids < 3) { fprintf(stderr, "--split-text %d: 3 .. 404 text ids per chunk\n", split_ids); return 1; }
   if ((devices > 1 || exchange == "rccl") && shard < 0) { // parent: one worker process per GPU
     if (candidates % devices) { fprintf(stderr, "--candidates %d does not divide over --devices %d\n", candidates, devices); return 1; }
     std::vector<int> map;
@@ -234,7 +255,21 @@ int main(int argc, char **argv) {
   tokens.resize(n);
   // --split-text: the chunks' text ids (a message that fits one chunk keeps the path without the flag)
   std::vector<std::vector<int32_t>> chunk_tokens;
-  if (split_ids > 0) {
+  std::vector<int32_t> chunk_voice; // several --voice: the voice of every chunk (tts_split_turns: one turn per line, "<index>|" in front names its voice)
+  if (multi_voice) {
+    std::vector<int32_t> starts(message.size() + 1), lens(message.size() + 1), vo(message.size() + 1);
+    const int k = tts_split_turns(ctx, message.c_str(), n_voices, split_ids > 0 ? split_ids : 404, starts.data(), lens.data(), vo.data(), (int)starts.size());
+    if (k < 0) return die(ctx, "split-turns");
+    if (k == 0) { fprintf(stderr, "the message holds no text\n"); return 1; }
+    for (int c = 0; c < k; c++) {
+      std::vector<int32_t> t(4096);
+      const int m = tts_tokenize(ctx, message.substr(starts[c], lens[c]).c_str(), t.data(), (int)t.size());
+      if (m < 0) return die(ctx, "tokenize");
+      t.resize(m);
+      chunk_tokens.push_back(t);
+      chunk_voice.push_back(vo[c]);
+    }
+  } else if (split_ids > 0) {
     std::vector<int32_t> starts(message.size() + 1), lens(message.size() + 1);
     const int k = tts_split_text(ctx, message.c_str(), split_ids, starts.data(), lens.data(), (int)starts.size());
     if (k < 0) return die(ctx, "split-text");
@@ -247,12 +282,38 @@ int main(int argc, char **argv) {
     }
   }
   const int n_chunks = (int)chunk_tokens.size(); // 0: one prompt
+  const bool chunked = n_chunks > 1 || multi_voice; // the prompt-group path (several voices: also for a single chunk)
 
   std::vector<float> voice(1024);
   {
     std::ifstream f(voicePath, std::ios::binary);
     if (!f) { std::cerr << "Error: Unable to open file " << voicePath << std::endl; return 1; }
     f.read((char *)voice.data(), 1024 * sizeof(float));
+  }
+  // several voices: the table [n_voices][1024] in the order of the --voice arguments, and the diffusion latents [n_voices][2048] if given
+  std::vector<float> voices, diff_latents;
+  if (multi_voice) {
+    voices.resize((size_t)n_voices * 1024);
+    for (int v = 0; v < n_voices; v++) {
+      std::ifstream f(voicePaths[v], std::ios::binary);
+      if (!f || !f.read((char *)(voices.data() + (size_t)v * 1024), 1024 * sizeof(float))) {
+        std::cerr << "Error: Unable to read 1024 floats from " << voicePaths[v] << std::endl;
+        return 1;
+      }
+    }
+    diff_latents.resize(diffLatentPaths.size() * 2048);
+    for (size_t v = 0; v < diffLatentPaths.size(); v++) {
+      std::ifstream f(diffLatentPaths[v], std::ios::binary);
+      if (!f || !f.read((char *)(diff_latents.data() + v * 2048), 2048 * sizeof(float))) {
+        std::cerr << "Error: Unable to read 2048 floats from " << diffLatentPaths[v] << std::endl;
+        return 1;
+      }
+    }
+    if (dry) { // plumbing check without a device: the chunks and their voices
+      for (int c = 0; c < n_chunks; c++) printf("chunk %d: voice %d, %d text ids\n", c, chunk_voice[c], (int)chunk_tokens[c].size());
+      tts_destroy(ctx);
+      return 0;
+    }
   }
   RcclWorld world;
   const bool use_rccl = shard >= 0 && !rccl_id.empty();
@@ -323,15 +384,18 @@ int main(int argc, char **argv) {
   std::vector<int32_t> codes((size_t)B_all * 502), rows(B_all);
   std::vector<float> latents((size_t)B_all * 500 * 1024);
   const float *lat_in = latents.data();
-  if (n_chunks > 1) {
+  if (chunked) {
     // all chunks in one autoregressive pass (chunk c: candidates [c B_ar, (c + 1) B_ar)), then candidate 0 or the CLVP best of every chunk
     std::vector<int32_t> ids, n_text(n_chunks), n_cand(n_chunks, B_ar);
     for (int c = 0; c < n_chunks; c++) { ids.insert(ids.end(), chunk_tokens[c].begin(), chunk_tokens[c].end()); n_text[c] = (int)chunk_tokens[c].size(); }
     int32_t nsteps = 0;
     const unsigned ar_flags = (fixed_codes > 0 ? TTS_AR_MASK_STOP : 0) | (B_ar > 1 ? TTS_AR_RETIRE : 0);
-    if (tts_autoregressive_multi(ctx, ids.data(), n_text.data(), n_chunks, voice.data(), n_cand.data(), fixed_codes > 0 ? fixed_codes : 500, ar_flags,
-                                 codes.data(), rows.data(), latents.data(), &nsteps))
-      return die(ctx, "autoregressive");
+    const int rc_ar = multi_voice // every chunk is a prompt group with its turn's voice
+                          ? tts_autoregressive_multi_voice(ctx, ids.data(), n_text.data(), n_chunks, voices.data(), n_voices, chunk_voice.data(), n_cand.data(),
+                                                           fixed_codes > 0 ? fixed_codes : 500, ar_flags, codes.data(), rows.data(), latents.data(), &nsteps)
+                          : tts_autoregressive_multi(ctx, ids.data(), n_text.data(), n_chunks, voice.data(), n_cand.data(), fixed_codes > 0 ? fixed_codes : 500,
+                                                     ar_flags, codes.data(), rows.data(), latents.data(), &nsteps);
+    if (rc_ar) return die(ctx, "autoregressive");
     mark("autoregressive");
     printf("tokens sampled: %d (%d chunks)\n", nsteps, n_chunks);
     if (!clvpPath.empty() && tts_load_clvp(ctx, clvpPath.c_str())) return die(ctx, "clvp_model_load");
@@ -352,7 +416,11 @@ int main(int argc, char **argv) {
       const int b = c * B_ar + best;
       kept_rows[c] = rows[b];
       kept.insert(kept.end(), latents.begin() + lat_off[b] * 1024, latents.begin() + lat_off[b + 1] * 1024);
-      printf("chunk %d: %d text ids, candidate %d kept, %d latent rows, %d mel frames\n", c, n_text[c], best, rows[b], tts_diffusion_frames(rows[b]));
+      if (multi_voice)
+        printf("chunk %d: voice %d, %d text ids, candidate %d kept, %d latent rows, %d mel frames\n", c, chunk_voice[c], n_text[c], best, rows[b],
+               tts_diffusion_frames(rows[b]));
+      else
+        printf("chunk %d: %d text ids, candidate %d kept, %d latent rows, %d mel frames\n", c, n_text[c], best, rows[b], tts_diffusion_frames(rows[b]));
     }
     latents.swap(kept);
     rows = kept_rows;
@@ -405,7 +473,7 @@ int main(int argc, char **argv) {
   bg.t.join();
   if (rc_diff) { fprintf(stderr, "diffusion_model_load: %s\n", err_diff.c_str()); return 1; }
   mark("wait for the diffusion + vocoder loads");
-  if (!diffLatentPath.empty()) {
+  if (!diffLatentPath.empty() && !multi_voice) {
     std::vector<float> dl(2048);
     std::ifstream f(diffLatentPath, std::ios::binary);
     if (!f || !f.read((char *)dl.data(), 2048 * sizeof(float))) { std::cerr << "Error: Unable to read 2048 floats from " << diffLatentPath << std::endl; return 1; }
@@ -422,7 +490,11 @@ int main(int argc, char **argv) {
   audio.assign(audio_total, 0.f);
   // B == 1: the reference's exact RNG order (AR uniforms, x_T, per-step noise, vocoder noise)
   const int noise_mode = (total_candidates == 1) ? TTS_NOISE_REFERENCE : TTS_NOISE_DEVICE;
-  if (tts_diffusion(ctx, lat_in, rows.data(), B, steps, nullptr, noise_mode, mel.data())) return die(ctx, "diffusion");
+  // several voices with their own diffusion latents: kept candidate c is chunk c, conditioned on its turn's voice (without: the model's own latent for all)
+  if (multi_voice && !diff_latents.empty()
+          ? tts_diffusion_multi_voice(ctx, lat_in, rows.data(), B, diff_latents.data(), n_voices, chunk_voice.data(), steps, nullptr, noise_mode, mel.data())
+          : tts_diffusion(ctx, lat_in, rows.data(), B, steps, nullptr, noise_mode, mel.data()))
+    return die(ctx, "diffusion");
   mark("diffusion");
   if (tts_diffusion_time_mlp_retries(ctx) > 0) // only ever seen while another process shares the GPU (include/tortoise_mi355x.h)
     fprintf(stderr, "[tortoise] the timestep MLP was re-evaluated %d times before two evaluations agreed\n", tts_diffusion_time_mlp_retries(ctx));
@@ -475,7 +547,7 @@ int main(int argc, char **argv) {
         }
       }
     }
-  } else if (n_chunks > 1) { // --split-text: the chunks' audio one after the other, one file
+  } else if (chunked) { // --split-text / several voices: the chunks' audio one after the other, one file
     write_one(audio.data(), (int64_t)audio.size(), 0, true);
   } else {
     size_t off = 0;

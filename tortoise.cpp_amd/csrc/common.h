@@ -336,6 +336,9 @@ struct ArStopBook {
 };
 // tts_split_text's rule on a tokenizer: byte ranges {start, length} of the chunks of `message`
 std::vector<std::pair<int, int>> split_text(const Tokenizer &tok, const std::string &message, int max_ids);
+// tts_split_turns' rule: the chunks of a multi-speaker message (byte range in `message`, voice index); false: a turn names a voice >= n_voices
+struct TurnChunk { int start, len, voice; };
+bool split_turns(const Tokenizer &tok, const std::string &message, int n_voices, int max_ids, std::vector<TurnChunk> &out, long *bad_voice);
 int trimmed_latent_rows(const int32_t *codes502);   // trim_latents row count
 struct DiffSchedule {
   int n = 0;

@@ -148,15 +148,17 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(const float *__restrict__
 }
 
 // Same normalisation but f32 output with the conditioning-latent scale/shift: code_norm at the end of
-// the latent conditioner (main.cpp:3291-3319).
+// the latent conditioner (main.cpp:3291-3319). `ss` is a table of conditioning latents [n_voices][2048] and sequence s reads row seq_voice[s]
+// (tts_diffusion_multi_voice); seq_voice == nullptr: the one row of the loaded model for every sequence. The arithmetic per element does not depend on it.
 __global__ __launch_bounds__(256) void gn_apply_f32_kernel(const float *__restrict__ x, const int *__restrict__ row_seq,
                                                            const float2 *__restrict__ stats, const float *__restrict__ g,
                                                            const float *__restrict__ b, const float *__restrict__ ss,
-                                                           float *__restrict__ y) {
+                                                           const int *__restrict__ seq_voice, float *__restrict__ y) {
   const int r = blockIdx.x, c = threadIdx.x * 4, s = row_seq[r];
   float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
   if (s >= 0) {
     const float2 st = stats[s * 32 + (c >> 5)];
+    if (seq_voice) ss += (size_t)seq_voice[s] * 2 * C;
     float4 v = *(const float4 *)(x + (size_t)r * C + c);
     float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
@@ -943,6 +945,11 @@ struct DiffState {
   }
   DevBuf code_emb, ce, ce16, xt16, inp16, net, temb, e1, emb, ss_all, ss_chk, xbuf, xoff, noise, seq_src, lat_in16, out_ct;
   PinnedBuf noise_host; // reference-order noise drawn step by step beside the device loop (diff_sample)
+  // tts_diffusion_multi_voice: this call's conditioning latents [n_voices][2048] followed by the candidates' rows of them [B], ONE upload per call; mv_tab / mv_idx
+  // point into it while the call runs and are null otherwise (every other entry point reads cond_latent, which the call neither reads nor writes)
+  DevBuf mv_buf;
+  const float *mv_tab = nullptr;
+  const int *mv_idx = nullptr;
   ~DiffState() { drop_step_graph(); for (void *p : owned) (void)hipFree(p); }
   int n_res() const { return n_integ + n_main + n_tail; }
 };
@@ -1728,8 +1735,10 @@ static int latent_conditioner(tts_ctx *ctx, DiffState *st, const float *latents_
   CHECK(gemm(ctx, "diff_gemm", c3, ll));
   for (int i = 0; i < st->n_lc; i++) CHECK(attention_block(ctx, st, ll, wk, wk.X(), st->lc_attn[i], lc_ref));
   CHECK(gn_stats(ctx, ll, wk, wk.X()));
+  // the voice: the loaded model's latent for every sequence, or (tts_diffusion_multi_voice) this call's table and the sequences' rows of it — sequence s of
+  // the latent layout is candidate s
   gn_apply_f32_kernel<<<ll.rows, 256, 0, ctx->stream>>>(wk.X(), ll.d_row_seq.as<int>(), wk.stats.as<float2>(), st->code_g, st->code_b,
-                                                        st->cond_latent, wk.H());
+                                                        st->mv_tab ? st->mv_tab : st->cond_latent, st->mv_tab ? st->mv_idx : nullptr, wk.H());
   TTS_HIP(ctx, hipGetLastError());
   return TTS_OK;
 }
@@ -2114,6 +2123,35 @@ int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, 
     fprintf(stderr, "[tts timing] diffusion: setup %.1f ms, time MLP + noise %.1f, %d steps %.1f (issued in %.1f, graph capture + instantiate %.1f), mel copy %.1f\n",
             ms(t_begin, t_setup), ms(t_setup, t_pre), n_steps, ms(t_pre, t_loop), ms(t_pre, t_issued), t_capture, ms(t_loop, now()));
   return TTS_OK;
+}
+
+// tts_diffusion_multi_voice: tts_diffusion with candidate c conditioned on voice_latents[voice_of[c]] instead of the loaded model's latent. The voice enters the
+// stage at ONE place (the scale/shift of the code norm that ends latent_conditioner), and nothing is kept from one call to the next (the code embedding, h0 and the
+// hoisted integrator's ce16_all are rebuilt by every call from that call's conditioner output), so the table and the candidates' rows of it are all this adds:
+// one upload, no launch. The unconditioned sequences — the only ones share_uncond merges — never read a voice.
+int diff_sample_voices(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, const float *voice_latents, int n_voices, const int32_t *voice_of,
+                       int n_steps, const float *noise, int noise_mode, float *mel_out) {
+  DiffState *st = ctx->diff;
+  if (!st) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
+  if (!latents || !rows || !mel_out || B < 1 || n_steps < 2 || !voice_latents || !voice_of) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_multi_voice: bad argument");
+  if (n_voices < 1 || n_voices > (1 << 20)) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_multi_voice: %d voices", n_voices);
+  for (int c = 0; c < B; c++) {
+    if (rows[c] < 1 || rows[c] > 500) return fail(ctx, TTS_ERR_ARG, "latent rows %d out of range", rows[c]);
+    if (voice_of[c] < 0 || voice_of[c] >= n_voices)
+      return fail(ctx, TTS_ERR_ARG, "tts_diffusion_multi_voice: candidate %d names voice %d of %d", c, voice_of[c], n_voices);
+  }
+  const size_t nf = (size_t)n_voices * 2 * C;
+  for (size_t i = 0; i < nf; i++)
+    if (!std::isfinite(voice_latents[i])) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_multi_voice: voice %d holds a non-finite value", (int)(i / (2 * C)));
+  std::vector<float> up(nf + (size_t)B); // [n_voices][2048] floats | [B] ints
+  memcpy(up.data(), voice_latents, nf * 4);
+  memcpy(up.data() + nf, voice_of, (size_t)B * 4);
+  TTS_HIP(ctx, st->mv_buf.reserve(up.size() * 4));
+  TTS_HIP(ctx, hipMemcpy(st->mv_buf.p, up.data(), up.size() * 4, hipMemcpyHostToDevice));
+  struct Reset { DiffState *s; ~Reset() { s->mv_tab = nullptr; s->mv_idx = nullptr; } } reset{st}; // also when the call ends in an exception (api.cpp: guarded)
+  st->mv_tab = st->mv_buf.as<float>();
+  st->mv_idx = (const int *)(st->mv_buf.as<float>() + nf);
+  return diff_sample(ctx, latents, rows, B, n_steps, noise, noise_mode, mel_out);
 }
 
 } // namespace tts

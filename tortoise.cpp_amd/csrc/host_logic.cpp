@@ -864,6 +864,32 @@ std::vector<std::pair<int, int>> split_text(const Tokenizer &tok, const std::str
   return out;
 }
 
+// Turn splitter (tts_split_turns; the rule is stated in include/tortoise_mi355x.h): turns are the lines of the message, a turn that begins with
+// "<decimal index>|" (blanks in front of the digits allowed) speaks with that voice and the prefix is not text, a turn without one keeps the voice of the
+// turn before it (the first: voice 0); every turn's text then goes through split_text. Returns false for a voice index >= n_voices (*bad_voice says which).
+bool split_turns(const Tokenizer &tok, const std::string &msg, int n_voices, int max_ids, std::vector<TurnChunk> &out, long *bad_voice) {
+  const int n = (int)msg.size();
+  int voice = 0;
+  for (int a = 0; a <= n;) {
+    int b = a;
+    while (b < n && msg[b] != '\n') b++;
+    int p = a;
+    while (p < b && (msg[p] == ' ' || msg[p] == '\t')) p++;
+    int q = p;
+    long idx = 0;
+    while (q < b && msg[q] >= '0' && msg[q] <= '9') { idx = std::min(idx * 10 + (msg[q] - '0'), 1000000000L); q++; }
+    int text0 = a;
+    if (q > p && q < b && msg[q] == '|') {
+      if (idx >= n_voices) { if (bad_voice) *bad_voice = idx; return false; }
+      voice = (int)idx;
+      text0 = q + 1;
+    }
+    for (const std::pair<int, int> &c : split_text(tok, msg.substr(text0, b - text0), max_ids)) out.push_back({text0 + c.first, c.second, voice});
+    a = b + 1;
+  }
+  return true;
+}
+
 } // namespace tts
 
 // ---- host-logic probes: the host-side pieces of the stage drivers, callable without a GPU (tests/test_host_parity.py) ----
