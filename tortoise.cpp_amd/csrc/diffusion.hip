@@ -815,10 +815,11 @@ __global__ void rows_to_ct_kernel(const float *__restrict__ net, int row0, int T
 struct AttnDev {
   float *norm_g, *norm_b, *qkv_b, *proj_b, *bias_tab;
   __half *qkv_w, *proj_w;
+  __half *qkv_wf; // fragment-major image of qkv_w (gemm_f16.h: gemm_wfrag_index)
   __half *proj_w_split; // [C][hi(s w) | lo(s w)]: proj_out's F32 weight as a split-precision pair; s = 1 / proj_alpha keeps the low halves normal
   float proj_alpha;     // 1 / s, s = the largest power of two with max|W| s < 30000 (64 for |W| up to 468; round 6: was a fixed 64, whose hi half overflows at |W| > 1023)
 };
-struct ResDev { float *in_g, *in_b, *in_bias, *emb_w, *emb_b, *out_g, *out_b, *out_bias; __half *in_w, *out_w; };
+struct ResDev { float *in_g, *in_b, *in_bias, *emb_w, *emb_b, *out_g, *out_b, *out_bias; __half *in_w, *out_w, *in_wf; }; // in_wf: fragment-major image of in_w
 
 // Packed row layout: sequence s occupies rows [start[s], start[s]+len[s]); start % 8 == 0; at least one
 // zero guard row before and after every sequence; total padded to a multiple of 128.
@@ -994,7 +995,8 @@ struct Loader { // its jobs run on several threads (common.h: run_parallel): `us
     return put(t->data, dst);
   }
   // conv weight file layout w[(co*cin + ci)*k + tap] -> fp16 [co_pad][tap*cin_pad + ci] (zero padded)
-  int conv16(const std::string &name, int cout, int cin, int k, int cout_pad, int cin_pad, __half **dst) {
+  // dst_frag (k = 1 only): also the fragment-major image that gemm_f16_wreg_kernel streams into registers
+  int conv16(const std::string &name, int cout, int cin, int k, int cout_pad, int cin_pad, __half **dst, __half **dst_frag = nullptr) {
     const HostTensor *t = get(name, (int64_t)cout * cin * k);
     if (!t) return TTS_ERR_FORMAT;
     std::vector<__half> h((size_t)cout_pad * k * cin_pad, __float2half(0.f));
@@ -1003,13 +1005,19 @@ struct Loader { // its jobs run on several threads (common.h: run_parallel): `us
       for (int ci = 0; ci < cin; ci++)
         for (int tap = 0; tap < k; tap++)
           h[(size_t)co * k * cin_pad + (size_t)tap * cin_pad + ci] = __float2half_rn(w[((size_t)co * cin + ci) * k + tap]);
+    if (dst_frag) {
+      std::vector<__half> f(h.size());
+      for (int n = 0; n < cout_pad; n++)
+        for (int c = 0; c < cin_pad; c++) f[gemm_wfrag_index(n, c, cin_pad)] = h[(size_t)n * cin_pad + c];
+      if (int r = put(f, dst_frag)) return r;
+    }
     return put(h, dst);
   }
   int attn(const std::string &p, AttnDev &a) {
     int r;
     if ((r = f32(p + ".norm.weight", C, &a.norm_g))) return r;
     if ((r = f32(p + ".norm.bias", C, &a.norm_b))) return r;
-    if ((r = conv16(p + ".qkv.weight", 3 * C, C, 1, 3 * C, C, &a.qkv_w))) return r;
+    if ((r = conv16(p + ".qkv.weight", 3 * C, C, 1, 3 * C, C, &a.qkv_w, &a.qkv_wf))) return r;
     if ((r = f32(p + ".qkv.bias", 3 * C, &a.qkv_b))) return r;
     if ((r = conv16(p + ".proj_out.weight", C, C, 1, C, C, &a.proj_w))) return r;
     {
@@ -1058,7 +1066,7 @@ struct Loader { // its jobs run on several threads (common.h: run_parallel): `us
     int r;
     if ((r = f32(p + ".in_layers.0.weight", C, &w.in_g))) return r;
     if ((r = f32(p + ".in_layers.0.bias", C, &w.in_b))) return r;
-    if ((r = conv16(p + ".in_layers.2.weight", C, C, 1, C, C, &w.in_w))) return r;
+    if ((r = conv16(p + ".in_layers.2.weight", C, C, 1, C, C, &w.in_w, &w.in_wf))) return r;
     if ((r = f32(p + ".in_layers.2.bias", C, &w.in_bias))) return r;
     if ((r = f32(p + ".emb_layers.1.weight", 2 * C * C, &w.emb_w))) return r;
     if ((r = f32(p + ".emb_layers.1.bias", 2 * C, &w.emb_b))) return r;
@@ -1206,6 +1214,13 @@ static int gemm(tts_ctx *ctx, const char *fam, GemmArgs &g, const Layout &lay, i
     } else if (g.mode == GEMM_OUT_F16) CHECK(fp16_check(ctx, g.outH, (size_t)g.M * g.ldh));
   }
   return TTS_OK;
+}
+
+// option gemm_wreg (bit 0: k = 1 in_layers, bit 1: QKV projection): does this class stream its weight through registers (gemm_f16_wreg_kernel)
+static int gemm_wreg_class(const tts_ctx *ctx, int bit) { return (ctx->gemm_wreg & bit) ? 1 : 0; }
+// the image of a weight with a fragment-major copy that the GEMM of this layout will stream (for the GroupNorm's weight touch)
+static const __half *gemm_wreg_image(const tts_ctx *ctx, int bit, const Layout &lay, int N, const __half *w, const __half *wf) {
+  return gemm_wreg_class(ctx, bit) && gemm_auto_th(lay.rows, N) == 8 ? wf : w;
 }
 
 static GemmArgs gemm_base(const Layout &lay, const __half *A, int lda, int nseg, int kseg, const __half *W, int N,
@@ -1459,10 +1474,11 @@ static int gn(tts_ctx *ctx, const DiffState *st, const Layout &lay, const float 
 // st_x: statistics of x (nullptr: reduce them here); st_h_out: where the GEMM's epilogue leaves the statistics of H (nullptr: none) — option latency_mode
 static int res_in_layers(tts_ctx *ctx, const DiffState *st, const Layout &lay, Work &wk, const float *x, const ResDev &w, float *H,
                          const long long *st_x = nullptr, long long *st_h_out = nullptr) {
-  CHECK(gn(ctx, st, lay, x, st_x, w.in_g, w.in_b, nullptr, 1, wk.A16(), w.in_w, (size_t)C * C * 2));
+  CHECK(gn(ctx, st, lay, x, st_x, w.in_g, w.in_b, nullptr, 1, wk.A16(), gemm_wreg_image(ctx, 1, lay, C, w.in_w, w.in_wf), (size_t)C * C * 2));
   DBG_SUM("res.in gn", wk.A16(), (size_t)lay.rows * C * 2);
   GemmArgs g = gemm_base(lay, wk.A16(), C, 1, C, w.in_w, C, w.in_bias);
   g.mode = st_h_out ? GEMM_OUT_F32_STATS : GEMM_OUT_F32; g.outF = H; g.ldo = C; g.resid = nullptr;
+  g.Wf = w.in_wf; g.wreg = gemm_wreg_class(ctx, 1);
   g.st_out = st_h_out; g.st_stripe_ll = (int)st->gn_stripe_ll; g.chunk_seq = lay.d_chunk_seq.as<int>();
   CHECK(gemm(ctx, "diff_gemm", g, lay));
   DBG_SUM("res.in conv", H, (size_t)lay.rows * C * 4);
@@ -1483,13 +1499,14 @@ static int attention_block(tts_ctx *ctx, DiffState *st, const Layout &lay, Work 
   const bool f32 = ctx->attn_f32 != 0 || force_ref;
   const bool pw16 = !f32 && ctx->attn_proj_f16; // weight touch for the two GEMMs that follow: the proj_out matrix this mode will stream
   const bool lat = st->lat && wk.st_x != nullptr; // option latency_mode: X's statistics come from (and go to) the GEMM epilogues
-  CHECK(gn(ctx, st, lay, X, lat ? wk.st_x : nullptr, w.norm_g, w.norm_b, nullptr, 0, wk.A16(), w.qkv_w, (size_t)3 * C * C * 2, pw16 ? w.proj_w : w.proj_w_split,
+  CHECK(gn(ctx, st, lay, X, lat ? wk.st_x : nullptr, w.norm_g, w.norm_b, nullptr, 0, wk.A16(), gemm_wreg_image(ctx, 2, lay, 3 * C, w.qkv_w, w.qkv_wf), (size_t)3 * C * C * 2, pw16 ? w.proj_w : w.proj_w_split,
            (size_t)C * C * (pw16 ? 2 : 4)));
   long long *st_out = lat ? st->new_stats_slot() : nullptr;
   wk.st_x = st_out;
   DBG_SUM("attn gn", wk.A16(), (size_t)lay.rows * C * 2);
   GemmArgs g = gemm_base(lay, wk.A16(), C, 1, C, w.qkv_w, 3 * C, w.qkv_b);
   g.mode = f32 ? GEMM_OUT_QKV_SPLIT : GEMM_OUT_QKV;
+  g.Wf = w.qkv_wf; g.wreg = gemm_wreg_class(ctx, 2);
   g.outH = wk.qk16.as<__half>(); g.ldh = 2048; g.outVt = wk.vt16.as<__half>(); g.ldvt = wk.rows + 128;
   g.outH2 = wk.qk16_lo.as<__half>(); g.outVt2 = wk.vt16_lo.as<__half>();
   CHECK(gemm(ctx, "diff_gemm", g, lay));

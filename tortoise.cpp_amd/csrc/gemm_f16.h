@@ -9,12 +9,17 @@
 // packed along M with a zero guard row between them, so a k=3 convolution needs no im2col and no
 // boundary masking) or one half of a channel concat (two buffers, offset 0).
 //
-// Two kernels, both (16 h) x 128 x 64 tiles (h = 1..8 sixteen-row blocks, a launch parameter), 4 waves (2 x 2), operands staged
+// Kernels, all (16 h) x 128 x 64 tiles (h = 1..8 sixteen-row blocks, a launch parameter), 4 waves (2 x 2), operands staged
 // by direct global->LDS DMA (global_load_lds_dwordx4) into a lane-linear image whose 16-byte chunks are
 // XOR-swizzled by (row>>1)&7 on the SOURCE address, so ds_read_b128 fragment reads spread over all banks:
 //   gemm_f16_vh_kernel        any segment structure; one LDS stage, 4 workgroups per CU overlap each other
 //   gemm_f16_conv3_vh_kernel  the k=3 convolution: one activation slab shared by the three taps, weight tiles
 //                             double-buffered (counted vmcnt + raw barriers)
+//   gemm_f16_wreg_kernel      one K segment, 128-row tiles, F32 / QKV outputs (the k = 1 in_layers convolution and the QKV projection at the benchmark's batch): the WEIGHT
+//                             operand never touches LDS — each wave loads its MFMA fragments from a fragment-major image built at load time, one K tile ahead; LDS is a
+//                             two-slot ring of activation tiles, one raw barrier per K tile. Bit-identical to gemm_f16_vh_kernel. Measured against it in the benchmark
+//                             (profiles/gemm_wreg_same_box_ab.txt): QKV projection 183.0 -> 170.9 us, in_layers 82.2 -> 73.6 us, headline +1.7 %. Adopted for both
+//                             classes (option gemm_wreg); the dual-B and k = 3 kernels were not ported, and a two-tile distance is not instantiated (see the kernel).
 // launch_gemm_f16 picks between them and chooses h. Round 3 rewrote both around two measurements
 // (profiles/r3_gemm_tile_tables.txt, profiles/r3_gemm_epilogue.txt):
 //  * tile-height / dispatch-order policies (tables of mixed heights, tallest-first, whole rounds filled exactly) change nothing:
@@ -57,6 +62,8 @@ struct GemmArgs {
   int lda;             // halves
   const __half *W;     // [N][ldw]; segment seg starts at column w_off[seg] (defaults: ldw = nseg*kseg, w_off = seg*kseg)
   int ldw_, w_off_[3], custom_w; // set custom_w = 1 to use ldw_/w_off_ (e.g. split-precision: hi|lo halves reused)
+  const __half *Wf;    // the fragment-major image of W (gemm_wfrag_index), or nullptr
+  int wreg;            // 1 with Wf: stream the weight through registers where gemm_f16_wreg_kernel takes the shape
   int M, N;            // multiples of 128 (buffers are padded)
   const float *bias;   // [N] or nullptr
   const int *row_seq;  // [M]: sequence id, <0 for guard/padding rows (output forced to 0); may be null
@@ -574,6 +581,240 @@ static __global__ __launch_bounds__(256, KU == 1 ? 3 : 1) void gemm_f16_vh_dualb
   else gemm_vh_dualb_body<MODE, 0, KU>(g, m0, n0, nblk, lane, wave);
 }
 
+// Weight operand through REGISTERS (gemm_f16_wreg_kernel; one K segment, 128-row tiles, F32 / QKV outputs). The weight is constant from load time on, so the loader
+// stores a second, fragment-major image of it:
+//   Wf[n / 16][k / 32][lane = ((k % 32) / 8) * 16 + n % 16][k % 8]
+// = the 8 halves lane (fr, fq) of a v_mfma_f32_16x16x32_f16 weight fragment holds, W[n0 + fr][k0 + 8 fq ..] — the same register contents in the swapped and in the
+// natural operand order — so one fragment is one fully coalesced 1 KB global_load_dwordx4 per wave and never touches LDS. The four waves lie 1 x 4 along N: wave w owns
+// all rows of the tile x columns 32 w .. 32 w + 31, no weight fragment is fetched twice. LDS holds only activation tiles, as a ring of D + 1 slots of 16 KB filled by
+// LDS-DMA D K tiles ahead; the weight fragments of those D tiles wait in registers (16 per tile). ONE raw barrier per K tile:
+//   wait (counted vmcnt) for tile t  ->  barrier (every wave has also left tile t - 1)  ->  request tile t + D into the slot / registers of tile t - 1  ->  multiply tile t.
+// vmcnt is one in-order counter for the DMA pieces and the register loads: a wave issues exactly MI / 2 + 4 of them per K tile (DMA rows past a short tile are clamped,
+// not skipped), so "all but the youngest D - 1 tiles" is one immediate. The register loads are inline asm: beside an LDS-DMA in flight hipcc waits vmcnt(0) for every
+// ordinary VGPR-destination load; their destinations are named by the wait statement ("+v") so that no consumer is scheduled above it.
+// Every accumulator adds the same products in the same K order through the same instruction and operand order as gemm_vh_body: bit-identical outputs.
+static inline size_t gemm_wfrag_index(int n, int k, int K) { // index (in halves) of W[n][k] in the fragment-major image
+  return ((((size_t)(n >> 4) * (K >> 5) + (k >> 5)) * 64 + ((k >> 3) & 3) * 16 + (n & 15)) << 3) + (k & 7);
+}
+
+// wave-uniform base (SGPR pair) + the lane's 32-bit byte offset: no 64-bit address registers
+template <int OFF> __device__ __forceinline__ void wreg_load(half8 &d, const __half *base, unsigned voff) {
+  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(d) : "v"(voff), "s"(base), "i"(OFF));
+}
+template <int N> __device__ __forceinline__ void wreg_wait(half8 &a, half8 &b, half8 &c, half8 &d) {
+  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "i"(N) : "memory");
+}
+
+// acc[i][j]: 16-row block i of the tile, columns n0 + 32 wave + 16 j ..; only blocks i < nblk are stored
+template <int MODE, int MI, bool NAT>
+__device__ __forceinline__ void gemm_epilogue_wreg(const GemmArgs &g, floatx4 (&acc)[MI][2], int m0, int n0, int nblk, int wave, int fr, int fq) {
+  const int c0 = n0 + wave * 32;
+  const bool hb = g.bias != nullptr, hs = g.row_seq != nullptr;
+  const float *bp = hb ? g.bias : (const float *)g.W;   // unconditional loads, values selected afterwards (see gemm_epilogue_vh)
+  const int *sp = hs ? g.row_seq : (const int *)g.A[0];
+  if (NAT) {
+    const int h = c0 / 192, w0 = c0 - h * 192;
+    { // V, natural operand order: acc[i][j][r] = C[m0 + 16 i + 4 fq + r][c0 + 16 j + fr]
+      float bv[2];
+      int4 sq[MI];
+#pragma unroll
+      for (int j = 0; j < 2; j++) bv[j] = bp[c0 + j * 16 + fr];
+#pragma unroll
+      for (int i = 0; i < MI; i++) sq[i] = *(const int4 *)(sp + m0 + min(i, nblk - 1) * 16 + fq * 4);
+#pragma unroll
+      for (int j = 0; j < 2; j++) bv[j] = hb ? bv[j] : 0.f;
+#pragma unroll
+      for (int i = 0; i < MI; i++) sq[i] = hs ? sq[i] : make_int4(0, 0, 0, 0);
+#pragma unroll
+      for (int i = 0; i < MI; i++) {
+        if (i < nblk) {
+          const int rbase = m0 + i * 16 + fq * 4;
+          const bool gd[4] = {sq[i].x < 0, sq[i].y < 0, sq[i].z < 0, sq[i].w < 0};
+#pragma unroll
+          for (int j = 0; j < 2; j++) {
+            float v[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) v[r] = gd[r] ? 0.f : acc[i][j][r] + bv[j];
+            const size_t o = (size_t)(h * 64 + (w0 - 128) + j * 16 + fr) * g.ldvt + rbase;
+            *(uint2 *)(g.outVt + o) = pack_half4(v[0], v[1], v[2], v[3]);
+            if (MODE == GEMM_OUT_QKV_SPLIT) *(uint2 *)(g.outVt2 + o) = pack_half4(split_lo(v[0]), split_lo(v[1]), split_lo(v[2]), split_lo(v[3]));
+          }
+        }
+      }
+      return;
+    }
+  }
+  // swapped operand order: acc[i][j][r] = C[m0 + 16 i + fr][c0 + 16 j + 4 fq + r]
+  const int col0 = c0 + fq * 4;
+  float4 b4[2];
+  int sq[MI];
+#pragma unroll
+  for (int j = 0; j < 2; j++) b4[j] = *(const float4 *)(bp + col0 + j * 16);
+#pragma unroll
+  for (int i = 0; i < MI; i++) sq[i] = sp[m0 + min(i, nblk - 1) * 16 + fr];
+#pragma unroll
+  for (int j = 0; j < 2; j++) b4[j] = hb ? b4[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int i = 0; i < MI; i++) sq[i] = hs ? sq[i] : 0;
+  auto finish = [&](int i, int j) { // bias, guard: the adds of gemm_epilogue_vh
+    float4 v = make_float4(acc[i][j][0] + b4[j].x, acc[i][j][1] + b4[j].y, acc[i][j][2] + b4[j].z, acc[i][j][3] + b4[j].w);
+    if (sq[i] < 0) v = make_float4(0.f, 0.f, 0.f, 0.f);
+    return v;
+  };
+  if (MODE == GEMM_OUT_F32) {
+#pragma unroll
+    for (int i = 0; i < MI; i++) {
+      if (i < nblk) {
+        float *op = g.outF + (size_t)(m0 + i * 16 + fr) * g.ldo + col0;
+#pragma unroll
+        for (int j = 0; j < 2; j++) *(float4 *)(op + j * 16) = finish(i, j);
+      }
+    }
+  } else { // Q or K columns of the QKV projection
+    const int h = c0 / 192, w0 = c0 - h * 192;
+#pragma unroll
+    for (int i = 0; i < MI; i++) {
+      if (i < nblk) {
+        __half *op = g.outH + (size_t)(m0 + i * 16 + fr) * g.ldh + h * 128 + w0 + fq * 4;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          const float4 v = finish(i, j);
+          *(uint2 *)(op + j * 16) = pack_half4(v.x, v.y, v.z, v.w);
+          if (MODE == GEMM_OUT_QKV_SPLIT)
+            *(uint2 *)(g.outH2 + (op - g.outH) + j * 16) = pack_half4(split_lo(v.x), split_lo(v.y), split_lo(v.z), split_lo(v.w));
+        }
+      }
+    }
+  }
+}
+
+// NAT: this wave's columns are V columns of a QKV projection (natural operand order). A template parameter of the whole body, not of the K loop alone: with two K loops in one
+// function hipcc spills the weight registers inside both (seen in the ISA)
+template <int MODE, int MI, int D, bool NAT>
+__device__ __forceinline__ void gemm_wreg_body(const GemmArgs &g, int m0, int n0, int nblk, int lane, int wave) {
+  extern __shared__ __attribute__((aligned(16))) char smem_dyn[]; // ONE LDS object (see gemm_vh_body)
+  char *smem = smem_dyn;
+  constexpr int S = D + 1;            // ring slots = weight register sets
+  constexpr int NPA = MI / 2;         // DMA pieces (8 rows) per wave and K tile
+  constexpr int PER = NPA + 4;        // vmcnt events per wave and K tile
+  static_assert(D == 1 || D == 2, "prefetch distance");
+  const int T = g.kseg >> 6, KS = g.kseg >> 5;
+  const int prow = lane >> 3, pslot = lane & 7;
+  const int fr = lane & 15, fq = lane >> 4;
+  unsigned aoff[NPA]; // byte offsets from a wave-uniform base: the DMA takes the SGPR-base addressing form
+#pragma unroll
+  for (int i = 0; i < NPA; i++) {
+    const int row = (wave + 4 * i) * 8 + prow; // LDS row; the source row is clamped into the tile (short tiles: duplicates, never stored)
+    aoff[i] = (unsigned)((min(row, nblk * 16 - 1) * g.lda + (pslot ^ lds_swz(row)) * 8) * 2);
+  }
+  const char *aseg = (const char *)(g.A[0] + (ptrdiff_t)(g.row_off[0] + m0) * g.lda);
+  const __half *wp0 = g.Wf + (size_t)((n0 >> 4) + wave * 2) * KS * 512, *wp1 = wp0 + (size_t)KS * 512; // wave-uniform
+  const unsigned wlane = lane * 16;
+  const bool resid_first = MODE == GEMM_OUT_F32 && g.resid != nullptr;
+  floatx4 acc[MI][2];
+  if (resid_first) { // accumulators start from the residual, as in gemm_vh_body
+#pragma unroll
+    for (int i = 0; i < MI; i++) {
+      const int row = m0 + min(i, nblk - 1) * 16 + fr;
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        const float4 rr = *(const float4 *)(g.resid + (size_t)row * g.ldo + n0 + wave * 32 + j * 16 + fq * 4);
+        acc[i][j] = (floatx4){rr.x, rr.y, rr.z, rr.w};
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < MI; i++)
+#pragma unroll
+      for (int j = 0; j < 2; j++) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+  }
+  half8 w[S][2][2]; // [set][k step][column block]
+  auto issue = [&](int t, auto set_c) {
+    constexpr int U = decltype(set_c)::value;
+    const char *ab = aseg + (t << 7);
+#pragma unroll
+    for (int i = 0; i < NPA; i++) __builtin_amdgcn_global_load_lds((gptr_t)(ab + aoff[i]), (lptr_t)(smem + U * 16384 + (wave + 4 * i) * 1024), 16, 0, 0);
+    const __half *q0 = wp0 + (size_t)t * 1024, *q1 = wp1 + (size_t)t * 1024;
+    wreg_load<0>(w[U][0][0], q0, wlane);
+    wreg_load<0>(w[U][0][1], q1, wlane);
+    wreg_load<1024>(w[U][1][0], q0, wlane);
+    wreg_load<1024>(w[U][1][1], q1, wlane);
+  };
+  auto kloop = [&]() {
+    auto step = [&](int t, auto u_c) {
+      constexpr int U = decltype(u_c)::value;
+      // tile t has landed: everything but the younger tiles already requested (t + 1 .. t + D - 1, where they exist)
+      if (D == 2 && t + 1 < T) wreg_wait<PER>(w[U][0][0], w[U][0][1], w[U][1][0], w[U][1][1]);
+      else wreg_wait<0>(w[U][0][0], w[U][0][1], w[U][1][0], w[U][1][1]);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // this wave's fragment reads of tile t - 1 are complete
+      __builtin_amdgcn_s_barrier();
+      if (t + D < T) issue(t + D, std::integral_constant<int, (U + D) % S>{});
+      const char *sa = smem + U * 16384;
+      // activation fragments one at a time, AHEAD fragments ahead of the MFMA pair that consumes them (the register budget has no room for a K step's worth)
+      constexpr int AHEAD = 2;
+      half8 af[AHEAD + 1];
+      auto frag = [&](int x) { return *(const half8 *)(sa + lds_off((x % MI) * 16 + fr, (x / MI) * 4 + fq)); }; // x = ks * MI + i
+#pragma unroll
+      for (int x = 0; x < AHEAD; x++) af[x] = frag(x);
+#pragma unroll
+      for (int x = 0; x < 2 * MI; x++) {
+        if (x + AHEAD < 2 * MI) af[(x + AHEAD) % (AHEAD + 1)] = frag(x + AHEAD);
+        const int ks = x / MI, i = x % MI;
+        const half8 a = af[x % (AHEAD + 1)];
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          if (NAT) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, w[U][ks][j], acc[i][j], 0, 0, 0);
+          else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[U][ks][j], a, acc[i][j], 0, 0, 0);
+        }
+      }
+      // keep that order: hipcc's scheduler otherwise sinks every read to its consumers (one fragment register set, the LDS latency exposed 2 MI times per tile)
+      __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 0);
+#pragma unroll
+      for (int x = 0; x < 2 * MI; x++) {
+        if (x + AHEAD < 2 * MI) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      }
+    };
+    for (int t0 = 0; t0 < T; t0 += S) {
+      step(t0, std::integral_constant<int, 0>{});
+      if (t0 + 1 < T) step(t0 + 1, std::integral_constant<int, 1>{});
+      if (S == 3 && t0 + 2 < T) step(t0 + 2, std::integral_constant<int, S - 1>{});
+    }
+  };
+  issue(0, std::integral_constant<int, 0>{});
+  if (D == 2) issue(1, std::integral_constant<int, 1>{}); // T >= D (checked by the launcher)
+  // Retire the residual loads HERE (a use makes hipcc place its wait now): pending at the loop they would force a wait in front of the first MFMA of every tile
+#pragma unroll
+  for (int i = 0; i < MI; i++)
+#pragma unroll
+    for (int j = 0; j < 2; j++) asm volatile("" : "+v"(acc[i][j]));
+  kloop();
+  gemm_epilogue_wreg<MODE, MI, NAT>(g, acc, m0, n0, nblk, wave, fr, fq);
+}
+
+// D = 1: a two-slot ring, 32 KB, 4 workgroups per CU with 128 registers per wave (126 used, no spill; the loop waits vmcnt(0) once per tile, which is exact at this distance:
+// nothing younger is in flight). D = 2 (three slots, 3 workgroups per CU) compiles to a loop that rotates the weight register sets through v_mov copies — copies of
+// inline-asm load destinations that may not have landed — and is therefore not instantiated.
+static constexpr int GEMM_WREG_D = 1, GEMM_WREG_LDS = (GEMM_WREG_D + 1) * 16384;
+template <int MODE, int D = GEMM_WREG_D>
+static __global__ __launch_bounds__(256, 4) void gemm_f16_wreg_kernel(GemmArgs g) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int m0, n0, nblk;
+  if (!gemm_vh_tile(g, m0, n0, nblk)) return;
+  if (gemm_mode_qkv(MODE) && ((n0 + wave * 32) % 192) >= 128) { // wave-uniform; every body passes the same barriers
+    if (nblk > 4) gemm_wreg_body<MODE, 8, D, true>(g, m0, n0, nblk, lane, wave);
+    else gemm_wreg_body<MODE, 4, D, true>(g, m0, n0, nblk, lane, wave);
+  } else {
+    if (nblk > 4) gemm_wreg_body<MODE, 8, D, false>(g, m0, n0, nblk, lane, wave);
+    else gemm_wreg_body<MODE, 4, D, false>(g, m0, n0, nblk, lane, wave);
+  }
+}
+// the shapes gemm_f16_wreg_kernel takes (launch_gemm_f16 has chosen th and ku)
+static inline bool gemm_takes_wreg(const GemmArgs &g, int th, int ku) {
+  return g.wreg > 0 && g.Wf && !g.tiles && g.nseg == 1 && !g.custom_w && th == 8 && ku == 1 && (g.kseg >> 6) >= 2 &&
+         (g.mode == GEMM_OUT_F32 || g.mode == GEMM_OUT_QKV || g.mode == GEMM_OUT_QKV_SPLIT);
+}
+
 // k = 3 convolution as ONE GEMM with a shared activation slab. The three taps are three row-shifted GEMM
 // segments over the SAME activation rows (row_off = -1, 0, +1), so per 64-channel chunk the kernel stages the
 // 16 nblk + 2 activation rows m0-1 .. once and multiplies them three times, each time against that tap's weight
@@ -684,6 +925,14 @@ static inline bool gemm_is_conv3(const GemmArgs &g) {
          !gemm_mode_qkv(g.mode) && !gemm_mode_scaled(g.mode);
 }
 
+// tile height (16-row blocks) launch_gemm_f16 chooses for an M x N problem
+static inline int gemm_auto_th(int M, int N) {
+  const int maxb = ((M >> 4) + 7) / 8 + 1, NT = N >> 7;
+  int th = 2;
+  while (th < 8 && 8 * ((maxb + th - 1) / th) * NT > 1024) th *= 2;
+  return th;
+}
+
 static inline hipError_t launch_gemm_f16(const GemmArgs &g, hipStream_t s) {
   GemmArgs gg = g;
   const int NT = g.N >> 7, ktot = g.nseg * g.kseg, nb = g.M >> 4;
@@ -713,7 +962,7 @@ static inline hipError_t launch_gemm_f16(const GemmArgs &g, hipStream_t s) {
     const int maxb = (nb + 7) / 8 + 1; // blocks of the largest XCD range (upper bound)
     auto tiles_at = [&](int h) { return 8 * ((maxb + h - 1) / h) * NT; };
     int th = g.th;
-    if (th <= 0) { th = 2; while (th < 8 && tiles_at(th) > 1024) th *= 2; }
+    if (th <= 0) th = gemm_auto_th(g.M, g.N);
     // One utterance (M = 1 792 rows, N = 1 024: 224 tiles of 64 rows = at most one workgroup per CU): four K tiles per barrier pair at 64-row tiles — a lone
     // workgroup pays its DMA round trip and two barriers per 256 of K instead of per 64 (profiles/r6_small_gemm.txt: k = 1 12.6 -> 11.6 us warm, 22.8 -> 17.9 us
     // with cold weights; the K = 2 048 integrating conv 25.7 / 36.2 -> 20.3 / 27.8). Same products in the same order: bit-identical to every other tiling.
@@ -731,7 +980,11 @@ static inline hipError_t launch_gemm_f16(const GemmArgs &g, hipStream_t s) {
     }
     grid = 8 * mt_max * NT;
   }
-  if (gemm_is_conv3(g)) {
+  if (gemm_takes_wreg(g, gg.th, ku)) {
+    if (g.mode == GEMM_OUT_F32) gemm_f16_wreg_kernel<GEMM_OUT_F32><<<grid, 256, GEMM_WREG_LDS, s>>>(gg);
+    else if (g.mode == GEMM_OUT_QKV) gemm_f16_wreg_kernel<GEMM_OUT_QKV><<<grid, 256, GEMM_WREG_LDS, s>>>(gg);
+    else gemm_f16_wreg_kernel<GEMM_OUT_QKV_SPLIT><<<grid, 256, GEMM_WREG_LDS, s>>>(gg);
+  } else if (gemm_is_conv3(g)) {
     static bool attr = false;
     if (!attr) {
       (void)hipFuncSetAttribute((const void *)gemm_f16_conv3_vh_kernel<GEMM_OUT_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, CONV3_VH_LDS);
