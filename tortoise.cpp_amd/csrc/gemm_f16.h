@@ -9,18 +9,22 @@
 // packed along M with a zero guard row between them, so a k=3 convolution needs no im2col and no
 // boundary masking) or one half of a channel concat (two buffers, offset 0).
 //
-// Kernels, all (16 h) x 128 x 64 tiles (h = 1..8 sixteen-row blocks, a launch parameter), 4 waves (2 x 2), operands staged
-// by direct global->LDS DMA (global_load_lds_dwordx4) into a lane-linear image whose 16-byte chunks are
-// XOR-swizzled by (row>>1)&7 on the SOURCE address, so ds_read_b128 fragment reads spread over all banks:
-//   gemm_f16_vh_kernel        any segment structure; one LDS stage, 4 workgroups per CU overlap each other
-//   gemm_f16_conv3_vh_kernel  the k=3 convolution: one activation slab shared by the three taps, weight tiles
-//                             double-buffered (counted vmcnt + raw barriers)
-//   gemm_f16_wreg_kernel      one K segment, 128-row tiles, F32 / QKV outputs (the k = 1 in_layers convolution and the QKV projection at the benchmark's batch): the WEIGHT
-//                             operand never touches LDS — each wave loads its MFMA fragments from a fragment-major image built at load time, one K tile ahead; LDS is a
-//                             two-slot ring of activation tiles, one raw barrier per K tile. Bit-identical to gemm_f16_vh_kernel. Measured against it in the benchmark
+// Kernels. All of them: (16 h) x 128 x 64 tiles (h = 1..8 sixteen-row blocks, a launch parameter), 4 waves, the tile walk of gemm_vh_tile, operands staged
+// by direct global->LDS DMA (global_load_lds_dwordx4) into a lane-linear image whose 16-byte chunks are XOR-swizzled on the SOURCE
+// address, so ds_read_b128 fragment reads spread over all banks, f32 accumulators that may start from the residual, and one epilogue family (gemm_epilogue_vh for the
+// 2 x 2 kernels, its copy gemm_epilogue_wreg for the 1 x 4 layout). gemm_dma_off gives the DMA offsets of the vh, dual-B and wreg bodies and gemm_acc_start the
+// accumulator start of the vh and wreg bodies; the dual-B start, the k = 3 offsets, the dual-B body and the wreg epilogue are copies, kept apart for the registers
+// unifying them cost (see the comment at each; profiles/gemm_refactor_isa.txt). The three 2 x 2 kernels run one body per number of 16-row blocks of the calling
+// wave (gemm_for_my_mi). What differs:
+//   gemm_f16_vh_kernel        any segment structure; one LDS stage, 4 workgroups per CU overlap each other; KU K tiles per barrier pair for small problems
+//   gemm_f16_vh_dualb_kernel  the hi | lo halves of ONE weight over one activation operand: both weight tiles of a K tile staged side by side, every A fragment feeds two products
+//   gemm_f16_conv3_vh_kernel  the k=3 convolution: one activation slab shared by the three taps, weight tiles double-buffered (counted vmcnt + raw barriers)
+//   gemm_f16_wreg_kernel      one K segment, 128-row tiles, F32 / QKV outputs (the k = 1 in_layers convolution and the QKV projection at the benchmark's batch): waves 1 x 4,
+//                             the WEIGHT operand never touches LDS — each wave loads its MFMA fragments from a fragment-major image built at load time, one K tile ahead;
+//                             LDS is a two-slot ring of activation tiles, one raw barrier per K tile. Bit-identical to gemm_f16_vh_kernel. Measured against it in the benchmark
 //                             (profiles/gemm_wreg_same_box_ab.txt): QKV projection 183.0 -> 170.9 us, in_layers 82.2 -> 73.6 us, headline +1.7 %. Adopted for both
 //                             classes (option gemm_wreg); the dual-B and k = 3 kernels were not ported, and a two-tile distance is not instantiated (see the kernel).
-// launch_gemm_f16 picks between them and chooses h. Round 3 rewrote both around two measurements
+// gemm_plan picks between them and chooses h; launch_gemm_f16 launches what it says. Round 3 rewrote the kernels around two measurements
 // (profiles/r3_gemm_tile_tables.txt, profiles/r3_gemm_epilogue.txt):
 //  * tile-height / dispatch-order policies (tables of mixed heights, tallest-first, whole rounds filled exactly) change nothing:
 //    a partially filled round runs proportionally faster, the launch is bound by total work, not by rounds;
@@ -28,9 +32,9 @@
 //    residual load under a runtime `ptr ? load : 0` select is branched around by hipcc and waited for with vmcnt(0) — which also
 //    waits for the previous block's stores (one in-order counter). Every epilogue load is now issued up front, unconditionally,
 //    and the stores follow back to back.
-// Measured-and-rejected variants: tools/ (gemm_f16_onetile.h = the round-2 kernels, gemm_f16_experiments.h, gemm_f16_big.h = the 256-column
-// 8-phase kernel of round 3: one workgroup per CU, two wave groups in strict alternation — 94 vs 78 us on in_layers, 238 vs 204 on the QKV
-// projection, per-phase timeline in profiles/r3_gemm_256col_kernel.txt).
+// Measured and rejected (the sources are in git history): the one-tile kernels of round 2, and the 256-column 8-phase kernel of round 3 (one workgroup per CU, two
+// wave groups in strict alternation — 94 vs 78 us on in_layers, 238 vs 204 on the QKV projection, per-phase timeline in profiles/r3_gemm_256col_kernel.txt). A 2-D XCD
+// partition through explicit per-XCD tile tables (round 6, profiles/r6_gemm_xcd2d.txt) changed no launch time; the table path left the kernels with its probe.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
@@ -79,11 +83,9 @@ struct GemmArgs {
   const int *chunk_seq;    //                   [M / 8]: owning sequence of an aligned 8-row chunk (sequences start at multiples of 8 rows), -1 = guard rows only
   int dual_b;              // 1: the two segments are the hi / lo halves of ONE weight over ONE activation operand -> gemm_f16_vh_dualb_kernel (GEMM_OUT_F32_SCALED only)
   int mode;
-  // tile walk, set by launch_gemm_f16: th = 16-row blocks per tile (0: chosen from the problem size), cn = column tiles per L2 chunk
+  // tile walk, set by launch_gemm_f16 from gemm_plan: th = 16-row blocks per tile (0: chosen from the problem size), cn = column tiles per L2 chunk
   int th, cn;
   int ku; // K tiles per barrier pair of gemm_f16_vh_kernel (0 / 1: one; 2, 4: small problems, set by launch_gemm_f16 or a tool)
-  // developer tools only (tools/gemm_tab_bench.hip): explicit per-XCD tile lists [8][tab_len] of {first row, blocks, first column, 0}
-  const int4 *tiles; int tab_len;
 };
 
 
@@ -341,11 +343,54 @@ __device__ __forceinline__ void gemm_epilogue_vh(const GemmArgs &g, floatx4 (&ac
   }
 }
 
+// Pieces every kernel shares.
+// Offset (halves) of a lane's 16 bytes of the 8-row DMA piece `piece` of an operand tile: 8 lanes per row, the chunk swizzled by the LDS row. The source row is
+// first + min(row, clamp): the k = 3 and the register-streamed kernel clamp rows past their operand into it (duplicates that are never multiplied / stored).
+__device__ __forceinline__ int gemm_dma_off(int piece, int lane, int first, int clamp, int ld) {
+  const int row = piece * 8 + (lane >> 3);
+  return (first + min(row, clamp)) * ld + ((lane & 7) ^ lds_swz(row)) * 8;
+}
+static constexpr int GEMM_NO_CLAMP = 0x7fffffff;
+// Accumulators START from the residual (F32 outputs, swapped operand order: acc[i][j] = 4 consecutive columns of one row): the
+// residual read is issued with the first operand tile and hides behind it, instead of being a dependent HBM round trip in front
+// of the stores when the K loop is over. The sum is the same set of f32 adds in a different order.
+// GEMM_OUT_F32_SCALED (out = alpha acc + bias + resid, alpha a power of two): the accumulators start from resid / alpha — exact, and scaled back
+// exactly by the epilogue.
+// NB 16-column blocks from column c0, the lane holds columns 4 fq .. of each; row_of(i) = the lane's row of block i.
+template <int MODE, int MI, int NB, class ROW>
+__device__ __forceinline__ void gemm_acc_start(const GemmArgs &g, floatx4 (&acc)[MI > 0 ? MI : 1][NB], bool resid_first, int c0, int fq, ROW row_of) {
+  if (resid_first) {
+    const float rs = gemm_mode_scaled(MODE) ? 1.0f / g.alpha : 1.0f;
+#pragma unroll
+    for (int i = 0; i < MI; i++) {
+      const int row = row_of(i);
+#pragma unroll
+      for (int j = 0; j < NB; j++) {
+        const float4 rr = *(const float4 *)(g.resid + (size_t)row * g.ldo + c0 + j * 16 + fq * 4);
+        acc[i][j] = (floatx4){rr.x * rs, rr.y * rs, rr.z * rs, rr.w * rs};
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < MI; i++)
+#pragma unroll
+      for (int j = 0; j < NB; j++) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+  }
+}
+// The body of a 2 x 2 kernel is instantiated per number of 16-row blocks of the calling WAVE (0..4): the waves of a workgroup may run different
+// instantiations; all of them issue the same DMA pieces and pass the same barriers. f(std::integral_constant<int, blocks of this wave>)
+template <class F> __device__ __forceinline__ void gemm_for_my_mi(int nblk, int wave, F f) {
+  const int my_mi = (nblk - (wave >> 1) + 1) >> 1;
+  if (my_mi == 4) f(std::integral_constant<int, 4>{});
+  else if (my_mi == 3) f(std::integral_constant<int, 3>{});
+  else if (my_mi == 2) f(std::integral_constant<int, 2>{});
+  else if (my_mi == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{}); // 1-block tile: this wave only moves operands
+}
+
 // Any segment structure (k = 1 convolutions, projections, channel concats, split-precision operands): one 32 KB LDS stage filled by
 // LDS-DMA, 4 workgroups per CU overlap each other's load / compute phases.
-// The body is instantiated per number of 16-row blocks of the calling WAVE (0..4): the waves of a workgroup may run different
-// instantiations; all of them issue the same DMA pieces and pass the same two barriers per K tile.
-// KU (round 6): K tiles per barrier pair. KU = 2 stages two 64-deep tiles side by side (64 KB, 2 workgroups per CU) and multiplies them between ONE pair of barriers: a
+// Two barriers per K tile. KU (round 6): K tiles per barrier pair. KU = 2 stages two 64-deep tiles side by side (64 KB, 2 workgroups per CU) and multiplies them between ONE pair of barriers: a
 // small problem (one utterance: at most two workgroups per CU) pays a DMA round trip + two barriers per pair instead of per tile. Same products in the same order:
 // bit-identical to KU = 1.
 template <int MODE, int MI, int KU = 1>
@@ -357,43 +402,15 @@ __device__ __forceinline__ void gemm_vh_body(const GemmArgs &g, int m0, int n0, 
   const int my_pa = (2 * nblk - wave + 3) >> 2; // 8-row DMA pieces wave, wave + 4, .. of the A tile moved by this wave
   const int tiles_per_seg = g.kseg >> 6;
   const int ldw = g.custom_w ? g.ldw_ : g.nseg * g.kseg;
-  const int prow = lane >> 3, pslot = lane & 7;
   int aoff[4], boff[4];
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int row = (wave + 4 * i) * 8 + prow;
-    aoff[i] = (m0 + row) * g.lda + (pslot ^ lds_swz(row)) * 8; // pieces past the tile are never issued
-  }
+  for (int i = 0; i < 4; i++) aoff[i] = gemm_dma_off(wave + 4 * i, lane, m0, GEMM_NO_CLAMP, g.lda);
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int row = (wave * 4 + i) * 8 + prow;
-    boff[i] = (n0 + row) * ldw + (pslot ^ lds_swz(row)) * 8;
-  }
+  for (int i = 0; i < 4; i++) boff[i] = gemm_dma_off(wave * 4 + i, lane, n0, GEMM_NO_CLAMP, ldw);
   const int fr = lane & 15, fq = lane >> 4;
-  // Accumulators START from the residual (F32 outputs, swapped operand order: acc[i][j] = 4 consecutive columns of one row): the
-  // residual read is issued with the first operand tile and hides behind it, instead of being a dependent HBM round trip in front
-  // of the stores when the K loop is over. The sum is the same set of f32 adds in a different order.
-  // GEMM_OUT_F32_SCALED (out = alpha acc + bias + resid, alpha a power of two): the accumulators start from resid / alpha — exact, and scaled back
-  // exactly by the epilogue.
   const bool resid_first = gemm_mode_f32(MODE) && g.resid != nullptr;
   floatx4 acc[MA][4];
-  if (resid_first) {
-    const float rs = gemm_mode_scaled(MODE) ? 1.0f / g.alpha : 1.0f;
-#pragma unroll
-    for (int i = 0; i < MI; i++) {
-      const int row = m0 + vh_blk(wm, i) * 16 + fr;
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const float4 rr = *(const float4 *)(g.resid + (size_t)row * g.ldo + n0 + wn * 64 + j * 16 + fq * 4);
-        acc[i][j] = (floatx4){rr.x * rs, rr.y * rs, rr.z * rs, rr.w * rs};
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < MI; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-  }
+  gemm_acc_start<MODE, MI, 4>(g, acc, resid_first, n0 + wn * 64, fq, [&](int i) { return m0 + vh_blk(wm, i) * 16 + fr; });
   char *sa = smem, *sb = smem + 16384;
   // operand order (see gemm_epilogue_vh): natural only for the V columns of a QKV projection (wave-uniform)
   const bool natural = gemm_mode_qkv(MODE) && (((n0 + wn * 64) % 192) >= 128);
@@ -448,6 +465,8 @@ __device__ __forceinline__ void gemm_vh_body(const GemmArgs &g, int m0, int n0, 
 // tile are staged side by side (16 KB A + 2 x 16 KB B = 48 KB, 3 workgroups per CU) and every A fragment read from LDS feeds both products — against two
 // K segments through gemm_vh_body: 48 instead of 64 KB of DMA, 24 instead of 32 KB of fragment reads and 2 instead of 4 barriers per 64 MFMAs.
 // g.W = [N][ldw_] with the hi half at column w_off_[0] and the lo half at w_off_[1] (custom_w); g.nseg == 2, g.A[0] == g.A[1], equal row offsets.
+// Kept apart from gemm_vh_body: one body templated on the number of weight images cost 5 (KU 1) / 8 (KU 2) VGPRs in gemm_f16_vh_dualb_kernel<4, *>, and gemm_acc_start
+// here 2 in the same two instantiations (profiles/gemm_refactor_isa.txt).
 static constexpr int GEMM_DUALB_LDS = 49152;
 template <int MODE, int MI, int KU = 1>
 __device__ __forceinline__ void gemm_vh_dualb_body(const GemmArgs &g, int m0, int n0, int nblk, int lane, int wave) {
@@ -457,18 +476,11 @@ __device__ __forceinline__ void gemm_vh_dualb_body(const GemmArgs &g, int m0, in
   const int wm = wave >> 1, wn = wave & 1;
   const int my_pa = (2 * nblk - wave + 3) >> 2;
   const int ntiles = g.kseg >> 6, ldw = g.ldw_;
-  const int prow = lane >> 3, pslot = lane & 7;
   int aoff[4], boff[4];
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int row = (wave + 4 * i) * 8 + prow;
-    aoff[i] = (m0 + row) * g.lda + (pslot ^ lds_swz(row)) * 8;
-  }
+  for (int i = 0; i < 4; i++) aoff[i] = gemm_dma_off(wave + 4 * i, lane, m0, GEMM_NO_CLAMP, g.lda);
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const int row = (wave * 4 + i) * 8 + prow;
-    boff[i] = (n0 + row) * ldw + (pslot ^ lds_swz(row)) * 8;
-  }
+  for (int i = 0; i < 4; i++) boff[i] = gemm_dma_off(wave * 4 + i, lane, n0, GEMM_NO_CLAMP, ldw);
   const int fr = lane & 15, fq = lane >> 4;
   const bool resid_first = gemm_mode_f32(MODE) && g.resid != nullptr;
   floatx4 acc[MA][4];
@@ -537,11 +549,6 @@ __device__ __forceinline__ void gemm_vh_dualb_body(const GemmArgs &g, int m0, in
 // stream through. (With plain m-major order the 6 MB QKV weight thrashed L2: 417 MB fetched per launch for 64 MB of operands.)
 __device__ __forceinline__ bool gemm_vh_tile(const GemmArgs &g, int &m0, int &n0, int &nblk) {
   const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-  if (g.tiles) { // developer tools: explicit per-XCD lists
-    const int4 td = g.tiles[xcd * g.tab_len + idx];
-    m0 = __builtin_amdgcn_readfirstlane(td.x); nblk = __builtin_amdgcn_readfirstlane(td.y); n0 = __builtin_amdgcn_readfirstlane(td.z);
-    return nblk > 0;
-  }
   const int nb = g.M >> 4, NT = g.N >> 7;
   const int b0 = (int)((long long)nb * xcd >> 3), b1 = (int)((long long)nb * (xcd + 1) >> 3);
   const int mt = (b1 - b0 + g.th - 1) / g.th;
@@ -560,12 +567,7 @@ static __global__ __launch_bounds__(256, WGS) void gemm_f16_vh_kernel(GemmArgs g
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6); // scalar: LDS-DMA bases stay in SGPRs
   int m0, n0, nblk;
   if (!gemm_vh_tile(g, m0, n0, nblk)) return;
-  const int my_mi = (nblk - (wave >> 1) + 1) >> 1; // 16-row blocks of this wave
-  if (my_mi == 4) gemm_vh_body<MODE, 4, KU>(g, m0, n0, nblk, lane, wave);
-  else if (my_mi == 3) gemm_vh_body<MODE, 3, KU>(g, m0, n0, nblk, lane, wave);
-  else if (my_mi == 2) gemm_vh_body<MODE, 2, KU>(g, m0, n0, nblk, lane, wave);
-  else if (my_mi == 1) gemm_vh_body<MODE, 1, KU>(g, m0, n0, nblk, lane, wave);
-  else gemm_vh_body<MODE, 0, KU>(g, m0, n0, nblk, lane, wave); // 1-block tile: this wave only moves operands
+  gemm_for_my_mi(nblk, wave, [&](auto mi) { gemm_vh_body<MODE, decltype(mi)::value, KU>(g, m0, n0, nblk, lane, wave); });
 }
 
 template <int MODE, int KU = 1>
@@ -573,12 +575,7 @@ static __global__ __launch_bounds__(256, KU == 1 ? 3 : 1) void gemm_f16_vh_dualb
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int m0, n0, nblk;
   if (!gemm_vh_tile(g, m0, n0, nblk)) return;
-  const int my_mi = (nblk - (wave >> 1) + 1) >> 1;
-  if (my_mi == 4) gemm_vh_dualb_body<MODE, 4, KU>(g, m0, n0, nblk, lane, wave);
-  else if (my_mi == 3) gemm_vh_dualb_body<MODE, 3, KU>(g, m0, n0, nblk, lane, wave);
-  else if (my_mi == 2) gemm_vh_dualb_body<MODE, 2, KU>(g, m0, n0, nblk, lane, wave);
-  else if (my_mi == 1) gemm_vh_dualb_body<MODE, 1, KU>(g, m0, n0, nblk, lane, wave);
-  else gemm_vh_dualb_body<MODE, 0, KU>(g, m0, n0, nblk, lane, wave);
+  gemm_for_my_mi(nblk, wave, [&](auto mi) { gemm_vh_dualb_body<MODE, decltype(mi)::value, KU>(g, m0, n0, nblk, lane, wave); });
 }
 
 // Weight operand through REGISTERS (gemm_f16_wreg_kernel; one K segment, 128-row tiles, F32 / QKV outputs). The weight is constant from load time on, so the loader
@@ -606,6 +603,8 @@ template <int N> __device__ __forceinline__ void wreg_wait(half8 &a, half8 &b, h
 }
 
 // acc[i][j]: 16-row block i of the tile, columns n0 + 32 wave + 16 j ..; only blocks i < nblk are stored
+// Kept apart from gemm_epilogue_vh: one epilogue templated on the wave's part of the tile left this kernel at 126 VGPRs and every object built with
+// -amdgpu-mfma-vgpr-form unchanged, but cost 4 VGPRs in gemm_f16_vh_kernel<2, 1, 4> (160 -> 164) and 12 in <3, 1, 4> (164 -> 176) as ar.o and vocoder.o compile them
 template <int MODE, int MI, bool NAT>
 __device__ __forceinline__ void gemm_epilogue_wreg(const GemmArgs &g, floatx4 (&acc)[MI][2], int m0, int n0, int nblk, int wave, int fr, int fq) {
   const int c0 = n0 + wave * 32;
@@ -699,35 +698,16 @@ __device__ __forceinline__ void gemm_wreg_body(const GemmArgs &g, int m0, int n0
   constexpr int PER = NPA + 4;        // vmcnt events per wave and K tile
   static_assert(D == 1 || D == 2, "prefetch distance");
   const int T = g.kseg >> 6, KS = g.kseg >> 5;
-  const int prow = lane >> 3, pslot = lane & 7;
   const int fr = lane & 15, fq = lane >> 4;
   unsigned aoff[NPA]; // byte offsets from a wave-uniform base: the DMA takes the SGPR-base addressing form
 #pragma unroll
-  for (int i = 0; i < NPA; i++) {
-    const int row = (wave + 4 * i) * 8 + prow; // LDS row; the source row is clamped into the tile (short tiles: duplicates, never stored)
-    aoff[i] = (unsigned)((min(row, nblk * 16 - 1) * g.lda + (pslot ^ lds_swz(row)) * 8) * 2);
-  }
+  for (int i = 0; i < NPA; i++) aoff[i] = (unsigned)(gemm_dma_off(wave + 4 * i, lane, 0, nblk * 16 - 1, g.lda) * 2);
   const char *aseg = (const char *)(g.A[0] + (ptrdiff_t)(g.row_off[0] + m0) * g.lda);
   const __half *wp0 = g.Wf + (size_t)((n0 >> 4) + wave * 2) * KS * 512, *wp1 = wp0 + (size_t)KS * 512; // wave-uniform
   const unsigned wlane = lane * 16;
   const bool resid_first = MODE == GEMM_OUT_F32 && g.resid != nullptr;
   floatx4 acc[MI][2];
-  if (resid_first) { // accumulators start from the residual, as in gemm_vh_body
-#pragma unroll
-    for (int i = 0; i < MI; i++) {
-      const int row = m0 + min(i, nblk - 1) * 16 + fr;
-#pragma unroll
-      for (int j = 0; j < 2; j++) {
-        const float4 rr = *(const float4 *)(g.resid + (size_t)row * g.ldo + n0 + wave * 32 + j * 16 + fq * 4);
-        acc[i][j] = (floatx4){rr.x, rr.y, rr.z, rr.w};
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < MI; i++)
-#pragma unroll
-      for (int j = 0; j < 2; j++) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-  }
+  gemm_acc_start<MODE, MI, 2>(g, acc, resid_first, n0 + wave * 32, fq, [&](int i) { return m0 + min(i, nblk - 1) * 16 + fr; });
   half8 w[S][2][2]; // [set][k step][column block]
   auto issue = [&](int t, auto set_c) {
     constexpr int U = decltype(set_c)::value;
@@ -809,9 +789,9 @@ static __global__ __launch_bounds__(256, 4) void gemm_f16_wreg_kernel(GemmArgs g
     else gemm_wreg_body<MODE, 4, D, false>(g, m0, n0, nblk, lane, wave);
   }
 }
-// the shapes gemm_f16_wreg_kernel takes (launch_gemm_f16 has chosen th and ku)
+// the shapes gemm_f16_wreg_kernel takes (gemm_plan has chosen th and ku)
 static inline bool gemm_takes_wreg(const GemmArgs &g, int th, int ku) {
-  return g.wreg > 0 && g.Wf && !g.tiles && g.nseg == 1 && !g.custom_w && th == 8 && ku == 1 && (g.kseg >> 6) >= 2 &&
+  return g.wreg > 0 && g.Wf && g.nseg == 1 && !g.custom_w && th == 8 && ku == 1 && (g.kseg >> 6) >= 2 &&
          (g.mode == GEMM_OUT_F32 || g.mode == GEMM_OUT_QKV || g.mode == GEMM_OUT_QKV_SPLIT);
 }
 
@@ -835,7 +815,7 @@ __device__ __forceinline__ void gemm_conv3_vh_body(const GemmArgs &g, int m0, in
   const int nchunks = g.kseg >> 6, ldw = 3 * g.kseg, nph = 3 * nchunks;
   const int prow = lane >> 3, pslot = lane & 7;
   const int fr = lane & 15, fq = lane >> 4;
-  floatx4 acc[MA][4];
+  floatx4 acc[MA][4]; // from zero: the residual is read by the epilogue (EPI_RESID_LOAD)
 #pragma unroll
   for (int i = 0; i < MI; i++)
 #pragma unroll
@@ -843,7 +823,7 @@ __device__ __forceinline__ void gemm_conv3_vh_body(const GemmArgs &g, int m0, in
   char *sa = smem, *sb = smem + (128 + 8) * 128;
   const __half *abase = g.A[0] + (ptrdiff_t)(m0 - 1) * g.lda; // slab row s = activation row m0 - 1 + s (the buffer has its guard rows)
   const __half *wbase = g.W + (size_t)n0 * ldw;
-  int aoff[5], boff[4];
+  int aoff[5], boff[4]; // kept apart from gemm_dma_off: with it (and gemm_for_my_mi) gemm_f16_conv3_vh_kernel<5> took 168 VGPRs against 166
 #pragma unroll
   for (int i = 0; i < 5; i++) {
     const int row = (wave + 4 * i) * 8 + prow;
@@ -911,12 +891,7 @@ static __global__ __launch_bounds__(256, 3) void gemm_f16_conv3_vh_kernel(GemmAr
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int m0, n0, nblk;
   if (!gemm_vh_tile(g, m0, n0, nblk)) return;
-  const int my_mi = (nblk - (wave >> 1) + 1) >> 1;
-  if (my_mi == 4) gemm_conv3_vh_body<MODE, 4>(g, m0, n0, nblk, lane, wave);
-  else if (my_mi == 3) gemm_conv3_vh_body<MODE, 3>(g, m0, n0, nblk, lane, wave);
-  else if (my_mi == 2) gemm_conv3_vh_body<MODE, 2>(g, m0, n0, nblk, lane, wave);
-  else if (my_mi == 1) gemm_conv3_vh_body<MODE, 1>(g, m0, n0, nblk, lane, wave);
-  else gemm_conv3_vh_body<MODE, 0>(g, m0, n0, nblk, lane, wave);
+  gemm_for_my_mi(nblk, wave, [&](auto mi) { gemm_conv3_vh_body<MODE, decltype(mi)::value>(g, m0, n0, nblk, lane, wave); });
 }
 
 // k = 3 convolution (three row-shifted segments of one activation buffer, tap-major weights): shared-slab kernel
@@ -933,105 +908,110 @@ static inline int gemm_auto_th(int M, int N) {
   return th;
 }
 
-static inline hipError_t launch_gemm_f16(const GemmArgs &g, hipStream_t s) {
-  GemmArgs gg = g;
+// What launch_gemm_f16 does with a set of arguments: pure host arithmetic, no HIP call (the kernel tests read it to say which kernel ran). th / ku / cn / grid / lds are the
+// EFFECTIVE values, those of the instantiation that is launched: the k = 3 and the register-streamed kernel have no KU (1), the dual-B kernel has 1 and 2.
+enum { GEMM_KERNEL_VH = 0, GEMM_KERNEL_DUALB = 1, GEMM_KERNEL_CONV3 = 2, GEMM_KERNEL_WREG = 3 };
+struct GemmPlan {
+  hipError_t err; // hipErrorInvalidValue: refused, nothing is launched (the other fields still say what the rules select)
+  int kernel;     // GEMM_KERNEL_*
+  int th, ku, cn; // 16-row blocks per tile, K tiles per barrier pair, column tiles per L2 chunk
+  int grid, lds;  // workgroups, dynamic LDS bytes
+};
+static inline GemmPlan gemm_plan(const GemmArgs &g) {
+  GemmPlan p = {};
   const int NT = g.N >> 7, ktot = g.nseg * g.kseg, nb = g.M >> 4;
+  p.err = hipSuccess;
   if (gemm_mode_scaled(g.mode)) { // the accumulators start from resid / alpha and are scaled back by alpha: exact only for a non-zero power of two
     int e;
-    if (!(g.alpha != 0.f) || std::fabs(std::frexp(g.alpha, &e)) != 0.5f) return hipErrorInvalidValue;
+    if (!(g.alpha != 0.f) || std::fabs(std::frexp(g.alpha, &e)) != 0.5f) p.err = hipErrorInvalidValue;
   }
-  if (gemm_mode_stats(g.mode) && (!g.st_out || !g.chunk_seq || g.st_stripe_ll <= 0)) return hipErrorInvalidValue;
+  if (gemm_mode_stats(g.mode) && (!g.st_out || !g.chunk_seq || g.st_stripe_ll <= 0)) p.err = hipErrorInvalidValue;
   // dual_b names ONE kernel: a caller whose arguments do not describe "hi | lo halves of one weight over one activation operand" gets an error, not another kernel
-  if (g.dual_b && !(gemm_mode_scaled(g.mode) && g.nseg == 2 && g.custom_w && g.A[0] == g.A[1] && g.row_off[0] == g.row_off[1])) return hipErrorInvalidValue;
+  if (g.dual_b && !(gemm_mode_scaled(g.mode) && g.nseg == 2 && g.custom_w && g.A[0] == g.A[1] && g.row_off[0] == g.row_off[1])) p.err = hipErrorInvalidValue;
   int ku = (g.ku == 2 || g.ku == 4) && (g.kseg % (64 * g.ku)) == 0 ? g.ku : 1;
-  int grid;
-  if (g.tiles) grid = 8 * g.tab_len;
-  else {
-    // L2 chunking of the column tiles: pays for wide outputs (N = 3072: 200 us with chunks of 8 column tiles against 232 unchunked and 207-219
-    // with chunks of 6) and costs ~3 % when the activations would have to stream twice for a narrow one (N = 1024, K = 3072)
-    // -> only chunk when NT > 8; the chunk is the largest divisor of NT whose weight rows fit ~2.5 MB
-    int cn = NT;
-    if (NT > 8)
-      for (cn = NT; cn > 1; cn--)
-        if (NT % cn == 0 && (size_t)cn * 128 * ktot * 2 <= (size_t)2560 * 1024) break;
-    gg.cn = cn;
-    // Tile height: 128 rows unless the problem is small. Mixed heights, exactly filled rounds and tallest-first orders were measured
-    // through explicit tile tables (tools/gemm_tab_bench.hip, profiles/r3_gemm_tile_tables.txt): no policy beats uniform 128-row
-    // tiles at the benchmark's sizes. Small problems (a single utterance: M = 1 792 rows) want more, shorter tiles — halve the height
-    // while the grid stays within one round of the ~1024 resident slots.
-    const int maxb = (nb + 7) / 8 + 1; // blocks of the largest XCD range (upper bound)
-    auto tiles_at = [&](int h) { return 8 * ((maxb + h - 1) / h) * NT; };
-    int th = g.th;
-    if (th <= 0) th = gemm_auto_th(g.M, g.N);
-    // One utterance (M = 1 792 rows, N = 1 024: 224 tiles of 64 rows = at most one workgroup per CU): four K tiles per barrier pair at 64-row tiles — a lone
-    // workgroup pays its DMA round trip and two barriers per 256 of K instead of per 64 (profiles/r6_small_gemm.txt: k = 1 12.6 -> 11.6 us warm, 22.8 -> 17.9 us
-    // with cold weights; the K = 2 048 integrating conv 25.7 / 36.2 -> 20.3 / 27.8). Same products in the same order: bit-identical to every other tiling.
-    // (the split-weight proj_out, 48 KB per K tile: two per barrier pair, 21.5 -> 19.1 us warm / 28.3 -> 25.6 cold; the k = 3 kernel has its own pipeline and only takes
-    // the 64-row tiles: 27.3 -> 25.5 / 35.6 -> 32.2)
-    if (g.th <= 0 && g.ku == 0 && NT <= 8 && tiles_at(4) <= 256 && (g.kseg % 256) == 0) {
-      th = 4;
-      if (!gemm_is_conv3(g)) ku = g.dual_b ? 2 : 4;
-    }
-    gg.th = th;
-    int mt_max = 0;
-    for (int x = 0; x < 8; x++) {
-      const int b0 = (int)((long long)nb * x >> 3), b1 = (int)((long long)nb * (x + 1) >> 3);
-      mt_max = std::max(mt_max, (b1 - b0 + th - 1) / th);
-    }
-    grid = 8 * mt_max * NT;
+  // L2 chunking of the column tiles: pays for wide outputs (N = 3072: 200 us with chunks of 8 column tiles against 232 unchunked and 207-219
+  // with chunks of 6) and costs ~3 % when the activations would have to stream twice for a narrow one (N = 1024, K = 3072)
+  // -> only chunk when NT > 8; the chunk is the largest divisor of NT whose weight rows fit ~2.5 MB
+  p.cn = NT;
+  if (NT > 8)
+    for (p.cn = NT; p.cn > 1; p.cn--)
+      if (NT % p.cn == 0 && (size_t)p.cn * 128 * ktot * 2 <= (size_t)2560 * 1024) break;
+  // Tile height: 128 rows unless the problem is small. Mixed heights, exactly filled rounds and tallest-first orders were measured
+  // through explicit tile tables (profiles/r3_gemm_tile_tables.txt): no policy beats uniform 128-row
+  // tiles at the benchmark's sizes. Small problems (a single utterance: M = 1 792 rows) want more, shorter tiles — halve the height
+  // while the grid stays within one round of the ~1024 resident slots.
+  const int maxb = (nb + 7) / 8 + 1; // blocks of the largest XCD range (upper bound)
+  p.th = g.th > 0 ? g.th : gemm_auto_th(g.M, g.N);
+  // One utterance (M = 1 792 rows, N = 1 024: 224 tiles of 64 rows = at most one workgroup per CU): four K tiles per barrier pair at 64-row tiles — a lone
+  // workgroup pays its DMA round trip and two barriers per 256 of K instead of per 64 (profiles/r6_small_gemm.txt: k = 1 12.6 -> 11.6 us warm, 22.8 -> 17.9 us
+  // with cold weights; the K = 2 048 integrating conv 25.7 / 36.2 -> 20.3 / 27.8). Same products in the same order: bit-identical to every other tiling.
+  // (the split-weight proj_out, 48 KB per K tile: two per barrier pair, 21.5 -> 19.1 us warm / 28.3 -> 25.6 cold; the k = 3 kernel has its own pipeline and only takes
+  // the 64-row tiles: 27.3 -> 25.5 / 35.6 -> 32.2)
+  if (g.th <= 0 && g.ku == 0 && NT <= 8 && 8 * ((maxb + 3) / 4) * NT <= 256 && (g.kseg % 256) == 0) {
+    p.th = 4;
+    if (!gemm_is_conv3(g)) ku = g.dual_b ? 2 : 4;
   }
-  if (gemm_takes_wreg(g, gg.th, ku)) {
-    if (g.mode == GEMM_OUT_F32) gemm_f16_wreg_kernel<GEMM_OUT_F32><<<grid, 256, GEMM_WREG_LDS, s>>>(gg);
-    else if (g.mode == GEMM_OUT_QKV) gemm_f16_wreg_kernel<GEMM_OUT_QKV><<<grid, 256, GEMM_WREG_LDS, s>>>(gg);
-    else gemm_f16_wreg_kernel<GEMM_OUT_QKV_SPLIT><<<grid, 256, GEMM_WREG_LDS, s>>>(gg);
-  } else if (gemm_is_conv3(g)) {
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void *)gemm_f16_conv3_vh_kernel<GEMM_OUT_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, CONV3_VH_LDS);
-      (void)hipFuncSetAttribute((const void *)gemm_f16_conv3_vh_kernel<GEMM_OUT_F32_STATS>, hipFuncAttributeMaxDynamicSharedMemorySize, CONV3_VH_LDS);
-      (void)hipFuncSetAttribute((const void *)gemm_f16_conv3_vh_kernel<GEMM_OUT_F16>, hipFuncAttributeMaxDynamicSharedMemorySize, CONV3_VH_LDS);
-      attr = true;
-    }
-    if (g.mode == GEMM_OUT_F32) gemm_f16_conv3_vh_kernel<GEMM_OUT_F32><<<grid, 256, CONV3_VH_LDS, s>>>(gg);
-    else if (g.mode == GEMM_OUT_F32_STATS) gemm_f16_conv3_vh_kernel<GEMM_OUT_F32_STATS><<<grid, 256, CONV3_VH_LDS, s>>>(gg);
-    else gemm_f16_conv3_vh_kernel<GEMM_OUT_F16><<<grid, 256, CONV3_VH_LDS, s>>>(gg);
-  } else if (g.dual_b && gemm_mode_scaled(g.mode) && g.nseg == 2 && g.custom_w && g.A[0] == g.A[1] && g.row_off[0] == g.row_off[1]) {
-    // ku: 2 or 3 K tiles per barrier pair for a grid of at most one workgroup per CU (96 / 144 KB of LDS)
-#define TTS_DUALB_LAUNCH(MODE_)                                                                                                                     \
-  do {                                                                                                                                              \
-    if (ku == 2) {                                                                                                                                  \
-      static bool a2 = false;                                                                                                                       \
-      if (!a2) { (void)hipFuncSetAttribute((const void *)gemm_f16_vh_dualb_kernel<MODE_, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GEMM_DUALB_LDS); a2 = true; } \
-      gemm_f16_vh_dualb_kernel<MODE_, 2><<<grid, 256, 2 * GEMM_DUALB_LDS, s>>>(gg);                                                                  \
-    } else gemm_f16_vh_dualb_kernel<MODE_, 1><<<grid, 256, GEMM_DUALB_LDS, s>>>(gg);                                                                \
-  } while (0)
-    if (g.mode == GEMM_OUT_F32_SCALED) TTS_DUALB_LAUNCH(GEMM_OUT_F32_SCALED);
-    else TTS_DUALB_LAUNCH(GEMM_OUT_F32_SCALED_STATS);
-#undef TTS_DUALB_LAUNCH
-  } else {
-    // KU > 1: 64 / 128 KB of LDS -> 2 / 1 workgroups per CU (the occupancy bound of the launch is a compile-time promise: WGS)
-#define TTS_VH_LAUNCH(MODE_)                                                                                                                      \
-  do {                                                                                                                                            \
-    if (ku == 1) gemm_f16_vh_kernel<MODE_, 4><<<grid, 256, GEMM_VH_LDS, s>>>(gg);                                                                 \
-    else if (ku == 2) {                                                                                                                           \
-      static bool a2 = false;                                                                                                                     \
-      if (!a2) { (void)hipFuncSetAttribute((const void *)gemm_f16_vh_kernel<MODE_, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * GEMM_VH_LDS); a2 = true; } \
-      gemm_f16_vh_kernel<MODE_, 2, 2><<<grid, 256, 2 * GEMM_VH_LDS, s>>>(gg);                                                                     \
-    } else {                                                                                                                                      \
-      static bool a4 = false;                                                                                                                     \
-      if (!a4) { (void)hipFuncSetAttribute((const void *)gemm_f16_vh_kernel<MODE_, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * GEMM_VH_LDS); a4 = true; } \
-      gemm_f16_vh_kernel<MODE_, 1, 4><<<grid, 256, 4 * GEMM_VH_LDS, s>>>(gg);                                                                     \
-    }                                                                                                                                             \
-  } while (0)
-    if (g.mode == GEMM_OUT_F32) TTS_VH_LAUNCH(GEMM_OUT_F32);
-    else if (g.mode == GEMM_OUT_F16) TTS_VH_LAUNCH(GEMM_OUT_F16);
-    else if (g.mode == GEMM_OUT_QKV) TTS_VH_LAUNCH(GEMM_OUT_QKV);
-    else if (g.mode == GEMM_OUT_QKV_SPLIT) TTS_VH_LAUNCH(GEMM_OUT_QKV_SPLIT);
-    else if (g.mode == GEMM_OUT_F32_SCALED) TTS_VH_LAUNCH(GEMM_OUT_F32_SCALED);
-    else if (g.mode == GEMM_OUT_F32_STATS) TTS_VH_LAUNCH(GEMM_OUT_F32_STATS);
-    else TTS_VH_LAUNCH(GEMM_OUT_F32_SCALED_STATS);
-#undef TTS_VH_LAUNCH
+  int mt_max = 0; // tiles of the XCD with the most blocks: the grid is padded to 8 times that
+  for (int x = 0; x < 8; x++) {
+    const int b0 = (int)((long long)nb * x >> 3), b1 = (int)((long long)nb * (x + 1) >> 3);
+    mt_max = std::max(mt_max, (b1 - b0 + p.th - 1) / p.th);
   }
+  p.grid = 8 * mt_max * NT;
+  if (gemm_takes_wreg(g, p.th, ku)) { p.kernel = GEMM_KERNEL_WREG; p.ku = 1; p.lds = GEMM_WREG_LDS; }
+  else if (gemm_is_conv3(g)) { p.kernel = GEMM_KERNEL_CONV3; p.ku = 1; p.lds = CONV3_VH_LDS; }
+  else if (g.dual_b) { p.kernel = GEMM_KERNEL_DUALB; p.ku = ku == 2 ? 2 : 1; p.lds = p.ku * GEMM_DUALB_LDS; } // a requested KU of 4 has no dual-B instantiation
+  else { p.kernel = GEMM_KERNEL_VH; p.ku = ku; p.lds = ku * GEMM_VH_LDS; } // KU > 1: 64 / 128 KB of LDS -> 2 / 1 workgroups per CU
+  return p;
+}
+
+// One instantiation's launch. More dynamic LDS than the 48 KB a kernel may use by default (the k = 3 kernel, KU 2 / 4, dual-B KU 2) is asked for once per instantiation.
+// The threshold names exactly those: dual-B KU 1 (48 KB) and every smaller stage are never raised; a change of an LDS size changes which instantiations get the call.
+static_assert(GEMM_DUALB_LDS <= 48 * 1024 && GEMM_VH_LDS <= 48 * 1024 && GEMM_WREG_LDS <= 48 * 1024 && CONV3_VH_LDS > 48 * 1024, "which launches raise their dynamic LDS limit");
+template <void (*KERN)(GemmArgs)> static inline void gemm_launch(const GemmPlan &p, const GemmArgs &g, hipStream_t s) {
+  if (p.lds > 48 * 1024) {
+    static bool raised = false;
+    if (!raised) { (void)hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, p.lds); raised = true; }
+  }
+  KERN<<<p.grid, 256, p.lds, s>>>(g);
+}
+// mode -> instantiation, once per kernel. The occupancy bound of a KU > 1 launch is a compile-time promise: WGS
+template <int KU> static inline void gemm_launch_vh(const GemmPlan &p, const GemmArgs &g, hipStream_t s) {
+  constexpr int WGS = KU == 1 ? 4 : KU == 2 ? 2 : 1;
+  switch (g.mode) {
+    case GEMM_OUT_F32: return gemm_launch<gemm_f16_vh_kernel<GEMM_OUT_F32, WGS, KU>>(p, g, s);
+    case GEMM_OUT_F16: return gemm_launch<gemm_f16_vh_kernel<GEMM_OUT_F16, WGS, KU>>(p, g, s);
+    case GEMM_OUT_QKV: return gemm_launch<gemm_f16_vh_kernel<GEMM_OUT_QKV, WGS, KU>>(p, g, s);
+    case GEMM_OUT_QKV_SPLIT: return gemm_launch<gemm_f16_vh_kernel<GEMM_OUT_QKV_SPLIT, WGS, KU>>(p, g, s);
+    case GEMM_OUT_F32_SCALED: return gemm_launch<gemm_f16_vh_kernel<GEMM_OUT_F32_SCALED, WGS, KU>>(p, g, s);
+    case GEMM_OUT_F32_STATS: return gemm_launch<gemm_f16_vh_kernel<GEMM_OUT_F32_STATS, WGS, KU>>(p, g, s);
+    default: return gemm_launch<gemm_f16_vh_kernel<GEMM_OUT_F32_SCALED_STATS, WGS, KU>>(p, g, s);
+  }
+}
+template <int KU> static inline void gemm_launch_dualb(const GemmPlan &p, const GemmArgs &g, hipStream_t s) {
+  if (g.mode == GEMM_OUT_F32_SCALED) gemm_launch<gemm_f16_vh_dualb_kernel<GEMM_OUT_F32_SCALED, KU>>(p, g, s);
+  else gemm_launch<gemm_f16_vh_dualb_kernel<GEMM_OUT_F32_SCALED_STATS, KU>>(p, g, s);
+}
+static inline void gemm_launch_conv3(const GemmPlan &p, const GemmArgs &g, hipStream_t s) {
+  if (g.mode == GEMM_OUT_F32) gemm_launch<gemm_f16_conv3_vh_kernel<GEMM_OUT_F32>>(p, g, s);
+  else if (g.mode == GEMM_OUT_F32_STATS) gemm_launch<gemm_f16_conv3_vh_kernel<GEMM_OUT_F32_STATS>>(p, g, s);
+  else gemm_launch<gemm_f16_conv3_vh_kernel<GEMM_OUT_F16>>(p, g, s);
+}
+static inline void gemm_launch_wreg(const GemmPlan &p, const GemmArgs &g, hipStream_t s) {
+  if (g.mode == GEMM_OUT_F32) gemm_launch<gemm_f16_wreg_kernel<GEMM_OUT_F32>>(p, g, s);
+  else if (g.mode == GEMM_OUT_QKV) gemm_launch<gemm_f16_wreg_kernel<GEMM_OUT_QKV>>(p, g, s);
+  else gemm_launch<gemm_f16_wreg_kernel<GEMM_OUT_QKV_SPLIT>>(p, g, s);
+}
+
+static inline hipError_t launch_gemm_f16(const GemmArgs &g, hipStream_t s) {
+  const GemmPlan p = gemm_plan(g);
+  if (p.err != hipSuccess) return p.err;
+  GemmArgs gg = g;
+  gg.th = p.th;
+  gg.cn = p.cn;
+  if (p.kernel == GEMM_KERNEL_WREG) gemm_launch_wreg(p, gg, s);
+  else if (p.kernel == GEMM_KERNEL_CONV3) gemm_launch_conv3(p, gg, s);
+  else if (p.kernel == GEMM_KERNEL_DUALB) p.ku == 2 ? gemm_launch_dualb<2>(p, gg, s) : gemm_launch_dualb<1>(p, gg, s);
+  else p.ku == 4 ? gemm_launch_vh<4>(p, gg, s) : p.ku == 2 ? gemm_launch_vh<2>(p, gg, s) : gemm_launch_vh<1>(p, gg, s);
   return hipGetLastError();
 }
 

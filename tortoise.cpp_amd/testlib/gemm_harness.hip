@@ -60,25 +60,11 @@ GemmArgs host_args(const tts_gemm_case &c) { // the fields the dispatcher reads;
   return g;
 }
 
-// What launch_gemm_f16 selects for these arguments: the launcher's own rules, restated through the header's predicates (g.Wf must be set where an image exists).
-void plan(const GemmArgs &g, char *buf, int cap) {
-  const int NT = g.N >> 7, nb = g.M >> 4, ktot = g.nseg * g.kseg;
-  int ku = (g.ku == 2 || g.ku == 4) && (g.kseg % (64 * g.ku)) == 0 ? g.ku : 1;
-  int cn = NT;
-  if (NT > 8)
-    for (cn = NT; cn > 1; cn--)
-      if (NT % cn == 0 && (size_t)cn * 128 * ktot * 2 <= (size_t)2560 * 1024) break;
-  const int maxb = (nb + 7) / 8 + 1;
-  int th = g.th > 0 ? g.th : gemm_auto_th(g.M, g.N);
-  if (g.th <= 0 && g.ku == 0 && NT <= 8 && 8 * ((maxb + 3) / 4) * NT <= 256 && (g.kseg % 256) == 0) {
-    th = 4;
-    if (!gemm_is_conv3(g)) ku = g.dual_b ? 2 : 4;
-  }
-  const char *k = "vh";
-  if (gemm_takes_wreg(g, th, ku)) { k = "wreg"; ku = 1; }
-  else if (gemm_is_conv3(g)) { k = "conv3"; ku = 1; }
-  else if (g.dual_b) { k = "dualb"; ku = ku == 2 ? 2 : 1; }
-  snprintf(buf, cap, "%s mode=%d th=%d ku=%d cn=%d", k, g.mode, th, ku, cn);
+// What launch_gemm_f16 does with these arguments, in the words of its own plan (g.Wf must be set where an image exists).
+void describe(const GemmArgs &g, char *buf, int cap) {
+  static const char *const names[] = {"vh", "dualb", "conv3", "wreg"};
+  const GemmPlan p = gemm_plan(g);
+  snprintf(buf, cap, "%s mode=%d th=%d ku=%d cn=%d", names[p.kernel], g.mode, p.th, p.ku, p.cn);
 }
 
 struct Dev { // one device allocation: margin | payload | margin
@@ -144,13 +130,13 @@ bool valid(const tts_gemm_case &c, bool run) { // run: the output buffers are ne
 
 extern "C" {
 
-// the kernel / th / ku / cn the launcher's rules select for a case, without running it (host only)
+// the kernel / th / ku / cn the launcher selects for a case, without running it (host only: gemm_plan)
 int tts_gemm_test_plan(const tts_gemm_case *c, char *buf, int cap) {
   if (!c || !buf || cap <= 0 || !valid(*c, false)) return (int)hipErrorInvalidValue;
   GemmArgs g = host_args(*c);
   static const __half wf_placeholder[1] = {};
   if (c->wreg && c->nseg == 1 && !c->custom_w) g.Wf = wf_placeholder;
-  plan(g, buf, cap);
+  describe(g, buf, cap);
   return 0;
 }
 
@@ -206,7 +192,7 @@ int tts_gemm_test_run(const tts_gemm_case *cp) {
     }
     if (c.has_chunk_seq) { HT(cseq.alloc((size_t)c.M / 8 * 4, 0xFF)); HT(cseq.put(c.chunk_seq)); g.chunk_seq = (const int *)cseq.data(); }
   }
-  plan(g, g_last, sizeof g_last);
+  describe(g, g_last, sizeof g_last);
   hipStream_t s;
   HT(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   hipError_t e = hipDeviceSynchronize(); // the fills above ran on the null stream
