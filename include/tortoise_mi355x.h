@@ -118,7 +118,16 @@ const char *tts_last_error(const tts_ctx *ctx);
  * "load_threads" (0 default = min(16, hardware threads); set BEFORE tts_load_*): host threads that read, upload and (diffusion) re-lay-out the tensors; 1 = serial.
  * "load_device_pack" (1 default; set BEFORE tts_load_ar): decode layouts built by kernels from the uploaded file tensors (0: by the host threads). Same bits.
  * "noise_pipeline", "rng_fast_normal" (1 default): production of TTS_NOISE_REFERENCE draws (beside the device loop; two-phase normal distribution). Results and the RNG
- * state afterwards are those of single std::normal_distribution draws either way (tests/test_host_parity.py); 0 = the single-draw forms. */
+ * state afterwards are those of single std::normal_distribution draws either way (tests/test_host_parity.py); 0 = the single-draw forms.
+ * Additions within version 8 (no prototype changed; sticky per context, read by tts_diffusion and tts_diffusion_multi_voice; a refused value changes nothing):
+ * "diff_sampler" (0 default: the reference's ancestral DDPM step, main.cpp:5970-6030; 1: DDIM — upstream tortoise-tts' ddim_sample on the same network output,
+ * guidance and clipped x0, which the reference does not have; any other value: TTS_ERR_ARG). Only the last kernel of a sampling step differs: graph replay, latency_mode,
+ * hoist_integrator, share_uncond, multi-voice and rng_shard_* work as before. What 20-30 DDIM steps SOUND like cannot be judged without trained weights: the tests pin the
+ * arithmetic.
+ * "ddim_eta" (0 default; [0, 1], else TTS_ERR_ARG; read only when diff_sampler = 1): 0 = deterministic DDIM, the only noise is x_T; > 0 adds sigma_t z per step (1 = the
+ * ancestral variance). See tts_diffusion for the noise layout.
+ * "cond_free_k" (2.0 default = the reference's base_k, main.cpp:5988; finite and >= 0, else TTS_ERR_ARG): conditioning-free guidance strength of both samplers,
+ * cfk_t = k (1 - t / n). At 2.0 every bit of the output is what it was. */
 int tts_set_option(tts_ctx *ctx, const char *key, double value);
 
 /* ---- weight files (drop-in format: magic 0x67676d6c + name-keyed F32 records) ------------- */
@@ -312,7 +321,12 @@ int tts_diffusion_forward(tts_ctx *ctx, const float *latents, int latent_rows, c
  *   noise_mode (when noise==NULL): TTS_NOISE_REFERENCE draws from the ctx RNG in the reference's
  *   order, candidate by candidate; TTS_NOISE_DEVICE uses a counter-based device generator
  *   (seed = ctx seed, stream = candidate) — not the reference's noise, documented in DESIGN.md.
- *   mel_out: per candidate [100][T_c] back to back. */
+ *   mel_out: per candidate [100][T_c] back to back.
+ *   Option "diff_sampler" = 1 (DDIM; additions within version 8), "ddim_eta" = 0: only x_T exists. noise: [sum_c 100*T_c] floats, one x_T per candidate;
+ *   TTS_NOISE_REFERENCE draws exactly 100*T_c normals per candidate from the ctx RNG, candidate after candidate, and nothing else — NOT the reference's
+ *   consumption (81 vectors per candidate): the reference has no DDIM; TTS_NOISE_DEVICE uses the x_T stream of the ancestral sampler, so the same seed starts both
+ *   samplers from the same x_T. No per-step noise is drawn, allocated or uploaded. "ddim_eta" > 0: layout, draw order and device generator keys are exactly the
+ *   ancestral sampler's — n_steps + 1 vectors per candidate, the last one drawn and unused. */
 enum { TTS_NOISE_REFERENCE = 0, TTS_NOISE_DEVICE = 1 };
 int tts_diffusion(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates,
                   int n_steps, const float *noise, int noise_mode, float *mel_out);
@@ -357,7 +371,12 @@ int tts_write_wav(const char *path, const float *samples, int64_t n, int sample_
  *   cfk = conditioning-free k, coef1/coef2 = posterior mean coefficients.
  * tts_host_timestep_embedding: main.cpp:5496-5521. tts_host_rel_bucket: main.cpp:4722-4749.
  * tts_host_pad_codes: apply_padding, main.cpp:4510-4532 (n <= 500 sampled codes -> 502). tts_host_trimmed_rows: trim_latents
- *   row count, main.cpp:4873-4915. */
+ *   row count, main.cpp:4873-4915.
+ * tts_host_schedule_ddim (addition within version 8; not in the reference): the DDIM scalars of option "diff_sampler" = 1 on the same respaced schedule, index =
+ *   respaced t, each [n_steps]: acp = cumulative alpha product, acp_prev = that of the step before (1 at t = 0), both as the driver holds them in double;
+ *   sigma = eta sqrt((1 - acp_prev) / (1 - acp)) sqrt(1 - acp / acp_prev), c_x0 = sqrt(acp_prev), c_eps = sqrt(1 - acp_prev - sigma^2), evaluated in double and
+ *   narrowed to the floats the update kernel reads. TTS_ERR_ARG for n_steps < 2 or eta outside [0, 1]. */
+int tts_host_schedule_ddim(int n_steps, double eta, double *acp, double *acp_prev, float *c_x0, float *c_eps, float *sigma);
 int tts_host_schedule(int n_steps, int32_t *timestep_map, float *max_log, float *min_log, float *cfk, float *sqrt_recip,
                       float *sqrt_recipm1, float *coef1, float *coef2);
 void tts_host_timestep_embedding(int t, float *out1024);

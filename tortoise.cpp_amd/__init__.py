@@ -22,6 +22,7 @@ NOISE_REFERENCE, NOISE_DEVICE = 0, 1
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
+_f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
 
 
 def build(verbose=False):
@@ -79,7 +80,7 @@ def lib():
         "tts_vocoder": (ci, [vp, _f32p, _i32p, ci, vp, ci, _f32p]),
         "tts_vocoder_chunk": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p, C.POINTER(ci)]),
         "tts_write_wav": (ci, [C.c_char_p, _f32p, C.c_int64, ci]),
-        "tts_host_schedule": (ci, [ci, _i32p] + [_f32p] * 7), "tts_host_timestep_embedding": (None, [ci, _f32p]),
+        "tts_host_schedule": (ci, [ci, _i32p] + [_f32p] * 7), "tts_host_schedule_ddim": (ci, [ci, C.c_double, _f64p, _f64p, _f32p, _f32p, _f32p]), "tts_host_timestep_embedding": (None, [ci, _f32p]),
         "tts_host_rel_bucket": (ci, [ci, ci]), "tts_host_pad_codes": (ci, [_i32p, ci, _i32p]), "tts_host_trimmed_rows": (ci, [_i32p]),
         "tts_host_fp8_e4m3": (C.c_uint8, [cf]), "tts_host_mel_frames": (ci, [C.c_int64]),
         "tts_host_mel_diffusion100": (ci, [_f32p, C.c_int64, ci, _f32p]), "tts_host_mel_voice80": (ci, [_f32p, C.c_int64, vp, _f32p]),
@@ -376,7 +377,8 @@ class Engine:
         return out
 
     def diffusion(self, latents_list, n_steps=80, noise=None, noise_mode=NOISE_REFERENCE, voice_latents=None, voice_of_candidate=None):
-        """latents_list: list of [L_c,1024]. noise: list of [(n_steps+1), 100*T_c] or None. Returns list of mel [100,T_c].
+        """latents_list: list of [L_c,1024]. noise: list of [(n_steps+1), 100*T_c] or None (option diff_sampler = 1 with ddim_eta = 0: list of x_T [100*T_c]).
+        Returns list of mel [100,T_c]. The sampler, its eta and the guidance strength are engine options (set_option: diff_sampler, ddim_eta, cond_free_k).
         voice_latents [V, 2048] + voice_of_candidate [B]: candidate c is conditioned on voice_latents[voice_of_candidate[c]] instead of the loaded model's
         latent (tts_diffusion_multi_voice)."""
         rows = np.array([len(l) for l in latents_list], np.int32)
@@ -444,6 +446,17 @@ def host_schedule(n_steps):
     if rc:
         raise TtsError("tts_host_schedule failed (%d)" % rc)
     return tm, dict(zip(HOST_SCHED_KEYS, arrs))
+
+
+def host_schedule_ddim(n_steps, eta=0.0):
+    """The DDIM scalars of option diff_sampler = 1 (host arithmetic, no device needed), index = respaced t: dict of acp, acp_prev (float64), c_x0, c_eps,
+    sigma (float32)."""
+    acp, prev = np.empty(n_steps, np.float64), np.empty(n_steps, np.float64)
+    f = [np.empty(n_steps, np.float32) for _ in range(3)]
+    rc = lib().tts_host_schedule_ddim(n_steps, float(eta), acp, prev, *f)
+    if rc:
+        raise TtsError("tts_host_schedule_ddim failed (%d)" % rc)
+    return dict(acp=acp, acp_prev=prev, c_x0=f[0], c_eps=f[1], sigma=f[2])
 
 
 def host_timestep_embedding(t):

@@ -2,6 +2,7 @@
 #include "common.h"
 #include <sched.h>
 #include <cctype>
+#include <cmath>
 #include <algorithm>
 #include <chrono>
 #include <fstream>
@@ -186,6 +187,18 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
   else if (k == "ar_weights") {
     if (value != 0 && value != 1 && value != 2) return fail(c, TTS_ERR_ARG, "ar_weights: 0 (f32), 1 (fp16) or 2 (fp8 e4m3)");
     c->ar_weights = (int)value;
+  }
+  else if (k == "diff_sampler") { // additions within version 8: the sampler of tts_diffusion / tts_diffusion_multi_voice
+    if (value != 0 && value != 1) return fail(c, TTS_ERR_ARG, "diff_sampler: 0 (ancestral DDPM) or 1 (DDIM)");
+    c->diff_sampler = (int)value;
+  }
+  else if (k == "ddim_eta") {
+    if (!(value >= 0 && value <= 1)) return fail(c, TTS_ERR_ARG, "ddim_eta: a value in [0, 1]");
+    c->ddim_eta = value;
+  }
+  else if (k == "cond_free_k") {
+    if (!std::isfinite(value) || value < 0 || !std::isfinite((float)value)) return fail(c, TTS_ERR_ARG, "cond_free_k: a finite value >= 0");
+    c->cond_free_k = (float)value;
   }
   else if (k == "prof_eager_every") c->prof_eager_every = value < 1 ? 1 : (int)value;
   else if (k == "stream_cus") {

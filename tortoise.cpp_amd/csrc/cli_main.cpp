@@ -35,6 +35,10 @@
 //   tts_vocoder call and their audio is written to --output in message order as ONE file. --diffusion-latent: none (every speaker uses the model's own latent)
 //   or one per --voice; anything else is a usage error (exit 1) before a model is loaded. Not with --devices > 1: the conditioning broadcast carries one voice.
 //   --dry-run 1 prints one line per chunk ("chunk k: voice v, n text ids") and exits 0.
+// --sampler ddpm|ddim (default ddpm = the reference's ancestral loop; ddim = upstream tortoise-tts' ddim_sample, option diff_sampler), --ddim-eta <x> (0 .. 1, default 0 =
+//   deterministic) and --cond-free-k <x> (guidance strength, default 2.0): the diffusion sampler behind --steps, which keeps its meaning. Another sampler name or a value
+//   out of range is a usage error (exit 1) before a model is loaded or a worker started. --devices N workers receive the flags with the rest of the command line;
+//   --timing 1 echoes them ("[timing] sampler ...", one line per process).
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -69,6 +73,9 @@ int main(int argc, char **argv) {
   bool timing = false;
   int test_fail_shard = -1, test_slow_shard = -1;
   std::vector<std::pair<std::string, double>> engine_options; // --option key=value (repeatable): tts_set_option before the models are loaded
+  std::string sampler = "ddpm";
+  double ddim_eta = 0.0, cond_free_k = 2.0;
+  bool have_sampler = false, have_eta = false, have_k = false; // a flag that is absent leaves the engine's option (default, or --option) alone
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
   for (int i = 1; i < argc - 1; ++i) {
     std::string a(argv[i]);
@@ -98,6 +105,9 @@ int main(int argc, char **argv) {
     }
     else if (a == "--diffusion-latent") { diffLatentPath = argv[i + 1]; diffLatentPaths.push_back(diffLatentPath); }
     else if (a == "--split-text") split_ids = std::stoi(argv[i + 1]);
+    else if (a == "--sampler") { sampler = argv[i + 1]; have_sampler = true; }
+    else if (a == "--ddim-eta") { ddim_eta = std::atof(argv[i + 1]); have_eta = true; }
+    else if (a == "--cond-free-k") { cond_free_k = std::atof(argv[i + 1]); have_k = true; }
     else if (a == "--rccl-id") rccl_id = argv[i + 1]; // worker mode (set by the parent)
     else if (a == "--shard") { // worker mode (set by the parent): "r/N"
       std::string v(argv[i + 1]);
@@ -106,6 +116,9 @@ int main(int argc, char **argv) {
     }
   }
   if (exchange != "files" && exchange != "rccl") { fprintf(stderr, "--exchange %s: files or rccl\n", exchange.c_str()); return 1; }
+  if (sampler != "ddpm" && sampler != "ddim") { fprintf(stderr, "--sampler %s: ddpm or ddim\n", sampler.c_str()); return 1; }
+  if (!(ddim_eta >= 0.0 && ddim_eta <= 1.0)) { fprintf(stderr, "--ddim-eta %g: a value in 0 .. 1\n", ddim_eta); return 1; }
+  if (!(cond_free_k >= 0.0) || !std::isfinite(cond_free_k)) { fprintf(stderr, "--cond-free-k %g: a finite value >= 0\n", cond_free_k); return 1; }
   if (split_ids != 0 && (devices > 1 || exchange == "rccl" || shard >= 0)) {
     fprintf(stderr, "--split-text cannot be combined with --devices > 1 or --exchange rccl (one process runs all chunks)\n");
     return 1;
@@ -244,6 +257,13 @@ int main(int argc, char **argv) {
   if (have_seed) tts_seed(ctx, (uint32_t)seed);
   for (const auto &kv : engine_options)
     if (tts_set_option(ctx, kv.first.c_str(), kv.second)) return die(ctx, "--option");
+  if ((have_sampler && tts_set_option(ctx, "diff_sampler", sampler == "ddim" ? 1.0 : 0.0)) || (have_eta && tts_set_option(ctx, "ddim_eta", ddim_eta)) ||
+      (have_k && tts_set_option(ctx, "cond_free_k", cond_free_k)))
+    return die(ctx, "--sampler");
+  if (timing) {
+    if (shard >= 0) fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d (worker %d/%d)\n", sampler.c_str(), ddim_eta, cond_free_k, steps, shard, nshards);
+    else fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d\n", sampler.c_str(), ddim_eta, cond_free_k, steps);
+  }
   if (shard >= 0) {
     tts_set_option(ctx, "rng_shard_offset", (double)(shard * candidates));
     tts_set_option(ctx, "rng_shard_total", (double)total_candidates);

@@ -153,6 +153,9 @@ struct tts_ctx {
   int attn_q64 = 0; // option "attn_q64": diffusion attention with 64-query workgroups: 0 never (default: measured, no gain), 1 always, 2 = when the 128-query grid has at most 256 workgroups (bit-identical)
   int hoist_integrator = 1; // option "hoist_integrator": small diffusion batches evaluate the conditioning_timestep_integrator layers (which never see x_t) for all sampling steps before the loop, in benchmark-sized batches (bit-identical; 0 = inside every step)
   int latency_mode = 0;    // option "latency_mode": small diffusion batches (<= 2 048 packed rows) take the GroupNorm statistics from the producing GEMM's epilogue (diffusion.hip: gn_apply_kernel); not bit-identical to the batch path
+  int diff_sampler = 0;    // option "diff_sampler": 0 = the reference's ancestral DDPM step (ddpm_update_kernel), 1 = DDIM (ddim_update_kernel; upstream tortoise-tts' ddim_sample)
+  double ddim_eta = 0;     // option "ddim_eta" in [0, 1]: 0 = deterministic DDIM (only x_T is noise); read only when diff_sampler = 1
+  float cond_free_k = 2.0f; // option "cond_free_k": the conditioning-free guidance strength at t = n (main.cpp's base_k = 2.0), both samplers
   bool capturing = false;  // a hipGraph is being captured on the stream: ProfScope records nothing (event records would become graph nodes)
   int diff_graph = 1;      // option "diff_graph": the diffusion step is captured once per call and replayed (0: every step launched eagerly)
   int prof_eager_every = 8; // while a diff_* family is profiled, every Nth diffusion step runs eagerly with its event pairs; the others replay the graph
@@ -347,7 +350,13 @@ struct DiffSchedule {
   std::vector<int> timestep_map;
   // per sampled step t (already cast the way the reference casts them for the update)
   std::vector<float> max_log, min_log, cfk, sqrt_recip, sqrt_recipm1, coef1, coef2;
+  float base_k = 2.0; // conditioning-free guidance strength (option "cond_free_k"; set before build)
+  std::vector<double> acp, prev; // cumulative alpha product of the respaced schedule and of the step before (1 at t = 0)
   void build(int n_steps);
+  // DDIM (upstream tortoise-tts ddim_sample; not in the reference): x_{t-1} = c_x0 x0 + c_eps eps + sigma z. After build(); eta in [0, 1].
+  std::vector<double> ddim_sigma, ddim_c_x0, ddim_c_eps; // double tables, float at the point of use
+  std::vector<float> c_x0, c_eps, sigma;
+  void build_ddim(double eta);
 };
 void timestep_embedding(int t, float *out1024);
 int rel_bucket(int i, int c);

@@ -795,6 +795,47 @@ __global__ __launch_bounds__(128) void ddpm_update_kernel(const float *__restric
   x[xi] = outv;
 }
 
+// DDIM step (upstream tortoise-tts ddim_sample on p_mean_variance with clip_denoised; the reference has no such sampler) for every candidate, in place on x: the grid,
+// block and indexing of ddpm_update_kernel, the same StepEntry (guidance k, sqrt_recip, sqrt_recipm1, noise block, generator key) plus this step's DdimEntry.
+// Channels 100..199 of net (the learned variance) are not read. Every f32 operation is rounded once (no FMA contraction), for the reason ddpm_update_kernel gives:
+// the numpy restatement the tests hold this kernel to performs exactly these roundings.
+struct DdimEntry { float c_x0, c_eps, sigma, pad; };
+__global__ __launch_bounds__(128) void ddim_update_kernel(const float *__restrict__ net, float *__restrict__ x,
+                                                          const int64_t *__restrict__ x_off, const int *__restrict__ row_seq,
+                                                          const int *__restrict__ row_t, const int *__restrict__ seq_len,
+                                                          const int *__restrict__ seq_start, int ncand, const StepEntry *__restrict__ tab,
+                                                          const DdimEntry *__restrict__ dtab, const int *__restrict__ ctr,
+                                                          const float *__restrict__ noise_base /* or null */, uint64_t seed,
+                                                          uint32_t stream0 /* global id of candidate 0 */) {
+  const int r = blockIdx.x, s = row_seq[r], ch = threadIdx.x;
+  if (s < 0 || s >= ncand || ch >= 100) return;
+  const int k = *ctr;
+  const StepEntry e = tab[k];
+  const StepScalars sc = e.sc;
+  const DdimEntry d = dtab[k];
+  const float *noise = e.has_noise ? noise_base + e.noise_off : nullptr; // same layout as x
+  const int T = seq_len[s], t = row_t[r];
+  const size_t xi = x_off[s] + (size_t)ch * T + t;
+  const float eps_c = net[(size_t)r * 256 + ch];
+  const float eps_u = net[(size_t)(seq_start[s + ncand] + t) * 256 + ch];
+  const float xv = x[xi];
+  float outv;
+  {
+#pragma clang fp contract(off)
+    const float eps_g = (1 + sc.cfk) * eps_c - sc.cfk * eps_u;
+    const float xs = sc.sqrt_recip * xv;
+    float x0 = xs - sc.sqrt_recipm1 * eps_g;
+    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float eps_h = (xs - x0) / sc.sqrt_recipm1; // always re-derived from the clipped x0, as upstream (_predict_eps_from_xstart)
+    outv = d.c_x0 * x0 + d.c_eps * eps_h;
+    if (!sc.is_last && d.sigma != 0.0f) {
+      const float nz = noise ? noise[xi] : philox_normal(seed, stream0 + (uint32_t)s, e.philox_step, (uint32_t)(ch * T + t));
+      outv = outv + d.sigma * nz;
+    }
+  }
+  x[xi] = outv;
+}
+
 __global__ void philox_fill_kernel(float *__restrict__ x, int64_t n, uint64_t seed, uint32_t stream, uint32_t step) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) x[i] = philox_normal(seed, stream, step, (uint32_t)i);
@@ -936,6 +977,7 @@ struct DiffState {
   int gn_site = 0, gn_sites_max = 0;
   size_t gn_slot_ll = 0, gn_stripe_ll = 0; // long longs per slot = FX_STRIPES stripes x (sequences x 32 groups x 4)
   long long *new_stats_slot() { long long *p = gn_stats.as<long long>() + (size_t)gn_site * gn_slot_ll; gn_site++; return p; }
+  DevBuf ddim_tab; // DdimEntry[n_steps] (option diff_sampler = 1)
   DevBuf step_tab, step_ctr, ss_cur; // StepEntry[n_steps] | int step counter | this step's scale/shift block (fixed address)
   hipGraph_t step_graph = nullptr;
   hipGraphExec_t step_exec = nullptr;
@@ -2007,8 +2049,14 @@ int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, 
   if (timing) (void)hipStreamSynchronize(ctx->stream);
   const auto t_setup = now();
   Layout &lay = st->lay;
+  // option diff_sampler: 0 = the reference's ancestral step, 1 = DDIM. Deterministic DDIM (ddim_eta = 0) has ONE noise vector per candidate, x_T: n_vec = 1 below
+  // (no per-step block is drawn, allocated or uploaded); with eta > 0 layout, draw order and generator keys are those of the ancestral sampler.
+  const bool ddim = ctx->diff_sampler == 1;
+  const int n_vec = ddim && ctx->ddim_eta == 0 ? 1 : n_steps + 1;
   DiffSchedule sched;
+  sched.base_k = ctx->cond_free_k;
   sched.build(n_steps);
+  if (ddim) sched.build_ddim(ctx->ddim_eta);
   std::vector<int> ts(n_steps);
   for (int idx = 0; idx < n_steps; idx++) ts[idx] = sched.timestep_map[n_steps - 1 - idx]; // time_embedding_{idx} (5819-5825)
   CHECK(precompute_time(ctx, st, ts));
@@ -2028,7 +2076,7 @@ int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, 
   // order (x_T, then step after step), the stream orders copy k + 1 in front of step k's update kernel. More candidates draw candidate after candidate
   // (main.cpp:5638, 6020-6021): their order does not allow it.
   bool pipe_noise = host_noise && !noise && B == 1 && ctx->noise_pipeline != 0;
-  if (pipe_noise && st->noise_host.reserve((size_t)total * (n_steps + 1) * 4) != hipSuccess) { (void)hipGetLastError(); pipe_noise = false; }
+  if (pipe_noise && st->noise_host.reserve((size_t)total * n_vec * 4) != hipSuccess) { (void)hipGetLastError(); pipe_noise = false; }
   auto draw_block = [&](int k) { // block k of the one candidate into the pinned buffer, then on its way to the device
     float *dst = st->noise_host.as<float>() + (size_t)k * total;
     rng_normal_fill(ctx, dst, total);
@@ -2036,22 +2084,22 @@ int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, 
   };
   std::vector<float> hn;
   if (pipe_noise) {
-    TTS_HIP(ctx, st->noise.reserve((size_t)total * (n_steps + 1) * 4));
+    TTS_HIP(ctx, st->noise.reserve((size_t)total * n_vec * 4));
     TTS_HIP(ctx, draw_block(0));
     TTS_HIP(ctx, hipMemcpyAsync(st->xbuf.p, st->noise.p, total * 4, hipMemcpyDeviceToDevice, ctx->stream));
   } else if (host_noise) {
     // per step a [cand][100][T] block in the layout of x: block 0 = x_T, block 1+idx = step idx
-    hn.resize((size_t)total * (n_steps + 1));
-    if (noise) { // caller layout: per candidate (n_steps+1) consecutive vectors
+    hn.resize((size_t)total * n_vec);
+    if (noise) { // caller layout: per candidate n_vec = (n_steps+1) consecutive vectors (deterministic DDIM: x_T alone)
       size_t src = 0;
       for (int c = 0; c < B; c++)
-        for (int k = 0; k <= n_steps; k++) {
+        for (int k = 0; k < n_vec; k++) {
           memcpy(hn.data() + (size_t)k * total + xoff[c], noise + src, (size_t)100 * lay.len[c] * 4);
           src += (size_t)100 * lay.len[c];
         }
     } else { // the reference's draw order, candidate after candidate (main.cpp:5638, 6020-6021)
       for (int c = 0; c < B; c++)
-        for (int k = 0; k <= n_steps; k++) {
+        for (int k = 0; k < n_vec; k++) {
           float *dst = hn.data() + (size_t)k * total + xoff[c];
           rng_normal_fill(ctx, dst, (int64_t)100 * lay.len[c]);
         }
@@ -2074,7 +2122,7 @@ int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, 
     const int t = n_steps - 1 - idx;
     tab[idx].sc = StepScalars{sched.max_log[t], sched.min_log[t], sched.cfk[t], sched.sqrt_recip[t], sched.sqrt_recipm1[t],
                               sched.coef1[t], sched.coef2[t], t == 0 ? 1 : 0};
-    tab[idx].has_noise = host_noise ? 1 : 0;
+    tab[idx].has_noise = host_noise && n_vec > 1 ? 1 : 0;
     tab[idx].noise_off = (long long)(idx + 1) * total;
     tab[idx].philox_step = (unsigned)idx;
     tab[idx].pad = 0;
@@ -2083,6 +2131,15 @@ int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, 
   TTS_HIP(ctx, st->step_ctr.reserve(64));
   TTS_HIP(ctx, st->ss_cur.reserve(ss_stride * 4));
   TTS_HIP(ctx, hipMemcpyAsync(st->step_tab.p, tab.data(), tab.size() * sizeof(StepEntry), hipMemcpyHostToDevice, ctx->stream));
+  std::vector<DdimEntry> dtab(ddim ? n_steps : 0);
+  if (ddim) {
+    for (int idx = 0; idx < n_steps; idx++) {
+      const int t = n_steps - 1 - idx;
+      dtab[idx] = DdimEntry{sched.c_x0[t], sched.c_eps[t], sched.sigma[t], 0.f};
+    }
+    TTS_HIP(ctx, st->ddim_tab.reserve(dtab.size() * sizeof(DdimEntry)));
+    TTS_HIP(ctx, hipMemcpyAsync(st->ddim_tab.p, dtab.data(), dtab.size() * sizeof(DdimEntry), hipMemcpyHostToDevice, ctx->stream));
+  }
   TTS_HIP(ctx, hipMemsetAsync(st->step_ctr.p, 0, 64, ctx->stream));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // `tab` is a host vector: the copy must have read it before it goes out of scope
   // One sampling step, identical for every step (all per-step values are read through the device counter): launched eagerly or
@@ -2095,6 +2152,12 @@ int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, 
     CHECK(network_forward(ctx, st, st->ss_cur.as<float>()));
     {
       ProfScope ps(ctx, "diff_update");
+      if (ddim)
+        ddim_update_kernel<<<lay.rows, 128, 0, ctx->stream>>>(
+            st->net.as<float>(), st->xbuf.as<float>(), st->xoff.as<int64_t>(), lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(),
+            lay.d_len.as<int>(), lay.d_start.as<int>(), B, st->step_tab.as<StepEntry>(), st->ddim_tab.as<DdimEntry>(), st->step_ctr.as<int>(),
+            host_noise && n_vec > 1 ? st->noise.as<float>() : nullptr, ctx->seed_value, (uint32_t)shard_base(ctx));
+      else
       ddpm_update_kernel<<<lay.rows, 128, 0, ctx->stream>>>(
           st->net.as<float>(), st->xbuf.as<float>(), st->xoff.as<int64_t>(), lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(),
           lay.d_len.as<int>(), lay.d_start.as<int>(), B, st->step_tab.as<StepEntry>(), st->step_ctr.as<int>(),
@@ -2127,7 +2190,7 @@ int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, 
   }
   for (int idx = 0; idx < n_steps; idx++) {
     const bool eager = !use_graph || (prof_diff && idx % ctx->prof_eager_every == 0);
-    if (pipe_noise) TTS_HIP(ctx, draw_block(idx + 1)); // read by this step's update kernel
+    if (pipe_noise && n_vec > 1) TTS_HIP(ctx, draw_block(idx + 1)); // read by this step's update kernel (deterministic DDIM: block 0 = x_T was the only one)
     if (eager) CHECK(enqueue_step());
     else TTS_HIP(ctx, hipGraphLaunch(st->step_exec, ctx->stream));
   }

@@ -764,7 +764,8 @@ void DiffSchedule::build(int n_steps) {
     prod = (i == 0) ? alpha : prod * alpha;
     acp4000[i] = prod;
   }
-  std::vector<double> beta(n), acp(n), prev(n), pvar(n), plv(n);
+  std::vector<double> beta(n), pvar(n), plv(n);
+  acp.assign(n, 0.0); prev.assign(n, 0.0);
   float last = 1.0; // float on purpose (main.cpp:5663)
   for (int k = 0; k < n; k++) {
     beta[k] = 1 - (acp4000[timestep_map[k]] / last);
@@ -782,7 +783,6 @@ void DiffSchedule::build(int n_steps) {
   for (int k = 1; k < n; k++) plv[k] = std::log(pvar[k]);
   max_log.resize(n); min_log.resize(n); cfk.resize(n); sqrt_recip.resize(n); sqrt_recipm1.resize(n);
   coef1.resize(n); coef2.resize(n);
-  const float base_k = 2.0;
   for (int t = 0; t < n; t++) {
     max_log[t] = std::log(beta[t]);
     min_log[t] = plv[t];
@@ -791,6 +791,20 @@ void DiffSchedule::build(int n_steps) {
     sqrt_recipm1[t] = std::sqrt(1.0f / acp[t] - 1);
     coef1[t] = beta[t] * std::sqrt(prev[t]) / (1.0 - acp[t]);
     coef2[t] = (1.0 - prev[t]) * std::sqrt(1.0 - beta[t]) / (1.0 - acp[t]);
+  }
+}
+
+// DDIM per-step scalars (Song et al. 2021 eq. 12 / 16, as upstream tortoise-tts' ddim_sample states them) on the respaced schedule of build().
+// At t = 0 (prev = 1): sigma = 0, c_x0 = 1, c_eps = 0. For eta <= 1 the argument of the last root is acp (1 - prev)^2 / ((1 - acp) prev) >= 0 at eta = 1 and
+// grows as eta falls.
+void DiffSchedule::build_ddim(double eta) {
+  ddim_sigma.resize(n); ddim_c_x0.resize(n); ddim_c_eps.resize(n);
+  c_x0.resize(n); c_eps.resize(n); sigma.resize(n);
+  for (int t = 0; t < n; t++) {
+    ddim_sigma[t] = eta * std::sqrt((1.0 - prev[t]) / (1.0 - acp[t])) * std::sqrt(1.0 - acp[t] / prev[t]);
+    ddim_c_x0[t] = std::sqrt(prev[t]);
+    ddim_c_eps[t] = std::sqrt(std::max(0.0, 1.0 - prev[t] - ddim_sigma[t] * ddim_sigma[t]));
+    sigma[t] = (float)ddim_sigma[t]; c_x0[t] = (float)ddim_c_x0[t]; c_eps[t] = (float)ddim_c_eps[t];
   }
 }
 
@@ -903,6 +917,17 @@ extern "C" int tts_host_schedule(int n_steps, int32_t *timestep_map, float *max_
     max_log[t] = s.max_log[t]; min_log[t] = s.min_log[t]; cfk[t] = s.cfk[t];
     sqrt_recip[t] = s.sqrt_recip[t]; sqrt_recipm1[t] = s.sqrt_recipm1[t];
     coef1[t] = s.coef1[t]; coef2[t] = s.coef2[t];
+  }
+  return TTS_OK;
+}
+extern "C" int tts_host_schedule_ddim(int n_steps, double eta, double *acp, double *acp_prev, float *c_x0, float *c_eps, float *sigma) {
+  if (n_steps < 2 || !(eta >= 0.0 && eta <= 1.0) || !acp || !acp_prev || !c_x0 || !c_eps || !sigma) return TTS_ERR_ARG; // (a NaN eta fails both comparisons)
+  tts::DiffSchedule s;
+  s.build(n_steps);
+  s.build_ddim(eta);
+  for (int t = 0; t < n_steps; t++) {
+    acp[t] = s.acp[t]; acp_prev[t] = s.prev[t];
+    c_x0[t] = s.c_x0[t]; c_eps[t] = s.c_eps[t]; sigma[t] = s.sigma[t];
   }
   return TTS_OK;
 }
