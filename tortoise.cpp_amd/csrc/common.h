@@ -137,8 +137,8 @@ struct tts_ctx {
   int ar_weights = 0;      // option "ar_weights": 0 = f32 weights in the decode step (reference numerics), 1 = fp16 weights, 2 = OCP fp8 (e4m3) weights with a power-of-two scale per output column (set before tts_load_ar)
   int dec_f32_mfma = 0;    // option "dec_f32_mfma": the decode step's LayerNorm-GEMVs use exact-f32 MFMA products instead of split fp16 (set before tts_load_ar; +1 us per launch)
   int attn_f32 = 0;        // option "attn_f32": the diffusion AttentionBlock in reference precision (F32 QK^T / softmax / PV / proj_out, main.cpp:3848-3875) via split-fp16 MFMA operands; 0 = fp16 operands (throughput mode)
-  static constexpr int GEMM_WREG_ALL = 3;
-  int gemm_wreg = GEMM_WREG_ALL; // option "gemm_wreg": classes of diffusion GEMMs whose weight operand is streamed into registers from its fragment-major image (bit 0: k = 1 in_layers, bit 1: QKV projection); 0 = the LDS-staged kernels
+  static constexpr int GEMM_WREG_ALL = 7;
+  int gemm_wreg = GEMM_WREG_ALL; // option "gemm_wreg": classes of diffusion GEMMs whose weight operand is streamed into registers from its fragment-major image (bit 0: k = 1 in_layers, bit 1: QKV projection, bit 2: k = 3 out_layers); 0 = the LDS-staged kernels
   int proj_dual_b = 1;     // option "proj_dual_b" (developer A/B): the split-weight proj_out GEMM stages both weight halves per activation tile (1) or runs two K segments (0)
   int attn_f32_drop = 0;   // option "attn_f32_drop" (developer ablation inside attn_f32 = 1): bit 0 q/k, bit 1 v, bit 2 attention output lose their low halves (= the fp16 rounding of the default mode, one operand at a time)
   int lc_attn_f32 = 1;     // option "lc_attn_f32": the latent conditioner's AttentionBlocks (once per utterance; their output enters every step) in reference precision whatever attn_f32 says; 0 = follow attn_f32 (rounds 1-4)

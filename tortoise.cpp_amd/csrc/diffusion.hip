@@ -860,7 +860,7 @@ struct AttnDev {
   __half *proj_w_split; // [C][hi(s w) | lo(s w)]: proj_out's F32 weight as a split-precision pair; s = 1 / proj_alpha keeps the low halves normal
   float proj_alpha;     // 1 / s, s = the largest power of two with max|W| s < 30000 (64 for |W| up to 468; round 6: was a fixed 64, whose hi half overflows at |W| > 1023)
 };
-struct ResDev { float *in_g, *in_b, *in_bias, *emb_w, *emb_b, *out_g, *out_b, *out_bias; __half *in_w, *out_w, *in_wf; }; // in_wf: fragment-major image of in_w
+struct ResDev { float *in_g, *in_b, *in_bias, *emb_w, *emb_b, *out_g, *out_b, *out_bias; __half *in_w, *out_w, *in_wf, *out_wf; }; // in_wf: fragment-major image of in_w; out_wf: the per-tap images of out_w (gemm_wfrag3_index)
 
 // Packed row layout: sequence s occupies rows [start[s], start[s]+len[s]); start % 8 == 0; at least one
 // zero guard row before and after every sequence; total padded to a multiple of 128.
@@ -1037,7 +1037,7 @@ struct Loader { // its jobs run on several threads (common.h: run_parallel): `us
     return put(t->data, dst);
   }
   // conv weight file layout w[(co*cin + ci)*k + tap] -> fp16 [co_pad][tap*cin_pad + ci] (zero padded)
-  // dst_frag (k = 1 only): also the fragment-major image that gemm_f16_wreg_kernel streams into registers
+  // dst_frag: also the fragment-major image that gemm_f16_wreg_kernel (k = 1) / gemm_f16_conv3_wreg_kernel (k = 3: one image per tap) streams into registers
   int conv16(const std::string &name, int cout, int cin, int k, int cout_pad, int cin_pad, __half **dst, __half **dst_frag = nullptr) {
     const HostTensor *t = get(name, (int64_t)cout * cin * k);
     if (!t) return TTS_ERR_FORMAT;
@@ -1050,7 +1050,8 @@ struct Loader { // its jobs run on several threads (common.h: run_parallel): `us
     if (dst_frag) {
       std::vector<__half> f(h.size());
       for (int n = 0; n < cout_pad; n++)
-        for (int c = 0; c < cin_pad; c++) f[gemm_wfrag_index(n, c, cin_pad)] = h[(size_t)n * cin_pad + c];
+        for (int tap = 0; tap < k; tap++)
+          for (int c = 0; c < cin_pad; c++) f[gemm_wfrag3_index(n, tap, c, cout_pad, cin_pad)] = h[((size_t)n * k + tap) * cin_pad + c]; // k = 1: gemm_wfrag_index
       if (int r = put(f, dst_frag)) return r;
     }
     return put(h, dst);
@@ -1114,7 +1115,7 @@ struct Loader { // its jobs run on several threads (common.h: run_parallel): `us
     if ((r = f32(p + ".emb_layers.1.bias", 2 * C, &w.emb_b))) return r;
     if ((r = f32(p + ".out_layers.0.weight", C, &w.out_g))) return r;
     if ((r = f32(p + ".out_layers.0.bias", C, &w.out_b))) return r;
-    if ((r = conv16(p + ".out_layers.3.weight", C, C, 3, C, C, &w.out_w))) return r;
+    if ((r = conv16(p + ".out_layers.3.weight", C, C, 3, C, C, &w.out_w, &w.out_wf))) return r;
     if ((r = f32(p + ".out_layers.3.bias", C, &w.out_bias))) return r;
     return TTS_OK;
   }
@@ -1258,7 +1259,8 @@ static int gemm(tts_ctx *ctx, const char *fam, GemmArgs &g, const Layout &lay, i
   return TTS_OK;
 }
 
-// option gemm_wreg (bit 0: k = 1 in_layers, bit 1: QKV projection): does this class stream its weight through registers (gemm_f16_wreg_kernel)
+// option gemm_wreg (bit 0: k = 1 in_layers, bit 1: QKV projection, bit 2: k = 3 out_layers): does this class stream its weight through registers
+// (gemm_f16_wreg_kernel, gemm_f16_conv3_wreg_kernel)
 static int gemm_wreg_class(const tts_ctx *ctx, int bit) { return (ctx->gemm_wreg & bit) ? 1 : 0; }
 // the image of a weight with a fragment-major copy that the GEMM of this layout will stream (for the GroupNorm's weight touch)
 static const __half *gemm_wreg_image(const tts_ctx *ctx, int bit, const Layout &lay, int N, const __half *w, const __half *wf) {
@@ -1627,9 +1629,11 @@ static int res_block(tts_ctx *ctx, DiffState *st, const Layout &lay, Work &wk, f
   }
   DBG_SUM("res.out ss", ss, (size_t)2 * C * 4);
   DBG_SUM("res.out hpre", Hpre, (size_t)lay.rows * C * 4);
-  CHECK(gn(ctx, st, lay, Hpre, lat ? st_h : nullptr, w.out_g, w.out_b, ss, 1, wk.A16(), w.out_w, (size_t)3 * C * C * 2));
+  // the weight the GEMM below will read: the per-tap images where gemm_f16_conv3_wreg_kernel takes it (F32 output, 128-row tiles)
+  CHECK(gn(ctx, st, lay, Hpre, lat ? st_h : nullptr, w.out_g, w.out_b, ss, 1, wk.A16(), lat ? w.out_w : gemm_wreg_image(ctx, 4, lay, C, w.out_w, w.out_wf), (size_t)3 * C * C * 2));
   DBG_SUM("res.out gn", wk.A16(), (size_t)lay.rows * C * 2);
   GemmArgs c3 = gemm_base(lay, wk.A16(), C, 3, C, w.out_w, C, w.out_bias);
+  c3.Wf = w.out_wf; c3.wreg = gemm_wreg_class(ctx, 4);
   long long *st_out = lat ? st->new_stats_slot() : nullptr;
   c3.mode = st_out ? GEMM_OUT_F32_STATS : GEMM_OUT_F32; c3.outF = X; c3.ldo = C; c3.resid = xin;
   c3.st_out = st_out; c3.st_stripe_ll = (int)st->gn_stripe_ll; c3.chunk_seq = lay.d_chunk_seq.as<int>();

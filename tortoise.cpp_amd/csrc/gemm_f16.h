@@ -12,7 +12,7 @@
 // Kernels. All of them: (16 h) x 128 x 64 tiles (h = 1..8 sixteen-row blocks, a launch parameter), 4 waves, the tile walk of gemm_vh_tile, operands staged
 // by direct global->LDS DMA (global_load_lds_dwordx4) into a lane-linear image whose 16-byte chunks are XOR-swizzled on the SOURCE
 // address, so ds_read_b128 fragment reads spread over all banks, f32 accumulators that may start from the residual, and one epilogue family (gemm_epilogue_vh for the
-// 2 x 2 kernels, its copy gemm_epilogue_wreg for the 1 x 4 layout). gemm_dma_off gives the DMA offsets of the vh, dual-B and wreg bodies and gemm_acc_start the
+// 2 x 2 kernels, its copies gemm_epilogue_wreg / gemm_epilogue_conv3_wreg for the 1 x 4 layout). gemm_dma_off gives the DMA offsets of the vh, dual-B and wreg bodies and gemm_acc_start the
 // accumulator start of the vh and wreg bodies; the dual-B start, the k = 3 offsets, the dual-B body and the wreg epilogue are copies, kept apart for the registers
 // unifying them cost (see the comment at each; profiles/gemm_refactor_isa.txt). The three 2 x 2 kernels run one body per number of 16-row blocks of the calling
 // wave (gemm_for_my_mi). What differs:
@@ -23,7 +23,10 @@
 //                             the WEIGHT operand never touches LDS — each wave loads its MFMA fragments from a fragment-major image built at load time, one K tile ahead;
 //                             LDS is a two-slot ring of activation tiles, one raw barrier per K tile. Bit-identical to gemm_f16_vh_kernel. Measured against it in the benchmark
 //                             (profiles/gemm_wreg_same_box_ab.txt): QKV projection 183.0 -> 170.9 us, in_layers 82.2 -> 73.6 us, headline +1.7 %. Adopted for both
-//                             classes (option gemm_wreg); the dual-B and k = 3 kernels were not ported, and a two-tile distance is not instantiated (see the kernel).
+//                             classes (option gemm_wreg); a two-tile distance is not instantiated (see the kernel).
+//   gemm_f16_conv3_wreg_kernel the same move for the k = 3 convolution (F32 output with or without residual, 128-row tiles): per-tap fragment-major weight images, waves 1 x 4,
+//                             weight register sets rotating per tap, LDS = a two-slot ring of activation SLABS (34 KB, 4 workgroups per CU), one raw barrier per 64-channel
+//                             chunk. Bit-identical to gemm_f16_conv3_vh_kernel. The dual-B kernel is not ported.
 // gemm_plan picks between them and chooses h; launch_gemm_f16 launches what it says. Round 3 rewrote the kernels around two measurements
 // (profiles/r3_gemm_tile_tables.txt, profiles/r3_gemm_epilogue.txt):
 //  * tile-height / dispatch-order policies (tables of mixed heights, tallest-first, whole rounds filled exactly) change nothing:
@@ -66,8 +69,8 @@ struct GemmArgs {
   int lda;             // halves
   const __half *W;     // [N][ldw]; segment seg starts at column w_off[seg] (defaults: ldw = nseg*kseg, w_off = seg*kseg)
   int ldw_, w_off_[3], custom_w; // set custom_w = 1 to use ldw_/w_off_ (e.g. split-precision: hi|lo halves reused)
-  const __half *Wf;    // the fragment-major image of W (gemm_wfrag_index), or nullptr
-  int wreg;            // 1 with Wf: stream the weight through registers where gemm_f16_wreg_kernel takes the shape
+  const __half *Wf;    // the fragment-major image of W (one segment: gemm_wfrag_index; the k = 3 convolution: gemm_wfrag3_index), or nullptr
+  int wreg;            // 1 with Wf: stream the weight through registers where gemm_f16_wreg_kernel / gemm_f16_conv3_wreg_kernel takes the shape
   int M, N;            // multiples of 128 (buffers are padded)
   const float *bias;   // [N] or nullptr
   const int *row_seq;  // [M]: sequence id, <0 for guard/padding rows (output forced to 0); may be null
@@ -900,6 +903,193 @@ static inline bool gemm_is_conv3(const GemmArgs &g) {
          !gemm_mode_qkv(g.mode) && !gemm_mode_scaled(g.mode);
 }
 
+// k = 3 convolution with the WEIGHT operand through registers (gemm_f16_conv3_wreg_kernel; GEMM_OUT_F32 with or without residual, 128-row tiles). The move of
+// gemm_f16_wreg_kernel applied to the shared-slab kernel: the loader keeps one fragment-major image per tap,
+//   Wf3[tap][n / 16][k / 32][lane][k % 8]   (gemm_wfrag3_index: tap * N * K + gemm_wfrag_index(n, k, K)),
+// the waves lie 1 x 4 along N (all rows of the tile x 32 columns each, no weight fragment fetched twice) and LDS holds only the activation slab, as a ring of TWO
+// slots of 17 KB (34 KB: four workgroups per CU). Per 64-channel chunk a wave requests its 5 slab pieces (17 pieces over four waves; waves 1-3 repeat piece 16, the
+// same bytes to the same place, so that every wave counts the same vmcnt events) and 3 x 4 weight fragments, against 17 + 48 pieces staged by the LDS kernel, and
+// passes ONE barrier instead of six. The weight registers rotate per PHASE (one tap of one chunk: 4 fragments = 16 VGPRs per set, two sets): a chunk's worth per
+// set (48) does not fit beside 64 accumulator registers in the 128 of four workgroups per CU. Order of a chunk kc (slab slot kc & 1):
+//   tap 0: wait vmcnt(0) [slab kc and W(kc, 0), nothing younger in flight] -> barrier (slab kc complete in every wave's view; every wave has left slot (kc + 1) & 1)
+//          -> request W(kc, 1), THEN slab kc + 1 (vmcnt is one in-order counter: the weights the next phase waits for must be older than the slab) -> multiply
+//   tap 1: wait vmcnt(5) [all but the slab pieces: W(kc, 1)] -> request W(kc, 2) -> multiply          (last chunk: the last slab again, into the free slot)
+//   tap 2: wait vmcnt(0) [slab kc + 1, requested two phases ago, and W(kc, 2)] -> request W(kc + 1, 0) -> multiply
+// Accumulators start from zero and add chunk, tap, K step in the order of gemm_conv3_vh_body, weight fragment first; the epilogue adds bias, then the loaded
+// residual, then zeroes guard rows, as gemm_epilogue_vh<.., EPI_RESID_LOAD> does: bit-identical to gemm_f16_conv3_vh_kernel.
+static inline size_t gemm_wfrag3_index(int n, int tap, int k, int N, int K) { // index (in halves) of tap `tap` of W[n][tap * K + k] in the per-tap fragment-major images
+  return (size_t)tap * N * K + gemm_wfrag_index(n, k, K);
+}
+static constexpr int CONV3_WREG_SLOT = (128 + 8) * 128, CONV3_WREG_LDS = 2 * CONV3_WREG_SLOT;
+
+// gemm_epilogue_wreg's F32 branch with the residual read here: (acc + bias) + resid, guard rows zeroed; blocks in pairs, the next pair's loads in flight while this
+// pair is stored (the order of gemm_epilogue_vh<.., EPI_RESID_LOAD>). resid may alias outF: a lane reads exactly the elements it writes, before it writes them
+template <int MI, bool RESID>
+__device__ __forceinline__ void gemm_epilogue_conv3_wreg(const GemmArgs &g, floatx4 (&acc)[MI][2], int m0, int n0, int nblk, int wave, int fr, int fq) {
+  const int col0 = n0 + wave * 32 + fq * 4;
+  const bool hb = g.bias != nullptr, hs = g.row_seq != nullptr;
+  const float *bp = hb ? g.bias : (const float *)g.W; // unconditional loads, values selected afterwards (see gemm_epilogue_vh)
+  const int *sp = hs ? g.row_seq : (const int *)g.A[0];
+  float4 b4[2], rr[2][2];
+  int sq[MI];
+  auto load_pair = [&](int p) {
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const float *rp = g.resid + (size_t)(m0 + min(2 * p + q, nblk - 1) * 16 + fr) * g.ldo + col0; // blocks past a short tile re-read its last one (never used)
+#pragma unroll
+      for (int j = 0; j < 2; j++) rr[q][j] = *(const float4 *)(rp + j * 16);
+    }
+  };
+  if (RESID) load_pair(0);
+#pragma unroll
+  for (int j = 0; j < 2; j++) b4[j] = *(const float4 *)(bp + col0 + j * 16);
+#pragma unroll
+  for (int i = 0; i < MI; i++) sq[i] = sp[m0 + min(i, nblk - 1) * 16 + fr];
+#pragma unroll
+  for (int j = 0; j < 2; j++) b4[j] = hb ? b4[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int i = 0; i < MI; i++) sq[i] = hs ? sq[i] : 0;
+#pragma unroll
+  for (int p = 0; p < MI / 2; p++) {
+    float4 v[2][2];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const int i = 2 * p + q;
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        float4 t = make_float4(acc[i][j][0] + b4[j].x, acc[i][j][1] + b4[j].y, acc[i][j][2] + b4[j].z, acc[i][j][3] + b4[j].w);
+        if (RESID) { t.x += rr[q][j].x; t.y += rr[q][j].y; t.z += rr[q][j].z; t.w += rr[q][j].w; }
+        if (sq[i] < 0) t = make_float4(0.f, 0.f, 0.f, 0.f);
+        v[q][j] = t;
+      }
+    }
+    if (RESID && p + 1 < MI / 2) load_pair(p + 1);
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      const int i = 2 * p + q;
+      if (i < nblk) {
+        float *op = g.outF + (size_t)(m0 + i * 16 + fr) * g.ldo + col0;
+#pragma unroll
+        for (int j = 0; j < 2; j++) *(float4 *)(op + j * 16) = v[q][j];
+      }
+    }
+  }
+}
+
+template <int MI, bool RESID>
+__device__ __forceinline__ void gemm_conv3_wreg_body(const GemmArgs &g, int m0, int n0, int nblk, int lane, int wave) {
+  extern __shared__ __attribute__((aligned(16))) char smem_dyn[]; // ONE LDS object (see gemm_vh_body)
+  char *smem = smem_dyn;
+  constexpr int NP = 2 * MI + 1;     // 8-row pieces of the slab (rows m0 - 1 .. m0 + 16 MI)
+  constexpr int NPA = (NP + 3) / 4;  // requested per wave and chunk: vmcnt events of a slab
+  const int nchunks = g.kseg >> 6, KS = g.kseg >> 5;
+  const int fr = lane & 15, fq = lane >> 4;
+  unsigned aoff[NPA]; // byte offsets from a wave-uniform base; rows past a short tile are clamped into it (duplicates that are never stored)
+#pragma unroll
+  for (int i = 0; i < NPA; i++) aoff[i] = (unsigned)(gemm_dma_off(min(wave + 4 * i, NP - 1), lane, 0, nblk * 16 + 1, g.lda) * 2);
+  const char *aseg = (const char *)(g.A[0] + (ptrdiff_t)(m0 - 1) * g.lda); // slab row s = activation row m0 - 1 + s (the buffer has its guard rows)
+  const size_t tap_stride = (size_t)g.N * g.kseg;
+  const __half *wp = g.Wf + (size_t)((n0 >> 4) + wave * 2) * KS * 512; // tap 0, this wave's first column block (wave-uniform)
+  const unsigned wlane = lane * 16;
+  floatx4 acc[MI][2]; // from zero: the residual is read by the epilogue
+#pragma unroll
+  for (int i = 0; i < MI; i++)
+#pragma unroll
+    for (int j = 0; j < 2; j++) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+  // fragment read addresses: lds_off(16 i + fr + tap, 4 ks + fq) = 2048 i + lds_off(fr + tap, 4 ks + fq) (the swizzle has period 8 rows): one register per (tap, K step),
+  // block and slot are immediate offsets. Opaque to hipcc, which otherwise keeps an address per (block, tap, K step) and spills them
+  int fbase[3][2];
+#pragma unroll
+  for (int tap = 0; tap < 3; tap++)
+#pragma unroll
+    for (int ks = 0; ks < 2; ks++) {
+      fbase[tap][ks] = lds_off(fr + tap, ks * 4 + fq);
+      asm volatile("" : "+v"(fbase[tap][ks]));
+    }
+  half8 w[2][2][2]; // [set][k step][column block]
+  auto issue_w = [&](int kc, int tap, auto set_c) {
+    constexpr int U = decltype(set_c)::value;
+    const __half *q0 = wp + (size_t)tap * tap_stride + (size_t)min(kc, nchunks - 1) * 1024, *q1 = q0 + (size_t)KS * 512; // past the last chunk: see issue_slab
+    wreg_load<0>(w[U][0][0], q0, wlane);
+    wreg_load<0>(w[U][0][1], q1, wlane);
+    wreg_load<1024>(w[U][1][0], q0, wlane);
+    wreg_load<1024>(w[U][1][1], q1, wlane);
+  };
+  auto issue_slab = [&](int kc, int slot) {
+    const char *ab = aseg + (min(kc, nchunks - 1) << 7); // past the last chunk: the last one again, into the free slot (every phase counts the same vmcnt events)
+    asm volatile("" : "+s"(ab));
+#pragma unroll
+    for (int i = 0; i < NPA; i++) {
+      unsigned o = aoff[i];
+      asm volatile("" : "+v"(o)); // base and offset opaque: scalar base + 32-bit lane offset (hipcc otherwise re-associates them into 64-bit VGPR addresses kept across the loop)
+      __builtin_amdgcn_global_load_lds((gptr_t)(ab + o), (lptr_t)(smem + slot * CONV3_WREG_SLOT + min(wave + 4 * i, NP - 1) * 1024), 16, 0, 0);
+    }
+  };
+  // one phase: chunk kc (PAR = kc & 1 names its slab slot), tap TAP. No branch around a wait or a request: a join would copy weight registers (v_mov of a load
+  // destination that may not have landed)
+  auto phase = [&](int kc, auto par_c, auto tap_c) {
+    constexpr int PAR = decltype(par_c)::value, TAP = decltype(tap_c)::value, U = PAR ^ (TAP & 1);
+    wreg_wait<TAP == 1 ? NPA : 0>(w[U][0][0], w[U][0][1], w[U][1][0], w[U][1][1]);
+    if (TAP == 0) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // this wave's fragment reads of chunk kc - 1 are complete
+      __builtin_amdgcn_s_barrier();
+    }
+    if (TAP < 2) issue_w(kc, TAP + 1, std::integral_constant<int, U ^ 1>{});
+    else issue_w(kc + 1, 0, std::integral_constant<int, U ^ 1>{});
+    if (TAP == 0) issue_slab(kc + 1, PAR ^ 1);
+    const char *sa = smem + PAR * CONV3_WREG_SLOT;
+    // activation fragments one at a time, AHEAD fragments ahead of the MFMA pair that consumes them (see gemm_wreg_body)
+    constexpr int AHEAD = 2;
+    half8 af[AHEAD + 1];
+    auto frag = [&](int x) { return *(const half8 *)(sa + fbase[TAP][x / MI] + (x % MI) * 2048); }; // x = ks * MI + i
+#pragma unroll
+    for (int x = 0; x < AHEAD; x++) af[x] = frag(x);
+#pragma unroll
+    for (int x = 0; x < 2 * MI; x++) {
+      if (x + AHEAD < 2 * MI) af[(x + AHEAD) % (AHEAD + 1)] = frag(x + AHEAD);
+      const int ks = x / MI, i = x % MI;
+      const half8 a = af[x % (AHEAD + 1)];
+#pragma unroll
+      for (int j = 0; j < 2; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[U][ks][j], a, acc[i][j], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x100, AHEAD, 0);
+#pragma unroll
+    for (int x = 0; x < 2 * MI; x++) {
+      if (x + AHEAD < 2 * MI) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+    }
+  };
+  auto chunk = [&](int kc, auto par_c) {
+    phase(kc, par_c, std::integral_constant<int, 0>{});
+    phase(kc, par_c, std::integral_constant<int, 1>{});
+    phase(kc, par_c, std::integral_constant<int, 2>{});
+  };
+  issue_slab(0, 0);
+  issue_w(0, 0, std::integral_constant<int, 0>{});
+  for (int kc = 0; kc < nchunks; kc += 2) { // two chunks per trip: slab slots and register sets are compile-time
+    chunk(kc, std::integral_constant<int, 0>{});
+    if (kc + 1 < nchunks) chunk(kc + 1, std::integral_constant<int, 1>{});
+  }
+  // the last phase's (repeated) weight request lands before its registers are reused; the repeated slab has landed at the last tap 2
+  wreg_wait<0>(w[0][0][0], w[0][0][1], w[0][1][0], w[0][1][1]);
+  wreg_wait<0>(w[1][0][0], w[1][0][1], w[1][1][0], w[1][1][1]);
+  gemm_epilogue_conv3_wreg<MI, RESID>(g, acc, m0, n0, nblk, wave, fr, fq);
+}
+
+template <bool RESID>
+static __global__ __launch_bounds__(256, 4) void gemm_f16_conv3_wreg_kernel(GemmArgs g) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int m0, n0, nblk;
+  if (!gemm_vh_tile(g, m0, n0, nblk)) return;
+  if (nblk > 4) gemm_conv3_wreg_body<8, RESID>(g, m0, n0, nblk, lane, wave);
+  else gemm_conv3_wreg_body<4, RESID>(g, m0, n0, nblk, lane, wave);
+}
+// the shapes gemm_f16_conv3_wreg_kernel takes: g.Wf is then the per-tap image (gemm_wfrag3_index). The STATS and F16 modes, shorter tiles and so the small grids stay
+// with the LDS-staged kernel
+static inline bool gemm_takes_conv3_wreg(const GemmArgs &g, int th) {
+  return g.wreg > 0 && g.Wf && gemm_is_conv3(g) && th == 8 && g.mode == GEMM_OUT_F32;
+}
+
 // tile height (16-row blocks) launch_gemm_f16 chooses for an M x N problem
 static inline int gemm_auto_th(int M, int N) {
   const int maxb = ((M >> 4) + 7) / 8 + 1, NT = N >> 7;
@@ -910,7 +1100,7 @@ static inline int gemm_auto_th(int M, int N) {
 
 // What launch_gemm_f16 does with a set of arguments: pure host arithmetic, no HIP call (the kernel tests read it to say which kernel ran). th / ku / cn / grid / lds are the
 // EFFECTIVE values, those of the instantiation that is launched: the k = 3 and the register-streamed kernel have no KU (1), the dual-B kernel has 1 and 2.
-enum { GEMM_KERNEL_VH = 0, GEMM_KERNEL_DUALB = 1, GEMM_KERNEL_CONV3 = 2, GEMM_KERNEL_WREG = 3 };
+enum { GEMM_KERNEL_VH = 0, GEMM_KERNEL_DUALB = 1, GEMM_KERNEL_CONV3 = 2, GEMM_KERNEL_WREG = 3, GEMM_KERNEL_CONV3_WREG = 4 };
 struct GemmPlan {
   hipError_t err; // hipErrorInvalidValue: refused, nothing is launched (the other fields still say what the rules select)
   int kernel;     // GEMM_KERNEL_*
@@ -958,6 +1148,7 @@ static inline GemmPlan gemm_plan(const GemmArgs &g) {
   }
   p.grid = 8 * mt_max * NT;
   if (gemm_takes_wreg(g, p.th, ku)) { p.kernel = GEMM_KERNEL_WREG; p.ku = 1; p.lds = GEMM_WREG_LDS; }
+  else if (gemm_takes_conv3_wreg(g, p.th)) { p.kernel = GEMM_KERNEL_CONV3_WREG; p.ku = 1; p.lds = CONV3_WREG_LDS; }
   else if (gemm_is_conv3(g)) { p.kernel = GEMM_KERNEL_CONV3; p.ku = 1; p.lds = CONV3_VH_LDS; }
   else if (g.dual_b) { p.kernel = GEMM_KERNEL_DUALB; p.ku = ku == 2 ? 2 : 1; p.lds = p.ku * GEMM_DUALB_LDS; } // a requested KU of 4 has no dual-B instantiation
   else { p.kernel = GEMM_KERNEL_VH; p.ku = ku; p.lds = ku * GEMM_VH_LDS; } // KU > 1: 64 / 128 KB of LDS -> 2 / 1 workgroups per CU
@@ -966,7 +1157,7 @@ static inline GemmPlan gemm_plan(const GemmArgs &g) {
 
 // One instantiation's launch. More dynamic LDS than the 48 KB a kernel may use by default (the k = 3 kernel, KU 2 / 4, dual-B KU 2) is asked for once per instantiation.
 // The threshold names exactly those: dual-B KU 1 (48 KB) and every smaller stage are never raised; a change of an LDS size changes which instantiations get the call.
-static_assert(GEMM_DUALB_LDS <= 48 * 1024 && GEMM_VH_LDS <= 48 * 1024 && GEMM_WREG_LDS <= 48 * 1024 && CONV3_VH_LDS > 48 * 1024, "which launches raise their dynamic LDS limit");
+static_assert(GEMM_DUALB_LDS <= 48 * 1024 && GEMM_VH_LDS <= 48 * 1024 && GEMM_WREG_LDS <= 48 * 1024 && CONV3_WREG_LDS <= 48 * 1024 && CONV3_VH_LDS > 48 * 1024, "which launches raise their dynamic LDS limit");
 template <void (*KERN)(GemmArgs)> static inline void gemm_launch(const GemmPlan &p, const GemmArgs &g, hipStream_t s) {
   if (p.lds > 48 * 1024) {
     static bool raised = false;
@@ -996,6 +1187,10 @@ static inline void gemm_launch_conv3(const GemmPlan &p, const GemmArgs &g, hipSt
   else if (g.mode == GEMM_OUT_F32_STATS) gemm_launch<gemm_f16_conv3_vh_kernel<GEMM_OUT_F32_STATS>>(p, g, s);
   else gemm_launch<gemm_f16_conv3_vh_kernel<GEMM_OUT_F16>>(p, g, s);
 }
+static inline void gemm_launch_conv3_wreg(const GemmPlan &p, const GemmArgs &g, hipStream_t s) {
+  if (g.resid) gemm_launch<gemm_f16_conv3_wreg_kernel<true>>(p, g, s);
+  else gemm_launch<gemm_f16_conv3_wreg_kernel<false>>(p, g, s);
+}
 static inline void gemm_launch_wreg(const GemmPlan &p, const GemmArgs &g, hipStream_t s) {
   if (g.mode == GEMM_OUT_F32) gemm_launch<gemm_f16_wreg_kernel<GEMM_OUT_F32>>(p, g, s);
   else if (g.mode == GEMM_OUT_QKV) gemm_launch<gemm_f16_wreg_kernel<GEMM_OUT_QKV>>(p, g, s);
@@ -1009,6 +1204,7 @@ static inline hipError_t launch_gemm_f16(const GemmArgs &g, hipStream_t s) {
   gg.th = p.th;
   gg.cn = p.cn;
   if (p.kernel == GEMM_KERNEL_WREG) gemm_launch_wreg(p, gg, s);
+  else if (p.kernel == GEMM_KERNEL_CONV3_WREG) gemm_launch_conv3_wreg(p, gg, s);
   else if (p.kernel == GEMM_KERNEL_CONV3) gemm_launch_conv3(p, gg, s);
   else if (p.kernel == GEMM_KERNEL_DUALB) p.ku == 2 ? gemm_launch_dualb<2>(p, gg, s) : gemm_launch_dualb<1>(p, gg, s);
   else p.ku == 4 ? gemm_launch_vh<4>(p, gg, s) : p.ku == 2 ? gemm_launch_vh<2>(p, gg, s) : gemm_launch_vh<1>(p, gg, s);

@@ -1,5 +1,5 @@
 // Test-only harness around launch_gemm_f16 (csrc/gemm_f16.h, included unchanged): host arrays in, host arrays out, one launch on a stream of its own.
-// Built as libtts_gemm_test.so next to the product library; links nothing from it and is not part of it (tests/test_gemm_kernels_gpu.py is the only user).
+// Built as libtts_gemm_test.so next to the product library; links nothing from it and is not part of it (tests/test_gemm_kernels_gpu.py and tests/test_gemm_wreg_k3_*.py are the only users).
 //
 // The GPU is shared: a case is validated completely BEFORE anything is launched (shapes, every pointer the chosen mode reads or writes, leading dimensions,
 // the rows -1 and M the k = 3 kernel reads, the ">= 128 N / 128 M bytes" the epilogue's dummy loads need), and every device buffer carries a canary margin in
@@ -38,6 +38,7 @@ struct tts_gemm_case {
 
 int tts_gemm_test_margin(void) { return TTS_GEMM_TEST_MARGIN; }
 int tts_gemm_test_auto_th(int M, int N) { return gemm_auto_th(M, N); }
+long long tts_gemm_test_wfrag3_index(int n, int tap, int k, int N, int K) { return (long long)gemm_wfrag3_index(n, tap, k, N, K); } // where the loader puts tap `tap` of W[n][tap * K + k]
 
 } // extern "C"
 
@@ -62,7 +63,7 @@ GemmArgs host_args(const tts_gemm_case &c) { // the fields the dispatcher reads;
 
 // What launch_gemm_f16 does with these arguments, in the words of its own plan (g.Wf must be set where an image exists).
 void describe(const GemmArgs &g, char *buf, int cap) {
-  static const char *const names[] = {"vh", "dualb", "conv3", "wreg"};
+  static const char *const names[] = {"vh", "dualb", "conv3", "wreg", "conv3w"};
   const GemmPlan p = gemm_plan(g);
   snprintf(buf, cap, "%s mode=%d th=%d ku=%d cn=%d", names[p.kernel], g.mode, p.th, p.ku, p.cn);
 }
@@ -81,6 +82,11 @@ struct Dev { // one device allocation: margin | payload | margin
   hipError_t put(const void *h) { return hipMemcpy(data(), h, bytes, hipMemcpyHostToDevice); }
   hipError_t get_all(void *h) const { return hipMemcpy(h, p, bytes + 2 * TTS_GEMM_TEST_MARGIN, hipMemcpyDeviceToHost); }
 };
+
+// the k = 3 convolution as the product describes it: three taps of ONE buffer, tap-major weight (gemm_is_conv3 reads the same from GemmArgs)
+bool conv3_shape(const tts_gemm_case &c) {
+  return c.nseg == 3 && !c.custom_w && !c.a_sel[0] && !c.a_sel[1] && !c.a_sel[2] && c.row_off[0] == -1 && c.row_off[1] == 0 && c.row_off[2] == 1;
+}
 
 bool valid(const tts_gemm_case &c, bool run) { // run: the output buffers are needed too (a plan names none)
   if (c.M < 16 || c.M > 131072 || (c.M & 15) || c.N < 128 || c.N > 4096 || (c.N & 127)) return false;
@@ -131,14 +137,17 @@ bool valid(const tts_gemm_case &c, bool run) { // run: the output buffers are ne
 extern "C" {
 
 // the kernel / th / ku / cn the launcher selects for a case, without running it (host only: gemm_plan)
-int tts_gemm_test_plan(const tts_gemm_case *c, char *buf, int cap) {
+static int plan_case(const tts_gemm_case *c, char *buf, int cap, bool images) {
   if (!c || !buf || cap <= 0 || !valid(*c, false)) return (int)hipErrorInvalidValue;
   GemmArgs g = host_args(*c);
   static const __half wf_placeholder[1] = {};
-  if (c->wreg && c->nseg == 1 && !c->custom_w) g.Wf = wf_placeholder;
+  if (c->wreg && ((c->nseg == 1 && !c->custom_w) || (images && conv3_shape(*c)))) g.Wf = wf_placeholder;
   describe(g, buf, cap);
   return 0;
 }
+int tts_gemm_test_plan(const tts_gemm_case *c, char *buf, int cap) { return plan_case(c, buf, cap, false); }
+// the plan of tts_gemm_test_run_images: a case with wreg set also has the per-tap image of a k = 3 weight
+int tts_gemm_test_plan_images(const tts_gemm_case *c, char *buf, int cap) { return plan_case(c, buf, cap, true); }
 
 int tts_gemm_test_last_kernel(char *buf, int cap) {
   if (!buf || cap <= 0) return (int)hipErrorInvalidValue;
@@ -148,7 +157,7 @@ int tts_gemm_test_last_kernel(char *buf, int cap) {
 
 #define HT(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
 
-int tts_gemm_test_run(const tts_gemm_case *cp) {
+static int run_case(const tts_gemm_case *cp, bool images) {
   if (!cp || !valid(*cp, true)) return (int)hipErrorInvalidValue;
   const tts_gemm_case &c = *cp;
   const int ldw = c.custom_w ? c.ldw : c.nseg * c.kseg;
@@ -166,6 +175,13 @@ int tts_gemm_test_run(const tts_gemm_case *cp) {
     std::vector<uint16_t> img((size_t)c.N * c.kseg);
     for (int n = 0; n < c.N; n++)
       for (int k = 0; k < c.kseg; k++) img[gemm_wfrag_index(n, k, c.kseg)] = c.W[(size_t)n * c.kseg + k];
+    HT(wf.alloc(w_bytes, 0)); HT(wf.put(img.data()));
+    g.Wf = (const __half *)wf.data();
+  } else if (images && c.wreg && conv3_shape(c)) { // one fragment-major image per tap, as the loader builds them
+    std::vector<uint16_t> img((size_t)c.N * 3 * c.kseg);
+    for (int n = 0; n < c.N; n++)
+      for (int tap = 0; tap < 3; tap++)
+        for (int k = 0; k < c.kseg; k++) img[gemm_wfrag3_index(n, tap, k, c.N, c.kseg)] = c.W[((size_t)n * 3 + tap) * c.kseg + k];
     HT(wf.alloc(w_bytes, 0)); HT(wf.put(img.data()));
     g.Wf = (const __half *)wf.data();
   }
@@ -208,5 +224,9 @@ int tts_gemm_test_run(const tts_gemm_case *cp) {
   if (st.p) HT(st.get_all(c.st));
   return (int)(e != hipSuccess ? e : es);
 }
+
+int tts_gemm_test_run(const tts_gemm_case *cp) { return run_case(cp, false); }
+// tts_gemm_test_run that also builds the per-tap image of a k = 3 weight when the case sets wreg (tts_gemm_test_run keeps such a case on the LDS-staged kernel)
+int tts_gemm_test_run_images(const tts_gemm_case *cp) { return run_case(cp, true); }
 
 } // extern "C"
