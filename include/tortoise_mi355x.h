@@ -127,7 +127,24 @@ const char *tts_last_error(const tts_ctx *ctx);
  * "ddim_eta" (0 default; [0, 1], else TTS_ERR_ARG; read only when diff_sampler = 1): 0 = deterministic DDIM, the only noise is x_T; > 0 adds sigma_t z per step (1 = the
  * ancestral variance). See tts_diffusion for the noise layout.
  * "cond_free_k" (2.0 default = the reference's base_k, main.cpp:5988; finite and >= 0, else TTS_ERR_ARG): conditioning-free guidance strength of both samplers,
- * cfk_t = k (1 - t / n). At 2.0 every bit of the output is what it was. */
+ * cfk_t = k (1 - t / n). At 2.0 every bit of the output is what it was.
+ * Additions within version 8, the autoregressive sampler's controls (no prototype changed; sticky per context; a refused value changes nothing and returns
+ * TTS_ERR_ARG; read by tts_sample, tts_ar_step_sample, tts_autoregressive, tts_autoregressive_multi and tts_autoregressive_multi_voice). The defaults are the
+ * literals of the reference's process_logits_and_sample (main.cpp:4753-4806); upstream tortoise-tts passes temperature, top_k, top_p and repetition_penalty to HF
+ * generate on every call (api.py: TextToSpeech.tts). At the defaults every bit of every output and the RNG state afterwards are what they were; the RNG consumption
+ * (two uniforms per candidate and step, candidate order, rng_shard_*) does not depend on them.
+ * "ar_temperature" (0.8 default; finite and > 0, narrowed to float): logit /= temperature (temp_inplace, main.cpp:4617-4621).
+ * "ar_top_k" (50 default; an integer in 1 .. 8194): top_k_inplace (main.cpp:4636-4641), ties at the k-th value survive. The device prefilter's lists (device_topk)
+ * serve top-k <= 100; above that every candidate is sampled from its full row, fetched one by one: correct and slow (tts_ar_topk_fallbacks counts them).
+ * "ar_top_p" (0.8 default; (0, 1]): top_p_inplace (main.cpp:4657-4693) with its quirks — ascending sort, softmax over the sorted vector, in-place cumulative sum,
+ * the last element never masked — masking while the sum is <= 1 - top_p (at 0.8 exactly the reference's `<= 0.2`).
+ * "ar_repetition_penalty" (2.0 default; finite and >= 1, narrowed to float): apply_penalty (main.cpp:4562-4570), g < 0 ? g * p : g / p.
+ * "ar_penalty_scope" (0 default): WHICH ids are penalised. 0 = the reference: the ids of the graph's last input (the prompt-shaped [1 ... 1, 8192] at step 0, the
+ * previous sample afterwards; main.cpp:4771-4777). 1 = upstream: HF generate's RepetitionPenaltyLogitsProcessor sees the whole input_ids, here every id fed since
+ * tts_ar_begin* (through tts_ar_step or tts_ar_step_sample, in any mix; a step fed twice counts once) plus 1 and 8192. tts_sample penalises the ids it is given
+ * under either scope: a caller stepping by hand passes the accumulated history. Under scope 1 the decode step keeps the set on the device and its prefilter
+ * penalises before it thresholds (one more node in the step graph of tts_ar_step, none in tts_ar_step_sample's). Whether the wider penalty SOUNDS better cannot be
+ * judged without trained weights: the tests pin the arithmetic (DESIGN.md "What pins the sampler controls"). */
 int tts_set_option(tts_ctx *ctx, const char *key, double value);
 
 /* ---- weight files (drop-in format: magic 0x67676d6c + name-keyed F32 records) ------------- */
@@ -386,6 +403,14 @@ int tts_host_rel_bucket(int query, int key);
  * where the engine would fetch the full row. For tests of the list logic without a GPU. */
 int tts_host_sample_row(const float *row8194, const int32_t *penalty_ids, int n_ids, float uniform);
 int tts_host_sample_prefiltered(const float *row8194, const int32_t *penalty_ids, int n_ids, float uniform, int keep);
+/* The same two with the sampler's controls explicit and no context (n_ids may be 0; -2: a refused argument).
+ * mode 0: the production path on a full row (fast scan, literal fallback); mode 1: the literal formulation only. */
+int tts_host_sample_row_ex(const float *row8194, const int32_t *penalty_ids, int n_ids, float uniform, float temperature, int top_k, float top_p, float penalty,
+                           int mode);
+/* the list path on a host restatement of the device prefilter; already_penalised = 1 models penalty scope 1 (the list is taken from the penalised row and holds
+ * penalised values). -1 = the engine would fetch the row */
+int tts_host_sample_prefiltered_ex(const float *row8194, const int32_t *penalty_ids, int n_ids, float uniform, float temperature, int top_k, float top_p,
+                                   float penalty, int keep, int already_penalised);
 int tts_host_pad_codes(const int32_t *codes, int n, int32_t *out502);
 int tts_host_trimmed_rows(const int32_t *codes502);
 /* tts_autoregressive_multi's stop bookkeeping on scripted samples (random-init weights never sample the stop token): samples [max_steps][B] = what the

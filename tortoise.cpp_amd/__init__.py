@@ -63,6 +63,7 @@ def lib():
         "tts_ar_step_sample": (ci, [vp, _i32p, ci, C.c_uint, _i32p]), "tts_ar_topk_fallbacks": (ci, [vp]), "tts_diffusion_time_mlp_retries": (ci, [vp]), "tts_diffusion_fp16_check": (ci, [vp, C.POINTER(C.c_int64)]),
         "tts_device_numa_node": (ci, [vp, C.c_char_p, ci]), "tts_pin_to_device_numa_node": (ci, [vp]),
         "tts_host_sample_row": (ci, [_f32p, _i32p, ci, cf]), "tts_host_sample_prefiltered": (ci, [_f32p, _i32p, ci, cf, ci]),
+        "tts_host_sample_row_ex": (ci, [_f32p, _i32p, ci, cf, cf, ci, cf, cf, ci]), "tts_host_sample_prefiltered_ex": (ci, [_f32p, _i32p, ci, cf, cf, ci, cf, cf, ci, ci]),
         "tts_autoregressive": (ci, [vp, _i32p, ci, _f32p, ci, ci, C.c_uint, _i32p, _i32p, vp, _i32p]),
         "tts_ar_stop_status": (ci, [vp, _i32p, ci]), "tts_ar_set_stop_schedule": (ci, [vp, C.c_void_p, ci]),
         "tts_ar_begin_multi": (ci, [vp, _i32p, _i32p, ci, _f32p, _i32p, ci]),
@@ -476,6 +477,21 @@ def host_sample_prefiltered(row, ids, uniform, keep=64):
     cannot decide and the engine would fetch the full row."""
     ids = np.ascontiguousarray(ids, np.int32)
     return lib().tts_host_sample_prefiltered(np.ascontiguousarray(row, np.float32), ids, len(ids), float(uniform), keep)
+
+
+def host_sample_row_ex(row, ids, uniform, temperature=0.8, top_k=50, top_p=0.8, penalty=2.0, mode=0):
+    """host_sample_row with the sampler's controls explicit. mode 0: the production path (fast scan, literal fallback); 1: the literal formulation only."""
+    ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    return lib().tts_host_sample_row_ex(np.ascontiguousarray(row, np.float32), ids, len(ids), float(uniform), float(temperature), int(top_k), float(top_p),
+                                        float(penalty), int(mode))
+
+
+def host_sample_prefiltered_ex(row, ids, uniform, temperature=0.8, top_k=50, top_p=0.8, penalty=2.0, keep=64, already_penalised=False):
+    """host_sample_prefiltered with the controls explicit. already_penalised: the list is taken from the penalised row (penalty scope 1). -1: the engine
+    would fetch the full row."""
+    ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    return lib().tts_host_sample_prefiltered_ex(np.ascontiguousarray(row, np.float32), ids, len(ids), float(uniform), float(temperature), int(top_k),
+                                                float(top_p), float(penalty), int(keep), int(bool(already_penalised)))
 
 
 def host_rel_buckets(n):

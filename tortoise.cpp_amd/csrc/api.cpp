@@ -16,6 +16,7 @@ int ar_prefill(tts_ctx *, float *);
 int ar_step(tts_ctx *, const int32_t *, int, float *, int mode);
 const int32_t *ar_host_lists(tts_ctx *);
 const float *ar_fetch_logits_row(tts_ctx *, int);
+void ar_history_ids(const tts_ctx *, int c, std::vector<int32_t> &out);
 int ar_batch(const tts_ctx *);
 int ar_latents(tts_ctx *, const int32_t *, int, int, float *);
 int ar_layers(const tts_ctx *);
@@ -200,6 +201,27 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     if (!std::isfinite(value) || value < 0 || !std::isfinite((float)value)) return fail(c, TTS_ERR_ARG, "cond_free_k: a finite value >= 0");
     c->cond_free_k = (float)value;
   }
+  // additions within version 8: the autoregressive sampler's controls (read by tts_sample, tts_ar_step_sample and the tts_autoregressive* drivers)
+  else if (k == "ar_temperature") {
+    if (!std::isfinite(value) || !(value > 0) || !std::isfinite((float)value) || !((float)value > 0)) return fail(c, TTS_ERR_ARG, "ar_temperature: a finite value > 0");
+    c->ar_sp.temp = (float)value;
+  }
+  else if (k == "ar_top_k") {
+    if (!(value >= 1 && value <= TTS_VOCAB_MEL) || value != std::floor(value)) return fail(c, TTS_ERR_ARG, "ar_top_k: an integer in 1 .. %d", TTS_VOCAB_MEL);
+    c->ar_sp.top_k = (int)value;
+  }
+  else if (k == "ar_top_p") {
+    if (!(value > 0 && value <= 1) || !((float)value > 0)) return fail(c, TTS_ERR_ARG, "ar_top_p: a value in (0, 1]");
+    c->ar_sp.top_p = (float)value;
+  }
+  else if (k == "ar_repetition_penalty") {
+    if (!std::isfinite(value) || !(value >= 1) || !std::isfinite((float)value)) return fail(c, TTS_ERR_ARG, "ar_repetition_penalty: a finite value >= 1");
+    c->ar_sp.penalty = (float)value;
+  }
+  else if (k == "ar_penalty_scope") {
+    if (value != 0 && value != 1) return fail(c, TTS_ERR_ARG, "ar_penalty_scope: 0 (the ids of the last input) or 1 (every id fed since tts_ar_begin)");
+    c->ar_penalty_scope = (int)value;
+  }
   else if (k == "prof_eager_every") c->prof_eager_every = value < 1 ? 1 : (int)value;
   else if (k == "stream_cus") {
     // Partition of the chip between two contexts of one process (INTEGRATION.md "two-context pipeline"): value n > 0 re-creates this
@@ -330,7 +352,13 @@ int tts_ar_step(tts_ctx *c, const int32_t *prev, int i, float *logits) {
 static int step_sample(tts_ctx *c, const int32_t *prev, int i, bool mask_stop, int32_t *out, int *fallbacks) {
   if (int rc = ar_step(c, prev, i, nullptr, mask_stop ? 2 : 1)) return rc;
   const int B = ar_batch(c);
-  if (sample_candidates_list(c, ar_host_lists(c), prev, 1, B, out, [&](int b) { return ar_fetch_logits_row(c, b); }, fallbacks))
+  std::vector<int32_t> hist; // penalty scope 1: the lists hold penalised values; only a full-row fallback needs the candidate's history as ids
+  const bool scope1 = c->ar_penalty_scope == 1;
+  const PenaltyIdsFn ids_of = [&](int b, const int32_t *&p, int &n) {
+    if (scope1) { ar_history_ids(c, b, hist); p = hist.data(); n = (int)hist.size(); }
+    else { p = prev + b; n = 1; }
+  };
+  if (sample_candidates_list(c, ar_host_lists(c), ids_of, scope1, B, out, [&](int b) { return ar_fetch_logits_row(c, b); }, fallbacks))
     return fail(c, TTS_ERR_HIP, "tts_ar_step_sample: fetching a logits row failed");
   return TTS_OK;
 }
@@ -353,6 +381,31 @@ int tts_diffusion_fp16_check(tts_ctx *c, int64_t counts[2]) {
 int tts_host_sample_row(const float *row, const int32_t *ids, int ids_per_cand, float uniform) {
   if (!row || !ids || ids_per_cand < 1) return -1;
   return sample_one_row(row, ids, ids_per_cand, uniform);
+}
+static bool sampler_params_ok(const float *row, const int32_t *ids, int n_ids, float temperature, int top_k, float top_p, float penalty) {
+  if (!row || n_ids < 0 || (n_ids > 0 && !ids)) return false;
+  for (int i = 0; i < n_ids; i++)
+    if (ids[i] < 0 || ids[i] >= TTS_VOCAB_MEL) return false;
+  return std::isfinite(temperature) && temperature > 0 && top_k >= 1 && top_k <= TTS_VOCAB_MEL && top_p > 0 && top_p <= 1 && std::isfinite(penalty) && penalty >= 1;
+}
+int tts_host_sample_row_ex(const float *row, const int32_t *ids, int n_ids, float uniform, float temperature, int top_k, float top_p, float penalty, int mode) {
+  if (!sampler_params_ok(row, ids, n_ids, temperature, top_k, top_p, penalty) || (mode != 0 && mode != 1)) return -2;
+  SamplerParams sp; sp.temp = temperature; sp.top_k = top_k; sp.top_p = top_p; sp.penalty = penalty;
+  return sample_one_row_ex(row, ids, n_ids, uniform, sp, mode == 1);
+}
+int tts_host_sample_prefiltered_ex(const float *row, const int32_t *ids, int n_ids, float uniform, float temperature, int top_k, float top_p, float penalty, int keep,
+                                   int already_penalised) {
+  if (!sampler_params_ok(row, ids, n_ids, temperature, top_k, top_p, penalty) || keep < 1 || keep > TTS_PF_MAX) return -2;
+  SamplerParams sp; sp.temp = temperature; sp.top_k = top_k; sp.top_p = top_p; sp.penalty = penalty;
+  std::vector<int32_t> list(TTS_PF_WORDS);
+  std::vector<float> pen; // already_penalised: what sample_prefilter_kernel<true> thresholds, the penalised row
+  if (already_penalised) {
+    pen.assign(row, row + TTS_VOCAB_MEL);
+    for (int i = 0; i < n_ids; i++) { const float g = row[ids[i]]; pen[ids[i]] = g < 0 ? g * penalty : g / penalty; }
+    row = pen.data();
+  }
+  if (host_prefilter_row(row, keep, list.data()) < 0) return -1;
+  return sample_one_from_list_ex(list.data(), ids, n_ids, uniform, sp, already_penalised != 0);
 }
 int tts_host_sample_prefiltered(const float *row, const int32_t *ids, int ids_per_cand, float uniform, int keep) {
   if (!row || !ids || ids_per_cand < 1 || keep < 1 || keep > TTS_PF_MAX) return -2;
@@ -423,6 +476,12 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
   std::vector<int32_t> next; // the samples of the coming iteration when the device-top-k step already produced them
   bool have_next = false;
   c->topk_fallbacks = 0;
+  // Penalty scope 1 (option "ar_penalty_scope"; HF generate's repetition penalty as upstream tortoise-tts runs it): every id fed since ar_begin_groups plus 1 and
+  // 8192. ar_step keeps that set per candidate (the bitmap its penalising prefilter reads); the full-row sampler gets it as an id list. At step 0 nothing has
+  // been fed: the set is {1, 8192}, exactly the distinct ids of the prompt-shaped row above.
+  const bool scope1 = c->ar_penalty_scope == 1;
+  std::vector<std::vector<int32_t>> hist(scope1 ? B : 0);
+  std::vector<int32_t> hist_one;
   int i = 0;
   for (;;) {
     double t0 = now();
@@ -430,7 +489,11 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
     else {
       if (flags & TTS_AR_MASK_STOP)
         for (int b = 0; b < B; b++) logits[(size_t)b * V + 8193] = -1e30f;
-      sample_candidates(c, logits, ids.data(), ids_per_cand, B, samples.data());
+      if (scope1 && i > 0) {
+        for (int b = 0; b < B; b++) ar_history_ids(c, b, hist[b]);
+        sample_candidates(c, logits, [&](int b, const int32_t *&p, int &n) { p = hist[b].data(); n = (int)hist[b].size(); }, B, samples.data());
+      } else
+        sample_candidates(c, logits, ids.data(), ids_per_cand, B, samples.data());
       t_sample += now() - t0;
     }
     const bool all_ended = book.step(samples.data(), i, retire, sched ? c->stop_schedule.data() : nullptr);
@@ -454,7 +517,11 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
     t_step += now() - t0;
     t0 = now();
     next.resize(B);
-    if (sample_candidates_list(c, ar_host_lists(c), ids.data(), 1, B, next.data(), [&](int b) { return ar_fetch_logits_row(c, b); }, &c->topk_fallbacks,
+    const PenaltyIdsFn ids_of = [&](int b, const int32_t *&p, int &n) {
+      if (scope1) { ar_history_ids(c, b, hist_one); p = hist_one.data(); n = (int)hist_one.size(); }
+      else { p = ids.data() + b; n = 1; }
+    };
+    if (sample_candidates_list(c, ar_host_lists(c), ids_of, scope1, B, next.data(), [&](int b) { return ar_fetch_logits_row(c, b); }, &c->topk_fallbacks,
                                book.retired.data()))
       return fail(c, TTS_ERR_HIP, "tts_autoregressive: fetching a logits row failed");
     t_sample += now() - t0;

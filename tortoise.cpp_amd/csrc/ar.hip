@@ -1185,22 +1185,52 @@ __device__ __forceinline__ unsigned pf_key(float v) {
   return (u >> 31) ? ~u : (u | 0x80000000u);
 }
 
-__global__ __launch_bounds__(256) void sample_prefilter_kernel(const float *__restrict__ logits, int mask_stop, int32_t *__restrict__ out) {
+// PEN (option "ar_penalty_scope" = 1, upstream's full-history repetition penalty): the kernel penalises before it thresholds. hist = the
+// candidates' history bitmaps [B][TTS_HIST_WORDS] (bit i: id i was fed since tts_ar_begin*, or is 1 / 8192), toks = the ids this step was fed
+// (ArState::h_toks): candidate c's token joins its set here — thread 0 stores the bit, every thread also compares its indices against the token
+// itself, so nobody waits for that store — and the set is idempotent under a step fed twice. The stop mask comes first, then
+// g < 0 ? g * penalty : g / penalty in plain float arithmetic (what apply_penalty does on the host: correctly rounded multiply and divide, no
+// fast-math), and the lists carry the penalised values; the host tail then applies temperature, top-k, top-p and the multinomial only.
+// pf_min: the keep window's lower bound (common.h: pf_min_for(top_k)); above TTS_PF_MAX no list is written (n = -1 for every candidate).
+template <bool PEN>
+__device__ __forceinline__ float pf_value(const float *__restrict__ src, int i, int mask_stop, bool pen, float penalty) {
+  float v = src[i];
+  if (mask_stop && i == V - 1) v = -1e30f; // TTS_AR_MASK_STOP: the stop token 8193 is never sampled
+  if (PEN && pen) v = (v < 0.f) ? v * penalty : v / penalty;
+  return v;
+}
+
+template <bool PEN>
+__global__ __launch_bounds__(256) void sample_prefilter_kernel(const float *__restrict__ logits, int mask_stop, int pf_min, int32_t *__restrict__ out,
+                                                               uint32_t *__restrict__ hist, const int32_t *__restrict__ toks, float penalty) {
   constexpr int NJ = (V + 255) / 256; // 33
   __shared__ int red[2][4];
   __shared__ int4 tab[NJ];
   const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float *src = logits + (size_t)c * V;
   int32_t *o = out + (size_t)c * TTS_PF_WORDS;
+  unsigned long long penm = 0ull; // PEN: bit j = this thread's logit j is penalised
+  if (PEN) {
+    uint32_t *hc = hist + (size_t)c * TTS_HIST_WORDS;
+    const int tok = toks[c]; // 0 <= tok < V (ar_step checks)
+    if (tid == 0) hc[tok >> 5] |= 1u << (tok & 31); // one workgroup per candidate, one writer
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+      const int i = j * 256 + tid;
+      if (i < V && (((hc[i >> 5] >> (i & 31)) & 1u) || i == tok)) penm |= 1ull << j;
+    }
+  }
+  if (pf_min > TTS_PF_MAX) { // top-k beyond what a 128-entry list can serve: the host samples every candidate from its full row
+    if (tid == 0) o[0] = -1;
+    return;
+  }
   unsigned key[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; j++) {
     const int i = j * 256 + tid;
-    float v = i < V ? src[i] : 0.f;
-    if (mask_stop && i == V - 1) v = -1e30f; // TTS_AR_MASK_STOP: the stop token 8193 is never sampled
-    key[j] = i < V ? pf_key(v) : 0u;          // padding: key 0 is below every probe (probes are > 0)
+    key[j] = i < V ? pf_key(pf_value<PEN>(src, i, mask_stop, (penm >> j) & 1ull, penalty)) : 0u; // padding: key 0 is below every probe (probes are > 0)
   }
-  unsigned lo = 0u, hi = 0xffffffffu, t = 0u; // count(lo) > PF_MAX, count(hi) < PF_MIN
+  unsigned lo = 0u, hi = 0xffffffffu, t = 0u; // count(lo) > PF_MAX, count(hi) < pf_min
   int n = -1, it = 0;
   while (hi - lo > 1u) {
     const unsigned mid = lo + ((hi - lo) >> 1);
@@ -1212,10 +1242,10 @@ __global__ __launch_bounds__(256) void sample_prefilter_kernel(const float *__re
     const int cnt = red[it & 1][0] + red[it & 1][1] + red[it & 1][2] + red[it & 1][3];
     it++;
     if (cnt > TTS_PF_MAX) lo = mid;
-    else if (cnt < TTS_PF_MIN) hi = mid;
+    else if (cnt < pf_min) hi = mid;
     else { n = cnt; t = mid; break; }
   }
-  if (n < 0) { // more than PF_MAX - PF_MIN + 1 logits tie at the 64th place: the host takes the full row
+  if (n < 0) { // more than PF_MAX - pf_min + 1 values tie at the pf_min-th place: the host takes the full row
     if (tid == 0) o[0] = -1;
     return;
   }
@@ -1234,14 +1264,20 @@ __global__ __launch_bounds__(256) void sample_prefilter_kernel(const float *__re
     if (key[j] >= t) {
       const int i = j * 256 + tid;
       const int pos = base + (wave > 0 ? r.x : 0) + (wave > 1 ? r.y : 0) + (wave > 2 ? r.z : 0) + __popcll(m & below);
-      float v = src[i];
-      if (mask_stop && i == V - 1) v = -1e30f;
       o[4 + pos] = i;
-      o[4 + TTS_PF_MAX + pos] = __float_as_int(v);
+      o[4 + TTS_PF_MAX + pos] = __float_as_int(pf_value<PEN>(src, i, mask_stop, (penm >> j) & 1ull, penalty));
     }
     base += r.x + r.y + r.z + r.w;
   }
   if (tid == 0) { o[0] = n; o[1] = 0; o[2] = 0; o[3] = 0; }
+}
+
+// Penalty scope 1, a step that hands back the logits (tts_ar_step): the fed ids join the candidates' history sets here, since no prefilter runs.
+__global__ void hist_mark_kernel(const int32_t *__restrict__ toks, int B, uint32_t *__restrict__ hist) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= B) return;
+  const int tok = toks[c];
+  hist[(size_t)c * TTS_HIST_WORDS + (tok >> 5)] |= 1u << (tok & 31); // one thread per candidate: its own row
 }
 
 
@@ -1291,6 +1327,14 @@ struct ArState {
   int32_t *h_pf = nullptr;     // pinned [B][TTS_PF_WORDS]: the device prefilter's lists (step_mode != 0), written by the kernel itself
   int step_mode = 0;           // what the step hands to the host: 0 = the logits, 1 = the prefilter's lists, 2 = lists with the stop token masked
   int h_cap_B = 0;             // candidates the pinned buffers were sized for
+  // Penalty scope 1 (option "ar_penalty_scope"): per candidate the set of ids fed since ar_begin_groups plus 1 and 8192, [B][TTS_HIST_WORDS]. The host copy is
+  // kept by every ar_step whatever the scope (B stores); the device copy is what the scope-1 step graphs read and extend, and is uploaded from the host copy
+  // by the first scope-1 step after a begin or after a scope-0 step (which does not touch it).
+  std::vector<uint32_t> hist_host;
+  DevBuf hist;
+  bool hist_dev_valid = false;
+  int step_scope = 0, step_pf_min = TTS_PF_MIN; // what the step being enqueued bakes in: the penalty scope, the prefilter's keep bound
+  float step_penalty = 2.0f;                    // and, under scope 1, the penalty
   // one captured step per mode (a caller alternating tts_ar_step / tts_ar_step_sample, or bench's device_topk on/off loop, re-instantiated
   // the ~150-node graph on every switch)
   hipGraph_t graphs[3] = {};
@@ -1298,16 +1342,21 @@ struct ArState {
   // everything the captured step bakes into its nodes: the graph of the previous utterance is replayed when nothing moved
   struct GraphSig {
     int B = 0, max_pos = 0, lut = 0, wmode = 0, mode = 0, multi = 0;
-    const void *p[12] = {};
+    int scope = 0, pf_min = 0; // the sampler controls a step bakes in: penalty scope (an extra node / the penalising prefilter), the prefilter's keep bound (modes 1, 2)
+    float penalty = 0;         // scope 1, modes 1 / 2
+    const void *p[13] = {};
     bool operator==(const GraphSig &o) const {
-      return B == o.B && max_pos == o.max_pos && lut == o.lut && wmode == o.wmode && mode == o.mode && multi == o.multi && std::equal(p, p + 12, o.p);
+      return B == o.B && max_pos == o.max_pos && lut == o.lut && wmode == o.wmode && mode == o.mode && multi == o.multi && scope == o.scope &&
+             pf_min == o.pf_min && penalty == o.penalty && std::equal(p, p + 13, o.p);
     }
   } graph_sigs[3];
   GraphSig current_sig(int lut, int wmode) const {
     GraphSig g;
     g.B = B; g.max_pos = max_pos; g.lut = lut; g.wmode = wmode; g.mode = step_mode; g.multi = multi;
-    const void *q[12] = {h.p, qkv.p, att.p, ff.p, kcache.p, vcache.p, d_toks.p, logits.p, h_toks, h_logits, h_pf, multi ? row_off.p : nullptr};
-    std::copy(q, q + 12, g.p);
+    g.scope = step_scope; g.pf_min = step_mode ? step_pf_min : 0; g.penalty = (step_scope && step_mode) ? step_penalty : 0.f;
+    const void *q[13] = {h.p, qkv.p, att.p, ff.p, kcache.p, vcache.p, d_toks.p, logits.p, h_toks, h_logits, h_pf, multi ? row_off.p : nullptr,
+                         step_scope ? hist.p : nullptr};
+    std::copy(q, q + 13, g.p);
     return g;
   }
   void drop_graph(int m) {
@@ -2031,6 +2080,13 @@ int ar_begin_groups(tts_ctx *ctx, const int32_t *text_ids, const int *n_text, in
     TTS_HIP(ctx, hipHostMalloc((void **)&st->h_pf, (size_t)B * TTS_PF_WORDS * 4));
     st->h_cap_B = B;
   }
+  st->hist_host.assign((size_t)B * TTS_HIST_WORDS, 0u); // a fresh history per begin: ids 1 and 8192 (what the prompt-shaped row of step 0 penalises)
+  for (int b = 0; b < B; b++) {
+    uint32_t *hb = st->hist_host.data() + (size_t)b * TTS_HIST_WORDS;
+    hb[1 >> 5] |= 1u << (1 & 31);
+    hb[8192 >> 5] |= 1u << (8192 & 31);
+  }
+  st->hist_dev_valid = false;
   // the decode-step graph is kept: ar_step re-captures it only if a buffer moved or the batch shape changed (GraphSig)
   // the decode step's h4 layout holds whole tiles of 16 candidates: the padding rows of the last tile are read (never stored), keep them finite
   CHECK(reserve_rows(ctx, st, std::max((B + 15) / 16 * 16, st->P)));
@@ -2163,11 +2219,16 @@ static int enqueue_decode_step(tts_ctx *ctx, ArState *st) {
     else if (wm == 1) dec_ln_gemv_kernel<DEC_LOGITS, 2, false, true><<<dim3(VPAD / 16, tiles), 256, 0, ctx->stream>>>(a);
     else DEC_LN_LAUNCH(DEC_LOGITS, dim3(VPAD / 16, tiles), true); }
   if (st->step_mode == 0) {
+    if (st->step_scope) hist_mark_kernel<<<(B + 255) / 256, 256, 0, ctx->stream>>>(st->h_toks, B, st->hist.as<uint32_t>()); // the one node scope 1 adds
     TTS_HIP(ctx, hipMemcpyAsync(st->h_logits, st->logits.p, (size_t)B * V * 4, hipMemcpyDeviceToHost, ctx->stream));
   } else { // the sampler's top-k prefilter on the device: 16 KB instead of 524 KB back to the host per step of 16 candidates
     ProfScope ps(ctx, "ar_prefilter", (double)B * V * 4.0);
     // the lists are written straight into pinned host memory (1 KB per candidate over PCIe from the kernel's stores): no copy node behind the graph
-    sample_prefilter_kernel<<<B, 256, 0, ctx->stream>>>(st->logits.as<float>(), st->step_mode == 2, st->h_pf);
+    if (st->step_scope)
+      sample_prefilter_kernel<true><<<B, 256, 0, ctx->stream>>>(st->logits.as<float>(), st->step_mode == 2, st->step_pf_min, st->h_pf, st->hist.as<uint32_t>(),
+                                                                 st->h_toks, st->step_penalty);
+    else
+      sample_prefilter_kernel<false><<<B, 256, 0, ctx->stream>>>(st->logits.as<float>(), st->step_mode == 2, st->step_pf_min, st->h_pf, nullptr, nullptr, 1.0f);
   }
   TTS_HIP(ctx, hipGetLastError());
   return TTS_OK;
@@ -2182,15 +2243,26 @@ int ar_step(tts_ctx *ctx, const int32_t *prev_ids, int step_i, float *logits_out
   if (mode < 0 || mode > 2 || (mode && logits_out)) return fail(ctx, TTS_ERR_ARG, "ar_step: bad mode");
   st->step_mode = mode;
   if (step_i < 0 || st->P + step_i >= st->max_pos) return fail(ctx, TTS_ERR_LIMIT, "step %d beyond the KV cache", step_i); // (P: the longest prompt's)
-  for (int c = 0; c < st->B; c++) {
+  for (int c = 0; c < st->B; c++)
     if (prev_ids[c] < 0 || prev_ids[c] >= V) return fail(ctx, TTS_ERR_ARG, "mel token %d out of range", prev_ids[c]);
-    st->h_toks[c] = prev_ids[c];
-  }
-  st->h_toks[st->B] = st->multi ? step_i : st->P + step_i; // n_past (several prompts: the kernels add the row's P, ArState::row_off)
-  st->h_toks[st->B + 1] = step_i + 2; // mel position id (main.cpp:5244)
   // checked here, not inside enqueue_decode_step: that runs between hipStreamBeginCapture and hipStreamEndCapture
   if (ctx->ar_weights != 0 && ctx->ar_weights != st->loaded_wmode)
     return fail(ctx, TTS_ERR_STATE, "option ar_weights = %d must be set before tts_load_ar (the fp16 / fp8 slabs are packed at load)", ctx->ar_weights);
+  // the sampler controls this step bakes into its nodes (GraphSig), and the history sets of penalty scope 1
+  st->step_scope = ctx->ar_penalty_scope;
+  st->step_pf_min = pf_min_for(ctx->ar_sp.top_k);
+  st->step_penalty = ctx->ar_sp.penalty;
+  if (st->step_scope && !st->hist_dev_valid) { // before this step's ids join the host copy: the step's own kernel adds them on the device
+    TTS_HIP(ctx, st->hist.reserve(st->hist_host.size() * 4));
+    TTS_HIP(ctx, hipMemcpy(st->hist.p, st->hist_host.data(), st->hist_host.size() * 4, hipMemcpyHostToDevice));
+  }
+  st->hist_dev_valid = st->step_scope != 0;
+  for (int c = 0; c < st->B; c++) {
+    st->h_toks[c] = prev_ids[c];
+    st->hist_host[(size_t)c * TTS_HIST_WORDS + (prev_ids[c] >> 5)] |= 1u << (prev_ids[c] & 31);
+  }
+  st->h_toks[st->B] = st->multi ? step_i : st->P + step_i; // n_past (several prompts: the kernels add the row's P, ArState::row_off)
+  st->h_toks[st->B + 1] = step_i + 2; // mel position id (main.cpp:5244)
   static const bool no_graph = getenv("TTS_NO_GRAPH") != nullptr; // e.g. under rocprofv3, which crashes on graph replays here
   // event records are not captured: the step runs eagerly while one of its own kernel families ("ar_*") is profiled
   // ("ar_decode_step" brackets the whole graph replay and keeps the graph)
@@ -2219,6 +2291,16 @@ int ar_step(tts_ctx *ctx, const int32_t *prev_ids, int step_i, float *logits_out
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (logits_out) memcpy(logits_out, st->h_logits, (size_t)st->B * V * 4);
   return TTS_OK;
+}
+
+// Candidate c's history set as ascending ids (penalty scope 1: what the full-row sampler penalises; the host copy of the bitmap the device kernel reads).
+void ar_history_ids(const tts_ctx *ctx, int c, std::vector<int32_t> &out) {
+  out.clear();
+  const ArState *st = ctx->ar;
+  if (!st || c < 0 || c >= st->B) return;
+  const uint32_t *hb = st->hist_host.data() + (size_t)c * TTS_HIST_WORDS;
+  for (int w = 0; w < TTS_HIST_WORDS; w++)
+    for (uint32_t m = hb[w]; m; m &= m - 1) out.push_back(w * 32 + __builtin_ctz(m));
 }
 
 // The pinned lists of the last mode 1 / 2 step ([B][TTS_PF_WORDS]).

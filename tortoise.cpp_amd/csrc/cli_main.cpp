@@ -39,6 +39,11 @@
 //   deterministic) and --cond-free-k <x> (guidance strength, default 2.0): the diffusion sampler behind --steps, which keeps its meaning. Another sampler name or a value
 //   out of range is a usage error (exit 1) before a model is loaded or a worker started. --devices N workers receive the flags with the rest of the command line;
 //   --timing 1 echoes them ("[timing] sampler ...", one line per process).
+// --temperature <x> (> 0, default 0.8), --top-k <n> (1 .. 8194, default 50), --top-p <x> (0 < x <= 1, default 0.8), --repetition-penalty <x> (>= 1, default 2.0) and
+//   --penalty-scope last|history (default last = the reference: the ids of the last input; history = upstream's HF generate: every code sampled so far): the
+//   autoregressive sampler (options ar_temperature, ar_top_k, ar_top_p, ar_repetition_penalty, ar_penalty_scope). A value out of range or another scope name is a usage
+//   error (exit 1) before a model is loaded or a worker started; an absent flag leaves the engine option alone. --devices N workers receive the flags with the rest
+//   of the command line; --timing 1 echoes them ("[timing] ar sampler ...").
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -76,6 +81,9 @@ int main(int argc, char **argv) {
   std::string sampler = "ddpm";
   double ddim_eta = 0.0, cond_free_k = 2.0;
   bool have_sampler = false, have_eta = false, have_k = false; // a flag that is absent leaves the engine's option (default, or --option) alone
+  double ar_temp = 0.8, ar_top_k = 50, ar_top_p = 0.8, ar_pen = 2.0; // the autoregressive sampler's controls, same rule
+  std::string ar_scope = "last";
+  bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
   for (int i = 1; i < argc - 1; ++i) {
     std::string a(argv[i]);
@@ -108,6 +116,11 @@ int main(int argc, char **argv) {
     else if (a == "--sampler") { sampler = argv[i + 1]; have_sampler = true; }
     else if (a == "--ddim-eta") { ddim_eta = std::atof(argv[i + 1]); have_eta = true; }
     else if (a == "--cond-free-k") { cond_free_k = std::atof(argv[i + 1]); have_k = true; }
+    else if (a == "--temperature") { ar_temp = std::atof(argv[i + 1]); have_temp = true; }
+    else if (a == "--top-k") { ar_top_k = std::atof(argv[i + 1]); have_top_k = true; }
+    else if (a == "--top-p") { ar_top_p = std::atof(argv[i + 1]); have_top_p = true; }
+    else if (a == "--repetition-penalty") { ar_pen = std::atof(argv[i + 1]); have_pen = true; }
+    else if (a == "--penalty-scope") { ar_scope = argv[i + 1]; have_scope = true; }
     else if (a == "--rccl-id") rccl_id = argv[i + 1]; // worker mode (set by the parent)
     else if (a == "--shard") { // worker mode (set by the parent): "r/N"
       std::string v(argv[i + 1]);
@@ -119,6 +132,11 @@ int main(int argc, char **argv) {
   if (sampler != "ddpm" && sampler != "ddim") { fprintf(stderr, "--sampler %s: ddpm or ddim\n", sampler.c_str()); return 1; }
   if (!(ddim_eta >= 0.0 && ddim_eta <= 1.0)) { fprintf(stderr, "--ddim-eta %g: a value in 0 .. 1\n", ddim_eta); return 1; }
   if (!(cond_free_k >= 0.0) || !std::isfinite(cond_free_k)) { fprintf(stderr, "--cond-free-k %g: a finite value >= 0\n", cond_free_k); return 1; }
+  if (!std::isfinite(ar_temp) || !((float)ar_temp > 0) || !std::isfinite((float)ar_temp)) { fprintf(stderr, "--temperature %g: a finite value > 0\n", ar_temp); return 1; }
+  if (!(ar_top_k >= 1 && ar_top_k <= 8194) || ar_top_k != std::floor(ar_top_k)) { fprintf(stderr, "--top-k %g: an integer in 1 .. 8194\n", ar_top_k); return 1; }
+  if (!(ar_top_p > 0 && ar_top_p <= 1) || !((float)ar_top_p > 0)) { fprintf(stderr, "--top-p %g: a value in (0, 1]\n", ar_top_p); return 1; }
+  if (!std::isfinite(ar_pen) || !(ar_pen >= 1) || !std::isfinite((float)ar_pen)) { fprintf(stderr, "--repetition-penalty %g: a finite value >= 1\n", ar_pen); return 1; }
+  if (ar_scope != "last" && ar_scope != "history") { fprintf(stderr, "--penalty-scope %s: last or history\n", ar_scope.c_str()); return 1; }
   if (split_ids != 0 && (devices > 1 || exchange == "rccl" || shard >= 0)) {
     fprintf(stderr, "--split-text cannot be combined with --devices > 1 or --exchange rccl (one process runs all chunks)\n");
     return 1;
@@ -260,7 +278,12 @@ int main(int argc, char **argv) {
   if ((have_sampler && tts_set_option(ctx, "diff_sampler", sampler == "ddim" ? 1.0 : 0.0)) || (have_eta && tts_set_option(ctx, "ddim_eta", ddim_eta)) ||
       (have_k && tts_set_option(ctx, "cond_free_k", cond_free_k)))
     return die(ctx, "--sampler");
+  if ((have_temp && tts_set_option(ctx, "ar_temperature", ar_temp)) || (have_top_k && tts_set_option(ctx, "ar_top_k", ar_top_k)) ||
+      (have_top_p && tts_set_option(ctx, "ar_top_p", ar_top_p)) || (have_pen && tts_set_option(ctx, "ar_repetition_penalty", ar_pen)) ||
+      (have_scope && tts_set_option(ctx, "ar_penalty_scope", ar_scope == "history" ? 1.0 : 0.0)))
+    return die(ctx, "--temperature / --top-k / --top-p / --repetition-penalty / --penalty-scope");
   if (timing) {
+    fprintf(stderr, "[timing] ar sampler temperature %g, top-k %g, top-p %g, repetition-penalty %g, penalty-scope %s\n", ar_temp, ar_top_k, ar_top_p, ar_pen, ar_scope.c_str());
     if (shard >= 0) fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d (worker %d/%d)\n", sampler.c_str(), ddim_eta, cond_free_k, steps, shard, nshards);
     else fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d\n", sampler.c_str(), ddim_eta, cond_free_k, steps);
   }

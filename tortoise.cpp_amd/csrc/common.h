@@ -93,6 +93,15 @@ struct DiffCondEncState;
 struct Tokenizer;
 struct SamplerPool;
 void sampler_pool_free(SamplerPool *p);
+// The autoregressive sampler's controls (options "ar_temperature", "ar_top_k", "ar_top_p", "ar_repetition_penalty"): the defaults are the literals of
+// process_logits_and_sample (main.cpp:4753-4806); upstream tortoise-tts passes the same four to HF generate on every call.
+struct SamplerParams {
+  float temp = 0.8f;    // logit /= temp (temp_inplace)
+  int top_k = 50;       // top_k_inplace: ties at the k-th value survive
+  float top_p = 0.8f;   // top_p_inplace masks while the ascending cumulative sum is <= 1 - top_p (the reference's literal 0.2)
+  float penalty = 2.0f; // apply_penalty: g < 0 ? g * penalty : g / penalty
+  double top_p_cut() const { return 1.0 - (double)top_p; } // compared against the float sum widened to double, as `x <= 0.2` is; exact: 1 - 0.8f is the largest float below 0.2
+};
 
 } // namespace tts
 
@@ -119,6 +128,8 @@ struct tts_ctx {
   tts::DiffCondEncState *dcond = nullptr; // diffusion conditioning encoder (extras.hip; not in the reference)
   tts::Tokenizer *tok = nullptr;
   tts::SamplerPool *sampler_pool = nullptr; // worker threads for the per-candidate sampler scans (host_logic.cpp)
+  tts::SamplerParams ar_sp;                 // options "ar_temperature" / "ar_top_k" / "ar_top_p" / "ar_repetition_penalty"
+  int ar_penalty_scope = 0;                 // option "ar_penalty_scope": 0 = the reference (the ids of the last input), 1 = upstream's HF generate (every id fed since tts_ar_begin*, plus 1 and 8192)
   int device_topk = 1;                      // option "device_topk": tts_autoregressive's loop samples from the device prefilter's lists
   int time_mlp_retries = 0;                 // evaluations of the diffusion time MLP that disagreed with their repetition (diffusion.hip: precompute_time)
   int topk_fallbacks = 0;                   // candidates x steps of the last tts_autoregressive call that needed their full row
@@ -314,15 +325,28 @@ struct Tokenizer {
 };
 void sample_candidates(tts_ctx *ctx, const float *logits, const int32_t *ids, int ids_per_cand, int B,
                        int32_t *out);
+// The penalty ids of candidate c. Called from the sampler pool's threads, except by sample_candidates_list with already_penalised (only its serial
+// full-row fallback asks, so the callee may build the ids on demand into one scratch buffer).
+using PenaltyIdsFn = std::function<void(int c, const int32_t *&ids, int &n_ids)>;
+void sample_candidates(tts_ctx *ctx, const float *logits, const PenaltyIdsFn &ids_of, int B, int32_t *out);
 // Device top-k prefilter of the decode step (ar.hip: sample_prefilter_kernel; option "device_topk"): per candidate TTS_PF_WORDS
 // 32-bit words {n, 0, 0, 0, idx[TTS_PF_MAX], logit bits[TTS_PF_MAX]} = every logit >= a threshold that keeps TTS_PF_MIN..TTS_PF_MAX
-// of the 8194, in index order (n = -1: no such threshold, the host samples from the full row).
-enum { TTS_PF_MIN = 64, TTS_PF_MAX = 128, TTS_PF_WORDS = 4 + 2 * TTS_PF_MAX };
+// of the 8194, in index order (n = -1: no such threshold, the host samples from the full row). The window's lower bound follows the sampler's top-k
+// (pf_min: TTS_PF_MIN serves the default 50); above TTS_PF_TOPK_MAX no window fits the list and every candidate takes its full row.
+// Penalty scope 1 (sample_prefilter_kernel<true>): the lists hold PENALISED values, the penalty set being the candidate's history bitmap of
+// TTS_HIST_WORDS 32-bit words (bit i = id i was fed since tts_ar_begin*, plus 1 and 8192).
+enum { TTS_PF_MIN = 64, TTS_PF_MAX = 128, TTS_PF_WORDS = 4 + 2 * TTS_PF_MAX, TTS_PF_SLACK = TTS_PF_MIN - 50, TTS_PF_TOPK_MAX = 100, TTS_HIST_WORDS = 257 };
+inline int pf_min_for(int top_k) { return top_k <= TTS_PF_TOPK_MAX ? top_k + TTS_PF_SLACK : TTS_PF_MAX + 1; } // a bound above TTS_PF_MAX: the kernel writes n = -1 for every candidate
 int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
+                           const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired = nullptr);
+int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const PenaltyIdsFn &ids_of, bool already_penalised, int B, int32_t *out,
                            const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired = nullptr);
 int host_prefilter_row(const float *row, int keep, int32_t *list);
 int sample_one_row(const float *row, const int32_t *ids, int ids_per_cand, float uniform);
 int sample_one_from_list(const int32_t *list, const int32_t *ids, int ids_per_cand, float uniform);
+// the same two and the literal formulation with explicit parameters (tts_host_sample_row_ex / tts_host_sample_prefiltered_ex)
+int sample_one_row_ex(const float *row, const int32_t *ids, int n_ids, float uniform, const SamplerParams &p, bool literal_only);
+int sample_one_from_list_ex(const int32_t *list, const int32_t *ids, int n_ids, float uniform, const SamplerParams &p, bool already_penalised);
 void pad_codes(std::vector<int> &codes);            // apply_padding
 // Stop rule of the decode loop (main.cpp:5188-5249) for a batch of prompt groups: group g holds candidates [c0[g], c0[g] + n[g]).
 // Strict (the reference's rule, per group): a candidate's sequence freezes at its first 8193 and the group ENDS in the first iteration where all

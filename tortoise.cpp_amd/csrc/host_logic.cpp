@@ -344,7 +344,7 @@ std::vector<int> Tokenizer::encode(const std::string &message) const {
 // ---------------------------------------------------------------------------------------------
 static inline float exp_like_reference(float v) { return (float)::exp((double)v); } // exp(float) -> ::exp(double)
 
-static int multinomial_literal(std::vector<float> &l, float sample) {
+static int multinomial_literal(std::vector<float> &l, float sample, double top_p_cut) {
   const int V = (int)l.size();
   const float LOWEST = std::numeric_limits<float>::lowest();
   std::vector<std::pair<float, int>> pairs(V);
@@ -357,7 +357,7 @@ static int multinomial_literal(std::vector<float> &l, float sample) {
   for (int i = 0; i < V; i++) sl[i] /= sum;
   for (int i = 1; i < V; i++) sl[i] += sl[i - 1];
   for (int i = 0; i < V - 1; i++)
-    if (sl[i] <= 0.2) l[pairs[i].second] = LOWEST;
+    if (sl[i] <= top_p_cut) l[pairs[i].second] = LOWEST; // float against double, as the reference's `<= 0.2`
   sum = 0;
   for (int i = 0; i < V; i++) { l[i] = exp_like_reference(l[i]); sum += l[i]; }
   float cum = 0;
@@ -371,27 +371,35 @@ static int multinomial_literal(std::vector<float> &l, float sample) {
 struct Surv { float v; int idx; float e; };
 
 // Tail shared by the full-row scan and the device-prefiltered list: `s` = the top-k survivors in INDEX order with their tempered
-// values. top-p over the ascending order, final softmax + multinomial in index order. Returns -1 when two survivors tie (the
-// caller falls back to the literal formulation to inherit std::sort's tie order).
-static int sample_survivors(std::vector<Surv> &s, std::vector<Surv> &asc, float sample) {
+// values. top-p over the ascending order, final softmax + multinomial in index order. Survivors that tie: their exp terms are equal, so
+// every sum below is the same number whichever of them std::sort puts first, and the order matters only where the top-p cut (or the
+// exemption of the last element) separates two of them — then the tail returns -1 and the caller takes the literal formulation to inherit
+// std::sort's tie order (measured on the 2-layer synthetic model: bit-equal logits among the 50 survivors in about 1 row of 200).
+// Also -1 when a softmax sum is not a positive finite number (exp overflows at a small temperature: the literal formulation's NaN
+// handling is then the definition).
+static int sample_survivors(std::vector<Surv> &s, std::vector<Surv> &asc, float sample, double top_p_cut) {
   const int V = TTS_VOCAB_MEL;
   const float LOWEST = std::numeric_limits<float>::lowest();
   asc = s;
   std::sort(asc.begin(), asc.end(), [](const Surv &a, const Surv &b) { return a.v < b.v; });
-  for (size_t i = 1; i < asc.size(); i++)
-    if (asc[i].v == asc[i - 1].v) return -1;
   // top-p over the ascending survivors (non-survivors contribute exp(lowest) = +0)
   float sum = 0;
   for (auto &a : asc) { a.e = exp_like_reference(a.v); sum += a.e; }
+  if (!(sum > 0) || !std::isfinite(sum)) return -1;
   float cum = 0;
+  bool prev_below = false;
   for (size_t i = 0; i < asc.size(); i++) {
     cum += asc[i].e / sum;
-    if (i + 1 < asc.size() && cum <= 0.2)
+    const bool below = cum <= top_p_cut, last = i + 1 == asc.size();
+    if (i > 0 && asc[i].v == asc[i - 1].v && (below != prev_below || (last && below))) return -1; // the cut / the exemption falls inside a tie
+    prev_below = below;
+    if (!last && below)
       for (auto &b : s) if (b.idx == asc[i].idx) b.v = LOWEST; // cut
   }
   // final softmax + multinomial in index order
   sum = 0;
   for (auto &a : s) { a.e = (a.v == LOWEST) ? 0.f : exp_like_reference(a.v); sum += a.e; }
+  if (!(sum > 0) || !std::isfinite(sum)) return -1;
   if (!(0.0f < sample)) return 0; // cumulative(=0) >= sample already at index 0
   cum = 0;
   for (auto &a : s) {
@@ -401,15 +409,54 @@ static int sample_survivors(std::vector<Surv> &s, std::vector<Surv> &asc, float 
   return V - 1;
 }
 
-// One candidate, given its uniform draw: pure function of its arguments (runs on the sampler pool's threads).
-static int sample_one(const float *src, const int32_t *ids, int ids_per_cand, float sample) {
-  const int V = TTS_VOCAB_MEL, TOPK = 50;
+static inline float penalised(float g, float penalty) { return (g < 0) ? g * penalty : g / penalty; } // apply_penalty, main.cpp:4562-4570
+
+// The survivors of temp_inplace + top_k_inplace are {i : val(i) / temp >= hmin / temp}, hmin = the k-th largest penalised value (float
+// division by a positive temp is monotone, so the k-th largest quotient is the quotient of the k-th largest). That set is an up-set
+// {val >= cut}: cut = the smallest float whose quotient still reaches hmin / temp, found by stepping down from hmin. For ordinary values at
+// most two adjacent floats share a quotient; where the quotient saturates (overflow to inf, underflow to 0) the class is unbounded: after
+// 8 steps the caller gives up (false) and takes the literal formulation / the full row.
+static bool topk_cut(float hmin, float temp, float &cut) {
   const float LOWEST = std::numeric_limits<float>::lowest();
-  const float temp = 0.8;
+  const float kth = hmin / temp;
+  cut = hmin;
+  for (int tries = 0;; tries++) {
+    const float below = std::nextafter(cut, LOWEST);
+    if (below == cut) return false;
+    if (!(below / temp >= kth)) return true;
+    if (tries == 8) return false;
+    cut = below;
+  }
+}
+
+// Above this top-k the full-row sampler goes straight to the literal formulation (the heap scan below is built for a few dozen survivors).
+static const int FAST_TOPK_MAX = 512;
+
+// One candidate, given its uniform draw: pure function of its arguments (runs on the sampler pool's threads).
+static int sample_one(const float *src, const int32_t *ids, int ids_per_cand, float sample, const SamplerParams &p, bool literal_only = false) {
+  const int V = TTS_VOCAB_MEL, TOPK = p.top_k;
+  const float LOWEST = std::numeric_limits<float>::lowest();
+  const float temp = p.temp;
   thread_local std::vector<Surv> s, asc;
   thread_local std::vector<float> l; // only materialised for the (rare) literal fallback
-  // gather -> apply_penalty(2.0) -> scatter touches at most a few distinct ids (the prompt-shaped
-  // [1 ... 1, 8192] at step 0, the previous sample afterwards): keep them as overrides
+  thread_local std::vector<float> prow, heap;
+  auto literal = [&]() {
+    l.assign(src, src + V);
+    for (int j = 0; j < ids_per_cand; j++) {
+      const int id = ids[j];
+      l[id] = penalised(src[id], p.penalty);
+    }
+    for (int i = 0; i < V; i++) l[i] /= temp;
+    std::vector<float> tmp(l);
+    std::nth_element(tmp.begin(), tmp.begin() + (V - TOPK), tmp.end());
+    const float kth = tmp[V - TOPK];
+    for (int i = 0; i < V; i++) if (l[i] < kth) l[i] = LOWEST;
+    return multinomial_literal(l, sample, p.top_p_cut());
+  };
+  if (literal_only || TOPK > FAST_TOPK_MAX) return literal();
+  // gather -> apply_penalty -> scatter touches at most a few distinct ids under penalty scope 0 (the prompt-shaped
+  // [1 ... 1, 8192] at step 0, the previous sample afterwards): keep them as overrides. More than four (scope 1: the
+  // whole history): a penalised copy of the row is scanned instead.
   int pid[4]; float pval[4]; int np = 0;
   bool many = false;
   for (int j = 0; j < ids_per_cand; j++) {
@@ -418,81 +465,74 @@ static int sample_one(const float *src, const int32_t *ids, int ids_per_cand, fl
     for (int q = 0; q < np; q++) seen |= (pid[q] == id);
     if (seen) continue;
     if (np == 4) { many = true; break; }
-    const float g = src[id];
-    pid[np] = id; pval[np] = (g < 0) ? g * 2.0f : g / 2.0f; np++;
+    pid[np] = id; pval[np] = penalised(src[id], p.penalty); np++;
   }
-  auto literal = [&]() {
-    l.assign(src, src + V);
-    for (int j = 0; j < ids_per_cand; j++) {
-      const int id = ids[j];
-      const float g = src[id];
-      l[id] = (g < 0) ? g * 2.0f : g / 2.0f;
-    }
-    for (int i = 0; i < V; i++) l[i] /= temp;
-    std::vector<float> tmp(l);
-    std::nth_element(tmp.begin(), tmp.begin() + (V - TOPK), tmp.end());
-    const float kth = tmp[V - TOPK];
-    for (int i = 0; i < V; i++) if (l[i] < kth) l[i] = LOWEST;
-    return multinomial_literal(l, sample);
-  };
-  if (many) return literal();
-  auto val = [&](int i) { for (int q = 0; q < np; q++) if (pid[q] == i) return pval[q]; return src[i]; };
-  // k-th largest penalised logit: min-heap of the 50 largest seen so far (almost every element fails
+  const float *row = src;
+  if (many) {
+    prow.assign(src, src + V);
+    for (int j = 0; j < ids_per_cand; j++) prow[ids[j]] = penalised(src[ids[j]], p.penalty);
+    row = prow.data();
+    np = 0;
+  }
+  auto val = [&](int i) { for (int q = 0; q < np; q++) if (pid[q] == i) return pval[q]; return row[i]; };
+  // k-th largest penalised logit: min-heap of the k largest seen so far (almost every element fails
   // the single compare against the heap minimum)
-  float heap[TOPK];
+  heap.resize(TOPK);
   for (int i = 0; i < TOPK; i++) heap[i] = val(i);
-  std::make_heap(heap, heap + TOPK, std::greater<float>());
+  std::make_heap(heap.begin(), heap.end(), std::greater<float>());
   float hmin = heap[0];
   for (int i = TOPK; i < V; i++) {
-    float x = src[i];
-    if (x <= hmin) continue;              // (penalised values are <= their source unless negative*2, handled by val)
+    float x = row[i];
+    if (x <= hmin) continue;              // (penalised values are <= their source: x * p <= x < 0, x / p <= x otherwise, p >= 1)
     x = val(i);
     if (x <= hmin) continue;
-    std::pop_heap(heap, heap + TOPK, std::greater<float>());
+    std::pop_heap(heap.begin(), heap.end(), std::greater<float>());
     heap[TOPK - 1] = x;
-    std::push_heap(heap, heap + TOPK, std::greater<float>());
+    std::push_heap(heap.begin(), heap.end(), std::greater<float>());
     hmin = heap[0];
   }
-  // a penalised NEGATIVE logit is x*2 < x, a positive one x/2 < x: overrides never exceed src, so the scan
-  // above cannot miss them. Threshold on the tempered values: ties (also those created by the division's
-  // rounding: at most two adjacent floats share a quotient) survive, as in val_where_below_thresh.
-  const float kth = hmin / temp;
-  float cut = hmin;
-  for (int q = 0; q < 4; q++) cut = std::nextafter(cut, LOWEST);
+  // overrides never exceed their source, so the scan above cannot miss them. Threshold on the tempered values: ties (also
+  // those created by the division's rounding) survive, as in val_where_below_thresh: exactly the values >= cut (topk_cut).
+  float cut;
+  if (!topk_cut(hmin, temp, cut)) return literal();
   s.clear();
   for (int i = 0; i < V; i++) {
-    if (src[i] < cut) continue;
-    const float v = val(i) / temp;
-    if (v >= kth) s.push_back({v, i, 0.f});
+    if (row[i] < cut) continue;
+    const float x = val(i);
+    if (x >= cut) s.push_back({x / temp, i, 0.f});
   }
-  const int pick = sample_survivors(s, asc, sample);
+  const int pick = sample_survivors(s, asc, sample, p.top_p_cut());
   return pick < 0 ? literal() : pick; // a tie: inherit std::sort's tie order from the literal formulation
 }
 
-// The same candidate from the decode step's device prefilter (ar.hip: sample_prefilter_kernel): `n` (index, logit) pairs in index
-// order holding EVERY logit >= the smallest one listed, 54 <= n. Returns the id sample_one would return on the full row, or -1 when
-// that cannot be guaranteed from the list alone (the caller then fetches the row):
-//   - penalised values never exceed their source (x * 2 < x < 0, x / 2 <= x otherwise), so an unlisted logit stays below
-//     thr = min(list) after the penalty, while at least n - 4 >= 50 listed ones keep their value >= thr: the 50th largest penalised
-//     value `hmin` is >= thr and is found among the listed ones;
-//   - sample_one keeps i when src[i] >= cut (= hmin - 4 ulps) and val(i) / temp >= hmin / temp: with thr <= cut every such i is listed.
-//     thr > cut (the ~14 logits between rank 50 and rank n within 4 ulps of each other) -> -1;
-//   - more than 4 distinct penalty ids or a tie among the survivors need the literal formulation over the full row -> -1.
-static int sample_one_list(int n, const int32_t *idx, const float *lv, const int32_t *ids, int ids_per_cand, float sample) {
-  const int TOPK = 50;
-  const float LOWEST = std::numeric_limits<float>::lowest();
-  const float temp = 0.8;
+// The same candidate from the decode step's device prefilter (ar.hip: sample_prefilter_kernel): `n` (index, value) pairs in index
+// order holding EVERY value >= the smallest one listed (thr). already_penalised = false (penalty scope 0): the values are raw logits and
+// the penalty is applied here; true (scope 1): the kernel applied it. Returns the id sample_one would return on the full row, or -1 when
+// that cannot be guaranteed from the list alone (the caller then fetches the row). For any temperature > 0, top-k and penalty >= 1:
+//   - a penalised value never exceeds its source (x * p <= x < 0, x / p <= x otherwise), so in both forms every unlisted id has a
+//     penalised value < thr;
+//   - hmin = the k-th largest penalised value among the listed ones (n >= k) and cut = the smallest float with cut / temp >= hmin / temp
+//     (topk_cut: exact). The list decides iff thr <= cut: then hmin >= thr, the k largest penalised values of the row are all listed and
+//     hmin is the row's k-th largest; and every unlisted value is < cut, i.e. its quotient is < hmin / temp: no survivor is missing.
+//     thr > cut (the logits between rank k and rank n within an ulp or two of each other) -> -1;
+//   - raw lists: more than 4 distinct penalty ids are not looked up here -> -1; a tie among the survivors needs the literal
+//     formulation over the full row -> -1.
+static int sample_one_list(int n, const int32_t *idx, const float *lv, const int32_t *ids, int ids_per_cand, float sample, const SamplerParams &p,
+                           bool already_penalised) {
+  const int TOPK = p.top_k;
+  const float temp = p.temp;
   thread_local std::vector<Surv> s, asc;
   thread_local std::vector<float> pv;
-  if (n < TOPK + 4) return -1;
+  if (n < TOPK) return -1;
   int pid[4]; int np = 0;
-  for (int j = 0; j < ids_per_cand; j++) {
-    bool seen = false;
-    for (int q = 0; q < np; q++) seen |= (pid[q] == ids[j]);
-    if (seen) continue;
-    if (np == 4) return -1;
-    pid[np++] = ids[j];
-  }
+  if (!already_penalised)
+    for (int j = 0; j < ids_per_cand; j++) {
+      bool seen = false;
+      for (int q = 0; q < np; q++) seen |= (pid[q] == ids[j]);
+      if (seen) continue;
+      if (np == 4) return -1;
+      pid[np++] = ids[j];
+    }
   pv.resize(n);
   float thr = lv[0];
   for (int i = 0; i < n; i++) {
@@ -500,23 +540,19 @@ static int sample_one_list(int n, const int32_t *idx, const float *lv, const int
     thr = std::min(thr, g);
     bool pen = false;
     for (int q = 0; q < np; q++) pen |= (pid[q] == idx[i]);
-    pv[i] = pen ? ((g < 0) ? g * 2.0f : g / 2.0f) : g;
+    pv[i] = pen ? penalised(g, p.penalty) : g;
   }
-  asc.resize(n); // scratch: the 50th largest penalised value
+  asc.resize(n); // scratch: the k-th largest penalised value
   for (int i = 0; i < n; i++) asc[i].v = pv[i];
   std::nth_element(asc.begin(), asc.begin() + (TOPK - 1), asc.end(), [](const Surv &a, const Surv &b) { return a.v > b.v; });
   const float hmin = asc[TOPK - 1].v;
-  const float kth = hmin / temp;
-  float cut = hmin;
-  for (int q = 0; q < 4; q++) cut = std::nextafter(cut, LOWEST);
+  float cut;
+  if (!topk_cut(hmin, temp, cut)) return -1;
   if (!(thr <= cut)) return -1;
   s.clear();
-  for (int i = 0; i < n; i++) {
-    if (lv[i] < cut) continue;
-    const float v = pv[i] / temp;
-    if (v >= kth) s.push_back({v, idx[i], 0.f});
-  }
-  return sample_survivors(s, asc, sample);
+  for (int i = 0; i < n; i++)
+    if (pv[i] >= cut) s.push_back({pv[i] / temp, idx[i], 0.f});
+  return sample_survivors(s, asc, sample, p.top_p_cut());
 }
 
 // Small persistent pool for the per-candidate sampler work (16 independent scans of 8194 logits between two
@@ -614,30 +650,42 @@ static void run_on_pool(tts_ctx *ctx, int B, const std::function<void(int)> &one
   ctx->sampler_pool->run(B, one);
 }
 
-void sample_candidates(tts_ctx *ctx, const float *logits, const int32_t *ids, int ids_per_cand, int B,
-                       int32_t *out) {
+void sample_candidates(tts_ctx *ctx, const float *logits, const PenaltyIdsFn &ids_of, int B, int32_t *out) {
   const int V = TTS_VOCAB_MEL;
   std::vector<float> samples;
   draw_uniforms(ctx, B, samples);
-  run_on_pool(ctx, B, [&](int c) { out[c] = sample_one(logits + (size_t)c * V, ids + (size_t)c * ids_per_cand, ids_per_cand, samples[c]); });
+  const SamplerParams sp = ctx->ar_sp;
+  run_on_pool(ctx, B, [&](int c) {
+    const int32_t *ids = nullptr; int n_ids = 0;
+    ids_of(c, ids, n_ids);
+    out[c] = sample_one(logits + (size_t)c * V, ids, n_ids, samples[c], sp);
+  });
+}
+void sample_candidates(tts_ctx *ctx, const float *logits, const int32_t *ids, int ids_per_cand, int B,
+                       int32_t *out) {
+  sample_candidates(ctx, logits, [&](int c, const int32_t *&p, int &n) { p = ids + (size_t)c * ids_per_cand; n = ids_per_cand; }, B, out);
 }
 
-// The decode loop's sampler over the device prefilter's lists (ar.hip: [B][TTS_PF_WORDS] = {n, 0, 0, 0, idx[128], logit[128]}), same
-// uniforms, same ids. A candidate whose list cannot decide (n < 0: the device found no threshold keeping 64..128 logits; or
-// sample_one_list's -1) is sampled from its full row, fetched through `full_row` (which applies the stop mask itself).
+// The decode loop's sampler over the device prefilter's lists (ar.hip: [B][TTS_PF_WORDS] = {n, 0, 0, 0, idx[128], value[128]}), same
+// uniforms, same ids. A candidate whose list cannot decide (n < 0: the device found no threshold keeping pf_min..128 values; or
+// sample_one_list's -1) is sampled from its full row, fetched through `full_row` (which applies the stop mask itself) and penalised
+// here with ids_of(c) in either form.
 // `retired` (may be null): candidates whose sequence has ended (TTS_AR_RETIRE). Their uniforms are drawn like everybody's — the stream stays the reference's — but
 // nothing is sampled for them (out = 8193): round 5's ragged bench pass spent 27 ms per utterance evaluating lists and fetching full logits rows for candidates whose
 // sample the loop then threw away.
-int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
+int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const PenaltyIdsFn &ids_of, bool already_penalised, int B, int32_t *out,
                            const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired) {
   std::vector<float> samples;
   draw_uniforms(ctx, B, samples);
+  const SamplerParams sp = ctx->ar_sp;
   auto one = [&](int c) {
     if (retired && retired[c]) { out[c] = 8193; return; }
     const int32_t *l = lists + (size_t)c * TTS_PF_WORDS;
     const int n = l[0];
-    out[c] = (n < 1 || n > TTS_PF_MAX) ? -1
-                                       : sample_one_list(n, l + 4, (const float *)(l + 4 + TTS_PF_MAX), ids + (size_t)c * ids_per_cand, ids_per_cand, samples[c]);
+    if (n < 1 || n > TTS_PF_MAX) { out[c] = -1; return; }
+    const int32_t *ids = nullptr; int n_ids = 0;
+    if (!already_penalised) ids_of(c, ids, n_ids);
+    out[c] = sample_one_list(n, l + 4, (const float *)(l + 4 + TTS_PF_MAX), ids, n_ids, samples[c], sp, already_penalised);
   };
   if (B < 8 || ctx->sampler_threads == 0) { for (int c = 0; c < B; c++) one(c); } // ~2 us per list: the pool's wake-up costs more below 8
   else run_on_pool(ctx, B, one);
@@ -646,14 +694,21 @@ int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const int32_t *id
     if (out[c] >= 0) continue;
     const float *row = full_row(c);
     if (!row) return -1;
-    out[c] = sample_one(row, ids + (size_t)c * ids_per_cand, ids_per_cand, samples[c]);
+    const int32_t *ids = nullptr; int n_ids = 0;
+    ids_of(c, ids, n_ids);
+    out[c] = sample_one(row, ids, n_ids, samples[c], sp);
     fb++;
   }
   if (n_fallbacks) *n_fallbacks += fb;
   return 0;
 }
+int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
+                           const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired) {
+  return sample_candidates_list(ctx, lists, [&](int c, const int32_t *&p, int &n) { p = ids + (size_t)c * ids_per_cand; n = ids_per_cand; }, false, B, out,
+                                full_row, n_fallbacks, retired);
+}
 
-// Host restatement of the device prefilter for tests (tts_host_sample_prefiltered): the `keep` largest logits and every tie of the
+// Host restatement of the device prefilter for tests (tts_host_sample_prefiltered*): the `keep` largest values and every tie of the
 // smallest of them, in index order; n = -1 when that exceeds the list capacity.
 int host_prefilter_row(const float *row, int keep, int32_t *list) {
   const int V = TTS_VOCAB_MEL;
@@ -672,11 +727,17 @@ int host_prefilter_row(const float *row, int keep, int32_t *list) {
   return n;
 }
 
-int sample_one_row(const float *row, const int32_t *ids, int ids_per_cand, float uniform) { return sample_one(row, ids, ids_per_cand, uniform); }
-int sample_one_from_list(const int32_t *list, const int32_t *ids, int ids_per_cand, float uniform) {
+int sample_one_row_ex(const float *row, const int32_t *ids, int n_ids, float uniform, const SamplerParams &p, bool literal_only) {
+  return sample_one(row, ids, n_ids, uniform, p, literal_only);
+}
+int sample_one_from_list_ex(const int32_t *list, const int32_t *ids, int n_ids, float uniform, const SamplerParams &p, bool already_penalised) {
   const int n = list[0];
   if (n < 1 || n > TTS_PF_MAX) return -1;
-  return sample_one_list(n, list + 4, (const float *)(list + 4 + TTS_PF_MAX), ids, ids_per_cand, uniform);
+  return sample_one_list(n, list + 4, (const float *)(list + 4 + TTS_PF_MAX), ids, n_ids, uniform, p, already_penalised);
+}
+int sample_one_row(const float *row, const int32_t *ids, int ids_per_cand, float uniform) { return sample_one(row, ids, ids_per_cand, uniform, SamplerParams()); }
+int sample_one_from_list(const int32_t *list, const int32_t *ids, int ids_per_cand, float uniform) {
+  return sample_one_from_list_ex(list, ids, ids_per_cand, uniform, SamplerParams(), false);
 }
 
 // apply_padding, main.cpp:4510-4532 (the 8139 is the reference's literal, not 8193)
