@@ -325,6 +325,29 @@ int tts_clvp_score(tts_ctx *ctx, const int32_t *text_ids, int n_text, const int3
 /* ---- diffusion stage ----------------------------------------------------------------------- */
 /* T = L*4*24000/22050 (main.cpp:5616-5617) */
 int tts_diffusion_frames(int latent_rows);
+
+/* ---- HiFi-GAN decoder (not in the reference; additions within version 8, no prototype changed) ---------------------------------- */
+/* The second decoder of upstream tortoise-tts (api_fast.py; a HiFi-GAN generator taken from XTTS): the autoregressive stage's latents and the
+ * speaker latent (the --voice vector) straight to 24 kHz audio — no diffusion, no noise, no vocoder, so the same inputs always give the same
+ * samples. Upstream's source and weights are not available offline: the arithmetic is the one DESIGN.md states ("What pins the HiFi-GAN
+ * decoder"), pinned between this library, a torch restatement and that statement, unpinned against upstream; how it sounds is unjudged.
+ * File: the reference's container format, plain weights (weight-norm folded at conversion), names as tortoise.cpp_amd/synth_weights.py:
+ * hifigan_tensor_shapes lists them. A missing, unknown or mis-shaped tensor: TTS_ERR_FORMAT. */
+int tts_load_hifigan(tts_ctx *ctx, const char *path);
+/* Samples per candidate: 256 * tts_diffusion_frames(latent_rows) (the latents are interpolated to the diffusion stage's frame rate first). */
+int tts_hifigan_samples(int latent_rows);
+/* Frames on either side of a sample that can influence it (the generator is purely convolutional: interpolation 9, conv_pre 3, ResBlocks and
+ * transposed convolutions 9.3, rounded up): changing latent row L - 1 leaves the samples before 256 * (T - TTS_HFG_HALO_FRAMES) bit-identical, and a
+ * chunked call — not provided — would need this much context. */
+#define TTS_HFG_HALO_FRAMES 24
+/* latents: the trimmed rows of tts_autoregressive*, candidates back to back, rows[c] rows of 1024 each; voices [n_voices][1024]; candidate c
+ * speaks with voices[voice_of_candidate[c]] (voice_of_candidate == NULL: every candidate uses voice 0). audio_out: tts_hifigan_samples(rows[c])
+ * floats per candidate, back to back. One launch sequence for the whole ragged batch, one upload, one download; a candidate's samples do not depend
+ * on what else is in the batch. Every argument is checked before any device work: TTS_ERR_STATE before tts_load_hifigan; TTS_ERR_ARG for
+ * n_candidates < 1, n_voices < 1, rows < 1, a null pointer, a voice index outside [0, n_voices) or a non-finite latent or voice value;
+ * TTS_ERR_LIMIT for rows > 500 (or more than 4096 candidates). Profiler family: "hfg_conv" (work = FLOPs). */
+int tts_hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices,
+                       const int32_t *voice_of_candidate, float *audio_out);
 /* One diffusion_graph evaluation (main.cpp:5749-5841 cond / 5866-5961 uncond): inputs
  * input_latent_tensor [L][1024], noise_tensor = x_t [100][T], timestep (raw 0..3999 value whose
  * sinusoidal embedding the reference uploads as time_embedding_{i}); conditioning_free as the

@@ -75,6 +75,8 @@ def lib():
         "tts_split_turns": (ci, [vp, C.c_char_p, ci, ci, _i32p, _i32p, _i32p, ci]),
         "tts_host_ar_stop_run": (ci, [_i32p, ci, _i32p, ci, C.c_uint, vp, _i32p, _i32p, _i32p, vp]),
         "tts_diffusion_frames": (ci, [ci]),
+        "tts_load_hifigan": (ci, [vp, C.c_char_p]), "tts_hifigan_samples": (ci, [ci]),
+        "tts_hifigan_decode": (ci, [vp, vp, vp, ci, vp, ci, vp, vp]),
         "tts_diffusion_forward": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p]),
         "tts_diffusion": (ci, [vp, _f32p, _i32p, ci, ci, vp, ci, _f32p]),
         "tts_vocoder_samples": (ci, [ci]),
@@ -361,6 +363,32 @@ class Engine:
             codes[i, :len(c)] = c
         out = np.empty(len(codes_list), np.float32)
         self._ck(self.L.tts_clvp_score(self.h, np.ascontiguousarray(text_ids, np.int32), len(text_ids), codes.reshape(-1), lens, len(codes_list), stride, out))
+        return out
+
+    # ---- HiFi-GAN decoder (not in the reference): latents + speaker latent -> 24 kHz audio ----
+    def load_hifigan(self, path):
+        self._ck(self.L.tts_load_hifigan(self.h, path.encode()))
+
+    @staticmethod
+    def hifigan_samples(L):
+        return lib().tts_hifigan_samples(L)
+
+    def hifigan_decode(self, latents_list, voices, voice_of=None):
+        """latents_list: list of [L_c, 1024] (the trimmed rows of autoregressive()); voices: [1024] or [V, 1024]; voice_of [B] or None (every
+        candidate uses voice 0). Returns a list of float32 waveforms, 256 * frames(L_c) samples each (tts_hifigan_decode: one call)."""
+        rows = np.array([len(l) for l in latents_list], np.int32)
+        lat = np.ascontiguousarray(np.concatenate([np.asarray(l, np.float32).reshape(-1, DMODEL) for l in latents_list]))
+        tab = np.ascontiguousarray(voices, np.float32).reshape(-1, DMODEL)
+        idx = None if voice_of is None else np.ascontiguousarray(voice_of, np.int32)
+        if idx is not None and len(idx) != len(rows):
+            raise TtsError("voice_of names %d candidates, %d given" % (len(idx), len(rows)))
+        ns = [self.hifigan_samples(int(r)) for r in rows]
+        audio = np.empty(sum(ns), np.float32)
+        self._ck(self.L.tts_hifigan_decode(self.h, _ptr(lat), _ptr(rows), len(rows), _ptr(tab), len(tab), _ptr(idx), _ptr(audio)))
+        out, off = [], 0
+        for n in ns:
+            out.append(audio[off:off + n].copy())
+            off += n
         return out
 
     # ---- diffusion ----

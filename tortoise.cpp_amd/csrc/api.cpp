@@ -137,6 +137,7 @@ void tts_destroy(tts_ctx *c) {
   if (c->clvp) clvp_free(c->clvp);
   if (c->venc) voice_enc_free(c->venc);
   if (c->dcond) diff_cond_enc_free(c->dcond);
+  if (c->hifigan) hifigan_free(c->hifigan);
   if (c->fp16_counts) (void)hipFree(c->fp16_counts);
   delete c->tok;
   for (auto &kv : c->prof)
@@ -232,7 +233,7 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     // hipExtStreamCreateWithCUMask on gfx950: bit i = XCD i % 8, CU slot i / 8 (tools/cu_mask_probe.hip); an XCD with no bit set is
     // unrestricted, so every XCD keeps at least one CU. Only before any model is loaded / graph captured on the old stream.
     if (c->device < 0) return fail(c, TTS_ERR_HIP, "host-only context: no stream");
-    if (c->ar || c->diff || c->voc || c->clvp || c->venc || c->dcond) return fail(c, TTS_ERR_STATE, "stream_cus must be set before the models are loaded");
+    if (c->ar || c->diff || c->voc || c->clvp || c->venc || c->dcond || c->hifigan) return fail(c, TTS_ERR_STATE, "stream_cus must be set before the models are loaded");
     (void)hipSetDevice(c->device);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return fail(c, TTS_ERR_HIP, "hipGetDeviceProperties failed");
@@ -286,6 +287,13 @@ int tts_clvp_score(tts_ctx *c, const int32_t *text_ids, int n_text, const int32_
                    int code_stride, float *scores_out) {
   NEED_CTX(c);
   return guarded(c, [&] { return clvp_score(c, text_ids, n_text, codes, code_len, n_candidates, code_stride, scores_out); });
+}
+int tts_load_hifigan(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return hifigan_load(c, path); }); }
+int tts_hifigan_samples(int latent_rows) { return 256 * tts_diffusion_frames(latent_rows); }
+int tts_hifigan_decode(tts_ctx *c, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices,
+                       const int32_t *voice_of_candidate, float *audio_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return hifigan_decode(c, latents, rows, n_candidates, voices, n_voices, voice_of_candidate, audio_out); });
 }
 int tts_ar_layers(const tts_ctx *c) { return c ? ar_layers(c) : 0; }
 int tts_diffusion_layers(const tts_ctx *c) { return c ? diff_layers(c) : 0; }

@@ -44,6 +44,11 @@
 //   autoregressive sampler (options ar_temperature, ar_top_k, ar_top_p, ar_repetition_penalty, ar_penalty_scope). A value out of range or another scope name is a usage
 //   error (exit 1) before a model is loaded or a worker started; an absent flag leaves the engine option alone. --devices N workers receive the flags with the rest
 //   of the command line; --timing 1 echoes them ("[timing] ar sampler ...").
+// --decoder diffusion|hifigan (default diffusion = the reference's 80 diffusion steps + UnivNet): hifigan sends the kept candidates' latents and their voices through ONE
+//   tts_hifigan_decode call (upstream tortoise-tts' api_fast.py path: no diffusion, no noise, no vocoder) and writes 256 samples per frame. --hifigan-model <file>
+//   (default <models>/ggml-hifigan-model.bin); the diffusion and vocoder models are then neither loaded nor required. --clvp, --split-text and several --voice work
+//   as with the diffusion decoder. Usage errors (exit 1, before a model is loaded): another decoder name; with hifigan any of --steps, --sampler, --ddim-eta,
+//   --cond-free-k, --diffusion-latent (they configure the decoder that is not run), --devices > 1 or --exchange rccl. --timing 1 names the decoder ("[timing] decoder ...").
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -83,6 +88,8 @@ int main(int argc, char **argv) {
   bool have_sampler = false, have_eta = false, have_k = false; // a flag that is absent leaves the engine's option (default, or --option) alone
   double ar_temp = 0.8, ar_top_k = 50, ar_top_p = 0.8, ar_pen = 2.0; // the autoregressive sampler's controls, same rule
   std::string ar_scope = "last";
+  std::string decoder = "diffusion", hifiganPath;
+  bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
   for (int i = 1; i < argc - 1; ++i) {
@@ -93,7 +100,9 @@ int main(int argc, char **argv) {
     else if (a == "--seed") { seed = std::stoi(argv[i + 1]); have_seed = true; }
     else if (a == "--models") modelsDir = argv[i + 1];
     else if (a == "--candidates") candidates = std::stoi(argv[i + 1]);
-    else if (a == "--steps") steps = std::stoi(argv[i + 1]);
+    else if (a == "--steps") { steps = std::stoi(argv[i + 1]); have_steps = true; }
+    else if (a == "--decoder") decoder = argv[i + 1];
+    else if (a == "--hifigan-model") hifiganPath = argv[i + 1];
     else if (a == "--device") device = std::stoi(argv[i + 1]);
     else if (a == "--codes") fixed_codes = std::stoi(argv[i + 1]); // exactly N sampled codes, stop token masked (synthetic weights never stop)
     else if (a == "--devices") devices = std::stoi(argv[i + 1]);
@@ -129,6 +138,13 @@ int main(int argc, char **argv) {
     }
   }
   if (exchange != "files" && exchange != "rccl") { fprintf(stderr, "--exchange %s: files or rccl\n", exchange.c_str()); return 1; }
+  if (decoder != "diffusion" && decoder != "hifigan") { fprintf(stderr, "--decoder %s: diffusion or hifigan\n", decoder.c_str()); return 1; }
+  const bool use_hifigan = decoder == "hifigan";
+  if (use_hifigan) {
+    const char *bad = have_steps ? "--steps" : have_sampler ? "--sampler" : have_eta ? "--ddim-eta" : have_k ? "--cond-free-k" : !diffLatentPaths.empty() ? "--diffusion-latent" : nullptr;
+    if (bad) { fprintf(stderr, "%s configures the diffusion decoder, which --decoder hifigan does not run\n", bad); return 1; }
+    if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--decoder hifigan cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
+  }
   if (sampler != "ddpm" && sampler != "ddim") { fprintf(stderr, "--sampler %s: ddpm or ddim\n", sampler.c_str()); return 1; }
   if (!(ddim_eta >= 0.0 && ddim_eta <= 1.0)) { fprintf(stderr, "--ddim-eta %g: a value in 0 .. 1\n", ddim_eta); return 1; }
   if (!(cond_free_k >= 0.0) || !std::isfinite(cond_free_k)) { fprintf(stderr, "--cond-free-k %g: a finite value >= 0\n", cond_free_k); return 1; }
@@ -286,6 +302,7 @@ int main(int argc, char **argv) {
     fprintf(stderr, "[timing] ar sampler temperature %g, top-k %g, top-p %g, repetition-penalty %g, penalty-scope %s\n", ar_temp, ar_top_k, ar_top_p, ar_pen, ar_scope.c_str());
     if (shard >= 0) fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d (worker %d/%d)\n", sampler.c_str(), ddim_eta, cond_free_k, steps, shard, nshards);
     else fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d\n", sampler.c_str(), ddim_eta, cond_free_k, steps);
+    fprintf(stderr, "[timing] decoder %s\n", decoder.c_str());
   }
   if (shard >= 0) {
     tts_set_option(ctx, "rng_shard_offset", (double)(shard * candidates));
@@ -415,7 +432,9 @@ int main(int argc, char **argv) {
   int rc_diff = 0, rc_voc = 0;
   std::string err_diff, err_voc;
   struct Joiner { std::thread t; ~Joiner() { if (t.joinable()) t.join(); } } bg;
+  if (hifiganPath.empty()) hifiganPath = modelsDir + "/ggml-hifigan-model.bin";
   bg.t = std::thread([&]() {
+    if (use_hifigan) return; // its one model (56 MB, plain synchronous uploads) is loaded in front of its stage, as the reference loads every model
     rc_diff = tts_load_diffusion(ctx, (modelsDir + "/ggml-diffusion-model.bin").c_str());
     if (rc_diff) { err_diff = tts_last_error(ctx); return; }
     rc_voc = tts_load_vocoder(ctx, (modelsDir + "/ggml-vocoder-model.bin").c_str());
@@ -515,6 +534,17 @@ int main(int argc, char **argv) {
 
   bg.t.join();
   if (rc_diff) { fprintf(stderr, "diffusion_model_load: %s\n", err_diff.c_str()); return 1; }
+  if (use_hifigan) { // the kept candidates and their voices through one call
+    if (tts_load_hifigan(ctx, hifiganPath.c_str())) return die(ctx, "hifigan_model_load");
+    mark("load hifigan");
+    size_t total = 0;
+    for (int c = 0; c < B; c++) { nsamp.push_back((size_t)tts_hifigan_samples(rows[c])); total += nsamp.back(); }
+    audio.assign(total, 0.f);
+    if (multi_voice ? tts_hifigan_decode(ctx, lat_in, rows.data(), B, voices.data(), n_voices, chunk_voice.data(), audio.data())
+                    : tts_hifigan_decode(ctx, lat_in, rows.data(), B, voice.data(), 1, nullptr, audio.data()))
+      return die(ctx, "hifigan");
+    mark("hifigan");
+  } else {
   mark("wait for the diffusion + vocoder loads");
   if (!diffLatentPath.empty() && !multi_voice) {
     std::vector<float> dl(2048);
@@ -545,6 +575,7 @@ int main(int argc, char **argv) {
   if (tts_vocoder(ctx, mel.data(), frames.data(), B, nullptr, noise_mode, audio.data())) return die(ctx, "vocoder");
   mark("vocoder");
   for (int c = 0; c < B; c++) nsamp.push_back((size_t)tts_vocoder_samples(frames[c]));
+  } // diffusion decoder
   } // !dry
   auto write_one = [&](const float *samples, int64_t ns, int gc, bool is_output) {
     const std::string path = is_output ? outputPath : outputPath + "." + std::to_string(gc) + ".wav";

@@ -90,6 +90,7 @@ struct VocState;
 struct ClvpState;
 struct VoiceEncState;
 struct DiffCondEncState;
+struct HifiganState;
 struct Tokenizer;
 struct SamplerPool;
 void sampler_pool_free(SamplerPool *p);
@@ -126,6 +127,7 @@ struct tts_ctx {
   tts::ClvpState *clvp = nullptr; // candidate re-ranker (extras.hip; not in the reference)
   tts::VoiceEncState *venc = nullptr; // voice-conditioning encoder (extras.hip; not in the reference)
   tts::DiffCondEncState *dcond = nullptr; // diffusion conditioning encoder (extras.hip; not in the reference)
+  tts::HifiganState *hifigan = nullptr; // HiFi-GAN decoder: latents -> waveform (hifigan.hip; not in the reference: upstream's api_fast.py path)
   tts::Tokenizer *tok = nullptr;
   tts::SamplerPool *sampler_pool = nullptr; // worker threads for the per-candidate sampler scans (host_logic.cpp)
   tts::SamplerParams ar_sp;                 // options "ar_temperature" / "ar_top_k" / "ar_top_p" / "ar_repetition_penalty"
@@ -404,6 +406,10 @@ int diff_set_cond_latent(tts_ctx *ctx, const float *latent2048); // diffusion.hi
 int voice_enc_load(tts_ctx *ctx, const char *path);
 void voice_enc_free(VoiceEncState *);
 int voice_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out1024);
+int hifigan_load(tts_ctx *ctx, const char *path);
+void hifigan_free(HifiganState *);
+int hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices, const int32_t *voice_of_candidate,
+                   float *audio_out);
 int clvp_load(tts_ctx *ctx, const char *path);
 void clvp_free(ClvpState *);
 int clvp_score(tts_ctx *ctx, const int32_t *text_ids, int n_text, const int32_t *codes, const int32_t *code_len, int n_candidates, int code_stride,

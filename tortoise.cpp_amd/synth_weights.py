@@ -265,6 +265,54 @@ def write_diffusion_conditioning_encoder(path, blocks=5, seed=1239):
     w.close()
 
 
+HIFIGAN_UP = ((8, 16), (8, 16), (2, 4), (2, 4))  # (stride, kernel) of the four transposed convolutions
+HIFIGAN_RES_K = (3, 7, 11)                       # kernel sizes of the three ResBlocks of a stage
+HIFIGAN_RES_D = (1, 3, 5)                        # dilations of convs1 inside a ResBlock
+
+
+def hifigan_tensor_shapes():
+    """{name: PyTorch shape} of ggml-hifigan-model.bin: THE name table of the HiFi-GAN decoder (the loader in csrc/hifigan.hip spells the same
+    names; correct both when an upstream checkpoint shows different ones). Weight-norm is folded at conversion time: plain weights only."""
+    sh = {"hifigan.conv_pre.weight": (512, 1024, 7), "hifigan.conv_pre.bias": (512,),
+          "hifigan.cond_layer.weight": (512, 1024, 1), "hifigan.cond_layer.bias": (512,)}
+    ch = 512
+    for i, (u, ku) in enumerate(HIFIGAN_UP):
+        sh["hifigan.ups.%d.weight" % i] = (ch, ch // 2, ku)  # ConvTranspose1d: [Cin][Cout][K]
+        sh["hifigan.ups.%d.bias" % i] = (ch // 2,)
+        ch //= 2
+        for j, k in enumerate(HIFIGAN_RES_K):
+            for n in range(len(HIFIGAN_RES_D)):
+                for cv in ("convs1", "convs2"):
+                    p = "hifigan.resblocks.%d.%s.%d." % (3 * i + j, cv, n)
+                    sh[p + "weight"] = (ch, ch, k)
+                    sh[p + "bias"] = (ch,)
+    sh["hifigan.conv_post.weight"] = (1, 32, 7)
+    sh["hifigan.conv_post.bias"] = (1,)
+    return sh
+
+
+def write_hifigan(path, seed=1240, gain=1.0):
+    """ggml-hifigan-model.bin: the HiFi-GAN generator of upstream tortoise-tts' api_fast.py path (taken from XTTS): autoregressive latents + the
+    speaker latent -> 24 kHz waveform, no diffusion and no vocoder. Upstream's source and weights are not available offline: the arithmetic
+    is the one DESIGN.md ("What pins the HiFi-GAN decoder") states, the names are hifigan_tensor_shapes(). The branch gains keep the residual
+    stream at unit scale through the 36 ResBlocks; `gain` scales conv_post, so that the pre-tanh output has a standard deviation of a few
+    tenths for unit-variance latents (neither saturated nor near zero)."""
+    g = _Gen(seed)
+    w = GgmlWriter(path)
+    for name, shape in hifigan_tensor_shapes().items():
+        if name.endswith(".bias"):
+            w.add(name, g.normal(shape, 0.02))
+            continue
+        if ".ups." in name:   # every output sample sees K / stride taps of every input channel
+            i = int(name.split(".")[2])
+            fan, gn = shape[0] * shape[2] // HIFIGAN_UP[i][0], 1.4
+        else:
+            fan = shape[1] * shape[2]
+            gn = {"conv_pre": 1.0, "cond_layer": 0.5, "convs1": 1.4, "convs2": 0.45, "conv_post": 0.6 * gain}[name.split(".")[-3 if "convs" in name else -2]]
+        w.add(name, g.lecun(shape, fan, gn))
+    w.close()
+
+
 def write_all(out_dir, ar_layers=30, diff_main=10, diff_tail=3, diff_integ=3, diff_lc=4, seed=1234):
     import os
     os.makedirs(out_dir, exist_ok=True)
