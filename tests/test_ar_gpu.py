@@ -235,6 +235,28 @@ def test_fp16_decode_weights_option(pkg, oracle, small_models, voice):
     e2.close()
 
 
+def test_f32_mfma_decode_option(pkg, oracle, small_models, voice):
+    """Option dec_f32_mfma = 1 at load: the LayerNorm-GEMVs of the decode step multiply exact f32 products on the f32 slabs (layout mfma16, host-packed) instead of split
+    fp16. Exact products are no worse than the default's three fp16 products per K step, so the gate is test_prefill_and_steps_logits' own."""
+    eng = pkg.Engine(0)
+    try:
+        eng.set_option("dec_f32_mfma", 1)
+        eng.load(ar=small_models + "/ggml-model.bin")
+        ar = oracle.AR(oracle.Model(small_models + "/ggml-model.bin"))
+        toks, B = DEFAULT_TOKENS, 4
+        eng.ar_begin(toks, voice, B, 8)
+        ar.start(toks, voice, B, len(toks) + 2 + 9)
+        errs = [rel_err(eng.ar_prefill(), ar.prefill())]
+        rs = np.random.RandomState(B)
+        for i in range(3):
+            prev = rs.randint(0, 8192, B).astype(np.int32)
+            errs.append(rel_err(eng.ar_step(prev, i), ar.step(prev, i)))
+        print("dec_f32_mfma: logits rel err, prompt pass and steps", ["%.1e" % e for e in errs])
+        assert max(errs) < 1e-4
+    finally:
+        eng.close()
+
+
 def test_maximum_sizes(engine, oracle, small_models, voice):
     """The reference's limits at once: 404 text ids (all text positions), 500 sampled codes (what apply_padding accepts, main.cpp:4517),
     decode context 406 + 500 positions, the latent pass over all 502 mel positions (907 rows per candidate)."""

@@ -72,6 +72,62 @@ def test_malformed_vocoder_files(pkg, small_models, tmp_path):
         eng.close()
 
 
+def _payload_span(path, target):
+    """(offset, bytes) of the payload of record `target` in a weight file"""
+    with open(path, "rb") as f:
+        f.read(4)
+        while True:
+            n_dims, ln, _ = struct.unpack("<iii", f.read(12))
+            ne = struct.unpack("<%di" % n_dims, f.read(4 * n_dims))
+            name = f.read(ln).decode()
+            nbytes = 4 * int(np.prod(ne))
+            if name == target:
+                return f.tell(), nbytes
+            f.seek(nbytes, 1)
+
+
+LOADER_PATHS = {"device": {}, "host": {"load_device_pack": 0}}  # tts_load_ar: layouts by kernels from the file's tensors (default) / by the host packers
+
+
+@pytest.mark.parametrize("path", list(LOADER_PATHS))
+def test_malformed_ar_files(pkg, small_models, voice, tmp_path, path):
+    """Both loader paths of tts_load_ar look tensors up through one shape-checked function: a missing tensor, a wrong shape (on a small tensor that is resident and on
+    a matrix whose payload the device path leaves in the file: over 256 KB), an unknown name and a file cut inside a payload fail with the tensor's name."""
+    good = os.path.join(small_models, "ggml-model.bin")
+    h = "inference_model.transformer.h."
+    eng = pkg.Engine(0)
+    for k, v in LOADER_PATHS[path].items():
+        eng.set_option(k, v)
+
+    def bad(fname, edit, match):
+        p = str(tmp_path / fname)
+        _rewrite(good, p, edit)
+        with pytest.raises(pkg.TtsError, match=match):
+            eng.load(ar=p)
+    try:
+        bad("missing_layer.bin", lambda n, ne, d: None if n == h + "1.attn.c_proj.weight" else (n, ne, d), r"h\.1\.attn\.c_proj\.weight' missing from AR model file")
+        bad("missing_head.bin", lambda n, ne, d: None if n == "inference_model.lm_head.1.bias" else (n, ne, d), r"lm_head\.1 missing")
+        bad("bias_shape.bin", lambda n, ne, d: (n, [ne[0] // 2], d[:len(d) // 2]) if n == h + "0.mlp.c_fc.bias" else (n, ne, d),
+            r"h\.0\.mlp\.c_fc\.bias' has wrong shape in model file: got \[2048, 1\], expected \[4096, 1\]")
+        assert _payload_span(good, h + "1.mlp.c_fc.weight")[1] > 256 << 10
+        bad("matrix_shape.bin", lambda n, ne, d: (n, ne[::-1], d) if n == h + "1.mlp.c_fc.weight" else (n, ne, d),
+            r"h\.1\.mlp\.c_fc\.weight' has wrong shape in model file: got \[1024, 4096\], expected \[4096, 1024\]")
+        bad("unknown.bin", lambda n, ne, d: ("mel_pos_embedding.weird", ne, d) if n == "mel_pos_embedding.emb.weight" else (n, ne, d),
+            r"unknown tensor 'mel_pos_embedding\.weird'")
+        off, nbytes = _payload_span(good, h + "1.mlp.c_proj.weight")
+        assert nbytes > 256 << 10
+        p = str(tmp_path / "trunc.bin")
+        with open(good, "rb") as f, open(p, "wb") as g:
+            g.write(f.read(off + nbytes // 2))
+        with pytest.raises(pkg.TtsError, match="truncated"):
+            eng.load(ar=p)
+        eng.load(ar=good)  # the context is still usable
+        eng.ar_begin(DEFAULT_TOKENS, voice, 2, 4)
+        assert np.isfinite(eng.ar_prefill()).all()
+    finally:
+        eng.close()
+
+
 def test_call_order_and_argument_limits(pkg, small_models, voice):
     eng = pkg.Engine(0)
     try:
@@ -111,11 +167,15 @@ def test_call_order_and_argument_limits(pkg, small_models, voice):
         eng.close()
 
 
-def test_ar_weight_beyond_the_split_precision_range_is_rejected(pkg, small_models, tmp_path):
+@pytest.mark.parametrize("path", list(LOADER_PATHS))
+def test_ar_weight_beyond_the_split_precision_range_is_rejected(pkg, small_models, tmp_path, path):
     """The AR stage holds 64 W as an fp16 hi | lo pair (ar.hip: W16_SCALE): |W| >= 937 would become an fp16 infinity inside the MFMA operands. Such a file
-    fails at load with the tensor's name (round 6; weights of a trained GPT-2 are three orders of magnitude below), one at |W| = 100 loads."""
+    fails at load with the tensor's name (round 6; weights of a trained GPT-2 are three orders of magnitude below), one at |W| = 100 loads. Both loader paths
+    (max |w| found on the host / by a kernel) report it through one function."""
     good = os.path.join(small_models, "ggml-model.bin")
     eng = pkg.Engine(0)
+    for k, v in LOADER_PATHS[path].items():
+        eng.set_option(k, v)
 
     def scaled(target, peak):
         def edit(n, ne, d):

@@ -190,16 +190,56 @@ __global__ __launch_bounds__(256) void split_weight_kernel(const float *__restri
   }
 }
 
-// ---- load-time re-layouts on the device (round 6) -------------------------------------------------
-// The host packers above (strip_major, fold_layernorm, pack_mfma16h, pack_cols4) are index permutations plus one rounding each; tts_load_ar spent 5.9 s in them on one
-// core and still 0.5 s on sixteen. The same permutations as kernels: a worker uploads a tensor as it lies in the file and the layouts are produced from that copy.
-// Same arithmetic per element (f32 multiply by the LayerNorm gain, exact scaling by 64, round-to-nearest-even fp16 hi / lo, the double-precision column sums of the
-// folded bias in ascending k): the buffers equal the host packers' byte for byte (tests/test_ar_gpu.py compares the logits of the two loads bit for bit).
+// ---- load-time weight layouts: one index map per layout, shared by the host packers and the device kernels ------------------------------
+// Every layout below is a permutation of a weight matrix w [K][N] (N contiguous) plus at most one rounding per element. Each is written once, as a function from an
+// output offset to the source element, and applied twice: by the host packers (ArLoader, options load_device_pack = 0 / load_threads = 1 and the A/B slab options) in a loop
+// over the output, and by the pk_* kernels (the default: a worker uploads a tensor as it lies in the file and the layouts are produced from that copy; tts_load_ar spent
+// 5.9 s in the host loops on one core and still 0.5 s on sixteen). Same arithmetic per element on both sides (f32 multiply by the LayerNorm gain, exact scaling by 64,
+// round-to-nearest-even fp16 hi / lo, the double-precision column sums of the folded bias in ascending k): the buffers are equal byte for byte
+// (tests/test_ar_gpu.py compares the logits of the loads bit for bit).
+struct WAt { size_t k, n; }; // source element w[k][n]
+// strip-major: 64-column strips, [N/64][K][64], so that the K-chunk a GEMV workgroup streams is ONE contiguous region and a wave's load instruction covers 1 KB of
+// consecutive bytes (the reference re-transposes every matrix in every graph execution; here the layout is chosen once). 64 consecutive offsets are 64 consecutive sources.
+__host__ __device__ __forceinline__ WAt strip_major_at(size_t o, int K, int N) {
+  const size_t s0 = o / ((size_t)K * 64), rem = o % ((size_t)K * 64);
+  return {rem / 64, s0 * 64 + rem % 64};
+}
+// mfma16 (decode step, K = 1024, f32): slab of workgroup cb (16 columns) = 4 waves x 16 groups x 64 lanes x float4, where lane (m = lane & 15, q = lane >> 4) of wave wv
+// holds W[256 wv + 16 g + 4 q + j][16 cb + m], j = 0..3, for group g.
+__host__ __device__ __forceinline__ WAt mfma16_at(size_t o) {
+  const size_t j = o & 3, lane = (o >> 2) & 63, g = (o >> 8) & 15, wv = (o >> 12) & 3, cb = o >> 14;
+  return {wv * 256 + g * 16 + 4 * (lane >> 4) + j, cb * 16 + (lane & 15)};
+}
+// mfma16h (decode step, K = 1024, the fp16 family): the same slab for the fp16 MFMAs. Lane (m, q) of wave wv holds for K step s (32 k) the 8 values
+// k = 256 wv + 32 s + 8 q + e of column 16 cb + m: element i = (((cb 4 + wv) 8 + s) 64 + lane) 8 + e of the K N. Three encodings of that one order:
+//   fp16(64 w) at slot i, 16 contiguous bytes per lane and K step (option ar_weights = 1);
+//   split precision (the default): 8 fp16 hi at slot hilo, then 8 fp16 lo at hilo + 8 (hi = fp16(64 w), lo = fp16(64 w - hi)): 32 contiguous bytes per lane, 2 KB per
+//   wave and step;
+//   one e4m3 BYTE per value at slot fp8 (option ar_weights = 2): a lane's K steps 2 t and 2 t + 1 share one 16-byte load, byte ((((cb 4 + wv) 4 + t) 64 + lane) 2 + (s & 1)) 8 + e.
+struct Mfma16hAt { size_t k, n, hilo, fp8; };
+__host__ __device__ __forceinline__ Mfma16hAt mfma16h_at(size_t i) {
+  const size_t e = i & 7, lane = (i >> 3) & 63, s = (i >> 9) & 7, wv = (i >> 12) & 3, cb = i >> 14;
+  return {wv * 256 + s * 32 + 8 * (lane >> 4) + e, cb * 16 + (lane & 15), (i >> 3) * 16 + e, ((((cb * 4 + wv) * 4 + (s >> 1)) * 64 + lane) * 2 + (s & 1)) * 8 + e};
+}
+// cols4 (decode step, K = 1024 KG): slab of workgroup cb (4 columns) = KG x 4 x 256 threads x 4 values (the 4 columns: a float4, 4 fp16 or 4 e4m3 bytes), thread t
+// holding k = 1024 i + 4 t + kk.
+__host__ __device__ __forceinline__ WAt cols4_at(size_t o, int K) {
+  const unsigned c = o & 3, tid = (o >> 2) & 255, kk = (o >> 10) & 3, q = (unsigned)(o >> 12), KG = K / 1024; // q = cb KG + i
+  return {(size_t)(q % KG) * 1024 + 4 * tid + kk, (size_t)(q / KG) * 4 + c};
+}
+// the split-precision pair of 64 w
+struct HiLo { __half hi, lo; };
+__host__ __device__ __forceinline__ HiLo split_hilo(float w) {
+  const float v = W16_SCALE * w;
+  const __half hi = __float2half_rn(v);
+  return {hi, __float2half_rn(v - __half2float(hi))};
+}
+
 __global__ __launch_bounds__(256) void pk_strip_major_kernel(const float *__restrict__ w, int K, int N, float *__restrict__ t) {
   const size_t total = (size_t)K * N;
   for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256) {
-    const size_t s0 = o / ((size_t)K * 64), rem = o % ((size_t)K * 64);
-    t[o] = w[(rem / 64) * N + s0 * 64 + (rem % 64)];
+    const WAt a = strip_major_at(o, K, N);
+    t[o] = w[a.k * N + a.n];
   }
 }
 __global__ __launch_bounds__(256) void pk_fold_kernel(const float *__restrict__ w, int K, int N, const float *__restrict__ g, float *__restrict__ wf) {
@@ -222,27 +262,21 @@ __global__ __launch_bounds__(256) void pk_fold_bias_kernel(const float *__restri
   }
   cf[n] = (float)((double)c[n] + acc);
 }
-// pack_mfma16h: one thread per weight (K = 1024)
+// the split-precision mfma16h slab: one thread per weight (K = 1024)
 __global__ __launch_bounds__(256) void pk_mfma16h_kernel(const float *__restrict__ w, int N, __half *__restrict__ t) {
   const size_t total = (size_t)1024 * N;
-  for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256) {
-    const int e = (int)(o & 7), lane = (int)((o >> 3) & 63), s2 = (int)((o >> 9) & 7), wv = (int)((o >> 12) & 3);
-    const size_t cb = o >> 14;
-    const float v = W16_SCALE * w[(size_t)(wv * 256 + s2 * 32 + 8 * (lane >> 4) + e) * N + cb * 16 + (lane & 15)];
-    const __half hi = __float2half_rn(v);
-    const size_t base = ((((cb * 4 + wv) * 8 + s2) * 64 + lane) * 16);
-    t[base + e] = hi;
-    t[base + 8 + e] = __float2half_rn(v - __half2float(hi));
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const Mfma16hAt a = mfma16h_at(i);
+    const HiLo v = split_hilo(w[a.k * N + a.n]);
+    t[a.hilo] = v.hi;
+    t[a.hilo + 8] = v.lo;
   }
 }
 __global__ __launch_bounds__(256) void pk_cols4_kernel(const float *__restrict__ w, int K, int N, float *__restrict__ t) {
   const size_t total = (size_t)K * N;
-  const int KG = K / 1024;
   for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256) {
-    const int c = (int)(o & 3), tid = (int)((o >> 2) & 255), kk = (int)((o >> 10) & 3);
-    const size_t q = o >> 12; // cb * KG + i
-    const size_t cb = q / KG, i = q % KG;
-    t[o] = w[(i * 1024 + 4 * tid + kk) * N + cb * 4 + c];
+    const WAt a = cols4_at(o, K);
+    t[o] = w[a.k * N + a.n];
   }
 }
 // nn.Linear [V][D] -> [D][VPAD], zero padded
@@ -552,7 +586,7 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const float *__restrict
 // 32 cycles). Wave w covers k in [256w, 256w+256). Operands are fed swapped (A = weights,
 // B = activations) so that a lane ends with 4 consecutive output columns of one candidate. The 4 k values of
 // one MFMA are k0 + 4q + j for lane quarter q — a lane's activations are then one float4 of the natural
-// [row][k] layout; the weights are packed to match (pack_mfma16 below). LayerNorm is evaluated on the
+// [row][k] layout; the weights are packed to match (layout mfma16: mfma16_at). LayerNorm is evaluated on the
 // register-resident operands: a row's 1024 values live in 4 lanes x 4 waves.
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 enum { DEC_QKV = 0, DEC_GELU = 1, DEC_LOGITS = 2 };
@@ -565,9 +599,9 @@ __device__ long long tts_dec_trace[6 * 1024 * 8]; // slot: 0 LN1+QKV, 1 attentio
 struct DecLnArgs {
   const float *h;            // [rows][1024]
   const float *g1, *b1;      // DEC_LOGITS: ln_f (the LayerNorm feeding W is folded into W/bias at load)
-  const float *W;            // pack_mfma16 of diag(gamma) W
-  const __half *Wh;          // SPLIT 1: pack_mfma16h, the same matrix x 64 as fp16 hi|lo pairs; SPLIT 2: pack_mfma16q, fp16 hi only (option ar_weights = 1);
-                             // SPLIT 3: pack_mfma16o, OCP fp8 e4m3 of W / wscale[column] (option ar_weights = 2)
+  const float *W;            // layout mfma16 of diag(gamma) W
+  const __half *Wh;          // SPLIT 1: layout mfma16h, the same matrix x 64 as fp16 hi|lo pairs; SPLIT 2: mfma16h, fp16 hi only (option ar_weights = 1);
+                             // SPLIT 3: mfma16h, OCP fp8 e4m3 of W / wscale[column] (option ar_weights = 2)
   const float *bias;         // bias + beta . W
   int rows, n_valid, ldo;    // ldo: row stride of `out` for DEC_QKV (q) and DEC_LOGITS
   int prefill_B;             // DEC_QKV: 0 = decode (row = candidate, position n_past); > 0 = prompt pass (row = position,
@@ -795,13 +829,13 @@ __global__ __launch_bounds__(256) void dec_ln_gemv_kernel(DecLnArgs a_in) {
 }
 
 // h[rows][1024] += X[rows][K] . W[K][1024] + bias, K = 1024 * KG. One workgroup owns 4 output columns over the
-// whole K (W packed by pack_cols4: 16 KB x KG contiguous per workgroup); thread t holds k = 1024 i + 4 t + kk.
+// whole K (W in layout cols4, cols4_at: 16 KB x KG contiguous per workgroup); thread t holds k = 1024 i + 4 t + kk.
 // The 64 per-thread sums (16 candidates x 4 columns) are reduced with a 6-step exchange butterfly that
 // leaves output t on lane t, then across the 4 waves through LDS — a fixed summation tree.
 // NT threads per workgroup (256 or 512): with 512 the K range of a thread halves and twice as many activation loads
 // are in flight per CU — the c_proj of the MLP (K = 4096) reads 256 KB of activations per workgroup and is bound by how
 // many of those loads the CU keeps in flight.
-// WH: the slab holds fp16 weights (pack_cols4 order, 8 bytes per (k, 4 columns): option ar_weights = 1), converted to f32 in registers.
+// WH: the slab holds fp16 weights (cols4 order, 8 bytes per (k, 4 columns): option ar_weights = 1), converted to f32 in registers.
 // WH = 2: OCP fp8 (e4m3) weights, 4 bytes per (k, 4 columns), times the power-of-two wscale[column] after the reduction (option ar_weights = 2).
 template <int KG, int NT = 256, int WH = 0, bool NTW = false, bool HT = false> // HT: h is in the h4 layout (decode step)
 __global__ __launch_bounds__(NT) void dec_gemv_resid_kernel(const float *__restrict__ X, int rows, const float *__restrict__ W,
@@ -826,7 +860,7 @@ __global__ __launch_bounds__(NT) void dec_gemv_resid_kernel(const float *__restr
   for (int r = 0; r < 8; r++) xa0[r] = *(const float4 *)(X + (size_t)min(row0 + r, rows - 1) * K + 4 * tid);
   float4 w[NG][4];
   {
-    // pack_cols4 order: float4 index ((k / 1024) * 4 + kk) * 256 + (k % 1024) / 4 for k = g * NT * 4 + 4 * tid + kk
+    // cols4 order: float4 index ((k / 1024) * 4 + kk) * 256 + (k % 1024) / 4 for k = g * NT * 4 + 4 * tid + kk
     if (WH == 2) {
       const unsigned *wp = (const unsigned *)W + (size_t)cb * KG * 1024 + (tid & 255);
 #pragma unroll
@@ -1285,10 +1319,10 @@ struct ArLayerDev {
   float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
   float *w_attn, *b_attn, *w_proj, *b_proj, *w_fc, *b_fc, *w_fc2, *b_fc2;
   __half *s_attn = nullptr, *s_proj = nullptr, *s_fc = nullptr, *s_fc2 = nullptr; // [N][2K] hi|lo of 64*W^T
-  float *d_attn = nullptr, *d_fc = nullptr;   // pack_mfma16 of diag(ln gamma) W (decode step)
-  __half *dh_attn = nullptr, *dh_fc = nullptr; // pack_mfma16h of the same (split-precision variant)
+  float *d_attn = nullptr, *d_fc = nullptr;   // layout mfma16 of diag(ln gamma) W (decode step, option dec_f32_mfma)
+  __half *dh_attn = nullptr, *dh_fc = nullptr; // layout mfma16h, hi | lo, of the same (split-precision variant)
   float *db_attn = nullptr, *db_fc = nullptr; // bias + ln beta . W
-  float *d_proj = nullptr, *d_fc2 = nullptr;  // pack_cols4  (decode step)
+  float *d_proj = nullptr, *d_fc2 = nullptr;  // layout cols4 (decode step)
   __half *q_attn = nullptr, *q_fc = nullptr, *q_proj = nullptr, *q_fc2 = nullptr; // fp16-weight decode slabs (option ar_weights = 1 at load)
   // fp8-weight decode slabs (option ar_weights = 2 at load): e4m3 bytes in the same packing orders + one power-of-two scale per output column
   uint8_t *o_attn = nullptr, *o_fc = nullptr, *o_proj = nullptr, *o_fc2 = nullptr;
@@ -1300,10 +1334,10 @@ struct ArState {
   std::vector<ArLayerDev> L;
   float *text_emb = nullptr, *text_pos = nullptr, *mel_emb = nullptr, *mel_pos = nullptr;
   float *lnf_g = nullptr, *lnf_b = nullptr, *lmh_g = nullptr, *lmh_b = nullptr;
-  float *lm_w = nullptr /*[1024][VPAD] strip-major*/, *lm_b = nullptr /*[VPAD]*/, *d_lm = nullptr /*pack_mfma16, lm_head.0 folded*/, *d_lmb = nullptr;
-  __half *dh_lm = nullptr; // pack_mfma16h
-  __half *q_lm = nullptr;  // pack_mfma16q (option ar_weights = 1 at load)
-  uint8_t *o_lm = nullptr; // pack_mfma16o (option ar_weights = 2 at load)
+  float *lm_w = nullptr /*[1024][VPAD] strip-major*/, *lm_b = nullptr /*[VPAD]*/, *d_lm = nullptr /*mfma16, lm_head.0 folded*/, *d_lmb = nullptr;
+  __half *dh_lm = nullptr; // mfma16h hi | lo
+  __half *q_lm = nullptr;  // mfma16h fp16 (option ar_weights = 1 at load)
+  uint8_t *o_lm = nullptr; // mfma16h e4m3 (option ar_weights = 2 at load)
   float *os_lm = nullptr;
   int loaded_wmode = 0;    // the reduced-precision decode slabs this state was loaded with (0 = none, 1 = fp16, 2 = fp8)
   bool f32_mfma = false;   // option "dec_f32_mfma" at load: LayerNorm-GEMVs on v_mfma_f32_16x16x4_f32 (exact f32 products) instead of split fp16
@@ -1373,103 +1407,9 @@ struct ArState {
   }
 };
 
-void ar_free(ArState *s) { delete s; }
-
-static PinnedPool *ar_pin = nullptr; // pinned staging of the running ar_load (one load at a time per process: the loaders are not re-entrant across contexts)
-static hipStream_t ar_load_stream = nullptr;
-static hipError_t ar_h2d(void *dst, const void *src, size_t bytes) { return ar_pin ? ar_pin->upload(dst, src, bytes, ar_load_stream) : PinnedPool::copy_now(dst, src, bytes, ar_load_stream); }
-// a tensor that read_weight_file left in the file: pread() into pinned staging, DMA to dst
-static int ar_file_to_device(tts_ctx *ctx, const WeightFile &wf, const HostTensor &t, const std::string &name, void *dst) {
-  const size_t bytes = (size_t)t.nelem() * 4;
-  std::pair<void *, size_t> b = ar_pin ? ar_pin->take(bytes) : std::pair<void *, size_t>{nullptr, 0};
-  std::vector<float> tmp;
-  void *host = b.first;
-  if (!host) { tmp.resize((size_t)t.nelem()); host = tmp.data(); }
-  const bool ok = wf.read_payload(t, host);
-  const hipError_t e = ok ? PinnedPool::copy_now(dst, host, bytes, ar_load_stream) : hipSuccess;
-  if (ar_pin) ar_pin->give(b);
-  if (!ok) return fail(ctx, TTS_ERR_IO, "autoregressive_model_load: tensor '%s' truncated", name.c_str());
-  TTS_HIP(ctx, e);
-  return TTS_OK;
-}
-static std::mutex ar_own_mu; // ar_load builds the layers on several threads (common.h: run_parallel)
-static void ar_own(ArState *st, void *p) {
-  std::lock_guard<std::mutex> lk(ar_own_mu);
-  st->owned.push_back(p);
-}
-static int upload_h(tts_ctx *ctx, ArState *st, const std::vector<__half> &src, __half **dst) {
-  void *p = nullptr;
-  TTS_HIP(ctx, hipMalloc(&p, src.size() * sizeof(__half)));
-  ar_own(st, p);
-  TTS_HIP(ctx, ar_h2d(p, src.data(), src.size() * sizeof(__half)));
-  *dst = (__half *)p;
-  return TTS_OK;
-}
-
-static int upload(tts_ctx *ctx, ArState *st, const std::vector<float> &src, float **dst) {
-  void *p = nullptr;
-  TTS_HIP(ctx, hipMalloc(&p, src.size() * sizeof(float)));
-  ar_own(st, p);
-  TTS_HIP(ctx, ar_h2d(p, src.data(), src.size() * sizeof(float)));
-  *dst = (float *)p;
-  return TTS_OK;
-}
-
-// Weight matrices [K][N] (N contiguous) are re-tiled at load into 64-column strips, [N/64][K][64], so that the
-// K-chunk a GEMV workgroup streams is ONE contiguous region and a wave's load instruction covers 1 KB of
-// consecutive bytes (the reference re-transposes every matrix in every graph execution; here the layout
-// is chosen once).
-static std::vector<float> strip_major(const float *w, int K, int N) {
-  std::vector<float> t((size_t)K * N);
-  for (int s0 = 0; s0 < N / 64; s0++)
-    for (int k = 0; k < K; k++) memcpy(&t[((size_t)s0 * K + k) * 64], &w[(size_t)k * N + s0 * 64], 64 * sizeof(float));
-  return t;
-}
-
-// Decode-step layouts (w is [K][N], N contiguous).
-// pack_mfma16 (K = 1024): slab of workgroup cb (16 columns) = 4 waves x 16 groups x 64 lanes x float4, where lane
-// (m = lane & 15, q = lane >> 4) of wave wv holds W[256 wv + 16 g + 4 q + j][16 cb + m], j = 0..3, for group g.
-static std::vector<float> pack_mfma16(const float *w, int K, int N) {
-  std::vector<float> t((size_t)K * N);
-  for (int cb = 0; cb < N / 16; cb++)
-    for (int wv = 0; wv < 4; wv++)
-      for (int g = 0; g < 16; g++)
-        for (int lane = 0; lane < 64; lane++)
-          for (int j = 0; j < 4; j++)
-            t[((((size_t)cb * 4 + wv) * 16 + g) * 64 + lane) * 4 + j] =
-                w[(size_t)(wv * 256 + g * 16 + 4 * (lane >> 4) + j) * N + cb * 16 + (lane & 15)];
-  return t;
-}
-// pack_mfma16h (K = 1024): the same slab for the split-precision fp16 MFMA. Lane (m, q) of wave wv holds for K step s
-// (32 k) the 8 values k = 256 wv + 32 s + 8 q + e of column 16 cb + m, times 64, as 8 fp16 hi followed by 8 fp16 lo
-// (hi = fp16(64 w), lo = fp16(64 w - hi)): 32 contiguous bytes per lane, 2 KB per wave and step.
-static std::vector<__half> pack_mfma16h(const float *w, int K, int N) {
-  std::vector<__half> t((size_t)K * N * 2);
-  for (int cb = 0; cb < N / 16; cb++)
-    for (int wv = 0; wv < 4; wv++)
-      for (int s2 = 0; s2 < 8; s2++)
-        for (int lane = 0; lane < 64; lane++)
-          for (int e = 0; e < 8; e++) {
-            const float v = 64.0f * w[(size_t)(wv * 256 + s2 * 32 + 8 * (lane >> 4) + e) * N + cb * 16 + (lane & 15)];
-            const __half hi = __float2half_rn(v);
-            const size_t base = ((((size_t)cb * 4 + wv) * 8 + s2) * 64 + lane) * 16;
-            t[base + e] = hi;
-            t[base + 8 + e] = __float2half_rn(v - __half2float(hi));
-          }
-  return t;
-}
-// pack_mfma16q: pack_mfma16h without the lo halves — fp16(64 w), 16 contiguous bytes per lane and K step (option ar_weights = 1).
-static std::vector<__half> pack_mfma16q(const float *w, int K, int N) {
-  std::vector<__half> t((size_t)K * N);
-  for (int cb = 0; cb < N / 16; cb++)
-    for (int wv = 0; wv < 4; wv++)
-      for (int s2 = 0; s2 < 8; s2++)
-        for (int lane = 0; lane < 64; lane++)
-          for (int e = 0; e < 8; e++)
-            t[((((size_t)cb * 4 + wv) * 8 + s2) * 64 + lane) * 8 + e] =
-                __float2half_rn(64.0f * w[(size_t)(wv * 256 + s2 * 32 + 8 * (lane >> 4) + e) * N + cb * 16 + (lane & 15)]);
-  return t;
-}
+// ---------------------------------------------------------------------------------------------
+// loader
+// ---------------------------------------------------------------------------------------------
 // ---- OCP fp8 e4m3 (1-4-3, bias 7, largest finite 448, no infinities): round to nearest even, saturating ----
 static uint8_t fp8_e4m3_encode(float f) {
   const uint8_t sign = std::signbit(f) ? 0x80 : 0;
@@ -1506,49 +1446,41 @@ static std::vector<float> fp8_col_scales(const float *w, int K, int N) {
   }
   return sc;
 }
-// pack_mfma16o: pack_mfma16q's order with one BYTE per value (e4m3 of w / scale[column]); a lane's K steps 2 i and 2 i + 1 share one
-// 16-byte load: byte ((((cb 4 + wv) 4 + i) 64 + lane) 2 + (s & 1)) 8 + e
-static std::vector<uint8_t> pack_mfma16o(const float *w, int K, int N, const std::vector<float> &sc) {
-  std::vector<uint8_t> t((size_t)K * N);
-  for (int cb = 0; cb < N / 16; cb++)
-    for (int wv = 0; wv < 4; wv++)
-      for (int s2 = 0; s2 < 8; s2++)
-        for (int lane = 0; lane < 64; lane++)
-          for (int e = 0; e < 8; e++) {
-            const int n = cb * 16 + (lane & 15);
-            t[(((((size_t)cb * 4 + wv) * 4 + (s2 >> 1)) * 64 + lane) * 2 + (s2 & 1)) * 8 + e] =
-                fp8_e4m3_encode(w[(size_t)(wv * 256 + s2 * 32 + 8 * (lane >> 4) + e) * N + n] / sc[n]);
-          }
+
+// ---- host packers: a loop over the output offsets of a layout (the *_at maps beside the pk_* kernels, where the layouts are described) and one element encoder ----
+struct EncF32 { float operator()(float w, size_t) const { return w; } };
+struct EncF16 { float scale; __half operator()(float w, size_t) const { return __float2half_rn(scale * w); } };      // scale 1 or 64: exact
+struct EncFp8 { const float *sc; uint8_t operator()(float w, size_t n) const { return fp8_e4m3_encode(w / sc[n]); } }; // sc: fp8_col_scales
+// t[o] = enc(w[k][n], n) with (k, n) = at(o): every layout and encoding whose value for offset o lies AT o. RUN consecutive offsets have consecutive sources (a row of
+// a strip: 64, the columns of cols4: 4), so the map is evaluated once per run
+template <class T, int RUN, class At, class Enc> static std::vector<T> pack(const float *w, int K, int N, At at, Enc enc) {
+  std::vector<T> t((size_t)K * N);
+  for (size_t o = 0; o < t.size(); o += RUN) {
+    const auto a = at(o);
+    const float *src = &w[a.k * N + a.n];
+    for (int j = 0; j < RUN; j++) t[o + j] = enc(src[j], a.n + j);
+  }
   return t;
 }
-// pack_cols4o: pack_cols4's order with one byte per value: 4 bytes (the 4 columns) per (k, workgroup)
-static std::vector<uint8_t> pack_cols4o(const float *w, int K, int N, const std::vector<float> &sc) {
-  std::vector<uint8_t> t((size_t)K * N);
-  const int KG = K / 1024;
-  for (int cb = 0; cb < N / 4; cb++)
-    for (int i = 0; i < KG; i++)
-      for (int kk = 0; kk < 4; kk++)
-        for (int tid = 0; tid < 256; tid++)
-          for (int c = 0; c < 4; c++)
-            t[((((size_t)cb * KG + i) * 4 + kk) * 256 + tid) * 4 + c] =
-                fp8_e4m3_encode(w[(size_t)(i * 1024 + 4 * tid + kk) * N + cb * 4 + c] / sc[cb * 4 + c]);
+static std::vector<float> strip_major(const float *w, int K, int N) {
+  return pack<float, 64>(w, K, N, [=](size_t o) { return strip_major_at(o, K, N); }, EncF32{});
+}
+static std::vector<__half> pack_mfma16h(const float *w, int N) { // the split-precision encoding: hi | lo
+  std::vector<__half> t((size_t)1024 * N * 2);
+  for (size_t i = 0; i < (size_t)1024 * N; i++) {
+    const Mfma16hAt a = mfma16h_at(i);
+    const HiLo v = split_hilo(w[a.k * N + a.n]);
+    t[a.hilo] = v.hi;
+    t[a.hilo + 8] = v.lo;
+  }
   return t;
 }
-static std::vector<__half> to_half(const std::vector<float> &v) {
-  std::vector<__half> t(v.size());
-  for (size_t i = 0; i < v.size(); i++) t[i] = __float2half_rn(v[i]);
-  return t;
-}
-// pack_cols4 (K = 1024 KG): slab of workgroup cb (4 columns) = KG x 4 x 256 threads x float4 (the 4 columns),
-// thread t holding k = 1024 i + 4 t + kk.
-static std::vector<float> pack_cols4(const float *w, int K, int N) {
-  std::vector<float> t((size_t)K * N);
-  const int KG = K / 1024;
-  for (int cb = 0; cb < N / 4; cb++)
-    for (int i = 0; i < KG; i++)
-      for (int kk = 0; kk < 4; kk++)
-        for (int tid = 0; tid < 256; tid++)
-          memcpy(&t[((((size_t)cb * KG + i) * 4 + kk) * 256 + tid) * 4], &w[(size_t)(i * 1024 + 4 * tid + kk) * N + cb * 4], 16);
+static std::vector<uint8_t> pack_mfma16o(const float *w, int N, const std::vector<float> &sc) { // the e4m3 encoding
+  std::vector<uint8_t> t((size_t)1024 * N);
+  for (size_t i = 0; i < t.size(); i++) {
+    const Mfma16hAt a = mfma16h_at(i);
+    t[a.fp8] = fp8_e4m3_encode(w[a.k * N + a.n] / sc[a.n]);
+  }
   return t;
 }
 
@@ -1566,27 +1498,293 @@ static void fold_layernorm(const float *w, int K, int N, const float *g, const f
   for (int n = 0; n < N; n++) cf[n] = (float)((double)c[n] + acc[n]);
 }
 
-static int fetch(tts_ctx *ctx, ArState *st, const WeightFile &wf, const std::string &name, int64_t ne0, int64_t ne1,
-                 float **dst, bool tile = false) {
-  auto it = wf.t.find(name);
-  if (it == wf.t.end()) return fail(ctx, TTS_ERR_FORMAT, "tensor '%s' missing from AR model file", name.c_str());
-  const HostTensor &t = it->second;
-  if (t.ne[0] != ne0 || t.ne[1] != ne1 || t.nelem() != ne0 * ne1)
-    return fail(ctx, TTS_ERR_FORMAT, "tensor '%s' has wrong shape in model file: got [%d, %d], expected [%d, %d]",
-                name.c_str(), (int)t.ne[0], (int)t.ne[1], (int)ne0, (int)ne1);
-  if (t.data.empty() && t.file_off >= 0) { // left in the file (device-packing load): file -> pinned staging -> device
-    if (tile) return fail(ctx, TTS_ERR_STATE, "internal: strip-major re-layout of a tensor that was not read ('%s')", name.c_str());
-    void *p = nullptr;
-    TTS_HIP(ctx, hipMalloc(&p, (size_t)t.nelem() * 4));
-    ar_own(st, p);
-    const int r = ar_file_to_device(ctx, wf, t, name, p);
-    if (r) return r;
-    *dst = (float *)p;
+namespace {
+// The four matrices [K][N] of a layer and where their layouts go: strip-major f32 (multi-row GEMV), the hi | lo copy of the multi-row MFMA passes, and the decode slab
+// as f32 / fp16 (option ar_weights = 1) / e4m3 + column scales (ar_weights = 2) — in cols4 order, or for the two matrices a LayerNorm feeds (LAYER_FOLDS) in mfma16 /
+// mfma16h order with the LayerNorm folded in (the f32 one only under dec_f32_mfma; their default slab is LayerFold::dh).
+struct LayerMat {
+  const char *suffix; int K, N;
+  float *ArLayerDev::*strip; __half *ArLayerDev::*split;
+  float *ArLayerDev::*d; __half *ArLayerDev::*q; uint8_t *ArLayerDev::*o; float *ArLayerDev::*os;
+};
+const LayerMat LAYER_MATS[4] = {
+    {".attn.c_attn.weight", D, 3 * D, &ArLayerDev::w_attn, &ArLayerDev::s_attn, &ArLayerDev::d_attn, &ArLayerDev::q_attn, &ArLayerDev::o_attn, &ArLayerDev::os_attn},
+    {".attn.c_proj.weight", D, D, &ArLayerDev::w_proj, &ArLayerDev::s_proj, &ArLayerDev::d_proj, &ArLayerDev::q_proj, &ArLayerDev::o_proj, &ArLayerDev::os_proj},
+    {".mlp.c_fc.weight", D, FF, &ArLayerDev::w_fc, &ArLayerDev::s_fc, &ArLayerDev::d_fc, &ArLayerDev::q_fc, &ArLayerDev::o_fc, &ArLayerDev::os_fc},
+    {".mlp.c_proj.weight", FF, D, &ArLayerDev::w_fc2, &ArLayerDev::s_fc2, &ArLayerDev::d_fc2, &ArLayerDev::q_fc2, &ArLayerDev::o_fc2, &ArLayerDev::os_fc2}};
+// LayerNorm `ln` (gain g, offset b) folded into LAYER_MATS[mat] (bias c): split-precision slab dh, folded bias db
+struct LayerFold {
+  int mat; const char *ln, *bias;
+  float *ArLayerDev::*g, *ArLayerDev::*b, *ArLayerDev::*c;
+  __half *ArLayerDev::*dh; float *ArLayerDev::*db;
+};
+const LayerFold LAYER_FOLDS[2] = {
+    {0, ".ln_1", ".attn.c_attn.bias", &ArLayerDev::ln1_g, &ArLayerDev::ln1_b, &ArLayerDev::b_attn, &ArLayerDev::dh_attn, &ArLayerDev::db_attn},
+    {2, ".ln_2", ".mlp.c_fc.bias", &ArLayerDev::ln2_g, &ArLayerDev::ln2_b, &ArLayerDev::b_fc, &ArLayerDev::dh_fc, &ArLayerDev::db_fc}};
+struct FoldDst { float **d; __half **dh; float **db; __half **q; uint8_t **o; float **os; }; // a layer's (the two tables) or the head's
+
+// Device layouts from the file's tensors. Two ways (equal byte for byte): kernels from uploaded file-order copies (option load_device_pack, default 1, for the default
+// decode arithmetic), or the host packers — kept for the reduced-precision slab options and the f32-MFMA variant (they are A/B options) and for load_threads = 1 (the
+// serial loader, the reference of the equality test). head(), globals() and layer(i) are independent jobs run on several threads (common.h: run_parallel): `owned` and
+// `temps` are touched under `mu`.
+struct ArLoader {
+  tts_ctx *ctx; ArState *st; const WeightFile &wf; const bool dev_pack;
+  const bool pinned;               // load_threads = 1 copies without the pool, as the serial loader always did
+  PinnedPool pin{(size_t)18 << 20, 6};
+  std::mutex mu;
+  std::vector<void *> temps;       // file-order copies and folded matrices: freed once the packing kernels have run
+  // temporaries come out of ONE device allocation (a few hundred hipMalloc / hipFree pairs cost 0.1 s): the file's tensors once more + the gain-folded matrices + the head
+  char *arena = nullptr; size_t arena_cap = 0; std::atomic<size_t> arena_at{0};
+  // ... and so do the layouts that stay (4.4 GB in ~400 pieces: one hipMalloc now, one hipFree in tts_destroy)
+  char *keep = nullptr; size_t keep_cap = 0; std::atomic<size_t> keep_at{0};
+  unsigned *d_max = nullptr;       // device path: max |w| bits, per layer the four matrices, then the two gain-folded ones
+  const std::string hp = "inference_model.transformer.h.";
+  ArLoader(tts_ctx *c, ArState *s, const WeightFile &w, bool dp) : ctx(c), st(s), wf(w), dev_pack(dp), pinned(c->load_threads != 1) {}
+  ~ArLoader() {
+    for (void *q : temps) (void)hipFree(q);
+    if (arena) (void)hipFree(arena);
+  }
+  static int pgrid(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 8192); }
+
+  int reserve() { // device path: the two arenas (without them: one allocation per buffer) and the max |w| slots
+    if (!dev_pack) return TTS_OK;
+    size_t need = (size_t)st->n_layers * ((size_t)D * 3 * D + (size_t)D * FF) * 4 + (size_t)3 * D * VPAD * 4 + ((size_t)8 << 20);
+    for (auto &kv : wf.t) need += (size_t)kv.second.nelem() * 4 + 256;
+    if (hipMalloc((void **)&arena, need) == hipSuccess) arena_cap = need;
+    else (void)hipGetLastError();
+    const size_t per_layer = ((size_t)12 * D * D) * 4 /* strip-major f32 */ + ((size_t)7 * D * D) * 4 /* split-fp16 decode slabs */ + ((size_t)5 * D * D) * 4 /* 4-column slabs */ +
+                             ((size_t)12 * D * D) * 4 /* hi | lo copies for the multi-row passes */ + (size_t)(3 * D + FF) * 4 + 64 * 256;
+    need = (size_t)st->n_layers * per_layer + (size_t)D * VPAD * 8 + (size_t)VPAD * 4 + ((size_t)1 << 20);
+    if (hipMalloc((void **)&keep, need) == hipSuccess) { keep_cap = need; st->owned.push_back(keep); }
+    else (void)hipGetLastError();
+    const size_t nmax = (size_t)st->n_layers * 6 * 4;
+    if (!(d_max = (unsigned *)alloc(nmax, true))) return TTS_ERR_HIP;
+    TTS_HIP(ctx, hipMemsetAsync(d_max, 0, nmax, ctx->stream));
     return TTS_OK;
   }
-  if (tile) return upload(ctx, st, strip_major(t.data.data(), (int)ne1, (int)ne0), dst);
-  return upload(ctx, st, t.data, dst);
-}
+  void *fresh(size_t bytes, bool temp) { // an allocation of its own: the state's, or (temp) the loader's
+    void *q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); fail(ctx, TTS_ERR_HIP, "hipMalloc of %zu bytes failed while loading the AR model", bytes); return nullptr; }
+    std::lock_guard<std::mutex> lk(mu);
+    (temp ? temps : st->owned).push_back(q);
+    return q;
+  }
+  void *alloc(size_t bytes, bool temp) { // out of the arena of its kind while there is one with room
+    char *base = temp ? arena : keep;
+    if (base) {
+      const size_t sz = (bytes + 255) & ~(size_t)255, at = (temp ? arena_at : keep_at).fetch_add(sz);
+      if (at + sz <= (temp ? arena_cap : keep_cap)) return base + at;
+    }
+    return fresh(bytes, temp);
+  }
+  hipError_t h2d(void *dst, const void *src, size_t bytes) { return pinned ? pin.upload(dst, src, bytes, ctx->load_stream) : PinnedPool::copy_now(dst, src, bytes, ctx->load_stream); }
+  template <class T> int put(const std::vector<T> &h, T **dst) {
+    void *p = fresh(h.size() * sizeof(T), false);
+    if (!p) return TTS_ERR_HIP;
+    TTS_HIP(ctx, h2d(p, h.data(), h.size() * sizeof(T)));
+    *dst = (T *)p;
+    return TTS_OK;
+  }
+  const HostTensor *get(const std::string &name, int64_t ne0, int64_t ne1) {
+    auto it = wf.t.find(name);
+    if (it == wf.t.end()) { fail(ctx, TTS_ERR_FORMAT, "tensor '%s' missing from AR model file", name.c_str()); return nullptr; }
+    const HostTensor &t = it->second;
+    if (t.ne[0] != ne0 || t.ne[1] != ne1 || t.nelem() != ne0 * ne1) {
+      fail(ctx, TTS_ERR_FORMAT, "tensor '%s' has wrong shape in model file: got [%d, %d], expected [%d, %d]", name.c_str(), (int)t.ne[0], (int)t.ne[1], (int)ne0, (int)ne1);
+      return nullptr;
+    }
+    return &t;
+  }
+  // the tensor as it lies in the file into a device buffer of its own (temp: one that lives as long as the loader); a payload that read_weight_file left in the file
+  // (device path) goes file -> pinned staging -> device
+  int to_device(const std::string &name, const HostTensor &t, bool temp, float **dst) {
+    const size_t bytes = (size_t)t.nelem() * 4;
+    void *q = temp ? alloc(bytes, true) : fresh(bytes, false);
+    if (!q) return TTS_ERR_HIP;
+    if (t.data.empty() && t.file_off >= 0) {
+      std::pair<void *, size_t> b = pinned ? pin.take(bytes) : std::pair<void *, size_t>{nullptr, 0};
+      std::vector<float> tmp;
+      void *host = b.first;
+      if (!host) { tmp.resize((size_t)t.nelem()); host = tmp.data(); }
+      const bool ok = wf.read_payload(t, host);
+      const hipError_t e = ok ? PinnedPool::copy_now(q, host, bytes, ctx->load_stream) : hipSuccess;
+      pin.give(b);
+      if (!ok) return fail(ctx, TTS_ERR_IO, "autoregressive_model_load: tensor '%s' truncated", name.c_str());
+      TTS_HIP(ctx, e);
+    } else TTS_HIP(ctx, h2d(q, t.data.data(), bytes));
+    *dst = (float *)q;
+    return TTS_OK;
+  }
+  int f32(const std::string &name, int64_t ne0, int64_t ne1, float **dst, bool temp = false) {
+    const HostTensor *t = get(name, ne0, ne1);
+    return t ? to_device(name, *t, temp, dst) : (int)TTS_ERR_FORMAT;
+  }
+  const float *host(const std::string &name) { return wf.t.at(name).data.data(); } // of a tensor that get() has seen
+
+  // The split-precision layouts hold 64 W as fp16 hi | lo (W16_SCALE): a trained GPT-2 never comes near |W| = 937, but a file that does must fail loudly instead of
+  // turning into an fp16 infinity inside the MFMA operands (the diffusion stage's proj_out pair picks its scale per tensor instead). Checked per layer for the four
+  // matrices of the file, then the two gain-folded ones: on the host path as they are built, on the device path from pk_absmax_kernel's results after the jobs.
+  int range_guard(const std::string &name, float m) {
+    if (m * W16_SCALE < 60000.0f) return TTS_OK;
+    return fail(ctx, TTS_ERR_FORMAT, "tensor '%s': max |w| = %g does not fit the split-precision fp16 layout (|w| < %g)", name.c_str(), m, 60000.0 / W16_SCALE);
+  }
+  static float host_absmax(const float *w, size_t n) {
+    float m = 0.f;
+    for (size_t i = 0; i < n; i++) m = std::max(m, std::fabs(w[i]));
+    return m;
+  }
+  std::string guard_name(const std::string &layer, int j) {
+    return j < 4 ? layer + LAYER_MATS[j].suffix : layer + LAYER_MATS[LAYER_FOLDS[j - 4].mat].suffix + " (LayerNorm gain folded in)";
+  }
+  int device_range_guard() {
+    if (!dev_pack) return TTS_OK;
+    TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<float> mx((size_t)st->n_layers * 6); // the bits pk_absmax_kernel ordered as unsigned integers
+    TTS_HIP(ctx, hipMemcpy(mx.data(), d_max, mx.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < st->n_layers; i++)
+      for (int j = 0; j < 6; j++)
+        if (int r = range_guard(guard_name(hp + std::to_string(i), j), mx[(size_t)i * 6 + j])) return r;
+    return TTS_OK;
+  }
+
+  // LayerNorm (g, b) folded into w [D][N] with bias c — the gain into the matrix, b . w + c as the new bias — and every decode slab of the folded matrix.
+  // Host path (w, g, b, c on the host): folded once, then each slab that the options ask for, before the caller folds its next matrix.
+  int fold_host(const float *w, int N, const float *g, const float *b, const float *c, const std::string *guard, const FoldDst &dst) {
+    std::vector<float> wfold, cfold;
+    fold_layernorm(w, D, N, g, b, c, wfold, cfold);
+    int r;
+    if (guard && (r = range_guard(*guard, host_absmax(wfold.data(), wfold.size())))) return r;
+    if (st->f32_mfma && (r = put(pack<float, 1>(wfold.data(), D, N, [](size_t o) { return mfma16_at(o); }, EncF32{}), dst.d))) return r;
+    if ((r = put(pack_mfma16h(wfold.data(), N), dst.dh)) || (r = put(cfold, dst.db))) return r;
+    if (ctx->ar_weights == 1 && (r = put(pack<__half, 1>(wfold.data(), D, N, [](size_t i) { return mfma16h_at(i); }, EncF16{W16_SCALE}), dst.q))) return r;
+    if (ctx->ar_weights == 2) {
+      const std::vector<float> sc = fp8_col_scales(wfold.data(), D, N);
+      if ((r = put(pack_mfma16o(wfold.data(), N, sc), dst.o)) || (r = put(sc, dst.os))) return r;
+    }
+    return TTS_OK;
+  }
+  // Device path (w the file-order copy, g, b, c on the device): the default slab and bias; max |folded w| into *mx when given
+  int fold_dev(const float *w, int N, const float *g, const float *b, const float *c, unsigned *mx, const FoldDst &dst) {
+    const size_t n = (size_t)D * N;
+    float *fold = (float *)alloc(n * 4, true);
+    if (!fold || !(*dst.dh = (__half *)alloc(n * 2 * sizeof(__half), false)) || !(*dst.db = (float *)alloc((size_t)N * 4, false))) return TTS_ERR_HIP;
+    pk_fold_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(w, D, N, g, fold);
+    if (mx) pk_absmax_kernel<<<std::min(pgrid(n), 1024), 256, 0, ctx->stream>>>(fold, n, mx);
+    pk_mfma16h_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(fold, N, *dst.dh);
+    pk_fold_bias_kernel<<<(N + 255) / 256, 256, 0, ctx->stream>>>(w, D, N, b, c, *dst.db);
+    return TTS_OK;
+  }
+
+  int globals() {
+    int r;
+    if ((r = f32("text_embedding.weight", D, 256, &st->text_emb)) || (r = f32("text_pos_embedding.emb.weight", D, 404, &st->text_pos)) ||
+        (r = f32("mel_embedding.weight", D, V, &st->mel_emb)) || (r = f32("mel_pos_embedding.emb.weight", D, 608, &st->mel_pos)) ||
+        (r = f32("inference_model.transformer.ln_f.weight", D, 1, &st->lnf_g)) || (r = f32("inference_model.transformer.ln_f.bias", D, 1, &st->lnf_b)) ||
+        (r = f32("inference_model.lm_head.0.weight", D, 1, &st->lmh_g)) || (r = f32("inference_model.lm_head.0.bias", D, 1, &st->lmh_b))) return r;
+    return TTS_OK;
+  }
+  // One layer = 50 MB of f32 weights re-tiled into the decode slabs, the strip-major copies and (after the jobs) the split-fp16 MFMA layouts; on the host ~0.2 s of one
+  // core + the uploads (tts_load_ar 5.9 s on one thread: see DESIGN.md section 5). The two paths differ in who runs the permutations.
+  int layer(int i) {
+    const std::string p = hp + std::to_string(i);
+    ArLayerDev &l = st->L[i];
+    int r;
+    if ((r = f32(p + ".ln_1.weight", D, 1, &l.ln1_g)) || (r = f32(p + ".ln_1.bias", D, 1, &l.ln1_b)) || (r = f32(p + ".ln_2.weight", D, 1, &l.ln2_g)) ||
+        (r = f32(p + ".ln_2.bias", D, 1, &l.ln2_b)) || (r = f32(p + ".attn.c_attn.bias", 3 * D, 1, &l.b_attn)) || (r = f32(p + ".attn.c_proj.bias", D, 1, &l.b_proj)) ||
+        (r = f32(p + ".mlp.c_fc.bias", FF, 1, &l.b_fc)) || (r = f32(p + ".mlp.c_proj.bias", D, 1, &l.b_fc2))) return r;
+    const HostTensor *t[4];
+    for (int j = 0; j < 4; j++)
+      if (!(t[j] = get(p + LAYER_MATS[j].suffix, LAYER_MATS[j].N, LAYER_MATS[j].K))) return TTS_ERR_FORMAT;
+    const float *w[4]; // the matrices in file order: on the host, or (device path) temporary copies on the device
+    for (int j = 0; j < 4; j++) {
+      const LayerMat &m = LAYER_MATS[j];
+      const size_t n = (size_t)m.K * m.N;
+      if (dev_pack) {
+        float *raw = nullptr;
+        if ((r = to_device(p + m.suffix, *t[j], true, &raw))) return r;
+        if (!(l.*m.strip = (float *)alloc(n * 4, false))) return TTS_ERR_HIP;
+        pk_strip_major_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(raw, m.K, m.N, l.*m.strip);
+        pk_absmax_kernel<<<std::min(pgrid(n), 1024), 256, 0, ctx->stream>>>(raw, n, d_max + (size_t)i * 6 + j);
+        w[j] = raw;
+      } else {
+        w[j] = t[j]->data.data();
+        if ((r = put(strip_major(w[j], m.K, m.N), &(l.*m.strip)))) return r;
+      }
+    }
+    if (!dev_pack)
+      for (int j = 0; j < 4; j++)
+        if ((r = range_guard(guard_name(p, j), host_absmax(w[j], t[j]->data.size())))) return r;
+    for (int q = 0; q < 2; q++) {
+      const LayerFold &f = LAYER_FOLDS[q];
+      const LayerMat &m = LAYER_MATS[f.mat];
+      const FoldDst dst{&(l.*m.d), &(l.*f.dh), &(l.*f.db), &(l.*m.q), &(l.*m.o), &(l.*m.os)};
+      const std::string guard = guard_name(p, 4 + q);
+      if ((r = dev_pack ? fold_dev(w[f.mat], m.N, l.*f.g, l.*f.b, l.*f.c, d_max + (size_t)i * 6 + 4 + q, dst)
+                        : fold_host(w[f.mat], m.N, host(p + f.ln + ".weight"), host(p + f.ln + ".bias"), host(p + f.bias), &guard, dst))) return r;
+    }
+    for (int j = 0; j < 4; j++) { // the two that no LayerNorm feeds: 4-column slabs
+      const LayerMat &m = LAYER_MATS[j];
+      if (j == LAYER_FOLDS[0].mat || j == LAYER_FOLDS[1].mat) continue;
+      const auto at = [&m](size_t o) { return cols4_at(o, m.K); };
+      if (dev_pack) {
+        if (!(l.*m.d = (float *)alloc((size_t)m.K * m.N * 4, false))) return TTS_ERR_HIP;
+        pk_cols4_kernel<<<pgrid((size_t)m.K * m.N), 256, 0, ctx->stream>>>(w[j], m.K, m.N, l.*m.d);
+        continue;
+      }
+      if ((r = put(pack<float, 4>(w[j], m.K, m.N, at, EncF32{}), &(l.*m.d)))) return r;
+      if (ctx->ar_weights == 1 && (r = put(pack<__half, 4>(w[j], m.K, m.N, at, EncF16{1.0f}), &(l.*m.q)))) return r;
+      if (ctx->ar_weights == 2) {
+        const std::vector<float> sc = fp8_col_scales(w[j], m.K, m.N);
+        if ((r = put(pack<uint8_t, 4>(w[j], m.K, m.N, at, EncFp8{sc.data()}), &(l.*m.o))) || (r = put(sc, &(l.*m.os)))) return r;
+      }
+    }
+    if (dev_pack) TTS_HIP(ctx, hipGetLastError());
+    return TTS_OK;
+  }
+  // lm_head.1: nn.Linear [8194][1024] -> [1024][VPAD] so that it streams like the Conv1D weights, lm_head.0's LayerNorm folded into its decode slabs
+  int head() {
+    const std::string w1 = "inference_model.lm_head.1.weight", ln = "inference_model.lm_head.0";
+    auto it = wf.t.find(w1), ib = wf.t.find("inference_model.lm_head.1.bias");
+    if (it == wf.t.end() || ib == wf.t.end()) return fail(ctx, TTS_ERR_FORMAT, "lm_head.1 missing from model file");
+    if (it->second.ne[0] != D || it->second.ne[1] != V || ib->second.nelem() != V)
+      return fail(ctx, TTS_ERR_FORMAT, "tensor 'inference_model.lm_head.1.weight' has wrong shape in model file");
+    const HostTensor *g0 = get(ln + ".weight", D, 1), *b0 = get(ln + ".bias", D, 1);
+    if (!g0 || !b0) return TTS_ERR_FORMAT;
+    std::vector<float> bt(VPAD, 0.f);
+    std::copy(ib->second.data.begin(), ib->second.data.end(), bt.begin());
+    int r;
+    if ((r = put(bt, &st->lm_b))) return r;
+    const FoldDst dst{&st->d_lm, &st->dh_lm, &st->d_lmb, &st->q_lm, &st->o_lm, &st->os_lm};
+    const size_t n = (size_t)D * VPAD;
+    if (dev_pack) {
+      float *raw = nullptr, *g = nullptr, *b = nullptr, *wt = (float *)alloc(n * 4, true);
+      if ((r = to_device(w1, it->second, true, &raw)) || (r = to_device(ln + ".weight", *g0, true, &g)) || (r = to_device(ln + ".bias", *b0, true, &b))) return r;
+      if (!wt || !(st->lm_w = (float *)alloc(n * 4, false))) return TTS_ERR_HIP;
+      pk_transpose_pad_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(raw, V, D, VPAD, wt);
+      pk_strip_major_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(wt, D, VPAD, st->lm_w);
+      if ((r = fold_dev(wt, VPAD, g, b, st->lm_b, nullptr, dst))) return r;
+      TTS_HIP(ctx, hipGetLastError());
+      return TTS_OK;
+    }
+    std::vector<float> wt(n, 0.f);
+    const float *w = it->second.data.data();
+    for (int v = 0; v < V; v++)
+      for (int k = 0; k < D; k++) wt[(size_t)k * VPAD + v] = w[(size_t)v * D + k];
+    if ((r = put(strip_major(wt.data(), D, VPAD), &st->lm_w))) return r;
+    return fold_host(wt.data(), VPAD, g0->data.data(), b0->data.data(), bt.data(), nullptr, dst);
+  }
+  int split_copies() { // hi | lo copies for the multi-row MFMA path, from the strip-major ones
+    for (ArLayerDev &l : st->L)
+      for (const LayerMat &m : LAYER_MATS) {
+        if (!(l.*m.split = (__half *)alloc((size_t)m.N * 2 * m.K * sizeof(__half), false))) return TTS_ERR_HIP;
+        split_weight_kernel<<<dim3(m.N / 32, m.K / 32), 256, 0, ctx->stream>>>(l.*m.strip, m.K, m.N, l.*m.split);
+      }
+    return TTS_OK;
+  }
+};
+} // namespace
+
+void ar_free(ArState *s) { delete s; }
 
 int ar_load(tts_ctx *ctx, const char *path) {
   static const bool timing = getenv("TTS_TIMING") != nullptr; // host-side breakdown on stderr
@@ -1599,15 +1797,10 @@ int ar_load(tts_ctx *ctx, const char *path) {
   int rc = read_weight_file(path, wf, err, dev_pack ? (size_t)256 << 10 : (size_t)-1);
   const double t_read = since(t0);
   if (rc != TTS_OK) return fail(ctx, rc, "autoregressive_model_load: %s", err.c_str());
-  static std::mutex load_mu; // one tts_load_ar at a time per process (ar_pin is shared)
-  std::lock_guard<std::mutex> load_lk(load_mu);
   std::unique_ptr<ArState> st(new ArState());
-  PinnedPool pin{(size_t)18 << 20, 6};
-  struct PinScope { PinnedPool *&slot; PinScope(PinnedPool *&s, PinnedPool *p) : slot(s) { slot = p; } ~PinScope() { slot = nullptr; } } pin_scope(ar_pin, ctx->load_threads == 1 ? nullptr : &pin);
-  ar_load_stream = ctx->load_stream;
+  ArLoader ld(ctx, st.get(), wf, dev_pack);
   st->f32_mfma = ctx->dec_f32_mfma != 0;
-  const std::string hp = "inference_model.transformer.h.";
-  while (wf.has(hp + std::to_string(st->n_layers) + ".ln_1.weight")) st->n_layers++;
+  while (wf.has(ld.hp + std::to_string(st->n_layers) + ".ln_1.weight")) st->n_layers++;
   if (st->n_layers == 0) return fail(ctx, TTS_ERR_FORMAT, "no transformer layers in '%s'", path);
   // every tensor in the file must be known (main.cpp:834-838)
   for (auto &kv : wf.t) {
@@ -1616,273 +1809,13 @@ int ar_load(tts_ctx *ctx, const char *path) {
               n == "mel_pos_embedding.emb.weight" || n.rfind("inference_model.", 0) == 0;
     if (!ok) return fail(ctx, TTS_ERR_FORMAT, "unknown tensor '%s' in model file", n.c_str());
   }
-#define FETCH(name, a, b, dst) do { int _r = fetch(ctx, st.get(), wf, name, a, b, dst); if (_r) return _r; } while (0)
-#define FETCHT(name, a, b, dst) do { int _r = fetch(ctx, st.get(), wf, name, a, b, dst, true); if (_r) return _r; } while (0)
-  // Device-side re-layouts (option load_device_pack, default 1) for the default decode arithmetic; the reduced-precision slab options and the f32-MFMA variant keep the
-  // host packers (they are A/B options), and so does load_threads = 1 (the serial loader of rounds 1-5, kept as the reference for the equality test).
-  std::mutex tmp_mu;
-  std::vector<void *> temps; // file-order copies and folded matrices: freed once the packing kernels have run
-  // temporaries come out of ONE device allocation (a few hundred hipMalloc / hipFree pairs cost 0.1 s): the file's tensors once more + the gain-folded matrices + the head
-  char *arena = nullptr;
-  size_t arena_cap = 0;
-  std::atomic<size_t> arena_at{0};
-  if (dev_pack) {
-    size_t need = (size_t)st->n_layers * ((size_t)D * 3 * D + (size_t)D * FF) * 4 + (size_t)3 * D * VPAD * 4 + ((size_t)8 << 20);
-    for (auto &kv : wf.t) need += (size_t)kv.second.nelem() * 4 + 256;
-    if (hipMalloc((void **)&arena, need) == hipSuccess) arena_cap = need;
-    else (void)hipGetLastError(); // fall back to one allocation per temporary
-  }
-  struct ArenaFree { char *&p; ~ArenaFree() { if (p) (void)hipFree(p); } } arena_free{arena};
-  // ... and so do the layouts that stay (4.4 GB in ~400 pieces: one hipMalloc now, one hipFree in tts_destroy)
-  char *keep = nullptr;
-  size_t keep_cap = 0;
-  std::atomic<size_t> keep_at{0};
-  if (dev_pack) {
-    const size_t per_layer = ((size_t)12 * D * D) * 4 /* strip-major f32 */ + ((size_t)7 * D * D) * 4 /* split-fp16 decode slabs */ + ((size_t)5 * D * D) * 4 /* 4-column slabs */ +
-                             ((size_t)12 * D * D) * 4 /* hi | lo copies for the multi-row passes */ + (size_t)(3 * D + FF) * 4 + 64 * 256;
-    const size_t need = (size_t)st->n_layers * per_layer + (size_t)D * VPAD * 8 + (size_t)VPAD * 4 + ((size_t)1 << 20);
-    if (hipMalloc((void **)&keep, need) == hipSuccess) { keep_cap = need; ar_own(st.get(), keep); }
-    else (void)hipGetLastError();
-  }
-  auto dalloc = [&](size_t bytes, bool temp) -> void * {
-    if (temp && arena) {
-      const size_t sz = (bytes + 255) & ~(size_t)255, at = arena_at.fetch_add(sz);
-      if (at + sz <= arena_cap) return arena + at;
-    }
-    if (!temp && keep) {
-      const size_t sz = (bytes + 255) & ~(size_t)255, at = keep_at.fetch_add(sz);
-      if (at + sz <= keep_cap) return keep + at;
-    }
-    void *q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); fail(ctx, TTS_ERR_HIP, "hipMalloc of %zu bytes failed while loading the AR model", bytes); return nullptr; }
-    if (temp) { std::lock_guard<std::mutex> lk(tmp_mu); temps.push_back(q); }
-    else ar_own(st.get(), q);
-    return q;
-  };
-  struct TempFree { std::vector<void *> &v; ~TempFree() { for (void *q : v) (void)hipFree(q); } } temp_free{temps};
-  auto pgrid = [](size_t n) { return (int)std::min<size_t>((n + 255) / 256, 8192); };
-  // the tensor as it lies in the file, shape-checked like fetch(), into a temporary device buffer
-  auto raw_up = [&](const std::string &name, int64_t ne0, int64_t ne1, float **dst) -> int {
-    auto it = wf.t.find(name);
-    if (it == wf.t.end()) return fail(ctx, TTS_ERR_FORMAT, "tensor '%s' missing from AR model file", name.c_str());
-    const HostTensor &t = it->second;
-    if (t.ne[0] != ne0 || t.ne[1] != ne1 || t.nelem() != ne0 * ne1)
-      return fail(ctx, TTS_ERR_FORMAT, "tensor '%s' has wrong shape in model file: got [%d, %d], expected [%d, %d]", name.c_str(), (int)t.ne[0], (int)t.ne[1], (int)ne0, (int)ne1);
-    void *q = dalloc((size_t)t.nelem() * 4, true);
-    if (!q) return TTS_ERR_HIP;
-    if (t.data.empty() && t.file_off >= 0) { const int r = ar_file_to_device(ctx, wf, t, name, q); if (r) return r; }
-    else TTS_HIP(ctx, ar_h2d(q, t.data.data(), (size_t)t.nelem() * 4));
-    *dst = (float *)q;
-    return TTS_OK;
-  };
-  unsigned *d_max = nullptr; // max |w| bits: per layer the four matrices, then the two gain-folded ones
-  if (dev_pack) {
-    d_max = (unsigned *)dalloc((size_t)st->n_layers * 6 * 4, true);
-    if (!d_max) return TTS_ERR_HIP;
-    TTS_HIP(ctx, hipMemsetAsync(d_max, 0, (size_t)st->n_layers * 6 * 4, ctx->stream));
-  }
-  auto build_globals = [&]() -> int {
-    FETCH("text_embedding.weight", D, 256, &st->text_emb);
-    FETCH("text_pos_embedding.emb.weight", D, 404, &st->text_pos);
-    FETCH("mel_embedding.weight", D, V, &st->mel_emb);
-    FETCH("mel_pos_embedding.emb.weight", D, 608, &st->mel_pos);
-    FETCH("inference_model.transformer.ln_f.weight", D, 1, &st->lnf_g);
-    FETCH("inference_model.transformer.ln_f.bias", D, 1, &st->lnf_b);
-    FETCH("inference_model.lm_head.0.weight", D, 1, &st->lmh_g);
-    FETCH("inference_model.lm_head.0.bias", D, 1, &st->lmh_b);
-    return TTS_OK;
-  };
   st->L.resize(st->n_layers);
-  // One layer = 50 MB of f32 weights re-tiled into the decode slabs, the strip-major copies and the split-fp16 MFMA layouts on the host (~0.2 s of one core) + their
-  // uploads: layers are independent, built on several threads (round 6: tts_load_ar 5.9 s -> see DESIGN.md section 5; option load_threads = 1 restores the serial loader).
-  auto build_layer = [&](int i) -> int {
-    std::string p = hp + std::to_string(i);
-    ArLayerDev &l = st->L[i];
-    FETCH(p + ".ln_1.weight", D, 1, &l.ln1_g); FETCH(p + ".ln_1.bias", D, 1, &l.ln1_b);
-    FETCH(p + ".ln_2.weight", D, 1, &l.ln2_g); FETCH(p + ".ln_2.bias", D, 1, &l.ln2_b);
-    FETCH(p + ".attn.c_attn.bias", 3 * D, 1, &l.b_attn); FETCH(p + ".attn.c_proj.bias", D, 1, &l.b_proj);
-    FETCH(p + ".mlp.c_fc.bias", FF, 1, &l.b_fc); FETCH(p + ".mlp.c_proj.bias", D, 1, &l.b_fc2);
-    int r;
-    if (dev_pack) {
-      struct M { const char *name; int K, N; float **strip; float *raw; } m[4] = {
-          {".attn.c_attn.weight", D, 3 * D, &l.w_attn, nullptr}, {".attn.c_proj.weight", D, D, &l.w_proj, nullptr},
-          {".mlp.c_fc.weight", D, FF, &l.w_fc, nullptr}, {".mlp.c_proj.weight", FF, D, &l.w_fc2, nullptr}};
-      for (int j = 0; j < 4; j++) {
-        if ((r = raw_up(p + m[j].name, m[j].N, m[j].K, &m[j].raw))) return r;
-        const size_t n = (size_t)m[j].K * m[j].N;
-        if (!(*m[j].strip = (float *)dalloc(n * 4, false))) return TTS_ERR_HIP;
-        pk_strip_major_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(m[j].raw, m[j].K, m[j].N, *m[j].strip);
-        pk_absmax_kernel<<<std::min(pgrid(n), 1024), 256, 0, ctx->stream>>>(m[j].raw, n, d_max + (size_t)i * 6 + j);
-      }
-      struct F { int j; const float *g, *b, *c; __half **dh; float **db; } f[2] = {{0, l.ln1_g, l.ln1_b, l.b_attn, &l.dh_attn, &l.db_attn},
-                                                                                   {2, l.ln2_g, l.ln2_b, l.b_fc, &l.dh_fc, &l.db_fc}};
-      for (int q = 0; q < 2; q++) { // LayerNorm gain folded into the matrix the normalised rows feed, then the split-fp16 decode slabs; beta . W + c as the new bias
-        const int N = m[f[q].j].N;
-        const size_t n = (size_t)D * N;
-        float *fold = (float *)dalloc(n * 4, true);
-        if (!fold || !(*f[q].dh = (__half *)dalloc(n * 2 * sizeof(__half), false)) || !(*f[q].db = (float *)dalloc((size_t)N * 4, false))) return TTS_ERR_HIP;
-        pk_fold_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(m[f[q].j].raw, D, N, f[q].g, fold);
-        pk_absmax_kernel<<<std::min(pgrid(n), 1024), 256, 0, ctx->stream>>>(fold, n, d_max + (size_t)i * 6 + 4 + q);
-        pk_mfma16h_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(fold, N, *f[q].dh);
-        pk_fold_bias_kernel<<<(N + 255) / 256, 256, 0, ctx->stream>>>(m[f[q].j].raw, D, N, f[q].b, f[q].c, *f[q].db);
-      }
-      if (!(l.d_proj = (float *)dalloc((size_t)D * D * 4, false)) || !(l.d_fc2 = (float *)dalloc((size_t)FF * D * 4, false))) return TTS_ERR_HIP;
-      pk_cols4_kernel<<<pgrid((size_t)D * D), 256, 0, ctx->stream>>>(m[1].raw, D, D, l.d_proj);
-      pk_cols4_kernel<<<pgrid((size_t)FF * D), 256, 0, ctx->stream>>>(m[3].raw, FF, D, l.d_fc2);
-      TTS_HIP(ctx, hipGetLastError());
-      return TTS_OK;
-    }
-    FETCHT(p + ".attn.c_attn.weight", 3 * D, D, &l.w_attn);
-    FETCHT(p + ".attn.c_proj.weight", D, D, &l.w_proj);
-    FETCHT(p + ".mlp.c_fc.weight", FF, D, &l.w_fc);
-    FETCHT(p + ".mlp.c_proj.weight", D, FF, &l.w_fc2);
-    // The split-precision layouts hold 64 W as fp16 hi | lo (W16_SCALE): a trained GPT-2 never comes near |W| = 937, but a file that does must fail loudly instead of
-    // turning into an fp16 infinity inside the MFMA operands (round 6; the diffusion stage's proj_out pair picks its scale per tensor instead)
-    auto split_range = [&](const std::string &name, const float *w, size_t n) -> int {
-      float m = 0.f;
-      for (size_t i = 0; i < n; i++) m = std::max(m, std::fabs(w[i]));
-      if (!(m * W16_SCALE < 60000.0f)) return fail(ctx, TTS_ERR_FORMAT, "tensor '%s': max |w| = %g does not fit the split-precision fp16 layout (|w| < %g)", name.c_str(), m, 60000.0 / W16_SCALE);
-      return TTS_OK;
-    };
-    for (const char *wn : {".attn.c_attn.weight", ".attn.c_proj.weight", ".mlp.c_fc.weight", ".mlp.c_proj.weight"})
-      if ((r = split_range(p + wn, wf.t.at(p + wn).data.data(), wf.t.at(p + wn).data.size()))) return r;
-    std::vector<float> wfold, cfold;
-    fold_layernorm(wf.t.at(p + ".attn.c_attn.weight").data.data(), D, 3 * D, wf.t.at(p + ".ln_1.weight").data.data(),
-                   wf.t.at(p + ".ln_1.bias").data.data(), wf.t.at(p + ".attn.c_attn.bias").data.data(), wfold, cfold);
-    if ((r = split_range(p + ".attn.c_attn.weight (LayerNorm gain folded in)", wfold.data(), wfold.size()))) return r;
-    if (st->f32_mfma && (r = upload(ctx, st.get(), pack_mfma16(wfold.data(), D, 3 * D), &l.d_attn))) return r;
-    if ((r = upload_h(ctx, st.get(), pack_mfma16h(wfold.data(), D, 3 * D), &l.dh_attn))) return r;
-    if ((r = upload(ctx, st.get(), cfold, &l.db_attn))) return r;
-    fold_layernorm(wf.t.at(p + ".mlp.c_fc.weight").data.data(), D, FF, wf.t.at(p + ".ln_2.weight").data.data(),
-                   wf.t.at(p + ".ln_2.bias").data.data(), wf.t.at(p + ".mlp.c_fc.bias").data.data(), wfold, cfold);
-    if ((r = split_range(p + ".mlp.c_fc.weight (LayerNorm gain folded in)", wfold.data(), wfold.size()))) return r;
-    if (st->f32_mfma && (r = upload(ctx, st.get(), pack_mfma16(wfold.data(), D, FF), &l.d_fc))) return r;
-    if ((r = upload_h(ctx, st.get(), pack_mfma16h(wfold.data(), D, FF), &l.dh_fc))) return r;
-    if ((r = upload(ctx, st.get(), cfold, &l.db_fc))) return r;
-    if ((r = upload(ctx, st.get(), pack_cols4(wf.t.at(p + ".attn.c_proj.weight").data.data(), D, D), &l.d_proj))) return r;
-    if ((r = upload(ctx, st.get(), pack_cols4(wf.t.at(p + ".mlp.c_proj.weight").data.data(), FF, D), &l.d_fc2))) return r;
-    if (ctx->ar_weights == 2) { // fp8-weight decode slabs
-      auto up8 = [&](const std::vector<uint8_t> &src, uint8_t **dst) {
-        void *q = nullptr;
-        TTS_HIP(ctx, hipMalloc(&q, src.size()));
-        ar_own(st.get(), q);
-        TTS_HIP(ctx, ar_h2d(q, src.data(), src.size()));
-        *dst = (uint8_t *)q;
-        return (int)TTS_OK;
-      };
-      std::vector<float> sc;
-      fold_layernorm(wf.t.at(p + ".attn.c_attn.weight").data.data(), D, 3 * D, wf.t.at(p + ".ln_1.weight").data.data(),
-                     wf.t.at(p + ".ln_1.bias").data.data(), wf.t.at(p + ".attn.c_attn.bias").data.data(), wfold, cfold);
-      sc = fp8_col_scales(wfold.data(), D, 3 * D);
-      if ((r = up8(pack_mfma16o(wfold.data(), D, 3 * D, sc), &l.o_attn)) || (r = upload(ctx, st.get(), sc, &l.os_attn))) return r;
-      fold_layernorm(wf.t.at(p + ".mlp.c_fc.weight").data.data(), D, FF, wf.t.at(p + ".ln_2.weight").data.data(),
-                     wf.t.at(p + ".ln_2.bias").data.data(), wf.t.at(p + ".mlp.c_fc.bias").data.data(), wfold, cfold);
-      sc = fp8_col_scales(wfold.data(), D, FF);
-      if ((r = up8(pack_mfma16o(wfold.data(), D, FF, sc), &l.o_fc)) || (r = upload(ctx, st.get(), sc, &l.os_fc))) return r;
-      const float *wp = wf.t.at(p + ".attn.c_proj.weight").data.data(), *w2 = wf.t.at(p + ".mlp.c_proj.weight").data.data();
-      sc = fp8_col_scales(wp, D, D);
-      if ((r = up8(pack_cols4o(wp, D, D, sc), &l.o_proj)) || (r = upload(ctx, st.get(), sc, &l.os_proj))) return r;
-      sc = fp8_col_scales(w2, FF, D);
-      if ((r = up8(pack_cols4o(w2, FF, D, sc), &l.o_fc2)) || (r = upload(ctx, st.get(), sc, &l.os_fc2))) return r;
-    }
-    if (ctx->ar_weights == 1) { // fp16-weight decode slabs (same packing orders)
-      fold_layernorm(wf.t.at(p + ".attn.c_attn.weight").data.data(), D, 3 * D, wf.t.at(p + ".ln_1.weight").data.data(),
-                     wf.t.at(p + ".ln_1.bias").data.data(), wf.t.at(p + ".attn.c_attn.bias").data.data(), wfold, cfold);
-      if ((r = upload_h(ctx, st.get(), pack_mfma16q(wfold.data(), D, 3 * D), &l.q_attn))) return r;
-      fold_layernorm(wf.t.at(p + ".mlp.c_fc.weight").data.data(), D, FF, wf.t.at(p + ".ln_2.weight").data.data(),
-                     wf.t.at(p + ".ln_2.bias").data.data(), wf.t.at(p + ".mlp.c_fc.bias").data.data(), wfold, cfold);
-      if ((r = upload_h(ctx, st.get(), pack_mfma16q(wfold.data(), D, FF), &l.q_fc))) return r;
-      if ((r = upload_h(ctx, st.get(), to_half(pack_cols4(wf.t.at(p + ".attn.c_proj.weight").data.data(), D, D)), &l.q_proj))) return r;
-      if ((r = upload_h(ctx, st.get(), to_half(pack_cols4(wf.t.at(p + ".mlp.c_proj.weight").data.data(), FF, D)), &l.q_fc2))) return r;
-    }
-    return TTS_OK;
-  };
-  // lm_head.1: nn.Linear [8194][1024] -> [1024][VPAD] so that it streams like the Conv1D weights (one more job beside the layers)
-  auto build_head = [&]() -> int {
-    auto it = wf.t.find("inference_model.lm_head.1.weight");
-    auto ib = wf.t.find("inference_model.lm_head.1.bias");
-    if (it == wf.t.end() || ib == wf.t.end()) return fail(ctx, TTS_ERR_FORMAT, "lm_head.1 missing from model file");
-    if (it->second.ne[0] != D || it->second.ne[1] != V || ib->second.nelem() != V)
-      return fail(ctx, TTS_ERR_FORMAT, "tensor 'inference_model.lm_head.1.weight' has wrong shape in model file");
-    if (dev_pack) {
-      std::vector<float> bt(VPAD, 0.f);
-      std::copy(ib->second.data.begin(), ib->second.data.end(), bt.begin());
-      int r = upload(ctx, st.get(), bt, &st->lm_b); if (r) return r;
-      float *rw = nullptr, *g0 = nullptr, *b0 = nullptr;
-      if ((r = raw_up("inference_model.lm_head.1.weight", D, V, &rw)) || (r = raw_up("inference_model.lm_head.0.weight", D, 1, &g0)) ||
-          (r = raw_up("inference_model.lm_head.0.bias", D, 1, &b0))) return r;
-      const size_t n = (size_t)D * VPAD;
-      float *wt = (float *)dalloc(n * 4, true), *fold = (float *)dalloc(n * 4, true);
-      if (!wt || !fold || !(st->lm_w = (float *)dalloc(n * 4, false)) || !(st->dh_lm = (__half *)dalloc(n * 2 * sizeof(__half), false)) ||
-          !(st->d_lmb = (float *)dalloc((size_t)VPAD * 4, false))) return TTS_ERR_HIP;
-      pk_transpose_pad_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(rw, V, D, VPAD, wt);
-      pk_strip_major_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(wt, D, VPAD, st->lm_w);
-      pk_fold_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(wt, D, VPAD, g0, fold);
-      pk_mfma16h_kernel<<<pgrid(n), 256, 0, ctx->stream>>>(fold, VPAD, st->dh_lm);
-      pk_fold_bias_kernel<<<(VPAD + 255) / 256, 256, 0, ctx->stream>>>(wt, D, VPAD, b0, st->lm_b, st->d_lmb);
-      TTS_HIP(ctx, hipGetLastError());
-      return TTS_OK;
-    }
-    std::vector<float> wt((size_t)D * VPAD, 0.f), bt(VPAD, 0.f);
-    const float *w = it->second.data.data();
-    for (int n = 0; n < V; n++)
-      for (int k = 0; k < D; k++) wt[(size_t)k * VPAD + n] = w[(size_t)n * D + k];
-    std::copy(ib->second.data.begin(), ib->second.data.end(), bt.begin());
-    int r = upload(ctx, st.get(), strip_major(wt.data(), D, VPAD), &st->lm_w); if (r) return r;
-    { // decode head: lm_head.0 LayerNorm folded into lm_head.1
-      std::vector<float> wfold, cfold;
-      fold_layernorm(wt.data(), D, VPAD, wf.t.at("inference_model.lm_head.0.weight").data.data(),
-                     wf.t.at("inference_model.lm_head.0.bias").data.data(), bt.data(), wfold, cfold);
-      if (st->f32_mfma) { r = upload(ctx, st.get(), pack_mfma16(wfold.data(), D, VPAD), &st->d_lm); if (r) return r; }
-      r = upload_h(ctx, st.get(), pack_mfma16h(wfold.data(), D, VPAD), &st->dh_lm); if (r) return r;
-      if (ctx->ar_weights == 1) { r = upload_h(ctx, st.get(), pack_mfma16q(wfold.data(), D, VPAD), &st->q_lm); if (r) return r; }
-      if (ctx->ar_weights == 2) {
-        const std::vector<float> sc = fp8_col_scales(wfold.data(), D, VPAD);
-        const std::vector<uint8_t> o = pack_mfma16o(wfold.data(), D, VPAD, sc);
-        void *q = nullptr;
-        TTS_HIP(ctx, hipMalloc(&q, o.size()));
-        st->owned.push_back(q);
-        TTS_HIP(ctx, ar_h2d(q, o.data(), o.size()));
-        st->o_lm = (uint8_t *)q;
-        r = upload(ctx, st.get(), sc, &st->os_lm); if (r) return r;
-      }
-      r = upload(ctx, st.get(), cfold, &st->d_lmb); if (r) return r;
-    }
-    r = upload(ctx, st.get(), bt, &st->lm_b); if (r) return r;
-    return TTS_OK;
-  };
+  if ((rc = ld.reserve())) return rc;
   const auto t1 = std::chrono::steady_clock::now();
-  const int nl = st->n_layers;
-  if (int r = run_parallel(ctx, nl + 2, [&](int i) { return i == 0 ? build_head() : i == 1 ? build_globals() : build_layer(i - 2); })) return r; // the head (0.2 s) first
-  if (dev_pack) { // the range guard of the split-precision layouts, from the device's max |w| values, in the host path's order and words
-    TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<unsigned> mx((size_t)nl * 6);
-    TTS_HIP(ctx, hipMemcpy(mx.data(), d_max, mx.size() * 4, hipMemcpyDeviceToHost));
-    static const char *wn[6] = {".attn.c_attn.weight", ".attn.c_proj.weight", ".mlp.c_fc.weight", ".mlp.c_proj.weight", ".attn.c_attn.weight (LayerNorm gain folded in)",
-                                ".mlp.c_fc.weight (LayerNorm gain folded in)"};
-    static const int order[6] = {0, 1, 2, 3, 4, 5};
-    for (int i = 0; i < nl; i++)
-      for (int j : order) {
-        float m;
-        memcpy(&m, &mx[(size_t)i * 6 + j], 4);
-        if (!(m * W16_SCALE < 60000.0f))
-          return fail(ctx, TTS_ERR_FORMAT, "tensor '%s': max |w| = %g does not fit the split-precision fp16 layout (|w| < %g)", (hp + std::to_string(i) + wn[j]).c_str(), m, 60000.0 / W16_SCALE);
-      }
-  }
+  if ((rc = run_parallel(ctx, st->n_layers + 2, [&](int i) { return i == 0 ? ld.head() : i == 1 ? ld.globals() : ld.layer(i - 2); }))) return rc; // the head (0.2 s) first
+  if ((rc = ld.device_range_guard())) return rc;
   const double t_layers = since(t1);
-#undef FETCH
-#undef FETCHT
-  for (int i = 0; i < st->n_layers; i++) { // split-precision copies for the multi-row MFMA path
-    ArLayerDev &l = st->L[i];
-    struct { const float *w; int K, N; __half **dst; } jobs[4] = {
-        {l.w_attn, D, 3 * D, &l.s_attn}, {l.w_proj, D, D, &l.s_proj}, {l.w_fc, D, FF, &l.s_fc}, {l.w_fc2, FF, D, &l.s_fc2}};
-    for (auto &j : jobs) {
-      void *p = dalloc((size_t)j.N * 2 * j.K * sizeof(__half), false);
-      if (!p) return TTS_ERR_HIP;
-      split_weight_kernel<<<dim3(j.N / 32, j.K / 32), 256, 0, ctx->stream>>>(j.w, j.K, j.N, (__half *)p);
-      *j.dst = (__half *)p;
-    }
-  }
+  if ((rc = ld.split_copies())) return rc;
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   st->loaded_wmode = ctx->ar_weights;
   if (ctx->ar) ar_free(ctx->ar);
