@@ -337,8 +337,8 @@ int tts_load_hifigan(tts_ctx *ctx, const char *path);
 /* Samples per candidate: 256 * tts_diffusion_frames(latent_rows) (the latents are interpolated to the diffusion stage's frame rate first). */
 int tts_hifigan_samples(int latent_rows);
 /* Frames on either side of a sample that can influence it (the generator is purely convolutional: interpolation 9, conv_pre 3, ResBlocks and
- * transposed convolutions 9.3, rounded up): changing latent row L - 1 leaves the samples before 256 * (T - TTS_HFG_HALO_FRAMES) bit-identical, and a
- * chunked call — not provided — would need this much context. */
+ * transposed convolutions 9.3, rounded up): changing latent row L - 1 leaves the samples before 256 * (T - TTS_HFG_HALO_FRAMES) bit-identical, and the
+ * chunked call, tts_hifigan_chunk below, evaluates this much context on either side of the frames it returns. */
 #define TTS_HFG_HALO_FRAMES 24
 /* latents: the trimmed rows of tts_autoregressive*, candidates back to back, rows[c] rows of 1024 each; voices [n_voices][1024]; candidate c
  * speaks with voices[voice_of_candidate[c]] (voice_of_candidate == NULL: every candidate uses voice 0). audio_out: tts_hifigan_samples(rows[c])
@@ -348,6 +348,39 @@ int tts_hifigan_samples(int latent_rows);
  * TTS_ERR_LIMIT for rows > 500 (or more than 4096 candidates). Profiler family: "hfg_conv" (work = FLOPs). */
 int tts_hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices,
                        const int32_t *voice_of_candidate, float *audio_out);
+/* Additions within version 8 (no prototype changed): the streaming forms of the decoder (upstream's api_fast.py is mainly used as tts_stream: audio leaves while
+ * the GPT is still sampling).
+ * tts_hifigan_chunk: a window of the generator for a ragged batch. latents, rows, voices and voice_of_candidate are exactly tts_hifigan_decode's (the WHOLE
+ * latents of every candidate); candidate c gets the samples [256 frame0[c], 256 (frame0[c] + n_frames[c])) of its utterance, audio_out holds 256 n_frames[c]
+ * floats per candidate back to back. One launch sequence, one upload, one download; only the frames [frame0 - TTS_HFG_HALO_FRAMES, frame0 + n_frames +
+ * TTS_HFG_HALO_FRAMES), clipped to the utterance, are evaluated.
+ *   Contract: for ANY partition of [0, T_c) into chunks the concatenation is bit for bit tts_hifigan_decode's output; a chunk's bits depend neither on the
+ *   partition nor on the rest of the batch (every output element is summed in the whole call's order; option "hfg_small_m" — the row count up to which a
+ *   convolution of a chunked call runs on a 32-row tile whose waves tile the channels, 0 = never, the default: the variant is opt-in until it is measured — changes no bit either).
+ *   Prefix property: when `latents` holds only the first L' rows of an utterance that will have L >= L' rows, every sample of the frames below
+ *   tts_diffusion_frames(L') - TTS_HFG_HALO_FRAMES is already the final one (tts_hifigan_stream depends on it).
+ *   Checks, before any device work, a refused call changes nothing: tts_hifigan_decode's own, and TTS_ERR_ARG for a null frame0 or n_frames, frame0 < 0,
+ *   n_frames < 1 or frame0 + n_frames > tts_diffusion_frames(rows[c]). */
+int tts_hifigan_chunk(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices,
+                      const int32_t *voice_of_candidate, const int32_t *frame0, const int32_t *n_frames, float *audio_out);
+/* tts_hifigan_stream: tts_autoregressive for ONE candidate (the reference's own workload and upstream tts_stream's; re-ranking several candidates cannot
+ * stream) whose audio leaves through `cb` while the loop is still sampling. The sampling loop is tts_autoregressive's — sampler controls, stop rule, flags,
+ * stop schedule, RNG consumption: codes_out [502], rows_out [1], steps_out and the RNG state afterwards are those of tts_autoregressive(n_candidates = 1).
+ * After every stride_codes new codes the latent pass runs over the rows whose inputs are final (after k sampled codes: rows 0 .. k), tts_hifigan_chunk decodes
+ * the frames that became final, [emitted, tts_diffusion_frames(k + 1) - TTS_HFG_HALO_FRAMES), and cb(user, samples, n_samples, 0) receives them (the buffer
+ * is valid during the callback only). After the loop the remaining rows come from tts_autoregressive's own latent pass and the remaining frames arrive with
+ * is_last = 1. The concatenated samples are bit for bit tts_hifigan_decode of the latents the call returns (latents_out: rows_out[0] rows, capacity 500 * 1024
+ * floats, may be NULL): a row is kept as it was when audio was first decoded from it. Every prefix pass runs on the multi-row kernels (at least 32 rows), so
+ * for an utterance that keeps 31 rows or more the latents — and with them the audio — are tts_autoregressive's bit for bit; a shorter utterance ends on the
+ * exact-f32 GEMV pass, which sums in another order, and its latents agree to about 1e-6 relative.
+ * A nonzero return of cb ends the call with TTS_ERR_STATE ("cancelled by the callback"); the next tts_autoregressive* call starts afresh. TTS_ERR_ARG for
+ * stride_codes < 1 or a null cb; TTS_ERR_STATE before tts_load_ar or tts_load_hifigan; every other check as in tts_autoregressive. The buffers of the longest
+ * latent pass are reserved before the loop, so the captured decode step is never re-captured inside it: tts_hifigan_stream_recaptures returns the number of
+ * decode-step graphs captured inside the last call's loop after its first step (0). */
+typedef int (*tts_audio_cb)(void *user, const float *samples, int n_samples, int is_last);
+int tts_hifigan_stream(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice1024, int max_steps, unsigned flags, int stride_codes,
+                       tts_audio_cb cb, void *user, int32_t *codes_out /*[502]*/, int32_t *rows_out, float *latents_out /*may be NULL*/, int32_t *steps_out);
+int tts_hifigan_stream_recaptures(const tts_ctx *ctx);
 /* One diffusion_graph evaluation (main.cpp:5749-5841 cond / 5866-5961 uncond): inputs
  * input_latent_tensor [L][1024], noise_tensor = x_t [100][T], timestep (raw 0..3999 value whose
  * sinusoidal embedding the reference uploads as time_embedding_{i}); conditioning_free as the
@@ -435,6 +468,9 @@ int tts_host_sample_row_ex(const float *row8194, const int32_t *penalty_ids, int
 int tts_host_sample_prefiltered_ex(const float *row8194, const int32_t *penalty_ids, int n_ids, float uniform, float temperature, int top_k, float top_p,
                                    float penalty, int keep, int already_penalised);
 int tts_host_pad_codes(const int32_t *codes, int n, int32_t *out502);
+/* tts_hifigan_stream's row bookkeeping (addition within version 8): the latent rows that are final after the first k sampled codes (none the stop token) —
+ * k + 1, cut where tts_host_trimmed_rows will cut and at 500. They are a prefix of the rows tts_host_pad_codes + tts_host_trimmed_rows give at the end. */
+int tts_host_stream_final_rows(const int32_t *codes, int k);
 int tts_host_trimmed_rows(const int32_t *codes502);
 /* tts_autoregressive_multi's stop bookkeeping on scripted samples (random-init weights never sample the stop token): samples [max_steps][B] = what the
  * sampler returns at each iteration, n_cand [G] the groups, flags and stop_at [B] (or NULL) as in tts_autoregressive_multi. codes_out [B][502] (padded like the

@@ -23,6 +23,7 @@ NOISE_REFERENCE, NOISE_DEVICE = 0, 1
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+AUDIO_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int)  # tts_audio_cb
 
 
 def build(verbose=False):
@@ -77,6 +78,9 @@ def lib():
         "tts_diffusion_frames": (ci, [ci]),
         "tts_load_hifigan": (ci, [vp, C.c_char_p]), "tts_hifigan_samples": (ci, [ci]),
         "tts_hifigan_decode": (ci, [vp, vp, vp, ci, vp, ci, vp, vp]),
+        "tts_hifigan_chunk": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp]),
+        "tts_hifigan_stream": (ci, [vp, vp, ci, vp, ci, C.c_uint, ci, vp, vp, vp, vp, vp, vp]), "tts_hifigan_stream_recaptures": (ci, [vp]),
+        "tts_host_stream_final_rows": (ci, [vp, ci]),
         "tts_diffusion_forward": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p]),
         "tts_diffusion": (ci, [vp, _f32p, _i32p, ci, ci, vp, ci, _f32p]),
         "tts_vocoder_samples": (ci, [ci]),
@@ -390,6 +394,54 @@ class Engine:
             out.append(audio[off:off + n].copy())
             off += n
         return out
+
+    def hifigan_chunk(self, latents_list, voices, frame0, n_frames, voice_of=None):
+        """Frames [frame0[c], frame0[c] + n_frames[c]) of every candidate's utterance (latents_list, voices, voice_of as hifigan_decode: the whole latents).
+        Returns a list of float32 waveforms, 256 * n_frames[c] samples each, the bits of hifigan_decode's slice (tts_hifigan_chunk: one call)."""
+        rows = np.array([len(l) for l in latents_list], np.int32)
+        lat = np.ascontiguousarray(np.concatenate([np.asarray(l, np.float32).reshape(-1, DMODEL) for l in latents_list]))
+        tab = np.ascontiguousarray(voices, np.float32).reshape(-1, DMODEL)
+        idx = None if voice_of is None else np.ascontiguousarray(voice_of, np.int32)
+        f0 = np.ascontiguousarray(np.broadcast_to(np.asarray(frame0, np.int32), rows.shape))
+        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, np.int32), rows.shape))
+        if idx is not None and len(idx) != len(rows):
+            raise TtsError("voice_of names %d candidates, %d given" % (len(idx), len(rows)))
+        audio = np.empty(256 * int(np.maximum(nf, 0).sum()), np.float32)
+        self._ck(self.L.tts_hifigan_chunk(self.h, _ptr(lat), _ptr(rows), len(rows), _ptr(tab), len(tab), _ptr(idx), _ptr(f0), _ptr(nf), _ptr(audio)))
+        return [a.copy() for a in np.split(audio, np.cumsum(256 * nf)[:-1])]
+
+    def hifigan_stream(self, tokens, voice, max_steps, flags=0, stride=16, on_chunk=None):
+        """tts_hifigan_stream: one candidate whose audio leaves while the loop samples. Returns (codes [502], rows, latents [rows, 1024], chunks, steps): chunks
+        is the list of (samples, is_last) in arrival order, steps the loop's step count as autoregressive() returns it. on_chunk(samples, is_last) is called
+        for each chunk as it arrives; a true return cancels the call (TtsError), and so does an exception it raises, which is raised again here once the
+        call has returned."""
+        codes = np.empty(502, np.int32)
+        rows = np.zeros(1, np.int32)
+        steps = np.zeros(1, np.int32)
+        lat = np.empty((500, DMODEL), np.float32)
+        chunks, raised = [], []
+
+        @AUDIO_CB
+        def cb(_user, samples, n, is_last):
+            try:  # ctypes would print and swallow an exception that leaves a callback, and the call would go on
+                a = np.ctypeslib.as_array(samples, (n,)).copy()
+                chunks.append((a, bool(is_last)))
+                return 1 if (on_chunk is not None and on_chunk(a, bool(is_last))) else 0
+            except BaseException as e:
+                raised.append(e)
+                return 1
+
+        tok = np.ascontiguousarray(tokens, np.int32)
+        v = np.ascontiguousarray(voice, np.float32)
+        rc = self.L.tts_hifigan_stream(self.h, _ptr(tok), len(tok), _ptr(v), max_steps, flags, stride, C.cast(cb, C.c_void_p), None, _ptr(codes), _ptr(rows),
+                                       _ptr(lat), _ptr(steps))
+        if raised:
+            raise raised[0]
+        self._ck(rc)
+        return codes, int(rows[0]), lat[:int(rows[0])].copy(), chunks, int(steps[0])
+
+    def hifigan_stream_recaptures(self):
+        return self.L.tts_hifigan_stream_recaptures(self.h)
 
     # ---- diffusion ----
     @staticmethod

@@ -12,6 +12,8 @@ namespace tts {
 int ar_begin(tts_ctx *, const int32_t *, int, const float *, int, int);
 int ar_begin_groups(tts_ctx *, const int32_t *, const int *, int, const float *, int n_voices, const int *voice_of, const int *, int);
 int ar_latents_group(tts_ctx *, int, const int32_t *, int, float *);
+int ar_stream_reserve(tts_ctx *, int n_mel);
+int ar_graph_captures(const tts_ctx *);
 int ar_prefill(tts_ctx *, float *);
 int ar_step(tts_ctx *, const int32_t *, int, float *, int mode);
 const int32_t *ar_host_lists(tts_ctx *);
@@ -223,6 +225,10 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     if (value != 0 && value != 1) return fail(c, TTS_ERR_ARG, "ar_penalty_scope: 0 (the ids of the last input) or 1 (every id fed since tts_ar_begin)");
     c->ar_penalty_scope = (int)value;
   }
+  else if (k == "hfg_small_m") { // addition within version 8: tile selection of tts_hifigan_chunk, same bits either way
+    if (!(value >= 0 && value <= (1 << 24)) || value != std::floor(value)) return fail(c, TTS_ERR_ARG, "hfg_small_m: a row count in 0 .. 2^24 (0 = never)");
+    c->hfg_small_m = (int)value;
+  }
   else if (k == "prof_eager_every") c->prof_eager_every = value < 1 ? 1 : (int)value;
   else if (k == "stream_cus") {
     // Partition of the chip between two contexts of one process (INTEGRATION.md "two-context pipeline"): value n > 0 re-creates this
@@ -295,6 +301,13 @@ int tts_hifigan_decode(tts_ctx *c, const float *latents, const int32_t *rows, in
   NEED_CTX(c);
   return guarded(c, [&] { return hifigan_decode(c, latents, rows, n_candidates, voices, n_voices, voice_of_candidate, audio_out); });
 }
+int tts_hifigan_chunk(tts_ctx *c, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices,
+                      const int32_t *voice_of_candidate, const int32_t *frame0, const int32_t *n_frames, float *audio_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return hifigan_chunk(c, latents, rows, n_candidates, voices, n_voices, voice_of_candidate, frame0, n_frames, audio_out); });
+}
+int tts_hifigan_stream_recaptures(const tts_ctx *c) { return c ? c->stream_recaptures : -1; }
+int tts_host_stream_final_rows(const int32_t *codes, int k) { return (k < 0 || (k > 0 && !codes)) ? TTS_ERR_ARG : stream_final_rows(codes, k); }
 int tts_ar_layers(const tts_ctx *c) { return c ? ar_layers(c) : 0; }
 int tts_diffusion_layers(const tts_ctx *c) { return c ? diff_layers(c) : 0; }
 
@@ -436,8 +449,44 @@ int tts_sample(tts_ctx *c, const float *logits, const int32_t *ids, int ids_per_
 // autoregressive(), main.cpp:5042-5367, for G prompt groups in one decode loop (tts_autoregressive: G = 1; tts_autoregressive_multi). Group g's
 // prompt is text_ids[t0_g .. + n_text[g]), its candidates [c0_g, c0_g + n_cand[g]) of the batch. voice: [n_voices][1024], group g reads row voice_of[g]
 // (tts_autoregressive_multi_voice; voice_of == nullptr: one voice for all). Nothing after ar_begin_groups depends on the voices.
+//
+// tts_hifigan_stream (one candidate, `hs` non-null): the same loop; after every hs->stride new codes the latent pass runs over the rows that are already
+// final and the HiFi-GAN chunk path decodes the frames that became final, which go to the callback while the loop goes on sampling.
+struct HfgStream {
+  int stride;
+  tts_audio_cb cb;
+  void *user;
+  const float *voice;
+  int have = 0, emitted = 0;            // latent rows held (frozen once a chunk was decoded from them), frames handed to the callback
+  std::vector<float> lat, pass, audio;  // the utterance's latent rows; one pass' output; one chunk's samples
+  std::vector<int32_t> codes;           // the pass' input: 8192, the sampled codes, 83 beyond (never read: n_mel ends before)
+};
+// Latent rows [hs->have, L) from a pass over the first L rows (the earlier rows are kept as they were when their audio left: what the callback got stays the
+// decode of the latents the call returns), then the frames [hs->emitted, upto) of an utterance of L rows so far to the callback.
+static int stream_emit(tts_ctx *c, HfgStream *hs, const int32_t *codes502, int L, int upto, int is_last) {
+  if (L > hs->have) {
+    // The last pass is tts_autoregressive's, length and all. A pass over a prefix runs at least 32 rows (the rows past L read padding and are dropped: causal),
+    // so that it takes the multi-row path (ar.hip run_layers: rows >= 32) that every utterance of 31 rows or more ends on — the exact-f32 GEMV path of shorter
+    // passes sums in another order, and its split-K factor depends on the row count.
+    const int n_mel = is_last ? std::min(502, L + 1) : std::max(L, 32), n_out = std::min(500, n_mel);
+    hs->pass.resize((size_t)n_out * TTS_DMODEL);
+    if (int rc = ar_latents_group(c, 0, codes502, n_mel, hs->pass.data())) return rc;
+    hs->lat.resize((size_t)L * TTS_DMODEL);
+    std::copy(hs->pass.begin() + (size_t)hs->have * TTS_DMODEL, hs->pass.begin() + (size_t)L * TTS_DMODEL, hs->lat.begin() + (size_t)hs->have * TTS_DMODEL);
+    hs->have = L;
+  }
+  const int32_t rows = hs->have, f0 = hs->emitted, n = upto - hs->emitted;
+  if (n < 1) return TTS_OK;
+  hs->audio.resize((size_t)n * 256);
+  if (int rc = hifigan_chunk(c, hs->lat.data(), &rows, 1, hs->voice, 1, nullptr, &f0, &n, hs->audio.data())) return rc;
+  hs->emitted = upto;
+  if (hs->cb(hs->user, hs->audio.data(), n * 256, is_last)) return fail(c, TTS_ERR_STATE, "tts_hifigan_stream: cancelled by the callback");
+  return TTS_OK;
+}
+
 static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n_text, int G, const float *voice, int n_voices, const int *voice_of,
-                               const int *n_cand, int max_steps, unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
+                               const int *n_cand, int max_steps, unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out,
+                               HfgStream *hs = nullptr) {
   static const bool timing = getenv("TTS_TIMING") != nullptr; // developer aid: host-side breakdown of the stage on stderr
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_begin = now(), t_sample = 0, t_step = 0;
@@ -454,8 +503,13 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
     if (!warned) { fprintf(stderr, "tts_autoregressive: a stop schedule is set but the call does not pass TTS_AR_MASK_STOP | TTS_AR_RETIRE: ignored\n"); warned = true; }
   }
   if (sched && (int)c->stop_schedule.size() != B) return fail(c, TTS_ERR_ARG, "tts_autoregressive: the stop schedule holds %d candidates, the call %d", (int)c->stop_schedule.size(), B);
+  if (hs) c->stream_recaptures = 0;
   int rc = ar_begin_groups(c, text_ids, n_text, G, voice, n_voices, voice_of, n_cand, max_steps);
   if (rc) return rc;
+  // the longest latent pass a streaming call can run (trim_latents keeps at most 9 rows past the codes), reserved once the call is known to be valid and
+  // before the decode step's buffers are used
+  if (hs && (rc = ar_stream_reserve(c, std::max(32, std::min(502, max_steps + 10))))) return rc;
+  int captures0 = -1; // decode-step graphs captured when the loop's first step had run
   const int V = TTS_VOCAB_MEL;
   std::vector<float> logits0((size_t)B * V);
   const double t_after_begin = now();
@@ -513,6 +567,16 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
       if ((flags & TTS_AR_MASK_STOP) || retire) break;
       return fail(c, TTS_ERR_LIMIT, "no stop token within %d steps", max_steps);
     }
+    if (hs && i % hs->stride == 0) { // i codes so far, none of them the stop token (one candidate: the loop ends with it)
+      const std::vector<int> &sq = book.seq[0];
+      hs->codes.assign(502, 83);
+      hs->codes[0] = 8192;
+      std::copy(sq.begin(), sq.begin() + std::min<size_t>(sq.size(), 501), hs->codes.begin() + 1);
+      const int L = stream_final_rows(hs->codes.data() + 1, (int)sq.size());
+      const int upto = tts_diffusion_frames(L) - TTS_HFG_HALO_FRAMES;
+      if (L > hs->have && upto > hs->emitted && (rc = stream_emit(c, hs, hs->codes.data(), L, upto, 0))) return rc;
+    }
+    if (captures0 < 0 && i > 1) captures0 = ar_graph_captures(c);
     t0 = now();
     if (!c->device_topk) {
       if ((rc = ar_step(c, samples.data(), i - 1, nullptr, 0))) return rc;
@@ -536,6 +600,7 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
     have_next = true;
   }
   const double t_after_loop = now();
+  if (hs) c->stream_recaptures = captures0 < 0 ? 0 : ar_graph_captures(c) - captures0;
   if (steps_out) *steps_out = i;
   std::vector<std::vector<int>> &seq = book.seq;
   c->ar_stopped.assign(B, 0); // who was cut at max_steps (TTS_AR_RETIRE / TTS_AR_MASK_STOP): tts_ar_stop_status
@@ -549,6 +614,12 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
       rows_out[b] = trimmed_latent_rows(codes_out + (size_t)b * 502);
       max_rows[g] = std::max(max_rows[g], rows_out[b]);
     }
+  if (hs) { // the remaining rows from tts_autoregressive's own pass, the remaining frames with is_last
+    if (rows_out[0] < hs->have) return fail(c, TTS_ERR_STATE, "tts_hifigan_stream: %d rows were final, the utterance keeps %d", hs->have, rows_out[0]);
+    if ((rc = stream_emit(c, hs, codes_out, rows_out[0], tts_diffusion_frames(rows_out[0]), 1))) return rc;
+    if (latents_out) std::copy(hs->lat.begin(), hs->lat.end(), latents_out);
+    return TTS_OK;
+  }
   if (!latents_out) return TTS_OK;
   // latent pass over the mel prefix that trim_latents keeps (causal: rows beyond it cannot matter), per group over its own prompt and rows
   const double t_before_lat = now();
@@ -576,6 +647,22 @@ int tts_autoregressive(tts_ctx *c, const int32_t *text_ids, int n_text, const fl
   NEED_CTX(c);
   return guarded(c, [&] {
     return autoregressive_impl(c, text_ids, &n_text, 1, voice, 1, nullptr, &B, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
+  });
+}
+
+int tts_hifigan_stream(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, int max_steps, unsigned flags, int stride_codes, tts_audio_cb cb,
+                       void *user, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
+  NEED_CTX(c);
+  if (stride_codes < 1 || !cb) return fail(c, TTS_ERR_ARG, "tts_hifigan_stream: bad argument (stride_codes %d: >= 1, a callback)", stride_codes);
+  if (!c->ar) return fail(c, TTS_ERR_STATE, "AR model not loaded");
+  if (!c->hifigan) return fail(c, TTS_ERR_STATE, "tts_load_hifigan not called");
+  if (voice)
+    for (int i = 0; i < TTS_DMODEL; i++)
+      if (!std::isfinite(voice[i])) return fail(c, TTS_ERR_ARG, "tts_hifigan_stream: the voice holds a non-finite value");
+  return guarded(c, [&] {
+    HfgStream hs{stride_codes, cb, user, voice};
+    const int B = 1;
+    return autoregressive_impl(c, text_ids, &n_text, 1, voice, 1, nullptr, &B, max_steps, flags, codes_out, rows_out, latents_out, steps_out, &hs);
   });
 }
 

@@ -1373,6 +1373,7 @@ struct ArState {
   // the ~150-node graph on every switch)
   hipGraph_t graphs[3] = {};
   hipGraphExec_t graph_execs[3] = {};
+  int graph_captures = 0; // decode-step graphs captured since the model was loaded (tts_ar_graph_captures)
   // everything the captured step bakes into its nodes: the graph of the previous utterance is replayed when nothing moved
   struct GraphSig {
     int B = 0, max_pos = 0, lut = 0, wmode = 0, mode = 0, multi = 0;
@@ -2209,6 +2210,7 @@ int ar_step(tts_ctx *ctx, const int32_t *prev_ids, int step_i, float *logits_out
     if (!st->graph_execs[mode]) {
       st->graph_sigs[mode] = sig;
       TTS_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+      st->graph_captures++;
       int rc = enqueue_decode_step(ctx, st);
       hipError_t e = hipStreamEndCapture(ctx->stream, &st->graphs[mode]);
       if (rc || e != hipSuccess) { st->drop_graph(mode); if (rc) return rc; TTS_HIP(ctx, e); } // never keep a half-captured graph
@@ -2329,6 +2331,28 @@ int ar_latents_group(tts_ctx *ctx, int g, const int32_t *codes502, int n_mel, fl
   if (!st->prefill_done) CHECK(ar_prefill(ctx, nullptr));
   return latents_group(ctx, st, g, codes502, st->g_n[g], n_mel, out);
 }
+
+// tts_hifigan_stream runs latent passes of growing length BETWEEN decode steps. A DevBuf that grows frees and reallocates, and the captured decode step bakes
+// h, qkv, att and ff into its nodes (GraphSig): growing inside the loop would be safe and re-capture the ~150-node graph at every growth. Called right after
+// ar_begin_groups (which has validated the call; nothing has run on the buffers yet) with the longest pass the call can run, so that nothing moves afterwards.
+int ar_stream_reserve(tts_ctx *ctx, int n_mel) {
+  ArState *st = ctx->ar;
+  if (!st || st->B < 1) return fail(ctx, TTS_ERR_STATE, "tts_ar_begin not called");
+  const int n_text = st->n_text;
+  CHECK(reserve_rows(ctx, st, std::max({16, n_text + 2, n_mel})));
+  TTS_HIP(ctx, hipMemsetAsync(st->h.p, 0, st->h.cap, ctx->stream)); // ar_begin_groups' zeroed padding rows, again: h may have moved
+  const size_t lat = (size_t)st->n_layers * (1 + n_text + n_mel) * D * sizeof(__half);
+  TTS_HIP(ctx, st->lat_k.reserve(lat));
+  TTS_HIP(ctx, st->lat_v.reserve(lat));
+  if (n_mel >= 32) { // launch_mfma_matmul's operands
+    const size_t rpad = (size_t)(n_mel + 127) & ~(size_t)127;
+    TTS_HIP(ctx, st->a_hi.reserve(rpad * FF * sizeof(__half)));
+    TTS_HIP(ctx, st->a_lo.reserve(rpad * FF * sizeof(__half)));
+    TTS_HIP(ctx, st->part.reserve(rpad * FF * sizeof(float)));
+  }
+  return TTS_OK;
+}
+int ar_graph_captures(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->graph_captures : 0; }
 
 int ar_layers(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->n_layers : 0; }
 int ar_batch(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->B : 0; }

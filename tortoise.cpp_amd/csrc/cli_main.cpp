@@ -49,6 +49,11 @@
 //   (default <models>/ggml-hifigan-model.bin); the diffusion and vocoder models are then neither loaded nor required. --clvp, --split-text and several --voice work
 //   as with the diffusion decoder. Usage errors (exit 1, before a model is loaded): another decoder name; with hifigan any of --steps, --sampler, --ddim-eta,
 //   --cond-free-k, --diffusion-latent (they configure the decoder that is not run), --devices > 1 or --exchange rccl. --timing 1 names the decoder ("[timing] decoder ...").
+// --stream (with --decoder hifigan; no value) [--stream-stride N, default 16]: one candidate through tts_hifigan_stream. The samples are appended to the WAV as the
+//   callback receives them, while the autoregressive stage is still sampling, and the header's two sizes are fixed at the end: the file is byte for byte the one the
+//   run without --stream writes. --timing 1 prints when the first samples arrived ("[timing] first audio ..."), from the start of the process and from the start of the
+//   autoregressive stage. Usage errors (exit 1, before a model is loaded): --stream with --decoder diffusion, --clvp, --split-text, several --voice, --candidates > 1
+//   or --devices > 1; --stream-stride < 1.
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -65,6 +70,22 @@
 #include <unistd.h>
 #include <chrono>
 #include <thread>
+
+// --stream: the callback of tts_hifigan_stream appends the samples to the open WAV
+struct StreamSink {
+  FILE *f = nullptr;
+  int64_t samples = 0;
+  int calls = 0;
+  bool failed = false;
+  std::chrono::steady_clock::time_point t_ar, t_first;
+  static int on_audio(void *user, const float *s, int n, int /*is_last*/) {
+    StreamSink *k = (StreamSink *)user;
+    if (k->calls++ == 0) k->t_first = std::chrono::steady_clock::now();
+    if (fwrite(s, sizeof(float), (size_t)n, k->f) != (size_t)n || fflush(k->f)) { k->failed = true; return 1; }
+    k->samples += n;
+    return 0;
+  }
+};
 
 static int die(tts_ctx *c, const char *what) {
   fprintf(stderr, "%s: %s\n", what, tts_last_error(c));
@@ -92,9 +113,18 @@ int main(int argc, char **argv) {
   bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
+  bool stream = false;
+  int stream_stride = 16;
+  StreamSink sink;
+  for (int i = 1; i < argc; ++i) { // --stream is the one flag without a value: every other "--flag" owns the slot after it, which is not looked at here
+    const std::string a(argv[i]);
+    if (a == "--stream") stream = true;
+    else if (a.rfind("--", 0) == 0) ++i;
+  }
   for (int i = 1; i < argc - 1; ++i) {
     std::string a(argv[i]);
-    if (a == "--voice") { voicePath = argv[i + 1]; voicePaths.push_back(voicePath); }
+    if (a == "--stream-stride") stream_stride = std::stoi(argv[i + 1]);
+    else if (a == "--voice") { voicePath = argv[i + 1]; voicePaths.push_back(voicePath); }
     else if (a == "--message") message = argv[i + 1];
     else if (a == "--output") outputPath = argv[i + 1];
     else if (a == "--seed") { seed = std::stoi(argv[i + 1]); have_seed = true; }
@@ -144,6 +174,12 @@ int main(int argc, char **argv) {
     const char *bad = have_steps ? "--steps" : have_sampler ? "--sampler" : have_eta ? "--ddim-eta" : have_k ? "--cond-free-k" : !diffLatentPaths.empty() ? "--diffusion-latent" : nullptr;
     if (bad) { fprintf(stderr, "%s configures the diffusion decoder, which --decoder hifigan does not run\n", bad); return 1; }
     if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--decoder hifigan cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
+  }
+  if (stream) {
+    const char *bad = !use_hifigan ? "--decoder diffusion" : !clvpPath.empty() ? "--clvp" : split_ids > 0 ? "--split-text" : voicePaths.size() > 1 ? "several --voice" :
+                      candidates > 1 ? "--candidates > 1" : (devices > 1 || shard >= 0) ? "--devices > 1" : nullptr;
+    if (bad) { fprintf(stderr, "--stream serves one candidate of one voice through the HiFi-GAN decoder: it cannot be combined with %s\n", bad); return 1; }
+    if (stream_stride < 1) { fprintf(stderr, "--stream-stride %d: at least 1\n", stream_stride); return 1; }
   }
   if (sampler != "ddpm" && sampler != "ddim") { fprintf(stderr, "--sampler %s: ddpm or ddim\n", sampler.c_str()); return 1; }
   if (!(ddim_eta >= 0.0 && ddim_eta <= 1.0)) { fprintf(stderr, "--ddim-eta %g: a value in 0 .. 1\n", ddim_eta); return 1; }
@@ -493,10 +529,34 @@ int main(int argc, char **argv) {
     // More than one candidate (in this process or across --devices shards): the throughput stop rule. The reference's "all B samples of ONE
     // step are 8193" practically never fires for B > 1 (and would need a per-step exchange between shards); every sequence is the same.
     const unsigned ar_flags = (fixed_codes > 0 ? TTS_AR_MASK_STOP : 0) | (total_candidates > 1 ? TTS_AR_RETIRE : 0);
-    if (tts_autoregressive(ctx, tokens.data(), n, voice.data(), B_ar, fixed_codes > 0 ? fixed_codes : 500, ar_flags,
-                           codes.data(), rows.data(), latents.data(), &nsteps))
-      return die(ctx, "autoregressive");
-    mark("autoregressive");
+    if (stream) { // the decoder's model first: audio leaves while the loop samples
+      if (tts_load_hifigan(ctx, hifiganPath.c_str())) return die(ctx, "hifigan_model_load");
+      mark("load hifigan");
+      if (tts_write_wav(outputPath.c_str(), nullptr, 0, 24000)) { std::cerr << "Error opening output file." << std::endl; return 1; }
+      sink.f = fopen(outputPath.c_str(), "r+b");
+      if (!sink.f || fseek(sink.f, 0, SEEK_END)) { std::cerr << "Error opening output file." << std::endl; return 1; }
+      sink.t_ar = clk::now();
+      const int rc_s = tts_hifigan_stream(ctx, tokens.data(), n, voice.data(), fixed_codes > 0 ? fixed_codes : 500, ar_flags, stream_stride, StreamSink::on_audio,
+                                          &sink, codes.data(), rows.data(), nullptr, &nsteps);
+      if (!rc_s) { // the two sizes of the header: RIFF chunk at byte 4, data chunk at byte 40
+        const int32_t data_size = (int32_t)(sink.samples * 4), file_size = 36 + data_size;
+        if (fseek(sink.f, 4, SEEK_SET) || fwrite(&file_size, 4, 1, sink.f) != 1 || fseek(sink.f, 40, SEEK_SET) || fwrite(&data_size, 4, 1, sink.f) != 1) sink.failed = true;
+      }
+      if (fclose(sink.f)) sink.failed = true;
+      sink.f = nullptr;
+      if (rc_s) return die(ctx, "hifigan_stream");
+      if (sink.failed) { std::cerr << "Error writing output file." << std::endl; return 1; }
+      mark("autoregressive + hifigan (streamed)");
+      if (timing)
+        fprintf(stderr, "[timing] first audio           %8.1f ms after the autoregressive stage began (at %8.1f), %d callbacks, stride %d\n",
+                std::chrono::duration<double, std::milli>(sink.t_first - sink.t_ar).count(), std::chrono::duration<double, std::milli>(sink.t_first - t_start).count(),
+                sink.calls, stream_stride);
+    } else {
+      if (tts_autoregressive(ctx, tokens.data(), n, voice.data(), B_ar, fixed_codes > 0 ? fixed_codes : 500, ar_flags,
+                             codes.data(), rows.data(), latents.data(), &nsteps))
+        return die(ctx, "autoregressive");
+      mark("autoregressive");
+    }
     printf("tokens sampled: %d\n", nsteps);
     if (fixed_codes <= 0) {
       std::vector<int32_t> stopped(B_ar);
@@ -534,7 +594,8 @@ int main(int argc, char **argv) {
 
   bg.t.join();
   if (rc_diff) { fprintf(stderr, "diffusion_model_load: %s\n", err_diff.c_str()); return 1; }
-  if (use_hifigan) { // the kept candidates and their voices through one call
+  if (stream) { // written already
+  } else if (use_hifigan) { // the kept candidates and their voices through one call
     if (tts_load_hifigan(ctx, hifiganPath.c_str())) return die(ctx, "hifigan_model_load");
     mark("load hifigan");
     size_t total = 0;
@@ -582,7 +643,8 @@ int main(int argc, char **argv) {
     if (tts_write_wav(path.c_str(), samples, ns, 24000)) std::cerr << "Error opening output file." << std::endl;
     else if (is_output) std::cout << "WAV file saved successfully. :^)" << std::endl;
   };
-  if (use_rccl) {
+  if (stream) std::cout << "WAV file saved successfully. :^)" << std::endl;
+  else if (use_rccl) {
     auto bail = [&]() { fprintf(stderr, "rccl: %s\n", world.err.c_str()); return 1; };
     std::vector<char> g;
     if (kept_gc >= 0) { // every rank's winner: (score, global candidate, samples); the best one's audio goes to rank 0

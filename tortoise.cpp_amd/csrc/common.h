@@ -170,6 +170,9 @@ struct tts_ctx {
   double ddim_eta = 0;     // option "ddim_eta" in [0, 1]: 0 = deterministic DDIM (only x_T is noise); read only when diff_sampler = 1
   float cond_free_k = 2.0f; // option "cond_free_k": the conditioning-free guidance strength at t = n (main.cpp's base_k = 2.0), both samplers
   bool capturing = false;  // a hipGraph is being captured on the stream: ProfScope records nothing (event records would become graph nodes)
+  int stream_recaptures = 0; // decode-step graphs captured inside the last tts_hifigan_stream call's loop after its first step (tts_hifigan_stream_recaptures)
+  int hfg_small_m = 0;     // option "hfg_small_m": tts_hifigan_chunk runs a convolution whose longest window has at most this many rows on the small-M tile (0, the default until
+                           // profiles/hifigan_stream.txt holds a measurement in its favour: never)
   int diff_graph = 1;      // option "diff_graph": the diffusion step is captured once per call and replayed (0: every step launched eagerly)
   int prof_eager_every = 8; // while a diff_* family is profiled, every Nth diffusion step runs eagerly with its event pairs; the others replay the graph
   std::map<std::string, tts::ProfEntry> prof;
@@ -410,6 +413,11 @@ int hifigan_load(tts_ctx *ctx, const char *path);
 void hifigan_free(HifiganState *);
 int hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices, const int32_t *voice_of_candidate,
                    float *audio_out);
+int hifigan_chunk(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices, const int32_t *voice_of_candidate,
+                  const int32_t *frame0, const int32_t *n_frames, float *audio_out);
+// Latent rows of a one-candidate utterance that are final after its first k sampled codes (none of them the stop token): the rows whose inputs
+// 8192, c_0 .. c_{k-1} pad_codes will not rewrite, cut where trimmed_latent_rows will cut (tts_hifigan_stream; host_logic.cpp)
+int stream_final_rows(const int32_t *codes, int k);
 int clvp_load(tts_ctx *ctx, const char *path);
 void clvp_free(ClvpState *);
 int clvp_score(tts_ctx *ctx, const int32_t *text_ids, int n_text, const int32_t *codes, const int32_t *code_len, int n_candidates, int code_stride,

@@ -1,4 +1,4 @@
-// HiFi-GAN decoder on MI355X (gfx950): autoregressive latents + speaker latent -> 24 kHz waveform      tts_load_hifigan / tts_hifigan_decode
+// HiFi-GAN decoder on MI355X (gfx950): autoregressive latents + speaker latent -> 24 kHz waveform      tts_load_hifigan / tts_hifigan_decode / tts_hifigan_chunk
 //
 // The reference has one decoder (80 diffusion steps + UnivNet). Upstream tortoise-tts has a second one, the api_fast.py path: a HiFi-GAN
 // generator taken from XTTS that reads the autoregressive stage's latents and the speaker latent and writes the waveform directly — no
@@ -27,6 +27,8 @@
 //
 // A call is one launch sequence for the whole ragged batch: one upload (latents, voice table, candidate table), 1 + 1 + 1 + 4 x 19 + 1 launches,
 // one download. Nothing of it depends on the batch: a candidate's samples are the same bits alone or in any batch.
+// tts_hifigan_chunk runs the same sequence over a window of every candidate (hifigan_run); every output element is summed in hfg_conv_kernel's order whatever
+// the window and the tile, so the chunks of any partition are the bits of the whole call.
 #include "common.h"
 #include <cmath>
 
@@ -37,11 +39,16 @@ constexpr int HFG_LAT = 1024, HFG_C0 = 512, HFG_STAGES = 4, HFG_MAX_ROWS = 500, 
 constexpr int HFG_UP[HFG_STAGES] = {8, 8, 2, 2};         // stride u of the transposed convolutions (kernel 2 u, padding u / 2)
 constexpr int HFG_RK[3] = {3, 7, 11}, HFG_RD[3] = {1, 3, 5}; // ResBlock kernel sizes / dilations of convs1
 constexpr int HFG_TM = 256;                              // output rows of a workgroup: 4 waves x 64
-constexpr int HFG_SEQ = 8;                               // ints per candidate in the table: {start frame, T, voice, L, first latent row, frames before it, 0, 0}
+constexpr int HFG_TS = 32;                               // output rows of a workgroup of the small-M variant: one MFMA tile, the 4 waves tile the channels
+// ints per candidate in the table: {start frame in the buffers, frames evaluated W, voice, L, first latent row, output frames before it, w0, keep0, keep_n}.
+// tts_hifigan_decode: W = T, w0 = keep0 = 0, keep_n = T. tts_hifigan_chunk: the window [w0, w0 + W) of the utterance is evaluated (w0 = its absolute first
+// frame, which only the interpolation reads) and conv_post writes the frames [keep0, keep0 + keep_n) of the window. Nine, not the eight of the whole-utterance
+// table with its two spare ints: the window needs w0 and, for conv_post, which of its frames to keep and how many.
+constexpr int HFG_SEQ = 9;
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-// Receptive field of one output sample, in frames on either side (what a chunked call would need, and what the tests' locality check uses):
+// Receptive field of one output sample, in frames on either side (the halo of tts_hifigan_chunk's window, and what the tests' locality check uses):
 // the two interpolations reach 9 frames back from the last latent row ((1.5 + 4 + 1) / 0.91875 + 1.5), conv_pre 3, and stage i adds
 // (1 + 60) rows at R_i rows per frame (one input row of the transposed convolution; ResBlock k = 11: sum_d (5 d + 5) = 60 rows), conv_post 3 / 256:
 // 9 + 3 + 61 / 8 + 61 / 64 + 61 / 128 + 61 / 256 + 3 / 256 = 21.3.
@@ -141,6 +148,68 @@ __global__ __launch_bounds__(256) void hfg_conv_kernel(const HfgConv a) {
     }
 }
 
+// The small-M variant (tts_hifigan_chunk's low-rate levels: a streaming window is ~80 frames, 80 rows at conv_pre and 640 in stage 0, where the 256-row tile
+// idles most of its waves on a handful of CUs). One workgroup: 32 rows x 128 output channels (x one phase); the four waves tile the CHANNELS, one 32 x 32 MFMA
+// tile each, so a short window spreads over 8 x as many row blocks and no wave multiplies rows that are predicated away. Staging (33-float rows, leaky_relu on
+// the way in, zero predication), the per-element order (channel chunks ascending, taps, k pairs on the same MFMA with the same lane-half split) and the epilogue
+// are hfg_conv_kernel's: every output element is the same chain of the same instructions on the same operands, hence the same bits.
+__global__ __launch_bounds__(256) void hfg_conv_small_kernel(const HfgConv a) {
+  extern __shared__ float sx[];
+  const int s = blockIdx.y;
+  const int f0 = a.seq[HFG_SEQ * s], T = a.seq[HFG_SEQ * s + 1], voice = a.seq[HFG_SEQ * s + 2];
+  const int Tin = T * a.rate, t0 = blockIdx.x * HFG_TS;
+  if (t0 >= Tin) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lr = lane & 31, lk = lane >> 5;
+  const int phase = blockIdx.z % a.phases, n0 = (blockIdx.z / a.phases) * 128 + wave * 32;
+  int lo = a.lo;
+  const float *w = a.w;
+  if (a.phases > 1) {
+    lo = (phase + a.pad_t) / a.phases - 1;
+    w += (size_t)phase * a.taps * a.cin * a.cout;
+  }
+  const int win = HFG_TS + (a.taps - 1) * a.dil;
+  const float *in = a.in + (size_t)f0 * a.rate * a.cin;
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; r++) acc[r] = 0.f;
+  for (int c0 = 0; c0 < a.cin; c0 += 32) {
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < win * 8; idx += 256) {
+      const int r = idx >> 3, q = (idx & 7) * 4, t = t0 + lo + r;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (t >= 0 && t < Tin) v = *(const float4 *)(in + (size_t)t * a.cin + c0 + q);
+      float *d = sx + r * 33 + q;
+      d[0] = v.x < 0.f ? v.x * a.slope : v.x;
+      d[1] = v.y < 0.f ? v.y * a.slope : v.y;
+      d[2] = v.z < 0.f ? v.z * a.slope : v.z;
+      d[3] = v.w < 0.f ? v.w * a.slope : v.w;
+    }
+    __syncthreads();
+    for (int tap = 0; tap < a.taps; tap++) {
+      const float *xr = sx + (lr + tap * a.dil) * 33 + lk;
+      const float *wr = w + (size_t)(tap * a.cin + c0 + lk) * a.cout + n0 + lr;
+#pragma unroll 8
+      for (int k = 0; k < 32; k += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xr[k], wr[(size_t)k * a.cout], acc, 0, 0, 0);
+    }
+  }
+  const size_t obase = (size_t)f0 * a.rate * a.phases * a.cout;
+  const int col = n0 + lr;
+  float bv = a.bias[col];
+  if (a.cbias) bv += a.cbias[(size_t)voice * a.cout + col];
+#pragma unroll
+  for (int r = 0; r < 16; r++) {
+    const int t = t0 + 8 * (r >> 2) + 4 * lk + (r & 3);
+    if (t < Tin) {
+      const size_t o = obase + ((size_t)t * a.phases + phase) * a.cout + col;
+      float v = acc[r] + bv;
+      if (a.resid) v += a.resid[o];
+      if (a.acc_mode == 1) v += a.out[o];
+      else if (a.acc_mode == 2) v = (a.out[o] + v) / 3.0f;
+      a.out[o] = v;
+    }
+  }
+}
+
 // z[t][c] of every candidate: F.interpolate(scale_factor = 4, linear, align_corners = False) then the same with 24000 / 22050 on the result
 // (source position (dst + 0.5) / scale - 0.5 clamped at 0, upper neighbour clamped at the last element: 1 / scale = 0.25 and 0.91875)
 __global__ __launch_bounds__(256) void hfg_interp_kernel(const float *__restrict__ lat, const int *__restrict__ seq, float *__restrict__ z) {
@@ -148,7 +217,8 @@ __global__ __launch_bounds__(256) void hfg_interp_kernel(const float *__restrict
   const int f0 = seq[HFG_SEQ * s], T = seq[HFG_SEQ * s + 1], L = seq[HFG_SEQ * s + 3];
   if (t >= T) return;
   const float *lp = lat + (size_t)seq[HFG_SEQ * s + 4] * HFG_LAT;
-  const float src2 = fmaxf(((float)t + 0.5f) * 0.91875f - 0.5f, 0.f);
+  const int ta = seq[HFG_SEQ * s + 6] + t; // the frame's index in the whole utterance: a frame is a function of it and of L alone, so a window needs no halo here
+  const float src2 = fmaxf(((float)ta + 0.5f) * 0.91875f - 0.5f, 0.f);
   const int i0 = min((int)src2, 4 * L - 1), i1 = min(i0 + 1, 4 * L - 1);
   const float l2 = src2 - (float)i0;
   const float sa = fmaxf(((float)i0 + 0.5f) * 0.25f - 0.5f, 0.f), sb = fmaxf(((float)i1 + 0.5f) * 0.25f - 0.5f, 0.f);
@@ -171,14 +241,15 @@ __global__ __launch_bounds__(256) void hfg_cond_kernel(const float *__restrict__
   if (lane == 0) cond[(size_t)v * HFG_C0 + co] = sum + b[co];
 }
 
-// audio = tanh(conv_post(leaky_relu(x, 0.01))): 32 -> 1 channels, k 7; one thread per sample (224 multiply-adds: the stage is bound by reading x)
+// audio = tanh(conv_post(leaky_relu(x, 0.01))): 32 -> 1 channels, k 7; one thread per sample (224 multiply-adds: the stage is bound by reading x).
+// Only the kept frames of the evaluated window are written (the whole utterance for tts_hifigan_decode).
 __global__ __launch_bounds__(256) void hfg_post_kernel(const float *__restrict__ x, const float *__restrict__ w /*[7][32]*/, const float *__restrict__ b,
                                                        const int *__restrict__ seq, float *__restrict__ audio) {
   __shared__ float sw[7 * 32];
   const int s = blockIdx.y;
-  const int f0 = seq[HFG_SEQ * s], T = seq[HFG_SEQ * s + 1], before = seq[HFG_SEQ * s + 5];
-  const int n = T * 256, t = blockIdx.x * 256 + threadIdx.x;
-  if (blockIdx.x * 256 >= n) return;
+  const int f0 = seq[HFG_SEQ * s], T = seq[HFG_SEQ * s + 1], before = seq[HFG_SEQ * s + 5], keep0 = seq[HFG_SEQ * s + 7], keep_n = seq[HFG_SEQ * s + 8];
+  const int n = T * 256, j = blockIdx.x * 256 + threadIdx.x, t = keep0 * 256 + j;
+  if ((int)blockIdx.x >= keep_n) return;
   if (threadIdx.x < 7 * 32) sw[threadIdx.x] = w[threadIdx.x];
   __syncthreads();
   const float *xp = x + (size_t)f0 * 256 * 32;
@@ -197,7 +268,7 @@ __global__ __launch_bounds__(256) void hfg_post_kernel(const float *__restrict__
       sum += (v.w < 0.f ? v.w * 0.01f : v.w) * wq[3];
     }
   }
-  audio[(size_t)before * 256 + t] = tanhf(sum);
+  audio[(size_t)before * 256 + j] = tanhf(sum);
 }
 } // namespace
 
@@ -295,30 +366,45 @@ int hifigan_load(tts_ctx *ctx, const char *path) {
   return TTS_OK;
 }
 
-int hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, const float *voices, int n_voices, const int32_t *voice_of, float *audio_out) {
+// tts_hifigan_decode (frame0 == n_frames == nullptr: every candidate's whole utterance, the 256-row tile everywhere) and tts_hifigan_chunk (candidate c's
+// frames [frame0[c], frame0[c] + n_frames[c]): the window of TTS_HFG_HALO_FRAMES more on either side, clipped to the utterance, goes through the same launch
+// sequence as a sequence of its own; where the window touches an end of the utterance the convolutions' zero predication IS the boundary condition, at a cut it
+// is wrong within the halo only, and conv_post does not write the halo).
+static int hifigan_run(tts_ctx *ctx, const char *who, const float *latents, const int32_t *rows, int B, const float *voices, int n_voices, const int32_t *voice_of,
+                       const int32_t *frame0, const int32_t *n_frames, float *audio_out) {
   HifiganState *st = ctx->hifigan;
+  const bool chunk = frame0 != nullptr;
   if (!st) return fail(ctx, TTS_ERR_STATE, "tts_load_hifigan not called");
-  if (!latents || !rows || !voices || !audio_out || B < 1) return fail(ctx, TTS_ERR_ARG, "tts_hifigan_decode: bad argument");
-  if (n_voices < 1 || n_voices > (1 << 20)) return fail(ctx, TTS_ERR_ARG, "tts_hifigan_decode: %d voices", n_voices);
-  if (B > HFG_MAX_CAND) return fail(ctx, TTS_ERR_LIMIT, "tts_hifigan_decode: %d candidates (at most %d per call)", B, HFG_MAX_CAND);
+  if (!latents || !rows || !voices || !audio_out || B < 1) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", who);
+  if (n_voices < 1 || n_voices > (1 << 20)) return fail(ctx, TTS_ERR_ARG, "%s: %d voices", who, n_voices);
+  if (B > HFG_MAX_CAND) return fail(ctx, TTS_ERR_LIMIT, "%s: %d candidates (at most %d per call)", who, B, HFG_MAX_CAND);
   std::vector<int> seq((size_t)HFG_SEQ * B, 0);
-  int64_t lat_rows = 0, frames = 0, fpad = 0;
-  int maxT = 0;
+  int64_t lat_rows = 0, frames = 0, fpad = 0, wframes = 0;
+  int maxW = 0, maxKeep = 0;
   for (int c = 0; c < B; c++) {
-    if (rows[c] < 1) return fail(ctx, TTS_ERR_ARG, "tts_hifigan_decode: candidate %d has %d latent rows", c, rows[c]);
-    if (rows[c] > HFG_MAX_ROWS) return fail(ctx, TTS_ERR_LIMIT, "tts_hifigan_decode: candidate %d has %d latent rows (at most %d)", c, rows[c], HFG_MAX_ROWS);
+    if (rows[c] < 1) return fail(ctx, TTS_ERR_ARG, "%s: candidate %d has %d latent rows", who, c, rows[c]);
+    if (rows[c] > HFG_MAX_ROWS) return fail(ctx, TTS_ERR_LIMIT, "%s: candidate %d has %d latent rows (at most %d)", who, c, rows[c], HFG_MAX_ROWS);
     const int v = voice_of ? voice_of[c] : 0;
-    if (v < 0 || v >= n_voices) return fail(ctx, TTS_ERR_ARG, "tts_hifigan_decode: candidate %d names voice %d of %d", c, v, n_voices);
+    if (v < 0 || v >= n_voices) return fail(ctx, TTS_ERR_ARG, "%s: candidate %d names voice %d of %d", who, c, v, n_voices);
     const int T = tts_diffusion_frames(rows[c]);
+    int w0 = 0, w1 = T, keep0 = 0, keep_n = T;
+    if (chunk) {
+      if (frame0[c] < 0 || n_frames[c] < 1) return fail(ctx, TTS_ERR_ARG, "%s: candidate %d asks for %d frames from frame %d", who, c, n_frames[c], frame0[c]);
+      if ((int64_t)frame0[c] + n_frames[c] > T)
+        return fail(ctx, TTS_ERR_ARG, "%s: candidate %d asks for frames [%d, %lld) of %d", who, c, frame0[c], (long long)frame0[c] + n_frames[c], T);
+      w0 = std::max(0, frame0[c] - TTS_HFG_HALO_FRAMES); w1 = std::min(T, frame0[c] + n_frames[c] + TTS_HFG_HALO_FRAMES);
+      keep0 = frame0[c] - w0; keep_n = n_frames[c];
+    }
+    const int W = w1 - w0;
     int *q = &seq[(size_t)HFG_SEQ * c];
-    q[0] = (int)fpad; q[1] = T; q[2] = v; q[3] = rows[c]; q[4] = (int)lat_rows; q[5] = (int)frames;
-    lat_rows += rows[c]; frames += T; fpad += (T + 7) / 8 * 8; maxT = std::max(maxT, T);
+    q[0] = (int)fpad; q[1] = W; q[2] = v; q[3] = rows[c]; q[4] = (int)lat_rows; q[5] = (int)frames; q[6] = w0; q[7] = keep0; q[8] = keep_n;
+    lat_rows += rows[c]; frames += keep_n; wframes += W; fpad += (W + 7) / 8 * 8; maxW = std::max(maxW, W); maxKeep = std::max(maxKeep, keep_n);
   }
   const size_t n_lat = (size_t)lat_rows * HFG_LAT, n_voice = (size_t)n_voices * HFG_LAT;
   for (size_t i = 0; i < n_lat; i++)
-    if (!std::isfinite(latents[i])) return fail(ctx, TTS_ERR_ARG, "tts_hifigan_decode: latent row %d holds a non-finite value", (int)(i / HFG_LAT));
+    if (!std::isfinite(latents[i])) return fail(ctx, TTS_ERR_ARG, "%s: latent row %d holds a non-finite value", who, (int)(i / HFG_LAT));
   for (size_t i = 0; i < n_voice; i++)
-    if (!std::isfinite(voices[i])) return fail(ctx, TTS_ERR_ARG, "tts_hifigan_decode: voice %d holds a non-finite value", (int)(i / HFG_LAT));
+    if (!std::isfinite(voices[i])) return fail(ctx, TTS_ERR_ARG, "%s: voice %d holds a non-finite value", who, (int)(i / HFG_LAT));
   // one upload: latents | voice table | candidate table
   std::vector<float> up(n_lat + n_voice + seq.size());
   memcpy(up.data(), latents, n_lat * 4);
@@ -337,18 +423,26 @@ int hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, int 
   const float *d_lat = st->in.as<float>(), *d_voice = d_lat + n_lat;
   const int *d_seq = (const int *)(d_voice + n_voice);
   float *z = st->z.as<float>(), *cb = st->cb.as<float>(), *x = st->x.as<float>(), *u = st->u.as<float>(), *t = st->t.as<float>(), *m = st->m.as<float>();
-  hfg_interp_kernel<<<dim3(maxT, B), 256, 0, ctx->stream>>>(d_lat, d_seq, z);
+  hfg_interp_kernel<<<dim3(maxW, B), 256, 0, ctx->stream>>>(d_lat, d_seq, z);
   hfg_cond_kernel<<<dim3(HFG_C0 / 4, n_voices), 256, 0, ctx->stream>>>(st->cond.w, st->cond.b, d_voice, cb);
+  // Option "hfg_small_m": a chunked call runs a convolution on the small-M variant when its longest window has at most that many rows at the convolution's
+  // level and the output channels fill the four waves (0: never). The whole-utterance call keeps the 256-row tile.
+  const int small_rows = chunk ? ctx->hfg_small_m : 0;
   auto conv = [&](const float *in, float *out, const float *resid, const HfgLayer &l, int cin, int cout, int taps, int dil, int phases, int rate, float slope,
                   int acc_mode, const float *cbias) {
     HfgConv a{};
     a.in = in; a.out = out; a.resid = resid; a.w = l.w; a.bias = l.b; a.cbias = cbias; a.seq = d_seq;
     a.cin = cin; a.cout = cout; a.taps = taps; a.dil = dil; a.lo = -dil * (taps - 1) / 2; a.phases = phases; a.pad_t = phases / 2; a.rate = rate;
     a.slope = slope; a.acc_mode = acc_mode;
+    ProfScope ps(ctx, "hfg_conv", 2.0 * (double)wframes * rate * phases * taps * cin * cout);
+    if (cout % 128 == 0 && (int64_t)maxW * rate <= small_rows) {
+      const dim3 grid((unsigned)(((size_t)maxW * rate + HFG_TS - 1) / HFG_TS), (unsigned)B, (unsigned)(cout / 128 * phases));
+      hfg_conv_small_kernel<<<grid, 256, (size_t)(HFG_TS + (taps - 1) * dil) * 33 * 4, ctx->stream>>>(a);
+      return;
+    }
     const int nt = cout >= 64 ? 2 : 1;
-    const dim3 grid((unsigned)(((size_t)maxT * rate + HFG_TM - 1) / HFG_TM), (unsigned)B, (unsigned)(cout / (32 * nt) * phases));
+    const dim3 grid((unsigned)(((size_t)maxW * rate + HFG_TM - 1) / HFG_TM), (unsigned)B, (unsigned)(cout / (32 * nt) * phases));
     const size_t lds = (size_t)(HFG_TM + (taps - 1) * dil) * 33 * 4;
-    ProfScope ps(ctx, "hfg_conv", 2.0 * (double)frames * rate * phases * taps * cin * cout);
     if (nt == 2) hfg_conv_kernel<2><<<grid, 256, lds, ctx->stream>>>(a);
     else hfg_conv_kernel<1><<<grid, 256, lds, ctx->stream>>>(a);
   };
@@ -369,11 +463,22 @@ int hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, int 
     }
     cur = m;
   }
-  hfg_post_kernel<<<dim3(maxT, B), 256, 0, ctx->stream>>>(cur, st->post.w, st->post.b, d_seq, st->audio.as<float>());
+  hfg_post_kernel<<<dim3(maxKeep, B), 256, 0, ctx->stream>>>(cur, st->post.w, st->post.b, d_seq, st->audio.as<float>());
   TTS_HIP(ctx, hipGetLastError());
   TTS_HIP(ctx, hipMemcpyAsync(audio_out, st->audio.p, (size_t)frames * 256 * 4, hipMemcpyDeviceToHost, ctx->stream));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return TTS_OK;
+}
+
+int hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, const float *voices, int n_voices, const int32_t *voice_of, float *audio_out) {
+  return hifigan_run(ctx, "tts_hifigan_decode", latents, rows, B, voices, n_voices, voice_of, nullptr, nullptr, audio_out);
+}
+
+int hifigan_chunk(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, const float *voices, int n_voices, const int32_t *voice_of, const int32_t *frame0,
+                  const int32_t *n_frames, float *audio_out) {
+  if (!ctx->hifigan) return fail(ctx, TTS_ERR_STATE, "tts_load_hifigan not called");
+  if (!frame0 || !n_frames) return fail(ctx, TTS_ERR_ARG, "tts_hifigan_chunk: bad argument");
+  return hifigan_run(ctx, "tts_hifigan_chunk", latents, rows, B, voices, n_voices, voice_of, frame0, n_frames, audio_out);
 }
 
 } // namespace tts

@@ -790,6 +790,19 @@ int trimmed_latent_rows(const int32_t *codes502) {
   return 500;
 }
 
+// tts_hifigan_stream: latent row j is a function of the inputs 0 .. j (causal), input 0 is 8192 and input 1 + i the i-th sampled code; pad_codes rewrites from
+// the stop token onward, so after k sampled non-stop codes the rows 0 .. k are final. trim_latents cuts at the first run of more than 8 codes 83 and at 500
+// rows. A run the sampler itself produced counts, and the padding is 83s too: when the last 8 sampled codes are 83 and the utterance is cut here, the padding
+// completes the run and row k is trimmed, so it is not declared final yet.
+int stream_final_rows(const int32_t *codes, int k) {
+  int run = 0;
+  for (int c = 0; c < k && c < 500; c++) {
+    run = (codes[c] == 83) ? run + 1 : 0;
+    if (run > 8) return c;
+  }
+  return std::min(std::min(k + 1, k - run + 8), 500);
+}
+
 // get_relative_position_buckets, main.cpp:4722-4749 (i = query, c = key)
 int rel_bucket(int i, int c) {
   const int dist = std::abs(c - i);
