@@ -381,6 +381,55 @@ typedef int (*tts_audio_cb)(void *user, const float *samples, int n_samples, int
 int tts_hifigan_stream(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice1024, int max_steps, unsigned flags, int stride_codes,
                        tts_audio_cb cb, void *user, int32_t *codes_out /*[502]*/, int32_t *rows_out, float *latents_out /*may be NULL*/, int32_t *steps_out);
 int tts_hifigan_stream_recaptures(const tts_ctx *ctx);
+/* In-flight batching of the autoregressive stage (additions within version 8). A session is a batch of n_slots rows; a request (one prompt, one voice,
+ * n_cand candidates, its own seed) may join at any step and leave at any step, and everything it returns is bit for bit what
+ * tts_seed(seed) + tts_autoregressive(n_candidates = n_cand, max_steps, flags) returns for it alone.
+ * tts_ar_session_open: K/V caches for n_slots rows of max_text + 2 + max_steps + 1 positions and every buffer that the decode step, a prompt pass of
+ *   max_text + 2 rows and a latent pass of max_cand x 502 rows can touch: nothing the captured step bakes into its nodes moves while the session is open
+ *   (tts_ar_session_recaptures: decode-step graphs captured after the session's first step, 0). The step graph is kept for the next session of the same shape.
+ *   The options "ar_temperature", "ar_top_k", "ar_top_p", "ar_repetition_penalty", "ar_penalty_scope", "ar_weights", "ggml_lut" and "device_topk" are read
+ *   HERE and hold for the whole session: tts_set_option on an open session's context changes what later calls outside the session see, never the session.
+ *   flags: TTS_AR_MASK_STOP / TTS_AR_RETIRE with their tts_autoregressive meaning, for every request. Replaces any tts_ar_begin* state; a session that is
+ *   already open is closed first. TTS_ERR_ARG: n_slots < 1, max_cand outside 1 .. n_slots, max_text < 1, max_steps < 1, unknown flags; TTS_ERR_LIMIT:
+ *   max_text > 404, max_steps > 500, more than 1024 positions, more than 4096 slots.
+ *   While a session is open tts_ar_begin*, tts_ar_prefill, tts_ar_step*, tts_ar_latents, tts_autoregressive* and tts_hifigan_stream return TTS_ERR_STATE;
+ *   after tts_ar_session_close they behave exactly as before. No session call touches the context's generator.
+ * tts_ar_session_admit: the request takes the LOWEST contiguous run of n_cand free slots (first fit: tts_host_session_first_fit on the busy map returns the
+ *   run's first index or -1); without one, TTS_ERR_LIMIT and nothing changes (retry after a collect). Every argument is checked before any device work
+ *   (TTS_ERR_ARG: a null pointer, n_text < 1, n_cand < 1, an id outside 0 .. 255, a non-finite voice value, a stop_at entry < 1; TTS_ERR_LIMIT: n_text >
+ *   max_text, n_cand > max_cand). The call runs the request's prompt pass between two steps (the live rows wait for it: prompt passes are not chunked), resets
+ *   the request's penalty history and samples its first codes from the prompt pass's logits. The request owns a std::mt19937 seeded with `seed`, consumed as
+ *   tts_autoregressive consumes the context's after tts_seed(seed) with the rng_shard_* options unset: two uniforms per candidate and step, candidate order,
+ *   retired candidates included. stop_at [n_cand] (may be NULL): the request's tts_ar_set_stop_schedule, honoured only in a session opened with
+ *   TTS_AR_MASK_STOP | TTS_AR_RETIRE. Returns the request id (>= 0; ids are not reused within a session).
+ * tts_ar_session_room: the longest run of contiguous free slots.
+ * tts_ar_session_step: ONE replay of ONE captured graph over all n_slots rows: a live request's row is fed its previous sample at its own step i (mel
+ *   position i + 2, context n_text + 2 + i), then the host samples the live rows. Stop rule per request as tts_autoregressive's; a strict request that reaches
+ *   max_steps finishes with an error of its own (tts_ar_session_collect returns TTS_ERR_LIMIT for it) and no other request is affected. Returns the number of
+ *   live requests left (0 with none: nothing runs).
+ * tts_ar_session_finished: ids of the finished, not yet collected requests, oldest first (at most cap are written); returns their number.
+ * tts_ar_session_collect: a FINISHED request's results: what tts_autoregressive returns (codes_out [n_cand][502], rows_out [n_cand], latents_out: the
+ *   candidates' trimmed rows back to back, may be NULL; *steps_out, may be NULL) and what tts_ar_stop_status would (stopped_out [n_cand], may be NULL); then
+ *   the slots are free. A finished request keeps its slots, with its prompt's K/V rows intact, until it is collected or cancelled. TTS_ERR_ARG: an unknown id;
+ *   TTS_ERR_STATE: still running.
+ * tts_ar_session_logits: diagnostic: the request's rows of the last step's logits, from HBM ([n_cand][8194], unmasked).
+ * tts_ar_session_cancel: drops a running or finished request; its slots are free. tts_ar_session_close: drops everything.
+ * Every call on a host-only context returns TTS_ERR_HIP; a call that needs an open session returns TTS_ERR_STATE without one. */
+int tts_ar_session_open(tts_ctx *ctx, int n_slots, int max_cand, int max_text, int max_steps, unsigned flags);
+int tts_ar_session_admit(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice1024, int n_cand, uint32_t seed,
+                         const int32_t *stop_at /* [n_cand] or NULL */);
+int tts_ar_session_room(const tts_ctx *ctx);
+int tts_ar_session_step(tts_ctx *ctx);
+int tts_ar_session_finished(tts_ctx *ctx, int32_t *ids_out, int cap);
+int tts_ar_session_collect(tts_ctx *ctx, int request, int32_t *codes_out /*[n_cand][502]*/, int32_t *rows_out, float *latents_out /*may be NULL*/,
+                           int32_t *steps_out, int32_t *stopped_out /*[n_cand]*/);
+int tts_ar_session_logits(tts_ctx *ctx, int request, float *logits_out /*[n_cand][8194]*/);
+int tts_ar_session_cancel(tts_ctx *ctx, int request);
+int tts_ar_session_close(tts_ctx *ctx);
+int tts_ar_session_recaptures(const tts_ctx *ctx);
+/* host probe: the allocator's rule. busy [n_slots] (nonzero = taken): the first index of the lowest run of n_cand free slots, or -1 (also for a null map,
+ * n_slots < 1 or n_cand < 1). */
+int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand);
 /* One diffusion_graph evaluation (main.cpp:5749-5841 cond / 5866-5961 uncond): inputs
  * input_latent_tensor [L][1024], noise_tensor = x_t [100][T], timestep (raw 0..3999 value whose
  * sinusoidal embedding the reference uploads as time_embedding_{i}); conditioning_free as the

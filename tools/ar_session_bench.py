@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""In-flight batching against static batching on one arrival list, and what a session step costs against a plain step.
+
+Full-size synthetic weights (30 GPT-2 layers), one process, one loaded model, a fixed list of requests: text length, number of codes (through stop_at, with
+TTS_AR_MASK_STOP | TTS_AR_RETIRE) and arrival step. The clock of both schedulers is the decode step: a request "arrives" once that many steps have run.
+  (a) static batching: whatever has queued when the previous batch ends runs through tts_autoregressive_multi (at most --slots rows per batch, in arrival order);
+      a batch occupies the clock for as many steps as its longest request
+  (b) the session: tts_ar_session_admit as soon as a request has arrived and a run of free slots exists, tts_ar_session_collect as soon as it is finished
+For each: mean and 95th percentile of steps and of wall time from arrival to collected latents, and codes per second over the whole list. The wall time of a request
+is the host clock from the moment the scheduler's step counter reached its arrival step.
+  (c) a full session step (every slot live, all rows at the same step) alternated with tts_ar_step_sample at the same B: what the per-row block costs per step
+Host clock around synchronous calls; the two variants of (c) alternate in blocks, WARM untimed steps in front of each block, then the median and min .. max.
+
+  python tools/ar_session_bench.py [--slots 16] [--requests 24] [--seed 1] [--steps 200] [--warm 20] [--models DIR] [--out FILE]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import tortoise_cpp_amd_loader  # noqa: E402
+
+MAX_STEPS = 500
+
+
+def make_requests(n, seed):
+    """(text ids, n_cand, codes, arrival step): utterances of 60 .. 400 codes, prompts of 12 .. 200 ids, one candidate each, arrivals ~ one per 40 steps"""
+    rs = np.random.RandomState(seed)
+    out, t = [], 0
+    for k in range(n):
+        n_text = int(rs.randint(12, 201))
+        tok = np.concatenate([[255], rs.randint(1, 250, n_text - 2), [0]]).astype(np.int32)
+        out.append(dict(tokens=tok, n_cand=1, codes=int(rs.randint(60, 401)), at=t, seed=1000 + k))
+        t += int(rs.exponential(40.0))
+    return out
+
+
+def pct(xs, q):
+    xs = sorted(xs)
+    return xs[min(len(xs) - 1, int(np.ceil(q * len(xs))) - 1)]
+
+
+def static_batching(e, reqs, voice, slots):
+    clock, t_arr, done = 0, {}, {}
+    queue = list(range(len(reqs)))
+    t0 = time.perf_counter()
+    while queue:
+        if reqs[queue[0]]["at"] > clock:
+            clock = reqs[queue[0]]["at"]  # idle until the next arrival
+        now = time.perf_counter()
+        for k in queue:
+            if reqs[k]["at"] <= clock:
+                t_arr.setdefault(k, now)
+        batch = [k for k in queue if reqs[k]["at"] <= clock][:slots]
+        e.set_stop_schedule([reqs[k]["codes"] for k in batch])
+        e.seed(7)
+        _, _, _, steps = e.autoregressive_multi([reqs[k]["tokens"] for k in batch], voice, [1] * len(batch), MAX_STEPS, mask_stop=True, retire=True)
+        e.set_stop_schedule(None)
+        clock += steps
+        now = time.perf_counter()
+        for k in batch:
+            done[k] = (clock - reqs[k]["at"], now - t_arr[k])
+            queue.remove(k)
+    return done, time.perf_counter() - t0
+
+
+def session(e, reqs, voice, slots):
+    clock, t_arr, done, rid_of = 0, {}, {}, {}
+    queue = list(range(len(reqs)))
+    e.ar_session_open(slots, 1, max(len(r["tokens"]) for r in reqs), MAX_STEPS, mask_stop=True, retire=True)
+    t0 = time.perf_counter()
+    try:
+        while queue or rid_of:
+            now = time.perf_counter()
+            for k in queue:
+                if reqs[k]["at"] <= clock:
+                    t_arr.setdefault(k, now)
+            for rid in e.ar_session_finished():
+                k = rid_of.pop(rid)
+                e.ar_session_collect(rid)
+                done[k] = (clock - reqs[k]["at"], time.perf_counter() - t_arr[k])
+            while queue and reqs[queue[0]]["at"] <= clock and e.ar_session_room() >= reqs[queue[0]]["n_cand"]:
+                k = queue.pop(0)
+                rid_of[e.ar_session_admit(reqs[k]["tokens"], voice, 1, reqs[k]["seed"], [reqs[k]["codes"]])] = k
+            if rid_of:
+                e.ar_session_step()
+                clock += 1
+            elif queue:
+                clock = max(clock, reqs[queue[0]]["at"])
+    finally:
+        e.ar_session_close()
+    return done, time.perf_counter() - t0
+
+
+def step_cost(e, voice, B, steps, warm, rounds=4):
+    """blocks of tts_ar_step_sample steps and of session steps with every slot live, alternated (a session excludes tts_ar_step* while it is open, so the
+    alternation is by block, not by step); every block starts from a fresh begin / a fresh session, so both run the same context lengths"""
+    tok = np.concatenate([[255], np.arange(1, 15), [0]]).astype(np.int32)
+    n = max(1, steps // rounds)
+    ts, tp = [], []
+    for _ in range(rounds):
+        e.ar_begin(tok, voice, B, warm + n + 1)
+        e.ar_prefill()
+        prev = np.full(B, 100, np.int32)
+        for i in range(warm + n):
+            t0 = time.perf_counter()
+            prev = e.ar_step_sample(prev, i, mask_stop=True)
+            t1 = time.perf_counter()
+            if i >= warm:
+                tp.append((t1 - t0) * 1e3)
+        e.ar_session_open(B, 1, len(tok), warm + n + 2, mask_stop=True, retire=True)
+        try:
+            for b in range(B):
+                e.ar_session_admit(tok, voice, 1, b, None)
+            for i in range(warm + n):
+                t0 = time.perf_counter()
+                e.ar_session_step()
+                t1 = time.perf_counter()
+                if i >= warm:
+                    ts.append((t1 - t0) * 1e3)
+        finally:
+            e.ar_session_close()
+    return tp, ts
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--slots", type=int, default=16)
+    ap.add_argument("--requests", type=int, default=24)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warm", type=int, default=20)
+    ap.add_argument("--models", default=os.environ.get("TTS_BENCH_MODELS", "/tmp/tts_bench_models"))
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    pkg = tortoise_cpp_amd_loader.load()
+    from tortoise_cpp_amd import synth_weights as sw
+    os.makedirs(a.models, exist_ok=True)
+    ar_path = os.path.join(a.models, "ggml-model.bin")
+    if not os.path.exists(ar_path):
+        sw.write_ar(ar_path, 30, seed=1234)
+    e = pkg.Engine(0)
+    e.load(ar=ar_path)
+    voice = np.fromfile(os.path.join(ROOT, "models", "mol.bin"), np.float32)
+    reqs = make_requests(a.requests, a.seed)
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    say("tools/ar_session_bench.py: %d requests (seed %d), %d slots, codes %d .. %d, arrivals over %d steps" %
+        (len(reqs), a.seed, a.slots, min(r["codes"] for r in reqs), max(r["codes"] for r in reqs), reqs[-1]["at"]))
+    total_codes = sum(r["codes"] for r in reqs)
+    for name, fn in (("warm-up (untimed)", static_batching), ("(a) static batching", static_batching), ("(b) session", session)):
+        done, wall = fn(e, reqs, voice, a.slots)
+        if name.startswith("warm"):
+            continue
+        st, wt = [d[0] for d in done.values()], [d[1] * 1e3 for d in done.values()]
+        say("%-20s arrival -> latents: steps mean %7.1f p95 %5d | wall mean %8.1f ms p95 %8.1f ms | %7.1f codes/s (%.2f s in all)" %
+            (name, statistics.mean(st), pct(st, 0.95), statistics.mean(wt), pct(wt, 0.95), total_codes / wall, wall))
+    tp, ts = step_cost(e, voice, a.slots, a.steps, a.warm)
+    say("(c) B = %d, %d steps each, every row live at the same step (host clock around the synchronous call):" % (a.slots, a.steps))
+    say("    tts_ar_step_sample   median %.3f ms (min %.3f .. max %.3f)" % (statistics.median(tp), min(tp), max(tp)))
+    say("    tts_ar_session_step  median %.3f ms (min %.3f .. max %.3f)" % (statistics.median(ts), min(ts), max(ts)))
+    e.close()
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n" + "\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

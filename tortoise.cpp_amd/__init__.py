@@ -81,6 +81,11 @@ def lib():
         "tts_hifigan_chunk": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp]),
         "tts_hifigan_stream": (ci, [vp, vp, ci, vp, ci, C.c_uint, ci, vp, vp, vp, vp, vp, vp]), "tts_hifigan_stream_recaptures": (ci, [vp]),
         "tts_host_stream_final_rows": (ci, [vp, ci]),
+        "tts_ar_session_open": (ci, [vp, ci, ci, ci, ci, C.c_uint]), "tts_ar_session_admit": (ci, [vp, vp, ci, vp, ci, C.c_uint32, vp]),
+        "tts_ar_session_room": (ci, [vp]), "tts_ar_session_step": (ci, [vp]), "tts_ar_session_finished": (ci, [vp, vp, ci]),
+        "tts_ar_session_collect": (ci, [vp, ci, vp, vp, vp, vp, vp]), "tts_ar_session_logits": (ci, [vp, ci, vp]),
+        "tts_ar_session_cancel": (ci, [vp, ci]), "tts_ar_session_close": (ci, [vp]), "tts_ar_session_recaptures": (ci, [vp]),
+        "tts_host_session_first_fit": (ci, [vp, ci, ci]),
         "tts_diffusion_forward": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p]),
         "tts_diffusion": (ci, [vp, _f32p, _i32p, ci, ci, vp, ci, _f32p]),
         "tts_vocoder_samples": (ci, [ci]),
@@ -327,6 +332,75 @@ class Engine:
         out = np.zeros(B, np.int32)
         self._ck(self.L.tts_ar_stop_status(self.h, out, B))
         return out
+
+    # ---- in-flight batching: requests join and leave a running batch (tts_ar_session_*) ----
+    def ar_session_open(self, n_slots, max_cand, max_text, max_steps, mask_stop=False, retire=False):
+        """A batch of n_slots rows that requests of up to max_cand candidates and max_text ids join and leave at any step. The sampler controls, ar_weights,
+        ggml_lut and device_topk are read here and hold until ar_session_close()."""
+        self._ck(self.L.tts_ar_session_open(self.h, n_slots, max_cand, max_text, max_steps, (AR_MASK_STOP if mask_stop else 0) | (AR_RETIRE if retire else 0)))
+        self._session_cand = {}
+
+    def ar_session_admit(self, tokens, voice, n_cand, seed, stop_at=None):
+        """Admits a request into the lowest run of n_cand free slots and returns its id; TtsError (status -6) when there is no such run."""
+        tok = np.ascontiguousarray(tokens, np.int32)
+        v = np.ascontiguousarray(voice, np.float32)
+        sa = None if stop_at is None else np.ascontiguousarray(stop_at, np.int32)
+        if v.size != DMODEL or (sa is not None and len(sa) != n_cand):
+            raise ValueError("voice [1024]; stop_at [n_cand]")
+        rid = self._ck(self.L.tts_ar_session_admit(self.h, _ptr(tok), len(tok), _ptr(v), n_cand, seed, _ptr(sa)))
+        self._session_cand[rid] = n_cand
+        return rid
+
+    def ar_session_room(self):
+        return self._ck(self.L.tts_ar_session_room(self.h))
+
+    def ar_session_step(self):
+        """One decode step for every live row; returns the number of live requests left."""
+        return self._ck(self.L.tts_ar_session_step(self.h))
+
+    def ar_session_finished(self):
+        """Ids of the finished, not yet collected requests, oldest first."""
+        out = np.zeros(max(1, len(self._session_cand)), np.int32)
+        n = self._ck(self.L.tts_ar_session_finished(self.h, _ptr(out), len(out)))
+        return [int(x) for x in out[:min(n, len(out))]]
+
+    def ar_session_collect(self, request, want_latents=True):
+        """A finished request's (codes [n_cand,502], rows [n_cand], list of trimmed latents, steps, stopped [n_cand]); its slots are free afterwards."""
+        B = self._session_cand[request]
+        codes = np.empty((B, 502), np.int32)
+        rows = np.empty(B, np.int32)
+        steps = np.zeros(1, np.int32)
+        stopped = np.zeros(B, np.int32)
+        lat = np.empty((B * 500, DMODEL), np.float32) if want_latents else None
+        rc = self.L.tts_ar_session_collect(self.h, request, _ptr(codes), _ptr(rows), _ptr(lat), _ptr(steps), _ptr(stopped))
+        if rc == -6:  # a strict request that reached max_steps: gone, its slots are free
+            self._session_cand.pop(request, None)
+        self._ck(rc)
+        self._session_cand.pop(request, None)
+        lats = None
+        if want_latents:
+            lats, off = [], 0
+            for r in rows:
+                lats.append(lat[off:off + r].copy())
+                off += r
+        return codes, rows, lats, int(steps[0]), stopped
+
+    def ar_session_logits(self, request):
+        """Diagnostic: the request's rows of the last step's logits [n_cand, 8194]."""
+        out = np.empty((self._session_cand[request], VOCAB_MEL), np.float32)
+        self._ck(self.L.tts_ar_session_logits(self.h, request, _ptr(out)))
+        return out
+
+    def ar_session_cancel(self, request):
+        self._ck(self.L.tts_ar_session_cancel(self.h, request))
+        self._session_cand.pop(request, None)
+
+    def ar_session_close(self):
+        self._ck(self.L.tts_ar_session_close(self.h))
+        self._session_cand = {}
+
+    def ar_session_recaptures(self):
+        return self._ck(self.L.tts_ar_session_recaptures(self.h))
 
     # ---- voice-conditioning encoder (not in the reference) ----
     def load_voice_encoder(self, path):
@@ -618,6 +692,12 @@ def host_ar_stop_run(n_cand, samples, max_steps, flags=0, stop_at=None):
     inputs = np.full((max_steps, B), -1, np.int32)
     rc = lib().tts_host_ar_stop_run(nc, len(nc), smp.reshape(-1), max_steps, flags, _ptr(sa), codes.reshape(-1), stopped, steps, _ptr(inputs))
     return rc, codes, stopped, int(steps[0]), inputs
+
+
+def host_session_first_fit(busy, n_cand):
+    """The session allocator's rule: the first index of the lowest run of n_cand free slots of the busy map, or -1."""
+    b = np.ascontiguousarray(busy, np.uint8)
+    return lib().tts_host_session_first_fit(_ptr(b), len(b), n_cand)
 
 
 def host_trimmed_rows(codes502):

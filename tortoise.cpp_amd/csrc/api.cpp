@@ -14,6 +14,13 @@ int ar_begin_groups(tts_ctx *, const int32_t *, const int *, int, const float *,
 int ar_latents_group(tts_ctx *, int, const int32_t *, int, float *);
 int ar_stream_reserve(tts_ctx *, int n_mel);
 int ar_graph_captures(const tts_ctx *);
+int ar_session_open(tts_ctx *, int n_slots, int max_cand, int max_text, int max_steps);
+void ar_session_close(tts_ctx *);
+int ar_session_prompt(tts_ctx *, int c0, int n_cand, const int32_t *text_ids, int n_text, const float *voice, float *logits_row);
+int ar_session_step(tts_ctx *, const int32_t *toks, const int32_t *n_past, const int32_t *pos_id, const char *live, int mode);
+int ar_session_recaptures(const tts_ctx *);
+int ar_session_latents(tts_ctx *, int c0, int n_text, const int32_t *codes502, int nb, int n_mel, float *out);
+int ar_session_logits(tts_ctx *, int c0, int n, float *out);
 int ar_prefill(tts_ctx *, float *);
 int ar_step(tts_ctx *, const int32_t *, int, float *, int mode);
 const int32_t *ar_host_lists(tts_ctx *);
@@ -30,7 +37,69 @@ int diff_sample_voices(tts_ctx *, const float *, const int32_t *, int, const flo
 int voc_run(tts_ctx *, const float *, const int32_t *, int, const float *, int, float *);
 } // namespace tts
 
+// The book of an open session (tts_ar_session_*): which slots are taken, and per request what tts_autoregressive keeps in its locals for one call.
+namespace tts {
+struct SessionRequest {
+  int id = 0, c0 = 0, n_cand = 0, n_text = 0;
+  std::mt19937 gen;              // seeded at admission: tts_autoregressive's stream after tts_seed(seed)
+  ArStopBook book;               // one group
+  std::vector<int32_t> stop_at;  // the request's stop schedule (empty: none)
+  std::vector<int32_t> samples;  // the tokens the next step feeds (after ArStopBook::step)
+  int i = 0;                     // tts_autoregressive's loop counter: iterations applied so far
+  int state = 0;                 // 0 running, 1 finished, 2 finished by reaching max_steps in strict mode (collect returns TTS_ERR_LIMIT)
+};
+struct ArSession {
+  int n_slots = 0, max_cand = 0, max_text = 0, max_steps = 0;
+  unsigned flags = 0;
+  // the options read once at tts_ar_session_open: every session call runs under them (SessionOptions), whatever tts_set_option has stored since
+  SamplerParams sp;
+  int scope = 0, ar_weights = 0, ggml_lut = 0, device_topk = 1;
+  std::vector<uint8_t> busy;
+  std::map<int, SessionRequest> reqs;
+  std::vector<int> finished; // ids, oldest first
+  int next_id = 0;
+};
+} // namespace tts
+
 using namespace tts;
+
+namespace {
+struct SessionOptions { // puts the session's options into the context for the length of one call
+  tts_ctx *c;
+  SamplerParams sp;
+  int scope, w, lut, topk;
+  SessionOptions(tts_ctx *ctx, const ArSession &s) : c(ctx), sp(ctx->ar_sp), scope(ctx->ar_penalty_scope), w(ctx->ar_weights), lut(ctx->ggml_lut), topk(ctx->device_topk) {
+    c->ar_sp = s.sp; c->ar_penalty_scope = s.scope; c->ar_weights = s.ar_weights; c->ggml_lut = s.ggml_lut; c->device_topk = s.device_topk;
+  }
+  ~SessionOptions() { c->ar_sp = sp; c->ar_penalty_scope = scope; c->ar_weights = w; c->ggml_lut = lut; c->device_topk = topk; }
+};
+// first fit: the first index of the lowest run of n_cand free slots, or -1
+int session_first_fit(const uint8_t *busy, int n_slots, int n_cand) {
+  int run = 0;
+  for (int i = 0; i < n_slots; i++) {
+    run = busy[i] ? 0 : run + 1;
+    if (run == n_cand) return i - n_cand + 1;
+  }
+  return -1;
+}
+void session_release(ArSession &s, int id) {
+  auto it = s.reqs.find(id);
+  if (it == s.reqs.end()) return;
+  std::fill(s.busy.begin() + it->second.c0, s.busy.begin() + it->second.c0 + it->second.n_cand, (uint8_t)0);
+  s.finished.erase(std::remove(s.finished.begin(), s.finished.end(), id), s.finished.end());
+  s.reqs.erase(it);
+}
+// One iteration of tts_autoregressive's loop from the samples on: the stop rule, then the loop's two exits.
+void session_advance(ArSession &s, SessionRequest &r) {
+  const bool retire = (s.flags & TTS_AR_RETIRE) != 0;
+  const bool sched = !r.stop_at.empty() && (s.flags & TTS_AR_MASK_STOP) && retire;
+  const bool all_ended = r.book.step(r.samples.data(), r.i, retire, sched ? r.stop_at.data() : nullptr);
+  r.i++;
+  if (all_ended) r.state = 1;
+  else if (r.i >= s.max_steps) r.state = ((s.flags & TTS_AR_MASK_STOP) || retire) ? 1 : 2;
+  if (r.state) s.finished.push_back(r.id);
+}
+} // namespace
 
 hipEvent_t tts::prof_event(tts_ctx *c) {
   if (!c->ev_pool.empty()) { hipEvent_t e = c->ev_pool.back(); c->ev_pool.pop_back(); return e; }
@@ -130,6 +199,7 @@ int tts_pin_to_device_numa_node(tts_ctx *c) {
 void tts_destroy(tts_ctx *c) {
   if (!c) return;
   if (c->sampler_pool) sampler_pool_free(c->sampler_pool);
+  delete c->session;
   if (c->device < 0) { delete c->tok; delete c; return; }
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
@@ -274,7 +344,13 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     (void)hipSetDevice((c)->device);                                                           \
   } while (0)
 
-int tts_load_ar(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return ar_load(c, path); }); }
+// While a session is open (tts_ar_session_open) the AR state is the session's: the single-call entry points refuse.
+#define NO_SESSION(c, name)                                                                                          \
+  do {                                                                                                               \
+    if ((c)->session) return fail((c), TTS_ERR_STATE, "%s: a session is open (tts_ar_session_close first)", name); \
+  } while (0)
+
+int tts_load_ar(tts_ctx *c, const char *path) { NEED_CTX(c); NO_SESSION(c, "tts_load_ar"); return guarded(c, [&] { return ar_load(c, path); }); }
 int tts_load_diffusion(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return diff_load(c, path); }); }
 int tts_load_vocoder(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return voc_load(c, path); }); }
 int tts_load_diffusion_conditioning_encoder(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return diff_cond_enc_load(c, path); }); }
@@ -362,11 +438,13 @@ int tts_tokenize(tts_ctx *c, const char *message, int32_t *out, int cap) {
 
 int tts_ar_begin(tts_ctx *c, const int32_t *ids, int n, const float *voice, int B, int max_steps) {
   NEED_CTX(c);
+  NO_SESSION(c, "tts_ar_begin");
   return guarded(c, [&] { return ar_begin(c, ids, n, voice, B, max_steps); });
 }
-int tts_ar_prefill(tts_ctx *c, float *logits) { NEED_CTX(c); return guarded(c, [&] { return ar_prefill(c, logits); }); }
+int tts_ar_prefill(tts_ctx *c, float *logits) { NEED_CTX(c); NO_SESSION(c, "tts_ar_prefill"); return guarded(c, [&] { return ar_prefill(c, logits); }); }
 int tts_ar_step(tts_ctx *c, const int32_t *prev, int i, float *logits) {
   NEED_CTX(c);
+  NO_SESSION(c, "tts_ar_step");
   return guarded(c, [&] { return ar_step(c, prev, i, logits, 0); });
 }
 // decode step + sampler in one call: the device prefilter's lists cross PCIe instead of the logits (ar.hip: sample_prefilter_kernel)
@@ -379,12 +457,13 @@ static int step_sample(tts_ctx *c, const int32_t *prev, int i, bool mask_stop, i
     if (scope1) { ar_history_ids(c, b, hist); p = hist.data(); n = (int)hist.size(); }
     else { p = prev + b; n = 1; }
   };
-  if (sample_candidates_list(c, ar_host_lists(c), ids_of, scope1, B, out, [&](int b) { return ar_fetch_logits_row(c, b); }, fallbacks))
+  if (sample_candidates_list(c, c->generator, ar_host_lists(c), ids_of, scope1, B, out, [&](int b) { return ar_fetch_logits_row(c, b); }, fallbacks))
     return fail(c, TTS_ERR_HIP, "tts_ar_step_sample: fetching a logits row failed");
   return TTS_OK;
 }
 int tts_ar_step_sample(tts_ctx *c, const int32_t *prev, int i, unsigned flags, int32_t *samples_out) {
   NEED_CTX(c);
+  NO_SESSION(c, "tts_ar_step_sample");
   if (!prev || !samples_out) return TTS_ERR_ARG;
   return guarded(c, [&] {
     if (ar_batch(c) < 1) return fail(c, TTS_ERR_STATE, "tts_ar_begin not called"); // before the shard check: with no AR state the batch is 0
@@ -436,6 +515,7 @@ int tts_host_sample_prefiltered(const float *row, const int32_t *ids, int ids_pe
 }
 int tts_ar_latents(tts_ctx *c, const int32_t *codes, int nb, int n_mel, float *out) {
   NEED_CTX(c);
+  NO_SESSION(c, "tts_ar_latents");
   return guarded(c, [&] { return ar_latents(c, codes, nb, n_mel, out); });
 }
 int tts_sample(tts_ctx *c, const float *logits, const int32_t *ids, int ids_per_cand, int B, int32_t *out) {
@@ -443,7 +523,7 @@ int tts_sample(tts_ctx *c, const float *logits, const int32_t *ids, int ids_per_
   for (int i = 0; i < B * ids_per_cand; i++)
     if (ids[i] < 0 || ids[i] >= TTS_VOCAB_MEL) return fail(c, TTS_ERR_ARG, "penalty id out of range");
   if (int rc = shard_check(c, B)) return rc;
-  return guarded(c, [&] { sample_candidates(c, logits, ids, ids_per_cand, B, out); return (int)TTS_OK; });
+  return guarded(c, [&] { sample_candidates(c, c->generator, logits, ids, ids_per_cand, B, out); return (int)TTS_OK; });
 }
 
 // autoregressive(), main.cpp:5042-5367, for G prompt groups in one decode loop (tts_autoregressive: G = 1; tts_autoregressive_multi). Group g's
@@ -553,9 +633,9 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
         for (int b = 0; b < B; b++) logits[(size_t)b * V + 8193] = -1e30f;
       if (scope1 && i > 0) {
         for (int b = 0; b < B; b++) ar_history_ids(c, b, hist[b]);
-        sample_candidates(c, logits, [&](int b, const int32_t *&p, int &n) { p = hist[b].data(); n = (int)hist[b].size(); }, B, samples.data());
+        sample_candidates(c, c->generator, logits, [&](int b, const int32_t *&p, int &n) { p = hist[b].data(); n = (int)hist[b].size(); }, B, samples.data());
       } else
-        sample_candidates(c, logits, ids.data(), ids_per_cand, B, samples.data());
+        sample_candidates(c, c->generator, logits, ids.data(), ids_per_cand, B, samples.data());
       t_sample += now() - t0;
     }
     const bool all_ended = book.step(samples.data(), i, retire, sched ? c->stop_schedule.data() : nullptr);
@@ -593,7 +673,7 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
       if (scope1) { ar_history_ids(c, b, hist_one); p = hist_one.data(); n = (int)hist_one.size(); }
       else { p = ids.data() + b; n = 1; }
     };
-    if (sample_candidates_list(c, ar_host_lists(c), ids_of, scope1, B, next.data(), [&](int b) { return ar_fetch_logits_row(c, b); }, &c->topk_fallbacks,
+    if (sample_candidates_list(c, c->generator, ar_host_lists(c), ids_of, scope1, B, next.data(), [&](int b) { return ar_fetch_logits_row(c, b); }, &c->topk_fallbacks,
                                book.retired.data()))
       return fail(c, TTS_ERR_HIP, "tts_autoregressive: fetching a logits row failed");
     t_sample += now() - t0;
@@ -645,6 +725,7 @@ static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n
 int tts_autoregressive(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, int B, int max_steps,
                        unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
   NEED_CTX(c);
+  NO_SESSION(c, "tts_autoregressive");
   return guarded(c, [&] {
     return autoregressive_impl(c, text_ids, &n_text, 1, voice, 1, nullptr, &B, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
   });
@@ -653,6 +734,7 @@ int tts_autoregressive(tts_ctx *c, const int32_t *text_ids, int n_text, const fl
 int tts_hifigan_stream(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, int max_steps, unsigned flags, int stride_codes, tts_audio_cb cb,
                        void *user, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
   NEED_CTX(c);
+  NO_SESSION(c, "tts_hifigan_stream");
   if (stride_codes < 1 || !cb) return fail(c, TTS_ERR_ARG, "tts_hifigan_stream: bad argument (stride_codes %d: >= 1, a callback)", stride_codes);
   if (!c->ar) return fail(c, TTS_ERR_STATE, "AR model not loaded");
   if (!c->hifigan) return fail(c, TTS_ERR_STATE, "tts_load_hifigan not called");
@@ -669,6 +751,7 @@ int tts_hifigan_stream(tts_ctx *c, const int32_t *text_ids, int n_text, const fl
 int tts_autoregressive_multi(tts_ctx *c, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voice, const int32_t *n_cand, int max_steps,
                              unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
   NEED_CTX(c);
+  NO_SESSION(c, "tts_autoregressive_multi");
   if (n_prompts < 1 || !n_text || !n_cand) return fail(c, TTS_ERR_ARG, "tts_autoregressive_multi: bad argument");
   return guarded(c, [&] {
     return autoregressive_impl(c, text_ids, n_text, n_prompts, voice, 1, nullptr, n_cand, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
@@ -677,6 +760,7 @@ int tts_autoregressive_multi(tts_ctx *c, const int32_t *text_ids, const int32_t 
 
 int tts_ar_begin_multi(tts_ctx *c, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voice, const int32_t *n_cand, int max_steps) {
   NEED_CTX(c);
+  NO_SESSION(c, "tts_ar_begin_multi");
   if (n_prompts < 1 || !n_text || !n_cand) return fail(c, TTS_ERR_ARG, "tts_ar_begin_multi: bad argument");
   return guarded(c, [&] { return ar_begin_groups(c, text_ids, n_text, n_prompts, voice, 1, nullptr, n_cand, max_steps); });
 }
@@ -685,6 +769,7 @@ int tts_ar_begin_multi(tts_ctx *c, const int32_t *text_ids, const int32_t *n_tex
 int tts_ar_begin_multi_voice(tts_ctx *c, const int32_t *text_ids, const int32_t *n_text, int n_prompts, const float *voices, int n_voices,
                              const int32_t *voice_of_prompt, const int32_t *n_cand, int max_steps) {
   NEED_CTX(c);
+  NO_SESSION(c, "tts_ar_begin_multi_voice");
   if (n_prompts < 1 || !n_text || !n_cand || !voices || !voice_of_prompt || n_voices < 1) return fail(c, TTS_ERR_ARG, "tts_ar_begin_multi_voice: bad argument");
   return guarded(c, [&] { return ar_begin_groups(c, text_ids, n_text, n_prompts, voices, n_voices, voice_of_prompt, n_cand, max_steps); });
 }
@@ -693,6 +778,7 @@ int tts_autoregressive_multi_voice(tts_ctx *c, const int32_t *text_ids, const in
                                    const int32_t *voice_of_prompt, const int32_t *n_cand, int max_steps, unsigned flags, int32_t *codes_out, int32_t *rows_out,
                                    float *latents_out, int32_t *steps_out) {
   NEED_CTX(c);
+  NO_SESSION(c, "tts_autoregressive_multi_voice");
   if (n_prompts < 1 || !n_text || !n_cand || !voices || !voice_of_prompt || n_voices < 1)
     return fail(c, TTS_ERR_ARG, "tts_autoregressive_multi_voice: bad argument");
   return guarded(c, [&] {
@@ -742,6 +828,233 @@ int tts_ar_stop_status(tts_ctx *c, int32_t *stopped_out, int n_candidates) {
   if (!c || !stopped_out || n_candidates < 1) return TTS_ERR_ARG;
   if ((int)c->ar_stopped.size() != n_candidates) return fail(c, TTS_ERR_STATE, "tts_ar_stop_status: the last tts_autoregressive call had %d candidates", (int)c->ar_stopped.size());
   std::copy(c->ar_stopped.begin(), c->ar_stopped.end(), stopped_out);
+  return TTS_OK;
+}
+
+// ---- in-flight batching (include/tortoise_mi355x.h: tts_ar_session_*) ----
+int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand) {
+  if (!busy || n_slots < 1 || n_cand < 1) return -1;
+  return session_first_fit(busy, n_slots, n_cand);
+}
+
+#define NEED_SESSION(c, name)                                                                       \
+  do {                                                                                              \
+    if (!(c)->session) return fail((c), TTS_ERR_STATE, "%s: tts_ar_session_open not called", name); \
+  } while (0)
+
+int tts_ar_session_close(tts_ctx *c) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_close");
+  delete c->session;
+  c->session = nullptr;
+  ar_session_close(c);
+  return TTS_OK;
+}
+
+int tts_ar_session_open(tts_ctx *c, int n_slots, int max_cand, int max_text, int max_steps, unsigned flags) {
+  NEED_CTX(c);
+  if (!c->ar) return fail(c, TTS_ERR_STATE, "AR model not loaded");
+  if (n_slots < 1 || max_cand < 1 || max_cand > n_slots || max_text < 1 || max_steps < 1 || (flags & ~(unsigned)(TTS_AR_MASK_STOP | TTS_AR_RETIRE)))
+    return fail(c, TTS_ERR_ARG, "tts_ar_session_open: bad argument (n_slots %d: >= 1, max_cand %d: 1 .. n_slots, max_text %d, max_steps %d: >= 1, flags %u)", n_slots,
+                max_cand, max_text, max_steps, flags);
+  if (n_slots > 4096) return fail(c, TTS_ERR_LIMIT, "tts_ar_session_open: %d slots, at most 4096", n_slots);
+  if (max_text > 404) return fail(c, TTS_ERR_LIMIT, "text of %d ids; the model has 404 text positions", max_text);
+  if (max_steps > 500) return fail(c, TTS_ERR_LIMIT, "max_steps %d exceeds the 500 codes apply_padding accepts", max_steps);
+  if (max_text + 2 + max_steps + 1 > 1024) return fail(c, TTS_ERR_LIMIT, "context of %d positions exceeds 1024", max_text + 2 + max_steps + 1);
+  return guarded(c, [&] {
+    if (c->session) { delete c->session; c->session = nullptr; ar_session_close(c); }
+    std::unique_ptr<ArSession> s(new ArSession());
+    s->n_slots = n_slots; s->max_cand = max_cand; s->max_text = max_text; s->max_steps = max_steps; s->flags = flags;
+    s->sp = c->ar_sp; s->scope = c->ar_penalty_scope; s->ar_weights = c->ar_weights; s->ggml_lut = c->ggml_lut; s->device_topk = c->device_topk;
+    s->busy.assign((size_t)n_slots, 0);
+    if (int rc = ar_session_open(c, n_slots, max_cand, max_text, max_steps)) return rc;
+    c->topk_fallbacks = 0;
+    c->session = s.release();
+    return (int)TTS_OK;
+  });
+}
+
+int tts_ar_session_room(const tts_ctx *c) {
+  if (!c) return TTS_ERR_ARG;
+  if (c->device < 0) return TTS_ERR_HIP;
+  if (!c->session) return TTS_ERR_STATE;
+  int best = 0, run = 0;
+  for (uint8_t b : c->session->busy) { run = b ? 0 : run + 1; best = std::max(best, run); }
+  return best;
+}
+
+int tts_ar_session_recaptures(const tts_ctx *c) {
+  if (!c) return TTS_ERR_ARG;
+  if (c->device < 0) return TTS_ERR_HIP;
+  if (!c->session) return TTS_ERR_STATE;
+  return ar_session_recaptures(c);
+}
+
+int tts_ar_session_admit(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, int n_cand, uint32_t seed, const int32_t *stop_at) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_admit");
+  ArSession &s = *c->session;
+  // every argument before any device work
+  if (!text_ids || !voice || n_text < 1 || n_cand < 1) return fail(c, TTS_ERR_ARG, "tts_ar_session_admit: bad argument (%d ids, %d candidates)", n_text, n_cand);
+  if (n_text > s.max_text) return fail(c, TTS_ERR_LIMIT, "tts_ar_session_admit: %d ids, the session was opened for %d", n_text, s.max_text);
+  if (n_cand > s.max_cand) return fail(c, TTS_ERR_LIMIT, "tts_ar_session_admit: %d candidates, the session was opened for %d", n_cand, s.max_cand);
+  for (int i = 0; i < n_text; i++)
+    if (text_ids[i] < 0 || text_ids[i] >= 256) return fail(c, TTS_ERR_ARG, "text id %d out of range", text_ids[i]);
+  for (int i = 0; i < TTS_DMODEL; i++)
+    if (!std::isfinite(voice[i])) return fail(c, TTS_ERR_ARG, "tts_ar_session_admit: the voice holds a non-finite value");
+  if (stop_at)
+    for (int b = 0; b < n_cand; b++)
+      if (stop_at[b] < 1) return fail(c, TTS_ERR_ARG, "tts_ar_session_admit: candidate %d would stop before its first code", b);
+  const int c0 = session_first_fit(s.busy.data(), s.n_slots, n_cand);
+  if (c0 < 0) return fail(c, TTS_ERR_LIMIT, "tts_ar_session_admit: no run of %d free slots (collect a finished request first)", n_cand);
+  return guarded(c, [&] {
+    SessionOptions opt(c, s);
+    const int V = TTS_VOCAB_MEL, P = n_text + 2;
+    std::vector<float> row((size_t)V);
+    if (int rc = ar_session_prompt(c, c0, n_cand, text_ids, n_text, voice, row.data())) return rc;
+    SessionRequest r;
+    r.id = s.next_id; r.c0 = c0; r.n_cand = n_cand; r.n_text = n_text;
+    r.gen.seed(seed);
+    r.book.init(&n_cand, 1);
+    if (stop_at) r.stop_at.assign(stop_at, stop_at + n_cand);
+    // tts_autoregressive's iteration 0: every candidate samples from the prompt's logits under the prompt-shaped penalty row [1 ... 1, 8192]
+    if (s.flags & TTS_AR_MASK_STOP) row[8193] = -1e30f;
+    std::vector<float> logits0((size_t)n_cand * V);
+    for (int b = 0; b < n_cand; b++) std::copy(row.begin(), row.end(), logits0.begin() + (size_t)b * V);
+    std::vector<int32_t> ids((size_t)P * n_cand, 1);
+    for (int b = 0; b < n_cand; b++) ids[(size_t)b * P + P - 1] = 8192;
+    r.samples.resize(n_cand);
+    sample_candidates(c, r.gen, logits0.data(), ids.data(), P, n_cand, r.samples.data());
+    std::fill(s.busy.begin() + c0, s.busy.begin() + c0 + n_cand, (uint8_t)1);
+    SessionRequest &slot = s.reqs[r.id] = std::move(r);
+    s.next_id++;
+    session_advance(s, slot);
+    return slot.id;
+  });
+}
+
+int tts_ar_session_step(tts_ctx *c) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_step");
+  ArSession &s = *c->session;
+  return guarded(c, [&] {
+    int n_live = 0;
+    for (auto &kv : s.reqs) n_live += kv.second.state == 0;
+    if (n_live == 0) return 0;
+    SessionOptions opt(c, s);
+    const int V = TTS_VOCAB_MEL;
+    // An empty slot sits at position 0. A finished request's rows are parked at position n_text + 2, the first mel position that its latent pass recomputes
+    // anyway: its prompt's K/V rows [0, n_text + 1) stay as the prompt pass wrote them until the request is collected, and the row reads written memory only.
+    std::vector<int32_t> toks((size_t)s.n_slots, 8193), n_past((size_t)s.n_slots, 0), pos((size_t)s.n_slots, 0);
+    std::vector<char> live((size_t)s.n_slots, 0);
+    for (auto &kv : s.reqs) {
+      const SessionRequest &r = kv.second;
+      for (int b = 0; b < r.n_cand; b++) {
+        const int k = r.c0 + b;
+        if (r.state == 0) { toks[k] = r.samples[b]; n_past[k] = r.n_text + 2 + (r.i - 1); pos[k] = (r.i - 1) + 2; live[k] = 1; }
+        else { n_past[k] = r.n_text + 2; pos[k] = 2; }
+      }
+    }
+    const bool mask = (s.flags & TTS_AR_MASK_STOP) != 0, scope1 = s.scope == 1;
+    const int mode = s.device_topk ? (mask ? 2 : 1) : 0;
+    if (int rc = ar_session_step(c, toks.data(), n_past.data(), pos.data(), live.data(), mode)) return rc;
+    std::vector<std::vector<int32_t>> hist;
+    std::vector<int32_t> hist_one, next;
+    for (auto &kv : s.reqs) {
+      SessionRequest &r = kv.second;
+      if (r.state != 0) continue;
+      next.assign((size_t)r.n_cand, 0);
+      if (mode == 0) { // the full rows, as tts_autoregressive with device_topk = 0
+        float *logits = ar_host_logits(c) + (size_t)r.c0 * V;
+        if (mask)
+          for (int b = 0; b < r.n_cand; b++) logits[(size_t)b * V + 8193] = -1e30f;
+        if (scope1) {
+          hist.resize((size_t)r.n_cand);
+          for (int b = 0; b < r.n_cand; b++) ar_history_ids(c, r.c0 + b, hist[b]);
+          sample_candidates(c, r.gen, logits, [&](int b, const int32_t *&p, int &n) { p = hist[b].data(); n = (int)hist[b].size(); }, r.n_cand, next.data());
+        } else
+          sample_candidates(c, r.gen, logits, r.samples.data(), 1, r.n_cand, next.data());
+      } else {
+        const PenaltyIdsFn ids_of = [&](int b, const int32_t *&p, int &n) {
+          if (scope1) { ar_history_ids(c, r.c0 + b, hist_one); p = hist_one.data(); n = (int)hist_one.size(); }
+          else { p = r.samples.data() + b; n = 1; }
+        };
+        if (sample_candidates_list(c, r.gen, ar_host_lists(c) + (size_t)r.c0 * TTS_PF_WORDS, ids_of, scope1, r.n_cand, next.data(),
+                                   [&](int b) { return ar_fetch_logits_row(c, r.c0 + b); }, &c->topk_fallbacks, r.book.retired.data()))
+          return fail(c, TTS_ERR_HIP, "tts_ar_session_step: fetching a logits row failed");
+      }
+      r.samples = next;
+      session_advance(s, r);
+      n_live -= r.state != 0;
+    }
+    return n_live;
+  });
+}
+
+int tts_ar_session_finished(tts_ctx *c, int32_t *ids_out, int cap) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_finished");
+  if (cap < 0 || (cap > 0 && !ids_out)) return fail(c, TTS_ERR_ARG, "tts_ar_session_finished: bad argument");
+  const std::vector<int> &f = c->session->finished;
+  for (int k = 0; k < (int)f.size() && k < cap; k++) ids_out[k] = f[k];
+  return (int)f.size();
+}
+
+int tts_ar_session_collect(tts_ctx *c, int request, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out, int32_t *stopped_out) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_collect");
+  ArSession &s = *c->session;
+  if (!codes_out || !rows_out) return fail(c, TTS_ERR_ARG, "tts_ar_session_collect: null output");
+  auto it = s.reqs.find(request);
+  if (it == s.reqs.end()) return fail(c, TTS_ERR_ARG, "tts_ar_session_collect: no request %d", request);
+  if (it->second.state == 0) return fail(c, TTS_ERR_STATE, "tts_ar_session_collect: request %d is still running", request);
+  if (it->second.state == 2) {
+    session_release(s, request);
+    return fail(c, TTS_ERR_LIMIT, "no stop token within %d steps", s.max_steps);
+  }
+  return guarded(c, [&] {
+    SessionOptions opt(c, s);
+    SessionRequest &r = it->second;
+    std::vector<std::vector<int>> seq = r.book.seq; // (the request stays collectable if the latent pass fails)
+    int max_rows = 0;
+    for (int b = 0; b < r.n_cand; b++) {
+      if (stopped_out) stopped_out[b] = (!seq[b].empty() && seq[b].back() == 8193) ? 1 : 0;
+      if (seq[b].size() > 500) seq[b].resize(500);
+      pad_codes(seq[b]);
+      std::copy(seq[b].begin(), seq[b].end(), codes_out + (size_t)b * 502);
+      rows_out[b] = trimmed_latent_rows(codes_out + (size_t)b * 502);
+      max_rows = std::max(max_rows, rows_out[b]);
+    }
+    if (steps_out) *steps_out = r.i;
+    if (latents_out) { // the latent pass over the mel prefix that trim_latents keeps, as tts_autoregressive's
+      const int n_mel = std::min(502, max_rows + 1), n_out = std::min(500, n_mel);
+      std::vector<float> lat((size_t)r.n_cand * n_out * TTS_DMODEL);
+      if (int rc = ar_session_latents(c, r.c0, r.n_text, codes_out, r.n_cand, n_mel, lat.data())) return rc;
+      size_t off = 0;
+      for (int b = 0; b < r.n_cand; b++) {
+        std::copy(lat.begin() + (size_t)b * n_out * TTS_DMODEL, lat.begin() + ((size_t)b * n_out + rows_out[b]) * TTS_DMODEL, latents_out + off);
+        off += (size_t)rows_out[b] * TTS_DMODEL;
+      }
+    }
+    session_release(s, request);
+    return (int)TTS_OK;
+  });
+}
+
+int tts_ar_session_logits(tts_ctx *c, int request, float *logits_out) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_logits");
+  if (!logits_out) return fail(c, TTS_ERR_ARG, "tts_ar_session_logits: null output");
+  auto it = c->session->reqs.find(request);
+  if (it == c->session->reqs.end()) return fail(c, TTS_ERR_ARG, "tts_ar_session_logits: no request %d", request);
+  return guarded(c, [&] { return ar_session_logits(c, it->second.c0, it->second.n_cand, logits_out); });
+}
+
+int tts_ar_session_cancel(tts_ctx *c, int request) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_cancel");
+  if (!c->session->reqs.count(request)) return fail(c, TTS_ERR_ARG, "tts_ar_session_cancel: no request %d", request);
+  session_release(*c->session, request);
   return TTS_OK;
 }
 

@@ -559,6 +559,26 @@ __global__ __launch_bounds__(256) void embed_step_kernel(const float *__restrict
   *(float4 *)(h4 + h4_index(r, 4 * threadIdx.x)) = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); // h4 layout, see below
 }
 
+// The same kernel for a session step (tts_ar_session_step): every row is at its own step. The pinned host block is [tokens[B] | n_past[Bpad] | pos_id[B]]
+// (Bpad = B in whole tiles of 16). Block r's three words have workgroup-uniform addresses: three independent scalar loads issued together, the one PCIe
+// round trip of the kernel above. Block r leaves its context length in row_off[r], the array the RO kernels behind it add to the step state's n_past,
+// which block 0 sets to 0. The tile padding of row_off (rows B .. Bpad) was zeroed when the session was opened and is never written.
+__global__ __launch_bounds__(256) void embed_session_kernel(const float *__restrict__ mel_emb, const float *__restrict__ mel_pos,
+                                                            const int *__restrict__ host_step, int B, int Bpad, StepState *__restrict__ ss_out,
+                                                            int *__restrict__ row_off, float *__restrict__ h4) {
+  const int r = blockIdx.x;
+  const int tok = host_step[r], n_past = host_step[B + r], pos_id = host_step[B + Bpad + r];
+  // (the empty asm wants all three in SGPRs HERE: left alone, hipcc sinks n_past's load into the branch below, a second dependent round trip for wave 0)
+  asm volatile("" ::"s"(tok), "s"(n_past), "s"(pos_id));
+  if (threadIdx.x == 0) {
+    row_off[r] = n_past;
+    if (r == 0) { ss_out->n_past = 0; ss_out->pos_id = 0; }
+  }
+  const float4 a = ((const float4 *)(mel_emb + (size_t)tok * D))[threadIdx.x];
+  const float4 b = ((const float4 *)(mel_pos + (size_t)pos_id * D))[threadIdx.x];
+  *(float4 *)(h4 + h4_index(r, 4 * threadIdx.x)) = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+
 // Round 4 — the residual stream of the DECODE step lives in an interleaved layout, `h4`:
 //     element (candidate r, channel k)  ->  h4[r / 16][k / 4][r % 16][k % 4]       (16-byte groups of 4 channels, the 16 candidates of a tile adjacent)
 // The LayerNorm-GEMV kernels feed the activations to the matrix pipe as the B operand: lane (m = candidate, q) holds 8 consecutive channels, so with the
@@ -1351,6 +1371,10 @@ struct ArState {
   std::vector<int> g_c0, g_n, g_t0, g_ntext;
   std::vector<int> g_voice;  // group g's row of the voice table `voice` ([n_voices][1024]; the single-voice entry points: one row, all 0)
   bool multi = false;
+  // A session (tts_ar_session_*): B slots, each row at its own step. The step's first kernel writes every row's context length into row_off and sets the
+  // step state's n_past to 0 (embed_session_kernel); the host block behind h_toks is [tokens[B] | n_past[Bpad] | pos_id[B]].
+  bool session = false;
+  int sess_captures0 = -1;   // graph_captures when the session's first step had run (tts_ar_session_recaptures)
   DevBuf row_off;            // multi: [tiles * 16] ints, P of the row's group (0 past the batch); the step state's n_past is then the step index
   DevBuf voice, kcache, vcache, lat_k, lat_v;
   DevBuf h, xn, qkv, att, ff, part, desc, logits, hn, a_hi, a_lo;
@@ -1371,12 +1395,12 @@ struct ArState {
   float step_penalty = 2.0f;                    // and, under scope 1, the penalty
   // one captured step per mode (a caller alternating tts_ar_step / tts_ar_step_sample, or bench's device_topk on/off loop, re-instantiated
   // the ~150-node graph on every switch)
-  hipGraph_t graphs[3] = {};
-  hipGraphExec_t graph_execs[3] = {};
+  hipGraph_t graphs[4] = {};         // [3]: the session step (one mode per session; kept across sessions of the same shape)
+  hipGraphExec_t graph_execs[4] = {};
   int graph_captures = 0; // decode-step graphs captured since the model was loaded (tts_ar_graph_captures)
   // everything the captured step bakes into its nodes: the graph of the previous utterance is replayed when nothing moved
   struct GraphSig {
-    int B = 0, max_pos = 0, lut = 0, wmode = 0, mode = 0, multi = 0;
+    int B = 0, max_pos = 0, lut = 0, wmode = 0, mode = 0, multi = 0; // multi: 2 = a session step
     int scope = 0, pf_min = 0; // the sampler controls a step bakes in: penalty scope (an extra node / the penalising prefilter), the prefilter's keep bound (modes 1, 2)
     float penalty = 0;         // scope 1, modes 1 / 2
     const void *p[13] = {};
@@ -1384,12 +1408,12 @@ struct ArState {
       return B == o.B && max_pos == o.max_pos && lut == o.lut && wmode == o.wmode && mode == o.mode && multi == o.multi && scope == o.scope &&
              pf_min == o.pf_min && penalty == o.penalty && std::equal(p, p + 13, o.p);
     }
-  } graph_sigs[3];
+  } graph_sigs[4];
   GraphSig current_sig(int lut, int wmode) const {
     GraphSig g;
-    g.B = B; g.max_pos = max_pos; g.lut = lut; g.wmode = wmode; g.mode = step_mode; g.multi = multi;
+    g.B = B; g.max_pos = max_pos; g.lut = lut; g.wmode = wmode; g.mode = step_mode; g.multi = session ? 2 : multi;
     g.scope = step_scope; g.pf_min = step_mode ? step_pf_min : 0; g.penalty = (step_scope && step_mode) ? step_penalty : 0.f;
-    const void *q[13] = {h.p, qkv.p, att.p, ff.p, kcache.p, vcache.p, d_toks.p, logits.p, h_toks, h_logits, h_pf, multi ? row_off.p : nullptr,
+    const void *q[13] = {h.p, qkv.p, att.p, ff.p, kcache.p, vcache.p, d_toks.p, logits.p, h_toks, h_logits, h_pf, (multi || session) ? row_off.p : nullptr,
                          step_scope ? hist.p : nullptr};
     std::copy(q, q + 13, g.p);
     return g;
@@ -1400,7 +1424,7 @@ struct ArState {
     graph_execs[m] = nullptr; graphs[m] = nullptr;
   }
   ~ArState() {
-    for (int m = 0; m < 3; m++) drop_graph(m);
+    for (int m = 0; m < 4; m++) drop_graph(m);
     if (h_toks) (void)hipHostFree(h_toks);
     if (h_logits) (void)hipHostFree(h_logits);
     if (h_pf) (void)hipHostFree(h_pf);
@@ -1944,6 +1968,21 @@ static int reserve_rows(tts_ctx *ctx, ArState *st, int rows) {
   return TTS_OK;
 }
 
+// The step's pinned host buffers for B rows. h_toks holds the larger of the two host blocks: [tokens[B] | n_past, pos_id] and a session's
+// [tokens[B] | n_past[Bpad] | pos_id[B]].
+static int reserve_pinned(tts_ctx *ctx, ArState *st, int B) {
+  if (B <= st->h_cap_B) return TTS_OK; // pinned allocations are slow (milliseconds): keep them across utterances
+  if (st->h_toks) (void)hipHostFree(st->h_toks);
+  if (st->h_logits) (void)hipHostFree(st->h_logits);
+  if (st->h_pf) (void)hipHostFree(st->h_pf);
+  st->h_toks = nullptr; st->h_logits = nullptr; st->h_pf = nullptr; st->h_cap_B = 0;
+  TTS_HIP(ctx, hipHostMalloc((void **)&st->h_toks, ((size_t)3 * B + 16) * 4));
+  TTS_HIP(ctx, hipHostMalloc((void **)&st->h_logits, (size_t)B * V * 4));
+  TTS_HIP(ctx, hipHostMalloc((void **)&st->h_pf, (size_t)B * TTS_PF_WORDS * 4));
+  st->h_cap_B = B;
+  return TTS_OK;
+}
+
 static int embed(tts_ctx *ctx, ArState *st, const std::vector<int4> &desc) {
   TTS_HIP(ctx, hipMemcpyAsync(st->desc.p, desc.data(), desc.size() * sizeof(int4), hipMemcpyHostToDevice, ctx->stream));
   EmbedTables t{{st->voice.as<float>(), st->text_emb, st->mel_emb}, {st->text_pos, st->mel_pos}};
@@ -1986,6 +2025,7 @@ int ar_begin_groups(tts_ctx *ctx, const int32_t *text_ids, const int *n_text, in
   if (voice_of) st->g_voice.assign(voice_of, voice_of + G);
   for (int g = 1; g < G; g++) { st->g_c0[g] = st->g_c0[g - 1] + n_cand[g - 1]; st->g_t0[g] = st->g_t0[g - 1] + n_text[g - 1]; }
   st->multi = G > 1;
+  st->session = false;
   st->n_text = P_max - 2; st->P = P_max;
   st->prefill_done = false;
   st->max_pos = max_pos;
@@ -2004,16 +2044,7 @@ int ar_begin_groups(tts_ctx *ctx, const int32_t *text_ids, const int *n_text, in
     TTS_HIP(ctx, st->row_off.reserve(off.size() * sizeof(int)));
     TTS_HIP(ctx, hipMemcpy(st->row_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
   }
-  if (B > st->h_cap_B) { // pinned allocations are slow (milliseconds): keep them across utterances
-    if (st->h_toks) (void)hipHostFree(st->h_toks);
-    if (st->h_logits) (void)hipHostFree(st->h_logits);
-    if (st->h_pf) (void)hipHostFree(st->h_pf);
-    st->h_toks = nullptr; st->h_logits = nullptr; st->h_pf = nullptr; st->h_cap_B = 0;
-    TTS_HIP(ctx, hipHostMalloc((void **)&st->h_toks, (size_t)(B + 2) * 4));
-    TTS_HIP(ctx, hipHostMalloc((void **)&st->h_logits, (size_t)B * V * 4));
-    TTS_HIP(ctx, hipHostMalloc((void **)&st->h_pf, (size_t)B * TTS_PF_WORDS * 4));
-    st->h_cap_B = B;
-  }
+  CHECK(reserve_pinned(ctx, st, B));
   st->hist_host.assign((size_t)B * TTS_HIST_WORDS, 0u); // a fresh history per begin: ids 1 and 8192 (what the prompt-shaped row of step 0 penalises)
   for (int b = 0; b < B; b++) {
     uint32_t *hb = st->hist_host.data() + (size_t)b * TTS_HIST_WORDS;
@@ -2036,11 +2067,11 @@ int ar_begin(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voi
 // Prefill (main.cpp:2586-2665): [voice | text_emb+pos | mel_emb(8192)+mel_pos(0)] — identical for all
 // candidates, so it is evaluated once and its K/V rows are written into every candidate's cache.
 // Several prompts (tts_ar_begin_multi): one such pass per group, its K/V rows written into the caches of the group's candidates only.
-static int prefill_group(tts_ctx *ctx, ArState *st, int g) {
-  const int n_text = st->g_ntext[g], P = n_text + 2, c0 = st->g_c0[g];
-  const int *tok = st->tokens.data() + st->g_t0[g];
+// A session's request (tts_ar_session_admit): the same pass over its slot range [c0, c0 + n_cand).
+static int prompt_pass(tts_ctx *ctx, ArState *st, int c0, int n_cand, int n_text, const int *tok, int voice_row) {
+  const int P = n_text + 2;
   std::vector<int4> desc(P);
-  desc[0] = make_int4(0, st->g_voice[g], -1, 0); // the group's row of the voice table
+  desc[0] = make_int4(0, voice_row, -1, 0); // the group's row of the voice table
   for (int i = 0; i < n_text; i++) desc[1 + i] = make_int4(1, tok[i], 0, i);
   desc[P - 1] = make_int4(2, 8192, 1, 0);
   CHECK(embed(ctx, st, desc));
@@ -2053,7 +2084,7 @@ static int prefill_group(tts_ctx *ctx, ArState *st, int g) {
     const ArLayerDev &w = st->L[l];
     __half *kc = st->kcache.as<__half>() + l * layer_stride + cand0, *vc = st->vcache.as<__half>() + l * layer_stride + cand0;
     { ProfScope ps(ctx, "ar_gemv", 3.0 * D * D * 4.0 * tiles);
-      DecLnArgs a{h, nullptr, nullptr, w.d_attn, w.dh_attn, w.db_attn, P, 3 * D, 3 * D, st->g_n[g], qkv, kc, vc, nullptr, st->max_pos, ctx->ggml_lut};
+      DecLnArgs a{h, nullptr, nullptr, w.d_attn, w.dh_attn, w.db_attn, P, 3 * D, 3 * D, n_cand, qkv, kc, vc, nullptr, st->max_pos, ctx->ggml_lut};
       DEC_LN_LAUNCH(DEC_QKV, dim3(3 * D / 16, tiles), false); }
     { ProfScope ps(ctx, "ar_attention");
       attention_kernel<<<dim3(P, NH), 64, 0, ctx->stream>>>(qkv, kc, vc, att, P, 0, st->max_pos, ctx->ggml_lut); }
@@ -2072,6 +2103,10 @@ static int prefill_group(tts_ctx *ctx, ArState *st, int g) {
     DEC_LN_LAUNCH(DEC_LOGITS, dim3(VPAD / 16, 1), false); }
   TTS_HIP(ctx, hipGetLastError());
   return TTS_OK;
+}
+
+static int prefill_group(tts_ctx *ctx, ArState *st, int g) {
+  return prompt_pass(ctx, st, st->g_c0[g], st->g_n[g], st->g_ntext[g], st->tokens.data() + st->g_t0[g], st->g_voice[g]);
 }
 
 int ar_prefill(tts_ctx *ctx, float *logits_out) {
@@ -2113,22 +2148,26 @@ static int enqueue_decode_step(tts_ctx *ctx, ArState *st) {
   const size_t layer_stride = (size_t)B * st->max_pos * D;
   const int wm = ctx->ar_weights; // 1 / 2: fp16 / fp8 weights, a half / a quarter of the bytes per step (throughput modes, not f32-exact); checked by ar_step
   const double wb = wm == 2 ? 1.0 : wm == 1 ? 2.0 : 4.0;
-  const int *ro = st->multi ? st->row_off.as<int>() : nullptr; // several prompts: the rows' context offsets (n_past = step index + row_off[row])
-  embed_step_kernel<<<B, 256, 0, ctx->stream>>>(st->mel_emb, st->mel_pos, st->h_toks, B, (StepState *)(st->d_toks.as<int>() + B), h);
+  const bool ro_k = st->multi || st->session; // several prompts: the rows' context offsets (n_past = step index + row_off[row]); a session: the rows' context lengths
+  const int *ro = ro_k ? st->row_off.as<int>() : nullptr;
+  if (st->session)
+    embed_session_kernel<<<B, 256, 0, ctx->stream>>>(st->mel_emb, st->mel_pos, st->h_toks, B, tiles * 16, (StepState *)(st->d_toks.as<int>() + B), st->row_off.as<int>(), h);
+  else
+    embed_step_kernel<<<B, 256, 0, ctx->stream>>>(st->mel_emb, st->mel_pos, st->h_toks, B, (StepState *)(st->d_toks.as<int>() + B), h);
   for (int l = 0; l < st->n_layers; l++) {
     const ArLayerDev &w = st->L[l];
     __half *kc = st->kcache.as<__half>() + l * layer_stride, *vc = st->vcache.as<__half>() + l * layer_stride;
     { ProfScope ps(ctx, "ar_gemv", 3.0 * D * D * wb * tiles);
       DecLnArgs a{h, nullptr, nullptr, w.d_attn, wm == 2 ? (const __half *)w.o_attn : wm == 1 ? w.q_attn : w.dh_attn, w.db_attn, B, 3 * D, D, 0, q, kc, vc, ss,
                   st->max_pos, ctx->ggml_lut, w.os_attn, ro};
-      if (st->multi) launch_dec_qkv<true>(ctx, st, wm, dim3(3 * D / 16, tiles), a);
+      if (ro_k) launch_dec_qkv<true>(ctx, st, wm, dim3(3 * D / 16, tiles), a);
       else launch_dec_qkv<false>(ctx, st, wm, dim3(3 * D / 16, tiles), a); }
     { ProfScope ps(ctx, "ar_attention");
       if (ctx->ggml_lut) {
-        if (st->multi) attn_decode_kernel<true><<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, 1, ro);
+        if (ro_k) attn_decode_kernel<true><<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, 1, ro);
         else attn_decode_kernel<false><<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, 1, nullptr);
       } else {
-        if (st->multi) attn_decode_fast_kernel<true><<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, ro);
+        if (ro_k) attn_decode_fast_kernel<true><<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, ro);
         else attn_decode_fast_kernel<false><<<dim3(B, NH), 256, 0, ctx->stream>>>(q, kc, vc, ss, st->max_pos, att, nullptr);
       } }
     { ProfScope ps(ctx, "ar_gemv", 1.0 * D * D * wb * tiles);
@@ -2168,6 +2207,32 @@ static int enqueue_decode_step(tts_ctx *ctx, ArState *st) {
   return TTS_OK;
 }
 
+// Runs the step that the state describes: replays graph slot `slot` (captured first when the slot is empty or anything its nodes bake in has moved: GraphSig),
+// or launches the kernels eagerly while one of their families is profiled. Slots 0 .. 2: ar_step's modes; 3: the session step.
+static int launch_step(tts_ctx *ctx, ArState *st, int slot, double step_bytes) {
+  static const bool no_graph = getenv("TTS_NO_GRAPH") != nullptr; // e.g. under rocprofv3, which crashes on graph replays here
+  // event records are not captured: the step runs eagerly while one of its own kernel families ("ar_*") is profiled
+  // ("ar_decode_step" brackets the whole graph replay and keeps the graph)
+  bool prof_ar = ctx->prof_on && ctx->prof_filter.empty();
+  for (const std::string &f : ctx->prof_filter) prof_ar |= ctx->prof_on && f.rfind("ar_", 0) == 0 && f != "ar_decode_step";
+  if (prof_ar || no_graph) return enqueue_decode_step(ctx, st);
+  const ArState::GraphSig sig = st->current_sig(ctx->ggml_lut, ctx->ar_weights);
+  if (st->graph_execs[slot] && !(sig == st->graph_sigs[slot])) st->drop_graph(slot);
+  if (!st->graph_execs[slot]) {
+    st->graph_sigs[slot] = sig;
+    TTS_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+    st->graph_captures++;
+    int rc = enqueue_decode_step(ctx, st);
+    hipError_t e = hipStreamEndCapture(ctx->stream, &st->graphs[slot]);
+    if (rc || e != hipSuccess) { st->drop_graph(slot); if (rc) return rc; TTS_HIP(ctx, e); } // never keep a half-captured graph
+    e = hipGraphInstantiate(&st->graph_execs[slot], st->graphs[slot], nullptr, nullptr, 0);
+    if (e != hipSuccess) { st->drop_graph(slot); TTS_HIP(ctx, e); }
+  }
+  ProfScope ps(ctx, "ar_decode_step", step_bytes);
+  TTS_HIP(ctx, hipGraphLaunch(st->graph_execs[slot], ctx->stream));
+  return TTS_OK;
+}
+
 // Decode step i (main.cpp:2667-2693, 5227-5247): mel_emb[tok] + mel_pos[i+2], n_past = P + i.
 // mode 0: the logits come back ([B][8194], logits_out may be null: ar_host_logits); mode 1 / 2: the device prefilter's lists come back
 // instead (ar_host_lists; 2 = stop token masked first) and the logits stay in HBM (ar_fetch_logits_row). Each mode is its own graph.
@@ -2197,32 +2262,10 @@ int ar_step(tts_ctx *ctx, const int32_t *prev_ids, int step_i, float *logits_out
   }
   st->h_toks[st->B] = st->multi ? step_i : st->P + step_i; // n_past (several prompts: the kernels add the row's P, ArState::row_off)
   st->h_toks[st->B + 1] = step_i + 2; // mel position id (main.cpp:5244)
-  static const bool no_graph = getenv("TTS_NO_GRAPH") != nullptr; // e.g. under rocprofv3, which crashes on graph replays here
-  // event records are not captured: the step runs eagerly while one of its own kernel families ("ar_*") is profiled
-  // ("ar_decode_step" brackets the whole graph replay and keeps the graph)
-  bool prof_ar = ctx->prof_on && ctx->prof_filter.empty();
-  for (const std::string &f : ctx->prof_filter) prof_ar |= ctx->prof_on && f.rfind("ar_", 0) == 0 && f != "ar_decode_step";
-  if (prof_ar || no_graph) {
-    CHECK(enqueue_decode_step(ctx, st));
-  } else {
-    const ArState::GraphSig sig = st->current_sig(ctx->ggml_lut, ctx->ar_weights);
-    if (st->graph_execs[mode] && !(sig == st->graph_sigs[mode])) st->drop_graph(mode);
-    if (!st->graph_execs[mode]) {
-      st->graph_sigs[mode] = sig;
-      TTS_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-      st->graph_captures++;
-      int rc = enqueue_decode_step(ctx, st);
-      hipError_t e = hipStreamEndCapture(ctx->stream, &st->graphs[mode]);
-      if (rc || e != hipSuccess) { st->drop_graph(mode); if (rc) return rc; TTS_HIP(ctx, e); } // never keep a half-captured graph
-      e = hipGraphInstantiate(&st->graph_execs[mode], st->graphs[mode], nullptr, nullptr, 0);
-      if (e != hipSuccess) { st->drop_graph(mode); TTS_HIP(ctx, e); }
-    }
-    // HBM-bound step: every weight once (f32: 12 d^2 per layer + the padded head) + the fp16 K/V rows read + logits
-    const double step_bytes = (ctx->ar_weights == 2 ? 1.0 : ctx->ar_weights == 1 ? 2.0 : 4.0) * ((double)st->n_layers * 12.0 * D * D + (double)D * V) +
-                              (double)st->B * st->n_layers * 2.0 * (st->P + step_i + 1) * D * 2.0 + (double)st->B * V * 4.0;
-    ProfScope ps(ctx, "ar_decode_step", step_bytes);
-    TTS_HIP(ctx, hipGraphLaunch(st->graph_execs[mode], ctx->stream));
-  }
+  // HBM-bound step: every weight once (f32: 12 d^2 per layer + the padded head) + the fp16 K/V rows read + logits
+  const double step_bytes = (ctx->ar_weights == 2 ? 1.0 : ctx->ar_weights == 1 ? 2.0 : 4.0) * ((double)st->n_layers * 12.0 * D * D + (double)D * V) +
+                            (double)st->B * st->n_layers * 2.0 * (st->P + step_i + 1) * D * 2.0 + (double)st->B * V * 4.0;
+  CHECK(launch_step(ctx, st, mode, step_bytes));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (logits_out) memcpy(logits_out, st->h_logits, (size_t)st->B * V * 4);
   return TTS_OK;
@@ -2282,13 +2325,14 @@ static int latents_check(tts_ctx *ctx, const ArState *st, int n_text, const int3
   return TTS_OK;
 }
 
-static int latents_group(tts_ctx *ctx, ArState *st, int g, const int32_t *codes502, int nb, int n_mel, float *out) {
-  const int Sp = 1 + st->g_ntext[g], S = Sp + n_mel, rows = nb * n_mel;
+// c0: the cache row that holds the prompt's K/V rows (a group's first candidate; a session request's first slot), n_text: that prompt's length.
+static int latents_rows(tts_ctx *ctx, ArState *st, int c0, int n_text, const int32_t *codes502, int nb, int n_mel, float *out) {
+  const int Sp = 1 + n_text, S = Sp + n_mel, rows = nb * n_mel;
   CHECK(reserve_rows(ctx, st, rows));
   const size_t lat_stride = (size_t)nb * S * D; // per layer: [cand][S][1024]
   TTS_HIP(ctx, st->lat_k.reserve(st->n_layers * lat_stride * sizeof(__half)));
   TTS_HIP(ctx, st->lat_v.reserve(st->n_layers * lat_stride * sizeof(__half)));
-  const size_t src0 = (size_t)st->g_c0[g] * st->max_pos * D; // the group's first candidate holds its prompt rows
+  const size_t src0 = (size_t)c0 * st->max_pos * D;
   copy_prompt_kv_kernel<<<dim3(Sp, nb, 2 * st->n_layers), 256, 0, ctx->stream>>>(
       st->kcache.as<__half>() + src0, st->vcache.as<__half>() + src0, (size_t)st->B * st->max_pos * D, st->lat_k.as<__half>(), st->lat_v.as<__half>(),
       lat_stride, S, st->n_layers);
@@ -2307,6 +2351,10 @@ static int latents_group(tts_ctx *ctx, ArState *st, int g, const int32_t *codes5
                                 ctx->stream));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return TTS_OK;
+}
+
+static int latents_group(tts_ctx *ctx, ArState *st, int g, const int32_t *codes502, int nb, int n_mel, float *out) {
+  return latents_rows(ctx, st, st->g_c0[g], st->g_ntext[g], codes502, nb, n_mel, out);
 }
 
 // tts_ar_latents. Several prompts: nb must be the whole batch, every candidate is evaluated against its own prompt (out [B][min(500, n_mel)][1024]).
@@ -2353,6 +2401,141 @@ int ar_stream_reserve(tts_ctx *ctx, int n_mel) {
   return TTS_OK;
 }
 int ar_graph_captures(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->graph_captures : 0; }
+
+// ---------------------------------------------------------------------------------------------
+// Sessions (tts_ar_session_*): the device side. The book of slots and requests is the caller's (api.cpp); here a session is a batch of n_slots rows whose
+// caches hold max_text + 2 + max_steps + 1 positions, every row at its own step (ArState::session).
+// ---------------------------------------------------------------------------------------------
+static void hist_reset_row(uint32_t *hb) { // what a begin leaves: ids 1 and 8192 (the prompt-shaped penalty row of step 0)
+  std::fill(hb, hb + TTS_HIST_WORDS, 0u);
+  hb[1 >> 5] |= 1u << (1 & 31);
+  hb[8192 >> 5] |= 1u << (8192 & 31);
+}
+
+// Every buffer that the decode step, a prompt pass of max_text + 2 rows and a latent pass of max_cand x 502 rows can touch is reserved here: nothing the
+// captured step bakes into its nodes (GraphSig) moves while the session is open. The caller has checked the limits.
+int ar_session_open(tts_ctx *ctx, int n_slots, int max_cand, int max_text, int max_steps) {
+  ArState *st = ctx->ar;
+  if (!st) return fail(ctx, TTS_ERR_STATE, "AR model not loaded");
+  if (ctx->ar_weights != 0 && ctx->ar_weights != st->loaded_wmode)
+    return fail(ctx, TTS_ERR_STATE, "option ar_weights = %d must be set before tts_load_ar (the fp16 / fp8 slabs are packed at load)", ctx->ar_weights);
+  const int B = n_slots, Bpad = (B + 15) / 16 * 16, P = max_text + 2, max_pos = P + max_steps + 1;
+  st->B = 0; // (a failure below leaves no half-open state behind)
+  st->session = false;
+  st->g_c0.clear(); st->g_n.clear(); st->g_t0.clear(); st->g_ntext.clear(); st->g_voice.clear(); st->tokens.clear();
+  st->multi = false;
+  st->n_text = max_text; st->P = P; st->max_pos = max_pos;
+  st->prefill_done = false;
+  TTS_HIP(ctx, st->voice.reserve((size_t)B * D * 4)); // one row per slot: a request's voice sits in the row of its first slot
+  const size_t cache = (size_t)st->n_layers * B * max_pos * D * sizeof(__half);
+  TTS_HIP(ctx, st->kcache.reserve(cache));
+  TTS_HIP(ctx, st->vcache.reserve(cache));
+  TTS_HIP(ctx, st->d_toks.reserve((size_t)(B + 2) * 4));
+  TTS_HIP(ctx, st->logits.reserve((size_t)B * V * 4));
+  TTS_HIP(ctx, st->row_off.reserve((size_t)Bpad * sizeof(int)));
+  TTS_HIP(ctx, hipMemsetAsync(st->row_off.p, 0, (size_t)Bpad * sizeof(int), ctx->stream));
+  CHECK(reserve_pinned(ctx, st, B));
+  st->hist_host.assign((size_t)B * TTS_HIST_WORDS, 0u);
+  for (int b = 0; b < B; b++) hist_reset_row(st->hist_host.data() + (size_t)b * TTS_HIST_WORDS);
+  TTS_HIP(ctx, st->hist.reserve(st->hist_host.size() * 4));
+  TTS_HIP(ctx, hipMemcpy(st->hist.p, st->hist_host.data(), st->hist_host.size() * 4, hipMemcpyHostToDevice));
+  st->hist_dev_valid = false; // (a later tts_ar_begin* starts from its own host copy)
+  const int lat_rows = max_cand * 502, S_max = std::min(1024, 1 + max_text + 502);
+  CHECK(reserve_rows(ctx, st, std::max({Bpad, P, lat_rows})));
+  TTS_HIP(ctx, hipMemsetAsync(st->h.p, 0, st->h.cap, ctx->stream)); // the tile padding rows of the h4 layout are read (never stored): finite
+  const size_t lat = (size_t)st->n_layers * max_cand * S_max * D * sizeof(__half);
+  TTS_HIP(ctx, st->lat_k.reserve(lat));
+  TTS_HIP(ctx, st->lat_v.reserve(lat));
+  const size_t rpad = (size_t)(lat_rows + 127) & ~(size_t)127; // launch_mfma_matmul's operands; launch_gemv's partials (at most 16 K splits of 31 rows)
+  TTS_HIP(ctx, st->a_hi.reserve(rpad * FF * sizeof(__half)));
+  TTS_HIP(ctx, st->a_lo.reserve(rpad * FF * sizeof(__half)));
+  TTS_HIP(ctx, st->part.reserve(std::max(rpad, (size_t)16 * 32) * FF * sizeof(float)));
+  // An empty slot sits at position 0 with token 8193: every step stores its K/V row there before the attention reads it, so it never reads
+  // uninitialised memory.
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  st->sess_captures0 = -1;
+  st->session = true;
+  st->B = B;
+  return TTS_OK;
+}
+
+void ar_session_close(tts_ctx *ctx) {
+  ArState *st = ctx->ar;
+  if (!st || !st->session) return;
+  st->session = false;
+  st->B = 0; // tts_ar_begin* starts over; the session's step graph stays for the next session of the same shape
+}
+
+// A request's prompt pass into its slots [c0, c0 + n_cand): its voice goes to row c0 of the voice table, its K/V rows into its slots' caches only, its first
+// logits to row c0 (copied to logits_row), and its history sets start over in the host copy and in the device rows. The caller has checked the arguments.
+int ar_session_prompt(tts_ctx *ctx, int c0, int n_cand, const int32_t *text_ids, int n_text, const float *voice, float *logits_row) {
+  ArState *st = ctx->ar;
+  if (!st || !st->session || c0 < 0 || n_cand < 1 || c0 + n_cand > st->B || n_text < 1 || n_text > st->n_text)
+    return fail(ctx, TTS_ERR_STATE, "tts_ar_session_admit: no session, or a request outside it");
+  TTS_HIP(ctx, hipMemcpy(st->voice.as<float>() + (size_t)c0 * D, voice, (size_t)D * 4, hipMemcpyHostToDevice));
+  uint32_t *hb = st->hist_host.data() + (size_t)c0 * TTS_HIST_WORDS;
+  for (int b = 0; b < n_cand; b++) hist_reset_row(hb + (size_t)b * TTS_HIST_WORDS);
+  TTS_HIP(ctx, hipMemcpy(st->hist.as<uint32_t>() + (size_t)c0 * TTS_HIST_WORDS, hb, (size_t)n_cand * TTS_HIST_WORDS * 4, hipMemcpyHostToDevice));
+  const std::vector<int> tok(text_ids, text_ids + n_text);
+  CHECK(prompt_pass(ctx, st, c0, n_cand, n_text, tok.data(), c0));
+  TTS_HIP(ctx, hipMemcpyAsync(logits_row, st->logits.as<float>() + (size_t)c0 * V, (size_t)V * 4, hipMemcpyDeviceToHost, ctx->stream));
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return TTS_OK;
+}
+
+// One step over all slots: row r is fed toks[r] at mel position pos_id[r] with n_past[r] positions behind it. live[r]: the row belongs to a running request
+// (its token joins the row's history set in the host copy; on the device the step's own kernels add it for every row, and an admission resets the rows it
+// takes). mode as ar_step's.
+int ar_session_step(tts_ctx *ctx, const int32_t *toks, const int32_t *n_past, const int32_t *pos_id, const char *live, int mode) {
+  ArState *st = ctx->ar;
+  if (!st || !st->session || st->B == 0) return fail(ctx, TTS_ERR_STATE, "tts_ar_session_open not called");
+  if (mode < 0 || mode > 2) return fail(ctx, TTS_ERR_ARG, "ar_session_step: bad mode");
+  const int B = st->B, Bpad = (B + 15) / 16 * 16;
+  for (int r = 0; r < B; r++) {
+    if (toks[r] < 0 || toks[r] >= V) return fail(ctx, TTS_ERR_ARG, "mel token %d out of range", toks[r]);
+    if (n_past[r] < 0 || n_past[r] >= st->max_pos) return fail(ctx, TTS_ERR_LIMIT, "slot %d: position %d beyond the KV cache", r, n_past[r]);
+    if (pos_id[r] < 0 || pos_id[r] >= 608) return fail(ctx, TTS_ERR_LIMIT, "slot %d: mel position %d of 608", r, pos_id[r]);
+  }
+  st->step_mode = mode;
+  st->step_scope = ctx->ar_penalty_scope;
+  st->step_pf_min = pf_min_for(ctx->ar_sp.top_k);
+  st->step_penalty = ctx->ar_sp.penalty;
+  double kv_rows = 0;
+  for (int r = 0; r < B; r++) {
+    st->h_toks[r] = toks[r];
+    st->h_toks[B + r] = n_past[r];
+    st->h_toks[B + Bpad + r] = pos_id[r];
+    if (live[r]) st->hist_host[(size_t)r * TTS_HIST_WORDS + (toks[r] >> 5)] |= 1u << (toks[r] & 31);
+    kv_rows += n_past[r] + 1;
+  }
+  for (int r = B; r < Bpad; r++) st->h_toks[B + r] = 0;
+  const double step_bytes = (ctx->ar_weights == 2 ? 1.0 : ctx->ar_weights == 1 ? 2.0 : 4.0) * ((double)st->n_layers * 12.0 * D * D + (double)D * V) +
+                            kv_rows * st->n_layers * 2.0 * D * 2.0 + (double)B * V * 4.0;
+  CHECK(launch_step(ctx, st, 3, step_bytes));
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (st->sess_captures0 < 0) st->sess_captures0 = st->graph_captures;
+  return TTS_OK;
+}
+int ar_session_recaptures(const tts_ctx *ctx) {
+  const ArState *st = ctx->ar;
+  return (st && st->session && st->sess_captures0 >= 0) ? st->graph_captures - st->sess_captures0 : 0;
+}
+
+// The latent pass of a request: nb candidates over the prompt rows of slot c0 (n_text ids) and n_mel codes each; out [nb][min(500, n_mel)][1024].
+int ar_session_latents(tts_ctx *ctx, int c0, int n_text, const int32_t *codes502, int nb, int n_mel, float *out) {
+  ArState *st = ctx->ar;
+  if (!st || !st->session || c0 < 0 || c0 + nb > st->B) return fail(ctx, TTS_ERR_STATE, "tts_ar_session_open not called");
+  CHECK(latents_check(ctx, st, n_text, codes502, nb, n_mel));
+  return latents_rows(ctx, st, c0, n_text, codes502, nb, n_mel, out);
+}
+
+// Rows [c0, c0 + n) of the last step's logits, from HBM.
+int ar_session_logits(tts_ctx *ctx, int c0, int n, float *out) {
+  ArState *st = ctx->ar;
+  if (!st || !st->session || c0 < 0 || n < 1 || c0 + n > st->B) return fail(ctx, TTS_ERR_STATE, "tts_ar_session_open not called");
+  TTS_HIP(ctx, hipMemcpy(out, st->logits.as<float>() + (size_t)c0 * V, (size_t)n * V * 4, hipMemcpyDeviceToHost));
+  return TTS_OK;
+}
 
 int ar_layers(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->n_layers : 0; }
 int ar_batch(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->B : 0; }

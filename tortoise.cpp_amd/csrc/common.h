@@ -94,6 +94,7 @@ struct HifiganState;
 struct Tokenizer;
 struct SamplerPool;
 void sampler_pool_free(SamplerPool *p);
+struct ArSession; // the book of an open session (tts_ar_session_*): api.cpp
 // The autoregressive sampler's controls (options "ar_temperature", "ar_top_k", "ar_top_p", "ar_repetition_penalty"): the defaults are the literals of
 // process_logits_and_sample (main.cpp:4753-4806); upstream tortoise-tts passes the same four to HF generate on every call.
 struct SamplerParams {
@@ -129,6 +130,7 @@ struct tts_ctx {
   tts::DiffCondEncState *dcond = nullptr; // diffusion conditioning encoder (extras.hip; not in the reference)
   tts::HifiganState *hifigan = nullptr; // HiFi-GAN decoder: latents -> waveform (hifigan.hip; not in the reference: upstream's api_fast.py path)
   tts::Tokenizer *tok = nullptr;
+  tts::ArSession *session = nullptr;        // non-null while a session is open: tts_ar_begin*, tts_autoregressive* and tts_hifigan_stream then return TTS_ERR_STATE
   tts::SamplerPool *sampler_pool = nullptr; // worker threads for the per-candidate sampler scans (host_logic.cpp)
   tts::SamplerParams ar_sp;                 // options "ar_temperature" / "ar_top_k" / "ar_top_p" / "ar_repetition_penalty"
   int ar_penalty_scope = 0;                 // option "ar_penalty_scope": 0 = the reference (the ids of the last input), 1 = upstream's HF generate (every id fed since tts_ar_begin*, plus 1 and 8192)
@@ -328,12 +330,14 @@ struct Tokenizer {
   bool load(const char *path);
   std::vector<int> encode(const std::string &message) const;
 };
-void sample_candidates(tts_ctx *ctx, const float *logits, const int32_t *ids, int ids_per_cand, int B,
+// `gen`: the generator the uniforms are drawn from, two per candidate in candidate order. The context's own (ctx->generator) is consumed as a shard of the declared
+// batch (rng_shard_*); any other generator (a session request's) as a whole stream of its own.
+void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const float *logits, const int32_t *ids, int ids_per_cand, int B,
                        int32_t *out);
 // The penalty ids of candidate c. Called from the sampler pool's threads, except by sample_candidates_list with already_penalised (only its serial
 // full-row fallback asks, so the callee may build the ids on demand into one scratch buffer).
 using PenaltyIdsFn = std::function<void(int c, const int32_t *&ids, int &n_ids)>;
-void sample_candidates(tts_ctx *ctx, const float *logits, const PenaltyIdsFn &ids_of, int B, int32_t *out);
+void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const float *logits, const PenaltyIdsFn &ids_of, int B, int32_t *out);
 // Device top-k prefilter of the decode step (ar.hip: sample_prefilter_kernel; option "device_topk"): per candidate TTS_PF_WORDS
 // 32-bit words {n, 0, 0, 0, idx[TTS_PF_MAX], logit bits[TTS_PF_MAX]} = every logit >= a threshold that keeps TTS_PF_MIN..TTS_PF_MAX
 // of the 8194, in index order (n = -1: no such threshold, the host samples from the full row). The window's lower bound follows the sampler's top-k
@@ -342,9 +346,9 @@ void sample_candidates(tts_ctx *ctx, const float *logits, const PenaltyIdsFn &id
 // TTS_HIST_WORDS 32-bit words (bit i = id i was fed since tts_ar_begin*, plus 1 and 8192).
 enum { TTS_PF_MIN = 64, TTS_PF_MAX = 128, TTS_PF_WORDS = 4 + 2 * TTS_PF_MAX, TTS_PF_SLACK = TTS_PF_MIN - 50, TTS_PF_TOPK_MAX = 100, TTS_HIST_WORDS = 257 };
 inline int pf_min_for(int top_k) { return top_k <= TTS_PF_TOPK_MAX ? top_k + TTS_PF_SLACK : TTS_PF_MAX + 1; } // a bound above TTS_PF_MAX: the kernel writes n = -1 for every candidate
-int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
+int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
                            const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired = nullptr);
-int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const PenaltyIdsFn &ids_of, bool already_penalised, int B, int32_t *out,
+int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const int32_t *lists, const PenaltyIdsFn &ids_of, bool already_penalised, int B, int32_t *out,
                            const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired = nullptr);
 int host_prefilter_row(const float *row, int keep, int32_t *list);
 int sample_one_row(const float *row, const int32_t *ids, int ids_per_cand, float uniform);

@@ -628,16 +628,20 @@ void sampler_pool_free(SamplerPool *p) { delete p; }
 // Sharded batch (options "rng_shard_offset" / "rng_shard_total"): this context holds candidates
 // [offset, offset + B) of a batch of `total`; the used uniform of (step s, global candidate c) is output 2 (s total + c) + 1
 // of the one mt19937 stream, so the draws of the other ranks' candidates are skipped (each uniform is one 32-bit output).
-static void draw_uniforms(tts_ctx *ctx, int B, std::vector<float> &samples) {
-  const int total = ctx->rng_shard_total > 0 ? ctx->rng_shard_total : B, c0 = shard_base(ctx);
+// `gen`: the stream the uniforms come from. The context's own generator is one shard of the declared batch; any other generator (a session request's,
+// tts_ar_session_admit) is a whole stream of its own: two uniforms per candidate and step, nothing skipped.
+static void draw_uniforms(tts_ctx *ctx, std::mt19937 &gen, int B, std::vector<float> &samples) {
+  const bool own = &gen == &ctx->generator;
+  const int total = own && ctx->rng_shard_total > 0 ? ctx->rng_shard_total : B, c0 = own ? shard_base(ctx) : 0;
   samples.resize(B);
-  if (c0 > 0) ctx->generator.discard(2ull * c0);
+  if (c0 > 0) gen.discard(2ull * c0);
+  std::uniform_real_distribution<float> &dist = ctx->distribution; // holds its bounds only: no state is shared between generators
   for (int c = 0; c < B; c++) {
-    float sample = ctx->distribution(ctx->generator); // first draw discarded (main.cpp:4708-4709)
-    sample = ctx->distribution(ctx->generator);
+    float sample = dist(gen); // first draw discarded (main.cpp:4708-4709)
+    sample = dist(gen);
     samples[c] = sample;
   }
-  if (total - c0 - B > 0) ctx->generator.discard(2ull * (total - c0 - B));
+  if (total - c0 - B > 0) gen.discard(2ull * (total - c0 - B));
 }
 
 static void run_on_pool(tts_ctx *ctx, int B, const std::function<void(int)> &one) {
@@ -650,10 +654,10 @@ static void run_on_pool(tts_ctx *ctx, int B, const std::function<void(int)> &one
   ctx->sampler_pool->run(B, one);
 }
 
-void sample_candidates(tts_ctx *ctx, const float *logits, const PenaltyIdsFn &ids_of, int B, int32_t *out) {
+void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const float *logits, const PenaltyIdsFn &ids_of, int B, int32_t *out) {
   const int V = TTS_VOCAB_MEL;
   std::vector<float> samples;
-  draw_uniforms(ctx, B, samples);
+  draw_uniforms(ctx, gen, B, samples);
   const SamplerParams sp = ctx->ar_sp;
   run_on_pool(ctx, B, [&](int c) {
     const int32_t *ids = nullptr; int n_ids = 0;
@@ -661,9 +665,9 @@ void sample_candidates(tts_ctx *ctx, const float *logits, const PenaltyIdsFn &id
     out[c] = sample_one(logits + (size_t)c * V, ids, n_ids, samples[c], sp);
   });
 }
-void sample_candidates(tts_ctx *ctx, const float *logits, const int32_t *ids, int ids_per_cand, int B,
+void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const float *logits, const int32_t *ids, int ids_per_cand, int B,
                        int32_t *out) {
-  sample_candidates(ctx, logits, [&](int c, const int32_t *&p, int &n) { p = ids + (size_t)c * ids_per_cand; n = ids_per_cand; }, B, out);
+  sample_candidates(ctx, gen, logits, [&](int c, const int32_t *&p, int &n) { p = ids + (size_t)c * ids_per_cand; n = ids_per_cand; }, B, out);
 }
 
 // The decode loop's sampler over the device prefilter's lists (ar.hip: [B][TTS_PF_WORDS] = {n, 0, 0, 0, idx[128], value[128]}), same
@@ -673,10 +677,10 @@ void sample_candidates(tts_ctx *ctx, const float *logits, const int32_t *ids, in
 // `retired` (may be null): candidates whose sequence has ended (TTS_AR_RETIRE). Their uniforms are drawn like everybody's — the stream stays the reference's — but
 // nothing is sampled for them (out = 8193): round 5's ragged bench pass spent 27 ms per utterance evaluating lists and fetching full logits rows for candidates whose
 // sample the loop then threw away.
-int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const PenaltyIdsFn &ids_of, bool already_penalised, int B, int32_t *out,
+int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const int32_t *lists, const PenaltyIdsFn &ids_of, bool already_penalised, int B, int32_t *out,
                            const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired) {
   std::vector<float> samples;
-  draw_uniforms(ctx, B, samples);
+  draw_uniforms(ctx, gen, B, samples);
   const SamplerParams sp = ctx->ar_sp;
   auto one = [&](int c) {
     if (retired && retired[c]) { out[c] = 8193; return; }
@@ -702,9 +706,9 @@ int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const PenaltyIdsF
   if (n_fallbacks) *n_fallbacks += fb;
   return 0;
 }
-int sample_candidates_list(tts_ctx *ctx, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
+int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
                            const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired) {
-  return sample_candidates_list(ctx, lists, [&](int c, const int32_t *&p, int &n) { p = ids + (size_t)c * ids_per_cand; n = ids_per_cand; }, false, B, out,
+  return sample_candidates_list(ctx, gen, lists, [&](int c, const int32_t *&p, int &n) { p = ids + (size_t)c * ids_per_cand; n = ids_per_cand; }, false, B, out,
                                 full_row, n_fallbacks, retired);
 }
 
