@@ -427,6 +427,33 @@ int tts_ar_session_logits(tts_ctx *ctx, int request, float *logits_out /*[n_cand
 int tts_ar_session_cancel(tts_ctx *ctx, int request);
 int tts_ar_session_close(tts_ctx *ctx);
 int tts_ar_session_recaptures(const tts_ctx *ctx);
+/* Session audio (additions within version 8): every ONE-candidate request of a session receives HiFi-GAN audio while it decodes, as tts_hifigan_stream
+ * delivers it for a single request. A session that never calls tts_ar_session_enable_audio behaves and allocates exactly as before.
+ * tts_ar_session_enable_audio: after tts_ar_session_open and before the first admit. Reserves the latent pass' K/V rows per slot,
+ *   [layer][slot][S_max][1024] fp16 for K and for V with S_max = 1 + max_text + min(502, max_steps + 10), that is 2 * n_layers * n_slots * S_max * 2048 bytes:
+ *   about as much again as the session's decode cache (max_text + 2 + max_steps + 1 positions per slot), and every buffer the incremental latent pass can
+ *   grow, so that tts_ar_session_recaptures stays 0. TTS_ERR_STATE without an open session, before tts_load_hifigan, after an admission, or when the
+ *   session pinned "ggml_lut" = 1 (that mode's attention kernel has no incremental form); TTS_ERR_ARG for stride_steps < 1; TTS_ERR_HIP on a host-only context.
+ * What tts_ar_session_step adds in such a session: on every stride_steps-th step of the SESSION (a global clock: requests admitted at different steps fall
+ *   due together) and on the step in which a request finishes, ONE incremental latent pass computes the new final rows of every request that is due (after k
+ *   sampled codes the rows 0 .. k are final; a finishing request: its remaining rows) against the K/V rows kept from its earlier passes, and ONE
+ *   tts_hifigan_chunk call decodes, as a ragged batch, the frames [emitted, tts_diffusion_frames(rows so far) - TTS_HFG_HALO_FRAMES) of each (a finishing
+ *   request: to the end). A step in which a request finishes without the clock being due serves the finishing requests only. A row is frozen once audio has
+ *   been decoded from it. The samples wait in a host buffer per request.
+ * tts_ar_session_audio: drains whole frames (a multiple of 256 samples, at most cap_samples) of `request` into out and returns the count, which may be 0;
+ *   *is_last = 1 when the request has finished and this call emptied its buffer (else 0). TTS_ERR_ARG for an unknown, collected or cancelled id, a negative
+ *   cap_samples, a null pointer, or a request of several candidates (re-ranking cannot stream: such requests are admitted and run as before, without audio);
+ *   TTS_ERR_STATE in a session without audio. Audio stays drainable until tts_ar_session_collect or tts_ar_session_cancel, which drop what is left.
+ * tts_ar_session_collect on such a request returns the latents with the frozen rows (no further latent pass runs).
+ *   Contract, for every one-candidate request of an audio session: codes, rows, steps and stop status are those of tts_seed + tts_autoregressive of the
+ *   request alone, bit for bit; the concatenated audio is bit for bit tts_hifigan_decode of the latents that collect returns, with the request's voice; for
+ *   a request that keeps 31 rows or more those latents are tts_autoregressive's bit for bit (the incremental pass always runs the multi-row kernels; a
+ *   shorter request alone ends on the exact-f32 GEMV pass, which sums in another order, and agrees within the 1e-4 relative bound tts_hifigan_stream's short utterances are held to). None of this depends on
+ *   stride_steps, on the slot or on who else is in the batch, and no session call touches the context's generator. Slot reuse, cancel and close leave
+ *   nothing behind that a later request can read: a request's prompt rows are copied in at its admission and every other K/V row is written by the
+ *   request's own passes before it is read. */
+int tts_ar_session_enable_audio(tts_ctx *ctx, int stride_steps);
+int tts_ar_session_audio(tts_ctx *ctx, int request, float *out, int cap_samples, int32_t *is_last);
 /* host probe: the allocator's rule. busy [n_slots] (nonzero = taken): the first index of the lowest run of n_cand free slots, or -1 (also for a null map,
  * n_slots < 1 or n_cand < 1). */
 int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand);

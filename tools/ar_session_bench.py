@@ -11,7 +11,13 @@ is the host clock from the moment the scheduler's step counter reached its arriv
   (c) a full session step (every slot live, all rows at the same step) alternated with tts_ar_step_sample at the same B: what the per-row block costs per step
 Host clock around synchronous calls; the two variants of (c) alternate in blocks, WARM untimed steps in front of each block, then the median and min .. max.
 
-  python tools/ar_session_bench.py [--slots 16] [--requests 24] [--seed 1] [--steps 200] [--warm 20] [--models DIR] [--out FILE]"""
+--audio STRIDE (session audio: tts_ar_session_enable_audio, synthetic HiFi-GAN weights) replaces (a) .. (c) by
+  (d) the session with audio at that stride, drained after every step: per request the wall time from arrival to its first and to its last samples, and the
+      mean time of a tts_ar_session_step call (the audio passes included)
+  (e) the same session without audio: the mean time of a step, and arrival -> collected latents
+  (f) the static baseline: the same requests through tts_hifigan_stream at the same stride, one after another in arrival order
+
+  python tools/ar_session_bench.py [--slots 16] [--requests 24] [--seed 1] [--steps 200] [--warm 20] [--audio STRIDE] [--models DIR] [--out FILE]"""
 import argparse
 import os
 import statistics
@@ -68,10 +74,15 @@ def static_batching(e, reqs, voice, slots):
     return done, time.perf_counter() - t0
 
 
-def session(e, reqs, voice, slots):
+def session(e, reqs, voice, slots, audio=0, stats=None):
+    """audio: the stride of tts_ar_session_enable_audio (0: a session without audio). stats, when given, receives step_ms (every tts_ar_session_step call) and
+    first / last ({request: seconds from arrival to its first / last samples})."""
     clock, t_arr, done, rid_of = 0, {}, {}, {}
     queue = list(range(len(reqs)))
+    step_ms, first, last = [], {}, {}
     e.ar_session_open(slots, 1, max(len(r["tokens"]) for r in reqs), MAX_STEPS, mask_stop=True, retire=True)
+    if audio:
+        e.ar_session_enable_audio(audio)
     t0 = time.perf_counter()
     try:
         while queue or rid_of:
@@ -87,13 +98,66 @@ def session(e, reqs, voice, slots):
                 k = queue.pop(0)
                 rid_of[e.ar_session_admit(reqs[k]["tokens"], voice, 1, reqs[k]["seed"], [reqs[k]["codes"]])] = k
             if rid_of:
+                t1 = time.perf_counter()
                 e.ar_session_step()
+                t2 = time.perf_counter()
+                step_ms.append((t2 - t1) * 1e3)
                 clock += 1
+                if audio:
+                    for rid, k in rid_of.items():
+                        samples, _ = e.ar_session_audio(rid)
+                        if len(samples):
+                            now = time.perf_counter()
+                            first.setdefault(k, now - t_arr[k])
+                            last[k] = now - t_arr[k]
             elif queue:
                 clock = max(clock, reqs[queue[0]]["at"])
     finally:
         e.ar_session_close()
+    if stats is not None:
+        stats.update(step_ms=step_ms, first=first, last=last)
     return done, time.perf_counter() - t0
+
+
+def static_stream(e, reqs, voice, stride):
+    """the requests one after another through tts_hifigan_stream, in arrival order; returns {request: (seconds from the call's start to its first samples,
+    to its last)}. A request that arrives while an earlier call runs waits for it: that queueing delay is not in these numbers."""
+    out = {}
+    for k, r in enumerate(reqs):
+        times = []
+
+        def on_chunk(samples, is_last):
+            times.append(time.perf_counter())
+        e.set_stop_schedule([r["codes"]])
+        e.seed(r["seed"])
+        t0 = time.perf_counter()
+        e.hifigan_stream(r["tokens"], voice, MAX_STEPS, 3, stride, on_chunk=on_chunk)
+        e.set_stop_schedule(None)
+        out[k] = (times[0] - t0, times[-1] - t0)
+    return out
+
+
+def audio_mode(e, reqs, voice, slots, stride, say):
+    session(e, reqs[:min(4, len(reqs))], voice, slots, audio=stride)  # warm-up (untimed): graphs, buffers
+    a, b = {}, {}
+    _, wall_a = session(e, reqs, voice, slots, audio=stride, stats=a)
+    done_b, wall_b = session(e, reqs, voice, slots, stats=b)
+    say("(d) session, audio stride %d: tts_ar_session_step mean %.3f ms median %.3f ms over %d steps (%.2f s in all)" %
+        (stride, statistics.mean(a["step_ms"]), statistics.median(a["step_ms"]), len(a["step_ms"]), wall_a))
+    say("(e) session, no audio      : tts_ar_session_step mean %.3f ms median %.3f ms over %d steps (%.2f s in all); arrival -> latents mean %.1f ms" %
+        (statistics.mean(b["step_ms"]), statistics.median(b["step_ms"]), len(b["step_ms"]), wall_b, statistics.mean(d[1] * 1e3 for d in done_b.values())))
+    t0 = time.perf_counter()
+    st = static_stream(e, reqs, voice, stride)
+    wall_f = time.perf_counter() - t0
+    say("(f) static tts_hifigan_stream, stride %d, one request after another: %.2f s in all" % (stride, wall_f))
+    say("    request  codes  ids | session: first audio  last audio | stream alone: first audio  last audio   (ms from arrival; the stream's from its own start)")
+    for k, r in enumerate(reqs):
+        say("    %7d  %5d  %3d | %20.1f  %10.1f | %25.1f  %10.1f" % (k, r["codes"], len(r["tokens"]), a["first"].get(k, float("nan")) * 1e3,
+                                                                    a["last"].get(k, float("nan")) * 1e3, st[k][0] * 1e3, st[k][1] * 1e3))
+    fa, la = [a["first"][k] * 1e3 for k in a["first"]], [a["last"][k] * 1e3 for k in a["last"]]
+    say("    session: first audio mean %.1f ms p95 %.1f ms, last audio mean %.1f ms p95 %.1f ms" % (statistics.mean(fa), pct(fa, 0.95), statistics.mean(la), pct(la, 0.95)))
+    say("    stream : first audio mean %.1f ms, last audio mean %.1f ms (each from its own start: the queueing behind earlier requests is on top)" %
+        (statistics.mean(v[0] * 1e3 for v in st.values()), statistics.mean(v[1] * 1e3 for v in st.values())))
 
 
 def step_cost(e, voice, B, steps, warm, rounds=4):
@@ -134,6 +198,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warm", type=int, default=20)
+    ap.add_argument("--audio", type=int, default=0, metavar="STRIDE")
     ap.add_argument("--models", default=os.environ.get("TTS_BENCH_MODELS", "/tmp/tts_bench_models"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -155,6 +220,17 @@ def main():
 
     say("tools/ar_session_bench.py: %d requests (seed %d), %d slots, codes %d .. %d, arrivals over %d steps" %
         (len(reqs), a.seed, a.slots, min(r["codes"] for r in reqs), max(r["codes"] for r in reqs), reqs[-1]["at"]))
+    if a.audio:
+        hfg = os.path.join(a.models, "ggml-hifigan-model.bin")
+        if not os.path.exists(hfg):
+            sw.write_hifigan(hfg, seed=77)
+        e.load_hifigan(hfg)
+        audio_mode(e, reqs, voice, a.slots, a.audio, say)
+        e.close()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n" + "\n".join(lines) + "\n")
+        return
     total_codes = sum(r["codes"] for r in reqs)
     for name, fn in (("warm-up (untimed)", static_batching), ("(a) static batching", static_batching), ("(b) session", session)):
         done, wall = fn(e, reqs, voice, a.slots)

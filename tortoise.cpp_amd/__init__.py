@@ -85,6 +85,7 @@ def lib():
         "tts_ar_session_room": (ci, [vp]), "tts_ar_session_step": (ci, [vp]), "tts_ar_session_finished": (ci, [vp, vp, ci]),
         "tts_ar_session_collect": (ci, [vp, ci, vp, vp, vp, vp, vp]), "tts_ar_session_logits": (ci, [vp, ci, vp]),
         "tts_ar_session_cancel": (ci, [vp, ci]), "tts_ar_session_close": (ci, [vp]), "tts_ar_session_recaptures": (ci, [vp]),
+        "tts_ar_session_enable_audio": (ci, [vp, ci]), "tts_ar_session_audio": (ci, [vp, ci, vp, ci, vp]),
         "tts_host_session_first_fit": (ci, [vp, ci, ci]),
         "tts_diffusion_forward": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p]),
         "tts_diffusion": (ci, [vp, _f32p, _i32p, ci, ci, vp, ci, _f32p]),
@@ -401,6 +402,21 @@ class Engine:
 
     def ar_session_recaptures(self):
         return self._ck(self.L.tts_ar_session_recaptures(self.h))
+
+    def ar_session_enable_audio(self, stride):
+        """Right after ar_session_open(): every one-candidate request receives HiFi-GAN audio while it decodes; an audio pass runs on every stride-th step of
+        the session and on the step in which a request finishes (load_hifigan() first)."""
+        self._ck(self.L.tts_ar_session_enable_audio(self.h, stride))
+
+    def ar_session_audio(self, request):
+        """Drains the request's decoded audio: (float32 samples, a multiple of 256, possibly none; is_last: the request has finished and nothing is left)."""
+        cap = 256 * self.frames(500)  # a whole utterance
+        buf = getattr(self, "_session_pcm", None)
+        if buf is None:
+            buf = self._session_pcm = np.empty(cap, np.float32)
+        last = np.zeros(1, np.int32)
+        n = self._ck(self.L.tts_ar_session_audio(self.h, request, _ptr(buf), cap, _ptr(last)))
+        return buf[:n].copy(), bool(last[0])
 
     # ---- voice-conditioning encoder (not in the reference) ----
     def load_voice_encoder(self, path):

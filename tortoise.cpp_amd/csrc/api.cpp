@@ -21,6 +21,9 @@ int ar_session_step(tts_ctx *, const int32_t *toks, const int32_t *n_past, const
 int ar_session_recaptures(const tts_ctx *);
 int ar_session_latents(tts_ctx *, int c0, int n_text, const int32_t *codes502, int nb, int n_mel, float *out);
 int ar_session_logits(tts_ctx *, int c0, int n, float *out);
+int ar_session_audio_enable(tts_ctx *, int max_steps);
+int ar_session_audio_prompt(tts_ctx *, int c0, int n_text);
+int ar_session_extend(tts_ctx *, const ArExtendItem *items, int n_items, float *out);
 int ar_prefill(tts_ctx *, float *);
 int ar_step(tts_ctx *, const int32_t *, int, float *, int mode);
 const int32_t *ar_host_lists(tts_ctx *);
@@ -47,6 +50,10 @@ struct SessionRequest {
   std::vector<int32_t> samples;  // the tokens the next step feeds (after ArStopBook::step)
   int i = 0;                     // tts_autoregressive's loop counter: iterations applied so far
   int state = 0;                 // 0 running, 1 finished, 2 finished by reaching max_steps in strict mode (collect returns TTS_ERR_LIMIT)
+  // Audio (a one-candidate request of a session with tts_ar_session_enable_audio): tts_hifigan_stream's book, HfgStream, per request.
+  bool audio = false, audio_done = false; // audio_done: the request has finished and its last frames are in pcm
+  int have = 0, emitted = 0;              // latent rows held (frozen once a chunk was decoded from them), frames decoded so far
+  std::vector<float> voice, lat, pcm;     // the request's voice [1024]; its latent rows [have][1024]; the samples tts_ar_session_audio has not drained yet
 };
 struct ArSession {
   int n_slots = 0, max_cand = 0, max_text = 0, max_steps = 0;
@@ -58,6 +65,8 @@ struct ArSession {
   std::map<int, SessionRequest> reqs;
   std::vector<int> finished; // ids, oldest first
   int next_id = 0;
+  int audio_stride = 0;      // tts_ar_session_enable_audio: steps of the session's clock between two audio passes (0: a session without audio)
+  long clock = 0;            // steps the session has run
 };
 } // namespace tts
 
@@ -100,6 +109,82 @@ void session_advance(ArSession &s, SessionRequest &r) {
   if (r.state) s.finished.push_back(r.id);
 }
 } // namespace
+
+// One audio pass of a session: every audio request that has just finished, and with clock_due every running one, brings its new final latent rows to ONE
+// incremental latent pass (ar_session_extend) and its new final frames to ONE ragged tts_hifigan_chunk call. stream_emit's rules per request: after k sampled
+// codes the rows stream_final_rows(k) are final and the frames below tts_diffusion_frames(rows) - TTS_HFG_HALO_FRAMES with them; a finished request keeps
+// trimmed_latent_rows rows and is decoded to its end; a row is frozen once audio has been decoded from it.
+static int session_audio_pass(tts_ctx *c, ArSession &s, bool clock_due) {
+  struct Due { SessionRequest *r; std::vector<int32_t> codes; int L, upto; bool last; };
+  std::vector<Due> due;
+  for (auto &kv : s.reqs) {
+    SessionRequest &r = kv.second;
+    if (!r.audio || r.audio_done || (r.state == 0 && !clock_due)) continue;
+    if (r.state == 2) { r.audio_done = true; continue; } // a strict request that found no stop token: an error of its own, nothing more to hear
+    Due d{&r, {}, 0, 0, r.state != 0};
+    std::vector<int> sq = r.book.seq[0];
+    if (d.last) { // what tts_ar_session_collect will return
+      if (sq.size() > 500) sq.resize(500);
+      pad_codes(sq);
+      d.codes.assign(sq.begin(), sq.end());
+      d.L = trimmed_latent_rows(d.codes.data());
+      d.upto = tts_diffusion_frames(d.L);
+      if (d.L < r.have) return fail(c, TTS_ERR_STATE, "tts_ar_session_step: request %d: %d rows were final, the utterance keeps %d", r.id, r.have, d.L);
+    } else { // sq.size() codes so far, none of them the stop token (one candidate: the request ends with it)
+      d.codes.assign(502, 83);
+      d.codes[0] = 8192;
+      std::copy(sq.begin(), sq.begin() + std::min<size_t>(sq.size(), 501), d.codes.begin() + 1);
+      d.L = stream_final_rows(d.codes.data() + 1, (int)sq.size());
+      d.upto = tts_diffusion_frames(d.L) - TTS_HFG_HALO_FRAMES;
+      if (d.L <= r.have || d.upto <= r.emitted) continue;
+    }
+    due.push_back(std::move(d));
+  }
+  if (due.empty()) return TTS_OK;
+  std::vector<ArExtendItem> items;
+  size_t new_rows = 0;
+  for (Due &d : due)
+    if (d.L > d.r->have) { items.push_back(ArExtendItem{d.r->c0, d.r->n_text, d.r->have, d.L, d.codes.data()}); new_rows += (size_t)(d.L - d.r->have); }
+  if (!items.empty()) {
+    std::vector<float> rows(new_rows * TTS_DMODEL);
+    if (int rc = ar_session_extend(c, items.data(), (int)items.size(), rows.data())) return rc;
+    size_t off = 0;
+    for (Due &d : due) {
+      if (d.L <= d.r->have) continue;
+      const size_t n = (size_t)(d.L - d.r->have) * TTS_DMODEL;
+      d.r->lat.insert(d.r->lat.end(), rows.begin() + off, rows.begin() + off + n);
+      d.r->have = d.L;
+      off += n;
+    }
+  }
+  std::vector<float> lat, voices, audio;
+  std::vector<int32_t> n_rows, voice_of, f0, nf;
+  size_t frames = 0;
+  for (Due &d : due) {
+    if (d.upto <= d.r->emitted) continue; // (a finished request that keeps no row, or whose frames are all out)
+    lat.insert(lat.end(), d.r->lat.begin(), d.r->lat.end());
+    voices.insert(voices.end(), d.r->voice.begin(), d.r->voice.end());
+    voice_of.push_back((int32_t)n_rows.size());
+    n_rows.push_back(d.r->have); f0.push_back(d.r->emitted); nf.push_back(d.upto - d.r->emitted);
+    frames += (size_t)(d.upto - d.r->emitted);
+  }
+  if (!n_rows.empty()) {
+    audio.resize(frames * 256);
+    if (int rc = hifigan_chunk(c, lat.data(), n_rows.data(), (int)n_rows.size(), voices.data(), (int)n_rows.size(), voice_of.data(), f0.data(), nf.data(), audio.data()))
+      return rc;
+    size_t off = 0;
+    for (Due &d : due) {
+      if (d.upto <= d.r->emitted) continue;
+      const size_t n = (size_t)(d.upto - d.r->emitted) * 256;
+      d.r->pcm.insert(d.r->pcm.end(), audio.begin() + off, audio.begin() + off + n);
+      d.r->emitted = d.upto;
+      off += n;
+    }
+  }
+  for (Due &d : due)
+    if (d.last) d.r->audio_done = true;
+  return TTS_OK;
+}
 
 hipEvent_t tts::prof_event(tts_ctx *c) {
   if (!c->ev_pool.empty()) { hipEvent_t e = c->ev_pool.back(); c->ev_pool.pop_back(); return e; }
@@ -925,10 +1010,17 @@ int tts_ar_session_admit(tts_ctx *c, const int32_t *text_ids, int n_text, const 
     for (int b = 0; b < n_cand; b++) ids[(size_t)b * P + P - 1] = 8192;
     r.samples.resize(n_cand);
     sample_candidates(c, r.gen, logits0.data(), ids.data(), P, n_cand, r.samples.data());
+    if (s.audio_stride && n_cand == 1) { // the prompt's rows of the latent pass, once, from the decode cache the prompt pass has just written
+      if (int rc = ar_session_audio_prompt(c, c0, n_text)) return rc;
+      r.audio = true;
+      r.voice.assign(voice, voice + TTS_DMODEL);
+    }
     std::fill(s.busy.begin() + c0, s.busy.begin() + c0 + n_cand, (uint8_t)1);
     SessionRequest &slot = s.reqs[r.id] = std::move(r);
     s.next_id++;
     session_advance(s, slot);
+    if (slot.audio && slot.state != 0) // finished with its first code: no step will see it
+      if (int rc = session_audio_pass(c, s, false)) return rc;
     return slot.id;
   });
 }
@@ -987,6 +1079,9 @@ int tts_ar_session_step(tts_ctx *c) {
       session_advance(s, r);
       n_live -= r.state != 0;
     }
+    s.clock++;
+    if (s.audio_stride)
+      if (int rc = session_audio_pass(c, s, s.clock % s.audio_stride == 0)) return rc;
     return n_live;
   });
 }
@@ -1026,7 +1121,9 @@ int tts_ar_session_collect(tts_ctx *c, int request, int32_t *codes_out, int32_t 
       max_rows = std::max(max_rows, rows_out[b]);
     }
     if (steps_out) *steps_out = r.i;
-    if (latents_out) { // the latent pass over the mel prefix that trim_latents keeps, as tts_autoregressive's
+    if (latents_out && r.audio && r.audio_done && r.have == rows_out[0]) { // the frozen rows: what the request's audio was decoded from
+      std::copy(r.lat.begin(), r.lat.end(), latents_out);
+    } else if (latents_out) { // the latent pass over the mel prefix that trim_latents keeps, as tts_autoregressive's
       const int n_mel = std::min(502, max_rows + 1), n_out = std::min(500, n_mel);
       std::vector<float> lat((size_t)r.n_cand * n_out * TTS_DMODEL);
       if (int rc = ar_session_latents(c, r.c0, r.n_text, codes_out, r.n_cand, n_mel, lat.data())) return rc;
@@ -1056,6 +1153,41 @@ int tts_ar_session_cancel(tts_ctx *c, int request) {
   if (!c->session->reqs.count(request)) return fail(c, TTS_ERR_ARG, "tts_ar_session_cancel: no request %d", request);
   session_release(*c->session, request);
   return TTS_OK;
+}
+
+int tts_ar_session_enable_audio(tts_ctx *c, int stride_steps) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_enable_audio");
+  ArSession &s = *c->session;
+  if (stride_steps < 1) return fail(c, TTS_ERR_ARG, "tts_ar_session_enable_audio: stride_steps %d: >= 1", stride_steps);
+  if (!c->hifigan) return fail(c, TTS_ERR_STATE, "tts_ar_session_enable_audio: tts_load_hifigan not called");
+  if (s.next_id > 0) return fail(c, TTS_ERR_STATE, "tts_ar_session_enable_audio: the session has admitted a request (call it right after tts_ar_session_open)");
+  if (s.ggml_lut) return fail(c, TTS_ERR_STATE, "tts_ar_session_enable_audio: the session runs under ggml_lut = 1, whose latent pass has no incremental form");
+  return guarded(c, [&] {
+    SessionOptions opt(c, s);
+    if (int rc = ar_session_audio_enable(c, s.max_steps)) return rc;
+    s.audio_stride = stride_steps;
+    return (int)TTS_OK;
+  });
+}
+
+int tts_ar_session_audio(tts_ctx *c, int request, float *out, int cap_samples, int32_t *is_last) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_audio");
+  ArSession &s = *c->session;
+  if (!s.audio_stride) return fail(c, TTS_ERR_STATE, "tts_ar_session_audio: tts_ar_session_enable_audio not called");
+  auto it = s.reqs.find(request);
+  if (it == s.reqs.end()) return fail(c, TTS_ERR_ARG, "tts_ar_session_audio: no request %d", request);
+  SessionRequest &r = it->second;
+  if (!r.audio) return fail(c, TTS_ERR_ARG, "tts_ar_session_audio: request %d has %d candidates (several candidates are re-ranked and cannot stream)", request, r.n_cand);
+  if (cap_samples < 0 || (cap_samples > 0 && !out) || !is_last) return fail(c, TTS_ERR_ARG, "tts_ar_session_audio: bad argument");
+  return guarded(c, [&] {
+    const size_t n = std::min(r.pcm.size(), (size_t)cap_samples) / 256 * 256; // whole frames
+    std::copy(r.pcm.begin(), r.pcm.begin() + n, out);
+    r.pcm.erase(r.pcm.begin(), r.pcm.begin() + n);
+    *is_last = (r.audio_done && r.pcm.empty()) ? 1 : 0;
+    return (int)n;
+  });
 }
 
 int tts_diffusion_frames(int L) { return L * 4 * 24000 / 22050; }

@@ -359,6 +359,25 @@ __global__ __launch_bounds__(256) void epilogue_kernel(const float *__restrict__
   }
 }
 
+// EPI_QKV of the split-precision path (ks = 1, pscale = 1 / 64) for a packed row space in which every row names its own cache row (ar_session_extend):
+// row r's K and V go to cache row row_dst[r] = slot * max_pos + position. The arithmetic is epilogue_kernel<EPI_QKV>'s.
+__global__ __launch_bounds__(256) void epilogue_qkv_ragged_kernel(const float *__restrict__ part, const float *__restrict__ bias, float *__restrict__ out,
+                                                                  const int *__restrict__ row_dst, __half *__restrict__ kdst, __half *__restrict__ vdst,
+                                                                  float pscale) {
+  const int r = blockIdx.x;
+  const size_t dst = (size_t)row_dst[r] * D;
+  for (int n = blockIdx.y * 256 + threadIdx.x; n < 3 * D; n += 256 * gridDim.y) {
+    float v = part[(size_t)r * 3 * D + n];
+    v = v * pscale + bias[n];
+    v = f16_round(v);
+    out[(size_t)r * 3 * D + n] = v;
+    if (n >= D) {
+      __half *base = (n < 2 * D) ? kdst : vdst;
+      base[dst + ((n < 2 * D) ? n - D : n - 2 * D)] = __float2half_rn(v);
+    }
+  }
+}
+
 // Causal attention of the multi-row passes (latent pass: 16 candidates x ~200 rows x 16 heads), default (non-LUT) numerics. One workgroup per
 // (candidate, head, block of 64 rows): lane = row, and the four waves split the KEYS (wave w takes the groups of 8 keys w, w + 4, ..) so that every SIMD
 // holds several waves to hide the LDS latency (one thread per row alone is < 1 wave per SIMD at 3 216 rows). The keys are staged through LDS in chunks of
@@ -368,22 +387,25 @@ __global__ __launch_bounds__(256) void epilogue_kernel(const float *__restrict__
 // Same arithmetic class as attention_kernel below (f32 weights, f32 accumulation; only the summation order and exp2 vs expf differ), which needed one wave
 // per (row, head) and re-read every K/V row from L2 per row: 225 us per layer at 3 216 rows.
 typedef _Float16 ar_half2 __attribute__((ext_vector_type(2)));
-__global__ __launch_bounds__(256) void attention_rows_kernel(const float *__restrict__ qkv, const __half *__restrict__ kc,
-                                                             const __half *__restrict__ vc, float *__restrict__ out, int S, int n_past,
-                                                             int max_pos) {
+// The workgroup's work, shared by attention_rows_kernel and attention_rows_ragged_kernel: rows s0 .. s0 + 63 of one sequence of S rows that sits n_past keys
+// into its cache. q: the sequence's first row in the qkv buffer at the head's columns (row stride 3 * D), kb / vb: key 0 of the sequence's cache at the head's
+// columns, o_rows: the sequence's first output row at the head's columns. A row's bits depend on its own query and the keys before it only: the keys are walked
+// from absolute position 0 in chunks of 128 and groups of 8 whatever S, n_past and s0 are.
+__device__ __forceinline__ void attention_rows_block(const float *__restrict__ q, const __half *__restrict__ kb, const __half *__restrict__ vb,
+                                                     float *__restrict__ o_rows, int S, int n_past, int s0) {
   constexpr int CH = 128; // keys per LDS chunk: 32 KB of LDS, three workgroups per CU (the registers allow three waves per SIMD)
   constexpr float L2E = 1.4426950408889634f;
   __shared__ __attribute__((aligned(16))) __half kvs[2 * CH * HD]; // K chunk | V chunk; reused for the merge: acc[wave][32 dims][lane], two passes
   __shared__ float wm[4][64], wl[4][64];
   __half *ks = kvs, *vs = kvs + CH * HD;
-  const int c = blockIdx.x, h = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int s0 = blockIdx.z * 64, s = s0 + lane;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s = s0 + lane;
   const bool live = s < S;
   const int nk = live ? n_past + s + 1 : 0;         // keys this row sees (ggml_diag_mask_inf(n_past))
   const int nk_block = n_past + min(S, s0 + 64);     // keys the block's last row sees
   ar_half2 q2[HD / 2];
   {
-    const float *qp = qkv + (size_t)(c * S + (live ? s : S - 1)) * 3 * D + h * HD;
+    const float *qp = q + (size_t)(live ? s : S - 1) * 3 * D;
 #pragma unroll
     for (int i = 0; i < HD / 4; i++) {
       const float4 f = ((const float4 *)qp)[i];
@@ -391,8 +413,6 @@ __global__ __launch_bounds__(256) void attention_rows_kernel(const float *__rest
       q2[2 * i + 1] = (ar_half2){(_Float16)f.z, (_Float16)f.w};
     }
   }
-  const __half *kb = kc + (size_t)c * max_pos * D + h * HD;
-  const __half *vb = vc + (size_t)c * max_pos * D + h * HD;
   float m = -INFINITY, l = 0.f, acc[HD];
 #pragma unroll
   for (int d = 0; d < HD; d++) acc[d] = 0.f;
@@ -480,9 +500,28 @@ __global__ __launch_bounds__(256) void attention_rows_kernel(const float *__rest
     }
   }
   if (!live) return;
-  float *op = out + (size_t)(c * S + s) * D + h * HD + wave * 16;
+  float *op = o_rows + (size_t)s * D + wave * 16;
 #pragma unroll
   for (int i = 0; i < 4; i++) ((float4 *)op)[i] = make_float4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+}
+__global__ __launch_bounds__(256) void attention_rows_kernel(const float *__restrict__ qkv, const __half *__restrict__ kc,
+                                                             const __half *__restrict__ vc, float *__restrict__ out, int S, int n_past,
+                                                             int max_pos) {
+  const int c = blockIdx.x, h = blockIdx.y;
+  attention_rows_block(qkv + (size_t)c * S * 3 * D + h * HD, kc + (size_t)c * max_pos * D + h * HD, vc + (size_t)c * max_pos * D + h * HD,
+                       out + (size_t)c * S * D + h * HD, S, n_past, blockIdx.z * 64);
+}
+// The ragged form (ar_session_extend): sequence i of the launch is items[i] = {first row in the packed row space, S, n_past, cache slot}: its S new rows sit
+// n_past keys into slot's cache, whose earlier rows were written by earlier passes. grid (n_items, NH, ceil(longest S / 64)): a block past its own sequence's
+// rows leaves before any barrier.
+__global__ __launch_bounds__(256) void attention_rows_ragged_kernel(const float *__restrict__ qkv, const __half *__restrict__ kc,
+                                                                    const __half *__restrict__ vc, float *__restrict__ out,
+                                                                    const int4 *__restrict__ items, int max_pos) {
+  const int4 it = items[blockIdx.x];
+  const int h = blockIdx.y, s0 = blockIdx.z * 64;
+  if (s0 >= it.y) return;
+  attention_rows_block(qkv + (size_t)it.x * 3 * D + h * HD, kc + (size_t)it.w * max_pos * D + h * HD, vc + (size_t)it.w * max_pos * D + h * HD,
+                       out + (size_t)it.x * D + h * HD, it.y, it.z, s0);
 }
 
 // Causal attention for one (row, head): q from the f16-rounded qkv buffer, K/V from an fp16 cache
@@ -1377,6 +1416,13 @@ struct ArState {
   int sess_captures0 = -1;   // graph_captures when the session's first step had run (tts_ar_session_recaptures)
   DevBuf row_off;            // multi: [tiles * 16] ints, P of the row's group (0 past the batch); the step state's n_past is then the step index
   DevBuf voice, kcache, vcache, lat_k, lat_v;
+  // Session audio (tts_ar_session_enable_audio): the latent pass' K/V rows of every slot, kept from one incremental pass (ar_session_extend) to the next:
+  // [layer][slot][sa_S][1024] fp16 each, sa_S = 1 + max_text + min(502, max_steps + 10), that is 2 * n_layers * n_slots * sa_S * 2048 bytes in all, about as
+  // much again as the session's decode cache (kcache + vcache: max_text + 2 + max_steps + 1 positions per slot). The decode cache's own mel rows cannot
+  // serve: they come from the GEMV path, in another summation order.
+  DevBuf sa_k, sa_v, sa_tab; // sa_tab: one launch sequence's tables, [items int4[n_slots] | row_dst int[sa_rows]]
+  int sa_S = 0;              // 0: the session has no audio
+  int sa_rows = 0;           // the most rows one launch sequence packs (the buffers reserved at enable time hold them)
   DevBuf h, xn, qkv, att, ff, part, desc, logits, hn, a_hi, a_lo;
   // decode-step graph
   DevBuf d_toks;
@@ -2455,6 +2501,7 @@ int ar_session_open(tts_ctx *ctx, int n_slots, int max_cand, int max_text, int m
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   st->sess_captures0 = -1;
   st->session = true;
+  st->sa_S = 0; st->sa_rows = 0; // no audio until tts_ar_session_enable_audio
   st->B = B;
   return TTS_OK;
 }
@@ -2463,6 +2510,7 @@ void ar_session_close(tts_ctx *ctx) {
   ArState *st = ctx->ar;
   if (!st || !st->session) return;
   st->session = false;
+  st->sa_S = 0; st->sa_rows = 0;
   st->B = 0; // tts_ar_begin* starts over; the session's step graph stays for the next session of the same shape
 }
 
@@ -2534,6 +2582,128 @@ int ar_session_logits(tts_ctx *ctx, int c0, int n, float *out) {
   ArState *st = ctx->ar;
   if (!st || !st->session || c0 < 0 || n < 1 || c0 + n > st->B) return fail(ctx, TTS_ERR_STATE, "tts_ar_session_open not called");
   TTS_HIP(ctx, hipMemcpy(out, st->logits.as<float>() + (size_t)c0 * V, (size_t)n * V * 4, hipMemcpyDeviceToHost));
+  return TTS_OK;
+}
+
+// ---- session audio: the ragged, incremental latent pass ----
+// Reserves the per-slot latent K/V rows and every buffer a launch sequence of ar_session_extend can grow (the captured step bakes h, qkv, att and ff into its
+// nodes: nothing may move once the session steps). Called before the first admission.
+int ar_session_audio_enable(tts_ctx *ctx, int max_steps) {
+  ArState *st = ctx->ar;
+  if (!st || !st->session || st->B < 1) return fail(ctx, TTS_ERR_STATE, "tts_ar_session_open not called");
+  const int B = st->B, S_max = 1 + st->n_text + std::min(502, max_steps + 10);
+  const size_t kv = (size_t)st->n_layers * B * S_max * D * sizeof(__half);
+  TTS_HIP(ctx, st->sa_k.reserve(kv));
+  TTS_HIP(ctx, st->sa_v.reserve(kv));
+  // every live request may bring its whole utterance to one pass (stride above max_steps, all finishing together); past 4096 rows the pass runs in
+  // several launch sequences (a row's bits do not depend on what else is packed beside it)
+  const int rows = std::max(512, std::min(4096, B * std::min(500, max_steps + 1)));
+  TTS_HIP(ctx, st->sa_tab.reserve((size_t)B * sizeof(int4) + (size_t)rows * sizeof(int)));
+  CHECK(reserve_rows(ctx, st, rows));
+  TTS_HIP(ctx, hipMemsetAsync(st->h.p, 0, st->h.cap, ctx->stream)); // ar_session_open's zeroed padding rows, again: h may have moved
+  const size_t rpad = (size_t)(rows + 127) & ~(size_t)127; // launch_mfma_matmul's operands
+  TTS_HIP(ctx, st->a_hi.reserve(rpad * FF * sizeof(__half)));
+  TTS_HIP(ctx, st->a_lo.reserve(rpad * FF * sizeof(__half)));
+  TTS_HIP(ctx, st->part.reserve(rpad * FF * sizeof(float)));
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  st->sa_S = S_max;
+  st->sa_rows = rows;
+  return TTS_OK;
+}
+
+// A one-candidate request's prompt rows [0, 1 + n_text), from the decode cache of its slot (its prompt pass has just written them) into the slot's latent K/V.
+int ar_session_audio_prompt(tts_ctx *ctx, int c0, int n_text) {
+  ArState *st = ctx->ar;
+  if (!st || !st->session || !st->sa_S || c0 < 0 || c0 >= st->B || n_text < 1 || n_text > st->n_text)
+    return fail(ctx, TTS_ERR_STATE, "tts_ar_session_enable_audio not called");
+  const size_t src0 = (size_t)c0 * st->max_pos * D, dst0 = (size_t)c0 * st->sa_S * D;
+  copy_prompt_kv_kernel<<<dim3(1 + n_text, 1, 2 * st->n_layers), 256, 0, ctx->stream>>>(
+      st->kcache.as<__half>() + src0, st->vcache.as<__half>() + src0, (size_t)st->B * st->max_pos * D, st->sa_k.as<__half>() + dst0, st->sa_v.as<__half>() + dst0,
+      (size_t)st->B * st->sa_S * D, st->sa_S, st->n_layers);
+  TTS_HIP(ctx, hipGetLastError());
+  return TTS_OK;
+}
+
+// One launch sequence over the packed new rows of items [0, n): run_layers' loop on the split-precision MFMA path whatever the row count (the GEMMs pad to
+// 128 rows themselves), with the two per-row pieces in their ragged forms. out: the items' rows back to back.
+static int extend_launch(tts_ctx *ctx, ArState *st, const ArExtendItem *items, int n, float *out) {
+  int rows = 0, max_S = 0;
+  for (int k = 0; k < n; k++) { rows += items[k].upto - items[k].have; max_S = std::max(max_S, items[k].upto - items[k].have); }
+  std::vector<int4> desc((size_t)rows);
+  std::vector<int> tab((size_t)4 * st->B + rows);
+  int *row_dst = tab.data() + (size_t)4 * st->B;
+  for (int k = 0, r = 0; k < n; k++) {
+    const ArExtendItem &it = items[k];
+    const int n_past = 1 + it.n_text + it.have;
+    tab[4 * k] = r; tab[4 * k + 1] = it.upto - it.have; tab[4 * k + 2] = n_past; tab[4 * k + 3] = it.slot;
+    for (int j = it.have; j < it.upto; j++, r++) {
+      desc[r] = make_int4(2, it.codes502[j], 1, j);
+      row_dst[r] = it.slot * st->sa_S + 1 + it.n_text + j;
+    }
+  }
+  TTS_HIP(ctx, hipMemcpyAsync(st->sa_tab.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+  const int4 *d_items = st->sa_tab.as<int4>();
+  const int *d_row_dst = st->sa_tab.as<int>() + (size_t)4 * st->B;
+  CHECK(embed(ctx, st, desc));
+  float *h = st->h.as<float>(), *xn = st->xn.as<float>(), *qkv = st->qkv.as<float>(), *att = st->att.as<float>(), *ff = st->ff.as<float>();
+  const KvDst nokv{nullptr, nullptr, 1, 0, 0, 0};
+  const float ps = 1.0f / W16_SCALE;
+  const size_t layer_stride = (size_t)st->B * st->sa_S * D;
+  for (int l = 0; l < st->n_layers; l++) {
+    const ArLayerDev &w = st->L[l];
+    __half *kc = st->sa_k.as<__half>() + l * layer_stride, *vc = st->sa_v.as<__half>() + l * layer_stride;
+    { ProfScope p(ctx, "ar_layernorm");
+      layernorm_kernel<<<rows, 256, 0, ctx->stream>>>(h, w.ln1_g, w.ln1_b, xn); }
+    CHECK(launch_mfma_matmul(ctx, st, xn, rows, w.s_attn, 3 * D, D));
+    { ProfScope p(ctx, "ar_epilogue");
+      epilogue_qkv_ragged_kernel<<<dim3(rows, 3 * D / 256), 256, 0, ctx->stream>>>(st->part.as<float>(), w.b_attn, qkv, d_row_dst, kc, vc, ps); }
+    { ProfScope p(ctx, "ar_attention");
+      attention_rows_ragged_kernel<<<dim3(n, NH, (max_S + 63) / 64), 256, 0, ctx->stream>>>(qkv, kc, vc, att, d_items, st->sa_S); }
+    CHECK(launch_mfma_matmul(ctx, st, att, rows, w.s_proj, D, D));
+    CHECK(launch_epilogue<EPI_RESID>(ctx, st, 1, rows, D, D, w.b_proj, h, D, nokv, ps));
+    { ProfScope p(ctx, "ar_layernorm");
+      layernorm_kernel<<<rows, 256, 0, ctx->stream>>>(h, w.ln2_g, w.ln2_b, xn); }
+    CHECK(launch_mfma_matmul(ctx, st, xn, rows, w.s_fc, FF, D));
+    CHECK(launch_epilogue<EPI_GELU>(ctx, st, 1, rows, FF, FF, w.b_fc, ff, FF, nokv, ps));
+    CHECK(launch_mfma_matmul(ctx, st, ff, rows, w.s_fc2, D, FF));
+    CHECK(launch_epilogue<EPI_RESID>(ctx, st, 1, rows, D, D, w.b_fc2, h, D, nokv, ps));
+  }
+  float *hn = st->hn.as<float>();
+  layernorm_kernel<<<rows, 256, 0, ctx->stream>>>(h, st->lnf_g, st->lnf_b, xn);
+  layernorm_kernel<<<rows, 256, 0, ctx->stream>>>(xn, st->lmh_g, st->lmh_b, hn);
+  TTS_HIP(ctx, hipGetLastError());
+  for (int k = 0, r = 0; k < n; k++) {
+    const int S = items[k].upto - items[k].have;
+    TTS_HIP(ctx, hipMemcpyAsync(out + (size_t)r * D, hn + (size_t)r * D, (size_t)S * D * 4, hipMemcpyDeviceToHost, ctx->stream));
+    r += S;
+  }
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return TTS_OK;
+}
+
+// The latent rows [have, upto) of every item (a one-candidate request in slot `slot` whose rows [0, have) went through earlier calls), computed alone
+// against the K/V rows those calls left: bit for bit the rows of a full latent pass (tts_ar_latents of 32 rows or more). Every argument is checked first.
+int ar_session_extend(tts_ctx *ctx, const ArExtendItem *items, int n_items, float *out) {
+  ArState *st = ctx->ar;
+  if (!st || !st->session || !st->sa_S) return fail(ctx, TTS_ERR_STATE, "tts_ar_session_enable_audio not called");
+  if (ctx->ggml_lut) return fail(ctx, TTS_ERR_STATE, "ar_session_extend: no incremental latent pass under ggml_lut = 1");
+  if (!items || n_items < 1 || n_items > st->B || !out) return fail(ctx, TTS_ERR_ARG, "ar_session_extend: bad argument");
+  for (int k = 0; k < n_items; k++) {
+    const ArExtendItem &it = items[k];
+    if (it.slot < 0 || it.slot >= st->B || it.n_text < 1 || it.n_text > st->n_text || it.have < 0 || it.upto <= it.have || it.upto > 500 || !it.codes502)
+      return fail(ctx, TTS_ERR_ARG, "ar_session_extend: item %d: slot %d, %d ids, rows [%d, %d)", k, it.slot, it.n_text, it.have, it.upto);
+    if (1 + it.n_text + it.upto > st->sa_S)
+      return fail(ctx, TTS_ERR_LIMIT, "ar_session_extend: item %d ends at position %d of %d", k, 1 + it.n_text + it.upto, st->sa_S);
+    for (int j = it.have; j < it.upto; j++)
+      if (it.codes502[j] < 0 || it.codes502[j] >= V) return fail(ctx, TTS_ERR_ARG, "mel code %d out of range", it.codes502[j]);
+  }
+  for (int k0 = 0; k0 < n_items;) { // launch sequences of at most sa_rows rows (one item has at most 500)
+    int k1 = k0, rows = 0;
+    while (k1 < n_items && rows + items[k1].upto - items[k1].have <= st->sa_rows) { rows += items[k1].upto - items[k1].have; k1++; }
+    CHECK(extend_launch(ctx, st, items + k0, k1 - k0, out));
+    out += (size_t)rows * D;
+    k0 = k1;
+  }
   return TTS_OK;
 }
 

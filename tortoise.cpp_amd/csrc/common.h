@@ -95,6 +95,9 @@ struct Tokenizer;
 struct SamplerPool;
 void sampler_pool_free(SamplerPool *p);
 struct ArSession; // the book of an open session (tts_ar_session_*): api.cpp
+// One request's share of an incremental latent pass (ar.hip: ar_session_extend): the rows [have, upto) of the request in slot `slot`, whose prompt has n_text
+// ids; codes502: the pass' input row by row (8192, then the sampled codes).
+struct ArExtendItem { int slot, n_text, have, upto; const int32_t *codes502; };
 // The autoregressive sampler's controls (options "ar_temperature", "ar_top_k", "ar_top_p", "ar_repetition_penalty"): the defaults are the literals of
 // process_logits_and_sample (main.cpp:4753-4806); upstream tortoise-tts passes the same four to HF generate on every call.
 struct SamplerParams {
