@@ -336,6 +336,9 @@ __global__ __launch_bounds__(256) void epilogue_kernel(const float *__restrict__
     for (int s = 1; s < ks; s++) v += part[((size_t)s * rows + r) * N + n];
     v = v * pscale + bias[n]; // pscale = 1 (f32 path) or 1/64 (split-precision weights are pre-scaled; exact power of 2)
     if (MODE == EPI_QKV) {
+      // the f32 sum is a value of its own, as in the reference (f32 add, then the fp16 conversion): without the empty asm hipcc fuses the FMA and the
+      // conversion into v_fma_mixlo_f16, which rounds the exact sum ONCE to fp16 and lands on the other neighbour at about half of the f32 ties
+      asm volatile("" : "+v"(v));
       v = f16_round(v);
       out[(size_t)r * ldo + n] = v;
       if (n >= D) {
@@ -369,6 +372,7 @@ __global__ __launch_bounds__(256) void epilogue_qkv_ragged_kernel(const float *_
   for (int n = blockIdx.y * 256 + threadIdx.x; n < 3 * D; n += 256 * gridDim.y) {
     float v = part[(size_t)r * 3 * D + n];
     v = v * pscale + bias[n];
+    asm volatile("" : "+v"(v)); // as epilogue_kernel<EPI_QKV>: round to f32, then to fp16
     v = f16_round(v);
     out[(size_t)r * 3 * D + n] = v;
     if (n >= D) {
