@@ -389,7 +389,8 @@ int tts_hifigan_stream_recaptures(const tts_ctx *ctx);
  *   (tts_ar_session_recaptures: decode-step graphs captured after the session's first step, 0). The step graph is kept for the next session of the same shape.
  *   The options "ar_temperature", "ar_top_k", "ar_top_p", "ar_repetition_penalty", "ar_penalty_scope", "ar_weights", "ggml_lut" and "device_topk" are read
  *   HERE and hold for the whole session: tts_set_option on an open session's context changes what later calls outside the session see, never the session.
- *   flags: TTS_AR_MASK_STOP / TTS_AR_RETIRE with their tts_autoregressive meaning, for every request. Replaces any tts_ar_begin* state; a session that is
+ *   flags: TTS_AR_MASK_STOP / TTS_AR_RETIRE with their tts_autoregressive meaning, for every request; TTS_AR_ROW_CONTROLS: see "Per-request sampler
+ *   controls" below. Replaces any tts_ar_begin* state; a session that is
  *   already open is closed first. TTS_ERR_ARG: n_slots < 1, max_cand outside 1 .. n_slots, max_text < 1, max_steps < 1, unknown flags; TTS_ERR_LIMIT:
  *   max_text > 404, max_steps > 500, more than 1024 positions, more than 4096 slots.
  *   While a session is open tts_ar_begin*, tts_ar_prefill, tts_ar_step*, tts_ar_latents, tts_autoregressive* and tts_hifigan_stream return TTS_ERR_STATE;
@@ -454,6 +455,44 @@ int tts_ar_session_recaptures(const tts_ctx *ctx);
  *   request's own passes before it is read. */
 int tts_ar_session_enable_audio(tts_ctx *ctx, int stride_steps);
 int tts_ar_session_audio(tts_ctx *ctx, int request, float *out, int cap_samples, int32_t *is_last);
+/* Per-request sampler controls and step limit (additions within version 8; no prototype changed). tts_ar_session_admit runs every request under the options
+ * the session pinned when it was opened. tts_ar_session_admit_ex takes a request descriptor that carries the request's own.
+ * tts_ar_request: plain C and able to grow: struct_size is sizeof(tts_ar_request) as the CALLER's header declares it, set by the caller before
+ *   tts_ar_request_init. Version 8 refuses a struct_size below its own sizeof(tts_ar_request) and reads exactly that many bytes. The rule for growth: fields
+ *   are only ever appended, and a library that declares a longer struct is to read only the fields struct_size covers. The five controls are doubles and are checked with the
+ *   very predicate tts_set_option applies to "ar_temperature", "ar_top_k", "ar_top_p", "ar_repetition_penalty" and "ar_penalty_scope". max_steps: 0 = the
+ *   session's, else 1 .. the session's max_steps (the request then stops there exactly as tts_autoregressive with that max_steps would).
+ * tts_ar_request_init: fills every field from the options the OPEN SESSION pinned (not from what tts_set_option holds now); n_cand = 1, seed = 0, stop_at =
+ *   NULL, max_steps = 0. TTS_ERR_ARG: a null pointer or a struct_size below the version 8 size; TTS_ERR_STATE without an open session.
+ * tts_ar_session_open accepts one more flag, TTS_AR_ROW_CONTROLS: only a session opened with it admits a request whose controls differ from the session's.
+ *   Such a session ends its captured step with a prefilter that reads every row's keep bound, penalty and penalty scope from a device table with one entry
+ *   per slot, written at admission for the slots the request takes, outside the graph; the step bakes none of the three in, so no admission, whatever its
+ *   controls, re-captures (tts_ar_session_recaptures stays 0), and the graph sits in a slot of its own: a session of the same shape opened without the flag
+ *   still finds its graph. Without the flag the session runs the graph it ran before, node for node. TTS_AR_MASK_STOP, TTS_AR_RETIRE, "ar_weights",
+ *   "ggml_lut" and "device_topk" stay per session. Step time against a session without the flag: profiles/ar_session_controls.txt (one measurement, 16 slots: the
+ *   difference lies inside the run-to-run spread).
+ * tts_ar_session_admit_ex: tts_ar_session_admit with the descriptor's n_cand, seed and stop_at, under every rule of that call, and returns the request id.
+ *   The request is sampled under its own controls from its first code (drawn at admission from the prompt pass's logits) to its last, and everything
+ *   tts_ar_session_collect returns for it is bit for bit what tts_set_option of its five controls + tts_seed(seed) + tts_ar_set_stop_schedule +
+ *   tts_autoregressive(n_cand, its max_steps, the session's flags) returns for it alone. A request whose top_k is above 100 takes the full-row path for
+ *   its rows only (tts_ar_topk_fallbacks counts them as in the single call). All checks run before any device work: TTS_ERR_ARG for a null descriptor, a
+ *   struct_size too small, a control tts_set_option would refuse, max_steps < 0; TTS_ERR_LIMIT for max_steps above the session's; TTS_ERR_STATE for controls
+ *   that differ from the session's in a session opened without TTS_AR_ROW_CONTROLS (the session stays usable; a per-request max_steps needs no device
+ *   support and is accepted with or without the flag). With the session's own controls and max_steps 0 the call IS tts_ar_session_admit.
+ * tts_host_ar_request_check: host probe, no GPU: the status tts_ar_session_admit_ex's descriptor checks return in a session of max_cand and max_steps
+ *   (TTS_OK, TTS_ERR_ARG or TTS_ERR_LIMIT; the text, the voice, free slots and the open flag are not its business). */
+enum { TTS_AR_ROW_CONTROLS = 8 }; /* a tts_ar_session_open flag, beside TTS_AR_MASK_STOP and TTS_AR_RETIRE */
+typedef struct tts_ar_request {
+  uint32_t struct_size;       /* sizeof(tts_ar_request): set by the caller before tts_ar_request_init */
+  int32_t n_cand;
+  uint32_t seed;
+  int32_t max_steps;          /* 0: the session's */
+  const int32_t *stop_at;     /* [n_cand] or NULL */
+  double temperature, top_k, top_p, repetition_penalty, penalty_scope;
+} tts_ar_request;
+int tts_ar_request_init(tts_ctx *ctx, tts_ar_request *req);
+int tts_ar_session_admit_ex(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice1024, const tts_ar_request *req);
+int tts_host_ar_request_check(const tts_ar_request *req, int max_cand, int max_steps);
 /* host probe: the allocator's rule. busy [n_slots] (nonzero = taken): the first index of the lowest run of n_cand free slots, or -1 (also for a null map,
  * n_slots < 1 or n_cand < 1). */
 int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand);

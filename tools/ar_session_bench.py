@@ -17,7 +17,16 @@ Host clock around synchronous calls; the two variants of (c) alternate in blocks
   (e) the same session without audio: the mean time of a step, and arrival -> collected latents
   (f) the static baseline: the same requests through tts_hifigan_stream at the same stride, one after another in arrival order
 
-  python tools/ar_session_bench.py [--slots 16] [--requests 24] [--seed 1] [--steps 200] [--warm 20] [--audio STRIDE] [--models DIR] [--out FILE]"""
+--row-controls (sessions opened with TTS_AR_ROW_CONTROLS: the step ends with the per-row prefilter) replaces (a) .. (c) by the same arrival list through
+  (g) a uniform session (every request under the session's controls: the step ends with the uniform prefilter)
+  (h) a rows session whose requests all carry the session's own controls: the work is identical, only the step's last node differs
+  (i) a rows session with mixed controls (a quarter of the requests each: the session's; temperature 1.3, top_k 5, top_p 0.5, penalty 1.2; scope 1, penalty 3,
+      top_k 100; scope 1, top_k 200, whose rows take the full-row path). Other codes are sampled, the stop schedule keeps the lengths: the same number of steps.
+(g) and (h) alternate --rounds times; per run the mean and median time of a tts_ar_session_step call, then per kind the median over the runs and the run-to-run
+spread (min .. max of the runs' means). --uniform-only: (g) alone (the same list on another build of the library, through TTS_LIB_PATH).
+
+  python tools/ar_session_bench.py [--slots 16] [--requests 24] [--seed 1] [--steps 200] [--warm 20] [--audio STRIDE | --row-controls [--rounds 3] | --uniform-only]
+                                   [--models DIR] [--out FILE]"""
 import argparse
 import os
 import statistics
@@ -74,13 +83,20 @@ def static_batching(e, reqs, voice, slots):
     return done, time.perf_counter() - t0
 
 
-def session(e, reqs, voice, slots, audio=0, stats=None):
+MIXED_CONTROLS = [None, dict(temperature=1.3, top_k=5, top_p=0.5, penalty=1.2, scope=0), dict(scope=1, penalty=3.0, top_k=100), dict(scope=1, top_k=200)]
+
+
+def session(e, reqs, voice, slots, audio=0, stats=None, rows=None):
     """audio: the stride of tts_ar_session_enable_audio (0: a session without audio). stats, when given, receives step_ms (every tts_ar_session_step call) and
-    first / last ({request: seconds from arrival to its first / last samples})."""
+    first / last ({request: seconds from arrival to its first / last samples}). rows: None = a uniform session; "own" = a rows session, every request
+    admitted with the session's own controls through tts_ar_session_admit_ex; "mixed" = request k under MIXED_CONTROLS[k % 4]."""
     clock, t_arr, done, rid_of = 0, {}, {}, {}
     queue = list(range(len(reqs)))
     step_ms, first, last = [], {}, {}
-    e.ar_session_open(slots, 1, max(len(r["tokens"]) for r in reqs), MAX_STEPS, mask_stop=True, retire=True)
+    if rows:
+        e.ar_session_open(slots, 1, max(len(r["tokens"]) for r in reqs), MAX_STEPS, mask_stop=True, retire=True, row_controls=True)
+    else:
+        e.ar_session_open(slots, 1, max(len(r["tokens"]) for r in reqs), MAX_STEPS, mask_stop=True, retire=True)
     if audio:
         e.ar_session_enable_audio(audio)
     t0 = time.perf_counter()
@@ -96,7 +112,8 @@ def session(e, reqs, voice, slots, audio=0, stats=None):
                 done[k] = (clock - reqs[k]["at"], time.perf_counter() - t_arr[k])
             while queue and reqs[queue[0]]["at"] <= clock and e.ar_session_room() >= reqs[queue[0]]["n_cand"]:
                 k = queue.pop(0)
-                rid_of[e.ar_session_admit(reqs[k]["tokens"], voice, 1, reqs[k]["seed"], [reqs[k]["codes"]])] = k
+                kw = dict(controls=(MIXED_CONTROLS[k % 4] or {}) if rows == "mixed" else {}) if rows else {}
+                rid_of[e.ar_session_admit(reqs[k]["tokens"], voice, 1, reqs[k]["seed"], [reqs[k]["codes"]], **kw)] = k
             if rid_of:
                 t1 = time.perf_counter()
                 e.ar_session_step()
@@ -160,6 +177,35 @@ def audio_mode(e, reqs, voice, slots, stride, say):
         (statistics.mean(v[0] * 1e3 for v in st.values()), statistics.mean(v[1] * 1e3 for v in st.values())))
 
 
+def row_controls_mode(e, reqs, voice, slots, rounds, say, uniform_only=False):
+    kinds = [("(g) uniform session", None)] if uniform_only else [("(g) uniform session", None), ("(h) rows session, own controls", "own")]
+    for _, rows in kinds:  # warm-up (untimed): graphs, buffers
+        session(e, reqs[:min(4, len(reqs))], voice, slots, rows=rows)
+    means = {name: [] for name, _ in kinds}
+    say("    %-34s %5s  %6s  %12s  %12s  %10s  %9s" % ("session kind", "round", "steps", "step mean ms", "step med. ms", "fallbacks", "wall s"))
+
+    def one(name, rows, rnd):
+        st = {}
+        _, wall = session(e, reqs, voice, slots, stats=st, rows=rows)
+        say("    %-34s %5d  %6d  %12.4f  %12.4f  %10d  %9.2f" % (name, rnd, len(st["step_ms"]), statistics.mean(st["step_ms"]), statistics.median(st["step_ms"]),
+                                                               e.topk_fallbacks(), wall))
+        return statistics.mean(st["step_ms"])
+
+    for rnd in range(rounds):
+        for name, rows in kinds:
+            means[name].append(one(name, rows, rnd))
+    if not uniform_only:
+        session(e, reqs[:min(4, len(reqs))], voice, slots, rows="mixed")
+        means["(i) rows session, mixed controls"] = [one("(i) rows session, mixed controls", "mixed", rnd) for rnd in range(rounds)]
+    for name, m in means.items():
+        say("    %-34s step mean over %d runs: median %.4f ms, run-to-run min %.4f .. max %.4f (spread %.4f ms = %.2f %%)" %
+            (name, len(m), statistics.median(m), min(m), max(m), max(m) - min(m), 100.0 * (max(m) - min(m)) / statistics.median(m)))
+    if not uniform_only:
+        u, r = statistics.median(means["(g) uniform session"]), statistics.median(means["(h) rows session, own controls"])
+        say("    rows (own controls) - uniform: %+.4f ms per step (%+.2f %%); uniform run-to-run spread %.4f ms" %
+            (r - u, 100.0 * (r - u) / u, max(means["(g) uniform session"]) - min(means["(g) uniform session"])))
+
+
 def step_cost(e, voice, B, steps, warm, rounds=4):
     """blocks of tts_ar_step_sample steps and of session steps with every slot live, alternated (a session excludes tts_ar_step* while it is open, so the
     alternation is by block, not by step); every block starts from a fresh begin / a fresh session, so both run the same context lengths"""
@@ -199,6 +245,9 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warm", type=int, default=20)
     ap.add_argument("--audio", type=int, default=0, metavar="STRIDE")
+    ap.add_argument("--row-controls", action="store_true")
+    ap.add_argument("--uniform-only", action="store_true")
+    ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--models", default=os.environ.get("TTS_BENCH_MODELS", "/tmp/tts_bench_models"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -226,6 +275,13 @@ def main():
             sw.write_hifigan(hfg, seed=77)
         e.load_hifigan(hfg)
         audio_mode(e, reqs, voice, a.slots, a.audio, say)
+        e.close()
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write("\n" + "\n".join(lines) + "\n")
+        return
+    if a.row_controls or a.uniform_only:
+        row_controls_mode(e, reqs, voice, a.slots, a.rounds, say, uniform_only=a.uniform_only)
         e.close()
         if a.out:
             with open(a.out, "a") as f:

@@ -18,6 +18,7 @@ VOCAB_MEL = 8194
 DMODEL = 1024
 AR_MASK_STOP = 1
 AR_RETIRE = 2
+AR_ROW_CONTROLS = 8  # tts_ar_session_open only
 NOISE_REFERENCE, NOISE_DEVICE = 0, 1
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
@@ -29,6 +30,16 @@ AUDIO_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_i
 def build(verbose=False):
     """hipcc --offload-arch=gfx950 build of the library + CLI (in-tree, cross-compiles without a GPU)."""
     subprocess.check_call(["make", "-C", HERE, "-j8", "all"], stdout=None if verbose else subprocess.DEVNULL)
+
+
+class ArRequest(C.Structure):
+    """tts_ar_request: one session request's candidates, seed, stop schedule, step limit and sampler controls (tts_ar_session_admit_ex)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_cand", C.c_int32), ("seed", C.c_uint32), ("max_steps", C.c_int32), ("stop_at", C.c_void_p),
+                ("temperature", C.c_double), ("top_k", C.c_double), ("top_p", C.c_double), ("repetition_penalty", C.c_double), ("penalty_scope", C.c_double)]
+
+
+# the keys of ar_session_admit(controls=...) and the descriptor fields they set
+AR_CONTROL_FIELDS = {"temperature": "temperature", "top_k": "top_k", "top_p": "top_p", "penalty": "repetition_penalty", "scope": "penalty_scope"}
 
 
 class TtsError(RuntimeError):
@@ -87,6 +98,8 @@ def lib():
         "tts_ar_session_cancel": (ci, [vp, ci]), "tts_ar_session_close": (ci, [vp]), "tts_ar_session_recaptures": (ci, [vp]),
         "tts_ar_session_enable_audio": (ci, [vp, ci]), "tts_ar_session_audio": (ci, [vp, ci, vp, ci, vp]),
         "tts_host_session_first_fit": (ci, [vp, ci, ci]),
+        "tts_ar_request_init": (ci, [vp, C.POINTER(ArRequest)]), "tts_ar_session_admit_ex": (ci, [vp, vp, ci, vp, C.POINTER(ArRequest)]),
+        "tts_host_ar_request_check": (ci, [C.POINTER(ArRequest), ci, ci]),
         "tts_diffusion_forward": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p]),
         "tts_diffusion": (ci, [vp, _f32p, _i32p, ci, ci, vp, ci, _f32p]),
         "tts_vocoder_samples": (ci, [ci]),
@@ -335,20 +348,42 @@ class Engine:
         return out
 
     # ---- in-flight batching: requests join and leave a running batch (tts_ar_session_*) ----
-    def ar_session_open(self, n_slots, max_cand, max_text, max_steps, mask_stop=False, retire=False):
+    def ar_session_open(self, n_slots, max_cand, max_text, max_steps, mask_stop=False, retire=False, row_controls=False):
         """A batch of n_slots rows that requests of up to max_cand candidates and max_text ids join and leave at any step. The sampler controls, ar_weights,
-        ggml_lut and device_topk are read here and hold until ar_session_close()."""
-        self._ck(self.L.tts_ar_session_open(self.h, n_slots, max_cand, max_text, max_steps, (AR_MASK_STOP if mask_stop else 0) | (AR_RETIRE if retire else 0)))
+        ggml_lut and device_topk are read here and hold until ar_session_close(). row_controls: requests may bring sampler controls of their own
+        (ar_session_admit(controls=...)); the step then ends with the per-row prefilter."""
+        flags = (AR_MASK_STOP if mask_stop else 0) | (AR_RETIRE if retire else 0) | (AR_ROW_CONTROLS if row_controls else 0)
+        self._ck(self.L.tts_ar_session_open(self.h, n_slots, max_cand, max_text, max_steps, flags))
         self._session_cand = {}
 
-    def ar_session_admit(self, tokens, voice, n_cand, seed, stop_at=None):
-        """Admits a request into the lowest run of n_cand free slots and returns its id; TtsError (status -6) when there is no such run."""
+    def ar_request(self, n_cand=1, seed=0, stop_at=None, controls=None, max_steps=None):
+        """A tts_ar_request filled from the open session's pinned options (tts_ar_request_init), then from the arguments. controls: a dict with any of
+        temperature, top_k, top_p, penalty, scope. The stop_at array must outlive the descriptor's use."""
+        req = ArRequest()
+        req.struct_size = C.sizeof(ArRequest)
+        self._ck(self.L.tts_ar_request_init(self.h, C.byref(req)))
+        req.n_cand, req.seed, req.max_steps = n_cand, seed, 0 if max_steps is None else max_steps
+        req.stop_at = None if stop_at is None else stop_at.ctypes.data
+        for k, v in (controls or {}).items():
+            if k not in AR_CONTROL_FIELDS:
+                raise ValueError("controls: any of %s, not %r" % (", ".join(AR_CONTROL_FIELDS), k))
+            setattr(req, AR_CONTROL_FIELDS[k], v)
+        return req
+
+    def ar_session_admit(self, tokens, voice, n_cand, seed, stop_at=None, controls=None, max_steps=None):
+        """Admits a request into the lowest run of n_cand free slots and returns its id; TtsError (status -6) when there is no such run. controls (a dict with
+        any of temperature, top_k, top_p, penalty, scope; missing keys take the session's values) and max_steps (at most the session's): the request's own;
+        with either the call goes through tts_ar_session_admit_ex. Controls that differ from the session's need ar_session_open(row_controls=True)."""
         tok = np.ascontiguousarray(tokens, np.int32)
         v = np.ascontiguousarray(voice, np.float32)
         sa = None if stop_at is None else np.ascontiguousarray(stop_at, np.int32)
         if v.size != DMODEL or (sa is not None and len(sa) != n_cand):
             raise ValueError("voice [1024]; stop_at [n_cand]")
-        rid = self._ck(self.L.tts_ar_session_admit(self.h, _ptr(tok), len(tok), _ptr(v), n_cand, seed, _ptr(sa)))
+        if controls is not None or max_steps is not None:
+            req = self.ar_request(n_cand, seed, sa, controls, max_steps)
+            rid = self._ck(self.L.tts_ar_session_admit_ex(self.h, _ptr(tok), len(tok), _ptr(v), C.byref(req)))
+        else:
+            rid = self._ck(self.L.tts_ar_session_admit(self.h, _ptr(tok), len(tok), _ptr(v), n_cand, seed, _ptr(sa)))
         self._session_cand[rid] = n_cand
         return rid
 
@@ -708,6 +743,12 @@ def host_ar_stop_run(n_cand, samples, max_steps, flags=0, stop_at=None):
     inputs = np.full((max_steps, B), -1, np.int32)
     rc = lib().tts_host_ar_stop_run(nc, len(nc), smp.reshape(-1), max_steps, flags, _ptr(sa), codes.reshape(-1), stopped, steps, _ptr(inputs))
     return rc, codes, stopped, int(steps[0]), inputs
+
+
+def host_ar_request_check(max_cand, max_steps, struct_size=None, n_cand=1, seed=0, req_max_steps=0, temperature=0.8, top_k=50, top_p=0.8, penalty=2.0, scope=0):
+    """The status tts_ar_session_admit_ex's descriptor checks return for these fields in a session of max_cand candidates and max_steps steps (no GPU)."""
+    req = ArRequest(C.sizeof(ArRequest) if struct_size is None else struct_size, n_cand, seed, req_max_steps, None, temperature, top_k, top_p, penalty, scope)
+    return lib().tts_host_ar_request_check(C.byref(req), max_cand, max_steps)
 
 
 def host_session_first_fit(busy, n_cand):

@@ -14,7 +14,8 @@ int ar_begin_groups(tts_ctx *, const int32_t *, const int *, int, const float *,
 int ar_latents_group(tts_ctx *, int, const int32_t *, int, float *);
 int ar_stream_reserve(tts_ctx *, int n_mel);
 int ar_graph_captures(const tts_ctx *);
-int ar_session_open(tts_ctx *, int n_slots, int max_cand, int max_text, int max_steps);
+int ar_session_open(tts_ctx *, int n_slots, int max_cand, int max_text, int max_steps, bool rows);
+int ar_session_controls(tts_ctx *, int c0, int n);
 void ar_session_close(tts_ctx *);
 int ar_session_prompt(tts_ctx *, int c0, int n_cand, const int32_t *text_ids, int n_text, const float *voice, float *logits_row);
 int ar_session_step(tts_ctx *, const int32_t *toks, const int32_t *n_past, const int32_t *pos_id, const char *live, int mode);
@@ -49,6 +50,9 @@ struct SessionRequest {
   std::vector<int32_t> stop_at;  // the request's stop schedule (empty: none)
   std::vector<int32_t> samples;  // the tokens the next step feeds (after ArStopBook::step)
   int i = 0;                     // tts_autoregressive's loop counter: iterations applied so far
+  // the request's own sampler controls and step limit (tts_ar_session_admit_ex; tts_ar_session_admit: the session's)
+  SamplerParams sp;
+  int scope = 0, max_steps = 0;
   int state = 0;                 // 0 running, 1 finished, 2 finished by reaching max_steps in strict mode (collect returns TTS_ERR_LIMIT)
   // Audio (a one-candidate request of a session with tts_ar_session_enable_audio): tts_hifigan_stream's book, HfgStream, per request.
   bool audio = false, audio_done = false; // audio_done: the request has finished and its last frames are in pcm
@@ -82,6 +86,16 @@ struct SessionOptions { // puts the session's options into the context for the l
   }
   ~SessionOptions() { c->ar_sp = sp; c->ar_penalty_scope = scope; c->ar_weights = w; c->ggml_lut = lut; c->device_topk = topk; }
 };
+struct SamplerOptions { // inside a SessionOptions: one request's sampler controls around the calls that sample or write its table rows
+  tts_ctx *c;
+  SamplerParams sp;
+  int scope;
+  SamplerOptions(tts_ctx *ctx, const SamplerParams &p, int sc) : c(ctx), sp(ctx->ar_sp), scope(ctx->ar_penalty_scope) { c->ar_sp = p; c->ar_penalty_scope = sc; }
+  ~SamplerOptions() { c->ar_sp = sp; c->ar_penalty_scope = scope; }
+};
+bool same_controls(const SamplerParams &a, int sa, const SamplerParams &b, int sb) {
+  return a.temp == b.temp && a.top_k == b.top_k && a.top_p == b.top_p && a.penalty == b.penalty && sa == sb;
+}
 // first fit: the first index of the lowest run of n_cand free slots, or -1
 int session_first_fit(const uint8_t *busy, int n_slots, int n_cand) {
   int run = 0;
@@ -105,7 +119,7 @@ void session_advance(ArSession &s, SessionRequest &r) {
   const bool all_ended = r.book.step(r.samples.data(), r.i, retire, sched ? r.stop_at.data() : nullptr);
   r.i++;
   if (all_ended) r.state = 1;
-  else if (r.i >= s.max_steps) r.state = ((s.flags & TTS_AR_MASK_STOP) || retire) ? 1 : 2;
+  else if (r.i >= r.max_steps) r.state = ((s.flags & TTS_AR_MASK_STOP) || retire) ? 1 : 2;
   if (r.state) s.finished.push_back(r.id);
 }
 } // namespace
@@ -311,6 +325,35 @@ int tts_version(void) { return TTS_API_VERSION; }
 
 const char *tts_last_error(const tts_ctx *c) { return c ? c->err.c_str() : "no context (no HIP device?)"; }
 
+// The autoregressive sampler's five controls: the ONE statement of what each accepts, for tts_set_option and for a request descriptor (tts_ar_session_admit_ex,
+// tts_host_ar_request_check). Returns the refusal's text, or null for a value that is fine.
+static const char *const kArControlKeys[5] = {"ar_temperature", "ar_top_k", "ar_top_p", "ar_repetition_penalty", "ar_penalty_scope"};
+static int ar_control_index(const std::string &k) {
+  for (int i = 0; i < 5; i++)
+    if (k == kArControlKeys[i]) return i;
+  return -1;
+}
+static const char *ar_control_error(int which, double value) {
+  static_assert(TTS_VOCAB_MEL == 8194, "the text below names the vocabulary size");
+  switch (which) {
+  case 0: return (!std::isfinite(value) || !(value > 0) || !std::isfinite((float)value) || !((float)value > 0)) ? "ar_temperature: a finite value > 0" : nullptr;
+  case 1: return (!(value >= 1 && value <= TTS_VOCAB_MEL) || value != std::floor(value)) ? "ar_top_k: an integer in 1 .. 8194" : nullptr;
+  case 2: return (!(value > 0 && value <= 1) || !((float)value > 0)) ? "ar_top_p: a value in (0, 1]" : nullptr;
+  case 3: return (!std::isfinite(value) || !(value >= 1) || !std::isfinite((float)value)) ? "ar_repetition_penalty: a finite value >= 1" : nullptr;
+  case 4: return (value != 0 && value != 1) ? "ar_penalty_scope: 0 (the ids of the last input) or 1 (every id fed since tts_ar_begin)" : nullptr;
+  }
+  return "unknown sampler control";
+}
+static void ar_control_store(int which, double value, SamplerParams &sp, int &scope) { // a value ar_control_error has passed
+  switch (which) {
+  case 0: sp.temp = (float)value; break;
+  case 1: sp.top_k = (int)value; break;
+  case 2: sp.top_p = (float)value; break;
+  case 3: sp.penalty = (float)value; break;
+  case 4: scope = (int)value; break;
+  }
+}
+
 int tts_set_option(tts_ctx *c, const char *key, double value) {
   if (!c || !key) return TTS_ERR_ARG;
   std::string k(key);
@@ -360,25 +403,11 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     c->cond_free_k = (float)value;
   }
   // additions within version 8: the autoregressive sampler's controls (read by tts_sample, tts_ar_step_sample and the tts_autoregressive* drivers)
-  else if (k == "ar_temperature") {
-    if (!std::isfinite(value) || !(value > 0) || !std::isfinite((float)value) || !((float)value > 0)) return fail(c, TTS_ERR_ARG, "ar_temperature: a finite value > 0");
-    c->ar_sp.temp = (float)value;
-  }
-  else if (k == "ar_top_k") {
-    if (!(value >= 1 && value <= TTS_VOCAB_MEL) || value != std::floor(value)) return fail(c, TTS_ERR_ARG, "ar_top_k: an integer in 1 .. %d", TTS_VOCAB_MEL);
-    c->ar_sp.top_k = (int)value;
-  }
-  else if (k == "ar_top_p") {
-    if (!(value > 0 && value <= 1) || !((float)value > 0)) return fail(c, TTS_ERR_ARG, "ar_top_p: a value in (0, 1]");
-    c->ar_sp.top_p = (float)value;
-  }
-  else if (k == "ar_repetition_penalty") {
-    if (!std::isfinite(value) || !(value >= 1) || !std::isfinite((float)value)) return fail(c, TTS_ERR_ARG, "ar_repetition_penalty: a finite value >= 1");
-    c->ar_sp.penalty = (float)value;
-  }
-  else if (k == "ar_penalty_scope") {
-    if (value != 0 && value != 1) return fail(c, TTS_ERR_ARG, "ar_penalty_scope: 0 (the ids of the last input) or 1 (every id fed since tts_ar_begin)");
-    c->ar_penalty_scope = (int)value;
+  // (and, per request, by tts_ar_session_admit_ex: ar_control_error is the one statement of what each of them accepts)
+  else if (ar_control_index(k) >= 0) {
+    const int which = ar_control_index(k);
+    if (const char *e = ar_control_error(which, value)) return fail(c, TTS_ERR_ARG, "%s", e);
+    ar_control_store(which, value, c->ar_sp, c->ar_penalty_scope);
   }
   else if (k == "hfg_small_m") { // addition within version 8: tile selection of tts_hifigan_chunk, same bits either way
     if (!(value >= 0 && value <= (1 << 24)) || value != std::floor(value)) return fail(c, TTS_ERR_ARG, "hfg_small_m: a row count in 0 .. 2^24 (0 = never)");
@@ -939,7 +968,8 @@ int tts_ar_session_close(tts_ctx *c) {
 int tts_ar_session_open(tts_ctx *c, int n_slots, int max_cand, int max_text, int max_steps, unsigned flags) {
   NEED_CTX(c);
   if (!c->ar) return fail(c, TTS_ERR_STATE, "AR model not loaded");
-  if (n_slots < 1 || max_cand < 1 || max_cand > n_slots || max_text < 1 || max_steps < 1 || (flags & ~(unsigned)(TTS_AR_MASK_STOP | TTS_AR_RETIRE)))
+  if (n_slots < 1 || max_cand < 1 || max_cand > n_slots || max_text < 1 || max_steps < 1 ||
+      (flags & ~(unsigned)(TTS_AR_MASK_STOP | TTS_AR_RETIRE | TTS_AR_ROW_CONTROLS)))
     return fail(c, TTS_ERR_ARG, "tts_ar_session_open: bad argument (n_slots %d: >= 1, max_cand %d: 1 .. n_slots, max_text %d, max_steps %d: >= 1, flags %u)", n_slots,
                 max_cand, max_text, max_steps, flags);
   if (n_slots > 4096) return fail(c, TTS_ERR_LIMIT, "tts_ar_session_open: %d slots, at most 4096", n_slots);
@@ -952,7 +982,7 @@ int tts_ar_session_open(tts_ctx *c, int n_slots, int max_cand, int max_text, int
     s->n_slots = n_slots; s->max_cand = max_cand; s->max_text = max_text; s->max_steps = max_steps; s->flags = flags;
     s->sp = c->ar_sp; s->scope = c->ar_penalty_scope; s->ar_weights = c->ar_weights; s->ggml_lut = c->ggml_lut; s->device_topk = c->device_topk;
     s->busy.assign((size_t)n_slots, 0);
-    if (int rc = ar_session_open(c, n_slots, max_cand, max_text, max_steps)) return rc;
+    if (int rc = ar_session_open(c, n_slots, max_cand, max_text, max_steps, (flags & TTS_AR_ROW_CONTROLS) != 0)) return rc;
     c->topk_fallbacks = 0;
     c->session = s.release();
     return (int)TTS_OK;
@@ -975,30 +1005,83 @@ int tts_ar_session_recaptures(const tts_ctx *c) {
   return ar_session_recaptures(c);
 }
 
-int tts_ar_session_admit(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, int n_cand, uint32_t seed, const int32_t *stop_at) {
+// What a request descriptor must satisfy in a session of max_cand candidates and max_steps steps, before any device work: the status, and in `why` the text.
+// On TTS_OK sp / scope hold the request's controls as the sampler will read them.
+static int request_check(const tts_ar_request *req, int max_cand, int max_steps, SamplerParams &sp, int &scope, std::string &why) {
+  char buf[160];
+  if (!req) { why = "null request"; return TTS_ERR_ARG; }
+  if (req->struct_size < sizeof(tts_ar_request)) {
+    snprintf(buf, sizeof buf, "struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_ar_request))", req->struct_size, sizeof(tts_ar_request));
+    why = buf;
+    return TTS_ERR_ARG;
+  }
+  if (req->n_cand < 1) { snprintf(buf, sizeof buf, "bad argument (%d candidates)", req->n_cand); why = buf; return TTS_ERR_ARG; }
+  if (req->n_cand > max_cand) { snprintf(buf, sizeof buf, "%d candidates, the session was opened for %d", req->n_cand, max_cand); why = buf; return TTS_ERR_LIMIT; }
+  if (req->stop_at)
+    for (int b = 0; b < req->n_cand; b++)
+      if (req->stop_at[b] < 1) { snprintf(buf, sizeof buf, "candidate %d would stop before its first code", b); why = buf; return TTS_ERR_ARG; }
+  if (req->max_steps < 0) { snprintf(buf, sizeof buf, "max_steps %d: 0 (the session's) or 1 .. %d", req->max_steps, max_steps); why = buf; return TTS_ERR_ARG; }
+  if (req->max_steps > max_steps) { snprintf(buf, sizeof buf, "max_steps %d, the session was opened for %d", req->max_steps, max_steps); why = buf; return TTS_ERR_LIMIT; }
+  const double v[5] = {req->temperature, req->top_k, req->top_p, req->repetition_penalty, req->penalty_scope};
+  for (int k = 0; k < 5; k++) {
+    if (const char *e = ar_control_error(k, v[k])) { why = e; return TTS_ERR_ARG; }
+    ar_control_store(k, v[k], sp, scope);
+  }
+  return TTS_OK;
+}
+
+int tts_host_ar_request_check(const tts_ar_request *req, int max_cand, int max_steps) {
+  if (max_cand < 1 || max_steps < 1) return TTS_ERR_ARG;
+  SamplerParams sp;
+  int scope = 0;
+  std::string why;
+  return request_check(req, max_cand, max_steps, sp, scope, why);
+}
+
+int tts_ar_request_init(tts_ctx *c, tts_ar_request *req) {
   NEED_CTX(c);
-  NEED_SESSION(c, "tts_ar_session_admit");
+  NEED_SESSION(c, "tts_ar_request_init");
+  if (!req) return fail(c, TTS_ERR_ARG, "tts_ar_request_init: null request");
+  if (req->struct_size < sizeof(tts_ar_request))
+    return fail(c, TTS_ERR_ARG, "tts_ar_request_init: struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_ar_request) first)", req->struct_size,
+                sizeof(tts_ar_request));
+  const ArSession &s = *c->session;
+  req->n_cand = 1; req->seed = 0; req->max_steps = 0; req->stop_at = nullptr;
+  req->temperature = s.sp.temp; req->top_k = s.sp.top_k; req->top_p = s.sp.top_p; req->repetition_penalty = s.sp.penalty; req->penalty_scope = s.scope;
+  return TTS_OK;
+}
+
+// tts_ar_session_admit and tts_ar_session_admit_ex (fn: the caller's name in the messages). sp / scope / max_steps: the request's, already checked.
+static int session_admit(tts_ctx *c, const char *fn, const int32_t *text_ids, int n_text, const float *voice, int n_cand, uint32_t seed, const int32_t *stop_at,
+                         const SamplerParams &sp, int scope, int max_steps) {
   ArSession &s = *c->session;
   // every argument before any device work
-  if (!text_ids || !voice || n_text < 1 || n_cand < 1) return fail(c, TTS_ERR_ARG, "tts_ar_session_admit: bad argument (%d ids, %d candidates)", n_text, n_cand);
-  if (n_text > s.max_text) return fail(c, TTS_ERR_LIMIT, "tts_ar_session_admit: %d ids, the session was opened for %d", n_text, s.max_text);
-  if (n_cand > s.max_cand) return fail(c, TTS_ERR_LIMIT, "tts_ar_session_admit: %d candidates, the session was opened for %d", n_cand, s.max_cand);
+  if (!text_ids || !voice || n_text < 1 || n_cand < 1) return fail(c, TTS_ERR_ARG, "%s: bad argument (%d ids, %d candidates)", fn, n_text, n_cand);
+  if (n_text > s.max_text) return fail(c, TTS_ERR_LIMIT, "%s: %d ids, the session was opened for %d", fn, n_text, s.max_text);
+  if (n_cand > s.max_cand) return fail(c, TTS_ERR_LIMIT, "%s: %d candidates, the session was opened for %d", fn, n_cand, s.max_cand);
   for (int i = 0; i < n_text; i++)
     if (text_ids[i] < 0 || text_ids[i] >= 256) return fail(c, TTS_ERR_ARG, "text id %d out of range", text_ids[i]);
   for (int i = 0; i < TTS_DMODEL; i++)
-    if (!std::isfinite(voice[i])) return fail(c, TTS_ERR_ARG, "tts_ar_session_admit: the voice holds a non-finite value");
+    if (!std::isfinite(voice[i])) return fail(c, TTS_ERR_ARG, "%s: the voice holds a non-finite value", fn);
   if (stop_at)
     for (int b = 0; b < n_cand; b++)
-      if (stop_at[b] < 1) return fail(c, TTS_ERR_ARG, "tts_ar_session_admit: candidate %d would stop before its first code", b);
+      if (stop_at[b] < 1) return fail(c, TTS_ERR_ARG, "%s: candidate %d would stop before its first code", fn, b);
+  const bool rows = (s.flags & TTS_AR_ROW_CONTROLS) != 0;
+  if (!rows && !same_controls(sp, scope, s.sp, s.scope))
+    return fail(c, TTS_ERR_STATE, "%s: the request's sampler controls differ from the session's (open the session with TTS_AR_ROW_CONTROLS)", fn);
   const int c0 = session_first_fit(s.busy.data(), s.n_slots, n_cand);
-  if (c0 < 0) return fail(c, TTS_ERR_LIMIT, "tts_ar_session_admit: no run of %d free slots (collect a finished request first)", n_cand);
+  if (c0 < 0) return fail(c, TTS_ERR_LIMIT, "%s: no run of %d free slots (collect a finished request first)", fn, n_cand);
   return guarded(c, [&] {
     SessionOptions opt(c, s);
+    SamplerOptions ropt(c, sp, scope); // the request's controls: its table rows, its first codes
     const int V = TTS_VOCAB_MEL, P = n_text + 2;
     std::vector<float> row((size_t)V);
     if (int rc = ar_session_prompt(c, c0, n_cand, text_ids, n_text, voice, row.data())) return rc;
+    if (rows) // every admission writes its rows: whatever the slots' last request left there (finished, cancelled or failed half-way) is gone
+      if (int rc = ar_session_controls(c, c0, n_cand)) return rc;
     SessionRequest r;
     r.id = s.next_id; r.c0 = c0; r.n_cand = n_cand; r.n_text = n_text;
+    r.sp = sp; r.scope = scope; r.max_steps = max_steps;
     r.gen.seed(seed);
     r.book.init(&n_cand, 1);
     if (stop_at) r.stop_at.assign(stop_at, stop_at + n_cand);
@@ -1025,6 +1108,25 @@ int tts_ar_session_admit(tts_ctx *c, const int32_t *text_ids, int n_text, const 
   });
 }
 
+int tts_ar_session_admit(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, int n_cand, uint32_t seed, const int32_t *stop_at) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_admit");
+  const ArSession &s = *c->session;
+  return session_admit(c, "tts_ar_session_admit", text_ids, n_text, voice, n_cand, seed, stop_at, s.sp, s.scope, s.max_steps);
+}
+
+int tts_ar_session_admit_ex(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, const tts_ar_request *req) {
+  NEED_CTX(c);
+  NEED_SESSION(c, "tts_ar_session_admit_ex");
+  const ArSession &s = *c->session;
+  SamplerParams sp;
+  int scope = 0;
+  std::string why;
+  if (int rc = request_check(req, s.max_cand, s.max_steps, sp, scope, why)) return fail(c, rc, "tts_ar_session_admit_ex: %s", why.c_str());
+  return session_admit(c, "tts_ar_session_admit_ex", text_ids, n_text, voice, req->n_cand, req->seed, req->stop_at, sp, scope,
+                       req->max_steps ? req->max_steps : s.max_steps);
+}
+
 int tts_ar_session_step(tts_ctx *c) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_step");
@@ -1047,7 +1149,7 @@ int tts_ar_session_step(tts_ctx *c) {
         else { n_past[k] = r.n_text + 2; pos[k] = 2; }
       }
     }
-    const bool mask = (s.flags & TTS_AR_MASK_STOP) != 0, scope1 = s.scope == 1;
+    const bool mask = (s.flags & TTS_AR_MASK_STOP) != 0;
     const int mode = s.device_topk ? (mask ? 2 : 1) : 0;
     if (int rc = ar_session_step(c, toks.data(), n_past.data(), pos.data(), live.data(), mode)) return rc;
     std::vector<std::vector<int32_t>> hist;
@@ -1055,6 +1157,8 @@ int tts_ar_session_step(tts_ctx *c) {
     for (auto &kv : s.reqs) {
       SessionRequest &r = kv.second;
       if (r.state != 0) continue;
+      SamplerOptions ropt(c, r.sp, r.scope); // the request's own controls: the uniform session's are the session's
+      const bool scope1 = r.scope == 1;
       next.assign((size_t)r.n_cand, 0);
       if (mode == 0) { // the full rows, as tts_autoregressive with device_topk = 0
         float *logits = ar_host_logits(c) + (size_t)r.c0 * V;
@@ -1104,8 +1208,9 @@ int tts_ar_session_collect(tts_ctx *c, int request, int32_t *codes_out, int32_t 
   if (it == s.reqs.end()) return fail(c, TTS_ERR_ARG, "tts_ar_session_collect: no request %d", request);
   if (it->second.state == 0) return fail(c, TTS_ERR_STATE, "tts_ar_session_collect: request %d is still running", request);
   if (it->second.state == 2) {
+    const int limit = it->second.max_steps;
     session_release(s, request);
-    return fail(c, TTS_ERR_LIMIT, "no stop token within %d steps", s.max_steps);
+    return fail(c, TTS_ERR_LIMIT, "no stop token within %d steps", limit);
   }
   return guarded(c, [&] {
     SessionOptions opt(c, s);

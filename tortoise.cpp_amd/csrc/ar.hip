@@ -1297,27 +1297,29 @@ __device__ __forceinline__ float pf_value(const float *__restrict__ src, int i, 
   return v;
 }
 
+// Bit j of the result: this thread's logit j (index j * 256 + tid) is penalised: its id is in the row's history set hc, or is the token this step was fed.
+__device__ __forceinline__ unsigned long long pf_history_mask(const uint32_t *__restrict__ hc, int tok, int tid) {
+  constexpr int NJ = (V + 255) / 256; // 33
+  unsigned long long penm = 0ull;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const int i = j * 256 + tid;
+    if (i < V && (((hc[i >> 5] >> (i & 31)) & 1u) || i == tok)) penm |= 1ull << j;
+  }
+  return penm;
+}
+
+// One row's list: threshold search, index-ordered compaction and the values (pf_value). The ONE body of sample_prefilter_kernel<false / true> and of
+// sample_prefilter_rows_kernel (a workgroup of 256 threads per row; src = the row's logits, o = its TTS_PF_WORDS words; penm: pf_history_mask, read only
+// under PEN). pf_min and penalty are workgroup-uniform.
 template <bool PEN>
-__global__ __launch_bounds__(256) void sample_prefilter_kernel(const float *__restrict__ logits, int mask_stop, int pf_min, int32_t *__restrict__ out,
-                                                               uint32_t *__restrict__ hist, const int32_t *__restrict__ toks, float penalty) {
+__device__ __forceinline__ void prefilter_row_block(const float *__restrict__ src, int32_t *__restrict__ o, int mask_stop, int pf_min, unsigned long long penm,
+                                                    float penalty) {
   constexpr int NJ = (V + 255) / 256; // 33
   __shared__ int red[2][4];
   __shared__ int4 tab[NJ];
-  const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float *src = logits + (size_t)c * V;
-  int32_t *o = out + (size_t)c * TTS_PF_WORDS;
-  unsigned long long penm = 0ull; // PEN: bit j = this thread's logit j is penalised
-  if (PEN) {
-    uint32_t *hc = hist + (size_t)c * TTS_HIST_WORDS;
-    const int tok = toks[c]; // 0 <= tok < V (ar_step checks)
-    if (tid == 0) hc[tok >> 5] |= 1u << (tok & 31); // one workgroup per candidate, one writer
-#pragma unroll
-    for (int j = 0; j < NJ; j++) {
-      const int i = j * 256 + tid;
-      if (i < V && (((hc[i >> 5] >> (i & 31)) & 1u) || i == tok)) penm |= 1ull << j;
-    }
-  }
-  if (pf_min > TTS_PF_MAX) { // top-k beyond what a 128-entry list can serve: the host samples every candidate from its full row
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (pf_min > TTS_PF_MAX) { // top-k beyond what a 128-entry list can serve: the host samples the candidate from its full row
     if (tid == 0) o[0] = -1;
     return;
   }
@@ -1369,6 +1371,37 @@ __global__ __launch_bounds__(256) void sample_prefilter_kernel(const float *__re
   if (tid == 0) { o[0] = n; o[1] = 0; o[2] = 0; o[3] = 0; }
 }
 
+template <bool PEN>
+__global__ __launch_bounds__(256) void sample_prefilter_kernel(const float *__restrict__ logits, int mask_stop, int pf_min, int32_t *__restrict__ out,
+                                                               uint32_t *__restrict__ hist, const int32_t *__restrict__ toks, float penalty) {
+  const int c = blockIdx.x, tid = threadIdx.x;
+  unsigned long long penm = 0ull; // PEN: bit j = this thread's logit j is penalised
+  if (PEN) {
+    uint32_t *hc = hist + (size_t)c * TTS_HIST_WORDS;
+    const int tok = toks[c]; // 0 <= tok < V (ar_step checks)
+    if (tid == 0) hc[tok >> 5] |= 1u << (tok & 31); // one workgroup per candidate, one writer
+    penm = pf_history_mask(hc, tok, tid);
+  }
+  prefilter_row_block<PEN>(logits + (size_t)c * V, out + (size_t)c * TTS_PF_WORDS, mask_stop, pf_min, penm, penalty);
+}
+
+// The prefilter of a session opened with TTS_AR_ROW_CONTROLS: every row under its own controls, none of them baked into the launch. ctl [rows padded to whole
+// tiles] = {pf_min_for(top_k), the penalty's bits, the penalty scope, 0} per row, written outside the graph (ar_session_controls: at admission, for the
+// slots the request takes, always); an empty or parked row keeps the entry of its last request and is never sampled. The entry's address is workgroup-uniform and
+// its load is issued first, beside the row's first logits loads. pf_min above TTS_PF_MAX writes n = -1 for this row only. Scope 1: the penalised values,
+// as sample_prefilter_kernel<true>; scope 0: pf_value<true> with no bit of penm set, which is sample_prefilter_kernel<false>'s value. The fed token joins the
+// row's history set whatever the scope, as in the scope-1 graph: an admission resets the rows it takes.
+__global__ __launch_bounds__(256) void sample_prefilter_rows_kernel(const float *__restrict__ logits, int mask_stop, const int4 *__restrict__ ctl,
+                                                                    int32_t *__restrict__ out, uint32_t *__restrict__ hist, const int32_t *__restrict__ toks) {
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const int4 rc = ctl[c];
+  uint32_t *hc = hist + (size_t)c * TTS_HIST_WORDS;
+  const int tok = toks[c]; // 0 <= tok < V (ar_session_step checks)
+  if (tid == 0) hc[tok >> 5] |= 1u << (tok & 31); // one workgroup per row, one writer
+  const unsigned long long penm = rc.z ? pf_history_mask(hc, tok, tid) : 0ull;
+  prefilter_row_block<true>(logits + (size_t)c * V, out + (size_t)c * TTS_PF_WORDS, mask_stop, rc.x, penm, __int_as_float(rc.y));
+}
+
 // Penalty scope 1, a step that hands back the logits (tts_ar_step): the fed ids join the candidates' history sets here, since no prefilter runs.
 __global__ void hist_mark_kernel(const int32_t *__restrict__ toks, int B, uint32_t *__restrict__ hist) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1417,6 +1450,11 @@ struct ArState {
   // A session (tts_ar_session_*): B slots, each row at its own step. The step's first kernel writes every row's context length into row_off and sets the
   // step state's n_past to 0 (embed_session_kernel); the host block behind h_toks is [tokens[B] | n_past[Bpad] | pos_id[B]].
   bool session = false;
+  // A session opened with TTS_AR_ROW_CONTROLS: its step ends with sample_prefilter_rows_kernel, which reads every row's sampler controls from ctl
+  // ([tiles * 16] int4 {pf_min_for(top_k), penalty bits, penalty scope, 0}; reserved at open, written by ar_session_controls outside the graph). Such a step
+  // bakes none of step_scope / step_pf_min / step_penalty and has a graph slot of its own, so a uniform session of the same shape keeps its graph.
+  bool rows = false;
+  DevBuf ctl;
   int sess_captures0 = -1;   // graph_captures when the session's first step had run (tts_ar_session_recaptures)
   DevBuf row_off;            // multi: [tiles * 16] ints, P of the row's group (0 past the batch); the step state's n_past is then the step index
   DevBuf voice, kcache, vcache, lat_k, lat_v;
@@ -1445,27 +1483,30 @@ struct ArState {
   float step_penalty = 2.0f;                    // and, under scope 1, the penalty
   // one captured step per mode (a caller alternating tts_ar_step / tts_ar_step_sample, or bench's device_topk on/off loop, re-instantiated
   // the ~150-node graph on every switch)
-  hipGraph_t graphs[4] = {};         // [3]: the session step (one mode per session; kept across sessions of the same shape)
-  hipGraphExec_t graph_execs[4] = {};
+  hipGraph_t graphs[5] = {};         // [3]: the session step (one mode per session; kept across sessions of the same shape); [4]: a rows session's step
+  hipGraphExec_t graph_execs[5] = {};
   int graph_captures = 0; // decode-step graphs captured since the model was loaded (tts_ar_graph_captures)
   // everything the captured step bakes into its nodes: the graph of the previous utterance is replayed when nothing moved
   struct GraphSig {
     int B = 0, max_pos = 0, lut = 0, wmode = 0, mode = 0, multi = 0; // multi: 2 = a session step
+    int rows = 0;              // a session with per-row controls: scope, pf_min and penalty below are 0, the history sets and the control table are always in p
     int scope = 0, pf_min = 0; // the sampler controls a step bakes in: penalty scope (an extra node / the penalising prefilter), the prefilter's keep bound (modes 1, 2)
     float penalty = 0;         // scope 1, modes 1 / 2
-    const void *p[13] = {};
+    const void *p[14] = {};
     bool operator==(const GraphSig &o) const {
-      return B == o.B && max_pos == o.max_pos && lut == o.lut && wmode == o.wmode && mode == o.mode && multi == o.multi && scope == o.scope &&
-             pf_min == o.pf_min && penalty == o.penalty && std::equal(p, p + 13, o.p);
+      return B == o.B && max_pos == o.max_pos && lut == o.lut && wmode == o.wmode && mode == o.mode && multi == o.multi && rows == o.rows && scope == o.scope &&
+             pf_min == o.pf_min && penalty == o.penalty && std::equal(p, p + 14, o.p);
     }
-  } graph_sigs[4];
+  } graph_sigs[5];
   GraphSig current_sig(int lut, int wmode) const {
     GraphSig g;
     g.B = B; g.max_pos = max_pos; g.lut = lut; g.wmode = wmode; g.mode = step_mode; g.multi = session ? 2 : multi;
-    g.scope = step_scope; g.pf_min = step_mode ? step_pf_min : 0; g.penalty = (step_scope && step_mode) ? step_penalty : 0.f;
-    const void *q[13] = {h.p, qkv.p, att.p, ff.p, kcache.p, vcache.p, d_toks.p, logits.p, h_toks, h_logits, h_pf, (multi || session) ? row_off.p : nullptr,
-                         step_scope ? hist.p : nullptr};
-    std::copy(q, q + 13, g.p);
+    const bool rw = session && rows;
+    g.rows = rw;
+    g.scope = rw ? 0 : step_scope; g.pf_min = (step_mode && !rw) ? step_pf_min : 0; g.penalty = (step_scope && step_mode && !rw) ? step_penalty : 0.f;
+    const void *q[14] = {h.p, qkv.p, att.p, ff.p, kcache.p, vcache.p, d_toks.p, logits.p, h_toks, h_logits, h_pf, (multi || session) ? row_off.p : nullptr,
+                         (step_scope || rw) ? hist.p : nullptr, rw ? ctl.p : nullptr};
+    std::copy(q, q + 14, g.p);
     return g;
   }
   void drop_graph(int m) {
@@ -1474,7 +1515,7 @@ struct ArState {
     graph_execs[m] = nullptr; graphs[m] = nullptr;
   }
   ~ArState() {
-    for (int m = 0; m < 4; m++) drop_graph(m);
+    for (int m = 0; m < 5; m++) drop_graph(m);
     if (h_toks) (void)hipHostFree(h_toks);
     if (h_logits) (void)hipHostFree(h_logits);
     if (h_pf) (void)hipHostFree(h_pf);
@@ -2241,13 +2282,17 @@ static int enqueue_decode_step(tts_ctx *ctx, ArState *st) {
     if (wm == 2) dec_ln_gemv_kernel<DEC_LOGITS, 3, true, true><<<dim3(VPAD / 16, tiles), 256, 0, ctx->stream>>>(a);
     else if (wm == 1) dec_ln_gemv_kernel<DEC_LOGITS, 2, false, true><<<dim3(VPAD / 16, tiles), 256, 0, ctx->stream>>>(a);
     else DEC_LN_LAUNCH(DEC_LOGITS, dim3(VPAD / 16, tiles), true); }
+  const bool rows = st->session && st->rows; // per-row controls: the history sets are kept for every row, the prefilter reads the control table
   if (st->step_mode == 0) {
-    if (st->step_scope) hist_mark_kernel<<<(B + 255) / 256, 256, 0, ctx->stream>>>(st->h_toks, B, st->hist.as<uint32_t>()); // the one node scope 1 adds
+    if (st->step_scope || rows) hist_mark_kernel<<<(B + 255) / 256, 256, 0, ctx->stream>>>(st->h_toks, B, st->hist.as<uint32_t>()); // the one node scope 1 adds
     TTS_HIP(ctx, hipMemcpyAsync(st->h_logits, st->logits.p, (size_t)B * V * 4, hipMemcpyDeviceToHost, ctx->stream));
   } else { // the sampler's top-k prefilter on the device: 16 KB instead of 524 KB back to the host per step of 16 candidates
     ProfScope ps(ctx, "ar_prefilter", (double)B * V * 4.0);
     // the lists are written straight into pinned host memory (1 KB per candidate over PCIe from the kernel's stores): no copy node behind the graph
-    if (st->step_scope)
+    if (rows)
+      sample_prefilter_rows_kernel<<<B, 256, 0, ctx->stream>>>(st->logits.as<float>(), st->step_mode == 2, st->ctl.as<int4>(), st->h_pf, st->hist.as<uint32_t>(),
+                                                               st->h_toks);
+    else if (st->step_scope)
       sample_prefilter_kernel<true><<<B, 256, 0, ctx->stream>>>(st->logits.as<float>(), st->step_mode == 2, st->step_pf_min, st->h_pf, st->hist.as<uint32_t>(),
                                                                  st->h_toks, st->step_penalty);
     else
@@ -2258,7 +2303,8 @@ static int enqueue_decode_step(tts_ctx *ctx, ArState *st) {
 }
 
 // Runs the step that the state describes: replays graph slot `slot` (captured first when the slot is empty or anything its nodes bake in has moved: GraphSig),
-// or launches the kernels eagerly while one of their families is profiled. Slots 0 .. 2: ar_step's modes; 3: the session step.
+// or launches the kernels eagerly while one of their families is profiled. Slots 0 .. 2: ar_step's modes; 3: the session step; 4: the step of a session with
+// per-row controls.
 static int launch_step(tts_ctx *ctx, ArState *st, int slot, double step_bytes) {
   static const bool no_graph = getenv("TTS_NO_GRAPH") != nullptr; // e.g. under rocprofv3, which crashes on graph replays here
   // event records are not captured: the step runs eagerly while one of its own kernel families ("ar_*") is profiled
@@ -2456,6 +2502,10 @@ int ar_graph_captures(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->graph_capt
 // Sessions (tts_ar_session_*): the device side. The book of slots and requests is the caller's (api.cpp); here a session is a batch of n_slots rows whose
 // caches hold max_text + 2 + max_steps + 1 positions, every row at its own step (ArState::session).
 // ---------------------------------------------------------------------------------------------
+// A control table entry from the controls the context holds at the moment (the caller has put the session's or the request's there).
+static int4 control_entry(const tts_ctx *ctx) {
+  return make_int4(pf_min_for(ctx->ar_sp.top_k), (int)__builtin_bit_cast(uint32_t, ctx->ar_sp.penalty), ctx->ar_penalty_scope, 0);
+}
 static void hist_reset_row(uint32_t *hb) { // what a begin leaves: ids 1 and 8192 (the prompt-shaped penalty row of step 0)
   std::fill(hb, hb + TTS_HIST_WORDS, 0u);
   hb[1 >> 5] |= 1u << (1 & 31);
@@ -2464,7 +2514,7 @@ static void hist_reset_row(uint32_t *hb) { // what a begin leaves: ids 1 and 819
 
 // Every buffer that the decode step, a prompt pass of max_text + 2 rows and a latent pass of max_cand x 502 rows can touch is reserved here: nothing the
 // captured step bakes into its nodes (GraphSig) moves while the session is open. The caller has checked the limits.
-int ar_session_open(tts_ctx *ctx, int n_slots, int max_cand, int max_text, int max_steps) {
+int ar_session_open(tts_ctx *ctx, int n_slots, int max_cand, int max_text, int max_steps, bool rows) {
   ArState *st = ctx->ar;
   if (!st) return fail(ctx, TTS_ERR_STATE, "AR model not loaded");
   if (ctx->ar_weights != 0 && ctx->ar_weights != st->loaded_wmode)
@@ -2472,6 +2522,7 @@ int ar_session_open(tts_ctx *ctx, int n_slots, int max_cand, int max_text, int m
   const int B = n_slots, Bpad = (B + 15) / 16 * 16, P = max_text + 2, max_pos = P + max_steps + 1;
   st->B = 0; // (a failure below leaves no half-open state behind)
   st->session = false;
+  st->rows = false;
   st->g_c0.clear(); st->g_n.clear(); st->g_t0.clear(); st->g_ntext.clear(); st->g_voice.clear(); st->tokens.clear();
   st->multi = false;
   st->n_text = max_text; st->P = P; st->max_pos = max_pos;
@@ -2490,6 +2541,11 @@ int ar_session_open(tts_ctx *ctx, int n_slots, int max_cand, int max_text, int m
   TTS_HIP(ctx, st->hist.reserve(st->hist_host.size() * 4));
   TTS_HIP(ctx, hipMemcpy(st->hist.p, st->hist_host.data(), st->hist_host.size() * 4, hipMemcpyHostToDevice));
   st->hist_dev_valid = false; // (a later tts_ar_begin* starts from its own host copy)
+  if (rows) { // the control table, padded to whole tiles: every row starts under the session's own controls (a valid entry; every admission writes its own)
+    TTS_HIP(ctx, st->ctl.reserve((size_t)Bpad * sizeof(int4)));
+    const std::vector<int4> own((size_t)Bpad, control_entry(ctx));
+    TTS_HIP(ctx, hipMemcpy(st->ctl.p, own.data(), own.size() * sizeof(int4), hipMemcpyHostToDevice));
+  }
   const int lat_rows = max_cand * 502, S_max = std::min(1024, 1 + max_text + 502);
   CHECK(reserve_rows(ctx, st, std::max({Bpad, P, lat_rows})));
   TTS_HIP(ctx, hipMemsetAsync(st->h.p, 0, st->h.cap, ctx->stream)); // the tile padding rows of the h4 layout are read (never stored): finite
@@ -2505,6 +2561,7 @@ int ar_session_open(tts_ctx *ctx, int n_slots, int max_cand, int max_text, int m
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   st->sess_captures0 = -1;
   st->session = true;
+  st->rows = rows;
   st->sa_S = 0; st->sa_rows = 0; // no audio until tts_ar_session_enable_audio
   st->B = B;
   return TTS_OK;
@@ -2514,6 +2571,7 @@ void ar_session_close(tts_ctx *ctx) {
   ArState *st = ctx->ar;
   if (!st || !st->session) return;
   st->session = false;
+  st->rows = false;
   st->sa_S = 0; st->sa_rows = 0;
   st->B = 0; // tts_ar_begin* starts over; the session's step graph stays for the next session of the same shape
 }
@@ -2532,6 +2590,16 @@ int ar_session_prompt(tts_ctx *ctx, int c0, int n_cand, const int32_t *text_ids,
   CHECK(prompt_pass(ctx, st, c0, n_cand, n_text, tok.data(), c0));
   TTS_HIP(ctx, hipMemcpyAsync(logits_row, st->logits.as<float>() + (size_t)c0 * V, (size_t)V * 4, hipMemcpyDeviceToHost, ctx->stream));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return TTS_OK;
+}
+
+// Rows [c0, c0 + n) of a rows session's control table take the controls the context holds (the caller has put the request's there at its admission):
+// written between two steps, outside the graph, as ar_session_prompt resets the history rows.
+int ar_session_controls(tts_ctx *ctx, int c0, int n) {
+  ArState *st = ctx->ar;
+  if (!st || !st->session || !st->rows || c0 < 0 || n < 1 || c0 + n > st->B) return fail(ctx, TTS_ERR_STATE, "ar_session_controls: no session with per-row controls, or rows outside it");
+  const std::vector<int4> e((size_t)n, control_entry(ctx));
+  TTS_HIP(ctx, hipMemcpy(st->ctl.as<int4>() + c0, e.data(), e.size() * sizeof(int4), hipMemcpyHostToDevice));
   return TTS_OK;
 }
 
@@ -2563,7 +2631,7 @@ int ar_session_step(tts_ctx *ctx, const int32_t *toks, const int32_t *n_past, co
   for (int r = B; r < Bpad; r++) st->h_toks[B + r] = 0;
   const double step_bytes = (ctx->ar_weights == 2 ? 1.0 : ctx->ar_weights == 1 ? 2.0 : 4.0) * ((double)st->n_layers * 12.0 * D * D + (double)D * V) +
                             kv_rows * st->n_layers * 2.0 * D * 2.0 + (double)B * V * 4.0;
-  CHECK(launch_step(ctx, st, 3, step_bytes));
+  CHECK(launch_step(ctx, st, st->rows ? 4 : 3, step_bytes));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (st->sess_captures0 < 0) st->sess_captures0 = st->graph_captures;
   return TTS_OK;
