@@ -496,6 +496,70 @@ int tts_host_ar_request_check(const tts_ar_request *req, int max_cand, int max_s
 /* host probe: the allocator's rule. busy [n_slots] (nonzero = taken): the first index of the lowest run of n_cand free slots, or -1 (also for a null map,
  * n_slots < 1 or n_cand < 1). */
 int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand);
+/* ---- In-flight batching for the diffusion stage (additions within version 8; no prototype changed) ----
+ * A diffusion session is one packed layout whose membership changes between sampling steps. Every request brings its own candidates, step count, sampler,
+ * eta, guidance strength, voice latent and noise, and runs from its own step 0 whatever step the others are at.
+ * Contract: tts_diff_session_collect returns, bit for bit, what the request returns ALONE through the single calls with "latency_mode" 0: tts_set_option of its
+ *   diff_sampler / ddim_eta / cond_free_k, tts_set_diffusion_conditioning_latent of its voice (if it brings one), then tts_diffusion(n_steps, noise) for explicit
+ *   noise, or tts_seed(seed) + tts_diffusion(NULL, TTS_NOISE_DEVICE) with the rng_shard_* options unset for noise == NULL (candidate c uses stream c). This holds
+ *   whatever else is in the layout, whatever step the other requests are at and whenever the request was admitted.
+ * tts_diff_request: plain C and able to grow under tts_ar_request's rule (struct_size = the caller's sizeof, fields are only appended). latents: the
+ *   candidates' [rows[c]][1024] back to back; rows in 1 .. 500; voice_latent2048 NULL = the loaded model's; noise: tts_diffusion's layout for this request alone
+ *   (per candidate n_steps + 1 vectors of 100 * T_c, deterministic DDIM: x_T alone) or NULL = the device generator under `seed`. sampler, ddim_eta and
+ *   cond_free_k are checked with the very predicate tts_set_option applies to "diff_sampler", "ddim_eta" and "cond_free_k".
+ * tts_diff_request_init: n_cand = 1, n_steps = 80, every pointer NULL, seed = 0, and the sampler, eta and k the session pinned when it was opened.
+ * tts_diff_session_open(max_packed_rows, max_requests): every option the diffusion stage reads is read here and holds until tts_diff_session_close, whatever
+ *   tts_set_option stores meanwhile: "attn_f32", "share_uncond", "hoist_integrator", "diff_graph", "gn_eps", "ggml_lut", "attn_proj_f16", "proj_dual_b",
+ *   "gemm_wreg", "attn_f32_drop", "lc_attn_f32", "attn_q64", "fp16_check", and "diff_sampler" / "ddim_eta" / "cond_free_k" as tts_diff_request_init's
+ *   defaults; the session always runs the batch-path GroupNorm ("latency_mode" is not bit-identical to it by design). With "hoist_integrator" on, every request
+ *   is hoisted and owns n_steps x packed rows x 2 KB of device memory until it is collected; a request may then take at most 16384 packed rows (the option's
+ *   value, if above 1), else tts_diff_session_admit returns TTS_ERR_LIMIT; a session opened with "hoist_integrator" 0 has no such bound. All activation buffers for max_packed_rows rows are allocated here. A session already open is closed first. TTS_ERR_ARG:
+ *   max_packed_rows < 128 or max_requests < 1; TTS_ERR_LIMIT: more than 2^20 rows or 4096 requests; TTS_ERR_STATE before tts_load_diffusion.
+ *   While a session is open tts_diffusion, tts_diffusion_multi_voice, tts_diffusion_forward and tts_load_diffusion return TTS_ERR_STATE (admission uses their
+ *   run state); after close they behave exactly as before. An AR session may be open on the same context.
+ * tts_diff_session_admit: returns the request id (>= 0, never reused in a session). Every check runs before any device work and a refused call changes
+ *   nothing: TTS_ERR_ARG for a null descriptor / latents / rows, a struct_size too small, n_cand < 1, rows outside 1 .. 500, n_steps < 2, a control
+ *   tts_set_option would refuse, a non-finite latent or voice value; TTS_ERR_LIMIT when the request's packed rows (tts_host_diff_packed_rows) exceed
+ *   tts_diff_session_room, exceed the hoisting bound above, or max_requests requests are held. Admission evaluates everything that does not depend on x_t for the request alone (latent
+ *   conditioner, time MLP, and with "hoist_integrator" the integrator layers of all its steps) into storage the request owns; it joins the layout at the next step.
+ * tts_diff_session_room: packed rows still free = max_packed_rows minus the packed rows of the running requests (a finished request holds none).
+ * tts_diff_session_step: one sampling step for every running request, each at its own step; returns the number still running (0 with none: no device work).
+ *   Admits, finishes and cancels since the previous step take effect here: ONE layout rebuild and ONE graph capture ("diff_graph" 1) for a step whose
+ *   membership changed, none otherwise. The host counts every request's steps: no device read detects a finish.
+ * tts_diff_session_finished: ids of finished, uncollected requests into ids[cap]; returns how many there are.
+ * tts_diff_session_collect: mel_out [cand][100][T_c] of a finished request, which then leaves the session. TTS_ERR_ARG: unknown id; TTS_ERR_STATE: still running.
+ * tts_diff_session_cancel: drops a request, running or finished; the others are unaffected.
+ * tts_diff_session_captures: step graphs captured since open.
+ * No session call touches the context's generator. Every call on a host-only context returns TTS_ERR_HIP; a call that needs an open session returns
+ * TTS_ERR_STATE without one.
+ * Host probes (no GPU): tts_host_diff_packed_rows: the rows Layout::build's rule gives a request alone, conditioned + unconditioned sequences: starts aligned
+ *   to 8 from row 8, one guard row after every sequence, total padded to 128 (TTS_ERR_ARG for a null list, n_cand < 1 or rows outside 1 .. 500).
+ *   tts_host_diff_request_check: the status tts_diff_session_admit's descriptor checks return in a session of max_packed_rows (free requests and the open
+ *   flag are not its business). */
+typedef struct tts_diff_request {
+  uint32_t struct_size;              /* sizeof(tts_diff_request): set by the caller before tts_diff_request_init */
+  int32_t n_cand;
+  const float *latents;              /* candidates back to back */
+  const int32_t *rows;               /* [n_cand], 1 .. 500 */
+  const float *voice_latent2048;     /* NULL: the loaded model's */
+  int32_t n_steps;                   /* >= 2 */
+  int32_t sampler;                   /* 0 ancestral, 1 DDIM */
+  double ddim_eta, cond_free_k;
+  const float *noise;                /* tts_diffusion's layout for this request alone, or NULL */
+  uint32_t seed;                     /* device generator when noise == NULL */
+} tts_diff_request;
+int tts_diff_request_init(tts_ctx *ctx, tts_diff_request *req);
+int tts_diff_session_open(tts_ctx *ctx, int max_packed_rows, int max_requests);
+int tts_diff_session_admit(tts_ctx *ctx, const tts_diff_request *req);
+int tts_diff_session_room(const tts_ctx *ctx);
+int tts_diff_session_step(tts_ctx *ctx);
+int tts_diff_session_finished(tts_ctx *ctx, int32_t *ids, int cap);
+int tts_diff_session_collect(tts_ctx *ctx, int request, float *mel_out);
+int tts_diff_session_cancel(tts_ctx *ctx, int request);
+int tts_diff_session_close(tts_ctx *ctx);
+int tts_diff_session_captures(const tts_ctx *ctx);
+int tts_host_diff_packed_rows(const int32_t *latent_rows, int n_cand);
+int tts_host_diff_request_check(const tts_diff_request *req, int max_packed_rows);
 /* One diffusion_graph evaluation (main.cpp:5749-5841 cond / 5866-5961 uncond): inputs
  * input_latent_tensor [L][1024], noise_tensor = x_t [100][T], timestep (raw 0..3999 value whose
  * sinusoidal embedding the reference uploads as time_embedding_{i}); conditioning_free as the

@@ -38,6 +38,12 @@ class ArRequest(C.Structure):
                 ("temperature", C.c_double), ("top_k", C.c_double), ("top_p", C.c_double), ("repetition_penalty", C.c_double), ("penalty_scope", C.c_double)]
 
 
+class DiffRequest(C.Structure):
+    """tts_diff_request: one diffusion-session request's candidates, step count, sampler controls, voice latent and noise (tts_diff_session_admit)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_cand", C.c_int32), ("latents", C.c_void_p), ("rows", C.c_void_p), ("voice_latent2048", C.c_void_p),
+                ("n_steps", C.c_int32), ("sampler", C.c_int32), ("ddim_eta", C.c_double), ("cond_free_k", C.c_double), ("noise", C.c_void_p), ("seed", C.c_uint32)]
+
+
 # the keys of ar_session_admit(controls=...) and the descriptor fields they set
 AR_CONTROL_FIELDS = {"temperature": "temperature", "top_k": "top_k", "top_p": "top_p", "penalty": "repetition_penalty", "scope": "penalty_scope"}
 
@@ -100,6 +106,11 @@ def lib():
         "tts_host_session_first_fit": (ci, [vp, ci, ci]),
         "tts_ar_request_init": (ci, [vp, C.POINTER(ArRequest)]), "tts_ar_session_admit_ex": (ci, [vp, vp, ci, vp, C.POINTER(ArRequest)]),
         "tts_host_ar_request_check": (ci, [C.POINTER(ArRequest), ci, ci]),
+        "tts_diff_request_init": (ci, [vp, C.POINTER(DiffRequest)]), "tts_diff_session_open": (ci, [vp, ci, ci]),
+        "tts_diff_session_admit": (ci, [vp, C.POINTER(DiffRequest)]), "tts_diff_session_room": (ci, [vp]), "tts_diff_session_step": (ci, [vp]),
+        "tts_diff_session_finished": (ci, [vp, vp, ci]), "tts_diff_session_collect": (ci, [vp, ci, vp]), "tts_diff_session_cancel": (ci, [vp, ci]),
+        "tts_diff_session_close": (ci, [vp]), "tts_diff_session_captures": (ci, [vp]),
+        "tts_host_diff_packed_rows": (ci, [vp, ci]), "tts_host_diff_request_check": (ci, [C.POINTER(DiffRequest), ci]),
         "tts_diffusion_forward": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p]),
         "tts_diffusion": (ci, [vp, _f32p, _i32p, ci, ci, vp, ci, _f32p]),
         "tts_vocoder_samples": (ci, [ci]),
@@ -140,6 +151,7 @@ class Engine:
         self.h = self.L.tts_create(device)
         if not self.h:
             raise TtsError("tts_create(%d) failed: no usable HIP device (this engine has no CPU path)" % device)
+        self._diff_frames = {}  # frames per candidate of the diffusion session's requests, by id (diff_session_collect sizes its buffer from it)
 
     def close(self):
         if getattr(self, "h", None):
@@ -605,6 +617,67 @@ class Engine:
             off += 100 * t
         return out
 
+    # ---- in-flight batching for the diffusion stage: requests join and leave a running layout (tts_diff_session_*) ----
+    def diff_session_open(self, max_packed_rows, max_requests):
+        """Opens a diffusion session for layouts of up to max_packed_rows rows (host_diff_packed_rows says what a request takes) and max_requests requests.
+        The options attn_f32, share_uncond, hoist_integrator, diff_graph and the sampler defaults are read here and hold until diff_session_close()."""
+        self._ck(self.L.tts_diff_session_open(self.h, max_packed_rows, max_requests))
+        self._diff_frames = {}
+
+    def diff_session_admit(self, latents_list, n_steps=None, sampler=None, ddim_eta=None, cond_free_k=None, voice_latent=None, noise=None, seed=0):
+        """Admits one request: latents_list as in diffusion(); noise: list of [(n_steps+1), 100*T_c] (deterministic DDIM: x_T [100*T_c]) or None = the device
+        generator under `seed`; voice_latent [2048] or None = the loaded model's. Arguments left None take the session's pinned value (tts_diff_request_init).
+        Returns the request id. The mel diff_session_collect() returns is bit for bit what diffusion() returns for the request alone."""
+        req = DiffRequest()
+        req.struct_size = C.sizeof(DiffRequest)
+        self._ck(self.L.tts_diff_request_init(self.h, C.byref(req)))
+        rows = np.array([len(l) for l in latents_list], np.int32)
+        lat = np.ascontiguousarray(np.concatenate([np.asarray(l, np.float32).reshape(-1, DMODEL) for l in latents_list]))
+        nz = None if noise is None else np.ascontiguousarray(np.concatenate([np.asarray(n, np.float32).reshape(-1) for n in noise]))
+        v = None if voice_latent is None else np.ascontiguousarray(voice_latent, np.float32).reshape(2 * DMODEL)
+        req.n_cand, req.latents, req.rows, req.voice_latent2048, req.noise, req.seed = len(rows), _ptr(lat), _ptr(rows), _ptr(v), _ptr(nz), seed
+        for field, value in (("n_steps", n_steps), ("sampler", sampler), ("ddim_eta", ddim_eta), ("cond_free_k", cond_free_k)):
+            if value is not None:
+                setattr(req, field, value)
+        rid = self._ck(self.L.tts_diff_session_admit(self.h, C.byref(req)))
+        self._diff_frames[rid] = [self.frames(int(r)) for r in rows]
+        return rid
+
+    def diff_session_room(self):
+        return self._ck(self.L.tts_diff_session_room(self.h))
+
+    def diff_session_step(self):
+        """One sampling step for every running request, each at its own step; returns how many are still running."""
+        return self._ck(self.L.tts_diff_session_step(self.h))
+
+    def diff_session_finished(self):
+        out = np.zeros(4096, np.int32)
+        n = self._ck(self.L.tts_diff_session_finished(self.h, _ptr(out), len(out)))
+        return [int(x) for x in out[:n]]
+
+    def diff_session_collect(self, request):
+        """A finished request's list of mel [100, T_c]; the request leaves the session."""
+        Ts = self._diff_frames.get(request) or []  # an id this engine never admitted: the library refuses it
+        mel = np.empty(max(1, sum(100 * t for t in Ts)), np.float32)
+        self._ck(self.L.tts_diff_session_collect(self.h, request, _ptr(mel)))
+        self._diff_frames.pop(request, None)
+        out, off = [], 0
+        for t in Ts:
+            out.append(mel[off:off + 100 * t].reshape(100, t).copy())
+            off += 100 * t
+        return out
+
+    def diff_session_cancel(self, request):
+        self._ck(self.L.tts_diff_session_cancel(self.h, request))
+        self._diff_frames.pop(request, None)
+
+    def diff_session_close(self):
+        self._ck(self.L.tts_diff_session_close(self.h))
+        self._diff_frames = {}
+
+    def diff_session_captures(self):
+        return self._ck(self.L.tts_diff_session_captures(self.h))
+
     # ---- vocoder ----
     def vocoder(self, mels, noise=None, noise_mode=NOISE_REFERENCE):
         frames = np.array([m.shape[1] for m in mels], np.int32)
@@ -749,6 +822,24 @@ def host_ar_request_check(max_cand, max_steps, struct_size=None, n_cand=1, seed=
     """The status tts_ar_session_admit_ex's descriptor checks return for these fields in a session of max_cand candidates and max_steps steps (no GPU)."""
     req = ArRequest(C.sizeof(ArRequest) if struct_size is None else struct_size, n_cand, seed, req_max_steps, None, temperature, top_k, top_p, penalty, scope)
     return lib().tts_host_ar_request_check(C.byref(req), max_cand, max_steps)
+
+
+def host_diff_packed_rows(latent_rows):
+    """Packed rows a diffusion-session request of these latent row counts takes (conditioned + unconditioned sequences, Layout::build's rule; no GPU)."""
+    r = np.ascontiguousarray(latent_rows, np.int32).reshape(-1)
+    return lib().tts_host_diff_packed_rows(_ptr(r), len(r))
+
+
+def host_diff_request_check(max_packed_rows, latents=None, rows=None, n_cand=None, n_steps=80, sampler=0, ddim_eta=0.0, cond_free_k=2.0, voice=None, struct_size=None,
+                            null_latents=False, null_rows=False):
+    """The status tts_diff_session_admit's descriptor checks return for these fields in a session with max_packed_rows free rows (no GPU). latents: list of
+    [L_c, 1024]; rows / n_cand override what the list implies."""
+    lat = np.ascontiguousarray(np.concatenate([np.asarray(l, np.float32).reshape(-1, DMODEL) for l in latents]))
+    rw = np.ascontiguousarray([len(l) for l in latents] if rows is None else rows, np.int32)
+    v = None if voice is None else np.ascontiguousarray(voice, np.float32).reshape(2 * DMODEL)
+    req = DiffRequest(C.sizeof(DiffRequest) if struct_size is None else struct_size, len(latents) if n_cand is None else n_cand, None if null_latents else _ptr(lat),
+                      None if null_rows else _ptr(rw), _ptr(v), n_steps, int(sampler), ddim_eta, cond_free_k, None, 0)
+    return lib().tts_host_diff_request_check(C.byref(req), max_packed_rows)
 
 
 def host_session_first_fit(busy, n_cand):

@@ -302,6 +302,7 @@ void tts_destroy(tts_ctx *c) {
   if (c->device < 0) { delete c->tok; delete c; return; }
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
+  diff_session_close(c);
   if (c->ar) ar_free(c->ar);
   if (c->diff) diff_free(c->diff);
   if (c->voc) voc_free(c->voc);
@@ -390,16 +391,17 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     if (value != 0 && value != 1 && value != 2) return fail(c, TTS_ERR_ARG, "ar_weights: 0 (f32), 1 (fp16) or 2 (fp8 e4m3)");
     c->ar_weights = (int)value;
   }
-  else if (k == "diff_sampler") { // additions within version 8: the sampler of tts_diffusion / tts_diffusion_multi_voice
-    if (value != 0 && value != 1) return fail(c, TTS_ERR_ARG, "diff_sampler: 0 (ancestral DDPM) or 1 (DDIM)");
+  else if (k == "diff_sampler") { // additions within version 8: the sampler of tts_diffusion / tts_diffusion_multi_voice (diff_control_error: the one statement of
+                                  // what the three accept, shared with a diffusion session's request descriptor)
+    if (const char *e = diff_control_error(0, value)) return fail(c, TTS_ERR_ARG, "%s", e);
     c->diff_sampler = (int)value;
   }
   else if (k == "ddim_eta") {
-    if (!(value >= 0 && value <= 1)) return fail(c, TTS_ERR_ARG, "ddim_eta: a value in [0, 1]");
+    if (const char *e = diff_control_error(1, value)) return fail(c, TTS_ERR_ARG, "%s", e);
     c->ddim_eta = value;
   }
   else if (k == "cond_free_k") {
-    if (!std::isfinite(value) || value < 0 || !std::isfinite((float)value)) return fail(c, TTS_ERR_ARG, "cond_free_k: a finite value >= 0");
+    if (const char *e = diff_control_error(2, value)) return fail(c, TTS_ERR_ARG, "%s", e);
     c->cond_free_k = (float)value;
   }
   // additions within version 8: the autoregressive sampler's controls (read by tts_sample, tts_ar_step_sample and the tts_autoregressive* drivers)
@@ -465,7 +467,12 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
   } while (0)
 
 int tts_load_ar(tts_ctx *c, const char *path) { NEED_CTX(c); NO_SESSION(c, "tts_load_ar"); return guarded(c, [&] { return ar_load(c, path); }); }
-int tts_load_diffusion(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return diff_load(c, path); }); }
+// While a diffusion session is open (tts_diff_session_open) its admissions own the diffusion run state: the single-call entry points refuse.
+#define NO_DIFF_SESSION(c, name)                                                                                                \
+  do {                                                                                                                        \
+    if ((c)->diff_session) return fail((c), TTS_ERR_STATE, "%s: a diffusion session is open (tts_diff_session_close first)", name); \
+  } while (0)
+int tts_load_diffusion(tts_ctx *c, const char *path) { NEED_CTX(c); NO_DIFF_SESSION(c, "tts_load_diffusion"); return guarded(c, [&] { return diff_load(c, path); }); }
 int tts_load_vocoder(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return voc_load(c, path); }); }
 int tts_load_diffusion_conditioning_encoder(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return diff_cond_enc_load(c, path); }); }
 int tts_diffusion_conditioning_latent(tts_ctx *c, const float *mel, const int32_t *frames, int n_clips, float *out2048) {
@@ -1295,21 +1302,96 @@ int tts_ar_session_audio(tts_ctx *c, int request, float *out, int cap_samples, i
   });
 }
 
-int tts_diffusion_frames(int L) { return L * 4 * 24000 / 22050; }
+// ---- diffusion session: the entry points (state and device work: diffusion.hip; descriptor checks: host_logic.cpp) ----
+#define NEED_DIFF_SESSION(c, name)                                                                          \
+  do {                                                                                                      \
+    if (!(c)->diff_session) return fail((c), TTS_ERR_STATE, "%s: tts_diff_session_open not called", name); \
+  } while (0)
+int tts_diff_session_open(tts_ctx *c, int max_packed_rows, int max_requests) {
+  NEED_CTX(c);
+  if (!c->diff) return fail(c, TTS_ERR_STATE, "diffusion model not loaded");
+  if (max_packed_rows < 128 || max_requests < 1)
+    return fail(c, TTS_ERR_ARG, "tts_diff_session_open: bad argument (max_packed_rows %d: >= 128, max_requests %d: >= 1)", max_packed_rows, max_requests);
+  if (max_packed_rows > (1 << 20) || max_requests > 4096)
+    return fail(c, TTS_ERR_LIMIT, "tts_diff_session_open: %d rows / %d requests, at most 2^20 / 4096", max_packed_rows, max_requests);
+  return guarded(c, [&] { return diff_session_open(c, max_packed_rows, max_requests); });
+}
+int tts_diff_session_close(tts_ctx *c) {
+  NEED_CTX(c);
+  NEED_DIFF_SESSION(c, "tts_diff_session_close");
+  diff_session_close(c);
+  return TTS_OK;
+}
+int tts_diff_request_init(tts_ctx *c, tts_diff_request *req) {
+  NEED_CTX(c);
+  NEED_DIFF_SESSION(c, "tts_diff_request_init");
+  if (!req) return fail(c, TTS_ERR_ARG, "tts_diff_request_init: null request");
+  if (req->struct_size < sizeof(tts_diff_request))
+    return fail(c, TTS_ERR_ARG, "tts_diff_request_init: struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_diff_request) first)", req->struct_size,
+                sizeof(tts_diff_request));
+  req->n_cand = 1; req->latents = nullptr; req->rows = nullptr; req->voice_latent2048 = nullptr; req->n_steps = 80; req->noise = nullptr; req->seed = 0;
+  diff_session_defaults(c, req);
+  return TTS_OK;
+}
+int tts_diff_session_room(const tts_ctx *c) {
+  if (!c) return TTS_ERR_ARG;
+  if (c->device < 0) return TTS_ERR_HIP;
+  if (!c->diff_session) return TTS_ERR_STATE;
+  return diff_session_room(c);
+}
+int tts_diff_session_captures(const tts_ctx *c) {
+  if (!c) return TTS_ERR_ARG;
+  if (c->device < 0) return TTS_ERR_HIP;
+  if (!c->diff_session) return TTS_ERR_STATE;
+  return diff_session_captures(c);
+}
+int tts_diff_session_admit(tts_ctx *c, const tts_diff_request *req) {
+  NEED_CTX(c);
+  NEED_DIFF_SESSION(c, "tts_diff_session_admit");
+  std::string why; // every check before any device work
+  if (int rc = diff_request_check(req, diff_session_room(c), why)) return fail(c, rc, "tts_diff_session_admit: %s", why.c_str());
+  return guarded(c, [&] { return diff_session_admit(c, req); });
+}
+int tts_diff_session_step(tts_ctx *c) {
+  NEED_CTX(c);
+  NEED_DIFF_SESSION(c, "tts_diff_session_step");
+  return guarded(c, [&] { return diff_session_step(c); });
+}
+int tts_diff_session_finished(tts_ctx *c, int32_t *ids, int cap) {
+  NEED_CTX(c);
+  NEED_DIFF_SESSION(c, "tts_diff_session_finished");
+  if (cap < 0 || (cap > 0 && !ids)) return fail(c, TTS_ERR_ARG, "tts_diff_session_finished: bad argument");
+  return guarded(c, [&] { return diff_session_finished(c, ids, cap); });
+}
+int tts_diff_session_collect(tts_ctx *c, int request, float *mel_out) {
+  NEED_CTX(c);
+  NEED_DIFF_SESSION(c, "tts_diff_session_collect");
+  if (!mel_out) return fail(c, TTS_ERR_ARG, "tts_diff_session_collect: null output");
+  return guarded(c, [&] { return diff_session_collect(c, request, mel_out); });
+}
+int tts_diff_session_cancel(tts_ctx *c, int request) {
+  NEED_CTX(c);
+  NEED_DIFF_SESSION(c, "tts_diff_session_cancel");
+  return guarded(c, [&] { return diff_session_cancel(c, request); });
+}
+
 int tts_diffusion_forward(tts_ctx *c, const float *latents, int L, const float *x_t, int timestep, int cond_free, float *out) {
   NEED_CTX(c);
+  NO_DIFF_SESSION(c, "tts_diffusion_forward");
   return guarded(c, [&] { return diff_forward(c, latents, L, x_t, timestep, cond_free, out); });
 }
 int tts_diffusion(tts_ctx *c, const float *latents, const int32_t *rows, int B, int n_steps, const float *noise,
                   int noise_mode, float *mel_out) {
   NEED_CTX(c);
   // the DEVICE noise streams are keyed by the global candidate id; host / reference noise does not look at the shard options
+  NO_DIFF_SESSION(c, "tts_diffusion");
   if (B >= 1 && !noise && noise_mode == TTS_NOISE_DEVICE) if (int rc = shard_check(c, B)) return rc;
   return guarded(c, [&] { return diff_sample(c, latents, rows, B, n_steps, noise, noise_mode, mel_out); });
 }
 int tts_diffusion_multi_voice(tts_ctx *c, const float *latents, const int32_t *rows, int B, const float *voice_latents, int n_voices,
                               const int32_t *voice_of_candidate, int n_steps, const float *noise, int noise_mode, float *mel_out) {
   NEED_CTX(c);
+  NO_DIFF_SESSION(c, "tts_diffusion_multi_voice");
   if (B >= 1 && !noise && noise_mode == TTS_NOISE_DEVICE) if (int rc = shard_check(c, B)) return rc;
   return guarded(c, [&] { return diff_sample_voices(c, latents, rows, B, voice_latents, n_voices, voice_of_candidate, n_steps, noise, noise_mode, mel_out); });
 }

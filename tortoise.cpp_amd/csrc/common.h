@@ -95,6 +95,7 @@ struct Tokenizer;
 struct SamplerPool;
 void sampler_pool_free(SamplerPool *p);
 struct ArSession; // the book of an open session (tts_ar_session_*): api.cpp
+struct DiffSession; // an open diffusion session (tts_diff_session_*): diffusion.hip
 // One request's share of an incremental latent pass (ar.hip: ar_session_extend): the rows [have, upto) of the request in slot `slot`, whose prompt has n_text
 // ids; codes502: the pass' input row by row (8192, then the sampled codes).
 struct ArExtendItem { int slot, n_text, have, upto; const int32_t *codes502; };
@@ -134,6 +135,7 @@ struct tts_ctx {
   tts::HifiganState *hifigan = nullptr; // HiFi-GAN decoder: latents -> waveform (hifigan.hip; not in the reference: upstream's api_fast.py path)
   tts::Tokenizer *tok = nullptr;
   tts::ArSession *session = nullptr;        // non-null while a session is open: tts_ar_begin*, tts_autoregressive* and tts_hifigan_stream then return TTS_ERR_STATE
+  tts::DiffSession *diff_session = nullptr; // non-null while a diffusion session is open: tts_diffusion, tts_diffusion_multi_voice, tts_diffusion_forward and tts_load_diffusion then return TTS_ERR_STATE
   tts::SamplerPool *sampler_pool = nullptr; // worker threads for the per-candidate sampler scans (host_logic.cpp)
   tts::SamplerParams ar_sp;                 // options "ar_temperature" / "ar_top_k" / "ar_top_p" / "ar_repetition_penalty"
   int ar_penalty_scope = 0;                 // option "ar_penalty_scope": 0 = the reference (the ids of the last input), 1 = upstream's HF generate (every id fed since tts_ar_begin*, plus 1 and 8192)
@@ -412,6 +414,24 @@ int diff_cond_enc_load(tts_ctx *ctx, const char *path);
 void diff_cond_enc_free(DiffCondEncState *);
 int diff_cond_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out2048);
 int diff_fp16_check(tts_ctx *ctx, int64_t counts[2]);            // diffusion.hip
+// The diffusion sampler's three controls (options "diff_sampler", "ddim_eta", "cond_free_k"): the ONE statement of what each accepts, for tts_set_option and for a
+// request descriptor (tts_diff_session_admit, tts_host_diff_request_check). which: 0 sampler, 1 eta, 2 k. Returns the refusal's text, or null (host_logic.cpp).
+const char *diff_control_error(int which, double value);
+// rows Layout::build gives the sequences `frames` (diffusion.hip): starts aligned to 8 from row 8, a guard row after each, total padded to 128 (host_logic.cpp)
+int diff_packed_rows(const int *frames, int n);
+// what a request descriptor must satisfy in a session of max_packed_rows, before any device work: the status and, in `why`, the text (host_logic.cpp)
+int diff_request_check(const tts_diff_request *req, int max_packed_rows, std::string &why);
+// the diffusion session (diffusion.hip); arguments already checked by api.cpp
+int diff_session_open(tts_ctx *ctx, int max_packed_rows, int max_requests);
+int diff_session_admit(tts_ctx *ctx, const tts_diff_request *req);
+int diff_session_room(const tts_ctx *ctx);
+int diff_session_step(tts_ctx *ctx);
+int diff_session_finished(tts_ctx *ctx, int32_t *ids, int cap);
+int diff_session_collect(tts_ctx *ctx, int request, float *mel_out);
+int diff_session_cancel(tts_ctx *ctx, int request);
+void diff_session_close(tts_ctx *ctx);
+int diff_session_captures(const tts_ctx *ctx);
+void diff_session_defaults(const tts_ctx *ctx, tts_diff_request *req); // the sampler, eta and k the open session pinned
 int diff_set_cond_latent(tts_ctx *ctx, const float *latent2048); // diffusion.hip: overrides the weight file's diffusion_conditioning_latent
 int voice_enc_load(tts_ctx *ctx, const char *path);
 void voice_enc_free(VoiceEncState *);

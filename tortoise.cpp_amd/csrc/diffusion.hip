@@ -755,27 +755,14 @@ __global__ __launch_bounds__(256) void step_begin_kernel(const float *__restrict
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < ss_stride / 4; i += (size_t)gridDim.x * 256) dst[i] = src[i];
 }
 __global__ void step_advance_kernel(int *ctr) { *ctr += 1; }
-__global__ __launch_bounds__(128) void ddpm_update_kernel(const float *__restrict__ net, float *__restrict__ x,
-                                                          const int64_t *__restrict__ x_off, const int *__restrict__ row_seq,
-                                                          const int *__restrict__ row_t, const int *__restrict__ seq_len,
-                                                          const int *__restrict__ seq_start, int ncand, const StepEntry *__restrict__ tab,
-                                                          const int *__restrict__ ctr, const float *__restrict__ noise_base /* or null */,
-                                                          uint64_t seed, uint32_t stream0 /* global id of candidate 0 */) {
-  const int r = blockIdx.x, s = row_seq[r], ch = threadIdx.x;
-  if (s < 0 || s >= ncand || ch >= 100) return;
-  const StepEntry e = tab[*ctr];
-  const StepScalars sc = e.sc;
-  const float *noise = e.has_noise ? noise_base + e.noise_off : nullptr; // same layout as x
-  const uint32_t step = e.philox_step;
-  const int T = seq_len[s], t = row_t[r];
-  const size_t xi = x_off[s] + (size_t)ch * T + t;
-  const float eps_c = net[(size_t)r * 256 + ch], var_c = net[(size_t)r * 256 + 100 + ch];
-  const float eps_u = net[(size_t)(seq_start[s + ncand] + t) * 256 + ch];
-  const float xv = x[xi];
-  // Every f32 operation below is the reference's, one rounding each (main.cpp:5970-6030 is plain C++ built without FMA contraction; the oracle's copy is compiled with
-  // -ffp-contract=off). hipcc would contract a * b + c * d into FMAs: a last-bit difference in x_t at EVERY step that the torch-f32 yardstick of the parity floor (which
-  // shares the oracle's update) does not have, and that a chaotic 80- / 200-step loop amplifies like any other f32 difference (round 6: the 200-step loop at full depth
-  // sat at 1.44-1.58 x its f32-vs-f32 floor in BOTH arithmetic modes).
+// The arithmetic of one element of the ancestral step: ONE body for ddpm_update_kernel and the session's diff_session_update_kernel.
+// Every f32 operation below is the reference's, one rounding each (main.cpp:5970-6030 is plain C++ built without FMA contraction; the oracle's copy is compiled with
+// -ffp-contract=off). hipcc would contract a * b + c * d into FMAs: a last-bit difference in x_t at EVERY step that the torch-f32 yardstick of the parity floor (which
+// shares the oracle's update) does not have, and that a chaotic 80- / 200-step loop amplifies like any other f32 difference (round 6: the 200-step loop at full depth
+// sat at 1.44-1.58 x its f32-vs-f32 floor in BOTH arithmetic modes).
+// noise: this step's block in the layout of x (the value is read at xi), or null: the device generator's stream `stream`, element idx.
+__device__ __forceinline__ float ddpm_step_value(const StepScalars &sc, float eps_c, float var_c, float eps_u, float xv, const float *__restrict__ noise, size_t xi,
+                                                 uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
   float mean, model_log_variance;
   {
 #pragma clang fp contract(off)
@@ -789,17 +776,52 @@ __global__ __launch_bounds__(128) void ddpm_update_kernel(const float *__restric
   }
   float outv = mean;
   if (!sc.is_last) {
-    const float nz = noise ? noise[xi] : philox_normal(seed, stream0 + (uint32_t)s, step, (uint32_t)(ch * T + t));
+    const float nz = noise ? noise[xi] : philox_normal(seed, stream, step, idx);
     outv = (float)((double)mean + exp(0.5 * (double)model_log_variance) * (double)nz);
   }
-  x[xi] = outv;
+  return outv;
+}
+// The same for the DDIM step (see ddim_update_kernel): the learned variance is not read.
+struct DdimEntry { float c_x0, c_eps, sigma, pad; };
+__device__ __forceinline__ float ddim_step_value(const StepScalars &sc, const DdimEntry &d, float eps_c, float eps_u, float xv, const float *__restrict__ noise, size_t xi,
+                                                 uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
+  float outv;
+  {
+#pragma clang fp contract(off)
+    const float eps_g = (1 + sc.cfk) * eps_c - sc.cfk * eps_u;
+    const float xs = sc.sqrt_recip * xv;
+    float x0 = xs - sc.sqrt_recipm1 * eps_g;
+    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+    const float eps_h = (xs - x0) / sc.sqrt_recipm1; // always re-derived from the clipped x0, as upstream (_predict_eps_from_xstart)
+    outv = d.c_x0 * x0 + d.c_eps * eps_h;
+    if (!sc.is_last && d.sigma != 0.0f) {
+      const float nz = noise ? noise[xi] : philox_normal(seed, stream, step, idx);
+      outv = outv + d.sigma * nz;
+    }
+  }
+  return outv;
+}
+__global__ __launch_bounds__(128) void ddpm_update_kernel(const float *__restrict__ net, float *__restrict__ x,
+                                                          const int64_t *__restrict__ x_off, const int *__restrict__ row_seq,
+                                                          const int *__restrict__ row_t, const int *__restrict__ seq_len,
+                                                          const int *__restrict__ seq_start, int ncand, const StepEntry *__restrict__ tab,
+                                                          const int *__restrict__ ctr, const float *__restrict__ noise_base /* or null */,
+                                                          uint64_t seed, uint32_t stream0 /* global id of candidate 0 */) {
+  const int r = blockIdx.x, s = row_seq[r], ch = threadIdx.x;
+  if (s < 0 || s >= ncand || ch >= 100) return;
+  const StepEntry e = tab[*ctr];
+  const float *noise = e.has_noise ? noise_base + e.noise_off : nullptr; // same layout as x
+  const int T = seq_len[s], t = row_t[r];
+  const size_t xi = x_off[s] + (size_t)ch * T + t;
+  const float eps_c = net[(size_t)r * 256 + ch], var_c = net[(size_t)r * 256 + 100 + ch];
+  const float eps_u = net[(size_t)(seq_start[s + ncand] + t) * 256 + ch];
+  x[xi] = ddpm_step_value(e.sc, eps_c, var_c, eps_u, x[xi], noise, xi, seed, stream0 + (uint32_t)s, e.philox_step, (uint32_t)(ch * T + t));
 }
 
 // DDIM step (upstream tortoise-tts ddim_sample on p_mean_variance with clip_denoised; the reference has no such sampler) for every candidate, in place on x: the grid,
 // block and indexing of ddpm_update_kernel, the same StepEntry (guidance k, sqrt_recip, sqrt_recipm1, noise block, generator key) plus this step's DdimEntry.
 // Channels 100..199 of net (the learned variance) are not read. Every f32 operation is rounded once (no FMA contraction), for the reason ddpm_update_kernel gives:
 // the numpy restatement the tests hold this kernel to performs exactly these roundings.
-struct DdimEntry { float c_x0, c_eps, sigma, pad; };
 __global__ __launch_bounds__(128) void ddim_update_kernel(const float *__restrict__ net, float *__restrict__ x,
                                                           const int64_t *__restrict__ x_off, const int *__restrict__ row_seq,
                                                           const int *__restrict__ row_t, const int *__restrict__ seq_len,
@@ -811,29 +833,104 @@ __global__ __launch_bounds__(128) void ddim_update_kernel(const float *__restric
   if (s < 0 || s >= ncand || ch >= 100) return;
   const int k = *ctr;
   const StepEntry e = tab[k];
-  const StepScalars sc = e.sc;
   const DdimEntry d = dtab[k];
   const float *noise = e.has_noise ? noise_base + e.noise_off : nullptr; // same layout as x
   const int T = seq_len[s], t = row_t[r];
   const size_t xi = x_off[s] + (size_t)ch * T + t;
   const float eps_c = net[(size_t)r * 256 + ch];
   const float eps_u = net[(size_t)(seq_start[s + ncand] + t) * 256 + ch];
-  const float xv = x[xi];
-  float outv;
-  {
-#pragma clang fp contract(off)
-    const float eps_g = (1 + sc.cfk) * eps_c - sc.cfk * eps_u;
-    const float xs = sc.sqrt_recip * xv;
-    float x0 = xs - sc.sqrt_recipm1 * eps_g;
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    const float eps_h = (xs - x0) / sc.sqrt_recipm1; // always re-derived from the clipped x0, as upstream (_predict_eps_from_xstart)
-    outv = d.c_x0 * x0 + d.c_eps * eps_h;
-    if (!sc.is_last && d.sigma != 0.0f) {
-      const float nz = noise ? noise[xi] : philox_normal(seed, stream0 + (uint32_t)s, e.philox_step, (uint32_t)(ch * T + t));
-      outv = outv + d.sigma * nz;
-    }
+  x[xi] = ddim_step_value(e.sc, d, eps_c, eps_u, x[xi], noise, xi, seed, stream0 + (uint32_t)s, e.philox_step, (uint32_t)(ch * T + t));
+}
+
+// ---- diffusion session (tts_diff_session_*): one packed layout whose sequences belong to different requests, each at a step of its own ----
+// What the step's kernels read of one request, by its slot: everything was computed at admission for the request alone and lives in storage the request owns.
+struct SessReqDev {
+  const float *ss_all;     // [n_steps][n_res][2048]: the request's scale / shift blocks (precompute_time)
+  const StepEntry *tab;    // [n_steps]
+  const DdimEntry *dtab;   // [n_steps], sampler 1 only
+  const __half *ce16_all;  // hoisted integrator: [n_steps][rows_local][1024], else null
+  float *x;                // [cand][100][T_c]
+  const float *noise;      // the request's noise blocks in the layout of x (StepEntry::noise_off), or null: the device generator under `seed`
+  unsigned long long seed;
+  int n_steps, sampler, rows_local, pad;
+};
+// Start of a session step. Request live[i] (a slot) copies the scale / shift block of ITS step to block `slot` of ss_cur; seq_step[s], the index of sequence s's
+// block that the GroupNorm kernels add to their ss pointer, is written from the sequence's slot. grid (16, n_live), block 256.
+__global__ __launch_bounds__(256) void diff_session_begin_kernel(const SessReqDev *__restrict__ req, const int *__restrict__ ctr, const int *__restrict__ live,
+                                                                 size_t ss_stride, float *__restrict__ ss_cur, const int *__restrict__ seq_req, int ns,
+                                                                 int *__restrict__ seq_step) {
+  const int slot = live[blockIdx.y], k = ctr[slot];
+  if (blockIdx.y == 0 && blockIdx.x == 0)
+    for (int s = threadIdx.x; s < ns; s += 256) seq_step[s] = seq_req[s];
+  if (k >= req[slot].n_steps) return; // finished: nothing of it is read
+  const float4 *src = (const float4 *)(req[slot].ss_all + (size_t)k * ss_stride);
+  float4 *dst = (float4 *)(ss_cur + (size_t)slot * ss_stride);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < ss_stride / 4; i += (size_t)gridDim.x * 256) dst[i] = src[i];
+}
+// End of a session step: the live requests' counters advance, nobody else's. One thread per live request.
+__global__ void diff_session_advance_kernel(const SessReqDev *__restrict__ req, int *__restrict__ ctr, const int *__restrict__ live, int n_live) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_live) return;
+  const int slot = live[i];
+  if (ctr[slot] < req[slot].n_steps) ctr[slot] += 1;
+}
+// xt_to_rows_kernel for the session: x of sequence s is its request's, at seq_xoff[s]; the unconditioned copy starts at row seq_partner[s] (-1 marks the
+// unconditioned sequences themselves). grid: rows; block 128.
+__global__ __launch_bounds__(128) void diff_session_xt_kernel(const SessReqDev *__restrict__ req, const int *__restrict__ seq_req, const int64_t *__restrict__ seq_xoff,
+                                                              const int *__restrict__ seq_partner, const int *__restrict__ row_seq, const int *__restrict__ row_t,
+                                                              const int *__restrict__ seq_len, __half *__restrict__ xt16) {
+  const int r = blockIdx.x, s = row_seq[r], ch = threadIdx.x;
+  if (s < 0) return;
+  const int p = seq_partner[s];
+  if (p < 0) return;
+  const int T = seq_len[s], t = row_t[r];
+  const float v = (ch < 100) ? req[seq_req[s]].x[seq_xoff[s] + (size_t)ch * T + t] : 0.f;
+  const __half hv = __float2half_rn(v);
+  xt16[(size_t)r * XTC + ch] = hv;
+  xt16[(size_t)(p + t) * XTC + ch] = hv;
+}
+// Row select (the session's select_step_slice_kernel): row r of the joint layout takes row row_src[r] of its own request's hoisted code-embedding operand, at that
+// request's own step. Guard rows: zero, as in the request's buffer. grid: rows; block 128 (one uint4 each).
+__global__ __launch_bounds__(128) void diff_session_row_select_kernel(const SessReqDev *__restrict__ req, const int *__restrict__ ctr, const int *__restrict__ seq_req,
+                                                                      const int *__restrict__ row_seq, const int *__restrict__ row_src, uint4 *__restrict__ dst) {
+  const int r = blockIdx.x, s = row_seq[r];
+  uint4 v = make_uint4(0u, 0u, 0u, 0u);
+  if (s >= 0) {
+    const int slot = seq_req[s];
+    const SessReqDev &q = req[slot];
+    const int k = min(ctr[slot], q.n_steps - 1);
+    v = ((const uint4 *)(q.ce16_all + ((size_t)k * q.rows_local + row_src[r]) * C))[threadIdx.x];
   }
-  x[xi] = outv;
+  dst[(size_t)r * (C / 8) + threadIdx.x] = v;
+}
+// The sampler update of a session step: per sequence the request's StepEntry / DdimEntry at the request's step, its sampler, its noise block or generator key (the
+// stream is the candidate's index in its request), and the unconditioned partner's first row from a table. Sequences of a request that has run all its steps are
+// left untouched. The arithmetic is ddpm_step_value / ddim_step_value, the bodies of the single call's kernels. grid: rows; block 128.
+__global__ __launch_bounds__(128) void diff_session_update_kernel(const float *__restrict__ net, const SessReqDev *__restrict__ req, const int *__restrict__ ctr,
+                                                                  const int *__restrict__ seq_req, const int64_t *__restrict__ seq_xoff,
+                                                                  const int *__restrict__ seq_partner, const int *__restrict__ seq_cand,
+                                                                  const int *__restrict__ row_seq, const int *__restrict__ row_t, const int *__restrict__ seq_len) {
+  const int r = blockIdx.x, s = row_seq[r], ch = threadIdx.x;
+  if (s < 0 || ch >= 100) return;
+  const int p = seq_partner[s];
+  if (p < 0) return;
+  const int slot = seq_req[s], k = ctr[slot];
+  const SessReqDev q = req[slot];
+  if (k >= q.n_steps) return;
+  const StepEntry e = q.tab[k];
+  const float *noise = e.has_noise ? q.noise + e.noise_off : nullptr; // same layout as x
+  const int T = seq_len[s], t = row_t[r];
+  const size_t xi = seq_xoff[s] + (size_t)ch * T + t;
+  const float eps_c = net[(size_t)r * 256 + ch];
+  const float eps_u = net[(size_t)(p + t) * 256 + ch];
+  const uint32_t stream = (uint32_t)seq_cand[s], idx = (uint32_t)(ch * T + t);
+  if (q.sampler == 1) {
+    const DdimEntry d = q.dtab[k];
+    q.x[xi] = ddim_step_value(e.sc, d, eps_c, eps_u, q.x[xi], noise, xi, q.seed, stream, e.philox_step, idx);
+  } else {
+    const float var_c = net[(size_t)r * 256 + 100 + ch];
+    q.x[xi] = ddpm_step_value(e.sc, eps_c, var_c, eps_u, q.x[xi], noise, xi, q.seed, stream, e.philox_step, idx);
+  }
 }
 
 __global__ void philox_fill_kernel(float *__restrict__ x, int64_t n, uint64_t seed, uint32_t stream, uint32_t step) {
@@ -869,7 +966,7 @@ struct Layout {
   std::vector<int> start, len;
   DevBuf d_row_seq, d_row_t, d_start, d_len, d_chunk_seq; // chunk_seq[r / 8]: owning sequence of an aligned 8-row chunk (-1: guard rows only)
   int build(tts_ctx *ctx, const std::vector<int> &lens) {
-    has_seq_step = false; ss_step_stride = 0;
+    has_seq_step = false; ss_step_stride = 0; gn_parts.clear();
     ns = (int)lens.size();
     len = lens;
     start.resize(ns);
@@ -899,6 +996,31 @@ struct Layout {
   int ss_step_stride = 0;
   bool has_seq_step = false;
   const int *seq_step_ptr() const { return has_seq_step ? d_seq_step.as<int>() : nullptr; }
+  // GroupNorm partition (the diffusion session): gn_fused picks its kernel by the layout's longest sequence, and the three kernels reduce in different orders. A
+  // layout that holds requests of different length classes (gn_class of the request's own longest sequence = the kernel the request gets alone) is normalised
+  // class by class: part k = the consecutive sequences [s0, s0 + ns) on rows [row0, row0 + rows), launched as a layout of its own (d_start_rel: starts relative
+  // to row0). Empty = one launch over the whole layout.
+  struct GnPart { int s0, ns, row0, rows, tmax; };
+  std::vector<GnPart> gn_parts;
+  DevBuf d_start_rel;
+  static int gn_class(int tmax) { return tmax <= 14 * 64 ? 0 : tmax <= 18 * 128 ? 1 : 2; }
+  int set_gn_parts(tts_ctx *ctx, const std::vector<int> &cls_of_seq) { // classes must be consecutive runs; after build()
+    gn_parts.clear();
+    std::vector<int> rel(ns, 0);
+    for (int s = 0; s < ns;) {
+      int e = s;
+      while (e < ns && cls_of_seq[e] == cls_of_seq[s]) e++;
+      GnPart g{s, e - s, s == 0 ? 0 : start[s], 0, 0};
+      g.rows = (e < ns ? start[e] : rows) - g.row0;
+      for (int i = s; i < e; i++) { rel[i] = start[i] - g.row0; g.tmax = std::max(g.tmax, len[i]); }
+      gn_parts.push_back(g);
+      s = e;
+    }
+    if (gn_parts.size() < 2) { gn_parts.clear(); return TTS_OK; }
+    TTS_HIP(ctx, d_start_rel.reserve((size_t)ns * 4));
+    TTS_HIP(ctx, hipMemcpy(d_start_rel.p, rel.data(), (size_t)ns * 4, hipMemcpyHostToDevice));
+    return TTS_OK;
+  }
   int set_seq_step(tts_ctx *ctx, const std::vector<int> &step_of_seq, int stride_floats) {
     TTS_HIP(ctx, d_seq_step.reserve(step_of_seq.size() * 4));
     TTS_HIP(ctx, hipMemcpy(d_seq_step.p, step_of_seq.data(), step_of_seq.size() * 4, hipMemcpyHostToDevice));
@@ -1399,18 +1521,25 @@ __global__ __launch_bounds__(NT) void gn_reg_kernel(const float *__restrict__ x,
 static int gn_fused(tts_ctx *ctx, const Layout &lay, const float *x, const float *g, const float *b, const float *ss, int do_silu,
                     __half *y, const void *wa = nullptr, size_t wa_bytes = 0, const void *wb = nullptr, size_t wb_bytes = 0) {
   ProfScope ps(ctx, "diff_gn_fused");
-  const int tmax = lay.max_len();
   // measured (round 3): one utterance 165.2 -> 156.6 ms per diffusion stage with the touch; the 16-candidate batch 864.8 -> 874.0 ms
   // (its GEMMs re-use every weight line from thousands of tiles: the touch only adds requests) -> small problems only
   if (lay.rows > 4096) { wa_bytes = 0; wb_bytes = 0; }
   const int silu_mode = ctx->ggml_lut ? 1 : ctx->attn_f32 ? 2 : 0; // see silu_dev
-#define GN_ARGS x, lay.d_start.as<int>(), lay.d_len.as<int>(), lay.rows, lay.ns, ctx->gn_eps, g, b, ss, do_silu, silu_mode, y, \
-                (const char *)wa, (int)(wa_bytes >> 7), (const char *)wb, (int)(wb_bytes >> 7), lay.seq_step_ptr(), lay.ss_step_stride
-  if (tmax <= 14 * 64) gn_reg_kernel<512, 14><<<dim3(32, lay.ns), 512, 0, ctx->stream>>>(GN_ARGS);
-  else if (tmax <= 18 * 128) gn_reg_kernel<1024, 18><<<dim3(32, lay.ns), 1024, 0, ctx->stream>>>(GN_ARGS);
-  else gn_fused_kernel<0><<<dim3(32, lay.ns), 256, 0, ctx->stream>>>(x, lay.d_start.as<int>(), lay.d_len.as<int>(), lay.rows, lay.ns, ctx->gn_eps, g, b, ss,
-                                                                    do_silu, silu_mode, y, lay.seq_step_ptr(), lay.ss_step_stride); // two sweeps over global memory
+  // one launch over the sequences [s0, s0 + ns) on rows [row0, row0 + rows): the whole layout, or one part of its GroupNorm partition (Layout::gn_parts)
+  auto launch = [&](const int *d_start, int s0, int ns, int row0, int rows, int tmax) {
+    const float *xp = x + (size_t)row0 * C;
+    __half *yp = y + (size_t)row0 * C;
+    const int *d_len = lay.d_len.as<int>() + s0, *step = lay.seq_step_ptr() ? lay.seq_step_ptr() + s0 : nullptr;
+#define GN_ARGS xp, d_start, d_len, rows, ns, ctx->gn_eps, g, b, ss, do_silu, silu_mode, yp, \
+                (const char *)wa, (int)(wa_bytes >> 7), (const char *)wb, (int)(wb_bytes >> 7), step, lay.ss_step_stride
+    if (tmax <= 14 * 64) gn_reg_kernel<512, 14><<<dim3(32, ns), 512, 0, ctx->stream>>>(GN_ARGS);
+    else if (tmax <= 18 * 128) gn_reg_kernel<1024, 18><<<dim3(32, ns), 1024, 0, ctx->stream>>>(GN_ARGS);
+    else gn_fused_kernel<0><<<dim3(32, ns), 256, 0, ctx->stream>>>(xp, d_start, d_len, rows, ns, ctx->gn_eps, g, b, ss,
+                                                                  do_silu, silu_mode, yp, step, lay.ss_step_stride); // two sweeps over global memory
 #undef GN_ARGS
+  };
+  if (lay.gn_parts.empty()) launch(lay.d_start.as<int>(), 0, lay.ns, 0, lay.rows, lay.max_len());
+  else for (const Layout::GnPart &p : lay.gn_parts) launch(lay.d_start_rel.as<int>() + p.s0, p.s0, p.ns, p.row0, p.rows, p.tmax);
   TTS_HIP(ctx, hipGetLastError());
   return TTS_OK;
 }
@@ -1806,36 +1935,25 @@ static int latent_conditioner(tts_ctx *ctx, DiffState *st, const float *latents_
   return TTS_OK;
 }
 
-// One network evaluation for every sequence of st->lay. Inputs: st->code_emb (f32 rows), st->xt16;
-// ss = this timestep's scale/shift block [n_res][2048]. Output: st->net [rows][256].
-static int network_forward(tts_ctx *ctx, DiffState *st, const float *ss) {
-  Layout &lay = st->lay;
-  Work &wk = st->wk;
-  Layout &il = st->share_integ ? st->ilay : st->lay; // layout of the integrator stage
-  Work &iw = st->share_integ ? st->iwk : st->wk;
-  float *ce = st->ce.as<float>();
-  if (st->n_integ == 0) TTS_HIP(ctx, hipMemcpyAsync(ce, st->code_emb.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  // option latency_mode: the statistics slots of this evaluation start empty (one memset node; every f32 GEMM of the step takes the next slot)
-  st->gn_site = 0;
-  iw.st_x = wk.st_x = iw.st_h = wk.st_h = nullptr;
-  if (st->lat) TTS_HIP(ctx, hipMemsetAsync(st->gn_stats.p, 0, (size_t)st->gn_sites_max * st->gn_slot_ll * 8, ctx->stream));
-  int j = 0;
-  __half *ce16 = st->ce16.as<__half>(), *inp16 = st->inp16.as<__half>();
-  if (st->hoisted) { // the integrator ran before the loop for every step (precompute_integrator): this step's slice
-    j = st->n_integ;
-    select_step_slice_kernel<<<256, 256, 0, ctx->stream>>>(st->ce16_all.as<uint4>(), (size_t)lay.rows * C / 8, st->step_ctr.as<int>(), (uint4 *)ce16);
-  } else {
-    for (int i = 0; i < st->n_integ; i++, j++) {
-      // first block: reads the code embedding directly, its timestep-independent half (st->h0) comes from setup_batch
-      if (i == 0) CHECK(res_block(ctx, st, il, iw, ce, st->integ_res[0], ss, st->code_emb.as<float>(), st->h0.as<float>(), st->lat ? st->gn_stats_h0.as<long long>() : nullptr));
-      else CHECK(res_block(ctx, st, il, iw, ce, st->integ_res[i], ss + (size_t)j * 2 * C));
-      CHECK(attention_block(ctx, st, il, iw, ce, st->integ_attn[i]));
-    }
-    if (st->share_integ) gather_f16_kernel<<<lay.rows, 256, 0, ctx->stream>>>(ce, st->ce_src.as<int>(), ce16);
-    else to_f16_kernel<<<lay.rows, 256, 0, ctx->stream>>>(ce, lay.d_row_seq.as<int>(), ce16);
+// The network is split at the integrator boundary so that the single call (network_forward) and the diffusion session (diff_session_enqueue_step) run the same two
+// halves, each on its own layout and buffers.
+// First half: the conditioning_timestep_integrator layers on layout il. code_emb / h0: the code embedding and in_layers of the first ResBlock applied to it (neither
+// depends on the timestep); result in ce (f32 rows of il). ss = block 0 of this evaluation's scale / shift blocks.
+static int network_integrator(tts_ctx *ctx, DiffState *st, Layout &il, Work &iw, float *ce, const float *code_emb, const float *h0, const float *ss) {
+  for (int i = 0; i < st->n_integ; i++) {
+    // first block: reads the code embedding directly, its timestep-independent half (h0) comes from setup_batch
+    if (i == 0) CHECK(res_block(ctx, st, il, iw, ce, st->integ_res[0], ss, code_emb, h0, st->lat ? st->gn_stats_h0.as<long long>() : nullptr));
+    else CHECK(res_block(ctx, st, il, iw, ce, st->integ_res[i], ss + (size_t)i * 2 * C));
+    CHECK(attention_block(ctx, st, il, iw, ce, st->integ_attn[i]));
   }
+  return TTS_OK;
+}
+// Second half: everything behind the integrator on layout lay. Inputs: ce16 (the integrator's output as an fp16 operand), xt16; ss as above (this half reads the
+// blocks from n_integ on). Output: net [rows][256].
+static int network_body(tts_ctx *ctx, DiffState *st, Layout &lay, Work &wk, const __half *ce16, const __half *xt16, __half *inp16, float *net, const float *ss) {
+  int j = st->n_integ;
   // inp_block: conv k3 100(->128) -> 1024 on x_t, output rounded to fp16 (operand of the next conv)
-  GemmArgs gi = gemm_base(lay, st->xt16.as<__half>() + XTC, XTC, 3, XTC, st->inp_w, C, st->inp_bias);
+  GemmArgs gi = gemm_base(lay, xt16 + XTC, XTC, 3, XTC, st->inp_w, C, st->inp_bias);
   gi.mode = GEMM_OUT_F16; gi.outH = inp16; gi.ldh = C;
   DBG_SUM("ce16", ce16, (size_t)lay.rows * C * 2);
   CHECK(gemm(ctx, "diff_gemm", gi, lay, 0, 300));
@@ -1855,10 +1973,35 @@ static int network_forward(tts_ctx *ctx, DiffState *st, const float *ss) {
   for (int i = 0; i < st->n_tail; i++, j++) CHECK(res_block(ctx, st, lay, wk, wk.X(), st->tail_res[i], ss + (size_t)j * 2 * C));
   CHECK(gn(ctx, st, lay, wk.X(), st->lat ? wk.st_x : nullptr, st->outn_g, st->outn_b, nullptr, 1, wk.A16()));
   GemmArgs go = gemm_base(lay, wk.A16(), C, 3, C, st->out_w, 256, st->out_bias);
-  go.mode = GEMM_OUT_F32; go.outF = st->net.as<float>(); go.ldo = 256; go.resid = nullptr;
+  go.mode = GEMM_OUT_F32; go.outF = net; go.ldo = 256; go.resid = nullptr;
   DBG_SUM("out gn", wk.A16(), (size_t)lay.rows * C * 2);
   CHECK(gemm(ctx, "diff_gemm", go, lay, 200, 0));
-  DBG_SUM("net", st->net.p, (size_t)lay.rows * 256 * 4);
+  DBG_SUM("net", net, (size_t)lay.rows * 256 * 4);
+  return TTS_OK;
+}
+
+// One network evaluation for every sequence of st->lay. Inputs: st->code_emb (f32 rows), st->xt16;
+// ss = this timestep's scale/shift block [n_res][2048]. Output: st->net [rows][256].
+static int network_forward(tts_ctx *ctx, DiffState *st, const float *ss) {
+  Layout &lay = st->lay;
+  Work &wk = st->wk;
+  Layout &il = st->share_integ ? st->ilay : st->lay; // layout of the integrator stage
+  Work &iw = st->share_integ ? st->iwk : st->wk;
+  float *ce = st->ce.as<float>();
+  if (st->n_integ == 0) TTS_HIP(ctx, hipMemcpyAsync(ce, st->code_emb.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  // option latency_mode: the statistics slots of this evaluation start empty (one memset node; every f32 GEMM of the step takes the next slot)
+  st->gn_site = 0;
+  iw.st_x = wk.st_x = iw.st_h = wk.st_h = nullptr;
+  if (st->lat) TTS_HIP(ctx, hipMemsetAsync(st->gn_stats.p, 0, (size_t)st->gn_sites_max * st->gn_slot_ll * 8, ctx->stream));
+  __half *ce16 = st->ce16.as<__half>();
+  if (st->hoisted) { // the integrator ran before the loop for every step (precompute_integrator): this step's slice
+    select_step_slice_kernel<<<256, 256, 0, ctx->stream>>>(st->ce16_all.as<uint4>(), (size_t)lay.rows * C / 8, st->step_ctr.as<int>(), (uint4 *)ce16);
+  } else {
+    CHECK(network_integrator(ctx, st, il, iw, ce, st->code_emb.as<float>(), st->h0.as<float>(), ss));
+    if (st->share_integ) gather_f16_kernel<<<lay.rows, 256, 0, ctx->stream>>>(ce, st->ce_src.as<int>(), ce16);
+    else to_f16_kernel<<<lay.rows, 256, 0, ctx->stream>>>(ce, lay.d_row_seq.as<int>(), ce16);
+  }
+  CHECK(network_body(ctx, st, lay, wk, ce16, st->xt16.as<__half>(), st->inp16.as<__half>(), st->net.as<float>(), ss));
   if (st->lat && st->gn_site > st->gn_sites_max) return fail(ctx, TTS_ERR_STATE, "latency_mode: %d statistics slots used, %d reserved", st->gn_site, st->gn_sites_max);
   return TTS_OK;
 }
@@ -2035,6 +2178,24 @@ int diff_forward(tts_ctx *ctx, const float *latents, int L, const float *x_t, in
   return TTS_OK;
 }
 
+// The per-step device tables of a sampling loop of n_steps (see StepEntry): entry idx belongs to respaced timestep n_steps - 1 - idx. has_noise: the steps read
+// host-provided noise blocks of `total` floats each (block 0 = x_T, block 1 + idx = step idx). One builder for tts_diffusion and for a session request.
+static void build_step_tables(const DiffSchedule &sched, int n_steps, bool ddim, bool has_noise, long long total, std::vector<StepEntry> &tab,
+                              std::vector<DdimEntry> &dtab) {
+  tab.assign(n_steps, StepEntry{});
+  dtab.assign(ddim ? n_steps : 0, DdimEntry{});
+  for (int idx = 0; idx < n_steps; idx++) {
+    const int t = n_steps - 1 - idx;
+    tab[idx].sc = StepScalars{sched.max_log[t], sched.min_log[t], sched.cfk[t], sched.sqrt_recip[t], sched.sqrt_recipm1[t],
+                              sched.coef1[t], sched.coef2[t], t == 0 ? 1 : 0};
+    tab[idx].has_noise = has_noise ? 1 : 0;
+    tab[idx].noise_off = (long long)(idx + 1) * total;
+    tab[idx].philox_step = (unsigned)idx;
+    tab[idx].pad = 0;
+    if (ddim) dtab[idx] = DdimEntry{sched.c_x0[t], sched.c_eps[t], sched.sigma[t], 0.f};
+  }
+}
+
 // tts_diffusion: the sampling loop for B candidates.
 int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, int n_steps, const float *noise, int noise_mode,
                 float *mel_out) {
@@ -2121,26 +2282,14 @@ int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, 
   const auto t_pre = now();
   const size_t ss_stride = (size_t)st->n_res() * 2 * C;
   // per-step table + device step counter (see StepEntry)
-  std::vector<StepEntry> tab(n_steps);
-  for (int idx = 0; idx < n_steps; idx++) {
-    const int t = n_steps - 1 - idx;
-    tab[idx].sc = StepScalars{sched.max_log[t], sched.min_log[t], sched.cfk[t], sched.sqrt_recip[t], sched.sqrt_recipm1[t],
-                              sched.coef1[t], sched.coef2[t], t == 0 ? 1 : 0};
-    tab[idx].has_noise = host_noise && n_vec > 1 ? 1 : 0;
-    tab[idx].noise_off = (long long)(idx + 1) * total;
-    tab[idx].philox_step = (unsigned)idx;
-    tab[idx].pad = 0;
-  }
+  std::vector<StepEntry> tab;
+  std::vector<DdimEntry> dtab;
+  build_step_tables(sched, n_steps, ddim, host_noise && n_vec > 1, total, tab, dtab);
   TTS_HIP(ctx, st->step_tab.reserve(tab.size() * sizeof(StepEntry)));
   TTS_HIP(ctx, st->step_ctr.reserve(64));
   TTS_HIP(ctx, st->ss_cur.reserve(ss_stride * 4));
   TTS_HIP(ctx, hipMemcpyAsync(st->step_tab.p, tab.data(), tab.size() * sizeof(StepEntry), hipMemcpyHostToDevice, ctx->stream));
-  std::vector<DdimEntry> dtab(ddim ? n_steps : 0);
   if (ddim) {
-    for (int idx = 0; idx < n_steps; idx++) {
-      const int t = n_steps - 1 - idx;
-      dtab[idx] = DdimEntry{sched.c_x0[t], sched.c_eps[t], sched.sigma[t], 0.f};
-    }
     TTS_HIP(ctx, st->ddim_tab.reserve(dtab.size() * sizeof(DdimEntry)));
     TTS_HIP(ctx, hipMemcpyAsync(st->ddim_tab.p, dtab.data(), dtab.size() * sizeof(DdimEntry), hipMemcpyHostToDevice, ctx->stream));
   }
@@ -2236,6 +2385,405 @@ int diff_sample_voices(tts_ctx *ctx, const float *latents, const int32_t *rows, 
   st->mv_tab = st->mv_buf.as<float>();
   st->mv_idx = (const int *)(st->mv_buf.as<float>() + nf);
   return diff_sample(ctx, latents, rows, B, n_steps, noise, noise_mode, mel_out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// diffusion session (tts_diff_session_*): in-flight batching for the sampling loop
+// ------------------------------------------------------------------------------------------------
+// A request's share of the session. Everything below was evaluated at admission for the request ALONE by the functions tts_diffusion runs (setup_batch,
+// precompute_time, precompute_integrator) and then moved or copied out of the single call's run state: a step of the joint layout only gathers from it.
+struct DiffSessReq {
+  int id = 0, slot = 0, n_cand = 0, n_steps = 0, sampler = 0, done = 0, cls = 0, packed = 0;
+  bool finished = false;
+  uint64_t seed = 0;
+  std::vector<int> T;        // frames per candidate
+  std::vector<int> seq_src;  // per sequence of the request (conditioned 0 .. n_cand - 1, then their unconditioned copies): its first row in the request's row buffers
+  int src_rows = 0;          // rows of those buffers (the request's own packed layout; its integrator layout without hoisting)
+  std::vector<int64_t> xoff; // candidate c's x in `x`
+  int64_t total = 0;
+  DevBuf ce16_all;           // hoisted: [n_steps][src_rows][1024] fp16
+  DevBuf code_emb, h0;       // not hoisted: [src_rows][1024] f32 each
+  DevBuf ss_all, tab, dtab, x, noise;
+};
+// the session's pinned options for the length of one session call: every option the diffusion stage reads between an admission's setup and a step's last kernel
+struct PinnedOptions {
+  float gn_eps;
+  int ggml_lut, attn_f32, attn_proj_f16, proj_dual_b, gemm_wreg, attn_f32_drop, lc_attn_f32, attn_q64, fp16_check, hoist_integrator, diff_graph, latency_mode;
+  bool share_uncond;
+  static PinnedOptions of(const tts_ctx *c) {
+    return PinnedOptions{c->gn_eps, c->ggml_lut, c->attn_f32, c->attn_proj_f16, c->proj_dual_b, c->gemm_wreg, c->attn_f32_drop, c->lc_attn_f32, c->attn_q64,
+                         c->fp16_check, c->hoist_integrator, c->diff_graph, c->latency_mode, c->share_uncond};
+  }
+  void put(tts_ctx *c) const {
+    c->gn_eps = gn_eps; c->ggml_lut = ggml_lut; c->attn_f32 = attn_f32; c->attn_proj_f16 = attn_proj_f16; c->proj_dual_b = proj_dual_b; c->gemm_wreg = gemm_wreg;
+    c->attn_f32_drop = attn_f32_drop; c->lc_attn_f32 = lc_attn_f32; c->attn_q64 = attn_q64; c->fp16_check = fp16_check; c->hoist_integrator = hoist_integrator;
+    c->diff_graph = diff_graph; c->latency_mode = latency_mode; c->share_uncond = share_uncond;
+  }
+};
+struct DiffSession {
+  int max_rows = 0, max_req = 0, buf_rows = 0;
+  PinnedOptions pinned{};
+  // the options read at tts_diff_session_open: every session call runs under them (SessOptions), whatever tts_set_option has stored since
+  int attn_f32 = 0, hoist = 0, graph = 0, sampler = 0;
+  bool share_uncond = true, hoisted = false;
+  double eta = 0;
+  float k = 2.0f;
+  std::map<int, std::unique_ptr<DiffSessReq>> reqs; // by id: the order of admission
+  std::vector<char> slot_busy;
+  int next_id = 0, captures = 0, n_live = 0;
+  bool dirty = true; // the membership changed since the layout was built
+  Layout lay;
+  Work wk;
+  DevBuf code_emb, h0, ce, ce16, inp16, xt16, net, ss_cur, ctr, req_tab, seq_req, seq_partner, seq_cand, seq_xoff, row_src, live;
+  hipGraph_t step_graph = nullptr;
+  hipGraphExec_t step_exec = nullptr;
+  void drop_step_graph() {
+    if (step_exec) (void)hipGraphExecDestroy(step_exec);
+    if (step_graph) (void)hipGraphDestroy(step_graph);
+    step_exec = nullptr; step_graph = nullptr;
+  }
+  ~DiffSession() { drop_step_graph(); }
+};
+namespace {
+struct SessOptions {
+  tts_ctx *c;
+  PinnedOptions saved;
+  SessOptions(tts_ctx *ctx, const DiffSession &s) : c(ctx), saved(PinnedOptions::of(ctx)) { s.pinned.put(ctx); }
+  ~SessOptions() { saved.put(c); }
+};
+void take(DevBuf &dst, DevBuf &src) { std::swap(dst.p, src.p); std::swap(dst.cap, src.cap); }
+} // namespace
+
+void diff_session_close(tts_ctx *ctx) {
+  if (!ctx->diff_session) return;
+  (void)hipStreamSynchronize(ctx->stream);
+  delete ctx->diff_session;
+  ctx->diff_session = nullptr;
+}
+int diff_session_captures(const tts_ctx *ctx) { return ctx->diff_session->captures; }
+void diff_session_defaults(const tts_ctx *ctx, tts_diff_request *req) {
+  const DiffSession &S = *ctx->diff_session;
+  req->sampler = S.sampler; req->ddim_eta = S.eta; req->cond_free_k = S.k;
+}
+int diff_session_room(const tts_ctx *ctx) {
+  const DiffSession &S = *ctx->diff_session;
+  int used = 0;
+  for (auto &kv : S.reqs) if (!kv.second->finished) used += kv.second->packed;
+  return std::max(0, S.max_rows - used);
+}
+
+int diff_session_open(tts_ctx *ctx, int max_packed_rows, int max_requests) {
+  DiffState *st = ctx->diff;
+  if (!st) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
+  diff_session_close(ctx);
+  std::unique_ptr<DiffSession> s(new DiffSession());
+  s->max_rows = max_packed_rows; s->max_req = max_requests; s->buf_rows = (max_packed_rows + 127) & ~127;
+  s->attn_f32 = ctx->attn_f32; s->share_uncond = ctx->share_uncond; s->hoist = ctx->hoist_integrator; s->graph = ctx->diff_graph;
+  s->pinned = PinnedOptions::of(ctx);
+  s->pinned.latency_mode = 0; // the batch path's GroupNorm, always
+  s->sampler = ctx->diff_sampler; s->eta = ctx->ddim_eta; s->k = ctx->cond_free_k;
+  // Every request of a session takes the same route through the integrator (one step graph serves them all): hoisted whenever the option is on (the two routes
+  // give the same bits). The single call's row threshold (HOIST_MAX_ROWS, or the option's value above 1) becomes the most a request of such a session may take:
+  // diff_session_admit refuses a larger one before any device work.
+  s->hoisted = s->hoist != 0 && st->n_integ > 0;
+  s->slot_busy.assign((size_t)max_requests, 0);
+  // all the step's buffers now, for the largest layout the session can hold: no admission reallocates what a captured step graph has baked in
+  const size_t R = (size_t)s->buf_rows;
+  CHECK(s->wk.reserve(ctx, (int)R, (int)R / 8));
+  auto rz = [&](DevBuf &b, size_t bytes) -> hipError_t {
+    hipError_t e = b.reserve(bytes);
+    return e == hipSuccess ? hipMemset(b.p, 0, b.cap) : e;
+  };
+  TTS_HIP(ctx, rz(s->ce16, R * C * 2));
+  TTS_HIP(ctx, rz(s->inp16, R * C * 2));
+  TTS_HIP(ctx, rz(s->xt16, (R + 2) * XTC * 2));
+  TTS_HIP(ctx, rz(s->net, R * 256 * 4));
+  if (!s->hoisted) {
+    TTS_HIP(ctx, rz(s->code_emb, R * C * 4));
+    TTS_HIP(ctx, rz(s->h0, R * C * 4));
+    TTS_HIP(ctx, rz(s->ce, R * C * 4));
+  }
+  TTS_HIP(ctx, rz(s->ss_cur, (size_t)max_requests * st->n_res() * 2 * C * 4));
+  TTS_HIP(ctx, rz(s->ctr, (size_t)max_requests * 4));
+  TTS_HIP(ctx, rz(s->req_tab, (size_t)max_requests * sizeof(SessReqDev)));
+  TTS_HIP(ctx, rz(s->live, (size_t)max_requests * 4));
+  ctx->diff_session = s.release();
+  return TTS_OK;
+}
+
+// Admission: the request alone through setup_batch / precompute_time / precompute_integrator — the single call's run state, which no step of the session reads —
+// and the results into storage the request owns. Nothing the captured step graph has baked in is written: the request joins the layout at the next step.
+int diff_session_admit(tts_ctx *ctx, const tts_diff_request *rq) {
+  DiffSession &S = *ctx->diff_session;
+  DiffState *st = ctx->diff;
+  int slot = -1;
+  for (int i = 0; i < S.max_req && slot < 0; i++) if (!S.slot_busy[i]) slot = i;
+  if (slot < 0) return fail(ctx, TTS_ERR_LIMIT, "tts_diff_session_admit: the session holds %d requests", S.max_req);
+  const int B = rq->n_cand, n_steps = rq->n_steps;
+  if (S.hoisted) { // a hoisted request owns n_steps x packed rows x 2 KB until it is collected: the single call's row cap bounds it, request by request
+    const int cap = S.hoist > 1 ? S.hoist : HOIST_MAX_ROWS, packed = tts_host_diff_packed_rows(rq->rows, B);
+    if (packed > cap)
+      return fail(ctx, TTS_ERR_LIMIT, "tts_diff_session_admit: the request takes %d packed rows; a session opened with hoist_integrator on admits at most %d per request "
+                  "(open the session with hoist_integrator 0 for larger ones)", packed, cap);
+  }
+  SessOptions opts(ctx, S);
+  std::vector<int> L(rq->rows, rq->rows + B);
+  std::unique_ptr<DiffSessReq> r(new DiffSessReq());
+  r->slot = slot; r->n_cand = B; r->n_steps = n_steps; r->sampler = rq->sampler; r->seed = rq->seed;
+  struct Reset { DiffState *s; ~Reset() { s->mv_tab = nullptr; s->mv_idx = nullptr; } } reset{st};
+  if (rq->voice_latent2048) { // the request's voice as a one-row table, every candidate on row 0 (see diff_sample_voices)
+    const size_t nf = (size_t)2 * C;
+    std::vector<float> up(nf + (size_t)B, 0.f); // (an all-zero float is the int 0)
+    memcpy(up.data(), rq->voice_latent2048, nf * 4);
+    TTS_HIP(ctx, st->mv_buf.reserve(up.size() * 4));
+    TTS_HIP(ctx, hipMemcpy(st->mv_buf.p, up.data(), up.size() * 4, hipMemcpyHostToDevice));
+    st->mv_tab = st->mv_buf.as<float>();
+    st->mv_idx = (const int *)(st->mv_buf.as<float>() + nf);
+  }
+  CHECK(setup_batch(ctx, st, rq->latents, L, true, true));
+  Layout &lay = st->lay;
+  r->packed = lay.rows;
+  r->cls = Layout::gn_class(lay.max_len());
+  const bool ddim = rq->sampler == 1;
+  const int n_vec = ddim && rq->ddim_eta == 0 ? 1 : n_steps + 1;
+  DiffSchedule sched;
+  sched.base_k = (float)rq->cond_free_k;
+  sched.build(n_steps);
+  if (ddim) sched.build_ddim(rq->ddim_eta);
+  std::vector<int> ts(n_steps);
+  for (int idx = 0; idx < n_steps; idx++) ts[idx] = sched.timestep_map[n_steps - 1 - idx];
+  CHECK(precompute_time(ctx, st, ts));
+  st->hoisted = S.hoisted;
+  if (S.hoisted) CHECK(precompute_integrator(ctx, st, n_steps));
+  // the row buffers: where each of the request's sequences starts in them
+  const Layout &il = st->share_integ ? st->ilay : st->lay;
+  r->T.assign(lay.len.begin(), lay.len.begin() + B);
+  r->seq_src.resize((size_t)2 * B);
+  if (S.hoisted) {
+    r->src_rows = lay.rows;
+    for (int s = 0; s < 2 * B; s++) r->seq_src[s] = lay.start[s];
+    take(r->ce16_all, st->ce16_all);
+  } else {
+    r->src_rows = il.rows;
+    for (int s = 0; s < 2 * B; s++) r->seq_src[s] = st->share_integ ? st->ce_src_host[lay.start[s]] : lay.start[s];
+    TTS_HIP(ctx, r->code_emb.reserve((size_t)il.rows * C * 4));
+    TTS_HIP(ctx, hipMemcpyAsync(r->code_emb.p, st->code_emb.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if (st->n_integ > 0) {
+      TTS_HIP(ctx, r->h0.reserve((size_t)il.rows * C * 4));
+      TTS_HIP(ctx, hipMemcpyAsync(r->h0.p, st->h0.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+  }
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  take(r->ss_all, st->ss_all);
+  // x and the noise, request-local in tts_diffusion's arrangement: [cand][100][T_c]; block 0 = x_T, block 1 + idx = step idx
+  r->xoff.resize(B);
+  for (int c = 0; c < B; c++) { r->xoff[c] = r->total; r->total += (int64_t)100 * lay.len[c]; }
+  const int64_t total = r->total;
+  TTS_HIP(ctx, r->x.reserve(total * 4));
+  if (rq->noise) {
+    std::vector<float> hn((size_t)total * n_vec);
+    size_t src = 0;
+    for (int c = 0; c < B; c++)
+      for (int k = 0; k < n_vec; k++) {
+        memcpy(hn.data() + (size_t)k * total + r->xoff[c], rq->noise + src, (size_t)100 * lay.len[c] * 4);
+        src += (size_t)100 * lay.len[c];
+      }
+    TTS_HIP(ctx, r->noise.reserve(hn.size() * 4));
+    TTS_HIP(ctx, hipMemcpy(r->noise.p, hn.data(), hn.size() * 4, hipMemcpyHostToDevice));
+    TTS_HIP(ctx, hipMemcpyAsync(r->x.p, r->noise.p, total * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  } else {
+    for (int c = 0; c < B; c++) {
+      const int64_t n = (int64_t)100 * lay.len[c];
+      philox_fill_kernel<<<(int)((n + 255) / 256), 256, 0, ctx->stream>>>(r->x.as<float>() + r->xoff[c], n, r->seed, (uint32_t)c, 0xFFFFFFFFu);
+    }
+    TTS_HIP(ctx, hipGetLastError());
+  }
+  std::vector<StepEntry> tab;
+  std::vector<DdimEntry> dtab;
+  build_step_tables(sched, n_steps, ddim, rq->noise != nullptr && n_vec > 1, total, tab, dtab);
+  TTS_HIP(ctx, r->tab.reserve(tab.size() * sizeof(StepEntry)));
+  TTS_HIP(ctx, hipMemcpy(r->tab.p, tab.data(), tab.size() * sizeof(StepEntry), hipMemcpyHostToDevice));
+  if (ddim) {
+    TTS_HIP(ctx, r->dtab.reserve(dtab.size() * sizeof(DdimEntry)));
+    TTS_HIP(ctx, hipMemcpy(r->dtab.p, dtab.data(), dtab.size() * sizeof(DdimEntry), hipMemcpyHostToDevice));
+  }
+  TTS_HIP(ctx, hipMemsetAsync(S.ctr.as<int>() + slot, 0, 4, ctx->stream)); // the slot of no sequence of the layout a captured graph holds
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  r->id = S.next_id++;
+  S.slot_busy[slot] = 1;
+  S.dirty = true;
+  const int id = r->id;
+  S.reqs[id] = std::move(r);
+  return id;
+}
+
+// The joint layout of the running requests and the tables the step's kernels read. Requests in the order of admission, grouped by GroupNorm class
+// (Layout::gn_parts); a request's conditioned sequences, then their unconditioned copies.
+static int diff_session_rebuild(tts_ctx *ctx, DiffSession &S) {
+  DiffState *st = ctx->diff;
+  std::vector<DiffSessReq *> live;
+  for (auto &kv : S.reqs) if (!kv.second->finished) live.push_back(kv.second.get());
+  std::stable_sort(live.begin(), live.end(), [](const DiffSessReq *a, const DiffSessReq *b) { return a->cls < b->cls; });
+  std::vector<int> lens, seq_req, seq_cand, cls, seq_local;
+  std::vector<int64_t> xoff;
+  std::vector<DiffSessReq *> owner;
+  for (DiffSessReq *r : live)
+    for (int ls = 0; ls < 2 * r->n_cand; ls++) {
+      const int c = ls % r->n_cand;
+      lens.push_back(r->T[c]); seq_req.push_back(r->slot); seq_cand.push_back(c); cls.push_back(r->cls); seq_local.push_back(ls);
+      xoff.push_back(r->xoff[c]); owner.push_back(r);
+    }
+  Layout &lay = S.lay;
+  CHECK(lay.build(ctx, lens));
+  if (lay.rows > S.buf_rows) return fail(ctx, TTS_ERR_STATE, "diffusion session: a layout of %d rows in buffers of %d", lay.rows, S.buf_rows);
+  const size_t ss_stride = (size_t)st->n_res() * 2 * C;
+  CHECK(lay.set_seq_step(ctx, seq_req, (int)ss_stride)); // block of ss_cur = the request's slot (diff_session_begin_kernel writes the same)
+  CHECK(lay.set_gn_parts(ctx, cls));
+  const int ns = lay.ns;
+  std::vector<int> partner(ns, -1), row_src(lay.rows, -1);
+  for (int s = 0; s < ns; s++) {
+    const DiffSessReq *r = owner[s];
+    if (seq_local[s] < r->n_cand) partner[s] = lay.start[s + r->n_cand]; // the request's sequences are consecutive
+    for (int t = 0; t < lens[s]; t++) row_src[lay.start[s] + t] = r->seq_src[seq_local[s]] + t;
+  }
+  std::vector<SessReqDev> tab((size_t)S.max_req, SessReqDev{});
+  std::vector<int> slots;
+  for (DiffSessReq *r : live) {
+    SessReqDev &d = tab[r->slot];
+    d.ss_all = r->ss_all.as<float>(); d.tab = r->tab.as<StepEntry>(); d.dtab = r->dtab.as<DdimEntry>(); d.ce16_all = r->ce16_all.as<__half>();
+    d.x = r->x.as<float>(); d.noise = r->noise.as<float>(); d.seed = r->seed; d.n_steps = r->n_steps; d.sampler = r->sampler; d.rows_local = r->src_rows;
+    slots.push_back(r->slot);
+  }
+  auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
+    hipError_t e = b.reserve(bytes);
+    return e == hipSuccess ? hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) : e;
+  };
+  TTS_HIP(ctx, up(S.seq_req, seq_req.data(), (size_t)ns * 4));
+  TTS_HIP(ctx, up(S.seq_partner, partner.data(), (size_t)ns * 4));
+  TTS_HIP(ctx, up(S.seq_cand, seq_cand.data(), (size_t)ns * 4));
+  TTS_HIP(ctx, up(S.seq_xoff, xoff.data(), (size_t)ns * 8));
+  TTS_HIP(ctx, up(S.row_src, row_src.data(), (size_t)lay.rows * 4));
+  TTS_HIP(ctx, up(S.req_tab, tab.data(), tab.size() * sizeof(SessReqDev)));
+  TTS_HIP(ctx, up(S.live, slots.data(), slots.size() * 4));
+  S.n_live = (int)slots.size();
+  // rows that belonged to a sequence of the previous layout may be guard rows now: the operand the k = 3 taps read across sequence ends starts from zero
+  TTS_HIP(ctx, hipMemsetAsync(S.xt16.p, 0, S.xt16.cap, ctx->stream));
+  if (!S.hoisted) { // the integrator runs inside the step: its two timestep-independent inputs, sequence by sequence from the requests' buffers
+    TTS_HIP(ctx, hipMemsetAsync(S.code_emb.p, 0, (size_t)lay.rows * C * 4, ctx->stream));
+    TTS_HIP(ctx, hipMemsetAsync(S.h0.p, 0, (size_t)lay.rows * C * 4, ctx->stream));
+    for (int s = 0; s < ns; s++) {
+      const DiffSessReq *r = owner[s];
+      const size_t dst = (size_t)lay.start[s] * C, src = (size_t)r->seq_src[seq_local[s]] * C, n = (size_t)lens[s] * C * 4;
+      TTS_HIP(ctx, hipMemcpyAsync(S.code_emb.as<float>() + dst, r->code_emb.as<float>() + src, n, hipMemcpyDeviceToDevice, ctx->stream));
+      if (st->n_integ > 0) TTS_HIP(ctx, hipMemcpyAsync(S.h0.as<float>() + dst, r->h0.as<float>() + src, n, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+  }
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return TTS_OK;
+}
+
+// One step of the joint layout: the single call's step with its four per-batch pieces replaced by their per-sequence forms (see the diff_session_* kernels); the
+// network between them is network_integrator / network_body, the halves network_forward runs.
+static int diff_session_enqueue_step(tts_ctx *ctx, DiffSession &S) {
+  DiffState *st = ctx->diff;
+  Layout &lay = S.lay;
+  const size_t ss_stride = (size_t)st->n_res() * 2 * C;
+  const SessReqDev *req = S.req_tab.as<SessReqDev>();
+  const int *ctr = S.ctr.as<int>(), *seq_req = S.seq_req.as<int>(), *partner = S.seq_partner.as<int>();
+  float *ss = S.ss_cur.as<float>();
+  diff_session_begin_kernel<<<dim3(16, S.n_live), 256, 0, ctx->stream>>>(req, ctr, S.live.as<int>(), ss_stride, ss, seq_req, lay.ns, lay.d_seq_step.as<int>());
+  diff_session_xt_kernel<<<lay.rows, 128, 0, ctx->stream>>>(req, seq_req, S.seq_xoff.as<int64_t>(), partner, lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(),
+                                                           lay.d_len.as<int>(), S.xt16.as<__half>() + XTC);
+  st->gn_site = 0;
+  S.wk.st_x = S.wk.st_h = nullptr;
+  __half *ce16 = S.ce16.as<__half>();
+  if (S.hoisted) {
+    diff_session_row_select_kernel<<<lay.rows, 128, 0, ctx->stream>>>(req, ctr, seq_req, lay.d_row_seq.as<int>(), S.row_src.as<int>(), (uint4 *)ce16);
+  } else {
+    float *ce = S.ce.as<float>();
+    if (st->n_integ == 0) TTS_HIP(ctx, hipMemcpyAsync(ce, S.code_emb.p, (size_t)lay.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    CHECK(network_integrator(ctx, st, lay, S.wk, ce, S.code_emb.as<float>(), S.h0.as<float>(), ss));
+    to_f16_kernel<<<lay.rows, 256, 0, ctx->stream>>>(ce, lay.d_row_seq.as<int>(), ce16);
+  }
+  CHECK(network_body(ctx, st, lay, S.wk, ce16, S.xt16.as<__half>(), S.inp16.as<__half>(), S.net.as<float>(), ss));
+  {
+    ProfScope ps(ctx, "diff_update");
+    diff_session_update_kernel<<<lay.rows, 128, 0, ctx->stream>>>(S.net.as<float>(), req, ctr, seq_req, S.seq_xoff.as<int64_t>(), partner, S.seq_cand.as<int>(),
+                                                                 lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(), lay.d_len.as<int>());
+  }
+  diff_session_advance_kernel<<<(S.n_live + 63) / 64, 64, 0, ctx->stream>>>(req, S.ctr.as<int>(), S.live.as<int>(), S.n_live);
+  TTS_HIP(ctx, hipGetLastError());
+  return TTS_OK;
+}
+
+int diff_session_step(tts_ctx *ctx) {
+  DiffSession &S = *ctx->diff_session;
+  DiffState *st = ctx->diff;
+  int running = 0;
+  for (auto &kv : S.reqs) running += kv.second->finished ? 0 : 1;
+  if (running == 0) return 0;
+  SessOptions opts(ctx, S);
+  st->lat = false; // the batch path's GroupNorm, always
+  static const bool no_graph_env = getenv("TTS_NO_GRAPH") != nullptr;
+  if (S.dirty) { // admits, finishes and cancels since the last step: one rebuild, one capture
+    S.drop_step_graph();
+    CHECK(diff_session_rebuild(ctx, S));
+    if (S.graph && !no_graph_env) {
+      ctx->capturing = true;
+      hipError_t eb = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
+      int rc = eb == hipSuccess ? diff_session_enqueue_step(ctx, S) : TTS_OK;
+      hipError_t ee = eb == hipSuccess ? hipStreamEndCapture(ctx->stream, &S.step_graph) : eb;
+      ctx->capturing = false;
+      if (rc) return rc;
+      TTS_HIP(ctx, ee);
+      TTS_HIP(ctx, hipGraphInstantiate(&S.step_exec, S.step_graph, nullptr, nullptr, 0));
+      S.captures++;
+    }
+    S.dirty = false;
+  }
+  if (S.step_exec) TTS_HIP(ctx, hipGraphLaunch(S.step_exec, ctx->stream));
+  else CHECK(diff_session_enqueue_step(ctx, S));
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // the host's own count: step counts are fixed, no device read detects a finish
+  running = 0;
+  for (auto &kv : S.reqs) {
+    DiffSessReq &r = *kv.second;
+    if (r.finished) continue;
+    if (++r.done >= r.n_steps) { r.finished = true; S.dirty = true; }
+    else running++;
+  }
+  return running;
+}
+
+int diff_session_finished(tts_ctx *ctx, int32_t *ids, int cap) {
+  int n = 0;
+  for (auto &kv : ctx->diff_session->reqs)
+    if (kv.second->finished) { if (ids && n < cap) ids[n] = kv.first; n++; }
+  return n;
+}
+
+static void diff_session_release(DiffSession &S, int request) {
+  auto it = S.reqs.find(request);
+  if (!it->second->finished) S.dirty = true; // a running request leaves the layout at the next step; until then no step runs, so nothing reads its buffers
+  S.slot_busy[it->second->slot] = 0;
+  S.reqs.erase(it);
+}
+int diff_session_collect(tts_ctx *ctx, int request, float *mel_out) {
+  DiffSession &S = *ctx->diff_session;
+  auto it = S.reqs.find(request);
+  if (it == S.reqs.end()) return fail(ctx, TTS_ERR_ARG, "tts_diff_session_collect: no request %d", request);
+  if (!it->second->finished) return fail(ctx, TTS_ERR_STATE, "tts_diff_session_collect: request %d is still running (%d of %d steps)", request, it->second->done, it->second->n_steps);
+  TTS_HIP(ctx, hipMemcpyAsync(mel_out, it->second->x.p, it->second->total * 4, hipMemcpyDeviceToHost, ctx->stream));
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  diff_session_release(S, request);
+  return TTS_OK;
+}
+int diff_session_cancel(tts_ctx *ctx, int request) {
+  DiffSession &S = *ctx->diff_session;
+  if (S.reqs.find(request) == S.reqs.end()) return fail(ctx, TTS_ERR_ARG, "tts_diff_session_cancel: no request %d", request);
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  diff_session_release(S, request);
+  return TTS_OK;
 }
 
 } // namespace tts

@@ -1180,3 +1180,67 @@ extern "C" int tts_write_wav(const char *path, const float *samples, int64_t n, 
   fclose(f);
   return TTS_OK;
 }
+
+// mel frames of a latent of L rows (pure host arithmetic; here so that the session's row probe below has it in every library this file is built into)
+extern "C" int tts_diffusion_frames(int L) { return L * 4 * 24000 / 22050; }
+
+// ---- diffusion session: the checks and probes that need no device (tts_diff_session_*) ----
+namespace tts {
+const char *diff_control_error(int which, double value) {
+  switch (which) {
+  case 0: return (value != 0 && value != 1) ? "diff_sampler: 0 (ancestral DDPM) or 1 (DDIM)" : nullptr;
+  case 1: return !(value >= 0 && value <= 1) ? "ddim_eta: a value in [0, 1]" : nullptr;
+  case 2: return (!std::isfinite(value) || value < 0 || !std::isfinite((float)value)) ? "cond_free_k: a finite value >= 0" : nullptr;
+  }
+  return "unknown diffusion control";
+}
+int diff_packed_rows(const int *frames, int n) {
+  long long r = 8;
+  for (int s = 0; s < n; s++) r = (r + frames[s] + 1 + 7) & ~7LL;
+  return (int)((r + 127) & ~127LL);
+}
+int diff_request_check(const tts_diff_request *req, int max_packed_rows, std::string &why) {
+  char buf[200];
+  if (!req) { why = "null request"; return TTS_ERR_ARG; }
+  if (req->struct_size < sizeof(tts_diff_request)) {
+    snprintf(buf, sizeof buf, "struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_diff_request))", req->struct_size, sizeof(tts_diff_request));
+    why = buf;
+    return TTS_ERR_ARG;
+  }
+  if (req->n_cand < 1) { snprintf(buf, sizeof buf, "bad argument (%d candidates)", req->n_cand); why = buf; return TTS_ERR_ARG; }
+  if (!req->latents || !req->rows) { why = "null latents or rows"; return TTS_ERR_ARG; }
+  if (req->n_cand > 4096) { snprintf(buf, sizeof buf, "%d candidates, at most 4096", req->n_cand); why = buf; return TTS_ERR_LIMIT; }
+  size_t n_lat = 0;
+  for (int c = 0; c < req->n_cand; c++) {
+    if (req->rows[c] < 1 || req->rows[c] > 500) { snprintf(buf, sizeof buf, "latent rows %d out of range (1 .. 500)", req->rows[c]); why = buf; return TTS_ERR_ARG; }
+    n_lat += (size_t)req->rows[c] * TTS_DMODEL;
+  }
+  if (req->n_steps < 2) { snprintf(buf, sizeof buf, "n_steps %d: at least 2", req->n_steps); why = buf; return TTS_ERR_ARG; }
+  const double v[3] = {(double)req->sampler, req->ddim_eta, req->cond_free_k};
+  for (int k = 0; k < 3; k++)
+    if (const char *e = diff_control_error(k, v[k])) { why = e; return TTS_ERR_ARG; }
+  for (size_t i = 0; i < n_lat; i++)
+    if (!std::isfinite(req->latents[i])) { why = "a latent holds a non-finite value"; return TTS_ERR_ARG; }
+  if (req->voice_latent2048)
+    for (int i = 0; i < 2 * TTS_DMODEL; i++)
+      if (!std::isfinite(req->voice_latent2048[i])) { why = "the voice latent holds a non-finite value"; return TTS_ERR_ARG; }
+  const int need = tts_host_diff_packed_rows(req->rows, req->n_cand);
+  if (need > max_packed_rows) { snprintf(buf, sizeof buf, "the request takes %d packed rows, %d are free", need, max_packed_rows); why = buf; return TTS_ERR_LIMIT; }
+  return TTS_OK;
+}
+} // namespace tts
+extern "C" int tts_host_diff_packed_rows(const int32_t *latent_rows, int n_cand) {
+  if (!latent_rows || n_cand < 1 || n_cand > 4096) return TTS_ERR_ARG;
+  std::vector<int> frames;
+  for (int pass = 0; pass < 2; pass++) // the conditioned sequences, then their unconditioned copies
+    for (int c = 0; c < n_cand; c++) {
+      if (latent_rows[c] < 1 || latent_rows[c] > 500) return TTS_ERR_ARG;
+      frames.push_back(tts_diffusion_frames(latent_rows[c]));
+    }
+  return tts::diff_packed_rows(frames.data(), (int)frames.size());
+}
+extern "C" int tts_host_diff_request_check(const tts_diff_request *req, int max_packed_rows) {
+  if (max_packed_rows < 1) return TTS_ERR_ARG;
+  std::string why;
+  return tts::diff_request_check(req, max_packed_rows, why);
+}
