@@ -8,197 +8,7 @@
 #include <fstream>
 #include <new>
 
-namespace tts {
-int ar_begin(tts_ctx *, const int32_t *, int, const float *, int, int);
-int ar_begin_groups(tts_ctx *, const int32_t *, const int *, int, const float *, int n_voices, const int *voice_of, const int *, int);
-int ar_latents_group(tts_ctx *, int, const int32_t *, int, float *);
-int ar_stream_reserve(tts_ctx *, int n_mel);
-int ar_graph_captures(const tts_ctx *);
-int ar_session_open(tts_ctx *, int n_slots, int max_cand, int max_text, int max_steps, bool rows);
-int ar_session_controls(tts_ctx *, int c0, int n);
-void ar_session_close(tts_ctx *);
-int ar_session_prompt(tts_ctx *, int c0, int n_cand, const int32_t *text_ids, int n_text, const float *voice, float *logits_row);
-int ar_session_step(tts_ctx *, const int32_t *toks, const int32_t *n_past, const int32_t *pos_id, const char *live, int mode);
-int ar_session_recaptures(const tts_ctx *);
-int ar_session_latents(tts_ctx *, int c0, int n_text, const int32_t *codes502, int nb, int n_mel, float *out);
-int ar_session_logits(tts_ctx *, int c0, int n, float *out);
-int ar_session_audio_enable(tts_ctx *, int max_steps);
-int ar_session_audio_prompt(tts_ctx *, int c0, int n_text);
-int ar_session_extend(tts_ctx *, const ArExtendItem *items, int n_items, float *out);
-int ar_prefill(tts_ctx *, float *);
-int ar_step(tts_ctx *, const int32_t *, int, float *, int mode);
-const int32_t *ar_host_lists(tts_ctx *);
-const float *ar_fetch_logits_row(tts_ctx *, int);
-void ar_history_ids(const tts_ctx *, int c, std::vector<int32_t> &out);
-int ar_batch(const tts_ctx *);
-int ar_latents(tts_ctx *, const int32_t *, int, int, float *);
-int ar_layers(const tts_ctx *);
-float *ar_host_logits(tts_ctx *);
-int diff_layers(const tts_ctx *);
-int diff_forward(tts_ctx *, const float *, int, const float *, int, int, float *);
-int diff_sample(tts_ctx *, const float *, const int32_t *, int, int, const float *, int, float *);
-int diff_sample_voices(tts_ctx *, const float *, const int32_t *, int, const float *, int, const int32_t *, int, const float *, int, float *);
-int voc_run(tts_ctx *, const float *, const int32_t *, int, const float *, int, float *);
-} // namespace tts
-
-// The book of an open session (tts_ar_session_*): which slots are taken, and per request what tts_autoregressive keeps in its locals for one call.
-namespace tts {
-struct SessionRequest {
-  int id = 0, c0 = 0, n_cand = 0, n_text = 0;
-  std::mt19937 gen;              // seeded at admission: tts_autoregressive's stream after tts_seed(seed)
-  ArStopBook book;               // one group
-  std::vector<int32_t> stop_at;  // the request's stop schedule (empty: none)
-  std::vector<int32_t> samples;  // the tokens the next step feeds (after ArStopBook::step)
-  int i = 0;                     // tts_autoregressive's loop counter: iterations applied so far
-  // the request's own sampler controls and step limit (tts_ar_session_admit_ex; tts_ar_session_admit: the session's)
-  SamplerParams sp;
-  int scope = 0, max_steps = 0;
-  int state = 0;                 // 0 running, 1 finished, 2 finished by reaching max_steps in strict mode (collect returns TTS_ERR_LIMIT)
-  // Audio (a one-candidate request of a session with tts_ar_session_enable_audio): tts_hifigan_stream's book, HfgStream, per request.
-  bool audio = false, audio_done = false; // audio_done: the request has finished and its last frames are in pcm
-  int have = 0, emitted = 0;              // latent rows held (frozen once a chunk was decoded from them), frames decoded so far
-  std::vector<float> voice, lat, pcm;     // the request's voice [1024]; its latent rows [have][1024]; the samples tts_ar_session_audio has not drained yet
-};
-struct ArSession {
-  int n_slots = 0, max_cand = 0, max_text = 0, max_steps = 0;
-  unsigned flags = 0;
-  // the options read once at tts_ar_session_open: every session call runs under them (SessionOptions), whatever tts_set_option has stored since
-  SamplerParams sp;
-  int scope = 0, ar_weights = 0, ggml_lut = 0, device_topk = 1;
-  std::vector<uint8_t> busy;
-  std::map<int, SessionRequest> reqs;
-  std::vector<int> finished; // ids, oldest first
-  int next_id = 0;
-  int audio_stride = 0;      // tts_ar_session_enable_audio: steps of the session's clock between two audio passes (0: a session without audio)
-  long clock = 0;            // steps the session has run
-};
-} // namespace tts
-
 using namespace tts;
-
-namespace {
-struct SessionOptions { // puts the session's options into the context for the length of one call
-  tts_ctx *c;
-  SamplerParams sp;
-  int scope, w, lut, topk;
-  SessionOptions(tts_ctx *ctx, const ArSession &s) : c(ctx), sp(ctx->ar_sp), scope(ctx->ar_penalty_scope), w(ctx->ar_weights), lut(ctx->ggml_lut), topk(ctx->device_topk) {
-    c->ar_sp = s.sp; c->ar_penalty_scope = s.scope; c->ar_weights = s.ar_weights; c->ggml_lut = s.ggml_lut; c->device_topk = s.device_topk;
-  }
-  ~SessionOptions() { c->ar_sp = sp; c->ar_penalty_scope = scope; c->ar_weights = w; c->ggml_lut = lut; c->device_topk = topk; }
-};
-struct SamplerOptions { // inside a SessionOptions: one request's sampler controls around the calls that sample or write its table rows
-  tts_ctx *c;
-  SamplerParams sp;
-  int scope;
-  SamplerOptions(tts_ctx *ctx, const SamplerParams &p, int sc) : c(ctx), sp(ctx->ar_sp), scope(ctx->ar_penalty_scope) { c->ar_sp = p; c->ar_penalty_scope = sc; }
-  ~SamplerOptions() { c->ar_sp = sp; c->ar_penalty_scope = scope; }
-};
-bool same_controls(const SamplerParams &a, int sa, const SamplerParams &b, int sb) {
-  return a.temp == b.temp && a.top_k == b.top_k && a.top_p == b.top_p && a.penalty == b.penalty && sa == sb;
-}
-// first fit: the first index of the lowest run of n_cand free slots, or -1
-int session_first_fit(const uint8_t *busy, int n_slots, int n_cand) {
-  int run = 0;
-  for (int i = 0; i < n_slots; i++) {
-    run = busy[i] ? 0 : run + 1;
-    if (run == n_cand) return i - n_cand + 1;
-  }
-  return -1;
-}
-void session_release(ArSession &s, int id) {
-  auto it = s.reqs.find(id);
-  if (it == s.reqs.end()) return;
-  std::fill(s.busy.begin() + it->second.c0, s.busy.begin() + it->second.c0 + it->second.n_cand, (uint8_t)0);
-  s.finished.erase(std::remove(s.finished.begin(), s.finished.end(), id), s.finished.end());
-  s.reqs.erase(it);
-}
-// One iteration of tts_autoregressive's loop from the samples on: the stop rule, then the loop's two exits.
-void session_advance(ArSession &s, SessionRequest &r) {
-  const bool retire = (s.flags & TTS_AR_RETIRE) != 0;
-  const bool sched = !r.stop_at.empty() && (s.flags & TTS_AR_MASK_STOP) && retire;
-  const bool all_ended = r.book.step(r.samples.data(), r.i, retire, sched ? r.stop_at.data() : nullptr);
-  r.i++;
-  if (all_ended) r.state = 1;
-  else if (r.i >= r.max_steps) r.state = ((s.flags & TTS_AR_MASK_STOP) || retire) ? 1 : 2;
-  if (r.state) s.finished.push_back(r.id);
-}
-} // namespace
-
-// One audio pass of a session: every audio request that has just finished, and with clock_due every running one, brings its new final latent rows to ONE
-// incremental latent pass (ar_session_extend) and its new final frames to ONE ragged tts_hifigan_chunk call. stream_emit's rules per request: after k sampled
-// codes the rows stream_final_rows(k) are final and the frames below tts_diffusion_frames(rows) - TTS_HFG_HALO_FRAMES with them; a finished request keeps
-// trimmed_latent_rows rows and is decoded to its end; a row is frozen once audio has been decoded from it.
-static int session_audio_pass(tts_ctx *c, ArSession &s, bool clock_due) {
-  struct Due { SessionRequest *r; std::vector<int32_t> codes; int L, upto; bool last; };
-  std::vector<Due> due;
-  for (auto &kv : s.reqs) {
-    SessionRequest &r = kv.second;
-    if (!r.audio || r.audio_done || (r.state == 0 && !clock_due)) continue;
-    if (r.state == 2) { r.audio_done = true; continue; } // a strict request that found no stop token: an error of its own, nothing more to hear
-    Due d{&r, {}, 0, 0, r.state != 0};
-    std::vector<int> sq = r.book.seq[0];
-    if (d.last) { // what tts_ar_session_collect will return
-      if (sq.size() > 500) sq.resize(500);
-      pad_codes(sq);
-      d.codes.assign(sq.begin(), sq.end());
-      d.L = trimmed_latent_rows(d.codes.data());
-      d.upto = tts_diffusion_frames(d.L);
-      if (d.L < r.have) return fail(c, TTS_ERR_STATE, "tts_ar_session_step: request %d: %d rows were final, the utterance keeps %d", r.id, r.have, d.L);
-    } else { // sq.size() codes so far, none of them the stop token (one candidate: the request ends with it)
-      d.codes.assign(502, 83);
-      d.codes[0] = 8192;
-      std::copy(sq.begin(), sq.begin() + std::min<size_t>(sq.size(), 501), d.codes.begin() + 1);
-      d.L = stream_final_rows(d.codes.data() + 1, (int)sq.size());
-      d.upto = tts_diffusion_frames(d.L) - TTS_HFG_HALO_FRAMES;
-      if (d.L <= r.have || d.upto <= r.emitted) continue;
-    }
-    due.push_back(std::move(d));
-  }
-  if (due.empty()) return TTS_OK;
-  std::vector<ArExtendItem> items;
-  size_t new_rows = 0;
-  for (Due &d : due)
-    if (d.L > d.r->have) { items.push_back(ArExtendItem{d.r->c0, d.r->n_text, d.r->have, d.L, d.codes.data()}); new_rows += (size_t)(d.L - d.r->have); }
-  if (!items.empty()) {
-    std::vector<float> rows(new_rows * TTS_DMODEL);
-    if (int rc = ar_session_extend(c, items.data(), (int)items.size(), rows.data())) return rc;
-    size_t off = 0;
-    for (Due &d : due) {
-      if (d.L <= d.r->have) continue;
-      const size_t n = (size_t)(d.L - d.r->have) * TTS_DMODEL;
-      d.r->lat.insert(d.r->lat.end(), rows.begin() + off, rows.begin() + off + n);
-      d.r->have = d.L;
-      off += n;
-    }
-  }
-  std::vector<float> lat, voices, audio;
-  std::vector<int32_t> n_rows, voice_of, f0, nf;
-  size_t frames = 0;
-  for (Due &d : due) {
-    if (d.upto <= d.r->emitted) continue; // (a finished request that keeps no row, or whose frames are all out)
-    lat.insert(lat.end(), d.r->lat.begin(), d.r->lat.end());
-    voices.insert(voices.end(), d.r->voice.begin(), d.r->voice.end());
-    voice_of.push_back((int32_t)n_rows.size());
-    n_rows.push_back(d.r->have); f0.push_back(d.r->emitted); nf.push_back(d.upto - d.r->emitted);
-    frames += (size_t)(d.upto - d.r->emitted);
-  }
-  if (!n_rows.empty()) {
-    audio.resize(frames * 256);
-    if (int rc = hifigan_chunk(c, lat.data(), n_rows.data(), (int)n_rows.size(), voices.data(), (int)n_rows.size(), voice_of.data(), f0.data(), nf.data(), audio.data()))
-      return rc;
-    size_t off = 0;
-    for (Due &d : due) {
-      if (d.upto <= d.r->emitted) continue;
-      const size_t n = (size_t)(d.upto - d.r->emitted) * 256;
-      d.r->pcm.insert(d.r->pcm.end(), audio.begin() + off, audio.begin() + off + n);
-      d.r->emitted = d.upto;
-      off += n;
-    }
-  }
-  for (Due &d : due)
-    if (d.last) d.r->audio_done = true;
-  return TTS_OK;
-}
 
 hipEvent_t tts::prof_event(tts_ctx *c) {
   if (!c->ev_pool.empty()) { hipEvent_t e = c->ev_pool.back(); c->ev_pool.pop_back(); return e; }
@@ -298,10 +108,10 @@ int tts_pin_to_device_numa_node(tts_ctx *c) {
 void tts_destroy(tts_ctx *c) {
   if (!c) return;
   if (c->sampler_pool) sampler_pool_free(c->sampler_pool);
-  delete c->session;
   if (c->device < 0) { delete c->tok; delete c; return; }
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
+  if (c->session) ar_drv_close(c);
   diff_session_close(c);
   if (c->ar) ar_free(c->ar);
   if (c->diff) diff_free(c->diff);
@@ -568,30 +378,11 @@ int tts_ar_step(tts_ctx *c, const int32_t *prev, int i, float *logits) {
   NO_SESSION(c, "tts_ar_step");
   return guarded(c, [&] { return ar_step(c, prev, i, logits, 0); });
 }
-// decode step + sampler in one call: the device prefilter's lists cross PCIe instead of the logits (ar.hip: sample_prefilter_kernel)
-static int step_sample(tts_ctx *c, const int32_t *prev, int i, bool mask_stop, int32_t *out, int *fallbacks) {
-  if (int rc = ar_step(c, prev, i, nullptr, mask_stop ? 2 : 1)) return rc;
-  const int B = ar_batch(c);
-  std::vector<int32_t> hist; // penalty scope 1: the lists hold penalised values; only a full-row fallback needs the candidate's history as ids
-  const bool scope1 = c->ar_penalty_scope == 1;
-  const PenaltyIdsFn ids_of = [&](int b, const int32_t *&p, int &n) {
-    if (scope1) { ar_history_ids(c, b, hist); p = hist.data(); n = (int)hist.size(); }
-    else { p = prev + b; n = 1; }
-  };
-  if (sample_candidates_list(c, c->generator, ar_host_lists(c), ids_of, scope1, B, out, [&](int b) { return ar_fetch_logits_row(c, b); }, fallbacks))
-    return fail(c, TTS_ERR_HIP, "tts_ar_step_sample: fetching a logits row failed");
-  return TTS_OK;
-}
 int tts_ar_step_sample(tts_ctx *c, const int32_t *prev, int i, unsigned flags, int32_t *samples_out) {
   NEED_CTX(c);
   NO_SESSION(c, "tts_ar_step_sample");
   if (!prev || !samples_out) return TTS_ERR_ARG;
-  return guarded(c, [&] {
-    if (ar_batch(c) < 1) return fail(c, TTS_ERR_STATE, "tts_ar_begin not called"); // before the shard check: with no AR state the batch is 0
-    if (int rc = shard_check(c, ar_batch(c))) return rc;
-    c->topk_fallbacks = 0;
-    return step_sample(c, prev, i, (flags & TTS_AR_MASK_STOP) != 0, samples_out, &c->topk_fallbacks);
-  });
+  return guarded(c, [&] { return ar_drv_step_sample(c, prev, i, flags, samples_out); });
 }
 int tts_ar_topk_fallbacks(const tts_ctx *c) { return c ? c->topk_fallbacks : -1; }
 int tts_diffusion_time_mlp_retries(const tts_ctx *c) { return c ? c->time_mlp_retries : -1; }
@@ -644,211 +435,16 @@ int tts_sample(tts_ctx *c, const float *logits, const int32_t *ids, int ids_per_
   for (int i = 0; i < B * ids_per_cand; i++)
     if (ids[i] < 0 || ids[i] >= TTS_VOCAB_MEL) return fail(c, TTS_ERR_ARG, "penalty id out of range");
   if (int rc = shard_check(c, B)) return rc;
-  return guarded(c, [&] { sample_candidates(c, c->generator, logits, ids, ids_per_cand, B, out); return (int)TTS_OK; });
+  return guarded(c, [&] { sample_candidates(c, c->generator, c->ar_sp, logits, ids, ids_per_cand, B, out); return (int)TTS_OK; });
 }
 
-// autoregressive(), main.cpp:5042-5367, for G prompt groups in one decode loop (tts_autoregressive: G = 1; tts_autoregressive_multi). Group g's
-// prompt is text_ids[t0_g .. + n_text[g]), its candidates [c0_g, c0_g + n_cand[g]) of the batch. voice: [n_voices][1024], group g reads row voice_of[g]
-// (tts_autoregressive_multi_voice; voice_of == nullptr: one voice for all). Nothing after ar_begin_groups depends on the voices.
-//
-// tts_hifigan_stream (one candidate, `hs` non-null): the same loop; after every hs->stride new codes the latent pass runs over the rows that are already
-// final and the HiFi-GAN chunk path decodes the frames that became final, which go to the callback while the loop goes on sampling.
-struct HfgStream {
-  int stride;
-  tts_audio_cb cb;
-  void *user;
-  const float *voice;
-  int have = 0, emitted = 0;            // latent rows held (frozen once a chunk was decoded from them), frames handed to the callback
-  std::vector<float> lat, pass, audio;  // the utterance's latent rows; one pass' output; one chunk's samples
-  std::vector<int32_t> codes;           // the pass' input: 8192, the sampled codes, 83 beyond (never read: n_mel ends before)
-};
-// Latent rows [hs->have, L) from a pass over the first L rows (the earlier rows are kept as they were when their audio left: what the callback got stays the
-// decode of the latents the call returns), then the frames [hs->emitted, upto) of an utterance of L rows so far to the callback.
-static int stream_emit(tts_ctx *c, HfgStream *hs, const int32_t *codes502, int L, int upto, int is_last) {
-  if (L > hs->have) {
-    // The last pass is tts_autoregressive's, length and all. A pass over a prefix runs at least 32 rows (the rows past L read padding and are dropped: causal),
-    // so that it takes the multi-row path (ar.hip run_layers: rows >= 32) that every utterance of 31 rows or more ends on — the exact-f32 GEMV path of shorter
-    // passes sums in another order, and its split-K factor depends on the row count.
-    const int n_mel = is_last ? std::min(502, L + 1) : std::max(L, 32), n_out = std::min(500, n_mel);
-    hs->pass.resize((size_t)n_out * TTS_DMODEL);
-    if (int rc = ar_latents_group(c, 0, codes502, n_mel, hs->pass.data())) return rc;
-    hs->lat.resize((size_t)L * TTS_DMODEL);
-    std::copy(hs->pass.begin() + (size_t)hs->have * TTS_DMODEL, hs->pass.begin() + (size_t)L * TTS_DMODEL, hs->lat.begin() + (size_t)hs->have * TTS_DMODEL);
-    hs->have = L;
-  }
-  const int32_t rows = hs->have, f0 = hs->emitted, n = upto - hs->emitted;
-  if (n < 1) return TTS_OK;
-  hs->audio.resize((size_t)n * 256);
-  if (int rc = hifigan_chunk(c, hs->lat.data(), &rows, 1, hs->voice, 1, nullptr, &f0, &n, hs->audio.data())) return rc;
-  hs->emitted = upto;
-  if (hs->cb(hs->user, hs->audio.data(), n * 256, is_last)) return fail(c, TTS_ERR_STATE, "tts_hifigan_stream: cancelled by the callback");
-  return TTS_OK;
-}
-
-static int autoregressive_impl(tts_ctx *c, const int32_t *text_ids, const int *n_text, int G, const float *voice, int n_voices, const int *voice_of,
-                               const int *n_cand, int max_steps, unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out,
-                               HfgStream *hs = nullptr) {
-  static const bool timing = getenv("TTS_TIMING") != nullptr; // developer aid: host-side breakdown of the stage on stderr
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_begin = now(), t_sample = 0, t_step = 0;
-  if (!codes_out || !rows_out) return fail(c, TTS_ERR_ARG, "tts_autoregressive: null output");
-  if (G < 1 || !n_text || !n_cand) return fail(c, TTS_ERR_ARG, "tts_autoregressive: bad argument");
-  int B = 0, P_max = 0;
-  for (int g = 0; g < G; g++) { B += n_cand[g] > 0 ? n_cand[g] : 0; P_max = std::max(P_max, n_text[g] + 2); }
-  if (max_steps > 500) return fail(c, TTS_ERR_LIMIT, "max_steps %d exceeds the 500 codes apply_padding accepts", max_steps);
-  // The stop schedule (tts_ar_set_stop_schedule: a bench / test device, not a reference feature) is checked BEFORE any device work, applies only to calls that pass
-  // TTS_AR_MASK_STOP | TTS_AR_RETIRE (the combination it is documented for: a strict call is never truncated by a forgotten schedule) and says so on stderr once.
-  const bool sched = !c->stop_schedule.empty() && (flags & TTS_AR_MASK_STOP) && (flags & TTS_AR_RETIRE);
-  if (!c->stop_schedule.empty() && !sched) {
-    static bool warned = false;
-    if (!warned) { fprintf(stderr, "tts_autoregressive: a stop schedule is set but the call does not pass TTS_AR_MASK_STOP | TTS_AR_RETIRE: ignored\n"); warned = true; }
-  }
-  if (sched && (int)c->stop_schedule.size() != B) return fail(c, TTS_ERR_ARG, "tts_autoregressive: the stop schedule holds %d candidates, the call %d", (int)c->stop_schedule.size(), B);
-  if (hs) c->stream_recaptures = 0;
-  int rc = ar_begin_groups(c, text_ids, n_text, G, voice, n_voices, voice_of, n_cand, max_steps);
-  if (rc) return rc;
-  // the longest latent pass a streaming call can run (trim_latents keeps at most 9 rows past the codes), reserved once the call is known to be valid and
-  // before the decode step's buffers are used
-  if (hs && (rc = ar_stream_reserve(c, std::max(32, std::min(502, max_steps + 10))))) return rc;
-  int captures0 = -1; // decode-step graphs captured when the loop's first step had run
-  const int V = TTS_VOCAB_MEL;
-  std::vector<float> logits0((size_t)B * V);
-  const double t_after_begin = now();
-  if ((rc = ar_prefill(c, logits0.data()))) return rc;
-  float *logits = logits0.data(); // after the first step: the pinned buffer the decode graph copies into (no extra host copy)
-  const double t_after_prefill = now();
-  // mel_transformer_inputs_vector: [1 ... 1, 8192] per candidate at step 0 (5095-5105), afterwards
-  // the previous samples (5208-5217). Several prompts: every row is padded to the longest prompt's P with more 1s — the penalty is applied once per
-  // DISTINCT id (sample_one / sample_one_list skip repeated ids; the literal form recomputes l[id] from the unpenalised logit), so the padded row
-  // penalises exactly what the group's own row does (tests/test_multi_prompt_cpu.py checks it on the sampler).
-  const int P = P_max;
-  std::vector<int32_t> ids((size_t)P * B, 1);
-  for (int b = 0; b < B; b++) ids[(size_t)b * P + P - 1] = 8192;
-  int ids_per_cand = P;
-  std::vector<int32_t> samples(B);
-  // Stop rule (ArStopBook, host_logic.cpp). Reference (strict, always for B == 1): the loop ends only in an iteration where ALL B samples are 8193
-  // (main.cpp:5214-5222), a candidate's sequence freezes at its first 8193 (5210-5213); several prompts: that rule per group, and an ended group's rows
-  // are fed 8193. TTS_AR_RETIRE (throughput mode): a candidate retires at its first 8193 — from then on its input token is forced to 8193
-  // and its samples are ignored — the loop ends when every candidate has retired, and reaching max_steps pads and returns instead of failing.
-  // The uniforms are consumed exactly as in strict mode (two per candidate and step, candidate order), so every
-  // sequence is the one strict mode would have produced.
-  const bool retire = (flags & TTS_AR_RETIRE) != 0;
-  if ((rc = shard_check(c, B))) return rc;
-  ArStopBook book;
-  book.init(n_cand, G);
-  std::vector<int32_t> next; // the samples of the coming iteration when the device-top-k step already produced them
-  bool have_next = false;
-  c->topk_fallbacks = 0;
-  // Penalty scope 1 (option "ar_penalty_scope"; HF generate's repetition penalty as upstream tortoise-tts runs it): every id fed since ar_begin_groups plus 1 and
-  // 8192. ar_step keeps that set per candidate (the bitmap its penalising prefilter reads); the full-row sampler gets it as an id list. At step 0 nothing has
-  // been fed: the set is {1, 8192}, exactly the distinct ids of the prompt-shaped row above.
-  const bool scope1 = c->ar_penalty_scope == 1;
-  std::vector<std::vector<int32_t>> hist(scope1 ? B : 0);
-  std::vector<int32_t> hist_one;
-  int i = 0;
-  for (;;) {
-    double t0 = now();
-    if (have_next) { samples = next; have_next = false; }
-    else {
-      if (flags & TTS_AR_MASK_STOP)
-        for (int b = 0; b < B; b++) logits[(size_t)b * V + 8193] = -1e30f;
-      if (scope1 && i > 0) {
-        for (int b = 0; b < B; b++) ar_history_ids(c, b, hist[b]);
-        sample_candidates(c, c->generator, logits, [&](int b, const int32_t *&p, int &n) { p = hist[b].data(); n = (int)hist[b].size(); }, B, samples.data());
-      } else
-        sample_candidates(c, c->generator, logits, ids.data(), ids_per_cand, B, samples.data());
-      t_sample += now() - t0;
-    }
-    const bool all_ended = book.step(samples.data(), i, retire, sched ? c->stop_schedule.data() : nullptr);
-    ids.assign(samples.begin(), samples.end());
-    ids_per_cand = 1;
-    i++;
-    if (all_ended) break;
-    if (i >= max_steps) {
-      if ((flags & TTS_AR_MASK_STOP) || retire) break;
-      return fail(c, TTS_ERR_LIMIT, "no stop token within %d steps", max_steps);
-    }
-    if (hs && i % hs->stride == 0) { // i codes so far, none of them the stop token (one candidate: the loop ends with it)
-      const std::vector<int> &sq = book.seq[0];
-      hs->codes.assign(502, 83);
-      hs->codes[0] = 8192;
-      std::copy(sq.begin(), sq.begin() + std::min<size_t>(sq.size(), 501), hs->codes.begin() + 1);
-      const int L = stream_final_rows(hs->codes.data() + 1, (int)sq.size());
-      const int upto = tts_diffusion_frames(L) - TTS_HFG_HALO_FRAMES;
-      if (L > hs->have && upto > hs->emitted && (rc = stream_emit(c, hs, hs->codes.data(), L, upto, 0))) return rc;
-    }
-    if (captures0 < 0 && i > 1) captures0 = ar_graph_captures(c);
-    t0 = now();
-    if (!c->device_topk) {
-      if ((rc = ar_step(c, samples.data(), i - 1, nullptr, 0))) return rc;
-      logits = ar_host_logits(c);
-      t_step += now() - t0;
-      continue;
-    }
-    // device top-k: the step hands back each candidate's ~64..128 largest logits and the sampler runs on those (same uniforms, same ids)
-    if ((rc = ar_step(c, samples.data(), i - 1, nullptr, (flags & TTS_AR_MASK_STOP) ? 2 : 1))) return rc;
-    t_step += now() - t0;
-    t0 = now();
-    next.resize(B);
-    const PenaltyIdsFn ids_of = [&](int b, const int32_t *&p, int &n) {
-      if (scope1) { ar_history_ids(c, b, hist_one); p = hist_one.data(); n = (int)hist_one.size(); }
-      else { p = ids.data() + b; n = 1; }
-    };
-    if (sample_candidates_list(c, c->generator, ar_host_lists(c), ids_of, scope1, B, next.data(), [&](int b) { return ar_fetch_logits_row(c, b); }, &c->topk_fallbacks,
-                               book.retired.data()))
-      return fail(c, TTS_ERR_HIP, "tts_autoregressive: fetching a logits row failed");
-    t_sample += now() - t0;
-    have_next = true;
-  }
-  const double t_after_loop = now();
-  if (hs) c->stream_recaptures = captures0 < 0 ? 0 : ar_graph_captures(c) - captures0;
-  if (steps_out) *steps_out = i;
-  std::vector<std::vector<int>> &seq = book.seq;
-  c->ar_stopped.assign(B, 0); // who was cut at max_steps (TTS_AR_RETIRE / TTS_AR_MASK_STOP): tts_ar_stop_status
-  for (int b = 0; b < B; b++) c->ar_stopped[b] = (!seq[b].empty() && seq[b].back() == 8193) ? 1 : 0;
-  std::vector<int> max_rows(G, 0);
-  for (int g = 0; g < G; g++)
-    for (int b = book.c0[g]; b < book.c0[g] + n_cand[g]; b++) {
-      if (seq[b].size() > 500) seq[b].resize(500); // the reference asserts (main.cpp:4517)
-      pad_codes(seq[b]);
-      std::copy(seq[b].begin(), seq[b].end(), codes_out + (size_t)b * 502);
-      rows_out[b] = trimmed_latent_rows(codes_out + (size_t)b * 502);
-      max_rows[g] = std::max(max_rows[g], rows_out[b]);
-    }
-  if (hs) { // the remaining rows from tts_autoregressive's own pass, the remaining frames with is_last
-    if (rows_out[0] < hs->have) return fail(c, TTS_ERR_STATE, "tts_hifigan_stream: %d rows were final, the utterance keeps %d", hs->have, rows_out[0]);
-    if ((rc = stream_emit(c, hs, codes_out, rows_out[0], tts_diffusion_frames(rows_out[0]), 1))) return rc;
-    if (latents_out) std::copy(hs->lat.begin(), hs->lat.end(), latents_out);
-    return TTS_OK;
-  }
-  if (!latents_out) return TTS_OK;
-  // latent pass over the mel prefix that trim_latents keeps (causal: rows beyond it cannot matter), per group over its own prompt and rows
-  const double t_before_lat = now();
-  size_t off = 0;
-  for (int g = 0; g < G; g++) {
-    const int n_mel = std::min(502, max_rows[g] + 1);
-    const int n_out = std::min(500, n_mel);
-    std::vector<float> lat((size_t)n_cand[g] * n_out * TTS_DMODEL);
-    if ((rc = ar_latents_group(c, g, codes_out + (size_t)book.c0[g] * 502, n_mel, lat.data()))) return rc;
-    for (int k = 0; k < n_cand[g]; k++) {
-      const int b = book.c0[g] + k;
-      std::copy(lat.begin() + (size_t)k * n_out * TTS_DMODEL, lat.begin() + ((size_t)k * n_out + rows_out[b]) * TTS_DMODEL, latents_out + off);
-      off += (size_t)rows_out[b] * TTS_DMODEL;
-    }
-  }
-  if (timing)
-    fprintf(stderr, "[tts timing] AR: begin %.1f ms, prefill %.1f, loop %.1f (steps %.1f in %d, sampler %.1f), latents %.1f, total %.1f\n",
-            t_after_begin - t_begin, t_after_prefill - t_after_begin, t_after_loop - t_after_prefill, t_step, i - 1, t_sample,
-            now() - t_before_lat, now() - t_begin);
-  return TTS_OK;
-}
-
+// The decode loop behind the calls below: ar_driver.cpp.
 int tts_autoregressive(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, int B, int max_steps,
                        unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out) {
   NEED_CTX(c);
   NO_SESSION(c, "tts_autoregressive");
   return guarded(c, [&] {
-    return autoregressive_impl(c, text_ids, &n_text, 1, voice, 1, nullptr, &B, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
+    return ar_drv_autoregressive(c, text_ids, &n_text, 1, voice, 1, nullptr, &B, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
   });
 }
 
@@ -863,9 +459,8 @@ int tts_hifigan_stream(tts_ctx *c, const int32_t *text_ids, int n_text, const fl
     for (int i = 0; i < TTS_DMODEL; i++)
       if (!std::isfinite(voice[i])) return fail(c, TTS_ERR_ARG, "tts_hifigan_stream: the voice holds a non-finite value");
   return guarded(c, [&] {
-    HfgStream hs{stride_codes, cb, user, voice};
     const int B = 1;
-    return autoregressive_impl(c, text_ids, &n_text, 1, voice, 1, nullptr, &B, max_steps, flags, codes_out, rows_out, latents_out, steps_out, &hs);
+    return ar_drv_autoregressive(c, text_ids, &n_text, 1, voice, 1, nullptr, &B, max_steps, flags, codes_out, rows_out, latents_out, steps_out, stride_codes, cb, user);
   });
 }
 
@@ -875,7 +470,7 @@ int tts_autoregressive_multi(tts_ctx *c, const int32_t *text_ids, const int32_t 
   NO_SESSION(c, "tts_autoregressive_multi");
   if (n_prompts < 1 || !n_text || !n_cand) return fail(c, TTS_ERR_ARG, "tts_autoregressive_multi: bad argument");
   return guarded(c, [&] {
-    return autoregressive_impl(c, text_ids, n_text, n_prompts, voice, 1, nullptr, n_cand, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
+    return ar_drv_autoregressive(c, text_ids, n_text, n_prompts, voice, 1, nullptr, n_cand, max_steps, flags, codes_out, rows_out, latents_out, steps_out);
   });
 }
 
@@ -903,7 +498,7 @@ int tts_autoregressive_multi_voice(tts_ctx *c, const int32_t *text_ids, const in
   if (n_prompts < 1 || !n_text || !n_cand || !voices || !voice_of_prompt || n_voices < 1)
     return fail(c, TTS_ERR_ARG, "tts_autoregressive_multi_voice: bad argument");
   return guarded(c, [&] {
-    return autoregressive_impl(c, text_ids, n_text, n_prompts, voices, n_voices, voice_of_prompt, n_cand, max_steps, flags, codes_out, rows_out, latents_out,
+    return ar_drv_autoregressive(c, text_ids, n_text, n_prompts, voices, n_voices, voice_of_prompt, n_cand, max_steps, flags, codes_out, rows_out, latents_out,
                                steps_out);
   });
 }
@@ -966,9 +561,7 @@ int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand) {
 int tts_ar_session_close(tts_ctx *c) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_close");
-  delete c->session;
-  c->session = nullptr;
-  ar_session_close(c);
+  ar_drv_close(c);
   return TTS_OK;
 }
 
@@ -983,26 +576,14 @@ int tts_ar_session_open(tts_ctx *c, int n_slots, int max_cand, int max_text, int
   if (max_text > 404) return fail(c, TTS_ERR_LIMIT, "text of %d ids; the model has 404 text positions", max_text);
   if (max_steps > 500) return fail(c, TTS_ERR_LIMIT, "max_steps %d exceeds the 500 codes apply_padding accepts", max_steps);
   if (max_text + 2 + max_steps + 1 > 1024) return fail(c, TTS_ERR_LIMIT, "context of %d positions exceeds 1024", max_text + 2 + max_steps + 1);
-  return guarded(c, [&] {
-    if (c->session) { delete c->session; c->session = nullptr; ar_session_close(c); }
-    std::unique_ptr<ArSession> s(new ArSession());
-    s->n_slots = n_slots; s->max_cand = max_cand; s->max_text = max_text; s->max_steps = max_steps; s->flags = flags;
-    s->sp = c->ar_sp; s->scope = c->ar_penalty_scope; s->ar_weights = c->ar_weights; s->ggml_lut = c->ggml_lut; s->device_topk = c->device_topk;
-    s->busy.assign((size_t)n_slots, 0);
-    if (int rc = ar_session_open(c, n_slots, max_cand, max_text, max_steps, (flags & TTS_AR_ROW_CONTROLS) != 0)) return rc;
-    c->topk_fallbacks = 0;
-    c->session = s.release();
-    return (int)TTS_OK;
-  });
+  return guarded(c, [&] { return ar_drv_open(c, n_slots, max_cand, max_text, max_steps, flags); });
 }
 
 int tts_ar_session_room(const tts_ctx *c) {
   if (!c) return TTS_ERR_ARG;
   if (c->device < 0) return TTS_ERR_HIP;
   if (!c->session) return TTS_ERR_STATE;
-  int best = 0, run = 0;
-  for (uint8_t b : c->session->busy) { run = b ? 0 : run + 1; best = std::max(best, run); }
-  return best;
+  return ar_drv_room(c);
 }
 
 int tts_ar_session_recaptures(const tts_ctx *c) {
@@ -1052,254 +633,68 @@ int tts_ar_request_init(tts_ctx *c, tts_ar_request *req) {
   if (req->struct_size < sizeof(tts_ar_request))
     return fail(c, TTS_ERR_ARG, "tts_ar_request_init: struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_ar_request) first)", req->struct_size,
                 sizeof(tts_ar_request));
-  const ArSession &s = *c->session;
   req->n_cand = 1; req->seed = 0; req->max_steps = 0; req->stop_at = nullptr;
-  req->temperature = s.sp.temp; req->top_k = s.sp.top_k; req->top_p = s.sp.top_p; req->repetition_penalty = s.sp.penalty; req->penalty_scope = s.scope;
+  ar_drv_defaults(c, req);
   return TTS_OK;
 }
 
-// tts_ar_session_admit and tts_ar_session_admit_ex (fn: the caller's name in the messages). sp / scope / max_steps: the request's, already checked.
-static int session_admit(tts_ctx *c, const char *fn, const int32_t *text_ids, int n_text, const float *voice, int n_cand, uint32_t seed, const int32_t *stop_at,
-                         const SamplerParams &sp, int scope, int max_steps) {
-  ArSession &s = *c->session;
-  // every argument before any device work
-  if (!text_ids || !voice || n_text < 1 || n_cand < 1) return fail(c, TTS_ERR_ARG, "%s: bad argument (%d ids, %d candidates)", fn, n_text, n_cand);
-  if (n_text > s.max_text) return fail(c, TTS_ERR_LIMIT, "%s: %d ids, the session was opened for %d", fn, n_text, s.max_text);
-  if (n_cand > s.max_cand) return fail(c, TTS_ERR_LIMIT, "%s: %d candidates, the session was opened for %d", fn, n_cand, s.max_cand);
-  for (int i = 0; i < n_text; i++)
-    if (text_ids[i] < 0 || text_ids[i] >= 256) return fail(c, TTS_ERR_ARG, "text id %d out of range", text_ids[i]);
-  for (int i = 0; i < TTS_DMODEL; i++)
-    if (!std::isfinite(voice[i])) return fail(c, TTS_ERR_ARG, "%s: the voice holds a non-finite value", fn);
-  if (stop_at)
-    for (int b = 0; b < n_cand; b++)
-      if (stop_at[b] < 1) return fail(c, TTS_ERR_ARG, "%s: candidate %d would stop before its first code", fn, b);
-  const bool rows = (s.flags & TTS_AR_ROW_CONTROLS) != 0;
-  if (!rows && !same_controls(sp, scope, s.sp, s.scope))
-    return fail(c, TTS_ERR_STATE, "%s: the request's sampler controls differ from the session's (open the session with TTS_AR_ROW_CONTROLS)", fn);
-  const int c0 = session_first_fit(s.busy.data(), s.n_slots, n_cand);
-  if (c0 < 0) return fail(c, TTS_ERR_LIMIT, "%s: no run of %d free slots (collect a finished request first)", fn, n_cand);
-  return guarded(c, [&] {
-    SessionOptions opt(c, s);
-    SamplerOptions ropt(c, sp, scope); // the request's controls: its table rows, its first codes
-    const int V = TTS_VOCAB_MEL, P = n_text + 2;
-    std::vector<float> row((size_t)V);
-    if (int rc = ar_session_prompt(c, c0, n_cand, text_ids, n_text, voice, row.data())) return rc;
-    if (rows) // every admission writes its rows: whatever the slots' last request left there (finished, cancelled or failed half-way) is gone
-      if (int rc = ar_session_controls(c, c0, n_cand)) return rc;
-    SessionRequest r;
-    r.id = s.next_id; r.c0 = c0; r.n_cand = n_cand; r.n_text = n_text;
-    r.sp = sp; r.scope = scope; r.max_steps = max_steps;
-    r.gen.seed(seed);
-    r.book.init(&n_cand, 1);
-    if (stop_at) r.stop_at.assign(stop_at, stop_at + n_cand);
-    // tts_autoregressive's iteration 0: every candidate samples from the prompt's logits under the prompt-shaped penalty row [1 ... 1, 8192]
-    if (s.flags & TTS_AR_MASK_STOP) row[8193] = -1e30f;
-    std::vector<float> logits0((size_t)n_cand * V);
-    for (int b = 0; b < n_cand; b++) std::copy(row.begin(), row.end(), logits0.begin() + (size_t)b * V);
-    std::vector<int32_t> ids((size_t)P * n_cand, 1);
-    for (int b = 0; b < n_cand; b++) ids[(size_t)b * P + P - 1] = 8192;
-    r.samples.resize(n_cand);
-    sample_candidates(c, r.gen, logits0.data(), ids.data(), P, n_cand, r.samples.data());
-    if (s.audio_stride && n_cand == 1) { // the prompt's rows of the latent pass, once, from the decode cache the prompt pass has just written
-      if (int rc = ar_session_audio_prompt(c, c0, n_text)) return rc;
-      r.audio = true;
-      r.voice.assign(voice, voice + TTS_DMODEL);
-    }
-    std::fill(s.busy.begin() + c0, s.busy.begin() + c0 + n_cand, (uint8_t)1);
-    SessionRequest &slot = s.reqs[r.id] = std::move(r);
-    s.next_id++;
-    session_advance(s, slot);
-    if (slot.audio && slot.state != 0) // finished with its first code: no step will see it
-      if (int rc = session_audio_pass(c, s, false)) return rc;
-    return slot.id;
-  });
-}
-
+// ---- the session's entry points (state and host rules: ar_driver.cpp; device work: ar.hip) ----
 int tts_ar_session_admit(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, int n_cand, uint32_t seed, const int32_t *stop_at) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_admit");
-  const ArSession &s = *c->session;
-  return session_admit(c, "tts_ar_session_admit", text_ids, n_text, voice, n_cand, seed, stop_at, s.sp, s.scope, s.max_steps);
+  return guarded(c, [&] { return ar_drv_admit(c, "tts_ar_session_admit", text_ids, n_text, voice, n_cand, seed, stop_at, nullptr, 0, 0); });
 }
-
 int tts_ar_session_admit_ex(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, const tts_ar_request *req) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_admit_ex");
-  const ArSession &s = *c->session;
   SamplerParams sp;
-  int scope = 0;
+  int scope = 0, max_cand = 0, max_steps = 0;
+  ar_drv_limits(c, max_cand, max_steps);
   std::string why;
-  if (int rc = request_check(req, s.max_cand, s.max_steps, sp, scope, why)) return fail(c, rc, "tts_ar_session_admit_ex: %s", why.c_str());
-  return session_admit(c, "tts_ar_session_admit_ex", text_ids, n_text, voice, req->n_cand, req->seed, req->stop_at, sp, scope,
-                       req->max_steps ? req->max_steps : s.max_steps);
+  if (int rc = request_check(req, max_cand, max_steps, sp, scope, why)) return fail(c, rc, "tts_ar_session_admit_ex: %s", why.c_str());
+  return guarded(c, [&] {
+    return ar_drv_admit(c, "tts_ar_session_admit_ex", text_ids, n_text, voice, req->n_cand, req->seed, req->stop_at, &sp, scope, req->max_steps);
+  });
 }
-
 int tts_ar_session_step(tts_ctx *c) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_step");
-  ArSession &s = *c->session;
-  return guarded(c, [&] {
-    int n_live = 0;
-    for (auto &kv : s.reqs) n_live += kv.second.state == 0;
-    if (n_live == 0) return 0;
-    SessionOptions opt(c, s);
-    const int V = TTS_VOCAB_MEL;
-    // An empty slot sits at position 0. A finished request's rows are parked at position n_text + 2, the first mel position that its latent pass recomputes
-    // anyway: its prompt's K/V rows [0, n_text + 1) stay as the prompt pass wrote them until the request is collected, and the row reads written memory only.
-    std::vector<int32_t> toks((size_t)s.n_slots, 8193), n_past((size_t)s.n_slots, 0), pos((size_t)s.n_slots, 0);
-    std::vector<char> live((size_t)s.n_slots, 0);
-    for (auto &kv : s.reqs) {
-      const SessionRequest &r = kv.second;
-      for (int b = 0; b < r.n_cand; b++) {
-        const int k = r.c0 + b;
-        if (r.state == 0) { toks[k] = r.samples[b]; n_past[k] = r.n_text + 2 + (r.i - 1); pos[k] = (r.i - 1) + 2; live[k] = 1; }
-        else { n_past[k] = r.n_text + 2; pos[k] = 2; }
-      }
-    }
-    const bool mask = (s.flags & TTS_AR_MASK_STOP) != 0;
-    const int mode = s.device_topk ? (mask ? 2 : 1) : 0;
-    if (int rc = ar_session_step(c, toks.data(), n_past.data(), pos.data(), live.data(), mode)) return rc;
-    std::vector<std::vector<int32_t>> hist;
-    std::vector<int32_t> hist_one, next;
-    for (auto &kv : s.reqs) {
-      SessionRequest &r = kv.second;
-      if (r.state != 0) continue;
-      SamplerOptions ropt(c, r.sp, r.scope); // the request's own controls: the uniform session's are the session's
-      const bool scope1 = r.scope == 1;
-      next.assign((size_t)r.n_cand, 0);
-      if (mode == 0) { // the full rows, as tts_autoregressive with device_topk = 0
-        float *logits = ar_host_logits(c) + (size_t)r.c0 * V;
-        if (mask)
-          for (int b = 0; b < r.n_cand; b++) logits[(size_t)b * V + 8193] = -1e30f;
-        if (scope1) {
-          hist.resize((size_t)r.n_cand);
-          for (int b = 0; b < r.n_cand; b++) ar_history_ids(c, r.c0 + b, hist[b]);
-          sample_candidates(c, r.gen, logits, [&](int b, const int32_t *&p, int &n) { p = hist[b].data(); n = (int)hist[b].size(); }, r.n_cand, next.data());
-        } else
-          sample_candidates(c, r.gen, logits, r.samples.data(), 1, r.n_cand, next.data());
-      } else {
-        const PenaltyIdsFn ids_of = [&](int b, const int32_t *&p, int &n) {
-          if (scope1) { ar_history_ids(c, r.c0 + b, hist_one); p = hist_one.data(); n = (int)hist_one.size(); }
-          else { p = r.samples.data() + b; n = 1; }
-        };
-        if (sample_candidates_list(c, r.gen, ar_host_lists(c) + (size_t)r.c0 * TTS_PF_WORDS, ids_of, scope1, r.n_cand, next.data(),
-                                   [&](int b) { return ar_fetch_logits_row(c, r.c0 + b); }, &c->topk_fallbacks, r.book.retired.data()))
-          return fail(c, TTS_ERR_HIP, "tts_ar_session_step: fetching a logits row failed");
-      }
-      r.samples = next;
-      session_advance(s, r);
-      n_live -= r.state != 0;
-    }
-    s.clock++;
-    if (s.audio_stride)
-      if (int rc = session_audio_pass(c, s, s.clock % s.audio_stride == 0)) return rc;
-    return n_live;
-  });
+  return guarded(c, [&] { return ar_drv_step(c); });
 }
-
 int tts_ar_session_finished(tts_ctx *c, int32_t *ids_out, int cap) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_finished");
   if (cap < 0 || (cap > 0 && !ids_out)) return fail(c, TTS_ERR_ARG, "tts_ar_session_finished: bad argument");
-  const std::vector<int> &f = c->session->finished;
-  for (int k = 0; k < (int)f.size() && k < cap; k++) ids_out[k] = f[k];
-  return (int)f.size();
+  return ar_drv_finished(c, ids_out, cap);
 }
-
 int tts_ar_session_collect(tts_ctx *c, int request, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out, int32_t *stopped_out) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_collect");
-  ArSession &s = *c->session;
   if (!codes_out || !rows_out) return fail(c, TTS_ERR_ARG, "tts_ar_session_collect: null output");
-  auto it = s.reqs.find(request);
-  if (it == s.reqs.end()) return fail(c, TTS_ERR_ARG, "tts_ar_session_collect: no request %d", request);
-  if (it->second.state == 0) return fail(c, TTS_ERR_STATE, "tts_ar_session_collect: request %d is still running", request);
-  if (it->second.state == 2) {
-    const int limit = it->second.max_steps;
-    session_release(s, request);
-    return fail(c, TTS_ERR_LIMIT, "no stop token within %d steps", limit);
-  }
-  return guarded(c, [&] {
-    SessionOptions opt(c, s);
-    SessionRequest &r = it->second;
-    std::vector<std::vector<int>> seq = r.book.seq; // (the request stays collectable if the latent pass fails)
-    int max_rows = 0;
-    for (int b = 0; b < r.n_cand; b++) {
-      if (stopped_out) stopped_out[b] = (!seq[b].empty() && seq[b].back() == 8193) ? 1 : 0;
-      if (seq[b].size() > 500) seq[b].resize(500);
-      pad_codes(seq[b]);
-      std::copy(seq[b].begin(), seq[b].end(), codes_out + (size_t)b * 502);
-      rows_out[b] = trimmed_latent_rows(codes_out + (size_t)b * 502);
-      max_rows = std::max(max_rows, rows_out[b]);
-    }
-    if (steps_out) *steps_out = r.i;
-    if (latents_out && r.audio && r.audio_done && r.have == rows_out[0]) { // the frozen rows: what the request's audio was decoded from
-      std::copy(r.lat.begin(), r.lat.end(), latents_out);
-    } else if (latents_out) { // the latent pass over the mel prefix that trim_latents keeps, as tts_autoregressive's
-      const int n_mel = std::min(502, max_rows + 1), n_out = std::min(500, n_mel);
-      std::vector<float> lat((size_t)r.n_cand * n_out * TTS_DMODEL);
-      if (int rc = ar_session_latents(c, r.c0, r.n_text, codes_out, r.n_cand, n_mel, lat.data())) return rc;
-      size_t off = 0;
-      for (int b = 0; b < r.n_cand; b++) {
-        std::copy(lat.begin() + (size_t)b * n_out * TTS_DMODEL, lat.begin() + ((size_t)b * n_out + rows_out[b]) * TTS_DMODEL, latents_out + off);
-        off += (size_t)rows_out[b] * TTS_DMODEL;
-      }
-    }
-    session_release(s, request);
-    return (int)TTS_OK;
-  });
+  return guarded(c, [&] { return ar_drv_collect(c, request, codes_out, rows_out, latents_out, steps_out, stopped_out); });
 }
-
 int tts_ar_session_logits(tts_ctx *c, int request, float *logits_out) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_logits");
   if (!logits_out) return fail(c, TTS_ERR_ARG, "tts_ar_session_logits: null output");
-  auto it = c->session->reqs.find(request);
-  if (it == c->session->reqs.end()) return fail(c, TTS_ERR_ARG, "tts_ar_session_logits: no request %d", request);
-  return guarded(c, [&] { return ar_session_logits(c, it->second.c0, it->second.n_cand, logits_out); });
+  return guarded(c, [&] { return ar_drv_logits(c, request, logits_out); });
 }
-
 int tts_ar_session_cancel(tts_ctx *c, int request) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_cancel");
-  if (!c->session->reqs.count(request)) return fail(c, TTS_ERR_ARG, "tts_ar_session_cancel: no request %d", request);
-  session_release(*c->session, request);
-  return TTS_OK;
+  return guarded(c, [&] { return ar_drv_cancel(c, request); });
 }
-
 int tts_ar_session_enable_audio(tts_ctx *c, int stride_steps) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_enable_audio");
-  ArSession &s = *c->session;
   if (stride_steps < 1) return fail(c, TTS_ERR_ARG, "tts_ar_session_enable_audio: stride_steps %d: >= 1", stride_steps);
   if (!c->hifigan) return fail(c, TTS_ERR_STATE, "tts_ar_session_enable_audio: tts_load_hifigan not called");
-  if (s.next_id > 0) return fail(c, TTS_ERR_STATE, "tts_ar_session_enable_audio: the session has admitted a request (call it right after tts_ar_session_open)");
-  if (s.ggml_lut) return fail(c, TTS_ERR_STATE, "tts_ar_session_enable_audio: the session runs under ggml_lut = 1, whose latent pass has no incremental form");
-  return guarded(c, [&] {
-    SessionOptions opt(c, s);
-    if (int rc = ar_session_audio_enable(c, s.max_steps)) return rc;
-    s.audio_stride = stride_steps;
-    return (int)TTS_OK;
-  });
+  return guarded(c, [&] { return ar_drv_enable_audio(c, stride_steps); });
 }
-
 int tts_ar_session_audio(tts_ctx *c, int request, float *out, int cap_samples, int32_t *is_last) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_session_audio");
-  ArSession &s = *c->session;
-  if (!s.audio_stride) return fail(c, TTS_ERR_STATE, "tts_ar_session_audio: tts_ar_session_enable_audio not called");
-  auto it = s.reqs.find(request);
-  if (it == s.reqs.end()) return fail(c, TTS_ERR_ARG, "tts_ar_session_audio: no request %d", request);
-  SessionRequest &r = it->second;
-  if (!r.audio) return fail(c, TTS_ERR_ARG, "tts_ar_session_audio: request %d has %d candidates (several candidates are re-ranked and cannot stream)", request, r.n_cand);
-  if (cap_samples < 0 || (cap_samples > 0 && !out) || !is_last) return fail(c, TTS_ERR_ARG, "tts_ar_session_audio: bad argument");
-  return guarded(c, [&] {
-    const size_t n = std::min(r.pcm.size(), (size_t)cap_samples) / 256 * 256; // whole frames
-    std::copy(r.pcm.begin(), r.pcm.begin() + n, out);
-    r.pcm.erase(r.pcm.begin(), r.pcm.begin() + n);
-    *is_last = (r.audio_done && r.pcm.empty()) ? 1 : 0;
-    return (int)n;
-  });
+  return guarded(c, [&] { return ar_drv_audio(c, request, out, cap_samples, is_last); });
 }
 
 // ---- diffusion session: the entry points (state and device work: diffusion.hip; descriptor checks: host_logic.cpp) ----

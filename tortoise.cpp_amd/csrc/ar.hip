@@ -2499,12 +2499,12 @@ int ar_stream_reserve(tts_ctx *ctx, int n_mel) {
 int ar_graph_captures(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->graph_captures : 0; }
 
 // ---------------------------------------------------------------------------------------------
-// Sessions (tts_ar_session_*): the device side. The book of slots and requests is the caller's (api.cpp); here a session is a batch of n_slots rows whose
+// Sessions (tts_ar_session_*): the device side. The book of slots and requests is the caller's (ar_driver.cpp); here a session is a batch of n_slots rows whose
 // caches hold max_text + 2 + max_steps + 1 positions, every row at its own step (ArState::session).
 // ---------------------------------------------------------------------------------------------
-// A control table entry from the controls the context holds at the moment (the caller has put the session's or the request's there).
-static int4 control_entry(const tts_ctx *ctx) {
-  return make_int4(pf_min_for(ctx->ar_sp.top_k), (int)__builtin_bit_cast(uint32_t, ctx->ar_sp.penalty), ctx->ar_penalty_scope, 0);
+// A control table entry: what the penalising prefilter reads of one row's sampler controls.
+static int4 control_entry(const SamplerParams &sp, int scope) {
+  return make_int4(pf_min_for(sp.top_k), (int)__builtin_bit_cast(uint32_t, sp.penalty), scope, 0);
 }
 static void hist_reset_row(uint32_t *hb) { // what a begin leaves: ids 1 and 8192 (the prompt-shaped penalty row of step 0)
   std::fill(hb, hb + TTS_HIST_WORDS, 0u);
@@ -2543,7 +2543,7 @@ int ar_session_open(tts_ctx *ctx, int n_slots, int max_cand, int max_text, int m
   st->hist_dev_valid = false; // (a later tts_ar_begin* starts from its own host copy)
   if (rows) { // the control table, padded to whole tiles: every row starts under the session's own controls (a valid entry; every admission writes its own)
     TTS_HIP(ctx, st->ctl.reserve((size_t)Bpad * sizeof(int4)));
-    const std::vector<int4> own((size_t)Bpad, control_entry(ctx));
+    const std::vector<int4> own((size_t)Bpad, control_entry(ctx->ar_sp, ctx->ar_penalty_scope));
     TTS_HIP(ctx, hipMemcpy(st->ctl.p, own.data(), own.size() * sizeof(int4), hipMemcpyHostToDevice));
   }
   const int lat_rows = max_cand * 502, S_max = std::min(1024, 1 + max_text + 502);
@@ -2593,12 +2593,12 @@ int ar_session_prompt(tts_ctx *ctx, int c0, int n_cand, const int32_t *text_ids,
   return TTS_OK;
 }
 
-// Rows [c0, c0 + n) of a rows session's control table take the controls the context holds (the caller has put the request's there at its admission):
-// written between two steps, outside the graph, as ar_session_prompt resets the history rows.
-int ar_session_controls(tts_ctx *ctx, int c0, int n) {
+// Rows [c0, c0 + n) of a rows session's control table take a request's controls at its admission: written between two steps, outside the graph, as
+// ar_session_prompt resets the history rows.
+int ar_session_controls(tts_ctx *ctx, int c0, int n, const SamplerParams &sp, int scope) {
   ArState *st = ctx->ar;
   if (!st || !st->session || !st->rows || c0 < 0 || n < 1 || c0 + n > st->B) return fail(ctx, TTS_ERR_STATE, "ar_session_controls: no session with per-row controls, or rows outside it");
-  const std::vector<int4> e((size_t)n, control_entry(ctx));
+  const std::vector<int4> e((size_t)n, control_entry(sp, scope));
   TTS_HIP(ctx, hipMemcpy(st->ctl.as<int4>() + c0, e.data(), e.size() * sizeof(int4), hipMemcpyHostToDevice));
   return TTS_OK;
 }

@@ -94,7 +94,7 @@ struct HifiganState;
 struct Tokenizer;
 struct SamplerPool;
 void sampler_pool_free(SamplerPool *p);
-struct ArSession; // the book of an open session (tts_ar_session_*): api.cpp
+struct ArSession; // the book of an open session (tts_ar_session_*): ar_driver.cpp
 struct DiffSession; // an open diffusion session (tts_diff_session_*): diffusion.hip
 // One request's share of an incremental latent pass (ar.hip: ar_session_extend): the rows [have, upto) of the request in slot `slot`, whose prompt has n_text
 // ids; codes502: the pass' input row by row (8192, then the sampled codes).
@@ -336,13 +336,13 @@ struct Tokenizer {
   std::vector<int> encode(const std::string &message) const;
 };
 // `gen`: the generator the uniforms are drawn from, two per candidate in candidate order. The context's own (ctx->generator) is consumed as a shard of the declared
-// batch (rng_shard_*); any other generator (a session request's) as a whole stream of its own.
-void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const float *logits, const int32_t *ids, int ids_per_cand, int B,
+// batch (rng_shard_*); any other generator (a session request's) as a whole stream of its own. `sp`: the controls every candidate of the call is sampled under.
+void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const SamplerParams &sp, const float *logits, const int32_t *ids, int ids_per_cand, int B,
                        int32_t *out);
 // The penalty ids of candidate c. Called from the sampler pool's threads, except by sample_candidates_list with already_penalised (only its serial
 // full-row fallback asks, so the callee may build the ids on demand into one scratch buffer).
 using PenaltyIdsFn = std::function<void(int c, const int32_t *&ids, int &n_ids)>;
-void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const float *logits, const PenaltyIdsFn &ids_of, int B, int32_t *out);
+void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const SamplerParams &sp, const float *logits, const PenaltyIdsFn &ids_of, int B, int32_t *out);
 // Device top-k prefilter of the decode step (ar.hip: sample_prefilter_kernel; option "device_topk"): per candidate TTS_PF_WORDS
 // 32-bit words {n, 0, 0, 0, idx[TTS_PF_MAX], logit bits[TTS_PF_MAX]} = every logit >= a threshold that keeps TTS_PF_MIN..TTS_PF_MAX
 // of the 8194, in index order (n = -1: no such threshold, the host samples from the full row). The window's lower bound follows the sampler's top-k
@@ -351,9 +351,10 @@ void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const float *logits, con
 // TTS_HIST_WORDS 32-bit words (bit i = id i was fed since tts_ar_begin*, plus 1 and 8192).
 enum { TTS_PF_MIN = 64, TTS_PF_MAX = 128, TTS_PF_WORDS = 4 + 2 * TTS_PF_MAX, TTS_PF_SLACK = TTS_PF_MIN - 50, TTS_PF_TOPK_MAX = 100, TTS_HIST_WORDS = 257 };
 inline int pf_min_for(int top_k) { return top_k <= TTS_PF_TOPK_MAX ? top_k + TTS_PF_SLACK : TTS_PF_MAX + 1; } // a bound above TTS_PF_MAX: the kernel writes n = -1 for every candidate
-int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
+int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const SamplerParams &sp, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
                            const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired = nullptr);
-int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const int32_t *lists, const PenaltyIdsFn &ids_of, bool already_penalised, int B, int32_t *out,
+int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const SamplerParams &sp, const int32_t *lists, const PenaltyIdsFn &ids_of, bool already_penalised, int B,
+                           int32_t *out,
                            const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired = nullptr);
 int host_prefilter_row(const float *row, int keep, int32_t *list);
 int sample_one_row(const float *row, const int32_t *ids, int ids_per_cand, float uniform);
@@ -402,9 +403,39 @@ int rel_bucket(int i, int c);
 // stage entry points implemented in the .hip files
 int ar_load(tts_ctx *ctx, const char *path);
 void ar_free(ArState *);
+int ar_begin(tts_ctx *, const int32_t *, int, const float *, int, int);
+int ar_begin_groups(tts_ctx *, const int32_t *, const int *, int, const float *, int n_voices, const int *voice_of, const int *, int);
+int ar_prefill(tts_ctx *, float *);
+int ar_step(tts_ctx *, const int32_t *, int, float *, int mode);
+int ar_batch(const tts_ctx *);
+int ar_layers(const tts_ctx *);
+float *ar_host_logits(tts_ctx *);
+const int32_t *ar_host_lists(tts_ctx *);
+const float *ar_fetch_logits_row(tts_ctx *, int);
+void ar_history_ids(const tts_ctx *, int c, std::vector<int32_t> &out);
+int ar_latents(tts_ctx *, const int32_t *, int, int, float *);
+int ar_latents_group(tts_ctx *, int, const int32_t *, int, float *);
+int ar_stream_reserve(tts_ctx *, int n_mel);
+int ar_graph_captures(const tts_ctx *);
+int ar_session_open(tts_ctx *, int n_slots, int max_cand, int max_text, int max_steps, bool rows);
+int ar_session_controls(tts_ctx *, int c0, int n, const SamplerParams &sp, int scope);
+void ar_session_close(tts_ctx *);
+int ar_session_prompt(tts_ctx *, int c0, int n_cand, const int32_t *text_ids, int n_text, const float *voice, float *logits_row);
+int ar_session_step(tts_ctx *, const int32_t *toks, const int32_t *n_past, const int32_t *pos_id, const char *live, int mode);
+int ar_session_recaptures(const tts_ctx *);
+int ar_session_latents(tts_ctx *, int c0, int n_text, const int32_t *codes502, int nb, int n_mel, float *out);
+int ar_session_logits(tts_ctx *, int c0, int n, float *out);
+int ar_session_audio_enable(tts_ctx *, int max_steps);
+int ar_session_audio_prompt(tts_ctx *, int c0, int n_text);
+int ar_session_extend(tts_ctx *, const ArExtendItem *items, int n_items, float *out);
 int diff_load(tts_ctx *ctx, const char *path);
 void diff_free(DiffState *);
+int diff_layers(const tts_ctx *);
+int diff_forward(tts_ctx *, const float *, int, const float *, int, int, float *);
+int diff_sample(tts_ctx *, const float *, const int32_t *, int, int, const float *, int, float *);
+int diff_sample_voices(tts_ctx *, const float *, const int32_t *, int, const float *, int, const int32_t *, int, const float *, int, float *);
 int voc_load(tts_ctx *ctx, const char *path);
+int voc_run(tts_ctx *, const float *, const int32_t *, int, const float *, int, float *);
 // frames of context tts_vocoder_chunk adds on either side of a window; vocoder.hip static_asserts that it covers the receptive field
 // computed from the architecture constants its loader enforces
 #define TTS_VOC_CHUNK_HALO 24
@@ -433,6 +464,59 @@ void diff_session_close(tts_ctx *ctx);
 int diff_session_captures(const tts_ctx *ctx);
 void diff_session_defaults(const tts_ctx *ctx, tts_diff_request *req); // the sampler, eta and k the open session pinned
 int diff_set_cond_latent(tts_ctx *ctx, const float *latent2048); // diffusion.hip: overrides the weight file's diffusion_conditioning_latent
+
+// ---- the AR request driver (ar_driver.cpp; its device-free rules: ar_rules.cpp): autoregressive(), main.cpp:5042-5367, stated once for the single calls,
+// tts_hifigan_stream and the sessions ----
+// One request's run through the decode loop: G prompt groups sampled under one set of controls. tts_autoregressive* drives one of these over ar_step, a session
+// a map of them (one group each) over ar_session_step.
+struct ArRun {
+  ArStopBook book;
+  std::vector<int32_t> samples; // the tokens the next step feeds (after ArStopBook::step)
+  std::vector<int32_t> stop_at; // the stop schedule, one iteration per candidate (empty: none; read only under TTS_AR_MASK_STOP | TTS_AR_RETIRE)
+  SamplerParams sp;
+  int scope = 0, max_steps = 0;
+  bool mask_stop = false, retire = false; // TTS_AR_MASK_STOP, TTS_AR_RETIRE
+  int i = 0;                    // iterations applied so far
+  int state = 0;                // 0 running, 1 finished, 2 max_steps reached in strict mode ("no stop token within %d steps")
+  void init(const int *n_cand, int G, const SamplerParams &p, int penalty_scope, int steps, unsigned flags, const int32_t *stops);
+  // One iteration from `samples` on: the stop rule, the counter, the loop's two exits.
+  void advance();
+};
+// What a candidate's sequence becomes: cut at 500 codes, apply_padding, trim_latents' row count. seq [n] -> codes_out [n][502], rows_out [n], stopped [n] or null
+// (1 = the sequence ends with the stop token, 0 = it was cut at max_steps); returns the largest row count.
+int ar_finish_codes(const std::vector<int> *seq, int n, int32_t *codes_out, int32_t *rows_out, int32_t *stopped);
+// The audio book of a one-candidate request (tts_hifigan_stream, a session with audio): a latent row is frozen once audio has been decoded from it.
+struct ArStreamBook {
+  int have = 0, emitted = 0; // latent rows held, frames decoded so far
+  std::vector<float> lat;    // [have][1024]
+  // What the sequence so far makes due. After k sampled codes (none the stop token) the rows stream_final_rows(k) are final and the frames below
+  // tts_diffusion_frames(rows) - TTS_HFG_HALO_FRAMES with them; a finished sequence (`last`) keeps ar_finish_codes' rows and is decoded to its end.
+  // 1: codes502 is the latent pass' input, rows [have, L) and frames [emitted, upto) are due (`last`: either range may be empty); 0: nothing new;
+  // TTS_ERR_STATE, text in `why`: more rows were declared final than the finished utterance keeps.
+  int due(const std::vector<int> &seq, bool last, std::vector<int32_t> &codes502, int &L, int &upto, std::string &why) const;
+};
+int session_first_fit(const uint8_t *busy, int n_slots, int n_cand); // first fit: the first index of the lowest run of n_cand free slots, or -1
+// the entry points; api.cpp has checked what needs no session state and wraps each call in `guarded`
+int ar_drv_step_sample(tts_ctx *ctx, const int32_t *prev, int i, unsigned flags, int32_t *samples_out);
+// stride_codes > 0: tts_hifigan_stream (one candidate), audio to cb(user, ...) while the loop goes on
+int ar_drv_autoregressive(tts_ctx *ctx, const int32_t *text_ids, const int *n_text, int G, const float *voice, int n_voices, const int *voice_of, const int *n_cand,
+                          int max_steps, unsigned flags, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out, int stride_codes = 0,
+                          tts_audio_cb cb = nullptr, void *user = nullptr);
+int ar_drv_open(tts_ctx *ctx, int n_slots, int max_cand, int max_text, int max_steps, unsigned flags);
+void ar_drv_close(tts_ctx *ctx);
+int ar_drv_room(const tts_ctx *ctx);
+void ar_drv_limits(const tts_ctx *ctx, int &max_cand, int &max_steps);
+void ar_drv_defaults(const tts_ctx *ctx, tts_ar_request *req); // the sampler controls the open session pinned
+// fn: the caller's name in the messages. sp null: the session's controls; max_steps 0: the session's.
+int ar_drv_admit(tts_ctx *ctx, const char *fn, const int32_t *text_ids, int n_text, const float *voice, int n_cand, uint32_t seed, const int32_t *stop_at,
+                 const SamplerParams *sp, int scope, int max_steps);
+int ar_drv_step(tts_ctx *ctx);
+int ar_drv_finished(tts_ctx *ctx, int32_t *ids_out, int cap);
+int ar_drv_collect(tts_ctx *ctx, int request, int32_t *codes_out, int32_t *rows_out, float *latents_out, int32_t *steps_out, int32_t *stopped_out);
+int ar_drv_logits(tts_ctx *ctx, int request, float *logits_out);
+int ar_drv_cancel(tts_ctx *ctx, int request);
+int ar_drv_enable_audio(tts_ctx *ctx, int stride_steps);
+int ar_drv_audio(tts_ctx *ctx, int request, float *out, int cap_samples, int32_t *is_last);
 int voice_enc_load(tts_ctx *ctx, const char *path);
 void voice_enc_free(VoiceEncState *);
 int voice_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out1024);

@@ -654,20 +654,19 @@ static void run_on_pool(tts_ctx *ctx, int B, const std::function<void(int)> &one
   ctx->sampler_pool->run(B, one);
 }
 
-void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const float *logits, const PenaltyIdsFn &ids_of, int B, int32_t *out) {
+void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const SamplerParams &sp, const float *logits, const PenaltyIdsFn &ids_of, int B, int32_t *out) {
   const int V = TTS_VOCAB_MEL;
   std::vector<float> samples;
   draw_uniforms(ctx, gen, B, samples);
-  const SamplerParams sp = ctx->ar_sp;
   run_on_pool(ctx, B, [&](int c) {
     const int32_t *ids = nullptr; int n_ids = 0;
     ids_of(c, ids, n_ids);
     out[c] = sample_one(logits + (size_t)c * V, ids, n_ids, samples[c], sp);
   });
 }
-void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const float *logits, const int32_t *ids, int ids_per_cand, int B,
+void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const SamplerParams &sp, const float *logits, const int32_t *ids, int ids_per_cand, int B,
                        int32_t *out) {
-  sample_candidates(ctx, gen, logits, [&](int c, const int32_t *&p, int &n) { p = ids + (size_t)c * ids_per_cand; n = ids_per_cand; }, B, out);
+  sample_candidates(ctx, gen, sp, logits, [&](int c, const int32_t *&p, int &n) { p = ids + (size_t)c * ids_per_cand; n = ids_per_cand; }, B, out);
 }
 
 // The decode loop's sampler over the device prefilter's lists (ar.hip: [B][TTS_PF_WORDS] = {n, 0, 0, 0, idx[128], value[128]}), same
@@ -677,11 +676,10 @@ void sample_candidates(tts_ctx *ctx, std::mt19937 &gen, const float *logits, con
 // `retired` (may be null): candidates whose sequence has ended (TTS_AR_RETIRE). Their uniforms are drawn like everybody's — the stream stays the reference's — but
 // nothing is sampled for them (out = 8193): round 5's ragged bench pass spent 27 ms per utterance evaluating lists and fetching full logits rows for candidates whose
 // sample the loop then threw away.
-int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const int32_t *lists, const PenaltyIdsFn &ids_of, bool already_penalised, int B, int32_t *out,
-                           const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired) {
+int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const SamplerParams &sp, const int32_t *lists, const PenaltyIdsFn &ids_of, bool already_penalised, int B,
+                           int32_t *out, const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired) {
   std::vector<float> samples;
   draw_uniforms(ctx, gen, B, samples);
-  const SamplerParams sp = ctx->ar_sp;
   auto one = [&](int c) {
     if (retired && retired[c]) { out[c] = 8193; return; }
     const int32_t *l = lists + (size_t)c * TTS_PF_WORDS;
@@ -706,9 +704,9 @@ int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const int32_t *lists
   if (n_fallbacks) *n_fallbacks += fb;
   return 0;
 }
-int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
+int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const SamplerParams &sp, const int32_t *lists, const int32_t *ids, int ids_per_cand, int B, int32_t *out,
                            const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired) {
-  return sample_candidates_list(ctx, gen, lists, [&](int c, const int32_t *&p, int &n) { p = ids + (size_t)c * ids_per_cand; n = ids_per_cand; }, false, B, out,
+  return sample_candidates_list(ctx, gen, sp, lists, [&](int c, const int32_t *&p, int &n) { p = ids + (size_t)c * ids_per_cand; n = ids_per_cand; }, false, B, out,
                                 full_row, n_fallbacks, retired);
 }
 
