@@ -18,6 +18,8 @@ def _latents(L, seed):
 # L=100 (T=435): attention tiles that are far from the diagonal and not the tail tile (constant-bias path);
 # L=250 (T=1088): the 1024-thread GroupNorm path (T > 896) and several query blocks per sequence;
 # L=500 (T=2176): the largest sequence the AR stage can produce (500 latent rows)
+# These lengths reach two of the three GroupNorm classes, and only through the whole network's 1e-3 gate: the one-pass kernel (T > 2304) is not run here, and
+# no length sits on a sweep boundary. tests/test_gn_kernels_gpu.py launches every GroupNorm kernel directly, the third class and the boundary lengths included.
 @pytest.mark.parametrize("models,L,timestep", [("small", 12, 3999), ("small", 43, 51), ("mid", 43, 2025), ("small", 1, 0),
                                                ("small", 100, 1000), ("small", 250, 500), ("small", 500, 100)])
 @pytest.mark.parametrize("cond_free", [False, True])
