@@ -1,4 +1,4 @@
-"""GPU: the DDIM sampler of the diffusion stage (options "diff_sampler" = 1, "ddim_eta", "cond_free_k"; diffusion.hip: ddim_update_kernel).
+"""GPU: the DDIM sampler of the diffusion stage (options "diff_sampler" = 1, "ddim_eta", "cond_free_k"; diffusion.hip: step_update_kernel, ddim_step_value).
 
 The reference and the oracle have no DDIM. The yardstick is a host-driven loop over the engine's own network: per step two tts_diffusion_forward calls (conditioned and
 conditioning-free) at the step's timestep, then the numpy float32 restatement of the update (tests/test_ddim_cpu.py: ddim_update, pinned there on a hand-checkable

@@ -173,7 +173,7 @@ struct tts_ctx {
   int attn_q64 = 0; // option "attn_q64": diffusion attention with 64-query workgroups: 0 never (default: measured, no gain), 1 always, 2 = when the 128-query grid has at most 256 workgroups (bit-identical)
   int hoist_integrator = 1; // option "hoist_integrator": small diffusion batches evaluate the conditioning_timestep_integrator layers (which never see x_t) for all sampling steps before the loop, in benchmark-sized batches (bit-identical; 0 = inside every step)
   int latency_mode = 0;    // option "latency_mode": small diffusion batches (<= 2 048 packed rows) take the GroupNorm statistics from the producing GEMM's epilogue (diffusion.hip: gn_apply_kernel); not bit-identical to the batch path
-  int diff_sampler = 0;    // option "diff_sampler": 0 = the reference's ancestral DDPM step (ddpm_update_kernel), 1 = DDIM (ddim_update_kernel; upstream tortoise-tts' ddim_sample)
+  int diff_sampler = 0;    // option "diff_sampler": 0 = the reference's ancestral DDPM step (step_update_kernel: ddpm_step_value), 1 = DDIM (ddim_step_value; upstream tortoise-tts' ddim_sample)
   double ddim_eta = 0;     // option "ddim_eta" in [0, 1]: 0 = deterministic DDIM (only x_T is noise); read only when diff_sampler = 1
   float cond_free_k = 2.0f; // option "cond_free_k": the conditioning-free guidance strength at t = n (main.cpp's base_k = 2.0), both samplers
   bool capturing = false;  // a hipGraph is being captured on the stream: ProfScope records nothing (event records would become graph nodes)

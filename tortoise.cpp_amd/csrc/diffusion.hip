@@ -222,11 +222,6 @@ __global__ __launch_bounds__(256) void gather_f32_kernel(const float *__restrict
   if (sr >= 0) v = *(const float4 *)(x + (size_t)sr * C + c);
   *(float4 *)(y + (size_t)r * C + c) = v;
 }
-// The current sampling step's slice of a per-step array (the hoisted integrator's code-embedding operand) -> the fixed address the step's kernels read.
-__global__ __launch_bounds__(256) void select_step_slice_kernel(const uint4 *__restrict__ all, size_t n16_per_step, const int *__restrict__ ctr, uint4 *__restrict__ dst) {
-  const uint4 *src = all + (size_t)(*ctr) * n16_per_step;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16_per_step; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
 
 // Multi-head attention with T5 relative-position bias (AttentionBlock, main.cpp:3232-3275).
 // One block = 128 queries of one (sequence, head): 4 waves x 32 queries; keys stream through a double
@@ -702,21 +697,6 @@ __global__ __launch_bounds__(256) void build_code_emb_kernel(const float *__rest
   *(float4 *)(out + (size_t)r * C + c) = v;
 }
 
-// x_t [cand][100][T] (f32, reference layout) -> fp16 GEMM operand rows [row][128] for the conditioned
-// and the unconditioned copy of the sequence. grid: rows of the cond sequences; block 128.
-__global__ __launch_bounds__(128) void xt_to_rows_kernel(const float *__restrict__ x, const int64_t *__restrict__ x_off,
-                                                         const int *__restrict__ row_seq, const int *__restrict__ row_t,
-                                                         const int *__restrict__ seq_len, const int *__restrict__ seq_start,
-                                                         int ncand, int has_uncond, __half *__restrict__ xt16) {
-  const int r = blockIdx.x, s = row_seq[r], ch = threadIdx.x;
-  if (s < 0 || s >= ncand) return;
-  const int T = seq_len[s], t = row_t[r];
-  float v = (ch < 100) ? x[x_off[s] + (size_t)ch * T + t] : 0.f;
-  const __half hv = __float2half_rn(v);
-  xt16[(size_t)r * XTC + ch] = hv;
-  if (has_uncond) xt16[(size_t)(seq_start[s + ncand] + t) * XTC + ch] = hv;
-}
-
 // Philox4x32-10 + Box-Muller (device noise mode).
 __device__ __forceinline__ void philox_round(uint32_t &c0, uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t k0, uint32_t k1) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
@@ -739,23 +719,14 @@ __device__ __forceinline__ float philox_normal(uint64_t seed, uint32_t stream, u
   return (idx & 1) ? rad * sn : rad * cs;
 }
 
-// Ancestral sampling step (main.cpp:5970-6030) for every candidate, in place on x [cand][100][T].
-// net: [rows][256] f32 (channels 0..99 eps, 100..199 variance logits). grid: cond rows; block 128.
+// The scalars of the ancestral sampling step (main.cpp:5970-6030).
 struct StepScalars { float max_log, min_log, cfk, sqrt_recip, sqrt_recipm1, coef1, coef2; int is_last; };
 // Everything of a sampling step that the reference keeps in host variables lives in a device table indexed by a device-side step
 // counter, so that ONE captured hipGraph of the step can be replayed for every step (main.cpp:5723-6033 rebuilds and re-uploads
 // its graph 160 times): the schedule scalars, the noise block of the step, the generator key.
 struct StepEntry { StepScalars sc; int has_noise; long long noise_off; unsigned philox_step; unsigned pad; };
 
-// Copies this step's [n_res][scale | shift] block to the fixed address the GroupNorm kernels read. grid: any, block 256.
-__global__ __launch_bounds__(256) void step_begin_kernel(const float *__restrict__ ss_all, size_t ss_stride, const int *__restrict__ ctr,
-                                                         float *__restrict__ ss_cur) {
-  const float4 *src = (const float4 *)(ss_all + (size_t)(*ctr) * ss_stride);
-  float4 *dst = (float4 *)ss_cur;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < ss_stride / 4; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
-__global__ void step_advance_kernel(int *ctr) { *ctr += 1; }
-// The arithmetic of one element of the ancestral step: ONE body for ddpm_update_kernel and the session's diff_session_update_kernel.
+// The arithmetic of one element of the ancestral step: the ancestral half of step_update_kernel.
 // Every f32 operation below is the reference's, one rounding each (main.cpp:5970-6030 is plain C++ built without FMA contraction; the oracle's copy is compiled with
 // -ffp-contract=off). hipcc would contract a * b + c * d into FMAs: a last-bit difference in x_t at EVERY step that the torch-f32 yardstick of the parity floor (which
 // shares the oracle's update) does not have, and that a chaotic 80- / 200-step loop amplifies like any other f32 difference (round 6: the 200-step loop at full depth
@@ -781,7 +752,9 @@ __device__ __forceinline__ float ddpm_step_value(const StepScalars &sc, float ep
   }
   return outv;
 }
-// The same for the DDIM step (see ddim_update_kernel): the learned variance is not read.
+// The same for the DDIM step (upstream tortoise-tts ddim_sample on p_mean_variance with clip_denoised; the reference has no such sampler): the StepEntry of the
+// ancestral step (guidance k, sqrt_recip, sqrt_recipm1, noise block, generator key) plus this step's DdimEntry. The learned variance is not read. Every f32 operation
+// is rounded once, for the reason above: the numpy restatement the tests hold this to performs exactly these roundings.
 struct DdimEntry { float c_x0, c_eps, sigma, pad; };
 __device__ __forceinline__ float ddim_step_value(const StepScalars &sc, const DdimEntry &d, float eps_c, float eps_u, float xv, const float *__restrict__ noise, size_t xi,
                                                  uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
@@ -801,84 +774,44 @@ __device__ __forceinline__ float ddim_step_value(const StepScalars &sc, const Dd
   }
   return outv;
 }
-__global__ __launch_bounds__(128) void ddpm_update_kernel(const float *__restrict__ net, float *__restrict__ x,
-                                                          const int64_t *__restrict__ x_off, const int *__restrict__ row_seq,
-                                                          const int *__restrict__ row_t, const int *__restrict__ seq_len,
-                                                          const int *__restrict__ seq_start, int ncand, const StepEntry *__restrict__ tab,
-                                                          const int *__restrict__ ctr, const float *__restrict__ noise_base /* or null */,
-                                                          uint64_t seed, uint32_t stream0 /* global id of candidate 0 */) {
-  const int r = blockIdx.x, s = row_seq[r], ch = threadIdx.x;
-  if (s < 0 || s >= ncand || ch >= 100) return;
-  const StepEntry e = tab[*ctr];
-  const float *noise = e.has_noise ? noise_base + e.noise_off : nullptr; // same layout as x
-  const int T = seq_len[s], t = row_t[r];
-  const size_t xi = x_off[s] + (size_t)ch * T + t;
-  const float eps_c = net[(size_t)r * 256 + ch], var_c = net[(size_t)r * 256 + 100 + ch];
-  const float eps_u = net[(size_t)(seq_start[s + ncand] + t) * 256 + ch];
-  x[xi] = ddpm_step_value(e.sc, eps_c, var_c, eps_u, x[xi], noise, xi, seed, stream0 + (uint32_t)s, e.philox_step, (uint32_t)(ch * T + t));
-}
 
-// DDIM step (upstream tortoise-tts ddim_sample on p_mean_variance with clip_denoised; the reference has no such sampler) for every candidate, in place on x: the grid,
-// block and indexing of ddpm_update_kernel, the same StepEntry (guidance k, sqrt_recip, sqrt_recipm1, noise block, generator key) plus this step's DdimEntry.
-// Channels 100..199 of net (the learned variance) are not read. Every f32 operation is rounded once (no FMA contraction), for the reason ddpm_update_kernel gives:
-// the numpy restatement the tests hold this kernel to performs exactly these roundings.
-__global__ __launch_bounds__(128) void ddim_update_kernel(const float *__restrict__ net, float *__restrict__ x,
-                                                          const int64_t *__restrict__ x_off, const int *__restrict__ row_seq,
-                                                          const int *__restrict__ row_t, const int *__restrict__ seq_len,
-                                                          const int *__restrict__ seq_start, int ncand, const StepEntry *__restrict__ tab,
-                                                          const DdimEntry *__restrict__ dtab, const int *__restrict__ ctr,
-                                                          const float *__restrict__ noise_base /* or null */, uint64_t seed,
-                                                          uint32_t stream0 /* global id of candidate 0 */) {
-  const int r = blockIdx.x, s = row_seq[r], ch = threadIdx.x;
-  if (s < 0 || s >= ncand || ch >= 100) return;
-  const int k = *ctr;
-  const StepEntry e = tab[k];
-  const DdimEntry d = dtab[k];
-  const float *noise = e.has_noise ? noise_base + e.noise_off : nullptr; // same layout as x
-  const int T = seq_len[s], t = row_t[r];
-  const size_t xi = x_off[s] + (size_t)ch * T + t;
-  const float eps_c = net[(size_t)r * 256 + ch];
-  const float eps_u = net[(size_t)(seq_start[s + ncand] + t) * 256 + ch];
-  x[xi] = ddim_step_value(e.sc, d, eps_c, eps_u, x[xi], noise, xi, seed, stream0 + (uint32_t)s, e.philox_step, (uint32_t)(ch * T + t));
-}
-
-// ---- diffusion session (tts_diff_session_*): one packed layout whose sequences belong to different requests, each at a step of its own ----
-// What the step's kernels read of one request, by its slot: everything was computed at admission for the request alone and lives in storage the request owns.
-struct SessReqDev {
+// ---- the sampling step's own kernels: one packed layout whose sequences belong to requests, each request at a step of its own ----
+// tts_diffusion and tts_diffusion_forward run ONE request in slot 0 that owns the whole layout; a diffusion session (tts_diff_session_*) runs up to max_requests.
+// What the kernels read of one request, by its slot: everything was computed for the request alone (prepare_request) and lives in storage the request owns.
+struct ReqDev {
   const float *ss_all;     // [n_steps][n_res][2048]: the request's scale / shift blocks (precompute_time)
   const StepEntry *tab;    // [n_steps]
   const DdimEntry *dtab;   // [n_steps], sampler 1 only
   const __half *ce16_all;  // hoisted integrator: [n_steps][rows_local][1024], else null
-  float *x;                // [cand][100][T_c]
+  float *x;                // [cand][100][T_c] (f32, reference layout)
   const float *noise;      // the request's noise blocks in the layout of x (StepEntry::noise_off), or null: the device generator under `seed`
   unsigned long long seed;
-  int n_steps, sampler, rows_local, pad;
+  int n_steps, sampler, rows_local;
+  unsigned stream_base;    // generator stream of candidate 0 (tts_diffusion: the shard's first global candidate; a session request: 0)
 };
-// Start of a session step. Request live[i] (a slot) copies the scale / shift block of ITS step to block `slot` of ss_cur; seq_step[s], the index of sequence s's
-// block that the GroupNorm kernels add to their ss pointer, is written from the sequence's slot. grid (16, n_live), block 256.
-__global__ __launch_bounds__(256) void diff_session_begin_kernel(const SessReqDev *__restrict__ req, const int *__restrict__ ctr, const int *__restrict__ live,
-                                                                 size_t ss_stride, float *__restrict__ ss_cur, const int *__restrict__ seq_req, int ns,
-                                                                 int *__restrict__ seq_step) {
+// Start of a step. Request live[i] (a slot) copies the scale / shift block of ITS step to block `slot` of ss_cur, the fixed address the GroupNorm kernels read.
+// grid (16, n_live), block 256.
+__global__ __launch_bounds__(256) void step_begin_kernel(const ReqDev *__restrict__ req, const int *__restrict__ ctr, const int *__restrict__ live,
+                                                         size_t ss_stride, float *__restrict__ ss_cur) {
   const int slot = live[blockIdx.y], k = ctr[slot];
-  if (blockIdx.y == 0 && blockIdx.x == 0)
-    for (int s = threadIdx.x; s < ns; s += 256) seq_step[s] = seq_req[s];
   if (k >= req[slot].n_steps) return; // finished: nothing of it is read
   const float4 *src = (const float4 *)(req[slot].ss_all + (size_t)k * ss_stride);
   float4 *dst = (float4 *)(ss_cur + (size_t)slot * ss_stride);
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < ss_stride / 4; i += (size_t)gridDim.x * 256) dst[i] = src[i];
 }
-// End of a session step: the live requests' counters advance, nobody else's. One thread per live request.
-__global__ void diff_session_advance_kernel(const SessReqDev *__restrict__ req, int *__restrict__ ctr, const int *__restrict__ live, int n_live) {
+// End of a step: the live requests' counters advance, nobody else's. One thread per live request.
+__global__ void step_advance_kernel(const ReqDev *__restrict__ req, int *__restrict__ ctr, const int *__restrict__ live, int n_live) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_live) return;
   const int slot = live[i];
   if (ctr[slot] < req[slot].n_steps) ctr[slot] += 1;
 }
-// xt_to_rows_kernel for the session: x of sequence s is its request's, at seq_xoff[s]; the unconditioned copy starts at row seq_partner[s] (-1 marks the
-// unconditioned sequences themselves). grid: rows; block 128.
-__global__ __launch_bounds__(128) void diff_session_xt_kernel(const SessReqDev *__restrict__ req, const int *__restrict__ seq_req, const int64_t *__restrict__ seq_xoff,
-                                                              const int *__restrict__ seq_partner, const int *__restrict__ row_seq, const int *__restrict__ row_t,
-                                                              const int *__restrict__ seq_len, __half *__restrict__ xt16) {
+// x_t -> fp16 GEMM operand rows [row][128] for the conditioned sequence and its unconditioned copy. x of sequence s is its request's, at seq_xoff[s]; the copy
+// starts at row seq_partner[s] (-1 marks the unconditioned sequences themselves; a sequence evaluated alone names its own first row and stores the same value
+// twice). grid: rows; block 128.
+__global__ __launch_bounds__(128) void step_xt_kernel(const ReqDev *__restrict__ req, const int *__restrict__ seq_req, const int64_t *__restrict__ seq_xoff,
+                                                      const int *__restrict__ seq_partner, const int *__restrict__ row_seq, const int *__restrict__ row_t,
+                                                      const int *__restrict__ seq_len, __half *__restrict__ xt16) {
   const int r = blockIdx.x, s = row_seq[r], ch = threadIdx.x;
   if (s < 0) return;
   const int p = seq_partner[s];
@@ -889,33 +822,33 @@ __global__ __launch_bounds__(128) void diff_session_xt_kernel(const SessReqDev *
   xt16[(size_t)r * XTC + ch] = hv;
   xt16[(size_t)(p + t) * XTC + ch] = hv;
 }
-// Row select (the session's select_step_slice_kernel): row r of the joint layout takes row row_src[r] of its own request's hoisted code-embedding operand, at that
-// request's own step. Guard rows: zero, as in the request's buffer. grid: rows; block 128 (one uint4 each).
-__global__ __launch_bounds__(128) void diff_session_row_select_kernel(const SessReqDev *__restrict__ req, const int *__restrict__ ctr, const int *__restrict__ seq_req,
-                                                                      const int *__restrict__ row_seq, const int *__restrict__ row_src, uint4 *__restrict__ dst) {
+// The hoisted integrator's code-embedding operand of this step: row r of the layout takes row row_src[r] of its own request's ce16_all, at that request's own step.
+// Guard rows: zero, as in the request's buffer. grid: rows; block 128 (one uint4 each).
+__global__ __launch_bounds__(128) void step_row_select_kernel(const ReqDev *__restrict__ req, const int *__restrict__ ctr, const int *__restrict__ seq_req,
+                                                              const int *__restrict__ row_seq, const int *__restrict__ row_src, uint4 *__restrict__ dst) {
   const int r = blockIdx.x, s = row_seq[r];
   uint4 v = make_uint4(0u, 0u, 0u, 0u);
   if (s >= 0) {
     const int slot = seq_req[s];
-    const SessReqDev &q = req[slot];
+    const ReqDev &q = req[slot];
     const int k = min(ctr[slot], q.n_steps - 1);
     v = ((const uint4 *)(q.ce16_all + ((size_t)k * q.rows_local + row_src[r]) * C))[threadIdx.x];
   }
   dst[(size_t)r * (C / 8) + threadIdx.x] = v;
 }
-// The sampler update of a session step: per sequence the request's StepEntry / DdimEntry at the request's step, its sampler, its noise block or generator key (the
-// stream is the candidate's index in its request), and the unconditioned partner's first row from a table. Sequences of a request that has run all its steps are
-// left untouched. The arithmetic is ddpm_step_value / ddim_step_value, the bodies of the single call's kernels. grid: rows; block 128.
-__global__ __launch_bounds__(128) void diff_session_update_kernel(const float *__restrict__ net, const SessReqDev *__restrict__ req, const int *__restrict__ ctr,
-                                                                  const int *__restrict__ seq_req, const int64_t *__restrict__ seq_xoff,
-                                                                  const int *__restrict__ seq_partner, const int *__restrict__ seq_cand,
-                                                                  const int *__restrict__ row_seq, const int *__restrict__ row_t, const int *__restrict__ seq_len) {
+// The sampler update, in place on the requests' x. net: [rows][256] f32 (channels 0..99 eps, 100..199 variance logits). Per sequence: the request's StepEntry /
+// DdimEntry at the request's step, its sampler, its noise block or generator key (stream = the request's base + the candidate's index in it), and the unconditioned
+// partner's first row from a table. Sequences of a request that has run all its steps are left untouched. grid: rows; block 128.
+__global__ __launch_bounds__(128) void step_update_kernel(const float *__restrict__ net, const ReqDev *__restrict__ req, const int *__restrict__ ctr,
+                                                          const int *__restrict__ seq_req, const int64_t *__restrict__ seq_xoff,
+                                                          const int *__restrict__ seq_partner, const int *__restrict__ seq_cand,
+                                                          const int *__restrict__ row_seq, const int *__restrict__ row_t, const int *__restrict__ seq_len) {
   const int r = blockIdx.x, s = row_seq[r], ch = threadIdx.x;
   if (s < 0 || ch >= 100) return;
   const int p = seq_partner[s];
   if (p < 0) return;
   const int slot = seq_req[s], k = ctr[slot];
-  const SessReqDev q = req[slot];
+  const ReqDev q = req[slot];
   if (k >= q.n_steps) return;
   const StepEntry e = q.tab[k];
   const float *noise = e.has_noise ? q.noise + e.noise_off : nullptr; // same layout as x
@@ -923,7 +856,7 @@ __global__ __launch_bounds__(128) void diff_session_update_kernel(const float *_
   const size_t xi = seq_xoff[s] + (size_t)ch * T + t;
   const float eps_c = net[(size_t)r * 256 + ch];
   const float eps_u = net[(size_t)(p + t) * 256 + ch];
-  const uint32_t stream = (uint32_t)seq_cand[s], idx = (uint32_t)(ch * T + t);
+  const uint32_t stream = q.stream_base + (uint32_t)seq_cand[s], idx = (uint32_t)(ch * T + t);
   if (q.sampler == 1) {
     const DdimEntry d = q.dtab[k];
     q.x[xi] = ddim_step_value(e.sc, d, eps_c, eps_u, q.x[xi], noise, xi, q.seed, stream, e.philox_step, idx);
@@ -1029,6 +962,14 @@ struct Layout {
   }
 };
 
+// Reserve, then zero the whole buffer when it grew: guard rows and halos of a row buffer are never written, and must read as zero from the first use on.
+static hipError_t reserve_zeroed(DevBuf &b, size_t bytes) {
+  const size_t old = b.cap;
+  hipError_t e = b.reserve(bytes);
+  if (e == hipSuccess && b.cap != old) e = hipMemset(b.p, 0, b.cap);
+  return e;
+}
+
 // Activation workspace for one layout. fp16 GEMM operands carry a 1-row zero halo on both sides (the
 // k=3 taps read rows -1 and `rows`) plus 128 rows of slack for the attention tiles.
 struct Work {
@@ -1043,26 +984,111 @@ struct Work {
   __half *A16() { return a16.as<__half>() + C; }
   __half *ATT16() { return att16.as<__half>() + C; }
   int reserve(tts_ctx *ctx, int r, int ns, bool split = false) { // split: the low-half buffers of the reference-precision AttentionBlock are needed whatever attn_f32 says
-    auto rz = [&](DevBuf &b, size_t bytes) -> hipError_t {
-      size_t old = b.cap;
-      hipError_t e = b.reserve(bytes);
-      if (e == hipSuccess && b.cap != old) e = hipMemset(b.p, 0, b.cap);
-      return e;
-    };
     rows = r;
-    TTS_HIP(ctx, rz(x, (size_t)r * C * 4));
-    TTS_HIP(ctx, rz(hbuf, (size_t)r * C * 4));
-    TTS_HIP(ctx, rz(a16, (size_t)(r + 2) * C * 2));
-    TTS_HIP(ctx, rz(att16, (size_t)(r + 2) * C * 2));
-    TTS_HIP(ctx, rz(qk16, (size_t)(r + 128) * 2048 * 2));
-    TTS_HIP(ctx, rz(vt16, (size_t)C * (r + 128) * 2));
-    TTS_HIP(ctx, rz(stats, (size_t)ns * 32 * sizeof(float2)));
+    TTS_HIP(ctx, reserve_zeroed(x, (size_t)r * C * 4));
+    TTS_HIP(ctx, reserve_zeroed(hbuf, (size_t)r * C * 4));
+    TTS_HIP(ctx, reserve_zeroed(a16, (size_t)(r + 2) * C * 2));
+    TTS_HIP(ctx, reserve_zeroed(att16, (size_t)(r + 2) * C * 2));
+    TTS_HIP(ctx, reserve_zeroed(qk16, (size_t)(r + 128) * 2048 * 2));
+    TTS_HIP(ctx, reserve_zeroed(vt16, (size_t)C * (r + 128) * 2));
+    TTS_HIP(ctx, reserve_zeroed(stats, (size_t)ns * 32 * sizeof(float2)));
     if (ctx->attn_f32 || split) {
-      TTS_HIP(ctx, rz(att16_lo, (size_t)(r + 2) * C * 2));
-      TTS_HIP(ctx, rz(qk16_lo, (size_t)(r + 128) * 2048 * 2));
-      TTS_HIP(ctx, rz(vt16_lo, (size_t)C * (r + 128) * 2));
+      TTS_HIP(ctx, reserve_zeroed(att16_lo, (size_t)(r + 2) * C * 2));
+      TTS_HIP(ctx, reserve_zeroed(qk16_lo, (size_t)(r + 128) * 2048 * 2));
+      TTS_HIP(ctx, reserve_zeroed(vt16_lo, (size_t)C * (r + 128) * 2));
     }
     return TTS_OK;
+  }
+};
+
+// A request of the sampling loop: B candidates of one utterance batch with their own step count, sampler, noise and tables. Everything below is evaluated for the
+// request ALONE by prepare_request and lives in storage the request owns; a step only gathers from it (ReqDev). tts_diffusion keeps one in DiffState across calls
+// (its buffers keep their capacity); tts_diff_session_admit fills a fresh one, and the session's bookkeeping of it rides along.
+struct DiffReq {
+  int n_cand = 0, n_steps = 0, sampler = 0;
+  uint64_t seed = 0;
+  uint32_t stream_base = 0;  // generator stream of candidate 0
+  bool host_noise = false;   // the steps read `noise` (block 0 = x_T, block 1 + idx = step idx), not the device generator
+  bool noise_streamed = false; // `noise` is reserved and nothing of it filled: the caller sends the blocks beside the loop (diff_sample)
+  int n_vec = 0;             // noise vectors per candidate: n_steps + 1, or 1 (deterministic DDIM: x_T alone)
+  std::vector<int> T;        // frames per candidate
+  std::vector<int64_t> xoff; // candidate c's x in `x`
+  int64_t total = 0;
+  DevBuf ce16_all;           // hoisted: [n_steps][src_rows][1024] fp16
+  DevBuf code_emb, h0;       // a session without hoisting: [src_rows][1024] f32 each
+  DevBuf ss_all, tab, dtab, x, noise;
+  std::chrono::steady_clock::time_point t_setup; // TTS_TIMING: when setup_batch had run
+  // the session's share
+  int id = 0, slot = 0, done = 0, cls = 0, packed = 0;
+  bool finished = false;
+  std::vector<int> seq_src;  // per sequence of the request (conditioned 0 .. n_cand - 1, then their unconditioned copies): its first row in the request's row buffers
+  int src_rows = 0;          // rows of those buffers (the request's own packed layout; its integrator layout without hoisting)
+  ReqDev dev() const {
+    return ReqDev{ss_all.as<float>(), tab.as<StepEntry>(), dtab.as<DdimEntry>(), ce16_all.as<__half>(), x.as<float>(), host_noise ? noise.as<float>() : nullptr,
+                  seed, n_steps, sampler, src_rows, stream_base};
+  }
+};
+
+// Everything one sampling step runs on: a packed layout, its workspace and row buffers, the per-slot state, the tables the step's kernels read, and the captured
+// step. Held once by DiffState (tts_diffusion, tts_diffusion_forward: one request in slot 0 that owns the layout) and once by an open DiffSession.
+struct StepBufs {
+  Layout lay;
+  Work wk;
+  DevBuf code_emb, h0, ce, ce16, inp16, xt16, net; // rows of lay
+  DevBuf ss_cur, ctr;                              // per slot: this step's scale / shift block (fixed address) | the device step counter
+  DevBuf tables;                                   // one upload: the pointers below
+  const ReqDev *req = nullptr;                     // by slot
+  const int64_t *seq_xoff = nullptr;
+  const int *seq_req = nullptr, *seq_partner = nullptr, *seq_cand = nullptr, *row_src = nullptr, *live = nullptr; // live: the slots of the running requests
+  int n_live = 0;
+  hipGraph_t step_graph = nullptr;
+  hipGraphExec_t step_exec = nullptr;
+  void drop_step_graph() {
+    if (step_exec) (void)hipGraphExecDestroy(step_exec);
+    if (step_graph) (void)hipGraphDestroy(step_graph);
+    step_exec = nullptr; step_graph = nullptr;
+  }
+  ~StepBufs() { drop_step_graph(); }
+  // the row buffers for a layout of `rows`; integ: the integrator runs inside the step (code embedding in, its f32 output)
+  int reserve_rows(tts_ctx *ctx, size_t rows, bool integ) {
+    TTS_HIP(ctx, reserve_zeroed(ce16, rows * C * 2));
+    TTS_HIP(ctx, reserve_zeroed(inp16, rows * C * 2));
+    TTS_HIP(ctx, reserve_zeroed(xt16, (rows + 2) * XTC * 2));
+    TTS_HIP(ctx, reserve_zeroed(net, rows * 256 * 4));
+    if (integ) {
+      TTS_HIP(ctx, reserve_zeroed(code_emb, rows * C * 4));
+      TTS_HIP(ctx, reserve_zeroed(ce, rows * C * 4));
+    }
+    return TTS_OK;
+  }
+  int set_tables(tts_ctx *ctx, const std::vector<ReqDev> &reqs, const std::vector<int> &slots, const std::vector<int64_t> &xoff, const std::vector<int> &sreq,
+                 const std::vector<int> &partner, const std::vector<int> &cand, const std::vector<int> &rsrc) {
+    std::vector<char> img;
+    auto put = [&](const void *p, size_t bytes) { const size_t o = img.size(); img.insert(img.end(), (const char *)p, (const char *)p + bytes); return o; };
+    const size_t o_req = put(reqs.data(), reqs.size() * sizeof(ReqDev)), o_xoff = put(xoff.data(), xoff.size() * 8); // the 8-byte items first
+    const size_t o_sreq = put(sreq.data(), sreq.size() * 4), o_partner = put(partner.data(), partner.size() * 4), o_cand = put(cand.data(), cand.size() * 4);
+    const size_t o_rsrc = put(rsrc.data(), rsrc.size() * 4), o_live = put(slots.data(), slots.size() * 4);
+    TTS_HIP(ctx, tables.reserve(img.size()));
+    TTS_HIP(ctx, hipMemcpy(tables.p, img.data(), img.size(), hipMemcpyHostToDevice));
+    const char *b = tables.as<char>();
+    req = (const ReqDev *)(b + o_req); seq_xoff = (const int64_t *)(b + o_xoff);
+    seq_req = (const int *)(b + o_sreq); seq_partner = (const int *)(b + o_partner); seq_cand = (const int *)(b + o_cand);
+    row_src = (const int *)(b + o_rsrc); live = (const int *)(b + o_live);
+    n_live = (int)slots.size();
+    return TTS_OK;
+  }
+  // One request in slot 0 that owns the layout: its candidates' sequences, then (tts_diffusion) their unconditioned copies; every row takes its own row of the
+  // request's buffers. A layout without copies (tts_diffusion_forward: one branch) names each sequence as its own partner.
+  int set_single(tts_ctx *ctx, const DiffReq &r) {
+    const int B = r.n_cand;
+    std::vector<int> sreq(lay.ns, 0), partner(lay.ns, -1), cand(lay.ns), rsrc(lay.rows, -1);
+    std::vector<int64_t> xoff(lay.ns);
+    for (int s = 0; s < lay.ns; s++) {
+      cand[s] = s; xoff[s] = r.xoff[s % B];
+      if (s < B) partner[s] = lay.start[lay.ns == B ? s : s + B];
+      for (int t = 0; t < lay.len[s]; t++) rsrc[lay.start[s] + t] = lay.start[s] + t;
+    }
+    return set_tables(ctx, {r.dev()}, {0}, xoff, sreq, partner, cand, rsrc);
   }
 };
 
@@ -1076,22 +1102,24 @@ struct DiffState {
   __half *lc_w = nullptr, *inp_w = nullptr, *integ_w = nullptr, *out_w = nullptr;
   std::vector<void *> owned;
   // run state
-  Layout lay, lat_lay, ilay;
-  Work wk, lat_wk, iwk;
+  StepBufs sb;  // the single call's step: layout `sb.lay` of the candidates' sequences and their unconditioned copies
+  DiffReq req;  // ... and its one request
+  Layout lat_lay, ilay;
+  Work lat_wk, iwk;
   // The conditioning_timestep_integrator stage sees only (code embedding, timestep): for the unconditioned branch its
   // input is the same vector at every position, so unconditioned sequences of equal length give identical results. With
   // share_integ the stage runs on ilay = [conditioned sequences | one unconditioned sequence per distinct length] and
   // its output rows are gathered into the full layout (ce_src: source row per row of `lay`).
   bool share_integ = false;
   DevBuf ce_src, iseq_src;
-  DevBuf h0; // in_layers of the first integrator ResBlock applied to the code embedding: the same at every step
+  // (sb.h0: in_layers of the first integrator ResBlock applied to the code embedding, the same at every step)
   // Hoisted integrator (round 6, small batches): the conditioning_timestep_integrator layers see only (code embedding, timestep) — never x_t (main.cpp:3322-3499) — so
   // their output for ALL sampling steps is evaluated before the loop, many timesteps per batch (play: [timestep][sequence] sequences with per-sequence scale / shift),
   // and a step only selects its slice of ce16_all. Same arithmetic per sequence: bit-identical to evaluating the layers inside every step.
   bool hoisted = false;
   Layout play;
   Work pwk;
-  DevBuf pcode, ph0, pce, psrc, pscatter, ce16_all;
+  DevBuf pcode, ph0, pce, psrc, pscatter;
   std::vector<int> ce_src_host; // share_integ: source row in ilay of every row of lay
   // option latency_mode (small layouts): per sampling step one statistics slot per f32 GEMM output, zeroed at the start of the step; h0's slot persists
   bool lat = false;
@@ -1099,23 +1127,14 @@ struct DiffState {
   int gn_site = 0, gn_sites_max = 0;
   size_t gn_slot_ll = 0, gn_stripe_ll = 0; // long longs per slot = FX_STRIPES stripes x (sequences x 32 groups x 4)
   long long *new_stats_slot() { long long *p = gn_stats.as<long long>() + (size_t)gn_site * gn_slot_ll; gn_site++; return p; }
-  DevBuf ddim_tab; // DdimEntry[n_steps] (option diff_sampler = 1)
-  DevBuf step_tab, step_ctr, ss_cur; // StepEntry[n_steps] | int step counter | this step's scale/shift block (fixed address)
-  hipGraph_t step_graph = nullptr;
-  hipGraphExec_t step_exec = nullptr;
-  void drop_step_graph() {
-    if (step_exec) (void)hipGraphExecDestroy(step_exec);
-    if (step_graph) (void)hipGraphDestroy(step_graph);
-    step_exec = nullptr; step_graph = nullptr;
-  }
-  DevBuf code_emb, ce, ce16, xt16, inp16, net, temb, e1, emb, ss_all, ss_chk, xbuf, xoff, noise, seq_src, lat_in16, out_ct;
+  DevBuf temb, e1, emb, ss_chk, seq_src, lat_in16, out_ct;
   PinnedBuf noise_host; // reference-order noise drawn step by step beside the device loop (diff_sample)
   // tts_diffusion_multi_voice: this call's conditioning latents [n_voices][2048] followed by the candidates' rows of them [B], ONE upload per call; mv_tab / mv_idx
   // point into it while the call runs and are null otherwise (every other entry point reads cond_latent, which the call neither reads nor writes)
   DevBuf mv_buf;
   const float *mv_tab = nullptr;
   const int *mv_idx = nullptr;
-  ~DiffState() { drop_step_graph(); for (void *p : owned) (void)hipFree(p); }
+  ~DiffState() { for (void *p : owned) (void)hipFree(p); }
   int n_res() const { return n_integ + n_main + n_tail; }
 };
 
@@ -1841,13 +1860,13 @@ static __global__ __launch_bounds__(256) void differ_kernel(const unsigned *__re
 }
 
 // Timestep MLP + every emb_layers linear for `n` timesteps at once:
-//   emb = W2 silu(W0 te + b0) + b2 (main.cpp:3331-3343); ss[j] = Wemb_j silu(emb) + bemb_j (3410-3428).
-static int precompute_time(tts_ctx *ctx, DiffState *st, const std::vector<int> &timesteps) {
+//   emb = W2 silu(W0 te + b0) + b2 (main.cpp:3331-3343); ss[j] = Wemb_j silu(emb) + bemb_j (3410-3428). Result: ss_all [n][n_res][2048], the request's.
+static int precompute_time(tts_ctx *ctx, DiffState *st, const std::vector<int> &timesteps, DevBuf &ss_all) {
   const int n = (int)timesteps.size(), nres = st->n_res();
   std::vector<float> te((size_t)n * C);
   for (int i = 0; i < n; i++) timestep_embedding(timesteps[i], te.data() + (size_t)i * C);
   TTS_HIP(ctx, st->temb.reserve(te.size() * 4)); TTS_HIP(ctx, st->e1.reserve(te.size() * 4)); TTS_HIP(ctx, st->emb.reserve(te.size() * 4));
-  TTS_HIP(ctx, st->ss_all.reserve((size_t)n * nres * 2 * C * 4));
+  TTS_HIP(ctx, ss_all.reserve((size_t)n * nres * 2 * C * 4));
   TTS_HIP(ctx, hipMemcpyAsync(st->temb.p, te.data(), te.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // SiLU of both hidden vectors is applied by the kernel that produces them (emb is only used activated): three launches fewer than a separate in-place
@@ -1870,7 +1889,7 @@ static int precompute_time(tts_ctx *ctx, DiffState *st, const std::vector<int> &
   // utterance (~50 us), a silent 1e-3-level perturbation of the whole sampling loop becomes either the right values or an error, and
   // tts_diffusion_time_mlp_retries() says if it ever fired.
 #ifdef TTS_DEBUG_NO_TIME_GUARD // developer build (tools/build_debug_lib.sh noguard): one evaluation, so that the probes see a fault itself
-  mlp(st->ss_all.as<float>());
+  mlp(ss_all.as<float>());
   if (false) {
 #else
   {
@@ -1880,10 +1899,10 @@ static int precompute_time(tts_ctx *ctx, DiffState *st, const std::vector<int> &
   int *flag = (int *)(st->ss_chk.as<float>() + nss);
   bool agreed = false;
   for (int attempt = 0; attempt < 64 && !agreed; attempt++) {
-    mlp(st->ss_all.as<float>());
+    mlp(ss_all.as<float>());
     mlp(st->ss_chk.as<float>());
     TTS_HIP(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
-    differ_kernel<<<64, 256, 0, ctx->stream>>>(st->ss_all.as<unsigned>(), st->ss_chk.as<unsigned>(), nss, flag);
+    differ_kernel<<<64, 256, 0, ctx->stream>>>(ss_all.as<unsigned>(), st->ss_chk.as<unsigned>(), nss, flag);
     int h = 1;
     TTS_HIP(ctx, hipMemcpyAsync(&h, flag, 4, hipMemcpyDeviceToHost, ctx->stream));
     TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1896,7 +1915,7 @@ static int precompute_time(tts_ctx *ctx, DiffState *st, const std::vector<int> &
   DBG_SUM("time temb", st->temb.p, (size_t)n * C * 4);
   DBG_SUM("time e1", st->e1.p, (size_t)n * C * 4);
   DBG_SUM("time emb", st->emb.p, (size_t)n * C * 4);
-  DBG_SUM("time ss_all", st->ss_all.p, (size_t)n * nres * 2 * C * 4);
+  DBG_SUM("time ss_all", ss_all.p, (size_t)n * nres * 2 * C * 4);
   return TTS_OK;
 }
 
@@ -1935,8 +1954,7 @@ static int latent_conditioner(tts_ctx *ctx, DiffState *st, const float *latents_
   return TTS_OK;
 }
 
-// The network is split at the integrator boundary so that the single call (network_forward) and the diffusion session (diff_session_enqueue_step) run the same two
-// halves, each on its own layout and buffers.
+// The network in two halves at the integrator boundary (the hoisted integrator runs the first half before the loop, on a layout of its own).
 // First half: the conditioning_timestep_integrator layers on layout il. code_emb / h0: the code embedding and in_layers of the first ResBlock applied to it (neither
 // depends on the timestep); result in ce (f32 rows of il). ss = block 0 of this evaluation's scale / shift blocks.
 static int network_integrator(tts_ctx *ctx, DiffState *st, Layout &il, Work &iw, float *ce, const float *code_emb, const float *h0, const float *ss) {
@@ -1980,41 +1998,42 @@ static int network_body(tts_ctx *ctx, DiffState *st, Layout &lay, Work &wk, cons
   return TTS_OK;
 }
 
-// One network evaluation for every sequence of st->lay. Inputs: st->code_emb (f32 rows), st->xt16;
-// ss = this timestep's scale/shift block [n_res][2048]. Output: st->net [rows][256].
-static int network_forward(tts_ctx *ctx, DiffState *st, const float *ss) {
-  Layout &lay = st->lay;
-  Work &wk = st->wk;
-  Layout &il = st->share_integ ? st->ilay : st->lay; // layout of the integrator stage
-  Work &iw = st->share_integ ? st->iwk : st->wk;
-  float *ce = st->ce.as<float>();
-  if (st->n_integ == 0) TTS_HIP(ctx, hipMemcpyAsync(ce, st->code_emb.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
+// One network evaluation for every sequence of sb.lay. Inputs: sb.code_emb (f32 rows), sb.xt16; ss = block 0 of this evaluation's scale / shift blocks
+// [n_res][2048] (per slot under sb.lay's seq_step). Output: sb.net [rows][256]. The route is DiffState's: share_integ (ilay / iwk), hoisted, lat — a session
+// runs with the first and the last off.
+static int network_forward(tts_ctx *ctx, DiffState *st, StepBufs &sb, const float *ss) {
+  Layout &lay = sb.lay;
+  Work &wk = sb.wk;
+  Layout &il = st->share_integ ? st->ilay : lay; // layout of the integrator stage
+  Work &iw = st->share_integ ? st->iwk : wk;
   // option latency_mode: the statistics slots of this evaluation start empty (one memset node; every f32 GEMM of the step takes the next slot)
   st->gn_site = 0;
   iw.st_x = wk.st_x = iw.st_h = wk.st_h = nullptr;
   if (st->lat) TTS_HIP(ctx, hipMemsetAsync(st->gn_stats.p, 0, (size_t)st->gn_sites_max * st->gn_slot_ll * 8, ctx->stream));
-  __half *ce16 = st->ce16.as<__half>();
-  if (st->hoisted) { // the integrator ran before the loop for every step (precompute_integrator): this step's slice
-    select_step_slice_kernel<<<256, 256, 0, ctx->stream>>>(st->ce16_all.as<uint4>(), (size_t)lay.rows * C / 8, st->step_ctr.as<int>(), (uint4 *)ce16);
+  __half *ce16 = sb.ce16.as<__half>();
+  if (st->hoisted) { // the integrator ran before the loop for every step (precompute_integrator): every row's slice of its request's step
+    step_row_select_kernel<<<lay.rows, 128, 0, ctx->stream>>>(sb.req, sb.ctr.as<int>(), sb.seq_req, lay.d_row_seq.as<int>(), sb.row_src, (uint4 *)ce16);
   } else {
-    CHECK(network_integrator(ctx, st, il, iw, ce, st->code_emb.as<float>(), st->h0.as<float>(), ss));
+    float *ce = sb.ce.as<float>();
+    if (st->n_integ == 0) TTS_HIP(ctx, hipMemcpyAsync(ce, sb.code_emb.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    CHECK(network_integrator(ctx, st, il, iw, ce, sb.code_emb.as<float>(), sb.h0.as<float>(), ss));
     if (st->share_integ) gather_f16_kernel<<<lay.rows, 256, 0, ctx->stream>>>(ce, st->ce_src.as<int>(), ce16);
     else to_f16_kernel<<<lay.rows, 256, 0, ctx->stream>>>(ce, lay.d_row_seq.as<int>(), ce16);
   }
-  CHECK(network_body(ctx, st, lay, wk, ce16, st->xt16.as<__half>(), st->inp16.as<__half>(), st->net.as<float>(), ss));
+  CHECK(network_body(ctx, st, lay, wk, ce16, sb.xt16.as<__half>(), sb.inp16.as<__half>(), sb.net.as<float>(), ss));
   if (st->lat && st->gn_site > st->gn_sites_max) return fail(ctx, TTS_ERR_STATE, "latency_mode: %d statistics slots used, %d reserved", st->gn_site, st->gn_sites_max);
   return TTS_OK;
 }
 
-// The conditioning_timestep_integrator layers for EVERY sampling step, before the loop (see DiffState::hoisted). Needs setup_batch (code embedding, h0) and
-// precompute_time (ss_all) of this call. Timesteps are processed in chunks of about one benchmark batch of rows (28 672): the regime the GEMMs are tuned for, instead
+// The conditioning_timestep_integrator layers for EVERY sampling step, before the loop (see DiffState::hoisted), into ce16_all [n_steps][rows][1024]. Needs
+// setup_batch (code embedding, h0) and precompute_time (ss_all) of this request. Timesteps are processed in chunks of about one benchmark batch of rows (28 672): the regime the GEMMs are tuned for, instead
 // of 22 launches per step at 1 792 rows.
-static int precompute_integrator(tts_ctx *ctx, DiffState *st, int n_steps) {
-  const Layout &lay = st->lay;
-  Layout &il = st->share_integ ? st->ilay : st->lay;
+static int precompute_integrator(tts_ctx *ctx, DiffState *st, int n_steps, const float *ss_all, DevBuf &ce16_all) {
+  const Layout &lay = st->sb.lay;
+  Layout &il = st->share_integ ? st->ilay : st->sb.lay;
   const int per = il.ns, nt_max = std::max(1, 28672 / il.rows);
   const size_t ss_stride = (size_t)st->n_res() * 2 * C;
-  TTS_HIP(ctx, st->ce16_all.reserve((size_t)n_steps * lay.rows * C * 2));
+  TTS_HIP(ctx, ce16_all.reserve((size_t)n_steps * lay.rows * C * 2));
   // row of il that feeds row r of lay (-1: guard rows), and (sequence, t) of every il row
   std::vector<int> il_of_lay(lay.rows, -1), il_seq(il.rows, -1), il_t(il.rows, 0);
   for (int s = 0; s < il.ns; s++)
@@ -2048,17 +2067,17 @@ static int precompute_integrator(tts_ctx *ctx, DiffState *st, int n_steps) {
     TTS_HIP(ctx, hipMemcpy(st->psrc.p, src.data(), src.size() * 4, hipMemcpyHostToDevice));
     TTS_HIP(ctx, hipMemcpy(st->pscatter.p, scat.data(), scat.size() * 4, hipMemcpyHostToDevice));
     TTS_HIP(ctx, st->pcode.reserve((size_t)pl.rows * C * 4)); TTS_HIP(ctx, st->ph0.reserve((size_t)pl.rows * C * 4)); TTS_HIP(ctx, st->pce.reserve((size_t)pl.rows * C * 4));
-    gather_f32_kernel<<<pl.rows, 256, 0, ctx->stream>>>(st->code_emb.as<float>(), st->psrc.as<int>(), st->pcode.as<float>());
-    gather_f32_kernel<<<pl.rows, 256, 0, ctx->stream>>>(st->h0.as<float>(), st->psrc.as<int>(), st->ph0.as<float>());
+    gather_f32_kernel<<<pl.rows, 256, 0, ctx->stream>>>(st->sb.code_emb.as<float>(), st->psrc.as<int>(), st->pcode.as<float>());
+    gather_f32_kernel<<<pl.rows, 256, 0, ctx->stream>>>(st->sb.h0.as<float>(), st->psrc.as<int>(), st->ph0.as<float>());
     float *ce = st->pce.as<float>();
-    const float *ssb = st->ss_all.as<float>(); // step 0's block; sequence s reads at + seq_step[s] * ss_stride
+    const float *ssb = ss_all; // step 0's block; sequence s reads at + seq_step[s] * ss_stride
     for (int i = 0; i < st->n_integ && rc == TTS_OK; i++) {
       if (i == 0) rc = res_block(ctx, st, pl, pw, ce, st->integ_res[0], ssb, st->pcode.as<float>(), st->ph0.as<float>());
       else rc = res_block(ctx, st, pl, pw, ce, st->integ_res[i], ssb + (size_t)i * 2 * C);
       if (rc == TTS_OK) rc = attention_block(ctx, st, pl, pw, ce, st->integ_attn[i]);
     }
     if (rc) break;
-    gather_f16_kernel<<<nt * lay.rows, 256, 0, ctx->stream>>>(ce, st->pscatter.as<int>(), st->ce16_all.as<__half>() + (size_t)idx0 * lay.rows * C);
+    gather_f16_kernel<<<nt * lay.rows, 256, 0, ctx->stream>>>(ce, st->pscatter.as<int>(), ce16_all.as<__half>() + (size_t)idx0 * lay.rows * C);
     TTS_HIP(ctx, hipGetLastError());
     TTS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the next chunk rebuilds the layout's host-side tables
   }
@@ -2073,22 +2092,11 @@ static int setup_batch(tts_ctx *ctx, DiffState *st, const float *latents, const 
   if (cond) for (int c = 0; c < B; c++) { lens.push_back(tts_diffusion_frames(L[c])); src.push_back(c); }
   if (uncond) for (int c = 0; c < B; c++) { lens.push_back(tts_diffusion_frames(L[c])); src.push_back(-1); }
   for (int t : lens) if (t < 1) return fail(ctx, TTS_ERR_ARG, "latent too short");
-  CHECK(st->lay.build(ctx, lens));
-  Layout &lay = st->lay;
-  CHECK(st->wk.reserve(ctx, lay.rows, lay.ns));
-  auto rz = [&](DevBuf &b, size_t bytes) -> hipError_t {
-    size_t old = b.cap;
-    hipError_t e = b.reserve(bytes);
-    if (e == hipSuccess && b.cap != old) e = hipMemset(b.p, 0, b.cap);
-    return e;
-  };
-  TTS_HIP(ctx, rz(st->code_emb, (size_t)lay.rows * C * 4));
-  TTS_HIP(ctx, rz(st->ce, (size_t)lay.rows * C * 4));
-  TTS_HIP(ctx, rz(st->ce16, (size_t)lay.rows * C * 2));
-  TTS_HIP(ctx, rz(st->inp16, (size_t)lay.rows * C * 2));
-  TTS_HIP(ctx, rz(st->xt16, (size_t)(lay.rows + 2) * XTC * 2));
-  TTS_HIP(ctx, hipMemset(st->xt16.p, 0, st->xt16.cap));
-  TTS_HIP(ctx, rz(st->net, (size_t)lay.rows * 256 * 4));
+  CHECK(st->sb.lay.build(ctx, lens));
+  Layout &lay = st->sb.lay;
+  CHECK(st->sb.wk.reserve(ctx, lay.rows, lay.ns));
+  CHECK(st->sb.reserve_rows(ctx, (size_t)lay.rows, true));
+  TTS_HIP(ctx, hipMemset(st->sb.xt16.p, 0, st->sb.xt16.cap));
   TTS_HIP(ctx, st->seq_src.reserve(lay.ns * 4));
   TTS_HIP(ctx, hipMemcpy(st->seq_src.p, src.data(), lay.ns * 4, hipMemcpyHostToDevice));
   // integrator layout: every conditioned sequence, one unconditioned sequence per distinct length
@@ -2120,7 +2128,7 @@ static int setup_batch(tts_ctx *ctx, DiffState *st, const float *latents, const 
     TTS_HIP(ctx, st->iseq_src.reserve(st->ilay.ns * 4));
     TTS_HIP(ctx, hipMemcpy(st->iseq_src.p, isrc.data(), st->ilay.ns * 4, hipMemcpyHostToDevice));
   }
-  Layout &il = st->share_integ ? st->ilay : st->lay;
+  Layout &il = st->share_integ ? st->ilay : st->sb.lay;
   if (cond) CHECK(latent_conditioner(ctx, st, latents, L));
   else { // layout still needed by build_code_emb (never dereferenced for uncond rows)
     CHECK(st->lat_lay.build(ctx, L));
@@ -2128,7 +2136,7 @@ static int setup_batch(tts_ctx *ctx, DiffState *st, const float *latents, const 
   }
   build_code_emb_kernel<<<il.rows, 256, 0, ctx->stream>>>(st->lat_wk.H(), st->lat_lay.d_start.as<int>(), st->lat_lay.d_len.as<int>(),
                                                           st->uncond_emb, il.d_row_seq.as<int>(), il.d_row_t.as<int>(), il.d_len.as<int>(),
-                                                          (st->share_integ ? st->iseq_src : st->seq_src).as<int>(), st->code_emb.as<float>());
+                                                          (st->share_integ ? st->iseq_src : st->seq_src).as<int>(), st->sb.code_emb.as<float>());
   TTS_HIP(ctx, hipGetLastError());
   // Option latency_mode, small layouts only (one or two utterances: the GroupNorm kernels are latency-bound there, 64 workgroups each): the f32 GEMMs of the sampling
   // step leave the GroupNorm statistics of their outputs in per-step slots and the GroupNorms become gn_apply_kernel. Not bit-identical to the batch path (variance from
@@ -2143,15 +2151,52 @@ static int setup_batch(tts_ctx *ctx, DiffState *st, const float *latents, const 
     TTS_HIP(ctx, hipMemsetAsync(st->gn_stats_h0.p, 0, st->gn_slot_ll * 8, ctx->stream));
   }
   if (st->n_integ > 0) {
-    TTS_HIP(ctx, rz(st->h0, (size_t)il.rows * C * 4));
+    TTS_HIP(ctx, reserve_zeroed(st->sb.h0, (size_t)il.rows * C * 4));
     // (the code embedding's own statistics are reduced by the GroupNorm kernel: once per utterance)
-    CHECK(res_in_layers(ctx, st, il, st->share_integ ? st->iwk : st->wk, st->code_emb.as<float>(), st->integ_res[0], st->h0.as<float>(), nullptr,
+    CHECK(res_in_layers(ctx, st, il, st->share_integ ? st->iwk : st->sb.wk, st->sb.code_emb.as<float>(), st->integ_res[0], st->sb.h0.as<float>(), nullptr,
                         st->lat ? st->gn_stats_h0.as<long long>() : nullptr));
   }
   return TTS_OK;
 }
 
-// tts_diffusion_forward: one evaluation of one branch (parity-test entry point).
+// One sampling step of sb, identical for every step (all per-step values are read through the device counters): launched eagerly or captured once and replayed.
+static int enqueue_step(tts_ctx *ctx, DiffState *st, StepBufs &sb) {
+  Layout &lay = sb.lay;
+  const size_t ss_stride = (size_t)st->n_res() * 2 * C;
+  int *ctr = sb.ctr.as<int>();
+  step_begin_kernel<<<dim3(16, sb.n_live), 256, 0, ctx->stream>>>(sb.req, ctr, sb.live, ss_stride, sb.ss_cur.as<float>());
+  step_xt_kernel<<<lay.rows, 128, 0, ctx->stream>>>(sb.req, sb.seq_req, sb.seq_xoff, sb.seq_partner, lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(),
+                                                   lay.d_len.as<int>(), sb.xt16.as<__half>() + XTC);
+  CHECK(network_forward(ctx, st, sb, sb.ss_cur.as<float>()));
+  {
+    ProfScope ps(ctx, "diff_update");
+    step_update_kernel<<<lay.rows, 128, 0, ctx->stream>>>(sb.net.as<float>(), sb.req, ctr, sb.seq_req, sb.seq_xoff, sb.seq_partner, sb.seq_cand,
+                                                         lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(), lay.d_len.as<int>());
+  }
+  step_advance_kernel<<<(sb.n_live + 63) / 64, 64, 0, ctx->stream>>>(sb.req, ctr, sb.live, sb.n_live);
+  TTS_HIP(ctx, hipGetLastError());
+  return TTS_OK;
+}
+// The step of sb as a graph (sb.step_exec), in place of the one sb held: its layout, buffers and tables are baked in.
+static int capture_step(tts_ctx *ctx, DiffState *st, StepBufs &sb) {
+  sb.drop_step_graph();
+  ctx->capturing = true;
+  hipError_t eb = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
+  int rc = eb == hipSuccess ? enqueue_step(ctx, st, sb) : TTS_OK;
+  hipError_t ee = eb == hipSuccess ? hipStreamEndCapture(ctx->stream, &sb.step_graph) : eb;
+  ctx->capturing = false;
+  if (rc) return rc;
+  TTS_HIP(ctx, ee);
+  TTS_HIP(ctx, hipGraphInstantiate(&sb.step_exec, sb.step_graph, nullptr, nullptr, 0));
+  return TTS_OK;
+}
+// TTS_NO_GRAPH (e.g. under rocprofv3): every step is launched eagerly, whatever "diff_graph" says.
+static bool no_graph_env() {
+  static const bool v = getenv("TTS_NO_GRAPH") != nullptr;
+  return v;
+}
+
+// tts_diffusion_forward: one evaluation of one branch (parity-test entry point): a request of one step whose sequence has no partner and gets no update.
 int diff_forward(tts_ctx *ctx, const float *latents, int L, const float *x_t, int timestep, int cond_free, float *out) {
   DiffState *st = ctx->diff;
   if (!st) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
@@ -2159,27 +2204,40 @@ int diff_forward(tts_ctx *ctx, const float *latents, int L, const float *x_t, in
   std::vector<int> Ls{L};
   CHECK(setup_batch(ctx, st, latents, Ls, !cond_free, cond_free));
   st->hoisted = false;
-  const int T = st->lay.len[0];
-  CHECK(precompute_time(ctx, st, std::vector<int>{timestep}));
-  TTS_HIP(ctx, st->xbuf.reserve((size_t)100 * T * 4));
-  TTS_HIP(ctx, hipMemcpyAsync(st->xbuf.p, x_t, (size_t)100 * T * 4, hipMemcpyHostToDevice, ctx->stream));
-  int64_t off0 = 0;
-  TTS_HIP(ctx, st->xoff.reserve(8));
-  TTS_HIP(ctx, hipMemcpyAsync(st->xoff.p, &off0, 8, hipMemcpyHostToDevice, ctx->stream));
-  Layout &lay = st->lay;
-  xt_to_rows_kernel<<<lay.rows, 128, 0, ctx->stream>>>(st->xbuf.as<float>(), st->xoff.as<int64_t>(), lay.d_row_seq.as<int>(),
-                                                       lay.d_row_t.as<int>(), lay.d_len.as<int>(), lay.d_start.as<int>(), 1, 0,
-                                                       st->xt16.as<__half>() + XTC);
-  CHECK(network_forward(ctx, st, st->ss_all.as<float>()));
+  StepBufs &sb = st->sb;
+  DiffReq &r = st->req;
+  const int T = sb.lay.len[0];
+  CHECK(precompute_time(ctx, st, std::vector<int>{timestep}, r.ss_all));
+  r.n_cand = 1; r.n_steps = 1; r.host_noise = false;
+  r.xoff.assign(1, 0);
+  TTS_HIP(ctx, r.x.reserve((size_t)100 * T * 4));
+  TTS_HIP(ctx, hipMemcpyAsync(r.x.p, x_t, (size_t)100 * T * 4, hipMemcpyHostToDevice, ctx->stream));
+  CHECK(sb.set_single(ctx, r));
+  Layout &lay = sb.lay;
+  step_xt_kernel<<<lay.rows, 128, 0, ctx->stream>>>(sb.req, sb.seq_req, sb.seq_xoff, sb.seq_partner, lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(),
+                                                   lay.d_len.as<int>(), sb.xt16.as<__half>() + XTC);
+  CHECK(network_forward(ctx, st, sb, r.ss_all.as<float>()));
   TTS_HIP(ctx, st->out_ct.reserve((size_t)200 * T * 4));
-  rows_to_ct_kernel<<<(200 * T + 255) / 256, 256, 0, ctx->stream>>>(st->net.as<float>(), lay.start[0], T, 200, 256, st->out_ct.as<float>());
+  rows_to_ct_kernel<<<(200 * T + 255) / 256, 256, 0, ctx->stream>>>(sb.net.as<float>(), lay.start[0], T, 200, 256, st->out_ct.as<float>());
   TTS_HIP(ctx, hipMemcpyAsync(out, st->out_ct.p, (size_t)200 * T * 4, hipMemcpyDeviceToHost, ctx->stream));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return TTS_OK;
 }
 
+// What prepare_request makes a request from.
+struct ReqSpec {
+  const float *latents; const int32_t *rows; int n_cand, n_steps; // the candidates' AR latents
+  int sampler; double eta; float k;                              // 0 = the reference's ancestral step, 1 = DDIM; ddim_eta; guidance k
+  const float *voices; int n_voices; const int32_t *voice_of;    // conditioning latents [n_voices][2048] and the candidates' rows of them (null: all row 0), or
+                                                                  // voices = null: the loaded model's latent
+  const float *noise; int noise_mode;                            // caller noise; else TTS_NOISE_REFERENCE: drawn here, candidate after candidate; else the device generator
+  PinnedBuf *stream_noise;                                       // reference order, one candidate: reserve only (DiffReq::noise_streamed), staged through this buffer
+  uint64_t seed; uint32_t stream_base;                           // the device generator's key and candidate 0's stream
+  int hoist_max_rows;                                            // the integrator layers run before the loop for layouts of at most this many rows
+  bool timing;                                                   // TTS_TIMING: synchronise after setup_batch and note the time
+};
 // The per-step device tables of a sampling loop of n_steps (see StepEntry): entry idx belongs to respaced timestep n_steps - 1 - idx. has_noise: the steps read
-// host-provided noise blocks of `total` floats each (block 0 = x_T, block 1 + idx = step idx). One builder for tts_diffusion and for a session request.
+// host-provided noise blocks of `total` floats each (block 0 = x_T, block 1 + idx = step idx).
 static void build_step_tables(const DiffSchedule &sched, int n_steps, bool ddim, bool has_noise, long long total, std::vector<StepEntry> &tab,
                               std::vector<DdimEntry> &dtab) {
   tab.assign(n_steps, StepEntry{});
@@ -2195,177 +2253,167 @@ static void build_step_tables(const DiffSchedule &sched, int n_steps, bool ddim,
     if (ddim) dtab[idx] = DdimEntry{sched.c_x0[t], sched.c_eps[t], sched.sigma[t], 0.f};
   }
 }
+// Everything of a request that is evaluated before its first step, for the request ALONE, in the single call's run state (st->sb, which no step of a session
+// reads) and into storage the request owns: the voice, layouts and code embedding (setup_batch), schedule and scale / shift blocks (precompute_time), the hoisted
+// integrator (precompute_integrator), x_T and the noise blocks, the step tables. The voice enters the stage at ONE place (the scale / shift of the code norm that
+// ends latent_conditioner), and nothing is kept from one request to the next, so the table and the candidates' rows of it are all a voice adds: one upload, no
+// launch. The unconditioned sequences — the only ones share_uncond merges — never read a voice.
+static int prepare_request(tts_ctx *ctx, DiffState *st, DiffReq &r, const ReqSpec &sp) {
+  const int B = sp.n_cand, n_steps = sp.n_steps;
+  struct Reset { DiffState *s; ~Reset() { s->mv_tab = nullptr; s->mv_idx = nullptr; } } reset{st}; // also when the call ends in an exception (api.cpp: guarded)
+  if (sp.voices) {
+    const size_t nf = (size_t)sp.n_voices * 2 * C;
+    std::vector<float> up(nf + (size_t)B, 0.f); // [n_voices][2048] floats | [B] ints (an all-zero float is the int 0)
+    memcpy(up.data(), sp.voices, nf * 4);
+    if (sp.voice_of) memcpy(up.data() + nf, sp.voice_of, (size_t)B * 4);
+    TTS_HIP(ctx, st->mv_buf.reserve(up.size() * 4));
+    TTS_HIP(ctx, hipMemcpy(st->mv_buf.p, up.data(), up.size() * 4, hipMemcpyHostToDevice));
+    st->mv_tab = st->mv_buf.as<float>();
+    st->mv_idx = (const int *)(st->mv_buf.as<float>() + nf);
+  }
+  CHECK(setup_batch(ctx, st, sp.latents, std::vector<int>(sp.rows, sp.rows + B), true, true));
+  if (sp.timing) (void)hipStreamSynchronize(ctx->stream);
+  r.t_setup = std::chrono::steady_clock::now();
+  Layout &lay = st->sb.lay;
+  r.n_cand = B; r.n_steps = n_steps; r.sampler = sp.sampler; r.seed = sp.seed; r.stream_base = sp.stream_base;
+  // Deterministic DDIM (ddim_eta = 0) has ONE noise vector per candidate, x_T: n_vec = 1 (no per-step block is drawn, allocated or uploaded); with eta > 0 layout,
+  // draw order and generator keys are those of the ancestral sampler.
+  const bool ddim = sp.sampler == 1;
+  const int n_vec = r.n_vec = ddim && sp.eta == 0 ? 1 : n_steps + 1;
+  DiffSchedule sched;
+  sched.base_k = sp.k;
+  sched.build(n_steps);
+  if (ddim) sched.build_ddim(sp.eta);
+  std::vector<int> ts(n_steps);
+  for (int idx = 0; idx < n_steps; idx++) ts[idx] = sched.timestep_map[n_steps - 1 - idx]; // time_embedding_{idx} (5819-5825)
+  CHECK(precompute_time(ctx, st, ts, r.ss_all));
+  // small layouts: the integrator layers of all steps now, in benchmark-sized batches (results are bit-identical either way)
+  st->hoisted = st->n_integ > 0 && lay.rows <= sp.hoist_max_rows;
+  if (st->hoisted) CHECK(precompute_integrator(ctx, st, n_steps, r.ss_all.as<float>(), r.ce16_all));
+  r.src_rows = lay.rows;
+  // x state [cand][100][T_c]
+  r.T.assign(lay.len.begin(), lay.len.begin() + B);
+  r.xoff.resize(B);
+  r.total = 0;
+  for (int c = 0; c < B; c++) { r.xoff[c] = r.total; r.total += (int64_t)100 * lay.len[c]; }
+  const int64_t total = r.total;
+  TTS_HIP(ctx, r.x.reserve(total * 4));
+  r.host_noise = sp.noise != nullptr || sp.noise_mode == TTS_NOISE_REFERENCE;
+  r.noise_streamed = r.host_noise && sp.stream_noise != nullptr;
+  if (r.noise_streamed && sp.stream_noise->reserve((size_t)total * n_vec * 4) != hipSuccess) { (void)hipGetLastError(); r.noise_streamed = false; }
+  if (r.noise_streamed) {
+    TTS_HIP(ctx, r.noise.reserve((size_t)total * n_vec * 4));
+  } else if (r.host_noise) {
+    // per step a [cand][100][T] block in the layout of x: block 0 = x_T, block 1+idx = step idx
+    std::vector<float> hn((size_t)total * n_vec);
+    size_t src = 0;
+    for (int c = 0; c < B; c++)
+      for (int k = 0; k < n_vec; k++) {
+        float *dst = hn.data() + (size_t)k * total + r.xoff[c];
+        if (sp.noise) { // caller layout: per candidate n_vec consecutive vectors
+          memcpy(dst, sp.noise + src, (size_t)100 * lay.len[c] * 4);
+          src += (size_t)100 * lay.len[c];
+        } else rng_normal_fill(ctx, dst, (int64_t)100 * lay.len[c]); // the reference's draw order, candidate after candidate (main.cpp:5638, 6020-6021)
+      }
+    TTS_HIP(ctx, r.noise.reserve(hn.size() * 4));
+    TTS_HIP(ctx, hipMemcpy(r.noise.p, hn.data(), hn.size() * 4, hipMemcpyHostToDevice));
+    TTS_HIP(ctx, hipMemcpyAsync(r.x.p, r.noise.p, total * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  } else {
+    for (int c = 0; c < B; c++) {
+      const int64_t n = (int64_t)100 * lay.len[c];
+      philox_fill_kernel<<<(int)((n + 255) / 256), 256, 0, ctx->stream>>>(r.x.as<float>() + r.xoff[c], n, r.seed, r.stream_base + (uint32_t)c, 0xFFFFFFFFu);
+    }
+    TTS_HIP(ctx, hipGetLastError());
+  }
+  std::vector<StepEntry> tab;
+  std::vector<DdimEntry> dtab;
+  build_step_tables(sched, n_steps, ddim, r.host_noise && n_vec > 1, total, tab, dtab);
+  TTS_HIP(ctx, r.tab.reserve(tab.size() * sizeof(StepEntry)));
+  TTS_HIP(ctx, hipMemcpyAsync(r.tab.p, tab.data(), tab.size() * sizeof(StepEntry), hipMemcpyHostToDevice, ctx->stream));
+  if (ddim) {
+    TTS_HIP(ctx, r.dtab.reserve(dtab.size() * sizeof(DdimEntry)));
+    TTS_HIP(ctx, hipMemcpyAsync(r.dtab.p, dtab.data(), dtab.size() * sizeof(DdimEntry), hipMemcpyHostToDevice, ctx->stream));
+  }
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the tables are host vectors: the copies must have read them before they go out of scope
+  return TTS_OK;
+}
 
-// tts_diffusion: the sampling loop for B candidates.
-int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, int n_steps, const float *noise, int noise_mode,
-                float *mel_out) {
+// tts_diffusion / tts_diffusion_multi_voice: the sampling loop for B candidates, candidate c conditioned on voices[voice_of[c]] or (voices = null) on the loaded
+// model's latent.
+static int diff_sample_with(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, const float *voices, int n_voices, const int32_t *voice_of,
+                            int n_steps, const float *noise, int noise_mode, float *mel_out) {
   DiffState *st = ctx->diff;
-  if (!st) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
-  if (!latents || !rows || !mel_out || B < 1 || n_steps < 2) return fail(ctx, TTS_ERR_ARG, "tts_diffusion: bad argument");
-  std::vector<int> L(rows, rows + B);
-  for (int l : L) if (l < 1 || l > 500) return fail(ctx, TTS_ERR_ARG, "latent rows %d out of range", l);
   static const bool timing = getenv("TTS_TIMING") != nullptr; // host-side breakdown on stderr
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
     return std::chrono::duration<double, std::milli>(b - a).count();
   };
   const auto t_begin = now();
-  CHECK(setup_batch(ctx, st, latents, L, true, true));
-  if (timing) (void)hipStreamSynchronize(ctx->stream);
-  const auto t_setup = now();
-  Layout &lay = st->lay;
-  // option diff_sampler: 0 = the reference's ancestral step, 1 = DDIM. Deterministic DDIM (ddim_eta = 0) has ONE noise vector per candidate, x_T: n_vec = 1 below
-  // (no per-step block is drawn, allocated or uploaded); with eta > 0 layout, draw order and generator keys are those of the ancestral sampler.
-  const bool ddim = ctx->diff_sampler == 1;
-  const int n_vec = ddim && ctx->ddim_eta == 0 ? 1 : n_steps + 1;
-  DiffSchedule sched;
-  sched.base_k = ctx->cond_free_k;
-  sched.build(n_steps);
-  if (ddim) sched.build_ddim(ctx->ddim_eta);
-  std::vector<int> ts(n_steps);
-  for (int idx = 0; idx < n_steps; idx++) ts[idx] = sched.timestep_map[n_steps - 1 - idx]; // time_embedding_{idx} (5819-5825)
-  CHECK(precompute_time(ctx, st, ts));
-  // small batches: the integrator layers of all steps now, in benchmark-sized batches (option hoist_integrator, default 1; results are bit-identical either way)
-  st->hoisted = ctx->hoist_integrator != 0 && st->n_integ > 0 && lay.rows <= (ctx->hoist_integrator > 1 ? ctx->hoist_integrator : HOIST_MAX_ROWS);
-  if (st->hoisted) CHECK(precompute_integrator(ctx, st, n_steps));
-  // x state [cand][100][T_c]
-  std::vector<int64_t> xoff(B);
-  int64_t total = 0;
-  for (int c = 0; c < B; c++) { xoff[c] = total; total += (int64_t)100 * lay.len[c]; }
-  TTS_HIP(ctx, st->xbuf.reserve(total * 4));
-  TTS_HIP(ctx, st->xoff.reserve(B * 8));
-  TTS_HIP(ctx, hipMemcpy(st->xoff.p, xoff.data(), B * 8, hipMemcpyHostToDevice));
-  const bool host_noise = noise != nullptr || noise_mode == TTS_NOISE_REFERENCE;
+  StepBufs &sb = st->sb;
+  DiffReq &r = st->req;
   // One candidate in the reference's draw order (what ./tortoise runs): 81 x 100 T normal draws from the libstdc++ objects take longer on the host (~3 ms per step at
   // T = 870) than the device takes for the step. Round 6: block k + 1 is drawn and sent while the device still works on steps <= k - 1 — the same draws in the same
   // order (x_T, then step after step), the stream orders copy k + 1 in front of step k's update kernel. More candidates draw candidate after candidate
   // (main.cpp:5638, 6020-6021): their order does not allow it.
-  bool pipe_noise = host_noise && !noise && B == 1 && ctx->noise_pipeline != 0;
-  if (pipe_noise && st->noise_host.reserve((size_t)total * n_vec * 4) != hipSuccess) { (void)hipGetLastError(); pipe_noise = false; }
+  const bool want_pipe = !noise && noise_mode == TTS_NOISE_REFERENCE && B == 1 && ctx->noise_pipeline != 0;
+  ReqSpec sp{latents, rows, B, n_steps, ctx->diff_sampler, ctx->ddim_eta, ctx->cond_free_k, voices, n_voices, voice_of, noise, noise_mode,
+             want_pipe ? &st->noise_host : nullptr, ctx->seed_value, (uint32_t)shard_base(ctx),
+             ctx->hoist_integrator == 0 ? 0 : ctx->hoist_integrator > 1 ? ctx->hoist_integrator : HOIST_MAX_ROWS, timing};
+  CHECK(prepare_request(ctx, st, r, sp));
+  const int64_t total = r.total;
   auto draw_block = [&](int k) { // block k of the one candidate into the pinned buffer, then on its way to the device
     float *dst = st->noise_host.as<float>() + (size_t)k * total;
     rng_normal_fill(ctx, dst, total);
-    return hipMemcpyAsync(st->noise.as<float>() + (size_t)k * total, dst, (size_t)total * 4, hipMemcpyHostToDevice, ctx->stream);
+    return hipMemcpyAsync(r.noise.as<float>() + (size_t)k * total, dst, (size_t)total * 4, hipMemcpyHostToDevice, ctx->stream);
   };
-  std::vector<float> hn;
-  if (pipe_noise) {
-    TTS_HIP(ctx, st->noise.reserve((size_t)total * n_vec * 4));
+  if (r.noise_streamed) {
     TTS_HIP(ctx, draw_block(0));
-    TTS_HIP(ctx, hipMemcpyAsync(st->xbuf.p, st->noise.p, total * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  } else if (host_noise) {
-    // per step a [cand][100][T] block in the layout of x: block 0 = x_T, block 1+idx = step idx
-    hn.resize((size_t)total * n_vec);
-    if (noise) { // caller layout: per candidate n_vec = (n_steps+1) consecutive vectors (deterministic DDIM: x_T alone)
-      size_t src = 0;
-      for (int c = 0; c < B; c++)
-        for (int k = 0; k < n_vec; k++) {
-          memcpy(hn.data() + (size_t)k * total + xoff[c], noise + src, (size_t)100 * lay.len[c] * 4);
-          src += (size_t)100 * lay.len[c];
-        }
-    } else { // the reference's draw order, candidate after candidate (main.cpp:5638, 6020-6021)
-      for (int c = 0; c < B; c++)
-        for (int k = 0; k < n_vec; k++) {
-          float *dst = hn.data() + (size_t)k * total + xoff[c];
-          rng_normal_fill(ctx, dst, (int64_t)100 * lay.len[c]);
-        }
-    }
-    TTS_HIP(ctx, st->noise.reserve(hn.size() * 4));
-    TTS_HIP(ctx, hipMemcpy(st->noise.p, hn.data(), hn.size() * 4, hipMemcpyHostToDevice));
-    TTS_HIP(ctx, hipMemcpyAsync(st->xbuf.p, st->noise.p, total * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  } else {
-    for (int c = 0; c < B; c++) {
-      int64_t n = (int64_t)100 * lay.len[c];
-      philox_fill_kernel<<<(int)((n + 255) / 256), 256, 0, ctx->stream>>>(st->xbuf.as<float>() + xoff[c], n, ctx->seed_value, (uint32_t)(shard_base(ctx) + c), 0xFFFFFFFFu);
-    }
+    TTS_HIP(ctx, hipMemcpyAsync(r.x.p, r.noise.p, total * 4, hipMemcpyDeviceToDevice, ctx->stream));
   }
+  // one request in slot 0, its device step counter at 0 (see StepEntry)
+  TTS_HIP(ctx, sb.ctr.reserve(64));
+  TTS_HIP(ctx, sb.ss_cur.reserve((size_t)st->n_res() * 2 * C * 4));
+  TTS_HIP(ctx, hipMemsetAsync(sb.ctr.p, 0, 64, ctx->stream));
+  CHECK(sb.set_single(ctx, r));
   if (timing) (void)hipStreamSynchronize(ctx->stream);
   const auto t_pre = now();
-  const size_t ss_stride = (size_t)st->n_res() * 2 * C;
-  // per-step table + device step counter (see StepEntry)
-  std::vector<StepEntry> tab;
-  std::vector<DdimEntry> dtab;
-  build_step_tables(sched, n_steps, ddim, host_noise && n_vec > 1, total, tab, dtab);
-  TTS_HIP(ctx, st->step_tab.reserve(tab.size() * sizeof(StepEntry)));
-  TTS_HIP(ctx, st->step_ctr.reserve(64));
-  TTS_HIP(ctx, st->ss_cur.reserve(ss_stride * 4));
-  TTS_HIP(ctx, hipMemcpyAsync(st->step_tab.p, tab.data(), tab.size() * sizeof(StepEntry), hipMemcpyHostToDevice, ctx->stream));
-  if (ddim) {
-    TTS_HIP(ctx, st->ddim_tab.reserve(dtab.size() * sizeof(DdimEntry)));
-    TTS_HIP(ctx, hipMemcpyAsync(st->ddim_tab.p, dtab.data(), dtab.size() * sizeof(DdimEntry), hipMemcpyHostToDevice, ctx->stream));
-  }
-  TTS_HIP(ctx, hipMemsetAsync(st->step_ctr.p, 0, 64, ctx->stream));
-  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // `tab` is a host vector: the copy must have read it before it goes out of scope
-  // One sampling step, identical for every step (all per-step values are read through the device counter): launched eagerly or
-  // captured once and replayed.
-  auto enqueue_step = [&]() -> int {
-    step_begin_kernel<<<16, 256, 0, ctx->stream>>>(st->ss_all.as<float>(), ss_stride, st->step_ctr.as<int>(), st->ss_cur.as<float>());
-    xt_to_rows_kernel<<<lay.rows, 128, 0, ctx->stream>>>(st->xbuf.as<float>(), st->xoff.as<int64_t>(), lay.d_row_seq.as<int>(),
-                                                         lay.d_row_t.as<int>(), lay.d_len.as<int>(), lay.d_start.as<int>(), B, 1,
-                                                         st->xt16.as<__half>() + XTC);
-    CHECK(network_forward(ctx, st, st->ss_cur.as<float>()));
-    {
-      ProfScope ps(ctx, "diff_update");
-      if (ddim)
-        ddim_update_kernel<<<lay.rows, 128, 0, ctx->stream>>>(
-            st->net.as<float>(), st->xbuf.as<float>(), st->xoff.as<int64_t>(), lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(),
-            lay.d_len.as<int>(), lay.d_start.as<int>(), B, st->step_tab.as<StepEntry>(), st->ddim_tab.as<DdimEntry>(), st->step_ctr.as<int>(),
-            host_noise && n_vec > 1 ? st->noise.as<float>() : nullptr, ctx->seed_value, (uint32_t)shard_base(ctx));
-      else
-      ddpm_update_kernel<<<lay.rows, 128, 0, ctx->stream>>>(
-          st->net.as<float>(), st->xbuf.as<float>(), st->xoff.as<int64_t>(), lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(),
-          lay.d_len.as<int>(), lay.d_start.as<int>(), B, st->step_tab.as<StepEntry>(), st->step_ctr.as<int>(),
-          host_noise ? st->noise.as<float>() : nullptr, ctx->seed_value, (uint32_t)shard_base(ctx));
-    }
-    step_advance_kernel<<<1, 1, 0, ctx->stream>>>(st->step_ctr.as<int>());
-    TTS_HIP(ctx, hipGetLastError());
-    return TTS_OK;
-  };
   // Event records cannot ride in the replayed graph: while a diff_* family is profiled every prof_eager_every-th step is launched
-  // eagerly (with its event pairs), the others replay the graph; "diff_graph" = 0 (or TTS_NO_GRAPH, e.g. under rocprofv3) launches
-  // every step eagerly.
-  static const bool no_graph_env = getenv("TTS_NO_GRAPH") != nullptr;
+  // eagerly (with its event pairs), the others replay the graph; "diff_graph" = 0 (or TTS_NO_GRAPH) launches every step eagerly.
   bool prof_diff = ctx->prof_on && ctx->prof_filter.empty();
   for (const std::string &f : ctx->prof_filter) prof_diff |= ctx->prof_on && f.rfind("diff_", 0) == 0;
-  const bool use_graph = ctx->diff_graph && !no_graph_env && n_steps > 2;
+  const bool use_graph = ctx->diff_graph && !no_graph_env() && n_steps > 2;
   double t_capture = 0;
-  if (use_graph) {
+  if (use_graph) { // layouts and buffers belong to this call
     const auto tc0 = now();
-    st->drop_step_graph(); // layouts and buffers belong to this call
-    ctx->capturing = true;
-    hipError_t eb = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-    int rc = eb == hipSuccess ? enqueue_step() : TTS_OK;
-    hipError_t ee = eb == hipSuccess ? hipStreamEndCapture(ctx->stream, &st->step_graph) : eb;
-    ctx->capturing = false;
-    if (rc) return rc;
-    TTS_HIP(ctx, ee);
-    TTS_HIP(ctx, hipGraphInstantiate(&st->step_exec, st->step_graph, nullptr, nullptr, 0));
+    CHECK(capture_step(ctx, st, sb));
     t_capture = ms(tc0, now());
   }
   for (int idx = 0; idx < n_steps; idx++) {
     const bool eager = !use_graph || (prof_diff && idx % ctx->prof_eager_every == 0);
-    if (pipe_noise && n_vec > 1) TTS_HIP(ctx, draw_block(idx + 1)); // read by this step's update kernel (deterministic DDIM: block 0 = x_T was the only one)
-    if (eager) CHECK(enqueue_step());
-    else TTS_HIP(ctx, hipGraphLaunch(st->step_exec, ctx->stream));
+    if (r.noise_streamed && r.n_vec > 1) TTS_HIP(ctx, draw_block(idx + 1)); // read by this step's update kernel (deterministic DDIM: block 0 = x_T was the only one)
+    if (eager) CHECK(enqueue_step(ctx, st, sb));
+    else TTS_HIP(ctx, hipGraphLaunch(sb.step_exec, ctx->stream));
   }
   const auto t_issued = now();
   if (timing) (void)hipStreamSynchronize(ctx->stream);
   const auto t_loop = now();
-  TTS_HIP(ctx, hipMemcpyAsync(mel_out, st->xbuf.p, total * 4, hipMemcpyDeviceToHost, ctx->stream));
+  TTS_HIP(ctx, hipMemcpyAsync(mel_out, r.x.p, total * 4, hipMemcpyDeviceToHost, ctx->stream));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (timing)
     fprintf(stderr, "[tts timing] diffusion: setup %.1f ms, time MLP + noise %.1f, %d steps %.1f (issued in %.1f, graph capture + instantiate %.1f), mel copy %.1f\n",
-            ms(t_begin, t_setup), ms(t_setup, t_pre), n_steps, ms(t_pre, t_loop), ms(t_pre, t_issued), t_capture, ms(t_loop, now()));
+            ms(t_begin, r.t_setup), ms(r.t_setup, t_pre), n_steps, ms(t_pre, t_loop), ms(t_pre, t_issued), t_capture, ms(t_loop, now()));
   return TTS_OK;
 }
-
-// tts_diffusion_multi_voice: tts_diffusion with candidate c conditioned on voice_latents[voice_of[c]] instead of the loaded model's latent. The voice enters the
-// stage at ONE place (the scale/shift of the code norm that ends latent_conditioner), and nothing is kept from one call to the next (the code embedding, h0 and the
-// hoisted integrator's ce16_all are rebuilt by every call from that call's conditioner output), so the table and the candidates' rows of it are all this adds:
-// one upload, no launch. The unconditioned sequences — the only ones share_uncond merges — never read a voice.
+int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, int n_steps, const float *noise, int noise_mode,
+                float *mel_out) {
+  if (!ctx->diff) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
+  if (!latents || !rows || !mel_out || B < 1 || n_steps < 2) return fail(ctx, TTS_ERR_ARG, "tts_diffusion: bad argument");
+  for (int c = 0; c < B; c++) if (rows[c] < 1 || rows[c] > 500) return fail(ctx, TTS_ERR_ARG, "latent rows %d out of range", rows[c]);
+  return diff_sample_with(ctx, latents, rows, B, nullptr, 0, nullptr, n_steps, noise, noise_mode, mel_out);
+}
 int diff_sample_voices(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, const float *voice_latents, int n_voices, const int32_t *voice_of,
                        int n_steps, const float *noise, int noise_mode, float *mel_out) {
-  DiffState *st = ctx->diff;
-  if (!st) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
+  if (!ctx->diff) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
   if (!latents || !rows || !mel_out || B < 1 || n_steps < 2 || !voice_latents || !voice_of) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_multi_voice: bad argument");
   if (n_voices < 1 || n_voices > (1 << 20)) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_multi_voice: %d voices", n_voices);
   for (int c = 0; c < B; c++) {
@@ -2376,35 +2424,12 @@ int diff_sample_voices(tts_ctx *ctx, const float *latents, const int32_t *rows, 
   const size_t nf = (size_t)n_voices * 2 * C;
   for (size_t i = 0; i < nf; i++)
     if (!std::isfinite(voice_latents[i])) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_multi_voice: voice %d holds a non-finite value", (int)(i / (2 * C)));
-  std::vector<float> up(nf + (size_t)B); // [n_voices][2048] floats | [B] ints
-  memcpy(up.data(), voice_latents, nf * 4);
-  memcpy(up.data() + nf, voice_of, (size_t)B * 4);
-  TTS_HIP(ctx, st->mv_buf.reserve(up.size() * 4));
-  TTS_HIP(ctx, hipMemcpy(st->mv_buf.p, up.data(), up.size() * 4, hipMemcpyHostToDevice));
-  struct Reset { DiffState *s; ~Reset() { s->mv_tab = nullptr; s->mv_idx = nullptr; } } reset{st}; // also when the call ends in an exception (api.cpp: guarded)
-  st->mv_tab = st->mv_buf.as<float>();
-  st->mv_idx = (const int *)(st->mv_buf.as<float>() + nf);
-  return diff_sample(ctx, latents, rows, B, n_steps, noise, noise_mode, mel_out);
+  return diff_sample_with(ctx, latents, rows, B, voice_latents, n_voices, voice_of, n_steps, noise, noise_mode, mel_out);
 }
 
 // ------------------------------------------------------------------------------------------------
 // diffusion session (tts_diff_session_*): in-flight batching for the sampling loop
 // ------------------------------------------------------------------------------------------------
-// A request's share of the session. Everything below was evaluated at admission for the request ALONE by the functions tts_diffusion runs (setup_batch,
-// precompute_time, precompute_integrator) and then moved or copied out of the single call's run state: a step of the joint layout only gathers from it.
-struct DiffSessReq {
-  int id = 0, slot = 0, n_cand = 0, n_steps = 0, sampler = 0, done = 0, cls = 0, packed = 0;
-  bool finished = false;
-  uint64_t seed = 0;
-  std::vector<int> T;        // frames per candidate
-  std::vector<int> seq_src;  // per sequence of the request (conditioned 0 .. n_cand - 1, then their unconditioned copies): its first row in the request's row buffers
-  int src_rows = 0;          // rows of those buffers (the request's own packed layout; its integrator layout without hoisting)
-  std::vector<int64_t> xoff; // candidate c's x in `x`
-  int64_t total = 0;
-  DevBuf ce16_all;           // hoisted: [n_steps][src_rows][1024] fp16
-  DevBuf code_emb, h0;       // not hoisted: [src_rows][1024] f32 each
-  DevBuf ss_all, tab, dtab, x, noise;
-};
 // the session's pinned options for the length of one session call: every option the diffusion stage reads between an admission's setup and a step's last kernel
 struct PinnedOptions {
   float gn_eps;
@@ -2428,21 +2453,11 @@ struct DiffSession {
   bool share_uncond = true, hoisted = false;
   double eta = 0;
   float k = 2.0f;
-  std::map<int, std::unique_ptr<DiffSessReq>> reqs; // by id: the order of admission
+  std::map<int, std::unique_ptr<DiffReq>> reqs; // by id: the order of admission
   std::vector<char> slot_busy;
-  int next_id = 0, captures = 0, n_live = 0;
+  int next_id = 0, captures = 0;
   bool dirty = true; // the membership changed since the layout was built
-  Layout lay;
-  Work wk;
-  DevBuf code_emb, h0, ce, ce16, inp16, xt16, net, ss_cur, ctr, req_tab, seq_req, seq_partner, seq_cand, seq_xoff, row_src, live;
-  hipGraph_t step_graph = nullptr;
-  hipGraphExec_t step_exec = nullptr;
-  void drop_step_graph() {
-    if (step_exec) (void)hipGraphExecDestroy(step_exec);
-    if (step_graph) (void)hipGraphDestroy(step_graph);
-    step_exec = nullptr; step_graph = nullptr;
-  }
-  ~DiffSession() { drop_step_graph(); }
+  StepBufs sb;       // the joint layout of the running requests
 };
 namespace {
 struct SessOptions {
@@ -2451,7 +2466,6 @@ struct SessOptions {
   SessOptions(tts_ctx *ctx, const DiffSession &s) : c(ctx), saved(PinnedOptions::of(ctx)) { s.pinned.put(ctx); }
   ~SessOptions() { saved.put(c); }
 };
-void take(DevBuf &dst, DevBuf &src) { std::swap(dst.p, src.p); std::swap(dst.cap, src.cap); }
 } // namespace
 
 void diff_session_close(tts_ctx *ctx) {
@@ -2489,37 +2503,24 @@ int diff_session_open(tts_ctx *ctx, int max_packed_rows, int max_requests) {
   s->slot_busy.assign((size_t)max_requests, 0);
   // all the step's buffers now, for the largest layout the session can hold: no admission reallocates what a captured step graph has baked in
   const size_t R = (size_t)s->buf_rows;
-  CHECK(s->wk.reserve(ctx, (int)R, (int)R / 8));
-  auto rz = [&](DevBuf &b, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(bytes);
-    return e == hipSuccess ? hipMemset(b.p, 0, b.cap) : e;
-  };
-  TTS_HIP(ctx, rz(s->ce16, R * C * 2));
-  TTS_HIP(ctx, rz(s->inp16, R * C * 2));
-  TTS_HIP(ctx, rz(s->xt16, (R + 2) * XTC * 2));
-  TTS_HIP(ctx, rz(s->net, R * 256 * 4));
-  if (!s->hoisted) {
-    TTS_HIP(ctx, rz(s->code_emb, R * C * 4));
-    TTS_HIP(ctx, rz(s->h0, R * C * 4));
-    TTS_HIP(ctx, rz(s->ce, R * C * 4));
-  }
-  TTS_HIP(ctx, rz(s->ss_cur, (size_t)max_requests * st->n_res() * 2 * C * 4));
-  TTS_HIP(ctx, rz(s->ctr, (size_t)max_requests * 4));
-  TTS_HIP(ctx, rz(s->req_tab, (size_t)max_requests * sizeof(SessReqDev)));
-  TTS_HIP(ctx, rz(s->live, (size_t)max_requests * 4));
+  StepBufs &sb = s->sb;
+  CHECK(sb.wk.reserve(ctx, (int)R, (int)R / 8));
+  CHECK(sb.reserve_rows(ctx, R, !s->hoisted));
+  if (!s->hoisted) TTS_HIP(ctx, reserve_zeroed(sb.h0, R * C * 4));
+  TTS_HIP(ctx, reserve_zeroed(sb.ss_cur, (size_t)max_requests * st->n_res() * 2 * C * 4));
+  TTS_HIP(ctx, reserve_zeroed(sb.ctr, (size_t)max_requests * 4));
   ctx->diff_session = s.release();
   return TTS_OK;
 }
 
-// Admission: the request alone through setup_batch / precompute_time / precompute_integrator — the single call's run state, which no step of the session reads —
-// and the results into storage the request owns. Nothing the captured step graph has baked in is written: the request joins the layout at the next step.
+// Admission: the request alone through prepare_request. Nothing the captured step graph has baked in is written: the request joins the layout at the next step.
 int diff_session_admit(tts_ctx *ctx, const tts_diff_request *rq) {
   DiffSession &S = *ctx->diff_session;
   DiffState *st = ctx->diff;
   int slot = -1;
   for (int i = 0; i < S.max_req && slot < 0; i++) if (!S.slot_busy[i]) slot = i;
   if (slot < 0) return fail(ctx, TTS_ERR_LIMIT, "tts_diff_session_admit: the session holds %d requests", S.max_req);
-  const int B = rq->n_cand, n_steps = rq->n_steps;
+  const int B = rq->n_cand;
   if (S.hoisted) { // a hoisted request owns n_steps x packed rows x 2 KB until it is collected: the single call's row cap bounds it, request by request
     const int cap = S.hoist > 1 ? S.hoist : HOIST_MAX_ROWS, packed = tts_host_diff_packed_rows(rq->rows, B);
     if (packed > cap)
@@ -2527,87 +2528,31 @@ int diff_session_admit(tts_ctx *ctx, const tts_diff_request *rq) {
                   "(open the session with hoist_integrator 0 for larger ones)", packed, cap);
   }
   SessOptions opts(ctx, S);
-  std::vector<int> L(rq->rows, rq->rows + B);
-  std::unique_ptr<DiffSessReq> r(new DiffSessReq());
-  r->slot = slot; r->n_cand = B; r->n_steps = n_steps; r->sampler = rq->sampler; r->seed = rq->seed;
-  struct Reset { DiffState *s; ~Reset() { s->mv_tab = nullptr; s->mv_idx = nullptr; } } reset{st};
-  if (rq->voice_latent2048) { // the request's voice as a one-row table, every candidate on row 0 (see diff_sample_voices)
-    const size_t nf = (size_t)2 * C;
-    std::vector<float> up(nf + (size_t)B, 0.f); // (an all-zero float is the int 0)
-    memcpy(up.data(), rq->voice_latent2048, nf * 4);
-    TTS_HIP(ctx, st->mv_buf.reserve(up.size() * 4));
-    TTS_HIP(ctx, hipMemcpy(st->mv_buf.p, up.data(), up.size() * 4, hipMemcpyHostToDevice));
-    st->mv_tab = st->mv_buf.as<float>();
-    st->mv_idx = (const int *)(st->mv_buf.as<float>() + nf);
-  }
-  CHECK(setup_batch(ctx, st, rq->latents, L, true, true));
-  Layout &lay = st->lay;
+  std::unique_ptr<DiffReq> r(new DiffReq());
+  // the request's voice as a one-row table, every candidate on row 0; the generator's streams are the candidates' indices in the request
+  ReqSpec sp{rq->latents, rq->rows, B, rq->n_steps, rq->sampler, rq->ddim_eta, (float)rq->cond_free_k, rq->voice_latent2048, 1, nullptr, rq->noise, TTS_NOISE_DEVICE,
+             nullptr, rq->seed, 0u, S.hoisted ? INT_MAX : 0, false};
+  CHECK(prepare_request(ctx, st, *r, sp));
+  const Layout &lay = st->sb.lay;
+  r->slot = slot;
   r->packed = lay.rows;
   r->cls = Layout::gn_class(lay.max_len());
-  const bool ddim = rq->sampler == 1;
-  const int n_vec = ddim && rq->ddim_eta == 0 ? 1 : n_steps + 1;
-  DiffSchedule sched;
-  sched.base_k = (float)rq->cond_free_k;
-  sched.build(n_steps);
-  if (ddim) sched.build_ddim(rq->ddim_eta);
-  std::vector<int> ts(n_steps);
-  for (int idx = 0; idx < n_steps; idx++) ts[idx] = sched.timestep_map[n_steps - 1 - idx];
-  CHECK(precompute_time(ctx, st, ts));
-  st->hoisted = S.hoisted;
-  if (S.hoisted) CHECK(precompute_integrator(ctx, st, n_steps));
   // the row buffers: where each of the request's sequences starts in them
-  const Layout &il = st->share_integ ? st->ilay : st->lay;
-  r->T.assign(lay.len.begin(), lay.len.begin() + B);
   r->seq_src.resize((size_t)2 * B);
   if (S.hoisted) {
-    r->src_rows = lay.rows;
     for (int s = 0; s < 2 * B; s++) r->seq_src[s] = lay.start[s];
-    take(r->ce16_all, st->ce16_all);
-  } else {
+  } else { // the integrator runs inside the session's step: its two timestep-independent inputs leave the single call's run state
+    const Layout &il = st->share_integ ? st->ilay : st->sb.lay;
     r->src_rows = il.rows;
     for (int s = 0; s < 2 * B; s++) r->seq_src[s] = st->share_integ ? st->ce_src_host[lay.start[s]] : lay.start[s];
     TTS_HIP(ctx, r->code_emb.reserve((size_t)il.rows * C * 4));
-    TTS_HIP(ctx, hipMemcpyAsync(r->code_emb.p, st->code_emb.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    TTS_HIP(ctx, hipMemcpyAsync(r->code_emb.p, st->sb.code_emb.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
     if (st->n_integ > 0) {
       TTS_HIP(ctx, r->h0.reserve((size_t)il.rows * C * 4));
-      TTS_HIP(ctx, hipMemcpyAsync(r->h0.p, st->h0.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      TTS_HIP(ctx, hipMemcpyAsync(r->h0.p, st->sb.h0.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
     }
   }
-  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  take(r->ss_all, st->ss_all);
-  // x and the noise, request-local in tts_diffusion's arrangement: [cand][100][T_c]; block 0 = x_T, block 1 + idx = step idx
-  r->xoff.resize(B);
-  for (int c = 0; c < B; c++) { r->xoff[c] = r->total; r->total += (int64_t)100 * lay.len[c]; }
-  const int64_t total = r->total;
-  TTS_HIP(ctx, r->x.reserve(total * 4));
-  if (rq->noise) {
-    std::vector<float> hn((size_t)total * n_vec);
-    size_t src = 0;
-    for (int c = 0; c < B; c++)
-      for (int k = 0; k < n_vec; k++) {
-        memcpy(hn.data() + (size_t)k * total + r->xoff[c], rq->noise + src, (size_t)100 * lay.len[c] * 4);
-        src += (size_t)100 * lay.len[c];
-      }
-    TTS_HIP(ctx, r->noise.reserve(hn.size() * 4));
-    TTS_HIP(ctx, hipMemcpy(r->noise.p, hn.data(), hn.size() * 4, hipMemcpyHostToDevice));
-    TTS_HIP(ctx, hipMemcpyAsync(r->x.p, r->noise.p, total * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  } else {
-    for (int c = 0; c < B; c++) {
-      const int64_t n = (int64_t)100 * lay.len[c];
-      philox_fill_kernel<<<(int)((n + 255) / 256), 256, 0, ctx->stream>>>(r->x.as<float>() + r->xoff[c], n, r->seed, (uint32_t)c, 0xFFFFFFFFu);
-    }
-    TTS_HIP(ctx, hipGetLastError());
-  }
-  std::vector<StepEntry> tab;
-  std::vector<DdimEntry> dtab;
-  build_step_tables(sched, n_steps, ddim, rq->noise != nullptr && n_vec > 1, total, tab, dtab);
-  TTS_HIP(ctx, r->tab.reserve(tab.size() * sizeof(StepEntry)));
-  TTS_HIP(ctx, hipMemcpy(r->tab.p, tab.data(), tab.size() * sizeof(StepEntry), hipMemcpyHostToDevice));
-  if (ddim) {
-    TTS_HIP(ctx, r->dtab.reserve(dtab.size() * sizeof(DdimEntry)));
-    TTS_HIP(ctx, hipMemcpy(r->dtab.p, dtab.data(), dtab.size() * sizeof(DdimEntry), hipMemcpyHostToDevice));
-  }
-  TTS_HIP(ctx, hipMemsetAsync(S.ctr.as<int>() + slot, 0, 4, ctx->stream)); // the slot of no sequence of the layout a captured graph holds
+  TTS_HIP(ctx, hipMemsetAsync(S.sb.ctr.as<int>() + slot, 0, 4, ctx->stream)); // the slot of no sequence of the layout a captured graph holds
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   r->id = S.next_id++;
   S.slot_busy[slot] = 1;
@@ -2621,98 +2566,52 @@ int diff_session_admit(tts_ctx *ctx, const tts_diff_request *rq) {
 // (Layout::gn_parts); a request's conditioned sequences, then their unconditioned copies.
 static int diff_session_rebuild(tts_ctx *ctx, DiffSession &S) {
   DiffState *st = ctx->diff;
-  std::vector<DiffSessReq *> live;
+  StepBufs &sb = S.sb;
+  std::vector<DiffReq *> live;
   for (auto &kv : S.reqs) if (!kv.second->finished) live.push_back(kv.second.get());
-  std::stable_sort(live.begin(), live.end(), [](const DiffSessReq *a, const DiffSessReq *b) { return a->cls < b->cls; });
+  std::stable_sort(live.begin(), live.end(), [](const DiffReq *a, const DiffReq *b) { return a->cls < b->cls; });
   std::vector<int> lens, seq_req, seq_cand, cls, seq_local;
   std::vector<int64_t> xoff;
-  std::vector<DiffSessReq *> owner;
-  for (DiffSessReq *r : live)
+  std::vector<DiffReq *> owner;
+  for (DiffReq *r : live)
     for (int ls = 0; ls < 2 * r->n_cand; ls++) {
       const int c = ls % r->n_cand;
       lens.push_back(r->T[c]); seq_req.push_back(r->slot); seq_cand.push_back(c); cls.push_back(r->cls); seq_local.push_back(ls);
       xoff.push_back(r->xoff[c]); owner.push_back(r);
     }
-  Layout &lay = S.lay;
+  Layout &lay = sb.lay;
   CHECK(lay.build(ctx, lens));
   if (lay.rows > S.buf_rows) return fail(ctx, TTS_ERR_STATE, "diffusion session: a layout of %d rows in buffers of %d", lay.rows, S.buf_rows);
   const size_t ss_stride = (size_t)st->n_res() * 2 * C;
-  CHECK(lay.set_seq_step(ctx, seq_req, (int)ss_stride)); // block of ss_cur = the request's slot (diff_session_begin_kernel writes the same)
+  CHECK(lay.set_seq_step(ctx, seq_req, (int)ss_stride)); // block of ss_cur = the request's slot
   CHECK(lay.set_gn_parts(ctx, cls));
   const int ns = lay.ns;
   std::vector<int> partner(ns, -1), row_src(lay.rows, -1);
   for (int s = 0; s < ns; s++) {
-    const DiffSessReq *r = owner[s];
+    const DiffReq *r = owner[s];
     if (seq_local[s] < r->n_cand) partner[s] = lay.start[s + r->n_cand]; // the request's sequences are consecutive
     for (int t = 0; t < lens[s]; t++) row_src[lay.start[s] + t] = r->seq_src[seq_local[s]] + t;
   }
-  std::vector<SessReqDev> tab((size_t)S.max_req, SessReqDev{});
+  std::vector<ReqDev> tab((size_t)S.max_req, ReqDev{});
   std::vector<int> slots;
-  for (DiffSessReq *r : live) {
-    SessReqDev &d = tab[r->slot];
-    d.ss_all = r->ss_all.as<float>(); d.tab = r->tab.as<StepEntry>(); d.dtab = r->dtab.as<DdimEntry>(); d.ce16_all = r->ce16_all.as<__half>();
-    d.x = r->x.as<float>(); d.noise = r->noise.as<float>(); d.seed = r->seed; d.n_steps = r->n_steps; d.sampler = r->sampler; d.rows_local = r->src_rows;
+  for (DiffReq *r : live) {
+    tab[r->slot] = r->dev();
     slots.push_back(r->slot);
   }
-  auto up = [&](DevBuf &b, const void *src, size_t bytes) -> hipError_t {
-    hipError_t e = b.reserve(bytes);
-    return e == hipSuccess ? hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) : e;
-  };
-  TTS_HIP(ctx, up(S.seq_req, seq_req.data(), (size_t)ns * 4));
-  TTS_HIP(ctx, up(S.seq_partner, partner.data(), (size_t)ns * 4));
-  TTS_HIP(ctx, up(S.seq_cand, seq_cand.data(), (size_t)ns * 4));
-  TTS_HIP(ctx, up(S.seq_xoff, xoff.data(), (size_t)ns * 8));
-  TTS_HIP(ctx, up(S.row_src, row_src.data(), (size_t)lay.rows * 4));
-  TTS_HIP(ctx, up(S.req_tab, tab.data(), tab.size() * sizeof(SessReqDev)));
-  TTS_HIP(ctx, up(S.live, slots.data(), slots.size() * 4));
-  S.n_live = (int)slots.size();
+  CHECK(sb.set_tables(ctx, tab, slots, xoff, seq_req, partner, seq_cand, row_src));
   // rows that belonged to a sequence of the previous layout may be guard rows now: the operand the k = 3 taps read across sequence ends starts from zero
-  TTS_HIP(ctx, hipMemsetAsync(S.xt16.p, 0, S.xt16.cap, ctx->stream));
+  TTS_HIP(ctx, hipMemsetAsync(sb.xt16.p, 0, sb.xt16.cap, ctx->stream));
   if (!S.hoisted) { // the integrator runs inside the step: its two timestep-independent inputs, sequence by sequence from the requests' buffers
-    TTS_HIP(ctx, hipMemsetAsync(S.code_emb.p, 0, (size_t)lay.rows * C * 4, ctx->stream));
-    TTS_HIP(ctx, hipMemsetAsync(S.h0.p, 0, (size_t)lay.rows * C * 4, ctx->stream));
+    TTS_HIP(ctx, hipMemsetAsync(sb.code_emb.p, 0, (size_t)lay.rows * C * 4, ctx->stream));
+    TTS_HIP(ctx, hipMemsetAsync(sb.h0.p, 0, (size_t)lay.rows * C * 4, ctx->stream));
     for (int s = 0; s < ns; s++) {
-      const DiffSessReq *r = owner[s];
+      const DiffReq *r = owner[s];
       const size_t dst = (size_t)lay.start[s] * C, src = (size_t)r->seq_src[seq_local[s]] * C, n = (size_t)lens[s] * C * 4;
-      TTS_HIP(ctx, hipMemcpyAsync(S.code_emb.as<float>() + dst, r->code_emb.as<float>() + src, n, hipMemcpyDeviceToDevice, ctx->stream));
-      if (st->n_integ > 0) TTS_HIP(ctx, hipMemcpyAsync(S.h0.as<float>() + dst, r->h0.as<float>() + src, n, hipMemcpyDeviceToDevice, ctx->stream));
+      TTS_HIP(ctx, hipMemcpyAsync(sb.code_emb.as<float>() + dst, r->code_emb.as<float>() + src, n, hipMemcpyDeviceToDevice, ctx->stream));
+      if (st->n_integ > 0) TTS_HIP(ctx, hipMemcpyAsync(sb.h0.as<float>() + dst, r->h0.as<float>() + src, n, hipMemcpyDeviceToDevice, ctx->stream));
     }
   }
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return TTS_OK;
-}
-
-// One step of the joint layout: the single call's step with its four per-batch pieces replaced by their per-sequence forms (see the diff_session_* kernels); the
-// network between them is network_integrator / network_body, the halves network_forward runs.
-static int diff_session_enqueue_step(tts_ctx *ctx, DiffSession &S) {
-  DiffState *st = ctx->diff;
-  Layout &lay = S.lay;
-  const size_t ss_stride = (size_t)st->n_res() * 2 * C;
-  const SessReqDev *req = S.req_tab.as<SessReqDev>();
-  const int *ctr = S.ctr.as<int>(), *seq_req = S.seq_req.as<int>(), *partner = S.seq_partner.as<int>();
-  float *ss = S.ss_cur.as<float>();
-  diff_session_begin_kernel<<<dim3(16, S.n_live), 256, 0, ctx->stream>>>(req, ctr, S.live.as<int>(), ss_stride, ss, seq_req, lay.ns, lay.d_seq_step.as<int>());
-  diff_session_xt_kernel<<<lay.rows, 128, 0, ctx->stream>>>(req, seq_req, S.seq_xoff.as<int64_t>(), partner, lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(),
-                                                           lay.d_len.as<int>(), S.xt16.as<__half>() + XTC);
-  st->gn_site = 0;
-  S.wk.st_x = S.wk.st_h = nullptr;
-  __half *ce16 = S.ce16.as<__half>();
-  if (S.hoisted) {
-    diff_session_row_select_kernel<<<lay.rows, 128, 0, ctx->stream>>>(req, ctr, seq_req, lay.d_row_seq.as<int>(), S.row_src.as<int>(), (uint4 *)ce16);
-  } else {
-    float *ce = S.ce.as<float>();
-    if (st->n_integ == 0) TTS_HIP(ctx, hipMemcpyAsync(ce, S.code_emb.p, (size_t)lay.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    CHECK(network_integrator(ctx, st, lay, S.wk, ce, S.code_emb.as<float>(), S.h0.as<float>(), ss));
-    to_f16_kernel<<<lay.rows, 256, 0, ctx->stream>>>(ce, lay.d_row_seq.as<int>(), ce16);
-  }
-  CHECK(network_body(ctx, st, lay, S.wk, ce16, S.xt16.as<__half>(), S.inp16.as<__half>(), S.net.as<float>(), ss));
-  {
-    ProfScope ps(ctx, "diff_update");
-    diff_session_update_kernel<<<lay.rows, 128, 0, ctx->stream>>>(S.net.as<float>(), req, ctr, seq_req, S.seq_xoff.as<int64_t>(), partner, S.seq_cand.as<int>(),
-                                                                 lay.d_row_seq.as<int>(), lay.d_row_t.as<int>(), lay.d_len.as<int>());
-  }
-  diff_session_advance_kernel<<<(S.n_live + 63) / 64, 64, 0, ctx->stream>>>(req, S.ctr.as<int>(), S.live.as<int>(), S.n_live);
-  TTS_HIP(ctx, hipGetLastError());
   return TTS_OK;
 }
 
@@ -2723,31 +2622,24 @@ int diff_session_step(tts_ctx *ctx) {
   for (auto &kv : S.reqs) running += kv.second->finished ? 0 : 1;
   if (running == 0) return 0;
   SessOptions opts(ctx, S);
-  st->lat = false; // the batch path's GroupNorm, always
-  static const bool no_graph_env = getenv("TTS_NO_GRAPH") != nullptr;
+  // the route of every step (network_forward): the integrator on the joint layout itself or hoisted, the batch path's GroupNorm
+  st->share_integ = false; st->hoisted = S.hoisted; st->lat = false;
   if (S.dirty) { // admits, finishes and cancels since the last step: one rebuild, one capture
-    S.drop_step_graph();
+    S.sb.drop_step_graph();
     CHECK(diff_session_rebuild(ctx, S));
-    if (S.graph && !no_graph_env) {
-      ctx->capturing = true;
-      hipError_t eb = hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal);
-      int rc = eb == hipSuccess ? diff_session_enqueue_step(ctx, S) : TTS_OK;
-      hipError_t ee = eb == hipSuccess ? hipStreamEndCapture(ctx->stream, &S.step_graph) : eb;
-      ctx->capturing = false;
-      if (rc) return rc;
-      TTS_HIP(ctx, ee);
-      TTS_HIP(ctx, hipGraphInstantiate(&S.step_exec, S.step_graph, nullptr, nullptr, 0));
+    if (S.graph && !no_graph_env()) {
+      CHECK(capture_step(ctx, st, S.sb));
       S.captures++;
     }
     S.dirty = false;
   }
-  if (S.step_exec) TTS_HIP(ctx, hipGraphLaunch(S.step_exec, ctx->stream));
-  else CHECK(diff_session_enqueue_step(ctx, S));
+  if (S.sb.step_exec) TTS_HIP(ctx, hipGraphLaunch(S.sb.step_exec, ctx->stream));
+  else CHECK(enqueue_step(ctx, st, S.sb));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // the host's own count: step counts are fixed, no device read detects a finish
   running = 0;
   for (auto &kv : S.reqs) {
-    DiffSessReq &r = *kv.second;
+    DiffReq &r = *kv.second;
     if (r.finished) continue;
     if (++r.done >= r.n_steps) { r.finished = true; S.dirty = true; }
     else running++;
