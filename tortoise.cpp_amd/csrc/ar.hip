@@ -22,7 +22,7 @@ namespace tts {
 
 static constexpr int D = 1024, NH = 16, HD = 64, FF = 4096, V = TTS_VOCAB_MEL, VPAD = 8256;
 
-// LayerNorm-GEMV decode kernels: split-precision fp16 MFMA (default: three products per K step, 2^-22 relative) or exact-f32 MFMA
+// LayerNorm-GEMV decode kernels: split-precision fp16 MFMA (default: three products per K step, operands carried to 2^-22 relative; f32 accumulation on top, see dec_ln_gemv_kernel) or exact-f32 MFMA
 // products (option "dec_f32_mfma" = 1, read by tts_load_ar: it selects the weight packing; ArState::f32_mfma).
 // Weight slabs of the decode step are streamed once per step by exactly one workgroup: non-temporal loads keep them from displacing the
 // activations / KV rows in L2 (MI355X_MICROARCH.md, row "nt-weights"; measured 1 008 vs 1 036 us per step, profiles/r3_bench_n1.json).
@@ -722,7 +722,9 @@ __device__ __forceinline__ void dec_layernorm(float4 (&x)[16], const float *__re
   }
 }
 
-// SPLIT: 0 = fp32 MFMA on f32 weights, 1 = split-precision fp16 MFMA (f32-exact to 2^-22), 2 = fp16 WEIGHTS (rounded once at load:
+// SPLIT: 0 = fp32 MFMA on f32 weights, 1 = split-precision fp16 MFMA (every PRODUCT to 2^-22 relative; the sum adds the f32 accumulation of 256 products per wave:
+// measured against float64 <= 0.2 x 2^-22 sum |x||w| on Gaussian columns, 1.1 on a row with one outlier channel; the f32 rounding of sum + bias comes on top,
+// tests/test_ar_dec_kernels_gpu.py), 2 = fp16 WEIGHTS (rounded once at load:
 // half the bytes streamed; the activations keep their hi + lo split) — the throughput mode of SURVEY 8d, option "ar_weights";
 // 3 = OCP fp8 (e4m3) WEIGHTS with a power-of-two scale per output column (a quarter of the bytes): converted to fp16 in
 // registers (exact: every e4m3 value is an fp16 value), multiplied on the fp16 MFMA against the hi + lo split activations.
@@ -812,7 +814,8 @@ __global__ __launch_bounds__(256) void dec_ln_gemv_kernel(DecLnArgs a_in) {
   floatx4 acc;
   if (SPLIT) {
     // split precision on the fp16 MFMA: x = xh + xl, 64 W = wh + wl; wh.xh + wl.xh + wh.xl (the dropped wl.xl term is
-    // 2^-22 relative), 24 MFMAs of 16 cycles instead of 64 fp32 MFMAs of 32
+    // 2^-22 relative to its product; an xl below 2^-14 is an fp16 subnormal and reaches the matrix pipe as one, not as 0: measured),
+    // 24 MFMAs of 16 cycles instead of 64 fp32 MFMAs of 32
     floatx4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0;
 #pragma unroll
     for (int s = 0; s < 8; s++) {
