@@ -20,6 +20,7 @@ AR_MASK_STOP = 1
 AR_RETIRE = 2
 AR_ROW_CONTROLS = 8  # tts_ar_session_open only
 NOISE_REFERENCE, NOISE_DEVICE = 0, 1
+SAMPLER_DDPM, SAMPLER_DDIM, SAMPLER_DPMPP_2M = 0, 1, 3  # option diff_sampler, tts_diff_request.sampler (2 is not a sampler)
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -117,7 +118,8 @@ def lib():
         "tts_vocoder": (ci, [vp, _f32p, _i32p, ci, vp, ci, _f32p]),
         "tts_vocoder_chunk": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p, C.POINTER(ci)]),
         "tts_write_wav": (ci, [C.c_char_p, _f32p, C.c_int64, ci]),
-        "tts_host_schedule": (ci, [ci, _i32p] + [_f32p] * 7), "tts_host_schedule_ddim": (ci, [ci, C.c_double, _f64p, _f64p, _f32p, _f32p, _f32p]), "tts_host_timestep_embedding": (None, [ci, _f32p]),
+        "tts_host_schedule": (ci, [ci, _i32p] + [_f32p] * 7), "tts_host_schedule_ddim": (ci, [ci, C.c_double, _f64p, _f64p, _f32p, _f32p, _f32p]),
+        "tts_host_schedule_dpmpp": (ci, [ci, _f32p, _f32p, _f32p, _i32p]), "tts_host_timestep_embedding": (None, [ci, _f32p]),
         "tts_host_rel_bucket": (ci, [ci, ci]), "tts_host_pad_codes": (ci, [_i32p, ci, _i32p]), "tts_host_trimmed_rows": (ci, [_i32p]),
         "tts_host_fp8_e4m3": (C.c_uint8, [cf]), "tts_host_mel_frames": (ci, [C.c_int64]),
         "tts_host_mel_diffusion100": (ci, [_f32p, C.c_int64, ci, _f32p]), "tts_host_mel_voice80": (ci, [_f32p, C.c_int64, vp, _f32p]),
@@ -595,8 +597,9 @@ class Engine:
         return out
 
     def diffusion(self, latents_list, n_steps=80, noise=None, noise_mode=NOISE_REFERENCE, voice_latents=None, voice_of_candidate=None):
-        """latents_list: list of [L_c,1024]. noise: list of [(n_steps+1), 100*T_c] or None (option diff_sampler = 1 with ddim_eta = 0: list of x_T [100*T_c]).
-        Returns list of mel [100,T_c]. The sampler, its eta and the guidance strength are engine options (set_option: diff_sampler, ddim_eta, cond_free_k).
+        """latents_list: list of [L_c,1024]. noise: list of [(n_steps+1), 100*T_c] or None (option diff_sampler = 1 with ddim_eta = 0, and
+        diff_sampler = 3: list of x_T [100*T_c]). Returns list of mel [100,T_c]. The sampler, its eta and the guidance strength are engine options (set_option:
+        diff_sampler 0 = ancestral DDPM, 1 = DDIM, 3 = DPM-Solver++(2M), deterministic: ddim_eta is checked and not read; ddim_eta; cond_free_k).
         voice_latents [V, 2048] + voice_of_candidate [B]: candidate c is conditioned on voice_latents[voice_of_candidate[c]] instead of the loaded model's
         latent (tts_diffusion_multi_voice)."""
         rows = np.array([len(l) for l in latents_list], np.int32)
@@ -625,8 +628,8 @@ class Engine:
         self._diff_frames = {}
 
     def diff_session_admit(self, latents_list, n_steps=None, sampler=None, ddim_eta=None, cond_free_k=None, voice_latent=None, noise=None, seed=0):
-        """Admits one request: latents_list as in diffusion(); noise: list of [(n_steps+1), 100*T_c] (deterministic DDIM: x_T [100*T_c]) or None = the device
-        generator under `seed`; voice_latent [2048] or None = the loaded model's. Arguments left None take the session's pinned value (tts_diff_request_init).
+        """Admits one request: latents_list as in diffusion(); noise: list of [(n_steps+1), 100*T_c] (deterministic DDIM and sampler = 3, DPM-Solver++(2M):
+        x_T [100*T_c]) or None = the device generator under `seed`; sampler: SAMPLER_DDPM (0), SAMPLER_DDIM (1) or SAMPLER_DPMPP_2M (3); voice_latent [2048] or None = the loaded model's. Arguments left None take the session's pinned value (tts_diff_request_init).
         Returns the request id. The mel diff_session_collect() returns is bit for bit what diffusion() returns for the request alone."""
         req = DiffRequest()
         req.struct_size = C.sizeof(DiffRequest)
@@ -738,6 +741,17 @@ def host_schedule_ddim(n_steps, eta=0.0):
     return dict(acp=acp, acp_prev=prev, c_x0=f[0], c_eps=f[1], sigma=f[2])
 
 
+def host_schedule_dpmpp(n_steps):
+    """The DPM-Solver++(2M) scalars of option diff_sampler = 3 (host arithmetic, no device needed), index = respaced t: dict of a, b, c (float32) and order (int32;
+    1 at t = n_steps - 1, 1 and 0, else 2): x_next = a x + b x0 + c x0_prev."""
+    f = [np.empty(n_steps, np.float32) for _ in range(3)]
+    order = np.empty(n_steps, np.int32)
+    rc = lib().tts_host_schedule_dpmpp(n_steps, *f, order)
+    if rc:
+        raise TtsError("tts_host_schedule_dpmpp failed (%d)" % rc)
+    return dict(a=f[0], b=f[1], c=f[2], order=order)
+
+
 def host_timestep_embedding(t):
     out = np.empty(1024, np.float32)
     lib().tts_host_timestep_embedding(int(t), out)
@@ -833,7 +847,7 @@ def host_diff_packed_rows(latent_rows):
 def host_diff_request_check(max_packed_rows, latents=None, rows=None, n_cand=None, n_steps=80, sampler=0, ddim_eta=0.0, cond_free_k=2.0, voice=None, struct_size=None,
                             null_latents=False, null_rows=False):
     """The status tts_diff_session_admit's descriptor checks return for these fields in a session with max_packed_rows free rows (no GPU). latents: list of
-    [L_c, 1024]; rows / n_cand override what the list implies."""
+    [L_c, 1024]; rows / n_cand override what the list implies. sampler: 0, 1 or 3 (DPM-Solver++(2M)) pass, as for tts_set_option("diff_sampler")."""
     lat = np.ascontiguousarray(np.concatenate([np.asarray(l, np.float32).reshape(-1, DMODEL) for l in latents]))
     rw = np.ascontiguousarray([len(l) for l in latents] if rows is None else rows, np.int32)
     v = None if voice is None else np.ascontiguousarray(voice, np.float32).reshape(2 * DMODEL)

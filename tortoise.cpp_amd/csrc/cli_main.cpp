@@ -35,7 +35,8 @@
 //   tts_vocoder call and their audio is written to --output in message order as ONE file. --diffusion-latent: none (every speaker uses the model's own latent)
 //   or one per --voice; anything else is a usage error (exit 1) before a model is loaded. Not with --devices > 1: the conditioning broadcast carries one voice.
 //   --dry-run 1 prints one line per chunk ("chunk k: voice v, n text ids") and exits 0.
-// --sampler ddpm|ddim (default ddpm = the reference's ancestral loop; ddim = upstream tortoise-tts' ddim_sample, option diff_sampler), --ddim-eta <x> (0 .. 1, default 0 =
+// --sampler ddpm|ddim|dpmpp2m (default ddpm = the reference's ancestral loop; ddim = upstream tortoise-tts' ddim_sample; dpmpp2m = DPM-Solver++(2M), the second-order
+//   multistep solver of upstream's fast presets, deterministic: --ddim-eta is checked and not read; option diff_sampler), --ddim-eta <x> (0 .. 1, default 0 =
 //   deterministic) and --cond-free-k <x> (guidance strength, default 2.0): the diffusion sampler behind --steps, which keeps its meaning. Another sampler name or a value
 //   out of range is a usage error (exit 1) before a model is loaded or a worker started. --devices N workers receive the flags with the rest of the command line;
 //   --timing 1 echoes them ("[timing] sampler ...", one line per process).
@@ -181,7 +182,7 @@ int main(int argc, char **argv) {
     if (bad) { fprintf(stderr, "--stream serves one candidate of one voice through the HiFi-GAN decoder: it cannot be combined with %s\n", bad); return 1; }
     if (stream_stride < 1) { fprintf(stderr, "--stream-stride %d: at least 1\n", stream_stride); return 1; }
   }
-  if (sampler != "ddpm" && sampler != "ddim") { fprintf(stderr, "--sampler %s: ddpm or ddim\n", sampler.c_str()); return 1; }
+  if (sampler != "ddpm" && sampler != "ddim" && sampler != "dpmpp2m") { fprintf(stderr, "--sampler %s: ddpm, ddim or dpmpp2m\n", sampler.c_str()); return 1; }
   if (!(ddim_eta >= 0.0 && ddim_eta <= 1.0)) { fprintf(stderr, "--ddim-eta %g: a value in 0 .. 1\n", ddim_eta); return 1; }
   if (!(cond_free_k >= 0.0) || !std::isfinite(cond_free_k)) { fprintf(stderr, "--cond-free-k %g: a finite value >= 0\n", cond_free_k); return 1; }
   if (!std::isfinite(ar_temp) || !((float)ar_temp > 0) || !std::isfinite((float)ar_temp)) { fprintf(stderr, "--temperature %g: a finite value > 0\n", ar_temp); return 1; }
@@ -327,7 +328,7 @@ int main(int argc, char **argv) {
   if (have_seed) tts_seed(ctx, (uint32_t)seed);
   for (const auto &kv : engine_options)
     if (tts_set_option(ctx, kv.first.c_str(), kv.second)) return die(ctx, "--option");
-  if ((have_sampler && tts_set_option(ctx, "diff_sampler", sampler == "ddim" ? 1.0 : 0.0)) || (have_eta && tts_set_option(ctx, "ddim_eta", ddim_eta)) ||
+  if ((have_sampler && tts_set_option(ctx, "diff_sampler", sampler == "dpmpp2m" ? (double)TTS_SAMPLER_DPMPP_2M : sampler == "ddim" ? (double)TTS_SAMPLER_DDIM : (double)TTS_SAMPLER_DDPM)) || (have_eta && tts_set_option(ctx, "ddim_eta", ddim_eta)) ||
       (have_k && tts_set_option(ctx, "cond_free_k", cond_free_k)))
     return die(ctx, "--sampler");
   if ((have_temp && tts_set_option(ctx, "ar_temperature", ar_temp)) || (have_top_k && tts_set_option(ctx, "ar_top_k", ar_top_k)) ||

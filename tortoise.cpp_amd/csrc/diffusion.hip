@@ -756,22 +756,53 @@ __device__ __forceinline__ float ddpm_step_value(const StepScalars &sc, float ep
 // ancestral step (guidance k, sqrt_recip, sqrt_recipm1, noise block, generator key) plus this step's DdimEntry. The learned variance is not read. Every f32 operation
 // is rounded once, for the reason above: the numpy restatement the tests hold this to performs exactly these roundings.
 struct DdimEntry { float c_x0, c_eps, sigma, pad; };
-__device__ __forceinline__ float ddim_step_value(const StepScalars &sc, const DdimEntry &d, float eps_c, float eps_u, float xv, const float *__restrict__ noise, size_t xi,
-                                                 uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
-  float outv;
+// The guided, clipped x0 prediction of a step (p_mean_variance with clip_denoised) and the scaled x it came from: the ONE statement of it for the DDIM and the
+// DPM-Solver++ bodies, so that a first-order step of the latter cannot drift from the former.
+struct GuidedX0 { float xs, x0; };
+__device__ __forceinline__ GuidedX0 guided_clipped_x0(const StepScalars &sc, float eps_c, float eps_u, float xv) {
+  GuidedX0 g;
   {
 #pragma clang fp contract(off)
     const float eps_g = (1 + sc.cfk) * eps_c - sc.cfk * eps_u;
-    const float xs = sc.sqrt_recip * xv;
-    float x0 = xs - sc.sqrt_recipm1 * eps_g;
-    x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    const float eps_h = (xs - x0) / sc.sqrt_recipm1; // always re-derived from the clipped x0, as upstream (_predict_eps_from_xstart)
-    outv = d.c_x0 * x0 + d.c_eps * eps_h;
+    g.xs = sc.sqrt_recip * xv;
+    const float x0 = g.xs - sc.sqrt_recipm1 * eps_g;
+    g.x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+  }
+  return g;
+}
+__device__ __forceinline__ float ddim_value_from_x0(const StepScalars &sc, const DdimEntry &d, const GuidedX0 &g, const float *__restrict__ noise, size_t xi,
+                                                    uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
+  float outv;
+  {
+#pragma clang fp contract(off)
+    const float eps_h = (g.xs - g.x0) / sc.sqrt_recipm1; // always re-derived from the clipped x0, as upstream (_predict_eps_from_xstart)
+    outv = d.c_x0 * g.x0 + d.c_eps * eps_h;
     if (!sc.is_last && d.sigma != 0.0f) {
       const float nz = noise ? noise[xi] : philox_normal(seed, stream, step, idx);
       outv = outv + d.sigma * nz;
     }
   }
+  return outv;
+}
+__device__ __forceinline__ float ddim_step_value(const StepScalars &sc, const DdimEntry &d, float eps_c, float eps_u, float xv, const float *__restrict__ noise, size_t xi,
+                                                 uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
+  return ddim_value_from_x0(sc, d, guided_clipped_x0(sc, eps_c, eps_u, xv), noise, xi, seed, stream, step, idx);
+}
+// DPM-Solver++(2M) (Lu et al. 2022; upstream tortoise-tts' fast presets; the reference has no such sampler) on the same guided, clipped x0. DpmEntry: this step's
+// scalars from DiffSchedule::build_dpmpp. A first-order step IS the DDIM eta-0 step on this step's DdimEntry (sigma = 0: no noise is read); a second-order step adds
+// the previous step's x0, which every step leaves in the request's d_prev (layout of x) after reading it. One rounding per f32 operation, as above.
+struct DpmEntry { float a, b, c; int order; };
+__device__ __forceinline__ float dpmpp_step_value(const StepScalars &sc, const DdimEntry &d, const DpmEntry &p, float eps_c, float eps_u, float xv,
+                                                  float *__restrict__ d_prev, size_t xi) {
+  const GuidedX0 g = guided_clipped_x0(sc, eps_c, eps_u, xv);
+  float outv;
+  if (p.order == 2) {
+#pragma clang fp contract(off)
+    outv = (p.a * xv + p.b * g.x0) + p.c * d_prev[xi];
+  } else {
+    outv = ddim_value_from_x0(sc, d, g, nullptr, xi, 0, 0, 0, 0);
+  }
+  d_prev[xi] = g.x0;
   return outv;
 }
 
@@ -781,9 +812,11 @@ __device__ __forceinline__ float ddim_step_value(const StepScalars &sc, const Dd
 struct ReqDev {
   const float *ss_all;     // [n_steps][n_res][2048]: the request's scale / shift blocks (precompute_time)
   const StepEntry *tab;    // [n_steps]
-  const DdimEntry *dtab;   // [n_steps], sampler 1 only
+  const DdimEntry *dtab;   // [n_steps], samplers 1 and 3 (3: the eta-0 table, read by its first-order steps)
+  const DpmEntry *ptab;    // [n_steps], sampler 3 only
   const __half *ce16_all;  // hoisted integrator: [n_steps][rows_local][1024], else null
   float *x;                // [cand][100][T_c] (f32, reference layout)
+  float *d_prev;           // sampler 3 only: the previous step's clipped x0 in the layout of x; written by every step, read from the request's second step on
   const float *noise;      // the request's noise blocks in the layout of x (StepEntry::noise_off), or null: the device generator under `seed`
   unsigned long long seed;
   int n_steps, sampler, rows_local;
@@ -837,7 +870,7 @@ __global__ __launch_bounds__(128) void step_row_select_kernel(const ReqDev *__re
   dst[(size_t)r * (C / 8) + threadIdx.x] = v;
 }
 // The sampler update, in place on the requests' x. net: [rows][256] f32 (channels 0..99 eps, 100..199 variance logits). Per sequence: the request's StepEntry /
-// DdimEntry at the request's step, its sampler, its noise block or generator key (stream = the request's base + the candidate's index in it), and the unconditioned
+// DdimEntry / DpmEntry at the request's step, its sampler, its noise block or generator key (stream = the request's base + the candidate's index in it), and the unconditioned
 // partner's first row from a table. Sequences of a request that has run all its steps are left untouched. grid: rows; block 128.
 __global__ __launch_bounds__(128) void step_update_kernel(const float *__restrict__ net, const ReqDev *__restrict__ req, const int *__restrict__ ctr,
                                                           const int *__restrict__ seq_req, const int64_t *__restrict__ seq_xoff,
@@ -860,6 +893,10 @@ __global__ __launch_bounds__(128) void step_update_kernel(const float *__restric
   if (q.sampler == 1) {
     const DdimEntry d = q.dtab[k];
     q.x[xi] = ddim_step_value(e.sc, d, eps_c, eps_u, q.x[xi], noise, xi, q.seed, stream, e.philox_step, idx);
+  } else if (q.sampler == 3) {
+    const DdimEntry d = q.dtab[k];
+    const DpmEntry pe = q.ptab[k];
+    q.x[xi] = dpmpp_step_value(e.sc, d, pe, eps_c, eps_u, q.x[xi], q.d_prev, xi);
   } else {
     const float var_c = net[(size_t)r * 256 + 100 + ch];
     q.x[xi] = ddpm_step_value(e.sc, eps_c, var_c, eps_u, q.x[xi], noise, xi, q.seed, stream, e.philox_step, idx);
@@ -1010,13 +1047,13 @@ struct DiffReq {
   uint32_t stream_base = 0;  // generator stream of candidate 0
   bool host_noise = false;   // the steps read `noise` (block 0 = x_T, block 1 + idx = step idx), not the device generator
   bool noise_streamed = false; // `noise` is reserved and nothing of it filled: the caller sends the blocks beside the loop (diff_sample)
-  int n_vec = 0;             // noise vectors per candidate: n_steps + 1, or 1 (deterministic DDIM: x_T alone)
+  int n_vec = 0;             // noise vectors per candidate: n_steps + 1, or 1 (deterministic DDIM and DPM-Solver++: x_T alone)
   std::vector<int> T;        // frames per candidate
   std::vector<int64_t> xoff; // candidate c's x in `x`
   int64_t total = 0;
   DevBuf ce16_all;           // hoisted: [n_steps][src_rows][1024] fp16
   DevBuf code_emb, h0;       // a session without hoisting: [src_rows][1024] f32 each
-  DevBuf ss_all, tab, dtab, x, noise;
+  DevBuf ss_all, tab, dtab, ptab, x, d_prev, noise;
   std::chrono::steady_clock::time_point t_setup; // TTS_TIMING: when setup_batch had run
   // the session's share
   int id = 0, slot = 0, done = 0, cls = 0, packed = 0;
@@ -1024,8 +1061,8 @@ struct DiffReq {
   std::vector<int> seq_src;  // per sequence of the request (conditioned 0 .. n_cand - 1, then their unconditioned copies): its first row in the request's row buffers
   int src_rows = 0;          // rows of those buffers (the request's own packed layout; its integrator layout without hoisting)
   ReqDev dev() const {
-    return ReqDev{ss_all.as<float>(), tab.as<StepEntry>(), dtab.as<DdimEntry>(), ce16_all.as<__half>(), x.as<float>(), host_noise ? noise.as<float>() : nullptr,
-                  seed, n_steps, sampler, src_rows, stream_base};
+    return ReqDev{ss_all.as<float>(), tab.as<StepEntry>(), dtab.as<DdimEntry>(), sampler == 3 ? ptab.as<DpmEntry>() : nullptr, ce16_all.as<__half>(), x.as<float>(),
+                  sampler == 3 ? d_prev.as<float>() : nullptr, host_noise ? noise.as<float>() : nullptr, seed, n_steps, sampler, src_rows, stream_base};
   }
 };
 
@@ -2227,7 +2264,7 @@ int diff_forward(tts_ctx *ctx, const float *latents, int L, const float *x_t, in
 // What prepare_request makes a request from.
 struct ReqSpec {
   const float *latents; const int32_t *rows; int n_cand, n_steps; // the candidates' AR latents
-  int sampler; double eta; float k;                              // 0 = the reference's ancestral step, 1 = DDIM; ddim_eta; guidance k
+  int sampler; double eta; float k;                              // 0 = the reference's ancestral step, 1 = DDIM, 3 = DPM-Solver++(2M); ddim_eta; guidance k
   const float *voices; int n_voices; const int32_t *voice_of;    // conditioning latents [n_voices][2048] and the candidates' rows of them (null: all row 0), or
                                                                   // voices = null: the loaded model's latent
   const float *noise; int noise_mode;                            // caller noise; else TTS_NOISE_REFERENCE: drawn here, candidate after candidate; else the device generator
@@ -2238,10 +2275,11 @@ struct ReqSpec {
 };
 // The per-step device tables of a sampling loop of n_steps (see StepEntry): entry idx belongs to respaced timestep n_steps - 1 - idx. has_noise: the steps read
 // host-provided noise blocks of `total` floats each (block 0 = x_T, block 1 + idx = step idx).
-static void build_step_tables(const DiffSchedule &sched, int n_steps, bool ddim, bool has_noise, long long total, std::vector<StepEntry> &tab,
-                              std::vector<DdimEntry> &dtab) {
+static void build_step_tables(const DiffSchedule &sched, int n_steps, bool ddim, bool dpm, bool has_noise, long long total, std::vector<StepEntry> &tab,
+                              std::vector<DdimEntry> &dtab, std::vector<DpmEntry> &ptab) {
   tab.assign(n_steps, StepEntry{});
   dtab.assign(ddim ? n_steps : 0, DdimEntry{});
+  ptab.assign(dpm ? n_steps : 0, DpmEntry{});
   for (int idx = 0; idx < n_steps; idx++) {
     const int t = n_steps - 1 - idx;
     tab[idx].sc = StepScalars{sched.max_log[t], sched.min_log[t], sched.cfk[t], sched.sqrt_recip[t], sched.sqrt_recipm1[t],
@@ -2251,6 +2289,7 @@ static void build_step_tables(const DiffSchedule &sched, int n_steps, bool ddim,
     tab[idx].philox_step = (unsigned)idx;
     tab[idx].pad = 0;
     if (ddim) dtab[idx] = DdimEntry{sched.c_x0[t], sched.c_eps[t], sched.sigma[t], 0.f};
+    if (dpm) ptab[idx] = DpmEntry{sched.dpm_a[t], sched.dpm_b[t], sched.dpm_c[t], sched.dpm_order[t]};
   }
 }
 // Everything of a request that is evaluated before its first step, for the request ALONE, in the single call's run state (st->sb, which no step of a session
@@ -2277,13 +2316,16 @@ static int prepare_request(tts_ctx *ctx, DiffState *st, DiffReq &r, const ReqSpe
   Layout &lay = st->sb.lay;
   r.n_cand = B; r.n_steps = n_steps; r.sampler = sp.sampler; r.seed = sp.seed; r.stream_base = sp.stream_base;
   // Deterministic DDIM (ddim_eta = 0) has ONE noise vector per candidate, x_T: n_vec = 1 (no per-step block is drawn, allocated or uploaded); with eta > 0 layout,
-  // draw order and generator keys are those of the ancestral sampler.
-  const bool ddim = sp.sampler == 1;
-  const int n_vec = r.n_vec = ddim && sp.eta == 0 ? 1 : n_steps + 1;
+  // draw order and generator keys are those of the ancestral sampler. DPM-Solver++(2M) is deterministic: its noise is DDIM eta 0's whatever eta holds, and its
+  // first-order steps read the eta-0 DDIM table.
+  const bool dpm = sp.sampler == 3, ddim = sp.sampler == 1 || dpm;
+  const double eta = dpm ? 0.0 : sp.eta;
+  const int n_vec = r.n_vec = ddim && eta == 0 ? 1 : n_steps + 1;
   DiffSchedule sched;
   sched.base_k = sp.k;
   sched.build(n_steps);
-  if (ddim) sched.build_ddim(sp.eta);
+  if (ddim) sched.build_ddim(eta);
+  if (dpm) sched.build_dpmpp();
   std::vector<int> ts(n_steps);
   for (int idx = 0; idx < n_steps; idx++) ts[idx] = sched.timestep_map[n_steps - 1 - idx]; // time_embedding_{idx} (5819-5825)
   CHECK(precompute_time(ctx, st, ts, r.ss_all));
@@ -2298,6 +2340,7 @@ static int prepare_request(tts_ctx *ctx, DiffState *st, DiffReq &r, const ReqSpe
   for (int c = 0; c < B; c++) { r.xoff[c] = r.total; r.total += (int64_t)100 * lay.len[c]; }
   const int64_t total = r.total;
   TTS_HIP(ctx, r.x.reserve(total * 4));
+  if (dpm) TTS_HIP(ctx, r.d_prev.reserve(total * 4)); // written by the request's first step before any step reads it
   r.host_noise = sp.noise != nullptr || sp.noise_mode == TTS_NOISE_REFERENCE;
   r.noise_streamed = r.host_noise && sp.stream_noise != nullptr;
   if (r.noise_streamed && sp.stream_noise->reserve((size_t)total * n_vec * 4) != hipSuccess) { (void)hipGetLastError(); r.noise_streamed = false; }
@@ -2327,12 +2370,17 @@ static int prepare_request(tts_ctx *ctx, DiffState *st, DiffReq &r, const ReqSpe
   }
   std::vector<StepEntry> tab;
   std::vector<DdimEntry> dtab;
-  build_step_tables(sched, n_steps, ddim, r.host_noise && n_vec > 1, total, tab, dtab);
+  std::vector<DpmEntry> ptab;
+  build_step_tables(sched, n_steps, ddim, dpm, r.host_noise && n_vec > 1, total, tab, dtab, ptab);
   TTS_HIP(ctx, r.tab.reserve(tab.size() * sizeof(StepEntry)));
   TTS_HIP(ctx, hipMemcpyAsync(r.tab.p, tab.data(), tab.size() * sizeof(StepEntry), hipMemcpyHostToDevice, ctx->stream));
   if (ddim) {
     TTS_HIP(ctx, r.dtab.reserve(dtab.size() * sizeof(DdimEntry)));
     TTS_HIP(ctx, hipMemcpyAsync(r.dtab.p, dtab.data(), dtab.size() * sizeof(DdimEntry), hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (dpm) {
+    TTS_HIP(ctx, r.ptab.reserve(ptab.size() * sizeof(DpmEntry)));
+    TTS_HIP(ctx, hipMemcpyAsync(r.ptab.p, ptab.data(), ptab.size() * sizeof(DpmEntry), hipMemcpyHostToDevice, ctx->stream));
   }
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the tables are host vectors: the copies must have read them before they go out of scope
   return TTS_OK;

@@ -884,6 +884,28 @@ void DiffSchedule::build_ddim(double eta) {
   }
 }
 
+// DPM-Solver++(2M) per-step scalars (Lu et al. 2022, multistep second order on the data prediction) on the respaced schedule of build(). Step t moves from level
+// acp[t] (alpha_s, sigma_s, lambda_s) to prev[t] (alpha_n, sigma_n, lambda_n); h = lambda_n - lambda_s, phi = alpha_n (1 - e^-h); the step before it came from level
+// acp[t + 1], r = (lambda_s - lambda(acp[t + 1])) / h. Second order: x_n = (sigma_n / sigma_s) x + phi (1 + 1 / 2r) x0 - (phi / 2r) x0_prev. First order (c = 0,
+// b = phi) at t = n - 1, which has no history, and at t = 1 and t = 0: the respaced schedule ends at timestep 0 of 4000, where log-SNR jumps by several step
+// widths, and a second-order update across that jump extrapolates with r ~ 0.1 (DESIGN.md "What pins the DPM-Solver++ sampler"). At t = 0 sigma_n = 0: (0, 1, 0).
+void DiffSchedule::build_dpmpp() {
+  dpm_a.assign(n, 0.f); dpm_b.assign(n, 0.f); dpm_c.assign(n, 0.f); dpm_order.assign(n, 1);
+  auto lambda = [](double a) { return 0.5 * std::log(a) - 0.5 * std::log(1.0 - a); };
+  dpm_b[0] = 1.f;
+  for (int t = 1; t < n; t++) {
+    const double sigma_s = std::sqrt(1.0 - acp[t]), alpha_n = std::sqrt(prev[t]), sigma_n = std::sqrt(1.0 - prev[t]);
+    const double lambda_s = lambda(acp[t]), h = lambda(prev[t]) - lambda_s, phi = alpha_n * -std::expm1(-h);
+    dpm_a[t] = (float)(sigma_n / sigma_s);
+    if (t >= 2 && t <= n - 2) {
+      const double r = (lambda_s - lambda(acp[t + 1])) / h;
+      dpm_order[t] = 2;
+      dpm_b[t] = (float)(phi * (1.0 + 1.0 / (2.0 * r)));
+      dpm_c[t] = (float)(-phi / (2.0 * r));
+    } else dpm_b[t] = (float)phi;
+  }
+}
+
 // Text splitter (tts_split_text; our own rule, stated in include/tortoise_mi355x.h). Chunks are byte ranges of the message; every chunk tokenizes to
 // at most max_ids ids. Token counts are those of Tokenizer::encode on the chunk's bytes (255 ... 0 included).
 std::vector<std::pair<int, int>> split_text(const Tokenizer &tok, const std::string &msg, int max_ids) {
@@ -1005,6 +1027,14 @@ extern "C" int tts_host_schedule_ddim(int n_steps, double eta, double *acp, doub
     acp[t] = s.acp[t]; acp_prev[t] = s.prev[t];
     c_x0[t] = s.c_x0[t]; c_eps[t] = s.c_eps[t]; sigma[t] = s.sigma[t];
   }
+  return TTS_OK;
+}
+extern "C" int tts_host_schedule_dpmpp(int n_steps, float *a, float *b, float *c, int32_t *order) {
+  if (n_steps < 2 || !a || !b || !c || !order) return TTS_ERR_ARG;
+  tts::DiffSchedule s;
+  s.build(n_steps);
+  s.build_dpmpp();
+  for (int t = 0; t < n_steps; t++) { a[t] = s.dpm_a[t]; b[t] = s.dpm_b[t]; c[t] = s.dpm_c[t]; order[t] = s.dpm_order[t]; }
   return TTS_OK;
 }
 extern "C" void tts_host_timestep_embedding(int t, float *out1024) { tts::timestep_embedding(t, out1024); }
@@ -1186,7 +1216,7 @@ extern "C" int tts_diffusion_frames(int L) { return L * 4 * 24000 / 22050; }
 namespace tts {
 const char *diff_control_error(int which, double value) {
   switch (which) {
-  case 0: return (value != 0 && value != 1) ? "diff_sampler: 0 (ancestral DDPM) or 1 (DDIM)" : nullptr;
+  case 0: return (value != 0 && value != 1 && value != 3) ? "diff_sampler: 0 (ancestral DDPM), 1 (DDIM) or 3 (DPM-Solver++(2M))" : nullptr;
   case 1: return !(value >= 0 && value <= 1) ? "ddim_eta: a value in [0, 1]" : nullptr;
   case 2: return (!std::isfinite(value) || value < 0 || !std::isfinite((float)value)) ? "cond_free_k: a finite value >= 0" : nullptr;
   }
