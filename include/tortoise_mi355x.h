@@ -150,7 +150,15 @@ const char *tts_last_error(const tts_ctx *ctx);
  * tts_ar_begin* (through tts_ar_step or tts_ar_step_sample, in any mix; a step fed twice counts once) plus 1 and 8192. tts_sample penalises the ids it is given
  * under either scope: a caller stepping by hand passes the accumulated history. Under scope 1 the decode step keeps the set on the device and its prefilter
  * penalises before it thresholds (one more node in the step graph of tts_ar_step, none in tts_ar_step_sample's). Whether the wider penalty SOUNDS better cannot be
- * judged without trained weights: the tests pin the arithmetic (DESIGN.md "What pins the sampler controls"). */
+ * judged without trained weights: the tests pin the arithmetic (DESIGN.md "What pins the sampler controls").
+ * "ar_typical_mass" (0 default = off; 0 < x < 1, also after narrowing to float; anything else TTS_ERR_ARG): locally typical sampling (Meister et al. 2022),
+ * upstream's typical_sampling / typical_mass, which hands HF's TypicalLogitsWarper(mass) to generate as a logits processor: it runs after the repetition penalty
+ * and before temperature, top-k and top-p. On the penalised row, in double: p = softmax, H = its entropy, d_i = |-ln p_i - H|; ids in ascending d are kept until
+ * their cumulative p reaches the mass (ties at the cut survive, the smallest d is always kept). Every other id has probability exactly 0 in all later stages; a
+ * typical set smaller than top-k survives top-k whole. The RNG consumption is unchanged. Under device_topk the decode step's prefilter decides the set on the
+ * device (the lists then hold the typical members only) and hands a row to the full-row path where its error bounds leave the set open (tts_ar_topk_fallbacks
+ * counts those). At 0 the step launches the kernels it launched before and every bit of every output is what it was. How it sounds is unjudged (no trained
+ * weights here); HF's warper evaluated in float64 is the reference (DESIGN.md "What pins typical sampling"). */
 int tts_set_option(tts_ctx *ctx, const char *key, double value);
 /* the values of "diff_sampler" and of tts_diff_request.sampler (2 is not a sampler) */
 enum { TTS_SAMPLER_DDPM = 0, TTS_SAMPLER_DDIM = 1, TTS_SAMPLER_DPMPP_2M = 3 };
@@ -466,12 +474,17 @@ int tts_ar_session_audio(tts_ctx *ctx, int request, float *out, int cap_samples,
 /* Per-request sampler controls and step limit (additions within version 8; no prototype changed). tts_ar_session_admit runs every request under the options
  * the session pinned when it was opened. tts_ar_session_admit_ex takes a request descriptor that carries the request's own.
  * tts_ar_request: plain C and able to grow: struct_size is sizeof(tts_ar_request) as the CALLER's header declares it, set by the caller before
- *   tts_ar_request_init. Version 8 refuses a struct_size below its own sizeof(tts_ar_request) and reads exactly that many bytes. The rule for growth: fields
- *   are only ever appended, and a library that declares a longer struct is to read only the fields struct_size covers. The five controls are doubles and are checked with the
+ *   tts_ar_request_init. Version 8 refuses a struct_size that is no header's struct (below) and reads only the fields it covers. The rule for growth: fields
+ *   are only ever appended, and a library that declares a longer struct is to read only the fields struct_size covers. The controls are doubles and are checked with the
  *   very predicate tts_set_option applies to "ar_temperature", "ar_top_k", "ar_top_p", "ar_repetition_penalty" and "ar_penalty_scope". max_steps: 0 = the
  *   session's, else 1 .. the session's max_steps (the request then stops there exactly as tts_autoregressive with that max_steps would).
- * tts_ar_request_init: fills every field from the options the OPEN SESSION pinned (not from what tts_set_option holds now); n_cand = 1, seed = 0, stop_at =
- *   NULL, max_steps = 0. TTS_ERR_ARG: a null pointer or a struct_size below the version 8 size; TTS_ERR_STATE without an open session.
+ *   typical_mass is the first appended field (the growth rule at work): struct_size is accepted when it is exactly the size of the struct up to penalty_scope
+ *   (64 bytes: a caller built before the field existed; its request runs under the session's pinned mass) or at least the present sizeof(tts_ar_request); a size
+ *   in between is no header's struct and is refused (TTS_ERR_ARG). The field is checked with tts_set_option's predicate for "ar_typical_mass"; a mass that
+ *   differs from the session's needs TTS_AR_ROW_CONTROLS like the other five (the table entry's fourth word holds the float's bits, 0 = off: rows with and
+ *   without typical sampling and with different masses share one launch, and no admission re-captures).
+ * tts_ar_request_init: fills every field struct_size covers from the options the OPEN SESSION pinned (not from what tts_set_option holds now); n_cand = 1, seed = 0, stop_at =
+ *   NULL, max_steps = 0. TTS_ERR_ARG: a null pointer or a refused struct_size; TTS_ERR_STATE without an open session.
  * tts_ar_session_open accepts one more flag, TTS_AR_ROW_CONTROLS: only a session opened with it admits a request whose controls differ from the session's.
  *   Such a session ends its captured step with a prefilter that reads every row's keep bound, penalty and penalty scope from a device table with one entry
  *   per slot, written at admission for the slots the request takes, outside the graph; the step bakes none of the three in, so no admission, whatever its
@@ -497,6 +510,7 @@ typedef struct tts_ar_request {
   int32_t max_steps;          /* 0: the session's */
   const int32_t *stop_at;     /* [n_cand] or NULL */
   double temperature, top_k, top_p, repetition_penalty, penalty_scope;
+  double typical_mass;        /* appended within version 8 ("ar_typical_mass"; 0 = off); read only when struct_size covers it */
 } tts_ar_request;
 int tts_ar_request_init(tts_ctx *ctx, tts_ar_request *req);
 int tts_ar_session_admit_ex(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice1024, const tts_ar_request *req);
@@ -661,6 +675,17 @@ int tts_host_sample_row_ex(const float *row8194, const int32_t *penalty_ids, int
  * penalised values). -1 = the engine would fetch the row */
 int tts_host_sample_prefiltered_ex(const float *row8194, const int32_t *penalty_ids, int n_ids, float uniform, float temperature, int top_k, float top_p,
                                    float penalty, int keep, int already_penalised);
+/* Typical sampling's host probes (additions within version 8; -2: a refused argument, mass outside (0, 1) after narrowing to float included).
+ * tts_host_typical_keep: the literal definition on a (penalised) row: keep_out8194[i] = 1 for the members; returns their number.
+ * tts_host_sample_row_typical: tts_host_sample_row_ex with the typical stage (mass 0: that very call). mode 0: the engine's full-row path; 1: the literal.
+ * tts_host_sample_prefiltered_typical: the list path. The host builds the list as the device does (the penalised row, the typical set under the device's
+ *   decision rule, the members >= the threshold that keeps `keep` .. 128 of them, or the whole set when it has fewer than `keep`) and runs the list tail; -1
+ *   where the list cannot decide (the engine would fetch the row). mass 0: tts_host_sample_prefiltered_ex with already_penalised = 1. */
+int tts_host_typical_keep(const float *row8194, double mass, uint8_t *keep_out8194);
+int tts_host_sample_row_typical(const float *row8194, const int32_t *penalty_ids, int n_ids, float uniform, float temperature, int top_k, float top_p,
+                                float penalty, double typical_mass, int mode);
+int tts_host_sample_prefiltered_typical(const float *row8194, const int32_t *penalty_ids, int n_ids, float uniform, float temperature, int top_k, float top_p,
+                                        float penalty, double typical_mass, int keep);
 int tts_host_pad_codes(const int32_t *codes, int n, int32_t *out502);
 /* tts_hifigan_stream's row bookkeeping (addition within version 8): the latent rows that are final after the first k sampled codes (none the stop token) —
  * k + 1, cut where tts_host_trimmed_rows will cut and at 500. They are a prefix of the rows tts_host_pad_codes + tts_host_trimmed_rows give at the end. */

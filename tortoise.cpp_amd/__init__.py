@@ -36,7 +36,11 @@ def build(verbose=False):
 class ArRequest(C.Structure):
     """tts_ar_request: one session request's candidates, seed, stop schedule, step limit and sampler controls (tts_ar_session_admit_ex)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_cand", C.c_int32), ("seed", C.c_uint32), ("max_steps", C.c_int32), ("stop_at", C.c_void_p),
-                ("temperature", C.c_double), ("top_k", C.c_double), ("top_p", C.c_double), ("repetition_penalty", C.c_double), ("penalty_scope", C.c_double)]
+                ("temperature", C.c_double), ("top_k", C.c_double), ("top_p", C.c_double), ("repetition_penalty", C.c_double), ("penalty_scope", C.c_double),
+                ("typical_mass", C.c_double)]   # appended within version 8; a descriptor of the size before it (AR_REQUEST_SIZE_V0) runs under the session's mass
+
+
+AR_REQUEST_SIZE_V0 = ArRequest.typical_mass.offset
 
 
 class DiffRequest(C.Structure):
@@ -46,7 +50,8 @@ class DiffRequest(C.Structure):
 
 
 # the keys of ar_session_admit(controls=...) and the descriptor fields they set
-AR_CONTROL_FIELDS = {"temperature": "temperature", "top_k": "top_k", "top_p": "top_p", "penalty": "repetition_penalty", "scope": "penalty_scope"}
+AR_CONTROL_FIELDS = {"temperature": "temperature", "top_k": "top_k", "top_p": "top_p", "penalty": "repetition_penalty", "scope": "penalty_scope",
+                     "typical_mass": "typical_mass"}
 
 
 class TtsError(RuntimeError):
@@ -83,6 +88,9 @@ def lib():
         "tts_device_numa_node": (ci, [vp, C.c_char_p, ci]), "tts_pin_to_device_numa_node": (ci, [vp]),
         "tts_host_sample_row": (ci, [_f32p, _i32p, ci, cf]), "tts_host_sample_prefiltered": (ci, [_f32p, _i32p, ci, cf, ci]),
         "tts_host_sample_row_ex": (ci, [_f32p, _i32p, ci, cf, cf, ci, cf, cf, ci]), "tts_host_sample_prefiltered_ex": (ci, [_f32p, _i32p, ci, cf, cf, ci, cf, cf, ci, ci]),
+        "tts_host_typical_keep": (ci, [_f32p, C.c_double, vp]),
+        "tts_host_sample_row_typical": (ci, [_f32p, _i32p, ci, cf, cf, ci, cf, cf, C.c_double, ci]),
+        "tts_host_sample_prefiltered_typical": (ci, [_f32p, _i32p, ci, cf, cf, ci, cf, cf, C.c_double, ci]),
         "tts_autoregressive": (ci, [vp, _i32p, ci, _f32p, ci, ci, C.c_uint, _i32p, _i32p, vp, _i32p]),
         "tts_ar_stop_status": (ci, [vp, _i32p, ci]), "tts_ar_set_stop_schedule": (ci, [vp, C.c_void_p, ci]),
         "tts_ar_begin_multi": (ci, [vp, _i32p, _i32p, ci, _f32p, _i32p, ci]),
@@ -372,7 +380,7 @@ class Engine:
 
     def ar_request(self, n_cand=1, seed=0, stop_at=None, controls=None, max_steps=None):
         """A tts_ar_request filled from the open session's pinned options (tts_ar_request_init), then from the arguments. controls: a dict with any of
-        temperature, top_k, top_p, penalty, scope. The stop_at array must outlive the descriptor's use."""
+        temperature, top_k, top_p, penalty, scope, typical_mass. The stop_at array must outlive the descriptor's use."""
         req = ArRequest()
         req.struct_size = C.sizeof(ArRequest)
         self._ck(self.L.tts_ar_request_init(self.h, C.byref(req)))
@@ -386,7 +394,7 @@ class Engine:
 
     def ar_session_admit(self, tokens, voice, n_cand, seed, stop_at=None, controls=None, max_steps=None):
         """Admits a request into the lowest run of n_cand free slots and returns its id; TtsError (status -6) when there is no such run. controls (a dict with
-        any of temperature, top_k, top_p, penalty, scope; missing keys take the session's values) and max_steps (at most the session's): the request's own;
+        any of temperature, top_k, top_p, penalty, scope, typical_mass; missing keys take the session's values) and max_steps (at most the session's): the request's own;
         with either the call goes through tts_ar_session_admit_ex. Controls that differ from the session's need ar_session_open(row_controls=True)."""
         tok = np.ascontiguousarray(tokens, np.int32)
         v = np.ascontiguousarray(voice, np.float32)
@@ -786,6 +794,31 @@ def host_sample_prefiltered_ex(row, ids, uniform, temperature=0.8, top_k=50, top
                                                 float(top_p), float(penalty), int(keep), int(bool(already_penalised)))
 
 
+def host_typical_keep(row, mass):
+    """The literal typical set of a (penalised) row [8194] at `mass` (narrowed to float, as the option is): a bool array [8194]."""
+    keep = np.zeros(VOCAB_MEL, np.uint8)
+    n = lib().tts_host_typical_keep(np.ascontiguousarray(row, np.float32), float(mass), _ptr(keep))
+    if n < 0:
+        raise TtsError("tts_host_typical_keep refused its arguments (%d)" % n)
+    assert n == int(keep.sum())
+    return keep.astype(bool)
+
+
+def host_sample_row_typical(row, ids, uniform, temperature=0.8, top_k=50, top_p=0.8, penalty=2.0, typical_mass=0.0, mode=0):
+    """host_sample_row_ex with the typical stage between the penalty and the temperature (typical_mass 0: that very call)."""
+    ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    return lib().tts_host_sample_row_typical(np.ascontiguousarray(row, np.float32), ids, len(ids), float(uniform), float(temperature), int(top_k), float(top_p),
+                                             float(penalty), float(typical_mass), int(mode))
+
+
+def host_sample_prefiltered_typical(row, ids, uniform, temperature=0.8, top_k=50, top_p=0.8, penalty=2.0, typical_mass=0.0, keep=64):
+    """The list path under typical sampling: the host builds the list as the device does (penalised row, the typical set under the device's decision rule)
+    and runs the list tail. -1: the engine would fetch the full row."""
+    ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    return lib().tts_host_sample_prefiltered_typical(np.ascontiguousarray(row, np.float32), ids, len(ids), float(uniform), float(temperature), int(top_k),
+                                                     float(top_p), float(penalty), float(typical_mass), int(keep))
+
+
 def host_rel_buckets(n):
     L = lib()
     return np.array([[L.tts_host_rel_bucket(i, c) for c in range(n)] for i in range(n)], np.int32)
@@ -832,9 +865,11 @@ def host_ar_stop_run(n_cand, samples, max_steps, flags=0, stop_at=None):
     return rc, codes, stopped, int(steps[0]), inputs
 
 
-def host_ar_request_check(max_cand, max_steps, struct_size=None, n_cand=1, seed=0, req_max_steps=0, temperature=0.8, top_k=50, top_p=0.8, penalty=2.0, scope=0):
+def host_ar_request_check(max_cand, max_steps, struct_size=None, n_cand=1, seed=0, req_max_steps=0, temperature=0.8, top_k=50, top_p=0.8, penalty=2.0, scope=0,
+                          typical_mass=0.0):
     """The status tts_ar_session_admit_ex's descriptor checks return for these fields in a session of max_cand candidates and max_steps steps (no GPU)."""
-    req = ArRequest(C.sizeof(ArRequest) if struct_size is None else struct_size, n_cand, seed, req_max_steps, None, temperature, top_k, top_p, penalty, scope)
+    req = ArRequest(C.sizeof(ArRequest) if struct_size is None else struct_size, n_cand, seed, req_max_steps, None, temperature, top_k, top_p, penalty, scope,
+                    typical_mass)
     return lib().tts_host_ar_request_check(C.byref(req), max_cand, max_steps)
 
 

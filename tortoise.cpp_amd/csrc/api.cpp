@@ -2,6 +2,7 @@
 #include "common.h"
 #include <sched.h>
 #include <cctype>
+#include <cstddef>
 #include <cmath>
 #include <algorithm>
 #include <chrono>
@@ -136,11 +137,11 @@ int tts_version(void) { return TTS_API_VERSION; }
 
 const char *tts_last_error(const tts_ctx *c) { return c ? c->err.c_str() : "no context (no HIP device?)"; }
 
-// The autoregressive sampler's five controls: the ONE statement of what each accepts, for tts_set_option and for a request descriptor (tts_ar_session_admit_ex,
+// The autoregressive sampler's six controls: the ONE statement of what each accepts, for tts_set_option and for a request descriptor (tts_ar_session_admit_ex,
 // tts_host_ar_request_check). Returns the refusal's text, or null for a value that is fine.
-static const char *const kArControlKeys[5] = {"ar_temperature", "ar_top_k", "ar_top_p", "ar_repetition_penalty", "ar_penalty_scope"};
+static const char *const kArControlKeys[6] = {"ar_temperature", "ar_top_k", "ar_top_p", "ar_repetition_penalty", "ar_penalty_scope", "ar_typical_mass"};
 static int ar_control_index(const std::string &k) {
-  for (int i = 0; i < 5; i++)
+  for (int i = 0; i < 6; i++)
     if (k == kArControlKeys[i]) return i;
   return -1;
 }
@@ -152,6 +153,7 @@ static const char *ar_control_error(int which, double value) {
   case 2: return (!(value > 0 && value <= 1) || !((float)value > 0)) ? "ar_top_p: a value in (0, 1]" : nullptr;
   case 3: return (!std::isfinite(value) || !(value >= 1) || !std::isfinite((float)value)) ? "ar_repetition_penalty: a finite value >= 1" : nullptr;
   case 4: return (value != 0 && value != 1) ? "ar_penalty_scope: 0 (the ids of the last input) or 1 (every id fed since tts_ar_begin)" : nullptr;
+  case 5: return (value != 0 && (!(value > 0 && value < 1) || !((float)value > 0 && (float)value < 1))) ? "ar_typical_mass: 0 (off) or a value in (0, 1)" : nullptr;
   }
   return "unknown sampler control";
 }
@@ -162,6 +164,7 @@ static void ar_control_store(int which, double value, SamplerParams &sp, int &sc
   case 2: sp.top_p = (float)value; break;
   case 3: sp.penalty = (float)value; break;
   case 4: scope = (int)value; break;
+  case 5: sp.typ_mass = (float)value; break;
   }
 }
 
@@ -419,6 +422,28 @@ int tts_host_sample_prefiltered_ex(const float *row, const int32_t *ids, int n_i
   if (host_prefilter_row(row, keep, list.data()) < 0) return -1;
   return sample_one_from_list_ex(list.data(), ids, n_ids, uniform, sp, already_penalised != 0);
 }
+int tts_host_typical_keep(const float *row, double mass, uint8_t *keep_out) {
+  if (!row || !keep_out || mass == 0 || ar_control_error(5, mass)) return -2;
+  return typical_keep(row, (double)(float)mass, (char *)keep_out);
+}
+int tts_host_sample_row_typical(const float *row, const int32_t *ids, int n_ids, float uniform, float temperature, int top_k, float top_p, float penalty, double mass,
+                                int mode) {
+  if (!sampler_params_ok(row, ids, n_ids, temperature, top_k, top_p, penalty) || (mode != 0 && mode != 1) || ar_control_error(5, mass)) return -2;
+  SamplerParams sp; sp.temp = temperature; sp.top_k = top_k; sp.top_p = top_p; sp.penalty = penalty; sp.typ_mass = (float)mass;
+  return sample_one_row_ex(row, ids, n_ids, uniform, sp, mode == 1);
+}
+int tts_host_sample_prefiltered_typical(const float *row, const int32_t *ids, int n_ids, float uniform, float temperature, int top_k, float top_p, float penalty,
+                                        double mass, int keep) {
+  if (ar_control_error(5, mass)) return -2;
+  if (mass == 0) return tts_host_sample_prefiltered_ex(row, ids, n_ids, uniform, temperature, top_k, top_p, penalty, keep, 1);
+  if (!sampler_params_ok(row, ids, n_ids, temperature, top_k, top_p, penalty) || keep < 1 || keep > TTS_PF_MAX) return -2;
+  SamplerParams sp; sp.temp = temperature; sp.top_k = top_k; sp.top_p = top_p; sp.penalty = penalty; sp.typ_mass = (float)mass;
+  std::vector<int32_t> list(TTS_PF_WORDS);
+  std::vector<float> pen(row, row + TTS_VOCAB_MEL); // what the typical body sees in either scope: the penalised row
+  for (int i = 0; i < n_ids; i++) { const float g = row[ids[i]]; pen[ids[i]] = g < 0 ? g * penalty : g / penalty; }
+  if (host_prefilter_row_typical(pen.data(), (double)sp.typ_mass, keep, list.data()) < 0) return -1;
+  return sample_one_from_list_ex(list.data(), ids, n_ids, uniform, sp, true);
+}
 int tts_host_sample_prefiltered(const float *row, const int32_t *ids, int ids_per_cand, float uniform, int keep) {
   if (!row || !ids || ids_per_cand < 1 || keep < 1 || keep > TTS_PF_MAX) return -2;
   std::vector<int32_t> list(TTS_PF_WORDS);
@@ -595,11 +620,16 @@ int tts_ar_session_recaptures(const tts_ctx *c) {
 
 // What a request descriptor must satisfy in a session of max_cand candidates and max_steps steps, before any device work: the status, and in `why` the text.
 // On TTS_OK sp / scope hold the request's controls as the sampler will read them.
-static int request_check(const tts_ar_request *req, int max_cand, int max_steps, SamplerParams &sp, int &scope, std::string &why) {
-  char buf[160];
+// The struct's growth rule: the size a header before "typical_mass" declared, or one that covers every field this library knows.
+static const size_t kArRequestSize0 = offsetof(tts_ar_request, typical_mass);
+static bool request_size_ok(uint32_t n) { return n == kArRequestSize0 || n >= sizeof(tts_ar_request); }
+// pinned_mass: what a descriptor of the older size runs under (the session's).
+static int request_check(const tts_ar_request *req, int max_cand, int max_steps, double pinned_mass, SamplerParams &sp, int &scope, std::string &why) {
+  char buf[200];
   if (!req) { why = "null request"; return TTS_ERR_ARG; }
-  if (req->struct_size < sizeof(tts_ar_request)) {
-    snprintf(buf, sizeof buf, "struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_ar_request))", req->struct_size, sizeof(tts_ar_request));
+  if (!request_size_ok(req->struct_size)) {
+    snprintf(buf, sizeof buf, "struct_size %u, version 8 declares %zu bytes (%zu before typical_mass was appended; set it to sizeof(tts_ar_request))", req->struct_size,
+             sizeof(tts_ar_request), kArRequestSize0);
     why = buf;
     return TTS_ERR_ARG;
   }
@@ -610,8 +640,9 @@ static int request_check(const tts_ar_request *req, int max_cand, int max_steps,
       if (req->stop_at[b] < 1) { snprintf(buf, sizeof buf, "candidate %d would stop before its first code", b); why = buf; return TTS_ERR_ARG; }
   if (req->max_steps < 0) { snprintf(buf, sizeof buf, "max_steps %d: 0 (the session's) or 1 .. %d", req->max_steps, max_steps); why = buf; return TTS_ERR_ARG; }
   if (req->max_steps > max_steps) { snprintf(buf, sizeof buf, "max_steps %d, the session was opened for %d", req->max_steps, max_steps); why = buf; return TTS_ERR_LIMIT; }
-  const double v[5] = {req->temperature, req->top_k, req->top_p, req->repetition_penalty, req->penalty_scope};
-  for (int k = 0; k < 5; k++) {
+  const double v[6] = {req->temperature, req->top_k, req->top_p, req->repetition_penalty, req->penalty_scope,
+                       req->struct_size >= sizeof(tts_ar_request) ? req->typical_mass : pinned_mass};
+  for (int k = 0; k < 6; k++) {
     if (const char *e = ar_control_error(k, v[k])) { why = e; return TTS_ERR_ARG; }
     ar_control_store(k, v[k], sp, scope);
   }
@@ -623,18 +654,21 @@ int tts_host_ar_request_check(const tts_ar_request *req, int max_cand, int max_s
   SamplerParams sp;
   int scope = 0;
   std::string why;
-  return request_check(req, max_cand, max_steps, sp, scope, why);
+  return request_check(req, max_cand, max_steps, 0.0, sp, scope, why);
 }
 
 int tts_ar_request_init(tts_ctx *c, tts_ar_request *req) {
   NEED_CTX(c);
   NEED_SESSION(c, "tts_ar_request_init");
   if (!req) return fail(c, TTS_ERR_ARG, "tts_ar_request_init: null request");
-  if (req->struct_size < sizeof(tts_ar_request))
+  if (!request_size_ok(req->struct_size))
     return fail(c, TTS_ERR_ARG, "tts_ar_request_init: struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_ar_request) first)", req->struct_size,
                 sizeof(tts_ar_request));
   req->n_cand = 1; req->seed = 0; req->max_steps = 0; req->stop_at = nullptr;
-  ar_drv_defaults(c, req);
+  tts_ar_request d;
+  ar_drv_defaults(c, &d);
+  req->temperature = d.temperature; req->top_k = d.top_k; req->top_p = d.top_p; req->repetition_penalty = d.repetition_penalty; req->penalty_scope = d.penalty_scope;
+  if (req->struct_size >= sizeof(tts_ar_request)) req->typical_mass = d.typical_mass; // an older caller's struct ends before the field
   return TTS_OK;
 }
 
@@ -651,7 +685,9 @@ int tts_ar_session_admit_ex(tts_ctx *c, const int32_t *text_ids, int n_text, con
   int scope = 0, max_cand = 0, max_steps = 0;
   ar_drv_limits(c, max_cand, max_steps);
   std::string why;
-  if (int rc = request_check(req, max_cand, max_steps, sp, scope, why)) return fail(c, rc, "tts_ar_session_admit_ex: %s", why.c_str());
+  tts_ar_request pinned;
+  ar_drv_defaults(c, &pinned);
+  if (int rc = request_check(req, max_cand, max_steps, pinned.typical_mass, sp, scope, why)) return fail(c, rc, "tts_ar_session_admit_ex: %s", why.c_str());
   return guarded(c, [&] {
     return ar_drv_admit(c, "tts_ar_session_admit_ex", text_ids, n_text, voice, req->n_cand, req->seed, req->stop_at, &sp, scope, req->max_steps);
   });

@@ -1312,12 +1312,159 @@ __device__ __forceinline__ unsigned long long pf_history_mask(const uint32_t *__
   return penm;
 }
 
+// Bit j: this thread's logit j is the token this step was fed (penalty scope 0 under typical sampling: the one id the host would penalise).
+__device__ __forceinline__ unsigned long long pf_token_mask(int tok, int tid) { return (tok & 255) == tid ? 1ull << (tok >> 8) : 0ull; }
+
+// ---------------------------------------------------------------------------------------------
+// Locally typical sampling on the device (option "ar_typical_mass"; the definition: host_logic.cpp typical_keep). One workgroup of 256 threads per row, the
+// row's 33 penalised logits per thread in registers. With a_i = m - x_i >= 0 (m = the row maximum, exact) the literal's distance d_i = |-ln p_i - H| is
+// |a_i - t|, t = sum a_i e_i / Z = H - ln Z, e_i = exp(-a_i), Z = sum e_i: ln Z cancels and ONE scalar orders the row. The body computes Z and sum a e in double
+// (block tree sums), p_i = e_i / Z, the distances' bit patterns as ordered 64-bit keys, and bisects on the key for theta = the smallest distance whose
+// inclusive mass M(theta) = sum {p_i : d_i <= theta} reaches the mass (M is a fixed tree sum of non-negative terms: monotone in theta; at most 63 probes, and
+// the search ends as soon as one distance is left in the interval).
+// Error bounds (u = 2^-53, V = 8194, all sums of same-signed terms, worst-case summation (V - 1) u; H <= ln V = 9.02, t <= ln V):
+//   literal: Z_L = Z (1 + (V + 1) u) -> ln p_i off by <= 9.2e-13 + u |ln p_i|; p_i relative 1.0e-12; H_L off by <= H (9.1e-13 + 1.0e-12) + 9.2e-13 <= 1.82e-11;
+//            d_L off by <= 1.92e-11 + 2 u (a_i + 9.02); a cumulative c_j relative <= 1.0e-12 + (V - 1) u = 1.92e-12.
+//   device:  Z', S' relative <= (V + 3) u (device exp: 1 ulp) -> t' off by <= 9.02 * 1.83e-12 = 1.65e-11; d' off by <= 1.65e-11 + 2 u (a_i + 9.02);
+//            M' relative <= 1.92e-12 + u.
+//   together |d' - d_L| <= 3.6e-11 + 4.4e-16 (a_i + 9.02) < E = TTS_TYP_TOL_D (2^-33 = 1.16e-10) + TTS_TYP_TOL_REL (2^-49 = 1.8e-15) (t + theta) for every element
+//   within 2 E of theta (a_i <= t + theta + 2 E), and |M' - c_L| <= 3.9e-12 < TTS_TYP_TOL_M (2^-35 = 2.9e-11): a margin of 3 and 7.
+// The set {d' <= theta} is the literal's, and is returned, only when
+//   - no other distance lies within 2 E of theta: then the literal orders every member before every non-member and every other member before the elements AT
+//     theta; those must share one logit value (equal logits have equal literal distances, and ties survive the literal's cut);
+//   - M(theta) >= mass + TTS_TYP_TOL_M and the mass strictly below theta is < mass - TTS_TYP_TOL_M: the literal's cumulative sum crosses the mass at an element AT theta.
+// Otherwise nm = -1: the host fetches the row and runs the literal (tts_ar_topk_fallbacks). Every value a branch depends on went through LDS: workgroup-uniform.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double typ_block_sum(double v, double (*red)[4], int &it, int lane, int wave) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  if (lane == 0) red[it & 1][wave] = v;
+  __syncthreads(); // double-buffered: one barrier per reduction
+  const double r = (red[it & 1][0] + red[it & 1][1]) + (red[it & 1][2] + red[it & 1][3]);
+  it++;
+  return r;
+}
+// two sums behind one barrier (red2: its own double buffer)
+__device__ __forceinline__ void typ_block_sum2(double &a, double &b, double (*red2)[4][2], int &it, int lane, int wave) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
+  if (lane == 0) { red2[it & 1][wave][0] = a; red2[it & 1][wave][1] = b; }
+  __syncthreads();
+  a = (red2[it & 1][0][0] + red2[it & 1][1][0]) + (red2[it & 1][2][0] + red2[it & 1][3][0]);
+  b = (red2[it & 1][0][1] + red2[it & 1][1][1]) + (red2[it & 1][2][1] + red2[it & 1][3][1]);
+  it++;
+}
+__device__ __forceinline__ float typ_block_max(float v, double (*red)[4], int &it, int lane, int wave) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  if (lane == 0) red[it & 1][wave] = (double)v;
+  __syncthreads();
+  const float r = fmaxf(fmaxf((float)red[it & 1][0], (float)red[it & 1][1]), fmaxf((float)red[it & 1][2], (float)red[it & 1][3]));
+  it++;
+  return r;
+}
+__device__ __forceinline__ float pf_unkey(unsigned k) { return __uint_as_float((k >> 31) ? (k & 0x7fffffffu) : ~k); } // pf_key's inverse (-0 comes back as +0)
+
+// key: the row's penalised logits as pf_key keys (index j * 256 + tid; entries past V are not read). memb: bit j = element j is a member. Returns the number of
+// members, or -1 (undecided).
+__device__ __forceinline__ int typical_members(const unsigned (&key)[(V + 255) / 256], float mass_f, unsigned long long &memb) {
+  constexpr int NJ = (V + 255) / 256;
+  __shared__ double red[2][4];
+  __shared__ double red2[2][4][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double mass = (double)mass_f;
+  int it = 0, it2 = 0;
+  memb = 0ull;
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NJ; j++)
+    if (j * 256 + tid < V) mx = fmaxf(mx, pf_unkey(key[j]));
+  const double m = (double)typ_block_max(mx, red, it, lane, wave);
+  double p[NJ];
+  double zs = 0.0, ss = 0.0;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    p[j] = 0.0;
+    if (j * 256 + tid < V) {
+      const double a = m - (double)pf_unkey(key[j]);
+      const double e = exp(-a);
+      p[j] = e; zs += e; ss += a * e;
+    }
+  }
+  const double Z = typ_block_sum(zs, red, it, lane, wave), S = typ_block_sum(ss, red, it, lane, wave);
+  if (!(Z > 0.0) || !isfinite(Z) || !isfinite(S)) return -1;
+  const double t = S / Z;
+  long long dk[NJ]; // the distance's bits: ordered as the distances are (d >= 0); past V: above every probe
+  double tot = 0.0;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    p[j] = p[j] / Z;
+    tot += p[j];
+    dk[j] = 0x7fffffffffffffffll;
+    if (j * 256 + tid < V) {
+      const double d = fabs((m - (double)pf_unkey(key[j])) - t);
+      if (isfinite(d)) dk[j] = __double_as_longlong(d);
+    }
+  }
+  long long lo = -1ll, hi = 0x7fefffffffffffffll; // M(lo) < mass <= M(hi); hi: the largest finite distance's pattern
+  double n_in = 0.0; // the number of distances in (lo, hi]
+#pragma unroll
+  for (int j = 0; j < NJ; j++) n_in += dk[j] <= hi ? 1.0 : 0.0;
+  typ_block_sum2(tot, n_in, red2, it2, lane, wave);
+  if (!(tot >= mass)) return -1; // the mass is never reached: the literal keeps the whole row
+  // Every probe also counts the distances in (lo, mid]: once a single distance is left in (lo, hi] it is theta (M is constant between two distances), which
+  // ends the search after some 20 probes instead of 63; distances that tie run the bisection to its end.
+  while (hi - lo > 1ll && n_in != 1.0) {
+    const long long mid = lo + ((hi - lo) >> 1);
+    double ms = 0.0, nc = 0.0;
+#pragma unroll
+    for (int j = 0; j < NJ; j++) {
+      ms += dk[j] <= mid ? p[j] : 0.0;
+      nc += (dk[j] <= mid && dk[j] > lo) ? 1.0 : 0.0;
+    }
+    typ_block_sum2(ms, nc, red2, it2, lane, wave);
+    if (ms >= mass) { hi = mid; n_in = nc; }
+    else { lo = mid; n_in -= nc; }
+  }
+  if (hi - lo > 1ll) { // one distance in (lo, hi]: its pattern (a non-negative double: fmaxf's order is not needed, the others contribute 0)
+    double dv = 0.0;
+#pragma unroll
+    for (int j = 0; j < NJ; j++)
+      if (dk[j] > lo && dk[j] <= hi) dv = __longlong_as_double(dk[j]);
+    hi = __double_as_longlong(typ_block_sum(dv, red, it, lane, wave)); // a sum with one non-zero term: exact
+  }
+  const double theta = __longlong_as_double(hi), E2 = 2.0 * (TTS_TYP_TOL_D + TTS_TYP_TOL_REL * (t + theta));
+  double m_le = 0.0, m_lt = 0.0, n_le = 0.0, n_eq = 0.0, n_win = 0.0;
+  float xe = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const double d = __longlong_as_double(dk[j]); // (past V: a NaN pattern, every comparison below is false)
+    if (dk[j] <= hi) { m_le += p[j]; n_le += 1.0; memb |= 1ull << j; }
+    if (dk[j] < hi) m_lt += p[j];
+    if (dk[j] == hi) { n_eq += 1.0; xe = fmaxf(xe, pf_unkey(key[j])); }
+    if (d >= theta - E2 && d <= theta + E2) n_win += 1.0;
+  }
+  m_le = typ_block_sum(m_le, red, it, lane, wave); m_lt = typ_block_sum(m_lt, red, it, lane, wave);
+  n_le = typ_block_sum(n_le, red, it, lane, wave); n_eq = typ_block_sum(n_eq, red, it, lane, wave); n_win = typ_block_sum(n_win, red, it, lane, wave);
+  xe = typ_block_max(xe, red, it, lane, wave);
+  double n_eqx = 0.0;
+#pragma unroll
+  for (int j = 0; j < NJ; j++)
+    if (dk[j] == hi && pf_unkey(key[j]) == xe) n_eqx += 1.0;
+  n_eqx = typ_block_sum(n_eqx, red, it, lane, wave);
+  const bool ok = m_le >= mass + TTS_TYP_TOL_M && m_lt < mass - TTS_TYP_TOL_M && n_win == n_eq && n_eqx == n_eq;
+  return ok ? (int)n_le : -1;
+}
+
 // One row's list: threshold search, index-ordered compaction and the values (pf_value). The ONE body of sample_prefilter_kernel<false / true> and of
 // sample_prefilter_rows_kernel (a workgroup of 256 threads per row; src = the row's logits, o = its TTS_PF_WORDS words; penm: pf_history_mask, read only
 // under PEN). pf_min and penalty are workgroup-uniform.
-template <bool PEN>
+// TYP (typical sampling, mass > 0 workgroup-uniform): the typical set of the penalised row is decided first (typical_members; undecided: n = -1); search, compaction
+// and value write then run over the members only, a non-member counting as masked (key 0). Fewer than pf_min members: the list is the whole set and header word
+// 1 says so (TTS_PF_WHOLE: the host tail accepts n < top_k under it).
+template <bool PEN, bool TYP = false>
 __device__ __forceinline__ void prefilter_row_block(const float *__restrict__ src, int32_t *__restrict__ o, int mask_stop, int pf_min, unsigned long long penm,
-                                                    float penalty) {
+                                                    float penalty, float mass = 0.f) {
   constexpr int NJ = (V + 255) / 256; // 33
   __shared__ int red[2][4];
   __shared__ int4 tab[NJ];
@@ -1334,6 +1481,19 @@ __device__ __forceinline__ void prefilter_row_block(const float *__restrict__ sr
   }
   unsigned lo = 0u, hi = 0xffffffffu, t = 0u; // count(lo) > PF_MAX, count(hi) < pf_min
   int n = -1, it = 0;
+  bool whole = false;
+  if (TYP) {
+    unsigned long long memb;
+    const int nm = typical_members(key, mass, memb);
+    if (nm < 0) {
+      if (tid == 0) o[0] = -1;
+      return;
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; j++)
+      if (!((memb >> j) & 1ull)) key[j] = 0u;
+    if (nm < pf_min) { whole = true; n = nm; t = 1u; hi = lo; } // nm < pf_min <= TTS_PF_MAX: every member (a finite value's key is >= 1); no search
+  }
   while (hi - lo > 1u) {
     const unsigned mid = lo + ((hi - lo) >> 1);
     int cw = 0;
@@ -1371,7 +1531,7 @@ __device__ __forceinline__ void prefilter_row_block(const float *__restrict__ sr
     }
     base += r.x + r.y + r.z + r.w;
   }
-  if (tid == 0) { o[0] = n; o[1] = 0; o[2] = 0; o[3] = 0; }
+  if (tid == 0) { o[0] = n; o[1] = (TYP && whole) ? TTS_PF_WHOLE : 0; o[2] = 0; o[3] = 0; }
 }
 
 template <bool PEN>
@@ -1388,12 +1548,30 @@ __global__ __launch_bounds__(256) void sample_prefilter_kernel(const float *__re
   prefilter_row_block<PEN>(logits + (size_t)c * V, out + (size_t)c * TTS_PF_WORDS, mask_stop, pf_min, penm, penalty);
 }
 
+// The prefilter under typical sampling (mass > 0), a kernel of its own: sample_prefilter_kernel<false / true> are what they were. The typical set is that of
+// the PENALISED row, so the kernel penalises in either scope and its lists hold penalised values: HIST (scope 1) with the history set as sample_prefilter_kernel<true>;
+// scope 0 the one id this step was fed, which is the id the host would penalise (the previous sample).
+template <bool HIST>
+__global__ __launch_bounds__(256) void sample_prefilter_typical_kernel(const float *__restrict__ logits, int mask_stop, int pf_min, int32_t *__restrict__ out,
+                                                                       uint32_t *__restrict__ hist, const int32_t *__restrict__ toks, float penalty, float mass) {
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const int tok = toks[c]; // 0 <= tok < V (ar_step checks)
+  unsigned long long penm;
+  if (HIST) {
+    uint32_t *hc = hist + (size_t)c * TTS_HIST_WORDS;
+    if (tid == 0) hc[tok >> 5] |= 1u << (tok & 31); // one workgroup per candidate, one writer
+    penm = pf_history_mask(hc, tok, tid);
+  } else penm = pf_token_mask(tok, tid);
+  prefilter_row_block<true, true>(logits + (size_t)c * V, out + (size_t)c * TTS_PF_WORDS, mask_stop, pf_min, penm, penalty, mass);
+}
+
 // The prefilter of a session opened with TTS_AR_ROW_CONTROLS: every row under its own controls, none of them baked into the launch. ctl [rows padded to whole
-// tiles] = {pf_min_for(top_k), the penalty's bits, the penalty scope, 0} per row, written outside the graph (ar_session_controls: at admission, for the
+// tiles] = {pf_min_for(top_k), the penalty's bits, the penalty scope, the typical mass' bits} per row, written outside the graph (ar_session_controls: at admission, for the
 // slots the request takes, always); an empty or parked row keeps the entry of its last request and is never sampled. The entry's address is workgroup-uniform and
 // its load is issued first, beside the row's first logits loads. pf_min above TTS_PF_MAX writes n = -1 for this row only. Scope 1: the penalised values,
 // as sample_prefilter_kernel<true>; scope 0: pf_value<true> with no bit of penm set, which is sample_prefilter_kernel<false>'s value. The fed token joins the
-// row's history set whatever the scope, as in the scope-1 graph: an admission resets the rows it takes.
+// row's history set whatever the scope, as in the scope-1 graph: an admission resets the rows it takes. The entry's fourth word: the bits of the row's typical
+// mass, 0 = off (a workgroup-uniform branch): rows with and without typical sampling and with different masses share the launch.
 __global__ __launch_bounds__(256) void sample_prefilter_rows_kernel(const float *__restrict__ logits, int mask_stop, const int4 *__restrict__ ctl,
                                                                     int32_t *__restrict__ out, uint32_t *__restrict__ hist, const int32_t *__restrict__ toks) {
   const int c = blockIdx.x, tid = threadIdx.x;
@@ -1401,6 +1579,11 @@ __global__ __launch_bounds__(256) void sample_prefilter_rows_kernel(const float 
   uint32_t *hc = hist + (size_t)c * TTS_HIST_WORDS;
   const int tok = toks[c]; // 0 <= tok < V (ar_session_step checks)
   if (tid == 0) hc[tok >> 5] |= 1u << (tok & 31); // one workgroup per row, one writer
+  if (rc.w) { // typical sampling: penalised in either scope (sample_prefilter_typical_kernel)
+    const unsigned long long pent = rc.z ? pf_history_mask(hc, tok, tid) : pf_token_mask(tok, tid);
+    prefilter_row_block<true, true>(logits + (size_t)c * V, out + (size_t)c * TTS_PF_WORDS, mask_stop, rc.x, pent, __int_as_float(rc.y), __int_as_float(rc.w));
+    return;
+  }
   const unsigned long long penm = rc.z ? pf_history_mask(hc, tok, tid) : 0ull;
   prefilter_row_block<true>(logits + (size_t)c * V, out + (size_t)c * TTS_PF_WORDS, mask_stop, rc.x, penm, __int_as_float(rc.y));
 }
@@ -1454,7 +1637,7 @@ struct ArState {
   // step state's n_past to 0 (embed_session_kernel); the host block behind h_toks is [tokens[B] | n_past[Bpad] | pos_id[B]].
   bool session = false;
   // A session opened with TTS_AR_ROW_CONTROLS: its step ends with sample_prefilter_rows_kernel, which reads every row's sampler controls from ctl
-  // ([tiles * 16] int4 {pf_min_for(top_k), penalty bits, penalty scope, 0}; reserved at open, written by ar_session_controls outside the graph). Such a step
+  // ([tiles * 16] int4 {pf_min_for(top_k), penalty bits, penalty scope, typical mass bits}; reserved at open, written by ar_session_controls outside the graph). Such a step
   // bakes none of step_scope / step_pf_min / step_penalty and has a graph slot of its own, so a uniform session of the same shape keeps its graph.
   bool rows = false;
   DevBuf ctl;
@@ -1483,7 +1666,8 @@ struct ArState {
   DevBuf hist;
   bool hist_dev_valid = false;
   int step_scope = 0, step_pf_min = TTS_PF_MIN; // what the step being enqueued bakes in: the penalty scope, the prefilter's keep bound
-  float step_penalty = 2.0f;                    // and, under scope 1, the penalty
+  float step_penalty = 2.0f;                    // and, under scope 1 or typical sampling, the penalty
+  float step_mass = 0.f;                        // and the typical mass (0: the prefilter kernels of before)
   // one captured step per mode (a caller alternating tts_ar_step / tts_ar_step_sample, or bench's device_topk on/off loop, re-instantiated
   // the ~150-node graph on every switch)
   hipGraph_t graphs[5] = {};         // [3]: the session step (one mode per session; kept across sessions of the same shape); [4]: a rows session's step
@@ -1494,11 +1678,12 @@ struct ArState {
     int B = 0, max_pos = 0, lut = 0, wmode = 0, mode = 0, multi = 0; // multi: 2 = a session step
     int rows = 0;              // a session with per-row controls: scope, pf_min and penalty below are 0, the history sets and the control table are always in p
     int scope = 0, pf_min = 0; // the sampler controls a step bakes in: penalty scope (an extra node / the penalising prefilter), the prefilter's keep bound (modes 1, 2)
-    float penalty = 0;         // scope 1, modes 1 / 2
+    float penalty = 0;         // scope 1 or typical sampling, modes 1 / 2
+    float mass = 0;            // the typical mass, modes 1 / 2
     const void *p[14] = {};
     bool operator==(const GraphSig &o) const {
       return B == o.B && max_pos == o.max_pos && lut == o.lut && wmode == o.wmode && mode == o.mode && multi == o.multi && rows == o.rows && scope == o.scope &&
-             pf_min == o.pf_min && penalty == o.penalty && std::equal(p, p + 14, o.p);
+             pf_min == o.pf_min && penalty == o.penalty && mass == o.mass && std::equal(p, p + 14, o.p);
     }
   } graph_sigs[5];
   GraphSig current_sig(int lut, int wmode) const {
@@ -1506,7 +1691,8 @@ struct ArState {
     g.B = B; g.max_pos = max_pos; g.lut = lut; g.wmode = wmode; g.mode = step_mode; g.multi = session ? 2 : multi;
     const bool rw = session && rows;
     g.rows = rw;
-    g.scope = rw ? 0 : step_scope; g.pf_min = (step_mode && !rw) ? step_pf_min : 0; g.penalty = (step_scope && step_mode && !rw) ? step_penalty : 0.f;
+    g.scope = rw ? 0 : step_scope; g.pf_min = (step_mode && !rw) ? step_pf_min : 0; g.mass = (step_mode && !rw) ? step_mass : 0.f;
+    g.penalty = ((step_scope || g.mass > 0.f) && step_mode && !rw) ? step_penalty : 0.f;
     const void *q[14] = {h.p, qkv.p, att.p, ff.p, kcache.p, vcache.p, d_toks.p, logits.p, h_toks, h_logits, h_pf, (multi || session) ? row_off.p : nullptr,
                          (step_scope || rw) ? hist.p : nullptr, rw ? ctl.p : nullptr};
     std::copy(q, q + 14, g.p);
@@ -2295,6 +2481,12 @@ static int enqueue_decode_step(tts_ctx *ctx, ArState *st) {
     if (rows)
       sample_prefilter_rows_kernel<<<B, 256, 0, ctx->stream>>>(st->logits.as<float>(), st->step_mode == 2, st->ctl.as<int4>(), st->h_pf, st->hist.as<uint32_t>(),
                                                                st->h_toks);
+    else if (st->step_mass > 0.f && st->step_scope)
+      sample_prefilter_typical_kernel<true><<<B, 256, 0, ctx->stream>>>(st->logits.as<float>(), st->step_mode == 2, st->step_pf_min, st->h_pf, st->hist.as<uint32_t>(),
+                                                                         st->h_toks, st->step_penalty, st->step_mass);
+    else if (st->step_mass > 0.f)
+      sample_prefilter_typical_kernel<false><<<B, 256, 0, ctx->stream>>>(st->logits.as<float>(), st->step_mode == 2, st->step_pf_min, st->h_pf, nullptr, st->h_toks,
+                                                                          st->step_penalty, st->step_mass);
     else if (st->step_scope)
       sample_prefilter_kernel<true><<<B, 256, 0, ctx->stream>>>(st->logits.as<float>(), st->step_mode == 2, st->step_pf_min, st->h_pf, st->hist.as<uint32_t>(),
                                                                  st->h_toks, st->step_penalty);
@@ -2350,6 +2542,7 @@ int ar_step(tts_ctx *ctx, const int32_t *prev_ids, int step_i, float *logits_out
   st->step_scope = ctx->ar_penalty_scope;
   st->step_pf_min = pf_min_for(ctx->ar_sp.top_k);
   st->step_penalty = ctx->ar_sp.penalty;
+  st->step_mass = ctx->ar_sp.typ_mass;
   if (st->step_scope && !st->hist_dev_valid) { // before this step's ids join the host copy: the step's own kernel adds them on the device
     TTS_HIP(ctx, st->hist.reserve(st->hist_host.size() * 4));
     TTS_HIP(ctx, hipMemcpy(st->hist.p, st->hist_host.data(), st->hist_host.size() * 4, hipMemcpyHostToDevice));
@@ -2507,7 +2700,7 @@ int ar_graph_captures(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->graph_capt
 // ---------------------------------------------------------------------------------------------
 // A control table entry: what the penalising prefilter reads of one row's sampler controls.
 static int4 control_entry(const SamplerParams &sp, int scope) {
-  return make_int4(pf_min_for(sp.top_k), (int)__builtin_bit_cast(uint32_t, sp.penalty), scope, 0);
+  return make_int4(pf_min_for(sp.top_k), (int)__builtin_bit_cast(uint32_t, sp.penalty), scope, (int)__builtin_bit_cast(uint32_t, sp.typ_mass)); // (mass 0.f: all bits 0)
 }
 static void hist_reset_row(uint32_t *hb) { // what a begin leaves: ids 1 and 8192 (the prompt-shaped penalty row of step 0)
   std::fill(hb, hb + TTS_HIST_WORDS, 0u);
@@ -2623,6 +2816,7 @@ int ar_session_step(tts_ctx *ctx, const int32_t *toks, const int32_t *n_past, co
   st->step_scope = ctx->ar_penalty_scope;
   st->step_pf_min = pf_min_for(ctx->ar_sp.top_k);
   st->step_penalty = ctx->ar_sp.penalty;
+  st->step_mass = ctx->ar_sp.typ_mass;
   double kv_rows = 0;
   for (int r = 0; r < B; r++) {
     st->h_toks[r] = toks[r];

@@ -49,7 +49,8 @@ static int sample_next(tts_ctx *c, const char *fn, const SampleCall &s, int32_t 
     if (a.history) { ar_history_ids(a.c, a.s.c0 + b, a.hist); p = a.hist.data(); k = (int)a.hist.size(); }
     else { p = a.s.ids + (size_t)b * a.s.ids_per_cand; k = a.s.ids_per_cand; }
   };
-  if (sample_candidates_list(c, s.gen, s.sp, ar_host_lists(c) + (size_t)s.c0 * TTS_PF_WORDS, ids_of, history, s.n, out,
+  // (typical sampling: the device penalises in either scope before it decides the set, so its lists hold penalised values)
+  if (sample_candidates_list(c, s.gen, s.sp, ar_host_lists(c) + (size_t)s.c0 * TTS_PF_WORDS, ids_of, history || s.sp.typ_mass > 0, s.n, out,
                              [&a](int b) { return ar_fetch_logits_row(a.c, a.s.c0 + b); }, s.fallbacks, s.retired))
     return fail(c, TTS_ERR_HIP, "%s: fetching a logits row failed", fn);
   return TTS_OK;
@@ -254,7 +255,7 @@ struct SessionOptions { // puts the session's options into the context for the l
   ~SessionOptions() { c->ar_sp = sp; c->ar_penalty_scope = scope; c->ar_weights = w; c->ggml_lut = lut; c->device_topk = topk; }
 };
 bool same_controls(const SamplerParams &a, int sa, const SamplerParams &b, int sb) {
-  return a.temp == b.temp && a.top_k == b.top_k && a.top_p == b.top_p && a.penalty == b.penalty && sa == sb;
+  return a.temp == b.temp && a.top_k == b.top_k && a.top_p == b.top_p && a.penalty == b.penalty && a.typ_mass == b.typ_mass && sa == sb;
 }
 void session_release(ArSession &s, int id) {
   auto it = s.reqs.find(id);
@@ -359,6 +360,7 @@ void ar_drv_limits(const tts_ctx *c, int &max_cand, int &max_steps) { max_cand =
 void ar_drv_defaults(const tts_ctx *c, tts_ar_request *req) {
   const ArSession &s = *c->session;
   req->temperature = s.sp.temp; req->top_k = s.sp.top_k; req->top_p = s.sp.top_p; req->repetition_penalty = s.sp.penalty; req->penalty_scope = s.scope;
+  req->typical_mass = s.sp.typ_mass;
 }
 
 int ar_drv_admit(tts_ctx *c, const char *fn, const int32_t *text_ids, int n_text, const float *voice, int n_cand, uint32_t seed, const int32_t *stop_at,

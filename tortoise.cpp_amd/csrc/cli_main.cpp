@@ -45,6 +45,8 @@
 //   autoregressive sampler (options ar_temperature, ar_top_k, ar_top_p, ar_repetition_penalty, ar_penalty_scope). A value out of range or another scope name is a usage
 //   error (exit 1) before a model is loaded or a worker started; an absent flag leaves the engine option alone. --devices N workers receive the flags with the rest
 //   of the command line; --timing 1 echoes them ("[timing] ar sampler ...").
+// --typical-mass <x> (0 = off, the default; 0 < x < 1): locally typical sampling (option ar_typical_mass; upstream's typical_sampling / typical_mass), under the
+//   same rules: out of range is a usage error; given, the value is appended to the "[timing] ar sampler" line.
 // --decoder diffusion|hifigan (default diffusion = the reference's 80 diffusion steps + UnivNet): hifigan sends the kept candidates' latents and their voices through ONE
 //   tts_hifigan_decode call (upstream tortoise-tts' api_fast.py path: no diffusion, no noise, no vocoder) and writes 256 samples per frame. --hifigan-model <file>
 //   (default <models>/ggml-hifigan-model.bin); the diffusion and vocoder models are then neither loaded nor required. --clvp, --split-text and several --voice work
@@ -110,6 +112,8 @@ int main(int argc, char **argv) {
   bool have_sampler = false, have_eta = false, have_k = false; // a flag that is absent leaves the engine's option (default, or --option) alone
   double ar_temp = 0.8, ar_top_k = 50, ar_top_p = 0.8, ar_pen = 2.0; // the autoregressive sampler's controls, same rule
   std::string ar_scope = "last";
+  double ar_typ = 0;
+  bool have_typ = false;
   std::string decoder = "diffusion", hifiganPath;
   bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
@@ -160,6 +164,7 @@ int main(int argc, char **argv) {
     else if (a == "--top-k") { ar_top_k = std::atof(argv[i + 1]); have_top_k = true; }
     else if (a == "--top-p") { ar_top_p = std::atof(argv[i + 1]); have_top_p = true; }
     else if (a == "--repetition-penalty") { ar_pen = std::atof(argv[i + 1]); have_pen = true; }
+    else if (a == "--typical-mass") { ar_typ = std::atof(argv[i + 1]); have_typ = true; }
     else if (a == "--penalty-scope") { ar_scope = argv[i + 1]; have_scope = true; }
     else if (a == "--rccl-id") rccl_id = argv[i + 1]; // worker mode (set by the parent)
     else if (a == "--shard") { // worker mode (set by the parent): "r/N"
@@ -189,6 +194,7 @@ int main(int argc, char **argv) {
   if (!(ar_top_k >= 1 && ar_top_k <= 8194) || ar_top_k != std::floor(ar_top_k)) { fprintf(stderr, "--top-k %g: an integer in 1 .. 8194\n", ar_top_k); return 1; }
   if (!(ar_top_p > 0 && ar_top_p <= 1) || !((float)ar_top_p > 0)) { fprintf(stderr, "--top-p %g: a value in (0, 1]\n", ar_top_p); return 1; }
   if (!std::isfinite(ar_pen) || !(ar_pen >= 1) || !std::isfinite((float)ar_pen)) { fprintf(stderr, "--repetition-penalty %g: a finite value >= 1\n", ar_pen); return 1; }
+  if (ar_typ != 0 && (!(ar_typ > 0 && ar_typ < 1) || !((float)ar_typ > 0 && (float)ar_typ < 1))) { fprintf(stderr, "--typical-mass %g: 0 (off) or a value in (0, 1)\n", ar_typ); return 1; }
   if (ar_scope != "last" && ar_scope != "history") { fprintf(stderr, "--penalty-scope %s: last or history\n", ar_scope.c_str()); return 1; }
   if (split_ids != 0 && (devices > 1 || exchange == "rccl" || shard >= 0)) {
     fprintf(stderr, "--split-text cannot be combined with --devices > 1 or --exchange rccl (one process runs all chunks)\n");
@@ -333,10 +339,12 @@ int main(int argc, char **argv) {
     return die(ctx, "--sampler");
   if ((have_temp && tts_set_option(ctx, "ar_temperature", ar_temp)) || (have_top_k && tts_set_option(ctx, "ar_top_k", ar_top_k)) ||
       (have_top_p && tts_set_option(ctx, "ar_top_p", ar_top_p)) || (have_pen && tts_set_option(ctx, "ar_repetition_penalty", ar_pen)) ||
-      (have_scope && tts_set_option(ctx, "ar_penalty_scope", ar_scope == "history" ? 1.0 : 0.0)))
-    return die(ctx, "--temperature / --top-k / --top-p / --repetition-penalty / --penalty-scope");
+      (have_scope && tts_set_option(ctx, "ar_penalty_scope", ar_scope == "history" ? 1.0 : 0.0)) || (have_typ && tts_set_option(ctx, "ar_typical_mass", ar_typ)))
+    return die(ctx, "--temperature / --top-k / --top-p / --repetition-penalty / --penalty-scope / --typical-mass");
   if (timing) {
-    fprintf(stderr, "[timing] ar sampler temperature %g, top-k %g, top-p %g, repetition-penalty %g, penalty-scope %s\n", ar_temp, ar_top_k, ar_top_p, ar_pen, ar_scope.c_str());
+    char typ[48] = ""; // (the line is what it was without the flag)
+    if (have_typ) snprintf(typ, sizeof typ, ", typical-mass %g", ar_typ);
+    fprintf(stderr, "[timing] ar sampler temperature %g, top-k %g, top-p %g, repetition-penalty %g, penalty-scope %s%s\n", ar_temp, ar_top_k, ar_top_p, ar_pen, ar_scope.c_str(), typ);
     if (shard >= 0) fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d (worker %d/%d)\n", sampler.c_str(), ddim_eta, cond_free_k, steps, shard, nshards);
     else fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d\n", sampler.c_str(), ddim_eta, cond_free_k, steps);
     fprintf(stderr, "[timing] decoder %s\n", decoder.c_str());

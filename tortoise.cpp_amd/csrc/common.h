@@ -107,6 +107,7 @@ struct SamplerParams {
   float top_p = 0.8f;   // top_p_inplace masks while the ascending cumulative sum is <= 1 - top_p (the reference's literal 0.2)
   float penalty = 2.0f; // apply_penalty: g < 0 ? g * penalty : g / penalty
   double top_p_cut() const { return 1.0 - (double)top_p; } // compared against the float sum widened to double, as `x <= 0.2` is; exact: 1 - 0.8f is the largest float below 0.2
+  float typ_mass = 0.f; // option "ar_typical_mass": 0 = off; 0 < mass < 1: locally typical sampling on the penalised row, before the temperature (host_logic.cpp: typical_keep)
 };
 
 } // namespace tts
@@ -357,6 +358,17 @@ int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const SamplerParams 
                            int32_t *out,
                            const std::function<const float *(int)> &full_row, int *n_fallbacks, const char *retired = nullptr);
 int host_prefilter_row(const float *row, int keep, int32_t *list);
+// Locally typical sampling ("ar_typical_mass"; host_logic.cpp). typical_keep: THE literal definition on a penalised row, keep[i] = 1 for the members; returns
+// their number. typical_keep_device_rule: the set as the device prefilter decides it (ar.hip: typical_members), the literal's set or -1 where the error bounds
+// leave it open. host_prefilter_row_typical: the list the device writes for a penalised row (header word 1 = TTS_PF_WHOLE: the whole typical set, n may be
+// below the sampler's top-k); -1 where the device would write n = -1.
+int typical_keep(const float *row, double mass, char *keep);
+int typical_keep_device_rule(const float *row, double mass, char *keep);
+int host_prefilter_row_typical(const float *row, double mass, int pf_min, int32_t *list);
+enum { TTS_PF_WHOLE = 1 };
+// What the device's distances and mass sums may differ from the literal's by (derived in ar.hip at typical_members): |d - d_literal| <= TTS_TYP_TOL_D +
+// TTS_TYP_TOL_REL (t + d), |M - c_literal| <= TTS_TYP_TOL_M.
+constexpr double TTS_TYP_TOL_D = 0x1p-33, TTS_TYP_TOL_REL = 0x1p-49, TTS_TYP_TOL_M = 0x1p-35;
 int sample_one_row(const float *row, const int32_t *ids, int ids_per_cand, float uniform);
 int sample_one_from_list(const int32_t *list, const int32_t *ids, int ids_per_cand, float uniform);
 // the same two and the literal formulation with explicit parameters (tts_host_sample_row_ex / tts_host_sample_prefiltered_ex)

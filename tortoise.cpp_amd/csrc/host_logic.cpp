@@ -368,6 +368,105 @@ static int multinomial_literal(std::vector<float> &l, float sample, double top_p
   return V - 1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Locally typical sampling (option "ar_typical_mass"; Meister et al. 2022, as HF's TypicalLogitsWarper states it and upstream tortoise-tts' typical_sampling /
+// typical_mass hands it to generate). THE definition, on the penalised float row x and in double throughout: m = max x; e_i = exp(x_i - m); Z = sum e_i in index
+// order; ln p_i = (x_i - m) - ln Z; p_i = exp(ln p_i); H = -sum p_i ln p_i (terms with p_i = 0 skipped); d_i = |-ln p_i - H|; stable ascending sort by d; c_j =
+// the cumulative p in that order; j* = the first j with c_j >= mass (V - 1 if none); the members are {i : d_i <= d_(j*)}: ties at the cut survive, the smallest d
+// is always kept. Every other statement of the stage (sample_one's engine path, the device body in ar.hip, typical_keep_device_rule) is held to this one.
+// ---------------------------------------------------------------------------------------------
+int typical_keep(const float *row, double mass, char *keep) {
+#pragma clang fp contract(off)
+  const int V = TTS_VOCAB_MEL;
+  thread_local std::vector<double> lnp, pr, d;
+  thread_local std::vector<int> ord;
+  lnp.resize(V); pr.resize(V); d.resize(V); ord.resize(V);
+  double m = (double)row[0];
+  for (int i = 1; i < V; i++) m = std::max(m, (double)row[i]);
+  double Z = 0;
+  for (int i = 0; i < V; i++) Z += std::exp((double)row[i] - m);
+  const double lnZ = std::log(Z);
+  double H = 0;
+  for (int i = 0; i < V; i++) {
+    lnp[i] = ((double)row[i] - m) - lnZ;
+    pr[i] = std::exp(lnp[i]);
+    if (pr[i] != 0) H -= pr[i] * lnp[i];
+  }
+  for (int i = 0; i < V; i++) { d[i] = std::fabs(-lnp[i] - H); ord[i] = i; }
+  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return d[a] < d[b]; });
+  double c = 0;
+  int js = V - 1;
+  for (int j = 0; j < V; j++) {
+    c += pr[ord[j]];
+    if (c >= mass) { js = j; break; }
+  }
+  const double cut = d[ord[js]];
+  int n = 0;
+  for (int i = 0; i < V; i++) { keep[i] = d[i] <= cut; n += keep[i]; }
+  return n;
+}
+
+// The set as the device body decides it (ar.hip: typical_members; the bounds are derived there and in DESIGN.md "What pins typical sampling"). With a = m - x >= 0
+// the distance is d_i = |a_i - t|, t = sum a_i e_i / Z = H - ln Z (ln Z cancels), so one scalar orders the row. theta = the smallest d whose inclusive mass
+// M(theta) = sum {p_i : d_i <= theta} reaches `mass`. The set {d <= theta} is the literal's when
+//   - no other d lies within 2 E of theta, E = TTS_TYP_TOL_D + TTS_TYP_TOL_REL (t + theta) >= |d - d_literal| (elements AT theta must share one logit value: equal
+//     logits have equal literal distances, and ties survive the literal's cut);
+//   - M(theta) >= mass + TTS_TYP_TOL_M and the mass strictly below theta is < mass - TTS_TYP_TOL_M (TTS_TYP_TOL_M >= |M - c_literal|).
+// Otherwise -1: the caller takes the full row and the literal. The sums here run in another order than the device's; both stay inside the same bounds.
+int typical_keep_device_rule(const float *row, double mass, char *keep) {
+#pragma clang fp contract(off)
+  const int V = TTS_VOCAB_MEL;
+  std::vector<double> e(V), d(V);
+  std::vector<int> ord(V);
+  float mf = row[0];
+  for (int i = 1; i < V; i++) mf = std::max(mf, row[i]);
+  const double m = (double)mf;
+  double Z = 0, S = 0;
+  for (int i = 0; i < V; i++) { e[i] = std::exp((double)row[i] - m); Z += e[i]; S += (m - (double)row[i]) * e[i]; }
+  if (!(Z > 0) || !std::isfinite(Z) || !std::isfinite(S)) return -1;
+  const double t = S / Z;
+  for (int i = 0; i < V; i++) { d[i] = std::fabs((m - (double)row[i]) - t); ord[i] = i; }
+  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return d[a] < d[b]; });
+  double below = 0;
+  for (int j = 0; j < V;) {
+    int k = j;
+    double at = 0;
+    while (k < V && d[ord[k]] == d[ord[j]]) at += e[ord[k++]] / Z;
+    const double incl = below + at;
+    if (incl >= mass) {
+      const double theta = d[ord[j]], E2 = 2.0 * (TTS_TYP_TOL_D + TTS_TYP_TOL_REL * (t + theta));
+      if (!(incl >= mass + TTS_TYP_TOL_M) || !(below < mass - TTS_TYP_TOL_M)) return -1;
+      for (int q = j + 1; q < k; q++) if (row[ord[q]] != row[ord[j]]) return -1;
+      if (j > 0 && d[ord[j - 1]] >= theta - E2) return -1;
+      if (k < V && d[ord[k]] <= theta + E2) return -1;
+      for (int i = 0; i < V; i++) keep[i] = d[i] <= theta;
+      return k;
+    }
+    below = incl;
+    j = k;
+  }
+  return -1; // the mass is never reached (the literal then keeps the whole row): left to the literal
+}
+
+int host_prefilter_row_typical(const float *row, double mass, int pf_min, int32_t *list) {
+  const int V = TTS_VOCAB_MEL;
+  std::fill(list, list + TTS_PF_WORDS, 0);
+  list[0] = -1;
+  if (pf_min > TTS_PF_MAX) return -1;
+  std::vector<char> keep(V);
+  const int nm = typical_keep_device_rule(row, mass, keep.data());
+  if (nm < 0) return -1;
+  std::vector<float> masked(row, row + V);
+  for (int i = 0; i < V; i++) if (!keep[i]) masked[i] = -std::numeric_limits<float>::infinity();
+  if (nm >= pf_min) return host_prefilter_row(masked.data(), pf_min, list); // the members >= the usual threshold
+  float *lv = (float *)(list + 4 + TTS_PF_MAX); // fewer than pf_min (<= TTS_PF_MAX) members: the whole set
+  int k = 0;
+  for (int i = 0; i < V; i++)
+    if (keep[i]) { list[4 + k] = i; lv[k] = row[i]; k++; }
+  list[0] = nm; list[1] = TTS_PF_WHOLE;
+  return nm;
+}
+
 struct Surv { float v; int idx; float e; };
 
 // Tail shared by the full-row scan and the device-prefiltered list: `s` = the top-k survivors in INDEX order with their tempered
@@ -440,11 +539,18 @@ static int sample_one(const float *src, const int32_t *ids, int ids_per_cand, fl
   thread_local std::vector<Surv> s, asc;
   thread_local std::vector<float> l; // only materialised for the (rare) literal fallback
   thread_local std::vector<float> prow, heap;
+  thread_local std::vector<char> tkeep;
+  const bool typ = p.typ_mass > 0;
   auto literal = [&]() {
     l.assign(src, src + V);
     for (int j = 0; j < ids_per_cand; j++) {
       const int id = ids[j];
       l[id] = penalised(src[id], p.penalty);
+    }
+    if (typ) { // the typical stage: after the penalty, before the temperature; a non-member has probability exactly 0 from here on, like top_k_inplace's masked entries
+      tkeep.resize(V);
+      typical_keep(l.data(), (double)p.typ_mass, tkeep.data());
+      for (int i = 0; i < V; i++) if (!tkeep[i]) l[i] = LOWEST;
     }
     for (int i = 0; i < V; i++) l[i] /= temp;
     std::vector<float> tmp(l);
@@ -454,6 +560,22 @@ static int sample_one(const float *src, const int32_t *ids, int ids_per_cand, fl
     return multinomial_literal(l, sample, p.top_p_cut());
   };
   if (literal_only || TOPK > FAST_TOPK_MAX) return literal();
+  if (typ) {
+    // The engine's path under typical sampling: the penalised row, the literal's member set (typical_keep: one formulation), non-members masked. At most
+    // top-k members: they all survive top-k (a masked entry has probability 0 and changes no sum), so the tail runs over the members; more: the scan below
+    // over the masked row.
+    prow.assign(src, src + V);
+    for (int j = 0; j < ids_per_cand; j++) prow[ids[j]] = penalised(src[ids[j]], p.penalty);
+    tkeep.resize(V);
+    const int nm = typical_keep(prow.data(), (double)p.typ_mass, tkeep.data());
+    for (int i = 0; i < V; i++) if (!tkeep[i]) prow[i] = LOWEST;
+    if (nm <= TOPK) {
+      s.clear();
+      for (int i = 0; i < V; i++) if (tkeep[i]) s.push_back({prow[i] / temp, i, 0.f});
+      const int pick = sample_survivors(s, asc, sample, p.top_p_cut());
+      return pick < 0 ? literal() : pick;
+    }
+  }
   // gather -> apply_penalty -> scatter touches at most a few distinct ids under penalty scope 0 (the prompt-shaped
   // [1 ... 1, 8192] at step 0, the previous sample afterwards): keep them as overrides. More than four (scope 1: the
   // whole history): a penalised copy of the row is scanned instead.
@@ -468,7 +590,8 @@ static int sample_one(const float *src, const int32_t *ids, int ids_per_cand, fl
     pid[np] = id; pval[np] = penalised(src[id], p.penalty); np++;
   }
   const float *row = src;
-  if (many) {
+  if (typ) { row = prow.data(); np = 0; } // penalised and masked above
+  else if (many) {
     prow.assign(src, src + V);
     for (int j = 0; j < ids_per_cand; j++) prow[ids[j]] = penalised(src[ids[j]], p.penalty);
     row = prow.data();
@@ -517,13 +640,16 @@ static int sample_one(const float *src, const int32_t *ids, int ids_per_cand, fl
 //     thr > cut (the logits between rank k and rank n within an ulp or two of each other) -> -1;
 //   - raw lists: more than 4 distinct penalty ids are not looked up here -> -1; a tie among the survivors needs the literal
 //     formulation over the full row -> -1.
+// Typical sampling (p.typ_mass > 0): the list holds the row's typical MEMBERS >= thr, penalised (already_penalised in either scope), and every non-member is
+// masked, so the argument above holds with "unlisted member" for "unlisted id". whole (header word 1 = TTS_PF_WHOLE): the list is the whole typical set; n may
+// be below top-k (the set then survives top-k whole) and nothing unlisted can be missing, so thr is not consulted.
 static int sample_one_list(int n, const int32_t *idx, const float *lv, const int32_t *ids, int ids_per_cand, float sample, const SamplerParams &p,
-                           bool already_penalised) {
+                           bool already_penalised, bool whole = false) {
   const int TOPK = p.top_k;
   const float temp = p.temp;
   thread_local std::vector<Surv> s, asc;
   thread_local std::vector<float> pv;
-  if (n < TOPK) return -1;
+  if (n < TOPK && !whole) return -1;
   int pid[4]; int np = 0;
   if (!already_penalised)
     for (int j = 0; j < ids_per_cand; j++) {
@@ -542,13 +668,18 @@ static int sample_one_list(int n, const int32_t *idx, const float *lv, const int
     for (int q = 0; q < np; q++) pen |= (pid[q] == idx[i]);
     pv[i] = pen ? penalised(g, p.penalty) : g;
   }
+  if (whole && n <= TOPK) {
+    s.clear();
+    for (int i = 0; i < n; i++) s.push_back({pv[i] / temp, idx[i], 0.f});
+    return sample_survivors(s, asc, sample, p.top_p_cut());
+  }
   asc.resize(n); // scratch: the k-th largest penalised value
   for (int i = 0; i < n; i++) asc[i].v = pv[i];
   std::nth_element(asc.begin(), asc.begin() + (TOPK - 1), asc.end(), [](const Surv &a, const Surv &b) { return a.v > b.v; });
   const float hmin = asc[TOPK - 1].v;
   float cut;
   if (!topk_cut(hmin, temp, cut)) return -1;
-  if (!(thr <= cut)) return -1;
+  if (!whole && !(thr <= cut)) return -1;
   s.clear();
   for (int i = 0; i < n; i++)
     if (pv[i] >= cut) s.push_back({pv[i] / temp, idx[i], 0.f});
@@ -687,7 +818,7 @@ int sample_candidates_list(tts_ctx *ctx, std::mt19937 &gen, const SamplerParams 
     if (n < 1 || n > TTS_PF_MAX) { out[c] = -1; return; }
     const int32_t *ids = nullptr; int n_ids = 0;
     if (!already_penalised) ids_of(c, ids, n_ids);
-    out[c] = sample_one_list(n, l + 4, (const float *)(l + 4 + TTS_PF_MAX), ids, n_ids, samples[c], sp, already_penalised);
+    out[c] = sample_one_list(n, l + 4, (const float *)(l + 4 + TTS_PF_MAX), ids, n_ids, samples[c], sp, already_penalised, sp.typ_mass > 0 && (l[1] & TTS_PF_WHOLE));
   };
   if (B < 8 || ctx->sampler_threads == 0) { for (int c = 0; c < B; c++) one(c); } // ~2 us per list: the pool's wake-up costs more below 8
   else run_on_pool(ctx, B, one);
@@ -735,7 +866,7 @@ int sample_one_row_ex(const float *row, const int32_t *ids, int n_ids, float uni
 int sample_one_from_list_ex(const int32_t *list, const int32_t *ids, int n_ids, float uniform, const SamplerParams &p, bool already_penalised) {
   const int n = list[0];
   if (n < 1 || n > TTS_PF_MAX) return -1;
-  return sample_one_list(n, list + 4, (const float *)(list + 4 + TTS_PF_MAX), ids, n_ids, uniform, p, already_penalised);
+  return sample_one_list(n, list + 4, (const float *)(list + 4 + TTS_PF_MAX), ids, n_ids, uniform, p, already_penalised, p.typ_mass > 0 && (list[1] & TTS_PF_WHOLE));
 }
 int sample_one_row(const float *row, const int32_t *ids, int ids_per_cand, float uniform) { return sample_one(row, ids, ids_per_cand, uniform, SamplerParams()); }
 int sample_one_from_list(const int32_t *list, const int32_t *ids, int ids_per_cand, float uniform) {
