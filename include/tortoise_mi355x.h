@@ -134,6 +134,15 @@ const char *tts_last_error(const tts_ctx *ctx);
  * ancestral variance). See tts_diffusion for the noise layout.
  * "cond_free_k" (2.0 default = the reference's base_k, main.cpp:5988; finite and >= 0, else TTS_ERR_ARG): conditioning-free guidance strength of both samplers,
  * cfk_t = k (1 - t / n). At 2.0 every bit of the output is what it was.
+ * "cond_free" (1 default = guided, every bit what it was; 0 = unguided; any other value, a non-integer or NaN: TTS_ERR_ARG): upstream tortoise-tts' cond_free. At 0
+ * the step's layout holds the conditioned sequences only (half the rows: tts_host_diff_packed_rows_ex, tts_diffusion_last_layout) and eps is the conditioned output
+ * itself, upstream's p_mean_variance with conditioning_free=False; the learned variance is the conditioned output's as before; "cond_free_k" is validated and not
+ * read; "share_uncond" has nothing to merge; the samplers, graph replay, hoist_integrator, latency_mode (two unguided utterances fit under its row limit),
+ * multi-voice and rng_shard_* work as before. "cond_free" 1 with "cond_free_k" 0 still evaluates both branches.
+ * "diff_temperature" (1.0 default; finite, >= 0 and finite after narrowing to float, else TTS_ERR_ARG): upstream's diffusion_temperature, x_T = (float)v * z_T, one
+ * f32 multiply per element, however z_T arrives (the caller's block 0, TTS_NOISE_REFERENCE draws, the device generator). Per-step noise is never scaled; RNG
+ * consumption, noise layout and generator keys do not change. At 1.0 nothing is multiplied or launched: every bit is what it was.
+ * How unguided or cooler sampling SOUNDS cannot be judged without trained weights: the tests pin the arithmetic (DESIGN.md "What pins unguided sampling").
  * Additions within version 8, the autoregressive sampler's controls (no prototype changed; sticky per context; a refused value changes nothing and returns
  * TTS_ERR_ARG; read by tts_sample, tts_ar_step_sample, tts_autoregressive, tts_autoregressive_multi and tts_autoregressive_multi_voice). The defaults are the
  * literals of the reference's process_logits_and_sample (main.cpp:4753-4806); upstream tortoise-tts passes temperature, top_k, top_p and repetition_penalty to HF
@@ -529,10 +538,15 @@ int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand);
  *   candidates' [rows[c]][1024] back to back; rows in 1 .. 500; voice_latent2048 NULL = the loaded model's; noise: tts_diffusion's layout for this request alone
  *   (per candidate n_steps + 1 vectors of 100 * T_c; deterministic DDIM and sampler 3: x_T alone) or NULL = the device generator under `seed`. sampler, ddim_eta and
  *   cond_free_k are checked with the very predicate tts_set_option applies to "diff_sampler", "ddim_eta" and "cond_free_k".
- * tts_diff_request_init: n_cand = 1, n_steps = 80, every pointer NULL, seed = 0, and the sampler, eta and k the session pinned when it was opened.
+ *   temperature and cond_free were appended within version 8 at offset 72, the struct's size before them (the 4 padding bytes after seed are never read), and
+ *   are checked with the predicates of "diff_temperature" and "cond_free". struct_size 72 is still accepted: the request then runs with the temperature and
+ *   cond_free the session pinned (tts_host_diff_request_check: the defaults 1.0 and 1); 73 .. sizeof(tts_diff_request) - 1 is no header's struct and is refused
+ *   (TTS_ERR_ARG); sizeof(tts_diff_request) and larger is accepted. A request is guided or unguided as a whole; one layout holds both kinds side by side.
+ * tts_diff_request_init: n_cand = 1, n_steps = 80, every pointer NULL, seed = 0, and the sampler, eta, k, temperature and cond_free the session pinned when it
+ *   was opened (a 72-byte descriptor: the fields it has).
  * tts_diff_session_open(max_packed_rows, max_requests): every option the diffusion stage reads is read here and holds until tts_diff_session_close, whatever
  *   tts_set_option stores meanwhile: "attn_f32", "share_uncond", "hoist_integrator", "diff_graph", "gn_eps", "ggml_lut", "attn_proj_f16", "proj_dual_b",
- *   "gemm_wreg", "attn_f32_drop", "lc_attn_f32", "attn_q64", "fp16_check", and "diff_sampler" / "ddim_eta" / "cond_free_k" as tts_diff_request_init's
+ *   "gemm_wreg", "attn_f32_drop", "lc_attn_f32", "attn_q64", "fp16_check", and "diff_sampler" / "ddim_eta" / "cond_free_k" / "diff_temperature" / "cond_free" as tts_diff_request_init's
  *   defaults; the session always runs the batch-path GroupNorm ("latency_mode" is not bit-identical to it by design). With "hoist_integrator" on, every request
  *   is hoisted and owns n_steps x packed rows x 2 KB of device memory until it is collected; a request may then take at most 16384 packed rows (the option's
  *   value, if above 1), else tts_diff_session_admit returns TTS_ERR_LIMIT; a session opened with "hoist_integrator" 0 has no such bound. All activation buffers for max_packed_rows rows are allocated here. A session already open is closed first. TTS_ERR_ARG:
@@ -541,7 +555,7 @@ int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand);
  *   run state); after close they behave exactly as before. An AR session may be open on the same context.
  * tts_diff_session_admit: returns the request id (>= 0, never reused in a session). Every check runs before any device work and a refused call changes
  *   nothing: TTS_ERR_ARG for a null descriptor / latents / rows, a struct_size too small, n_cand < 1, rows outside 1 .. 500, n_steps < 2, a control
- *   tts_set_option would refuse, a non-finite latent or voice value; TTS_ERR_LIMIT when the request's packed rows (tts_host_diff_packed_rows) exceed
+ *   tts_set_option would refuse, a non-finite latent or voice value; TTS_ERR_LIMIT when the request's packed rows (tts_host_diff_packed_rows_ex) exceed
  *   tts_diff_session_room, exceed the hoisting bound above, or max_requests requests are held. Admission evaluates everything that does not depend on x_t for the request alone (latent
  *   conditioner, time MLP, and with "hoist_integrator" the integrator layers of all its steps) into storage the request owns; it joins the layout at the next step.
  * tts_diff_session_room: packed rows still free = max_packed_rows minus the packed rows of the running requests (a finished request holds none).
@@ -556,6 +570,8 @@ int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand);
  * TTS_ERR_STATE without one.
  * Host probes (no GPU): tts_host_diff_packed_rows: the rows Layout::build's rule gives a request alone, conditioned + unconditioned sequences: starts aligned
  *   to 8 from row 8, one guard row after every sequence, total padded to 128 (TTS_ERR_ARG for a null list, n_cand < 1 or rows outside 1 .. 500).
+ *   tts_host_diff_packed_rows_ex(cond_free): the same with cond_free 1; with 0 the conditioned sequences only, what an unguided request takes (TTS_ERR_ARG
+ *   also for a cond_free other than 0 or 1). Admission, tts_diff_session_room and the hoisting bound count a request by this number.
  *   tts_host_diff_request_check: the status tts_diff_session_admit's descriptor checks return in a session of max_packed_rows (free requests and the open
  *   flag are not its business). */
 typedef struct tts_diff_request {
@@ -569,6 +585,8 @@ typedef struct tts_diff_request {
   double ddim_eta, cond_free_k;
   const float *noise;                /* tts_diffusion's layout for this request alone, or NULL */
   uint32_t seed;                     /* device generator when noise == NULL */
+  double temperature;                /* appended within version 8 ("diff_temperature"): x_T = (float)temperature * z_T; read only when struct_size covers it */
+  int32_t cond_free;                 /* appended within version 8 ("cond_free"): 1 guided, 0 unguided; read only when struct_size covers it */
 } tts_diff_request;
 int tts_diff_request_init(tts_ctx *ctx, tts_diff_request *req);
 int tts_diff_session_open(tts_ctx *ctx, int max_packed_rows, int max_requests);
@@ -581,6 +599,7 @@ int tts_diff_session_cancel(tts_ctx *ctx, int request);
 int tts_diff_session_close(tts_ctx *ctx);
 int tts_diff_session_captures(const tts_ctx *ctx);
 int tts_host_diff_packed_rows(const int32_t *latent_rows, int n_cand);
+int tts_host_diff_packed_rows_ex(const int32_t *latent_rows, int n_cand, int cond_free);
 int tts_host_diff_request_check(const tts_diff_request *req, int max_packed_rows);
 /* One diffusion_graph evaluation (main.cpp:5749-5841 cond / 5866-5961 uncond): inputs
  * input_latent_tensor [L][1024], noise_tensor = x_t [100][T], timestep (raw 0..3999 value whose
@@ -605,6 +624,10 @@ int tts_diffusion_forward(tts_ctx *ctx, const float *latents, int latent_rows, c
 enum { TTS_NOISE_REFERENCE = 0, TTS_NOISE_DEVICE = 1 };
 int tts_diffusion(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates,
                   int n_steps, const float *noise, int noise_mode, float *mel_out);
+/* The step layout of the last tts_diffusion / tts_diffusion_multi_voice call (addition within version 8): its packed rows and the sequences the network was
+ * evaluated on per step (guided: 2 per candidate; "cond_free" 0: 1 per candidate). What tells an engine that dropped the unconditioned branch from one that
+ * zeroed k. TTS_ERR_STATE before such a call, TTS_ERR_ARG for a null pointer, TTS_ERR_HIP on a host-only context. */
+int tts_diffusion_last_layout(const tts_ctx *ctx, int32_t *packed_rows_out, int32_t *sequences_out);
 /* The timestep MLP (main.cpp:3331-3343, 3410-3428: five tiny launches at the start of every tts_diffusion / tts_diffusion_forward call) is evaluated twice
  * and compared bit for bit, and repeated when the two evaluations disagree: a tripwire kept from round 4, when an earlier form of that kernel (packed f32 FMAs)
  * returned wrong sums while a second engine process used the same GPU. Number of disagreeing evaluations since the context was created:

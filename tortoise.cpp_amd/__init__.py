@@ -46,7 +46,8 @@ AR_REQUEST_SIZE_V0 = ArRequest.typical_mass.offset
 class DiffRequest(C.Structure):
     """tts_diff_request: one diffusion-session request's candidates, step count, sampler controls, voice latent and noise (tts_diff_session_admit)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_cand", C.c_int32), ("latents", C.c_void_p), ("rows", C.c_void_p), ("voice_latent2048", C.c_void_p),
-                ("n_steps", C.c_int32), ("sampler", C.c_int32), ("ddim_eta", C.c_double), ("cond_free_k", C.c_double), ("noise", C.c_void_p), ("seed", C.c_uint32)]
+                ("n_steps", C.c_int32), ("sampler", C.c_int32), ("ddim_eta", C.c_double), ("cond_free_k", C.c_double), ("noise", C.c_void_p), ("seed", C.c_uint32),
+                ("temperature", C.c_double), ("cond_free", C.c_int32)]  # appended within version 8 at offset 72 (the struct's size before them)
 
 
 # the keys of ar_session_admit(controls=...) and the descriptor fields they set
@@ -119,7 +120,8 @@ def lib():
         "tts_diff_session_admit": (ci, [vp, C.POINTER(DiffRequest)]), "tts_diff_session_room": (ci, [vp]), "tts_diff_session_step": (ci, [vp]),
         "tts_diff_session_finished": (ci, [vp, vp, ci]), "tts_diff_session_collect": (ci, [vp, ci, vp]), "tts_diff_session_cancel": (ci, [vp, ci]),
         "tts_diff_session_close": (ci, [vp]), "tts_diff_session_captures": (ci, [vp]),
-        "tts_host_diff_packed_rows": (ci, [vp, ci]), "tts_host_diff_request_check": (ci, [C.POINTER(DiffRequest), ci]),
+        "tts_host_diff_packed_rows": (ci, [vp, ci]), "tts_host_diff_packed_rows_ex": (ci, [vp, ci, ci]),
+        "tts_diffusion_last_layout": (ci, [vp, _i32p, _i32p]), "tts_host_diff_request_check": (ci, [C.POINTER(DiffRequest), ci]),
         "tts_diffusion_forward": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p]),
         "tts_diffusion": (ci, [vp, _f32p, _i32p, ci, ci, vp, ci, _f32p]),
         "tts_vocoder_samples": (ci, [ci]),
@@ -607,7 +609,8 @@ class Engine:
     def diffusion(self, latents_list, n_steps=80, noise=None, noise_mode=NOISE_REFERENCE, voice_latents=None, voice_of_candidate=None):
         """latents_list: list of [L_c,1024]. noise: list of [(n_steps+1), 100*T_c] or None (option diff_sampler = 1 with ddim_eta = 0, and
         diff_sampler = 3: list of x_T [100*T_c]). Returns list of mel [100,T_c]. The sampler, its eta and the guidance strength are engine options (set_option:
-        diff_sampler 0 = ancestral DDPM, 1 = DDIM, 3 = DPM-Solver++(2M), deterministic: ddim_eta is checked and not read; ddim_eta; cond_free_k).
+        diff_sampler 0 = ancestral DDPM, 1 = DDIM, 3 = DPM-Solver++(2M), deterministic: ddim_eta is checked and not read; ddim_eta; cond_free_k; cond_free 0 =
+        unguided, the conditioned sequences only; diff_temperature: x_T = temperature * z_T).
         voice_latents [V, 2048] + voice_of_candidate [B]: candidate c is conditioned on voice_latents[voice_of_candidate[c]] instead of the loaded model's
         latent (tts_diffusion_multi_voice)."""
         rows = np.array([len(l) for l in latents_list], np.int32)
@@ -628,6 +631,13 @@ class Engine:
             off += 100 * t
         return out
 
+    def diffusion_last_layout(self):
+        """(packed rows, sequences) of the step layout of the last diffusion() call (tts_diffusion_last_layout): 2 sequences per candidate guided, 1 with the
+        option cond_free 0."""
+        rows, seqs = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        self._ck(self.L.tts_diffusion_last_layout(self.h, rows, seqs))
+        return int(rows[0]), int(seqs[0])
+
     # ---- in-flight batching for the diffusion stage: requests join and leave a running layout (tts_diff_session_*) ----
     def diff_session_open(self, max_packed_rows, max_requests):
         """Opens a diffusion session for layouts of up to max_packed_rows rows (host_diff_packed_rows says what a request takes) and max_requests requests.
@@ -635,9 +645,10 @@ class Engine:
         self._ck(self.L.tts_diff_session_open(self.h, max_packed_rows, max_requests))
         self._diff_frames = {}
 
-    def diff_session_admit(self, latents_list, n_steps=None, sampler=None, ddim_eta=None, cond_free_k=None, voice_latent=None, noise=None, seed=0):
+    def diff_session_admit(self, latents_list, n_steps=None, sampler=None, ddim_eta=None, cond_free_k=None, voice_latent=None, noise=None, seed=0, cond_free=None,
+                           temperature=None):
         """Admits one request: latents_list as in diffusion(); noise: list of [(n_steps+1), 100*T_c] (deterministic DDIM and sampler = 3, DPM-Solver++(2M):
-        x_T [100*T_c]) or None = the device generator under `seed`; sampler: SAMPLER_DDPM (0), SAMPLER_DDIM (1) or SAMPLER_DPMPP_2M (3); voice_latent [2048] or None = the loaded model's. Arguments left None take the session's pinned value (tts_diff_request_init).
+        x_T [100*T_c]) or None = the device generator under `seed`; sampler: SAMPLER_DDPM (0), SAMPLER_DDIM (1) or SAMPLER_DPMPP_2M (3); voice_latent [2048] or None = the loaded model's; cond_free: 1 guided, 0 unguided (the request's conditioned sequences only; host_diff_packed_rows(rows, cond_free) says what it takes); temperature: x_T = temperature * z_T. Arguments left None take the session's pinned value (tts_diff_request_init).
         Returns the request id. The mel diff_session_collect() returns is bit for bit what diffusion() returns for the request alone."""
         req = DiffRequest()
         req.struct_size = C.sizeof(DiffRequest)
@@ -647,7 +658,8 @@ class Engine:
         nz = None if noise is None else np.ascontiguousarray(np.concatenate([np.asarray(n, np.float32).reshape(-1) for n in noise]))
         v = None if voice_latent is None else np.ascontiguousarray(voice_latent, np.float32).reshape(2 * DMODEL)
         req.n_cand, req.latents, req.rows, req.voice_latent2048, req.noise, req.seed = len(rows), _ptr(lat), _ptr(rows), _ptr(v), _ptr(nz), seed
-        for field, value in (("n_steps", n_steps), ("sampler", sampler), ("ddim_eta", ddim_eta), ("cond_free_k", cond_free_k)):
+        for field, value in (("n_steps", n_steps), ("sampler", sampler), ("ddim_eta", ddim_eta), ("cond_free_k", cond_free_k), ("temperature", temperature),
+                             ("cond_free", None if cond_free is None else int(cond_free))):
             if value is not None:
                 setattr(req, field, value)
         rid = self._ck(self.L.tts_diff_session_admit(self.h, C.byref(req)))
@@ -873,21 +885,25 @@ def host_ar_request_check(max_cand, max_steps, struct_size=None, n_cand=1, seed=
     return lib().tts_host_ar_request_check(C.byref(req), max_cand, max_steps)
 
 
-def host_diff_packed_rows(latent_rows):
-    """Packed rows a diffusion-session request of these latent row counts takes (conditioned + unconditioned sequences, Layout::build's rule; no GPU)."""
+def host_diff_packed_rows(latent_rows, cond_free=True):
+    """Packed rows a diffusion-session request of these latent row counts takes (conditioned + unconditioned sequences, Layout::build's rule; no GPU).
+    cond_free False / 0: an unguided request, the conditioned sequences only (tts_host_diff_packed_rows_ex)."""
     r = np.ascontiguousarray(latent_rows, np.int32).reshape(-1)
-    return lib().tts_host_diff_packed_rows(_ptr(r), len(r))
+    if cond_free is True or cond_free == 1:
+        return lib().tts_host_diff_packed_rows(_ptr(r), len(r))
+    return lib().tts_host_diff_packed_rows_ex(_ptr(r), len(r), int(cond_free))
 
 
 def host_diff_request_check(max_packed_rows, latents=None, rows=None, n_cand=None, n_steps=80, sampler=0, ddim_eta=0.0, cond_free_k=2.0, voice=None, struct_size=None,
-                            null_latents=False, null_rows=False):
+                            null_latents=False, null_rows=False, cond_free=1, temperature=1.0):
     """The status tts_diff_session_admit's descriptor checks return for these fields in a session with max_packed_rows free rows (no GPU). latents: list of
     [L_c, 1024]; rows / n_cand override what the list implies. sampler: 0, 1 or 3 (DPM-Solver++(2M)) pass, as for tts_set_option("diff_sampler")."""
     lat = np.ascontiguousarray(np.concatenate([np.asarray(l, np.float32).reshape(-1, DMODEL) for l in latents]))
     rw = np.ascontiguousarray([len(l) for l in latents] if rows is None else rows, np.int32)
     v = None if voice is None else np.ascontiguousarray(voice, np.float32).reshape(2 * DMODEL)
     req = DiffRequest(C.sizeof(DiffRequest) if struct_size is None else struct_size, len(latents) if n_cand is None else n_cand, None if null_latents else _ptr(lat),
-                      None if null_rows else _ptr(rw), _ptr(v), n_steps, int(sampler), ddim_eta, cond_free_k, None, 0)
+                      None if null_rows else _ptr(rw), _ptr(v), n_steps, int(sampler), ddim_eta, cond_free_k, None, 0, temperature, 0)
+    req.cond_free = int(cond_free)
     return lib().tts_host_diff_request_check(C.byref(req), max_packed_rows)
 
 

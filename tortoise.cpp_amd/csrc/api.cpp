@@ -217,6 +217,14 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     if (const char *e = diff_control_error(2, value)) return fail(c, TTS_ERR_ARG, "%s", e);
     c->cond_free_k = (float)value;
   }
+  else if (k == "diff_temperature") {
+    if (const char *e = diff_control_error(3, value)) return fail(c, TTS_ERR_ARG, "%s", e);
+    c->diff_temperature = value;
+  }
+  else if (k == "cond_free") {
+    if (const char *e = diff_control_error(4, value)) return fail(c, TTS_ERR_ARG, "%s", e);
+    c->cond_free = (int)value;
+  }
   // additions within version 8: the autoregressive sampler's controls (read by tts_sample, tts_ar_step_sample and the tts_autoregressive* drivers)
   // (and, per request, by tts_ar_session_admit_ex: ar_control_error is the one statement of what each of them accepts)
   else if (ar_control_index(k) >= 0) {
@@ -757,7 +765,7 @@ int tts_diff_request_init(tts_ctx *c, tts_diff_request *req) {
   NEED_CTX(c);
   NEED_DIFF_SESSION(c, "tts_diff_request_init");
   if (!req) return fail(c, TTS_ERR_ARG, "tts_diff_request_init: null request");
-  if (req->struct_size < sizeof(tts_diff_request))
+  if (!diff_request_size_ok(req->struct_size))
     return fail(c, TTS_ERR_ARG, "tts_diff_request_init: struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_diff_request) first)", req->struct_size,
                 sizeof(tts_diff_request));
   req->n_cand = 1; req->latents = nullptr; req->rows = nullptr; req->voice_latent2048 = nullptr; req->n_steps = 80; req->noise = nullptr; req->seed = 0;
@@ -780,7 +788,10 @@ int tts_diff_session_admit(tts_ctx *c, const tts_diff_request *req) {
   NEED_CTX(c);
   NEED_DIFF_SESSION(c, "tts_diff_session_admit");
   std::string why; // every check before any device work
-  if (int rc = diff_request_check(req, diff_session_room(c), why)) return fail(c, rc, "tts_diff_session_admit: %s", why.c_str());
+  tts_diff_request pinned;
+  pinned.struct_size = sizeof pinned;
+  diff_session_defaults(c, &pinned);
+  if (int rc = diff_request_check(req, diff_session_room(c), pinned.temperature, pinned.cond_free, why)) return fail(c, rc, "tts_diff_session_admit: %s", why.c_str());
   return guarded(c, [&] { return diff_session_admit(c, req); });
 }
 int tts_diff_session_step(tts_ctx *c) {
@@ -825,6 +836,13 @@ int tts_diffusion_multi_voice(tts_ctx *c, const float *latents, const int32_t *r
   NO_DIFF_SESSION(c, "tts_diffusion_multi_voice");
   if (B >= 1 && !noise && noise_mode == TTS_NOISE_DEVICE) if (int rc = shard_check(c, B)) return rc;
   return guarded(c, [&] { return diff_sample_voices(c, latents, rows, B, voice_latents, n_voices, voice_of_candidate, n_steps, noise, noise_mode, mel_out); });
+}
+int tts_diffusion_last_layout(const tts_ctx *c, int32_t *packed_rows_out, int32_t *sequences_out) {
+  if (!c || !packed_rows_out || !sequences_out) return TTS_ERR_ARG;
+  if (c->device < 0) return TTS_ERR_HIP;
+  if (c->last_diff_rows < 0) return TTS_ERR_STATE;
+  *packed_rows_out = c->last_diff_rows; *sequences_out = c->last_diff_seqs;
+  return TTS_OK;
 }
 int tts_vocoder_samples(int T) { return (T + 10) * 256 - 6; }
 int tts_vocoder(tts_ctx *c, const float *mel, const int32_t *frames, int B, const float *noise, int noise_mode, float *audio) {

@@ -40,6 +40,9 @@
 //   deterministic) and --cond-free-k <x> (guidance strength, default 2.0): the diffusion sampler behind --steps, which keeps its meaning. Another sampler name or a value
 //   out of range is a usage error (exit 1) before a model is loaded or a worker started. --devices N workers receive the flags with the rest of the command line;
 //   --timing 1 echoes them ("[timing] sampler ...", one line per process).
+// --cond-free 0|1 (default 1 = guided; 0 = unguided: the unconditioned branch is not evaluated, half the rows per step; option cond_free = upstream's cond_free) and
+//   --diffusion-temperature <x> (finite, >= 0, default 1: x_T = x * z_T; option diff_temperature = upstream's diffusion_temperature), under the same rules: another
+//   value is a usage error, workers receive them, --timing 1 echoes them on a line of their own ("[timing] cond-free ...").
 // --temperature <x> (> 0, default 0.8), --top-k <n> (1 .. 8194, default 50), --top-p <x> (0 < x <= 1, default 0.8), --repetition-penalty <x> (>= 1, default 2.0) and
 //   --penalty-scope last|history (default last = the reference: the ids of the last input; history = upstream's HF generate: every code sampled so far): the
 //   autoregressive sampler (options ar_temperature, ar_top_k, ar_top_p, ar_repetition_penalty, ar_penalty_scope). A value out of range or another scope name is a usage
@@ -51,7 +54,7 @@
 //   tts_hifigan_decode call (upstream tortoise-tts' api_fast.py path: no diffusion, no noise, no vocoder) and writes 256 samples per frame. --hifigan-model <file>
 //   (default <models>/ggml-hifigan-model.bin); the diffusion and vocoder models are then neither loaded nor required. --clvp, --split-text and several --voice work
 //   as with the diffusion decoder. Usage errors (exit 1, before a model is loaded): another decoder name; with hifigan any of --steps, --sampler, --ddim-eta,
-//   --cond-free-k, --diffusion-latent (they configure the decoder that is not run), --devices > 1 or --exchange rccl. --timing 1 names the decoder ("[timing] decoder ...").
+//   --cond-free-k, --cond-free, --diffusion-temperature, --diffusion-latent (they configure the decoder that is not run), --devices > 1 or --exchange rccl. --timing 1 names the decoder ("[timing] decoder ...").
 // --stream (with --decoder hifigan; no value) [--stream-stride N, default 16]: one candidate through tts_hifigan_stream. The samples are appended to the WAV as the
 //   callback receives them, while the autoregressive stage is still sampling, and the header's two sizes are fixed at the end: the file is byte for byte the one the
 //   run without --stream writes. --timing 1 prints when the first samples arrived ("[timing] first audio ..."), from the start of the process and from the start of the
@@ -109,6 +112,9 @@ int main(int argc, char **argv) {
   std::vector<std::pair<std::string, double>> engine_options; // --option key=value (repeatable): tts_set_option before the models are loaded
   std::string sampler = "ddpm";
   double ddim_eta = 0.0, cond_free_k = 2.0;
+  std::string cond_free = "1";
+  double diff_temp = 1.0;
+  bool have_cond_free = false, have_diff_temp = false;
   bool have_sampler = false, have_eta = false, have_k = false; // a flag that is absent leaves the engine's option (default, or --option) alone
   double ar_temp = 0.8, ar_top_k = 50, ar_top_p = 0.8, ar_pen = 2.0; // the autoregressive sampler's controls, same rule
   std::string ar_scope = "last";
@@ -160,6 +166,8 @@ int main(int argc, char **argv) {
     else if (a == "--sampler") { sampler = argv[i + 1]; have_sampler = true; }
     else if (a == "--ddim-eta") { ddim_eta = std::atof(argv[i + 1]); have_eta = true; }
     else if (a == "--cond-free-k") { cond_free_k = std::atof(argv[i + 1]); have_k = true; }
+    else if (a == "--cond-free") { cond_free = argv[i + 1]; have_cond_free = true; }
+    else if (a == "--diffusion-temperature") { diff_temp = std::atof(argv[i + 1]); have_diff_temp = true; }
     else if (a == "--temperature") { ar_temp = std::atof(argv[i + 1]); have_temp = true; }
     else if (a == "--top-k") { ar_top_k = std::atof(argv[i + 1]); have_top_k = true; }
     else if (a == "--top-p") { ar_top_p = std::atof(argv[i + 1]); have_top_p = true; }
@@ -177,7 +185,7 @@ int main(int argc, char **argv) {
   if (decoder != "diffusion" && decoder != "hifigan") { fprintf(stderr, "--decoder %s: diffusion or hifigan\n", decoder.c_str()); return 1; }
   const bool use_hifigan = decoder == "hifigan";
   if (use_hifigan) {
-    const char *bad = have_steps ? "--steps" : have_sampler ? "--sampler" : have_eta ? "--ddim-eta" : have_k ? "--cond-free-k" : !diffLatentPaths.empty() ? "--diffusion-latent" : nullptr;
+    const char *bad = have_steps ? "--steps" : have_sampler ? "--sampler" : have_eta ? "--ddim-eta" : have_k ? "--cond-free-k" : have_cond_free ? "--cond-free" : have_diff_temp ? "--diffusion-temperature" : !diffLatentPaths.empty() ? "--diffusion-latent" : nullptr;
     if (bad) { fprintf(stderr, "%s configures the diffusion decoder, which --decoder hifigan does not run\n", bad); return 1; }
     if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--decoder hifigan cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
   }
@@ -190,6 +198,8 @@ int main(int argc, char **argv) {
   if (sampler != "ddpm" && sampler != "ddim" && sampler != "dpmpp2m") { fprintf(stderr, "--sampler %s: ddpm, ddim or dpmpp2m\n", sampler.c_str()); return 1; }
   if (!(ddim_eta >= 0.0 && ddim_eta <= 1.0)) { fprintf(stderr, "--ddim-eta %g: a value in 0 .. 1\n", ddim_eta); return 1; }
   if (!(cond_free_k >= 0.0) || !std::isfinite(cond_free_k)) { fprintf(stderr, "--cond-free-k %g: a finite value >= 0\n", cond_free_k); return 1; }
+  if (cond_free != "0" && cond_free != "1") { fprintf(stderr, "--cond-free %s: 1 (guided) or 0 (unguided)\n", cond_free.c_str()); return 1; }
+  if (!(diff_temp >= 0.0) || !std::isfinite(diff_temp) || !std::isfinite((float)diff_temp)) { fprintf(stderr, "--diffusion-temperature %g: a finite value >= 0\n", diff_temp); return 1; }
   if (!std::isfinite(ar_temp) || !((float)ar_temp > 0) || !std::isfinite((float)ar_temp)) { fprintf(stderr, "--temperature %g: a finite value > 0\n", ar_temp); return 1; }
   if (!(ar_top_k >= 1 && ar_top_k <= 8194) || ar_top_k != std::floor(ar_top_k)) { fprintf(stderr, "--top-k %g: an integer in 1 .. 8194\n", ar_top_k); return 1; }
   if (!(ar_top_p > 0 && ar_top_p <= 1) || !((float)ar_top_p > 0)) { fprintf(stderr, "--top-p %g: a value in (0, 1]\n", ar_top_p); return 1; }
@@ -335,7 +345,8 @@ int main(int argc, char **argv) {
   for (const auto &kv : engine_options)
     if (tts_set_option(ctx, kv.first.c_str(), kv.second)) return die(ctx, "--option");
   if ((have_sampler && tts_set_option(ctx, "diff_sampler", sampler == "dpmpp2m" ? (double)TTS_SAMPLER_DPMPP_2M : sampler == "ddim" ? (double)TTS_SAMPLER_DDIM : (double)TTS_SAMPLER_DDPM)) || (have_eta && tts_set_option(ctx, "ddim_eta", ddim_eta)) ||
-      (have_k && tts_set_option(ctx, "cond_free_k", cond_free_k)))
+      (have_k && tts_set_option(ctx, "cond_free_k", cond_free_k)) || (have_cond_free && tts_set_option(ctx, "cond_free", cond_free == "1" ? 1.0 : 0.0)) ||
+      (have_diff_temp && tts_set_option(ctx, "diff_temperature", diff_temp)))
     return die(ctx, "--sampler");
   if ((have_temp && tts_set_option(ctx, "ar_temperature", ar_temp)) || (have_top_k && tts_set_option(ctx, "ar_top_k", ar_top_k)) ||
       (have_top_p && tts_set_option(ctx, "ar_top_p", ar_top_p)) || (have_pen && tts_set_option(ctx, "ar_repetition_penalty", ar_pen)) ||
@@ -347,6 +358,8 @@ int main(int argc, char **argv) {
     fprintf(stderr, "[timing] ar sampler temperature %g, top-k %g, top-p %g, repetition-penalty %g, penalty-scope %s%s\n", ar_temp, ar_top_k, ar_top_p, ar_pen, ar_scope.c_str(), typ);
     if (shard >= 0) fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d (worker %d/%d)\n", sampler.c_str(), ddim_eta, cond_free_k, steps, shard, nshards);
     else fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d\n", sampler.c_str(), ddim_eta, cond_free_k, steps);
+    if (shard >= 0) fprintf(stderr, "[timing] cond-free %s, diffusion-temperature %g (worker %d/%d)\n", cond_free.c_str(), diff_temp, shard, nshards);
+    else fprintf(stderr, "[timing] cond-free %s, diffusion-temperature %g\n", cond_free.c_str(), diff_temp);
     fprintf(stderr, "[timing] decoder %s\n", decoder.c_str());
   }
   if (shard >= 0) {

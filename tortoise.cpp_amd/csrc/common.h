@@ -177,6 +177,9 @@ struct tts_ctx {
   int diff_sampler = 0;    // option "diff_sampler": 0 = the reference's ancestral DDPM step (step_update_kernel: ddpm_step_value), 1 = DDIM (ddim_step_value; upstream tortoise-tts' ddim_sample), 3 = DPM-Solver++(2M) (dpmpp_step_value)
   double ddim_eta = 0;     // option "ddim_eta" in [0, 1]: 0 = deterministic DDIM (only x_T is noise); read only when diff_sampler = 1 (sampler 3 is deterministic)
   float cond_free_k = 2.0f; // option "cond_free_k": the conditioning-free guidance strength at t = n (main.cpp's base_k = 2.0), both samplers
+  int cond_free = 1;       // option "cond_free": 1 = guided (conditioned + unconditioned sequences per step); 0 = unguided: the conditioned sequences only, eps = eps_c (upstream's cond_free=False)
+  double diff_temperature = 1.0; // option "diff_temperature": x_T = (float)v * z_T (upstream's diffusion_temperature); 1 = no multiply, no launch
+  int last_diff_rows = -1, last_diff_seqs = 0; // step layout of the last tts_diffusion / tts_diffusion_multi_voice call (tts_diffusion_last_layout); -1: none yet
   bool capturing = false;  // a hipGraph is being captured on the stream: ProfScope records nothing (event records would become graph nodes)
   int stream_recaptures = 0; // decode-step graphs captured inside the last tts_hifigan_stream call's loop after its first step (tts_hifigan_stream_recaptures)
   int hfg_small_m = 0;     // option "hfg_small_m": tts_hifigan_chunk runs a convolution whose longest window has at most this many rows on the small-M tile (0, the default until
@@ -463,13 +466,15 @@ int diff_cond_enc_load(tts_ctx *ctx, const char *path);
 void diff_cond_enc_free(DiffCondEncState *);
 int diff_cond_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out2048);
 int diff_fp16_check(tts_ctx *ctx, int64_t counts[2]);            // diffusion.hip
-// The diffusion sampler's three controls (options "diff_sampler", "ddim_eta", "cond_free_k"): the ONE statement of what each accepts, for tts_set_option and for a
-// request descriptor (tts_diff_session_admit, tts_host_diff_request_check). which: 0 sampler, 1 eta, 2 k. Returns the refusal's text, or null (host_logic.cpp).
+// The diffusion sampler's five controls (options "diff_sampler", "ddim_eta", "cond_free_k", "diff_temperature", "cond_free"): the ONE statement of what each accepts, for tts_set_option and for a
+// request descriptor (tts_diff_session_admit, tts_host_diff_request_check). which: 0 sampler, 1 eta, 2 k, 3 temperature ("diff_temperature"), 4 cond_free ("cond_free"). Returns the refusal's text, or null (host_logic.cpp).
 const char *diff_control_error(int which, double value);
+bool diff_request_size_ok(uint32_t struct_size); // the growth rule of tts_diff_request (host_logic.cpp)
 // rows Layout::build gives the sequences `frames` (diffusion.hip): starts aligned to 8 from row 8, a guard row after each, total padded to 128 (host_logic.cpp)
 int diff_packed_rows(const int *frames, int n);
 // what a request descriptor must satisfy in a session of max_packed_rows, before any device work: the status and, in `why`, the text (host_logic.cpp)
-int diff_request_check(const tts_diff_request *req, int max_packed_rows, std::string &why);
+// pinned_temperature / pinned_cond_free: what a descriptor of the size before those fields were appended runs under (the session's)
+int diff_request_check(const tts_diff_request *req, int max_packed_rows, double pinned_temperature, int pinned_cond_free, std::string &why);
 // the diffusion session (diffusion.hip); arguments already checked by api.cpp
 int diff_session_open(tts_ctx *ctx, int max_packed_rows, int max_requests);
 int diff_session_admit(tts_ctx *ctx, const tts_diff_request *req);
@@ -480,7 +485,7 @@ int diff_session_collect(tts_ctx *ctx, int request, float *mel_out);
 int diff_session_cancel(tts_ctx *ctx, int request);
 void diff_session_close(tts_ctx *ctx);
 int diff_session_captures(const tts_ctx *ctx);
-void diff_session_defaults(const tts_ctx *ctx, tts_diff_request *req); // the sampler, eta and k the open session pinned
+void diff_session_defaults(const tts_ctx *ctx, tts_diff_request *req); // the sampler, eta, k and (where struct_size covers them) temperature and cond_free the open session pinned
 int diff_set_cond_latent(tts_ctx *ctx, const float *latent2048); // diffusion.hip: overrides the weight file's diffusion_conditioning_latent
 
 // ---- the AR request driver (ar_driver.cpp; its device-free rules: ar_rules.cpp): autoregressive(), main.cpp:5042-5367, stated once for the single calls,

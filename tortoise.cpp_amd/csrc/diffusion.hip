@@ -726,21 +726,28 @@ struct StepScalars { float max_log, min_log, cfk, sqrt_recip, sqrt_recipm1, coef
 // its graph 160 times): the schedule scalars, the noise block of the step, the generator key.
 struct StepEntry { StepScalars sc; int has_noise; long long noise_off; unsigned philox_step; unsigned pad; };
 
+// The eps a step's update works on: THE one statement of it for the three samplers (ddpm_step_value; guided_clipped_x0, hence the DDIM and DPM-Solver++ bodies).
+// Guided (option "cond_free" 1): the conditioning-free mix, two multiplies and a subtraction, one rounding each. Unguided ("cond_free" 0; upstream's
+// p_mean_variance with conditioning_free=False): eps_c itself; eps_u is not read (its caller loaded nothing) and neither is cfk.
+__device__ __forceinline__ float step_eps(const StepScalars &sc, float eps_c, float eps_u, bool guided) {
+#pragma clang fp contract(off)
+  return guided ? (1 + sc.cfk) * eps_c - sc.cfk * eps_u : eps_c;
+}
 // The arithmetic of one element of the ancestral step: the ancestral half of step_update_kernel.
 // Every f32 operation below is the reference's, one rounding each (main.cpp:5970-6030 is plain C++ built without FMA contraction; the oracle's copy is compiled with
 // -ffp-contract=off). hipcc would contract a * b + c * d into FMAs: a last-bit difference in x_t at EVERY step that the torch-f32 yardstick of the parity floor (which
 // shares the oracle's update) does not have, and that a chaotic 80- / 200-step loop amplifies like any other f32 difference (round 6: the 200-step loop at full depth
 // sat at 1.44-1.58 x its f32-vs-f32 floor in BOTH arithmetic modes).
 // noise: this step's block in the layout of x (the value is read at xi), or null: the device generator's stream `stream`, element idx.
-__device__ __forceinline__ float ddpm_step_value(const StepScalars &sc, float eps_c, float var_c, float eps_u, float xv, const float *__restrict__ noise, size_t xi,
-                                                 uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
+__device__ __forceinline__ float ddpm_step_value(const StepScalars &sc, bool guided, float eps_c, float var_c, float eps_u, float xv, const float *__restrict__ noise,
+                                                 size_t xi, uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
   float mean, model_log_variance;
   {
 #pragma clang fp contract(off)
     const float frac = (var_c + 1) / 2;
     // calculate_model_variance is called with (min_log, max_log) swapped (main.cpp:5998-5999)
     model_log_variance = frac * sc.min_log + (1 - frac) * sc.max_log;
-    const float eps = (1 + sc.cfk) * eps_c - sc.cfk * eps_u;
+    const float eps = step_eps(sc, eps_c, eps_u, guided);
     float x0 = sc.sqrt_recip * xv - sc.sqrt_recipm1 * eps;
     x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
     mean = sc.coef1 * x0 + sc.coef2 * xv;
@@ -759,11 +766,11 @@ struct DdimEntry { float c_x0, c_eps, sigma, pad; };
 // The guided, clipped x0 prediction of a step (p_mean_variance with clip_denoised) and the scaled x it came from: the ONE statement of it for the DDIM and the
 // DPM-Solver++ bodies, so that a first-order step of the latter cannot drift from the former.
 struct GuidedX0 { float xs, x0; };
-__device__ __forceinline__ GuidedX0 guided_clipped_x0(const StepScalars &sc, float eps_c, float eps_u, float xv) {
+__device__ __forceinline__ GuidedX0 guided_clipped_x0(const StepScalars &sc, bool guided, float eps_c, float eps_u, float xv) {
   GuidedX0 g;
   {
 #pragma clang fp contract(off)
-    const float eps_g = (1 + sc.cfk) * eps_c - sc.cfk * eps_u;
+    const float eps_g = step_eps(sc, eps_c, eps_u, guided);
     g.xs = sc.sqrt_recip * xv;
     const float x0 = g.xs - sc.sqrt_recipm1 * eps_g;
     g.x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
@@ -784,17 +791,17 @@ __device__ __forceinline__ float ddim_value_from_x0(const StepScalars &sc, const
   }
   return outv;
 }
-__device__ __forceinline__ float ddim_step_value(const StepScalars &sc, const DdimEntry &d, float eps_c, float eps_u, float xv, const float *__restrict__ noise, size_t xi,
-                                                 uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
-  return ddim_value_from_x0(sc, d, guided_clipped_x0(sc, eps_c, eps_u, xv), noise, xi, seed, stream, step, idx);
+__device__ __forceinline__ float ddim_step_value(const StepScalars &sc, const DdimEntry &d, bool guided, float eps_c, float eps_u, float xv,
+                                                 const float *__restrict__ noise, size_t xi, uint64_t seed, uint32_t stream, uint32_t step, uint32_t idx) {
+  return ddim_value_from_x0(sc, d, guided_clipped_x0(sc, guided, eps_c, eps_u, xv), noise, xi, seed, stream, step, idx);
 }
 // DPM-Solver++(2M) (Lu et al. 2022; upstream tortoise-tts' fast presets; the reference has no such sampler) on the same guided, clipped x0. DpmEntry: this step's
 // scalars from DiffSchedule::build_dpmpp. A first-order step IS the DDIM eta-0 step on this step's DdimEntry (sigma = 0: no noise is read); a second-order step adds
 // the previous step's x0, which every step leaves in the request's d_prev (layout of x) after reading it. One rounding per f32 operation, as above.
 struct DpmEntry { float a, b, c; int order; };
-__device__ __forceinline__ float dpmpp_step_value(const StepScalars &sc, const DdimEntry &d, const DpmEntry &p, float eps_c, float eps_u, float xv,
+__device__ __forceinline__ float dpmpp_step_value(const StepScalars &sc, const DdimEntry &d, const DpmEntry &p, bool guided, float eps_c, float eps_u, float xv,
                                                   float *__restrict__ d_prev, size_t xi) {
-  const GuidedX0 g = guided_clipped_x0(sc, eps_c, eps_u, xv);
+  const GuidedX0 g = guided_clipped_x0(sc, guided, eps_c, eps_u, xv);
   float outv;
   if (p.order == 2) {
 #pragma clang fp contract(off)
@@ -821,6 +828,8 @@ struct ReqDev {
   unsigned long long seed;
   int n_steps, sampler, rows_local;
   unsigned stream_base;    // generator stream of candidate 0 (tts_diffusion: the shard's first global candidate; a session request: 0)
+  int guided;              // 1: every sequence of the request has an unconditioned copy in the layout (seq_partner); 0 (option "cond_free" 0, tts_diffusion_forward):
+                           // its sequences stand alone, seq_partner names their own first row and no partner row is written or read
 };
 // Start of a step. Request live[i] (a slot) copies the scale / shift block of ITS step to block `slot` of ss_cur, the fixed address the GroupNorm kernels read.
 // grid (16, n_live), block 256.
@@ -840,8 +849,8 @@ __global__ void step_advance_kernel(const ReqDev *__restrict__ req, int *__restr
   if (ctr[slot] < req[slot].n_steps) ctr[slot] += 1;
 }
 // x_t -> fp16 GEMM operand rows [row][128] for the conditioned sequence and its unconditioned copy. x of sequence s is its request's, at seq_xoff[s]; the copy
-// starts at row seq_partner[s] (-1 marks the unconditioned sequences themselves; a sequence evaluated alone names its own first row and stores the same value
-// twice). grid: rows; block 128.
+// starts at row seq_partner[s] (-1 marks the unconditioned sequences themselves; a sequence of an unguided request names its own first row and writes its
+// operand row once). grid: rows; block 128.
 __global__ __launch_bounds__(128) void step_xt_kernel(const ReqDev *__restrict__ req, const int *__restrict__ seq_req, const int64_t *__restrict__ seq_xoff,
                                                       const int *__restrict__ seq_partner, const int *__restrict__ row_seq, const int *__restrict__ row_t,
                                                       const int *__restrict__ seq_len, __half *__restrict__ xt16) {
@@ -850,10 +859,11 @@ __global__ __launch_bounds__(128) void step_xt_kernel(const ReqDev *__restrict__
   const int p = seq_partner[s];
   if (p < 0) return;
   const int T = seq_len[s], t = row_t[r];
-  const float v = (ch < 100) ? req[seq_req[s]].x[seq_xoff[s] + (size_t)ch * T + t] : 0.f;
+  const ReqDev &q = req[seq_req[s]];
+  const float v = (ch < 100) ? q.x[seq_xoff[s] + (size_t)ch * T + t] : 0.f;
   const __half hv = __float2half_rn(v);
   xt16[(size_t)r * XTC + ch] = hv;
-  xt16[(size_t)(p + t) * XTC + ch] = hv;
+  if (q.guided) xt16[(size_t)(p + t) * XTC + ch] = hv;
 }
 // The hoisted integrator's code-embedding operand of this step: row r of the layout takes row row_src[r] of its own request's ce16_all, at that request's own step.
 // Guard rows: zero, as in the request's buffer. grid: rows; block 128 (one uint4 each).
@@ -871,7 +881,8 @@ __global__ __launch_bounds__(128) void step_row_select_kernel(const ReqDev *__re
 }
 // The sampler update, in place on the requests' x. net: [rows][256] f32 (channels 0..99 eps, 100..199 variance logits). Per sequence: the request's StepEntry /
 // DdimEntry / DpmEntry at the request's step, its sampler, its noise block or generator key (stream = the request's base + the candidate's index in it), and the unconditioned
-// partner's first row from a table. Sequences of a request that has run all its steps are left untouched. grid: rows; block 128.
+// partner's first row from a table (a guided request's; an unguided request's sequences read their own rows of net only: step_eps). Sequences of a request that
+// has run all its steps are left untouched. grid: rows; block 128.
 __global__ __launch_bounds__(128) void step_update_kernel(const float *__restrict__ net, const ReqDev *__restrict__ req, const int *__restrict__ ctr,
                                                           const int *__restrict__ seq_req, const int64_t *__restrict__ seq_xoff,
                                                           const int *__restrict__ seq_partner, const int *__restrict__ seq_cand,
@@ -888,24 +899,30 @@ __global__ __launch_bounds__(128) void step_update_kernel(const float *__restric
   const int T = seq_len[s], t = row_t[r];
   const size_t xi = seq_xoff[s] + (size_t)ch * T + t;
   const float eps_c = net[(size_t)r * 256 + ch];
-  const float eps_u = net[(size_t)(p + t) * 256 + ch];
+  const bool guided = q.guided != 0; // uniform over the workgroup
+  const float eps_u = guided ? net[(size_t)(p + t) * 256 + ch] : 0.f;
   const uint32_t stream = q.stream_base + (uint32_t)seq_cand[s], idx = (uint32_t)(ch * T + t);
   if (q.sampler == 1) {
     const DdimEntry d = q.dtab[k];
-    q.x[xi] = ddim_step_value(e.sc, d, eps_c, eps_u, q.x[xi], noise, xi, q.seed, stream, e.philox_step, idx);
+    q.x[xi] = ddim_step_value(e.sc, d, guided, eps_c, eps_u, q.x[xi], noise, xi, q.seed, stream, e.philox_step, idx);
   } else if (q.sampler == 3) {
     const DdimEntry d = q.dtab[k];
     const DpmEntry pe = q.ptab[k];
-    q.x[xi] = dpmpp_step_value(e.sc, d, pe, eps_c, eps_u, q.x[xi], q.d_prev, xi);
+    q.x[xi] = dpmpp_step_value(e.sc, d, pe, guided, eps_c, eps_u, q.x[xi], q.d_prev, xi);
   } else {
     const float var_c = net[(size_t)r * 256 + 100 + ch];
-    q.x[xi] = ddpm_step_value(e.sc, eps_c, var_c, eps_u, q.x[xi], noise, xi, q.seed, stream, e.philox_step, idx);
+    q.x[xi] = ddpm_step_value(e.sc, guided, eps_c, var_c, eps_u, q.x[xi], noise, xi, q.seed, stream, e.philox_step, idx);
   }
 }
 
 __global__ void philox_fill_kernel(float *__restrict__ x, int64_t n, uint64_t seed, uint32_t stream, uint32_t step) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) x[i] = philox_normal(seed, stream, step, (uint32_t)i);
+}
+// Option "diff_temperature": x_T = temperature * z_T over a request's whole x, one f32 multiply per element (upstream: torch.randn(shape) * temperature).
+__global__ void scale_xT_kernel(float *__restrict__ x, int64_t n, float temperature) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) x[i] = temperature * x[i];
 }
 
 // net output [rows][256] -> reference layout [200][T] for one sequence.
@@ -1045,6 +1062,8 @@ struct DiffReq {
   int n_cand = 0, n_steps = 0, sampler = 0;
   uint64_t seed = 0;
   uint32_t stream_base = 0;  // generator stream of candidate 0
+  bool guided = true;        // the layout holds an unconditioned copy of every candidate's sequence ("cond_free" 1); false: the conditioned sequences only
+  int n_seq() const { return guided ? 2 * n_cand : n_cand; } // the request's sequences in a layout: conditioned 0 .. n_cand - 1, then (guided) their copies
   bool host_noise = false;   // the steps read `noise` (block 0 = x_T, block 1 + idx = step idx), not the device generator
   bool noise_streamed = false; // `noise` is reserved and nothing of it filled: the caller sends the blocks beside the loop (diff_sample)
   int n_vec = 0;             // noise vectors per candidate: n_steps + 1, or 1 (deterministic DDIM and DPM-Solver++: x_T alone)
@@ -1058,11 +1077,11 @@ struct DiffReq {
   // the session's share
   int id = 0, slot = 0, done = 0, cls = 0, packed = 0;
   bool finished = false;
-  std::vector<int> seq_src;  // per sequence of the request (conditioned 0 .. n_cand - 1, then their unconditioned copies): its first row in the request's row buffers
+  std::vector<int> seq_src;  // per sequence of the request (n_seq(): conditioned 0 .. n_cand - 1, then a guided request's unconditioned copies): its first row in the request's row buffers
   int src_rows = 0;          // rows of those buffers (the request's own packed layout; its integrator layout without hoisting)
   ReqDev dev() const {
     return ReqDev{ss_all.as<float>(), tab.as<StepEntry>(), dtab.as<DdimEntry>(), sampler == 3 ? ptab.as<DpmEntry>() : nullptr, ce16_all.as<__half>(), x.as<float>(),
-                  sampler == 3 ? d_prev.as<float>() : nullptr, host_noise ? noise.as<float>() : nullptr, seed, n_steps, sampler, src_rows, stream_base};
+                  sampler == 3 ? d_prev.as<float>() : nullptr, host_noise ? noise.as<float>() : nullptr, seed, n_steps, sampler, src_rows, stream_base, guided ? 1 : 0};
   }
 };
 
@@ -1114,15 +1133,16 @@ struct StepBufs {
     n_live = (int)slots.size();
     return TTS_OK;
   }
-  // One request in slot 0 that owns the layout: its candidates' sequences, then (tts_diffusion) their unconditioned copies; every row takes its own row of the
-  // request's buffers. A layout without copies (tts_diffusion_forward: one branch) names each sequence as its own partner.
+  // One request in slot 0 that owns the layout: its candidates' sequences, then (a guided request) their unconditioned copies; every row takes its own row of the
+  // request's buffers. A layout without copies (an unguided request; tts_diffusion_forward: one branch) names each sequence as its own partner.
   int set_single(tts_ctx *ctx, const DiffReq &r) {
     const int B = r.n_cand;
+    if (lay.ns != r.n_seq()) return fail(ctx, TTS_ERR_STATE, "diffusion step: a layout of %d sequences for a request of %d", lay.ns, r.n_seq());
     std::vector<int> sreq(lay.ns, 0), partner(lay.ns, -1), cand(lay.ns), rsrc(lay.rows, -1);
     std::vector<int64_t> xoff(lay.ns);
     for (int s = 0; s < lay.ns; s++) {
       cand[s] = s; xoff[s] = r.xoff[s % B];
-      if (s < B) partner[s] = lay.start[lay.ns == B ? s : s + B];
+      if (s < B) partner[s] = lay.start[r.guided ? s + B : s];
       for (int t = 0; t < lay.len[s]; t++) rsrc[lay.start[s] + t] = lay.start[s] + t;
     }
     return set_tables(ctx, {r.dev()}, {0}, xoff, sreq, partner, cand, rsrc);
@@ -2245,7 +2265,7 @@ int diff_forward(tts_ctx *ctx, const float *latents, int L, const float *x_t, in
   DiffReq &r = st->req;
   const int T = sb.lay.len[0];
   CHECK(precompute_time(ctx, st, std::vector<int>{timestep}, r.ss_all));
-  r.n_cand = 1; r.n_steps = 1; r.host_noise = false;
+  r.n_cand = 1; r.n_steps = 1; r.host_noise = false; r.guided = false; r.sampler = 0;
   r.xoff.assign(1, 0);
   TTS_HIP(ctx, r.x.reserve((size_t)100 * T * 4));
   TTS_HIP(ctx, hipMemcpyAsync(r.x.p, x_t, (size_t)100 * T * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -2265,6 +2285,7 @@ int diff_forward(tts_ctx *ctx, const float *latents, int L, const float *x_t, in
 struct ReqSpec {
   const float *latents; const int32_t *rows; int n_cand, n_steps; // the candidates' AR latents
   int sampler; double eta; float k;                              // 0 = the reference's ancestral step, 1 = DDIM, 3 = DPM-Solver++(2M); ddim_eta; guidance k
+  bool guided; float temperature;                                // "cond_free" (false: the conditioned sequences only, k not read); "diff_temperature" (x_T = temperature z_T)
   const float *voices; int n_voices; const int32_t *voice_of;    // conditioning latents [n_voices][2048] and the candidates' rows of them (null: all row 0), or
                                                                   // voices = null: the loaded model's latent
   const float *noise; int noise_mode;                            // caller noise; else TTS_NOISE_REFERENCE: drawn here, candidate after candidate; else the device generator
@@ -2292,6 +2313,13 @@ static void build_step_tables(const DiffSchedule &sched, int n_steps, bool ddim,
     if (dpm) ptab[idx] = DpmEntry{sched.dpm_a[t], sched.dpm_b[t], sched.dpm_c[t], sched.dpm_order[t]};
   }
 }
+// Option "diff_temperature" on a request whose x holds z_T. The device copy of a host noise block 0 stays unscaled: nothing reads it again.
+static int scale_xT(tts_ctx *ctx, DiffReq &r, float temperature) {
+  if (temperature == 1.0f) return TTS_OK;
+  scale_xT_kernel<<<(int)((r.total + 255) / 256), 256, 0, ctx->stream>>>(r.x.as<float>(), r.total, temperature);
+  TTS_HIP(ctx, hipGetLastError());
+  return TTS_OK;
+}
 // Everything of a request that is evaluated before its first step, for the request ALONE, in the single call's run state (st->sb, which no step of a session
 // reads) and into storage the request owns: the voice, layouts and code embedding (setup_batch), schedule and scale / shift blocks (precompute_time), the hoisted
 // integrator (precompute_integrator), x_T and the noise blocks, the step tables. The voice enters the stage at ONE place (the scale / shift of the code norm that
@@ -2310,11 +2338,11 @@ static int prepare_request(tts_ctx *ctx, DiffState *st, DiffReq &r, const ReqSpe
     st->mv_tab = st->mv_buf.as<float>();
     st->mv_idx = (const int *)(st->mv_buf.as<float>() + nf);
   }
-  CHECK(setup_batch(ctx, st, sp.latents, std::vector<int>(sp.rows, sp.rows + B), true, true));
+  CHECK(setup_batch(ctx, st, sp.latents, std::vector<int>(sp.rows, sp.rows + B), true, sp.guided));
   if (sp.timing) (void)hipStreamSynchronize(ctx->stream);
   r.t_setup = std::chrono::steady_clock::now();
   Layout &lay = st->sb.lay;
-  r.n_cand = B; r.n_steps = n_steps; r.sampler = sp.sampler; r.seed = sp.seed; r.stream_base = sp.stream_base;
+  r.n_cand = B; r.n_steps = n_steps; r.sampler = sp.sampler; r.seed = sp.seed; r.stream_base = sp.stream_base; r.guided = sp.guided;
   // Deterministic DDIM (ddim_eta = 0) has ONE noise vector per candidate, x_T: n_vec = 1 (no per-step block is drawn, allocated or uploaded); with eta > 0 layout,
   // draw order and generator keys are those of the ancestral sampler. DPM-Solver++(2M) is deterministic: its noise is DDIM eta 0's whatever eta holds, and its
   // first-order steps read the eta-0 DDIM table.
@@ -2368,6 +2396,7 @@ static int prepare_request(tts_ctx *ctx, DiffState *st, DiffReq &r, const ReqSpe
     }
     TTS_HIP(ctx, hipGetLastError());
   }
+  if (!r.noise_streamed) CHECK(scale_xT(ctx, r, sp.temperature)); // streamed noise: x_T arrives after this function (diff_sample_with)
   std::vector<StepEntry> tab;
   std::vector<DdimEntry> dtab;
   std::vector<DpmEntry> ptab;
@@ -2404,7 +2433,7 @@ static int diff_sample_with(tts_ctx *ctx, const float *latents, const int32_t *r
   // order (x_T, then step after step), the stream orders copy k + 1 in front of step k's update kernel. More candidates draw candidate after candidate
   // (main.cpp:5638, 6020-6021): their order does not allow it.
   const bool want_pipe = !noise && noise_mode == TTS_NOISE_REFERENCE && B == 1 && ctx->noise_pipeline != 0;
-  ReqSpec sp{latents, rows, B, n_steps, ctx->diff_sampler, ctx->ddim_eta, ctx->cond_free_k, voices, n_voices, voice_of, noise, noise_mode,
+  ReqSpec sp{latents, rows, B, n_steps, ctx->diff_sampler, ctx->ddim_eta, ctx->cond_free_k, ctx->cond_free != 0, (float)ctx->diff_temperature, voices, n_voices, voice_of, noise, noise_mode,
              want_pipe ? &st->noise_host : nullptr, ctx->seed_value, (uint32_t)shard_base(ctx),
              ctx->hoist_integrator == 0 ? 0 : ctx->hoist_integrator > 1 ? ctx->hoist_integrator : HOIST_MAX_ROWS, timing};
   CHECK(prepare_request(ctx, st, r, sp));
@@ -2417,7 +2446,9 @@ static int diff_sample_with(tts_ctx *ctx, const float *latents, const int32_t *r
   if (r.noise_streamed) {
     TTS_HIP(ctx, draw_block(0));
     TTS_HIP(ctx, hipMemcpyAsync(r.x.p, r.noise.p, total * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    CHECK(scale_xT(ctx, r, sp.temperature));
   }
+  ctx->last_diff_rows = sb.lay.rows; ctx->last_diff_seqs = sb.lay.ns; // tts_diffusion_last_layout
   // one request in slot 0, its device step counter at 0 (see StepEntry)
   TTS_HIP(ctx, sb.ctr.reserve(64));
   TTS_HIP(ctx, sb.ss_cur.reserve((size_t)st->n_res() * 2 * C * 4));
@@ -2499,8 +2530,9 @@ struct DiffSession {
   // the options read at tts_diff_session_open: every session call runs under them (SessOptions), whatever tts_set_option has stored since
   int attn_f32 = 0, hoist = 0, graph = 0, sampler = 0;
   bool share_uncond = true, hoisted = false;
-  double eta = 0;
+  double eta = 0, temperature = 1.0;
   float k = 2.0f;
+  int cond_free = 1;
   std::map<int, std::unique_ptr<DiffReq>> reqs; // by id: the order of admission
   std::vector<char> slot_busy;
   int next_id = 0, captures = 0;
@@ -2526,6 +2558,7 @@ int diff_session_captures(const tts_ctx *ctx) { return ctx->diff_session->captur
 void diff_session_defaults(const tts_ctx *ctx, tts_diff_request *req) {
   const DiffSession &S = *ctx->diff_session;
   req->sampler = S.sampler; req->ddim_eta = S.eta; req->cond_free_k = S.k;
+  if (req->struct_size >= sizeof(tts_diff_request)) { req->temperature = S.temperature; req->cond_free = S.cond_free; } // an older caller's struct ends before them
 }
 int diff_session_room(const tts_ctx *ctx) {
   const DiffSession &S = *ctx->diff_session;
@@ -2543,7 +2576,7 @@ int diff_session_open(tts_ctx *ctx, int max_packed_rows, int max_requests) {
   s->attn_f32 = ctx->attn_f32; s->share_uncond = ctx->share_uncond; s->hoist = ctx->hoist_integrator; s->graph = ctx->diff_graph;
   s->pinned = PinnedOptions::of(ctx);
   s->pinned.latency_mode = 0; // the batch path's GroupNorm, always
-  s->sampler = ctx->diff_sampler; s->eta = ctx->ddim_eta; s->k = ctx->cond_free_k;
+  s->sampler = ctx->diff_sampler; s->eta = ctx->ddim_eta; s->k = ctx->cond_free_k; s->temperature = ctx->diff_temperature; s->cond_free = ctx->cond_free;
   // Every request of a session takes the same route through the integrator (one step graph serves them all): hoisted whenever the option is on (the two routes
   // give the same bits). The single call's row threshold (HOIST_MAX_ROWS, or the option's value above 1) becomes the most a request of such a session may take:
   // diff_session_admit refuses a larger one before any device work.
@@ -2569,8 +2602,11 @@ int diff_session_admit(tts_ctx *ctx, const tts_diff_request *rq) {
   for (int i = 0; i < S.max_req && slot < 0; i++) if (!S.slot_busy[i]) slot = i;
   if (slot < 0) return fail(ctx, TTS_ERR_LIMIT, "tts_diff_session_admit: the session holds %d requests", S.max_req);
   const int B = rq->n_cand;
+  const bool grown = rq->struct_size >= sizeof(tts_diff_request); // a descriptor that ends before temperature and cond_free runs under the session's
+  const bool guided = (grown ? rq->cond_free : S.cond_free) != 0;
+  const float temperature = (float)(grown ? rq->temperature : S.temperature);
   if (S.hoisted) { // a hoisted request owns n_steps x packed rows x 2 KB until it is collected: the single call's row cap bounds it, request by request
-    const int cap = S.hoist > 1 ? S.hoist : HOIST_MAX_ROWS, packed = tts_host_diff_packed_rows(rq->rows, B);
+    const int cap = S.hoist > 1 ? S.hoist : HOIST_MAX_ROWS, packed = tts_host_diff_packed_rows_ex(rq->rows, B, guided ? 1 : 0);
     if (packed > cap)
       return fail(ctx, TTS_ERR_LIMIT, "tts_diff_session_admit: the request takes %d packed rows; a session opened with hoist_integrator on admits at most %d per request "
                   "(open the session with hoist_integrator 0 for larger ones)", packed, cap);
@@ -2578,7 +2614,7 @@ int diff_session_admit(tts_ctx *ctx, const tts_diff_request *rq) {
   SessOptions opts(ctx, S);
   std::unique_ptr<DiffReq> r(new DiffReq());
   // the request's voice as a one-row table, every candidate on row 0; the generator's streams are the candidates' indices in the request
-  ReqSpec sp{rq->latents, rq->rows, B, rq->n_steps, rq->sampler, rq->ddim_eta, (float)rq->cond_free_k, rq->voice_latent2048, 1, nullptr, rq->noise, TTS_NOISE_DEVICE,
+  ReqSpec sp{rq->latents, rq->rows, B, rq->n_steps, rq->sampler, rq->ddim_eta, (float)rq->cond_free_k, guided, temperature, rq->voice_latent2048, 1, nullptr, rq->noise, TTS_NOISE_DEVICE,
              nullptr, rq->seed, 0u, S.hoisted ? INT_MAX : 0, false};
   CHECK(prepare_request(ctx, st, *r, sp));
   const Layout &lay = st->sb.lay;
@@ -2586,13 +2622,14 @@ int diff_session_admit(tts_ctx *ctx, const tts_diff_request *rq) {
   r->packed = lay.rows;
   r->cls = Layout::gn_class(lay.max_len());
   // the row buffers: where each of the request's sequences starts in them
-  r->seq_src.resize((size_t)2 * B);
+  const int n_seq = r->n_seq(); // = lay.ns: the request's own layout
+  r->seq_src.resize((size_t)n_seq);
   if (S.hoisted) {
-    for (int s = 0; s < 2 * B; s++) r->seq_src[s] = lay.start[s];
+    for (int s = 0; s < n_seq; s++) r->seq_src[s] = lay.start[s];
   } else { // the integrator runs inside the session's step: its two timestep-independent inputs leave the single call's run state
     const Layout &il = st->share_integ ? st->ilay : st->sb.lay;
     r->src_rows = il.rows;
-    for (int s = 0; s < 2 * B; s++) r->seq_src[s] = st->share_integ ? st->ce_src_host[lay.start[s]] : lay.start[s];
+    for (int s = 0; s < n_seq; s++) r->seq_src[s] = st->share_integ ? st->ce_src_host[lay.start[s]] : lay.start[s];
     TTS_HIP(ctx, r->code_emb.reserve((size_t)il.rows * C * 4));
     TTS_HIP(ctx, hipMemcpyAsync(r->code_emb.p, st->sb.code_emb.p, (size_t)il.rows * C * 4, hipMemcpyDeviceToDevice, ctx->stream));
     if (st->n_integ > 0) {
@@ -2611,7 +2648,7 @@ int diff_session_admit(tts_ctx *ctx, const tts_diff_request *rq) {
 }
 
 // The joint layout of the running requests and the tables the step's kernels read. Requests in the order of admission, grouped by GroupNorm class
-// (Layout::gn_parts); a request's conditioned sequences, then their unconditioned copies.
+// (Layout::gn_parts); a request's conditioned sequences, then (a guided request) their unconditioned copies: guided and unguided requests side by side.
 static int diff_session_rebuild(tts_ctx *ctx, DiffSession &S) {
   DiffState *st = ctx->diff;
   StepBufs &sb = S.sb;
@@ -2622,7 +2659,7 @@ static int diff_session_rebuild(tts_ctx *ctx, DiffSession &S) {
   std::vector<int64_t> xoff;
   std::vector<DiffReq *> owner;
   for (DiffReq *r : live)
-    for (int ls = 0; ls < 2 * r->n_cand; ls++) {
+    for (int ls = 0; ls < r->n_seq(); ls++) {
       const int c = ls % r->n_cand;
       lens.push_back(r->T[c]); seq_req.push_back(r->slot); seq_cand.push_back(c); cls.push_back(r->cls); seq_local.push_back(ls);
       xoff.push_back(r->xoff[c]); owner.push_back(r);
@@ -2637,7 +2674,7 @@ static int diff_session_rebuild(tts_ctx *ctx, DiffSession &S) {
   std::vector<int> partner(ns, -1), row_src(lay.rows, -1);
   for (int s = 0; s < ns; s++) {
     const DiffReq *r = owner[s];
-    if (seq_local[s] < r->n_cand) partner[s] = lay.start[s + r->n_cand]; // the request's sequences are consecutive
+    if (seq_local[s] < r->n_cand) partner[s] = lay.start[r->guided ? s + r->n_cand : s]; // the request's sequences are consecutive; an unguided one names itself
     for (int t = 0; t < lens[s]; t++) row_src[lay.start[s] + t] = r->seq_src[seq_local[s]] + t;
   }
   std::vector<ReqDev> tab((size_t)S.max_req, ReqDev{});

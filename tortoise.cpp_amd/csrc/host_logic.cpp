@@ -1350,6 +1350,8 @@ const char *diff_control_error(int which, double value) {
   case 0: return (value != 0 && value != 1 && value != 3) ? "diff_sampler: 0 (ancestral DDPM), 1 (DDIM) or 3 (DPM-Solver++(2M))" : nullptr;
   case 1: return !(value >= 0 && value <= 1) ? "ddim_eta: a value in [0, 1]" : nullptr;
   case 2: return (!std::isfinite(value) || value < 0 || !std::isfinite((float)value)) ? "cond_free_k: a finite value >= 0" : nullptr;
+  case 3: return (!std::isfinite(value) || value < 0 || !std::isfinite((float)value)) ? "diff_temperature: a finite value >= 0" : nullptr;
+  case 4: return (value != 0 && value != 1) ? "cond_free: 1 (guided) or 0 (unguided: the conditioned sequences only)" : nullptr;
   }
   return "unknown diffusion control";
 }
@@ -1358,11 +1360,14 @@ int diff_packed_rows(const int *frames, int n) {
   for (int s = 0; s < n; s++) r = (r + frames[s] + 1 + 7) & ~7LL;
   return (int)((r + 127) & ~127LL);
 }
-int diff_request_check(const tts_diff_request *req, int max_packed_rows, std::string &why) {
-  char buf[200];
+// The struct's growth rule (tts_ar_request's): the size a header before "temperature" declared, or one that covers every field this library knows.
+bool diff_request_size_ok(uint32_t n) { return n == offsetof(tts_diff_request, temperature) || n >= sizeof(tts_diff_request); }
+int diff_request_check(const tts_diff_request *req, int max_packed_rows, double pinned_temperature, int pinned_cond_free, std::string &why) {
+  char buf[240];
   if (!req) { why = "null request"; return TTS_ERR_ARG; }
-  if (req->struct_size < sizeof(tts_diff_request)) {
-    snprintf(buf, sizeof buf, "struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_diff_request))", req->struct_size, sizeof(tts_diff_request));
+  if (!diff_request_size_ok(req->struct_size)) {
+    snprintf(buf, sizeof buf, "struct_size %u, version 8 declares %zu bytes (%zu before temperature and cond_free were appended; set it to sizeof(tts_diff_request))",
+             req->struct_size, sizeof(tts_diff_request), offsetof(tts_diff_request, temperature));
     why = buf;
     return TTS_ERR_ARG;
   }
@@ -1375,23 +1380,26 @@ int diff_request_check(const tts_diff_request *req, int max_packed_rows, std::st
     n_lat += (size_t)req->rows[c] * TTS_DMODEL;
   }
   if (req->n_steps < 2) { snprintf(buf, sizeof buf, "n_steps %d: at least 2", req->n_steps); why = buf; return TTS_ERR_ARG; }
-  const double v[3] = {(double)req->sampler, req->ddim_eta, req->cond_free_k};
-  for (int k = 0; k < 3; k++)
+  const bool grown = req->struct_size >= sizeof(tts_diff_request); // an older caller's struct ends before the two fields
+  const double v[5] = {(double)req->sampler, req->ddim_eta, req->cond_free_k, grown ? req->temperature : pinned_temperature,
+                       grown ? (double)req->cond_free : (double)pinned_cond_free};
+  for (int k = 0; k < 5; k++)
     if (const char *e = diff_control_error(k, v[k])) { why = e; return TTS_ERR_ARG; }
   for (size_t i = 0; i < n_lat; i++)
     if (!std::isfinite(req->latents[i])) { why = "a latent holds a non-finite value"; return TTS_ERR_ARG; }
   if (req->voice_latent2048)
     for (int i = 0; i < 2 * TTS_DMODEL; i++)
       if (!std::isfinite(req->voice_latent2048[i])) { why = "the voice latent holds a non-finite value"; return TTS_ERR_ARG; }
-  const int need = tts_host_diff_packed_rows(req->rows, req->n_cand);
+  const int need = tts_host_diff_packed_rows_ex(req->rows, req->n_cand, (int)v[4]);
   if (need > max_packed_rows) { snprintf(buf, sizeof buf, "the request takes %d packed rows, %d are free", need, max_packed_rows); why = buf; return TTS_ERR_LIMIT; }
   return TTS_OK;
 }
 } // namespace tts
-extern "C" int tts_host_diff_packed_rows(const int32_t *latent_rows, int n_cand) {
-  if (!latent_rows || n_cand < 1 || n_cand > 4096) return TTS_ERR_ARG;
+extern "C" int tts_host_diff_packed_rows(const int32_t *latent_rows, int n_cand) { return tts_host_diff_packed_rows_ex(latent_rows, n_cand, 1); }
+extern "C" int tts_host_diff_packed_rows_ex(const int32_t *latent_rows, int n_cand, int cond_free) {
+  if (!latent_rows || n_cand < 1 || n_cand > 4096 || (cond_free != 0 && cond_free != 1)) return TTS_ERR_ARG;
   std::vector<int> frames;
-  for (int pass = 0; pass < 2; pass++) // the conditioned sequences, then their unconditioned copies
+  for (int pass = 0; pass < 1 + cond_free; pass++) // the conditioned sequences, then (guided) their unconditioned copies
     for (int c = 0; c < n_cand; c++) {
       if (latent_rows[c] < 1 || latent_rows[c] > 500) return TTS_ERR_ARG;
       frames.push_back(tts_diffusion_frames(latent_rows[c]));
@@ -1401,5 +1409,5 @@ extern "C" int tts_host_diff_packed_rows(const int32_t *latent_rows, int n_cand)
 extern "C" int tts_host_diff_request_check(const tts_diff_request *req, int max_packed_rows) {
   if (max_packed_rows < 1) return TTS_ERR_ARG;
   std::string why;
-  return tts::diff_request_check(req, max_packed_rows, why);
+  return tts::diff_request_check(req, max_packed_rows, 1.0, 1, why);
 }
