@@ -665,7 +665,11 @@ __global__ __launch_bounds__(256, 2) void diff_attn_f32_kernel(const __half *__r
       const float inv = 1.0f / l;
 #pragma unroll
       for (int dt = 0; dt < 4; dt++) {
-        const float v0 = o[i][dt][0] * inv, v1 = o[i][dt][1] * inv, v2 = o[i][dt][2] * inv, v3 = o[i][dt][3] * inv;
+        float v0 = o[i][dt][0] * inv, v1 = o[i][dt][1] * inv, v2 = o[i][dt][2] * inv, v3 = o[i][dt][3] * inv;
+        // the f32 quotient is a value of its own: both halves of the pair must round THE SAME f32 number. Without the empty asm hipcc fuses the product into one of
+        // the two fp16 conversions (v_fma_mixlo_f16 rounds the exact product once), and where the f32 product is a tie between two fp16 values the halves disagree:
+        // hi + lo is one fp16 unit of hi off (tests/test_dattn_kernels_gpu.py::test_split_output_halves_agree_on_an_f32_tie)
+        asm volatile("" : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3));
         const size_t off = (size_t)(r0 + qi) * C + h * 64 + dt * 16 + fq * 4;
         *(uint2 *)(out_hi + off) = pack_half4(v0, v1, v2, v3);
         *(uint2 *)(out_lo + off) = pack_half4(split_lo(v0), split_lo(v1), split_lo(v2), split_lo(v3));
