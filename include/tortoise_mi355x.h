@@ -199,6 +199,39 @@ int tts_load_diffusion_conditioning_encoder(tts_ctx *ctx, const char *path);
 int tts_diffusion_conditioning_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out2048);
 int tts_set_diffusion_conditioning_latent(tts_ctx *ctx, const float *latent2048);
 int tts_voice_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out1024);
+/* A voice from audio clips, on the device (added within version 8). Upstream's load_audio + get_conditioning_latents, restated from memory (upstream's source
+ * was not at hand; INTEGRATION.md says what that means): every clip is resampled to 22 050 Hz with torchaudio.functional.resample's default filter
+ * (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99); the AR side takes a 132 300-sample window of it (zero-padded behind, or cropped from crop_offset,
+ * which is clamped so that the window ends inside the clip), its 80-band log-mel (tts_host_mel_voice80's definition) and tts_voice_latent's encoder; the
+ * diffusion side resamples the 22 050 Hz signal again to 24 000 Hz, takes its first 102 400 samples (zero-padded behind), their un-normalised 100-band log-mel
+ * (tts_host_mel_diffusion100, normalize 0) and tts_diffusion_conditioning_latent's encoder. Resampler, STFT, mel and log run in f32 kernels on the context's
+ * stream; the mels go straight into the encoders' input buffers. The one host read between the upload and the latents is a 4-byte count of non-finite samples.
+ *
+ * tts_voice_audio_opts: plain C and able to grow under tts_ar_request's rule (struct_size = the caller's sizeof, set before tts_voice_audio_opts_init, which
+ *   fills the defaults: no norms, offset 0, full_clips 0). A NULL opts pointer means the defaults. mel_norms80: 80 per-band divisors of the AR side's log-mel
+ *   (upstream's data/mel_norms.pth) or NULL. full_clips 1: no window, every clip is used whole on both sides (more than 512 samples at either rate).
+ * tts_voice_from_audio: audio = the clips' mono samples one after the other, n_samples[c] and sample_rate[c] per clip. out1024 / out2048: either may be NULL,
+ *   that side is then skipped and its encoder need not be loaded. Legal while an AR or a diffusion session is open. All checks run before any device work and a
+ *   refused call changes nothing: TTS_ERR_STATE for an output whose encoder is not loaded; TTS_ERR_ARG for a null pointer, both outputs NULL, n_clips < 1, a
+ *   clip with no sample, a rate < 1, a refused struct_size, a negative crop_offset, a clip of 512 samples or fewer at an encoder's rate under full_clips;
+ *   TTS_ERR_LIMIT for a rate pair whose reduced tap table exceeds 4 Mi entries (22 051 -> 22 050) or a clip above 2^26 samples. A non-finite sample is found
+ *   on the device before an encoder runs: TTS_ERR_ARG, no output is written.
+ * tts_audio_mel: the mel the front-end hands to the encoder for ONE clip, bands = 80 (crop_offset and mel_norms80 apply) or 100 (neither does):
+ *   [bands][frames] into mel_out, which holds cap floats. Returns the frame count; with mel_out NULL only that. Needs no encoder. Errors as above.
+ * tts_read_wav: the inverse of tts_write_wav. RIFF/WAVE with PCM16, PCM24 or float32 samples, any channel count (averaged into mono), unknown chunks skipped.
+ *   Returns the mono sample count and the rate in *sample_rate; with out NULL only those (the size to allocate). TTS_ERR_IO: cannot open, truncated;
+ *   TTS_ERR_FORMAT: not RIFF/WAVE, no fmt chunk before the data, another sample format; TTS_ERR_ARG: cap below the sample count. */
+typedef struct tts_voice_audio_opts {
+  uint32_t struct_size;     /* sizeof(tts_voice_audio_opts): set by the caller before tts_voice_audio_opts_init */
+  const float *mel_norms80; /* NULL: the AR side's log-mel is not divided */
+  int64_t crop_offset;      /* first sample (at 22 050 Hz) of the AR side's window when the clip is longer than it */
+  int32_t full_clips;       /* 1: no window on either side */
+} tts_voice_audio_opts;
+int tts_voice_audio_opts_init(tts_voice_audio_opts *opts);
+int tts_voice_from_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                         float *out1024, float *out2048);
+int tts_audio_mel(tts_ctx *ctx, const float *audio, int64_t n, int sample_rate, int bands, const tts_voice_audio_opts *opts, float *mel_out, int64_t cap);
+int64_t tts_read_wav(const char *path, float *out, int64_t cap, int32_t *sample_rate);
 int tts_ar_layers(const tts_ctx *ctx);
 int tts_diffusion_layers(const tts_ctx *ctx);
 

@@ -12,7 +12,11 @@ data/mel_norms.pth saved as 80 floats (.npy or raw f32): without it the 80-band 
 Clip length follows upstream's get_conditioning_latents: the AR encoder sees exactly 132 300 samples at 22.05 kHz (format_conditioning: zero-padded,
 or cropped — upstream crops at a random offset; here at --crop-offset, default 0), the diffusion encoder exactly 102 400 samples at 24 kHz
 (pad_or_truncate: zero-padded or the first 102 400) and the UN-normalised log-mel (wav_to_univnet_mel(..., do_normalization=False));
---full-clips feeds whole clips instead."""
+--full-clips feeds whole clips instead.
+--frontend host (default: the path above) | device: tts_voice_from_audio does everything on the GPU, from the samples to both latents. The two differ on purpose:
+the device front-end is upstream's chain (torchaudio.functional.resample's sinc_interp_hann filter; the 24 kHz signal is resampled from the 22.05 kHz one, as
+upstream's models were conditioned), this script's host path resamples the source directly to each rate with scipy's resample_poly filter. The latents of the two
+front-ends are therefore close, not equal; tools/voice_audio_bench.py times both."""
 import argparse
 import os
 import struct
@@ -77,6 +81,7 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--crop-offset", type=int, default=0, help="first sample (22.05 kHz) of the AR encoder's 132 300-sample window in clips longer than that")
     ap.add_argument("--full-clips", action="store_true", help="do not pad / crop the clips to upstream's 132 300 / 102 400 samples")
+    ap.add_argument("--frontend", choices=("host", "device"), default="host", help="host: scipy resampler + tts_host_mel_*; device: tts_voice_from_audio (upstream's resampling chain)")
     a = ap.parse_args()
     import tortoise_cpp_amd_loader
     pkg = tortoise_cpp_amd_loader.load()
@@ -85,6 +90,16 @@ def main():
         norms = np.load(a.mel_norms) if a.mel_norms.endswith(".npy") else np.fromfile(a.mel_norms, np.float32)
         norms = np.asarray(norms, np.float32).reshape(80)
     clips = [read_wav(p) for p in a.clips]
+    if a.frontend == "device":
+        e = pkg.Engine(a.device)
+        e.load_voice_encoder(a.conditioning_model)
+        e.load_diffusion_conditioning_encoder(a.diffusion_conditioning_model)
+        v, d = e.voice_from_audio([x for x, _ in clips], [r for _, r in clips], mel_norms=norms, crop_offset=a.crop_offset, full_clips=a.full_clips)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        v.tofile(a.out + ".bin")
+        d.tofile(a.out + ".diffusion.bin")
+        print("%s.bin (1024 f32), %s.diffusion.bin (2048 f32) from %d clip(s), device front-end" % (a.out, a.out, len(clips)))
+        return
     fit = (lambda x, n, off=0: x) if a.full_clips else pad_or_crop
     mel80 = [pkg.host_mel_voice80(fit(resample(x, r, 22050), 132300, a.crop_offset), norms) for x, r in clips]
     mel100 = [pkg.host_mel_diffusion100(fit(resample(x, r, 24000), 102400), normalize=False) for x, r in clips]

@@ -50,6 +50,11 @@ class DiffRequest(C.Structure):
                 ("temperature", C.c_double), ("cond_free", C.c_int32)]  # appended within version 8 at offset 72 (the struct's size before them)
 
 
+class VoiceAudioOpts(C.Structure):
+    """tts_voice_audio_opts: the AR side's per-band norms, its crop offset, and full_clips (tts_voice_from_audio, tts_audio_mel)."""
+    _fields_ = [("struct_size", C.c_uint32), ("mel_norms80", C.c_void_p), ("crop_offset", C.c_int64), ("full_clips", C.c_int32)]
+
+
 # the keys of ar_session_admit(controls=...) and the descriptor fields they set
 AR_CONTROL_FIELDS = {"temperature": "temperature", "top_k": "top_k", "top_p": "top_p", "penalty": "repetition_penalty", "scope": "penalty_scope",
                      "typical_mass": "typical_mass"}
@@ -127,7 +132,9 @@ def lib():
         "tts_vocoder_samples": (ci, [ci]),
         "tts_vocoder": (ci, [vp, _f32p, _i32p, ci, vp, ci, _f32p]),
         "tts_vocoder_chunk": (ci, [vp, _f32p, ci, _f32p, ci, ci, _f32p, C.POINTER(ci)]),
-        "tts_write_wav": (ci, [C.c_char_p, _f32p, C.c_int64, ci]),
+        "tts_write_wav": (ci, [C.c_char_p, _f32p, C.c_int64, ci]), "tts_read_wav": (C.c_int64, [C.c_char_p, vp, C.c_int64, vp]),
+        "tts_voice_audio_opts_init": (ci, [C.POINTER(VoiceAudioOpts)]),
+        "tts_voice_from_audio": (ci, [vp, vp, vp, vp, ci, vp, vp, vp]), "tts_audio_mel": (ci, [vp, vp, C.c_int64, ci, ci, vp, vp, C.c_int64]),
         "tts_host_schedule": (ci, [ci, _i32p] + [_f32p] * 7), "tts_host_schedule_ddim": (ci, [ci, C.c_double, _f64p, _f64p, _f32p, _f32p, _f32p]),
         "tts_host_schedule_dpmpp": (ci, [ci, _f32p, _f32p, _f32p, _i32p]), "tts_host_timestep_embedding": (None, [ci, _f32p]),
         "tts_host_rel_bucket": (ci, [ci, ci]), "tts_host_pad_codes": (ci, [_i32p, ci, _i32p]), "tts_host_trimmed_rows": (ci, [_i32p]),
@@ -487,6 +494,43 @@ class Engine:
         mel = np.ascontiguousarray(np.concatenate([np.asarray(m, np.float32).reshape(-1) for m in mels]))
         out = np.empty(1024, np.float32)
         self._ck(self.L.tts_voice_latent(self.h, mel, frames, len(mels), out))
+        return out
+
+    # ---- a voice from audio clips, on the device (not in the reference) ----
+    def _audio_opts(self, mel_norms, crop_offset, full_clips, struct_size=None):
+        o = VoiceAudioOpts()
+        o.struct_size = C.sizeof(VoiceAudioOpts)
+        if self.L.tts_voice_audio_opts_init(C.byref(o)):
+            raise TtsError("tts_voice_audio_opts_init failed")
+        mn = None if mel_norms is None else np.ascontiguousarray(mel_norms, np.float32).reshape(80)
+        o.mel_norms80, o.crop_offset, o.full_clips = _ptr(mn), int(crop_offset), int(full_clips)
+        if struct_size is not None:
+            o.struct_size = struct_size
+        return o, mn  # mn: kept alive by the caller for the call's duration
+
+    def voice_from_audio(self, clips, rates, mel_norms=None, crop_offset=0, full_clips=False, want=(True, True)):
+        """clips: list of mono float32 sample arrays, rates: their sample rates (one int for all, or one per clip). Returns (voice latent [1024], diffusion
+        conditioning latent [2048]); want = (AR side, diffusion side): a side that is not wanted is None and its encoder need not be loaded."""
+        rates = [int(rates)] * len(clips) if np.isscalar(rates) else [int(r) for r in rates]
+        if len(rates) != len(clips):
+            raise TtsError("%d rates for %d clips" % (len(rates), len(clips)))
+        n = np.array([len(c) for c in clips], np.int64)
+        a = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1) for c in clips])) if len(clips) else np.zeros(1, np.float32)
+        r = np.array(rates, np.int32)
+        o, keep = self._audio_opts(mel_norms, crop_offset, full_clips)
+        out1 = np.empty(1024, np.float32) if want[0] else None
+        out2 = np.empty(2048, np.float32) if want[1] else None
+        self._ck(self.L.tts_voice_from_audio(self.h, _ptr(a), _ptr(n), _ptr(r), len(clips), C.addressof(o), _ptr(out1), _ptr(out2)))
+        return out1, out2
+
+    def audio_mel(self, audio, rate, bands, mel_norms=None, crop_offset=0, full_clips=False):
+        """[bands, frames] log-mel the front-end hands to the encoder for one clip: bands 80 (the input of voice_latent) or 100 (of
+        diffusion_conditioning_latent)."""
+        a = np.ascontiguousarray(audio, np.float32).reshape(-1)
+        o, keep = self._audio_opts(mel_norms, crop_offset, full_clips)
+        frames = self._ck(self.L.tts_audio_mel(self.h, _ptr(a), len(a), int(rate), int(bands), C.addressof(o), None, 0))
+        out = np.empty((int(bands), frames), np.float32)
+        self._ck(self.L.tts_audio_mel(self.h, _ptr(a), len(a), int(rate), int(bands), C.addressof(o), _ptr(out), out.size))
         return out
 
     def load_diffusion_conditioning_encoder(self, path):
@@ -946,6 +990,19 @@ def host_fp8_e4m3(values):
     L = lib()
     v = np.ascontiguousarray(values, np.float32).reshape(-1)
     return np.array([L.tts_host_fp8_e4m3(float(x)) for x in v], np.uint8).reshape(np.shape(values))
+
+
+def read_wav(path):
+    """(mono float32 samples, sample rate) of a RIFF/WAVE file with PCM16, PCM24 or float32 samples (tts_read_wav); TtsError carries the status."""
+    rate = C.c_int32(0)
+    n = lib().tts_read_wav(path.encode(), None, 0, C.byref(rate))
+    if n < 0:
+        raise TtsError("tts_read_wav(%s) failed (status %d)" % (path, n))
+    out = np.empty(n, np.float32)
+    n = lib().tts_read_wav(path.encode(), _ptr(out), n, C.byref(rate))
+    if n < 0:
+        raise TtsError("tts_read_wav(%s) failed (status %d)" % (path, n))
+    return out[:n], int(rate.value)
 
 
 def write_wav(path, samples, rate=24000):

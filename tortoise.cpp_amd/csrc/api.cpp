@@ -121,6 +121,7 @@ void tts_destroy(tts_ctx *c) {
   if (c->venc) voice_enc_free(c->venc);
   if (c->dcond) diff_cond_enc_free(c->dcond);
   if (c->hifigan) hifigan_free(c->hifigan);
+  if (c->afe) afe_free(c->afe);
   if (c->fp16_counts) (void)hipFree(c->fp16_counts);
   delete c->tok;
   for (auto &kv : c->prof)
@@ -305,6 +306,21 @@ int tts_load_voice_encoder(tts_ctx *c, const char *path) { NEED_CTX(c); return g
 int tts_voice_latent(tts_ctx *c, const float *mel, const int32_t *frames, int n_clips, float *out1024) {
   NEED_CTX(c);
   return guarded(c, [&] { return voice_enc_latent(c, mel, frames, n_clips, out1024); });
+}
+int tts_voice_audio_opts_init(tts_voice_audio_opts *o) {
+  if (!o || o->struct_size < sizeof(tts_voice_audio_opts)) return TTS_ERR_ARG;
+  o->mel_norms80 = nullptr; o->crop_offset = 0; o->full_clips = 0;
+  return TTS_OK;
+}
+// Legal while a session is open: the front-end and the two encoders own their buffers and touch no AR or diffusion state.
+int tts_voice_from_audio(tts_ctx *c, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                         float *out1024, float *out2048) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return afe_voice_from_audio(c, audio, n_samples, sample_rate, n_clips, opts, out1024, out2048); });
+}
+int tts_audio_mel(tts_ctx *c, const float *audio, int64_t n, int sample_rate, int bands, const tts_voice_audio_opts *opts, float *mel_out, int64_t cap) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return afe_audio_mel(c, audio, n, sample_rate, bands, opts, mel_out, cap); });
 }
 int tts_load_clvp(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return clvp_load(c, path); }); }
 int tts_clvp_score(tts_ctx *c, const int32_t *text_ids, int n_text, const int32_t *codes, const int32_t *code_len, int n_candidates,

@@ -60,6 +60,15 @@
 //   run without --stream writes. --timing 1 prints when the first samples arrived ("[timing] first audio ..."), from the start of the process and from the start of the
 //   autoregressive stage. Usage errors (exit 1, before a model is loaded): --stream with --decoder diffusion, --clvp, --split-text, several --voice, --candidates > 1
 //   or --devices > 1; --stream-stride < 1.
+// --voice-clips a.wav[,b.wav...] --conditioning-model F --diffusion-conditioning-model G [--mel-norms F] [--save-voice PREFIX]: a voice made from audio clips on
+//   the device (tts_voice_from_audio: RIFF WAV with PCM16, PCM24 or float32 samples at any rate; upstream's resampling, windows and mels). Every occurrence of
+//   --voice-clips is ONE voice made from its comma-separated clips; the voices are numbered in command-line order together with the --voice occurrences and work
+//   with the "<index>|" turns and with --decoder hifigan like them. F / G: the two encoder files (tools/convert_weights.py --conditioning-encoder /
+//   --diffusion-conditioning-encoder); with --decoder hifigan G is optional (without it no diffusion latent is made). --mel-norms: 80 raw f32, upstream's
+//   data/mel_norms.pth. --save-voice PREFIX (none, or one per --voice-clips, in order) writes PREFIX.bin and, when G is given, PREFIX.diffusion.bin: the files
+//   --voice and --diffusion-latent read. With the diffusion decoder a clip voice brings its own diffusion latent, so every --voice beside it needs its
+//   --diffusion-latent. Usage errors (exit 1, before a model is loaded): a missing encoder file, --dry-run 1, --devices > 1 or --exchange rccl, a wrong count of
+//   --save-voice or --diffusion-latent.
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -124,6 +133,8 @@ int main(int argc, char **argv) {
   bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
+  std::vector<std::string> voiceClips, saveVoice;              // parallel to voicePaths: the clip list of a --voice-clips voice ("" for a --voice file); --save-voice prefixes
+  std::string condModel, dcondModel, melNormsPath;
   bool stream = false;
   int stream_stride = 16;
   StreamSink sink;
@@ -135,7 +146,12 @@ int main(int argc, char **argv) {
   for (int i = 1; i < argc - 1; ++i) {
     std::string a(argv[i]);
     if (a == "--stream-stride") stream_stride = std::stoi(argv[i + 1]);
-    else if (a == "--voice") { voicePath = argv[i + 1]; voicePaths.push_back(voicePath); }
+    else if (a == "--voice") { voicePath = argv[i + 1]; voicePaths.push_back(voicePath); voiceClips.push_back(""); }
+    else if (a == "--voice-clips") { voicePath.clear(); voicePaths.push_back(""); voiceClips.push_back(argv[i + 1]); }
+    else if (a == "--conditioning-model") condModel = argv[i + 1];
+    else if (a == "--diffusion-conditioning-model") dcondModel = argv[i + 1];
+    else if (a == "--mel-norms") melNormsPath = argv[i + 1];
+    else if (a == "--save-voice") saveVoice.push_back(argv[i + 1]);
     else if (a == "--message") message = argv[i + 1];
     else if (a == "--output") outputPath = argv[i + 1];
     else if (a == "--seed") { seed = std::stoi(argv[i + 1]); have_seed = true; }
@@ -214,11 +230,37 @@ int main(int argc, char **argv) {
   // several voices (usage errors before any model is loaded / any worker is started)
   const int n_voices = std::max<int>(1, (int)voicePaths.size());
   const bool multi_voice = n_voices > 1;
-  if (!diffLatentPaths.empty() && (int)diffLatentPaths.size() != n_voices) {
+  int n_clip_voices = 0;
+  for (const std::string &c : voiceClips) n_clip_voices += !c.empty();
+  const int n_file_voices = (int)voicePaths.size() - n_clip_voices;
+  if (n_clip_voices == 0 && !diffLatentPaths.empty() && (int)diffLatentPaths.size() != n_voices) {
     fprintf(stderr, "%d --diffusion-latent for %d --voice: give none (every speaker uses the model's own latent) or one per voice, in the same order\n",
             (int)diffLatentPaths.size(), n_voices);
     return 1;
   }
+  if (n_clip_voices > 0) { // usage errors of --voice-clips
+    if (condModel.empty()) { fprintf(stderr, "--voice-clips needs --conditioning-model <file> (the voice-conditioning encoder)\n"); return 1; }
+    if (!use_hifigan && dcondModel.empty()) { fprintf(stderr, "--voice-clips with the diffusion decoder needs --diffusion-conditioning-model <file>\n"); return 1; }
+    if (dry) { fprintf(stderr, "--voice-clips runs on the device: it cannot be combined with --dry-run 1\n"); return 1; }
+    if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--voice-clips cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
+    if (!saveVoice.empty() && (int)saveVoice.size() != n_clip_voices) {
+      fprintf(stderr, "%d --save-voice for %d --voice-clips: give none or one per --voice-clips, in the same order\n", (int)saveVoice.size(), n_clip_voices);
+      return 1;
+    }
+    if (!use_hifigan && (int)diffLatentPaths.size() != n_file_voices) {
+      fprintf(stderr, "%d --diffusion-latent for %d --voice beside --voice-clips: a clip voice brings its own diffusion latent, so every --voice needs one\n",
+              (int)diffLatentPaths.size(), n_file_voices);
+      return 1;
+    }
+  } else if (!saveVoice.empty() || !condModel.empty() || !dcondModel.empty() || !melNormsPath.empty()) {
+    fprintf(stderr, "--save-voice, --conditioning-model, --diffusion-conditioning-model and --mel-norms belong to --voice-clips, which is absent\n");
+    return 1;
+  }
+  // the --diffusion-latent file of every voice ("" for a clip voice, or when none is given): the k-th occurrence belongs to the k-th --voice
+  std::vector<std::string> diffLatentOf(n_voices);
+  for (int v = 0, k = 0; v < (int)voicePaths.size(); v++)
+    if (voiceClips[v].empty() && k < (int)diffLatentPaths.size()) diffLatentOf[v] = diffLatentPaths[k++];
+  const bool clip_latents = n_clip_voices > 0 && !dcondModel.empty(); // the clip voices bring diffusion latents
   if (multi_voice && (devices > 1 || exchange == "rccl" || shard >= 0)) {
     fprintf(stderr, "several --voice cannot be combined with --devices > 1 or --exchange rccl (the conditioning broadcast carries one voice; one process runs all turns)\n");
     return 1;
@@ -366,6 +408,55 @@ int main(int argc, char **argv) {
     tts_set_option(ctx, "rng_shard_offset", (double)(shard * candidates));
     tts_set_option(ctx, "rng_shard_total", (double)total_candidates);
   }
+  // --voice-clips: every clip voice's two latents, made on the device before any other model is loaded
+  std::vector<std::vector<float>> clip1024(n_voices), clip2048(n_voices);
+  if (n_clip_voices > 0) {
+    if (tts_load_voice_encoder(ctx, condModel.c_str())) return die(ctx, "--conditioning-model");
+    if (clip_latents && tts_load_diffusion_conditioning_encoder(ctx, dcondModel.c_str())) return die(ctx, "--diffusion-conditioning-model");
+    std::vector<float> norms;
+    if (!melNormsPath.empty()) {
+      norms.resize(80);
+      std::ifstream f(melNormsPath, std::ios::binary);
+      if (!f || !f.read((char *)norms.data(), 80 * sizeof(float))) { std::cerr << "Error: Unable to read 80 floats from " << melNormsPath << std::endl; return 1; }
+    }
+    tts_voice_audio_opts vo;
+    vo.struct_size = sizeof vo;
+    tts_voice_audio_opts_init(&vo);
+    vo.mel_norms80 = norms.empty() ? nullptr : norms.data();
+    for (int v = 0, k = 0; v < n_voices; v++) {
+      if (voiceClips[v].empty()) continue;
+      std::vector<float> samples;
+      std::vector<int64_t> lens;
+      std::vector<int32_t> rates;
+      for (size_t p = 0; p <= voiceClips[v].size();) {
+        const size_t q = std::min(voiceClips[v].find(',', p), voiceClips[v].size());
+        const std::string path = voiceClips[v].substr(p, q - p);
+        p = q + 1;
+        if (path.empty()) continue;
+        int32_t rate = 0;
+        const int64_t cnt = tts_read_wav(path.c_str(), nullptr, 0, &rate);
+        if (cnt < 1) { fprintf(stderr, "--voice-clips %s: %s\n", path.c_str(), cnt == TTS_ERR_IO ? "cannot open, or truncated" : cnt == 0 ? "no samples" : "not a PCM16 / PCM24 / float32 RIFF WAV file"); return 1; }
+        samples.resize(samples.size() + (size_t)cnt);
+        if (tts_read_wav(path.c_str(), samples.data() + samples.size() - (size_t)cnt, cnt, &rate) != cnt) { fprintf(stderr, "--voice-clips %s: read error\n", path.c_str()); return 1; }
+        lens.push_back(cnt); rates.push_back(rate);
+      }
+      if (lens.empty()) { fprintf(stderr, "--voice-clips: an empty clip list\n"); return 1; }
+      clip1024[v].resize(1024);
+      if (clip_latents) clip2048[v].resize(2048);
+      if (tts_voice_from_audio(ctx, samples.data(), lens.data(), rates.data(), (int)lens.size(), &vo, clip1024[v].data(), clip_latents ? clip2048[v].data() : nullptr))
+        return die(ctx, "--voice-clips");
+      if (!saveVoice.empty()) {
+        std::ofstream f1(saveVoice[k] + ".bin", std::ios::binary);
+        if (!f1 || !f1.write((const char *)clip1024[v].data(), 1024 * sizeof(float))) { std::cerr << "Error: Unable to write " << saveVoice[k] << ".bin" << std::endl; return 1; }
+        if (clip_latents) {
+          std::ofstream f2(saveVoice[k] + ".diffusion.bin", std::ios::binary);
+          if (!f2 || !f2.write((const char *)clip2048[v].data(), 2048 * sizeof(float))) { std::cerr << "Error: Unable to write " << saveVoice[k] << ".diffusion.bin" << std::endl; return 1; }
+        }
+      }
+      k++;
+    }
+    mark("voice from clips");
+  }
   if (tts_tokenizer_load(ctx, (modelsDir + "/tokenizer.json").c_str()) < 0) return die(ctx, "tokenizer");
   std::vector<int32_t> tokens(4096);
   int n = tts_tokenize(ctx, message.c_str(), tokens.data(), (int)tokens.size());
@@ -403,7 +494,9 @@ int main(int argc, char **argv) {
   const bool chunked = n_chunks > 1 || multi_voice; // the prompt-group path (several voices: also for a single chunk)
 
   std::vector<float> voice(1024);
-  {
+  if (voicePath.empty()) { // the last voice named is a clip voice (several voices: `voices` below is what is read)
+    if (!multi_voice) voice = clip1024[0];
+  } else {
     std::ifstream f(voicePath, std::ios::binary);
     if (!f) { std::cerr << "Error: Unable to open file " << voicePath << std::endl; return 1; }
     f.read((char *)voice.data(), 1024 * sizeof(float));
@@ -413,17 +506,19 @@ int main(int argc, char **argv) {
   if (multi_voice) {
     voices.resize((size_t)n_voices * 1024);
     for (int v = 0; v < n_voices; v++) {
+      if (!voiceClips[v].empty()) { std::copy(clip1024[v].begin(), clip1024[v].end(), voices.begin() + (size_t)v * 1024); continue; }
       std::ifstream f(voicePaths[v], std::ios::binary);
       if (!f || !f.read((char *)(voices.data() + (size_t)v * 1024), 1024 * sizeof(float))) {
         std::cerr << "Error: Unable to read 1024 floats from " << voicePaths[v] << std::endl;
         return 1;
       }
     }
-    diff_latents.resize(diffLatentPaths.size() * 2048);
-    for (size_t v = 0; v < diffLatentPaths.size(); v++) {
-      std::ifstream f(diffLatentPaths[v], std::ios::binary);
-      if (!f || !f.read((char *)(diff_latents.data() + v * 2048), 2048 * sizeof(float))) {
-        std::cerr << "Error: Unable to read 2048 floats from " << diffLatentPaths[v] << std::endl;
+    if (!use_hifigan && (!diffLatentPaths.empty() || clip_latents)) diff_latents.resize((size_t)n_voices * 2048);
+    for (int v = 0; v < n_voices && !diff_latents.empty(); v++) {
+      if (!voiceClips[v].empty()) { std::copy(clip2048[v].begin(), clip2048[v].end(), diff_latents.begin() + (size_t)v * 2048); continue; }
+      std::ifstream f(diffLatentOf[v], std::ios::binary);
+      if (!f || !f.read((char *)(diff_latents.data() + (size_t)v * 2048), 2048 * sizeof(float))) {
+        std::cerr << "Error: Unable to read 2048 floats from " << diffLatentOf[v] << std::endl;
         return 1;
       }
     }
@@ -629,7 +724,9 @@ int main(int argc, char **argv) {
     mark("hifigan");
   } else {
   mark("wait for the diffusion + vocoder loads");
-  if (!diffLatentPath.empty() && !multi_voice) {
+  if (!multi_voice && clip_latents) { // the one voice is a clip voice: its own diffusion latent
+    if (tts_set_diffusion_conditioning_latent(ctx, clip2048[0].data())) return die(ctx, "diffusion_conditioning_latent");
+  } else if (!diffLatentPath.empty() && !multi_voice) {
     std::vector<float> dl(2048);
     std::ifstream f(diffLatentPath, std::ios::binary);
     if (!f || !f.read((char *)dl.data(), 2048 * sizeof(float))) { std::cerr << "Error: Unable to read 2048 floats from " << diffLatentPath << std::endl; return 1; }

@@ -91,6 +91,7 @@ struct ClvpState;
 struct VoiceEncState;
 struct DiffCondEncState;
 struct HifiganState;
+struct AfeState;
 struct Tokenizer;
 struct SamplerPool;
 void sampler_pool_free(SamplerPool *p);
@@ -134,6 +135,7 @@ struct tts_ctx {
   tts::VoiceEncState *venc = nullptr; // voice-conditioning encoder (extras.hip; not in the reference)
   tts::DiffCondEncState *dcond = nullptr; // diffusion conditioning encoder (extras.hip; not in the reference)
   tts::HifiganState *hifigan = nullptr; // HiFi-GAN decoder: latents -> waveform (hifigan.hip; not in the reference: upstream's api_fast.py path)
+  tts::AfeState *afe = nullptr; // audio front-end: its tables and buffers, made at the first tts_voice_from_audio / tts_audio_mel (audio_frontend.hip)
   tts::Tokenizer *tok = nullptr;
   tts::ArSession *session = nullptr;        // non-null while a session is open: tts_ar_begin*, tts_autoregressive* and tts_hifigan_stream then return TTS_ERR_STATE
   tts::DiffSession *diff_session = nullptr; // non-null while a diffusion session is open: tts_diffusion, tts_diffusion_multi_voice, tts_diffusion_forward and tts_load_diffusion then return TTS_ERR_STATE
@@ -543,6 +545,25 @@ int ar_drv_audio(tts_ctx *ctx, int request, float *out, int cap_samples, int32_t
 int voice_enc_load(tts_ctx *ctx, const char *path);
 void voice_enc_free(VoiceEncState *);
 int voice_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out1024);
+// The two halves of voice_enc_latent (and of diff_cond_enc_latent): *_begin checks the frame counts, sizes the buffers, uploads the row layout and returns the
+// device mel buffer [80 | 100][frames[c]] per clip, one after the other; *_run encodes what that buffer holds. The caller fills the buffer in between, on ctx->stream.
+int voice_enc_begin(tts_ctx *ctx, const int32_t *frames, int n_clips, float **d_mel);
+int voice_enc_run(tts_ctx *ctx, float *out1024);
+int diff_cond_enc_begin(tts_ctx *ctx, const int32_t *frames, int n_clips, float **d_mel);
+int diff_cond_enc_run(tts_ctx *ctx, float *out2048);
+// ---- audio front-end (audio_frontend.hip; its tables: host_logic.cpp) ----
+constexpr int64_t AFE_MAX_TABLE = 4 << 20;        // entries of a resampler tap table
+constexpr int AFE_WIN80 = 132300, AFE_WIN100 = 102400; // upstream's conditioning windows: 6 s at 22.05 kHz, 4.27 s at 24 kHz
+struct AfeResampleGeom { int o, n, width, taps; };
+int afe_resample_geometry(int orig_rate, int new_rate, AfeResampleGeom *g); // TTS_OK, TTS_ERR_ARG, or TTS_ERR_LIMIT for a table above AFE_MAX_TABLE
+void afe_resample_table(const AfeResampleGeom &g, float *tab);              // [n][taps]
+int64_t afe_resample_len(const AfeResampleGeom &g, int64_t n);              // ceil(n_new len / n_orig)
+void afe_fft_tables(float *tw_re, float *tw_im, float *win);                // [512], [512], [1024]
+int afe_filterbank(int bands, std::vector<int> &span, std::vector<float> &w);
+void afe_free(AfeState *);
+int afe_voice_from_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                         float *out1024, float *out2048);
+int afe_audio_mel(tts_ctx *ctx, const float *audio, int64_t n, int sample_rate, int bands, const tts_voice_audio_opts *opts, float *mel_out, int64_t cap);
 int hifigan_load(tts_ctx *ctx, const char *path);
 void hifigan_free(HifiganState *);
 int hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices, const int32_t *voice_of_candidate,

@@ -422,6 +422,10 @@ struct VoiceEncState {
   std::vector<VencBlock> blk;
   std::vector<void *> owned;
   DevBuf x, y16, qkv16, att16, a16, meta, mel;
+  std::vector<int> meta_h;          // the layout voice_enc_begin made, for voice_enc_run: [n_clips] first rows | [n_clips] frames
+  std::vector<long long> moff_h;
+  int n_clips = 0, rows = 0, maxlen = 0;
+  long long mel_floats = 0;
   ~VoiceEncState() { for (void *p : owned) (void)hipFree(p); }
 };
 void voice_enc_free(VoiceEncState *s) { delete s; }
@@ -491,14 +495,18 @@ int voice_enc_load(tts_ctx *ctx, const char *path) {
   return TTS_OK;
 }
 
-int voice_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out1024) {
+// voice_enc_latent in two halves (common.h): the layout and the buffers, then (once the mel buffer is filled: an upload here, the audio front-end's kernels in
+// tts_voice_from_audio) the encoder. The launch sequence of tts_voice_latent is what it was.
+int voice_enc_begin(tts_ctx *ctx, const int32_t *frames, int n_clips, float **d_mel) {
   VoiceEncState *st = ctx->venc;
   if (!st) return fail(ctx, TTS_ERR_STATE, "tts_load_voice_encoder not called");
-  if (!mel || !frames || n_clips < 1 || !out1024) return fail(ctx, TTS_ERR_ARG, "tts_voice_latent: bad arguments");
+  if (!frames || n_clips < 1 || !d_mel) return fail(ctx, TTS_ERR_ARG, "tts_voice_latent: bad arguments");
   constexpr int D = 1024;
   int rows = 0, maxlen = 0;
-  std::vector<int> meta(2 * n_clips);
-  std::vector<long long> moff(n_clips);
+  std::vector<int> &meta = st->meta_h;
+  meta.assign(2 * n_clips, 0);
+  std::vector<long long> &moff = st->moff_h; // both outlive this call: the copies below are asynchronous
+  moff.assign(n_clips, 0);
   long long off = 0;
   for (int s = 0; s < n_clips; s++) {
     if (frames[s] < 1 || frames[s] > 16384) return fail(ctx, TTS_ERR_ARG, "clip %d: %d mel frames (1 .. 16384 expected)", s, frames[s]);
@@ -513,11 +521,22 @@ int voice_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int 
   TTS_HIP(ctx, st->a16.reserve((size_t)M * 128 * 2));
   TTS_HIP(ctx, st->meta.reserve((size_t)2 * n_clips * 4 + (size_t)n_clips * 8 + 16));
   TTS_HIP(ctx, st->mel.reserve((size_t)off * 4));
-  int *d_start = st->meta.as<int>(), *d_len = d_start + n_clips;
+  int *d_start = st->meta.as<int>();
   long long *d_moff = (long long *)(st->meta.as<char>() + (((size_t)2 * n_clips * 4 + 7) & ~(size_t)7));
   TTS_HIP(ctx, hipMemcpyAsync(d_start, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   TTS_HIP(ctx, hipMemcpyAsync(d_moff, moff.data(), moff.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  TTS_HIP(ctx, hipMemcpyAsync(st->mel.p, mel, (size_t)off * 4, hipMemcpyHostToDevice, ctx->stream));
+  st->n_clips = n_clips; st->rows = rows; st->maxlen = maxlen; st->mel_floats = off;
+  *d_mel = st->mel.as<float>();
+  return TTS_OK;
+}
+
+int voice_enc_run(tts_ctx *ctx, float *out1024) {
+  VoiceEncState *st = ctx->venc;
+  constexpr int D = 1024;
+  const int n_clips = st->n_clips, rows = st->rows, maxlen = st->maxlen, M = (rows + 127) / 128 * 128;
+  const std::vector<int> &meta = st->meta_h;
+  int *d_start = st->meta.as<int>(), *d_len = d_start + n_clips;
+  long long *d_moff = (long long *)(st->meta.as<char>() + (((size_t)2 * n_clips * 4 + 7) & ~(size_t)7));
   TTS_HIP(ctx, hipMemsetAsync(st->a16.p, 0, (size_t)M * 128 * 2, ctx->stream)); // rows past the last frame: finite, never read back
   TTS_HIP(ctx, hipMemsetAsync(st->y16.p, 0, (size_t)M * D * 2, ctx->stream));
   TTS_HIP(ctx, hipMemsetAsync(st->att16.p, 0, (size_t)M * D * 2, ctx->stream));
@@ -551,6 +570,16 @@ int voice_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int 
   return TTS_OK;
 }
 
+int voice_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out1024) {
+  if (!ctx->venc) return fail(ctx, TTS_ERR_STATE, "tts_load_voice_encoder not called");
+  if (!mel || !frames || n_clips < 1 || !out1024) return fail(ctx, TTS_ERR_ARG, "tts_voice_latent: bad arguments");
+  float *d_mel = nullptr;
+  const int rc = voice_enc_begin(ctx, frames, n_clips, &d_mel);
+  if (rc) return rc;
+  TTS_HIP(ctx, hipMemcpyAsync(d_mel, mel, (size_t)ctx->venc->mel_floats * 4, hipMemcpyHostToDevice, ctx->stream));
+  return voice_enc_run(ctx, out1024);
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------
 // diffusion conditioning encoder (the other half of SURVEY 8 f3): upstream DiffusionTts.get_conditioning. 100-band mel of the reference clips
 // -> the 2048 floats the reference reads as the weight `diffusion_conditioning_latent` of ggml-diffusion-model.bin (main.cpp:1557-1560).
@@ -567,6 +596,10 @@ struct DiffCondEncState {
   std::vector<DcondBlock> blk;
   std::vector<void *> owned;
   DevBuf h1, x, y16, qkv16, att16, a16, meta, mel;
+  int n_clips = 0, r1 = 0, r2 = 0, max0 = 0; // the layout diff_cond_enc_begin made, for diff_cond_enc_run
+  std::vector<int> meta_h;
+  std::vector<long long> moff_h;
+  long long mel_floats = 0;
   ~DiffCondEncState() { for (void *p : owned) (void)hipFree(p); }
 };
 void diff_cond_enc_free(DiffCondEncState *s) { delete s; }
@@ -650,14 +683,17 @@ int diff_cond_enc_load(tts_ctx *ctx, const char *path) {
   return TTS_OK;
 }
 
-int diff_cond_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out2048) {
+// diff_cond_enc_latent in two halves, as voice_enc_begin / voice_enc_run
+int diff_cond_enc_begin(tts_ctx *ctx, const int32_t *frames, int n_clips, float **d_mel) {
   DiffCondEncState *st = ctx->dcond;
   if (!st) return fail(ctx, TTS_ERR_STATE, "tts_load_diffusion_conditioning_encoder not called");
-  if (!mel || !frames || n_clips < 1 || !out2048) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_conditioning_latent: bad arguments");
+  if (!frames || n_clips < 1 || !d_mel) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_conditioning_latent: bad arguments");
   constexpr int D = 2048;
   // three row layouts: the mel frames (T), after the first convolution (T1 = (T - 1) / 2 + 1), after the second (T2)
-  std::vector<int> meta(6 * n_clips);
-  std::vector<long long> moff(n_clips);
+  std::vector<int> &meta = st->meta_h; // both outlive this call: the copies below are asynchronous
+  std::vector<long long> &moff = st->moff_h;
+  meta.assign(6 * n_clips, 0);
+  moff.assign(n_clips, 0);
   int r1 = 0, r2 = 0, max0 = 0;
   long long off = 0;
   for (int s = 0; s < n_clips; s++) {
@@ -669,7 +705,6 @@ int diff_cond_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, 
     moff[s] = off;
     off += (long long)100 * frames[s]; r1 += T1; r2 += T2; max0 = std::max(max0, frames[s]);
   }
-  const int max1 = (max0 - 1) / 2 + 1, max2 = (max1 - 1) / 2 + 1;
   const int M1 = (r1 + 127) / 128 * 128, M2 = (r2 + 127) / 128 * 128;
   TTS_HIP(ctx, st->h1.reserve((size_t)M1 * 1024 * 4));
   TTS_HIP(ctx, st->x.reserve((size_t)M2 * D * 4));
@@ -683,7 +718,19 @@ int diff_cond_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, 
   long long *d_moff = (long long *)(st->meta.as<char>() + (((size_t)6 * n_clips * 4 + 7) & ~(size_t)7));
   TTS_HIP(ctx, hipMemcpyAsync(dm, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   TTS_HIP(ctx, hipMemcpyAsync(d_moff, moff.data(), moff.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-  TTS_HIP(ctx, hipMemcpyAsync(st->mel.p, mel, (size_t)off * 4, hipMemcpyHostToDevice, ctx->stream));
+  st->n_clips = n_clips; st->r1 = r1; st->r2 = r2; st->max0 = max0; st->mel_floats = off;
+  *d_mel = st->mel.as<float>();
+  return TTS_OK;
+}
+
+int diff_cond_enc_run(tts_ctx *ctx, float *out2048) {
+  DiffCondEncState *st = ctx->dcond;
+  constexpr int D = 2048;
+  const int n_clips = st->n_clips, r1 = st->r1, r2 = st->r2, max0 = st->max0;
+  const int max1 = (max0 - 1) / 2 + 1, max2 = (max1 - 1) / 2 + 1;
+  const int M1 = (r1 + 127) / 128 * 128, M2 = (r2 + 127) / 128 * 128;
+  int *dm = st->meta.as<int>();
+  long long *d_moff = (long long *)(st->meta.as<char>() + (((size_t)6 * n_clips * 4 + 7) & ~(size_t)7));
   float *h1 = st->h1.as<float>(), *x = st->x.as<float>();
   __half *a16 = st->a16.as<__half>(), *y = st->y16.as<__half>(), *qkv = st->qkv16.as<__half>(), *att = st->att16.as<__half>();
   auto gemm = [&](const __half *A, int K, const __half *W, int M, int N, const float *bias) {
@@ -718,6 +765,16 @@ int diff_cond_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, 
     out2048[c] = (float)(a / r2);
   }
   return TTS_OK;
+}
+
+int diff_cond_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *out2048) {
+  if (!ctx->dcond) return fail(ctx, TTS_ERR_STATE, "tts_load_diffusion_conditioning_encoder not called");
+  if (!mel || !frames || n_clips < 1 || !out2048) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_conditioning_latent: bad arguments");
+  float *d_mel = nullptr;
+  const int rc = diff_cond_enc_begin(ctx, frames, n_clips, &d_mel);
+  if (rc) return rc;
+  TTS_HIP(ctx, hipMemcpyAsync(d_mel, mel, (size_t)ctx->dcond->mel_floats * 4, hipMemcpyHostToDevice, ctx->stream));
+  return diff_cond_enc_run(ctx, out2048);
 }
 
 } // namespace tts

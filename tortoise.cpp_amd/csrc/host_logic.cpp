@@ -1411,3 +1411,109 @@ extern "C" int tts_host_diff_request_check(const tts_diff_request *req, int max_
   std::string why;
   return tts::diff_request_check(req, max_packed_rows, 1.0, 1, why);
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// Audio front-end on the device (csrc/audio_frontend.hip): the tables its kernels read, each evaluated in double here and rounded ONCE to float, and the
+// WAV reader. The mel side restates the functions above (mel_filterbank, the periodic Hann window) as tables; the resampler is upstream's
+// torchaudio.functional.resample with its defaults (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99).
+// ------------------------------------------------------------------------------------------------------------------------------
+namespace tts {
+static int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
+// o = orig / gcd, n = new / gcd, width = ceil(6 o / base), base = min(o, n) 0.99; the table is [n][2 width + o]
+int afe_resample_geometry(int orig_rate, int new_rate, AfeResampleGeom *g) {
+  if (orig_rate < 1 || new_rate < 1 || !g) return TTS_ERR_ARG;
+  const int64_t d = gcd64(orig_rate, new_rate);
+  g->o = (int)(orig_rate / d); g->n = (int)(new_rate / d);
+  const double base = std::min(g->o, g->n) * 0.99;
+  g->width = (int)std::ceil(6.0 * g->o / base);
+  g->taps = 2 * g->width + g->o;
+  return (int64_t)g->n * g->taps > AFE_MAX_TABLE ? TTS_ERR_LIMIT : TTS_OK;
+}
+// tab[p][k] = sinc(pi t) cos^2(pi t / 12) base / o with t = clamp((-p / n + (k - width) / o) base, -6, 6)
+void afe_resample_table(const AfeResampleGeom &g, float *tab) {
+  const double base = std::min(g.o, g.n) * 0.99, scale = base / g.o;
+  for (int p = 0; p < g.n; p++)
+    for (int k = 0; k < g.taps; k++) {
+      double t = (-(double)p / g.n + (double)(k - g.width) / g.o) * base;
+      t = std::max(-6.0, std::min(6.0, t));
+      const double win = std::cos(t * M_PI / 6.0 / 2.0), a = t * M_PI;
+      tab[(size_t)p * g.taps + k] = (float)((a == 0.0 ? 1.0 : std::sin(a) / a) * win * win * scale);
+    }
+}
+int64_t afe_resample_len(const AfeResampleGeom &g, int64_t n) { return (g.n * n + g.o - 1) / g.o; }
+// tw[k] = (cos, -sin)(2 pi k / 1024), k < 512; win[i] = periodic Hann
+void afe_fft_tables(float *tw_re, float *tw_im, float *win) {
+  for (int k = 0; k < 512; k++) { tw_re[k] = (float)std::cos(-2.0 * M_PI * k / 1024.0); tw_im[k] = (float)std::sin(-2.0 * M_PI * k / 1024.0); }
+  for (int i = 0; i < 1024; i++) win[i] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / 1024.0));
+}
+// The filterbank of `bands` (80: HTK scale, 22 050 Hz, 0 .. 8 000 Hz; 100: Slaney scale, 24 000 Hz, 0 .. 12 000 Hz), Slaney-normalised, as its non-zero span per
+// band: span[b] = {first bin, bin count, offset into w}. A band whose triangle holds no bin has count 0.
+int afe_filterbank(int bands, std::vector<int> &span, std::vector<float> &w) {
+  if (bands != 80 && bands != 100) return TTS_ERR_ARG;
+  const std::vector<double> fb = bands == 80 ? mel_filterbank(80, 1024, 22050.0, 0.0, 8000.0, true) : mel_filterbank(100, 1024, 24000.0, 0.0, 12000.0, false);
+  span.assign((size_t)3 * bands, 0);
+  w.clear();
+  for (int b = 0; b < bands; b++) {
+    int lo = 513, hi = -1;
+    for (int k = 0; k < 513; k++)
+      if (fb[(size_t)b * 513 + k] != 0.0) { lo = std::min(lo, k); hi = k; }
+    span[3 * b] = hi < 0 ? 0 : lo; span[3 * b + 1] = hi < 0 ? 0 : hi - lo + 1; span[3 * b + 2] = (int)w.size();
+    for (int k = lo; k <= hi; k++) w.push_back((float)fb[(size_t)b * 513 + k]);
+  }
+  return TTS_OK;
+}
+} // namespace tts
+
+// The inverse of tts_write_wav: RIFF/WAVE with PCM16, PCM24 or float32 samples (format 1 or 3, or WAVE_FORMAT_EXTENSIBLE with one of those as its sub-format),
+// any channel count (averaged), unknown chunks skipped (a chunk of odd size is followed by a pad byte).
+extern "C" int64_t tts_read_wav(const char *path, float *out, int64_t cap, int32_t *sample_rate) {
+  if (!path) return TTS_ERR_ARG;
+  FILE *f = fopen(path, "rb");
+  if (!f) return TTS_ERR_IO;
+  struct Closer { FILE *f; ~Closer() { fclose(f); } } closer{f};
+  unsigned char h[12];
+  if (fread(h, 1, 12, f) != 12) return TTS_ERR_IO;
+  if (memcmp(h, "RIFF", 4) || memcmp(h + 8, "WAVE", 4)) return TTS_ERR_FORMAT;
+  int fmt = 0, channels = 0, bits = 0, rate = 0;
+  auto u16 = [](const unsigned char *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); };
+  auto u32 = [](const unsigned char *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); };
+  for (;;) {
+    unsigned char ch[8];
+    if (fread(ch, 1, 8, f) != 8) return fmt ? TTS_ERR_IO : TTS_ERR_FORMAT; // the file ends before its data chunk
+    const uint32_t size = u32(ch + 4);
+    if (!memcmp(ch, "fmt ", 4)) {
+      unsigned char b[40] = {};
+      if (size < 16) return TTS_ERR_FORMAT;
+      const size_t take = std::min<size_t>(size, sizeof b);
+      if (fread(b, 1, take, f) != take) return TTS_ERR_IO;
+      fmt = (int)u16(b); channels = (int)u16(b + 2); rate = (int)u32(b + 4); bits = (int)u16(b + 14);
+      if (fmt == 0xFFFE && take >= 26) fmt = (int)u16(b + 24); // WAVE_FORMAT_EXTENSIBLE: the first two bytes of the sub-format GUID
+      if (fseek(f, (long)(size - take + (size & 1)), SEEK_CUR)) return TTS_ERR_IO;
+    } else if (!memcmp(ch, "data", 4)) {
+      if (!fmt) return TTS_ERR_FORMAT;
+      if (channels < 1 || rate < 1 || !((fmt == 1 && (bits == 16 || bits == 24)) || (fmt == 3 && bits == 32))) return TTS_ERR_FORMAT;
+      const int bps = bits / 8;
+      const int64_t frames = (int64_t)(size / ((uint32_t)bps * channels));
+      if (sample_rate) *sample_rate = rate;
+      if (!out) { // the count the file can deliver: a data chunk longer than the file is a truncated file
+        const long at = ftell(f);
+        if (at < 0 || fseek(f, 0, SEEK_END)) return TTS_ERR_IO;
+        return ftell(f) - at < frames * bps * channels ? TTS_ERR_IO : frames;
+      }
+      if (cap < frames) return TTS_ERR_ARG;
+      std::vector<unsigned char> row((size_t)bps * channels);
+      for (int64_t i = 0; i < frames; i++) {
+        if (fread(row.data(), 1, row.size(), f) != row.size()) return TTS_ERR_IO;
+        double a = 0;
+        for (int c = 0; c < channels; c++) {
+          const unsigned char *p = row.data() + (size_t)c * bps;
+          if (fmt == 3) { float v; memcpy(&v, p, 4); a += v; }
+          else if (bits == 16) a += (int16_t)u16(p) / 32768.0;
+          else a += ((int32_t)((uint32_t)p[0] << 8 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 24) >> 8) / 8388608.0; // sign-extended from bit 23
+        }
+        out[i] = (float)(a / channels);
+      }
+      return frames;
+    } else if (fseek(f, (long)(size + (size & 1)), SEEK_CUR)) return TTS_ERR_IO;
+  }
+}
