@@ -380,6 +380,38 @@ int tts_split_turns(tts_ctx *ctx, const char *message, int n_voices, int max_ids
 int tts_clvp_score(tts_ctx *ctx, const int32_t *text_ids, int n_text, const int32_t *codes, const int32_t *code_len,
                    int n_candidates, int code_stride, float *scores_out);
 
+/* CVVP, the second re-ranker of upstream tortoise-tts (tortoise/models/cvvp.py): do these codes sound like this speaker? Added within version 8. The model
+ * is RESTATED FROM MEMORY (upstream's source was not at hand, as for the audio front-end) and held against two independent float64 restatements
+ * (tests/cvvp_ref.py): parity is unpinned against upstream, pinned between independent restatements. csrc/cvvp.hip states the architecture.
+ * File: the reference's container format, tensor names of the upstream state dict (tortoise.cpp_amd/synth_weights.py: write_cvvp; tools/convert_weights.py
+ *   --cvvp). The model dimension comes from the file: 512 (upstream) or 1024, heads = dim / 64, a feed-forward width that is a multiple of 128, any depth >= 1;
+ *   anything else, or a file that is not a CVVP file (a CLVP file is one of those), is TTS_ERR_FORMAT.
+ * tts_cvvp_latent_dim: floats per latent (512 for upstream's file); < 0 before the load.
+ * tts_cvvp_rows: rows the conditioning side's two strided convolutions make of mel_frames frames, T1 = (T - 1) / 2 + 1, R = (T1 - 1) / 2 + 1 (517 -> 259 -> 130).
+ *   Pure: needs no context and no GPU. TTS_ERR_ARG below 1 frame.
+ * tts_cvvp_voice: one L2-normalised conditioning latent per clip. mel80 = the clips' [80][frames[c]] log-mels one after the other: the AR side's mel with
+ *   mel_norms applied (tts_audio_mel with bands 80), which is what upstream's format_conditioning hands to CVVP. latents_out [n_clips][latent dim]. A server
+ *   computes this once per voice and reuses it for every request of that voice.
+ * tts_cvvp_voice_audio: the same from samples (arguments as tts_voice_from_audio): the audio front-end's AR-side mel (the window, crop_offset and mel_norms80
+ *   of opts) is written straight into the stem's input buffer, no host copy of the mel. Bit-identical to tts_cvvp_voice of tts_audio_mel's output.
+ * tts_cvvp_score: codes / code_len / code_stride exactly as tts_clvp_score; voice_latents = [n_clips][latent dim] from the calls above.
+ *   scores_out[c] = mean over the clips of <voice latent, speech latent of candidate c> x exp(temperature) (upstream accumulates one CVVP evaluation per
+ *   conditioning clip and divides by the clip count). Upstream's blend with CLVP: clvp * (1 - cvvp_amount) + cvvp * cvvp_amount, the caller's to make.
+ * All legal while an AR or a diffusion session is open. Every check runs before any device work and a refused call changes nothing: TTS_ERR_STATE before
+ *   tts_load_cvvp; TTS_ERR_ARG for a null pointer, n_clips < 1, a clip with no frame, a code outside 0 .. 8191, code_len outside 1 .. code_stride, a non-finite
+ *   mel or latent value, full_clips 1 in opts (upstream scores the windowed clip); TTS_ERR_LIMIT above TTS_CVVP_MAX_FRAMES mel frames in a clip (the frame
+ *   count the other two conditioning encoders accept for the same attention kernel, launched over a grid of (clips, heads, rows / 256)) or above
+ *   4096 clips. tts_cvvp_voice_audio finds a non-finite SAMPLE on the device, as tts_voice_from_audio does: TTS_ERR_ARG, no output is written. */
+#define TTS_CVVP_MAX_FRAMES 16384
+int tts_load_cvvp(tts_ctx *ctx, const char *path);
+int tts_cvvp_latent_dim(const tts_ctx *ctx);
+int tts_cvvp_rows(int mel_frames);
+int tts_cvvp_voice(tts_ctx *ctx, const float *mel80, const int32_t *frames, int n_clips, float *latents_out);
+int tts_cvvp_voice_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                         float *latents_out);
+int tts_cvvp_score(tts_ctx *ctx, const float *voice_latents, int n_clips, const int32_t *codes, const int32_t *code_len, int n_candidates, int code_stride,
+                   float *scores_out);
+
 /* ---- diffusion stage ----------------------------------------------------------------------- */
 /* T = L*4*24000/22050 (main.cpp:5616-5617) */
 int tts_diffusion_frames(int latent_rows);

@@ -220,6 +220,46 @@ def convert_clvp(sd, path):
     return depth // 2
 
 
+def strip_wrap(sd):
+    """upstream's checkpoint wrapper puts a `.wrap.` component into the names of wrapped modules: the same tensors under the plain names"""
+    out = {}
+    for k, v in sd.items():
+        k2 = k.replace(".wrap.", ".")
+        if k2 in out:
+            raise SystemExit("convert_cvvp: '%s' appears with and without .wrap." % k2)
+        out[k2] = v
+    return out
+
+
+def convert_cvvp(sd, path):
+    """ggml-cvvp-model.bin for tts_load_cvvp: upstream tortoise-tts CVVP (cvvp.pth), tensors under their state-dict names (a `.wrap.` path component is
+    stripped; temperature 0-dim -> [1]; the rotary inv_freq buffers are kept if present, the loader recomputes them). A missing, unknown or mis-shaped tensor is
+    an error: the names and shapes are restated from memory (--list-expected cvvp), so a real checkpoint that differs must be seen, not mis-read."""
+    sd = {k: _np(v) for k, v in strip_wrap(sd).items()}
+    depth = 0
+    while "speech_transformer.transformer.attn_layers.layers.%d.0.g" % (2 * depth) in sd:
+        depth += 1
+    if depth == 0:
+        raise SystemExit("convert_cvvp: no speech_transformer layers (not the CVVP of tortoise-tts?)")
+    dim = sd["speech_emb.emb.weight"].shape[1] if "speech_emb.emb.weight" in sd else 512
+    exp = expected_tensors("cvvp", depth=depth, dim=dim)
+    for k in sorted(sd):
+        if k not in exp and not k.endswith("rotary_pos_emb.inv_freq"):
+            raise SystemExit("convert_cvvp: unexpected tensor '%s' (not the CVVP of tortoise-tts?)" % k)
+    w = GgmlWriter(path)
+    for k, shape in exp.items():
+        if k not in sd:
+            raise SystemExit("convert_cvvp: tensor '%s' is missing" % k)
+        if tuple(sd[k].shape) != tuple(shape):
+            raise SystemExit("convert_cvvp: tensor '%s' has shape %s, expected %s" % (k, list(sd[k].shape), list(shape)))
+        w.add(k, sd[k].reshape(container_shape("cvvp", k, shape)))
+    for k in sorted(sd):
+        if k.endswith("rotary_pos_emb.inv_freq"):
+            w.add(k, sd[k])
+    w.close()
+    return depth
+
+
 # ---- what each checkpoint is expected to hold (--list-expected) ---------------------------------------------------------------------
 # name -> PyTorch shape as tortoise-tts stores it, for the upstream architecture (or the one given). Written from the loaders' contracts
 # (main.cpp:682-792, 1244-1536, 1808-1923; csrc/extras.hip for the three containers the reference does not have), NOT from a checkpoint:
@@ -298,6 +338,25 @@ def expected_tensors(kind, **arch):
                 out[f + "1.net.0.proj.weight"] = (2 * ff, dim); out[f + "1.net.0.proj.bias"] = (2 * ff,)
                 out[f + "1.net.3.weight"] = (dim, ff); out[f + "1.net.3.bias"] = (dim,)
             out[enc + ".transformer.norm.weight"] = (dim,); out[enc + ".transformer.norm.bias"] = (dim,)
+    elif kind == "cvvp":  # cvvp.pth (names and shapes restated from memory: csrc/cvvp.hip), in write_cvvp's order
+        dim = arch.get("dim", 512)
+        ff, half = dim * arch.get("ff_mult", 1), dim // 2
+        out.update({"temperature": (), "cond_emb.0.weight": (half, 80, 5), "cond_emb.0.bias": (half,), "cond_emb.1.weight": (dim, half, 3), "cond_emb.1.bias": (dim,),
+                    "speech_emb.emb.weight": (8192, dim), "to_conditioning_latent.weight": (dim, dim), "to_speech_latent.weight": (dim, dim)})
+        for enc in ("conditioning_transformer", "speech_transformer"):
+            for i in range(arch.get("depth", 8)):
+                a, f = "%s.transformer.attn_layers.layers.%d." % (enc, 2 * i), "%s.transformer.attn_layers.layers.%d." % (enc, 2 * i + 1)
+                out[a + "0.g"] = (dim,)
+                for nm in ("to_q", "to_k", "to_v"):
+                    out[a + "1.%s.weight" % nm] = (dim, dim)
+                out[a + "1.to_out.weight"] = (dim, dim); out[a + "1.to_out.bias"] = (dim,)
+                out[f + "0.g"] = (dim,)
+                out[f + "1.net.0.proj.weight"] = (2 * ff, dim); out[f + "1.net.0.proj.bias"] = (2 * ff,)
+                out[f + "1.net.3.weight"] = (dim, ff); out[f + "1.net.3.bias"] = (dim,)
+            out[enc + ".transformer.norm.weight"] = (dim,); out[enc + ".transformer.norm.bias"] = (dim,)
+            out[enc + ".pre_combiner.0.weight"] = (dim, dim, 1); out[enc + ".pre_combiner.0.bias"] = (dim,)
+            attn(enc + ".pre_combiner.1", dim, rel=False)
+            out[enc + ".pre_combiner.2.weight"] = (dim, dim, 1); out[enc + ".pre_combiner.2.bias"] = (dim,)
     elif kind == "conditioning-encoder":  # autoregressive.pth: conditioning_encoder.*
         out["conditioning_encoder.init.weight"] = (D, 80, 1); out["conditioning_encoder.init.bias"] = (D,)
         for i in range(arch.get("blocks", 6)):
@@ -312,7 +371,7 @@ def expected_tensors(kind, **arch):
     return out
 
 
-EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder")
+EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp")
 
 
 def container_shape(kind, name, shape):
@@ -324,7 +383,7 @@ def container_shape(kind, name, shape):
         return (int(np.prod(shape)),)
     if kind == "vocoder" and name == "conv_post.1.weight":
         return shape[-2:]
-    if kind == "clvp" and name == "temperature":
+    if kind in ("clvp", "cvvp") and name == "temperature":
         return (1,)
     return tuple(shape)
 
@@ -376,6 +435,7 @@ def main():
     ap.add_argument("--diffusion-conditioning-encoder", help="diffusion_decoder.pth -> ggml-diffusion-conditioning-model.bin (its contextual_embedder.* tensors: "
                                                               "100-band mel -> the diffusion conditioning latent, tts_load_diffusion_conditioning_encoder; not in the reference)")
     ap.add_argument("--clvp", help="clvp2.pth of upstream tortoise-tts -> ggml-clvp-model.bin (candidate re-ranking, tts_load_clvp; not in the reference)")
+    ap.add_argument("--cvvp", help="cvvp.pth of upstream tortoise-tts -> ggml-cvvp-model.bin (candidate re-ranking against the voice clips, tts_load_cvvp; not in the reference)")
     ap.add_argument("--out")
     ap.add_argument("--list-expected", nargs="*", metavar="KIND", help="print every tensor name / shape the converter looks for per checkpoint kind (%s; "
                                                                         "default: all, upstream architecture) and exit" % ", ".join(EXPECTED_KINDS))
@@ -429,6 +489,8 @@ def main():
     if a.clvp:
         checked("clvp", load(a.clvp), a.clvp)
         print("ggml-clvp-model.bin: %d encoder layers" % convert_clvp(load(a.clvp), os.path.join(a.out, "ggml-clvp-model.bin")))
+    if a.cvvp:
+        print("ggml-cvvp-model.bin: %d encoder layers per side" % convert_cvvp(load(a.cvvp), os.path.join(a.out, "ggml-cvvp-model.bin")))
     if a.vocoder:
         checked("vocoder", load(a.vocoder), a.vocoder)
         print("ggml-vocoder-model.bin: %d res stacks" % convert_vocoder(load(a.vocoder), os.path.join(a.out, "ggml-vocoder-model.bin")))

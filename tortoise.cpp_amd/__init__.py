@@ -83,6 +83,9 @@ def lib():
         "tts_load_diffusion_conditioning_encoder": (ci, [vp, C.c_char_p]), "tts_diffusion_conditioning_latent": (ci, [vp, _f32p, _i32p, ci, _f32p]),
         "tts_set_diffusion_conditioning_latent": (ci, [vp, _f32p]),
         "tts_load_voice_encoder": (ci, [vp, C.c_char_p]), "tts_voice_latent": (ci, [vp, _f32p, _i32p, ci, _f32p]),
+        "tts_load_cvvp": (ci, [vp, C.c_char_p]), "tts_cvvp_latent_dim": (ci, [vp]), "tts_cvvp_rows": (ci, [ci]),
+        "tts_cvvp_voice": (ci, [vp, vp, vp, ci, vp]), "tts_cvvp_voice_audio": (ci, [vp, vp, vp, vp, ci, vp, vp]),
+        "tts_cvvp_score": (ci, [vp, vp, ci, vp, vp, ci, ci, vp]),
         "tts_clvp_score": (ci, [vp, _i32p, ci, _i32p, _i32p, ci, ci, _f32p]), "tts_ar_layers": (ci, [vp]), "tts_diffusion_layers": (ci, [vp]),
         "tts_seed": (None, [vp, C.c_uint32]), "tts_rng_load_state": (ci, [vp, C.c_char_p]), "tts_rng_save_state": (ci, [vp, C.c_char_p]),
         "tts_rng_uniform": (cf, [vp]), "tts_rng_normal": (None, [vp, _f32p, C.c_int64]),
@@ -160,6 +163,18 @@ def header_symbols():
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def blend_scores(clvp, cvvp, cvvp_amount):
+    """clvp() * (1 - cvvp_amount) + cvvp() * cvvp_amount in float32 (upstream tortoise-tts api.py); a side whose weight is 0 is not called."""
+    a = float(cvvp_amount)
+    if not 0.0 <= a <= 1.0:
+        raise TtsError("cvvp_amount %r: 0 .. 1" % (cvvp_amount,))
+    if a == 0.0:
+        return np.asarray(clvp(), np.float32)
+    if a == 1.0:
+        return np.asarray(cvvp(), np.float32)
+    return (np.asarray(clvp(), np.float32) * np.float32(1.0 - a) + np.asarray(cvvp(), np.float32) * np.float32(a)).astype(np.float32)
 
 
 class Engine:
@@ -561,6 +576,61 @@ class Engine:
         out = np.empty(len(codes_list), np.float32)
         self._ck(self.L.tts_clvp_score(self.h, np.ascontiguousarray(text_ids, np.int32), len(text_ids), codes.reshape(-1), lens, len(codes_list), stride, out))
         return out
+
+    # ---- CVVP: the candidates' codes against the voice clips (not in the reference) ----
+    def load_cvvp(self, path):
+        self._ck(self.L.tts_load_cvvp(self.h, path.encode()))
+
+    @property
+    def cvvp_latent_dim(self):
+        n = self.L.tts_cvvp_latent_dim(self.h)
+        if n < 0:
+            raise TtsError("tts_load_cvvp not called (status %d)" % n)
+        return n
+
+    @staticmethod
+    def cvvp_rows(mel_frames):
+        """rows the CVVP stem's two strided convolutions make of mel_frames frames (pure: no context, no GPU)"""
+        return lib().tts_cvvp_rows(int(mel_frames))
+
+    def cvvp_voice(self, mels):
+        """mels: list of [80, T_c] log-mels of the conditioning clips (audio_mel(clip, rate, 80, mel_norms)). Returns one normalised conditioning latent per
+        clip [n_clips, latent dim]: computed once per voice, reused for every cvvp_score of that voice."""
+        frames = np.array([np.shape(m)[1] for m in mels], np.int32)
+        mel = np.ascontiguousarray(np.concatenate([np.asarray(m, np.float32).reshape(-1) for m in mels])) if len(mels) else np.zeros(1, np.float32)
+        out = np.empty((len(mels), self.cvvp_latent_dim), np.float32)
+        self._ck(self.L.tts_cvvp_voice(self.h, _ptr(mel), _ptr(frames), len(mels), _ptr(out)))
+        return out
+
+    def cvvp_voice_audio(self, clips, rates, mel_norms=None, crop_offset=0, full_clips=False):
+        """the same from samples: clips and rates as voice_from_audio; the mel never leaves the device"""
+        rates = [int(rates)] * len(clips) if np.isscalar(rates) else [int(r) for r in rates]
+        if len(rates) != len(clips):
+            raise TtsError("%d rates for %d clips" % (len(rates), len(clips)))
+        n = np.array([len(c) for c in clips], np.int64)
+        a = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1) for c in clips])) if len(clips) else np.zeros(1, np.float32)
+        r = np.array(rates, np.int32)
+        o, keep = self._audio_opts(mel_norms, crop_offset, full_clips)
+        out = np.empty((len(clips), self.cvvp_latent_dim), np.float32)
+        self._ck(self.L.tts_cvvp_voice_audio(self.h, _ptr(a), _ptr(n), _ptr(r), len(clips), C.addressof(o), _ptr(out)))
+        return out
+
+    def cvvp_score(self, voice_latents, codes_list):
+        """voice_latents [n_clips, latent dim] from cvvp_voice / cvvp_voice_audio; codes_list as clvp_score. Returns scores [n_candidates]: the mean over the clips."""
+        lat = np.ascontiguousarray(voice_latents, np.float32).reshape(-1, self.cvvp_latent_dim)
+        lens = np.array([len(c) for c in codes_list], np.int32)
+        stride = max(int(lens.max()), 1) if len(lens) else 1
+        codes = np.zeros((len(codes_list), stride), np.int32)
+        for i, c in enumerate(codes_list):
+            codes[i, :len(c)] = c
+        out = np.empty(len(codes_list), np.float32)
+        self._ck(self.L.tts_cvvp_score(self.h, _ptr(lat), len(lat), _ptr(codes), _ptr(lens), len(codes_list), stride, _ptr(out)))
+        return out
+
+    def rerank(self, text_ids, codes_list, voice_latents=None, cvvp_amount=0.0):
+        """Upstream's blend of the two re-rankers, clvp * (1 - cvvp_amount) + cvvp * cvvp_amount; the caller keeps the arg-max. The side whose weight is 0 is not
+        evaluated (and its model need not be loaded)."""
+        return blend_scores(lambda: self.clvp_score(text_ids, codes_list), lambda: self.cvvp_score(voice_latents, codes_list), cvvp_amount)
 
     # ---- HiFi-GAN decoder (not in the reference): latents + speaker latent -> 24 kHz audio ----
     def load_hifigan(self, path):

@@ -118,6 +118,7 @@ void tts_destroy(tts_ctx *c) {
   if (c->diff) diff_free(c->diff);
   if (c->voc) voc_free(c->voc);
   if (c->clvp) clvp_free(c->clvp);
+  if (c->cvvp) cvvp_free(c->cvvp);
   if (c->venc) voice_enc_free(c->venc);
   if (c->dcond) diff_cond_enc_free(c->dcond);
   if (c->hifigan) hifigan_free(c->hifigan);
@@ -247,7 +248,7 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     // hipExtStreamCreateWithCUMask on gfx950: bit i = XCD i % 8, CU slot i / 8 (tools/cu_mask_probe.hip); an XCD with no bit set is
     // unrestricted, so every XCD keeps at least one CU. Only before any model is loaded / graph captured on the old stream.
     if (c->device < 0) return fail(c, TTS_ERR_HIP, "host-only context: no stream");
-    if (c->ar || c->diff || c->voc || c->clvp || c->venc || c->dcond || c->hifigan) return fail(c, TTS_ERR_STATE, "stream_cus must be set before the models are loaded");
+    if (c->ar || c->diff || c->voc || c->clvp || c->cvvp || c->venc || c->dcond || c->hifigan) return fail(c, TTS_ERR_STATE, "stream_cus must be set before the models are loaded");
     (void)hipSetDevice(c->device);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return fail(c, TTS_ERR_HIP, "hipGetDeviceProperties failed");
@@ -327,6 +328,28 @@ int tts_clvp_score(tts_ctx *c, const int32_t *text_ids, int n_text, const int32_
                    int code_stride, float *scores_out) {
   NEED_CTX(c);
   return guarded(c, [&] { return clvp_score(c, text_ids, n_text, codes, code_len, n_candidates, code_stride, scores_out); });
+}
+// CVVP: the second re-ranker (cvvp.hip). Legal while a session is open, as tts_voice_from_audio is: it owns its buffers and touches no AR or diffusion state.
+int tts_load_cvvp(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return cvvp_load(c, path); }); }
+int tts_cvvp_latent_dim(const tts_ctx *c) { return c ? cvvp_latent_dim(c) : TTS_ERR_ARG; }
+int tts_cvvp_rows(int mel_frames) { // the two strided convolutions of the stem: k 5 / stride 2 / padding 2, then k 3 / stride 2 / padding 1
+  if (mel_frames < 1) return TTS_ERR_ARG;
+  const int t1 = (mel_frames - 1) / 2 + 1;
+  return (t1 - 1) / 2 + 1;
+}
+int tts_cvvp_voice(tts_ctx *c, const float *mel80, const int32_t *frames, int n_clips, float *latents_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return cvvp_voice(c, mel80, frames, n_clips, latents_out); });
+}
+int tts_cvvp_voice_audio(tts_ctx *c, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                         float *latents_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return afe_cvvp_voice_audio(c, audio, n_samples, sample_rate, n_clips, opts, latents_out); });
+}
+int tts_cvvp_score(tts_ctx *c, const float *voice_latents, int n_clips, const int32_t *codes, const int32_t *code_len, int n_candidates, int code_stride,
+                   float *scores_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return cvvp_score(c, voice_latents, n_clips, codes, code_len, n_candidates, code_stride, scores_out); });
 }
 int tts_load_hifigan(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return hifigan_load(c, path); }); }
 int tts_hifigan_samples(int latent_rows) { return 256 * tts_diffusion_frames(latent_rows); }

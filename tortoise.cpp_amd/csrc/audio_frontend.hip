@@ -323,6 +323,23 @@ int afe_voice_from_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samp
   return TTS_OK;
 }
 
+// tts_cvvp_voice_audio: the AR side's mel (the window, crop_offset, mel_norms80) written straight into the CVVP stem's input buffer; no host copy of the mel
+int afe_cvvp_voice_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                         float *latents_out) {
+  const char *fn = "tts_cvvp_voice_audio";
+  if (!audio || !n_samples || !sample_rate || !latents_out) return fail(ctx, TTS_ERR_ARG, "%s: bad arguments", fn);
+  if (!ctx->cvvp) return fail(ctx, TTS_ERR_STATE, "tts_load_cvvp not called");
+  AfePlan pl;
+  int rc = afe_plan(ctx, fn, n_samples, sample_rate, n_clips, opts, true, false, pl);
+  if (rc) return rc;
+  if (opts && opts->full_clips) return fail(ctx, TTS_ERR_ARG, "%s: full_clips 1: CVVP scores the windowed clip, as upstream does; whole clips are not supported", fn);
+  if ((rc = afe_init(ctx))) return rc;
+  float *d80 = nullptr;
+  if ((rc = cvvp_voice_begin(ctx, pl.frames80.data(), n_clips, &d80))) return rc;
+  if ((rc = afe_front(ctx, fn, audio, pl, opts, d80, nullptr))) return rc;
+  return cvvp_voice_run(ctx, latents_out);
+}
+
 int afe_audio_mel(tts_ctx *ctx, const float *audio, int64_t n, int sample_rate, int bands, const tts_voice_audio_opts *opts, float *mel_out, int64_t cap) {
   const char *fn = "tts_audio_mel";
   if (!audio || (bands != 80 && bands != 100)) return fail(ctx, TTS_ERR_ARG, "%s: bad arguments (bands: 80 or 100)", fn);

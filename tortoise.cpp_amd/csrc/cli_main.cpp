@@ -69,6 +69,13 @@
 //   --voice and --diffusion-latent read. With the diffusion decoder a clip voice brings its own diffusion latent, so every --voice beside it needs its
 //   --diffusion-latent. Usage errors (exit 1, before a model is loaded): a missing encoder file, --dry-run 1, --devices > 1 or --exchange rccl, a wrong count of
 //   --save-voice or --diffusion-latent.
+// --cvvp <file> [--cvvp-amount x]: re-rank the candidates with CVVP as well (tts_load_cvvp: do these codes sound like this speaker?; not in the reference): every
+//   candidate's codes are scored against the clips of its voice, one conditioning latent per clip made once per voice (tts_cvvp_voice_audio with --mel-norms), and
+//   the candidate with the best clvp * (1 - x) + cvvp * x is kept, upstream's cvvp_amount. x defaults to 0.5 beside --clvp and to 1 without it; the side whose
+//   weight is 0 is neither loaded nor evaluated, so --cvvp-amount 0 is the run without --cvvp, byte for byte. Prints "cvvp scores:" beside "clvp scores:" (per chunk
+//   with --split-text or several voices, where every chunk is scored against its own voice's clips). Usage errors (exit 1, before a model is loaded): a voice
+//   given as a --voice latent file, which holds no audio (the default voice is one); --devices > 1 or --exchange rccl; --stream; x outside 0 .. 1; 0 < x < 1
+//   without --clvp; --cvvp-amount without --cvvp.
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -115,6 +122,9 @@ int main(int argc, char **argv) {
   bool have_seed = false;
   int seed = 0, candidates = 1, steps = 80, device = 0, fixed_codes = 0, devices = 1, shard = -1, nshards = 1, split_ids = 0;
   std::string device_map, clvpPath, exchange = "files", rccl_id, diffLatentPath;
+  std::string cvvpPath;
+  double cvvp_amount = 0.0;
+  bool have_cvvp_amount = false;
   bool dry = false, allow_shared = false;
   bool timing = false;
   int test_fail_shard = -1, test_slow_shard = -1;
@@ -166,6 +176,8 @@ int main(int argc, char **argv) {
     else if (a == "--device-map") device_map = argv[i + 1];
     else if (a == "--allow-shared-device") allow_shared = argv[i + 1][0] != '0';
     else if (a == "--clvp") clvpPath = argv[i + 1];
+    else if (a == "--cvvp") cvvpPath = argv[i + 1];
+    else if (a == "--cvvp-amount") { cvvp_amount = std::atof(argv[i + 1]); have_cvvp_amount = true; }
     else if (a == "--exchange") exchange = argv[i + 1];
     else if (a == "--dry-run") dry = argv[i + 1][0] != '0'; // plumbing check without a device, see below
     else if (a == "--timing") timing = argv[i + 1][0] != '0'; // wall clock of every phase of this process on stderr
@@ -206,7 +218,7 @@ int main(int argc, char **argv) {
     if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--decoder hifigan cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
   }
   if (stream) {
-    const char *bad = !use_hifigan ? "--decoder diffusion" : !clvpPath.empty() ? "--clvp" : split_ids > 0 ? "--split-text" : voicePaths.size() > 1 ? "several --voice" :
+    const char *bad = !use_hifigan ? "--decoder diffusion" : !clvpPath.empty() ? "--clvp" : !cvvpPath.empty() ? "--cvvp" : split_ids > 0 ? "--split-text" : voicePaths.size() > 1 ? "several --voice" :
                       candidates > 1 ? "--candidates > 1" : (devices > 1 || shard >= 0) ? "--devices > 1" : nullptr;
     if (bad) { fprintf(stderr, "--stream serves one candidate of one voice through the HiFi-GAN decoder: it cannot be combined with %s\n", bad); return 1; }
     if (stream_stride < 1) { fprintf(stderr, "--stream-stride %d: at least 1\n", stream_stride); return 1; }
@@ -256,6 +268,22 @@ int main(int argc, char **argv) {
     fprintf(stderr, "--save-voice, --conditioning-model, --diffusion-conditioning-model and --mel-norms belong to --voice-clips, which is absent\n");
     return 1;
   }
+  // --cvvp (usage errors before any model is loaded)
+  const bool have_cvvp = !cvvpPath.empty();
+  if (!have_cvvp && have_cvvp_amount) { fprintf(stderr, "--cvvp-amount belongs to --cvvp, which is absent\n"); return 1; }
+  if (have_cvvp) {
+    if (!have_cvvp_amount) cvvp_amount = clvpPath.empty() ? 1.0 : 0.5;
+    if (!(cvvp_amount >= 0.0 && cvvp_amount <= 1.0)) { fprintf(stderr, "--cvvp-amount %g: a value in 0 .. 1\n", cvvp_amount); return 1; }
+    if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--cvvp cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
+    if (n_file_voices > 0 || voicePaths.empty()) {
+      fprintf(stderr, "--cvvp scores the candidates against the audio clips of their voice: a --voice latent file holds no audio (give every voice as --voice-clips)\n");
+      return 1;
+    }
+    if (cvvp_amount > 0.0 && cvvp_amount < 1.0 && clvpPath.empty()) { fprintf(stderr, "--cvvp-amount %g blends CVVP with CLVP: it needs --clvp <file> (without --clvp the amount is 1)\n", cvvp_amount); return 1; }
+  }
+  // the side whose weight is 0 is neither loaded nor evaluated
+  const bool use_cvvp = have_cvvp && cvvp_amount > 0.0, use_clvp = !clvpPath.empty() && !(have_cvvp && cvvp_amount >= 1.0);
+  const bool rerank = use_clvp || use_cvvp;
   // the --diffusion-latent file of every voice ("" for a clip voice, or when none is given): the k-th occurrence belongs to the k-th --voice
   std::vector<std::string> diffLatentOf(n_voices);
   for (int v = 0, k = 0; v < (int)voicePaths.size(); v++)
@@ -410,7 +438,10 @@ int main(int argc, char **argv) {
   }
   // --voice-clips: every clip voice's two latents, made on the device before any other model is loaded
   std::vector<std::vector<float>> clip1024(n_voices), clip2048(n_voices);
+  std::vector<std::vector<float>> cvvp_lat(n_voices); // --cvvp: every clip voice's conditioning latents [clips][latent dim], made once
+  std::vector<int> cvvp_clips(n_voices, 0);
   if (n_clip_voices > 0) {
+    if (use_cvvp && tts_load_cvvp(ctx, cvvpPath.c_str())) return die(ctx, "cvvp_model_load");
     if (tts_load_voice_encoder(ctx, condModel.c_str())) return die(ctx, "--conditioning-model");
     if (clip_latents && tts_load_diffusion_conditioning_encoder(ctx, dcondModel.c_str())) return die(ctx, "--diffusion-conditioning-model");
     std::vector<float> norms;
@@ -445,6 +476,11 @@ int main(int argc, char **argv) {
       if (clip_latents) clip2048[v].resize(2048);
       if (tts_voice_from_audio(ctx, samples.data(), lens.data(), rates.data(), (int)lens.size(), &vo, clip1024[v].data(), clip_latents ? clip2048[v].data() : nullptr))
         return die(ctx, "--voice-clips");
+      if (use_cvvp) {
+        cvvp_clips[v] = (int)lens.size();
+        cvvp_lat[v].resize((size_t)cvvp_clips[v] * tts_cvvp_latent_dim(ctx));
+        if (tts_cvvp_voice_audio(ctx, samples.data(), lens.data(), rates.data(), cvvp_clips[v], &vo, cvvp_lat[v].data())) return die(ctx, "--cvvp");
+      }
       if (!saveVoice.empty()) {
         std::ofstream f1(saveVoice[k] + ".bin", std::ios::binary);
         if (!f1 || !f1.write((const char *)clip1024[v].data(), 1024 * sizeof(float))) { std::cerr << "Error: Unable to write " << saveVoice[k] << ".bin" << std::endl; return 1; }
@@ -550,6 +586,30 @@ int main(int argc, char **argv) {
   std::vector<size_t> nsamp;
   std::vector<int32_t> frames;
   const int B_ar = candidates;
+  // The re-rankers on the B_ar candidates of one prompt (codes [B_ar][502], rows [B_ar]) of voice v: clvp * (1 - amount) + cvvp * amount, in float. Prints the
+  // scores that were evaluated under `label`; returns the arg-max (-1: a call failed) and its blended score.
+  auto rank_candidates = [&](const int32_t *text_ids, int n_text, const int32_t *cand_codes, const int32_t *cand_rows, int v, const std::string &label, double *best_score) {
+    std::vector<float> sc(B_ar, 0.f), sv(B_ar, 0.f), blended(B_ar);
+    if (use_clvp && tts_clvp_score(ctx, text_ids, n_text, cand_codes + 1, cand_rows, B_ar, 502, sc.data())) return -1;
+    if (use_cvvp && tts_cvvp_score(ctx, cvvp_lat[v].data(), cvvp_clips[v], cand_codes + 1, cand_rows, B_ar, 502, sv.data())) return -1;
+    const float wa = (float)(1.0 - cvvp_amount), wb = (float)cvvp_amount;
+    for (int c = 0; c < B_ar; c++) blended[c] = !use_cvvp ? sc[c] : !use_clvp ? sv[c] : sc[c] * wa + sv[c] * wb;
+    int best = 0;
+    for (int c = 1; c < B_ar; c++)
+      if (blended[c] > blended[best]) best = c;
+    if (use_clvp && (use_cvvp || label.empty())) { // CLVP alone prints what it printed: one line for the single prompt, none per chunk
+      printf("%sclvp scores:", label.c_str());
+      for (int c = 0; c < B_ar; c++) printf(" %.5f", sc[c]);
+      printf("\n");
+    }
+    if (use_cvvp) {
+      printf("%scvvp scores:", label.c_str());
+      for (int c = 0; c < B_ar; c++) printf(" %.5f", sv[c]);
+      printf("\n");
+    }
+    *best_score = blended[best];
+    return best;
+  };
   if (dry) {
     // Plumbing check without a device (tests/test_distributed_cpu.py): the host sampler on fixed synthetic logits stands in for the AR stage (so the
     // RNG stream partition of a --devices run is the real one), a candidate's "audio" is its sampled ids, its CLVP score a function of them. Exercises
@@ -613,20 +673,18 @@ int main(int argc, char **argv) {
     if (rc_ar) return die(ctx, "autoregressive");
     mark("autoregressive");
     printf("tokens sampled: %d (%d chunks)\n", nsteps, n_chunks);
-    if (!clvpPath.empty() && tts_load_clvp(ctx, clvpPath.c_str())) return die(ctx, "clvp_model_load");
+    if (use_clvp && tts_load_clvp(ctx, clvpPath.c_str())) return die(ctx, "clvp_model_load");
     std::vector<size_t> lat_off(B_all + 1, 0);
     for (int b = 0; b < B_all; b++) lat_off[b + 1] = lat_off[b] + (size_t)rows[b];
     std::vector<float> kept;
     std::vector<int32_t> kept_rows(n_chunks);
     for (int c = 0; c < n_chunks; c++) {
       int best = 0;
-      if (!clvpPath.empty()) {
-        std::vector<float> scores(B_ar);
-        if (tts_clvp_score(ctx, chunk_tokens[c].data(), n_text[c], codes.data() + (size_t)c * B_ar * 502 + 1, rows.data() + (size_t)c * B_ar, B_ar, 502,
-                           scores.data()))
-          return die(ctx, "clvp");
-        for (int k = 1; k < B_ar; k++)
-          if (scores[k] > scores[best]) best = k;
+      if (rerank) { // every chunk against its own text and its own voice's clips
+        double score = 0;
+        best = rank_candidates(chunk_tokens[c].data(), n_text[c], codes.data() + (size_t)c * B_ar * 502, rows.data() + (size_t)c * B_ar, multi_voice ? chunk_voice[c] : 0,
+                               "chunk " + std::to_string(c) + " ", &score);
+        if (best < 0) return die(ctx, use_cvvp ? "clvp / cvvp" : "clvp");
       }
       const int b = c * B_ar + best;
       kept_rows[c] = rows[b];
@@ -684,28 +742,22 @@ int main(int argc, char **argv) {
 
     // CLVP re-ranking (extension): keep the candidate whose codes (the rows the diffusion stage would consume) score best against the text
     B = B_ar;
-    if (!clvpPath.empty()) {
-      if (tts_load_clvp(ctx, clvpPath.c_str())) return die(ctx, "clvp_model_load");
-      std::vector<float> scores(B_ar);
-      if (tts_clvp_score(ctx, tokens.data(), n, codes.data() + 1, rows.data(), B_ar, 502, scores.data())) return die(ctx, "clvp");
-      int best = 0;
-      for (int c = 1; c < B_ar; c++)
-        if (scores[c] > scores[best]) best = c;
-      printf("clvp scores:");
-      for (int c = 0; c < B_ar; c++) printf(" %.5f", scores[c]);
-      printf("\n");
+    if (rerank) {
+      if (use_clvp && tts_load_clvp(ctx, clvpPath.c_str())) return die(ctx, "clvp_model_load");
+      const int best = rank_candidates(tokens.data(), n, codes.data(), rows.data(), 0, "", &kept_score);
+      if (best < 0) return die(ctx, use_cvvp ? "clvp / cvvp" : "clvp");
       size_t off_rows = 0;
       for (int c = 0; c < best; c++) off_rows += (size_t)rows[c];
       lat_in = latents.data() + off_rows * 1024;
       rows[0] = rows[best];
       B = 1;
       kept_gc = (shard >= 0 ? shard * B_ar : 0) + best;
-      kept_score = scores[best];
       if (total_candidates > 1) { // device noise stays keyed by the kept candidate's global id
         tts_set_option(ctx, "rng_shard_offset", (double)kept_gc);
         tts_set_option(ctx, "rng_shard_total", (double)total_candidates);
       }
-      if (shard < 0) printf("clvp: candidate %d kept (score %.5f)\n", kept_gc, kept_score);
+      if (use_cvvp) printf("rerank: candidate %d kept (score %.5f, cvvp amount %g)\n", kept_gc, kept_score, cvvp_amount);
+      else if (shard < 0) printf("clvp: candidate %d kept (score %.5f)\n", kept_gc, kept_score);
     }
   }
 

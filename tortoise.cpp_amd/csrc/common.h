@@ -88,6 +88,7 @@ struct ArState;
 struct DiffState;
 struct VocState;
 struct ClvpState;
+struct CvvpState;
 struct VoiceEncState;
 struct DiffCondEncState;
 struct HifiganState;
@@ -132,6 +133,7 @@ struct tts_ctx {
   tts::DiffState *diff = nullptr;
   tts::VocState *voc = nullptr;
   tts::ClvpState *clvp = nullptr; // candidate re-ranker (extras.hip; not in the reference)
+  tts::CvvpState *cvvp = nullptr; // the other candidate re-ranker: codes against the voice clips (cvvp.hip; not in the reference)
   tts::VoiceEncState *venc = nullptr; // voice-conditioning encoder (extras.hip; not in the reference)
   tts::DiffCondEncState *dcond = nullptr; // diffusion conditioning encoder (extras.hip; not in the reference)
   tts::HifiganState *hifigan = nullptr; // HiFi-GAN decoder: latents -> waveform (hifigan.hip; not in the reference: upstream's api_fast.py path)
@@ -577,5 +579,17 @@ int clvp_load(tts_ctx *ctx, const char *path);
 void clvp_free(ClvpState *);
 int clvp_score(tts_ctx *ctx, const int32_t *text_ids, int n_text, const int32_t *codes, const int32_t *code_len, int n_candidates, int code_stride,
                float *scores_out);
+// ---- CVVP (cvvp.hip) ----
+int cvvp_load(tts_ctx *ctx, const char *path);
+void cvvp_free(CvvpState *);
+int cvvp_latent_dim(const tts_ctx *ctx);
+int cvvp_voice(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_clips, float *latents_out);
+// the two halves of cvvp_voice, as voice_enc_begin / voice_enc_run: the caller fills the device mel buffer [80][frames[c]] per clip in between, on ctx->stream
+int cvvp_voice_begin(tts_ctx *ctx, const int32_t *frames, int n_clips, float **d_mel);
+int cvvp_voice_run(tts_ctx *ctx, float *latents_out);
+int cvvp_score(tts_ctx *ctx, const float *voice_latents, int n_clips, const int32_t *codes, const int32_t *code_len, int n_candidates, int code_stride,
+               float *scores_out);
+int afe_cvvp_voice_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                         float *latents_out); // audio_frontend.hip
 
 } // namespace tts

@@ -2,6 +2,7 @@
 //   1. CLVP candidate re-ranking                      tts_load_clvp / tts_clvp_score
 //   2. the voice-conditioning encoder (AR side)        tts_load_voice_encoder / tts_voice_latent
 //   3. the diffusion conditioning encoder              tts_load_diffusion_conditioning_encoder / tts_diffusion_conditioning_latent
+// (CVVP, the other half of 1, is cvvp.hip: it launches this file's encoder layers, AttentionBlock and k = 3 im2col through the host functions of encoder.h.)
 //
 // 1. The reference has no CLVP: main.cpp:6575 writes candidate 0. Upstream tortoise-tts scores every autoregressive candidate with CLVP
 // (tortoise/models/clvp.py, use_xformers=True) and keeps the best; this file is that scorer, for a weight file in the reference's container
@@ -21,6 +22,7 @@
 // These run once per utterance (CLVP: 13 ms for 16 candidates) or once per voice: the kernels are written for clarity, not for the roofline.
 #include "common.h"
 #include "gemm_f16.h"
+#include "encoder.h"
 #include <cmath>
 
 namespace tts {
@@ -205,15 +207,11 @@ __global__ __launch_bounds__(256) void dcond_im2col_kernel(const float *__restri
 }
 } // namespace
 
-struct ClvpLayer {
-  float *g_attn = nullptr, *g_ff = nullptr, *b_out = nullptr, *b_ff1 = nullptr, *b_ff2 = nullptr;
-  __half *w_qkv = nullptr, *w_out = nullptr, *w_ff1 = nullptr, *w_ff2 = nullptr;
-};
 struct ClvpState {
   int dim = 0, depth = 0, inner = 0, ff = 0, n_text = 0, n_speech = 0;
   float temperature = 0.f;
   float *emb[2] = {nullptr, nullptr}, *norm_w[2] = {nullptr, nullptr}, *norm_b[2] = {nullptr, nullptr};
-  std::vector<ClvpLayer> L[2];
+  std::vector<EncLayer> L[2];
   std::vector<float> proj[2]; // to_text_latent / to_speech_latent [latent][dim] (host: 16 x dim x latent multiply-adds per call)
   int latent = 0;
   std::vector<void *> owned;
@@ -222,23 +220,58 @@ struct ClvpState {
 };
 void clvp_free(ClvpState *s) { delete s; }
 
-static int clvp_up(tts_ctx *ctx, ClvpState *st, const std::vector<float> &src, float **dst) {
+int enc_up(tts_ctx *ctx, std::vector<void *> &owned, const std::vector<float> &src, float **dst) {
   void *p = nullptr;
   TTS_HIP(ctx, hipMalloc(&p, src.size() * 4));
-  st->owned.push_back(p);
+  owned.push_back(p);
   TTS_HIP(ctx, hipMemcpy(p, src.data(), src.size() * 4, hipMemcpyHostToDevice));
   *dst = (float *)p;
   return TTS_OK;
 }
-static int clvp_up16(tts_ctx *ctx, ClvpState *st, const std::vector<const std::vector<float> *> &parts, __half **dst) {
+int enc_up16(tts_ctx *ctx, std::vector<void *> &owned, const std::vector<const std::vector<float> *> &parts, __half **dst) {
   std::vector<__half> h;
   for (auto *v : parts)
     for (float f : *v) h.push_back(__float2half_rn(f));
   void *p = nullptr;
   TTS_HIP(ctx, hipMalloc(&p, h.size() * 2));
-  st->owned.push_back(p);
+  owned.push_back(p);
   TTS_HIP(ctx, hipMemcpy(p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
   *dst = (__half *)p;
+  return TTS_OK;
+}
+
+// The encoder layers of a CLVP / CVVP file (encoder.h). The messages name the model the file should hold.
+int enc_load_layers(tts_ctx *ctx, const WeightFile &wf, const std::string &enc, const char *model, int depth, int d, int in, int ff, std::vector<void *> &owned,
+                    std::vector<EncLayer> &out) {
+  auto need = [&](const std::string &name, int64_t n0, int64_t n1) -> const HostTensor * {
+    auto it = wf.t.find(name);
+    if (it == wf.t.end()) { fail(ctx, TTS_ERR_FORMAT, "tensor '%s' missing from %s model file", name.c_str(), model); return nullptr; }
+    if (it->second.ne[0] != n0 || it->second.ne[1] != n1 || it->second.nelem() != n0 * n1) {
+      fail(ctx, TTS_ERR_FORMAT, "tensor '%s' has wrong shape in %s model file: got [%d, %d], expected [%d, %d]", name.c_str(), model,
+           (int)it->second.ne[0], (int)it->second.ne[1], (int)n0, (int)n1);
+      return nullptr;
+    }
+    return &it->second;
+  };
+  const std::string lp = ".transformer.attn_layers.layers.";
+  const HostTensor *t;
+  int rc = 0;
+  out.resize(depth);
+  for (int i = 0; i < depth; i++) {
+    EncLayer &l = out[i];
+    const std::string a = enc + lp + std::to_string(2 * i) + ".", f = enc + lp + std::to_string(2 * i + 1) + ".";
+    const HostTensor *q, *k, *v;
+    if (!(t = need(a + "0.g", d, 1)) || (rc = enc_up(ctx, owned, t->data, &l.g_attn))) return rc ? rc : TTS_ERR_FORMAT;
+    if (!(q = need(a + "1.to_q.weight", d, in)) || !(k = need(a + "1.to_k.weight", d, in)) || !(v = need(a + "1.to_v.weight", d, in))) return TTS_ERR_FORMAT;
+    if ((rc = enc_up16(ctx, owned, {&q->data, &k->data, &v->data}, &l.w_qkv))) return rc; // [3 inner][dim]: one projection launch
+    if (!(t = need(a + "1.to_out.weight", in, d)) || (rc = enc_up16(ctx, owned, {&t->data}, &l.w_out))) return rc ? rc : TTS_ERR_FORMAT;
+    if (!(t = need(a + "1.to_out.bias", d, 1)) || (rc = enc_up(ctx, owned, t->data, &l.b_out))) return rc ? rc : TTS_ERR_FORMAT;
+    if (!(t = need(f + "0.g", d, 1)) || (rc = enc_up(ctx, owned, t->data, &l.g_ff))) return rc ? rc : TTS_ERR_FORMAT;
+    if (!(t = need(f + "1.net.0.proj.weight", d, 2 * ff)) || (rc = enc_up16(ctx, owned, {&t->data}, &l.w_ff1))) return rc ? rc : TTS_ERR_FORMAT;
+    if (!(t = need(f + "1.net.0.proj.bias", 2 * ff, 1)) || (rc = enc_up(ctx, owned, t->data, &l.b_ff1))) return rc ? rc : TTS_ERR_FORMAT;
+    if (!(t = need(f + "1.net.3.weight", ff, d)) || (rc = enc_up16(ctx, owned, {&t->data}, &l.w_ff2))) return rc ? rc : TTS_ERR_FORMAT;
+    if (!(t = need(f + "1.net.3.bias", d, 1)) || (rc = enc_up(ctx, owned, t->data, &l.b_ff2))) return rc ? rc : TTS_ERR_FORMAT;
+  }
   return TTS_OK;
 }
 
@@ -279,28 +312,13 @@ int clvp_load(tts_ctx *ctx, const char *path) {
   size_t known = 5; // embeddings, projections, temperature
   for (int e = 0; e < 2; e++) {
     if (!(t = need(embs[e], d, e ? st->n_speech : st->n_text))) return TTS_ERR_FORMAT;
-    if ((rc = clvp_up(ctx, st.get(), t->data, &st->emb[e]))) return rc;
+    if ((rc = enc_up(ctx, st->owned, t->data, &st->emb[e]))) return rc;
     if (!(t = need(projs[e], d, st->latent))) return TTS_ERR_FORMAT;
     st->proj[e] = t->data;
-    st->L[e].resize(st->depth);
-    for (int i = 0; i < st->depth; i++) {
-      ClvpLayer &l = st->L[e][i];
-      const std::string a = std::string(encs[e]) + lp + std::to_string(2 * i) + ".", f = std::string(encs[e]) + lp + std::to_string(2 * i + 1) + ".";
-      const HostTensor *q, *k, *v;
-      if (!(t = need(a + "0.g", d, 1)) || (rc = clvp_up(ctx, st.get(), t->data, &l.g_attn))) return rc ? rc : TTS_ERR_FORMAT;
-      if (!(q = need(a + "1.to_q.weight", d, in)) || !(k = need(a + "1.to_k.weight", d, in)) || !(v = need(a + "1.to_v.weight", d, in))) return TTS_ERR_FORMAT;
-      if ((rc = clvp_up16(ctx, st.get(), {&q->data, &k->data, &v->data}, &l.w_qkv))) return rc; // [3 inner][dim]: one projection launch
-      if (!(t = need(a + "1.to_out.weight", in, d)) || (rc = clvp_up16(ctx, st.get(), {&t->data}, &l.w_out))) return rc ? rc : TTS_ERR_FORMAT;
-      if (!(t = need(a + "1.to_out.bias", d, 1)) || (rc = clvp_up(ctx, st.get(), t->data, &l.b_out))) return rc ? rc : TTS_ERR_FORMAT;
-      if (!(t = need(f + "0.g", d, 1)) || (rc = clvp_up(ctx, st.get(), t->data, &l.g_ff))) return rc ? rc : TTS_ERR_FORMAT;
-      if (!(t = need(f + "1.net.0.proj.weight", d, 2 * ff)) || (rc = clvp_up16(ctx, st.get(), {&t->data}, &l.w_ff1))) return rc ? rc : TTS_ERR_FORMAT;
-      if (!(t = need(f + "1.net.0.proj.bias", 2 * ff, 1)) || (rc = clvp_up(ctx, st.get(), t->data, &l.b_ff1))) return rc ? rc : TTS_ERR_FORMAT;
-      if (!(t = need(f + "1.net.3.weight", ff, d)) || (rc = clvp_up16(ctx, st.get(), {&t->data}, &l.w_ff2))) return rc ? rc : TTS_ERR_FORMAT;
-      if (!(t = need(f + "1.net.3.bias", d, 1)) || (rc = clvp_up(ctx, st.get(), t->data, &l.b_ff2))) return rc ? rc : TTS_ERR_FORMAT;
-      known += 11;
-    }
-    if (!(t = need(std::string(encs[e]) + ".transformer.norm.weight", d, 1)) || (rc = clvp_up(ctx, st.get(), t->data, &st->norm_w[e]))) return rc ? rc : TTS_ERR_FORMAT;
-    if (!(t = need(std::string(encs[e]) + ".transformer.norm.bias", d, 1)) || (rc = clvp_up(ctx, st.get(), t->data, &st->norm_b[e]))) return rc ? rc : TTS_ERR_FORMAT;
+    if ((rc = enc_load_layers(ctx, wf, encs[e], "CLVP", st->depth, d, in, ff, st->owned, st->L[e]))) return rc;
+    known += 11 * (size_t)st->depth;
+    if (!(t = need(std::string(encs[e]) + ".transformer.norm.weight", d, 1)) || (rc = enc_up(ctx, st->owned, t->data, &st->norm_w[e]))) return rc ? rc : TTS_ERR_FORMAT;
+    if (!(t = need(std::string(encs[e]) + ".transformer.norm.bias", d, 1)) || (rc = enc_up(ctx, st->owned, t->data, &st->norm_b[e]))) return rc ? rc : TTS_ERR_FORMAT;
     known += 2;
   }
   // every tensor in the file must be known (the loaders of the three reference models do the same, main.cpp:834-838); the rotary
@@ -312,6 +330,50 @@ int clvp_load(tts_ctx *ctx, const char *path) {
   if (ctx->clvp) clvp_free(ctx->clvp);
   ctx->clvp = st.release();
   return TTS_OK;
+}
+
+void enc_embed(tts_ctx *ctx, const float *emb, const int *d_tok, int dim, int rows, float *x) {
+  clvp_embed_kernel<<<rows, 256, 0, ctx->stream>>>(emb, d_tok, dim, x);
+}
+
+static GemmArgs enc_gemm(const __half *A, int K, const __half *W, int M, int N, const float *bias) {
+  GemmArgs g{};
+  for (int i = 0; i < 3; i++) { g.A[i] = A; g.row_off[i] = 0; }
+  g.nseg = 1; g.kseg = K; g.lda = K; g.W = W; g.M = M; g.N = N; g.bias = bias;
+  return g;
+}
+
+int enc_run_layers(tts_ctx *ctx, const std::vector<EncLayer> &layers, int d, int in, int ff, const EncWork &w) {
+  const int rows = w.rows, M = w.M;
+  float *x = w.x, *u = w.u;
+  __half *y = w.y, *qkv = w.qkv, *att = w.att;
+  for (const EncLayer &l : layers) {
+    ProfScope ps(ctx, "clvp_layer", 2.0 * rows * ((double)d * 3 * in + (double)in * d + (double)d * 2 * ff + (double)ff * d));
+    clvp_rmsnorm_kernel<<<rows, 256, 0, ctx->stream>>>(x, l.g_attn, d, y);
+    { GemmArgs g = enc_gemm(y, d, l.w_qkv, M, 3 * in, nullptr); g.mode = GEMM_OUT_F16; g.outH = qkv; g.ldh = 3 * in; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
+    clvp_attn_kernel<true, 64, false><<<dim3(w.nseq, in / CLVP_DH, (w.maxlen + 255) / 256), 256, 0, ctx->stream>>>(qkv, w.d_start, w.d_len, in, att, nullptr);
+    { GemmArgs g = enc_gemm(att, in, l.w_out, M, d, l.b_out); g.mode = GEMM_OUT_F32; g.outF = x; g.ldo = d; g.resid = x; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
+    clvp_rmsnorm_kernel<<<rows, 256, 0, ctx->stream>>>(x, l.g_ff, d, y);
+    { GemmArgs g = enc_gemm(y, d, l.w_ff1, M, 2 * ff, l.b_ff1); g.mode = GEMM_OUT_F32; g.outF = u; g.ldo = 2 * ff; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
+    clvp_geglu_kernel<<<rows, 256, 0, ctx->stream>>>(u, ff, y);
+    { GemmArgs g = enc_gemm(y, ff, l.w_ff2, M, d, l.b_ff2); g.mode = GEMM_OUT_F32; g.outF = x; g.ldo = d; g.resid = x; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
+  }
+  return TTS_OK;
+}
+
+int attn_block_run(tts_ctx *ctx, int D, const AttnBlockW &b, const EncWork &w) {
+  if (D == 512) venc_groupnorm_kernel<512><<<dim3(32, w.nseq), 256, 0, ctx->stream>>>(w.x, w.d_start, w.d_len, b.g, b.b, w.y);
+  else if (D == 1024) venc_groupnorm_kernel<1024><<<dim3(32, w.nseq), 256, 0, ctx->stream>>>(w.x, w.d_start, w.d_len, b.g, b.b, w.y);
+  else return fail(ctx, TTS_ERR_ARG, "attn_block_run: %d channels (512 or 1024)", D);
+  { GemmArgs g = enc_gemm(w.y, D, b.w_qkv, w.M, 3 * D, b.b_qkv); g.mode = GEMM_OUT_F16; g.outH = w.qkv; g.ldh = 3 * D; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
+  clvp_attn_kernel<false, 64, false><<<dim3(w.nseq, D / CLVP_DH, (w.maxlen + 255) / 256), 256, 0, ctx->stream>>>(w.qkv, w.d_start, w.d_len, D, w.att, nullptr);
+  { GemmArgs g = enc_gemm(w.att, D, b.w_proj, w.M, D, b.b_proj); g.mode = GEMM_OUT_F32; g.outF = w.x; g.ldo = D; g.resid = w.x; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
+  return TTS_OK;
+}
+
+void im2col3_rows(tts_ctx *ctx, const float *x, const int *in_start, const int *in_len, const int *out_start, const int *out_len, int max_out, int nseq, int cin,
+                  int kpad, __half *a16) {
+  dcond_im2col_kernel<false><<<dim3(max_out, nseq), 256, 0, ctx->stream>>>(x, nullptr, in_start, in_len, out_start, out_len, cin, kpad, a16);
 }
 
 // pooled latent of every sequence of one encoder: lens[n_seq] token counts, tokens concatenated
@@ -338,25 +400,11 @@ static int clvp_encode(tts_ctx *ctx, ClvpState *st, int e, const std::vector<int
   TTS_HIP(ctx, hipMemsetAsync(st->u32.p, 0, (size_t)M * 2 * ff * 4, ctx->stream));
   float *x = st->x.as<float>(), *u = st->u32.as<float>();
   __half *y = st->y16.as<__half>(), *qkv = st->qkv16.as<__half>(), *att = st->att16.as<__half>();
-  clvp_embed_kernel<<<rows, 256, 0, ctx->stream>>>(st->emb[e], d_tok, d, x);
-  auto gemm = [&](const __half *A, int K, const __half *W, int N, const float *bias) {
-    GemmArgs g{};
-    for (int i = 0; i < 3; i++) { g.A[i] = A; g.row_off[i] = 0; }
-    g.nseg = 1; g.kseg = K; g.lda = K; g.W = W; g.M = M; g.N = N; g.bias = bias;
-    return g;
-  };
-  for (int i = 0; i < st->depth; i++) {
-    const ClvpLayer &l = st->L[e][i];
-    ProfScope ps(ctx, "clvp_layer", 2.0 * rows * ((double)d * 3 * in + (double)in * d + (double)d * 2 * ff + (double)ff * d));
-    clvp_rmsnorm_kernel<<<rows, 256, 0, ctx->stream>>>(x, l.g_attn, d, y);
-    { GemmArgs g = gemm(y, d, l.w_qkv, 3 * in, nullptr); g.mode = GEMM_OUT_F16; g.outH = qkv; g.ldh = 3 * in; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
-    clvp_attn_kernel<true, 64, false><<<dim3(nseq, in / CLVP_DH, (maxlen + 255) / 256), 256, 0, ctx->stream>>>(qkv, d_start, d_len, in, att, nullptr);
-    { GemmArgs g = gemm(att, in, l.w_out, d, l.b_out); g.mode = GEMM_OUT_F32; g.outF = x; g.ldo = d; g.resid = x; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
-    clvp_rmsnorm_kernel<<<rows, 256, 0, ctx->stream>>>(x, l.g_ff, d, y);
-    { GemmArgs g = gemm(y, d, l.w_ff1, 2 * ff, l.b_ff1); g.mode = GEMM_OUT_F32; g.outF = u; g.ldo = 2 * ff; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
-    clvp_geglu_kernel<<<rows, 256, 0, ctx->stream>>>(u, ff, y);
-    { GemmArgs g = gemm(y, ff, l.w_ff2, d, l.b_ff2); g.mode = GEMM_OUT_F32; g.outF = x; g.ldo = d; g.resid = x; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
-  }
+  enc_embed(ctx, st->emb[e], d_tok, d, rows, x);
+  EncWork w;
+  w.d_start = d_start; w.d_len = d_len; w.nseq = nseq; w.rows = rows; w.maxlen = maxlen; w.M = M;
+  w.x = x; w.u = u; w.y = y; w.qkv = qkv; w.att = att;
+  { const int rc = enc_run_layers(ctx, st->L[e], d, in, ff, w); if (rc) return rc; }
   clvp_pool_kernel<<<nseq, 256, 0, ctx->stream>>>(x, d_start, d_len, st->norm_w[e], st->norm_b[e], d, st->pooled.as<float>());
   TTS_HIP(ctx, hipGetLastError());
   std::vector<float> pooled((size_t)nseq * d);
@@ -412,10 +460,7 @@ int clvp_score(tts_ctx *ctx, const int32_t *text_ids, int n_text, const int32_t 
 // ------------------------------------------------------------------------------------------------------------------------------
 // voice-conditioning encoder
 // ------------------------------------------------------------------------------------------------------------------------------
-struct VencBlock {
-  float *g = nullptr, *b = nullptr, *b_qkv = nullptr, *b_proj = nullptr;
-  __half *w_qkv = nullptr, *w_proj = nullptr;
-};
+using VencBlock = AttnBlockW;
 struct VoiceEncState {
   float *b_init = nullptr;
   __half *w_init = nullptr; // [1024][128]: K padded 80 -> 128
@@ -550,11 +595,12 @@ int voice_enc_run(tts_ctx *ctx, float *out1024) {
     return g;
   };
   { GemmArgs g = gemm(a16, 128, st->w_init, D, st->b_init); g.mode = GEMM_OUT_F32; g.outF = x; g.ldo = D; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
+  EncWork w;
+  w.d_start = d_start; w.d_len = d_len; w.nseq = n_clips; w.rows = rows; w.maxlen = maxlen; w.M = M;
+  w.x = x; w.y = y; w.qkv = qkv; w.att = att;
   for (const VencBlock &b : st->blk) {
-    venc_groupnorm_kernel<1024><<<dim3(32, n_clips), 256, 0, ctx->stream>>>(x, d_start, d_len, b.g, b.b, y);
-    { GemmArgs g = gemm(y, D, b.w_qkv, 3 * D, b.b_qkv); g.mode = GEMM_OUT_F16; g.outH = qkv; g.ldh = 3 * D; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
-    clvp_attn_kernel<false, 64, false><<<dim3(n_clips, D / CLVP_DH, (maxlen + 255) / 256), 256, 0, ctx->stream>>>(qkv, d_start, d_len, D, att, nullptr);
-    { GemmArgs g = gemm(att, D, b.w_proj, D, b.b_proj); g.mode = GEMM_OUT_F32; g.outF = x; g.ldo = D; g.resid = x; TTS_HIP(ctx, launch_gemm_f16(g, ctx->stream)); }
+    const int rc = attn_block_run(ctx, D, b, w);
+    if (rc) return rc;
   }
   TTS_HIP(ctx, hipGetLastError());
   // position 0 of every clip, mean over the clips

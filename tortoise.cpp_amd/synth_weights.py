@@ -229,6 +229,46 @@ def write_clvp(path, depth=20, dim=768, heads=12, ff_mult=2, seed=1237):
     w.close()
 
 
+CVVP_ENCODERS = ("conditioning_transformer", "speech_transformer")
+
+
+def write_cvvp(path, depth=8, dim=512, seed=1241, ff_mult=1):
+    """ggml-cvvp-model.bin: the CVVP re-ranker of upstream tortoise-tts (tortoise/models/cvvp.py, restated from memory: csrc/cvvp.hip states the architecture):
+    cond_emb = two strided convolutions over the 80-band mel, speech_emb over the mel codes, two CollapsingTransformers (CLVP's encoder layers with ff = dim, a
+    final LayerNorm, pre_combiner = k-1 conv, AttentionBlock, k-1 conv, mean over the rows), bias-free latent projections, cosine similarity x exp(temperature).
+    Tensor names = the upstream state dict's; k = 1 convolutions keep their 3-D [out, in, 1] shape. The reference has no CVVP: the container is this
+    repository's, in the reference's file format."""
+    g = _Gen(seed)
+    w = GgmlWriter(path)
+    inner, ff, half = dim, dim * ff_mult, dim // 2
+    w.add("temperature", np.array([1.0], np.float32))
+    w.add("cond_emb.0.weight", g.lecun((half, 80, 5), 400)); w.add("cond_emb.0.bias", g.normal((half,), 0.02))
+    w.add("cond_emb.1.weight", g.lecun((dim, half, 3), 3 * half)); w.add("cond_emb.1.bias", g.normal((dim,), 0.02))
+    w.add("speech_emb.emb.weight", g.normal((8192, dim), 0.5))
+    w.add("to_conditioning_latent.weight", g.lecun((dim, dim), dim))
+    w.add("to_speech_latent.weight", g.lecun((dim, dim), dim))
+    rs = 1.0 / np.sqrt(2.0 * depth)
+    for enc in CVVP_ENCODERS:
+        for i in range(depth):
+            a = "%s.transformer.attn_layers.layers.%d." % (enc, 2 * i)
+            f = "%s.transformer.attn_layers.layers.%d." % (enc, 2 * i + 1)
+            w.add(a + "0.g", g.gamma(dim))
+            for nm in ("to_q", "to_k", "to_v"):
+                w.add(a + "1.%s.weight" % nm, g.lecun((inner, dim), dim, 1.5))
+            w.add(a + "1.to_out.weight", g.lecun((dim, inner), inner, rs)); w.add(a + "1.to_out.bias", g.normal((dim,), 0.02))
+            w.add(f + "0.g", g.gamma(dim))
+            w.add(f + "1.net.0.proj.weight", g.lecun((2 * ff, dim), dim)); w.add(f + "1.net.0.proj.bias", g.normal((2 * ff,), 0.02))
+            w.add(f + "1.net.3.weight", g.lecun((dim, ff), ff, rs)); w.add(f + "1.net.3.bias", g.normal((dim,), 0.02))
+        w.add(enc + ".transformer.norm.weight", g.gamma(dim)); w.add(enc + ".transformer.norm.bias", g.beta(dim))
+        p = enc + ".pre_combiner."
+        w.add(p + "0.weight", g.lecun((dim, dim, 1), dim)); w.add(p + "0.bias", g.normal((dim,), 0.02))
+        w.add(p + "1.norm.weight", g.gamma(dim)); w.add(p + "1.norm.bias", g.beta(dim))
+        w.add(p + "1.qkv.weight", g.lecun((3 * dim, dim, 1), dim, 1.5)); w.add(p + "1.qkv.bias", g.normal((3 * dim,), 0.02))
+        w.add(p + "1.proj_out.weight", g.lecun((dim, dim, 1), dim, 0.5)); w.add(p + "1.proj_out.bias", g.normal((dim,), 0.02))
+        w.add(p + "2.weight", g.lecun((dim, dim, 1), dim)); w.add(p + "2.bias", g.normal((dim,), 0.02))
+    w.close()
+
+
 def write_voice_encoder(path, blocks=6, seed=1238):
     """ggml-conditioning-model.bin: the conditioning encoder of upstream tortoise-tts' UnifiedVoice (tortoise/models/autoregressive.py:
     ConditioningEncoder(80, 1024, attn_blocks=6, num_attn_heads=16) = Conv1d(80, 1024, 1) + 6 AttentionBlocks (GroupNorm32, qkv Conv1d k=1,
