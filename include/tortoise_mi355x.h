@@ -611,7 +611,7 @@ int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand);
  *   was opened (a 72-byte descriptor: the fields it has).
  * tts_diff_session_open(max_packed_rows, max_requests): every option the diffusion stage reads is read here and holds until tts_diff_session_close, whatever
  *   tts_set_option stores meanwhile: "attn_f32", "share_uncond", "hoist_integrator", "diff_graph", "gn_eps", "ggml_lut", "attn_proj_f16", "proj_dual_b",
- *   "gemm_wreg", "attn_f32_drop", "lc_attn_f32", "attn_q64", "fp16_check", and "diff_sampler" / "ddim_eta" / "cond_free_k" / "diff_temperature" / "cond_free" as tts_diff_request_init's
+ *   "gemm_wreg", "gemm_gn_fuse", "attn_f32_drop", "lc_attn_f32", "attn_q64", "fp16_check", and "diff_sampler" / "ddim_eta" / "cond_free_k" / "diff_temperature" / "cond_free" as tts_diff_request_init's
  *   defaults; the session always runs the batch-path GroupNorm ("latency_mode" is not bit-identical to it by design). With "hoist_integrator" on, every request
  *   is hoisted and owns n_steps x packed rows x 2 KB of device memory until it is collected; a request may then take at most 16384 packed rows (the option's
  *   value, if above 1), else tts_diff_session_admit returns TTS_ERR_LIMIT; a session opened with "hoist_integrator" 0 has no such bound. All activation buffers for max_packed_rows rows are allocated here. A session already open is closed first. TTS_ERR_ARG:

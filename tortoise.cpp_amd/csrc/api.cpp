@@ -192,6 +192,7 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
   else if (k == "attn_proj_f16") c->attn_proj_f16 = value != 0;
   else if (k == "proj_dual_b") c->proj_dual_b = value != 0;
   else if (k == "gemm_wreg") c->gemm_wreg = value == 1 ? tts_ctx::GEMM_WREG_ALL : value == 2 ? 1 : value == 3 ? 2 : value == 4 ? 4 : 0; // 0 the LDS-staged kernels, 1 every class that has a register-streamed kernel, 2 / 3 / 4 in_layers / QKV / k = 3 out_layers only (A/B)
+  else if (k == "gemm_gn_fuse") c->gemm_gn_fuse = value != 0;
   else if (k == "lc_attn_f32") c->lc_attn_f32 = value != 0;
   else if (k == "latency_mode") c->latency_mode = value != 0;
   else if (k == "fp16_check") c->fp16_check = value != 0;

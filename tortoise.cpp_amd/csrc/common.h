@@ -164,6 +164,7 @@ struct tts_ctx {
   int attn_f32 = 0;        // option "attn_f32": the diffusion AttentionBlock in reference precision (F32 QK^T / softmax / PV / proj_out, main.cpp:3848-3875) via split-fp16 MFMA operands; 0 = fp16 operands (throughput mode)
   static constexpr int GEMM_WREG_ALL = 7;
   int gemm_wreg = GEMM_WREG_ALL; // option "gemm_wreg": classes of diffusion GEMMs whose weight operand is streamed into registers from its fragment-major image (bit 0: k = 1 in_layers, bit 1: QKV projection, bit 2: k = 3 out_layers); 0 = the LDS-staged kernels
+  int gemm_gn_fuse = 1;    // option "gemm_gn_fuse": a ResBlock's k = 1 in_layers GEMM and the GroupNorm that consumes it run as one launch (gemm_f16.h: gemm_f16_gn_panel_kernel) where gemm_gn_panel_takes admits the layout (bit-identical); 0 = the pair
   int proj_dual_b = 1;     // option "proj_dual_b" (developer A/B): the split-weight proj_out GEMM stages both weight halves per activation tile (1) or runs two K segments (0)
   int attn_f32_drop = 0;   // option "attn_f32_drop" (developer ablation inside attn_f32 = 1): bit 0 q/k, bit 1 v, bit 2 attention output lose their low halves (= the fp16 rounding of the default mode, one operand at a time)
   int lc_attn_f32 = 1;     // option "lc_attn_f32": the latent conditioner's AttentionBlocks (once per utterance; their output enters every step) in reference precision whatever attn_f32 says; 0 = follow attn_f32 (rounds 1-4)

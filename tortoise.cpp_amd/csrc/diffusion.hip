@@ -1487,42 +1487,24 @@ static int gn_stats(tts_ctx *ctx, const Layout &lay, Work &wk, const float *x) {
   return TTS_OK;
 }
 // Register-resident variant: one workgroup of NT threads = one (sequence, 32-channel group); the [T][32] slab
-// (T <= NJ * NT / 8 rows) is read from HBM exactly once into NJ float4 per thread, mean and centred variance are
+// (T <= NJ * NT / 8 rows) is read exactly once into NJ float4 per thread, mean and centred variance are
 // reduced across the workgroup (two-pass on registers), and the normalised fp16 rows are written straight out.
-template <int NT, int NJ>
-__global__ __launch_bounds__(NT) void gn_reg_kernel(const float *__restrict__ x, const int *__restrict__ seq_start,
-                                                    const int *__restrict__ seq_len, int rows_total, int ns, float eps,
-                                                    const float *__restrict__ g, const float *__restrict__ b,
-                                                    const float *__restrict__ ss, int do_silu, int lut, __half *__restrict__ y,
-                                                    const char *__restrict__ pf0, int pf0_lines, const char *__restrict__ pf1, int pf1_lines,
-                                                    const int *__restrict__ seq_step, int ss_step_stride) {
+// gn_reg_body is that arithmetic, stated once: gn_reg_kernel reads the slab from global memory, gemm_f16_gn_panel_kernel (gemm_f16.h) from the f32 panel its GEMM
+// half left in LDS. load(t) = the thread's float4 of slab row t; touch() runs right behind the slab loads (gn_reg_kernel's weight touch).
+template <int NT, int NJ, class LOAD, class TOUCH>
+__device__ __forceinline__ void gn_reg_body(LOAD load, TOUCH touch, int s, int c, int T, int r0, const int *__restrict__ seq_start, int rows_total, int ns, float eps,
+                                            const float *__restrict__ g, const float *__restrict__ b, const float *__restrict__ ss, int do_silu, int lut,
+                                            __half *__restrict__ y, const int *__restrict__ seq_step, int ss_step_stride) {
   constexpr int NW = NT / 64, SWEEP = NT / 8;
   __shared__ float sh[2][NW];
-  __shared__ unsigned pf_sink[NW][64]; // landing zone of the weight touch below
-  // workgroup b runs on XCD b % 8: give each XCD whole sequences (all 32 groups of a row = the full 4 KB row go
-  // through one L2) instead of 128-byte slices of every row
-  const int bid = blockIdx.y * 32 + blockIdx.x, nbk = ns * 32, item = (bid & 7) * (nbk >> 3) + (bid >> 3); // nbk % 8 == 0 (32 groups)
-  const int s = item >> 5, grp = item & 31;
-  const int T = seq_len[s], r0 = seq_start[s];
-  const int q = threadIdx.x & 7, c = grp * 32 + q * 4, t0 = threadIdx.x >> 3;
-  const float *base = x + (size_t)r0 * C + c;
+  const int t0 = threadIdx.x >> 3;
   float4 v[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; j++) {
     const int t = t0 + j * SWEEP;
-    v[j] = *(const float4 *)(base + (size_t)min(t, T - 1) * C); // clamped rows are masked out of the sums below
+    v[j] = load(min(t, T - 1)); // clamped rows are masked out of the sums below
   }
-  // Weight touch for the GEMM(s) that consume this kernel's output: one dword of every 128-byte line of their weight matrices, spread
-  // over all threads of the launch, requested right behind the slab (LDS-DMA into a sink: no register is waiting for the data). The
-  // 0.36 GB of fp16 weights cycle through the 256 MB memory-side cache once per sampling step, so without it every K tile of the next
-  // GEMM is a miss to HBM for all of its workgroups at once (they walk K in lockstep): a k = 1 GEMM of one utterance takes 24 us with
-  // cold weights against 14 us when they sit in the memory-side cache (profiles/r2_gemm_small_problems.txt, round-3 addendum).
-  {
-    const int gi = (blockIdx.y * 32 + blockIdx.x) * NT + threadIdx.x, tt = 32 * ns * NT;
-    unsigned *sink = &pf_sink[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)][0];
-    for (int l = gi; l < pf0_lines; l += tt) __builtin_amdgcn_global_load_lds((gptr_t)(pf0 + (size_t)l * 128), (lptr_t)sink, 4, 0, 0);
-    for (int l = gi; l < pf1_lines; l += tt) __builtin_amdgcn_global_load_lds((gptr_t)(pf1 + (size_t)l * 128), (lptr_t)sink, 4, 0, 0);
-  }
+  touch();
   const float4 gg = *(const float4 *)(g + c), bb = *(const float4 *)(b + c);
   float sc4[4] = {1.f, 1.f, 1.f, 1.f}, sh4[4] = {0.f, 0.f, 0.f, 0.f};
   if (ss) {
@@ -1593,7 +1575,52 @@ __global__ __launch_bounds__(NT) void gn_reg_kernel(const float *__restrict__ x,
   for (int r = r0 + T + t0; r < gend; r += SWEEP) *(uint2 *)(y + (size_t)r * C + c) = make_uint2(0u, 0u);
   if (s == 0)
     for (int r = t0; r < r0; r += SWEEP) *(uint2 *)(y + (size_t)r * C + c) = make_uint2(0u, 0u);
+}
+template <int NT, int NJ>
+__global__ __launch_bounds__(NT) void gn_reg_kernel(const float *__restrict__ x, const int *__restrict__ seq_start,
+                                                    const int *__restrict__ seq_len, int rows_total, int ns, float eps,
+                                                    const float *__restrict__ g, const float *__restrict__ b,
+                                                    const float *__restrict__ ss, int do_silu, int lut, __half *__restrict__ y,
+                                                    const char *__restrict__ pf0, int pf0_lines, const char *__restrict__ pf1, int pf1_lines,
+                                                    const int *__restrict__ seq_step, int ss_step_stride) {
+  constexpr int NW = NT / 64;
+  __shared__ unsigned pf_sink[NW][64]; // landing zone of the weight touch below
+  // workgroup b runs on XCD b % 8: give each XCD whole sequences (all 32 groups of a row = the full 4 KB row go
+  // through one L2) instead of 128-byte slices of every row
+  const int bid = blockIdx.y * 32 + blockIdx.x, nbk = ns * 32, item = (bid & 7) * (nbk >> 3) + (bid >> 3); // nbk % 8 == 0 (32 groups)
+  const int s = item >> 5, grp = item & 31;
+  const int T = seq_len[s], r0 = seq_start[s];
+  const int q = threadIdx.x & 7, c = grp * 32 + q * 4;
+  const float *base = x + (size_t)r0 * C + c;
+  // Weight touch for the GEMM(s) that consume this kernel's output: one dword of every 128-byte line of their weight matrices, spread
+  // over all threads of the launch, requested right behind the slab (LDS-DMA into a sink: no register is waiting for the data). The
+  // 0.36 GB of fp16 weights cycle through the 256 MB memory-side cache once per sampling step, so without it every K tile of the next
+  // GEMM is a miss to HBM for all of its workgroups at once (they walk K in lockstep): a k = 1 GEMM of one utterance takes 24 us with
+  // cold weights against 14 us when they sit in the memory-side cache (profiles/r2_gemm_small_problems.txt, round-3 addendum).
+  auto touch = [&]() {
+    const int gi = (blockIdx.y * 32 + blockIdx.x) * NT + threadIdx.x, tt = 32 * ns * NT;
+    unsigned *sink = &pf_sink[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)][0];
+    for (int l = gi; l < pf0_lines; l += tt) __builtin_amdgcn_global_load_lds((gptr_t)(pf0 + (size_t)l * 128), (lptr_t)sink, 4, 0, 0);
+    for (int l = gi; l < pf1_lines; l += tt) __builtin_amdgcn_global_load_lds((gptr_t)(pf1 + (size_t)l * 128), (lptr_t)sink, 4, 0, 0);
+  };
+  gn_reg_body<NT, NJ>([&](int t) { return *(const float4 *)(base + (size_t)t * C); }, touch, s, c, T, r0, seq_start, rows_total, ns, eps, g, b, ss, do_silu, lut, y, seq_step,
+                      ss_step_stride);
   if (pf0_lines | pf1_lines) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the sink belongs to this workgroup until its last weight touch has landed
+}
+// The GroupNorm half of gemm_f16_gn_panel_kernel: gn_reg_kernel<512, 14>'s arithmetic on the f32 panel [row][32] of one (sequence, group) in LDS
+struct GnPanelTail {
+  __device__ __forceinline__ void operator()(const GemmGnPanelArgs &a, int s, int T, int r0, int c0, const char *panel) const {
+    const int q = threadIdx.x & 7;
+    gn_reg_body<512, 14>([&](int t) { return *(const float4 *)(panel + gnp_panel_f4(t, q)); }, []() {}, s, c0 + q * 4, T, r0, a.seq_start, a.rows_total, a.ns, a.eps, a.gn_g,
+                         a.gn_b, a.ss, a.do_silu, a.lut, a.y, a.seq_step, a.ss_step_stride);
+  }
+};
+
+static inline hipError_t launch_gemm_gn_panel(const GemmGnPanelArgs &a, hipStream_t s) {
+  static bool raised = false; // more dynamic LDS than a kernel may use by default: asked for once (as gemm_launch)
+  if (!raised) { (void)hipFuncSetAttribute((const void *)gemm_f16_gn_panel_kernel<GnPanelTail>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_GN_PANEL_LDS); raised = true; }
+  gemm_f16_gn_panel_kernel<GnPanelTail><<<gemm_gn_panel_grid(a.ns, a.N), 512, GEMM_GN_PANEL_LDS, s>>>(a, GnPanelTail{});
+  return hipGetLastError();
 }
 
 // stats + apply in one launch (see gn_fused_kernel). wa / wb: weight matrices (bytes) of the GEMMs that follow, touched into the
@@ -1821,6 +1848,24 @@ static int attention_block(tts_ctx *ctx, DiffState *st, const Layout &lay, Work 
   return TTS_OK;
 }
 
+// The k = 1 in_layers GEMM of a ResBlock and the GroupNorm (+ scale/shift, SiLU) in front of its k = 3 convolution as ONE launch, where gemm_gn_panel_takes admits the
+// layout (option gemm_gn_fuse): y = fp16(silu(gn(A . W^T + bias))) with the bits of launch_gemm_f16 (gemm_f16_wreg_kernel) + gn_reg_kernel<512, 14>. Profiled in the
+// GEMM's family with the GEMM's FLOPs: the class's time includes the normalisation.
+static int gemm_gn_panel(tts_ctx *ctx, const Layout &lay, const __half *A, const __half *Wf, const float *bias, const float *g, const float *b, const float *ss, __half *y) {
+  double mv = 0;
+  for (int l : lay.len) mv += l;
+  {
+    ProfScope ps(ctx, "diff_gemm_k1", 2.0 * mv * C * C);
+    GemmGnPanelArgs a{};
+    a.A = A; a.lda = C; a.Wf = Wf; a.N = C; a.K = C; a.bias = bias;
+    a.seq_start = lay.d_start.as<int>(); a.seq_len = lay.d_len.as<int>(); a.ns = lay.ns; a.rows_total = lay.rows;
+    a.eps = ctx->gn_eps; a.gn_g = g; a.gn_b = b; a.ss = ss; a.do_silu = 1; a.lut = ctx->ggml_lut ? 1 : ctx->attn_f32 ? 2 : 0; // see silu_dev
+    a.y = y; a.seq_step = lay.seq_step_ptr(); a.ss_step_stride = lay.ss_step_stride;
+    TTS_HIP(ctx, launch_gemm_gn_panel(a, ctx->stream));
+  }
+  return fp16_check(ctx, y, (size_t)lay.rows * C);
+}
+
 // ResBlock: X = Xin + out_layers(in_layers(Xin) with the step's scale/shift); Xin == nullptr: in place on X.
 // ss = this step's [scale | shift] for this block (device, 2048 floats). Hpre: in_layers(Xin) computed earlier (it does
 // not depend on the timestep), nullptr: computed here.
@@ -1830,6 +1875,22 @@ static int res_block(tts_ctx *ctx, DiffState *st, const Layout &lay, Work &wk, f
   const float *xin = Xin ? Xin : X;
   const bool lat = st->lat && (Hpre ? st_hpre != nullptr : wk.st_x != nullptr);
   const long long *st_h = st_hpre;
+#ifdef TTS_DEBUG_CHECKSUM
+  constexpr bool debug_sums = true; // the hashes below need H
+#else
+  constexpr bool debug_sums = false;
+#endif
+  if (!Hpre && gemm_gn_panel_takes(ctx->gemm_gn_fuse, st->lat, debug_sums, w.in_wf != nullptr, lay.gn_parts.empty() ? lay.max_len() : GEMM_GN_PANEL_ROWS + 1, lay.rows, C, C)) {
+    // in_layers' GEMM and this GroupNorm in one launch (gemm_f16_gn_panel_kernel): H is never written. GroupNorm-1 -> A16, the panel kernel A16 -> ATT16 (idle inside a
+    // ResBlock, same shape and halo), the k = 3 convolution reads ATT16. The same bits as the pair below.
+    CHECK(gn(ctx, st, lay, xin, nullptr, w.in_g, w.in_b, nullptr, 1, wk.A16()));
+    CHECK(gemm_gn_panel(ctx, lay, wk.A16(), w.in_wf, w.in_bias, w.out_g, w.out_b, ss, wk.ATT16()));
+    GemmArgs c3 = gemm_base(lay, wk.ATT16(), C, 3, C, w.out_w, C, w.out_bias);
+    c3.Wf = w.out_wf; c3.wreg = gemm_wreg_class(ctx, 4);
+    c3.mode = GEMM_OUT_F32; c3.outF = X; c3.ldo = C; c3.resid = xin;
+    wk.st_x = nullptr;
+    return gemm(ctx, "diff_gemm", c3, lay);
+  }
   if (!Hpre) {
     long long *slot = lat ? st->new_stats_slot() : nullptr;
     CHECK(res_in_layers(ctx, st, lay, wk, xin, w, wk.H(), lat ? wk.st_x : nullptr, slot));
@@ -2516,16 +2577,16 @@ int diff_sample_voices(tts_ctx *ctx, const float *latents, const int32_t *rows, 
 // the session's pinned options for the length of one session call: every option the diffusion stage reads between an admission's setup and a step's last kernel
 struct PinnedOptions {
   float gn_eps;
-  int ggml_lut, attn_f32, attn_proj_f16, proj_dual_b, gemm_wreg, attn_f32_drop, lc_attn_f32, attn_q64, fp16_check, hoist_integrator, diff_graph, latency_mode;
+  int ggml_lut, attn_f32, attn_proj_f16, proj_dual_b, gemm_wreg, attn_f32_drop, lc_attn_f32, attn_q64, fp16_check, hoist_integrator, diff_graph, latency_mode, gemm_gn_fuse;
   bool share_uncond;
   static PinnedOptions of(const tts_ctx *c) {
     return PinnedOptions{c->gn_eps, c->ggml_lut, c->attn_f32, c->attn_proj_f16, c->proj_dual_b, c->gemm_wreg, c->attn_f32_drop, c->lc_attn_f32, c->attn_q64,
-                         c->fp16_check, c->hoist_integrator, c->diff_graph, c->latency_mode, c->share_uncond};
+                         c->fp16_check, c->hoist_integrator, c->diff_graph, c->latency_mode, c->gemm_gn_fuse, c->share_uncond};
   }
   void put(tts_ctx *c) const {
     c->gn_eps = gn_eps; c->ggml_lut = ggml_lut; c->attn_f32 = attn_f32; c->attn_proj_f16 = attn_proj_f16; c->proj_dual_b = proj_dual_b; c->gemm_wreg = gemm_wreg;
     c->attn_f32_drop = attn_f32_drop; c->lc_attn_f32 = lc_attn_f32; c->attn_q64 = attn_q64; c->fp16_check = fp16_check; c->hoist_integrator = hoist_integrator;
-    c->diff_graph = diff_graph; c->latency_mode = latency_mode; c->share_uncond = share_uncond;
+    c->diff_graph = diff_graph; c->latency_mode = latency_mode; c->gemm_gn_fuse = gemm_gn_fuse; c->share_uncond = share_uncond;
   }
 };
 struct DiffSession {

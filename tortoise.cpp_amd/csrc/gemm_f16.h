@@ -27,6 +27,9 @@
 //   gemm_f16_conv3_wreg_kernel the same move for the k = 3 convolution (F32 output with or without residual, 128-row tiles): per-tap fragment-major weight images, waves 1 x 4,
 //                             weight register sets rotating per tap, LDS = a two-slot ring of activation SLABS (34 KB, 4 workgroups per CU), one raw barrier per 64-channel
 //                             chunk. Bit-identical to gemm_f16_conv3_vh_kernel. The dual-B kernel is not ported.
+//   gemm_f16_gn_panel_kernel  the k = 1 in_layers convolution of a ResBlock TOGETHER with the GroupNorm that consumes it: 512 threads own one sequence (<= 896 rows) x 64 output
+//                             channels, so the f32 output never goes to memory (see the kernel). Not planned by gemm_plan: diffusion.hip launches it where
+//                             gemm_gn_panel_takes admits the layout. Bit-identical to gemm_f16_wreg_kernel + gn_reg_kernel<512, 14>.
 // gemm_plan picks between them and chooses h; launch_gemm_f16 launches what it says. Round 3 rewrote the kernels around two measurements
 // (profiles/r3_gemm_tile_tables.txt, profiles/r3_gemm_epilogue.txt):
 //  * tile-height / dispatch-order policies (tables of mixed heights, tallest-first, whole rounds filled exactly) change nothing:
@@ -796,6 +799,178 @@ static __global__ __launch_bounds__(256, 4) void gemm_f16_wreg_kernel(GemmArgs g
 static inline bool gemm_takes_wreg(const GemmArgs &g, int th, int ku) {
   return g.wreg > 0 && g.Wf && g.nseg == 1 && !g.custom_w && th == 8 && ku == 1 && (g.kseg >> 6) >= 2 &&
          (g.mode == GEMM_OUT_F32 || g.mode == GEMM_OUT_QKV || g.mode == GEMM_OUT_QKV_SPLIT);
+}
+
+// GEMM + the GroupNorm that consumes it, in one launch (gemm_f16_gn_panel_kernel; the k = 1 in_layers convolution of a ResBlock, whose f32 output H has no other
+// reader than the GroupNorm in front of the k = 3 convolution). ONE workgroup of 512 threads owns one sequence (at most 896 rows) x 64 output channels = two GroupNorm
+// groups: 8 waves x (7 row blocks x 4 column blocks) of 16 x 16 accumulators, 112 VGPRs per lane. It therefore holds every value a group's statistics are made of: H
+// never goes to memory and no statistics cross workgroups.
+//   K loop   K tiles of 64 = whole 128-byte lines of every activation row (tiles of 32 in a two-slot ring were measured first: every line crossed the L2 -> L1 path twice,
+//            108 us per launch). ONE LDS slot of [896][64] halves (112 KB, gemm_dma_off's image) filled by LDS-DMA; the prefetch distance comes from registers: a wave
+//            copies its 14 fragments of tile t into registers, a second barrier frees the slot and tile t + 1 (14 pieces per wave) is requested before the 56 MFMAs
+//            of tile t are issued. The 8 weight fragments of a tile come from the fragment-major image straight into registers (as gemm_wreg_body): one set, the
+//            fragments of K step ks of tile t + 1 are requested right behind the 28 MFMAs that read step ks of tile t.
+//            Counted vmcnt, raw barriers (the counts are at the step). Rows past the sequence end are clamped to its last row
+//            (duplicates that are never normalised or stored). The fragment reads are inline asm: behind an LDS-DMA in flight hipcc puts a vmcnt(0) in front of
+//            every LDS read it knows of.
+//            Every accumulator starts at 0 and adds the same products in ascending K through the same instruction and operand order as gemm_wreg_body<.., NAT = false>,
+//            then the bias in one f32 add: the bits of gemm_f16_wreg_kernel<GEMM_OUT_F32>'s H.
+//   tail     per 32-channel group: acc + bias -> LDS as [row][32] f32 (the slot is free; 112 KB), then TAIL — the caller's GroupNorm body (diffusion.hip instantiates
+//            gn_reg_kernel<512, 14>'s) — reads its float4s from there. gnp_panel_f4 names the layout: rows of 128 bytes, chunk ^ (row & 7), conflict-free for the
+//            8-lane groups of the writes and for the reads.
+struct GemmGnPanelArgs {
+  const __half *A; int lda;   // activations [rows][lda] fp16 (row 0 of the packed layout)
+  const __half *Wf;           // fragment-major image of W[N][K] (gemm_wfrag_index)
+  int N, K;                   // N % 64 == 0, K % 64 == 0
+  const float *bias;          // [N] or nullptr
+  const int *seq_start, *seq_len; int ns, rows_total; // 1 <= seq_len[s] <= GEMM_GN_PANEL_ROWS
+  // the GroupNorm (gn_reg_kernel's arguments)
+  float eps; const float *gn_g, *gn_b, *ss; int do_silu, lut; __half *y; const int *seq_step; int ss_step_stride;
+};
+static constexpr int GEMM_GN_PANEL_ROWS = 896, GEMM_GN_PANEL_LDS = GEMM_GN_PANEL_ROWS * 128; // one K tile of fp16 = one 32-channel group of f32
+// byte offset of float4 chunk q (channels 4 q ..) of row t in the f32 panel
+__device__ __forceinline__ int gnp_panel_f4(int t, int q) { return t * 128 + ((q ^ (t & 7)) << 4); }
+template <int OFF> __device__ __forceinline__ void gnp_lds_read(half8 &d, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "i"(OFF));
+}
+// The plan rule: does a ResBlock's in_layers GEMM + GroupNorm pair of this layout go through the panel kernel. option: gemm_gn_fuse; stats: latency_mode statistics are
+// in play; debug_sums: a developer build hashes H; has_wf: the fragment-major image exists; max_len / rows: the layout's longest sequence / packed rows.
+static inline int gemm_auto_th(int M, int N);
+static inline bool gemm_gn_panel_takes(int option, bool stats, bool debug_sums, bool has_wf, int max_len, int rows, int N, int K) {
+  return option != 0 && !stats && !debug_sums && has_wf && max_len >= 1 && max_len <= GEMM_GN_PANEL_ROWS && gemm_auto_th(rows, N) == 8 && (N % 64) == 0 && K >= 64 && (K % 64) == 0;
+}
+static inline int gemm_gn_panel_grid(int ns, int N) { return 8 * ((ns * (N >> 6) + 7) / 8); } // padded to whole rounds of the 8 XCDs
+
+template <class TAIL>
+static __global__ __launch_bounds__(512) void gemm_f16_gn_panel_kernel(GemmGnPanelArgs a, TAIL tail) {
+  extern __shared__ __attribute__((aligned(16))) char smem_dyn[];
+  char *smem = smem_dyn;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // workgroup b runs on XCD b % 8: an XCD takes a contiguous range of (sequence, panel) items, sequence-major, so the panels of a sequence fetch its activations through one L2
+  const int np = a.N >> 6, nitems = a.ns * np, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
+  const int i0 = (int)((long long)nitems * xcd >> 3), i1 = (int)((long long)nitems * (xcd + 1) >> 3);
+  if (idx >= i1 - i0) return; // grid padding (whole workgroup, before any barrier)
+  const int item = i0 + idx, s = item / np, n0 = (item - s * np) << 6;
+  const int T = a.seq_len[s], r0 = a.seq_start[s];
+  const int KT = a.K >> 6, fr = lane & 15, fq = lane >> 4; // K tiles of 64: whole 128-byte lines of every activation row
+  // DMA piece p = 8 rows x 128 bytes (gemm_dma_off's image: chunk ^ lds_swz(row)); this wave moves pieces wave + 8 i, i < 14: rows 64 i + rb. The swizzle of those
+  // rows depends on the lane alone
+  const int rb = wave * 8 + (lane >> 3), lda2 = a.lda * 2;
+  const unsigned coloff = (unsigned)(((lane & 7) ^ lds_swz(lane >> 3)) << 4);
+  const char *aseg = (const char *)(a.A + (size_t)r0 * a.lda);
+  const size_t wstride = (size_t)(a.K >> 5) * 512; // halves between the images of two 16-column blocks
+  const __half *wp0 = a.Wf + (size_t)(n0 >> 4) * wstride, *wp1 = wp0 + wstride, *wp2 = wp1 + wstride, *wp3 = wp2 + wstride; // wave-uniform
+  const unsigned wlane = lane * 16;
+  // this wave's fragments: row blocks 7 wave .. 7 wave + 6, lane (fr, fq) = row fr, K chunk 4 ks + fq
+  const unsigned lds0 = (unsigned)(size_t)(lptr_t)smem + wave * 7 * 2048;
+  const unsigned fb0 = lds0 + lds_off(fr, fq), fb1 = lds0 + lds_off(fr, 4 + fq);
+  floatx4 acc[7][4];
+#pragma unroll
+  for (int i = 0; i < 7; i++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+  half8 w[2][4]; // [K step][column block]: ONE set; the fragments of tile t + 1 are requested into a K step's registers right behind the MFMAs that read them
+  auto dma = [&](int t) {
+    const char *ab = aseg + (t << 7);
+    int rbv = rb;
+    asm volatile("" : "+v"(rbv)); // the 14 offsets are recomputed per tile (a handful of VALU operations) instead of living in 14 registers across the loop
+#pragma unroll
+    for (int i = 0; i < 14; i++) {
+      const unsigned off = (unsigned)(min(rbv + 64 * i, T - 1) * lda2) + coloff;
+      __builtin_amdgcn_global_load_lds((gptr_t)(ab + off), (lptr_t)(smem + (wave + 8 * i) * 1024), 16, 0, 0);
+    }
+  };
+  auto wload = [&](int t, auto ks_c) {
+    constexpr int KS = decltype(ks_c)::value;
+    const size_t o = (size_t)t * 1024;
+    wreg_load<KS * 1024>(w[KS][0], wp0 + o, wlane);
+    wreg_load<KS * 1024>(w[KS][1], wp1 + o, wlane);
+    wreg_load<KS * 1024>(w[KS][2], wp2 + o, wlane);
+    wreg_load<KS * 1024>(w[KS][3], wp3 + o, wlane);
+  };
+  // every MFMA issued so far has been issued before anything behind this point (its accumulators are named): the weight registers it read may be reloaded
+  auto pin_acc = [&]() {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      asm volatile("" : "+v"(acc[0][j]), "+v"(acc[1][j]), "+v"(acc[2][j]), "+v"(acc[3][j]), "+v"(acc[4][j]), "+v"(acc[5][j]), "+v"(acc[6][j]));
+  };
+  // vmcnt is one in-order counter. Issue order per step: DMA(t + 1) [14], W(t + 1, 0) [4] .. W(t + 1, 1) [4]. At the top of step t only W(t, 1) may be pending (4);
+  // in front of the second K step everything younger than W(t, 1) may be: the 18 of this step, none in the last. One wait statement per place, in straight-line
+  // code, naming the registers it guards: waits under a branch, or a second register set, made hipcc copy load destinations in front of their wait (seen in the ISA).
+  auto step = [&](int t, auto last_c) {
+    constexpr bool LAST = decltype(last_c)::value;
+    wreg_wait<4>(w[0][0], w[0][1], w[0][2], w[0][3]);
+    __builtin_amdgcn_s_barrier(); // every wave's pieces of tile t have landed
+    asm volatile("" ::: "memory");
+    half8 af[2][7];
+    gnp_lds_read<0 * 2048>(af[0][0], fb0);
+    gnp_lds_read<1 * 2048>(af[0][1], fb0);
+    gnp_lds_read<2 * 2048>(af[0][2], fb0);
+    gnp_lds_read<3 * 2048>(af[0][3], fb0);
+    gnp_lds_read<4 * 2048>(af[0][4], fb0);
+    gnp_lds_read<5 * 2048>(af[0][5], fb0);
+    gnp_lds_read<6 * 2048>(af[0][6], fb0);
+    gnp_lds_read<0 * 2048>(af[1][0], fb1);
+    gnp_lds_read<1 * 2048>(af[1][1], fb1);
+    gnp_lds_read<2 * 2048>(af[1][2], fb1);
+    gnp_lds_read<3 * 2048>(af[1][3], fb1);
+    gnp_lds_read<4 * 2048>(af[1][4], fb1);
+    gnp_lds_read<5 * 2048>(af[1][5], fb1);
+    gnp_lds_read<6 * 2048>(af[1][6], fb1);
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+v"(af[0][0]), "+v"(af[0][1]), "+v"(af[0][2]), "+v"(af[0][3]), "+v"(af[0][4]), "+v"(af[0][5]), "+v"(af[0][6]), "+v"(af[1][0]), "+v"(af[1][1]),
+                   "+v"(af[1][2]), "+v"(af[1][3]), "+v"(af[1][4]), "+v"(af[1][5]), "+v"(af[1][6])
+                 :
+                 : "memory");
+    __builtin_amdgcn_s_barrier(); // every wave holds its fragments of tile t: the slot is free
+    asm volatile("" ::: "memory");
+    if (!LAST) dma(t + 1);
+#pragma unroll
+    for (int i = 0; i < 7; i++)
+#pragma unroll
+      for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[0][j], af[0][i], acc[i][j], 0, 0, 0);
+    if (!LAST) {
+      pin_acc();
+      wload(t + 1, std::integral_constant<int, 0>{});
+    }
+    wreg_wait<LAST ? 0 : 18>(w[1][0], w[1][1], w[1][2], w[1][3]);
+#pragma unroll
+    for (int i = 0; i < 7; i++)
+#pragma unroll
+      for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[1][j], af[1][i], acc[i][j], 0, 0, 0);
+    if (!LAST) {
+      pin_acc();
+      wload(t + 1, std::integral_constant<int, 1>{});
+    }
+  };
+  dma(0);
+  wload(0, std::integral_constant<int, 0>{});
+  wload(0, std::integral_constant<int, 1>{});
+  for (int t = 0; t + 1 < KT; t++) step(t, std::false_type{});
+  step(KT - 1, std::true_type{});
+  // nothing is in flight (the last step waited vmcnt(0)) and every wave has left the slot (its second barrier)
+  const bool hb = a.bias != nullptr;
+  const float *bp = hb ? a.bias : (const float *)a.Wf; // unconditional loads, values selected afterwards (see gemm_epilogue_vh)
+  float4 b4[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) b4[j] = *(const float4 *)(bp + n0 + j * 16 + fq * 4);
+#pragma unroll
+  for (int j = 0; j < 4; j++) b4[j] = hb ? b4[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int gi = 0; gi < 2; gi++) {
+    // (gi == 1: the tail's own barriers lie between its panel reads and these writes)
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+      const int row = (wave * 7 + i) * 16 + fr;
+#pragma unroll
+      for (int jj = 0; jj < 2; jj++) {
+        const int j = gi * 2 + jj;
+        *(float4 *)(smem + gnp_panel_f4(row, jj * 4 + fq)) = make_float4(acc[i][j][0] + b4[j].x, acc[i][j][1] + b4[j].y, acc[i][j][2] + b4[j].z, acc[i][j][3] + b4[j].w);
+      }
+    }
+    __syncthreads();
+    tail(a, s, T, r0, n0 + gi * 32, smem);
+  }
 }
 
 // k = 3 convolution as ONE GEMM with a shared activation slab. The three taps are three row-shifted GEMM
