@@ -1618,8 +1618,8 @@ struct GnPanelTail {
 
 static inline hipError_t launch_gemm_gn_panel(const GemmGnPanelArgs &a, hipStream_t s) {
   static bool raised = false; // more dynamic LDS than a kernel may use by default: asked for once (as gemm_launch)
-  if (!raised) { (void)hipFuncSetAttribute((const void *)gemm_f16_gn_panel_kernel<GnPanelTail>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_GN_PANEL_LDS); raised = true; }
-  gemm_f16_gn_panel_kernel<GnPanelTail><<<gemm_gn_panel_grid(a.ns, a.N), 512, GEMM_GN_PANEL_LDS, s>>>(a, GnPanelTail{});
+  if (!raised) { (void)hipFuncSetAttribute((const void *)gemm_f16_gn_panel_kernel<GnPanelTail>, hipFuncAttributeMaxDynamicSharedMemorySize, GEMM_GN_PANEL_LDS_LAUNCH); raised = true; }
+  gemm_f16_gn_panel_kernel<GnPanelTail><<<gemm_gn_panel_grid(a.ns, a.N), 512, GEMM_GN_PANEL_LDS_LAUNCH, s>>>(a, GnPanelTail{});
   return hipGetLastError();
 }
 

@@ -806,18 +806,25 @@ static inline bool gemm_takes_wreg(const GemmArgs &g, int th, int ku) {
 // groups: 8 waves x (7 row blocks x 4 column blocks) of 16 x 16 accumulators, 112 VGPRs per lane. It therefore holds every value a group's statistics are made of: H
 // never goes to memory and no statistics cross workgroups.
 //   K loop   K tiles of 64 = whole 128-byte lines of every activation row (tiles of 32 in a two-slot ring were measured first: every line crossed the L2 -> L1 path twice,
-//            108 us per launch). ONE LDS slot of [896][64] halves (112 KB, gemm_dma_off's image) filled by LDS-DMA; the prefetch distance comes from registers: a wave
-//            copies its 14 fragments of tile t into registers, a second barrier frees the slot and tile t + 1 (14 pieces per wave) is requested before the 56 MFMAs
-//            of tile t are issued. The 8 weight fragments of a tile come from the fragment-major image straight into registers (as gemm_wreg_body): one set, the
-//            fragments of K step ks of tile t + 1 are requested right behind the 28 MFMAs that read step ks of tile t.
-//            Counted vmcnt, raw barriers (the counts are at the step). Rows past the sequence end are clamped to its last row
-//            (duplicates that are never normalised or stored). The fragment reads are inline asm: behind an LDS-DMA in flight hipcc puts a vmcnt(0) in front of
-//            every LDS read it knows of.
+//            108 us per launch). ONE LDS slot of [896][64] halves (112 KB, gemm_dma_off's image) filled by LDS-DMA, and every wave stages exactly the rows it
+//            multiplies: wave w moves the 14 pieces of rows 112 w .. 112 w + 111 and its MFMAs read row blocks 7 w .. 7 w + 6, so the activation tile needs NO
+//            barrier. The wave's own counted vmcnt orders its fragment reads behind its DMA, and the prefetch distance comes from registers: a wave copies its 14
+//            fragments of tile t into registers, and behind the lgkmcnt(0) that retires those reads it requests its pieces of tile t + 1 into the same rows
+//            (program order inside one wave) before the 56 MFMAs of tile t are issued. (The first form dealt the pieces round-robin, wave w moving pieces w + 8 i,
+//            and walked K behind two workgroup-wide barriers per tile, "tile landed" and "slot free": 96 us per launch against 86.)
+//            The weight tile (8 fragments of 1 KB in the fragment-major image) goes through LDS once per workgroup instead of into the registers of all eight
+//            waves: wave w moves fragment w into a two-slot ring behind the activation slot (2 x 8 KB; 128 KB of LDS in all), lane-linear, so every wave's
+//            fragment reads are conflict-free. That costs ONE raw barrier per K tile, with the wave's 14 activation pieces of tile t + 1 in flight across it, and
+//            takes 56 of the 176 KB a K tile moved through the CU's load path: 84.5 us per launch against 86.7 without it (profiles/gemm_gn_panel_rows_ab.txt).
+//            Counted vmcnt (the counts are at the step). Rows past the sequence end are clamped to its last row (duplicates that are never normalised or stored;
+//            a wave whose rows all lie past the end stages and multiplies nothing else). The fragment reads are inline asm: behind an LDS-DMA in flight hipcc
+//            puts a vmcnt(0) in front of every LDS read it knows of.
 //            Every accumulator starts at 0 and adds the same products in ascending K through the same instruction and operand order as gemm_wreg_body<.., NAT = false>,
 //            then the bias in one f32 add: the bits of gemm_f16_wreg_kernel<GEMM_OUT_F32>'s H.
-//   tail     per 32-channel group: acc + bias -> LDS as [row][32] f32 (the slot is free; 112 KB), then TAIL — the caller's GroupNorm body (diffusion.hip instantiates
-//            gn_reg_kernel<512, 14>'s) — reads its float4s from there. gnp_panel_f4 names the layout: rows of 128 bytes, chunk ^ (row & 7), conflict-free for the
-//            8-lane groups of the writes and for the reads.
+//   tail     per 32-channel group: acc + bias -> LDS as [row][32] f32 (112 KB: a wave's panel rows are the LDS rows it staged, free once its own K loop is over),
+//            one workgroup-wide barrier, then TAIL — the caller's GroupNorm body (diffusion.hip instantiates
+//            gn_reg_kernel<512, 14>'s) — reads its float4s from there; TAIL's own barriers lie between those reads and the second group's writes. gnp_panel_f4
+//            names the layout: rows of 128 bytes, chunk ^ (row & 7), conflict-free for the 8-lane groups of the writes and for the reads.
 struct GemmGnPanelArgs {
   const __half *A; int lda;   // activations [rows][lda] fp16 (row 0 of the packed layout)
   const __half *Wf;           // fragment-major image of W[N][K] (gemm_wfrag_index)
@@ -828,6 +835,7 @@ struct GemmGnPanelArgs {
   float eps; const float *gn_g, *gn_b, *ss; int do_silu, lut; __half *y; const int *seq_step; int ss_step_stride;
 };
 static constexpr int GEMM_GN_PANEL_ROWS = 896, GEMM_GN_PANEL_LDS = GEMM_GN_PANEL_ROWS * 128; // one K tile of fp16 = one 32-channel group of f32
+static constexpr int GEMM_GN_PANEL_WRING = 2 * 8192, GEMM_GN_PANEL_LDS_LAUNCH = GEMM_GN_PANEL_LDS + GEMM_GN_PANEL_WRING; // + two slots of one weight tile [64 columns][64 K]
 // byte offset of float4 chunk q (channels 4 q ..) of row t in the f32 panel
 __device__ __forceinline__ int gnp_panel_f4(int t, int q) { return t * 128 + ((q ^ (t & 7)) << 4); }
 template <int OFF> __device__ __forceinline__ void gnp_lds_read(half8 &d, unsigned addr) {
@@ -853,14 +861,17 @@ static __global__ __launch_bounds__(512) void gemm_f16_gn_panel_kernel(GemmGnPan
   const int item = i0 + idx, s = item / np, n0 = (item - s * np) << 6;
   const int T = a.seq_len[s], r0 = a.seq_start[s];
   const int KT = a.K >> 6, fr = lane & 15, fq = lane >> 4; // K tiles of 64: whole 128-byte lines of every activation row
-  // DMA piece p = 8 rows x 128 bytes (gemm_dma_off's image: chunk ^ lds_swz(row)); this wave moves pieces wave + 8 i, i < 14: rows 64 i + rb. The swizzle of those
-  // rows depends on the lane alone
-  const int rb = wave * 8 + (lane >> 3), lda2 = a.lda * 2;
+  // DMA piece p = 8 rows x 128 bytes (gemm_dma_off's image: chunk ^ lds_swz(row)); this wave moves pieces 14 wave + i, i < 14: rows 112 wave + 8 i + (lane >> 3),
+  // exactly the 7 row blocks its own MFMAs read. The swizzle of those rows depends on the lane alone (112 = 14 x 8)
+  const int rb = wave * 112 + (lane >> 3), lda2 = a.lda * 2;
   const unsigned coloff = (unsigned)(((lane & 7) ^ lds_swz(lane >> 3)) << 4);
   const char *aseg = (const char *)(a.A + (size_t)r0 * a.lda);
   const size_t wstride = (size_t)(a.K >> 5) * 512; // halves between the images of two 16-column blocks
-  const __half *wp0 = a.Wf + (size_t)(n0 >> 4) * wstride, *wp1 = wp0 + wstride, *wp2 = wp1 + wstride, *wp3 = wp2 + wstride; // wave-uniform
-  const unsigned wlane = lane * 16;
+  // the weight tile of a K tile = 8 fragments of 1 KB in the fragment-major image, [K step][column block]; wave w stages fragment w (K step w >> 2, column block
+  // w & 3) for the whole workgroup into a two-slot ring behind the activation slot, lane-linear: every wave reads all 8 with its own lane offset, conflict-free
+  const __half *wsrc = a.Wf + (size_t)((n0 >> 4) + (wave & 3)) * wstride + (wave >> 2) * 512 + lane * 8;
+  char *wring = smem + GEMM_GN_PANEL_LDS;
+  const unsigned wfb = (unsigned)(size_t)(lptr_t)wring + lane * 16;
   // this wave's fragments: row blocks 7 wave .. 7 wave + 6, lane (fr, fq) = row fr, K chunk 4 ks + fq
   const unsigned lds0 = (unsigned)(size_t)(lptr_t)smem + wave * 7 * 2048;
   const unsigned fb0 = lds0 + lds_off(fr, fq), fb1 = lds0 + lds_off(fr, 4 + fq);
@@ -869,40 +880,29 @@ static __global__ __launch_bounds__(512) void gemm_f16_gn_panel_kernel(GemmGnPan
   for (int i = 0; i < 7; i++)
 #pragma unroll
     for (int j = 0; j < 4; j++) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-  half8 w[2][4]; // [K step][column block]: ONE set; the fragments of tile t + 1 are requested into a K step's registers right behind the MFMAs that read them
   auto dma = [&](int t) {
     const char *ab = aseg + (t << 7);
     int rbv = rb;
     asm volatile("" : "+v"(rbv)); // the 14 offsets are recomputed per tile (a handful of VALU operations) instead of living in 14 registers across the loop
 #pragma unroll
     for (int i = 0; i < 14; i++) {
-      const unsigned off = (unsigned)(min(rbv + 64 * i, T - 1) * lda2) + coloff;
-      __builtin_amdgcn_global_load_lds((gptr_t)(ab + off), (lptr_t)(smem + (wave + 8 * i) * 1024), 16, 0, 0);
+      const unsigned off = (unsigned)(min(rbv + 8 * i, T - 1) * lda2) + coloff;
+      __builtin_amdgcn_global_load_lds((gptr_t)(ab + off), (lptr_t)(smem + (wave * 14 + i) * 1024), 16, 0, 0);
     }
   };
-  auto wload = [&](int t, auto ks_c) {
-    constexpr int KS = decltype(ks_c)::value;
-    const size_t o = (size_t)t * 1024;
-    wreg_load<KS * 1024>(w[KS][0], wp0 + o, wlane);
-    wreg_load<KS * 1024>(w[KS][1], wp1 + o, wlane);
-    wreg_load<KS * 1024>(w[KS][2], wp2 + o, wlane);
-    wreg_load<KS * 1024>(w[KS][3], wp3 + o, wlane);
-  };
-  // every MFMA issued so far has been issued before anything behind this point (its accumulators are named): the weight registers it read may be reloaded
-  auto pin_acc = [&]() {
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-      asm volatile("" : "+v"(acc[0][j]), "+v"(acc[1][j]), "+v"(acc[2][j]), "+v"(acc[3][j]), "+v"(acc[4][j]), "+v"(acc[5][j]), "+v"(acc[6][j]));
-  };
-  // vmcnt is one in-order counter. Issue order per step: DMA(t + 1) [14], W(t + 1, 0) [4] .. W(t + 1, 1) [4]. At the top of step t only W(t, 1) may be pending (4);
-  // in front of the second K step everything younger than W(t, 1) may be: the 18 of this step, none in the last. One wait statement per place, in straight-line
-  // code, naming the registers it guards: waits under a branch, or a second register set, made hipcc copy load destinations in front of their wait (seen in the ISA).
+  auto wdma = [&](int t) { __builtin_amdgcn_global_load_lds((gptr_t)(wsrc + (size_t)t * 1024), (lptr_t)(wring + ((t & 1) << 13) + wave * 1024), 16, 0, 0); };
+  // Activations: a wave reads only LDS rows its own DMA wrote, so its own covering vmcnt orders the fragment reads behind the DMA (RAW), and the re-issue of that
+  // DMA behind the lgkmcnt(0) that retires the reads is program order inside one wave (WAR): no barrier. Weights: ONE raw barrier per K tile. Every wave waits for
+  // its own piece of W(t) in front of it, so behind it all 8 pieces have landed (RAW); and every wave retired its reads of W(t - 1) (lgkmcnt(0), step t - 1) in
+  // front of it, so behind it slot (t + 1) & 1 may be refilled (WAR).
+  // vmcnt is one in-order counter. Issue order per step: [activation reads] DMA(t + 1) [14], [barrier] W(t + 1) [1]; the prologue issues DMA(0), W(0). At the top
+  // of step t the queue holds DMA(t) [14], W(t) [1], oldest first: vmcnt(1) leaves only W(t) pending, the wave's 14 pieces of tile t have landed. In front of the
+  // barrier everything younger than W(t) may be pending: the 14 pieces of DMA(t + 1), which cross the barrier in flight; none in the last step. One wait statement
+  // per place, in straight-line code.
   auto step = [&](int t, auto last_c) {
     constexpr bool LAST = decltype(last_c)::value;
-    wreg_wait<4>(w[0][0], w[0][1], w[0][2], w[0][3]);
-    __builtin_amdgcn_s_barrier(); // every wave's pieces of tile t have landed
-    asm volatile("" ::: "memory");
-    half8 af[2][7];
+    asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); // this wave's own pieces of tile t: the only activation rows it reads
+    half8 af[2][7], w[2][4];
     gnp_lds_read<0 * 2048>(af[0][0], fb0);
     gnp_lds_read<1 * 2048>(af[0][1], fb0);
     gnp_lds_read<2 * 2048>(af[0][2], fb0);
@@ -922,33 +922,36 @@ static __global__ __launch_bounds__(512) void gemm_f16_gn_panel_kernel(GemmGnPan
                    "+v"(af[1][2]), "+v"(af[1][3]), "+v"(af[1][4]), "+v"(af[1][5]), "+v"(af[1][6])
                  :
                  : "memory");
-    __builtin_amdgcn_s_barrier(); // every wave holds its fragments of tile t: the slot is free
+    if (!LAST) dma(t + 1); // the wave holds its fragments of tile t: its rows are free
+    if (LAST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's piece of W(t)
+    else asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
+    __builtin_amdgcn_s_barrier(); // every wave's piece of W(t) has landed, and every wave has read W(t - 1)
     asm volatile("" ::: "memory");
-    if (!LAST) dma(t + 1);
+    if (!LAST) wdma(t + 1);
+    const unsigned wf = wfb + ((t & 1) << 13);
+    gnp_lds_read<0 * 1024>(w[0][0], wf);
+    gnp_lds_read<1 * 1024>(w[0][1], wf);
+    gnp_lds_read<2 * 1024>(w[0][2], wf);
+    gnp_lds_read<3 * 1024>(w[0][3], wf);
+    gnp_lds_read<4 * 1024>(w[1][0], wf);
+    gnp_lds_read<5 * 1024>(w[1][1], wf);
+    gnp_lds_read<6 * 1024>(w[1][2], wf);
+    gnp_lds_read<7 * 1024>(w[1][3], wf);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(w[0][0]), "+v"(w[0][1]), "+v"(w[0][2]), "+v"(w[0][3]), "+v"(w[1][0]), "+v"(w[1][1]), "+v"(w[1][2]), "+v"(w[1][3]) : : "memory");
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int i = 0; i < 7; i++)
+    for (int ks = 0; ks < 2; ks++)
 #pragma unroll
-      for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[0][j], af[0][i], acc[i][j], 0, 0, 0);
-    if (!LAST) {
-      pin_acc();
-      wload(t + 1, std::integral_constant<int, 0>{});
-    }
-    wreg_wait<LAST ? 0 : 18>(w[1][0], w[1][1], w[1][2], w[1][3]);
+      for (int i = 0; i < 7; i++)
 #pragma unroll
-    for (int i = 0; i < 7; i++)
-#pragma unroll
-      for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[1][j], af[1][i], acc[i][j], 0, 0, 0);
-    if (!LAST) {
-      pin_acc();
-      wload(t + 1, std::integral_constant<int, 1>{});
-    }
+        for (int j = 0; j < 4; j++) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[ks][j], af[ks][i], acc[i][j], 0, 0, 0);
   };
   dma(0);
-  wload(0, std::integral_constant<int, 0>{});
-  wload(0, std::integral_constant<int, 1>{});
+  wdma(0);
   for (int t = 0; t + 1 < KT; t++) step(t, std::false_type{});
   step(KT - 1, std::true_type{});
-  // nothing is in flight (the last step waited vmcnt(0)) and every wave has left the slot (its second barrier)
+  // nothing of this wave is in flight (its last step waited vmcnt(0)), and the panel rows it writes below are the rows it staged and read itself (the weight ring,
+  // which other waves may still be reading, lies behind the panel): no barrier in front of the writes. Other waves read them only behind the __syncthreads() that follows.
   const bool hb = a.bias != nullptr;
   const float *bp = hb ? a.bias : (const float *)a.Wf; // unconditional loads, values selected afterwards (see gemm_epilogue_vh)
   float4 b4[4];
