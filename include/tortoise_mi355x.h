@@ -722,6 +722,28 @@ int tts_vocoder(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_can
 int tts_vocoder_chunk(tts_ctx *ctx, const float *mel, int mel_frames, const float *noise, int frame0, int n_frames,
                       float *audio_out, int *n_samples_out);
 
+/* ---- BigVGAN vocoder (not in the reference; additions within version 8, no prototype changed) ---------------------------------- */
+/* The vocoder the tortoise forks put in UnivNet's place: NVIDIA's BigVGAN v1 (bigvgan_base_24khz_100band: 512 channels, strides 8 8 2 2;
+ * bigvgan_24khz_100band: 1536 channels, strides 4 4 2 2 2 2), which reads the 100-band, hop-256, 24 kHz log-mel tts_diffusion writes and needs no
+ * noise, so the same mel always gives the same samples. Upstream's source and weights are not available offline: the arithmetic is the one
+ * DESIGN.md states ("What pins the BigVGAN vocoder"), pinned between this library, two float64 restatements and that statement, unpinned against
+ * upstream; how it sounds is unjudged. File: the reference's container format, plain weights (weight-norm folded at conversion), names as
+ * tortoise.cpp_amd/synth_weights.py: bigvgan_tensor_shapes lists them. The configuration is read from the tensor shapes (C0 from
+ * bigvgan.conv_pre.weight, the stages from bigvgan.ups.{i}.0.weight, stride = kernel / 2; at most 6 stages). A missing, unknown or mis-shaped
+ * tensor, or strides whose product is not 256: TTS_ERR_FORMAT. */
+int tts_load_bigvgan(tts_ctx *ctx, const char *path);
+/* Samples per candidate: 256 * mel_frames (no frames are padded). Pure: needs no context and no GPU. */
+int tts_bigvgan_samples(int mel_frames);
+/* mel per candidate [100][T_c] (normalised, as returned by tts_diffusion: tts_vocoder's layout, de-normalised with its constants), candidates back
+ * to back; audio_out per candidate tts_bigvgan_samples(T_c) floats back to back. One launch sequence for the whole ragged batch, one upload, one
+ * download; a candidate's samples do not depend on what else is in the batch. Legal while an AR or a diffusion session is open (the stage owns its
+ * buffers). Every argument is checked before any device work and a refused call changes nothing: TTS_ERR_STATE before tts_load_bigvgan;
+ * TTS_ERR_ARG for a null pointer, n_candidates < 1, frames < 1 or a non-finite mel value; TTS_ERR_LIMIT above 4096 candidates or 4096 frames per
+ * candidate. Profiler families: "hfg_conv" (work = FLOPs), "bvg_act", "bvg_mel", "bvg_post" (work = bytes). */
+int tts_bigvgan(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_candidates, float *audio_out);
+/* out[0] = C0, out[1] = number of stages, out[2 .. 7] = their strides (0 beyond the last). TTS_ERR_STATE before tts_load_bigvgan. */
+int tts_bigvgan_config(tts_ctx *ctx, int32_t out[8]);
+
 /* ---- output -------------------------------------------------------------------------------- */
 /* writeWav (main.cpp:4821-4868): RIFF, fmt 16 B, tag 3 (IEEE float), mono, 32-bit. */
 int tts_write_wav(const char *path, const float *samples, int64_t n, int sample_rate);

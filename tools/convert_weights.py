@@ -30,7 +30,7 @@ sys.path.insert(0, ROOT)
 import tortoise_cpp_amd_loader  # noqa: E402
 
 tortoise_cpp_amd_loader.load()
-from tortoise_cpp_amd.synth_weights import GgmlWriter  # noqa: E402
+from tortoise_cpp_amd.synth_weights import GgmlWriter, bigvgan_filter, bigvgan_tensor_shapes  # noqa: E402
 
 
 def _np(t):
@@ -260,6 +260,42 @@ def convert_cvvp(sd, path):
     return depth
 
 
+def convert_bigvgan(sd, path):
+    """ggml-bigvgan-model.bin for tts_load_bigvgan: NVIDIA BigVGAN v1's generator (bigvgan_base_24khz_100band / bigvgan_24khz_100band; the state dict, or the one
+    under 'generator'), tensors under their state-dict names with the prefix `bigvgan.`. weight_g / weight_v are folded where present. The activations' fixed
+    low-pass buffers (`*.upsample.filter`, `*.downsample.lowpass.filter`) are not stored: each is checked against the closed form the kernels hold
+    (synth_weights.bigvgan_filter) to 1e-6 and dropped. C0 and the strides are read from the shapes; a missing, unknown or mis-shaped tensor is an error: the
+    names and shapes are restated from memory (--list-expected bigvgan), so a real checkpoint that differs must be seen, not mis-read."""
+    sd = fuse_weight_norm(sd["generator"] if "generator" in sd else sd)
+    f = bigvgan_filter()
+    for k in [k for k in sd if k.endswith(".filter")]:
+        v = sd.pop(k).astype(np.float64).reshape(-1)
+        if v.shape != (12,) or np.abs(v - f).max() > 1e-6:
+            raise SystemExit("convert_bigvgan: buffer '%s' is not the 12-tap Kaiser-windowed sinc the kernels hold (largest difference %s)"
+                             % (k, np.abs(v - f).max() if v.shape == (12,) else "shape %s" % list(v.shape)))
+    if "conv_pre.weight" not in sd or sd["conv_pre.weight"].ndim != 3:
+        raise SystemExit("convert_bigvgan: no conv_pre.weight (not a BigVGAN generator?)")
+    c0, rates = sd["conv_pre.weight"].shape[0], []
+    while "ups.%d.0.weight" % len(rates) in sd and len(rates) < 6:
+        rates.append(sd["ups.%d.0.weight" % len(rates)].shape[-1] // 2)
+    if int(np.prod(rates or [0])) != 256 or c0 % (1 << len(rates)):
+        raise SystemExit("convert_bigvgan: %d channels and strides %s: the strides must multiply to 256 (BigVGAN v1, 24 kHz, hop 256)" % (c0, rates))
+    exp = bigvgan_tensor_shapes(c0, tuple(rates))
+    for k in sorted(sd):
+        if "bigvgan." + k not in exp:
+            raise SystemExit("convert_bigvgan: unexpected tensor '%s'" % k)
+    w = GgmlWriter(path)
+    for name, shape in exp.items():
+        k = name[len("bigvgan."):]
+        if k not in sd:
+            raise SystemExit("convert_bigvgan: tensor '%s' is missing" % k)
+        if tuple(sd[k].shape) != tuple(shape):
+            raise SystemExit("convert_bigvgan: tensor '%s' has shape %s, expected %s" % (k, list(sd[k].shape), list(shape)))
+        w.add(name, sd[k])
+    w.close()
+    return c0, tuple(rates)
+
+
 # ---- what each checkpoint is expected to hold (--list-expected) ---------------------------------------------------------------------
 # name -> PyTorch shape as tortoise-tts stores it, for the upstream architecture (or the one given). Written from the loaders' contracts
 # (main.cpp:682-792, 1244-1536, 1808-1923; csrc/extras.hip for the three containers the reference does not have), NOT from a checkpoint:
@@ -366,12 +402,14 @@ def expected_tensors(kind, **arch):
         out["contextual_embedder.1.weight"] = (2048, 1024, 3); out["contextual_embedder.1.bias"] = (2048,)
         for i in range(arch.get("blocks", 5)):
             attn("contextual_embedder.%d" % (2 + i), 2048)
+    elif kind == "bigvgan":  # the generator's state dict after weight-norm folding, without the *.filter buffers; default: the base model
+        out.update({k[len("bigvgan."):]: v for k, v in bigvgan_tensor_shapes(arch.get("c0", 512), arch.get("rates", (8, 8, 2, 2))).items()})
     else:
         raise ValueError(kind)
     return out
 
 
-EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp")
+EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan")
 
 
 def container_shape(kind, name, shape):
@@ -436,6 +474,8 @@ def main():
                                                               "100-band mel -> the diffusion conditioning latent, tts_load_diffusion_conditioning_encoder; not in the reference)")
     ap.add_argument("--clvp", help="clvp2.pth of upstream tortoise-tts -> ggml-clvp-model.bin (candidate re-ranking, tts_load_clvp; not in the reference)")
     ap.add_argument("--cvvp", help="cvvp.pth of upstream tortoise-tts -> ggml-cvvp-model.bin (candidate re-ranking against the voice clips, tts_load_cvvp; not in the reference)")
+    ap.add_argument("--bigvgan", help="NVIDIA BigVGAN v1 generator (bigvgan_base_24khz_100band or bigvgan_24khz_100band: g_*.zip / .pt) -> ggml-bigvgan-model.bin "
+                                      "(the second vocoder, tts_load_bigvgan; not in the reference)")
     ap.add_argument("--out")
     ap.add_argument("--list-expected", nargs="*", metavar="KIND", help="print every tensor name / shape the converter looks for per checkpoint kind (%s; "
                                                                         "default: all, upstream architecture) and exit" % ", ".join(EXPECTED_KINDS))
@@ -491,6 +531,8 @@ def main():
         print("ggml-clvp-model.bin: %d encoder layers" % convert_clvp(load(a.clvp), os.path.join(a.out, "ggml-clvp-model.bin")))
     if a.cvvp:
         print("ggml-cvvp-model.bin: %d encoder layers per side" % convert_cvvp(load(a.cvvp), os.path.join(a.out, "ggml-cvvp-model.bin")))
+    if a.bigvgan:
+        print("ggml-bigvgan-model.bin: %d channels, strides %s" % convert_bigvgan(load(a.bigvgan), os.path.join(a.out, "ggml-bigvgan-model.bin")))
     if a.vocoder:
         checked("vocoder", load(a.vocoder), a.vocoder)
         print("ggml-vocoder-model.bin: %d res stacks" % convert_vocoder(load(a.vocoder), os.path.join(a.out, "ggml-vocoder-model.bin")))

@@ -114,6 +114,8 @@ def lib():
         "tts_load_hifigan": (ci, [vp, C.c_char_p]), "tts_hifigan_samples": (ci, [ci]),
         "tts_hifigan_decode": (ci, [vp, vp, vp, ci, vp, ci, vp, vp]),
         "tts_hifigan_chunk": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp]),
+        "tts_load_bigvgan": (ci, [vp, C.c_char_p]), "tts_bigvgan_samples": (ci, [ci]), "tts_bigvgan": (ci, [vp, vp, vp, ci, vp]),
+        "tts_bigvgan_config": (ci, [vp, vp]),
         "tts_hifigan_stream": (ci, [vp, vp, ci, vp, ci, C.c_uint, ci, vp, vp, vp, vp, vp, vp]), "tts_hifigan_stream_recaptures": (ci, [vp]),
         "tts_host_stream_final_rows": (ci, [vp, ci]),
         "tts_ar_session_open": (ci, [vp, ci, ci, ci, ci, C.c_uint]), "tts_ar_session_admit": (ci, [vp, vp, ci, vp, ci, C.c_uint32, vp]),
@@ -631,6 +633,36 @@ class Engine:
         """Upstream's blend of the two re-rankers, clvp * (1 - cvvp_amount) + cvvp * cvvp_amount; the caller keeps the arg-max. The side whose weight is 0 is not
         evaluated (and its model need not be loaded)."""
         return blend_scores(lambda: self.clvp_score(text_ids, codes_list), lambda: self.cvvp_score(voice_latents, codes_list), cvvp_amount)
+
+    # ---- BigVGAN vocoder (not in the reference): the diffusion stage's mel -> 24 kHz audio, beside vocoder() ----
+    def load_bigvgan(self, path):
+        self._ck(self.L.tts_load_bigvgan(self.h, path.encode()))
+
+    @staticmethod
+    def bigvgan_samples(frames):
+        return lib().tts_bigvgan_samples(frames)
+
+    def bigvgan_config(self):
+        """(C0, strides) of the loaded model, read from its tensor shapes (tts_bigvgan_config)."""
+        out = np.zeros(8, np.int32)
+        self._ck(self.L.tts_bigvgan_config(self.h, _ptr(out)))
+        return int(out[0]), tuple(int(u) for u in out[2:2 + out[1]])
+
+    def bigvgan(self, mels):
+        """mels: list of [100, T_c] (normalised, as diffusion() returns them). Returns a list of float32 waveforms, 256 * T_c samples each
+        (tts_bigvgan: one call, no noise)."""
+        frames = np.array([np.asarray(m).shape[-1] for m in mels], np.int32)
+        mel = np.ascontiguousarray(np.concatenate([np.asarray(m, np.float32).reshape(-1) for m in mels]))
+        if mel.size != 100 * int(frames.sum()):
+            raise TtsError("bigvgan: every mel is [100, T]")
+        ns = [self.bigvgan_samples(int(t)) for t in frames]
+        audio = np.empty(sum(ns), np.float32)
+        self._ck(self.L.tts_bigvgan(self.h, _ptr(mel), _ptr(frames), len(frames), _ptr(audio)))
+        out, off = [], 0
+        for n in ns:
+            out.append(audio[off:off + n].copy())
+            off += n
+        return out
 
     # ---- HiFi-GAN decoder (not in the reference): latents + speaker latent -> 24 kHz audio ----
     def load_hifigan(self, path):

@@ -122,6 +122,7 @@ void tts_destroy(tts_ctx *c) {
   if (c->venc) voice_enc_free(c->venc);
   if (c->dcond) diff_cond_enc_free(c->dcond);
   if (c->hifigan) hifigan_free(c->hifigan);
+  if (c->bigvgan) bigvgan_free(c->bigvgan);
   if (c->afe) afe_free(c->afe);
   if (c->fp16_counts) (void)hipFree(c->fp16_counts);
   delete c->tok;
@@ -365,6 +366,14 @@ int tts_hifigan_chunk(tts_ctx *c, const float *latents, const int32_t *rows, int
   return guarded(c, [&] { return hifigan_chunk(c, latents, rows, n_candidates, voices, n_voices, voice_of_candidate, frame0, n_frames, audio_out); });
 }
 int tts_hifigan_stream_recaptures(const tts_ctx *c) { return c ? c->stream_recaptures : -1; }
+// BigVGAN: the second vocoder (bigvgan.h). Legal while a session is open: it owns its buffers and touches no AR or diffusion state.
+int tts_load_bigvgan(tts_ctx *c, const char *path) { NEED_CTX(c); return guarded(c, [&] { return bigvgan_load(c, path); }); }
+int tts_bigvgan_samples(int mel_frames) { return 256 * mel_frames; }
+int tts_bigvgan(tts_ctx *c, const float *mel, const int32_t *frames, int n_candidates, float *audio_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return bigvgan_run(c, mel, frames, n_candidates, audio_out); });
+}
+int tts_bigvgan_config(tts_ctx *c, int32_t *out8) { NEED_CTX(c); return bigvgan_config(c, out8); }
 int tts_host_stream_final_rows(const int32_t *codes, int k) { return (k < 0 || (k > 0 && !codes)) ? TTS_ERR_ARG : stream_final_rows(codes, k); }
 int tts_ar_layers(const tts_ctx *c) { return c ? ar_layers(c) : 0; }
 int tts_diffusion_layers(const tts_ctx *c) { return c ? diff_layers(c) : 0; }

@@ -55,6 +55,11 @@
 //   (default <models>/ggml-hifigan-model.bin); the diffusion and vocoder models are then neither loaded nor required. --clvp, --split-text and several --voice work
 //   as with the diffusion decoder. Usage errors (exit 1, before a model is loaded): another decoder name; with hifigan any of --steps, --sampler, --ddim-eta,
 //   --cond-free-k, --cond-free, --diffusion-temperature, --diffusion-latent (they configure the decoder that is not run), --devices > 1 or --exchange rccl. --timing 1 names the decoder ("[timing] decoder ...").
+// --vocoder univnet|bigvgan (default univnet = the reference's vocoder): bigvgan sends the diffusion stage's mel through ONE tts_bigvgan call (NVIDIA BigVGAN v1, the
+//   vocoder the tortoise forks put in UnivNet's place: no noise is drawn) and writes 256 samples per frame. --bigvgan-model <file> (default
+//   <models>/ggml-bigvgan-model.bin); the UnivNet model is then neither loaded nor required. --clvp, --cvvp, --split-text, several --voice and every sampler flag
+//   work unchanged. Usage errors (exit 1, before a model is loaded): another vocoder name; bigvgan with --decoder hifigan, --devices > 1 or --exchange rccl.
+//   --timing 1 names the vocoder ("[timing] vocoder ...").
 // --stream (with --decoder hifigan; no value) [--stream-stride N, default 16]: one candidate through tts_hifigan_stream. The samples are appended to the WAV as the
 //   callback receives them, while the autoregressive stage is still sampling, and the header's two sizes are fixed at the end: the file is byte for byte the one the
 //   run without --stream writes. --timing 1 prints when the first samples arrived ("[timing] first audio ..."), from the start of the process and from the start of the
@@ -139,7 +144,7 @@ int main(int argc, char **argv) {
   std::string ar_scope = "last";
   double ar_typ = 0;
   bool have_typ = false;
-  std::string decoder = "diffusion", hifiganPath;
+  std::string decoder = "diffusion", hifiganPath, vocoder = "univnet", bigvganPath;
   bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
@@ -170,6 +175,8 @@ int main(int argc, char **argv) {
     else if (a == "--steps") { steps = std::stoi(argv[i + 1]); have_steps = true; }
     else if (a == "--decoder") decoder = argv[i + 1];
     else if (a == "--hifigan-model") hifiganPath = argv[i + 1];
+    else if (a == "--vocoder") vocoder = argv[i + 1];
+    else if (a == "--bigvgan-model") bigvganPath = argv[i + 1];
     else if (a == "--device") device = std::stoi(argv[i + 1]);
     else if (a == "--codes") fixed_codes = std::stoi(argv[i + 1]); // exactly N sampled codes, stop token masked (synthetic weights never stop)
     else if (a == "--devices") devices = std::stoi(argv[i + 1]);
@@ -216,6 +223,12 @@ int main(int argc, char **argv) {
     const char *bad = have_steps ? "--steps" : have_sampler ? "--sampler" : have_eta ? "--ddim-eta" : have_k ? "--cond-free-k" : have_cond_free ? "--cond-free" : have_diff_temp ? "--diffusion-temperature" : !diffLatentPaths.empty() ? "--diffusion-latent" : nullptr;
     if (bad) { fprintf(stderr, "%s configures the diffusion decoder, which --decoder hifigan does not run\n", bad); return 1; }
     if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--decoder hifigan cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
+  }
+  if (vocoder != "univnet" && vocoder != "bigvgan") { fprintf(stderr, "--vocoder %s: univnet or bigvgan\n", vocoder.c_str()); return 1; }
+  const bool use_bigvgan = vocoder == "bigvgan";
+  if (use_bigvgan) {
+    if (use_hifigan) { fprintf(stderr, "--vocoder bigvgan reads the diffusion decoder's mel: it cannot be combined with --decoder hifigan\n"); return 1; }
+    if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--vocoder bigvgan cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
   }
   if (stream) {
     const char *bad = !use_hifigan ? "--decoder diffusion" : !clvpPath.empty() ? "--clvp" : !cvvpPath.empty() ? "--cvvp" : split_ids > 0 ? "--split-text" : voicePaths.size() > 1 ? "several --voice" :
@@ -431,6 +444,7 @@ int main(int argc, char **argv) {
     if (shard >= 0) fprintf(stderr, "[timing] cond-free %s, diffusion-temperature %g (worker %d/%d)\n", cond_free.c_str(), diff_temp, shard, nshards);
     else fprintf(stderr, "[timing] cond-free %s, diffusion-temperature %g\n", cond_free.c_str(), diff_temp);
     fprintf(stderr, "[timing] decoder %s\n", decoder.c_str());
+    if (!use_hifigan) fprintf(stderr, "[timing] vocoder %s\n", vocoder.c_str());
   }
   if (shard >= 0) {
     tts_set_option(ctx, "rng_shard_offset", (double)(shard * candidates));
@@ -646,11 +660,12 @@ int main(int argc, char **argv) {
   std::string err_diff, err_voc;
   struct Joiner { std::thread t; ~Joiner() { if (t.joinable()) t.join(); } } bg;
   if (hifiganPath.empty()) hifiganPath = modelsDir + "/ggml-hifigan-model.bin";
+  if (bigvganPath.empty()) bigvganPath = modelsDir + "/ggml-bigvgan-model.bin";
   bg.t = std::thread([&]() {
     if (use_hifigan) return; // its one model (56 MB, plain synchronous uploads) is loaded in front of its stage, as the reference loads every model
     rc_diff = tts_load_diffusion(ctx, (modelsDir + "/ggml-diffusion-model.bin").c_str());
     if (rc_diff) { err_diff = tts_last_error(ctx); return; }
-    rc_voc = tts_load_vocoder(ctx, (modelsDir + "/ggml-vocoder-model.bin").c_str());
+    rc_voc = use_bigvgan ? tts_load_bigvgan(ctx, bigvganPath.c_str()) : tts_load_vocoder(ctx, (modelsDir + "/ggml-vocoder-model.bin").c_str());
     if (rc_voc) err_voc = tts_last_error(ctx);
   });
   if (tts_load_ar(ctx, (modelsDir + "/ggml-model.bin").c_str())) return die(ctx, "autoregressive_model_load");
@@ -789,7 +804,7 @@ int main(int argc, char **argv) {
   for (int c = 0; c < B; c++) {
     frames[c] = tts_diffusion_frames(rows[c]);
     mel_total += (size_t)100 * frames[c];
-    audio_total += (size_t)tts_vocoder_samples(frames[c]);
+    audio_total += (size_t)(use_bigvgan ? tts_bigvgan_samples(frames[c]) : tts_vocoder_samples(frames[c]));
   }
   std::vector<float> mel(mel_total);
   audio.assign(audio_total, 0.f);
@@ -803,10 +818,12 @@ int main(int argc, char **argv) {
   mark("diffusion");
   if (tts_diffusion_time_mlp_retries(ctx) > 0) // only ever seen while another process shares the GPU (include/tortoise_mi355x.h)
     fprintf(stderr, "[tortoise] the timestep MLP was re-evaluated %d times before two evaluations agreed\n", tts_diffusion_time_mlp_retries(ctx));
-  if (rc_voc) { fprintf(stderr, "vocoder_model_load: %s\n", err_voc.c_str()); return 1; }
-  if (tts_vocoder(ctx, mel.data(), frames.data(), B, nullptr, noise_mode, audio.data())) return die(ctx, "vocoder");
-  mark("vocoder");
-  for (int c = 0; c < B; c++) nsamp.push_back((size_t)tts_vocoder_samples(frames[c]));
+  if (rc_voc) { fprintf(stderr, "%s: %s\n", use_bigvgan ? "bigvgan_model_load" : "vocoder_model_load", err_voc.c_str()); return 1; }
+  if (use_bigvgan) { // no noise: nothing is drawn from the generator
+    if (tts_bigvgan(ctx, mel.data(), frames.data(), B, audio.data())) return die(ctx, "bigvgan");
+  } else if (tts_vocoder(ctx, mel.data(), frames.data(), B, nullptr, noise_mode, audio.data())) return die(ctx, "vocoder");
+  mark(use_bigvgan ? "bigvgan" : "vocoder");
+  for (int c = 0; c < B; c++) nsamp.push_back((size_t)(use_bigvgan ? tts_bigvgan_samples(frames[c]) : tts_vocoder_samples(frames[c])));
   } // diffusion decoder
   } // !dry
   auto write_one = [&](const float *samples, int64_t ns, int gc, bool is_output) {

@@ -92,6 +92,7 @@ struct CvvpState;
 struct VoiceEncState;
 struct DiffCondEncState;
 struct HifiganState;
+struct BigvganState;
 struct AfeState;
 struct Tokenizer;
 struct SamplerPool;
@@ -137,6 +138,7 @@ struct tts_ctx {
   tts::VoiceEncState *venc = nullptr; // voice-conditioning encoder (extras.hip; not in the reference)
   tts::DiffCondEncState *dcond = nullptr; // diffusion conditioning encoder (extras.hip; not in the reference)
   tts::HifiganState *hifigan = nullptr; // HiFi-GAN decoder: latents -> waveform (hifigan.hip; not in the reference: upstream's api_fast.py path)
+  tts::BigvganState *bigvgan = nullptr; // BigVGAN vocoder: mel -> waveform beside UnivNet (bigvgan.h, part of hifigan.hip's translation unit; not in the reference)
   tts::AfeState *afe = nullptr; // audio front-end: its tables and buffers, made at the first tts_voice_from_audio / tts_audio_mel (audio_frontend.hip)
   tts::Tokenizer *tok = nullptr;
   tts::ArSession *session = nullptr;        // non-null while a session is open: tts_ar_begin*, tts_autoregressive* and tts_hifigan_stream then return TTS_ERR_STATE
@@ -573,6 +575,10 @@ int hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, int 
                    float *audio_out);
 int hifigan_chunk(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices, const int32_t *voice_of_candidate,
                   const int32_t *frame0, const int32_t *n_frames, float *audio_out);
+int bigvgan_load(tts_ctx *ctx, const char *path);
+void bigvgan_free(BigvganState *);
+int bigvgan_config(tts_ctx *ctx, int32_t *out8);
+int bigvgan_run(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_candidates, float *audio_out);
 // Latent rows of a one-candidate utterance that are final after its first k sampled codes (none of them the stop token): the rows whose inputs
 // 8192, c_0 .. c_{k-1} pad_codes will not rewrite, cut where trimmed_latent_rows will cut (tts_hifigan_stream; host_logic.cpp)
 int stream_final_rows(const int32_t *codes, int k);

@@ -482,3 +482,4 @@ int hifigan_chunk(tts_ctx *ctx, const float *latents, const int32_t *rows, int B
 }
 
 } // namespace tts
+#include "bigvgan.h"

@@ -353,6 +353,152 @@ def write_hifigan(path, seed=1240, gain=1.0):
     w.close()
 
 
+BIGVGAN_BASE = (512, (8, 8, 2, 2))               # bigvgan_base_24khz_100band: C0, strides
+BIGVGAN_LARGE = (1536, (4, 4, 2, 2, 2, 2))       # bigvgan_24khz_100band
+MEL_MAX, MEL_MIN = 2.3143386840820312, -11.512925148010254  # tts_vocoder's de-normalisation constants
+
+
+def bigvgan_tensor_shapes(c0=512, rates=(8, 8, 2, 2)):
+    """{name: PyTorch shape} of ggml-bigvgan-model.bin: THE name table of the BigVGAN vocoder (the loader in csrc/bigvgan.h spells the same names and
+    reads c0 and the strides back from these shapes; correct both when an upstream checkpoint shows different ones). Weight-norm is folded and the
+    activations' fixed filter buffers are dropped at conversion time. The ResBlock kernels and dilations are HiFi-GAN's (HIFIGAN_RES_K, HIFIGAN_RES_D)."""
+    assert int(np.prod(rates)) == 256 and c0 % (1 << len(rates)) == 0 and len(rates) <= 6
+    sh = {"bigvgan.conv_pre.weight": (c0, 100, 7), "bigvgan.conv_pre.bias": (c0,)}
+    ch = c0
+    for i, u in enumerate(rates):
+        sh["bigvgan.ups.%d.0.weight" % i] = (ch, ch // 2, 2 * u)  # ConvTranspose1d: [Cin][Cout][K]
+        sh["bigvgan.ups.%d.0.bias" % i] = (ch // 2,)
+        ch //= 2
+        for j, k in enumerate(HIFIGAN_RES_K):
+            p = "bigvgan.resblocks.%d." % (3 * i + j)
+            for n in range(len(HIFIGAN_RES_D)):
+                for cv in ("convs1", "convs2"):
+                    sh[p + "%s.%d.weight" % (cv, n)] = (ch, ch, k)
+                    sh[p + "%s.%d.bias" % (cv, n)] = (ch,)
+            for n in range(6):
+                sh[p + "activations.%d.act.alpha" % n] = (ch,)
+                sh[p + "activations.%d.act.beta" % n] = (ch,)
+    sh["bigvgan.activation_post.act.alpha"] = (ch,)
+    sh["bigvgan.activation_post.act.beta"] = (ch,)
+    sh["bigvgan.conv_post.weight"] = (1, ch, 7)
+    sh["bigvgan.conv_post.bias"] = (1,)
+    return sh
+
+
+def bigvgan_filter(dtype=np.float64):
+    """The 12 taps of the activation's low-pass filter, closed form: kaiser_window(12, beta, periodic=False) * 2 * 0.25 * sinc(2 * 0.25 * t), t = -5.5 .. 5.5,
+    A = 2.285 * 5 * pi * 1.2 + 7.95, beta = 0.1102 * (A - 8.7), divided by its sum."""
+    A = 2.285 * 5 * np.pi * 1.2 + 7.95
+    f = np.kaiser(12, 0.1102 * (A - 8.7)) * 0.5 * np.sinc(0.5 * (np.arange(12) - 5.5))
+    return (f / f.sum()).astype(dtype)
+
+
+def bigvgan_act(x, a, b, dtype=np.float64, f=None):
+    """Activation1d(SnakeBeta, logscale) on rows x [R][C] in index form ("What pins the BigVGAN vocoder"): with cl(i, n) = min(max(i, 0), n - 1),
+    u[m] = 2 sum_j x[cl(j, R)] f[m + 5 - 2 j], s = u + sin^2(exp(a) u) / (exp(b) + 1e-9), y[t] = sum_k f[k] s[cl(2 t + k - 5, 2 R)]."""
+    f = bigvgan_filter(dtype) if f is None else f
+    R = len(x)
+    alpha = np.exp(np.asarray(a, np.float64)).astype(dtype)
+    inv_beta = (1.0 / (np.exp(np.asarray(b, np.float64)) + 1e-9)).astype(dtype)
+    xp = x[np.clip(np.arange(-3, R + 4), 0, R - 1)]  # xp[i] = x[cl(i - 3)]
+    u = np.zeros((2 * R,) + x.shape[1:], dtype)
+    for i in range(6):
+        u[0::2] += xp[5 - i:5 - i + R] * f[1 + 2 * i]  # m = 2 q: x[q + 2 - i] f[1 + 2 i]
+        u[1::2] += xp[6 - i:6 - i + R] * f[2 * i]      # m = 2 q + 1: x[q + 3 - i] f[2 i]
+    u *= dtype(2)
+    s = u + np.sin(alpha * u) ** 2 * inv_beta
+    sp = s[np.clip(np.arange(-5, 2 * R + 6), 0, 2 * R - 1)]  # sp[i] = s[cl(i - 5)]
+    y = np.zeros_like(x)
+    for k in range(12):
+        y += f[k] * sp[k:k + 2 * R:2]
+    return y
+
+
+def _bvg_conv(x, w, b, dil=1):
+    """Conv1d on rows x [R][cin], PyTorch weight [cout][cin][k], zero padding dil (k - 1) / 2"""
+    k, R = w.shape[2], len(x)
+    lo = dil * (k - 1) // 2
+    xp = np.concatenate([np.zeros((lo, x.shape[1]), x.dtype), x, np.zeros((lo, x.shape[1]), x.dtype)])
+    y = np.zeros((R, w.shape[0]), x.dtype) + b
+    for j in range(k):
+        y += xp[j * dil:j * dil + R] @ w[:, :, j].T
+    return y
+
+
+def _bvg_convt(x, w, b, u):
+    """ConvTranspose1d(stride u, kernel 2 u, padding u / 2) on rows x [R][cin], PyTorch weight [cin][cout][2 u]: a scatter, then the crop"""
+    R = len(x)
+    full = np.zeros(((R + 1) * u, w.shape[1]), x.dtype)
+    for k in range(2 * u):
+        full[k:k + R * u:u] += x @ w[:, :, k]
+    return full[u // 2:u // 2 + R * u] + b
+
+
+def bigvgan_forward(tensors, mel, dtype=np.float64, pre_tanh=False):
+    """The generator in index form on one normalised mel [100][T] -> 256 T samples ("What pins the BigVGAN vocoder"); every operand and every
+    operation in `dtype` (float64: a reference; float32: a restatement of the device's arithmetic in another summation order)."""
+    w = {k[len("bigvgan."):]: np.asarray(v).astype(dtype) for k, v in tensors.items()}
+    raw = {k[len("bigvgan."):]: v for k, v in tensors.items()}
+    f = bigvgan_filter(dtype)
+    n_stages = sum(1 for k in w if k.startswith("ups.") and k.endswith(".weight"))
+    m = np.asarray(mel).astype(dtype).T
+    x = (m + dtype(1)) / dtype(2) * dtype(dtype(MEL_MAX) - dtype(MEL_MIN)) + dtype(MEL_MIN)
+    x = _bvg_conv(x, w["conv_pre.weight"], w["conv_pre.bias"])
+    for i in range(n_stages):
+        x = _bvg_convt(x, w["ups.%d.0.weight" % i], w["ups.%d.0.bias" % i], w["ups.%d.0.weight" % i].shape[2] // 2)
+        acc = None
+        for j in range(3):
+            p, r = "resblocks.%d." % (3 * i + j), x
+            for n, d in enumerate(HIFIGAN_RES_D):
+                t = bigvgan_act(r, raw[p + "activations.%d.act.alpha" % (2 * n)], raw[p + "activations.%d.act.beta" % (2 * n)], dtype, f)
+                t = _bvg_conv(t, w[p + "convs1.%d.weight" % n], w[p + "convs1.%d.bias" % n], d)
+                t = bigvgan_act(t, raw[p + "activations.%d.act.alpha" % (2 * n + 1)], raw[p + "activations.%d.act.beta" % (2 * n + 1)], dtype, f)
+                r = r + _bvg_conv(t, w[p + "convs2.%d.weight" % n], w[p + "convs2.%d.bias" % n])
+            acc = r if acc is None else acc + r
+        x = acc / dtype(3)
+    x = bigvgan_act(x, raw["activation_post.act.alpha"], raw["activation_post.act.beta"], dtype, f)
+    y = _bvg_conv(x, w["conv_post.weight"], w["conv_post.bias"])[:, 0]
+    return y if pre_tanh else np.tanh(y)
+
+
+def bigvgan_test_mel(T, seed):
+    """a normalised mel [100][T] in [-1, 1], as tts_diffusion returns one (seeded; the tests' and the recipe's input)"""
+    return np.clip(np.random.default_rng(seed).standard_normal((100, T)) * 0.4, -1, 1).astype(np.float32)
+
+
+def bigvgan_tensors(c0=512, rates=(8, 8, 2, 2), seed=1250, post_peak=1.7):
+    """{name: float32 array}: the synthetic recipe. Convolution weights N(0, g / sqrt(cin k)) with g = 1 for conv_pre, ups (k = the 2 taps an output sees) and
+    convs1 and g = 0.3 for convs2; biases 0.05 N; a, b ~ 0.3 N; conv_post scaled so that the pre-tanh signal peaks at post_peak on bigvgan_test_mel(4, seed)
+    (without it the pre-tanh signal sits near +-20 and tanh hides every error behind it)."""
+    g = _Gen(seed)
+    t = {}
+    for name, shape in bigvgan_tensor_shapes(c0, rates).items():
+        if name.endswith(".bias"):
+            t[name] = g.normal(shape, 0.05)
+        elif name.endswith(".alpha") or name.endswith(".beta"):
+            t[name] = g.normal(shape, 0.3)
+        elif ".ups." in name:
+            t[name] = g.lecun(shape, shape[0] * 2)
+        else:
+            t[name] = g.lecun(shape, shape[1] * shape[2], 0.3 if "convs2" in name else 1.0)
+    peak = np.abs(bigvgan_forward(t, bigvgan_test_mel(4, seed), np.float64, pre_tanh=True)).max()
+    t["bigvgan.conv_post.weight"] = (t["bigvgan.conv_post.weight"] * (post_peak / peak)).astype(np.float32)
+    t["bigvgan.conv_post.bias"] = (t["bigvgan.conv_post.bias"] * (post_peak / peak)).astype(np.float32)
+    return t
+
+
+def write_bigvgan(path, c0=512, rates=(8, 8, 2, 2), seed=1250, post_peak=1.7):
+    """ggml-bigvgan-model.bin: NVIDIA's BigVGAN v1 generator (mel -> 24 kHz waveform; the vocoder the tortoise forks put in UnivNet's place). Upstream's source
+    and weights are not available offline: the arithmetic is the one DESIGN.md ("What pins the BigVGAN vocoder") states, the names are
+    bigvgan_tensor_shapes(c0, rates), the values bigvgan_tensors(...). Returns the tensors."""
+    t = bigvgan_tensors(c0, rates, seed, post_peak)
+    w = GgmlWriter(path)
+    for name, arr in t.items():
+        w.add(name, arr)
+    w.close()
+    return t
+
+
 def write_all(out_dir, ar_layers=30, diff_main=10, diff_tail=3, diff_integ=3, diff_lc=4, seed=1234):
     import os
     os.makedirs(out_dir, exist_ok=True)
