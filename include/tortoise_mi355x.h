@@ -744,6 +744,32 @@ int tts_bigvgan(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_can
 /* out[0] = C0, out[1] = number of stages, out[2 .. 7] = their strides (0 beyond the last). TTS_ERR_STATE before tts_load_bigvgan. */
 int tts_bigvgan_config(tts_ctx *ctx, int32_t out[8]);
 
+/* ---- tortoise-detect: the synthesized-speech classifier (not in the reference; additions within version 8, no prototype changed) -------------- */
+/* The classifier upstream tortoise-tts ships beside the generator (is_this_from_tortoise.py, models/classifier.py: AudioMiniEncoderWithClassifierHead):
+ * "probability that this clip came from Tortoise". A convolutional encoder on the raw 24 kHz waveform (stem 1 -> 32, k 3; five levels of two ResBlocks
+ * (GroupNorm, SiLU, k 5) and a k 5 / stride 4 downsample that doubles the channels; GroupNorm, SiLU, k 1 to 512), four AttentionBlocks (4 heads of 128),
+ * Linear(512 -> 2) on position 0, softmax. Upstream's source and weights are not available offline: the arithmetic is the one INTEGRATION.md and
+ * DESIGN.md ("What pins the classifier") state, pinned between this library and two float64 restatements, unpinned against upstream, unjudged on real
+ * audio. File: the reference's container format, names as tortoise.cpp_amd/synth_weights.py: classifier_tensor_shapes lists them. Base channels, depth,
+ * kernel size, embedding dimension, ResBlocks per level and attention blocks are read from the tensor names and shapes; the downsample factor and the
+ * head count from the 2-element tensor `classifier.config` (missing: 4 and 4). A missing, unknown or mis-shaped tensor, or a head dimension other than
+ * 64 or 128: TTS_ERR_FORMAT. The file is parsed before the device is asked for: a host-only context returns TTS_ERR_FORMAT for a broken file and
+ * TTS_ERR_HIP for a good one. */
+#define TTS_CLS_MAX_SAMPLES 220000 /* the crop: the first 9.17 s at 24 kHz */
+int tts_load_classifier(tts_ctx *ctx, const char *path);
+/* Positions the attention blocks see for a clip of n_samples_24k samples under upstream's configuration (the crop, then five times n -> (n - 1) / 4 + 1).
+ * Pure: needs no context and no GPU. TTS_ERR_ARG below 1. */
+int tts_classifier_positions(int n_samples_24k);
+/* audio: the clips back to back, n_samples[c] mono samples at sample_rate[c] Hz each. A clip is resampled to 24 kHz in one stage (the audio front end's
+ * polyphase resampler; a clip already at 24 kHz reaches the network bit for bit), clamped to [-1, 1] and cropped to its first TTS_CLS_MAX_SAMPLES samples.
+ * prob_out [n_clips]: softmax(logits)[0]; logits_out [n_clips][2] or NULL. One launch sequence for the whole ragged batch, one upload, one download; a
+ * clip's result does not depend on what else is in the batch. Legal while an AR or a diffusion session is open (the stage owns its buffers). Every argument
+ * is checked before any device work and a refused call changes nothing: TTS_ERR_HIP on a host-only context; TTS_ERR_STATE before tts_load_classifier;
+ * TTS_ERR_ARG for a null pointer, n_clips < 1, n_samples < 1, a rate outside the audio front end's range or a non-finite sample; TTS_ERR_LIMIT above 256
+ * clips or 2^26 samples in a clip. Profiler families: "cls_conv" (work = FLOPs), "cls_gn" (work = bytes), "cls_attn" (work = FLOPs). */
+int tts_classify_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, float *prob_out,
+                       float *logits_out);
+
 /* ---- output -------------------------------------------------------------------------------- */
 /* writeWav (main.cpp:4821-4868): RIFF, fmt 16 B, tag 3 (IEEE float), mono, 32-bit. */
 int tts_write_wav(const char *path, const float *samples, int64_t n, int sample_rate);

@@ -30,7 +30,7 @@ sys.path.insert(0, ROOT)
 import tortoise_cpp_amd_loader  # noqa: E402
 
 tortoise_cpp_amd_loader.load()
-from tortoise_cpp_amd.synth_weights import GgmlWriter, bigvgan_filter, bigvgan_tensor_shapes  # noqa: E402
+from tortoise_cpp_amd.synth_weights import GgmlWriter, bigvgan_filter, bigvgan_tensor_shapes, classifier_tensor_shapes  # noqa: E402
 
 
 def _np(t):
@@ -296,6 +296,54 @@ def convert_bigvgan(sd, path):
     return c0, tuple(rates)
 
 
+def classifier_arch(sd):
+    """(b0, depth, K, E, rb, attn) of a classifier state dict, read from its names and shapes as tts_load_classifier reads them"""
+    if "enc.init.weight" not in sd or sd["enc.init.weight"].ndim != 3:
+        raise SystemExit("convert_classifier: no enc.init.weight (not an AudioMiniEncoderWithClassifierHead?)")
+    b0, depth, blocks, i = sd["enc.init.weight"].shape[0], 0, 0, 0
+    while True:
+        if "enc.res.%d.op.weight" % i in sd:
+            depth += 1
+        elif "enc.res.%d.in_layers.2.weight" % i in sd:
+            blocks += 1
+        else:
+            break
+        i += 1
+    if depth < 1 or blocks < 1 or blocks % depth or "enc.final.2.weight" not in sd:
+        raise SystemExit("convert_classifier: %d ResBlocks and %d Downsamples under enc.res, enc.final.2.weight %s" % (blocks, depth, "enc.final.2.weight" in sd))
+    attn = 0
+    while "enc.attn.%d.norm.weight" % attn in sd:
+        attn += 1
+    return dict(b0=b0, depth=depth, K=sd["enc.res.0.in_layers.2.weight"].shape[-1], E=sd["enc.final.2.weight"].shape[0], rb=blocks // depth, attn=attn)
+
+
+def convert_classifier(sd, path, downsample_factor=4, heads=4):
+    """ggml-classifier-model.bin for tts_load_classifier: upstream tortoise-tts' classifier.pth (AudioMiniEncoderWithClassifierHead: enc.init, enc.res.*,
+    enc.final.*, enc.attn.*, head), tensors under their state-dict names with the prefix `classifier.`. What the shapes cannot give, the downsample factor and
+    the number of attention heads, is written into the 2-element tensor `classifier.config` (upstream: 4 and 4). The zero_module convolutions (out_layers.3,
+    proj_out) are written as the checkpoint holds them. A missing, unknown or mis-shaped tensor is an error: the names and shapes are restated from memory
+    (--list-expected classifier), so a real checkpoint that differs must be seen, not mis-read."""
+    sd = {k: v for k, v in sd.items() if not k.endswith("num_batches_tracked")}
+    arch = classifier_arch(sd)
+    if arch["E"] % heads or arch["E"] // heads not in (64, 128):
+        raise SystemExit("convert_classifier: %d channels in %d heads: the head dimension must be 64 or 128" % (arch["E"], heads))
+    exp = classifier_tensor_shapes(F=downsample_factor, H=heads, config=False, **arch)
+    for k in sorted(sd):
+        if "classifier." + k not in exp:
+            raise SystemExit("convert_classifier: unexpected tensor '%s'" % k)
+    w = GgmlWriter(path)
+    for name, shape in exp.items():
+        k = name[len("classifier."):]
+        if k not in sd:
+            raise SystemExit("convert_classifier: tensor '%s' is missing" % k)
+        if tuple(sd[k].shape) != tuple(shape):
+            raise SystemExit("convert_classifier: tensor '%s' has shape %s, expected %s" % (k, list(sd[k].shape), list(shape)))
+        w.add(name, sd[k])
+    w.add("classifier.config", np.array([downsample_factor, heads], np.float32))
+    w.close()
+    return arch["b0"], arch["depth"], arch["E"], heads
+
+
 # ---- what each checkpoint is expected to hold (--list-expected) ---------------------------------------------------------------------
 # name -> PyTorch shape as tortoise-tts stores it, for the upstream architecture (or the one given). Written from the loaders' contracts
 # (main.cpp:682-792, 1244-1536, 1808-1923; csrc/extras.hip for the three containers the reference does not have), NOT from a checkpoint:
@@ -404,12 +452,14 @@ def expected_tensors(kind, **arch):
             attn("contextual_embedder.%d" % (2 + i), 2048)
     elif kind == "bigvgan":  # the generator's state dict after weight-norm folding, without the *.filter buffers; default: the base model
         out.update({k[len("bigvgan."):]: v for k, v in bigvgan_tensor_shapes(arch.get("c0", 512), arch.get("rates", (8, 8, 2, 2))).items()})
+    elif kind == "classifier":  # classifier.pth: AudioMiniEncoderWithClassifierHead's state dict (classifier.config is the converter's, not the checkpoint's)
+        out.update({k[len("classifier."):]: v for k, v in classifier_tensor_shapes(config=False, **arch).items()})
     else:
         raise ValueError(kind)
     return out
 
 
-EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan")
+EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan", "classifier")
 
 
 def container_shape(kind, name, shape):
@@ -476,6 +526,10 @@ def main():
     ap.add_argument("--cvvp", help="cvvp.pth of upstream tortoise-tts -> ggml-cvvp-model.bin (candidate re-ranking against the voice clips, tts_load_cvvp; not in the reference)")
     ap.add_argument("--bigvgan", help="NVIDIA BigVGAN v1 generator (bigvgan_base_24khz_100band or bigvgan_24khz_100band: g_*.zip / .pt) -> ggml-bigvgan-model.bin "
                                       "(the second vocoder, tts_load_bigvgan; not in the reference)")
+    ap.add_argument("--classifier", help="classifier.pth of upstream tortoise-tts (tortoise-detect: AudioMiniEncoderWithClassifierHead) -> ggml-classifier-model.bin "
+                                         "(tts_load_classifier; not in the reference)")
+    ap.add_argument("--classifier-downsample-factor", type=int, default=4, help="with --classifier: the encoder's downsample factor (no shape holds it; upstream: 4)")
+    ap.add_argument("--classifier-heads", type=int, default=4, help="with --classifier: the attention blocks' heads (no shape holds it; upstream: 4)")
     ap.add_argument("--out")
     ap.add_argument("--list-expected", nargs="*", metavar="KIND", help="print every tensor name / shape the converter looks for per checkpoint kind (%s; "
                                                                         "default: all, upstream architecture) and exit" % ", ".join(EXPECTED_KINDS))
@@ -533,6 +587,9 @@ def main():
         print("ggml-cvvp-model.bin: %d encoder layers per side" % convert_cvvp(load(a.cvvp), os.path.join(a.out, "ggml-cvvp-model.bin")))
     if a.bigvgan:
         print("ggml-bigvgan-model.bin: %d channels, strides %s" % convert_bigvgan(load(a.bigvgan), os.path.join(a.out, "ggml-bigvgan-model.bin")))
+    if a.classifier:
+        print("ggml-classifier-model.bin: base %d channels, depth %d, embedding %d, %d heads"
+              % convert_classifier(load(a.classifier), os.path.join(a.out, "ggml-classifier-model.bin"), a.classifier_downsample_factor, a.classifier_heads))
     if a.vocoder:
         checked("vocoder", load(a.vocoder), a.vocoder)
         print("ggml-vocoder-model.bin: %d res stacks" % convert_vocoder(load(a.vocoder), os.path.join(a.out, "ggml-vocoder-model.bin")))

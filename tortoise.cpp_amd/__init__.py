@@ -116,6 +116,7 @@ def lib():
         "tts_hifigan_chunk": (ci, [vp, vp, vp, ci, vp, ci, vp, vp, vp, vp]),
         "tts_load_bigvgan": (ci, [vp, C.c_char_p]), "tts_bigvgan_samples": (ci, [ci]), "tts_bigvgan": (ci, [vp, vp, vp, ci, vp]),
         "tts_bigvgan_config": (ci, [vp, vp]),
+        "tts_load_classifier": (ci, [vp, C.c_char_p]), "tts_classifier_positions": (ci, [ci]), "tts_classify_audio": (ci, [vp, vp, vp, vp, ci, vp, vp]),
         "tts_hifigan_stream": (ci, [vp, vp, ci, vp, ci, C.c_uint, ci, vp, vp, vp, vp, vp, vp]), "tts_hifigan_stream_recaptures": (ci, [vp]),
         "tts_host_stream_final_rows": (ci, [vp, ci]),
         "tts_ar_session_open": (ci, [vp, ci, ci, ci, ci, C.c_uint]), "tts_ar_session_admit": (ci, [vp, vp, ci, vp, ci, C.c_uint32, vp]),
@@ -663,6 +664,27 @@ class Engine:
             out.append(audio[off:off + n].copy())
             off += n
         return out
+
+    # ---- tortoise-detect (not in the reference): upstream's synthesized-speech classifier on the raw waveform ----
+    def load_classifier(self, path):
+        self._ck(self.L.tts_load_classifier(self.h, path.encode()))
+
+    @staticmethod
+    def classifier_positions(n_samples_24k):
+        return lib().tts_classifier_positions(n_samples_24k)
+
+    def classify_audio(self, clips, rates):
+        """clips: list of mono float32 sample arrays, rates: their sample rates (one int for all, or one per clip). Returns (prob [n], logits [n, 2]):
+        prob = softmax(logits)[:, 0], "the probability that the clip is Tortoise's" (tts_classify_audio: one call for the ragged batch)."""
+        rates = [int(rates)] * len(clips) if np.isscalar(rates) else [int(r) for r in rates]
+        if len(rates) != len(clips):
+            raise TtsError("%d rates for %d clips" % (len(rates), len(clips)))
+        n = np.array([len(c) for c in clips], np.int64)
+        a = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1) for c in clips])) if len(clips) else np.zeros(1, np.float32)
+        r = np.array(rates, np.int32)
+        prob, logits = np.empty(len(clips), np.float32), np.empty((len(clips), 2), np.float32)
+        self._ck(self.L.tts_classify_audio(self.h, _ptr(a), _ptr(n), _ptr(r), len(clips), _ptr(prob), _ptr(logits)))
+        return prob, logits
 
     # ---- HiFi-GAN decoder (not in the reference): latents + speaker latent -> 24 kHz audio ----
     def load_hifigan(self, path):

@@ -123,6 +123,7 @@ void tts_destroy(tts_ctx *c) {
   if (c->dcond) diff_cond_enc_free(c->dcond);
   if (c->hifigan) hifigan_free(c->hifigan);
   if (c->bigvgan) bigvgan_free(c->bigvgan);
+  if (c->classifier) classifier_free(c->classifier);
   if (c->afe) afe_free(c->afe);
   if (c->fp16_counts) (void)hipFree(c->fp16_counts);
   delete c->tok;
@@ -374,6 +375,22 @@ int tts_bigvgan(tts_ctx *c, const float *mel, const int32_t *frames, int n_candi
   return guarded(c, [&] { return bigvgan_run(c, mel, frames, n_candidates, audio_out); });
 }
 int tts_bigvgan_config(tts_ctx *c, int32_t *out8) { NEED_CTX(c); return bigvgan_config(c, out8); }
+// tortoise-detect (classifier.h). The loader parses the file before it asks for the device, so a host-only context still tells a broken file (TTS_ERR_FORMAT) from a
+// good one (TTS_ERR_HIP). tts_classify_audio is legal while a session is open: it owns its buffers and touches no AR or diffusion state.
+int tts_load_classifier(tts_ctx *c, const char *path) {
+  if (!c) return TTS_ERR_ARG;
+  return guarded(c, [&] { return classifier_load(c, path); });
+}
+int tts_classifier_positions(int n_samples_24k) { // upstream's configuration: five downsamples by 4 of the cropped clip
+  if (n_samples_24k < 1) return TTS_ERR_ARG;
+  int n = n_samples_24k < TTS_CLS_MAX_SAMPLES ? n_samples_24k : TTS_CLS_MAX_SAMPLES;
+  for (int l = 0; l < 5; l++) n = (n - 1) / 4 + 1;
+  return n;
+}
+int tts_classify_audio(tts_ctx *c, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, float *prob_out, float *logits_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return classifier_run(c, audio, n_samples, sample_rate, n_clips, prob_out, logits_out, afe_resample_to_24k); });
+}
 int tts_host_stream_final_rows(const int32_t *codes, int k) { return (k < 0 || (k > 0 && !codes)) ? TTS_ERR_ARG : stream_final_rows(codes, k); }
 int tts_ar_layers(const tts_ctx *c) { return c ? ar_layers(c) : 0; }
 int tts_diffusion_layers(const tts_ctx *c) { return c ? diff_layers(c) : 0; }

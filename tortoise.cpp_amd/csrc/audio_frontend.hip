@@ -123,6 +123,8 @@ struct AfeState {
   std::map<std::pair<int, int>, std::unique_ptr<AfeTable>> tables; // one per reduced rate pair
   DevBuf fft, span[2], fbw[2], norms; // fft: tw_re[512] | tw_im[512] | win[1024]; [0] 80 bands, [1] 100 bands
   DevBuf audio, a22, a24, meta, count, mel;
+  std::vector<AfeResClip> cls_meta_h; // outlives the call: the copy is asynchronous
+  DevBuf cls_meta; // afe_resample_to_24k's clip records: the classifier's calls share nothing but the tap tables with the voice calls
   bool ready = false;
 };
 void afe_free(AfeState *s) { delete s; }
@@ -358,6 +360,30 @@ int afe_audio_mel(tts_ctx *ctx, const float *audio, int64_t n, int sample_rate, 
   TTS_HIP(ctx, hipMemcpyAsync(mel_out, d, (size_t)bands * frames * 4, hipMemcpyDeviceToHost, ctx->stream));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return frames;
+}
+// The classifier's input stage (classifier.h): every clip through afe_resample_kernel with the tap table of its rate -> 24 000 Hz, ONE stage as upstream's
+// load_audio (the voice calls above go through 22 050 Hz, as upstream's conditioning path does). Only the first out_len samples of a clip are computed. The
+// tables are the front end's (one per reduced rate pair, made at first use); the clip records have a buffer of their own. Launches only: the caller synchronises.
+int afe_resample_to_24k(tts_ctx *ctx, const float *d_src, float *d_dst, const ClsResampleClip *clips, int n_clips) {
+  if (!ctx->afe) ctx->afe = new AfeState();
+  AfeState *st = ctx->afe;
+  std::vector<AfeResClip> &h = st->cls_meta_h;
+  h.resize(n_clips);
+  std::vector<AfeTable *> tabs(n_clips, nullptr);
+  for (int s = 0; s < n_clips; s++) {
+    const int rc = afe_table(ctx, st, clips[s].rate, 24000, &tabs[s]);
+    if (rc) return fail(ctx, rc, "tts_classify_audio: no tap table for %d Hz -> 24000 Hz", clips[s].rate);
+    h[s] = AfeResClip{clips[s].in_off, clips[s].in_len, clips[s].out_off, clips[s].out_len};
+  }
+  TTS_HIP(ctx, st->cls_meta.reserve(h.size() * sizeof(AfeResClip)));
+  TTS_HIP(ctx, hipMemcpyAsync(st->cls_meta.p, h.data(), h.size() * sizeof(AfeResClip), hipMemcpyHostToDevice, ctx->stream));
+  for (int s = 0; s < n_clips; s++) {
+    const AfeResampleGeom &g = tabs[s]->g;
+    ProfScope ps(ctx, "afe_resample", 2.0 * clips[s].out_len * g.taps);
+    afe_resample_kernel<<<dim3((unsigned)((clips[s].out_len + 255) / 256), 1), 256, 0, ctx->stream>>>(d_src, tabs[s]->tab.as<float>(), st->cls_meta.as<AfeResClip>() + s,
+                                                                                                    g.o, g.n, g.width, g.taps, d_dst);
+  }
+  return TTS_OK;
 }
 #endif // TTS_AFE_KERNELS_ONLY
 

@@ -425,3 +425,4 @@ int bigvgan_run(tts_ctx *ctx, const float *mel, const int32_t *frames_in, int B,
 }
 
 } // namespace tts
+#include "classifier.h" // tortoise-detect: the same translation unit, the same convolution kernel

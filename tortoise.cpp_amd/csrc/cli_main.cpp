@@ -81,6 +81,10 @@
 //   with --split-text or several voices, where every chunk is scored against its own voice's clips). Usage errors (exit 1, before a model is loaded): a voice
 //   given as a --voice latent file, which holds no audio (the default voice is one); --devices > 1 or --exchange rccl; --stream; x outside 0 .. 1; 0 < x < 1
 //   without --clvp; --cvvp-amount without --cvvp.
+// --detect a.wav[,b.wav...] --classifier FILE: tortoise-detect, the classifier upstream ships beside the generator (tts_load_classifier / tts_classify_audio; not in
+//   the reference). Prints one line per clip, "detect: <path> <probability that the clip is Tortoise's>", and exits; no other model is loaded or required. On a
+//   synthesis run --classifier FILE scores the WAV the run has just written and prints "classifier: <path> <probability>" on stderr. Usage errors (exit 1,
+//   before a model is loaded): --detect without --classifier, either with --dry-run 1, --classifier with --devices > 1 or --exchange rccl.
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -114,6 +118,32 @@ struct StreamSink {
   }
 };
 
+// the clips of a comma-separated list of WAV files (mono mix, any rate) through ONE tts_classify_audio call; prob: one value per clip
+static int classify_wavs(tts_ctx *ctx, const std::string &list, std::vector<std::string> &paths, std::vector<float> &prob) {
+  std::vector<float> samples;
+  std::vector<int64_t> ns;
+  std::vector<int32_t> rates;
+  for (size_t a = 0; a <= list.size();) {
+    const size_t b = std::min(list.find(',', a), list.size());
+    const std::string path = list.substr(a, b - a);
+    a = b + 1;
+    if (path.empty()) continue;
+    int32_t rate = 0;
+    const int64_t cnt = tts_read_wav(path.c_str(), nullptr, 0, &rate);
+    if (cnt < 1) { fprintf(stderr, "%s: not a readable RIFF WAV with PCM16, PCM24 or float32 samples\n", path.c_str()); return 1; }
+    samples.resize(samples.size() + (size_t)cnt);
+    if (tts_read_wav(path.c_str(), samples.data() + samples.size() - (size_t)cnt, cnt, &rate) != cnt) { fprintf(stderr, "%s: read error\n", path.c_str()); return 1; }
+    paths.push_back(path); ns.push_back(cnt); rates.push_back(rate);
+  }
+  if (paths.empty()) { fprintf(stderr, "--detect: no clip given\n"); return 1; }
+  prob.assign(paths.size(), 0.f);
+  if (tts_classify_audio(ctx, samples.data(), ns.data(), rates.data(), (int)paths.size(), prob.data(), nullptr)) {
+    fprintf(stderr, "classify_audio: %s\n", tts_last_error(ctx));
+    return 1;
+  }
+  return 0;
+}
+
 static int die(tts_ctx *c, const char *what) {
   fprintf(stderr, "%s: %s\n", what, tts_last_error(c));
   return 1; // the reference exit(1)s on load failure (main.cpp:5089, 5634, 6069)
@@ -145,6 +175,7 @@ int main(int argc, char **argv) {
   double ar_typ = 0;
   bool have_typ = false;
   std::string decoder = "diffusion", hifiganPath, vocoder = "univnet", bigvganPath;
+  std::string detectClips, classifierPath;
   bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
@@ -177,6 +208,8 @@ int main(int argc, char **argv) {
     else if (a == "--hifigan-model") hifiganPath = argv[i + 1];
     else if (a == "--vocoder") vocoder = argv[i + 1];
     else if (a == "--bigvgan-model") bigvganPath = argv[i + 1];
+    else if (a == "--detect") detectClips = argv[i + 1];
+    else if (a == "--classifier") classifierPath = argv[i + 1];
     else if (a == "--device") device = std::stoi(argv[i + 1]);
     else if (a == "--codes") fixed_codes = std::stoi(argv[i + 1]); // exactly N sampled codes, stop token masked (synthetic weights never stop)
     else if (a == "--devices") devices = std::stoi(argv[i + 1]);
@@ -229,6 +262,22 @@ int main(int argc, char **argv) {
   if (use_bigvgan) {
     if (use_hifigan) { fprintf(stderr, "--vocoder bigvgan reads the diffusion decoder's mel: it cannot be combined with --decoder hifigan\n"); return 1; }
     if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--vocoder bigvgan cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
+  }
+  if (!detectClips.empty() && classifierPath.empty()) { fprintf(stderr, "--detect needs --classifier <file> (tools/convert_weights.py --classifier)\n"); return 1; }
+  if (!classifierPath.empty()) {
+    if (dry) { fprintf(stderr, "--classifier runs on the device: it cannot be combined with --dry-run 1\n"); return 1; }
+    if (detectClips.empty() && (devices > 1 || exchange == "rccl" || shard >= 0)) { fprintf(stderr, "--classifier cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
+  }
+  if (!detectClips.empty()) { // tortoise-detect: the classifier alone
+    tts_ctx *dctx = tts_create(device);
+    if (!dctx) { fprintf(stderr, "tts_create(%d) failed: no HIP device (this engine has no CPU path)\n", device); return 1; }
+    if (tts_load_classifier(dctx, classifierPath.c_str())) { const int rc = die(dctx, "classifier_model_load"); tts_destroy(dctx); return rc; }
+    std::vector<std::string> paths;
+    std::vector<float> prob;
+    const int rc = classify_wavs(dctx, detectClips, paths, prob);
+    for (size_t c = 0; !rc && c < paths.size(); c++) printf("detect: %s %.9g\n", paths[c].c_str(), (double)prob[c]);
+    tts_destroy(dctx);
+    return rc;
   }
   if (stream) {
     const char *bad = !use_hifigan ? "--decoder diffusion" : !clvpPath.empty() ? "--clvp" : !cvvpPath.empty() ? "--cvvp" : split_ids > 0 ? "--split-text" : voicePaths.size() > 1 ? "several --voice" :
@@ -888,6 +937,14 @@ int main(int argc, char **argv) {
     }
   }
   mark("write");
+  if (!classifierPath.empty()) { // the score of the WAV this run wrote
+    if (tts_load_classifier(ctx, classifierPath.c_str())) return die(ctx, "classifier_model_load");
+    std::vector<std::string> paths;
+    std::vector<float> prob;
+    if (classify_wavs(ctx, outputPath, paths, prob)) return 1;
+    fprintf(stderr, "classifier: %s %.9g\n", paths[0].c_str(), (double)prob[0]);
+    mark("classifier");
+  }
   tts_destroy(ctx);
   mark("tts_destroy");
   return 0;

@@ -93,6 +93,7 @@ struct VoiceEncState;
 struct DiffCondEncState;
 struct HifiganState;
 struct BigvganState;
+struct ClassifierState;
 struct AfeState;
 struct Tokenizer;
 struct SamplerPool;
@@ -139,6 +140,7 @@ struct tts_ctx {
   tts::DiffCondEncState *dcond = nullptr; // diffusion conditioning encoder (extras.hip; not in the reference)
   tts::HifiganState *hifigan = nullptr; // HiFi-GAN decoder: latents -> waveform (hifigan.hip; not in the reference: upstream's api_fast.py path)
   tts::BigvganState *bigvgan = nullptr; // BigVGAN vocoder: mel -> waveform beside UnivNet (bigvgan.h, part of hifigan.hip's translation unit; not in the reference)
+  tts::ClassifierState *classifier = nullptr; // tortoise-detect: waveform -> probability that the clip is synthesized (classifier.h, part of hifigan.hip's translation unit through bigvgan.h; not in the reference)
   tts::AfeState *afe = nullptr; // audio front-end: its tables and buffers, made at the first tts_voice_from_audio / tts_audio_mel (audio_frontend.hip)
   tts::Tokenizer *tok = nullptr;
   tts::ArSession *session = nullptr;        // non-null while a session is open: tts_ar_begin*, tts_autoregressive* and tts_hifigan_stream then return TTS_ERR_STATE
@@ -579,6 +581,17 @@ int bigvgan_load(tts_ctx *ctx, const char *path);
 void bigvgan_free(BigvganState *);
 int bigvgan_config(tts_ctx *ctx, int32_t *out8);
 int bigvgan_run(tts_ctx *ctx, const float *mel, const int32_t *frames, int n_candidates, float *audio_out);
+int classifier_load(tts_ctx *ctx, const char *path);
+void classifier_free(ClassifierState *);
+// One clip of afe_resample_to_24k: src[in_off .. + in_len) at `rate` Hz -> the first out_len samples of the clip at 24 kHz at dst[out_off ..] (both device
+// buffers, on ctx->stream; audio_frontend.hip: afe_resample_kernel with the tap table of rate -> 24 000, one stage as upstream's load_audio)
+struct ClsResampleClip { long long in_off, in_len, out_off, out_len; int rate; };
+int afe_resample_to_24k(tts_ctx *ctx, const float *d_src, float *d_dst, const ClsResampleClip *clips, int n_clips);
+// `resample`: the stage that brings the clips of another rate to 24 kHz. api.cpp hands in afe_resample_to_24k; hifigan.hip's translation unit, which the test
+// harnesses include without the audio front end, names no symbol of audio_frontend.hip.
+using ClsResampleFn = int (*)(tts_ctx *, const float *, float *, const ClsResampleClip *, int);
+int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, float *prob_out, float *logits_out,
+                   ClsResampleFn resample);
 // Latent rows of a one-candidate utterance that are final after its first k sampled codes (none of them the stop token): the rows whose inputs
 // 8192, c_0 .. c_{k-1} pad_codes will not rewrite, cut where trimmed_latent_rows will cut (tts_hifigan_stream; host_logic.cpp)
 int stream_final_rows(const int32_t *codes, int k);

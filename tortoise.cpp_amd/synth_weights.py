@@ -499,6 +499,147 @@ def write_bigvgan(path, c0=512, rates=(8, 8, 2, 2), seed=1250, post_peak=1.7):
     return t
 
 
+CLASSIFIER_UPSTREAM = dict(b0=32, depth=5, K=5, E=512, rb=2, attn=4, F=4, H=4)  # AudioMiniEncoderWithClassifierHead as upstream instantiates it
+CLASSIFIER_MAX_SAMPLES = 220000
+
+
+def classifier_groups(C):
+    """GroupNorm32's group count (upstream's normalization())"""
+    g = 8 if C <= 16 else 16 if C <= 64 else 32
+    while C % g:
+        g //= 2
+    return g
+
+
+def classifier_tensor_shapes(b0=32, depth=5, K=5, E=512, rb=2, attn=4, F=4, H=4, config=True):
+    """{name: PyTorch shape} of a classifier file (tts_load_classifier): upstream's state dict under the prefix `classifier.`, plus the 2-element
+    `classifier.config` = (downsample factor, attention heads), which no shape can give (config=False: left out; the loader then takes 4 and 4). enc.res is
+    the Sequential of depth x (rb ResBlocks, Downsample); restated from memory, unpinned against upstream."""
+    t = {"classifier.enc.init.weight": (b0, 1, 3), "classifier.enc.init.bias": (b0,)}
+    i = 0
+    for l in range(depth):
+        C = b0 << l
+        for _ in range(rb):
+            p = "classifier.enc.res.%d." % i
+            t.update({p + "in_layers.0.weight": (C,), p + "in_layers.0.bias": (C,), p + "in_layers.2.weight": (C, C, K), p + "in_layers.2.bias": (C,),
+                      p + "out_layers.0.weight": (C,), p + "out_layers.0.bias": (C,), p + "out_layers.3.weight": (C, C, K), p + "out_layers.3.bias": (C,)})
+            i += 1
+        t.update({"classifier.enc.res.%d.op.weight" % i: (2 * C, C, 5), "classifier.enc.res.%d.op.bias" % i: (2 * C,)})
+        i += 1
+    Cf = b0 << depth
+    t.update({"classifier.enc.final.0.weight": (Cf,), "classifier.enc.final.0.bias": (Cf,), "classifier.enc.final.2.weight": (E, Cf, 1),
+              "classifier.enc.final.2.bias": (E,)})
+    for a in range(attn):
+        p = "classifier.enc.attn.%d." % a
+        t.update({p + "norm.weight": (E,), p + "norm.bias": (E,), p + "qkv.weight": (3 * E, E, 1), p + "qkv.bias": (3 * E,),
+                  p + "proj_out.weight": (E, E, 1), p + "proj_out.bias": (E,)})
+    t.update({"classifier.head.weight": (2, E), "classifier.head.bias": (2,)})
+    if config:
+        t["classifier.config"] = (2,)
+    return t
+
+
+def classifier_tensors(seed=1260, **cfg):
+    """{name: float32 array}: the synthetic recipe. Convolutions N(0, g / sqrt(cin k)) with g = 1, and g = 0.5 for the ResBlocks' second convolution and the
+    attention's proj_out (upstream initialises both to zero; a trained file does not hold zeros, and zeros would hide those kernels from every test); GroupNorm
+    1 + 0.05 N and 0.05 N; biases 0.05 N; the head N(0, 3 / sqrt(E)) with bias 0.3 N: logits of order 1."""
+    c = dict(CLASSIFIER_UPSTREAM, **cfg)
+    g = _Gen(seed)
+    t = {}
+    for name, shape in classifier_tensor_shapes(**c).items():
+        if name == "classifier.config":
+            t[name] = np.array([c["F"], c["H"]], np.float32)
+        elif name.endswith(".bias") and ("in_layers.0" in name or "out_layers.0" in name or "final.0" in name or ".norm." in name):
+            t[name] = g.beta(shape[0])
+        elif name.endswith(".weight") and len(shape) == 1:
+            t[name] = g.gamma(shape[0])
+        elif name == "classifier.head.bias":
+            t[name] = g.normal(shape, 0.3)
+        elif name.endswith(".bias"):
+            t[name] = g.normal(shape, 0.05)
+        else:
+            t[name] = g.lecun(shape, int(np.prod(shape[1:])), 3.0 if name == "classifier.head.weight" else 0.5 if ("out_layers.3" in name or "proj_out" in name) else 1.0)
+    return t
+
+
+def write_classifier(path, seed=1260, **cfg):
+    """ggml-classifier-model.bin for tts_load_classifier. Upstream's source and weights are not available offline: the names are
+    classifier_tensor_shapes(...), the values classifier_tensors(...). Returns the tensors."""
+    t = classifier_tensors(seed, **cfg)
+    w = GgmlWriter(path)
+    for name, arr in t.items():
+        w.add(name, arr)
+    w.close()
+    return t
+
+
+def classifier_test_wave(n, seed):
+    """a 24 kHz test clip: noise and a tone, a few per cent of it outside [-1, 1] (the clamp has work to do)"""
+    r = np.random.default_rng(seed)
+    return (0.45 * r.standard_normal(n) + 0.3 * np.sin(np.arange(n) * 0.05 + seed)).astype(np.float32)
+
+
+def _cls_conv(h, w, b, stride=1):
+    """Conv1d on rows h [n][cin] with w [cout][cin][k], padding (k - 1) / 2 zeros at the clip's ends: one shifted matrix product per tap, taps ascending"""
+    k = w.shape[2]
+    pad = (k - 1) // 2
+    n = h.shape[0]
+    n_out = (n + 2 * pad - k) // stride + 1
+    hp = np.zeros((n + 2 * pad, h.shape[1]), h.dtype)
+    hp[pad:pad + n] = h
+    out = np.tile(b.astype(h.dtype), (n_out, 1))
+    for j in range(k):
+        out += hp[j:j + stride * (n_out - 1) + 1:stride] @ w[:, :, j].T.astype(h.dtype)
+    return out
+
+
+def _cls_gn_silu(h, gamma, beta, silu=True):
+    n, C = h.shape
+    G = classifier_groups(C)
+    x = h.reshape(n, G, C // G)
+    mean = x.mean(axis=(0, 2), keepdims=True)
+    var = ((x - mean) ** 2).mean(axis=(0, 2), keepdims=True)
+    y = ((x - mean) / np.sqrt(var + h.dtype.type(1e-5))).reshape(n, C) * gamma.astype(h.dtype) + beta.astype(h.dtype)
+    return y / (1 + np.exp(-y)) if silu else y
+
+
+def classifier_forward(tensors, wave, dtype=np.float64, clamp=True):
+    """The index form the kernels implement, in numpy: the logits [2] of one clip already at 24 kHz (clamp, crop, network). dtype=np.float32: the float32
+    restatement of the whole network. clamp=False: a seeded defect for the tests."""
+    t = {k[len("classifier."):]: np.asarray(v) for k, v in tensors.items()}
+    F, H = (int(v) for v in t["config"]) if "config" in t else (4, 4)
+    h = np.asarray(wave, dtype)
+    h = (np.clip(h, -1, 1) if clamp else h)[:CLASSIFIER_MAX_SAMPLES].reshape(-1, 1)
+    h = _cls_conv(h, t["enc.init.weight"], t["enc.init.bias"])
+    i = 0
+    while "enc.res.%d.op.weight" % i in t or "enc.res.%d.in_layers.2.weight" % i in t:
+        p = "enc.res.%d." % i
+        if p + "op.weight" in t:
+            h = _cls_conv(h, t[p + "op.weight"], t[p + "op.bias"], F)
+        else:
+            a = _cls_conv(_cls_gn_silu(h, t[p + "in_layers.0.weight"], t[p + "in_layers.0.bias"]), t[p + "in_layers.2.weight"], t[p + "in_layers.2.bias"])
+            h = h + _cls_conv(_cls_gn_silu(a, t[p + "out_layers.0.weight"], t[p + "out_layers.0.bias"]), t[p + "out_layers.3.weight"], t[p + "out_layers.3.bias"])
+        i += 1
+    h = _cls_conv(_cls_gn_silu(h, t["enc.final.0.weight"], t["enc.final.0.bias"]), t["enc.final.2.weight"], t["enc.final.2.bias"])
+    E = h.shape[1]
+    dh = E // H
+    a = 0
+    while "enc.attn.%d.norm.weight" % a in t:
+        p = "enc.attn.%d." % a
+        y = _cls_gn_silu(h, t[p + "norm.weight"], t[p + "norm.bias"], silu=False)
+        qkv = (y @ t[p + "qkv.weight"][:, :, 0].T.astype(dtype) + t[p + "qkv.bias"].astype(dtype)).reshape(-1, H, 3, dh)  # channel = head * 3 dh + {q, k, v} * dh + d
+        scale = dtype(dh) ** dtype(-0.25)
+        out = np.empty_like(h)
+        for hd in range(H):
+            q, k, v = qkv[:, hd, 0] * scale, qkv[:, hd, 1] * scale, qkv[:, hd, 2]
+            s = q @ k.T
+            s = np.exp(s - s.max(axis=1, keepdims=True))
+            out[:, hd * dh:(hd + 1) * dh] = (s / s.sum(axis=1, keepdims=True)) @ v
+        h = h + out @ t[p + "proj_out.weight"][:, :, 0].T.astype(dtype) + t[p + "proj_out.bias"].astype(dtype)
+        a += 1
+    return h[0] @ t["head.weight"].T.astype(dtype) + t["head.bias"].astype(dtype)
+
+
 def write_all(out_dir, ar_layers=30, diff_main=10, diff_tail=3, diff_integ=3, diff_lc=4, seed=1234):
     import os
     os.makedirs(out_dir, exist_ok=True)
