@@ -770,6 +770,63 @@ int tts_classifier_positions(int n_samples_24k);
 int tts_classify_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, float *prob_out,
                        float *logits_out);
 
+/* ---- the wav2vec2 CTC aligner: redact bracketed prompt text (not in the reference; additions within version 8, no prototype changed) ------------- */
+/* Upstream tortoise-tts lets a prompt carry text that steers the delivery but is not heard: "[I am so sad,] the package never came." The generator speaks
+ * the whole sentence, Wav2VecAlignment.redact cuts the bracketed words out of the waveform. The model is Wav2Vec2ForCTC in the stable-layer-norm
+ * configuration (wav2vec2-large-robust-...): clip normalisation (unbiased variance, eps 1e-7), N convolution layers each followed by LayerNorm and erf
+ * GELU, LayerNorm + Linear, a grouped positional convolution, `depth` pre-norm encoder layers (heads of 64), a final LayerNorm, Linear(D -> V), argmax.
+ * f32 throughout. Upstream's source and weights are not available offline: the arithmetic is the one DESIGN.md ("What pins the aligner") states, pinned
+ * between this library and two float64 restatements, unpinned against upstream; nothing is claimed about alignment quality. File: the reference's
+ * container format, names as tortoise.cpp_amd/synth_weights.py: aligner_tensor_shapes lists them (the HF state dict under `aligner.`). Every size is read
+ * from the tensor shapes; `aligner.config` = {heads, blank id, s_0 .. s_{N-1}} (missing: 16, 0, 5 2 2 2 2 2 2) and `aligner.vocab` [V] = the code point of
+ * every single-character token (the word delimiter as 32, every other token -1) hold integers in the container's one tensor type, f32. TTS_ERR_FORMAT: a
+ * missing, unknown or mis-shaped tensor; a head dimension other than 64; the group-norm (base-model) variant; channel counts the kernels cannot tile - C
+ * and D multiples of 64 up to 1024, the feed-forward width a multiple of 64, D / groups a multiple of 64 with (63 + K) (D / groups + 1) floats inside
+ * 64 KB, k_0 <= 64, s_0 <= 8, k_i <= 16, s_i <= 4, V <= 1024. The file is parsed before the device is asked for: a host-only context returns
+ * TTS_ERR_FORMAT for a broken file and TTS_ERR_HIP for a good one. */
+int tts_load_aligner(tts_ctx *ctx, const char *path);
+/* Frames of a clip of n_samples_16k samples under upstream's configuration (k = 10 3 3 3 3 2 2, s = 5 2 2 2 2 2 2: L <- (L - k) / s + 1). Pure: needs no
+ * context and no GPU. TTS_ERR_ARG for a clip that leaves less than one frame (below 400 samples). */
+int tts_aligner_frames(int n_samples_16k);
+/* The same under the LOADED configuration for a clip at any rate (what tts_aligner_ids writes for it), and the vocabulary: returns V, copies the V code
+ * points when vocab_out is not NULL (cap >= V) and the blank id when blank_out is not NULL. TTS_ERR_STATE before tts_load_aligner. */
+int tts_aligner_clip_frames(tts_ctx *ctx, int64_t n_samples, int sample_rate);
+int tts_aligner_vocab(tts_ctx *ctx, int32_t *vocab_out, int cap, int32_t *blank_out);
+/* audio: the clips back to back, n_samples[c] mono samples at sample_rate[c] Hz. A clip is resampled to 16 kHz in one stage (the audio front end's
+ * polyphase resampler; a clip already at 16 kHz reaches the network bit for bit). ids_out [n_clips][frame_stride]: the argmax of every frame, the lowest
+ * index on a tie; n_frames_out [n_clips]; logits_out NULL or [n_clips][frame_stride][V]. Only the first n_frames_out[c] entries of a clip are written.
+ * One launch sequence for the whole ragged batch; a clip's result does not depend on what else is in the batch; two calls agree bit for bit. Legal
+ * while an AR or a diffusion session is open (the stage owns its buffers). Every argument is checked before any device work and a refused call changes
+ * nothing: TTS_ERR_HIP on a host-only context; TTS_ERR_STATE before tts_load_aligner; TTS_ERR_ARG for a null pointer, n_clips < 1, n_samples < 1, a
+ * rate outside the audio front end's range, a non-finite sample, a clip that leaves less than one frame or more than frame_stride; TTS_ERR_LIMIT above
+ * 256 clips or 2^26 samples in a clip. Profiler families: "w2v_conv" (work = FLOPs), "w2v_attn" (work = FLOPs), "w2v_row" (work = bytes). */
+int tts_aligner_ids(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, int32_t *ids_out,
+                    int32_t *n_frames_out, int frame_stride, float *logits_out);
+/* One sample offset, in samples of the caller's clip, per character (code point) of the UTF-8 `text`: tts_host_ctc_align on the clip's ids. Returns the
+ * number of characters (cap must hold them). TTS_ERR_ARG, "the text does not match the audio", when a character cannot be placed; nothing is written. */
+int tts_align_audio(tts_ctx *ctx, const float *audio, int64_t n_samples, int sample_rate, const char *text, int64_t *offsets_out, int cap);
+/* The clip without the audio of the bracketed parts of `text`: for every kept interval (tts_host_redact_spans) clip[align[first] : align[last]],
+ * concatenated - the last character's own duration is cut, upstream's quirk, kept. Returns the number of samples kept (cap must hold them; out may be
+ * `audio`). A text without '[' returns the clip unchanged; unbalanced or nested brackets: TTS_ERR_ARG. */
+int64_t tts_redact_audio(tts_ctx *ctx, const float *audio, int64_t n_samples, int sample_rate, const char *text, float *out, int64_t cap);
+/* The host rules, pure (no context, no GPU). Text is UTF-8, a character is a code point, lower() folds A .. Z only. Each returns a count or a negative status.
+ * tts_host_ctc_decode: collapse runs of equal ids, drop the blank and every token whose vocab entry is -1, map the rest through vocab; returns the bytes
+ *   written without the terminator (cap includes it).
+ * tts_host_max_alignment(s1, s2): s1 with the characters s2 does not account for replaced by '~'. s1 empty: ""; s2 empty: '~' x len(s1); equal first
+ *   characters: that character + the alignment of the tails; otherwise a = align(s1, s2[1:]), b = '~' + align(s1[1:], s2), a if it has strictly more
+ *   non-'~' characters, else b. A '~' in s1: TTS_ERR_ARG.
+ * tts_host_ctc_align: fixed = max_alignment(lower(text), decode(ids)), step = n_samples / n_frames; character 0 at offset 0; the frames are walked once and
+ *   a frame whose id is the vocabulary id of the next non-'~' character of fixed places it at frame * step; every non-'~' character must be placed when
+ *   the frames end, and fixed must hold one (a text of which the audio holds nothing: upstream would interpolate every offset; here it fails), else
+ *   TTS_ERR_ARG; open offsets are interpolated linearly (integer floor) between the placed neighbours, n_samples behind the end.
+ * tts_host_redact_spans: the text without brackets in clean_out and the kept intervals {first character, last character} of every non-empty
+ *   unbracketed piece in intervals_out [n][2]; returns n. Unbalanced or nested brackets: TTS_ERR_ARG. */
+int tts_host_ctc_decode(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, char *out, int cap);
+int tts_host_max_alignment(const char *s1, const char *s2, char *out, int cap);
+int tts_host_ctc_align(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, const char *text, int64_t n_samples,
+                       int64_t *offsets_out, int cap);
+int tts_host_redact_spans(const char *text, char *clean_out, int cap, int32_t *intervals_out, int cap_intervals);
+
 /* ---- output -------------------------------------------------------------------------------- */
 /* writeWav (main.cpp:4821-4868): RIFF, fmt 16 B, tag 3 (IEEE float), mono, 32-bit. */
 int tts_write_wav(const char *path, const float *samples, int64_t n, int sample_rate);

@@ -30,7 +30,7 @@ sys.path.insert(0, ROOT)
 import tortoise_cpp_amd_loader  # noqa: E402
 
 tortoise_cpp_amd_loader.load()
-from tortoise_cpp_amd.synth_weights import GgmlWriter, bigvgan_filter, bigvgan_tensor_shapes, classifier_tensor_shapes  # noqa: E402
+from tortoise_cpp_amd.synth_weights import GgmlWriter, aligner_tensor_shapes, bigvgan_filter, bigvgan_tensor_shapes, classifier_tensor_shapes  # noqa: E402
 
 
 def _np(t):
@@ -349,6 +349,82 @@ def convert_classifier(sd, path, downsample_factor=4, heads=4):
 # (main.cpp:682-792, 1244-1536, 1808-1923; csrc/extras.hip for the three containers the reference does not have), NOT from a checkpoint:
 # the trained files are not obtainable offline, so the first person who has them gets a name / shape diff instead of a silent mismatch
 # (check_against below; tests/test_convert_weights.py requires this list and the synthetic writers to agree).
+def aligner_vocab_table(vocab, V):
+    """(int32 [V] code points, blank id) from HF's vocab.json {token: id}: a single-character token gives its lower-case code point (the prompt is lowered
+    before it is aligned), the word delimiter '|' is stored as a space (32), every other token - <pad>, <s>, </s>, <unk> - is -1; the CTC blank is <pad>."""
+    if sorted(vocab.values()) != list(range(V)):
+        raise SystemExit("convert_aligner: the vocabulary holds the ids %s, lm_head has %d rows" % (sorted(vocab.values())[:8] + ["..."], V))
+    if "<pad>" not in vocab:
+        raise SystemExit("convert_aligner: the vocabulary has no <pad> token (the CTC blank)")
+    table = np.full(V, -1, np.int32)
+    for tok, i in vocab.items():
+        if tok == "|":
+            table[i] = 32
+        elif len(tok) == 1:
+            table[i] = ord(tok.lower())
+    return table, int(vocab["<pad>"])
+
+
+def convert_aligner(sd, vocab, path, heads=16, strides=None):
+    """ggml-aligner-model.bin for tts_load_aligner: HF's Wav2Vec2ForCTC state dict (stable-layer-norm configuration, e.g. wav2vec2-large-robust-ft-*) with
+    `wav2vec2.` -> `aligner.` and `lm_head.` -> `aligner.lm_head.`. pos_conv_embed's weight-norm pair (weight_g / weight_v, or parametrizations.weight.original0 /
+    original1) is folded into one weight, w = g v / |v| with the norm over output and input channels per tap (weight_norm dim = 2); masked_spec_embed is
+    ignored. `aligner.config` = (heads, blank id, strides) and `aligner.vocab` are the converter's. Names and shapes are checked against
+    aligner_tensor_shapes (--list-expected aligner)."""
+    sd = {k: v for k, v in sd.items() if not k.endswith("masked_spec_embed")}
+    pc = "wav2vec2.encoder.pos_conv_embed.conv."
+    for g_name, v_name in ((pc + "weight_g", pc + "weight_v"), (pc + "parametrizations.weight.original0", pc + "parametrizations.weight.original1")):
+        if g_name in sd and v_name in sd:
+            g, v = sd.pop(g_name).double(), sd.pop(v_name).double()
+            sd[pc + "weight"] = (v * (g / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt())).float()
+    t = {}
+    for k, v in sd.items():
+        if k.startswith("wav2vec2."):
+            t["aligner." + k[len("wav2vec2."):]] = v
+        elif k.startswith("lm_head."):
+            t["aligner." + k] = v
+        else:
+            raise SystemExit("convert_aligner: unexpected tensor '%s'" % k)
+    fe = "aligner.feature_extractor.conv_layers.%d."
+    N = 0
+    while fe % N + "conv.weight" in t:
+        N += 1
+    if N == 0 or "aligner.lm_head.weight" not in t or "aligner.feature_projection.projection.weight" not in t or "aligner.encoder.pos_conv_embed.conv.weight" not in t:
+        raise SystemExit("convert_aligner: no feature_extractor.conv_layers / feature_projection / pos_conv_embed / lm_head (not a Wav2Vec2ForCTC state dict?)")
+    if any(fe % i + "layer_norm.weight" not in t or fe % i + "conv.bias" not in t for i in range(N)):
+        raise SystemExit("convert_aligner: a convolution layer without LayerNorm or bias: the group-norm (base-model) variant is not supported")
+    depth = 0
+    while "aligner.encoder.layers.%d.layer_norm.weight" % depth in t:
+        depth += 1
+    strides = tuple(strides) if strides else (5,) + (2,) * (N - 1)
+    if len(strides) != N:
+        raise SystemExit("convert_aligner: %d strides for %d convolution layers" % (len(strides), N))
+    pw = t["aligner.encoder.pos_conv_embed.conv.weight"]
+    D, V = int(pw.shape[0]), int(t["aligner.lm_head.weight"].shape[0])
+    if D % heads or D // heads != 64:
+        raise SystemExit("convert_aligner: %d channels in %d heads: the head dimension must be 64" % (D, heads))
+    ffw = t.get("aligner.encoder.layers.0.feed_forward.intermediate_dense.weight")
+    table, blank = aligner_vocab_table(vocab, V)
+    arch = dict(N=N, C=int(t[fe % 0 + "conv.weight"].shape[0]), k=tuple(int(t[fe % i + "conv.weight"].shape[2]) for i in range(N)), s=strides, D=D,
+                K=int(pw.shape[2]), G=D // int(pw.shape[1]), depth=depth, FF=int(ffw.shape[0]) if ffw is not None else 4 * D, V=V, H=heads, blank=blank)
+    exp = aligner_tensor_shapes(config=False, **arch)
+    del exp["aligner.vocab"]
+    for k in t:
+        if k not in exp:
+            raise SystemExit("convert_aligner: unexpected tensor '%s'" % k[len("aligner."):])
+    w = GgmlWriter(path)
+    for name, shape in exp.items():
+        if name not in t:
+            raise SystemExit("convert_aligner: tensor '%s' is missing" % name[len("aligner."):])
+        if tuple(t[name].shape) != tuple(shape):
+            raise SystemExit("convert_aligner: tensor '%s' has shape %s, expected %s" % (name[len("aligner."):], list(t[name].shape), list(shape)))
+        w.add(name, t[name].float().numpy())
+    w.add("aligner.config", np.array([heads, blank] + list(strides), np.float32))
+    w.add("aligner.vocab", table.astype(np.float32))
+    w.close()
+    return arch["N"], arch["C"], D, depth, V
+
+
 def expected_tensors(kind, **arch):
     D = 1024
     out = {}
@@ -454,12 +530,14 @@ def expected_tensors(kind, **arch):
         out.update({k[len("bigvgan."):]: v for k, v in bigvgan_tensor_shapes(arch.get("c0", 512), arch.get("rates", (8, 8, 2, 2))).items()})
     elif kind == "classifier":  # classifier.pth: AudioMiniEncoderWithClassifierHead's state dict (classifier.config is the converter's, not the checkpoint's)
         out.update({k[len("classifier."):]: v for k, v in classifier_tensor_shapes(config=False, **arch).items()})
+    elif kind == "aligner":  # Wav2Vec2ForCTC after the weight-norm fold (aligner.config and aligner.vocab are the converter's, not the checkpoint's)
+        out.update({k[len("aligner."):]: v for k, v in aligner_tensor_shapes(config=False, **arch).items() if k != "aligner.vocab"})
     else:
         raise ValueError(kind)
     return out
 
 
-EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan", "classifier")
+EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan", "classifier", "aligner")
 
 
 def container_shape(kind, name, shape):
@@ -530,6 +608,11 @@ def main():
                                          "(tts_load_classifier; not in the reference)")
     ap.add_argument("--classifier-downsample-factor", type=int, default=4, help="with --classifier: the encoder's downsample factor (no shape holds it; upstream: 4)")
     ap.add_argument("--classifier-heads", type=int, default=4, help="with --classifier: the attention blocks' heads (no shape holds it; upstream: 4)")
+    ap.add_argument("--aligner", help="pytorch_model.bin of a Wav2Vec2ForCTC checkpoint in the stable-layer-norm configuration (upstream tortoise-tts loads "
+                                      "jbetker/wav2vec2-large-robust-ft-libritts-voxpopuli) -> ggml-aligner-model.bin (tts_load_aligner; not in the reference)")
+    ap.add_argument("--aligner-vocab", help="with --aligner: the tokenizer's vocab.json {token: id}")
+    ap.add_argument("--aligner-heads", type=int, default=16, help="with --aligner: attention heads (no shape holds it; upstream: 16)")
+    ap.add_argument("--aligner-strides", help="with --aligner: the convolution strides, comma-separated (no shape holds them; upstream: 5,2,2,2,2,2,2)")
     ap.add_argument("--out")
     ap.add_argument("--list-expected", nargs="*", metavar="KIND", help="print every tensor name / shape the converter looks for per checkpoint kind (%s; "
                                                                         "default: all, upstream architecture) and exit" % ", ".join(EXPECTED_KINDS))
@@ -590,6 +673,13 @@ def main():
     if a.classifier:
         print("ggml-classifier-model.bin: base %d channels, depth %d, embedding %d, %d heads"
               % convert_classifier(load(a.classifier), os.path.join(a.out, "ggml-classifier-model.bin"), a.classifier_downsample_factor, a.classifier_heads))
+    if a.aligner:
+        if not a.aligner_vocab:
+            sys.exit("--aligner needs --aligner-vocab (the tokenizer's vocab.json)")
+        import json
+        print("ggml-aligner-model.bin: %d convolution layers of %d channels, dimension %d, %d encoder layers, %d tokens"
+              % convert_aligner(load(a.aligner), json.load(open(a.aligner_vocab)), os.path.join(a.out, "ggml-aligner-model.bin"), a.aligner_heads,
+                                [int(v) for v in a.aligner_strides.split(",")] if a.aligner_strides else None))
     if a.vocoder:
         checked("vocoder", load(a.vocoder), a.vocoder)
         print("ggml-vocoder-model.bin: %d res stacks" % convert_vocoder(load(a.vocoder), os.path.join(a.out, "ggml-vocoder-model.bin")))

@@ -117,6 +117,11 @@ def lib():
         "tts_load_bigvgan": (ci, [vp, C.c_char_p]), "tts_bigvgan_samples": (ci, [ci]), "tts_bigvgan": (ci, [vp, vp, vp, ci, vp]),
         "tts_bigvgan_config": (ci, [vp, vp]),
         "tts_load_classifier": (ci, [vp, C.c_char_p]), "tts_classifier_positions": (ci, [ci]), "tts_classify_audio": (ci, [vp, vp, vp, vp, ci, vp, vp]),
+        "tts_load_aligner": (ci, [vp, C.c_char_p]), "tts_aligner_frames": (ci, [ci]), "tts_aligner_clip_frames": (ci, [vp, C.c_int64, ci]),
+        "tts_aligner_vocab": (ci, [vp, vp, ci, vp]), "tts_aligner_ids": (ci, [vp, vp, vp, vp, ci, vp, vp, ci, vp]),
+        "tts_align_audio": (ci, [vp, vp, C.c_int64, ci, C.c_char_p, vp, ci]), "tts_redact_audio": (C.c_int64, [vp, vp, C.c_int64, ci, C.c_char_p, vp, C.c_int64]),
+        "tts_host_ctc_decode": (ci, [vp, ci, vp, ci, ci, vp, ci]), "tts_host_max_alignment": (ci, [C.c_char_p, C.c_char_p, vp, ci]),
+        "tts_host_ctc_align": (ci, [vp, ci, vp, ci, ci, C.c_char_p, C.c_int64, vp, ci]), "tts_host_redact_spans": (ci, [C.c_char_p, vp, ci, vp, ci]),
         "tts_hifigan_stream": (ci, [vp, vp, ci, vp, ci, C.c_uint, ci, vp, vp, vp, vp, vp, vp]), "tts_hifigan_stream_recaptures": (ci, [vp]),
         "tts_host_stream_final_rows": (ci, [vp, ci]),
         "tts_ar_session_open": (ci, [vp, ci, ci, ci, ci, C.c_uint]), "tts_ar_session_admit": (ci, [vp, vp, ci, vp, ci, C.c_uint32, vp]),
@@ -686,6 +691,52 @@ class Engine:
         self._ck(self.L.tts_classify_audio(self.h, _ptr(a), _ptr(n), _ptr(r), len(clips), _ptr(prob), _ptr(logits)))
         return prob, logits
 
+    # ---- the wav2vec2 CTC aligner (not in the reference): redact bracketed prompt text from the audio ----
+    def load_aligner(self, path):
+        self._ck(self.L.tts_load_aligner(self.h, path.encode()))
+
+    @staticmethod
+    def aligner_frames(n_samples_16k):
+        return lib().tts_aligner_frames(n_samples_16k)
+
+    def aligner_vocab(self):
+        """(vocab int32 [V]: the code point of every token or -1, blank id) of the loaded aligner"""
+        blank = C.c_int32(0)
+        V = self._ck(self.L.tts_aligner_vocab(self.h, None, 0, C.byref(blank)))
+        vocab = np.empty(V, np.int32)
+        self._ck(self.L.tts_aligner_vocab(self.h, _ptr(vocab), V, None))
+        return vocab, blank.value
+
+    def aligner_ids(self, clips, rates, logits=False):
+        """clips: list of mono float32 sample arrays, rates: one int for all or one per clip. Returns a list of int32 id arrays [frames], one per clip
+        (tts_aligner_ids: one call for the ragged batch); logits=True: (ids, list of float32 [frames, V])."""
+        rates = [int(rates)] * len(clips) if np.isscalar(rates) else [int(r) for r in rates]
+        if len(rates) != len(clips) or not clips:
+            raise TtsError("%d rates for %d clips" % (len(rates), len(clips)))
+        n = np.array([len(c) for c in clips], np.int64)
+        stride = max(1, max(self._ck(self.L.tts_aligner_clip_frames(self.h, len(c), r)) for c, r in zip(clips, rates)))
+        a = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1) for c in clips]))
+        r = np.array(rates, np.int32)
+        ids, nf = np.zeros((len(clips), stride), np.int32), np.zeros(len(clips), np.int32)
+        lg = np.zeros((len(clips), stride, self.aligner_vocab()[0].size), np.float32) if logits else None
+        self._ck(self.L.tts_aligner_ids(self.h, _ptr(a), _ptr(n), _ptr(r), len(clips), _ptr(ids), _ptr(nf), stride, None if lg is None else _ptr(lg)))
+        out = [ids[i, :nf[i]].copy() for i in range(len(clips))]
+        return (out, [lg[i, :nf[i]].copy() for i in range(len(clips))]) if logits else out
+
+    def align_audio(self, clip, rate, text):
+        """one sample offset (in samples of `clip`) per character of `text` (tts_align_audio)"""
+        clip = np.ascontiguousarray(clip, np.float32)
+        out = np.zeros(max(1, len(text)), np.int64)
+        n = self._ck(self.L.tts_align_audio(self.h, _ptr(clip), len(clip), int(rate), text.encode(), _ptr(out), len(out)))
+        return out[:n]
+
+    def redact_audio(self, clip, rate, text):
+        """`clip` without the audio of the bracketed parts of `text` (tts_redact_audio)"""
+        clip = np.ascontiguousarray(clip, np.float32)
+        out = np.zeros(max(1, len(clip)), np.float32)
+        n = self._ck(self.L.tts_redact_audio(self.h, _ptr(clip), len(clip), int(rate), text.encode(), _ptr(out), len(out)))
+        return out[:n]
+
     # ---- HiFi-GAN decoder (not in the reference): latents + speaker latent -> 24 kHz audio ----
     def load_hifigan(self, path):
         self._ck(self.L.tts_load_hifigan(self.h, path.encode()))
@@ -1114,6 +1165,49 @@ def host_fp8_e4m3(values):
     L = lib()
     v = np.ascontiguousarray(values, np.float32).reshape(-1)
     return np.array([L.tts_host_fp8_e4m3(float(x)) for x in v], np.uint8).reshape(np.shape(values))
+
+
+# ---- the host rules of alignment and redaction (tts_host_*; no context, no GPU). A failure raises TtsError whose .status is the C status. ----
+def _host_fail(what, rc):
+    e = TtsError("%s failed (status %d)" % (what, rc))
+    e.status = rc
+    raise e
+
+
+def host_ctc_decode(ids, vocab, blank):
+    ids, vocab = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(vocab, np.int32)
+    buf = C.create_string_buffer(4 * len(ids) + 1)
+    rc = lib().tts_host_ctc_decode(_ptr(ids), len(ids), _ptr(vocab), len(vocab), int(blank), buf, len(buf))
+    if rc < 0:
+        _host_fail("tts_host_ctc_decode", rc)
+    return buf.raw[:rc].decode()
+
+
+def host_max_alignment(s1, s2):
+    buf = C.create_string_buffer(4 * len(s1) + 1)
+    rc = lib().tts_host_max_alignment(s1.encode(), s2.encode(), buf, len(buf))
+    if rc < 0:
+        _host_fail("tts_host_max_alignment", rc)
+    return buf.raw[:rc].decode()
+
+
+def host_ctc_align(ids, vocab, blank, text, n_samples):
+    ids, vocab = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(vocab, np.int32)
+    out = np.zeros(max(1, len(text)), np.int64)
+    rc = lib().tts_host_ctc_align(_ptr(ids), len(ids), _ptr(vocab), len(vocab), int(blank), text.encode(), int(n_samples), _ptr(out), len(out))
+    if rc < 0:
+        _host_fail("tts_host_ctc_align", rc)
+    return out[:rc]
+
+
+def host_redact_spans(text):
+    """(text without brackets, [(first char, last char), ...] of the kept pieces)"""
+    buf = C.create_string_buffer(4 * len(text) + 1)
+    iv = np.zeros((len(text) + 1, 2), np.int32)
+    rc = lib().tts_host_redact_spans(text.encode(), buf, len(buf), _ptr(iv), len(iv))
+    if rc < 0:
+        _host_fail("tts_host_redact_spans", rc)
+    return buf.value.decode(), [tuple(int(v) for v in r) for r in iv[:rc]]
 
 
 def read_wav(path):

@@ -124,6 +124,7 @@ void tts_destroy(tts_ctx *c) {
   if (c->hifigan) hifigan_free(c->hifigan);
   if (c->bigvgan) bigvgan_free(c->bigvgan);
   if (c->classifier) classifier_free(c->classifier);
+  if (c->aligner) aligner_free(c->aligner);
   if (c->afe) afe_free(c->afe);
   if (c->fp16_counts) (void)hipFree(c->fp16_counts);
   delete c->tok;
@@ -390,6 +391,92 @@ int tts_classifier_positions(int n_samples_24k) { // upstream's configuration: f
 int tts_classify_audio(tts_ctx *c, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, float *prob_out, float *logits_out) {
   NEED_CTX(c);
   return guarded(c, [&] { return classifier_run(c, audio, n_samples, sample_rate, n_clips, prob_out, logits_out, afe_resample_to_24k); });
+}
+// The wav2vec2 CTC aligner (aligner.h) and what rests on it: tts_align_audio and tts_redact_audio are tts_aligner_ids of one clip followed by the host rules of
+// host_logic.cpp (ctc_align, redact_spans). Every argument is checked, and the text parsed, before any device work; an output is written only on success.
+int tts_load_aligner(tts_ctx *c, const char *path) {
+  if (!c) return TTS_ERR_ARG;
+  return guarded(c, [&] { return aligner_load(c, path); });
+}
+int tts_aligner_frames(int n_samples_16k) { // upstream's configuration: k = 10, 3, 3, 3, 3, 2, 2 and s = 5, 2, 2, 2, 2, 2, 2, no padding
+  static const int k[7] = {10, 3, 3, 3, 3, 2, 2}, s[7] = {5, 2, 2, 2, 2, 2, 2};
+  if (n_samples_16k < 1) return TTS_ERR_ARG;
+  int n = n_samples_16k;
+  for (int i = 0; i < 7; i++) {
+    if (n < k[i]) return TTS_ERR_ARG;
+    n = (n - k[i]) / s[i] + 1;
+  }
+  return n;
+}
+int tts_aligner_clip_frames(tts_ctx *c, int64_t n_samples, int sample_rate) { NEED_CTX(c); return aligner_clip_frames(c, n_samples, sample_rate); }
+int tts_aligner_vocab(tts_ctx *c, int32_t *vocab_out, int cap, int32_t *blank_out) { NEED_CTX(c); return aligner_vocab(c, vocab_out, cap, blank_out); }
+int tts_aligner_ids(tts_ctx *c, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, int32_t *ids_out, int32_t *n_frames_out,
+                    int frame_stride, float *logits_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return aligner_run(c, audio, n_samples, sample_rate, n_clips, ids_out, n_frames_out, frame_stride, logits_out, afe_resample_to_16k); });
+}
+// offsets of the characters of `text` (code points, brackets not interpreted) in the caller's clip
+static int align_clip(tts_ctx *c, const char *fn, const float *audio, int64_t n, int rate, const std::vector<int32_t> &text, std::vector<int64_t> &al) {
+  const int frames = aligner_clip_frames(c, n, rate);
+  if (frames < 0) return frames;
+  std::vector<int32_t> ids((size_t)frames), vocab;
+  int32_t got = 0, blank = 0, rate32 = rate;
+  int rc = aligner_run(c, audio, &n, &rate32, 1, ids.data(), &got, frames, nullptr, afe_resample_to_16k);
+  if (rc) return rc;
+  vocab.resize((size_t)aligner_vocab(c, nullptr, 0, &blank));
+  aligner_vocab(c, vocab.data(), (int)vocab.size(), nullptr);
+  std::string err;
+  rc = ctc_align(ids.data(), got, vocab.data(), (int)vocab.size(), blank, text, n, al, err);
+  return rc < 0 ? fail(c, rc, "%s: %s", fn, err.c_str()) : rc;
+}
+int tts_align_audio(tts_ctx *c, const float *audio, int64_t n_samples, int sample_rate, const char *text, int64_t *offsets_out, int cap) {
+  NEED_CTX(c);
+  return guarded(c, [&]() -> int {
+    if (!c->aligner) return fail(c, TTS_ERR_STATE, "tts_load_aligner not called");
+    std::vector<int32_t> t;
+    if (!audio || !text || !offsets_out || cap < 0) return fail(c, TTS_ERR_ARG, "tts_align_audio: bad argument");
+    if (utf8_decode(text, t) < 0) return fail(c, TTS_ERR_ARG, "tts_align_audio: the text is not UTF-8");
+    if ((int64_t)t.size() > cap) return fail(c, TTS_ERR_ARG, "tts_align_audio: room for %d of %d offsets", cap, (int)t.size());
+    std::vector<int64_t> al;
+    const int rc = align_clip(c, "tts_align_audio", audio, n_samples, sample_rate, t, al);
+    if (rc < 0) return rc;
+    for (size_t i = 0; i < al.size(); i++) offsets_out[i] = al[i];
+    return rc;
+  });
+}
+int64_t tts_redact_audio(tts_ctx *c, const float *audio, int64_t n_samples, int sample_rate, const char *text, float *out, int64_t cap) {
+  NEED_CTX(c);
+  return guarded(c, [&]() -> int {
+    const char *fn = "tts_redact_audio";
+    if (!c->aligner) return fail(c, TTS_ERR_STATE, "tts_load_aligner not called");
+    if (!audio || !text || !out || n_samples < 1) return fail(c, TTS_ERR_ARG, "%s: bad argument", fn);
+    if (n_samples > (1 << 26)) return fail(c, TTS_ERR_LIMIT, "%s: %lld samples, at most 2^26", fn, (long long)n_samples);
+    std::vector<int32_t> t, clean, iv;
+    std::string err;
+    if (utf8_decode(text, t) < 0) return fail(c, TTS_ERR_ARG, "%s: the text is not UTF-8", fn);
+    const int n_iv = redact_spans(t, clean, iv, err);
+    if (n_iv < 0) return fail(c, n_iv, "%s: %s", fn, err.c_str());
+    if (clean.size() == t.size()) { // no bracket: the clip unchanged, as upstream returns it before the model runs
+      if (cap < n_samples) return fail(c, TTS_ERR_ARG, "%s: room for %lld of %lld samples", fn, (long long)cap, (long long)n_samples);
+      for (int64_t i = 0; i < n_samples; i++)
+        if (!std::isfinite(audio[i])) return fail(c, TTS_ERR_ARG, "%s: the audio holds a non-finite sample (element %lld)", fn, (long long)i);
+      memmove(out, audio, (size_t)n_samples * 4);
+      return (int)n_samples;
+    }
+    if (clean.empty()) return 0; // every character is bracketed: nothing is kept
+    std::vector<int64_t> al;
+    const int rc = align_clip(c, fn, audio, n_samples, sample_rate, clean, al);
+    if (rc < 0) return rc;
+    int64_t total = 0;
+    for (int i = 0; i < n_iv; i++) total += std::max<int64_t>(0, al[iv[2 * i + 1]] - al[iv[2 * i]]);
+    if (total > cap) return fail(c, TTS_ERR_ARG, "%s: room for %lld of %lld samples", fn, (long long)cap, (long long)total);
+    int64_t at = 0;
+    for (int i = 0; i < n_iv; i++) { // clip[align[first] : align[last]]: the last character's own duration is cut, as upstream cuts it
+      const int64_t a = al[iv[2 * i]], b = al[iv[2 * i + 1]];
+      if (b > a) { memmove(out + at, audio + a, (size_t)(b - a) * 4); at += b - a; }
+    }
+    return (int)total;
+  });
 }
 int tts_host_stream_final_rows(const int32_t *codes, int k) { return (k < 0 || (k > 0 && !codes)) ? TTS_ERR_ARG : stream_final_rows(codes, k); }
 int tts_ar_layers(const tts_ctx *c) { return c ? ar_layers(c) : 0; }

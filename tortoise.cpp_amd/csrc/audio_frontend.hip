@@ -125,6 +125,8 @@ struct AfeState {
   DevBuf audio, a22, a24, meta, count, mel;
   std::vector<AfeResClip> cls_meta_h; // outlives the call: the copy is asynchronous
   DevBuf cls_meta; // afe_resample_to_24k's clip records: the classifier's calls share nothing but the tap tables with the voice calls
+  std::vector<AfeResClip> w2v_meta_h;
+  DevBuf w2v_meta; // afe_resample_to_16k's clip records (the aligner's calls)
   bool ready = false;
 };
 void afe_free(AfeState *s) { delete s; }
@@ -364,26 +366,35 @@ int afe_audio_mel(tts_ctx *ctx, const float *audio, int64_t n, int sample_rate, 
 // The classifier's input stage (classifier.h): every clip through afe_resample_kernel with the tap table of its rate -> 24 000 Hz, ONE stage as upstream's
 // load_audio (the voice calls above go through 22 050 Hz, as upstream's conditioning path does). Only the first out_len samples of a clip are computed. The
 // tables are the front end's (one per reduced rate pair, made at first use); the clip records have a buffer of their own. Launches only: the caller synchronises.
-int afe_resample_to_24k(tts_ctx *ctx, const float *d_src, float *d_dst, const ClsResampleClip *clips, int n_clips) {
+static int afe_resample_clips(tts_ctx *ctx, const float *d_src, float *d_dst, const ClsResampleClip *clips, int n_clips, int to_rate, const char *who,
+                              std::vector<AfeResClip> AfeState::*meta_h, DevBuf AfeState::*meta_d) {
   if (!ctx->afe) ctx->afe = new AfeState();
   AfeState *st = ctx->afe;
-  std::vector<AfeResClip> &h = st->cls_meta_h;
+  std::vector<AfeResClip> &h = st->*meta_h;
+  DevBuf &meta = st->*meta_d;
   h.resize(n_clips);
   std::vector<AfeTable *> tabs(n_clips, nullptr);
   for (int s = 0; s < n_clips; s++) {
-    const int rc = afe_table(ctx, st, clips[s].rate, 24000, &tabs[s]);
-    if (rc) return fail(ctx, rc, "tts_classify_audio: no tap table for %d Hz -> 24000 Hz", clips[s].rate);
+    const int rc = afe_table(ctx, st, clips[s].rate, to_rate, &tabs[s]);
+    if (rc) return fail(ctx, rc, "%s: no tap table for %d Hz -> %d Hz", who, clips[s].rate, to_rate);
     h[s] = AfeResClip{clips[s].in_off, clips[s].in_len, clips[s].out_off, clips[s].out_len};
   }
-  TTS_HIP(ctx, st->cls_meta.reserve(h.size() * sizeof(AfeResClip)));
-  TTS_HIP(ctx, hipMemcpyAsync(st->cls_meta.p, h.data(), h.size() * sizeof(AfeResClip), hipMemcpyHostToDevice, ctx->stream));
+  TTS_HIP(ctx, meta.reserve(h.size() * sizeof(AfeResClip)));
+  TTS_HIP(ctx, hipMemcpyAsync(meta.p, h.data(), h.size() * sizeof(AfeResClip), hipMemcpyHostToDevice, ctx->stream));
   for (int s = 0; s < n_clips; s++) {
     const AfeResampleGeom &g = tabs[s]->g;
     ProfScope ps(ctx, "afe_resample", 2.0 * clips[s].out_len * g.taps);
-    afe_resample_kernel<<<dim3((unsigned)((clips[s].out_len + 255) / 256), 1), 256, 0, ctx->stream>>>(d_src, tabs[s]->tab.as<float>(), st->cls_meta.as<AfeResClip>() + s,
+    afe_resample_kernel<<<dim3((unsigned)((clips[s].out_len + 255) / 256), 1), 256, 0, ctx->stream>>>(d_src, tabs[s]->tab.as<float>(), meta.as<AfeResClip>() + s,
                                                                                                     g.o, g.n, g.width, g.taps, d_dst);
   }
   return TTS_OK;
+}
+int afe_resample_to_24k(tts_ctx *ctx, const float *d_src, float *d_dst, const ClsResampleClip *clips, int n_clips) {
+  return afe_resample_clips(ctx, d_src, d_dst, clips, n_clips, 24000, "tts_classify_audio", &AfeState::cls_meta_h, &AfeState::cls_meta);
+}
+// The aligner's input stage (aligner.h): the same kernel and tables, to 16 000 Hz, one stage; clip records of its own.
+int afe_resample_to_16k(tts_ctx *ctx, const float *d_src, float *d_dst, const ClsResampleClip *clips, int n_clips) {
+  return afe_resample_clips(ctx, d_src, d_dst, clips, n_clips, 16000, "tts_aligner_ids", &AfeState::w2v_meta_h, &AfeState::w2v_meta);
 }
 #endif // TTS_AFE_KERNELS_ONLY
 

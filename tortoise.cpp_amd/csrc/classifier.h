@@ -643,3 +643,4 @@ int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, c
 }
 
 } // namespace tts
+#include "aligner.h" // the wav2vec2 CTC aligner: the same translation unit, the classifier's strided convolution and attention

@@ -85,6 +85,12 @@
 //   the reference). Prints one line per clip, "detect: <path> <probability that the clip is Tortoise's>", and exits; no other model is loaded or required. On a
 //   synthesis run --classifier FILE scores the WAV the run has just written and prints "classifier: <path> <probability>" on stderr. Usage errors (exit 1,
 //   before a model is loaded): --detect without --classifier, either with --dry-run 1, --classifier with --devices > 1 or --exchange rccl.
+// --aligner FILE: redact bracketed prompt text, as upstream's Wav2VecAlignment.redact does (tts_load_aligner / tts_redact_audio; not in the reference). In
+//   "[I am so sad,] the package never came." the bracketed words steer the delivery but are not heard: with the flag '[' and ']' are removed from the message
+//   before it is tokenised (the words are spoken), and the audio of the bracketed parts is cut out of the chosen candidate before --output is written. A message
+//   without brackets, or a run without --aligner (brackets or not), writes the bytes it wrote before. A failed alignment ("the text does not match the audio")
+//   exits 1 and writes no WAV. Usage errors (exit 1, before a model is loaded), for --aligner with a bracketed message only: --split-text, several voices,
+//   --stream, --devices > 1 or --exchange rccl, --dry-run 1; unbalanced or nested brackets.
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -175,7 +181,7 @@ int main(int argc, char **argv) {
   double ar_typ = 0;
   bool have_typ = false;
   std::string decoder = "diffusion", hifiganPath, vocoder = "univnet", bigvganPath;
-  std::string detectClips, classifierPath;
+  std::string detectClips, classifierPath, alignerPath;
   bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
@@ -210,6 +216,7 @@ int main(int argc, char **argv) {
     else if (a == "--bigvgan-model") bigvganPath = argv[i + 1];
     else if (a == "--detect") detectClips = argv[i + 1];
     else if (a == "--classifier") classifierPath = argv[i + 1];
+    else if (a == "--aligner") alignerPath = argv[i + 1];
     else if (a == "--device") device = std::stoi(argv[i + 1]);
     else if (a == "--codes") fixed_codes = std::stoi(argv[i + 1]); // exactly N sampled codes, stop token masked (synthetic weights never stop)
     else if (a == "--devices") devices = std::stoi(argv[i + 1]);
@@ -278,6 +285,23 @@ int main(int argc, char **argv) {
     for (size_t c = 0; !rc && c < paths.size(); c++) printf("detect: %s %.9g\n", paths[c].c_str(), (double)prob[c]);
     tts_destroy(dctx);
     return rc;
+  }
+  // --aligner with a bracketed message: the brackets leave the prompt, the text they hold leaves the audio
+  const bool redact = !alignerPath.empty() && message.find_first_of("[]") != std::string::npos;
+  const std::string promptText = message;
+  if (redact) {
+    if (split_ids > 0) { fprintf(stderr, "--aligner with bracketed text cannot be combined with --split-text\n"); return 1; }
+    if (voicePaths.size() > 1) { fprintf(stderr, "--aligner with bracketed text cannot be combined with several voices\n"); return 1; }
+    if (stream) { fprintf(stderr, "--aligner with bracketed text cannot be combined with --stream\n"); return 1; }
+    if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--aligner with bracketed text cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
+    if (dry) { fprintf(stderr, "--aligner runs on the device: bracketed text cannot be combined with --dry-run 1\n"); return 1; }
+    std::vector<char> clean(message.size() + 1);
+    std::vector<int32_t> iv(2 * (message.size() + 1));
+    if (tts_host_redact_spans(message.c_str(), clean.data(), (int)clean.size(), iv.data(), (int)message.size() + 1) < 0) {
+      fprintf(stderr, "--aligner: unbalanced or nested brackets in the message\n");
+      return 1;
+    }
+    message = clean.data();
   }
   if (stream) {
     const char *bad = !use_hifigan ? "--decoder diffusion" : !clvpPath.empty() ? "--clvp" : !cvvpPath.empty() ? "--cvvp" : split_ids > 0 ? "--split-text" : voicePaths.size() > 1 ? "several --voice" :
@@ -875,10 +899,20 @@ int main(int argc, char **argv) {
   for (int c = 0; c < B; c++) nsamp.push_back((size_t)(use_bigvgan ? tts_bigvgan_samples(frames[c]) : tts_vocoder_samples(frames[c])));
   } // diffusion decoder
   } // !dry
-  auto write_one = [&](const float *samples, int64_t ns, int gc, bool is_output) {
+  std::vector<float> redacted;
+  auto write_one = [&](const float *samples, int64_t ns, int gc, bool is_output) -> bool {
     const std::string path = is_output ? outputPath : outputPath + "." + std::to_string(gc) + ".wav";
+    if (redact && is_output) { // the chosen candidate without the audio of the bracketed text; a failed alignment writes nothing
+      if (tts_load_aligner(ctx, alignerPath.c_str())) { die(ctx, "aligner_model_load"); return false; }
+      redacted.resize((size_t)std::max<int64_t>(ns, 1));
+      const int64_t kept = tts_redact_audio(ctx, samples, ns, 24000, promptText.c_str(), redacted.data(), ns);
+      if (kept < 0) { die(ctx, "redact_audio"); return false; }
+      fprintf(stderr, "aligner: %lld of %lld samples kept\n", (long long)kept, (long long)ns);
+      samples = redacted.data(); ns = kept;
+    }
     if (tts_write_wav(path.c_str(), samples, ns, 24000)) std::cerr << "Error opening output file." << std::endl;
     else if (is_output) std::cout << "WAV file saved successfully. :^)" << std::endl;
+    return true;
   };
   if (stream) std::cout << "WAV file saved successfully. :^)" << std::endl;
   else if (use_rccl) {
@@ -928,7 +962,7 @@ int main(int argc, char **argv) {
       size_t ns = nsamp[c];
       const int gc = kept_gc >= 0 ? kept_gc : (shard >= 0 ? shard * B_ar : 0) + c; // global candidate index
       // the re-ranked winner of a single process IS the output; a worker's winner waits for the parent's pick under its candidate name
-      write_one(audio.data() + off, (int64_t)ns, gc, kept_gc >= 0 ? shard < 0 : gc == 0);
+      if (!write_one(audio.data() + off, (int64_t)ns, gc, kept_gc >= 0 ? shard < 0 : gc == 0)) return 1;
       off += ns;
     }
     if (kept_gc >= 0 && shard >= 0) {

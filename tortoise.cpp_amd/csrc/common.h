@@ -94,6 +94,7 @@ struct DiffCondEncState;
 struct HifiganState;
 struct BigvganState;
 struct ClassifierState;
+struct AlignerState;
 struct AfeState;
 struct Tokenizer;
 struct SamplerPool;
@@ -141,6 +142,7 @@ struct tts_ctx {
   tts::HifiganState *hifigan = nullptr; // HiFi-GAN decoder: latents -> waveform (hifigan.hip; not in the reference: upstream's api_fast.py path)
   tts::BigvganState *bigvgan = nullptr; // BigVGAN vocoder: mel -> waveform beside UnivNet (bigvgan.h, part of hifigan.hip's translation unit; not in the reference)
   tts::ClassifierState *classifier = nullptr; // tortoise-detect: waveform -> probability that the clip is synthesized (classifier.h, part of hifigan.hip's translation unit through bigvgan.h; not in the reference)
+  tts::AlignerState *aligner = nullptr; // wav2vec2 CTC aligner: waveform -> one token id per frame, for tts_align_audio / tts_redact_audio (aligner.h, part of hifigan.hip's translation unit through classifier.h; not in the reference)
   tts::AfeState *afe = nullptr; // audio front-end: its tables and buffers, made at the first tts_voice_from_audio / tts_audio_mel (audio_frontend.hip)
   tts::Tokenizer *tok = nullptr;
   tts::ArSession *session = nullptr;        // non-null while a session is open: tts_ar_begin*, tts_autoregressive* and tts_hifigan_stream then return TTS_ERR_STATE
@@ -592,6 +594,23 @@ int afe_resample_to_24k(tts_ctx *ctx, const float *d_src, float *d_dst, const Cl
 using ClsResampleFn = int (*)(tts_ctx *, const float *, float *, const ClsResampleClip *, int);
 int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, float *prob_out, float *logits_out,
                    ClsResampleFn resample);
+// The wav2vec2 CTC aligner (aligner.h). `resample` as above, to 16 kHz: api.cpp hands in afe_resample_to_16k.
+int afe_resample_to_16k(tts_ctx *ctx, const float *d_src, float *d_dst, const ClsResampleClip *clips, int n_clips);
+int aligner_load(tts_ctx *ctx, const char *path);
+void aligner_free(AlignerState *);
+int aligner_vocab(tts_ctx *ctx, int32_t *vocab_out, int cap, int32_t *blank_out);
+int aligner_clip_frames(tts_ctx *ctx, int64_t n_samples, int sample_rate);
+int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, int32_t *ids_out, int32_t *n_frames_out,
+                int frame_stride, float *logits_out, ClsResampleFn resample);
+// The host half of alignment and redaction (host_logic.cpp; exported as tts_host_*). Text is UTF-8; a character is a code point. Each returns a count or a
+// negative status and leaves the reason in `err`.
+int ctc_decode(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, std::vector<int32_t> &out, std::string &err);
+int utf8_decode(const char *s, std::vector<int32_t> &out);
+void utf8_encode(const std::vector<int32_t> &cp, std::string &out);
+int max_alignment(const std::vector<int32_t> &s1, const std::vector<int32_t> &s2, std::vector<int32_t> &out, std::string &err);
+int ctc_align(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, const std::vector<int32_t> &text, int64_t n_samples,
+              std::vector<int64_t> &offsets, std::string &err);
+int redact_spans(const std::vector<int32_t> &text, std::vector<int32_t> &clean, std::vector<int32_t> &intervals, std::string &err);
 // Latent rows of a one-candidate utterance that are final after its first k sampled codes (none of them the stop token): the rows whose inputs
 // 8192, c_0 .. c_{k-1} pad_codes will not rewrite, cut where trimmed_latent_rows will cut (tts_hifigan_stream; host_logic.cpp)
 int stream_final_rows(const int32_t *codes, int k);

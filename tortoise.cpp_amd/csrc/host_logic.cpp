@@ -1517,3 +1517,191 @@ extern "C" int64_t tts_read_wav(const char *path, float *out, int64_t cap, int32
     } else if (fseek(f, (long)(size + (size & 1)), SEEK_CUR)) return TTS_ERR_IO;
   }
 }
+
+// ---- alignment and redaction: the host half of the wav2vec2 CTC aligner (aligner.h). The project's statement of upstream tortoise-tts' Wav2VecAlignment rules
+// (max_alignment, align, redact), from memory: unpinned against upstream, pinned to the Python restatement of tests/aligner_ref.py. Text is UTF-8 and a
+// "character" is one code point; lower() folds 'A' .. 'Z' only. ----
+namespace tts {
+
+int utf8_decode(const char *s, std::vector<int32_t> &out) {
+  out.clear();
+  if (!s) return TTS_ERR_ARG;
+  const unsigned char *p = (const unsigned char *)s;
+  while (*p) {
+    int32_t c = *p++;
+    int more = c < 0x80 ? 0 : (c >> 5) == 6 ? 1 : (c >> 4) == 14 ? 2 : (c >> 3) == 30 ? 3 : -1;
+    if (more < 0) return TTS_ERR_ARG;
+    if (more) c &= 0x3f >> more;
+    for (int i = 0; i < more; i++) {
+      if ((*p & 0xc0) != 0x80) return TTS_ERR_ARG;
+      c = c << 6 | (*p++ & 0x3f);
+    }
+    out.push_back(c);
+  }
+  return (int)out.size();
+}
+
+void utf8_encode(const std::vector<int32_t> &cp, std::string &out) {
+  out.clear();
+  for (int32_t c : cp) {
+    if (c < 0x80) out += (char)c;
+    else if (c < 0x800) { out += (char)(0xc0 | c >> 6); out += (char)(0x80 | (c & 0x3f)); }
+    else if (c < 0x10000) { out += (char)(0xe0 | c >> 12); out += (char)(0x80 | (c >> 6 & 0x3f)); out += (char)(0x80 | (c & 0x3f)); }
+    else { out += (char)(0xf0 | c >> 18); out += (char)(0x80 | (c >> 12 & 0x3f)); out += (char)(0x80 | (c >> 6 & 0x3f)); out += (char)(0x80 | (c & 0x3f)); }
+  }
+}
+
+// CTC decode: collapse runs of equal ids, drop the blank and every token without a character (-1), map the rest through the vocabulary
+int ctc_decode(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, std::vector<int32_t> &out, std::string &err) {
+  out.clear();
+  if (n_frames < 0 || (n_frames && !ids) || !vocab || n_vocab < 1) { err = "ctc_decode: bad argument"; return TTS_ERR_ARG; }
+  for (int i = 0; i < n_frames; i++) {
+    if (ids[i] < 0 || ids[i] >= n_vocab) { err = "ctc_decode: frame " + std::to_string(i) + " holds id " + std::to_string(ids[i]) + " outside the vocabulary"; return TTS_ERR_ARG; }
+    if (i && ids[i] == ids[i - 1]) continue;
+    if (ids[i] == blank || vocab[ids[i]] < 0) continue;
+    out.push_back(vocab[ids[i]]);
+  }
+  return (int)out.size();
+}
+
+// max_alignment(s1, s2): s1 with every character that s2 cannot account for, in order, replaced by '~'. The recursion
+//   s1 empty -> "";  s2 empty -> '~' x len(s1);  s1[0] == s2[0] -> s1[0] + f(s1[1:], s2[1:]);
+//   else a = f(s1, s2[1:]), b = '~' + f(s1[1:], s2): a if it has strictly more non-'~' characters than b, else b
+// memoised on the two lengths, here as the table of its non-'~' counts filled from the ends, then one walk from the front taking the recursion's choices.
+int max_alignment(const std::vector<int32_t> &s1, const std::vector<int32_t> &s2, std::vector<int32_t> &out, std::string &err) {
+  out.clear();
+  for (int32_t c : s1)
+    if (c == '~') { err = "max_alignment: the text holds '~', the mark of an unaligned character"; return TTS_ERR_ARG; }
+  const size_t n1 = s1.size(), n2 = s2.size();
+  if ((n1 + 1) * (n2 + 1) > ((size_t)1 << 28)) { err = "max_alignment: the strings are too long"; return TTS_ERR_LIMIT; }
+  std::vector<int32_t> cnt((n1 + 1) * (n2 + 1), 0); // cnt[i][j]: non-'~' characters of f(s1[i:], s2[j:])
+  auto at = [&](size_t i, size_t j) -> int32_t & { return cnt[i * (n2 + 1) + j]; };
+  for (size_t i = n1; i-- > 0;)
+    for (size_t j = n2; j-- > 0;)
+      at(i, j) = s1[i] == s2[j] ? 1 + at(i + 1, j + 1) : std::max(at(i, j + 1), at(i + 1, j));
+  size_t i = 0, j = 0;
+  while (i < n1) {
+    if (j == n2) { out.push_back('~'); i++; }
+    else if (s1[i] == s2[j]) { out.push_back(s1[i]); i++; j++; }
+    else if (at(i, j + 1) > at(i + 1, j)) j++;
+    else { out.push_back('~'); i++; }
+  }
+  return (int)out.size();
+}
+
+// One sample offset per character of `text`, in samples of a clip of n_samples whose frames carry `ids`.
+int ctc_align(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, const std::vector<int32_t> &text, int64_t n_samples,
+              std::vector<int64_t> &al, std::string &err) {
+  al.clear();
+  if (n_frames < 1 || !ids || !vocab || n_vocab < 1 || n_samples < 1) { err = "ctc_align: bad argument"; return TTS_ERR_ARG; }
+  if (text.empty()) return 0;
+  std::vector<int32_t> low(text), pred, fixed;
+  for (int32_t &c : low)
+    if (c >= 'A' && c <= 'Z') c += 32;
+  int rc = ctc_decode(ids, n_frames, vocab, n_vocab, blank, pred, err);
+  if (rc < 0) return rc;
+  if ((rc = max_alignment(low, pred, fixed, err)) < 0) return rc;
+  // nothing of the text was heard: upstream's rule would place nothing and interpolate every offset between 0 and n_samples; here it is the failure
+  if (std::all_of(fixed.begin(), fixed.end(), [](int32_t c) { return c == '~'; })) { err = "the text does not match the audio"; return TTS_ERR_ARG; }
+  auto token = [&](int32_t cp) { // the vocabulary id of a character: the first token that carries it, -1 for none
+    for (int v = 0; v < n_vocab; v++)
+      if (vocab[v] == cp) return v;
+    return -1;
+  };
+  const int64_t step = n_samples / n_frames;
+  const size_t n = fixed.size();
+  al.assign(n, -1);
+  al[0] = 0; // character 0 sits at offset 0
+  size_t next = 1;
+  while (next < n && fixed[next] == '~') next++; // the '~' passed on the way stay open
+  for (int f = 0; f < n_frames && next < n; f++)
+    if (ids[f] == token(fixed[next])) {
+      al[next++] = (int64_t)f * step;
+      while (next < n && fixed[next] == '~') next++;
+    }
+  if (next < n) { al.clear(); err = "the text does not match the audio"; return TTS_ERR_ARG; }
+  // open offsets: linear between the placed neighbour before and the next placed one (n_samples behind the end), integer floor
+  for (size_t i = 1; i < n; i++) {
+    if (al[i] != -1) continue;
+    size_t nf = i + 1;
+    while (nf < n && al[nf] == -1) nf++;
+    const int64_t hi = nf < n ? al[nf] : n_samples, lo = al[i - 1], gap = hi - lo;
+    for (size_t j = i; j < nf; j++) {
+      const int64_t num = (int64_t)(j - i + 1) * gap, den = (int64_t)(nf - i + 1);
+      al[j] = (num >= 0 ? num / den : -((-num + den - 1) / den)) + lo;
+    }
+  }
+  return (int)n;
+}
+
+// The text without its brackets, and the kept intervals {first character, last character} (indices into the bare text) of every non-empty unbracketed
+// piece: upstream's non_redacted_intervals.
+int redact_spans(const std::vector<int32_t> &text, std::vector<int32_t> &clean, std::vector<int32_t> &iv, std::string &err) {
+  clean.clear(); iv.clear();
+  bool inside = false;
+  int32_t piece0 = 0;
+  auto close_piece = [&] {
+    if ((int32_t)clean.size() > piece0) { iv.push_back(piece0); iv.push_back((int32_t)clean.size() - 1); }
+  };
+  for (int32_t c : text) {
+    if (c == '[') {
+      if (inside) { err = "nested '[' in the text"; return TTS_ERR_ARG; }
+      close_piece();
+      inside = true;
+    } else if (c == ']') {
+      if (!inside) { err = "']' without '[' in the text"; return TTS_ERR_ARG; }
+      inside = false;
+      piece0 = (int32_t)clean.size();
+    } else clean.push_back(c);
+  }
+  if (inside) { err = "'[' without ']' in the text"; return TTS_ERR_ARG; }
+  close_piece();
+  return (int)iv.size() / 2;
+}
+
+static int put_utf8(const std::vector<int32_t> &cp, char *out, int cap) {
+  std::string s;
+  utf8_encode(cp, s);
+  if (!out || cap < (int)s.size() + 1) return TTS_ERR_ARG;
+  memcpy(out, s.c_str(), s.size() + 1);
+  return (int)s.size();
+}
+
+} // namespace tts
+
+extern "C" int tts_host_ctc_decode(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, char *out, int cap) {
+  std::vector<int32_t> cp;
+  std::string err;
+  const int rc = tts::ctc_decode(ids, n_frames, vocab, n_vocab, blank, cp, err);
+  return rc < 0 ? rc : tts::put_utf8(cp, out, cap);
+}
+extern "C" int tts_host_max_alignment(const char *s1, const char *s2, char *out, int cap) {
+  std::vector<int32_t> a, b, r;
+  std::string err;
+  if (tts::utf8_decode(s1, a) < 0 || tts::utf8_decode(s2, b) < 0) return TTS_ERR_ARG;
+  const int rc = tts::max_alignment(a, b, r, err);
+  return rc < 0 ? rc : tts::put_utf8(r, out, cap);
+}
+extern "C" int tts_host_ctc_align(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, const char *text, int64_t n_samples,
+                                  int64_t *offsets_out, int cap) {
+  std::vector<int32_t> t;
+  std::vector<int64_t> al;
+  std::string err;
+  if (tts::utf8_decode(text, t) < 0) return TTS_ERR_ARG;
+  const int rc = tts::ctc_align(ids, n_frames, vocab, n_vocab, blank, t, n_samples, al, err);
+  if (rc < 0) return rc;
+  if (rc > cap || (rc && !offsets_out)) return TTS_ERR_ARG;
+  for (int i = 0; i < rc; i++) offsets_out[i] = al[i];
+  return rc;
+}
+extern "C" int tts_host_redact_spans(const char *text, char *clean_out, int cap, int32_t *intervals_out, int cap_intervals) {
+  std::vector<int32_t> t, clean, iv;
+  std::string err;
+  if (tts::utf8_decode(text, t) < 0) return TTS_ERR_ARG;
+  const int rc = tts::redact_spans(t, clean, iv, err);
+  if (rc < 0) return rc;
+  if (rc > cap_intervals || (rc && !intervals_out)) return TTS_ERR_ARG;
+  if (tts::put_utf8(clean, clean_out, cap) < 0) return TTS_ERR_ARG;
+  for (size_t i = 0; i < iv.size(); i++) intervals_out[i] = iv[i];
+  return rc;
+}

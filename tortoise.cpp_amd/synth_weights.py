@@ -640,6 +640,159 @@ def classifier_forward(tensors, wave, dtype=np.float64, clamp=True):
     return h[0] @ t["head.weight"].T.astype(dtype) + t["head.bias"].astype(dtype)
 
 
+ALIGNER_UPSTREAM = dict(N=7, C=512, k=(10, 3, 3, 3, 3, 2, 2), s=(5, 2, 2, 2, 2, 2, 2), D=1024, K=128, G=16, depth=24, FF=4096, V=32, H=16, blank=0, config=True)
+
+
+def aligner_vocab(V):
+    """int32 [V]: the code point of every single-character token, HF's wav2vec2 order in spirit - four special tokens (the blank first), the word delimiter
+    (stored as a space, 32), a .. z, the apostrophe; every other token, the blank included, -1."""
+    cps = [-1, -1, -1, -1, 32] + list(range(ord("a"), ord("z") + 1)) + [ord("'")]
+    return np.array((cps + [-1] * V)[:V], np.int32)
+
+
+def aligner_tensor_shapes(N=7, C=512, k=(10, 3, 3, 3, 3, 2, 2), s=(5, 2, 2, 2, 2, 2, 2), D=1024, K=128, G=16, depth=24, FF=4096, V=32, H=16, blank=0, config=True):
+    """{name: PyTorch shape} of an aligner file (tts_load_aligner): HF's Wav2Vec2ForCTC state dict (stable-layer-norm configuration) with `wav2vec2.` replaced
+    by `aligner.` and `lm_head.` by `aligner.lm_head.`, pos_conv_embed's weight_g / weight_v folded into one weight, masked_spec_embed left out; plus
+    `aligner.config` = (heads, blank id, s_0 .. s_{N-1}) and `aligner.vocab` [V], integers held as f32 (the container's one tensor type). Restated from
+    memory, unpinned against upstream."""
+    t = {}
+    for i in range(N):
+        p = "aligner.feature_extractor.conv_layers.%d." % i
+        t.update({p + "conv.weight": (C, C if i else 1, k[i]), p + "conv.bias": (C,), p + "layer_norm.weight": (C,), p + "layer_norm.bias": (C,)})
+    t.update({"aligner.feature_projection.layer_norm.weight": (C,), "aligner.feature_projection.layer_norm.bias": (C,),
+              "aligner.feature_projection.projection.weight": (D, C), "aligner.feature_projection.projection.bias": (D,),
+              "aligner.encoder.pos_conv_embed.conv.weight": (D, D // G, K), "aligner.encoder.pos_conv_embed.conv.bias": (D,)})
+    for l in range(depth):
+        p = "aligner.encoder.layers.%d." % l
+        for q in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            t.update({p + "attention.%s.weight" % q: (D, D), p + "attention.%s.bias" % q: (D,)})
+        t.update({p + "layer_norm.weight": (D,), p + "layer_norm.bias": (D,), p + "feed_forward.intermediate_dense.weight": (FF, D),
+                  p + "feed_forward.intermediate_dense.bias": (FF,), p + "feed_forward.output_dense.weight": (D, FF), p + "feed_forward.output_dense.bias": (D,),
+                  p + "final_layer_norm.weight": (D,), p + "final_layer_norm.bias": (D,)})
+    t.update({"aligner.encoder.layer_norm.weight": (D,), "aligner.encoder.layer_norm.bias": (D,), "aligner.lm_head.weight": (V, D), "aligner.lm_head.bias": (V,)})
+    if config:
+        t["aligner.config"] = (2 + N,)
+    t["aligner.vocab"] = (V,)
+    return t
+
+
+def aligner_tensors(seed=1270, head_gain=16.0, **cfg):
+    """{name: float32 array}: the synthetic recipe. Convolutions and Linears N(0, 1 / sqrt(fan in)), the two projections that end a residual branch at half
+    that; LayerNorm 1 + 0.05 N and 0.05 N; biases 0.05 N; lm_head N(0, head_gain / sqrt(D)) with bias N(0, 1): logits of order head_gain, so that the two
+    largest of a frame lie far apart against the 1e-3 gate and the argmax is the same in every correct arithmetic (tests/test_aligner_cpu.py asserts the margin)."""
+    c = dict(ALIGNER_UPSTREAM, **cfg)
+    g = _Gen(seed)
+    t = {}
+    for name, shape in aligner_tensor_shapes(**c).items():
+        if name == "aligner.config":
+            t[name] = np.array([c["H"], c["blank"]] + list(c["s"]), np.float32)
+        elif name == "aligner.vocab":
+            t[name] = aligner_vocab(c["V"]).astype(np.float32)
+        elif "layer_norm" in name:
+            t[name] = g.gamma(shape[0]) if name.endswith(".weight") else g.beta(shape[0])
+        elif name == "aligner.lm_head.bias":
+            t[name] = g.normal(shape, 1.0)
+        elif name.endswith(".bias"):
+            t[name] = g.normal(shape, 0.05)
+        else:
+            gain = head_gain if name == "aligner.lm_head.weight" else 0.5 if ("out_proj" in name or "output_dense" in name) else 1.0
+            t[name] = g.lecun(shape, int(np.prod(shape[1:])), gain)
+    return t
+
+
+def write_aligner(path, seed=1270, head_gain=16.0, **cfg):
+    """ggml-aligner-model.bin for tts_load_aligner; every size a parameter (aligner_tensor_shapes). Returns the tensors."""
+    t = aligner_tensors(seed, head_gain, **cfg)
+    w = GgmlWriter(path)
+    for name, arr in t.items():
+        w.add(name, arr)
+    w.close()
+    return t
+
+
+def aligner_test_wave(n, seed):
+    """a 16 kHz test clip: noise and two tones on an offset, at a scale far from 1 (the clip normalisation has work to do)"""
+    r = np.random.default_rng(seed)
+    i = np.arange(n)
+    return (0.07 + 0.2 * r.standard_normal(n) + 0.15 * np.sin(i * 0.031 + seed) + 0.1 * np.sin(i * 0.0017)).astype(np.float32)
+
+
+_erf = np.vectorize(__import__("math").erf, otypes=[np.float64])
+
+
+def aligner_gelu(x):
+    """the exact GELU, 0.5 x (1 + erf(x / sqrt 2)); erf in double, the result in x's type"""
+    return (0.5 * x * (1 + _erf(np.asarray(x, np.float64) / np.sqrt(2.0)).astype(x.dtype))).astype(x.dtype)
+
+
+def _w2v_ln(h, g, b, eps=1e-5):
+    m = h.mean(axis=1, keepdims=True)
+    v = ((h - m) ** 2).mean(axis=1, keepdims=True)
+    return (h - m) / np.sqrt(v + h.dtype.type(eps)) * g.astype(h.dtype) + b.astype(h.dtype)
+
+
+def aligner_frames(n, k, s):
+    for ki, si in zip(k, s):
+        n = (n - ki) // si + 1 if n >= ki else 0
+    return n
+
+
+def aligner_forward(tensors, wave, dtype=np.float64):
+    """The index form the kernels implement, in numpy: the logits [frames][V] of one clip already at 16 kHz. dtype=np.float32: the float32 restatement of
+    the whole network."""
+    t = {k[len("aligner."):]: np.asarray(v) for k, v in tensors.items()}
+    N = 0
+    while "feature_extractor.conv_layers.%d.conv.weight" % N in t:
+        N += 1
+    cfgv = [int(v) for v in t["config"]] if "config" in t else [16, 0, 5] + [2] * (N - 1)
+    H, strides = cfgv[0], cfgv[2:]
+    x = np.asarray(wave, dtype)
+    n = len(x)
+    mean = x.sum() / n
+    var = ((x - mean) ** 2).sum() / (n - 1)
+    h = ((x - mean) / np.sqrt(var + dtype(1e-7))).reshape(-1, 1)
+    for i in range(N):
+        p = "feature_extractor.conv_layers.%d." % i
+        w, s = t[p + "conv.weight"].astype(dtype), strides[i]
+        k = w.shape[2]
+        n_out = (h.shape[0] - k) // s + 1
+        out = np.tile(t[p + "conv.bias"].astype(dtype), (n_out, 1))
+        for j in range(k):
+            out += h[j:j + s * (n_out - 1) + 1:s] @ w[:, :, j].T
+        h = aligner_gelu(_w2v_ln(out, t[p + "layer_norm.weight"], t[p + "layer_norm.bias"]))
+    h = _w2v_ln(h, t["feature_projection.layer_norm.weight"], t["feature_projection.layer_norm.bias"])
+    h = h @ t["feature_projection.projection.weight"].T.astype(dtype) + t["feature_projection.projection.bias"].astype(dtype)
+    T, D = h.shape
+    w = t["encoder.pos_conv_embed.conv.weight"].astype(dtype)
+    cg, K = w.shape[1], w.shape[2]
+    hp = np.zeros((T + 2 * (K // 2), D), dtype)
+    hp[K // 2:K // 2 + T] = h
+    pos = np.tile(t["encoder.pos_conv_embed.conv.bias"].astype(dtype), (T, 1))  # output rows 0 .. T - 1: an even K's extra last row is never made
+    for g in range(D // cg):
+        for j in range(K):
+            pos[:, g * cg:(g + 1) * cg] += hp[j:j + T, g * cg:(g + 1) * cg] @ w[g * cg:(g + 1) * cg, :, j].T
+    h = h + aligner_gelu(pos)
+    dh = D // H
+    lin = lambda x_, p_: x_ @ t[p_ + ".weight"].T.astype(dtype) + t[p_ + ".bias"].astype(dtype)  # noqa: E731
+    l = 0
+    while "encoder.layers.%d.layer_norm.weight" % l in t:
+        p = "encoder.layers.%d." % l
+        y = _w2v_ln(h, t[p + "layer_norm.weight"], t[p + "layer_norm.bias"])
+        q, k_, v = lin(y, p + "attention.q_proj"), lin(y, p + "attention.k_proj"), lin(y, p + "attention.v_proj")
+        att = np.empty_like(h)
+        for hd in range(H):
+            sl = slice(hd * dh, (hd + 1) * dh)
+            sc = (q[:, sl] @ k_[:, sl].T) * dtype(dh) ** dtype(-0.5)
+            sc = np.exp(sc - sc.max(axis=1, keepdims=True))
+            att[:, sl] = (sc / sc.sum(axis=1, keepdims=True)) @ v[:, sl]
+        h = h + lin(att, p + "attention.out_proj")
+        y = _w2v_ln(h, t[p + "final_layer_norm.weight"], t[p + "final_layer_norm.bias"])
+        h = h + lin(aligner_gelu(lin(y, p + "feed_forward.intermediate_dense")), p + "feed_forward.output_dense")
+        l += 1
+    h = _w2v_ln(h, t["encoder.layer_norm.weight"], t["encoder.layer_norm.bias"])
+    return lin(h, "lm_head")
+
+
 def write_all(out_dir, ar_layers=30, diff_main=10, diff_tail=3, diff_integ=3, diff_lc=4, seed=1234):
     import os
     os.makedirs(out_dir, exist_ok=True)
