@@ -827,6 +827,44 @@ int tts_host_ctc_align(const int32_t *ids, int n_frames, const int32_t *vocab, i
                        int64_t *offsets_out, int cap);
 int tts_host_redact_spans(const char *text, char *clean_out, int cap, int32_t *intervals_out, int cap_intervals);
 
+/* ---- random voices: upstream's RandomLatentConverter (not in the reference; additions within version 8, no prototype changed) ------------------ */
+/* The model upstream tortoise-tts runs when a caller gives neither clips nor latents (api.py: get_random_conditioning_latents; do_tts.py --voice random,
+ * its default): models/random_latent_generator.py with rlg_auto.pth (1024 channels: the AR conditioning latent tts_autoregressive* take as `voice`) and
+ * rlg_diffuser.pth (2048 channels: the diffusion conditioning latent). Five EqualLinear(D, D, lr_mul 0.1) layers, y = leaky_relu(F.linear(x, W * scale)
+ * + b * lr_mul, 0.2) * sqrt(2) with scale = lr_mul / sqrt(D), and one plain Linear, on z = randn(1, D). Upstream's source and weights are not available
+ * offline: this is stated from memory (DESIGN.md "What pins the random voice"), pinned between this library, two float64
+ * restatements and a float32 torch module written as upstream's forward; unpinned against upstream; how a random voice sounds is unjudged.
+ * Files: the reference's container format with upstream's state-dict names, layers.{0..L-1}.weight [D][D] and layers.{0..L-1}.bias [D]
+ * (tools/convert_weights.py --random-voice / --random-diffusion-voice). L and D are read from the names and shapes; W * scale and b * lr_mul are folded
+ * once at load, one f32 multiply per element, which is torch's rounding. f32 throughout: csrc/random_voice.h, one kernel per layer.
+ * tts_load_random_voice: either path may be NULL, that side is then left as it is (not loaded, or the model of an earlier call). TTS_ERR_FORMAT for a
+ *   non-square layer, layers of different sizes, a missing bias, fewer than two layers, an unknown tensor or a channel count the kernel does not take (a
+ *   multiple of 256 from 256 to 2048). The files are parsed before the device is asked for: a host-only context returns TTS_ERR_FORMAT for a broken file
+ *   and TTS_ERR_HIP for a good one. TTS_ERR_ARG when both paths are NULL.
+ * tts_random_voice_dim: side 0 = auto, 1 = diffusion: the channel count read from the file (1024 / 2048 for upstream's), 0 when the side is not loaded.
+ * tts_random_voice: n voices in one launch sequence per side on the context's stream (at most one noise fill and L dependent launches). Voice b draws its
+ *   input from the device Philox generator under seeds[b] (csrc/diffusion.hip's philox_normal with a counter tag of its own, 0x7717, and the side as its
+ *   stream value); where z_auto / z_diff [n][D] is given the side uses those values instead (a caller with torch.randn values reproduces upstream) and seeds
+ *   may be NULL. out_auto [n][D0], out_diff [n][D1]; either may be NULL: that side is skipped and need not be loaded. A voice's bits depend on its seed (or
+ *   its z row) only - not on n, its position, the other voices or the other side - and two calls give equal bytes. The context's std::mt19937 (tts_seed)
+ *   is never touched. Legal while an AR or a diffusion session is open. Every check runs before any device work and a refused call writes nothing:
+ *   TTS_ERR_HIP on a host-only context; TTS_ERR_STATE for an output whose side is not loaded; TTS_ERR_ARG for NULL seeds where a requested side has no z,
+ *   both outputs NULL, n < 1 or a non-finite z; TTS_ERR_LIMIT above TTS_RANDOM_VOICE_MAX voices. Profiler families: "rlg_layer", "rlg_noise" (work = bytes).
+ * tts_random_voice_noise: the exact input the generator gives that seed and side, out [cap >= D]; returns D. Feeding it back as z gives the same voice.
+ * tts_host_blend_voices: upstream's load_voices rule for several named voices, the mean of their latents, generalised to weights (NULL: equal):
+ *   out[i] = sum_v w[v] latents[v][i] / sum_v w[v], accumulated in double, rounded once. Needs no context. TTS_ERR_ARG for a null pointer, n or dim < 1, a
+ *   non-finite value, or weights that do not sum to a positive finite value.
+ * tts_host_random_voice_fold: the loader's fold of one layer, for the tests: equal != 0: w_out = w * fl(lr_mul / sqrt(dim)), b_out = b * fl(lr_mul) in f32;
+ *   equal == 0 (the last layer): copies. */
+#define TTS_RANDOM_VOICE_MAX 4096
+enum { TTS_RANDOM_VOICE_AUTO = 0, TTS_RANDOM_VOICE_DIFFUSION = 1 };
+int tts_load_random_voice(tts_ctx *ctx, const char *auto_path, const char *diff_path);
+int tts_random_voice_dim(const tts_ctx *ctx, int side);
+int tts_random_voice(tts_ctx *ctx, const uint64_t *seeds, int n, const float *z_auto, const float *z_diff, float *out_auto, float *out_diff);
+int tts_random_voice_noise(tts_ctx *ctx, uint64_t seed, int side, float *out, int cap);
+int tts_host_blend_voices(const float *latents, const float *weights, int n, int dim, float *out);
+int tts_host_random_voice_fold(const float *w, const float *b, int dim, int equal, float *w_out, float *b_out);
+
 /* ---- output -------------------------------------------------------------------------------- */
 /* writeWav (main.cpp:4821-4868): RIFF, fmt 16 B, tag 3 (IEEE float), mono, 32-bit. */
 int tts_write_wav(const char *path, const float *samples, int64_t n, int sample_rate);

@@ -30,7 +30,8 @@ sys.path.insert(0, ROOT)
 import tortoise_cpp_amd_loader  # noqa: E402
 
 tortoise_cpp_amd_loader.load()
-from tortoise_cpp_amd.synth_weights import GgmlWriter, aligner_tensor_shapes, bigvgan_filter, bigvgan_tensor_shapes, classifier_tensor_shapes  # noqa: E402
+from tortoise_cpp_amd.synth_weights import (GgmlWriter, aligner_tensor_shapes, bigvgan_filter, bigvgan_tensor_shapes, classifier_tensor_shapes,  # noqa: E402
+                                            random_voice_tensor_shapes)
 
 
 def _np(t):
@@ -344,6 +345,32 @@ def convert_classifier(sd, path, downsample_factor=4, heads=4):
     return arch["b0"], arch["depth"], arch["E"], heads
 
 
+def convert_random_voice(sd, path):
+    """One side's file for tts_load_random_voice: rlg_auto.pth (1024 channels) or rlg_diffuser.pth (2048) of upstream tortoise-tts, the state dict of a
+    RandomLatentConverter: layers.{0..L-1}.weight [D][D] and layers.{0..L-1}.bias [D], written under their own names and unchanged - weight * scale and
+    bias * lr_mul are the loader's, one f32 multiply per element as torch performs it, so nothing is folded here. L and D are read from the state dict; a
+    missing, unknown, non-square or mis-sized tensor is an error (the names are restated from memory: --list-expected random_voice). Returns (L, D)."""
+    L = 0
+    while "layers.%d.weight" % L in sd:
+        L += 1
+    if L < 2:
+        raise SystemExit("convert_random_voice: %d layers.N.weight tensors (not a RandomLatentConverter state dict?)" % L)
+    D = int(sd["layers.0.weight"].shape[0])
+    exp = random_voice_tensor_shapes(D, L)
+    for k in sorted(sd):
+        if k not in exp:
+            raise SystemExit("convert_random_voice: unexpected tensor '%s'" % k)
+    w = GgmlWriter(path)
+    for name, shape in exp.items():
+        if name not in sd:
+            raise SystemExit("convert_random_voice: tensor '%s' is missing" % name)
+        if tuple(sd[name].shape) != tuple(shape):
+            raise SystemExit("convert_random_voice: tensor '%s' has shape %s, expected %s" % (name, list(sd[name].shape), list(shape)))
+        w.add(name, _np(sd[name]))
+    w.close()
+    return L, D
+
+
 # ---- what each checkpoint is expected to hold (--list-expected) ---------------------------------------------------------------------
 # name -> PyTorch shape as tortoise-tts stores it, for the upstream architecture (or the one given). Written from the loaders' contracts
 # (main.cpp:682-792, 1244-1536, 1808-1923; csrc/extras.hip for the three containers the reference does not have), NOT from a checkpoint:
@@ -532,12 +559,14 @@ def expected_tensors(kind, **arch):
         out.update({k[len("classifier."):]: v for k, v in classifier_tensor_shapes(config=False, **arch).items()})
     elif kind == "aligner":  # Wav2Vec2ForCTC after the weight-norm fold (aligner.config and aligner.vocab are the converter's, not the checkpoint's)
         out.update({k[len("aligner."):]: v for k, v in aligner_tensor_shapes(config=False, **arch).items() if k != "aligner.vocab"})
+    elif kind == "random_voice":  # rlg_auto.pth (dim 1024, the default) / rlg_diffuser.pth (dim 2048): a RandomLatentConverter's state dict
+        out.update(random_voice_tensor_shapes(arch.get("dim", 1024), arch.get("layers", 6)))
     else:
         raise ValueError(kind)
     return out
 
 
-EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan", "classifier", "aligner")
+EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan", "classifier", "aligner", "random_voice")
 
 
 def container_shape(kind, name, shape):
@@ -613,16 +642,21 @@ def main():
     ap.add_argument("--aligner-vocab", help="with --aligner: the tokenizer's vocab.json {token: id}")
     ap.add_argument("--aligner-heads", type=int, default=16, help="with --aligner: attention heads (no shape holds it; upstream: 16)")
     ap.add_argument("--aligner-strides", help="with --aligner: the convolution strides, comma-separated (no shape holds them; upstream: 5,2,2,2,2,2,2)")
+    ap.add_argument("--random-voice", help="rlg_auto.pth of upstream tortoise-tts (RandomLatentConverter, 1024 channels) -> ggml-random-voice-model.bin "
+                                           "(the AR side of tts_load_random_voice; not in the reference)")
+    ap.add_argument("--random-diffusion-voice", help="rlg_diffuser.pth of upstream tortoise-tts (RandomLatentConverter, 2048 channels) -> "
+                                                     "ggml-random-diffusion-voice-model.bin (the diffusion side of tts_load_random_voice; not in the reference)")
     ap.add_argument("--out")
     ap.add_argument("--list-expected", nargs="*", metavar="KIND", help="print every tensor name / shape the converter looks for per checkpoint kind (%s; "
                                                                         "default: all, upstream architecture) and exit" % ", ".join(EXPECTED_KINDS))
     a = ap.parse_args()
     if a.list_expected is not None:
         for kind in (a.list_expected or EXPECTED_KINDS):
-            exp = expected_tensors(kind)
-            print("# %s: %d tensors" % (kind, len(exp)))
-            for name, shape in exp.items():
-                print("%-28s %-88s %s" % (kind, name, "x".join(map(str, shape)) or "scalar"))
+            for label, arch in ((("random_voice (rlg_auto)", dict(dim=1024)), ("random_voice (rlg_diffuser)", dict(dim=2048))) if kind == "random_voice" else ((kind, {}),)):
+                exp = expected_tensors(kind, **arch)
+                print("# %s: %d tensors" % (label, len(exp)))
+                for name, shape in exp.items():
+                    print("%-28s %-88s %s" % (label, name, "x".join(map(str, shape)) or "scalar"))
         return
     if not a.out:
         ap.error("--out is required")
@@ -680,6 +714,11 @@ def main():
         print("ggml-aligner-model.bin: %d convolution layers of %d channels, dimension %d, %d encoder layers, %d tokens"
               % convert_aligner(load(a.aligner), json.load(open(a.aligner_vocab)), os.path.join(a.out, "ggml-aligner-model.bin"), a.aligner_heads,
                                 [int(v) for v in a.aligner_strides.split(",")] if a.aligner_strides else None))
+    if a.random_voice:
+        print("ggml-random-voice-model.bin: %d layers of %d channels" % convert_random_voice(load(a.random_voice), os.path.join(a.out, "ggml-random-voice-model.bin")))
+    if a.random_diffusion_voice:
+        print("ggml-random-diffusion-voice-model.bin: %d layers of %d channels"
+              % convert_random_voice(load(a.random_diffusion_voice), os.path.join(a.out, "ggml-random-diffusion-voice-model.bin")))
     if a.vocoder:
         checked("vocoder", load(a.vocoder), a.vocoder)
         print("ggml-vocoder-model.bin: %d res stacks" % convert_vocoder(load(a.vocoder), os.path.join(a.out, "ggml-vocoder-model.bin")))

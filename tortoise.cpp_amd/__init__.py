@@ -122,6 +122,9 @@ def lib():
         "tts_align_audio": (ci, [vp, vp, C.c_int64, ci, C.c_char_p, vp, ci]), "tts_redact_audio": (C.c_int64, [vp, vp, C.c_int64, ci, C.c_char_p, vp, C.c_int64]),
         "tts_host_ctc_decode": (ci, [vp, ci, vp, ci, ci, vp, ci]), "tts_host_max_alignment": (ci, [C.c_char_p, C.c_char_p, vp, ci]),
         "tts_host_ctc_align": (ci, [vp, ci, vp, ci, ci, C.c_char_p, C.c_int64, vp, ci]), "tts_host_redact_spans": (ci, [C.c_char_p, vp, ci, vp, ci]),
+        "tts_load_random_voice": (ci, [vp, C.c_char_p, C.c_char_p]), "tts_random_voice_dim": (ci, [vp, ci]),
+        "tts_random_voice": (ci, [vp, vp, ci, vp, vp, vp, vp]), "tts_random_voice_noise": (ci, [vp, C.c_uint64, ci, vp, ci]),
+        "tts_host_blend_voices": (ci, [vp, vp, ci, ci, vp]), "tts_host_random_voice_fold": (ci, [vp, vp, ci, ci, vp, vp]),
         "tts_hifigan_stream": (ci, [vp, vp, ci, vp, ci, C.c_uint, ci, vp, vp, vp, vp, vp, vp]), "tts_hifigan_stream_recaptures": (ci, [vp]),
         "tts_host_stream_final_rows": (ci, [vp, ci]),
         "tts_ar_session_open": (ci, [vp, ci, ci, ci, ci, C.c_uint]), "tts_ar_session_admit": (ci, [vp, vp, ci, vp, ci, C.c_uint32, vp]),
@@ -545,6 +548,47 @@ class Engine:
         out2 = np.empty(2048, np.float32) if want[1] else None
         self._ck(self.L.tts_voice_from_audio(self.h, _ptr(a), _ptr(n), _ptr(r), len(clips), C.addressof(o), _ptr(out1), _ptr(out2)))
         return out1, out2
+
+    # ---- random voices (not in the reference): upstream's RandomLatentConverter, what tts() runs when it is given neither clips nor latents ----
+    RANDOM_VOICE_SIDES = {"auto": 0, "diffusion": 1}
+
+    def load_random_voice(self, auto=None, diffusion=None):
+        """auto: rlg_auto converted (the AR conditioning latent's model), diffusion: rlg_diffuser converted; either may be None (tts_load_random_voice)."""
+        self._ck(self.L.tts_load_random_voice(self.h, None if auto is None else auto.encode(), None if diffusion is None else diffusion.encode()))
+
+    def random_voice_dim(self, side):
+        return self.L.tts_random_voice_dim(self.h, self.RANDOM_VOICE_SIDES[side])
+
+    def random_voice(self, seeds, z_auto=None, z_diff=None, sides=("auto", "diffusion")):
+        """n voices in one call. seeds: n unsigned 64-bit integers (or None where every requested side has a z); z_auto [n, 1024] / z_diff [n, 2048]: the
+        model's input in place of the device generator's (torch.randn values reproduce upstream). Returns (auto [n, 1024] or None, diffusion [n, 2048] or
+        None): a side not named in `sides` is None and need not be loaded."""
+        for s in sides:
+            if s not in self.RANDOM_VOICE_SIDES:
+                raise TtsError("side %r: 'auto' or 'diffusion'" % (s,))
+        sd = None if seeds is None else np.array([int(v) for v in (seeds if np.ndim(seeds) else [seeds])], np.uint64).reshape(-1)
+        za = None if z_auto is None else np.ascontiguousarray(z_auto, np.float32)
+        zd = None if z_diff is None else np.ascontiguousarray(z_diff, np.float32)
+        n = len(sd) if sd is not None else len(za) if za is not None and za.ndim == 2 else len(zd) if zd is not None and zd.ndim == 2 else 0
+        outs = []
+        for side, z in (("auto", za), ("diffusion", zd)):
+            dim = self.random_voice_dim(side)
+            if z is not None and side in sides and (z.ndim != 2 or z.shape != (n, dim)):
+                raise TtsError("z of the %s side has shape %s, (%d, %d) expected" % (side, z.shape, n, dim))
+            outs.append(np.empty((max(n, 0), dim), np.float32) if side in sides and dim > 0 and n > 0 else None)
+        # a side that is wanted but not loaded (or n = 0) is still handed to the library: the refusal and its text are the library's
+        dummy = np.empty(1, np.float32)
+        pa = _ptr(outs[0]) if outs[0] is not None else (_ptr(dummy) if "auto" in sides else None)
+        pd = _ptr(outs[1]) if outs[1] is not None else (_ptr(dummy) if "diffusion" in sides else None)
+        self._ck(self.L.tts_random_voice(self.h, _ptr(sd), n, _ptr(za) if "auto" in sides else None, _ptr(zd) if "diffusion" in sides else None, pa, pd))
+        return outs[0], outs[1]
+
+    def random_voice_noise(self, seed, side):
+        """the input the device generator gives `seed` on `side` ('auto' / 'diffusion'): random_voice(z = this) is random_voice(seeds = [seed])"""
+        dim = self.random_voice_dim(side)
+        out = np.empty(max(dim, 1), np.float32)
+        self._ck(self.L.tts_random_voice_noise(self.h, int(seed), self.RANDOM_VOICE_SIDES[side], _ptr(out), dim))
+        return out[:dim]
 
     def audio_mel(self, audio, rate, bands, mel_norms=None, crop_offset=0, full_clips=False):
         """[bands, frames] log-mel the front-end hands to the encoder for one clip: bands 80 (the input of voice_latent) or 100 (of
@@ -1208,6 +1252,31 @@ def host_redact_spans(text):
     if rc < 0:
         _host_fail("tts_host_redact_spans", rc)
     return buf.value.decode(), [tuple(int(v) for v in r) for r in iv[:rc]]
+
+
+def host_blend_voices(latents, weights=None):
+    """upstream's load_voices rule for several voices, the mean of their latents, with optional weights (tts_host_blend_voices): latents [n, dim] -> [dim]"""
+    x = np.ascontiguousarray(latents, np.float32)
+    if x.ndim != 2:
+        raise TtsError("latents: [n, dim] expected, got shape %s" % (x.shape,))
+    w = None if weights is None else np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if w is not None and len(w) != len(x):
+        raise TtsError("%d weights for %d voices" % (len(w), len(x)))
+    out = np.empty(x.shape[1], np.float32)
+    rc = lib().tts_host_blend_voices(_ptr(x), _ptr(w), x.shape[0], x.shape[1], _ptr(out))
+    if rc < 0:
+        _host_fail("tts_host_blend_voices", rc)
+    return out
+
+
+def host_random_voice_fold(w, b, equal=True):
+    """the loader's fold of one random-voice layer (tts_host_random_voice_fold): (w * scale, b * lr_mul) in float32, or copies for the last layer"""
+    w, b = np.ascontiguousarray(w, np.float32), np.ascontiguousarray(b, np.float32)
+    wo, bo = np.empty_like(w), np.empty_like(b)
+    rc = lib().tts_host_random_voice_fold(_ptr(w), _ptr(b), len(b), int(bool(equal)), _ptr(wo), _ptr(bo))
+    if rc < 0:
+        _host_fail("tts_host_random_voice_fold", rc)
+    return wo, bo
 
 
 def read_wav(path):

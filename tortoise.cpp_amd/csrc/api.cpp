@@ -125,6 +125,7 @@ void tts_destroy(tts_ctx *c) {
   if (c->bigvgan) bigvgan_free(c->bigvgan);
   if (c->classifier) classifier_free(c->classifier);
   if (c->aligner) aligner_free(c->aligner);
+  if (c->rlg) random_voice_free(c->rlg);
   if (c->afe) afe_free(c->afe);
   if (c->fp16_counts) (void)hipFree(c->fp16_counts);
   delete c->tok;
@@ -477,6 +478,21 @@ int64_t tts_redact_audio(tts_ctx *c, const float *audio, int64_t n_samples, int 
     }
     return (int)total;
   });
+}
+// Random voices (random_voice.h). The loader parses its files before it asks for the device, as tts_load_classifier does. tts_random_voice is legal while a
+// session is open, as tts_voice_from_audio is: it owns its buffers, touches no AR or diffusion state and never draws from the context's std::mt19937.
+int tts_load_random_voice(tts_ctx *c, const char *auto_path, const char *diff_path) {
+  if (!c) return TTS_ERR_ARG;
+  return guarded(c, [&] { return random_voice_load(c, auto_path, diff_path); });
+}
+int tts_random_voice_dim(const tts_ctx *c, int side) { return random_voice_dim(c, side); }
+int tts_random_voice(tts_ctx *c, const uint64_t *seeds, int n, const float *z_auto, const float *z_diff, float *out_auto, float *out_diff) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return random_voice_run(c, seeds, n, z_auto, z_diff, out_auto, out_diff); });
+}
+int tts_random_voice_noise(tts_ctx *c, uint64_t seed, int side, float *out, int cap) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return random_voice_noise(c, seed, side, out, cap); });
 }
 int tts_host_stream_final_rows(const int32_t *codes, int k) { return (k < 0 || (k > 0 && !codes)) ? TTS_ERR_ARG : stream_final_rows(codes, k); }
 int tts_ar_layers(const tts_ctx *c) { return c ? ar_layers(c) : 0; }

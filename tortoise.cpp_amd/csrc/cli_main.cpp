@@ -74,6 +74,16 @@
 //   --voice and --diffusion-latent read. With the diffusion decoder a clip voice brings its own diffusion latent, so every --voice beside it needs its
 //   --diffusion-latent. Usage errors (exit 1, before a model is loaded): a missing encoder file, --dry-run 1, --devices > 1 or --exchange rccl, a wrong count of
 //   --save-voice or --diffusion-latent.
+// --voice-random SEED --random-voice-model F [--random-diffusion-voice-model G] [--save-voice PREFIX]: a random voice, what upstream's do_tts.py --voice random (its
+//   default) and tts() without clips or latents produce: RandomLatentConverter on the device (tts_load_random_voice / tts_random_voice; not in the reference),
+//   its input drawn from the device generator under SEED, an unsigned 64-bit integer; --seed and the sampler's generator are not involved. Every occurrence of
+//   --voice-random is ONE voice, numbered in command-line order together with the --voice and --voice-clips occurrences, and works with the "<index>|" turns.
+//   F / G: the two model files (tools/convert_weights.py --random-voice / --random-diffusion-voice); G is required with the diffusion decoder and optional with
+//   --decoder hifigan. As a clip voice, a random voice brings its own diffusion latent, so every --voice file beside it needs its --diffusion-latent.
+//   --save-voice PREFIX (none, or one per --voice-clips and --voice-random together, in command-line order) writes PREFIX.bin and, when the diffusion latent was
+//   made, PREFIX.diffusion.bin: the run with --voice PREFIX.bin --diffusion-latent PREFIX.diffusion.bin and the same --seed writes the same WAV bytes. A literal
+//   --voice random keeps meaning a file named `random`. Usage errors (exit 1, before a model is loaded): a missing model file, --dry-run 1, --devices > 1 or
+//   --exchange rccl, a wrong count of --save-voice or --diffusion-latent, a SEED that is not an unsigned 64-bit integer.
 // --cvvp <file> [--cvvp-amount x]: re-rank the candidates with CVVP as well (tts_load_cvvp: do these codes sound like this speaker?; not in the reference): every
 //   candidate's codes are scored against the clips of its voice, one conditioning latent per clip made once per voice (tts_cvvp_voice_audio with --mel-norms), and
 //   the candidate with the best clvp * (1 - x) + cvvp * x is kept, upstream's cvvp_amount. x defaults to 0.5 beside --clvp and to 1 without it; the side whose
@@ -98,6 +108,8 @@
 #include <csignal>
 #include <cstdio>
 #include <cstdlib>
+#include <cerrno>
+#include <cctype>
 #include <fstream>
 #include <iomanip>
 #include <iostream>
@@ -185,6 +197,8 @@ int main(int argc, char **argv) {
   bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
+  std::vector<std::string> voiceRandom;                        // parallel to voicePaths: "R" + the SEED text of a --voice-random voice ("" for every other voice)
+  std::string rlgModel, rlgDiffModel;                          // --random-voice-model / --random-diffusion-voice-model
   std::vector<std::string> voiceClips, saveVoice;              // parallel to voicePaths: the clip list of a --voice-clips voice ("" for a --voice file); --save-voice prefixes
   std::string condModel, dcondModel, melNormsPath;
   bool stream = false;
@@ -198,8 +212,11 @@ int main(int argc, char **argv) {
   for (int i = 1; i < argc - 1; ++i) {
     std::string a(argv[i]);
     if (a == "--stream-stride") stream_stride = std::stoi(argv[i + 1]);
-    else if (a == "--voice") { voicePath = argv[i + 1]; voicePaths.push_back(voicePath); voiceClips.push_back(""); }
-    else if (a == "--voice-clips") { voicePath.clear(); voicePaths.push_back(""); voiceClips.push_back(argv[i + 1]); }
+    else if (a == "--voice") { voicePath = argv[i + 1]; voicePaths.push_back(voicePath); voiceClips.push_back(""); voiceRandom.push_back(""); }
+    else if (a == "--voice-clips") { voicePath.clear(); voicePaths.push_back(""); voiceClips.push_back(argv[i + 1]); voiceRandom.push_back(""); }
+    else if (a == "--voice-random") { voicePath.clear(); voicePaths.push_back(""); voiceClips.push_back(""); voiceRandom.push_back(std::string("R") + argv[i + 1]); }
+    else if (a == "--random-voice-model") rlgModel = argv[i + 1];
+    else if (a == "--random-diffusion-voice-model") rlgDiffModel = argv[i + 1];
     else if (a == "--conditioning-model") condModel = argv[i + 1];
     else if (a == "--diffusion-conditioning-model") dcondModel = argv[i + 1];
     else if (a == "--mel-norms") melNormsPath = argv[i + 1];
@@ -330,8 +347,34 @@ int main(int argc, char **argv) {
   const bool multi_voice = n_voices > 1;
   int n_clip_voices = 0;
   for (const std::string &c : voiceClips) n_clip_voices += !c.empty();
-  const int n_file_voices = (int)voicePaths.size() - n_clip_voices;
-  if (n_clip_voices == 0 && !diffLatentPaths.empty() && (int)diffLatentPaths.size() != n_voices) {
+  // --voice-random: its SEED is an unsigned 64-bit integer, digits only
+  std::vector<uint64_t> randSeed(voicePaths.size(), 0);
+  int n_rand_voices = 0;
+  for (size_t v = 0; v < voiceRandom.size(); v++) {
+    if (!voiceRandom[v].empty()) { // a --voice-random occurrence
+      const std::string t = voiceRandom[v].substr(1);
+      char *end = nullptr;
+      errno = 0;
+      const unsigned long long sv = t.empty() || !isdigit((unsigned char)t[0]) ? 0 : strtoull(t.c_str(), &end, 10);
+      if (t.empty() || !end || *end || errno == ERANGE) { fprintf(stderr, "--voice-random %s: SEED must be an unsigned 64-bit integer\n", t.c_str()); return 1; }
+      randSeed[v] = (uint64_t)sv;
+      n_rand_voices++;
+    }
+  }
+  auto is_random = [&](int v) { return v < (int)voicePaths.size() && !voiceRandom[v].empty(); };
+  auto is_made = [&](int v) { return v < (int)voicePaths.size() && (!voiceClips[v].empty() || is_random(v)); }; // a clip or a random voice: it brings its own latents
+  const int n_file_voices = (int)voicePaths.size() - n_clip_voices - n_rand_voices;
+  const int n_made_voices = n_clip_voices + n_rand_voices;
+  if (n_rand_voices > 0) { // usage errors of --voice-random
+    if (rlgModel.empty()) { fprintf(stderr, "--voice-random needs --random-voice-model <file> (tools/convert_weights.py --random-voice)\n"); return 1; }
+    if (!use_hifigan && rlgDiffModel.empty()) { fprintf(stderr, "--voice-random with the diffusion decoder needs --random-diffusion-voice-model <file>\n"); return 1; }
+    if (dry) { fprintf(stderr, "--voice-random runs on the device: it cannot be combined with --dry-run 1\n"); return 1; }
+    if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--voice-random cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
+  } else if (!rlgModel.empty() || !rlgDiffModel.empty()) {
+    fprintf(stderr, "--random-voice-model and --random-diffusion-voice-model belong to --voice-random, which is absent\n");
+    return 1;
+  }
+  if (n_made_voices == 0 && !diffLatentPaths.empty() && (int)diffLatentPaths.size() != n_voices) {
     fprintf(stderr, "%d --diffusion-latent for %d --voice: give none (every speaker uses the model's own latent) or one per voice, in the same order\n",
             (int)diffLatentPaths.size(), n_voices);
     return 1;
@@ -341,18 +384,20 @@ int main(int argc, char **argv) {
     if (!use_hifigan && dcondModel.empty()) { fprintf(stderr, "--voice-clips with the diffusion decoder needs --diffusion-conditioning-model <file>\n"); return 1; }
     if (dry) { fprintf(stderr, "--voice-clips runs on the device: it cannot be combined with --dry-run 1\n"); return 1; }
     if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--voice-clips cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
-    if (!saveVoice.empty() && (int)saveVoice.size() != n_clip_voices) {
-      fprintf(stderr, "%d --save-voice for %d --voice-clips: give none or one per --voice-clips, in the same order\n", (int)saveVoice.size(), n_clip_voices);
+  } else if ((!saveVoice.empty() && n_rand_voices == 0) || !condModel.empty() || !dcondModel.empty() || !melNormsPath.empty()) {
+    fprintf(stderr, "--save-voice, --conditioning-model, --diffusion-conditioning-model and --mel-norms belong to --voice-clips, which is absent\n");
+    return 1;
+  }
+  if (n_made_voices > 0) { // what the clip and the random voices share
+    if (!saveVoice.empty() && (int)saveVoice.size() != n_made_voices) {
+      fprintf(stderr, "%d --save-voice for %d --voice-clips and --voice-random: give none or one per such voice, in the same order\n", (int)saveVoice.size(), n_made_voices);
       return 1;
     }
     if (!use_hifigan && (int)diffLatentPaths.size() != n_file_voices) {
-      fprintf(stderr, "%d --diffusion-latent for %d --voice beside --voice-clips: a clip voice brings its own diffusion latent, so every --voice needs one\n",
+      fprintf(stderr, "%d --diffusion-latent for %d --voice beside --voice-clips or --voice-random: such a voice brings its own diffusion latent, so every --voice needs one\n",
               (int)diffLatentPaths.size(), n_file_voices);
       return 1;
     }
-  } else if (!saveVoice.empty() || !condModel.empty() || !dcondModel.empty() || !melNormsPath.empty()) {
-    fprintf(stderr, "--save-voice, --conditioning-model, --diffusion-conditioning-model and --mel-norms belong to --voice-clips, which is absent\n");
-    return 1;
   }
   // --cvvp (usage errors before any model is loaded)
   const bool have_cvvp = !cvvpPath.empty();
@@ -361,7 +406,7 @@ int main(int argc, char **argv) {
     if (!have_cvvp_amount) cvvp_amount = clvpPath.empty() ? 1.0 : 0.5;
     if (!(cvvp_amount >= 0.0 && cvvp_amount <= 1.0)) { fprintf(stderr, "--cvvp-amount %g: a value in 0 .. 1\n", cvvp_amount); return 1; }
     if (devices > 1 || exchange == "rccl" || shard >= 0) { fprintf(stderr, "--cvvp cannot be combined with --devices > 1 or --exchange rccl\n"); return 1; }
-    if (n_file_voices > 0 || voicePaths.empty()) {
+    if (n_file_voices + n_rand_voices > 0 || voicePaths.empty()) {
       fprintf(stderr, "--cvvp scores the candidates against the audio clips of their voice: a --voice latent file holds no audio (give every voice as --voice-clips)\n");
       return 1;
     }
@@ -373,8 +418,14 @@ int main(int argc, char **argv) {
   // the --diffusion-latent file of every voice ("" for a clip voice, or when none is given): the k-th occurrence belongs to the k-th --voice
   std::vector<std::string> diffLatentOf(n_voices);
   for (int v = 0, k = 0; v < (int)voicePaths.size(); v++)
-    if (voiceClips[v].empty() && k < (int)diffLatentPaths.size()) diffLatentOf[v] = diffLatentPaths[k++];
-  const bool clip_latents = n_clip_voices > 0 && !dcondModel.empty(); // the clip voices bring diffusion latents
+    if (!is_made(v) && k < (int)diffLatentPaths.size()) diffLatentOf[v] = diffLatentPaths[k++];
+  const bool rand_latents = n_rand_voices > 0 && !rlgDiffModel.empty(); // the random voices bring diffusion latents
+  // the clip voices bring diffusion latents (the name covers both kinds from here on: with the diffusion decoder either kind must bring them)
+  const bool clip_latents = (n_clip_voices > 0 && !dcondModel.empty()) || rand_latents;
+  const bool clip_enc_latents = n_clip_voices > 0 && !dcondModel.empty();
+  std::vector<int> saveIdx(n_voices, -1); // the --save-voice of every clip / random voice
+  for (int v = 0, k = 0; v < (int)voicePaths.size(); v++)
+    if (is_made(v)) saveIdx[v] = k++;
   if (multi_voice && (devices > 1 || exchange == "rccl" || shard >= 0)) {
     fprintf(stderr, "several --voice cannot be combined with --devices > 1 or --exchange rccl (the conditioning broadcast carries one voice; one process runs all turns)\n");
     return 1;
@@ -530,7 +581,7 @@ int main(int argc, char **argv) {
   if (n_clip_voices > 0) {
     if (use_cvvp && tts_load_cvvp(ctx, cvvpPath.c_str())) return die(ctx, "cvvp_model_load");
     if (tts_load_voice_encoder(ctx, condModel.c_str())) return die(ctx, "--conditioning-model");
-    if (clip_latents && tts_load_diffusion_conditioning_encoder(ctx, dcondModel.c_str())) return die(ctx, "--diffusion-conditioning-model");
+    if (clip_enc_latents && tts_load_diffusion_conditioning_encoder(ctx, dcondModel.c_str())) return die(ctx, "--diffusion-conditioning-model");
     std::vector<float> norms;
     if (!melNormsPath.empty()) {
       norms.resize(80);
@@ -541,8 +592,9 @@ int main(int argc, char **argv) {
     vo.struct_size = sizeof vo;
     tts_voice_audio_opts_init(&vo);
     vo.mel_norms80 = norms.empty() ? nullptr : norms.data();
-    for (int v = 0, k = 0; v < n_voices; v++) {
+    for (int v = 0; v < n_voices; v++) {
       if (voiceClips[v].empty()) continue;
+      const int k = saveIdx[v];
       std::vector<float> samples;
       std::vector<int64_t> lens;
       std::vector<int32_t> rates;
@@ -560,8 +612,8 @@ int main(int argc, char **argv) {
       }
       if (lens.empty()) { fprintf(stderr, "--voice-clips: an empty clip list\n"); return 1; }
       clip1024[v].resize(1024);
-      if (clip_latents) clip2048[v].resize(2048);
-      if (tts_voice_from_audio(ctx, samples.data(), lens.data(), rates.data(), (int)lens.size(), &vo, clip1024[v].data(), clip_latents ? clip2048[v].data() : nullptr))
+      if (clip_enc_latents) clip2048[v].resize(2048);
+      if (tts_voice_from_audio(ctx, samples.data(), lens.data(), rates.data(), (int)lens.size(), &vo, clip1024[v].data(), clip_enc_latents ? clip2048[v].data() : nullptr))
         return die(ctx, "--voice-clips");
       if (use_cvvp) {
         cvvp_clips[v] = (int)lens.size();
@@ -571,14 +623,43 @@ int main(int argc, char **argv) {
       if (!saveVoice.empty()) {
         std::ofstream f1(saveVoice[k] + ".bin", std::ios::binary);
         if (!f1 || !f1.write((const char *)clip1024[v].data(), 1024 * sizeof(float))) { std::cerr << "Error: Unable to write " << saveVoice[k] << ".bin" << std::endl; return 1; }
-        if (clip_latents) {
+        if (clip_enc_latents) {
           std::ofstream f2(saveVoice[k] + ".diffusion.bin", std::ios::binary);
           if (!f2 || !f2.write((const char *)clip2048[v].data(), 2048 * sizeof(float))) { std::cerr << "Error: Unable to write " << saveVoice[k] << ".diffusion.bin" << std::endl; return 1; }
         }
       }
-      k++;
     }
     mark("voice from clips");
+  }
+  // --voice-random: every random voice's two latents in ONE call, before any other model is loaded; nothing here draws from the sampler's generator
+  if (n_rand_voices > 0) {
+    if (tts_load_random_voice(ctx, rlgModel.c_str(), rand_latents ? rlgDiffModel.c_str() : nullptr)) return die(ctx, "--random-voice-model");
+    if (tts_random_voice_dim(ctx, TTS_RANDOM_VOICE_AUTO) != 1024 || (rand_latents && tts_random_voice_dim(ctx, TTS_RANDOM_VOICE_DIFFUSION) != 2048)) {
+      fprintf(stderr, "--random-voice-model / --random-diffusion-voice-model: %d and %d channels, 1024 and 2048 expected\n", tts_random_voice_dim(ctx, TTS_RANDOM_VOICE_AUTO),
+              tts_random_voice_dim(ctx, TTS_RANDOM_VOICE_DIFFUSION));
+      return 1;
+    }
+    std::vector<uint64_t> seeds;
+    for (int v = 0; v < n_voices; v++)
+      if (is_random(v)) seeds.push_back(randSeed[v]);
+    std::vector<float> r1((size_t)n_rand_voices * 1024), r2(rand_latents ? (size_t)n_rand_voices * 2048 : 0);
+    if (tts_random_voice(ctx, seeds.data(), n_rand_voices, nullptr, nullptr, r1.data(), rand_latents ? r2.data() : nullptr)) return die(ctx, "--voice-random");
+    for (int v = 0, j = 0; v < n_voices; v++) {
+      if (!is_random(v)) continue;
+      clip1024[v].assign(r1.begin() + (size_t)j * 1024, r1.begin() + (size_t)(j + 1) * 1024);
+      if (rand_latents) clip2048[v].assign(r2.begin() + (size_t)j * 2048, r2.begin() + (size_t)(j + 1) * 2048);
+      if (!saveVoice.empty()) {
+        const int k = saveIdx[v];
+        std::ofstream f1(saveVoice[k] + ".bin", std::ios::binary);
+        if (!f1 || !f1.write((const char *)clip1024[v].data(), 1024 * sizeof(float))) { std::cerr << "Error: Unable to write " << saveVoice[k] << ".bin" << std::endl; return 1; }
+        if (rand_latents) {
+          std::ofstream f2(saveVoice[k] + ".diffusion.bin", std::ios::binary);
+          if (!f2 || !f2.write((const char *)clip2048[v].data(), 2048 * sizeof(float))) { std::cerr << "Error: Unable to write " << saveVoice[k] << ".diffusion.bin" << std::endl; return 1; }
+        }
+      }
+      j++;
+    }
+    mark("random voices");
   }
   if (tts_tokenizer_load(ctx, (modelsDir + "/tokenizer.json").c_str()) < 0) return die(ctx, "tokenizer");
   std::vector<int32_t> tokens(4096);
@@ -629,7 +710,7 @@ int main(int argc, char **argv) {
   if (multi_voice) {
     voices.resize((size_t)n_voices * 1024);
     for (int v = 0; v < n_voices; v++) {
-      if (!voiceClips[v].empty()) { std::copy(clip1024[v].begin(), clip1024[v].end(), voices.begin() + (size_t)v * 1024); continue; }
+      if (is_made(v)) { std::copy(clip1024[v].begin(), clip1024[v].end(), voices.begin() + (size_t)v * 1024); continue; }
       std::ifstream f(voicePaths[v], std::ios::binary);
       if (!f || !f.read((char *)(voices.data() + (size_t)v * 1024), 1024 * sizeof(float))) {
         std::cerr << "Error: Unable to read 1024 floats from " << voicePaths[v] << std::endl;
@@ -638,7 +719,7 @@ int main(int argc, char **argv) {
     }
     if (!use_hifigan && (!diffLatentPaths.empty() || clip_latents)) diff_latents.resize((size_t)n_voices * 2048);
     for (int v = 0; v < n_voices && !diff_latents.empty(); v++) {
-      if (!voiceClips[v].empty()) { std::copy(clip2048[v].begin(), clip2048[v].end(), diff_latents.begin() + (size_t)v * 2048); continue; }
+      if (is_made(v)) { std::copy(clip2048[v].begin(), clip2048[v].end(), diff_latents.begin() + (size_t)v * 2048); continue; }
       std::ifstream f(diffLatentOf[v], std::ios::binary);
       if (!f || !f.read((char *)(diff_latents.data() + (size_t)v * 2048), 2048 * sizeof(float))) {
         std::cerr << "Error: Unable to read 2048 floats from " << diffLatentOf[v] << std::endl;

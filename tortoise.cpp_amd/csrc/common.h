@@ -95,6 +95,7 @@ struct HifiganState;
 struct BigvganState;
 struct ClassifierState;
 struct AlignerState;
+struct RandomVoiceState;
 struct AfeState;
 struct Tokenizer;
 struct SamplerPool;
@@ -143,6 +144,7 @@ struct tts_ctx {
   tts::BigvganState *bigvgan = nullptr; // BigVGAN vocoder: mel -> waveform beside UnivNet (bigvgan.h, part of hifigan.hip's translation unit; not in the reference)
   tts::ClassifierState *classifier = nullptr; // tortoise-detect: waveform -> probability that the clip is synthesized (classifier.h, part of hifigan.hip's translation unit through bigvgan.h; not in the reference)
   tts::AlignerState *aligner = nullptr; // wav2vec2 CTC aligner: waveform -> one token id per frame, for tts_align_audio / tts_redact_audio (aligner.h, part of hifigan.hip's translation unit through classifier.h; not in the reference)
+  tts::RandomVoiceState *rlg = nullptr; // random voices: upstream's RandomLatentConverter, one model per side (random_voice.h, part of extras.hip's translation unit; not in the reference)
   tts::AfeState *afe = nullptr; // audio front-end: its tables and buffers, made at the first tts_voice_from_audio / tts_audio_mel (audio_frontend.hip)
   tts::Tokenizer *tok = nullptr;
   tts::ArSession *session = nullptr;        // non-null while a session is open: tts_ar_begin*, tts_autoregressive* and tts_hifigan_stream then return TTS_ERR_STATE
@@ -611,6 +613,15 @@ int max_alignment(const std::vector<int32_t> &s1, const std::vector<int32_t> &s2
 int ctc_align(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, const std::vector<int32_t> &text, int64_t n_samples,
               std::vector<int64_t> &offsets, std::string &err);
 int redact_spans(const std::vector<int32_t> &text, std::vector<int32_t> &clean, std::vector<int32_t> &intervals, std::string &err);
+// ---- random voices (random_voice.h; the fold and the blend: host_logic.cpp) ----
+// One layer's operands as the kernel reads them: w_out = fl(w * scale) and b_out = fl(b * lr_mul) for an EqualLinear (equal != 0; lr_mul = 0.1,
+// scale = lr_mul / sqrt(dim), both rounded to f32 first, as torch rounds a Python scalar that meets an f32 tensor), copies for the plain Linear.
+void rlg_fold(const float *w, const float *b, int dim, int equal, float *w_out, float *b_out);
+int random_voice_load(tts_ctx *ctx, const char *auto_path, const char *diff_path);
+void random_voice_free(RandomVoiceState *);
+int random_voice_dim(const tts_ctx *ctx, int side);
+int random_voice_run(tts_ctx *ctx, const uint64_t *seeds, int n, const float *z_auto, const float *z_diff, float *out_auto, float *out_diff);
+int random_voice_noise(tts_ctx *ctx, uint64_t seed, int side, float *out, int cap);
 // Latent rows of a one-candidate utterance that are final after its first k sampled codes (none of them the stop token): the rows whose inputs
 // 8192, c_0 .. c_{k-1} pad_codes will not rewrite, cut where trimmed_latent_rows will cut (tts_hifigan_stream; host_logic.cpp)
 int stream_final_rows(const int32_t *codes, int k);

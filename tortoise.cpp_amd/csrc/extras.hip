@@ -824,3 +824,4 @@ int diff_cond_enc_latent(tts_ctx *ctx, const float *mel, const int32_t *frames, 
 }
 
 } // namespace tts
+#include "random_voice.h" // random voices (RandomLatentConverter): the same translation unit as the voice encoder whose latent it replaces

@@ -1705,3 +1705,44 @@ extern "C" int tts_host_redact_spans(const char *text, char *clean_out, int cap,
   for (size_t i = 0; i < iv.size(); i++) intervals_out[i] = iv[i];
   return rc;
 }
+
+// ---- random voices (random_voice.h): the load-time fold and the blend of several voices ----
+namespace tts {
+void rlg_fold(const float *w, const float *b, int dim, int equal, float *w_out, float *b_out) {
+  const size_t nw = (size_t)dim * dim;
+  if (!equal) {
+    if (w_out != w) memcpy(w_out, w, nw * sizeof(float));
+    if (b_out != b) memcpy(b_out, b, (size_t)dim * sizeof(float));
+    return;
+  }
+  const double lr_mul_d = 0.1;
+  const float lr_mul = (float)lr_mul_d, scale = (float)(lr_mul_d / std::sqrt((double)dim));
+  for (size_t i = 0; i < nw; i++) w_out[i] = w[i] * scale;
+  for (int i = 0; i < dim; i++) b_out[i] = b[i] * lr_mul;
+}
+} // namespace tts
+extern "C" int tts_host_random_voice_fold(const float *w, const float *b, int dim, int equal, float *w_out, float *b_out) {
+  if (!w || !b || !w_out || !b_out || dim < 1 || dim > 65536) return TTS_ERR_ARG;
+  tts::rlg_fold(w, b, dim, equal, w_out, b_out);
+  return TTS_OK;
+}
+// upstream's load_voices rule for several named voices (the mean of their latents), generalised to weights: out[i] = sum_v w[v] x[v][i] / sum_v w[v],
+// accumulated in double in voice order, rounded once
+extern "C" int tts_host_blend_voices(const float *latents, const float *weights, int n, int dim, float *out) {
+  if (!latents || !out || n < 1 || dim < 1) return TTS_ERR_ARG;
+  double wsum = 0;
+  for (int v = 0; v < n; v++) {
+    const double wv = weights ? (double)weights[v] : 1.0;
+    if (!std::isfinite(wv)) return TTS_ERR_ARG;
+    wsum += wv;
+  }
+  if (!(wsum > 0) || !std::isfinite(wsum)) return TTS_ERR_ARG;
+  for (size_t i = 0; i < (size_t)n * dim; i++)
+    if (!std::isfinite(latents[i])) return TTS_ERR_ARG;
+  for (int i = 0; i < dim; i++) {
+    double a = 0;
+    for (int v = 0; v < n; v++) a += (weights ? (double)weights[v] : 1.0) * (double)latents[(size_t)v * dim + i];
+    out[i] = (float)(a / wsum);
+  }
+  return TTS_OK;
+}

@@ -793,6 +793,47 @@ def aligner_forward(tensors, wave, dtype=np.float64):
     return lin(h, "lm_head")
 
 
+RANDOM_VOICE_LR_MUL = 0.1  # EqualLinear(..., lr_mul=0.1): a constructor constant of upstream's RandomLatentConverter, not a tensor
+
+
+def random_voice_tensor_shapes(dim=1024, layers=6):
+    """{name: PyTorch shape} of one random-voice file (tts_load_random_voice): upstream's RandomLatentConverter state dict, layers.{0..layers-1}.weight
+    [dim][dim] and .bias [dim]; the first layers - 1 are EqualLinear, the last a plain nn.Linear. Restated from memory, unpinned against upstream."""
+    t = {}
+    for l in range(layers):
+        t["layers.%d.weight" % l] = (dim, dim)
+        t["layers.%d.bias" % l] = (dim,)
+    return t
+
+
+def random_voice_tensors(dim=1024, seed=1270, layers=6):
+    """{name: float32 array}: upstream's own initialisation of EqualLinear, weight = randn / lr_mul, but biases N(0, 2) in place of its zeros (a zero bias would
+    hide an error in the bias scale: b * lr_mul is then of order 0.2 beside pre-activations of order 1); the last layer nn.Linear's default, uniform
+    (-1 / sqrt(dim), 1 / sqrt(dim)) for weight and bias, the bias widened to N(0, 0.1) so that it shows beside the output."""
+    g = _Gen(seed)
+    t = {}
+    for l in range(layers):
+        if l < layers - 1:
+            t["layers.%d.weight" % l] = (g.normal((dim, dim), 1.0) / np.float32(RANDOM_VOICE_LR_MUL)).astype(np.float32)
+            t["layers.%d.bias" % l] = g.normal((dim,), 2.0)
+        else:
+            k = 1.0 / np.sqrt(dim)
+            t["layers.%d.weight" % l] = g.rng.uniform(-k, k, (dim, dim)).astype(np.float32)
+            t["layers.%d.bias" % l] = g.normal((dim,), 0.1)
+    return t
+
+
+def write_random_voice(path, dim, seed, layers=6):
+    """One side's file for tts_load_random_voice (dim 1024: rlg_auto, 2048: rlg_diffuser). Upstream's weights are not available offline: the names are
+    random_voice_tensor_shapes(...), the values random_voice_tensors(...). Returns the tensors."""
+    t = random_voice_tensors(dim, seed, layers)
+    w = GgmlWriter(path)
+    for name, arr in t.items():
+        w.add(name, arr)
+    w.close()
+    return t
+
+
 def write_all(out_dir, ar_layers=30, diff_main=10, diff_tail=3, diff_integ=3, diff_lc=4, seed=1234):
     import os
     os.makedirs(out_dir, exist_ok=True)
