@@ -865,6 +865,49 @@ int tts_random_voice_noise(tts_ctx *ctx, uint64_t seed, int side, float *out, in
 int tts_host_blend_voices(const float *latents, const float *weights, int n, int dim, float *out);
 int tts_host_random_voice_fold(const float *w, const float *b, int dim, int equal, float *w_out, float *b_out);
 
+/* ---- speech codes from audio: upstream's DVAE encoder (not in the reference; additions within version 8, no prototype changed) -------------------- */
+/* get_codebook_indices of the discrete VAE upstream tortoise-tts trains its AR model on (dvae.pth: DiscreteVAE(channels 80, positional_dims 1, num_tokens
+ * 8192, codebook_dim 512, hidden_dim 512, num_layers 2, num_resnet_blocks 3, kernel_size 3, no normalization)): every other path of this library goes text ->
+ * codes -> audio, this one goes audio -> codes. Upstream's source and weights are not available offline: the model is stated from memory (INTEGRATION.md
+ * section 20, DESIGN.md "What pins the DVAE"), pinned between this library and two float64 restatements; unpinned against upstream; nothing is claimed about
+ * code accuracy on real audio or about how a re-voiced clip sounds.
+ *   h = ReLU(Conv1d(80 -> 512, k 3, stride 2, pad 1)(mel));  h = ReLU(Conv1d(512 -> 1024, k 3, stride 2, pad 1)(h))                 encoder.0.0, encoder.1.0
+ *   3 x:  h = h + Conv1(ReLU(Conv3(ReLU(Conv3(h)))))   (pad 1; no activation on a block's input)                                    encoder.{2,3,4}.net.{0,2,4}
+ *   z = Conv1d(1024 -> 512, k 1)(h);  code[t] = argmin_j |z[t] - E[:, j]|^2, the lowest index on a tie                             encoder.5, codebook.embed [512][8192]
+ * The mel is the AR side's: 22 050 Hz, 80 bands, log, divided by mel_norms; tts_audio_mel with bands 80 and full_clips 1. f32 throughout (csrc/dvae.h).
+ * File: the reference's container format, upstream's state-dict names under "dvae." (tools/convert_weights.py --dvae drops the decoder and the EMA buffers);
+ * every size is read from the tensor shapes, an optional "dvae.config" = {stride} (default 2).
+ * tts_load_dvae: TTS_ERR_FORMAT for a missing or misshapen tensor, an unknown tensor, or sizes the kernels do not tile (1 .. 128 mel channels; odd kernel sizes up
+ *   to 7; stride 1 .. 4; channel counts multiples of 64 up to 4096; codebook dim a multiple of 32 up to 512; tokens a multiple of 32 up to 65536). The file is
+ *   parsed before the device is asked for: a host-only context returns TTS_ERR_FORMAT for a broken file and TTS_ERR_HIP for a good one.
+ * tts_dvae_rows: codes of a clip of mel_frames frames under upstream's configuration, (T - 1) / 2 + 1 twice (tts_cvvp_rows' formula); pure. TTS_ERR_ARG below 1.
+ * tts_dvae_tokens, tts_dvae_dim: the codebook's size (8192 for upstream's) and the channels of a z_out row (512), 0 before tts_load_dvae.
+ * tts_dvae_codes: mel80 = the clips' mels back to back, clip s band-major [80][frames[s]]. One launch sequence for the whole ragged batch. codes_out
+ *   [n_clips][code_stride], z_out NULL or [n_clips][code_stride][dim] (the encoder's output in front of the quantiser): the first n_codes_out[s] entries of a clip
+ *   are written, the rest is left alone. A clip's bits are the same alone or in any batch, and two calls agree. Legal while an AR or a diffusion session is open.
+ *   Every check runs before any device work and a refused call writes nothing: TTS_ERR_HIP on a host-only context; TTS_ERR_STATE before tts_load_dvae;
+ *   TTS_ERR_ARG for a null pointer, n_clips < 1, frames < 1, a non-finite mel value, or a clip with more codes than code_stride; TTS_ERR_LIMIT above
+ *   TTS_DVAE_MAX_CLIPS clips or TTS_DVAE_MAX_FRAMES frames in a clip. Profiler families: "dvae_conv", "dvae_vq" (work = FLOPs).
+ * tts_dvae_codes_audio: clips as tts_voice_from_audio takes them; the audio front end's mel of the WHOLE clip (full_clips 1 whatever opts holds; mel_norms80
+ *   and the resampler as in opts) goes straight into the encoder's input. Bit-identical to tts_dvae_codes of tts_audio_mel(bands 80, full_clips 1)'s output.
+ *   Also TTS_ERR_ARG for what tts_audio_mel refuses (512 samples or fewer at 22 050 Hz, a non-finite sample); TTS_ERR_STATE for a model that reads other than 80 bands.
+ * tts_ar_latents_for_codes: tts_ar_begin(one candidate) + tts_ar_prefill + tts_host_pad_codes + tts_ar_latents + tts_host_trimmed_rows as one call, bit for
+ *   bit that sequence: the latents of a recording's codes under its transcript and ANOTHER voice, which diffusion + vocoder or HiFi-GAN re-speak. latents_out
+ *   [500][1024]: the first *rows_out rows are written. Never touches the generator. Replaces any tts_ar_begin* state; TTS_ERR_STATE while a session is open;
+ *   TTS_ERR_ARG for a null pointer, n_text or n_codes < 1 or a code outside 0 .. 8191; TTS_ERR_LIMIT above 500 codes (chunking a longer recording is the caller's). */
+#define TTS_DVAE_MAX_CLIPS 256
+#define TTS_DVAE_MAX_FRAMES 16384
+int tts_load_dvae(tts_ctx *ctx, const char *path);
+int tts_dvae_rows(int mel_frames);
+int tts_dvae_tokens(const tts_ctx *ctx);
+int tts_dvae_dim(const tts_ctx *ctx);
+int tts_dvae_codes(tts_ctx *ctx, const float *mel80, const int32_t *frames, int n_clips, int32_t *codes_out, int32_t *n_codes_out, int code_stride,
+                   float *z_out);
+int tts_dvae_codes_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips,
+                         const tts_voice_audio_opts *opts, int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out);
+int tts_ar_latents_for_codes(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice1024, const int32_t *codes, int n_codes,
+                             int32_t *rows_out, float *latents_out);
+
 /* ---- output -------------------------------------------------------------------------------- */
 /* writeWav (main.cpp:4821-4868): RIFF, fmt 16 B, tag 3 (IEEE float), mono, 32-bit. */
 int tts_write_wav(const char *path, const float *samples, int64_t n, int sample_rate);

@@ -31,7 +31,7 @@ import tortoise_cpp_amd_loader  # noqa: E402
 
 tortoise_cpp_amd_loader.load()
 from tortoise_cpp_amd.synth_weights import (GgmlWriter, aligner_tensor_shapes, bigvgan_filter, bigvgan_tensor_shapes, classifier_tensor_shapes,  # noqa: E402
-                                            random_voice_tensor_shapes)
+                                            dvae_tensor_shapes, random_voice_tensor_shapes)
 
 
 def _np(t):
@@ -371,6 +371,45 @@ def convert_random_voice(sd, path):
     return L, D
 
 
+DVAE_DROPPED = ("decoder.", "codebook.cluster_size", "codebook.embed_avg", "codebook.initted", "codes", "total_codes", "loss_fn.")
+
+
+def convert_dvae(sd, path, stride=2):
+    """dvae.pth of upstream tortoise-tts (DiscreteVAE's state dict) -> the file tts_load_dvae reads: the encoder's convolutions and codebook.embed under
+    `dvae.`, unchanged, plus dvae.config = (stride,) (no shape holds it; upstream: 2). Only get_codebook_indices is wanted, so the decoder, the EMA buffers
+    (codebook.cluster_size, codebook.embed_avg, codebook.initted), the recorded codes and the loss are DROPPED; any other unknown tensor is an error, as is a
+    missing or mis-sized one (the names are restated from memory: --list-expected dvae). Every size is read from the state dict. Returns
+    (strided layers, ResBlocks, hidden channels, codebook dim, tokens)."""
+    sd = {k: v for k, v in sd.items() if not k.startswith(DVAE_DROPPED)}
+    L = 0
+    while "encoder.%d.0.weight" % L in sd:
+        L += 1
+    nb = 0
+    while "encoder.%d.net.0.weight" % (L + nb) in sd:
+        nb += 1
+    if L < 1 or "codebook.embed" not in sd or "encoder.%d.weight" % (L + nb) not in sd:
+        raise SystemExit("convert_dvae: no encoder.N.0.weight, encoder.%d.weight or codebook.embed (not a DiscreteVAE state dict?)" % (L + nb))
+    w0 = sd["encoder.0.0.weight"]
+    dim, tokens = (int(v) for v in sd["codebook.embed"].shape)
+    exp = dvae_tensor_shapes(channels=int(w0.shape[1]), hidden=int(w0.shape[0]), layers=L, blocks=nb, dim=dim, tokens=tokens, k=int(w0.shape[2]), stride=stride)
+    for k in sorted(sd):
+        if "dvae." + k not in exp:
+            raise SystemExit("convert_dvae: unexpected tensor '%s'" % k)
+    w = GgmlWriter(path)
+    for name, shape in exp.items():
+        if name == "dvae.config":
+            w.add(name, np.array([stride], np.float32))
+            continue
+        k = name[len("dvae."):]
+        if k not in sd:
+            raise SystemExit("convert_dvae: tensor '%s' is missing" % k)
+        if tuple(sd[k].shape) != tuple(shape):
+            raise SystemExit("convert_dvae: tensor '%s' has shape %s, expected %s" % (k, list(sd[k].shape), list(shape)))
+        w.add(name, _np(sd[k]))
+    w.close()
+    return L, nb, int(sd["encoder.%d.0.weight" % (L - 1)].shape[0]), dim, tokens
+
+
 # ---- what each checkpoint is expected to hold (--list-expected) ---------------------------------------------------------------------
 # name -> PyTorch shape as tortoise-tts stores it, for the upstream architecture (or the one given). Written from the loaders' contracts
 # (main.cpp:682-792, 1244-1536, 1808-1923; csrc/extras.hip for the three containers the reference does not have), NOT from a checkpoint:
@@ -561,12 +600,14 @@ def expected_tensors(kind, **arch):
         out.update({k[len("aligner."):]: v for k, v in aligner_tensor_shapes(config=False, **arch).items() if k != "aligner.vocab"})
     elif kind == "random_voice":  # rlg_auto.pth (dim 1024, the default) / rlg_diffuser.pth (dim 2048): a RandomLatentConverter's state dict
         out.update(random_voice_tensor_shapes(arch.get("dim", 1024), arch.get("layers", 6)))
+    elif kind == "dvae":  # dvae.pth: DiscreteVAE's encoder and codebook.embed (the decoder and the EMA buffers are dropped; dvae.config is the converter's)
+        out.update({k[len("dvae."):]: v for k, v in dvae_tensor_shapes(config=False, **arch).items()})
     else:
         raise ValueError(kind)
     return out
 
 
-EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan", "classifier", "aligner", "random_voice")
+EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan", "classifier", "aligner", "random_voice", "dvae")
 
 
 def container_shape(kind, name, shape):
@@ -646,6 +687,9 @@ def main():
                                            "(the AR side of tts_load_random_voice; not in the reference)")
     ap.add_argument("--random-diffusion-voice", help="rlg_diffuser.pth of upstream tortoise-tts (RandomLatentConverter, 2048 channels) -> "
                                                      "ggml-random-diffusion-voice-model.bin (the diffusion side of tts_load_random_voice; not in the reference)")
+    ap.add_argument("--dvae", help="dvae.pth of upstream tortoise-tts (DiscreteVAE) -> ggml-dvae-model.bin (speech codes from audio, tts_load_dvae: the encoder and "
+                                   "the codebook; the decoder and the EMA buffers are dropped; not in the reference)")
+    ap.add_argument("--dvae-stride", type=int, default=2, help="with --dvae: the strided layers' stride (no shape holds it; upstream: 2)")
     ap.add_argument("--out")
     ap.add_argument("--list-expected", nargs="*", metavar="KIND", help="print every tensor name / shape the converter looks for per checkpoint kind (%s; "
                                                                         "default: all, upstream architecture) and exit" % ", ".join(EXPECTED_KINDS))
@@ -719,6 +763,9 @@ def main():
     if a.random_diffusion_voice:
         print("ggml-random-diffusion-voice-model.bin: %d layers of %d channels"
               % convert_random_voice(load(a.random_diffusion_voice), os.path.join(a.out, "ggml-random-diffusion-voice-model.bin")))
+    if a.dvae:
+        print("ggml-dvae-model.bin: %d strided layers, %d ResBlocks of %d channels, codebook %d x %d tokens"
+              % convert_dvae(load(a.dvae), os.path.join(a.out, "ggml-dvae-model.bin"), a.dvae_stride))
     if a.vocoder:
         checked("vocoder", load(a.vocoder), a.vocoder)
         print("ggml-vocoder-model.bin: %d res stacks" % convert_vocoder(load(a.vocoder), os.path.join(a.out, "ggml-vocoder-model.bin")))

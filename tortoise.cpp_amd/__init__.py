@@ -124,6 +124,9 @@ def lib():
         "tts_host_ctc_align": (ci, [vp, ci, vp, ci, ci, C.c_char_p, C.c_int64, vp, ci]), "tts_host_redact_spans": (ci, [C.c_char_p, vp, ci, vp, ci]),
         "tts_load_random_voice": (ci, [vp, C.c_char_p, C.c_char_p]), "tts_random_voice_dim": (ci, [vp, ci]),
         "tts_random_voice": (ci, [vp, vp, ci, vp, vp, vp, vp]), "tts_random_voice_noise": (ci, [vp, C.c_uint64, ci, vp, ci]),
+        "tts_load_dvae": (ci, [vp, C.c_char_p]), "tts_dvae_rows": (ci, [ci]), "tts_dvae_tokens": (ci, [vp]), "tts_dvae_dim": (ci, [vp]),
+        "tts_dvae_codes": (ci, [vp, vp, vp, ci, vp, vp, ci, vp]), "tts_dvae_codes_audio": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
+        "tts_ar_latents_for_codes": (ci, [vp, vp, ci, vp, vp, ci, vp, vp]),
         "tts_host_blend_voices": (ci, [vp, vp, ci, ci, vp]), "tts_host_random_voice_fold": (ci, [vp, vp, ci, ci, vp, vp]),
         "tts_hifigan_stream": (ci, [vp, vp, ci, vp, ci, C.c_uint, ci, vp, vp, vp, vp, vp, vp]), "tts_hifigan_stream_recaptures": (ci, [vp]),
         "tts_host_stream_final_rows": (ci, [vp, ci]),
@@ -734,6 +737,68 @@ class Engine:
         prob, logits = np.empty(len(clips), np.float32), np.empty((len(clips), 2), np.float32)
         self._ck(self.L.tts_classify_audio(self.h, _ptr(a), _ptr(n), _ptr(r), len(clips), _ptr(prob), _ptr(logits)))
         return prob, logits
+
+    # ---- the DVAE encoder (not in the reference): speech codes from audio ----
+    def load_dvae(self, path):
+        self._ck(self.L.tts_load_dvae(self.h, path.encode()))
+
+    @staticmethod
+    def dvae_rows(mel_frames):
+        """codes the DVAE encoder's two strided convolutions make of mel_frames frames (pure: no context, no GPU)"""
+        return lib().tts_dvae_rows(int(mel_frames))
+
+    @property
+    def dvae_tokens(self):
+        return self.L.tts_dvae_tokens(self.h)
+
+    def _dvae_out(self, n_clips, stride, z):
+        codes, nc = np.zeros((n_clips, stride), np.int32), np.zeros(n_clips, np.int32)
+        zz = np.zeros((n_clips, stride, self.L.tts_dvae_dim(self.h)), np.float32) if z else None
+        return codes, nc, zz
+
+    @staticmethod
+    def _dvae_split(codes, nc, zz):
+        out = [codes[i, :nc[i]].copy() for i in range(len(nc))]
+        return out if zz is None else (out, [zz[i, :nc[i]].copy() for i in range(len(nc))])
+
+    def dvae_codes(self, mels, z=False):
+        """mels: list of [80, T_c] log-mels (audio_mel(clip, rate, 80, mel_norms, full_clips=True)). Returns a list of int32 code arrays, one per clip
+        (tts_dvae_codes: one call for the ragged batch); z=True: (codes, list of float32 [codes, dim], the encoder's output in front of the quantiser)."""
+        if not len(mels):
+            raise TtsError("dvae_codes: no clips")
+        frames = np.array([np.shape(m)[1] for m in mels], np.int32)
+        mel = np.ascontiguousarray(np.concatenate([np.asarray(m, np.float32).reshape(-1) for m in mels]))
+        stride = max(1, max(self.dvae_rows(int(f)) for f in frames))
+        codes, nc, zz = self._dvae_out(len(mels), stride, z)
+        self._ck(self.L.tts_dvae_codes(self.h, _ptr(mel), _ptr(frames), len(mels), _ptr(codes), _ptr(nc), stride, None if zz is None else _ptr(zz)))
+        return self._dvae_split(codes, nc, zz)
+
+    def dvae_codes_audio(self, clips, rates, mel_norms=None, z=False):
+        """the same from samples: clips and rates as voice_from_audio, always the whole clip; the mel never leaves the device"""
+        rates = [int(rates)] * len(clips) if np.isscalar(rates) else [int(r) for r in rates]
+        if len(rates) != len(clips) or not len(clips):
+            raise TtsError("%d rates for %d clips" % (len(rates), len(clips)))
+        n = np.array([len(c) for c in clips], np.int64)
+        a = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1) for c in clips]))
+        r = np.array(rates, np.int32)
+        o, keep = self._audio_opts(mel_norms, 0, True)
+        frames = [self._ck(self.L.tts_audio_mel(self.h, _ptr(np.ascontiguousarray(c, np.float32)), len(c), rt, 80, C.addressof(o), None, 0)) for c, rt in zip(clips, rates)]
+        stride = max(1, max(self.dvae_rows(f) for f in frames))
+        codes, nc, zz = self._dvae_out(len(clips), stride, z)
+        self._ck(self.L.tts_dvae_codes_audio(self.h, _ptr(a), _ptr(n), _ptr(r), len(clips), C.addressof(o), _ptr(codes), _ptr(nc), stride,
+                                             None if zz is None else _ptr(zz)))
+        return self._dvae_split(codes, nc, zz)
+
+    def ar_latents_for_codes(self, tokens, voice, codes):
+        """latents [rows, 1024] of GIVEN speech codes (a recording's, from dvae_codes) under a text and a voice: ar_begin + ar_prefill + host_pad_codes +
+        ar_latents + host_trimmed_rows as one call (tts_ar_latents_for_codes), bit for bit; no sampling, the generator is not touched."""
+        tokens = np.ascontiguousarray(tokens, np.int32)
+        codes = np.ascontiguousarray(codes, np.int32)
+        voice = np.ascontiguousarray(voice, np.float32)
+        rows = C.c_int32(0)
+        out = np.empty((500, DMODEL), np.float32)
+        self._ck(self.L.tts_ar_latents_for_codes(self.h, _ptr(tokens), len(tokens), _ptr(voice), _ptr(codes), len(codes), C.byref(rows), _ptr(out)))
+        return out[:rows.value].copy()
 
     # ---- the wav2vec2 CTC aligner (not in the reference): redact bracketed prompt text from the audio ----
     def load_aligner(self, path):

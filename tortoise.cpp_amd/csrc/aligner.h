@@ -700,3 +700,5 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
 }
 
 } // namespace tts
+
+#include "dvae.h" // the DVAE encoder: the same translation unit, the classifier's strided convolution and hfg_conv_kernel

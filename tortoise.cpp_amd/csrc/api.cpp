@@ -125,6 +125,7 @@ void tts_destroy(tts_ctx *c) {
   if (c->bigvgan) bigvgan_free(c->bigvgan);
   if (c->classifier) classifier_free(c->classifier);
   if (c->aligner) aligner_free(c->aligner);
+  if (c->dvae) dvae_free(c->dvae);
   if (c->rlg) random_voice_free(c->rlg);
   if (c->afe) afe_free(c->afe);
   if (c->fp16_counts) (void)hipFree(c->fp16_counts);
@@ -493,6 +494,52 @@ int tts_random_voice(tts_ctx *c, const uint64_t *seeds, int n, const float *z_au
 int tts_random_voice_noise(tts_ctx *c, uint64_t seed, int side, float *out, int cap) {
   NEED_CTX(c);
   return guarded(c, [&] { return random_voice_noise(c, seed, side, out, cap); });
+}
+// The DVAE encoder (dvae.h): audio -> speech codes. The loader parses the file before it asks for the device, as tts_load_classifier does. The two code calls are
+// legal while a session is open: the stage owns its buffers and touches no AR or diffusion state.
+int tts_load_dvae(tts_ctx *c, const char *path) {
+  if (!c) return TTS_ERR_ARG;
+  return guarded(c, [&] { return dvae_load(c, path); });
+}
+int tts_dvae_rows(int mel_frames) { return tts_cvvp_rows(mel_frames); } // upstream's configuration: two convolutions k 3 / stride 2 / padding 1
+int tts_dvae_tokens(const tts_ctx *c) { return dvae_tokens(c); }
+int tts_dvae_dim(const tts_ctx *c) { return dvae_dim(c); }
+int tts_dvae_codes(tts_ctx *c, const float *mel80, const int32_t *frames, int n_clips, int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return dvae_codes(c, mel80, frames, n_clips, codes_out, n_codes_out, code_stride, z_out); });
+}
+int tts_dvae_codes_audio(tts_ctx *c, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                         int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return afe_dvae_codes_audio(c, audio, n_samples, sample_rate, n_clips, opts, codes_out, n_codes_out, code_stride, z_out); });
+}
+// tts_ar_begin (one candidate), tts_ar_prefill, tts_host_pad_codes, tts_ar_latents, tts_host_trimmed_rows as one call: the latents of GIVEN codes (a recording's,
+// from tts_dvae_codes) under a text and a voice. No sampling: the context's generator is never touched.
+int tts_ar_latents_for_codes(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice1024, const int32_t *codes, int n_codes, int32_t *rows_out,
+                             float *latents_out) {
+  NEED_CTX(c);
+  NO_SESSION(c, "tts_ar_latents_for_codes");
+  return guarded(c, [&]() -> int {
+    const char *fn = "tts_ar_latents_for_codes";
+    if (!text_ids || n_text < 1 || !voice1024 || !codes || n_codes < 1 || !rows_out || !latents_out) return fail(c, TTS_ERR_ARG, "%s: bad argument", fn);
+    if (n_codes > 500) return fail(c, TTS_ERR_LIMIT, "%s: %d codes, at most 500 (chunk longer recordings)", fn, n_codes);
+    for (int i = 0; i < n_codes; i++)
+      if (codes[i] < 0 || codes[i] >= 8192) return fail(c, TTS_ERR_ARG, "%s: code %d at position %d (0 .. 8191: a speech code, not a start or stop token)", fn, codes[i], i);
+    int rc = ar_begin(c, text_ids, n_text, voice1024, 1, 1);
+    if (rc) return rc;
+    std::vector<float> logits(TTS_VOCAB_MEL), lat((size_t)500 * 1024);
+    if ((rc = ar_prefill(c, logits.data()))) return rc;
+    std::vector<int> padded(codes, codes + n_codes);
+    pad_codes(padded);
+    if (padded.size() != 502) return fail(c, TTS_ERR_LIMIT, "%s: %d codes pad to %d, not 502", fn, n_codes, (int)padded.size());
+    std::vector<int32_t> c502(padded.begin(), padded.end());
+    if ((rc = ar_latents(c, c502.data(), 1, 502, lat.data()))) return rc;
+    const int rows = trimmed_latent_rows(c502.data());
+    if (rows < 0 || rows > 500) return fail(c, TTS_ERR_LIMIT, "%s: %d latent rows", fn, rows);
+    memcpy(latents_out, lat.data(), (size_t)rows * 1024 * 4);
+    *rows_out = rows;
+    return TTS_OK;
+  });
 }
 int tts_host_stream_final_rows(const int32_t *codes, int k) { return (k < 0 || (k > 0 && !codes)) ? TTS_ERR_ARG : stream_final_rows(codes, k); }
 int tts_ar_layers(const tts_ctx *c) { return c ? ar_layers(c) : 0; }

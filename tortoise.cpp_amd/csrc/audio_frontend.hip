@@ -344,6 +344,30 @@ int afe_cvvp_voice_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samp
   return cvvp_voice_run(ctx, latents_out);
 }
 
+// tts_dvae_codes_audio: the AR side's mel of the WHOLE clip (full_clips 1 whatever opts says: the codes are the recording's; mel_norms80 from opts) written
+// straight into the DVAE stem's input buffer; no host copy of the mel. The bits of tts_dvae_codes on tts_audio_mel(bands 80, full_clips 1) of every clip.
+int afe_dvae_codes_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                         int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out) {
+  const char *fn = "tts_dvae_codes_audio";
+  if (!ctx->dvae) return fail(ctx, TTS_ERR_STATE, "tts_load_dvae not called");
+  if (!audio || !n_samples || !sample_rate || !codes_out || !n_codes_out || n_clips < 1 || code_stride < 1) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", fn);
+  if (dvae_mel_channels(ctx) != 80) return fail(ctx, TTS_ERR_STATE, "%s: the loaded DVAE reads %d mel channels, the audio front end makes 80", fn, dvae_mel_channels(ctx));
+  if (opts && opts->struct_size < sizeof(tts_voice_audio_opts))
+    return fail(ctx, TTS_ERR_ARG, "%s: struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_voice_audio_opts))", fn, opts->struct_size, sizeof(tts_voice_audio_opts));
+  tts_voice_audio_opts full{};
+  full.struct_size = sizeof(tts_voice_audio_opts);
+  if (opts) full = *opts;
+  full.full_clips = 1; full.crop_offset = 0;
+  AfePlan pl;
+  int rc = afe_plan(ctx, fn, n_samples, sample_rate, n_clips, &full, true, false, pl);
+  if (rc) return rc;
+  float *d80 = nullptr;
+  if ((rc = dvae_begin(ctx, fn, pl.frames80.data(), n_clips, code_stride, &d80))) return rc; // every check of the DVAE side before any device work
+  if ((rc = afe_init(ctx))) return rc;
+  if ((rc = afe_front(ctx, fn, audio, pl, &full, d80, nullptr))) return rc;
+  return dvae_run(ctx, codes_out, n_codes_out, code_stride, z_out);
+}
+
 int afe_audio_mel(tts_ctx *ctx, const float *audio, int64_t n, int sample_rate, int bands, const tts_voice_audio_opts *opts, float *mel_out, int64_t cap) {
   const char *fn = "tts_audio_mel";
   if (!audio || (bands != 80 && bands != 100)) return fail(ctx, TTS_ERR_ARG, "%s: bad arguments (bands: 80 or 100)", fn);

@@ -101,6 +101,14 @@
 //   without brackets, or a run without --aligner (brackets or not), writes the bytes it wrote before. A failed alignment ("the text does not match the audio")
 //   exits 1 and writes no WAV. Usage errors (exit 1, before a model is loaded), for --aligner with a bracketed message only: --split-text, several voices,
 //   --stream, --devices > 1 or --exchange rccl, --dry-run 1; unbalanced or nested brackets.
+// --dvae FILE: the DVAE encoder, speech codes from audio (tts_load_dvae / tts_dvae_codes_audio; not in the reference). --mel-norms FILE gives the AR side's
+//   per-band norms, as with --voice-clips.
+//   --codes-from a.wav[,b.wav...] [--codes-out FILE]: prints "codes: <path> c0 c1 ..." per clip, or writes one line of space-separated codes per clip to FILE,
+//   and exits; no other model is loaded or required and nothing is synthesised.
+//   --revoice in.wav --message "transcript": the recording's codes under its transcript and the chosen voice (tts_ar_latents_for_codes: no sampling), then the
+//   chosen decoder chain (diffusion + vocoder, or --decoder hifigan) -> --output: the recording re-spoken in the other voice. Every voice option works as before.
+//   Usage errors (exit 1, before a model is loaded): --codes-from or --revoice without --dvae, either with --dry-run 1, --revoice with --split-text,
+//   --candidates > 1, several voices, --stream, --clvp / --cvvp, --devices > 1 or --exchange rccl, an unreadable clip, or a clip of more than 500 codes.
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -135,6 +143,26 @@ struct StreamSink {
     return 0;
   }
 };
+
+// one WAV file (mono mix, any rate) appended to `samples`; false with a message on stderr
+static bool read_clip(const std::string &path, std::vector<float> &samples, int64_t *n, int32_t *rate) {
+  const int64_t cnt = tts_read_wav(path.c_str(), nullptr, 0, rate);
+  if (cnt < 1) { fprintf(stderr, "%s: not a readable RIFF WAV with PCM16, PCM24 or float32 samples\n", path.c_str()); return false; }
+  samples.resize(samples.size() + (size_t)cnt);
+  if (tts_read_wav(path.c_str(), samples.data() + samples.size() - (size_t)cnt, cnt, rate) != cnt) { fprintf(stderr, "%s: read error\n", path.c_str()); return false; }
+  *n = cnt;
+  return true;
+}
+// codes a clip of n samples at `rate` Hz gives the DVAE under upstream's configuration: the mel of the whole clip at 22 050 Hz, hop 256
+static int clip_codes(int64_t n, int rate) { return tts_dvae_rows((int)((n * 22050 + rate - 1) / rate / 256) + 1); }
+// --mel-norms FILE: 80 floats, or none
+static bool read_norms(const std::string &path, std::vector<float> &norms) {
+  if (path.empty()) return true;
+  norms.resize(80);
+  std::ifstream f(path, std::ios::binary);
+  if (!f || !f.read((char *)norms.data(), 80 * sizeof(float))) { std::cerr << "Error: Unable to read 80 floats from " << path << std::endl; return false; }
+  return true;
+}
 
 // the clips of a comma-separated list of WAV files (mono mix, any rate) through ONE tts_classify_audio call; prob: one value per clip
 static int classify_wavs(tts_ctx *ctx, const std::string &list, std::vector<std::string> &paths, std::vector<float> &prob) {
@@ -194,6 +222,7 @@ int main(int argc, char **argv) {
   bool have_typ = false;
   std::string decoder = "diffusion", hifiganPath, vocoder = "univnet", bigvganPath;
   std::string detectClips, classifierPath, alignerPath;
+  std::string dvaePath, codesFrom, codesOut, revoicePath;
   bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
@@ -234,6 +263,10 @@ int main(int argc, char **argv) {
     else if (a == "--detect") detectClips = argv[i + 1];
     else if (a == "--classifier") classifierPath = argv[i + 1];
     else if (a == "--aligner") alignerPath = argv[i + 1];
+    else if (a == "--dvae") dvaePath = argv[i + 1];
+    else if (a == "--codes-from") codesFrom = argv[i + 1];
+    else if (a == "--codes-out") codesOut = argv[i + 1];
+    else if (a == "--revoice") revoicePath = argv[i + 1];
     else if (a == "--device") device = std::stoi(argv[i + 1]);
     else if (a == "--codes") fixed_codes = std::stoi(argv[i + 1]); // exactly N sampled codes, stop token masked (synthetic weights never stop)
     else if (a == "--devices") devices = std::stoi(argv[i + 1]);
@@ -302,6 +335,73 @@ int main(int argc, char **argv) {
     for (size_t c = 0; !rc && c < paths.size(); c++) printf("detect: %s %.9g\n", paths[c].c_str(), (double)prob[c]);
     tts_destroy(dctx);
     return rc;
+  }
+  // --dvae: speech codes from audio
+  const bool revoice = !revoicePath.empty();
+  std::vector<float> rv_samples; // --revoice: the recording, read before any model is loaded (a clip over 500 codes is a usage error)
+  int64_t rv_n = 0;
+  int32_t rv_rate = 0;
+  if ((!codesFrom.empty() || revoice) && dvaePath.empty()) {
+    fprintf(stderr, "usage: %s needs --dvae <file> (tools/convert_weights.py --dvae)\n", revoice ? "--revoice" : "--codes-from");
+    return 1;
+  }
+  if (!codesOut.empty() && codesFrom.empty()) { fprintf(stderr, "usage: --codes-out needs --codes-from <a.wav[,b.wav...]>\n"); return 1; }
+  if (!dvaePath.empty() && dry) { fprintf(stderr, "usage: --dvae runs on the device: it cannot be combined with --dry-run 1\n"); return 1; }
+  if (revoice) {
+    const char *bad = !codesFrom.empty() ? "--codes-from" : split_ids > 0 ? "--split-text" : candidates > 1 ? "--candidates > 1" : voicePaths.size() > 1 ? "several voices" :
+                      stream ? "--stream" : (!clvpPath.empty() || !cvvpPath.empty()) ? "--clvp / --cvvp" : (devices > 1 || exchange == "rccl" || shard >= 0) ? "--devices > 1 or --exchange rccl" :
+                      fixed_codes > 0 ? "--codes" : nullptr;
+    if (bad) { fprintf(stderr, "usage: --revoice re-speaks one recording in one voice without sampling: it cannot be combined with %s\n", bad); return 1; }
+    if (message.empty()) { fprintf(stderr, "usage: --revoice needs --message \"the recording's transcript\"\n"); return 1; }
+    if (!read_clip(revoicePath, rv_samples, &rv_n, &rv_rate)) return 1;
+    if (clip_codes(rv_n, rv_rate) > 500) {
+      fprintf(stderr, "usage: --revoice %s: %lld samples at %d Hz make %d codes, at most 500 (about 23 s; cut the recording)\n", revoicePath.c_str(), (long long)rv_n,
+              rv_rate, clip_codes(rv_n, rv_rate));
+      return 1;
+    }
+  }
+  if (!codesFrom.empty()) { // the encoder alone: one tts_dvae_codes_audio call for all clips
+    std::vector<float> samples, norms;
+    std::vector<int64_t> ns;
+    std::vector<int32_t> rates;
+    std::vector<std::string> paths;
+    int stride = 1;
+    for (size_t a = 0; a <= codesFrom.size();) {
+      const size_t b = std::min(codesFrom.find(',', a), codesFrom.size());
+      const std::string path = codesFrom.substr(a, b - a);
+      a = b + 1;
+      if (path.empty()) continue;
+      int64_t cnt = 0;
+      int32_t rate = 0;
+      if (!read_clip(path, samples, &cnt, &rate)) return 1;
+      paths.push_back(path); ns.push_back(cnt); rates.push_back(rate);
+      stride = std::max(stride, clip_codes(cnt, rate) + 1);
+    }
+    if (paths.empty()) { fprintf(stderr, "usage: --codes-from: no clip given\n"); return 1; }
+    if (!read_norms(melNormsPath, norms)) return 1;
+    tts_ctx *dctx = tts_create(device);
+    if (!dctx) { fprintf(stderr, "tts_create(%d) failed: no HIP device (this engine has no CPU path)\n", device); return 1; }
+    if (tts_load_dvae(dctx, dvaePath.c_str())) { const int rc = die(dctx, "dvae_model_load"); tts_destroy(dctx); return rc; }
+    tts_voice_audio_opts vo;
+    vo.struct_size = sizeof vo;
+    tts_voice_audio_opts_init(&vo);
+    vo.mel_norms80 = norms.empty() ? nullptr : norms.data();
+    std::vector<int32_t> codes(paths.size() * (size_t)stride), nc(paths.size());
+    if (tts_dvae_codes_audio(dctx, samples.data(), ns.data(), rates.data(), (int)paths.size(), &vo, codes.data(), nc.data(), stride, nullptr)) {
+      const int rc = die(dctx, "dvae_codes_audio");
+      tts_destroy(dctx);
+      return rc;
+    }
+    tts_destroy(dctx);
+    FILE *out = codesOut.empty() ? stdout : fopen(codesOut.c_str(), "w");
+    if (!out) { fprintf(stderr, "--codes-out %s: cannot be opened\n", codesOut.c_str()); return 1; }
+    for (size_t c = 0; c < paths.size(); c++) {
+      if (codesOut.empty()) fprintf(out, "codes: %s", paths[c].c_str());
+      for (int i = 0; i < nc[c]; i++) fprintf(out, i || codesOut.empty() ? " %d" : "%d", codes[c * (size_t)stride + i]);
+      fprintf(out, "\n");
+    }
+    if (!codesOut.empty() && fclose(out)) { fprintf(stderr, "--codes-out %s: write error\n", codesOut.c_str()); return 1; }
+    return 0;
   }
   // --aligner with a bracketed message: the brackets leave the prompt, the text they hold leaves the audio
   const bool redact = !alignerPath.empty() && message.find_first_of("[]") != std::string::npos;
@@ -895,14 +995,29 @@ int main(int argc, char **argv) {
         fprintf(stderr, "[timing] first audio           %8.1f ms after the autoregressive stage began (at %8.1f), %d callbacks, stride %d\n",
                 std::chrono::duration<double, std::milli>(sink.t_first - sink.t_ar).count(), std::chrono::duration<double, std::milli>(sink.t_first - t_start).count(),
                 sink.calls, stream_stride);
+    } else if (revoice) { // the recording's codes in place of sampled ones: no sampling, the generator is not touched
+      std::vector<float> norms;
+      if (!read_norms(melNormsPath, norms)) return 1;
+      if (tts_load_dvae(ctx, dvaePath.c_str())) return die(ctx, "dvae_model_load");
+      tts_voice_audio_opts vo;
+      vo.struct_size = sizeof vo;
+      tts_voice_audio_opts_init(&vo);
+      vo.mel_norms80 = norms.empty() ? nullptr : norms.data();
+      std::vector<int32_t> rcodes(512);
+      int32_t n_codes = 0;
+      if (tts_dvae_codes_audio(ctx, rv_samples.data(), &rv_n, &rv_rate, 1, &vo, rcodes.data(), &n_codes, 512, nullptr)) return die(ctx, "dvae_codes_audio");
+      if (n_codes > 500) { fprintf(stderr, "usage: --revoice %s: %d codes, at most 500 (cut the recording)\n", revoicePath.c_str(), n_codes); return 1; }
+      if (tts_ar_latents_for_codes(ctx, tokens.data(), n, voice.data(), rcodes.data(), n_codes, rows.data(), latents.data())) return die(ctx, "ar_latents_for_codes");
+      mark("dvae codes + latents");
+      printf("revoice: %d codes, %d latent rows\n", n_codes, rows[0]);
     } else {
       if (tts_autoregressive(ctx, tokens.data(), n, voice.data(), B_ar, fixed_codes > 0 ? fixed_codes : 500, ar_flags,
                              codes.data(), rows.data(), latents.data(), &nsteps))
         return die(ctx, "autoregressive");
       mark("autoregressive");
     }
-    printf("tokens sampled: %d\n", nsteps);
-    if (fixed_codes <= 0) {
+    if (!revoice) printf("tokens sampled: %d\n", nsteps);
+    if (fixed_codes <= 0 && !revoice) {
       std::vector<int32_t> stopped(B_ar);
       if (tts_ar_stop_status(ctx, stopped.data(), B_ar) == 0)
         for (int c = 0; c < B_ar; c++)

@@ -95,6 +95,7 @@ struct HifiganState;
 struct BigvganState;
 struct ClassifierState;
 struct AlignerState;
+struct DvaeState;
 struct RandomVoiceState;
 struct AfeState;
 struct Tokenizer;
@@ -144,6 +145,7 @@ struct tts_ctx {
   tts::BigvganState *bigvgan = nullptr; // BigVGAN vocoder: mel -> waveform beside UnivNet (bigvgan.h, part of hifigan.hip's translation unit; not in the reference)
   tts::ClassifierState *classifier = nullptr; // tortoise-detect: waveform -> probability that the clip is synthesized (classifier.h, part of hifigan.hip's translation unit through bigvgan.h; not in the reference)
   tts::AlignerState *aligner = nullptr; // wav2vec2 CTC aligner: waveform -> one token id per frame, for tts_align_audio / tts_redact_audio (aligner.h, part of hifigan.hip's translation unit through classifier.h; not in the reference)
+  tts::DvaeState *dvae = nullptr; // the DVAE encoder: mel -> speech codes, for tts_dvae_codes / tts_dvae_codes_audio (dvae.h, part of hifigan.hip's translation unit through aligner.h; not in the reference)
   tts::RandomVoiceState *rlg = nullptr; // random voices: upstream's RandomLatentConverter, one model per side (random_voice.h, part of extras.hip's translation unit; not in the reference)
   tts::AfeState *afe = nullptr; // audio front-end: its tables and buffers, made at the first tts_voice_from_audio / tts_audio_mel (audio_frontend.hip)
   tts::Tokenizer *tok = nullptr;
@@ -604,6 +606,17 @@ int aligner_vocab(tts_ctx *ctx, int32_t *vocab_out, int cap, int32_t *blank_out)
 int aligner_clip_frames(tts_ctx *ctx, int64_t n_samples, int sample_rate);
 int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, int32_t *ids_out, int32_t *n_frames_out,
                 int frame_stride, float *logits_out, ClsResampleFn resample);
+// The DVAE encoder (dvae.h). dvae_begin / dvae_run are tts_dvae_codes in two halves, as cvvp_voice_begin / cvvp_voice_run: the audio front end fills *d_mel between them.
+int dvae_load(tts_ctx *ctx, const char *path);
+void dvae_free(DvaeState *);
+int dvae_tokens(const tts_ctx *ctx);
+int dvae_dim(const tts_ctx *ctx);
+int dvae_mel_channels(const tts_ctx *ctx);
+int dvae_begin(tts_ctx *ctx, const char *fn, const int32_t *frames, int n_clips, int code_stride, float **d_mel);
+int dvae_run(tts_ctx *ctx, int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out);
+int dvae_codes(tts_ctx *ctx, const float *mel80, const int32_t *frames, int n_clips, int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out);
+int afe_dvae_codes_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                         int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out);
 // The host half of alignment and redaction (host_logic.cpp; exported as tts_host_*). Text is UTF-8; a character is a code point. Each returns a count or a
 // negative status and leaves the reason in `err`.
 int ctc_decode(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, std::vector<int32_t> &out, std::string &err);

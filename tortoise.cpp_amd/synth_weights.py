@@ -834,6 +834,66 @@ def write_random_voice(path, dim, seed, layers=6):
     return t
 
 
+DVAE_UPSTREAM = dict(channels=80, hidden=512, layers=2, blocks=3, dim=512, tokens=8192, k=3, stride=2)
+
+
+def dvae_tensor_shapes(channels=80, hidden=512, layers=2, blocks=3, dim=512, tokens=8192, k=3, stride=2, config=True):
+    """{name: PyTorch shape} of a DVAE file (tts_load_dvae): the encoder and the codebook of upstream's DiscreteVAE state dict under `dvae.` - strided layer i
+    `encoder.i.0` with hidden * 2^i output channels (upstream: 512, then 1024), ResBlock j
+    `encoder.(layers + j).net.{0,2,4}`, the final k = 1 convolution `encoder.(layers + blocks)`, `codebook.embed` [dim][tokens] - plus `dvae.config` = (stride,),
+    an integer held as f32. The decoder and the EMA buffers (codebook.cluster_size, codebook.embed_avg) are not part of the file. Restated from memory, unpinned
+    against upstream."""
+    t = {}
+    cin = channels
+    for i in range(layers):
+        cout = hidden * 2 ** i
+        t["dvae.encoder.%d.0.weight" % i] = (cout, cin, k)
+        t["dvae.encoder.%d.0.bias" % i] = (cout,)
+        cin = cout
+    for j in range(blocks):
+        p = "dvae.encoder.%d.net." % (layers + j)
+        for q, kk in ((0, k), (2, k), (4, 1)):
+            t[p + "%d.weight" % q] = (cin, cin, kk)
+            t[p + "%d.bias" % q] = (cin,)
+    t["dvae.encoder.%d.weight" % (layers + blocks)] = (dim, cin, 1)
+    t["dvae.encoder.%d.bias" % (layers + blocks)] = (dim,)
+    t["dvae.codebook.embed"] = (dim, tokens)
+    if config:
+        t["dvae.config"] = (1,)
+    return t
+
+
+def dvae_tensors(seed=1280, **cfg):
+    """{name: float32 array}: the synthetic recipe. Convolutions N(0, sqrt(2 / fan in)) (they feed or follow a ReLU), the k = 1 convolution that ends a ResBlock at
+    a quarter of that, the final convolution N(0, 1 / sqrt(fan in)); biases 0.05 N; the codebook N(0, 1): z of order 1 against Gaussian codes, the setting the
+    issue's estimate of undecided rows is made for (tests/test_dvae_cpu.py computes the share for the inputs the tests use)."""
+    c = dict(DVAE_UPSTREAM, **cfg)
+    g = _Gen(seed)
+    t = {}
+    last = "dvae.encoder.%d.weight" % (c["layers"] + c["blocks"])
+    for name, shape in dvae_tensor_shapes(**c).items():
+        if name == "dvae.config":
+            t[name] = np.array([c["stride"]], np.float32)
+        elif name == "dvae.codebook.embed":
+            t[name] = g.normal(shape, 1.0)
+        elif name.endswith(".bias"):
+            t[name] = g.normal(shape, 0.05)
+        else:
+            gain = 1.0 if name == last else 0.25 * np.sqrt(2.0) if ".net.4." in name else np.sqrt(2.0)
+            t[name] = g.lecun(shape, int(np.prod(shape[1:])), gain)
+    return t
+
+
+def write_dvae(path, seed=1280, **cfg):
+    """ggml-dvae-model.bin for tts_load_dvae; every size a parameter (dvae_tensor_shapes). Upstream's weights are not available offline. Returns the tensors."""
+    t = dvae_tensors(seed, **cfg)
+    w = GgmlWriter(path)
+    for name, arr in t.items():
+        w.add(name, arr)
+    w.close()
+    return t
+
+
 def write_all(out_dir, ar_layers=30, diff_main=10, diff_tail=3, diff_integ=3, diff_lc=4, seed=1234):
     import os
     os.makedirs(out_dir, exist_ok=True)
