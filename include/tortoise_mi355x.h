@@ -908,6 +908,35 @@ int tts_dvae_codes_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samp
 int tts_ar_latents_for_codes(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice1024, const int32_t *codes, int n_codes,
                              int32_t *rows_out, float *latents_out);
 
+/* ---- teacher-forced scores of given codes under the AR model (not in the reference; additions within version 8, no prototype changed) --------------- */
+/* How probable is a code sequence under the AR model, given a transcript and a voice: the quantity upstream's UnifiedVoice.forward returns as its mel loss.
+ * tts_ar_score_codes: tts_ar_begin (one prompt, one voice) + the prompt pass + ONE batched latent pass over every candidate's rows + one fused head launch
+ *   (csrc/ar_score.h: the [rows][8194] logits live in MFMA accumulators only and never reach HBM or the host). Candidate c with n = n_codes[c] codes
+ *   (codes [n_cand][code_stride], each 0 .. 8191) has n + 1 scored rows; every output is [n_cand][code_stride + 1], entries past n are left alone:
+ *     row 0          input 8192 (start) at mel position 0      logp_out[c][0] = log P(code 0)
+ *     row 1 .. n-1   input code j-1 at the mode's position     logp_out[c][j] = log P(code j)
+ *     row n          input code n-1 at the mode's position     logp_out[c][n] = log P(stop 8193)
+ *   so sum_j logp_out[c][j] is the log-likelihood of the sequence including its stop. stop_logp_out (or NULL): the stop token's log-prob at every row;
+ *   greedy_out (or NULL): the argmax id at every row, the lowest on a tie; lse_out (or NULL): log sum exp of the row's logits.
+ *   positions: TTS_SCORE_POS_DECODE puts code i at mel position i + 2, which is what the sampler saw (the decode step feeds step i's token at position i + 2,
+ *   the quirk of the reference's decode loop), so it scores sampled candidates as they were sampled; TTS_SCORE_POS_TRAIN puts code i at i + 1,
+ *   the latent pass's and upstream forward()'s rule: its hidden rows are bit for bit tts_ar_latents' rows for the same inputs.
+ *   The pass is uniform over max(n_codes) + 1 rows per candidate; shorter candidates are continued with code 83, which no scored row sees (causal mask).
+ *   Below 32 rows in total the latent pass takes its GEMV path and from 32 rows on its MFMA path, as tts_ar_latents does (another summation order); within one
+ *   path a candidate's bits are the same alone or in any batch, and two calls agree. The scores are always the f32 model's: option ar_weights = 1 / 2 changes the
+ *   decode slabs only, the head read here is the unfolded f32 lm_head.
+ *   Never touches the generator. Replaces any tts_ar_begin* state. TTS_ERR_HIP on a host-only context; TTS_ERR_STATE while a session is open or before
+ *   tts_load_ar; TTS_ERR_ARG for a null pointer, n_cand < 1, n_text < 1, n_codes[c] < 1 or > code_stride, a code outside 0 .. 8191, or positions outside
+ *   {0, 1}; TTS_ERR_LIMIT above 500 codes, above 64 candidates, or when 1 + n_text + max n + 1 > 1024. Every check runs before any device work and a refused
+ *   call writes nothing. Profiler family: "ar_score" (work = FLOPs).
+ * tts_host_ar_score_rows: the row table above for one candidate, pure (no context, no GPU): input_ids, mel_pos, targets [n_codes + 1]. TTS_ERR_ARG for a
+ *   null pointer, n_codes < 1, a code outside 0 .. 8191 or positions outside {0, 1}; TTS_ERR_LIMIT above 500 codes. */
+#define TTS_SCORE_POS_DECODE 0
+#define TTS_SCORE_POS_TRAIN 1
+int tts_ar_score_codes(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice1024, const int32_t *codes, const int32_t *n_codes, int n_cand,
+                       int code_stride, int positions, float *logp_out, float *stop_logp_out, int32_t *greedy_out, float *lse_out);
+int tts_host_ar_score_rows(const int32_t *codes, int n_codes, int positions, int32_t *input_ids, int32_t *mel_pos, int32_t *targets);
+
 /* ---- output -------------------------------------------------------------------------------- */
 /* writeWav (main.cpp:4821-4868): RIFF, fmt 16 B, tag 3 (IEEE float), mono, 32-bit. */
 int tts_write_wav(const char *path, const float *samples, int64_t n, int sample_rate);

@@ -21,6 +21,7 @@ AR_RETIRE = 2
 AR_ROW_CONTROLS = 8  # tts_ar_session_open only
 NOISE_REFERENCE, NOISE_DEVICE = 0, 1
 SAMPLER_DDPM, SAMPLER_DDIM, SAMPLER_DPMPP_2M = 0, 1, 3  # option diff_sampler, tts_diff_request.sampler (2 is not a sampler)
+SCORE_POSITIONS = {"decode": 0, "train": 1}  # TTS_SCORE_POS_DECODE / TTS_SCORE_POS_TRAIN (tts_ar_score_codes)
 
 _f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
@@ -127,6 +128,7 @@ def lib():
         "tts_load_dvae": (ci, [vp, C.c_char_p]), "tts_dvae_rows": (ci, [ci]), "tts_dvae_tokens": (ci, [vp]), "tts_dvae_dim": (ci, [vp]),
         "tts_dvae_codes": (ci, [vp, vp, vp, ci, vp, vp, ci, vp]), "tts_dvae_codes_audio": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
         "tts_ar_latents_for_codes": (ci, [vp, vp, ci, vp, vp, ci, vp, vp]),
+        "tts_ar_score_codes": (ci, [vp, vp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]), "tts_host_ar_score_rows": (ci, [vp, ci, ci, vp, vp, vp]),
         "tts_host_blend_voices": (ci, [vp, vp, ci, ci, vp]), "tts_host_random_voice_fold": (ci, [vp, vp, ci, ci, vp, vp]),
         "tts_hifigan_stream": (ci, [vp, vp, ci, vp, ci, C.c_uint, ci, vp, vp, vp, vp, vp, vp]), "tts_hifigan_stream_recaptures": (ci, [vp]),
         "tts_host_stream_final_rows": (ci, [vp, ci]),
@@ -789,6 +791,26 @@ class Engine:
                                              None if zz is None else _ptr(zz)))
         return self._dvae_split(codes, nc, zz)
 
+    def ar_score_codes(self, tokens, voice, codes_list, positions="decode"):
+        """Teacher-forced scores of given code sequences under a text and a voice (tts_ar_score_codes): one batched latent pass and one fused head launch, no
+        sampling. positions "decode" (code i at mel position i + 2: what the sampler saw) or "train" (i + 1: the latent pass's). Per candidate a dict of arrays
+        [n + 1]: logp (log P of code j, the last entry the stop token's), stop_logp, greedy (the argmax id) and lse."""
+        if positions not in SCORE_POSITIONS:
+            raise TtsError("positions %r: 'decode' or 'train'" % (positions,))
+        tokens, voice = np.ascontiguousarray(tokens, np.int32), np.ascontiguousarray(voice, np.float32)
+        seqs = [np.ascontiguousarray(c, np.int32).reshape(-1) for c in codes_list]
+        n = np.array([len(s) for s in seqs], np.int32)
+        stride = max(1, int(n.max())) if len(seqs) else 1
+        codes = np.zeros((len(seqs), stride), np.int32)
+        for b, s in enumerate(seqs):
+            codes[b, :len(s)] = s
+        logp, stop, lse = (np.full((len(seqs), stride + 1), np.nan, np.float32) for _ in range(3))
+        greedy = np.full((len(seqs), stride + 1), -1, np.int32)
+        self._ck(self.L.tts_ar_score_codes(self.h, _ptr(tokens), len(tokens), _ptr(voice), _ptr(codes), _ptr(n), len(seqs), stride, SCORE_POSITIONS[positions],
+                                           _ptr(logp), _ptr(stop), _ptr(greedy), _ptr(lse)))
+        return [{"logp": logp[b, :n[b] + 1].copy(), "stop_logp": stop[b, :n[b] + 1].copy(), "greedy": greedy[b, :n[b] + 1].copy(), "lse": lse[b, :n[b] + 1].copy()}
+                for b in range(len(seqs))]
+
     def ar_latents_for_codes(self, tokens, voice, codes):
         """latents [rows, 1024] of GIVEN speech codes (a recording's, from dvae_codes) under a text and a voice: ar_begin + ar_prefill + host_pad_codes +
         ar_latents + host_trimmed_rows as one call (tts_ar_latents_for_codes), bit for bit; no sampling, the generator is not touched."""
@@ -1171,6 +1193,18 @@ def host_pad_codes(codes):
     if rc:
         raise TtsError("tts_host_pad_codes failed (%d)" % rc)
     return out
+
+
+def host_ar_score_rows(codes, positions="decode"):
+    """The row table of tts_ar_score_codes for one candidate (tts_host_ar_score_rows; pure): (input_ids, mel_pos, targets), each [len(codes) + 1]."""
+    if positions not in SCORE_POSITIONS:
+        raise TtsError("positions %r: 'decode' or 'train'" % (positions,))
+    codes = np.ascontiguousarray(codes, np.int32).reshape(-1)
+    ids, pos, tgt = (np.zeros(len(codes) + 1, np.int32) for _ in range(3))
+    rc = lib().tts_host_ar_score_rows(_ptr(codes), len(codes), SCORE_POSITIONS[positions], _ptr(ids), _ptr(pos), _ptr(tgt))
+    if rc:
+        _host_fail("tts_host_ar_score_rows", rc)
+    return ids, pos, tgt
 
 
 def _prompt_args(prompts, n_cand):

@@ -541,6 +541,57 @@ int tts_ar_latents_for_codes(tts_ctx *c, const int32_t *text_ids, int n_text, co
     return TTS_OK;
   });
 }
+// Teacher-forced scores of GIVEN codes under a text and a voice: tts_ar_begin (one candidate) + the prompt pass + the latent pass over the row table of
+// tts_host_ar_score_rows + the fused head (ar_score.h). Every check runs before any device work; no sampling: the context's generator is never touched.
+int tts_ar_score_codes(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice1024, const int32_t *codes, const int32_t *n_codes, int n_cand,
+                       int code_stride, int positions, float *logp_out, float *stop_logp_out, int32_t *greedy_out, float *lse_out) {
+  NEED_CTX(c);
+  NO_SESSION(c, "tts_ar_score_codes");
+  return guarded(c, [&]() -> int {
+    const char *fn = "tts_ar_score_codes";
+    if (!c->ar) return fail(c, TTS_ERR_STATE, "%s: AR model not loaded", fn);
+    if (!text_ids || n_text < 1 || !voice1024 || !codes || !n_codes || n_cand < 1 || code_stride < 1 || !logp_out) return fail(c, TTS_ERR_ARG, "%s: bad argument", fn);
+    if (positions != TTS_SCORE_POS_DECODE && positions != TTS_SCORE_POS_TRAIN) return fail(c, TTS_ERR_ARG, "%s: positions %d (0 decode, 1 train)", fn, positions);
+    if (n_cand > 64) return fail(c, TTS_ERR_LIMIT, "%s: %d candidates, at most 64", fn, n_cand);
+    int n_max = 0;
+    for (int b = 0; b < n_cand; b++) {
+      if (n_codes[b] < 1 || n_codes[b] > code_stride) return fail(c, TTS_ERR_ARG, "%s: candidate %d has %d codes (1 .. code_stride %d)", fn, b, n_codes[b], code_stride);
+      if (n_codes[b] > 500) return fail(c, TTS_ERR_LIMIT, "%s: candidate %d has %d codes, at most 500 (chunk longer recordings)", fn, b, n_codes[b]);
+      for (int i = 0; i < n_codes[b]; i++) {
+        const int v = codes[(size_t)b * code_stride + i];
+        if (v < 0 || v >= 8192) return fail(c, TTS_ERR_ARG, "%s: candidate %d: code %d at position %d (0 .. 8191: a speech code, not a start or stop token)", fn, b, v, i);
+      }
+      n_max = std::max(n_max, n_codes[b]);
+    }
+    if (1 + n_text + n_max + 1 > 1024) return fail(c, TTS_ERR_LIMIT, "%s: %d text ids and %d codes exceed the 1024 positions", fn, n_text, n_max);
+    // the uniform pass: n_max + 1 rows per candidate, shorter candidates continued with code 83 (causal: no scored row sees the padding)
+    const int n_rows = n_max + 1;
+    std::vector<int32_t> ids((size_t)n_cand * n_rows), pos(ids.size()), tgt(ids.size()), padded((size_t)n_max);
+    for (int b = 0; b < n_cand; b++) {
+      std::copy(codes + (size_t)b * code_stride, codes + (size_t)b * code_stride + n_codes[b], padded.begin());
+      std::fill(padded.begin() + n_codes[b], padded.end(), 83);
+      const size_t o = (size_t)b * n_rows;
+      int rc = ar_score_row_table(padded.data(), n_max, positions, &ids[o], &pos[o], &tgt[o]);
+      if (rc) return fail(c, rc, "%s: row table", fn);
+      tgt[o + n_codes[b]] = 8193; // the candidate's own last row predicts the stop token
+    }
+    int rc = ar_begin(c, text_ids, n_text, voice1024, 1, 1);
+    if (rc) return rc;
+    if ((rc = ar_prefill(c, nullptr))) return rc;
+    std::vector<float> out((size_t)4 * n_cand * n_rows);
+    if ((rc = ar_score_rows(c, ids.data(), pos.data(), tgt.data(), n_cand, n_rows, out.data()))) return rc;
+    const size_t R = (size_t)n_cand * n_rows, os = (size_t)code_stride + 1;
+    for (int b = 0; b < n_cand; b++)
+      for (int j = 0; j <= n_codes[b]; j++) {
+        const size_t r = (size_t)b * n_rows + j;
+        if (lse_out) lse_out[b * os + j] = out[r];
+        logp_out[b * os + j] = out[R + r];
+        if (stop_logp_out) stop_logp_out[b * os + j] = out[2 * R + r];
+        if (greedy_out) memcpy(&greedy_out[b * os + j], &out[3 * R + r], 4);
+      }
+    return TTS_OK;
+  });
+}
 int tts_host_stream_final_rows(const int32_t *codes, int k) { return (k < 0 || (k > 0 && !codes)) ? TTS_ERR_ARG : stream_final_rows(codes, k); }
 int tts_ar_layers(const tts_ctx *c) { return c ? ar_layers(c) : 0; }
 int tts_diffusion_layers(const tts_ctx *c) { return c ? diff_layers(c) : 0; }

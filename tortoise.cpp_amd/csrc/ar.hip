@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include "ar_score.h"
 
 namespace tts {
 
@@ -1652,6 +1653,7 @@ struct ArState {
   int sa_S = 0;              // 0: the session has no audio
   int sa_rows = 0;           // the most rows one launch sequence packs (the buffers reserved at enable time hold them)
   DevBuf h, xn, qkv, att, ff, part, desc, logits, hn, a_hi, a_lo;
+  DevBuf score_ws, score_io; // ar_score_rows: the slab partials; [targets | lse | logp | stop_logp | greedy] of the scored rows
   // decode-step graph
   DevBuf d_toks;
   int32_t *h_toks = nullptr;   // pinned
@@ -2618,7 +2620,9 @@ static int latents_check(tts_ctx *ctx, const ArState *st, int n_text, const int3
 }
 
 // c0: the cache row that holds the prompt's K/V rows (a group's first candidate; a session request's first slot), n_text: that prompt's length.
-static int latents_rows(tts_ctx *ctx, ArState *st, int c0, int n_text, const int32_t *codes502, int nb, int n_mel, float *out) {
+// The body tts_ar_latents and tts_ar_score_codes share: desc [nb][n_mel] = (2, input id, 1, mel position id) of every row; leaves hn [nb * n_mel][1024] on the
+// device, enqueued on the context's stream.
+static int latents_body(tts_ctx *ctx, ArState *st, int c0, int n_text, const std::vector<int4> &desc, int nb, int n_mel) {
   const int Sp = 1 + n_text, S = Sp + n_mel, rows = nb * n_mel;
   CHECK(reserve_rows(ctx, st, rows));
   const size_t lat_stride = (size_t)nb * S * D; // per layer: [cand][S][1024]
@@ -2628,19 +2632,50 @@ static int latents_rows(tts_ctx *ctx, ArState *st, int c0, int n_text, const int
   copy_prompt_kv_kernel<<<dim3(Sp, nb, 2 * st->n_layers), 256, 0, ctx->stream>>>(
       st->kcache.as<__half>() + src0, st->vcache.as<__half>() + src0, (size_t)st->B * st->max_pos * D, st->lat_k.as<__half>(), st->lat_v.as<__half>(),
       lat_stride, S, st->n_layers);
-  std::vector<int4> desc(rows);
-  for (int c = 0; c < nb; c++)
-    for (int j = 0; j < n_mel; j++) desc[(size_t)c * n_mel + j] = make_int4(2, codes502[c * 502 + j], 1, j);
   CHECK(embed(ctx, st, desc));
   CHECK(run_layers(ctx, st, rows, n_mel, Sp, st->lat_k.as<__half>(), st->lat_v.as<__half>(), lat_stride, S, 0));
   float *xn = st->xn.as<float>(), *hn = st->hn.as<float>();
   layernorm_kernel<<<rows, 256, 0, ctx->stream>>>(st->h.as<float>(), st->lnf_g, st->lnf_b, xn);
   layernorm_kernel<<<rows, 256, 0, ctx->stream>>>(xn, st->lmh_g, st->lmh_b, hn);
   TTS_HIP(ctx, hipGetLastError());
+  return TTS_OK;
+}
+
+static int latents_rows(tts_ctx *ctx, ArState *st, int c0, int n_text, const int32_t *codes502, int nb, int n_mel, float *out) {
+  std::vector<int4> desc((size_t)nb * n_mel);
+  for (int c = 0; c < nb; c++)
+    for (int j = 0; j < n_mel; j++) desc[(size_t)c * n_mel + j] = make_int4(2, codes502[c * 502 + j], 1, j);
+  CHECK(latents_body(ctx, st, c0, n_text, desc, nb, n_mel));
+  const float *hn = st->hn.as<float>();
   const int n_out = std::min(500, n_mel);
   for (int c = 0; c < nb; c++)
     TTS_HIP(ctx, hipMemcpyAsync(out + (size_t)c * n_out * D, hn + (size_t)c * n_mel * D, (size_t)n_out * D * 4, hipMemcpyDeviceToHost,
                                 ctx->stream));
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return TTS_OK;
+}
+
+// tts_ar_score_codes behind tts_ar_begin (one prompt, one voice) and the prompt pass: the latent pass over nb candidates x n_rows rows (input_ids / mel_pos /
+// targets [nb][n_rows], the row table of tts_host_ar_score_rows, padded by the caller), then the fused head over hn. out [4][nb * n_rows] on the host:
+// lse | logp | stop_logp | greedy (int32 bits), copied once behind one synchronisation. Always the f32 head (lm_w), whatever ar_weights holds.
+int ar_score_rows(tts_ctx *ctx, const int32_t *input_ids, const int32_t *mel_pos, const int32_t *targets, int nb, int n_rows, float *out) {
+  ArState *st = ctx->ar;
+  if (!st || st->B == 0 || st->multi || st->session || !st->prefill_done) return fail(ctx, TTS_ERR_STATE, "ar_score_rows: no single-prompt tts_ar_begin + prompt pass");
+  const int rows = nb * n_rows;
+  if (!ar_score_shape_ok(rows, D, V, VPAD)) return fail(ctx, TTS_ERR_ARG, "ar_score_rows: %d rows", rows);
+  std::vector<int4> desc((size_t)rows);
+  for (int r = 0; r < rows; r++) desc[r] = make_int4(2, input_ids[r], 1, mel_pos[r]);
+  CHECK(latents_body(ctx, st, st->g_c0[0], st->g_ntext[0], desc, nb, n_rows));
+  TTS_HIP(ctx, st->score_ws.reserve(ar_score_ws_floats(rows, V) * 4));
+  TTS_HIP(ctx, st->score_io.reserve((size_t)5 * rows * 4));
+  int *d_tgt = st->score_io.as<int>();
+  float *d_out = st->score_io.as<float>() + rows;
+  TTS_HIP(ctx, hipMemcpyAsync(d_tgt, targets, (size_t)rows * 4, hipMemcpyHostToDevice, ctx->stream));
+  { ProfScope ps(ctx, "ar_score", 2.0 * rows * (double)D * V);
+    const ArScore a{st->hn.as<float>(), st->lm_w, st->lm_b, d_tgt, st->score_ws.as<float>(), rows, D, V, VPAD};
+    const ArScoreOut o{d_out, d_out + rows, d_out + 2 * (size_t)rows, (int *)(d_out + 3 * (size_t)rows), nullptr, nullptr};
+    TTS_HIP(ctx, ar_score_launch(a, o, ctx->stream)); }
+  TTS_HIP(ctx, hipMemcpyAsync(out, d_out, (size_t)4 * rows * 4, hipMemcpyDeviceToHost, ctx->stream));
   TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return TTS_OK;
 }

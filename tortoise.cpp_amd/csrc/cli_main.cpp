@@ -109,6 +109,14 @@
 //   chosen decoder chain (diffusion + vocoder, or --decoder hifigan) -> --output: the recording re-spoken in the other voice. Every voice option works as before.
 //   Usage errors (exit 1, before a model is loaded): --codes-from or --revoice without --dvae, either with --dry-run 1, --revoice with --split-text,
 //   --candidates > 1, several voices, --stream, --clvp / --cvvp, --devices > 1 or --exchange rccl, an unreadable clip, or a clip of more than 500 codes.
+// --score-audio a.wav[,b.wav...] (with --dvae FILE) or --score-codes FILE (lines in --codes-out's format), with --message "transcript", any voice source and the
+//   AR model: teacher-forced scores of the clips' codes under the transcript and the voice (tts_ar_score_codes: one batched pass, no sampling; nothing is
+//   synthesised and no other model is loaded). [--score-positions decode|train], default train (upstream forward()'s positions; decode = what the sampler saw).
+//   Per clip one line "score: <path or FILE:line> <codes n> <total log-likelihood of the n codes and the stop> <mean negative log-likelihood in nats per scored
+//   position, n + 1 of them> <perplexity = exp of that> <the stop token's log-prob at the last position> <share of positions whose argmax is the target>".
+//   Usage errors (exit 1, before a model is loaded): both options at once, --score-audio without --dvae, no --message, --dry-run 1, --score-positions without
+//   either or with another word, a combination with --revoice, --codes-from, --split-text, --stream, several voices, --devices > 1 or --exchange rccl, an
+//   unreadable clip or codes file, a line that is not 1 .. 500 codes in 0 .. 8191, more than 64 clips, a clip of more than 500 codes (chunking is the caller's).
 #include "tortoise_mi355x.h"
 #include "cli_rccl.h"
 #include <algorithm>
@@ -222,7 +230,7 @@ int main(int argc, char **argv) {
   bool have_typ = false;
   std::string decoder = "diffusion", hifiganPath, vocoder = "univnet", bigvganPath;
   std::string detectClips, classifierPath, alignerPath;
-  std::string dvaePath, codesFrom, codesOut, revoicePath;
+  std::string dvaePath, codesFrom, codesOut, revoicePath, scoreAudio, scoreCodes, scorePositions;
   bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
   std::vector<std::string> voicePaths, diffLatentPaths;        // every occurrence of --voice / --diffusion-latent: the k-th is voice k
@@ -267,6 +275,9 @@ int main(int argc, char **argv) {
     else if (a == "--codes-from") codesFrom = argv[i + 1];
     else if (a == "--codes-out") codesOut = argv[i + 1];
     else if (a == "--revoice") revoicePath = argv[i + 1];
+    else if (a == "--score-audio") scoreAudio = argv[i + 1];
+    else if (a == "--score-codes") scoreCodes = argv[i + 1];
+    else if (a == "--score-positions") scorePositions = argv[i + 1];
     else if (a == "--device") device = std::stoi(argv[i + 1]);
     else if (a == "--codes") fixed_codes = std::stoi(argv[i + 1]); // exactly N sampled codes, stop token masked (synthetic weights never stop)
     else if (a == "--devices") devices = std::stoi(argv[i + 1]);
@@ -402,6 +413,68 @@ int main(int argc, char **argv) {
     }
     if (!codesOut.empty() && fclose(out)) { fprintf(stderr, "--codes-out %s: write error\n", codesOut.c_str()); return 1; }
     return 0;
+  }
+  // --score-audio / --score-codes: everything that can be refused is refused here, before a model is loaded
+  const bool score = !scoreAudio.empty() || !scoreCodes.empty();
+  std::vector<float> sc_samples;
+  std::vector<int64_t> sc_ns;
+  std::vector<int32_t> sc_rates, sc_codes /*[clips][500]*/, sc_n;
+  std::vector<std::string> sc_names;
+  if (!scorePositions.empty() && !score) { fprintf(stderr, "usage: --score-positions needs --score-audio or --score-codes\n"); return 1; }
+  if (score) {
+    if (!scoreAudio.empty() && !scoreCodes.empty()) { fprintf(stderr, "usage: --score-audio and --score-codes cannot be combined\n"); return 1; }
+    if (!scoreAudio.empty() && dvaePath.empty()) { fprintf(stderr, "usage: --score-audio needs --dvae <file> (tools/convert_weights.py --dvae)\n"); return 1; }
+    if (dry) { fprintf(stderr, "usage: --score-audio / --score-codes run on the device: they cannot be combined with --dry-run 1\n"); return 1; }
+    if (!scorePositions.empty() && scorePositions != "decode" && scorePositions != "train") { fprintf(stderr, "usage: --score-positions %s: decode or train\n", scorePositions.c_str()); return 1; }
+    const char *bad = revoice ? "--revoice" : split_ids > 0 ? "--split-text" : stream ? "--stream" : voicePaths.size() > 1 ? "several voices" :
+                      (devices > 1 || exchange == "rccl" || shard >= 0) ? "--devices > 1 or --exchange rccl" : nullptr;
+    if (bad) { fprintf(stderr, "usage: --score-audio / --score-codes score given codes under one transcript and one voice: they cannot be combined with %s\n", bad); return 1; }
+    if (message.empty()) { fprintf(stderr, "usage: --score-audio / --score-codes need --message \"the transcript\"\n"); return 1; }
+    if (!scoreAudio.empty()) {
+      for (size_t a = 0; a <= scoreAudio.size();) {
+        const size_t b = std::min(scoreAudio.find(',', a), scoreAudio.size());
+        const std::string path = scoreAudio.substr(a, b - a);
+        a = b + 1;
+        if (path.empty()) continue;
+        int64_t cnt = 0;
+        int32_t rate = 0;
+        if (!read_clip(path, sc_samples, &cnt, &rate)) return 1;
+        if (clip_codes(cnt, rate) > 500) {
+          fprintf(stderr, "usage: --score-audio %s: %lld samples at %d Hz make %d codes, at most 500 (about 23 s; cut the recording)\n", path.c_str(), (long long)cnt, rate,
+                  clip_codes(cnt, rate));
+          return 1;
+        }
+        sc_names.push_back(path); sc_ns.push_back(cnt); sc_rates.push_back(rate);
+      }
+      if (sc_names.empty()) { fprintf(stderr, "usage: --score-audio: no clip given\n"); return 1; }
+    } else {
+      std::ifstream f(scoreCodes);
+      if (!f) { fprintf(stderr, "usage: --score-codes %s: cannot be opened\n", scoreCodes.c_str()); return 1; }
+      std::string line;
+      for (int ln = 1; std::getline(f, line); ln++) {
+        if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+        std::vector<int32_t> row;
+        const char *p = line.c_str();
+        for (;;) {
+          char *end = nullptr;
+          const long v = std::strtol(p, &end, 10);
+          if (end == p) break;
+          if (v < 0 || v >= 8192) { fprintf(stderr, "usage: --score-codes %s:%d: code %ld (0 .. 8191)\n", scoreCodes.c_str(), ln, v); return 1; }
+          row.push_back((int32_t)v);
+          p = end;
+        }
+        if (std::string(p).find_first_not_of(" \t\r") != std::string::npos || row.empty() || row.size() > 500) {
+          fprintf(stderr, "usage: --score-codes %s:%d: a line holds 1 .. 500 space-separated codes\n", scoreCodes.c_str(), ln);
+          return 1;
+        }
+        sc_n.push_back((int32_t)row.size());
+        row.resize(500, 0);
+        sc_codes.insert(sc_codes.end(), row.begin(), row.end());
+        sc_names.push_back(scoreCodes + ":" + std::to_string(ln));
+      }
+      if (sc_names.empty()) { fprintf(stderr, "usage: --score-codes %s: no codes\n", scoreCodes.c_str()); return 1; }
+    }
+    if (sc_names.size() > 64) { fprintf(stderr, "usage: --score-audio / --score-codes: %d clips, at most 64 in one call\n", (int)sc_names.size()); return 1; }
   }
   // --aligner with a bracketed message: the brackets leave the prompt, the text they hold leaves the audio
   const bool redact = !alignerPath.empty() && message.find_first_of("[]") != std::string::npos;
@@ -916,7 +989,7 @@ int main(int argc, char **argv) {
   if (hifiganPath.empty()) hifiganPath = modelsDir + "/ggml-hifigan-model.bin";
   if (bigvganPath.empty()) bigvganPath = modelsDir + "/ggml-bigvgan-model.bin";
   bg.t = std::thread([&]() {
-    if (use_hifigan) return; // its one model (56 MB, plain synchronous uploads) is loaded in front of its stage, as the reference loads every model
+    if (use_hifigan || score) return; // --score-*: the AR model alone; hifigan: its one model (56 MB, plain synchronous uploads) is loaded in front of its stage, as the reference loads every model
     rc_diff = tts_load_diffusion(ctx, (modelsDir + "/ggml-diffusion-model.bin").c_str());
     if (rc_diff) { err_diff = tts_last_error(ctx); return; }
     rc_voc = use_bigvgan ? tts_load_bigvgan(ctx, bigvganPath.c_str()) : tts_load_vocoder(ctx, (modelsDir + "/ggml-vocoder-model.bin").c_str());
@@ -924,6 +997,45 @@ int main(int argc, char **argv) {
   });
   if (tts_load_ar(ctx, (modelsDir + "/ggml-model.bin").c_str())) return die(ctx, "autoregressive_model_load");
   mark("load autoregressive");
+  if (score) { // given codes under the transcript and the voice: one tts_ar_score_codes call, nothing is synthesised
+    const int nc = (int)sc_names.size();
+    if (!scoreAudio.empty()) {
+      std::vector<float> norms;
+      if (!read_norms(melNormsPath, norms)) return 1;
+      if (tts_load_dvae(ctx, dvaePath.c_str())) return die(ctx, "dvae_model_load");
+      tts_voice_audio_opts vo;
+      vo.struct_size = sizeof vo;
+      tts_voice_audio_opts_init(&vo);
+      vo.mel_norms80 = norms.empty() ? nullptr : norms.data();
+      std::vector<int32_t> wide((size_t)nc * 512);
+      sc_n.resize(nc);
+      if (tts_dvae_codes_audio(ctx, sc_samples.data(), sc_ns.data(), sc_rates.data(), nc, &vo, wide.data(), sc_n.data(), 512, nullptr)) return die(ctx, "dvae_codes_audio");
+      sc_codes.assign((size_t)nc * 500, 0);
+      for (int c = 0; c < nc; c++) {
+        if (sc_n[c] > 500) { fprintf(stderr, "usage: --score-audio %s: %d codes, at most 500 (cut the recording)\n", sc_names[c].c_str(), sc_n[c]); return 1; }
+        std::copy(wide.begin() + (size_t)c * 512, wide.begin() + (size_t)c * 512 + sc_n[c], sc_codes.begin() + (size_t)c * 500);
+      }
+    }
+    std::vector<float> logp((size_t)nc * 501), stop((size_t)nc * 501);
+    std::vector<int32_t> greedy((size_t)nc * 501);
+    const int positions = scorePositions == "decode" ? TTS_SCORE_POS_DECODE : TTS_SCORE_POS_TRAIN;
+    if (tts_ar_score_codes(ctx, tokens.data(), n, voice.data(), sc_codes.data(), sc_n.data(), nc, 500, positions, logp.data(), stop.data(), greedy.data(), nullptr))
+      return die(ctx, "ar_score_codes");
+    mark("score");
+    for (int c = 0; c < nc; c++) {
+      double total = 0;
+      int hits = 0;
+      for (int j = 0; j <= sc_n[c]; j++) {
+        total += (double)logp[(size_t)c * 501 + j];
+        hits += greedy[(size_t)c * 501 + j] == (j == sc_n[c] ? 8193 : sc_codes[(size_t)c * 500 + j]);
+      }
+      const double nll = -total / (sc_n[c] + 1);
+      printf("score: %s %d %.9g %.9g %.9g %.9g %.9g\n", sc_names[c].c_str(), sc_n[c], total, nll, std::exp(nll), (double)stop[(size_t)c * 501 + sc_n[c]],
+             (double)hits / (sc_n[c] + 1));
+    }
+    tts_destroy(ctx);
+    return 0;
+  }
   const int B_all = B_ar * std::max(1, n_chunks); // --split-text: candidates of all chunks
   std::vector<int32_t> codes((size_t)B_all * 502), rows(B_all);
   std::vector<float> latents((size_t)B_all * 500 * 1024);

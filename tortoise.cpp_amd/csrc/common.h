@@ -451,6 +451,8 @@ const float *ar_fetch_logits_row(tts_ctx *, int);
 void ar_history_ids(const tts_ctx *, int c, std::vector<int32_t> &out);
 int ar_latents(tts_ctx *, const int32_t *, int, int, float *);
 int ar_latents_group(tts_ctx *, int, const int32_t *, int, float *);
+int ar_score_rows(tts_ctx *, const int32_t *input_ids, const int32_t *mel_pos, const int32_t *targets, int nb, int n_rows, float *out4);
+int ar_score_row_table(const int32_t *codes, int n_codes, int positions, int32_t *input_ids, int32_t *mel_pos, int32_t *targets); // tts_host_ar_score_rows
 int ar_stream_reserve(tts_ctx *, int n_mel);
 int ar_graph_captures(const tts_ctx *);
 int ar_session_open(tts_ctx *, int n_slots, int max_cand, int max_text, int max_steps, bool rows);

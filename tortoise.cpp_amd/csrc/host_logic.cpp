@@ -1179,6 +1179,25 @@ extern "C" int tts_host_pad_codes(const int32_t *codes, int n, int32_t *out502) 
   return TTS_OK;
 }
 extern "C" int tts_host_trimmed_rows(const int32_t *codes502) { return tts::trimmed_latent_rows(codes502); }
+// The row table of tts_ar_score_codes, stated once: n codes have n + 1 scored rows. Row 0 feeds the start token 8192 at mel position 0 and predicts code 0; row
+// j >= 1 feeds code j - 1 and predicts code j, the last one the stop token 8193. Code i sits at mel position i + 2 in TTS_SCORE_POS_DECODE (what the decode
+// step saw: ar_step feeds step i's token at position i + 2) and at i + 1 in TTS_SCORE_POS_TRAIN (the latent pass's and upstream forward()'s).
+int tts::ar_score_row_table(const int32_t *codes, int n, int positions, int32_t *input_ids, int32_t *mel_pos, int32_t *targets) {
+  if (!codes || !input_ids || !mel_pos || !targets || n < 1 || (positions != TTS_SCORE_POS_DECODE && positions != TTS_SCORE_POS_TRAIN)) return TTS_ERR_ARG;
+  if (n > 500) return TTS_ERR_LIMIT;
+  for (int i = 0; i < n; i++)
+    if (codes[i] < 0 || codes[i] >= 8192) return TTS_ERR_ARG;
+  const int shift = positions == TTS_SCORE_POS_DECODE ? 2 : 1;
+  for (int j = 0; j <= n; j++) {
+    input_ids[j] = j == 0 ? 8192 : codes[j - 1];
+    mel_pos[j] = j == 0 ? 0 : j - 1 + shift;
+    targets[j] = j == n ? 8193 : codes[j];
+  }
+  return TTS_OK;
+}
+extern "C" int tts_host_ar_score_rows(const int32_t *codes, int n_codes, int positions, int32_t *input_ids, int32_t *mel_pos, int32_t *targets) {
+  return tts::ar_score_row_table(codes, n_codes, positions, input_ids, mel_pos, targets);
+}
 // The decode loop's stop bookkeeping (tts::ArStopBook, the one tts_autoregressive_multi runs) on scripted samples: samples [max_steps][B] are what the
 // sampler returns at each iteration. Outputs as the driver's: codes [B][502] (padded), stopped [B], *steps; inputs [max_steps][B] (may be null): the tokens fed to
 // the decode step after each iteration. TTS_ERR_LIMIT when strict mode reaches max_steps.
