@@ -257,3 +257,12 @@ def test_loader_refusals(tmp_path, what, edit):
     edit(t)
     rc, _, err = V.parse(_write(tmp_path, t))
     assert rc == FMT and what in err, (rc, err)
+
+
+def test_reader_messages_have_the_shared_shape(tmp_path):
+    import model_io_cases as M
+
+    def load(t):
+        rc, _, err = V.parse(_write(tmp_path, t))
+        return rc, err
+    M.reader_messages(load, R.model("tiny")[1], "BigVGAN", "bigvgan.ups.1.0.bias", FMT)

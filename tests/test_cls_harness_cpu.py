@@ -148,3 +148,32 @@ def test_loader_host_half_reads_the_configuration_and_repacks():
         w_ = np.exp(s - s.max(1, keepdims=True))
         want[:, h * dh:(h + 1) * dh] = (w_ / w_.sum(1, keepdims=True)) @ v
     assert np.abs(att - want).max() < 1e-5  # qkv was rounded to float32 on the way
+
+
+def test_level_tables_against_an_independent_spelling():
+    """cls_levels, the function classifier_run and the harness both call, against tests/model_io_cases.levels: a one-row clip, a clip across a ceil8 boundary
+    that downsamples to one row, a clip with a second GroupNorm tile; every level carries its tile start and the clip's first sample."""
+    import model_io_cases as M
+    L = K.harness()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    for n, depth, F in (((1, 9, 257), 2, 4), ((257, 1, 9), 1, 2), ((220000, 8), 3, 4)):
+        tab, rows, tiles, max_n = np.zeros((depth + 1, len(n), K.SEQ), np.int32), np.zeros(depth + 1, np.int64), np.zeros(depth + 1, np.int64), np.zeros(depth + 1, np.int32)
+        assert L.tts_cls_test_levels(p(np.array(n, np.int32)), len(n), depth, F, p(tab), p(rows), p(tiles), p(max_n)) == 0
+        want = M.levels(n, lambda v, l: (v - 1) // F + 1, depth + 1, 8, K.GN_TILE, True)
+        for got, ref in zip((tab, rows, tiles, max_n), want):
+            assert np.array_equal(got, ref), (n, got, ref)
+    assert tab[3, 1, 1] == 1 and not (tab[:, :, 0] % 8).any()
+
+
+def test_reader_messages_have_the_shared_shape(tmp_path):
+    import model_io_cases as M
+    from tortoise_cpp_amd import synth_weights as sw
+
+    def load(t):
+        w = sw.GgmlWriter(str(tmp_path / "m.bin"))
+        for k, a in t.items():
+            w.add(k, a)
+        w.close()
+        rc, _, msg = K.parse(str(tmp_path / "m.bin"))
+        return rc, msg
+    M.reader_messages(load, R.model("tiny")[1], "classifier", "classifier.enc.final.2.bias", -3)

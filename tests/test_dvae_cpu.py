@@ -154,6 +154,33 @@ def test_loader_host_half_and_repack():
     assert R.harness().tts_dvae_test_vq_tile() == R.VQ_TILE and R.harness().tts_dvae_test_vq_slab() == R.VQ_SLAB
 
 
+def test_level_tables_against_an_independent_spelling():
+    """dvae_levels, the function dvae_begin and the harness both call, against tests/model_io_cases.levels: a one-frame clip, odd lengths, clips packed without
+    gaps, the first mel float (cin x the frames before the clip) on level 0 only."""
+    import model_io_cases as M
+    L = R.harness()
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    for n, layers, stride, cin in (((1, 9, 257), 2, 2, 80), ((2, 1, 3), 1, 4, 7), ((16384,), 3, 3, 128)):
+        tab, rows, max_n = np.zeros((layers + 1, len(n), M.SEQ), np.int32), np.zeros(layers + 1, np.int64), np.zeros(layers + 1, np.int32)
+        assert L.tts_dvae_test_levels(p(np.array(n, np.int32)), len(n), layers, stride, cin, p(tab), p(rows), p(max_n)) == 0
+        want = M.levels(n, lambda v, l: (v - 1) // stride + 1, layers + 1, 1, 0, False, cin)
+        assert np.array_equal(tab, want[0]) and np.array_equal(rows, want[1]) and np.array_equal(max_n, want[3]), (n, tab, want)
+        if len(n) == 3:
+            assert tab[0, 2, 4] == cin * (n[0] + n[1]) and not tab[:, :, 3].any() and not tab[1:, :, 4].any()
+        if (layers, stride) == (2, 2):
+            assert [R.rows(v) for v in n] == list(tab[2, :, 1])
+
+
+def test_reader_messages_have_the_shared_shape(tmp_path):
+    """The DVAE reads its sizes off the tensors, so a bias of another length is refused in its own words (BROKEN below); the rest is ModelReader's."""
+    import model_io_cases as M
+
+    def load(t):
+        rc, _, msg = R.parse(_write(tmp_path / "m.bin", t).decode())
+        return rc, msg
+    M.reader_messages(load, R.model("mid")[1], "DVAE", "dvae.encoder.3.net.2.bias", FMT, extent=False)
+
+
 BROKEN = [("'dvae.encoder.1.0.bias' missing", lambda t: t.pop("dvae.encoder.1.0.bias")),
           ("'dvae.codebook.embed' missing", lambda t: t.pop("dvae.codebook.embed")),
           ("unknown tensors", lambda t: t.__setitem__("dvae.decoder.0.weight", np.zeros(3, np.float32))),

@@ -142,3 +142,33 @@ def test_repack_feeds_the_kernels(tmp_path):
         assert np.array_equal(K.packed(path, 8).reshape(Dm, V), t["aligner.lm_head.weight"].T)
     rc, arch, msg = K.parse(str(tmp_path / "nowhere.bin"))
     assert rc < 0 and msg
+
+
+def test_level_tables_against_an_independent_spelling():
+    """w2v_levels, the function aligner_run and the harness both call, against tests/model_io_cases.levels: a one-row clip, a clip across a ceil8 boundary, a
+    clip that ends as one frame, a clip with a second statistics tile; the tile start and the first sample on level 0 only."""
+    import model_io_cases as M
+    L = K.harness()
+    p = lambda a: a.ctypes.data_as(K.C.c_void_p)  # noqa: E731
+    for n, k, s in (((1, 9, 257), (1, 1), (3, 2)), ((5, 9, K.ST_TILE + 1), (3, 2), (2, 2)), ((400, 16000), (10, 3, 3, 2), (5, 2, 2, 2))):
+        N = len(k)
+        tab, rows, tiles, max_n = np.zeros((N + 1, len(n), K.SEQ), K.i32), np.zeros(N + 1, np.int64), np.zeros(N + 1, np.int64), np.zeros(N + 1, K.i32)
+        assert L.tts_w2v_test_levels(p(np.array(n, K.i32)), len(n), N, p(np.array(k, K.i32)), p(np.array(s, K.i32)), p(tab), p(rows), p(tiles), p(max_n)) == 0
+        want = M.levels(n, lambda v, l: 0 if v < k[l] else (v - k[l]) // s[l] + 1, N + 1, 8, K.ST_TILE, False)
+        assert np.array_equal(tab, want[0]) and np.array_equal(rows, want[1]) and tiles[0] == want[2][0] and np.array_equal(max_n, want[3]), (n, tab, want)
+        if n[0] == 5:
+            assert tab[2, 0, 1] == 1 and tab[0, 2, 3] == 2 and not tab[1:, :, 3:5].any()
+
+
+def test_reader_messages_have_the_shared_shape(tmp_path):
+    import model_io_cases as M
+    from tortoise_cpp_amd import synth_weights as sw
+
+    def load(t):
+        w = sw.GgmlWriter(str(tmp_path / "m.bin"))
+        for name, a in t.items():
+            w.add(name, a)
+        w.close()
+        rc, _, msg = K.parse(str(tmp_path / "m.bin"))
+        return rc, msg
+    M.reader_messages(load, R.model(next(iter(R.CONFIGS)))[1], "aligner", "aligner.lm_head.bias", -3)

@@ -1,6 +1,6 @@
 // wav2vec2 CTC aligner on MI355X (gfx950): a waveform -> one token id per 20 ms frame             tts_load_aligner / tts_aligner_ids / tts_align_audio / tts_redact_audio
 //
-// Included once, as the last line of classifier.h (hifigan.hip's translation unit): Wav2Vec2ForCTC in the "stable layer norm" configuration upstream tortoise-tts
+// Included once, as the last line of classifier.h (hifigan.hip's translation unit; its loader and clip ingest are model_io.h's): Wav2Vec2ForCTC in the "stable layer norm" configuration upstream tortoise-tts
 // loads for Wav2VecAlignment. Upstream's source and weights are not available offline: the contract is the arithmetic below ("What pins the
 // aligner"), checked between two float64 spellings (tests/aligner_ref.py); unpinned against upstream. f32 throughout: alignment rests on a per-frame argmax.
 //
@@ -282,19 +282,23 @@ void w2v_launch_head(const float *x, const float *w, const float *b, const int *
 // what the reused and the new kernels can tile: the head of this file states the rule
 bool w2v_channels_ok(int c) { return c >= 64 && c <= W2V_MAX_C && c % 64 == 0; }
 inline int w2v_conv_frames(int64_t n, int k, int s) { return n < k ? 0 : (int)((n - k) / s + 1); }
+// The tables of aligner_run (and of the test harness): level 0 = the samples, level i the output of convolution i - 1 (k[i - 1] taps, stride s[i - 1], no
+// padding); a clip's first row a multiple of 8; level 0 carries the clip's first statistics tile and its first sample at 16 kHz
+template <class T>
+LevelTable w2v_levels(const T *n, int B, int N, const int *k, const int *s) {
+  return level_table(n, B, N + 1, [k, s](int64_t v, int l) { return w2v_conv_frames(v, k[l], s[l]); }, 8, W2V_ST_TILE, false);
+}
 } // namespace
 
 // The model as the loader's host half leaves it (no device call): the configuration from the tensor shapes, every tensor repacked for the kernels.
-struct W2vHostLin { std::vector<float> w, b; }; // w: [cin][cout] (a convolution: [tap][cin][cout])
-struct W2vHostLn { std::vector<float> g, b; };
-struct W2vHostLayer { W2vHostLn n1, n2; W2vHostLin qkv, out, w1, w2; }; // qkv: [D][3 D], q | k | v, head h at columns h * 64 of each
+// HostLayer w: a Linear's [cin][cout], a convolution's [tap][cin][cout], a LayerNorm's gamma
+struct W2vHostLayer { HostLayer n1, n2, qkv, out, w1, w2; }; // qkv: [D][3 D], q | k | v, head h at columns h * 64 of each
 struct W2vHost {
   int N = 0, C = 0, D = 0, K = 0, cg = 0, depth = 0, FF = 0, V = 0, H = 16, blank = 0;
   std::vector<int> k, s;
-  std::vector<W2vHostLin> conv; // conv[0] keeps PyTorch's [C][1][k_0]
-  std::vector<W2vHostLn> conv_n;
-  W2vHostLn proj_n, enc_n;
-  W2vHostLin proj, pos, head; // pos: [group][tap][cin][cout]; head: [D][V]
+  std::vector<HostLayer> conv, conv_n; // conv[0] keeps PyTorch's [C][1][k_0]
+  HostLayer proj_n, enc_n;
+  HostLayer proj, pos, head; // pos: [group][tap][cin][cout]; head: [D][V]
   std::vector<W2vHostLayer> layers;
   std::vector<int32_t> vocab;
 };
@@ -302,33 +306,12 @@ struct W2vHost {
 int aligner_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, W2vHost &h) {
   const std::string P = "aligner.", FE = P + "feature_extractor.conv_layers.", EN = P + "encoder.";
   if (!wf.has(FE + "0.conv.weight")) return fail(ctx, TTS_ERR_FORMAT, "'%s' is not an aligner model file", path);
-  size_t known = 0;
-  // PyTorch shape [d0][d1][d2] = container ne {d2, d1, d0}; d2 = 0: [d0][d1]; d1 = 0: a vector of d0
-  auto need = [&](const std::string &name, int64_t d0, int64_t d1, int64_t d2) -> const HostTensor * {
-    auto it = wf.t.find(name);
-    if (it == wf.t.end()) { fail(ctx, TTS_ERR_FORMAT, "tensor '%s' missing from aligner model file", name.c_str()); return nullptr; }
-    const HostTensor &t = it->second;
-    const int nd = d2 ? 3 : d1 ? 2 : 1;
-    const int64_t want[3] = {nd == 3 ? d2 : nd == 2 ? d1 : d0, nd == 3 ? d1 : nd == 2 ? d0 : 1, nd == 3 ? d0 : 1};
-    bool ok = t.n_dims == nd && (int64_t)t.data.size() == t.nelem();
-    for (int i = 0; i < nd && ok; i++) ok = t.ne[i] == want[i];
-    if (!ok) {
-      fail(ctx, TTS_ERR_FORMAT, "tensor '%s' has wrong shape in aligner model file: got [%d, %d, %d] (%d dims), expected [%d, %d, %d]", name.c_str(),
-           (int)t.ne[0], (int)t.ne[1], (int)t.ne[2], t.n_dims, (int)want[0], (int)want[1], (int)want[2]);
-      return nullptr;
-    }
-    known++;
-    return &t;
-  };
-  auto dims = [&](const std::string &name, int nd) -> const HostTensor * {
-    auto it = wf.t.find(name);
-    return it != wf.t.end() && it->second.n_dims == nd ? &it->second : nullptr;
-  };
+  ModelReader rd{wf, ctx, "aligner"};
   // the configuration: N, C and k_i from the convolutions; D from the projection; K and D / G from pos_conv; depth and the width from the layers; V from lm_head
   while (wf.has(FE + std::to_string(h.N) + ".conv.weight")) h.N++;
   if (h.N > W2V_MAX_CONV) return fail(ctx, TTS_ERR_FORMAT, "aligner model file: %d convolution layers (at most %d)", h.N, W2V_MAX_CONV);
   for (int i = 0; i < h.N; i++) {
-    const HostTensor *t = dims(FE + std::to_string(i) + ".conv.weight", 3);
+    const HostTensor *t = rd.peek(FE + std::to_string(i) + ".conv.weight", 3);
     if (!t) return fail(ctx, TTS_ERR_FORMAT, "tensor '%s%d.conv.weight' has wrong shape in aligner model file (3 dims)", FE.c_str(), i);
     if (i == 0) h.C = (int)t->ne[2];
     h.k.push_back((int)t->ne[0]);
@@ -341,12 +324,12 @@ int aligner_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, W2vHost 
   for (int i = 1; i < h.N; i++)
     if (h.k[i] < 1 || h.k[i] > 16) return fail(ctx, TTS_ERR_FORMAT, "aligner model file: kernel size %d of convolution layer %d (1 .. 16)", h.k[i], i);
   {
-    const HostTensor *t = dims(P + "feature_projection.projection.weight", 2);
+    const HostTensor *t = rd.peek(P + "feature_projection.projection.weight", 2);
     h.D = t ? (int)t->ne[1] : 0;
     if (!w2v_channels_ok(h.D)) return fail(ctx, TTS_ERR_FORMAT, "aligner model file: model dimension %d (a multiple of 64, 64 .. %d)", h.D, W2V_MAX_C);
   }
   {
-    const HostTensor *t = dims(EN + "pos_conv_embed.conv.weight", 3);
+    const HostTensor *t = rd.peek(EN + "pos_conv_embed.conv.weight", 3);
     if (!t) return fail(ctx, TTS_ERR_FORMAT,
                         "tensor '%spos_conv_embed.conv.weight' missing from aligner model file (the converter folds weight_g / weight_v into it)", EN.c_str());
     h.K = (int)t->ne[0]; h.cg = (int)t->ne[1];
@@ -357,17 +340,17 @@ int aligner_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, W2vHost 
   while (wf.has(EN + "layers." + std::to_string(h.depth) + ".layer_norm.weight")) h.depth++;
   if (h.depth < 1) return fail(ctx, TTS_ERR_FORMAT, "tensor '%slayers.0.layer_norm.weight' missing from aligner model file", EN.c_str());
   {
-    const HostTensor *t = dims(EN + "layers.0.feed_forward.intermediate_dense.weight", 2);
+    const HostTensor *t = rd.peek(EN + "layers.0.feed_forward.intermediate_dense.weight", 2);
     h.FF = t ? (int)t->ne[1] : 0;
     if (h.FF < 64 || h.FF % 64) return fail(ctx, TTS_ERR_FORMAT, "aligner model file: feed-forward width %d (a multiple of 64)", h.FF);
-    t = dims(P + "lm_head.weight", 2);
+    t = rd.peek(P + "lm_head.weight", 2);
     h.V = t ? (int)t->ne[1] : 0;
     if (h.V < 1 || h.V > W2V_MAX_V) return fail(ctx, TTS_ERR_FORMAT, "aligner model file: vocabulary of %d tokens (1 .. %d)", h.V, W2V_MAX_V);
   }
   h.s.assign(h.N, 2);
   h.s[0] = 5;
   if (wf.has(P + "config")) { // what no shape holds: {heads, blank id, s_0 .. s_{N-1}}, integers
-    const HostTensor *t = need(P + "config", 2 + h.N, 0, 0);
+    const HostTensor *t = rd.need(P + "config", 2 + h.N, 0, 0);
     if (!t) return TTS_ERR_FORMAT;
     for (float v : t->data)
       if (v != (float)(int)v) return fail(ctx, TTS_ERR_FORMAT, "tensor 'aligner.config' holds %g: {heads, blank id, strides} are integers", (double)v);
@@ -380,7 +363,7 @@ int aligner_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, W2vHost 
     return fail(ctx, TTS_ERR_FORMAT, "aligner model file: %d channels in %d heads: the head dimension must be 64", h.D, h.H);
   if (h.blank < 0 || h.blank >= h.V) return fail(ctx, TTS_ERR_FORMAT, "aligner model file: blank id %d outside the vocabulary of %d", h.blank, h.V);
   {
-    const HostTensor *t = need(P + "vocab", h.V, 0, 0);
+    const HostTensor *t = rd.need(P + "vocab", h.V, 0, 0);
     if (!t) return TTS_ERR_FORMAT;
     h.vocab.resize(h.V);
     for (int i = 0; i < h.V; i++) {
@@ -389,59 +372,36 @@ int aligner_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, W2vHost 
       h.vocab[i] = (int)v;
     }
   }
-  auto lin = [&](const std::string &p, int cout, int cin, W2vHostLin &l) -> int { // Linear [cout][cin] -> [cin][cout]
-    const HostTensor *w, *b;
-    if (!(w = need(p + ".weight", cout, cin, 0)) || !(b = need(p + ".bias", cout, 0, 0))) return TTS_ERR_FORMAT;
-    l.w.resize((size_t)cin * cout);
-    for (int co = 0; co < cout; co++)
-      for (int ci = 0; ci < cin; ci++) l.w[(size_t)ci * cout + co] = w->data[(size_t)co * cin + ci];
-    l.b = b->data;
-    return TTS_OK;
-  };
-  auto norm = [&](const std::string &p, int c, W2vHostLn &g) -> int {
-    const HostTensor *w, *b;
-    if (!(w = need(p + ".weight", c, 0, 0)) || !(b = need(p + ".bias", c, 0, 0))) return TTS_ERR_FORMAT;
-    g.g = w->data; g.b = b->data;
-    return TTS_OK;
-  };
   int rc;
   h.conv.resize(h.N); h.conv_n.resize(h.N);
   for (int i = 0; i < h.N; i++) {
     const std::string p = FE + std::to_string(i);
-    const int cin = i ? h.C : 1, k = h.k[i];
-    const HostTensor *w, *b;
-    if (!(w = need(p + ".conv.weight", h.C, cin, k)) || !(b = need(p + ".conv.bias", h.C, 0, 0))) return TTS_ERR_FORMAT;
-    if (i == 0) h.conv[i].w = w->data;
-    else { // Conv1d [cout][cin][k] -> [k][cin][cout]
-      h.conv[i].w.resize((size_t)k * cin * h.C);
-      for (int co = 0; co < h.C; co++)
-        for (int ci = 0; ci < cin; ci++)
-          for (int j = 0; j < k; j++) h.conv[i].w[((size_t)j * cin + ci) * h.C + co] = w->data[((size_t)co * cin + ci) * k + j];
-    }
-    h.conv[i].b = b->data;
-    if ((rc = norm(p + ".layer_norm", h.C, h.conv_n[i]))) return rc;
+    if ((rc = i ? rd.conv(p + ".conv", h.C, h.C, h.k[i], h.conv[i]) : rd.raw(p + ".conv", h.C, 1, h.k[0], h.conv[0])) ||
+        (rc = rd.norm(p + ".layer_norm", h.C, h.conv_n[i])))
+      return rc;
   }
-  if ((rc = norm(P + "feature_projection.layer_norm", h.C, h.proj_n)) || (rc = lin(P + "feature_projection.projection", h.D, h.C, h.proj))) return rc;
-  {
+  if ((rc = rd.norm(P + "feature_projection.layer_norm", h.C, h.proj_n)) || (rc = rd.linear(P + "feature_projection.projection", h.D, h.C, h.proj))) return rc;
+  { // the grouped convolution [g cg + cout][cin][k] -> [g][k][cin][cout]
     const int D = h.D, cg = h.cg, K = h.K;
-    const HostTensor *w, *b;
-    if (!(w = need(EN + "pos_conv_embed.conv.weight", D, cg, K)) || !(b = need(EN + "pos_conv_embed.conv.bias", D, 0, 0))) return TTS_ERR_FORMAT;
+    HostLayer raw;
+    if ((rc = rd.raw(EN + "pos_conv_embed.conv", D, cg, K, raw))) return rc;
     h.pos.w.resize((size_t)D * cg * K);
     for (int g = 0; g < D / cg; g++)
       for (int co = 0; co < cg; co++)
         for (int ci = 0; ci < cg; ci++)
-          for (int j = 0; j < K; j++) h.pos.w[(((size_t)g * K + j) * cg + ci) * cg + co] = w->data[((size_t)(g * cg + co) * cg + ci) * K + j];
-    h.pos.b = b->data;
+          for (int j = 0; j < K; j++) h.pos.w[(((size_t)g * K + j) * cg + ci) * cg + co] = raw.w[((size_t)(g * cg + co) * cg + ci) * K + j];
+    h.pos.b = raw.b;
   }
   h.layers.resize(h.depth);
   for (int l = 0; l < h.depth; l++) {
     const std::string p = EN + "layers." + std::to_string(l);
     W2vHostLayer &y = h.layers[l];
     const int D = h.D;
-    W2vHostLin q[3];
-    if ((rc = norm(p + ".layer_norm", D, y.n1)) || (rc = lin(p + ".attention.q_proj", D, D, q[0])) || (rc = lin(p + ".attention.k_proj", D, D, q[1])) ||
-        (rc = lin(p + ".attention.v_proj", D, D, q[2])) || (rc = lin(p + ".attention.out_proj", D, D, y.out)) || (rc = norm(p + ".final_layer_norm", D, y.n2)) ||
-        (rc = lin(p + ".feed_forward.intermediate_dense", h.FF, D, y.w1)) || (rc = lin(p + ".feed_forward.output_dense", D, h.FF, y.w2)))
+    HostLayer q[3];
+    if ((rc = rd.norm(p + ".layer_norm", D, y.n1)) || (rc = rd.linear(p + ".attention.q_proj", D, D, q[0])) || (rc = rd.linear(p + ".attention.k_proj", D, D, q[1])) ||
+        (rc = rd.linear(p + ".attention.v_proj", D, D, q[2])) || (rc = rd.linear(p + ".attention.out_proj", D, D, y.out)) ||
+        (rc = rd.norm(p + ".final_layer_norm", D, y.n2)) || (rc = rd.linear(p + ".feed_forward.intermediate_dense", h.FF, D, y.w1)) ||
+        (rc = rd.linear(p + ".feed_forward.output_dense", D, h.FF, y.w2)))
       return rc;
     y.qkv.w.resize((size_t)3 * D * D); y.qkv.b.resize((size_t)3 * D); // the q | k | v blocks cls_attn_kernel reads
     for (int j = 0; j < 3; j++) {
@@ -449,25 +409,21 @@ int aligner_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, W2vHost 
       memcpy(&y.qkv.b[(size_t)j * D], q[j].b.data(), (size_t)D * 4);
     }
   }
-  if ((rc = norm(EN + "layer_norm", h.D, h.enc_n)) || (rc = lin(P + "lm_head", h.V, h.D, h.head))) return rc;
-  if (wf.t.size() != known) return fail(ctx, TTS_ERR_FORMAT, "unknown tensors in aligner model file '%s' (%d tensors, %d expected)", path, (int)wf.t.size(), (int)known);
-  return TTS_OK;
+  if ((rc = rd.norm(EN + "layer_norm", h.D, h.enc_n)) || (rc = rd.linear(P + "lm_head", h.V, h.D, h.head))) return rc;
+  return rd.finish(path);
 }
 
-struct W2vLn { float *g = nullptr, *b = nullptr; };
-struct W2vLayer { W2vLn n1, n2; HfgLayer qkv, out, w1, w2; };
+struct W2vLayer { HfgLayer n1, n2, qkv, out, w1, w2; };
 struct AlignerState {
   int N = 0, C = 0, D = 0, K = 0, cg = 0, depth = 0, FF = 0, V = 0, H = 16, blank = 0;
   std::vector<int> k, s;
   std::vector<int32_t> vocab;
-  std::vector<HfgLayer> conv;
-  std::vector<W2vLn> conv_n;
-  W2vLn proj_n, enc_n;
+  std::vector<HfgLayer> conv, conv_n;
+  HfgLayer proj_n, enc_n;
   HfgLayer proj, pos, head;
   std::vector<W2vLayer> layers;
-  std::vector<void *> owned;
+  DevWeights dev;
   DevBuf in, wav, part, stat, a, t, h, h2, y, qkv, att, ff, ids, logits;
-  ~AlignerState() { for (void *p : owned) (void)hipFree(p); }
 };
 void aligner_free(AlignerState *s) { delete s; }
 
@@ -485,27 +441,17 @@ int aligner_load(tts_ctx *ctx, const char *path) {
   std::unique_ptr<AlignerState> st(new AlignerState());
   st->N = h->N; st->C = h->C; st->D = h->D; st->K = h->K; st->cg = h->cg; st->depth = h->depth; st->FF = h->FF; st->V = h->V; st->H = h->H; st->blank = h->blank;
   st->k = h->k; st->s = h->s; st->vocab = h->vocab;
-  auto up = [&](const std::vector<float> &src, float **dst) -> int {
-    void *p = nullptr;
-    TTS_HIP(ctx, hipMalloc(&p, src.size() * 4));
-    st->owned.push_back(p);
-    TTS_HIP(ctx, hipMemcpy(p, src.data(), src.size() * 4, hipMemcpyHostToDevice));
-    *dst = (float *)p;
-    return TTS_OK;
-  };
-  auto layer = [&](const W2vHostLin &s, HfgLayer &d) -> int { int e = up(s.w, &d.w); return e ? e : up(s.b, &d.b); };
-  auto ln = [&](const W2vHostLn &s, W2vLn &d) -> int { int e = up(s.g, &d.g); return e ? e : up(s.b, &d.b); };
+  auto up = [&](const HostLayer &s, HfgLayer &d) { return st->dev.up(ctx, s, d); };
   st->conv.resize(h->N); st->conv_n.resize(h->N); st->layers.resize(h->depth);
   for (int i = 0; i < h->N; i++)
-    if ((rc = layer(h->conv[i], st->conv[i])) || (rc = ln(h->conv_n[i], st->conv_n[i]))) return rc;
-  if ((rc = ln(h->proj_n, st->proj_n)) || (rc = layer(h->proj, st->proj)) || (rc = layer(h->pos, st->pos)) || (rc = ln(h->enc_n, st->enc_n)) ||
-      (rc = layer(h->head, st->head)))
+    if ((rc = up(h->conv[i], st->conv[i])) || (rc = up(h->conv_n[i], st->conv_n[i]))) return rc;
+  if ((rc = up(h->proj_n, st->proj_n)) || (rc = up(h->proj, st->proj)) || (rc = up(h->pos, st->pos)) || (rc = up(h->enc_n, st->enc_n)) ||
+      (rc = up(h->head, st->head)))
     return rc;
   for (int l = 0; l < h->depth; l++) {
     const W2vHostLayer &s = h->layers[l];
     W2vLayer &d = st->layers[l];
-    if ((rc = ln(s.n1, d.n1)) || (rc = ln(s.n2, d.n2)) || (rc = layer(s.qkv, d.qkv)) || (rc = layer(s.out, d.out)) || (rc = layer(s.w1, d.w1)) ||
-        (rc = layer(s.w2, d.w2)))
+    if ((rc = up(s.n1, d.n1)) || (rc = up(s.n2, d.n2)) || (rc = up(s.qkv, d.qkv)) || (rc = up(s.out, d.out)) || (rc = up(s.w1, d.w1)) || (rc = up(s.w2, d.w2)))
       return rc;
   }
   if (ctx->aligner) aligner_free(ctx->aligner);
@@ -550,54 +496,25 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
   if (!st) return fail(ctx, TTS_ERR_STATE, "tts_load_aligner not called");
   if (!audio || !n_samples || !rates || !ids_out || !n_frames_out || !resample || B < 1 || frame_stride < 1) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", fn);
   if (B > W2V_MAX_CLIPS) return fail(ctx, TTS_ERR_LIMIT, "%s: %d clips (at most %d per call)", fn, B, W2V_MAX_CLIPS);
-  const int N = st->N, L = N + 1, C = st->C, D = st->D, V = st->V;
-  std::vector<ClsResampleClip> rs;
-  std::vector<int64_t> src_off(B), n16(B);
+  const int N = st->N, C = st->C, D = st->D, V = st->V;
+  ClipIngest clips;
   std::vector<int> frames(B);
-  int64_t total_src = 0, total16 = 0;
-  for (int s = 0; s < B; s++) {
-    const int64_t n = n_samples[s];
-    if (n < 1) return fail(ctx, TTS_ERR_ARG, "%s: clip %d: %lld samples", fn, s, (long long)n);
-    if (n > (1 << 26)) return fail(ctx, TTS_ERR_LIMIT, "%s: clip %d: %lld samples, at most 2^26", fn, s, (long long)n);
-    AfeResampleGeom g;
-    if (rates[s] < 1 || afe_resample_geometry(rates[s], 16000, &g) != TTS_OK)
-      return fail(ctx, TTS_ERR_ARG, "%s: clip %d: sample rate %d is outside the audio front end's range", fn, s, rates[s]);
-    src_off[s] = total_src;
-    n16[s] = rates[s] == 16000 ? n : afe_resample_len(g, n);
-    if (n16[s] > (1 << 26)) return fail(ctx, TTS_ERR_LIMIT, "%s: clip %d: %lld samples at 16 kHz, at most 2^26", fn, s, (long long)n16[s]);
-    int64_t f = n16[s];
+  int rc = clip_ingest(ctx, fn, audio, n_samples, rates, B, 16000, 0, clips, [&](int s, int64_t n16) {
+    int64_t f = n16;
     for (int i = 0; i < N; i++) f = w2v_conv_frames(f, st->k[i], st->s[i]);
-    if (f < 1) return fail(ctx, TTS_ERR_ARG, "%s: clip %d: %lld samples at 16 kHz leave less than one frame", fn, s, (long long)n16[s]);
+    if (f < 1) return fail(ctx, TTS_ERR_ARG, "%s: clip %d: %lld samples at 16 kHz leave less than one frame", fn, s, (long long)n16);
     if (f > frame_stride) return fail(ctx, TTS_ERR_ARG, "%s: clip %d has %d frames, frame_stride is %d", fn, s, (int)f, frame_stride);
     frames[s] = (int)f;
-    if (rates[s] != 16000) rs.push_back(ClsResampleClip{total_src, n, total16, n16[s], rates[s]});
-    total_src += n; total16 += (n16[s] + 7) / 8 * 8;
-  }
-  if (total16 > (1ll << 30)) return fail(ctx, TTS_ERR_LIMIT, "%s: %lld samples at 16 kHz in one call, at most 2^30", fn, (long long)total16);
-  for (int64_t i = 0; i < total_src; i++)
-    if (!std::isfinite(audio[i])) return fail(ctx, TTS_ERR_ARG, "%s: the audio holds a non-finite sample (element %lld)", fn, (long long)i);
-  // the tables: level l's HFG_SEQ records {first row, rows, 0, first statistics tile (level 0), first sample at 16 kHz (level 0)}
-  std::vector<int> tab((size_t)L * B * HFG_SEQ, 0);
-  std::vector<int64_t> rows(L, 0);
-  std::vector<int> max_n(L, 0);
-  int64_t tiles = 0;
-  for (int s = 0; s < B; s++) {
-    int64_t n = n16[s];
-    for (int l = 0; l < L; l++) {
-      int *q = &tab[((size_t)l * B + s) * HFG_SEQ];
-      q[0] = (int)rows[l]; q[1] = (int)n;
-      if (l == 0) { q[3] = (int)tiles; q[4] = (int)rows[0]; tiles += (n + W2V_ST_TILE - 1) / W2V_ST_TILE; }
-      rows[l] += (n + 7) / 8 * 8; max_n[l] = std::max(max_n[l], (int)n);
-      if (l < N) n = w2v_conv_frames(n, st->k[l], st->s[l]);
-    }
-  }
-  const int64_t R = rows[N];
-  std::vector<float> up((size_t)total_src + tab.size());
-  memcpy(up.data(), audio, (size_t)total_src * 4);
-  memcpy(up.data() + total_src, tab.data(), tab.size() * 4);
-  TTS_HIP(ctx, st->in.reserve(up.size() * 4));
+    return (int)TTS_OK;
+  });
+  if (rc) return rc;
+  const LevelTable lt = w2v_levels(clips.n_dst.data(), B, N, st->k.data(), st->s.data());
+  const std::vector<int64_t> &rows = lt.rows;
+  const std::vector<int> &max_n = lt.max_n;
+  const int64_t R = rows[N], total16 = clips.total_dst;
+  TTS_HIP(ctx, st->in.reserve(clip_upload_floats(clips, lt) * 4));
   TTS_HIP(ctx, st->wav.reserve((size_t)total16 * 4));
-  TTS_HIP(ctx, st->part.reserve((size_t)tiles * sizeof(double2)));
+  TTS_HIP(ctx, st->part.reserve((size_t)lt.tiles[0] * sizeof(double2)));
   TTS_HIP(ctx, st->stat.reserve((size_t)B * sizeof(double2)));
   TTS_HIP(ctx, st->a.reserve((size_t)rows[1] * C * 4));
   TTS_HIP(ctx, st->t.reserve((size_t)rows[1] * C * 4));
@@ -610,25 +527,16 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
   TTS_HIP(ctx, st->ids.reserve((size_t)R * 4));
   if (logits_out) TTS_HIP(ctx, st->logits.reserve((size_t)R * V * 4));
   hipStream_t sm = ctx->stream;
-  TTS_HIP(ctx, hipMemcpyAsync(st->in.p, up.data(), up.size() * 4, hipMemcpyHostToDevice, sm));
-  const float *d_src = st->in.as<float>();
-  const int *d_tab = (const int *)(d_src + total_src);
-  auto seq = [&](int l) { return d_tab + (size_t)l * B * HFG_SEQ; };
   float *wav = st->wav.as<float>();
-  // a clip at 16 kHz reaches the network bit for bit; the others through the audio front end's resampler, one stage
-  for (int s = 0; s < B; s++)
-    if (rates[s] == 16000)
-      TTS_HIP(ctx, hipMemcpyAsync(wav + tab[(size_t)s * HFG_SEQ + 4], d_src + src_off[s], (size_t)n16[s] * 4, hipMemcpyDeviceToDevice, sm));
-  if (!rs.empty()) {
-    const int rc = resample(ctx, d_src, wav, rs.data(), (int)rs.size());
-    if (rc) return rc;
-  }
+  const int *d_tab = nullptr;
+  if ((rc = clip_upload(ctx, clips, lt, audio, rates, 16000, st->in, wav, resample, &d_tab))) return rc;
+  auto seq = [&](int l) { return d_tab + (size_t)l * B * HFG_SEQ; };
   float *a = st->a.as<float>(), *t = st->t.as<float>(), *h = st->h.as<float>(), *h2 = st->h2.as<float>(), *y = st->y.as<float>();
   float *qkv = st->qkv.as<float>(), *att = st->att.as<float>(), *ff = st->ff.as<float>();
   double2 *stat = st->stat.as<double2>();
-  auto ln = [&](const float *x, float *out, const W2vLn &p, int l, int ch, int gelu) {
+  auto ln = [&](const float *x, float *out, const HfgLayer &p, int l, int ch, int gelu) {
     ProfScope ps(ctx, "w2v_row", (double)rows[l] * ch * 4 * 2);
-    w2v_launch_ln(x, out, p.g, p.b, seq(l), ch, gelu, max_n[l], B, sm);
+    w2v_launch_ln(x, out, p.w, p.b, seq(l), ch, gelu, max_n[l], B, sm);
   };
   auto linear = [&](const float *in, float *out, const float *resid, const HfgLayer &w, int cin, int cout) {
     ProfScope ps(ctx, "w2v_conv", 2.0 * (double)R * cin * cout);
@@ -691,7 +599,7 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
   if (logits_out) TTS_HIP(ctx, hipMemcpyAsync(lg.data(), st->logits.p, lg.size() * 4, hipMemcpyDeviceToHost, sm));
   TTS_HIP(ctx, hipStreamSynchronize(sm));
   for (int s = 0; s < B; s++) {
-    const size_t f0 = (size_t)tab[((size_t)N * B + s) * HFG_SEQ];
+    const size_t f0 = (size_t)lt.rec(N, s)[0];
     n_frames_out[s] = frames[s];
     memcpy(ids_out + (size_t)s * frame_stride, &ids[f0], (size_t)frames[s] * 4);
     if (logits_out) memcpy(logits_out + (size_t)s * frame_stride * V, &lg[f0 * V], (size_t)frames[s] * V * 4);

@@ -1,6 +1,6 @@
 // BigVGAN vocoder on MI355X (gfx950): 100-band log-mel -> 24 kHz waveform                         tts_load_bigvgan / tts_bigvgan / tts_bigvgan_config
 //
-// Included once, as the last line of hifigan.hip: BigVGAN (v1: bigvgan_base_24khz_100band, bigvgan_24khz_100band) is HiFi-GAN's generator with every
+// Included once, as the last line of hifigan.hip (whose host half starts with model_io.h: the tensor reader and the weight store): BigVGAN (v1: bigvgan_base_24khz_100band, bigvgan_24khz_100band) is HiFi-GAN's generator with every
 // leaky ReLU replaced by an anti-aliased periodic activation and no activation in front of the transposed convolutions, so its convolutions ARE
 // hfg_conv_kernel<1|2> with slope 1, no conditioning vector and voice 0, on HfgConv / HFG_SEQ candidate tables exactly as hifigan_run builds them.
 // New here: the mel front end, the activation and conv_post. NVIDIA's source and weights are not available offline: the contract is the arithmetic of
@@ -160,84 +160,59 @@ int bvg_pad32(int c) { return (c + 31) / 32 * 32; }
 
 // The model as the loader's host half leaves it: the configuration read from the tensor shapes, every tensor repacked and zero-padded for the kernels.
 // bigvgan_parse makes it without a device call (the tests read its table through a host probe); bigvgan_load uploads it.
-struct BvgHostLayer { std::vector<float> w, b; };
-struct BvgHostAct { std::vector<float> alpha, inv_beta; }; // exp(a) and 1 / (exp(b) + 1e-9), evaluated in double, rounded once
+using BvgHostAct = HostLayer; // w: alpha = exp(a), b: inv_beta = 1 / (exp(b) + 1e-9), evaluated in double, rounded once
 struct BvgHost {
   int c0 = 0, n_stages = 0, up[BVG_MAX_STAGES] = {0, 0, 0, 0, 0, 0};
   int ch[BVG_MAX_STAGES + 1] = {0, 0, 0, 0, 0, 0, 0}; // padded channels: ch[0] after conv_pre, ch[i + 1] after stage i
-  BvgHostLayer pre, post, ups[BVG_MAX_STAGES], c1[BVG_MAX_STAGES][3][3], c2[BVG_MAX_STAGES][3][3];
+  HostLayer pre, post, ups[BVG_MAX_STAGES], c1[BVG_MAX_STAGES][3][3], c2[BVG_MAX_STAGES][3][3];
   BvgHostAct act[BVG_MAX_STAGES][3][6], act_post;
 };
 
 int bigvgan_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, BvgHost &h) {
   if (!wf.has("bigvgan.conv_pre.weight")) return fail(ctx, TTS_ERR_FORMAT, "'%s' is not a BigVGAN model file", path);
-  size_t known = 0;
-  // PyTorch shape [d0][d1][d2] (d2 = 0: a vector of d0) = container ne {d2, d1, d0}
-  auto need = [&](const std::string &name, int64_t d0, int64_t d1, int64_t d2) -> const HostTensor * {
-    auto it = wf.t.find(name);
-    if (it == wf.t.end()) { fail(ctx, TTS_ERR_FORMAT, "tensor '%s' missing from BigVGAN model file", name.c_str()); return nullptr; }
-    const HostTensor &t = it->second;
-    const bool ok = d2 ? (t.n_dims == 3 && t.ne[0] == d2 && t.ne[1] == d1 && t.ne[2] == d0) : (t.n_dims == 1 && t.ne[0] == d0);
-    if (!ok || t.nelem() != (d2 ? d0 * d1 * d2 : d0) || (int64_t)t.data.size() != t.nelem()) {
-      fail(ctx, TTS_ERR_FORMAT, "tensor '%s' has wrong shape in BigVGAN model file: got [%d, %d, %d] (%d dims), expected [%d, %d, %d]", name.c_str(),
-           (int)t.ne[0], (int)t.ne[1], (int)t.ne[2], t.n_dims, (int)(d2 ? d2 : d0), (int)(d2 ? d1 : 1), (int)(d2 ? d0 : 1));
-      return nullptr;
-    }
-    known++;
-    return &t;
-  };
+  ModelReader rd{wf, ctx, "BigVGAN"};
   // the configuration: C0 from conv_pre.weight, the stages from the ups.* weights (ConvTranspose1d [cin][cout][2 u])
   {
-    const HostTensor &t = wf.t.find("bigvgan.conv_pre.weight")->second;
-    if (t.n_dims != 3 || t.ne[2] < 2 || t.ne[2] > 8192) return fail(ctx, TTS_ERR_FORMAT, "tensor 'bigvgan.conv_pre.weight' has wrong shape in BigVGAN model file");
-    h.c0 = (int)t.ne[2];
+    const HostTensor *t = rd.peek("bigvgan.conv_pre.weight", 3);
+    if (!t || t->ne[2] < 2 || t->ne[2] > 8192) return fail(ctx, TTS_ERR_FORMAT, "tensor 'bigvgan.conv_pre.weight' has wrong shape in BigVGAN model file");
+    h.c0 = (int)t->ne[2];
   }
   int64_t prod = 1;
   while (h.n_stages < BVG_MAX_STAGES) {
-    auto it = wf.t.find("bigvgan.ups." + std::to_string(h.n_stages) + ".0.weight");
-    if (it == wf.t.end()) break;
-    const int64_t ku = it->second.n_dims == 3 ? it->second.ne[0] : 0;
+    const std::string name = "bigvgan.ups." + std::to_string(h.n_stages) + ".0.weight";
+    if (!rd.has(name)) break;
+    const HostTensor *t = rd.peek(name, 3);
+    const int64_t ku = t ? t->ne[0] : 0;
     if (ku < 4 || ku % 4 || ku > 512) return fail(ctx, TTS_ERR_FORMAT, "BigVGAN model file: ups.%d has kernel %d (twice an even stride)", h.n_stages, (int)ku);
     h.up[h.n_stages++] = (int)(ku / 2);
     prod *= ku / 2;
   }
   if (prod != 256) return fail(ctx, TTS_ERR_FORMAT, "BigVGAN model file: the strides of its %d stages multiply to %lld, not to the 256 samples of a mel frame", h.n_stages, (long long)prod);
   if (h.c0 % (1 << h.n_stages)) return fail(ctx, TTS_ERR_FORMAT, "BigVGAN model file: %d channels cannot be halved %d times", h.c0, h.n_stages);
-  // Conv1d [cout][cin][k] -> [k][cin_p][cout_p], zero where a padded channel is an operand or a result
-  auto conv = [&](const std::string &p, int cout, int cin, int k, int coutp, int cinp, BvgHostLayer &l) -> int {
-    const HostTensor *w, *b;
-    if (!(w = need(p + ".weight", cout, cin, k)) || !(b = need(p + ".bias", cout, 0, 0))) return TTS_ERR_FORMAT;
-    l.w.assign((size_t)k * cinp * coutp, 0.f);
-    for (int co = 0; co < cout; co++)
-      for (int ci = 0; ci < cin; ci++)
-        for (int j = 0; j < k; j++) l.w[((size_t)j * cinp + ci) * coutp + co] = w->data[((size_t)co * cin + ci) * k + j];
-    l.b.assign(coutp, 0.f);
-    std::copy(b->data.begin(), b->data.end(), l.b.begin());
-    return TTS_OK;
-  };
+  // every Conv1d through rd.conv: [k][cin_p][cout_p], zero where a padded channel is an operand or a result
   auto act = [&](const std::string &p, int c, int cp, BvgHostAct &a) -> int {
-    const HostTensor *al, *be;
-    if (!(al = need(p + ".act.alpha", c, 0, 0)) || !(be = need(p + ".act.beta", c, 0, 0))) return TTS_ERR_FORMAT;
-    a.alpha.assign(cp, 1.f); a.inv_beta.assign(cp, 1.f); // a = b = 0 on the padded channels (whose input is exactly 0)
+    HostLayer raw; // the file's a and b
+    if (rd.vec_pair(p, ".act.alpha", ".act.beta", c, raw)) return TTS_ERR_FORMAT;
+    a.w.assign(cp, 1.f); a.b.assign(cp, 1.f); // a = b = 0 on the padded channels (whose input is exactly 0)
     for (int i = 0; i < c; i++) {
-      a.alpha[i] = (float)std::exp((double)al->data[i]);
-      a.inv_beta[i] = (float)(1.0 / (std::exp((double)be->data[i]) + 1e-9));
-      if (!std::isfinite(a.alpha[i]) || !std::isfinite(a.inv_beta[i])) return fail(ctx, TTS_ERR_FORMAT, "tensor '%s.act': channel %d has no finite alpha, 1 / beta", p.c_str(), i);
+      a.w[i] = (float)std::exp((double)raw.w[i]);
+      a.b[i] = (float)(1.0 / (std::exp((double)raw.b[i]) + 1e-9));
+      if (!std::isfinite(a.w[i]) || !std::isfinite(a.b[i])) return fail(ctx, TTS_ERR_FORMAT, "tensor '%s.act': channel %d has no finite alpha, 1 / beta", p.c_str(), i);
     }
     return TTS_OK;
   };
   int rc;
   h.ch[0] = bvg_pad32(h.c0);
-  if ((rc = conv("bigvgan.conv_pre", h.c0, BVG_MEL, 7, h.ch[0], BVG_MEL_PAD, h.pre))) return rc;
+  if ((rc = rd.conv("bigvgan.conv_pre", h.c0, BVG_MEL, 7, h.pre, h.ch[0], BVG_MEL_PAD))) return rc;
   int c = h.c0;
   for (int i = 0; i < h.n_stages; i++) {
     const int u = h.up[i], ku = 2 * u, pad = u / 2, cin = c, cout = c / 2, cinp = h.ch[i], coutp = bvg_pad32(cout);
     h.ch[i + 1] = coutp;
     const std::string p = "bigvgan.ups." + std::to_string(i) + ".0";
     const HostTensor *w, *b;
-    if (!(w = need(p + ".weight", cin, cout, ku)) || !(b = need(p + ".bias", cout, 0, 0))) return TTS_ERR_FORMAT;
+    if (!(w = rd.need(p + ".weight", cin, cout, ku)) || !(b = rd.need(p + ".bias", cout, 0, 0))) return TTS_ERR_FORMAT;
     // ConvTranspose1d [cin][cout][ku] -> [phase][2][cin_p][cout_p]: tap 0 = kernel index k0 + u (input row q + s_p - 1), tap 1 = k0 (row q + s_p)
-    BvgHostLayer &l = h.ups[i];
+    HostLayer &l = h.ups[i];
     l.w.assign((size_t)u * 2 * cinp * coutp, 0.f);
     for (int ph = 0; ph < u; ph++) {
       const int k0 = (ph + pad) % u;
@@ -251,35 +226,26 @@ int bigvgan_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, BvgHost 
     for (int j = 0; j < 3; j++) {
       const std::string rb = "bigvgan.resblocks." + std::to_string(3 * i + j);
       for (int n = 0; n < 3; n++) {
-        if ((rc = conv(rb + ".convs1." + std::to_string(n), c, c, HFG_RK[j], coutp, coutp, h.c1[i][j][n]))) return rc;
-        if ((rc = conv(rb + ".convs2." + std::to_string(n), c, c, HFG_RK[j], coutp, coutp, h.c2[i][j][n]))) return rc;
+        if ((rc = rd.conv(rb + ".convs1." + std::to_string(n), c, c, HFG_RK[j], h.c1[i][j][n], coutp, coutp))) return rc;
+        if ((rc = rd.conv(rb + ".convs2." + std::to_string(n), c, c, HFG_RK[j], h.c2[i][j][n], coutp, coutp))) return rc;
       }
       for (int n = 0; n < 6; n++)
         if ((rc = act(rb + ".activations." + std::to_string(n), c, coutp, h.act[i][j][n]))) return rc;
     }
   }
   if ((rc = act("bigvgan.activation_post", c, h.ch[h.n_stages], h.act_post))) return rc;
-  { // conv_post [1][c][7] -> [7][c_p]
-    const HostTensor *w, *b;
-    if (!(w = need("bigvgan.conv_post.weight", 1, c, 7)) || !(b = need("bigvgan.conv_post.bias", 1, 0, 0))) return TTS_ERR_FORMAT;
-    const int cp = h.ch[h.n_stages];
-    h.post.w.assign((size_t)7 * cp, 0.f);
-    for (int ci = 0; ci < c; ci++)
-      for (int j = 0; j < 7; j++) h.post.w[(size_t)j * cp + ci] = w->data[(size_t)ci * 7 + j];
-    h.post.b = b->data;
-  }
-  if (wf.t.size() != known) return fail(ctx, TTS_ERR_FORMAT, "unknown tensors in BigVGAN model file '%s' (%d tensors, %d expected)", path, (int)wf.t.size(), (int)known);
-  return TTS_OK;
+  // conv_post [1][c][7] -> [7][c_p]
+  if ((rc = rd.conv("bigvgan.conv_post", 1, c, 7, h.post, 1, h.ch[h.n_stages]))) return rc;
+  return rd.finish(path);
 }
 
-struct BvgAct { float *alpha = nullptr, *inv_beta = nullptr; };
+using BvgAct = HfgLayer; // w: alpha, b: inv_beta
 struct BigvganState {
   int c0 = 0, n_stages = 0, up[BVG_MAX_STAGES] = {0, 0, 0, 0, 0, 0}, ch[BVG_MAX_STAGES + 1] = {0, 0, 0, 0, 0, 0, 0};
   HfgLayer pre, post, ups[BVG_MAX_STAGES], c1[BVG_MAX_STAGES][3][3], c2[BVG_MAX_STAGES][3][3];
   BvgAct act[BVG_MAX_STAGES][3][6], act_post;
-  std::vector<void *> owned;
+  DevWeights dev;
   DevBuf in, mel, x, u, t, m, a, audio;
-  ~BigvganState() { for (void *p : owned) (void)hipFree(p); }
 };
 void bigvgan_free(BigvganState *s) { delete s; }
 
@@ -291,27 +257,18 @@ int bigvgan_load(tts_ctx *ctx, const char *path) {
   std::unique_ptr<BvgHost> h(new BvgHost());
   if ((rc = bigvgan_parse(ctx, wf, path, *h))) return rc;
   std::unique_ptr<BigvganState> st(new BigvganState());
-  auto up = [&](const std::vector<float> &src, float **dst) -> int {
-    void *p = nullptr;
-    TTS_HIP(ctx, hipMalloc(&p, src.size() * 4));
-    st->owned.push_back(p);
-    TTS_HIP(ctx, hipMemcpy(p, src.data(), src.size() * 4, hipMemcpyHostToDevice));
-    *dst = (float *)p;
-    return TTS_OK;
-  };
-  auto layer = [&](const BvgHostLayer &s, HfgLayer &d) -> int { int e = up(s.w, &d.w); return e ? e : up(s.b, &d.b); };
-  auto actv = [&](const BvgHostAct &s, BvgAct &d) -> int { int e = up(s.alpha, &d.alpha); return e ? e : up(s.inv_beta, &d.inv_beta); };
+  auto up = [&](const HostLayer &s, HfgLayer &d) { return st->dev.up(ctx, s, d); };
   st->c0 = h->c0; st->n_stages = h->n_stages;
   for (int i = 0; i < BVG_MAX_STAGES; i++) st->up[i] = h->up[i];
   for (int i = 0; i <= BVG_MAX_STAGES; i++) st->ch[i] = h->ch[i];
-  if ((rc = layer(h->pre, st->pre)) || (rc = layer(h->post, st->post)) || (rc = actv(h->act_post, st->act_post))) return rc;
+  if ((rc = up(h->pre, st->pre)) || (rc = up(h->post, st->post)) || (rc = up(h->act_post, st->act_post))) return rc;
   for (int i = 0; i < h->n_stages; i++) {
-    if ((rc = layer(h->ups[i], st->ups[i]))) return rc;
+    if ((rc = up(h->ups[i], st->ups[i]))) return rc;
     for (int j = 0; j < 3; j++) {
       for (int n = 0; n < 3; n++)
-        if ((rc = layer(h->c1[i][j][n], st->c1[i][j][n])) || (rc = layer(h->c2[i][j][n], st->c2[i][j][n]))) return rc;
+        if ((rc = up(h->c1[i][j][n], st->c1[i][j][n])) || (rc = up(h->c2[i][j][n], st->c2[i][j][n]))) return rc;
       for (int n = 0; n < 6; n++)
-        if ((rc = actv(h->act[i][j][n], st->act[i][j][n]))) return rc;
+        if ((rc = up(h->act[i][j][n], st->act[i][j][n]))) return rc;
     }
   }
   if (ctx->bigvgan) bigvgan_free(ctx->bigvgan);
@@ -391,7 +348,7 @@ int bigvgan_run(tts_ctx *ctx, const float *mel, const int32_t *frames_in, int B,
   auto actv = [&](const float *in, float *out, const BvgAct &p, int C, int rate) {
     ProfScope ps(ctx, "bvg_act", 2.0 * (double)frames * rate * C * 4);
     const dim3 grid((unsigned)(((size_t)maxT * rate + BVG_ACT_RUNS * BVG_RUN - 1) / (BVG_ACT_RUNS * BVG_RUN)), (unsigned)B, (unsigned)(C / 32));
-    bvg_act_kernel<<<grid, 256, 0, ctx->stream>>>(in, out, p.alpha, p.inv_beta, d_seq, C, rate);
+    bvg_act_kernel<<<grid, 256, 0, ctx->stream>>>(in, out, p.w, p.b, d_seq, C, rate);
   };
   conv(st->mel.as<float>(), x, nullptr, st->pre, BVG_MEL_PAD, st->ch[0], 7, 1, 1, 1, 0);
   const float *cur = x;
@@ -415,7 +372,7 @@ int bigvgan_run(tts_ctx *ctx, const float *mel, const int32_t *frames_in, int B,
   }
   {
     ProfScope ps(ctx, "bvg_post", (double)frames * 256 * (st->ch[st->n_stages] + 1) * 4);
-    bvg_post_kernel<<<dim3(maxT, B), 256, 0, ctx->stream>>>(cur, st->post.w, st->post.b, st->act_post.alpha, st->act_post.inv_beta, d_seq, st->audio.as<float>(),
+    bvg_post_kernel<<<dim3(maxT, B), 256, 0, ctx->stream>>>(cur, st->post.w, st->post.b, st->act_post.w, st->act_post.b, d_seq, st->audio.as<float>(),
                                                            st->ch[st->n_stages]);
   }
   TTS_HIP(ctx, hipGetLastError());

@@ -1,6 +1,7 @@
 // tortoise-detect on MI355X (gfx950): a 24 kHz waveform -> "probability that the clip came from Tortoise"      tts_load_classifier / tts_classify_audio
 //
-// Included once, as the last line of bigvgan.h (itself the last line of hifigan.hip): upstream's AudioMiniEncoderWithClassifierHead is a convolutional encoder on the raw
+// Included once, as the last line of bigvgan.h (itself the last line of hifigan.hip, whose model_io.h holds the tensor reader, the weight store, the level
+// tables and the clip ingest used here): upstream's AudioMiniEncoderWithClassifierHead is a convolutional encoder on the raw
 // waveform whose C -> C convolutions ARE hfg_conv_kernel<1|2> with slope 1, no conditioning vector and voice 0, on HFG_SEQ records with one row per "frame"
 // (rate 1), one table per level. Upstream's source and weights are not available offline: the contract is the arithmetic of DESIGN.md ("What pins the
 // classifier"), checked between two float64 spellings (tests/classifier_ref.py); unpinned against upstream, unjudged on real audio.
@@ -306,49 +307,32 @@ void cls_launch_conv(const float *in, float *out, const float *resid, const floa
   else hfg_conv_kernel<1><<<grid, 256, lds, st>>>(a);
 }
 bool cls_pow2_channels(int c) { return c >= 32 && c <= CLS_MAX_C && (c & (c - 1)) == 0; }
+// The tables of classifier_run (and of the test harness): levels 0 .. depth, a Downsample (k 5, stride F, pad 2) between two; every level's records carry
+// {first row, rows, 0, first GroupNorm tile, first sample of the clip at 24 kHz}, a clip's first row a multiple of 8
+template <class T>
+LevelTable cls_levels(const T *n, int B, int depth, int F) {
+  return level_table(n, B, depth + 1, [F](int64_t v, int) { return (v - 1) / F + 1; }, 8, CLS_GN_TILE, true);
+}
 } // namespace
 
 // The model as the loader's host half leaves it (no device call): the configuration from the tensor names and shapes, every tensor repacked for the kernels.
-struct ClsHostConv { std::vector<float> w, b; };
-struct ClsHostGn { std::vector<float> g, b; };
-struct ClsHostRes { ClsHostGn n1, n2; ClsHostConv ca, cb; };
-struct ClsHostAttn { ClsHostGn n; ClsHostConv qkv, proj; }; // qkv: [E][3 E] with the output channels in q | k | v order, head h at columns h * dh of each
+// (w, b of a norm: gamma, beta, here and in ClassifierState)
+struct ClsHostRes { HostLayer n1, n2, ca, cb; };
+struct ClsHostAttn { HostLayer n, qkv, proj; }; // qkv: [E][3 E] with the output channels in q | k | v order, head h at columns h * dh of each
 struct ClsHost {
   int b0 = 0, depth = 0, K = 0, E = 0, rb = 0, n_attn = 0, F = 4, H = 4;
-  ClsHostConv stem, fin, head;
-  ClsHostGn fin_n;
+  HostLayer stem, fin, head, fin_n;
   std::vector<ClsHostRes> res; // [depth][rb]
-  std::vector<ClsHostConv> down;
+  std::vector<HostLayer> down;
   std::vector<ClsHostAttn> attn;
 };
 
 int classifier_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, ClsHost &h) {
   if (!wf.has("classifier.enc.init.weight")) return fail(ctx, TTS_ERR_FORMAT, "'%s' is not a classifier model file", path);
-  size_t known = 0;
-  // PyTorch shape [d0][d1][d2] = container ne {d2, d1, d0}; d2 = 0: [d0][d1]; d1 = 0: a vector of d0
-  auto need = [&](const std::string &name, int64_t d0, int64_t d1, int64_t d2) -> const HostTensor * {
-    auto it = wf.t.find(name);
-    if (it == wf.t.end()) { fail(ctx, TTS_ERR_FORMAT, "tensor '%s' missing from classifier model file", name.c_str()); return nullptr; }
-    const HostTensor &t = it->second;
-    const int nd = d2 ? 3 : d1 ? 2 : 1;
-    const int64_t want[3] = {nd == 3 ? d2 : nd == 2 ? d1 : d0, nd == 3 ? d1 : nd == 2 ? d0 : 1, nd == 3 ? d0 : 1};
-    bool ok = t.n_dims == nd && (int64_t)t.data.size() == t.nelem();
-    for (int i = 0; i < nd && ok; i++) ok = t.ne[i] == want[i];
-    if (!ok) {
-      fail(ctx, TTS_ERR_FORMAT, "tensor '%s' has wrong shape in classifier model file: got [%d, %d, %d] (%d dims), expected [%d, %d, %d]", name.c_str(),
-           (int)t.ne[0], (int)t.ne[1], (int)t.ne[2], t.n_dims, (int)want[0], (int)want[1], (int)want[2]);
-      return nullptr;
-    }
-    known++;
-    return &t;
-  };
-  auto dims = [&](const std::string &name, int nd) -> const HostTensor * {
-    auto it = wf.t.find(name);
-    return it != wf.t.end() && it->second.n_dims == nd ? &it->second : nullptr;
-  };
+  ModelReader rd{wf, ctx, "classifier"};
   // the configuration: B0 from init.weight; enc.res.{i} is a ResBlock (in_layers / out_layers) or a Downsample (op); E from final.2.weight
   {
-    const HostTensor *t = dims("classifier.enc.init.weight", 3);
+    const HostTensor *t = rd.peek("classifier.enc.init.weight", 3);
     if (!t || !cls_pow2_channels((int)t->ne[2])) return fail(ctx, TTS_ERR_FORMAT, "tensor 'classifier.enc.init.weight' has wrong shape in classifier model file (base channels: a power of two, 32 .. 1024)");
     h.b0 = (int)t->ne[2];
   }
@@ -361,7 +345,7 @@ int classifier_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, ClsHo
       h.depth++;
     } else if (wf.has(p + ".in_layers.2.weight")) {
       if (n_res == 0) {
-        const HostTensor *t = dims(p + ".in_layers.2.weight", 3);
+        const HostTensor *t = rd.peek(p + ".in_layers.2.weight", 3);
         h.K = t ? (int)t->ne[0] : 0;
       }
       n_res++;
@@ -372,13 +356,13 @@ int classifier_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, ClsHo
   if (h.K < 1 || h.K > 11 || h.K % 2 == 0) return fail(ctx, TTS_ERR_FORMAT, "classifier model file: ResBlock kernel size %d (odd, 1 .. 11)", h.K);
   if (!cls_pow2_channels(h.b0 << h.depth)) return fail(ctx, TTS_ERR_FORMAT, "classifier model file: %d channels after %d levels (at most %d)", h.b0 << h.depth, h.depth, CLS_MAX_C);
   {
-    const HostTensor *t = dims("classifier.enc.final.2.weight", 3);
+    const HostTensor *t = rd.peek("classifier.enc.final.2.weight", 3);
     h.E = t ? (int)t->ne[2] : 0;
     if (h.E != 256 && h.E != 512 && h.E != 1024) return fail(ctx, TTS_ERR_FORMAT, "classifier model file: embedding dimension %d (256, 512 or 1024)", h.E);
   }
   while (wf.has("classifier.enc.attn." + std::to_string(h.n_attn) + ".norm.weight")) h.n_attn++;
   if (wf.has("classifier.config")) { // what the shapes cannot give: {downsample factor, attention heads}
-    const HostTensor *t = need("classifier.config", 2, 0, 0);
+    const HostTensor *t = rd.need("classifier.config", 2, 0, 0);
     if (!t) return TTS_ERR_FORMAT;
     h.F = (int)t->data[0]; h.H = (int)t->data[1];
     if ((float)h.F != t->data[0] || (float)h.H != t->data[1] || h.F < 2 || h.F > 6 || h.H < 1)
@@ -386,29 +370,8 @@ int classifier_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, ClsHo
   }
   if (h.E % h.H || (h.E / h.H != 64 && h.E / h.H != 128))
     return fail(ctx, TTS_ERR_FORMAT, "classifier model file: %d channels in %d heads: the head dimension must be 64 or 128", h.E, h.H);
-  // Conv1d [cout][cin][k] -> [k][cin][cout]
-  auto conv = [&](const std::string &p, int cout, int cin, int k, ClsHostConv &l) -> int {
-    const HostTensor *w, *b;
-    if (!(w = need(p + ".weight", cout, cin, k)) || !(b = need(p + ".bias", cout, 0, 0))) return TTS_ERR_FORMAT;
-    l.w.resize((size_t)k * cin * cout);
-    for (int co = 0; co < cout; co++)
-      for (int ci = 0; ci < cin; ci++)
-        for (int j = 0; j < k; j++) l.w[((size_t)j * cin + ci) * cout + co] = w->data[((size_t)co * cin + ci) * k + j];
-    l.b = b->data;
-    return TTS_OK;
-  };
-  auto norm = [&](const std::string &p, int c, ClsHostGn &g) -> int {
-    const HostTensor *w, *b;
-    if (!(w = need(p + ".weight", c, 0, 0)) || !(b = need(p + ".bias", c, 0, 0))) return TTS_ERR_FORMAT;
-    g.g = w->data; g.b = b->data;
-    return TTS_OK;
-  };
   int rc;
-  { // the stem keeps PyTorch's [B0][1][3]
-    const HostTensor *w, *b;
-    if (!(w = need("classifier.enc.init.weight", h.b0, 1, 3)) || !(b = need("classifier.enc.init.bias", h.b0, 0, 0))) return TTS_ERR_FORMAT;
-    h.stem.w = w->data; h.stem.b = b->data;
-  }
+  if ((rc = rd.raw("classifier.enc.init", h.b0, 1, 3, h.stem))) return rc; // the stem keeps PyTorch's [B0][1][3]
   h.res.resize((size_t)h.depth * h.rb);
   h.down.resize(h.depth);
   for (int l = 0, i = 0; l < h.depth; l++) {
@@ -416,61 +379,45 @@ int classifier_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, ClsHo
     for (int j = 0; j < h.rb; j++, i++) {
       const std::string p = "classifier.enc.res." + std::to_string(i);
       ClsHostRes &r = h.res[(size_t)l * h.rb + j];
-      if ((rc = norm(p + ".in_layers.0", C, r.n1)) || (rc = conv(p + ".in_layers.2", C, C, h.K, r.ca)) || (rc = norm(p + ".out_layers.0", C, r.n2)) ||
-          (rc = conv(p + ".out_layers.3", C, C, h.K, r.cb)))
+      if ((rc = rd.norm(p + ".in_layers.0", C, r.n1)) || (rc = rd.conv(p + ".in_layers.2", C, C, h.K, r.ca)) || (rc = rd.norm(p + ".out_layers.0", C, r.n2)) ||
+          (rc = rd.conv(p + ".out_layers.3", C, C, h.K, r.cb)))
         return rc;
     }
-    if ((rc = conv("classifier.enc.res." + std::to_string(i++) + ".op", 2 * C, C, 5, h.down[l]))) return rc;
+    if ((rc = rd.conv("classifier.enc.res." + std::to_string(i++) + ".op", 2 * C, C, 5, h.down[l]))) return rc;
   }
   const int Cf = h.b0 << h.depth;
-  if ((rc = norm("classifier.enc.final.0", Cf, h.fin_n)) || (rc = conv("classifier.enc.final.2", h.E, Cf, 1, h.fin))) return rc;
+  if ((rc = rd.norm("classifier.enc.final.0", Cf, h.fin_n)) || (rc = rd.conv("classifier.enc.final.2", h.E, Cf, 1, h.fin))) return rc;
   h.attn.resize(h.n_attn);
   const int E = h.E, dh = E / h.H;
   for (int i = 0; i < h.n_attn; i++) {
     const std::string p = "classifier.enc.attn." + std::to_string(i);
     ClsHostAttn &a = h.attn[i];
-    const HostTensor *qw, *qb, *pw, *pb;
-    if ((rc = norm(p + ".norm", E, a.n))) return rc;
-    if (!(qw = need(p + ".qkv.weight", 3 * E, E, 1)) || !(qb = need(p + ".qkv.bias", 3 * E, 0, 0)) || !(pw = need(p + ".proj_out.weight", E, E, 1)) ||
-        !(pb = need(p + ".proj_out.bias", E, 0, 0)))
-      return TTS_ERR_FORMAT;
-    // QKVAttentionLegacy: output channel = head * 3 dh + {q, k, v} * dh + d  ->  the q | k | v blocks cls_attn_kernel reads, head hd at columns hd * dh;
-    // both k = 1 convolutions [cout][cin][1] -> hfg_conv_kernel's [cin][cout]
+    HostLayer q; // both k = 1 convolutions [cout][cin][1] -> hfg_conv_kernel's [cin][cout]
+    if ((rc = rd.norm(p + ".norm", E, a.n)) || (rc = rd.conv(p + ".qkv", 3 * E, E, 1, q)) || (rc = rd.conv(p + ".proj_out", E, E, 1, a.proj))) return rc;
+    // QKVAttentionLegacy: output channel = head * 3 dh + {q, k, v} * dh + d  ->  the q | k | v blocks cls_attn_kernel reads, head hd at columns hd * dh
     a.qkv.w.resize((size_t)3 * E * E); a.qkv.b.resize((size_t)3 * E);
     for (int hd = 0; hd < h.H; hd++)
       for (int tq = 0; tq < 3; tq++)
         for (int d = 0; d < dh; d++) {
           const int o = hd * 3 * dh + tq * dh + d, n = tq * E + hd * dh + d;
-          a.qkv.b[n] = qb->data[o];
-          for (int ci = 0; ci < E; ci++) a.qkv.w[(size_t)ci * 3 * E + n] = qw->data[(size_t)o * E + ci];
+          a.qkv.b[n] = q.b[o];
+          for (int ci = 0; ci < E; ci++) a.qkv.w[(size_t)ci * 3 * E + n] = q.w[(size_t)ci * 3 * E + o];
         }
-    a.proj.w.resize((size_t)E * E);
-    for (int co = 0; co < E; co++)
-      for (int ci = 0; ci < E; ci++) a.proj.w[(size_t)ci * E + co] = pw->data[(size_t)co * E + ci];
-    a.proj.b = pb->data;
   }
-  {
-    const HostTensor *w, *b;
-    if (!(w = need("classifier.head.weight", 2, E, 0)) || !(b = need("classifier.head.bias", 2, 0, 0))) return TTS_ERR_FORMAT;
-    h.head.w = w->data; h.head.b = b->data;
-  }
-  if (wf.t.size() != known) return fail(ctx, TTS_ERR_FORMAT, "unknown tensors in classifier model file '%s' (%d tensors, %d expected)", path, (int)wf.t.size(), (int)known);
-  return TTS_OK;
+  if ((rc = rd.raw("classifier.head", 2, E, 0, h.head))) return rc;
+  return rd.finish(path);
 }
 
-struct ClsGn { float *g = nullptr, *b = nullptr; };
-struct ClsRes { ClsGn n1, n2; HfgLayer ca, cb; };
-struct ClsAttn { ClsGn n; HfgLayer qkv, proj; };
+struct ClsRes { HfgLayer n1, n2, ca, cb; };
+struct ClsAttn { HfgLayer n, qkv, proj; };
 struct ClassifierState {
   int b0 = 0, depth = 0, K = 0, E = 0, rb = 0, F = 4, H = 4;
-  HfgLayer stem, fin, head;
-  ClsGn fin_n;
+  HfgLayer stem, fin, head, fin_n;
   std::vector<ClsRes> res;
   std::vector<HfgLayer> down;
   std::vector<ClsAttn> attn;
-  std::vector<void *> owned;
+  DevWeights dev;
   DevBuf in, wav, h, a, t, part, stat, x, y, qkv, att, out;
-  ~ClassifierState() { for (void *p : owned) (void)hipFree(p); }
 };
 void classifier_free(ClassifierState *s) { delete s; }
 
@@ -487,26 +434,17 @@ int classifier_load(tts_ctx *ctx, const char *path) {
   (void)hipSetDevice(ctx->device);
   std::unique_ptr<ClassifierState> st(new ClassifierState());
   st->b0 = h->b0; st->depth = h->depth; st->K = h->K; st->E = h->E; st->rb = h->rb; st->F = h->F; st->H = h->H;
-  auto up = [&](const std::vector<float> &src, float **dst) -> int {
-    void *p = nullptr;
-    TTS_HIP(ctx, hipMalloc(&p, src.size() * 4));
-    st->owned.push_back(p);
-    TTS_HIP(ctx, hipMemcpy(p, src.data(), src.size() * 4, hipMemcpyHostToDevice));
-    *dst = (float *)p;
-    return TTS_OK;
-  };
-  auto layer = [&](const ClsHostConv &s, HfgLayer &d) -> int { int e = up(s.w, &d.w); return e ? e : up(s.b, &d.b); };
-  auto gn = [&](const ClsHostGn &s, ClsGn &d) -> int { int e = up(s.g, &d.g); return e ? e : up(s.b, &d.b); };
-  if ((rc = layer(h->stem, st->stem)) || (rc = layer(h->fin, st->fin)) || (rc = layer(h->head, st->head)) || (rc = gn(h->fin_n, st->fin_n))) return rc;
+  auto up = [&](const HostLayer &s, HfgLayer &d) { return st->dev.up(ctx, s, d); };
+  if ((rc = up(h->stem, st->stem)) || (rc = up(h->fin, st->fin)) || (rc = up(h->head, st->head)) || (rc = up(h->fin_n, st->fin_n))) return rc;
   st->res.resize(h->res.size()); st->down.resize(h->down.size()); st->attn.resize(h->attn.size());
   for (size_t i = 0; i < h->res.size(); i++)
-    if ((rc = gn(h->res[i].n1, st->res[i].n1)) || (rc = gn(h->res[i].n2, st->res[i].n2)) || (rc = layer(h->res[i].ca, st->res[i].ca)) ||
-        (rc = layer(h->res[i].cb, st->res[i].cb)))
+    if ((rc = up(h->res[i].n1, st->res[i].n1)) || (rc = up(h->res[i].n2, st->res[i].n2)) || (rc = up(h->res[i].ca, st->res[i].ca)) ||
+        (rc = up(h->res[i].cb, st->res[i].cb)))
       return rc;
   for (size_t i = 0; i < h->down.size(); i++)
-    if ((rc = layer(h->down[i], st->down[i]))) return rc;
+    if ((rc = up(h->down[i], st->down[i]))) return rc;
   for (size_t i = 0; i < h->attn.size(); i++)
-    if ((rc = gn(h->attn[i].n, st->attn[i].n)) || (rc = layer(h->attn[i].qkv, st->attn[i].qkv)) || (rc = layer(h->attn[i].proj, st->attn[i].proj))) return rc;
+    if ((rc = up(h->attn[i].n, st->attn[i].n)) || (rc = up(h->attn[i].qkv, st->attn[i].qkv)) || (rc = up(h->attn[i].proj, st->attn[i].proj))) return rc;
   if (ctx->classifier) classifier_free(ctx->classifier);
   ctx->classifier = st.release();
   return TTS_OK;
@@ -521,49 +459,21 @@ int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, c
   if (!audio || !n_samples || !rates || !prob_out || !resample || B < 1) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", fn);
   if (B > CLS_MAX_CLIPS) return fail(ctx, TTS_ERR_LIMIT, "%s: %d clips (at most %d per call)", fn, B, CLS_MAX_CLIPS);
   const int depth = st->depth, F = st->F, L = depth + 1;
-  std::vector<ClsResampleClip> rs;
-  std::vector<int64_t> src_off(B), n24(B);
-  int64_t total_src = 0, total24 = 0;
-  for (int s = 0; s < B; s++) {
-    const int64_t n = n_samples[s];
-    if (n < 1) return fail(ctx, TTS_ERR_ARG, "%s: clip %d: %lld samples", fn, s, (long long)n);
-    if (n > (1 << 26)) return fail(ctx, TTS_ERR_LIMIT, "%s: clip %d: %lld samples, at most 2^26", fn, s, (long long)n);
-    AfeResampleGeom g;
-    if (rates[s] < 1 || afe_resample_geometry(rates[s], 24000, &g) != TTS_OK)
-      return fail(ctx, TTS_ERR_ARG, "%s: clip %d: sample rate %d is outside the audio front end's range", fn, s, rates[s]);
-    src_off[s] = total_src;
-    n24[s] = std::min<int64_t>(rates[s] == 24000 ? n : afe_resample_len(g, n), TTS_CLS_MAX_SAMPLES); // the crop: only these are ever computed
-    if (rates[s] != 24000) rs.push_back(ClsResampleClip{total_src, n, total24, n24[s], rates[s]});
-    total_src += n; total24 += (n24[s] + 7) / 8 * 8;
-  }
-  for (int64_t i = 0; i < total_src; i++)
-    if (!std::isfinite(audio[i])) return fail(ctx, TTS_ERR_ARG, "%s: the audio holds a non-finite sample (element %lld)", fn, (long long)i);
-  // the tables: level l's HFG_SEQ records {first row, rows, 0, first GroupNorm tile, first sample at 24 kHz}
-  std::vector<int> tab((size_t)L * B * HFG_SEQ, 0);
-  std::vector<int64_t> rows(L, 0), tiles(L, 0);
-  std::vector<int> max_n(L, 0);
-  for (int s = 0, o24 = 0; s < B; s++) {
-    int n = (int)n24[s];
-    for (int l = 0; l < L; l++) {
-      int *q = &tab[((size_t)l * B + s) * HFG_SEQ];
-      q[0] = (int)rows[l]; q[1] = n; q[3] = (int)tiles[l]; q[4] = o24;
-      rows[l] += (n + 7) / 8 * 8; tiles[l] += (n + CLS_GN_TILE - 1) / CLS_GN_TILE; max_n[l] = std::max(max_n[l], n);
-      if (l < depth) n = (n - 1) / F + 1;
-    }
-    o24 += (int)((n24[s] + 7) / 8 * 8);
-  }
+  ClipIngest clips; // the crop: only TTS_CLS_MAX_SAMPLES of a clip are ever computed
+  int rc = clip_ingest(ctx, fn, audio, n_samples, rates, B, 24000, TTS_CLS_MAX_SAMPLES, clips, [](int, int64_t) { return TTS_OK; });
+  if (rc) return rc;
+  const LevelTable lt = cls_levels(clips.n_dst.data(), B, depth, F);
+  const std::vector<int64_t> &rows = lt.rows;
+  const std::vector<int> &max_n = lt.max_n;
   const int E = st->E;
-  std::vector<float> up((size_t)total_src + tab.size());
-  memcpy(up.data(), audio, (size_t)total_src * 4);
-  memcpy(up.data() + total_src, tab.data(), tab.size() * 4);
   size_t act = 0; // floats of the widest level: level 0 unless the clips are a few samples long
   for (int l = 0; l < L; l++) act = std::max(act, (size_t)rows[l] * (st->b0 << l));
-  TTS_HIP(ctx, st->in.reserve(up.size() * 4));
-  TTS_HIP(ctx, st->wav.reserve((size_t)total24 * 4));
+  TTS_HIP(ctx, st->in.reserve(clip_upload_floats(clips, lt) * 4));
+  TTS_HIP(ctx, st->wav.reserve((size_t)clips.total_dst * 4));
   TTS_HIP(ctx, st->h.reserve(act * 4));
   TTS_HIP(ctx, st->a.reserve(act * 4));
   TTS_HIP(ctx, st->t.reserve(act * 4));
-  TTS_HIP(ctx, st->part.reserve((size_t)tiles[0] * 32 * sizeof(double2)));
+  TTS_HIP(ctx, st->part.reserve((size_t)lt.tiles[0] * 32 * sizeof(double2)));
   TTS_HIP(ctx, st->stat.reserve((size_t)B * 32 * sizeof(double2)));
   TTS_HIP(ctx, st->x.reserve((size_t)rows[depth] * E * 4));
   TTS_HIP(ctx, st->y.reserve((size_t)rows[depth] * E * 4));
@@ -571,24 +481,15 @@ int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, c
   TTS_HIP(ctx, st->att.reserve((size_t)rows[depth] * E * 4));
   TTS_HIP(ctx, st->out.reserve((size_t)B * 3 * 4));
   hipStream_t sm = ctx->stream;
-  TTS_HIP(ctx, hipMemcpyAsync(st->in.p, up.data(), up.size() * 4, hipMemcpyHostToDevice, sm));
-  const float *d_src = st->in.as<float>();
-  const int *d_tab = (const int *)(d_src + total_src);
-  auto seq = [&](int l) { return d_tab + (size_t)l * B * HFG_SEQ; };
   float *wav = st->wav.as<float>();
-  // a clip at 24 kHz reaches the network bit for bit; the others through the audio front end's resampler, one stage, cropped
-  for (int s = 0; s < B; s++)
-    if (rates[s] == 24000)
-      TTS_HIP(ctx, hipMemcpyAsync(wav + tab[(size_t)s * HFG_SEQ + 4], d_src + src_off[s], (size_t)n24[s] * 4, hipMemcpyDeviceToDevice, sm));
-  if (!rs.empty()) {
-    const int rc = resample(ctx, d_src, wav, rs.data(), (int)rs.size());
-    if (rc) return rc;
-  }
+  const int *d_tab = nullptr;
+  if ((rc = clip_upload(ctx, clips, lt, audio, rates, 24000, st->in, wav, resample, &d_tab))) return rc;
+  auto seq = [&](int l) { return d_tab + (size_t)l * B * HFG_SEQ; };
   float *h = st->h.as<float>(), *av = st->a.as<float>(), *t = st->t.as<float>();
   double2 *part = st->part.as<double2>(), *stat = st->stat.as<double2>();
-  auto gn = [&](const float *x, const ClsGn &p, int l, int C) {
+  auto gn = [&](const float *x, const HfgLayer &p, int l, int C) {
     ProfScope ps(ctx, "cls_gn", (double)rows[l] * C * 4 * 3);
-    cls_launch_gn_silu(x, av, p.g, p.b, seq(l), C, max_n[l], B, part, stat, sm);
+    cls_launch_gn_silu(x, av, p.w, p.b, seq(l), C, max_n[l], B, part, stat, sm);
   };
   auto conv = [&](const float *in, float *out, const float *resid, const HfgLayer &w, int l, int cin, int cout, int taps) {
     ProfScope ps(ctx, "cls_conv", 2.0 * (double)rows[l] * taps * cin * cout);
@@ -622,7 +523,7 @@ int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, c
   conv(av, x, nullptr, st->fin, depth, Cf, E, 1);
   for (const ClsAttn &b : st->attn) { // one profiler entry per block: GroupNorm, the two projections and the attention between them
     ProfScope ps(ctx, "cls_attn", 2.0 * (double)rows[depth] * E * (4.0 * E + 2.0 * max_n[depth]));
-    cls_launch_gn_silu(x, y, b.n.g, b.n.b, seq(depth), E, max_n[depth], B, part, stat, sm, 0);
+    cls_launch_gn_silu(x, y, b.n.w, b.n.b, seq(depth), E, max_n[depth], B, part, stat, sm, 0);
     cls_launch_conv(y, qkv, nullptr, b.qkv.w, b.qkv.b, seq(depth), E, 3 * E, 1, max_n[depth], B, sm);
     cls_launch_attn(qkv, att, seq(depth), E, st->H, max_n[depth], B, sm);
     cls_launch_conv(att, x, x, b.proj.w, b.proj.b, seq(depth), E, E, 1, max_n[depth], B, sm);

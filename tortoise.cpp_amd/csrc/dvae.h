@@ -1,6 +1,6 @@
 // The DVAE encoder on MI355X (gfx950): an 80-band mel -> the 8192-entry speech codes the AR model is trained on      tts_load_dvae / tts_dvae_codes / tts_dvae_codes_audio
 //
-// Included once, as the last line of aligner.h (hifigan.hip's translation unit): get_codebook_indices of upstream tortoise-tts' DiscreteVAE(channels 80,
+// Included once, as the last line of aligner.h (hifigan.hip's translation unit; its loader and level tables are model_io.h's): get_codebook_indices of upstream tortoise-tts' DiscreteVAE(channels 80,
 // positional_dims 1, num_tokens 8192, codebook_dim 512, hidden_dim 512, num_layers 2, num_resnet_blocks 3, kernel_size 3, no normalization). Upstream's source and
 // weights are not available offline: the contract is the arithmetic below ("What pins the DVAE"), checked between two float64 spellings
 // (tests/dvae_ref.py); unpinned against upstream. f32 throughout: a code is an argmin.
@@ -245,10 +245,16 @@ void dvae_code_norms(const float *E, int D, int N, float *e2) {
 }
 inline int dvae_conv_rows(int n, int stride) { return (n - 1) / stride + 1; } // odd k, pad (k - 1) / 2
 bool dvae_channels_ok(int c) { return c >= 64 && c <= DVAE_MAX_C && c % 64 == 0; }
+// The tables of dvae_begin (and of the test harness): level 0 = the mel frames, level i the output of strided layer i - 1; the clips packed without gaps;
+// level 0 carries the first float of the clip's band-major mel [cin][frames]
+template <class T>
+LevelTable dvae_levels(const T *frames, int B, int L, int stride, int cin) {
+  return level_table(frames, B, L + 1, [stride](int64_t v, int) { return dvae_conv_rows((int)v, stride); }, 1, 0, false, cin);
+}
 } // namespace
 
 // The model as the loader's host half leaves it (no device call): the configuration from the tensor names and shapes, every tensor repacked for the kernels.
-struct DvaeHostConv { std::vector<float> w, b; int cin = 0, cout = 0, k = 0; }; // w: [tap][cin][cout]
+struct DvaeHostConv : HostLayer { int cin = 0, cout = 0, k = 0; }; // w: [tap][cin][cout]
 struct DvaeHost {
   int L = 0, blocks = 0, cin = 0, H = 0, dim = 0, N = 0, stride = 2;
   std::vector<DvaeHostConv> down;              // the strided layers; down[0] is the stem
@@ -260,29 +266,22 @@ struct DvaeHost {
 int dvae_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, DvaeHost &h) {
   const std::string P = "dvae.", EN = P + "encoder.";
   if (!wf.has(EN + "0.0.weight")) return fail(ctx, TTS_ERR_FORMAT, "'%s' is not a DVAE model file", path);
-  size_t known = 0;
-  // Conv1d [cout][cin][k] = container ne {k, cin, cout} -> [k][cin][cout]; the sizes are the tensor's own
+  ModelReader rd{wf, ctx, "DVAE"};
+  // Conv1d [cout][cin][k] -> [k][cin][cout]; the sizes are the tensor's own, checked here in the DVAE's words; rd.conv reports a tensor that is missing
   auto conv = [&](const std::string &p, int want_cin, DvaeHostConv &c) -> int {
-    auto iw = wf.t.find(p + ".weight"), ib = wf.t.find(p + ".bias");
-    if (iw == wf.t.end() || ib == wf.t.end()) return fail(ctx, TTS_ERR_FORMAT, "tensor '%s.%s' missing from DVAE model file", p.c_str(), iw == wf.t.end() ? "weight" : "bias");
-    const HostTensor &w = iw->second, &b = ib->second;
-    if (w.n_dims != 3 || (int64_t)w.data.size() != w.nelem() || w.ne[0] < 1 || w.ne[1] < 1 || w.ne[2] < 1 || w.ne[0] > DVAE_MAX_K || w.ne[1] > DVAE_MAX_C ||
-        w.ne[2] > DVAE_MAX_C)
-      return fail(ctx, TTS_ERR_FORMAT, "tensor '%s.weight' has wrong shape in DVAE model file: got [%d, %d, %d] (%d dims), expected [cout][cin][k <= %d]", p.c_str(),
-                  (int)w.ne[0], (int)w.ne[1], (int)w.ne[2], w.n_dims, DVAE_MAX_K);
-    c.k = (int)w.ne[0]; c.cin = (int)w.ne[1]; c.cout = (int)w.ne[2];
-    if (c.k % 2 == 0) return fail(ctx, TTS_ERR_FORMAT, "DVAE model file: '%s.weight' has %d taps (an odd kernel size, padding (k - 1) / 2)", p.c_str(), c.k);
-    if (want_cin && c.cin != want_cin)
-      return fail(ctx, TTS_ERR_FORMAT, "tensor '%s.weight' has wrong shape in DVAE model file: %d input channels, the layer before it writes %d", p.c_str(), c.cin, want_cin);
-    if (b.n_dims != 1 || b.ne[0] != c.cout || (int64_t)b.data.size() != b.nelem())
-      return fail(ctx, TTS_ERR_FORMAT, "tensor '%s.bias' has wrong shape in DVAE model file: got %d values, expected %d", p.c_str(), (int)b.ne[0], c.cout);
-    c.w.resize((size_t)c.k * c.cin * c.cout);
-    for (int co = 0; co < c.cout; co++)
-      for (int ci = 0; ci < c.cin; ci++)
-        for (int j = 0; j < c.k; j++) c.w[((size_t)j * c.cin + ci) * c.cout + co] = w.data[((size_t)co * c.cin + ci) * c.k + j];
-    c.b = b.data;
-    known += 2;
-    return TTS_OK;
+    if (const HostTensor *w = rd.peek(p + ".weight")) {
+      if (w->n_dims != 3 || w->ne[0] < 1 || w->ne[1] < 1 || w->ne[2] < 1 || w->ne[0] > DVAE_MAX_K || w->ne[1] > DVAE_MAX_C || w->ne[2] > DVAE_MAX_C)
+        return fail(ctx, TTS_ERR_FORMAT, "tensor '%s.weight' has wrong shape in DVAE model file: got [%d, %d, %d] (%d dims), expected [cout][cin][k <= %d]", p.c_str(),
+                    (int)w->ne[0], (int)w->ne[1], (int)w->ne[2], w->n_dims, DVAE_MAX_K);
+      c.k = (int)w->ne[0]; c.cin = (int)w->ne[1]; c.cout = (int)w->ne[2];
+      if (c.k % 2 == 0) return fail(ctx, TTS_ERR_FORMAT, "DVAE model file: '%s.weight' has %d taps (an odd kernel size, padding (k - 1) / 2)", p.c_str(), c.k);
+      if (want_cin && c.cin != want_cin)
+        return fail(ctx, TTS_ERR_FORMAT, "tensor '%s.weight' has wrong shape in DVAE model file: %d input channels, the layer before it writes %d", p.c_str(), c.cin, want_cin);
+      const HostTensor *b = rd.peek(p + ".bias", 1);
+      if (b && b->ne[0] != c.cout)
+        return fail(ctx, TTS_ERR_FORMAT, "tensor '%s.bias' has wrong shape in DVAE model file: got %d values, expected %d", p.c_str(), (int)b->ne[0], c.cout);
+    }
+    return rd.conv(p, c.cout, c.cin, c.k, c);
   };
   while (wf.has(EN + std::to_string(h.L) + ".0.weight")) h.L++;
   if (h.L > DVAE_MAX_LAYERS) return fail(ctx, TTS_ERR_FORMAT, "DVAE model file: %d strided layers (at most %d)", h.L, DVAE_MAX_LAYERS);
@@ -314,9 +313,8 @@ int dvae_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, DvaeHost &h
     return fail(ctx, TTS_ERR_FORMAT, "DVAE model file: the last convolution has %d taps and %d output channels (k 1; the codebook dim a multiple of 32, 32 .. %d)",
                 h.head.k, h.dim, DVAE_MAX_DIM);
   {
-    auto it = wf.t.find(P + "codebook.embed");
-    if (it == wf.t.end()) return fail(ctx, TTS_ERR_FORMAT, "tensor 'dvae.codebook.embed' missing from DVAE model file");
-    const HostTensor &t = it->second;
+    if (!rd.has(P + "codebook.embed")) return fail(ctx, TTS_ERR_FORMAT, "tensor 'dvae.codebook.embed' missing from DVAE model file");
+    const HostTensor &t = *rd.peek(P + "codebook.embed");
     if (t.n_dims != 2 || t.ne[1] != h.dim || (int64_t)t.data.size() != t.nelem())
       return fail(ctx, TTS_ERR_FORMAT, "tensor 'dvae.codebook.embed' has wrong shape in DVAE model file: got [%d, %d] (%d dims), expected [%d][tokens]", (int)t.ne[1],
                   (int)t.ne[0], t.n_dims, h.dim);
@@ -328,34 +326,28 @@ int dvae_parse(tts_ctx *ctx, const WeightFile &wf, const char *path, DvaeHost &h
     h.E = t.data;
     h.e2.resize((size_t)h.N);
     dvae_code_norms(h.E.data(), h.dim, h.N, h.e2.data());
-    known++;
+    rd.known++;
   }
-  if (wf.has(P + "config")) { // what no shape holds: {stride}, an integer
-    const HostTensor &t = wf.t.find(P + "config")->second;
-    if (t.n_dims != 1 || t.ne[0] != 1 || t.data.size() != 1 || t.data[0] != (float)(int)t.data[0])
+  if (const HostTensor *t = rd.peek(P + "config")) { // what no shape holds: {stride}, an integer
+    if (t->n_dims != 1 || t->ne[0] != 1 || t->data.size() != 1 || t->data[0] != (float)(int)t->data[0])
       return fail(ctx, TTS_ERR_FORMAT, "tensor 'dvae.config' has wrong shape in DVAE model file: {stride}, one integer");
-    h.stride = (int)t.data[0];
-    known++;
+    h.stride = (int)t->data[0];
+    rd.known++;
   }
   if (h.stride < 1 || h.stride > DVAE_MAX_STRIDE) return fail(ctx, TTS_ERR_FORMAT, "DVAE model file: stride %d (1 .. %d)", h.stride, DVAE_MAX_STRIDE);
-  if (wf.t.size() != known) return fail(ctx, TTS_ERR_FORMAT, "unknown tensors in DVAE model file '%s' (%d tensors, %d expected)", path, (int)wf.t.size(), (int)known);
-  return TTS_OK;
+  return rd.finish(path);
 }
 
-struct DvaeConv { float *w = nullptr, *b = nullptr; int cin = 0, cout = 0, k = 0; };
+struct DvaeConv : HfgLayer { int cin = 0, cout = 0, k = 0; };
 struct DvaeState {
   int L = 0, blocks = 0, cin = 0, H = 0, dim = 0, N = 0, stride = 2;
   std::vector<DvaeConv> down;
   std::vector<std::array<DvaeConv, 3>> res;
   DvaeConv head;
   float *E = nullptr, *e2 = nullptr;
-  std::vector<void *> owned;
+  DevWeights dev;
   DevBuf mel, tab, a, b, h, z, pv, pi, codes;
-  // the layout dvae_begin made, for dvae_run
-  std::vector<int> tab_h, rows_of, max_n;
-  std::vector<int64_t> total;
-  int n_clips = 0;
-  ~DvaeState() { for (void *p : owned) (void)hipFree(p); }
+  LevelTable lt; // the layout dvae_begin made, for dvae_run (and the source of its asynchronous upload)
 };
 void dvae_free(DvaeState *s) { delete s; }
 
@@ -372,18 +364,9 @@ int dvae_load(tts_ctx *ctx, const char *path) {
   (void)hipSetDevice(ctx->device);
   std::unique_ptr<DvaeState> st(new DvaeState());
   st->L = h->L; st->blocks = h->blocks; st->cin = h->cin; st->H = h->H; st->dim = h->dim; st->N = h->N; st->stride = h->stride;
-  auto up = [&](const std::vector<float> &src, float **dst) -> int {
-    void *p = nullptr;
-    TTS_HIP(ctx, hipMalloc(&p, src.size() * 4));
-    st->owned.push_back(p);
-    TTS_HIP(ctx, hipMemcpy(p, src.data(), src.size() * 4, hipMemcpyHostToDevice));
-    *dst = (float *)p;
-    return TTS_OK;
-  };
   auto layer = [&](const DvaeHostConv &s, DvaeConv &d) -> int {
     d.cin = s.cin; d.cout = s.cout; d.k = s.k;
-    int e = up(s.w, &d.w);
-    return e ? e : up(s.b, &d.b);
+    return st->dev.up(ctx, s, d);
   };
   st->down.resize(h->L); st->res.resize(h->blocks);
   for (int i = 0; i < h->L; i++)
@@ -391,7 +374,7 @@ int dvae_load(tts_ctx *ctx, const char *path) {
   for (int j = 0; j < h->blocks; j++)
     for (int q = 0; q < 3; q++)
       if ((rc = layer(h->res[j][q], st->res[j][q]))) return rc;
-  if ((rc = layer(h->head, st->head)) || (rc = up(h->E, &st->E)) || (rc = up(h->e2, &st->e2))) return rc;
+  if ((rc = layer(h->head, st->head)) || (rc = st->dev.up(ctx, h->E, &st->E)) || (rc = st->dev.up(ctx, h->e2, &st->e2))) return rc;
   if (ctx->dvae) dvae_free(ctx->dvae);
   ctx->dvae = st.release();
   return TTS_OK;
@@ -408,7 +391,7 @@ int dvae_begin(tts_ctx *ctx, const char *fn, const int32_t *frames, int n_clips,
   if (!st) return fail(ctx, TTS_ERR_STATE, "tts_load_dvae not called");
   if (!frames || n_clips < 1 || code_stride < 1 || !d_mel) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", fn);
   if (n_clips > DVAE_MAX_CLIPS) return fail(ctx, TTS_ERR_LIMIT, "%s: %d clips (at most %d per call)", fn, n_clips, DVAE_MAX_CLIPS);
-  const int B = n_clips, L = st->L, NL = L + 1;
+  const int B = n_clips, L = st->L;
   for (int s = 0; s < B; s++) {
     if (frames[s] < 1) return fail(ctx, TTS_ERR_ARG, "%s: clip %d: %d mel frames (at least 1 expected)", fn, s, frames[s]);
     if (frames[s] > DVAE_MAX_FRAMES) return fail(ctx, TTS_ERR_LIMIT, "%s: clip %d: %d mel frames, at most %d", fn, s, frames[s], DVAE_MAX_FRAMES);
@@ -416,27 +399,14 @@ int dvae_begin(tts_ctx *ctx, const char *fn, const int32_t *frames, int n_clips,
     for (int l = 0; l < L; l++) n = dvae_conv_rows(n, st->stride);
     if (n > code_stride) return fail(ctx, TTS_ERR_ARG, "%s: clip %d has %d codes, code_stride is %d", fn, s, n, code_stride);
   }
-  // the tables: level l's HFG_SEQ records {first row, rows, 0, 0, first float of the clip's mel (level 0)}
-  std::vector<int> tab((size_t)NL * B * HFG_SEQ, 0), rows_of(B), max_n(NL, 0);
-  std::vector<int64_t> total(NL, 0);
-  int64_t moff = 0;
-  for (int s = 0; s < B; s++) {
-    int n = frames[s];
-    for (int l = 0; l < NL; l++) {
-      int *q = &tab[((size_t)l * B + s) * HFG_SEQ];
-      q[0] = (int)total[l]; q[1] = n;
-      if (l == 0) { q[4] = (int)moff; moff += (int64_t)st->cin * n; }
-      total[l] += n; max_n[l] = std::max(max_n[l], n);
-      if (l < L) n = dvae_conv_rows(n, st->stride);
-      else rows_of[s] = n;
-    }
-  }
-  const int64_t R = total[L];
+  LevelTable lt = dvae_levels(frames, B, L, st->stride, st->cin);
+  const std::vector<int64_t> &total = lt.rows;
+  const int64_t R = total[L], moff = (int64_t)st->cin * total[0];
   size_t act = (size_t)R * st->H; // a and b: the strided layers before the last write them in turn, then the ResBlocks' two intermediate tensors
   for (int i = 0; i + 1 < L; i++) act = std::max(act, (size_t)total[i + 1] * st->down[i].cout);
   const int slabs = dvae_vq_slabs(st->N);
   TTS_HIP(ctx, st->mel.reserve((size_t)moff * 4));
-  TTS_HIP(ctx, st->tab.reserve(tab.size() * 4));
+  TTS_HIP(ctx, st->tab.reserve(lt.tab.size() * 4));
   TTS_HIP(ctx, st->a.reserve(act * 4));
   TTS_HIP(ctx, st->b.reserve(act * 4));
   TTS_HIP(ctx, st->h.reserve((size_t)R * st->H * 4));
@@ -444,8 +414,8 @@ int dvae_begin(tts_ctx *ctx, const char *fn, const int32_t *frames, int n_clips,
   TTS_HIP(ctx, st->pv.reserve((size_t)slabs * R * 4));
   TTS_HIP(ctx, st->pi.reserve((size_t)slabs * R * 4));
   TTS_HIP(ctx, st->codes.reserve((size_t)R * 4));
-  st->tab_h.swap(tab); st->rows_of.swap(rows_of); st->max_n.swap(max_n); st->total.swap(total); st->n_clips = B; // outlive this call: the copy is asynchronous
-  TTS_HIP(ctx, hipMemcpyAsync(st->tab.p, st->tab_h.data(), st->tab_h.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  st->lt = std::move(lt); // outlives this call: the copy is asynchronous
+  TTS_HIP(ctx, hipMemcpyAsync(st->tab.p, st->lt.tab.data(), st->lt.tab.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   *d_mel = st->mel.as<float>();
   return TTS_OK;
 }
@@ -453,9 +423,9 @@ int dvae_begin(tts_ctx *ctx, const char *fn, const int32_t *frames, int n_clips,
 // codes_out [B][code_stride], z_out null or [B][code_stride][dim]: the first n_codes_out[s] entries of a clip are written, the rest is left alone.
 int dvae_run(tts_ctx *ctx, int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out) {
   DvaeState *st = ctx->dvae;
-  const int B = st->n_clips, L = st->L, D = st->dim;
-  const std::vector<int> &max_n = st->max_n;
-  const std::vector<int64_t> &total = st->total;
+  const int B = st->lt.B, L = st->L, D = st->dim;
+  const std::vector<int> &max_n = st->lt.max_n;
+  const std::vector<int64_t> &total = st->lt.rows;
   const int64_t R = total[L];
   hipStream_t sm = ctx->stream;
   const int *d_tab = st->tab.as<int>();
@@ -502,8 +472,8 @@ int dvae_run(tts_ctx *ctx, int32_t *codes_out, int32_t *n_codes_out, int code_st
   if (z_out) TTS_HIP(ctx, hipMemcpyAsync(zh.data(), z, zh.size() * 4, hipMemcpyDeviceToHost, sm));
   TTS_HIP(ctx, hipStreamSynchronize(sm));
   for (int s = 0; s < B; s++) {
-    const size_t f0 = (size_t)st->tab_h[((size_t)L * B + s) * HFG_SEQ];
-    const int n = st->rows_of[s];
+    const size_t f0 = (size_t)st->lt.rec(L, s)[0];
+    const int n = st->lt.rec(L, s)[1];
     n_codes_out[s] = n;
     memcpy(codes_out + (size_t)s * code_stride, &codes[f0], (size_t)n * 4);
     if (z_out) memcpy(z_out + (size_t)s * code_stride * D, &zh[f0 * D], (size_t)n * D * 4);

@@ -271,25 +271,18 @@ __global__ __launch_bounds__(256) void hfg_post_kernel(const float *__restrict__
   audio[(size_t)before * 256 + j] = tanhf(sum);
 }
 } // namespace
+} // namespace tts
+#include "model_io.h" // ModelReader, DevWeights, the level tables and the clip ingest of every model of this translation unit
+namespace tts {
 
-struct HfgLayer { float *w = nullptr, *b = nullptr; };
 struct HifiganState {
   HfgLayer pre, cond, post, ups[HFG_STAGES], c1[HFG_STAGES][3][3], c2[HFG_STAGES][3][3];
-  std::vector<void *> owned;
+  DevWeights dev;
   DevBuf in, z, cb, x, u, t, m, audio;
-  ~HifiganState() { for (void *p : owned) (void)hipFree(p); }
 };
 void hifigan_free(HifiganState *s) { delete s; }
 
-static int hfg_up(tts_ctx *ctx, HifiganState *st, const std::vector<float> &src, float **dst) {
-  void *p = nullptr;
-  TTS_HIP(ctx, hipMalloc(&p, src.size() * 4));
-  st->owned.push_back(p);
-  TTS_HIP(ctx, hipMemcpy(p, src.data(), src.size() * 4, hipMemcpyHostToDevice));
-  *dst = (float *)p;
-  return TTS_OK;
-}
-
+// Every tensor is uploaded as it is parsed: a broken file reports whichever fails first, the tensor or an upload before it.
 int hifigan_load(tts_ctx *ctx, const char *path) {
   WeightFile wf;
   std::string err;
@@ -297,44 +290,21 @@ int hifigan_load(tts_ctx *ctx, const char *path) {
   if (rc != TTS_OK) return fail(ctx, rc, "hifigan_load: %s", err.c_str());
   if (!wf.has("hifigan.conv_pre.weight")) return fail(ctx, TTS_ERR_FORMAT, "'%s' is not a HiFi-GAN model file", path);
   std::unique_ptr<HifiganState> st(new HifiganState());
-  size_t known = 0;
-  // PyTorch shape [d0][d1][d2] (d2 = 0: a vector of d0) = container ne {d2, d1, d0}
-  auto need = [&](const std::string &name, int64_t d0, int64_t d1, int64_t d2) -> const HostTensor * {
-    auto it = wf.t.find(name);
-    if (it == wf.t.end()) { fail(ctx, TTS_ERR_FORMAT, "tensor '%s' missing from HiFi-GAN model file", name.c_str()); return nullptr; }
-    const HostTensor &t = it->second;
-    const bool ok = d2 ? (t.n_dims == 3 && t.ne[0] == d2 && t.ne[1] == d1 && t.ne[2] == d0) : (t.n_dims == 1 && t.ne[0] == d0);
-    if (!ok || t.nelem() != (d2 ? d0 * d1 * d2 : d0) || (int64_t)t.data.size() != t.nelem()) {
-      fail(ctx, TTS_ERR_FORMAT, "tensor '%s' has wrong shape in HiFi-GAN model file: got [%d, %d, %d] (%d dims), expected [%d, %d, %d]", name.c_str(),
-           (int)t.ne[0], (int)t.ne[1], (int)t.ne[2], t.n_dims, (int)(d2 ? d2 : d0), (int)(d2 ? d1 : 1), (int)(d2 ? d0 : 1));
-      return nullptr;
-    }
-    known++;
-    return &t;
-  };
-  // Conv1d [cout][cin][k] -> [k][cin][cout]
+  ModelReader rd{wf, ctx, "HiFi-GAN"};
+  HostLayer h;
   auto conv = [&](const std::string &p, int cout, int cin, int k, HfgLayer &l) -> int {
-    const HostTensor *w, *b;
-    if (!(w = need(p + ".weight", cout, cin, k)) || !(b = need(p + ".bias", cout, 0, 0))) return TTS_ERR_FORMAT;
-    std::vector<float> r((size_t)k * cin * cout);
-    for (int co = 0; co < cout; co++)
-      for (int ci = 0; ci < cin; ci++)
-        for (int j = 0; j < k; j++) r[((size_t)j * cin + ci) * cout + co] = w->data[((size_t)co * cin + ci) * k + j];
-    int e = hfg_up(ctx, st.get(), r, &l.w);
-    return e ? e : hfg_up(ctx, st.get(), b->data, &l.b);
+    const int e = rd.conv(p, cout, cin, k, h);
+    return e ? e : st->dev.up(ctx, h, l);
   };
   if ((rc = conv("hifigan.conv_pre", HFG_C0, HFG_LAT, 7, st->pre))) return rc;
-  { // cond_layer stays [cout][cin]: a matrix-vector product per voice
-    const HostTensor *w, *b;
-    if (!(w = need("hifigan.cond_layer.weight", HFG_C0, HFG_LAT, 1)) || !(b = need("hifigan.cond_layer.bias", HFG_C0, 0, 0))) return TTS_ERR_FORMAT;
-    if ((rc = hfg_up(ctx, st.get(), w->data, &st->cond.w)) || (rc = hfg_up(ctx, st.get(), b->data, &st->cond.b))) return rc;
-  }
+  // cond_layer stays [cout][cin]: a matrix-vector product per voice
+  if ((rc = rd.raw("hifigan.cond_layer", HFG_C0, HFG_LAT, 1, h)) || (rc = st->dev.up(ctx, h, st->cond))) return rc;
   int ch = HFG_C0;
   for (int i = 0; i < HFG_STAGES; i++) {
     const int u = HFG_UP[i], ku = 2 * u, pad = u / 2, cin = ch, cout = ch / 2;
     const std::string p = "hifigan.ups." + std::to_string(i);
     const HostTensor *w, *b;
-    if (!(w = need(p + ".weight", cin, cout, ku)) || !(b = need(p + ".bias", cout, 0, 0))) return TTS_ERR_FORMAT;
+    if (!(w = rd.need(p + ".weight", cin, cout, ku)) || !(b = rd.need(p + ".bias", cout, 0, 0))) return TTS_ERR_FORMAT;
     // ConvTranspose1d [cin][cout][ku] -> [phase][2][cin][cout]: tap 0 = kernel index k0 + u (input row q + s_p - 1), tap 1 = k0 (row q + s_p)
     std::vector<float> r((size_t)u * 2 * cin * cout);
     for (int ph = 0; ph < u; ph++) {
@@ -343,7 +313,7 @@ int hifigan_load(tts_ctx *ctx, const char *path) {
         for (int ci = 0; ci < cin; ci++)
           for (int co = 0; co < cout; co++) r[(((size_t)ph * 2 + j) * cin + ci) * cout + co] = w->data[((size_t)ci * cout + co) * ku + k0 + (1 - j) * u];
     }
-    if ((rc = hfg_up(ctx, st.get(), r, &st->ups[i].w)) || (rc = hfg_up(ctx, st.get(), b->data, &st->ups[i].b))) return rc;
+    if ((rc = st->dev.up(ctx, r, &st->ups[i].w)) || (rc = st->dev.up(ctx, b->data, &st->ups[i].b))) return rc;
     ch = cout;
     for (int j = 0; j < 3; j++)
       for (int n = 0; n < 3; n++) {
@@ -352,15 +322,8 @@ int hifigan_load(tts_ctx *ctx, const char *path) {
         if ((rc = conv(rb + ".convs2." + std::to_string(n), ch, ch, HFG_RK[j], st->c2[i][j][n]))) return rc;
       }
   }
-  { // conv_post [1][32][7] -> [7][32]
-    const HostTensor *w, *b;
-    if (!(w = need("hifigan.conv_post.weight", 1, 32, 7)) || !(b = need("hifigan.conv_post.bias", 1, 0, 0))) return TTS_ERR_FORMAT;
-    std::vector<float> r(7 * 32);
-    for (int ci = 0; ci < 32; ci++)
-      for (int j = 0; j < 7; j++) r[j * 32 + ci] = w->data[ci * 7 + j];
-    if ((rc = hfg_up(ctx, st.get(), r, &st->post.w)) || (rc = hfg_up(ctx, st.get(), b->data, &st->post.b))) return rc;
-  }
-  if (wf.t.size() != known) return fail(ctx, TTS_ERR_FORMAT, "unknown tensors in HiFi-GAN model file '%s' (%d tensors, %d expected)", path, (int)wf.t.size(), (int)known);
+  // conv_post [1][32][7] -> [7][32]
+  if ((rc = conv("hifigan.conv_post", 1, 32, 7, st->post)) || (rc = rd.finish(path))) return rc;
   if (ctx->hifigan) hifigan_free(ctx->hifigan);
   ctx->hifigan = st.release();
   return TTS_OK;

@@ -147,7 +147,7 @@ long long tts_bvg_test_packed(const char *path, int which, int i, int j, int n, 
   if (rc != TTS_OK) return rc;
   if (i < 0 || i >= h->n_stages || j < 0 || j > 2 || n < 0 || n > (which == 4 || which == 5 ? 5 : 2)) return TTS_ERR_ARG;
   const std::vector<float> *v = which == 0 ? &h->pre.w : which == 1 ? &h->ups[i].w : which == 2 ? &h->c1[i][j][n].w : which == 3 ? &h->c2[i][j][n].w :
-                                which == 4 ? &h->act[i][j][n].alpha : which == 5 ? &h->act[i][j][n].inv_beta : which == 6 ? &h->post.w : which == 7 ? &h->ups[i].b : nullptr;
+                                which == 4 ? &h->act[i][j][n].w : which == 5 ? &h->act[i][j][n].b : which == 6 ? &h->post.w : which == 7 ? &h->ups[i].b : nullptr;
   if (!v) return TTS_ERR_ARG;
   if (out) memcpy(out, v->data(), (size_t)std::min<long long>(cap, (long long)v->size()) * 4);
   return (long long)v->size();

@@ -22,8 +22,8 @@ enum { TTS_CLS_TEST_STEM = 0, TTS_CLS_TEST_GN = 1, TTS_CLS_TEST_DOWN = 2, TTS_CL
 enum { TTS_CLS_TEST_MAX_CLIPS = 4, TTS_CLS_TEST_MAX_ROWS = 4096, TTS_CLS_TEST_MAX_FLOATS = 1 << 21 };
 
 // One case. Host pointers only. `out` holds TTS_CLS_TEST_MARGIN bytes, the payload, TTS_CLS_TEST_MARGIN bytes; the payload starts as the sentinel.
-//   n        [ns] rows of every clip. The HFG_SEQ table is built from it by classifier_run's rule: first row = the running sum of ceil8(n), first GroupNorm
-//            tile = the running sum of ceil(n / tile), first sample = the first row.
+//   n        [ns] rows of every clip. The HFG_SEQ table is built from it by cls_levels, which classifier_run calls: first row = the running sum of ceil8(n),
+//            first GroupNorm tile = the running sum of ceil(n / tile), first sample = the first row.
 //   start    null, or [ns] first rows that replace the running sum (validated: multiples of 8, in order, no overlap, inside `rows`)
 //   rows     rows of the input buffer (a multiple of 8)
 //   STEM     in = samples [rows], clip s at start[s]; w [C][3], bias [C]; out f32 [rows][C]
@@ -66,23 +66,23 @@ struct Dev { // one device allocation: margin | payload | margin
 
 int ceil8(int v) { return (v + 7) / 8 * 8; }
 
-// the table of `n` rows per clip inside a buffer of `rows` rows; false: a layout classifier_run never builds
+// the table of `n` rows per clip inside a buffer of `rows` rows: level 0 of cls_levels, the function classifier_run calls, with `start` in the place of its
+// first rows; false: a layout classifier_run never builds
 bool table(const int *n, const int *start, int ns, int rows, std::vector<int> &seq, int &max_n, int &tiles) {
-  seq.assign((size_t)HFG_SEQ * ns, 0);
-  int64_t next = 0;
-  max_n = 0; tiles = 0;
-  for (int s = 0; s < ns; s++) {
+  for (int s = 0; s < ns; s++)
     if (n[s] < 1 || n[s] > rows) return false;
-    int64_t st = next;
+  LevelTable t = cls_levels(n, ns, 0, 1);
+  int64_t next = 0;
+  for (int s = 0; s < ns; s++) {
+    int *q = &t.tab[(size_t)HFG_SEQ * s];
     if (start) {
-      st = start[s];
-      if (st % 8 || st < next) return false; // an overlap lets two workgroups write the same rows
+      if (start[s] % 8 || start[s] < next) return false; // an overlap lets two workgroups write the same rows
+      q[0] = q[4] = start[s];
     }
-    if (st + ceil8(n[s]) > rows) return false;
-    int *q = &seq[(size_t)HFG_SEQ * s];
-    q[0] = (int)st; q[1] = n[s]; q[3] = tiles; q[4] = (int)st;
-    next = st + ceil8(n[s]); tiles += (n[s] + CLS_GN_TILE - 1) / CLS_GN_TILE; max_n = std::max(max_n, n[s]);
+    next = (int64_t)q[0] + ceil8(n[s]);
+    if (next > rows) return false;
   }
+  seq.swap(t.tab); max_n = t.max_n[0]; tiles = (int)t.tiles[0];
   return true;
 }
 
@@ -105,8 +105,9 @@ bool valid(const tts_cls_case &c, Plan &p) {
       if (c.taps < 1 || c.taps > 11 || c.taps % 2 == 0 || c.stride < 2 || c.stride > 6) return false;
       if (cls_down_lds(c.taps, c.stride) > 64 * 1024) return false;
       if (c.rows_out < 8 || c.rows_out % 8 || c.rows_out > TTS_CLS_TEST_MAX_ROWS || (int64_t)c.rows_out * c.C2 > TTS_CLS_TEST_MAX_FLOATS) return false;
+      const LevelTable two = cls_levels(c.n, c.ns, 1, c.stride); // the Downsample's output rows, as classifier_run counts them
       p.n_out.resize(c.ns);
-      for (int s = 0; s < c.ns; s++) p.n_out[s] = (c.n[s] - 1) / c.stride + 1;
+      for (int s = 0; s < c.ns; s++) p.n_out[s] = two.rec(1, s)[1];
       return table(p.n_out.data(), c.start_out, c.ns, c.rows_out, p.seq_out, p.max_out, p.tiles_out);
     }
     default: // ATTN: qkv[(first row + t) * 3 C + {0, C, 2 C} + h * DH + d], out[(first row + t) * C + h * DH + d], t < n, h < heads, d < DH = 64 or 128
@@ -131,6 +132,15 @@ int tts_cls_test_table(const tts_cls_case *c, int *in_tab, int *out_tab) {
   if (!c || !in_tab || !valid(*c, p)) return (int)hipErrorInvalidValue;
   memcpy(in_tab, p.seq.data(), p.seq.size() * sizeof(int));
   if (out_tab && !p.seq_out.empty()) memcpy(out_tab, p.seq_out.data(), p.seq_out.size() * sizeof(int));
+  return 0;
+}
+
+// classifier_run's tables for clips of n[s] samples at 24 kHz (host only): tab [depth + 1][ns][9], rows / tiles / max_n [depth + 1]
+int tts_cls_test_levels(const int *n, int ns, int depth, int F, int *tab, long long *rows, long long *tiles, int *max_n) {
+  if (!n || !tab || !rows || !tiles || !max_n || ns < 1 || depth < 0 || F < 1) return (int)hipErrorInvalidValue;
+  const LevelTable t = cls_levels(n, ns, depth, F);
+  memcpy(tab, t.tab.data(), t.tab.size() * sizeof(int));
+  for (int l = 0; l <= depth; l++) { rows[l] = t.rows[l]; tiles[l] = t.tiles[l]; max_n[l] = t.max_n[l]; }
   return 0;
 }
 

@@ -24,7 +24,7 @@ enum { TTS_DVAE_TEST_STEM = 0, TTS_DVAE_TEST_DOWN = 1, TTS_DVAE_TEST_VQ = 2 };
 enum { TTS_DVAE_TEST_MAX_CLIPS = 4, TTS_DVAE_TEST_MAX_ROWS = 1 << 12, TTS_DVAE_TEST_MAX_FLOATS = 1 << 23 };
 
 // One case. Host pointers only. `out` (and `out2`) hold TTS_DVAE_TEST_MARGIN bytes, the payload, TTS_DVAE_TEST_MARGIN bytes; the payload starts as the sentinel.
-//   n      [ns] frames (STEM) or rows (DOWN) of every clip; the HFG_SEQ tables are built from it by dvae_begin's rule: first row = the running sum of the rows,
+//   n      [ns] frames (STEM) or rows (DOWN) of every clip; the HFG_SEQ tables are built from it by dvae_levels, which dvae_begin calls: first row = the running sum of the rows,
 //          first mel float = cin x the running sum of the frames; the output rows of a clip are (n - 1) / stride + 1. VQ: unused (ns = 1).
 //   STEM   in = the mels back to back, clip s band-major [cin][n[s]]; w [taps][cin][cout], bias [cout]; out f32 [rows_out][cout]
 //   DOWN   in [rows][cin]; w [taps][cin][cout], bias [cout]; out f32 [rows_out][cout] = ReLU(Conv1d(stride, pad (taps - 1) / 2))
@@ -79,16 +79,12 @@ bool valid(const tts_dvae_case &c, Plan &p) {
   if (c.taps < 1 || c.taps > DVAE_MAX_K || c.taps % 2 == 0 || c.stride < 1 || c.stride > DVAE_MAX_STRIDE) return false;
   if (!dvae_channels_ok(c.cout)) return false;
   if (c.kind == TTS_DVAE_TEST_STEM ? (c.cin < 1 || c.cin > DVAE_MAX_CIN) : !dvae_channels_ok(c.cin)) return false; // DOWN: float4 loads of 32-channel chunks
-  p.seq.assign((size_t)HFG_SEQ * c.ns, 0); p.seq_out.assign((size_t)HFG_SEQ * c.ns, 0);
-  int64_t ri = 0, ro = 0;
-  for (int s = 0; s < c.ns; s++) {
+  for (int s = 0; s < c.ns; s++)
     if (c.n[s] < 1 || c.n[s] > TTS_DVAE_TEST_MAX_ROWS) return false;
-    const int no = dvae_conv_rows(c.n[s], c.stride);
-    int *q = &p.seq[(size_t)HFG_SEQ * s], *o = &p.seq_out[(size_t)HFG_SEQ * s];
-    q[0] = (int)ri; q[1] = c.n[s]; q[4] = (int)(ri * c.cin);
-    o[0] = (int)ro; o[1] = no;
-    ri += c.n[s]; ro += no; p.max_out = std::max(p.max_out, no);
-  }
+  const LevelTable t = dvae_levels(c.n, c.ns, 1, c.stride, c.cin); // the function dvae_begin calls, for one strided layer
+  p.seq.assign(t.rec(0, 0), t.rec(0, 0) + (size_t)HFG_SEQ * c.ns); p.seq_out.assign(t.rec(1, 0), t.rec(1, 0) + (size_t)HFG_SEQ * c.ns);
+  p.max_out = t.max_n[1];
+  const int64_t ri = t.rows[0], ro = t.rows[1];
   if (ri != c.rows || ro != c.rows_out) return false; // the buffers hold exactly the clips
   p.in_floats = ri * c.cin;
   return p.in_floats <= TTS_DVAE_TEST_MAX_FLOATS && ro * c.cout <= TTS_DVAE_TEST_MAX_FLOATS;
@@ -102,6 +98,15 @@ extern "C" {
 int tts_dvae_test_validate(const tts_dvae_case *c) {
   Plan p;
   return c && valid(*c, p) ? 0 : (int)hipErrorInvalidValue;
+}
+
+// dvae_begin's tables for clips of n[s] mel frames of cin channels behind L strided layers (host only): tab [L + 1][ns][9], rows / max_n [L + 1]
+int tts_dvae_test_levels(const int *n, int ns, int L, int stride, int cin, int *tab, long long *rows, int *max_n) {
+  if (!n || !tab || !rows || !max_n || ns < 1 || L < 0 || stride < 1 || cin < 1) return (int)hipErrorInvalidValue;
+  const LevelTable t = dvae_levels(n, ns, L, stride, cin);
+  memcpy(tab, t.tab.data(), t.tab.size() * sizeof(int));
+  for (int l = 0; l <= L; l++) { rows[l] = t.rows[l]; max_n[l] = t.max_n[l]; }
+  return 0;
 }
 
 // The loader's host half on a model file (no HIP call): its status, and for TTS_OK out[0 .. 6] = strided layers, ResBlocks, mel channels, hidden channels,

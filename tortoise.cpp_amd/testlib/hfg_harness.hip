@@ -49,7 +49,7 @@ struct tts_hfg_case {
 int tts_hfg_test_margin(void) { return TTS_HFG_TEST_MARGIN; }
 int tts_hfg_test_seq_ints(void) { return HFG_SEQ; }            // the width of the product's candidate record
 int tts_hfg_test_frames(int L) { return tts_diffusion_frames(L); } // T of an utterance of L latent rows, read from the product
-// dynamic LDS of a convolution launch: hifigan.hip:445 (the 256-row tile) and hifigan.hip:440 (the small-M tile)
+// dynamic LDS of a convolution launch: hifigan.hip:408 (the 256-row tile) and hifigan.hip:403 (the small-M tile)
 long long tts_hfg_test_lds_bytes(int kind, int taps, int dil) {
   return (long long)((kind == TTS_HFG_TEST_CONV_SMALL ? HFG_TS : HFG_TM) + (long long)(taps - 1) * dil) * 33 * 4;
 }
@@ -75,7 +75,7 @@ struct Dev { // one device allocation: margin | payload | margin
 
 int ceil8(int v) { return (v + 7) / 8 * 8; }
 bool is_conv(int k) { return k == TTS_HFG_TEST_CONV || k == TTS_HFG_TEST_CONV_SMALL; }
-int nt_of(int cout) { return cout >= 64 ? 2 : 1; } // hifigan.hip:443
+int nt_of(int cout) { return cout >= 64 ? 2 : 1; } // hifigan.hip:406
 
 // the product's table by hifigan_run's rule (the two lines are cited below), or false. maxW / maxKeep size the grids as hifigan_run's do.
 bool table(const tts_hfg_case &c, std::vector<int> &seq, int &maxW, int &maxKeep, int64_t &lat_rows, int64_t &kept) {
@@ -108,9 +108,9 @@ bool table(const tts_hfg_case &c, std::vector<int> &seq, int &maxW, int &maxKeep
     if (c.kind == TTS_HFG_TEST_INTERP && (int64_t)w0 + W > tts_diffusion_frames(L)) return false;
     // hfg_post_kernel reads x rows around (keep0 * 256 + j) and writes audio[before * 256 + j] for j < keep_n * 256: the kept frames lie inside the window
     if (keep0 < 0 || keep_n < 1 || (int64_t)keep0 + keep_n > W) return false;
-    int *r = &seq[(size_t)HFG_SEQ * s]; // hifigan.hip:400
+    int *r = &seq[(size_t)HFG_SEQ * s]; // hifigan.hip:363
     r[0] = (int)start; r[1] = W; r[2] = voice; r[3] = L; r[4] = (int)lat_rows; r[5] = (int)kept; r[6] = w0; r[7] = keep0; r[8] = keep_n;
-    lat_rows += L; kept += keep_n; fpad = start + ceil8(W); // hifigan.hip:401
+    lat_rows += L; kept += keep_n; fpad = start + ceil8(W); // hifigan.hip:364
     maxW = std::max(maxW, W); maxKeep = std::max(maxKeep, keep_n);
   }
   return true;
@@ -134,7 +134,7 @@ bool valid(const tts_hfg_case &c, std::vector<int> &seq, int &maxW, int &maxKeep
     // columns n0 + n * 32 + lr of w, bias, cbias, out with n0 = z * 32 nt: cout must be whole groups of 32 nt
     if (c.cout % (32 * nt_of(c.cout))) return false;
   } else {
-    // columns n0 + lr with n0 = z * 128 + wave * 32: cout must be whole groups of 128 (hifigan.hip:438)
+    // columns n0 + lr with n0 = z * 128 + wave * 32: cout must be whole groups of 128 (hifigan.hip:401)
     if (c.cout % 128) return false;
   }
   // w[(tap * cin + ..) * cout + ..], tap < taps; the LDS row (lr + tap * dil) * 33 < win * 33 needs taps >= 1, dil >= 1
@@ -217,13 +217,13 @@ int tts_hfg_test_run(const tts_hfg_case *cp) {
       case TTS_HFG_TEST_CONV: case TTS_HFG_TEST_CONV_SMALL: {
         const int cin = c.cin, cout = c.cout, taps = c.taps, dil = c.dil, phases = c.phases, rate = c.rate;
         HfgConv a{};
-        a.in = din; a.out = dy; a.resid = c.alias == 1 ? dy : (const float *)resid.data(); a.w = dw; a.bias = db; a.cbias = (const float *)cbias.data(); a.seq = d_seq; // hifigan.hip:434
-        a.cin = cin; a.cout = cout; a.taps = taps; a.dil = dil; a.lo = -dil * (taps - 1) / 2; a.phases = phases; a.pad_t = phases / 2; a.rate = rate; // hifigan.hip:435
-        a.slope = c.slope; a.acc_mode = c.acc_mode; // hifigan.hip:436
-        if (c.kind == TTS_HFG_TEST_CONV_SMALL) { // hifigan.hip:438-440 (the `cout % 128 == 0` rule is in valid(); the row threshold is the caller's choice of kind)
+        a.in = din; a.out = dy; a.resid = c.alias == 1 ? dy : (const float *)resid.data(); a.w = dw; a.bias = db; a.cbias = (const float *)cbias.data(); a.seq = d_seq; // hifigan.hip:397
+        a.cin = cin; a.cout = cout; a.taps = taps; a.dil = dil; a.lo = -dil * (taps - 1) / 2; a.phases = phases; a.pad_t = phases / 2; a.rate = rate; // hifigan.hip:398
+        a.slope = c.slope; a.acc_mode = c.acc_mode; // hifigan.hip:399
+        if (c.kind == TTS_HFG_TEST_CONV_SMALL) { // hifigan.hip:401-403 (the `cout % 128 == 0` rule is in valid(); the row threshold is the caller's choice of kind)
           const dim3 grid((unsigned)(((size_t)maxW * rate + HFG_TS - 1) / HFG_TS), (unsigned)B, (unsigned)(cout / 128 * phases));
           hfg_conv_small_kernel<<<grid, 256, (size_t)(HFG_TS + (taps - 1) * dil) * 33 * 4, s>>>(a);
-        } else { // hifigan.hip:443-447
+        } else { // hifigan.hip:406-410
           const int nt = cout >= 64 ? 2 : 1;
           const dim3 grid((unsigned)(((size_t)maxW * rate + HFG_TM - 1) / HFG_TM), (unsigned)B, (unsigned)(cout / (32 * nt) * phases));
           const size_t lds = (size_t)(HFG_TM + (taps - 1) * dil) * 33 * 4;
@@ -232,13 +232,13 @@ int tts_hfg_test_run(const tts_hfg_case *cp) {
         }
         break;
       }
-      case TTS_HFG_TEST_INTERP: // hifigan.hip:426
+      case TTS_HFG_TEST_INTERP: // hifigan.hip:389
         hfg_interp_kernel<<<dim3(maxW, B), 256, 0, s>>>(din, d_seq, dy);
         break;
-      case TTS_HFG_TEST_COND: // hifigan.hip:427
+      case TTS_HFG_TEST_COND: // hifigan.hip:390
         hfg_cond_kernel<<<dim3(HFG_C0 / 4, c.n_voices), 256, 0, s>>>(dw, db, din, dy);
         break;
-      default: // hifigan.hip:466
+      default: // hifigan.hip:429
         hfg_post_kernel<<<dim3(maxKeep, B), 256, 0, s>>>(din, dw, db, d_seq, dy);
         break;
     }

@@ -22,8 +22,8 @@ enum { TTS_W2V_TEST_STATS = 0, TTS_W2V_TEST_STEM = 1, TTS_W2V_TEST_LN = 2, TTS_W
 enum { TTS_W2V_TEST_MAX_CLIPS = 4, TTS_W2V_TEST_MAX_ROWS = 1 << 15, TTS_W2V_TEST_MAX_FLOATS = 1 << 21 };
 
 // One case. Host pointers only. `out` (and `out2`) hold TTS_W2V_TEST_MARGIN bytes, the payload, TTS_W2V_TEST_MARGIN bytes; the payload starts as the sentinel.
-//   n        [ns] rows (STATS, STEM: samples) of every clip. The HFG_SEQ table is built from it by aligner_run's rule: first row = the running sum of
-//            ceil8(n), first statistics tile = the running sum of ceil(n / tile), first sample = the first row.
+//   n        [ns] rows (STATS, STEM: samples) of every clip. The HFG_SEQ table is built from it by w2v_levels, which aligner_run calls: first row = the running
+//            sum of ceil8(n), first statistics tile = the running sum of ceil(n / tile), first sample = the first row.
 //   start    null, or [ns] first rows that replace the running sum (validated: multiples of 8, in order, no overlap, inside `rows`)
 //   rows     rows of the input buffer (a multiple of 8)
 //   STATS    in = samples [rows]; out f64 [ns][2] = {mean, 1 / sqrt(unbiased var + 1e-7)}
@@ -67,23 +67,23 @@ struct Dev { // one device allocation: margin | payload | margin
 
 int ceil8(int v) { return (v + 7) / 8 * 8; }
 
-// the table of `n` rows per clip inside a buffer of `rows` rows; false: a layout aligner_run never builds
+// the table of `n` rows per clip inside a buffer of `rows` rows: level 0 of w2v_levels, the function aligner_run calls, with `start` in the place of its
+// first rows; false: a layout aligner_run never builds
 bool table(const int *n, const int *start, int ns, int rows, std::vector<int> &seq, int &max_n, int &tiles) {
-  seq.assign((size_t)HFG_SEQ * ns, 0);
-  int64_t next = 0;
-  max_n = 0; tiles = 0;
-  for (int s = 0; s < ns; s++) {
+  for (int s = 0; s < ns; s++)
     if (n[s] < 1 || n[s] > rows) return false;
-    int64_t st = next;
+  LevelTable t = w2v_levels(n, ns, 0, nullptr, nullptr);
+  int64_t next = 0;
+  for (int s = 0; s < ns; s++) {
+    int *q = &t.tab[(size_t)HFG_SEQ * s];
     if (start) {
-      st = start[s];
-      if (st % 8 || st < next) return false; // an overlap lets two workgroups write the same rows
+      if (start[s] % 8 || start[s] < next) return false; // an overlap lets two workgroups write the same rows
+      q[0] = q[4] = start[s];
     }
-    if (st + ceil8(n[s]) > rows) return false;
-    int *q = &seq[(size_t)HFG_SEQ * s];
-    q[0] = (int)st; q[1] = n[s]; q[3] = tiles; q[4] = (int)st;
-    next = st + ceil8(n[s]); tiles += (n[s] + W2V_ST_TILE - 1) / W2V_ST_TILE; max_n = std::max(max_n, n[s]);
+    next = (int64_t)q[0] + ceil8(n[s]);
+    if (next > rows) return false;
   }
+  seq.swap(t.tab); max_n = t.max_n[0]; tiles = (int)t.tiles[0];
   return true;
 }
 
@@ -105,7 +105,7 @@ bool valid(const tts_w2v_case &c, Plan &p) {
       p.n_out.resize(c.ns);
       for (int s = 0; s < c.ns; s++) {
         if (c.n[s] < c.taps) return false; // sample (T - 1) stride + taps - 1 < n
-        p.n_out[s] = (c.n[s] - c.taps) / c.stride + 1;
+        p.n_out[s] = w2v_conv_frames(c.n[s], c.taps, c.stride); // as aligner_run counts them
       }
       return table(p.n_out.data(), c.start_out, c.ns, c.rows_out, p.seq_out, p.max_out, p.tiles_out);
     }
@@ -139,6 +139,17 @@ int tts_w2v_test_table(const tts_w2v_case *c, int *in_tab, int *out_tab) {
   if (!c || !in_tab || !valid(*c, p)) return (int)hipErrorInvalidValue;
   memcpy(in_tab, p.seq.data(), p.seq.size() * sizeof(int));
   if (out_tab && !p.seq_out.empty()) memcpy(out_tab, p.seq_out.data(), p.seq_out.size() * sizeof(int));
+  return 0;
+}
+
+// aligner_run's tables for clips of n[s] samples at 16 kHz behind N convolutions of k[i] taps and stride s[i] (host only): tab [N + 1][ns][9],
+// rows / max_n [N + 1], tiles [0] = the statistics tiles of level 0
+int tts_w2v_test_levels(const int *n, int ns, int N, const int *k, const int *s, int *tab, long long *rows, long long *tiles, int *max_n) {
+  if (!n || !tab || !rows || !tiles || !max_n || ns < 1 || N < 0 || (N && (!k || !s))) return (int)hipErrorInvalidValue;
+  const LevelTable t = w2v_levels(n, ns, N, k, s);
+  memcpy(tab, t.tab.data(), t.tab.size() * sizeof(int));
+  for (int l = 0; l <= N; l++) { rows[l] = t.rows[l]; max_n[l] = t.max_n[l]; }
+  tiles[0] = t.tiles[0];
   return 0;
 }
 
