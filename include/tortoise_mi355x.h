@@ -453,6 +453,11 @@ int tts_hifigan_decode(tts_ctx *ctx, const float *latents, const int32_t *rows, 
  *   n_frames < 1 or frame0 + n_frames > tts_diffusion_frames(rows[c]). */
 int tts_hifigan_chunk(tts_ctx *ctx, const float *latents, const int32_t *rows, int n_candidates, const float *voices, int n_voices,
                       const int32_t *voice_of_candidate, const int32_t *frame0, const int32_t *n_frames, float *audio_out);
+/* Option "hfg_precision" (0 default; addition within version 8, no prototype changed): operands of every convolution of tts_hifigan_decode, tts_hifigan_chunk,
+ * tts_hifigan_stream, session audio and tts_bigvgan. 0 = f32 (the f32-input MFMA, as before), 1 = fp16 operands with f32 accumulation, 2 = activation and weight
+ * each as an fp16 hi + lo pair (three products per step, f32 accumulation): the f32 mode's accuracy at about half its time. Any other value: TTS_ERR_ARG, nothing
+ * changes. Every contract of these calls (a chunk partition is the whole call bit for bit, a candidate is the same bits alone and in a batch) holds within a mode;
+ * the bits of two modes differ. Mode 1 is 1.4e-3 to 1.8e-3 from the float64 restatements: above the 1e-3 stage gate. "hfg_small_m" is ignored in modes 1 and 2. */
 /* tts_hifigan_stream: tts_autoregressive for ONE candidate (the reference's own workload and upstream tts_stream's; re-ranking several candidates cannot
  * stream) whose audio leaves through `cb` while the loop is still sampling. The sampling loop is tts_autoregressive's — sampler controls, stop rule, flags,
  * stop schedule, RNG consumption: codes_out [502], rows_out [1], steps_out and the RNG state afterwards are those of tts_autoregressive(n_candidates = 1).

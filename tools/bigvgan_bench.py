@@ -9,7 +9,10 @@ bench length (L = 200 latent rows: T = tts_diffusion_frames(200) mel frames each
   - the compiler's resource summary of the three new kernels (hipcc -Rpass-analysis=kernel-resource-usage on csrc/hifigan.hip, device code only).
 No time is a pass condition.
 
-  python tools/bigvgan_bench.py [--calls 7] [--warm 2] [--rows 200] [--skip-large] [--models DIR] [--out profiles/bigvgan.txt]"""
+  python tools/bigvgan_bench.py [--calls 7] [--warm 2] [--rows 200] [--skip-large] [--models DIR] [--out profiles/bigvgan.txt] [--precision 0,1,2]
+
+--precision M[,M..]: instead of the comparison with UnivNet, option hfg_precision at each listed value (0 f32, 1 fp16, 2 split fp16 pairs), the modes interleaved
+call by call: median, minimum and maximum of tts_bigvgan per mode and the hfg_conv family of a profiled call per mode (profiles/hfg_f16.txt)."""
 import argparse
 import os
 import re
@@ -75,8 +78,11 @@ def main():
     ap.add_argument("--rows", type=int, default=200)
     ap.add_argument("--skip-large", action="store_true")
     ap.add_argument("--models", default=os.path.join(os.environ.get("TTS_SYNTH_DIR", "/tmp/tts_synth"), "bigvgan_bench"))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bigvgan.txt"))
+    ap.add_argument("--out", default=None)  # profiles/bigvgan.txt, unless --precision is given: then nothing is written without it
+    ap.add_argument("--precision", default=None)
     a = ap.parse_args()
+    modes = [int(m) for m in a.precision.split(",")] if a.precision else None
+    a.out = a.out or (None if modes else os.path.join(ROOT, "profiles", "bigvgan.txt"))
     os.makedirs(a.models, exist_ok=True)
     lines = []
 
@@ -104,6 +110,26 @@ def main():
         say("== %s: C0 = %d, strides %s, %.0f MB of weights" % (name, c0, rates, os.path.getsize(path) / 1e6))
         for B in (16, 1):
             mels = [sw.bigvgan_test_mel(T, 100 + i) for i in range(B)]
+            if modes:
+                ts = {m: [] for m in modes}
+                for i in range(a.warm + a.calls):
+                    for m in modes:
+                        eng.set_option("hfg_precision", m)
+                        t = timed(lambda: eng.bigvgan(mels), 1, 0)
+                        if i >= a.warm:
+                            ts[m] += t
+                for m in modes:
+                    say("  %2d candidates  hfg_precision %d  tts_bigvgan  %s" % (B, m, fmt(ts[m])))
+                eng.set_option("prof_stride", 1)
+                for m in modes:
+                    eng.set_option("hfg_precision", m)
+                    eng.prof_reset(True)
+                    eng.bigvgan(mels)
+                    ms, n, work = eng.prof_get("hfg_conv")
+                    eng.prof_reset(False)
+                    say("  %2d candidates  hfg_precision %d  hfg_conv %8.2f ms on the device, %4d launches, %.1f TFLOP/s" % (B, m, ms, n, work / ms / 1e9))
+                eng.set_option("hfg_precision", 0)
+                continue
             tb, tv = [], []
             for _ in range(a.warm):
                 eng.bigvgan(mels); eng.vocoder(mels, noise_mode=pkg.NOISE_DEVICE)
@@ -130,8 +156,9 @@ def main():
     for k, v in sorted(resources().items()):
         say("  %-16s VGPRs %3d  SGPRs %3d  scratch %d B/lane  occupancy %d waves/SIMD  LDS %d B/workgroup"
             % (k, v.get("VGPRs", -1), v.get("TotalSGPRs", -1), v.get("ScratchSize", -1), v.get("Occupancy", -1), v.get("LDS Size", -1)))
-    with open(a.out, "w") as f:
-        f.write("\n".join(lines) + "\n")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":

@@ -3,7 +3,11 @@ noise, + tts_vocoder) on the same box in the same run: benchmark length (L = 200
 timed calls after two warm-ups; the "hfg_conv" profiler family's device time and achieved FLOP rate from a separate profiled call (event pairs drain the
 pipeline, so the profiled call is not one of the timed ones). The record of one run is profiles/hifigan_decoder.txt.
 
-  python tools/hifigan_bench.py [--calls 5] [--out FILE] [--no-diffusion 1]
+  python tools/hifigan_bench.py [--calls 5] [--out FILE] [--no-diffusion 1] [--precision 0,1,2]
+
+--precision M[,M..]: instead, option hfg_precision at each listed value (0 f32, 1 fp16, 2 split fp16 pairs) in one process, the modes interleaved call by call,
+`--calls` timed calls each after two warm-ups of every mode: median, minimum and maximum per mode, and the hfg_conv family of a profiled call per mode. A gain is
+read only where the ranges of two modes do not touch (profiles/hfg_f16.txt).
 
 The HiFi-GAN weights are synthetic (tortoise.cpp_amd/synth_weights.py: write_hifigan), the diffusion and vocoder weights the benchmark's."""
 import argparse
@@ -29,7 +33,10 @@ def main():
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-diffusion", type=int, default=0)
+    ap.add_argument("--precision", default=None)
     a = ap.parse_args()
+    modes = [int(m) for m in a.precision.split(",")] if a.precision else None
+    a.no_diffusion = a.no_diffusion or modes is not None
     d = os.environ.get("TTS_BENCH_MODELS", "/tmp/tts_bench_models")
     hp = os.path.join(d, "ggml-hifigan-model.bin")
     if not a.no_diffusion:
@@ -57,8 +64,33 @@ def main():
         print(lines[-1], flush=True)
         return statistics.median(ts)
 
+    def family(what):
+        eng.prof_reset(True)
+        eng.hifigan_decode(lats, voice)
+        ms, n, work = eng.prof_get("hfg_conv")
+        eng.prof_reset(False)
+        lines.append("%s  hfg_conv family: %d launches, %.1f ms on the device, %.3f TFLOP -> %.1f TFLOP/s" % (what, n, ms, work / 1e12, work / ms / 1e9))
+        print(lines[-1], flush=True)
+
+    for B in (16, 1) if modes else ():
+        lats = [np.random.RandomState(c).randn(L, 1024).astype(np.float32) for c in range(B)]
+        ts = {m: [] for m in modes}
+        for i in range(2 + a.calls):
+            for m in modes:
+                eng.set_option("hfg_precision", m)
+                t0 = time.perf_counter()
+                eng.hifigan_decode(lats, voice)
+                if i >= 2:
+                    ts[m].append(1e3 * (time.perf_counter() - t0))
+        for m in modes:
+            lines.append("B = %2d  hfg_precision %d  tts_hifigan_decode  median %8.1f ms  (min %8.1f max %8.1f)" % (B, m, statistics.median(ts[m]), min(ts[m]), max(ts[m])))
+            print(lines[-1], flush=True)
+        for m in modes:
+            eng.set_option("hfg_precision", m)
+            family("B = %2d  hfg_precision %d" % (B, m))
+        eng.set_option("hfg_precision", 0)
     res = {}
-    for B in (16, 1):
+    for B in () if modes else (16, 1):
         lats = [np.random.RandomState(c).randn(L, 1024).astype(np.float32) for c in range(B)]
         res[("hfg", B)] = timed("B = %2d  tts_hifigan_decode" % B, lambda: eng.hifigan_decode(lats, voice))
         eng.prof_reset(True)

@@ -258,15 +258,18 @@ int bigvgan_load(tts_ctx *ctx, const char *path) {
   if ((rc = bigvgan_parse(ctx, wf, path, *h))) return rc;
   std::unique_ptr<BigvganState> st(new BigvganState());
   auto up = [&](const HostLayer &s, HfgLayer &d) { return st->dev.up(ctx, s, d); };
+  // a convolution hfg_conv launches: its f32 tensor, and beside it the fp16 planes of option "hfg_precision" (pt = phases x taps)
+  auto upc = [&](const HostLayer &s, int pt, int cin, int cout, HfgLayer &d) { const int e = up(s, d); return e ? e : st->dev.pack(ctx, "BigVGAN", s.w, pt, cin, cout, d); };
   st->c0 = h->c0; st->n_stages = h->n_stages;
   for (int i = 0; i < BVG_MAX_STAGES; i++) st->up[i] = h->up[i];
   for (int i = 0; i <= BVG_MAX_STAGES; i++) st->ch[i] = h->ch[i];
-  if ((rc = up(h->pre, st->pre)) || (rc = up(h->post, st->post)) || (rc = up(h->act_post, st->act_post))) return rc;
+  if ((rc = upc(h->pre, 7, BVG_MEL_PAD, h->ch[0], st->pre)) || (rc = up(h->post, st->post)) || (rc = up(h->act_post, st->act_post))) return rc;
   for (int i = 0; i < h->n_stages; i++) {
-    if ((rc = up(h->ups[i], st->ups[i]))) return rc;
+    const int ch = h->ch[i + 1];
+    if ((rc = upc(h->ups[i], 2 * h->up[i], h->ch[i], ch, st->ups[i]))) return rc;
     for (int j = 0; j < 3; j++) {
       for (int n = 0; n < 3; n++)
-        if ((rc = up(h->c1[i][j][n], st->c1[i][j][n])) || (rc = up(h->c2[i][j][n], st->c2[i][j][n]))) return rc;
+        if ((rc = upc(h->c1[i][j][n], HFG_RK[j], ch, ch, st->c1[i][j][n])) || (rc = upc(h->c2[i][j][n], HFG_RK[j], ch, ch, st->c2[i][j][n]))) return rc;
       for (int n = 0; n < 6; n++)
         if ((rc = up(h->act[i][j][n], st->act[i][j][n]))) return rc;
     }
@@ -291,7 +294,7 @@ int bigvgan_config(tts_ctx *ctx, int32_t *out8) {
 int bigvgan_run(tts_ctx *ctx, const float *mel, const int32_t *frames_in, int B, float *audio_out) {
   BigvganState *st = ctx->bigvgan;
   if (!st) return fail(ctx, TTS_ERR_STATE, "tts_load_bigvgan not called");
-  if (!mel || !frames_in || !audio_out || B < 1) return fail(ctx, TTS_ERR_ARG, "tts_bigvgan: bad argument");
+  if (!mel || !frames_in || !audio_out || B < 1 || !hfg_precision_ok(ctx->hfg_precision)) return fail(ctx, TTS_ERR_ARG, "tts_bigvgan: bad argument");
   if (B > BVG_MAX_CAND) return fail(ctx, TTS_ERR_LIMIT, "tts_bigvgan: %d candidates (at most %d per call)", B, BVG_MAX_CAND);
   std::vector<int> seq((size_t)HFG_SEQ * B, 0);
   int64_t frames = 0, fpad = 0;
@@ -332,13 +335,16 @@ int bigvgan_run(tts_ctx *ctx, const float *mel, const int32_t *frames_in, int B,
     ProfScope ps(ctx, "bvg_mel", (double)frames * (BVG_MEL + BVG_MEL_PAD) * 4);
     bvg_mel_kernel<<<dim3(maxT, B), 128, 0, ctx->stream>>>(d_mel, d_seq, st->mel.as<float>());
   }
-  // hfg_conv_kernel as hifigan_run launches it, with slope 1 (no leaky ReLU), no conditioning vector; two column groups per workgroup where they divide cout
+  // hfg_conv_kernel as hifigan_run launches it, with slope 1 (no leaky ReLU), no conditioning vector; two column groups per workgroup where they divide cout.
+  // Option "hfg_precision" 1 / 2: hfg_conv_h_kernel (fp16 / split-pair operands) on the same descriptor, the same profiler family and FLOP count.
+  const int prec = ctx->hfg_precision;
   auto conv = [&](const float *in, float *out, const float *resid, const HfgLayer &l, int cin, int cout, int taps, int dil, int phases, int rate, int acc_mode) {
     HfgConv a{};
     a.in = in; a.out = out; a.resid = resid; a.w = l.w; a.bias = l.b; a.cbias = nullptr; a.seq = d_seq;
     a.cin = cin; a.cout = cout; a.taps = taps; a.dil = dil; a.lo = -dil * (taps - 1) / 2; a.phases = phases; a.pad_t = phases / 2; a.rate = rate;
     a.slope = 1.0f; a.acc_mode = acc_mode;
     ProfScope ps(ctx, "hfg_conv", 2.0 * (double)frames * rate * phases * taps * cin * cout);
+    if (prec) return hfg_conv_h_launch(ctx->stream, a, l.wh, l.wl, l.ws, prec == 2, (size_t)maxT * rate, B);
     const int nt = cout % 64 == 0 ? 2 : 1;
     const dim3 grid((unsigned)(((size_t)maxT * rate + HFG_TM - 1) / HFG_TM), (unsigned)B, (unsigned)(cout / (32 * nt) * phases));
     const size_t lds = (size_t)(HFG_TM + (taps - 1) * dil) * 33 * 4;

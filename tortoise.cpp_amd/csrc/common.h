@@ -199,6 +199,7 @@ struct tts_ctx {
   int stream_recaptures = 0; // decode-step graphs captured inside the last tts_hifigan_stream call's loop after its first step (tts_hifigan_stream_recaptures)
   int hfg_small_m = 0;     // option "hfg_small_m": tts_hifigan_chunk runs a convolution whose longest window has at most this many rows on the small-M tile (0, the default until
                            // profiles/hifigan_stream.txt holds a measurement in its favour: never)
+  int hfg_precision = 0;   // option "hfg_precision": operands of the convolutions of hifigan_run and bigvgan_run: 0 = f32 (hfg_conv_kernel), 1 = fp16, 2 = fp16 hi + lo pairs (hfg_conv_h_kernel)
   int diff_graph = 1;      // option "diff_graph": the diffusion step is captured once per call and replayed (0: every step launched eagerly)
   int prof_eager_every = 8; // while a diff_* family is profiled, every Nth diffusion step runs eagerly with its event pairs; the others replay the graph
   std::map<std::string, tts::ProfEntry> prof;
@@ -209,6 +210,9 @@ struct tts_ctx {
 namespace tts {
 
 int fail(tts_ctx *ctx, int code, const char *fmt, ...);
+
+// Option "hfg_precision": the values tts_set_option stores and hifigan_run / bigvgan_run accept (0 f32, 1 fp16, 2 split fp16 pairs)
+inline bool hfg_precision_ok(double v) { return v == 0 || v == 1 || v == 2; }
 
 // n draws of the context's normal distribution (sample_normal_noise, main.cpp:4695-4701: std::normal_distribution<double> over std::mt19937, values narrowed to float) into
 // dst, leaving generator and distribution in exactly the state n single draws leave them in. Large counts take a two-phase form of the same algorithm (host_logic.cpp).

@@ -21,9 +21,8 @@
 //   - the leaky_relu of its input fused into the staging of the operand,
 //   - bias, the per-voice conditioning vector, the residual add and the three-ResBlock mean fused into the epilogue,
 //   - a transposed convolution run as its u phases: phase p of the output is a 2-tap convolution of the input (grid z), written with row stride u.
-// The residual stream stays f32. Operand precision: f32 everywhere. The gate is 1e-3 on the waveform after 4 x (1 + 18) chained convolutions;
-// f32 MFMA holds it with two orders of magnitude to spare (measured 4e-6) at 1/16 of the fp16 MFMA rate, and the stage is still 7 x cheaper than the
-// diffusion path it replaces (118 against 872 ms for 16 candidates x 9.3 s: profiles/hifigan_decoder.txt). fp16 or split-pair operands for the 256- and 128-channel levels are the next step.
+// The residual stream stays f32. Operand precision: f32 by default (the gate is 1e-3 on the waveform after 4 x (1 + 18) chained convolutions; f32 MFMA holds it with two orders
+// of magnitude to spare, measured 4e-6, at 1/16 of the fp16 MFMA rate); option "hfg_precision" 1 / 2 runs every convolution on hfg_conv_h.h's fp16 / split-pair kernel instead.
 //
 // A call is one launch sequence for the whole ragged batch: one upload (latents, voice table, candidate table), 1 + 1 + 1 + 4 x 19 + 1 launches,
 // one download. Nothing of it depends on the batch: a candidate's samples are the same bits alone or in any batch.
@@ -272,6 +271,7 @@ __global__ __launch_bounds__(256) void hfg_post_kernel(const float *__restrict__
 }
 } // namespace
 } // namespace tts
+#include "hfg_conv_h.h" // hfg_conv_h_kernel and the weight packer: the same convolutions on the fp16 MFMA (option "hfg_precision")
 #include "model_io.h" // ModelReader, DevWeights, the level tables and the clip ingest of every model of this translation unit
 namespace tts {
 
@@ -293,8 +293,8 @@ int hifigan_load(tts_ctx *ctx, const char *path) {
   ModelReader rd{wf, ctx, "HiFi-GAN"};
   HostLayer h;
   auto conv = [&](const std::string &p, int cout, int cin, int k, HfgLayer &l) -> int {
-    const int e = rd.conv(p, cout, cin, k, h);
-    return e ? e : st->dev.up(ctx, h, l);
+    int e = rd.conv(p, cout, cin, k, h);
+    return e || (e = st->dev.up(ctx, h, l)) || cout % 32 ? e : st->dev.pack(ctx, rd.model, h.w, k, cin, cout, l); // conv_post (one channel) is no hfg_conv launch
   };
   if ((rc = conv("hifigan.conv_pre", HFG_C0, HFG_LAT, 7, st->pre))) return rc;
   // cond_layer stays [cout][cin]: a matrix-vector product per voice
@@ -313,7 +313,7 @@ int hifigan_load(tts_ctx *ctx, const char *path) {
         for (int ci = 0; ci < cin; ci++)
           for (int co = 0; co < cout; co++) r[(((size_t)ph * 2 + j) * cin + ci) * cout + co] = w->data[((size_t)ci * cout + co) * ku + k0 + (1 - j) * u];
     }
-    if ((rc = st->dev.up(ctx, r, &st->ups[i].w)) || (rc = st->dev.up(ctx, b->data, &st->ups[i].b))) return rc;
+    if ((rc = st->dev.up(ctx, r, &st->ups[i].w)) || (rc = st->dev.up(ctx, b->data, &st->ups[i].b)) || (rc = st->dev.pack(ctx, rd.model, r, 2 * u, cin, cout, st->ups[i]))) return rc;
     ch = cout;
     for (int j = 0; j < 3; j++)
       for (int n = 0; n < 3; n++) {
@@ -338,7 +338,7 @@ static int hifigan_run(tts_ctx *ctx, const char *who, const float *latents, cons
   HifiganState *st = ctx->hifigan;
   const bool chunk = frame0 != nullptr;
   if (!st) return fail(ctx, TTS_ERR_STATE, "tts_load_hifigan not called");
-  if (!latents || !rows || !voices || !audio_out || B < 1) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", who);
+  if (!latents || !rows || !voices || !audio_out || B < 1 || !hfg_precision_ok(ctx->hfg_precision)) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", who);
   if (n_voices < 1 || n_voices > (1 << 20)) return fail(ctx, TTS_ERR_ARG, "%s: %d voices", who, n_voices);
   if (B > HFG_MAX_CAND) return fail(ctx, TTS_ERR_LIMIT, "%s: %d candidates (at most %d per call)", who, B, HFG_MAX_CAND);
   std::vector<int> seq((size_t)HFG_SEQ * B, 0);
@@ -388,16 +388,16 @@ static int hifigan_run(tts_ctx *ctx, const char *who, const float *latents, cons
   float *z = st->z.as<float>(), *cb = st->cb.as<float>(), *x = st->x.as<float>(), *u = st->u.as<float>(), *t = st->t.as<float>(), *m = st->m.as<float>();
   hfg_interp_kernel<<<dim3(maxW, B), 256, 0, ctx->stream>>>(d_lat, d_seq, z);
   hfg_cond_kernel<<<dim3(HFG_C0 / 4, n_voices), 256, 0, ctx->stream>>>(st->cond.w, st->cond.b, d_voice, cb);
-  // Option "hfg_small_m": a chunked call runs a convolution on the small-M variant when its longest window has at most that many rows at the convolution's
-  // level and the output channels fill the four waves (0: never). The whole-utterance call keeps the 256-row tile.
-  const int small_rows = chunk ? ctx->hfg_small_m : 0;
+  // Option "hfg_small_m" (f32 mode): a chunked call runs a convolution on the small-M variant when its longest window has at most that many rows at its level and the output channels fill the four waves (0: never).
+  // Option "hfg_precision" 1 / 2: every convolution of the call runs on hfg_conv_h_kernel (fp16 / split-pair operands), one tile for every window: hfg_small_m is ignored.
+  const int prec = ctx->hfg_precision, small_rows = chunk && !prec ? ctx->hfg_small_m : 0;
   auto conv = [&](const float *in, float *out, const float *resid, const HfgLayer &l, int cin, int cout, int taps, int dil, int phases, int rate, float slope,
                   int acc_mode, const float *cbias) {
     HfgConv a{};
     a.in = in; a.out = out; a.resid = resid; a.w = l.w; a.bias = l.b; a.cbias = cbias; a.seq = d_seq;
     a.cin = cin; a.cout = cout; a.taps = taps; a.dil = dil; a.lo = -dil * (taps - 1) / 2; a.phases = phases; a.pad_t = phases / 2; a.rate = rate;
     a.slope = slope; a.acc_mode = acc_mode;
-    ProfScope ps(ctx, "hfg_conv", 2.0 * (double)wframes * rate * phases * taps * cin * cout);
+    ProfScope ps(ctx, "hfg_conv", 2.0 * (double)wframes * rate * phases * taps * cin * cout); if (prec) return hfg_conv_h_launch(ctx->stream, a, l.wh, l.wl, l.ws, prec == 2, (size_t)maxW * rate, B);
     if (cout % 128 == 0 && (int64_t)maxW * rate <= small_rows) {
       const dim3 grid((unsigned)(((size_t)maxW * rate + HFG_TS - 1) / HFG_TS), (unsigned)B, (unsigned)(cout / 128 * phases));
       hfg_conv_small_kernel<<<grid, 256, (size_t)(HFG_TS + (taps - 1) * dil) * 33 * 4, ctx->stream>>>(a);

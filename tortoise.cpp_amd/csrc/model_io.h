@@ -3,13 +3,17 @@
 //   DevWeights    those vectors on the device, owned by the model's state
 //   LevelTable    the per-level HFG_SEQ records of a ragged batch of clips
 //   ClipIngest    a batch of clips at any sample rate -> checked, uploaded and brought to the model's rate (classifier, aligner)
-// Included once, in hifigan.hip behind its kernels (HFG_SEQ is declared there); no kernel lives here.
+// Included once, in hifigan.hip behind its kernels (HFG_SEQ and hfg_pack_launch are declared there); no kernel lives here.
 #pragma once
 
 namespace tts {
 
 struct HostLayer { std::vector<float> w, b; };          // a repacked weight and its bias; a norm's gamma and beta; any pair of vectors
-struct HfgLayer { float *w = nullptr, *b = nullptr; }; // the same pair on the device
+struct HfgLayer {                                       // the same pair on the device
+  float *w = nullptr, *b = nullptr;
+  _Float16 *wh = nullptr, *wl = nullptr; // DevWeights::pack: w as fp16 hi + lo planes in MFMA-fragment order (hfg_conv_h.h); null on a layer no fp16 convolution reads
+  float *ws = nullptr;                   // [2][cout]: 1 / s and s, the power-of-two scale of every output channel
+};
 
 struct ModelReader {
   const WeightFile &wf;
@@ -102,6 +106,20 @@ struct DevWeights {
     return TTS_OK;
   }
   int up(tts_ctx *ctx, const HostLayer &s, HfgLayer &d) { int e = up(ctx, s.w, &d.w); return e ? e : up(ctx, s.b, &d.b); }
+  // The fp16 planes and scales of an uploaded convolution weight d.w = src [pt][cin][cout] (pt = phases x taps), built on the device beside it whatever
+  // "hfg_precision" says now: the option may be set after the load. A non-finite weight has no scale and no pair: the load fails.
+  int pack(tts_ctx *ctx, const char *model, const std::vector<float> &src, int pt, int cin, int cout, HfgLayer &d) {
+    for (size_t i = 0; i < src.size(); i++)
+      if (!std::isfinite(src[i])) return fail(ctx, TTS_ERR_FORMAT, "%s model file: a convolution weight is not finite (element %lld of a [%d][%d][%d] tensor)", model, (long long)i, pt, cin, cout);
+    void *p = nullptr;
+    TTS_HIP(ctx, hipMalloc(&p, src.size() * 4 + (size_t)cout * 8)); // hi | lo | scales: one allocation
+    owned.push_back(p);
+    d.wh = (_Float16 *)p; d.wl = d.wh + src.size(); d.ws = (float *)(d.wl + src.size());
+    hfg_pack_launch(ctx->stream, d.w, pt, cin, cout, d.wh, d.wl, d.ws);
+    TTS_HIP(ctx, hipGetLastError());
+    TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TTS_OK;
+  }
 };
 
 // The HFG_SEQ records of B clips on L levels, level by level: record (l, s) = {first row, rows, 0, first statistics tile, unit x the clip's first row on
