@@ -280,6 +280,30 @@ int tts_sample(tts_ctx *ctx, const float *logits, const int32_t *penalty_ids, in
 /* After a tts_ar_step_sample call the host copy of the logits is UNDEFINED: only the rows the sampler had to fetch in full were refreshed (the pinned buffer is shared),
  * the others still hold an earlier step's values. A caller that needs the logits uses tts_ar_step. Fails with TTS_ERR_STATE before tts_ar_begin. */
 int tts_ar_step_sample(tts_ctx *ctx, const int32_t *prev_ids, int step_i, unsigned flags, int32_t *samples_out);
+/* ---- the device sampler (additions within version 8) ----
+ * Option "ar_sampler": 0 (default) = the host sampler above over the context's std::mt19937, bit for bit what it was; 1 = the whole draw in one kernel per
+ *   row (csrc/ar.hip: sample_device_kernel): stop mask, penalty, x = logit / temperature, the top-k survivors (ties at the k-th value survive), softmax over
+ *   them with the maximum subtracted, an ascending cumulative sum in f32 (fixed order), top-p masks while it is <= 1 - top_p (never the last survivor), and
+ *   the first survivor whose renormalised cumulative sum reaches u. u = tts_host_ar_uniform(seed, rng_shard_offset + candidate, iteration) with the seed
+ *   tts_seed received: a candidate's ids depend on (seed, global candidate) alone, not on the batch, its position in it or its neighbours, and G ranks x B/G
+ *   candidates reproduce one rank x B. Read by tts_ar_step_sample, tts_autoregressive, tts_autoregressive_multi and tts_autoregressive_multi_voice; under
+ *   it the context's generator is never touched and the options "sampler_threads" and "device_topk" are not read. It is NOT the host sampler's id
+ *   sequence (another generator, the final draw over the ascending order). Not served: "ar_typical_mass" > 0 and "ar_top_k" > 512 (TTS_ERR_ARG from the
+ *   call that meets the combination); tts_ar_session_open and tts_hifigan_stream (TTS_ERR_STATE). A row with more than TTS_SD_MAX_SURVIVORS survivors
+ *   (all-equal logits) is never truncated: the call returns TTS_ERR_LIMIT.
+ * Option "ar_sync_steps" (integer 1 .. 64, default 1; read under ar_sampler = 1 by the tts_autoregressive* calls): decode steps enqueued between two waits
+ *   of the host. The tokens and the step counters stay on the device, so codes, rows, latents, steps and the stop status are identical for every value.
+ *   One step per wait whatever the option says while a stop schedule applies or several prompts run without TTS_AR_RETIRE.
+ * tts_sample_device: the kernel on caller-given rows logits [n][8194] under the context's controls and seed; row b is global candidate
+ *   rng_shard_offset + first_candidate + b at `iteration` and is penalised on penalty_ids[b][0 .. ids_per_cand) like tts_sample; flags: TTS_AR_MASK_STOP.
+ *   Every check runs before any device work: TTS_ERR_ARG (null pointer, n or ids_per_cand < 1, a negative iteration or candidate, an id outside the
+ *   vocabulary, another flag, the combinations above), then TTS_ERR_HIP on a host-only context; TTS_ERR_LIMIT for a degenerate row (samples_out untouched).
+ *   Needs no model. Profiler family "ar_sample" (work = bytes).
+ * tts_host_ar_uniform: the same u on the host, no GPU: Philox4x32-10, counter {0, iteration, candidate, 0x7718}, key = seed, (word 0 >> 8) * 2^-24. */
+#define TTS_SD_MAX_SURVIVORS 1024
+int tts_sample_device(tts_ctx *ctx, const float *logits, int n, const int32_t *penalty_ids, int ids_per_cand, int iteration, int first_candidate, unsigned flags,
+                      int32_t *samples_out);
+float tts_host_ar_uniform(uint64_t seed, uint32_t candidate, uint32_t iteration);
 int tts_ar_topk_fallbacks(const tts_ctx *ctx);
 /* The whole autoregressive() driver (main.cpp:5042-5367): prefill, sample/decode loop with the
  * reference's stop rule, apply_padding, latent pass, trim_latents.

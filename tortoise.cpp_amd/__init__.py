@@ -94,6 +94,7 @@ def lib():
         "tts_ar_begin": (ci, [vp, _i32p, ci, _f32p, ci, ci]), "tts_ar_prefill": (ci, [vp, _f32p]),
         "tts_ar_step": (ci, [vp, _i32p, ci, _f32p]), "tts_ar_latents": (ci, [vp, _i32p, ci, ci, _f32p]),
         "tts_sample": (ci, [vp, _f32p, _i32p, ci, ci, _i32p]),
+        "tts_sample_device": (ci, [vp, vp, ci, vp, ci, ci, ci, C.c_uint, vp]), "tts_host_ar_uniform": (cf, [C.c_uint64, C.c_uint32, C.c_uint32]),
         "tts_ar_step_sample": (ci, [vp, _i32p, ci, C.c_uint, _i32p]), "tts_ar_topk_fallbacks": (ci, [vp]), "tts_diffusion_time_mlp_retries": (ci, [vp]), "tts_diffusion_fp16_check": (ci, [vp, C.POINTER(C.c_int64)]),
         "tts_device_numa_node": (ci, [vp, C.c_char_p, ci]), "tts_pin_to_device_numa_node": (ci, [vp]),
         "tts_host_sample_row": (ci, [_f32p, _i32p, ci, cf]), "tts_host_sample_prefiltered": (ci, [_f32p, _i32p, ci, cf, ci]),
@@ -316,6 +317,16 @@ class Engine:
         ids = np.ascontiguousarray(penalty_ids, np.int32).reshape(logits.shape[0], -1)
         out = np.empty(logits.shape[0], np.int32)
         self._ck(self.L.tts_sample(self.h, logits.reshape(-1), ids.reshape(-1), ids.shape[1], logits.shape[0], out))
+        return out
+
+    def sample_device(self, logits, penalty_ids, iteration, first_candidate=0, mask_stop=False):
+        """tts_sample_device: the device sampler's kernel on the rows logits [n, 8194] under the context's controls and seed; row b is global candidate
+        rng_shard_offset + first_candidate + b at `iteration`, penalised on penalty_ids[b]."""
+        logits = np.ascontiguousarray(logits, np.float32).reshape(-1, VOCAB_MEL)
+        ids = np.ascontiguousarray(penalty_ids, np.int32).reshape(logits.shape[0], -1)
+        out = np.empty(logits.shape[0], np.int32)
+        self._ck(self.L.tts_sample_device(self.h, _ptr(logits), logits.shape[0], _ptr(ids), ids.shape[1], int(iteration), int(first_candidate),
+                                          AR_MASK_STOP if mask_stop else 0, _ptr(out)))
         return out
 
     def set_stop_schedule(self, stop_at=None):
@@ -1088,6 +1099,11 @@ class Engine:
 
 
 HOST_SCHED_KEYS = ["max_log", "min_log", "cfk", "sqrt_recip", "sqrt_recipm1", "coef1", "coef2"]
+
+
+def host_ar_uniform(seed, candidate, iteration):
+    """The device sampler's uniform for (seed, global candidate, iteration), on the host: a multiple of 2^-24 in [0, 1)."""
+    return float(lib().tts_host_ar_uniform(int(seed), int(candidate), int(iteration)))
 
 
 def host_schedule(n_steps):

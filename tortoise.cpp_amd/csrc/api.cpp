@@ -240,6 +240,11 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     if (const char *e = ar_control_error(which, value)) return fail(c, TTS_ERR_ARG, "%s", e);
     ar_control_store(which, value, c->ar_sp, c->ar_penalty_scope);
   }
+  else if (k == "ar_sampler" || k == "ar_sync_steps") { // additions within version 8: the device sampler (read by tts_ar_step_sample and the tts_autoregressive* drivers)
+    const int which = k == "ar_sync_steps";
+    if (const char *e = ar_sampler_option_error(which, value)) return fail(c, TTS_ERR_ARG, "%s", e);
+    (which ? c->ar_sync_steps : c->ar_sampler) = (int)value;
+  }
   else if (k == "hfg_small_m") { // addition within version 8: tile selection of tts_hifigan_chunk, same bits either way
     if (!(value >= 0 && value <= (1 << 24)) || value != std::floor(value)) return fail(c, TTS_ERR_ARG, "hfg_small_m: a row count in 0 .. 2^24 (0 = never)");
     c->hfg_small_m = (int)value;
@@ -741,6 +746,18 @@ int tts_sample(tts_ctx *c, const float *logits, const int32_t *ids, int ids_per_
   if (int rc = shard_check(c, B)) return rc;
   return guarded(c, [&] { sample_candidates(c, c->generator, c->ar_sp, logits, ids, ids_per_cand, B, out); return (int)TTS_OK; });
 }
+// The device twin of tts_sample (ar.hip: sample_device_kernel): every check before any device work.
+int tts_sample_device(tts_ctx *c, const float *logits, int n, const int32_t *ids, int ids_per_cand, int iteration, int first_candidate, unsigned flags, int32_t *out) {
+  if (!c || !logits || !ids || !out || n < 1 || ids_per_cand < 1 || iteration < 0 || first_candidate < 0 || (flags & ~(unsigned)TTS_AR_MASK_STOP)) return TTS_ERR_ARG;
+  if (n > (1 << 24) || first_candidate > (1 << 24)) return fail(c, TTS_ERR_LIMIT, "tts_sample_device: more than 2^24 candidates");
+  for (size_t i = 0; i < (size_t)n * ids_per_cand; i++)
+    if (ids[i] < 0 || ids[i] >= TTS_VOCAB_MEL) return fail(c, TTS_ERR_ARG, "penalty id out of range");
+  if (const char *e = ar_device_sampler_refusal(c->ar_sp)) return fail(c, TTS_ERR_ARG, "tts_sample_device: %s", e);
+  if (int rc = shard_check(c, first_candidate + n)) return rc;
+  NEED_CTX(c);
+  return guarded(c, [&] { return ar_sample_device_rows(c, logits, n, ids, ids_per_cand, iteration, first_candidate, flags, out); });
+}
+float tts_host_ar_uniform(uint64_t seed, uint32_t candidate, uint32_t iteration) { return ar_sample_uniform(seed, candidate, iteration); }
 
 // The decode loop behind the calls below: ar_driver.cpp.
 int tts_autoregressive(tts_ctx *c, const int32_t *text_ids, int n_text, const float *voice, int B, int max_steps,
@@ -757,6 +774,7 @@ int tts_hifigan_stream(tts_ctx *c, const int32_t *text_ids, int n_text, const fl
   NEED_CTX(c);
   NO_SESSION(c, "tts_hifigan_stream");
   if (stride_codes < 1 || !cb) return fail(c, TTS_ERR_ARG, "tts_hifigan_stream: bad argument (stride_codes %d: >= 1, a callback)", stride_codes);
+  if (c->ar_sampler) return fail(c, TTS_ERR_STATE, "tts_hifigan_stream: streaming runs on the host sampler (set ar_sampler to 0)");
   if (!c->ar) return fail(c, TTS_ERR_STATE, "AR model not loaded");
   if (!c->hifigan) return fail(c, TTS_ERR_STATE, "tts_load_hifigan not called");
   if (voice)
@@ -872,6 +890,7 @@ int tts_ar_session_close(tts_ctx *c) {
 int tts_ar_session_open(tts_ctx *c, int n_slots, int max_cand, int max_text, int max_steps, unsigned flags) {
   NEED_CTX(c);
   if (!c->ar) return fail(c, TTS_ERR_STATE, "AR model not loaded");
+  if (c->ar_sampler) return fail(c, TTS_ERR_STATE, "tts_ar_session_open: sessions run on the host sampler (set ar_sampler to 0)");
   if (n_slots < 1 || max_cand < 1 || max_cand > n_slots || max_text < 1 || max_steps < 1 ||
       (flags & ~(unsigned)(TTS_AR_MASK_STOP | TTS_AR_RETIRE | TTS_AR_ROW_CONTROLS)))
     return fail(c, TTS_ERR_ARG, "tts_ar_session_open: bad argument (n_slots %d: >= 1, max_cand %d: 1 .. n_slots, max_text %d, max_steps %d: >= 1, flags %u)", n_slots,

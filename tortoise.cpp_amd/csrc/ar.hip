@@ -1597,6 +1597,197 @@ __global__ void hist_mark_kernel(const int32_t *__restrict__ toks, int B, uint32
   hist[(size_t)c * TTS_HIST_WORDS + (tok >> 5)] |= 1u << (tok & 31); // one thread per candidate: its own row
 }
 
+// ---------------------------------------------------------------------------------------------
+// The device sampler (option "ar_sampler" = 1): one launch takes a row from its f32 logits to its next code, with no list and no host stage. One workgroup
+// of 256 threads per row; DESIGN.md "What pins the device sampler" derives the error bound of the sums below.
+//   1. 33 logits per thread as pf_key keys of x = pf_value<true>(...) / temp (stop mask, penalty, then a correctly rounded f32 division). The penalty set
+//      is the row's bitmap (iteration 0 and scope 1: pf_history_mask) or the one token the step was fed (scope 0: pf_token_mask).
+//   2. The k-th largest key, built bit by bit from the top (<= 32 ballot-popcount probes, one barrier each; a probe that counts exactly k ends the search):
+//      every x >= it survives, ties included. n survivors; n > TTS_SD_MAX_SURVIVORS (an all-equal row) sets the row's error word and writes no token.
+//   3. Index-ordered compaction of (x, index) into LDS, as the prefilter's.
+//   4. Rank pass: survivor e counts the survivors below it in (x, index) order and scatters itself to that place. Every lane of a wave reads the SAME
+//      sx[q] in the same cycle (an LDS broadcast: no bank conflict); the scatter's addresses are a permutation.
+//   5. Thread t owns the ascending survivors [4 t, 4 t + 4): e = expf(x - max), its running sum, then an inclusive Kogge-Stone scan over the wave
+//      (__shfl_up, 6 steps), the four wave totals through LDS, added in wave order. c_r = (wave offset + lanes below) + running sum: THE fixed order,
+//      no atomics; a c_r is a tree of at most 13 f32 additions of non-negative terms. Z = ((w0 + w1) + w2) + w3. All four waves work in the tail (at the usual
+//      n ~ 50 only the first 13 lanes of wave 0 hold a survivor; one wave with 16 per lane would serialise the rank pass of a 1024-survivor row).
+//   6. Top-p: r is masked while (double)(c_r / Z) <= 1 - top_p; m = the first r that is not, at most n - 1 (the last survivor is never masked). Skipped
+//      when 1 - top_p <= 0. base = c_{m-1} (0 for m = 0).
+//   7. u = ar_sample_uniform(seed, global candidate, iteration); the draw is the first r >= m with c_r >= base + u (Z - base) (the renormalised cumulative
+//      sum reaching u, without the division), n - 1 if rounding leaves none.
+// Outputs: the token into tok[row] (what the next step's embed kernel reads), {token, error word} into ring slot `slot` (pinned host memory). retire: a row
+// whose ended flag is set writes 8193 and does nothing else; a row that draws 8193 sets it.
+// ---------------------------------------------------------------------------------------------
+struct SdCtl { // the controls of one call / one decode loop, in device memory: the step graph bakes none of them
+  double cut;  // 1 - (double)top_p (SamplerParams::top_p_cut)
+  float temp, penalty;
+  int top_k, mask_stop, scope, retire;
+  uint32_t seed_lo, seed_hi, cand0, pad;
+};
+struct SdArgs {
+  const float *logits;  // [rows][V]
+  const int *src_row;   // row r samples from logits row src_row[r] (iteration 0: its group's prompt row), or null: r
+  const SdCtl *ctl;
+  int32_t *tok;         // [B] the tokens the step was fed (tok_in) and is fed next; null: no token buffer (tts_sample_device)
+  uint32_t *hist;       // [B][TTS_HIST_WORDS] the rows' penalty bitmaps
+  int32_t *ended;       // [B] or null
+  int2 *ring;           // {token, error word}: slot s holds B entries
+  const int *step;      // the device step counter, or null. slot = *step + 1, iteration = iter0 + slot (null: slot 0)
+  int iter0, B;
+  int tok_in;           // tok[r] was fed to this step: it is scope 0's penalty set and joins the row's bitmap under scope 1; 0: the bitmap alone
+};
+
+__device__ __forceinline__ int sd_block_min(int v, int (*wm)[4], int buf, int lane, int wave) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v = min(v, __shfl_xor(v, o));
+  if (lane == 0) wm[buf][wave] = v;
+  __syncthreads();
+  return min(min(wm[buf][0], wm[buf][1]), min(wm[buf][2], wm[buf][3]));
+}
+
+__global__ __launch_bounds__(256) void sample_device_kernel(SdArgs a) {
+  constexpr int NJ = (V + 255) / 256, CAP = TTS_SD_MAX_SURVIVORS, PER = CAP / 256;
+  __shared__ int red[2][4];
+  __shared__ int4 tab[NJ];
+  __shared__ float sx[CAP], ax[CAP]; // survivors in index order (later: the cumulative sums c_r); in ascending (x, index) order
+  __shared__ int si[CAP], ai[CAP];
+  __shared__ float wsum[4];
+  __shared__ int wm[2][4];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const SdCtl c = *a.ctl;
+  const int slot = a.step ? *a.step + 1 : 0;
+  int2 *out = a.ring + (size_t)slot * a.B + r;
+  if (a.ended && c.retire && a.ended[r]) { // workgroup-uniform
+    if (tid == 0) { a.tok[r] = 8193; *out = make_int2(8193, 0); }
+    return;
+  }
+  const int tok = a.tok_in ? a.tok[r] : -1; // 0 <= tok < V: the kernel's own output, or checked by the host
+  unsigned long long penm;
+  if (!a.tok_in || c.scope) {
+    uint32_t *hc = a.hist + (size_t)r * TTS_HIST_WORDS;
+    if (a.tok_in && tid == 0) hc[tok >> 5] |= 1u << (tok & 31); // one workgroup per row, one writer
+    penm = pf_history_mask(hc, tok, tid);
+  } else penm = pf_token_mask(tok, tid);
+  const float *src = a.logits + (size_t)(a.src_row ? a.src_row[r] : r) * V;
+  unsigned key[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const int i = j * 256 + tid;
+    key[j] = i < V ? pf_key(__fdiv_rn(pf_value<true>(src, i, c.mask_stop, (penm >> j) & 1ull, c.penalty), c.temp)) : 0u; // padding: below every probe
+  }
+  // the k-th largest key: the largest t with count(key >= t) >= k
+  unsigned t = 0u;
+  int n = 0, it = 0;
+  for (int b = 31; b >= 0; b--) {
+    const unsigned cand = t | (1u << b);
+    int cw = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; j++) cw += __popcll(__ballot(key[j] >= cand));
+    if (lane == 0) red[it & 1][wave] = cw;
+    __syncthreads(); // double-buffered: one barrier per probe
+    const int cnt = red[it & 1][0] + red[it & 1][1] + red[it & 1][2] + red[it & 1][3];
+    it++;
+    if (cnt >= c.top_k) { t = cand; n = cnt; if (cnt == c.top_k) break; } // exactly k at or above cand: nothing lies between cand and the k-th key
+  }
+  if (n < 1 || n > CAP) { // a degenerate row (or one of NaNs): never truncated, no token
+    if (tid == 0) *out = make_int2(-1, 1);
+    return;
+  }
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const int cw = __popcll(__ballot(key[j] >= t));
+    if (lane == 0) ((int *)&tab[j])[wave] = cw;
+  }
+  __syncthreads();
+  int pos0 = 0;
+#pragma unroll
+  for (int j = 0; j < NJ; j++) {
+    const int4 w = tab[j];
+    const unsigned long long m = __ballot(key[j] >= t);
+    if (key[j] >= t) {
+      const int pos = pos0 + (wave > 0 ? w.x : 0) + (wave > 1 ? w.y : 0) + (wave > 2 ? w.z : 0) + __popcll(m & below);
+      sx[pos] = pf_unkey(key[j]);
+      si[pos] = j * 256 + tid;
+    }
+    pos0 += w.x + w.y + w.z + w.w;
+  }
+  __syncthreads();
+  for (int e = tid; e < n; e += 256) { // rank pass
+    const float x = sx[e];
+    int rk = 0;
+    for (int q = 0; q < n; q++) {
+      const float y = sx[q];
+      rk += (y < x || (y == x && q < e)) ? 1 : 0;
+    }
+    ax[rk] = x;
+    ai[rk] = si[e];
+  }
+  __syncthreads();
+  const float mx = ax[n - 1];
+  float run[PER];
+  float acc = 0.f;
+#pragma unroll
+  for (int k = 0; k < PER; k++) {
+    const int idx = PER * tid + k;
+    acc = __fadd_rn(acc, idx < n ? expf(__fsub_rn(ax[idx], mx)) : 0.f);
+    run[k] = acc;
+  }
+  float incl = acc;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float y = __shfl_up(incl, o);
+    if (lane >= o) incl = __fadd_rn(incl, y);
+  }
+  float excl = __shfl_up(incl, 1);
+  if (lane == 0) excl = 0.f;
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  const float w0 = wsum[0], w01 = __fadd_rn(w0, wsum[1]), w012 = __fadd_rn(w01, wsum[2]), Z = __fadd_rn(w012, wsum[3]);
+  const float off = __fadd_rn(wave == 0 ? 0.f : wave == 1 ? w0 : wave == 2 ? w01 : w012, excl);
+  int first_open = n - 1; // the first r that top-p does not mask
+#pragma unroll
+  for (int k = PER - 1; k >= 0; k--) {
+    const int idx = PER * tid + k;
+    const float cr = __fadd_rn(off, run[k]);
+    run[k] = cr;
+    if (idx < n) {
+      sx[idx] = cr;
+      if (!(c.cut > 0.0 && (double)__fdiv_rn(cr, Z) <= c.cut)) first_open = min(first_open, idx);
+    }
+  }
+  const int m = sd_block_min(first_open, wm, 0, lane, wave); // (its barrier also publishes sx)
+  const float base = m > 0 ? sx[m - 1] : 0.f;
+  const float u = ar_sample_uniform((uint64_t)c.seed_lo | ((uint64_t)c.seed_hi << 32), c.cand0 + (uint32_t)r, (uint32_t)(a.iter0 + slot));
+  const float target = __fadd_rn(base, __fmul_rn(u, __fsub_rn(Z, base)));
+  int first_hit = n - 1;
+#pragma unroll
+  for (int k = PER - 1; k >= 0; k--) {
+    const int idx = PER * tid + k;
+    if (idx < n && idx >= m && run[k] >= target) first_hit = min(first_hit, idx);
+  }
+  const int pick = sd_block_min(first_hit, wm, 1, lane, wave);
+  if (tid == 0) {
+    const int id = ai[pick];
+    if (a.tok) a.tok[r] = id;
+    if (a.ended && c.retire && id == 8193) a.ended[r] = 1;
+    *out = make_int2(id, 0);
+  }
+}
+
+// The decode step's first and last kernels under the device sampler: the tokens come from the buffer sample_device_kernel wrote, the counters from the
+// device step counter (decode step s: n_past = n_past0 + s, mel position s + 2), which the graph's last node advances: the diffusion step graph's device-side
+// step counter, applied to the AR stage. Nothing of a step crosses to the host but the ring's entries.
+__global__ __launch_bounds__(256) void embed_dev_kernel(const float *__restrict__ mel_emb, const float *__restrict__ mel_pos, const int *__restrict__ tok,
+                                                        const int *__restrict__ step, int n_past0, StepState *__restrict__ ss_out, float *__restrict__ h4) {
+  const int r = blockIdx.x, s = *step, pos_id = s + 2;
+  if (r == 0 && threadIdx.x == 0) { ss_out->n_past = n_past0 + s; ss_out->pos_id = pos_id; }
+  const float4 a = ((const float4 *)(mel_emb + (size_t)tok[r] * D))[threadIdx.x];
+  const float4 b = ((const float4 *)(mel_pos + (size_t)pos_id * D))[threadIdx.x];
+  *(float4 *)(h4 + h4_index(r, 4 * threadIdx.x)) = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+__global__ void step_advance_kernel(int *__restrict__ step) { *step += 1; }
+
 
 struct ArLayerDev {
   float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
@@ -1672,8 +1863,12 @@ struct ArState {
   float step_mass = 0.f;                        // and the typical mass (0: the prefilter kernels of before)
   // one captured step per mode (a caller alternating tts_ar_step / tts_ar_step_sample, or bench's device_topk on/off loop, re-instantiated
   // the ~150-node graph on every switch)
-  hipGraph_t graphs[5] = {};         // [3]: the session step (one mode per session; kept across sessions of the same shape); [4]: a rows session's step
-  hipGraphExec_t graph_execs[5] = {};
+  // The device sampler (option "ar_sampler" = 1, step_mode 3): its step has graph slot 5, so switching the option keeps the other slots' graphs.
+  DevBuf sd_state;           // int [tokens[B] | ended[B] | step counter]
+  DevBuf sd_ctl, sd_map;     // SdCtl; iteration 0: the logits row of every candidate (its group's prompt row)
+  PinnedBuf sd_ring;         // int2 [iterations][B] {token, error word}, written by sample_device_kernel
+  hipGraph_t graphs[6] = {};         // [3]: the session step (one mode per session; kept across sessions of the same shape); [4]: a rows session's step; [5]: the device sampler's step
+  hipGraphExec_t graph_execs[6] = {};
   int graph_captures = 0; // decode-step graphs captured since the model was loaded (tts_ar_graph_captures)
   // everything the captured step bakes into its nodes: the graph of the previous utterance is replayed when nothing moved
   struct GraphSig {
@@ -1687,10 +1882,16 @@ struct ArState {
       return B == o.B && max_pos == o.max_pos && lut == o.lut && wmode == o.wmode && mode == o.mode && multi == o.multi && rows == o.rows && scope == o.scope &&
              pf_min == o.pf_min && penalty == o.penalty && mass == o.mass && std::equal(p, p + 14, o.p);
     }
-  } graph_sigs[5];
+  } graph_sigs[6];
   GraphSig current_sig(int lut, int wmode) const {
     GraphSig g;
     g.B = B; g.max_pos = max_pos; g.lut = lut; g.wmode = wmode; g.mode = step_mode; g.multi = session ? 2 : multi;
+    if (step_mode == 3) { // the device sampler's step: the controls are read from sd_ctl, the nodes bake pointers and the prompt length only
+      g.pf_min = multi ? 0 : P;
+      const void *q[14] = {h.p, qkv.p, att.p, ff.p, kcache.p, vcache.p, d_toks.p, logits.p, sd_state.p, sd_ctl.p, sd_ring.p, multi ? row_off.p : nullptr, hist.p, nullptr};
+      std::copy(q, q + 14, g.p);
+      return g;
+    }
     const bool rw = session && rows;
     g.rows = rw;
     g.scope = rw ? 0 : step_scope; g.pf_min = (step_mode && !rw) ? step_pf_min : 0; g.mass = (step_mode && !rw) ? step_mass : 0.f;
@@ -1706,7 +1907,7 @@ struct ArState {
     graph_execs[m] = nullptr; graphs[m] = nullptr;
   }
   ~ArState() {
-    for (int m = 0; m < 5; m++) drop_graph(m);
+    for (int m = 0; m < 6; m++) drop_graph(m);
     if (h_toks) (void)hipHostFree(h_toks);
     if (h_logits) (void)hipHostFree(h_logits);
     if (h_pf) (void)hipHostFree(h_pf);
@@ -2432,7 +2633,10 @@ static int enqueue_decode_step(tts_ctx *ctx, ArState *st) {
   const double wb = wm == 2 ? 1.0 : wm == 1 ? 2.0 : 4.0;
   const bool ro_k = st->multi || st->session; // several prompts: the rows' context offsets (n_past = step index + row_off[row]); a session: the rows' context lengths
   const int *ro = ro_k ? st->row_off.as<int>() : nullptr;
-  if (st->session)
+  int *sd = st->sd_state.as<int>(); // step_mode 3: [tokens[B] | ended[B] | step counter]
+  if (st->step_mode == 3)
+    embed_dev_kernel<<<B, 256, 0, ctx->stream>>>(st->mel_emb, st->mel_pos, sd, sd + 2 * B, st->multi ? 0 : st->P, (StepState *)(st->d_toks.as<int>() + B), h);
+  else if (st->session)
     embed_session_kernel<<<B, 256, 0, ctx->stream>>>(st->mel_emb, st->mel_pos, st->h_toks, B, tiles * 16, (StepState *)(st->d_toks.as<int>() + B), st->row_off.as<int>(), h);
   else
     embed_step_kernel<<<B, 256, 0, ctx->stream>>>(st->mel_emb, st->mel_pos, st->h_toks, B, (StepState *)(st->d_toks.as<int>() + B), h);
@@ -2474,7 +2678,12 @@ static int enqueue_decode_step(tts_ctx *ctx, ArState *st) {
     else if (wm == 1) dec_ln_gemv_kernel<DEC_LOGITS, 2, false, true><<<dim3(VPAD / 16, tiles), 256, 0, ctx->stream>>>(a);
     else DEC_LN_LAUNCH(DEC_LOGITS, dim3(VPAD / 16, tiles), true); }
   const bool rows = st->session && st->rows; // per-row controls: the history sets are kept for every row, the prefilter reads the control table
-  if (st->step_mode == 0) {
+  if (st->step_mode == 3) { // the device sampler: the next tokens stay on the device, the ring's entries go to pinned memory; the last node advances the counter
+    { ProfScope ps(ctx, "ar_sample", (double)B * V * 4.0);
+      sample_device_kernel<<<B, 256, 0, ctx->stream>>>(SdArgs{st->logits.as<float>(), nullptr, st->sd_ctl.as<SdCtl>(), sd, st->hist.as<uint32_t>(), sd + B,
+                                                              st->sd_ring.as<int2>(), sd + 2 * B, 0, B, 1}); }
+    step_advance_kernel<<<1, 1, 0, ctx->stream>>>(sd + 2 * B);
+  } else if (st->step_mode == 0) {
     if (st->step_scope || rows) hist_mark_kernel<<<(B + 255) / 256, 256, 0, ctx->stream>>>(st->h_toks, B, st->hist.as<uint32_t>()); // the one node scope 1 adds
     TTS_HIP(ctx, hipMemcpyAsync(st->h_logits, st->logits.p, (size_t)B * V * 4, hipMemcpyDeviceToHost, ctx->stream));
   } else { // the sampler's top-k prefilter on the device: 16 KB instead of 524 KB back to the host per step of 16 candidates
@@ -2587,6 +2796,139 @@ const float *ar_fetch_logits_row(tts_ctx *ctx, int c) {
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return nullptr;
   if (st->step_mode == 2) dst[V - 1] = -1e30f;
   return dst;
+}
+
+// ---- the device sampler's host side (option "ar_sampler" = 1) ----
+static SdCtl sd_controls(const tts_ctx *ctx, unsigned flags, int first_candidate) {
+  SdCtl c{};
+  c.cut = ctx->ar_sp.top_p_cut(); c.temp = ctx->ar_sp.temp; c.penalty = ctx->ar_sp.penalty; c.top_k = ctx->ar_sp.top_k;
+  c.mask_stop = (flags & TTS_AR_MASK_STOP) != 0; c.scope = ctx->ar_penalty_scope; c.retire = (flags & TTS_AR_RETIRE) != 0;
+  c.seed_lo = ctx->seed_value; c.seed_hi = 0u; // the seed tts_seed received
+  c.cand0 = (uint32_t)(shard_base(ctx) + first_candidate);
+  return c;
+}
+// What every step on the device sampler needs before it is enqueued: the option checks of ar_step, the buffers the graph's nodes name, the controls.
+// state: the [tokens | ended | step counter] block the step starts from.
+static int sd_prepare(tts_ctx *ctx, ArState *st, unsigned flags, int iters, const std::vector<int> &state) {
+  const int B = st->B;
+  if (ctx->ar_weights != 0 && ctx->ar_weights != st->loaded_wmode)
+    return fail(ctx, TTS_ERR_STATE, "option ar_weights = %d must be set before tts_load_ar (the fp16 / fp8 slabs are packed at load)", ctx->ar_weights);
+  TTS_HIP(ctx, st->sd_state.reserve(((size_t)2 * B + 1) * 4));
+  TTS_HIP(ctx, st->sd_ctl.reserve(sizeof(SdCtl)));
+  TTS_HIP(ctx, st->sd_ring.reserve((size_t)iters * B * sizeof(int2)));
+  TTS_HIP(ctx, st->hist.reserve(st->hist_host.size() * 4));
+  const SdCtl c = sd_controls(ctx, flags, 0);
+  TTS_HIP(ctx, hipMemcpy(st->sd_ctl.p, &c, sizeof c, hipMemcpyHostToDevice));
+  TTS_HIP(ctx, hipMemcpy(st->sd_state.p, state.data(), state.size() * 4, hipMemcpyHostToDevice));
+  st->step_mode = 3;
+  return TTS_OK;
+}
+
+int ar_dev_begin(tts_ctx *ctx, unsigned flags, int max_iters) {
+  ArState *st = ctx->ar;
+  if (!st || st->B == 0 || !st->prefill_done) return fail(ctx, TTS_ERR_STATE, "tts_ar_begin / tts_ar_prefill not called");
+  const int B = st->B;
+  CHECK(sd_prepare(ctx, st, flags, max_iters, std::vector<int>((size_t)2 * B + 1, 0)));
+  // the history sets as the begin left them ({1, 8192}: iteration 0's penalty set in either scope); the device extends them under scope 1, the host copy stays behind
+  TTS_HIP(ctx, hipMemcpy(st->hist.p, st->hist_host.data(), st->hist_host.size() * 4, hipMemcpyHostToDevice));
+  st->hist_dev_valid = false;
+  std::vector<int> map((size_t)B);
+  for (size_t g = 0; g < st->g_n.size(); g++)
+    for (int k = 0; k < st->g_n[g]; k++) map[(size_t)st->g_c0[g] + k] = st->g_c0[g];
+  TTS_HIP(ctx, st->sd_map.reserve((size_t)B * 4));
+  TTS_HIP(ctx, hipMemcpy(st->sd_map.p, map.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+  return TTS_OK;
+}
+
+int ar_dev_sample_prompt(tts_ctx *ctx) {
+  ArState *st = ctx->ar;
+  const int B = st->B;
+  int *sd = st->sd_state.as<int>();
+  ProfScope ps(ctx, "ar_sample", (double)B * V * 4.0);
+  sample_device_kernel<<<B, 256, 0, ctx->stream>>>(SdArgs{st->logits.as<float>(), st->sd_map.as<int>(), st->sd_ctl.as<SdCtl>(), sd, st->hist.as<uint32_t>(), sd + B,
+                                                          st->sd_ring.as<int2>(), nullptr, 0, B, 0});
+  TTS_HIP(ctx, hipGetLastError());
+  return TTS_OK;
+}
+
+int ar_dev_enqueue_steps(tts_ctx *ctx, int first_step, int n) {
+  ArState *st = ctx->ar;
+  if (first_step < 0 || n < 1 || st->P + first_step + n - 1 >= st->max_pos || (size_t)(first_step + n + 1) * st->B * sizeof(int2) > st->sd_ring.cap)
+    return fail(ctx, TTS_ERR_LIMIT, "steps [%d, %d) beyond the KV cache", first_step, first_step + n);
+  for (int s = first_step; s < first_step + n; s++) {
+    const double step_bytes = (ctx->ar_weights == 2 ? 1.0 : ctx->ar_weights == 1 ? 2.0 : 4.0) * ((double)st->n_layers * 12.0 * D * D + (double)D * V) +
+                              (double)st->B * st->n_layers * 2.0 * (st->P + s + 1) * D * 2.0 + (double)st->B * V * 4.0;
+    CHECK(launch_step(ctx, st, 5, step_bytes));
+  }
+  return TTS_OK;
+}
+
+int ar_dev_wait(tts_ctx *ctx) {
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return TTS_OK;
+}
+
+const int32_t *ar_dev_ring(const tts_ctx *ctx) { return ctx->ar ? ctx->ar->sd_ring.as<int32_t>() : nullptr; }
+
+int ar_dev_feed(tts_ctx *ctx, const int32_t *toks) { // (the stream is idle: the driver has waited)
+  ArState *st = ctx->ar;
+  TTS_HIP(ctx, hipMemcpy(st->sd_state.p, toks, (size_t)st->B * 4, hipMemcpyHostToDevice));
+  return TTS_OK;
+}
+
+int ar_dev_step_sample(tts_ctx *ctx, const int32_t *prev, int step_i, unsigned flags, int32_t *out) {
+  ArState *st = ctx->ar;
+  if (!st || st->B == 0) return fail(ctx, TTS_ERR_STATE, "tts_ar_begin not called");
+  const int B = st->B;
+  if (step_i < 0 || st->P + step_i >= st->max_pos) return fail(ctx, TTS_ERR_LIMIT, "step %d beyond the KV cache", step_i);
+  for (int c = 0; c < B; c++)
+    if (prev[c] < 0 || prev[c] >= V) return fail(ctx, TTS_ERR_ARG, "mel token %d out of range", prev[c]);
+  std::vector<int> state((size_t)2 * B + 1, 0);
+  std::copy(prev, prev + B, state.begin());
+  state[(size_t)2 * B] = step_i;
+  CHECK(sd_prepare(ctx, st, flags & TTS_AR_MASK_STOP, st->max_pos - st->P + 1, state));
+  if (ctx->ar_penalty_scope && !st->hist_dev_valid) // as ar_step: before this step's ids join the host copy, the kernel adds them on the device
+    TTS_HIP(ctx, hipMemcpy(st->hist.p, st->hist_host.data(), st->hist_host.size() * 4, hipMemcpyHostToDevice));
+  st->hist_dev_valid = ctx->ar_penalty_scope != 0;
+  for (int c = 0; c < B; c++) st->hist_host[(size_t)c * TTS_HIST_WORDS + (prev[c] >> 5)] |= 1u << (prev[c] & 31);
+  CHECK(ar_dev_enqueue_steps(ctx, step_i, 1));
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const int2 *e = st->sd_ring.as<int2>() + (size_t)(step_i + 1) * B;
+  for (int c = 0; c < B; c++) {
+    if (e[c].y) return fail(ctx, TTS_ERR_LIMIT, "tts_ar_step_sample: candidate %d has more than %d survivors (a degenerate row)", c, TTS_SD_MAX_SURVIVORS);
+    out[c] = e[c].x;
+  }
+  return TTS_OK;
+}
+
+int ar_sample_device_rows(tts_ctx *ctx, const float *logits, int n, const int32_t *ids, int ids_per_cand, int iteration, int first_candidate, unsigned flags,
+                          int32_t *out) {
+  DevBuf d_logits, d_hist, d_ctl, d_out;
+  TTS_HIP(ctx, d_logits.reserve((size_t)n * V * 4));
+  TTS_HIP(ctx, d_hist.reserve((size_t)n * TTS_HIST_WORDS * 4));
+  TTS_HIP(ctx, d_ctl.reserve(sizeof(SdCtl)));
+  TTS_HIP(ctx, d_out.reserve((size_t)n * sizeof(int2)));
+  std::vector<uint32_t> hist((size_t)n * TTS_HIST_WORDS, 0u); // the ids it is given, as the bitmaps the kernel reads
+  for (int b = 0; b < n; b++)
+    for (int k = 0; k < ids_per_cand; k++) {
+      const int id = ids[(size_t)b * ids_per_cand + k];
+      hist[(size_t)b * TTS_HIST_WORDS + (id >> 5)] |= 1u << (id & 31);
+    }
+  SdCtl c = sd_controls(ctx, flags & TTS_AR_MASK_STOP, first_candidate);
+  TTS_HIP(ctx, hipMemcpy(d_logits.p, logits, (size_t)n * V * 4, hipMemcpyHostToDevice));
+  TTS_HIP(ctx, hipMemcpy(d_hist.p, hist.data(), hist.size() * 4, hipMemcpyHostToDevice));
+  TTS_HIP(ctx, hipMemcpy(d_ctl.p, &c, sizeof c, hipMemcpyHostToDevice));
+  { ProfScope ps(ctx, "ar_sample", (double)n * V * 4.0);
+    sample_device_kernel<<<n, 256, 0, ctx->stream>>>(SdArgs{d_logits.as<float>(), nullptr, d_ctl.as<SdCtl>(), nullptr, d_hist.as<uint32_t>(), nullptr, d_out.as<int2>(),
+                                                            nullptr, iteration, n, 0}); }
+  TTS_HIP(ctx, hipGetLastError());
+  TTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<int2> res((size_t)n);
+  TTS_HIP(ctx, hipMemcpy(res.data(), d_out.p, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
+  for (int b = 0; b < n; b++)
+    if (res[b].y) return fail(ctx, TTS_ERR_LIMIT, "tts_sample_device: row %d has more than %d survivors (a degenerate row)", b, TTS_SD_MAX_SURVIVORS);
+  for (int b = 0; b < n; b++) out[b] = res[b].x;
+  return TTS_OK;
 }
 
 // Latent pass (main.cpp:2053-2519, 5280-5352): full causal forward without the decode cache.

@@ -61,6 +61,10 @@ int ar_drv_step_sample(tts_ctx *c, const int32_t *prev, int i, unsigned flags, i
   if (ar_batch(c) < 1) return fail(c, TTS_ERR_STATE, "tts_ar_begin not called"); // before the shard check: with no AR state the batch is 0
   if (int rc = shard_check(c, ar_batch(c))) return rc;
   c->topk_fallbacks = 0;
+  if (c->ar_sampler) { // the device sampler: neither the lists nor the context's generator
+    if (const char *e = ar_device_sampler_refusal(c->ar_sp)) return fail(c, TTS_ERR_ARG, "tts_ar_step_sample: %s", e);
+    return ar_dev_step_sample(c, prev, i, flags, samples_out);
+  }
   SampleCall s(c->generator);
   s.sp = c->ar_sp; s.scope = c->ar_penalty_scope; s.mask_stop = (flags & TTS_AR_MASK_STOP) != 0;
   s.n = ar_batch(c); s.ids = prev; s.fallbacks = &c->topk_fallbacks;
@@ -119,6 +123,42 @@ static int stream_emit(tts_ctx *c, HfgStream &hs, int L, int upto, int is_last) 
   return TTS_OK;
 }
 
+// The decode loop on the device sampler (option "ar_sampler" = 1): the draw, the next tokens and the step counters stay on the device; the host reads
+// {token, error word} pairs from the pinned ring and applies ArRun::advance to them, one iteration at a time. Up to `ar_sync_steps` steps are enqueued
+// between two waits; steps enqueued behind the iteration that ends the run are discarded (the next tts_ar_begin* rebuilds the state). The device keeps
+// one of the driver's rules itself, TTS_AR_RETIRE's ended flag. host_rules: the run has rules the device does not keep (a stop schedule; several prompt
+// groups in strict mode, whose ended groups are fed 8193): one step per wait, and the tokens ArRun::advance changed are written back before the next step.
+static int device_loop(tts_ctx *c, ArRun &run, int B, bool host_rules, double &t_step) {
+  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const int N = host_rules ? 1 : c->ar_sync_steps;
+  const unsigned flags = (run.mask_stop ? TTS_AR_MASK_STOP : 0u) | (run.retire ? TTS_AR_RETIRE : 0u);
+  if (int rc = ar_dev_begin(c, flags, run.max_steps)) return rc;
+  if (int rc = ar_dev_sample_prompt(c)) return rc;
+  int have = 1; // iterations [0, have) are enqueued
+  for (;;) {
+    const double t0 = now();
+    if (int rc = ar_dev_wait(c)) return rc;
+    t_step += now() - t0;
+    const int32_t *ring = ar_dev_ring(c);
+    while (run.i < have) {
+      const int32_t *e = ring + (size_t)run.i * B * 2;
+      bool moved = false;
+      for (int b = 0; b < B; b++) {
+        if (e[2 * b + 1]) return fail(c, TTS_ERR_LIMIT, "tts_autoregressive: candidate %d has more than %d survivors at iteration %d (a degenerate row)", b, TTS_SD_MAX_SURVIVORS, run.i);
+        run.samples[b] = e[2 * b];
+      }
+      run.advance();
+      if (run.state) return TTS_OK;
+      for (int b = 0; b < B; b++) moved |= run.samples[b] != e[2 * b];
+      if (moved && run.i == have) // (host_rules: N = 1, so every iteration is the last one enqueued)
+        if (int rc = ar_dev_feed(c, run.samples.data())) return rc;
+    }
+    const int n = std::min(N, run.max_steps - have); // iteration max_steps - 1 is the last one ArRun looks at
+    if (int rc = ar_dev_enqueue_steps(c, have - 1, n)) return rc;
+    have += n;
+  }
+}
+
 // G prompt groups in one decode loop (tts_autoregressive: G = 1; tts_autoregressive_multi). Group g's prompt is text_ids[t0_g .. + n_text[g]), its candidates
 // [c0_g, c0_g + n_cand[g]) of the batch. voice: [n_voices][1024], group g reads row voice_of[g] (tts_autoregressive_multi_voice; voice_of == nullptr: one voice
 // for all). Nothing after ar_begin_groups depends on the voices.
@@ -130,6 +170,8 @@ int ar_drv_autoregressive(tts_ctx *c, const int32_t *text_ids, const int *n_text
   double t_begin = now(), t_sample = 0, t_step = 0;
   if (!codes_out || !rows_out) return fail(c, TTS_ERR_ARG, "tts_autoregressive: null output");
   if (G < 1 || !n_text || !n_cand) return fail(c, TTS_ERR_ARG, "tts_autoregressive: bad argument");
+  if (c->ar_sampler)
+    if (const char *e = ar_device_sampler_refusal(c->ar_sp)) return fail(c, TTS_ERR_ARG, "tts_autoregressive: %s", e);
   int B = 0, P = 0; // P: the longest prompt's
   for (int g = 0; g < G; g++) { B += n_cand[g] > 0 ? n_cand[g] : 0; P = std::max(P, n_text[g] + 2); }
   if (max_steps > 500) return fail(c, TTS_ERR_LIMIT, "max_steps %d exceeds the 500 codes apply_padding accepts", max_steps);
@@ -150,9 +192,10 @@ int ar_drv_autoregressive(tts_ctx *c, const int32_t *text_ids, const int *n_text
   // before the decode step's buffers are used
   if (hs && (rc = ar_stream_reserve(c, std::max(32, std::min(502, max_steps + 10))))) return rc;
   int captures0 = -1; // decode-step graphs captured when the loop's first step had run
-  std::vector<float> logits0((size_t)B * TTS_VOCAB_MEL);
+  const bool dev = c->ar_sampler != 0; // the device sampler: iteration 0 samples from the prompt pass' rows where they lie
+  std::vector<float> logits0(dev ? 0 : (size_t)B * TTS_VOCAB_MEL);
   const double t_after_begin = now();
-  if ((rc = ar_prefill(c, logits0.data()))) return rc;
+  if ((rc = ar_prefill(c, dev ? nullptr : logits0.data()))) return rc;
   const double t_after_prefill = now();
   // mel_transformer_inputs_vector: [1 ... 1, 8192] per candidate at step 0 (5095-5105), afterwards the previous samples (5208-5217). Several prompts: every
   // row is padded to the longest prompt's P with more 1s — the penalty is applied once per DISTINCT id (sample_one / sample_one_list skip repeated ids; the
@@ -166,7 +209,11 @@ int ar_drv_autoregressive(tts_ctx *c, const int32_t *text_ids, const int *n_text
   c->topk_fallbacks = 0;
   // The uniforms are consumed the same way in every mode (two per candidate and step, candidate order), so every sequence is the one strict mode would produce.
   float *rows = logits0.data(); // iteration 0: the prompt pass' rows; later the pinned buffer the decode graph copies into, or null: the device top-k's lists
-  for (;;) {
+  if (dev) {
+    if ((rc = device_loop(c, run, B, sched || (G > 1 && !(flags & TTS_AR_RETIRE)), t_step))) return rc;
+    if (run.state == 2) return fail(c, TTS_ERR_LIMIT, "no stop token within %d steps", max_steps);
+  }
+  while (!dev) {
     double t0 = now();
     SampleCall s(c->generator, run, 0);
     s.rows = rows; s.fallbacks = &c->topk_fallbacks;

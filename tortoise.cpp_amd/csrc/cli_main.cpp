@@ -50,6 +50,10 @@
 //   of the command line; --timing 1 echoes them ("[timing] ar sampler ...").
 // --typical-mass <x> (0 = off, the default; 0 < x < 1): locally typical sampling (option ar_typical_mass; upstream's typical_sampling / typical_mass), under the
 //   same rules: out of range is a usage error; given, the value is appended to the "[timing] ar sampler" line.
+// --ar-sampler host|device (default host = the reference's sampler over std::mt19937) and --ar-sync-steps <n> (1 .. 64, default 1): the device sampler (options
+//   ar_sampler, ar_sync_steps: the draw in one kernel per candidate, uniforms keyed by seed and candidate, n decode steps enqueued per wait). Usage errors (exit 1,
+//   before a model is loaded): another sampler name, n out of range, --ar-sync-steps without --ar-sampler device, and with device any of --typical-mass > 0,
+//   --top-k > 512 or --stream. --devices N workers receive the flags; --timing 1 appends them to the "[timing] ar sampler" line when given.
 // --decoder diffusion|hifigan (default diffusion = the reference's 80 diffusion steps + UnivNet): hifigan sends the kept candidates' latents and their voices through ONE
 //   tts_hifigan_decode call (upstream tortoise-tts' api_fast.py path: no diffusion, no noise, no vocoder) and writes 256 samples per frame. --hifigan-model <file>
 //   (default <models>/ggml-hifigan-model.bin); the diffusion and vocoder models are then neither loaded nor required. --clvp, --split-text and several --voice work
@@ -230,6 +234,9 @@ int main(int argc, char **argv) {
   std::string ar_scope = "last";
   double ar_typ = 0;
   bool have_typ = false;
+  std::string ar_sampler = "host";
+  double ar_sync = 1;
+  bool have_ar_sampler = false, have_ar_sync = false;
   std::string decoder = "diffusion", hifiganPath, vocoder = "univnet", bigvganPath;
   std::string detectClips, classifierPath, alignerPath;
   std::string dvaePath, codesFrom, codesOut, revoicePath, scoreAudio, scoreCodes, scorePositions;
@@ -317,6 +324,8 @@ int main(int argc, char **argv) {
     else if (a == "--repetition-penalty") { ar_pen = std::atof(argv[i + 1]); have_pen = true; }
     else if (a == "--typical-mass") { ar_typ = std::atof(argv[i + 1]); have_typ = true; }
     else if (a == "--penalty-scope") { ar_scope = argv[i + 1]; have_scope = true; }
+    else if (a == "--ar-sampler") { ar_sampler = argv[i + 1]; have_ar_sampler = true; }
+    else if (a == "--ar-sync-steps") { ar_sync = std::atof(argv[i + 1]); have_ar_sync = true; }
     else if (a == "--rccl-id") rccl_id = argv[i + 1]; // worker mode (set by the parent)
     else if (a == "--shard") { // worker mode (set by the parent): "r/N"
       std::string v(argv[i + 1]);
@@ -517,6 +526,13 @@ int main(int argc, char **argv) {
   if (!std::isfinite(ar_pen) || !(ar_pen >= 1) || !std::isfinite((float)ar_pen)) { fprintf(stderr, "--repetition-penalty %g: a finite value >= 1\n", ar_pen); return 1; }
   if (ar_typ != 0 && (!(ar_typ > 0 && ar_typ < 1) || !((float)ar_typ > 0 && (float)ar_typ < 1))) { fprintf(stderr, "--typical-mass %g: 0 (off) or a value in (0, 1)\n", ar_typ); return 1; }
   if (ar_scope != "last" && ar_scope != "history") { fprintf(stderr, "--penalty-scope %s: last or history\n", ar_scope.c_str()); return 1; }
+  if (ar_sampler != "host" && ar_sampler != "device") { fprintf(stderr, "--ar-sampler %s: host or device\n", ar_sampler.c_str()); return 1; }
+  if (!(ar_sync >= 1 && ar_sync <= 64) || ar_sync != std::floor(ar_sync)) { fprintf(stderr, "--ar-sync-steps %g: an integer in 1 .. 64\n", ar_sync); return 1; }
+  if (have_ar_sync && ar_sampler != "device") { fprintf(stderr, "--ar-sync-steps needs --ar-sampler device\n"); return 1; }
+  if (ar_sampler == "device") {
+    const char *bad = ar_typ > 0 ? "--typical-mass > 0" : ar_top_k > 512 ? "--top-k > 512" : stream ? "--stream" : nullptr;
+    if (bad) { fprintf(stderr, "--ar-sampler device cannot be combined with %s\n", bad); return 1; }
+  }
   if (split_ids != 0 && (devices > 1 || exchange == "rccl" || shard >= 0)) {
     fprintf(stderr, "--split-text cannot be combined with --devices > 1 or --exchange rccl (one process runs all chunks)\n");
     return 1;
@@ -739,9 +755,12 @@ int main(int argc, char **argv) {
       (have_top_p && tts_set_option(ctx, "ar_top_p", ar_top_p)) || (have_pen && tts_set_option(ctx, "ar_repetition_penalty", ar_pen)) ||
       (have_scope && tts_set_option(ctx, "ar_penalty_scope", ar_scope == "history" ? 1.0 : 0.0)) || (have_typ && tts_set_option(ctx, "ar_typical_mass", ar_typ)))
     return die(ctx, "--temperature / --top-k / --top-p / --repetition-penalty / --penalty-scope / --typical-mass");
+  if ((have_ar_sampler && tts_set_option(ctx, "ar_sampler", ar_sampler == "device" ? 1.0 : 0.0)) || (have_ar_sync && tts_set_option(ctx, "ar_sync_steps", ar_sync)))
+    return die(ctx, "--ar-sampler / --ar-sync-steps");
   if (timing) {
-    char typ[48] = ""; // (the line is what it was without the flag)
+    char typ[96] = ""; // (the line is what it was without the flags)
     if (have_typ) snprintf(typ, sizeof typ, ", typical-mass %g", ar_typ);
+    if (have_ar_sampler) snprintf(typ + strlen(typ), sizeof typ - strlen(typ), ", ar-sampler %s, ar-sync-steps %g", ar_sampler.c_str(), ar_sync);
     fprintf(stderr, "[timing] ar sampler temperature %g, top-k %g, top-p %g, repetition-penalty %g, penalty-scope %s%s\n", ar_temp, ar_top_k, ar_top_p, ar_pen, ar_scope.c_str(), typ);
     if (shard >= 0) fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d (worker %d/%d)\n", sampler.c_str(), ddim_eta, cond_free_k, steps, shard, nshards);
     else fprintf(stderr, "[timing] sampler %s, ddim-eta %g, cond-free-k %g, steps %d\n", sampler.c_str(), ddim_eta, cond_free_k, steps);

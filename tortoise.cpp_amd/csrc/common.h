@@ -155,6 +155,8 @@ struct tts_ctx {
   tts::SamplerParams ar_sp;                 // options "ar_temperature" / "ar_top_k" / "ar_top_p" / "ar_repetition_penalty"
   int ar_penalty_scope = 0;                 // option "ar_penalty_scope": 0 = the reference (the ids of the last input), 1 = upstream's HF generate (every id fed since tts_ar_begin*, plus 1 and 8192)
   int device_topk = 1;                      // option "device_topk": tts_autoregressive's loop samples from the device prefilter's lists
+  int ar_sampler = 0;                       // option "ar_sampler": 0 = the host sampler over the context's mt19937; 1 = sample_device_kernel (ar.hip): no list, no host stage, uniforms from Philox keyed by (seed, global candidate, iteration)
+  int ar_sync_steps = 1;                    // option "ar_sync_steps" (read under ar_sampler = 1): decode steps the driver enqueues before it waits on the token ring
   int time_mlp_retries = 0;                 // evaluations of the diffusion time MLP that disagreed with their repetition (diffusion.hip: precompute_time)
   int topk_fallbacks = 0;                   // candidates x steps of the last tts_autoregressive call that needed their full row
   int sampler_threads = -1;                 // -1: min(7, hardware threads - 1); option "sampler_threads"
@@ -312,6 +314,22 @@ inline int shard_check(tts_ctx *c, int B) {
   return TTS_OK;
 }
 
+// The device sampler's uniform: Philox4x32-10 (diffusion.hip's generator) under a counter tag of its own, counter = {0, iteration, global candidate, tag},
+// key = the seed; the first output word's top 24 bits: u in [0, 1), a multiple of 2^-24. One function for the kernel and for tts_host_ar_uniform.
+constexpr uint32_t AR_PHILOX_TAG = 0x7718u; // counter word 3: the diffusion stage has 0x7715, the vocoder 0x7716, the random voices 0x7717
+enum { TTS_SD_TOPK_MAX = 512 }; // sample_device_kernel: the largest top-k it serves (host_logic.cpp: FAST_TOPK_MAX); its LDS holds TTS_SD_MAX_SURVIVORS survivors
+__host__ __device__ inline float ar_sample_uniform(uint64_t seed, uint32_t candidate, uint32_t iteration) {
+  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+  uint32_t c0 = 0u, c1 = iteration, c2 = candidate, c3 = AR_PHILOX_TAG, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int r = 0; r < 10; r++) {
+    const uint64_t p0 = (uint64_t)M0 * c0, p1 = (uint64_t)M1 * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return (float)(c0 >> 8) * 0x1p-24f;
+}
+
 #define TTS_HIP(ctx, expr)                                                                      \
   do {                                                                                          \
     hipError_t _e = (expr);                                                                     \
@@ -459,6 +477,25 @@ int ar_score_rows(tts_ctx *, const int32_t *input_ids, const int32_t *mel_pos, c
 int ar_score_row_table(const int32_t *codes, int n_codes, int positions, int32_t *input_ids, int32_t *mel_pos, int32_t *targets); // tts_host_ar_score_rows
 int ar_stream_reserve(tts_ctx *, int n_mel);
 int ar_graph_captures(const tts_ctx *);
+// ---- the device sampler (option "ar_sampler" = 1; ar.hip: sample_device_kernel) ----
+// Options "ar_sampler" (which 0) and "ar_sync_steps" (which 1): the refusal's text, or null (host_logic.cpp).
+const char *ar_sampler_option_error(int which, double value);
+// What the device sampler does not serve: typical sampling, top-k above its 512. The refusal's text, or null (host_logic.cpp).
+const char *ar_device_sampler_refusal(const SamplerParams &sp);
+// The run state of a decode loop on the device sampler. ar_dev_begin (after ar_prefill): controls, history sets, ended flags, step counter 0, a ring of
+// max_iters x B {token, error word} pairs in pinned memory. ar_dev_sample_prompt enqueues iteration 0 (from the prompt pass' rows, ring slot 0),
+// ar_dev_enqueue_steps n replays of the step graph (decode step s fills ring slot s + 1; the counter is the device's); ar_dev_wait waits for all of them.
+// ar_dev_feed overwrites the tokens the next step is fed (the driver's rules the device does not keep: a stop schedule, an ended group in strict mode).
+int ar_dev_begin(tts_ctx *, unsigned flags, int max_iters);
+int ar_dev_sample_prompt(tts_ctx *);
+int ar_dev_enqueue_steps(tts_ctx *, int first_step, int n);
+int ar_dev_wait(tts_ctx *);
+const int32_t *ar_dev_ring(const tts_ctx *); // [max_iters][B][2]
+int ar_dev_feed(tts_ctx *, const int32_t *toks);
+int ar_dev_step_sample(tts_ctx *, const int32_t *prev, int step_i, unsigned flags, int32_t *out); // tts_ar_step_sample under ar_sampler = 1
+// tts_sample_device: the kernel on caller-given rows (arguments checked by api.cpp); needs no AR model
+int ar_sample_device_rows(tts_ctx *, const float *logits, int n, const int32_t *ids, int ids_per_cand, int iteration, int first_candidate, unsigned flags,
+                          int32_t *out);
 int ar_session_open(tts_ctx *, int n_slots, int max_cand, int max_text, int max_steps, bool rows);
 int ar_session_controls(tts_ctx *, int c0, int n, const SamplerParams &sp, int scope);
 void ar_session_close(tts_ctx *);

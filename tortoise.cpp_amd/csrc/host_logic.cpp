@@ -530,6 +530,18 @@ static bool topk_cut(float hmin, float temp, float &cut) {
 
 // Above this top-k the full-row sampler goes straight to the literal formulation (the heap scan below is built for a few dozen survivors).
 static const int FAST_TOPK_MAX = 512;
+static_assert(TTS_SD_TOPK_MAX == FAST_TOPK_MAX, "the device sampler serves the top-k range of the fast host path");
+
+// Options "ar_sampler" and "ar_sync_steps": the ONE statement of what each accepts.
+const char *ar_sampler_option_error(int which, double value) {
+  if (which == 0) return (value != 0 && value != 1) ? "ar_sampler: 0 (the host sampler over the context's mt19937) or 1 (the device sampler)" : nullptr;
+  return (!(value >= 1 && value <= 64) || value != std::floor(value)) ? "ar_sync_steps: an integer in 1 .. 64" : nullptr;
+}
+const char *ar_device_sampler_refusal(const SamplerParams &sp) {
+  if (sp.typ_mass > 0) return "ar_sampler = 1 does not serve typical sampling (ar_typical_mass > 0)";
+  if (sp.top_k > TTS_SD_TOPK_MAX) return "ar_sampler = 1 serves ar_top_k up to 512";
+  return nullptr;
+}
 
 // One candidate, given its uniform draw: pure function of its arguments (runs on the sampler pool's threads).
 static int sample_one(const float *src, const int32_t *ids, int ids_per_cand, float sample, const SamplerParams &p, bool literal_only = false) {
