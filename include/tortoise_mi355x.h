@@ -937,6 +937,39 @@ int tts_dvae_codes_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samp
 int tts_ar_latents_for_codes(tts_ctx *ctx, const int32_t *text_ids, int n_text, const float *voice1024, const int32_t *codes, int n_codes,
                              int32_t *rows_out, float *latents_out);
 
+/* ---- speech codes back to the mel: upstream's DVAE decoder (not in the reference; additions within version 8, no prototype changed) ---------------- */
+/* DiscreteVAE.decode of the same model (use_transposed_convs=False, no normalization): what the codes of a recording or of the AR sampler describe, and how
+ * lossy they are. Stated from memory, as the encoder; UNPINNED AGAINST UPSTREAM (DESIGN.md "What pins the DVAE decoder"):
+ *   e = E[:, code[t]];  h = Conv1d(512 -> 1024, k 1)(e)                                                                               decoder.0
+ *   3 x:  h = h + Conv1(ReLU(Conv3(ReLU(Conv3(h)))))                                                                                  decoder.{1,2,3}.net.{0,2,4}
+ *   h = ReLU(Conv1d(1024 -> 1024, k 3, pad 1)(nearest_upsample(h, 2)));  h = ReLU(Conv1d(1024 -> 512, k 3, pad 1)(nearest_upsample(h, 2)))   decoder.{4,5}.0.conv
+ *   mel = Conv1d(512 -> 80, k 1)(h)                                                                                                   decoder.6
+ * f32 throughout (csrc/dvae_dec.h). File: a file of its own (tools/convert_weights.py --dvae-decoder): the decoder's tensors and codebook.embed under "dvae.",
+ * an optional "dvae.config" = {the up-sampling factor} (default 2); every size is read from the tensor names and shapes. It does not need tts_load_dvae.
+ * tts_load_dvae_decoder: TTS_ERR_FORMAT as tts_load_dvae states it (the same ranges, 1 .. 8 up-sampling layers), and for a checkpoint with transposed
+ *   convolutions (decoder.N.0.weight instead of decoder.N.0.conv.weight), with a message that says so. Parsed before the device is asked for.
+ * tts_dvae_decode_frames: mel frames of a clip of n_codes codes, n_codes x factor^layers (x 4 for upstream's); 0 before tts_load_dvae_decoder, TTS_ERR_ARG below 1.
+ * tts_dvae_decoder_channels: the mel bands the loaded decoder writes (80), 0 before the load.
+ * tts_dvae_decode: codes [n_clips][code_stride], the first n_codes[s] of clip s are read. One launch sequence for the ragged batch. mel_out: the clips back to
+ *   back, clip s band-major [channels][frames_out[s]]: what tts_dvae_codes reads as mel80; cap: the floats mel_out holds. A clip's bits are the same alone
+ *   or in any batch, and two calls agree. Legal while an AR or a diffusion session is open. Every check runs before any device work and a refused call writes
+ *   nothing: TTS_ERR_HIP on a host-only context; TTS_ERR_STATE before tts_load_dvae_decoder; TTS_ERR_ARG for a null pointer, n_clips < 1, n_codes < 1 or
+ *   above code_stride, a code outside 0 .. tokens - 1, or a mel larger than cap; TTS_ERR_LIMIT above TTS_DVAE_MAX_CLIPS clips or when a clip decodes to more
+ *   than TTS_DVAE_MAX_FRAMES frames. Profiler family "dvae_dec" (sub-families _embed, _res, _up, _head: work = FLOPs; _err: bytes).
+ * tts_dvae_reconstruct: mel80 / frames as tts_dvae_codes takes them -> the encoder, the decoder on the codes where the quantiser left them (they never leave
+ *   the device), and per clip l1_out = mean |mel - recon|, mse_out = mean (mel - recon)^2 over all bands of the first min(T, T') frames, accumulated in double
+ *   in a fixed order. mel_out NULL or the reconstructions back to back as tts_dvae_decode writes them (clip s: tts_dvae_decode_frames(its codes) frames): the
+ *   bits of tts_dvae_decode on tts_dvae_codes' output. TTS_ERR_STATE unless both halves are loaded and agree in tokens and mel channels; otherwise the
+ *   checks of tts_dvae_codes and tts_dvae_decode.
+ * tts_dvae_reconstruct_audio: clips as tts_dvae_codes_audio takes them; n_codes_out NULL or [n_clips]; cap: the floats mel_out (NULL or as above) holds. */
+int tts_load_dvae_decoder(tts_ctx *ctx, const char *path);
+int tts_dvae_decode_frames(const tts_ctx *ctx, int n_codes);
+int tts_dvae_decoder_channels(const tts_ctx *ctx);
+int tts_dvae_decode(tts_ctx *ctx, const int32_t *codes, const int32_t *n_codes, int n_clips, int code_stride, float *mel_out, int32_t *frames_out, int64_t cap);
+int tts_dvae_reconstruct(tts_ctx *ctx, const float *mel80, const int32_t *frames, int n_clips, float *l1_out, float *mse_out, float *mel_out /* may be NULL */);
+int tts_dvae_reconstruct_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips,
+                               const tts_voice_audio_opts *opts, float *l1_out, float *mse_out, int32_t *n_codes_out, float *mel_out, int64_t cap);
+
 /* ---- teacher-forced scores of given codes under the AR model (not in the reference; additions within version 8, no prototype changed) --------------- */
 /* How probable is a code sequence under the AR model, given a transcript and a voice: the quantity upstream's UnifiedVoice.forward returns as its mel loss.
  * tts_ar_score_codes: tts_ar_begin (one prompt, one voice) + the prompt pass + ONE batched latent pass over every candidate's rows + one fused head launch

@@ -31,7 +31,7 @@ import tortoise_cpp_amd_loader  # noqa: E402
 
 tortoise_cpp_amd_loader.load()
 from tortoise_cpp_amd.synth_weights import (GgmlWriter, aligner_tensor_shapes, bigvgan_filter, bigvgan_tensor_shapes, classifier_tensor_shapes,  # noqa: E402
-                                            dvae_tensor_shapes, random_voice_tensor_shapes)
+                                            dvae_decoder_tensor_shapes, dvae_tensor_shapes, random_voice_tensor_shapes)
 
 
 def _np(t):
@@ -410,6 +410,48 @@ def convert_dvae(sd, path, stride=2):
     return L, nb, int(sd["encoder.%d.0.weight" % (L - 1)].shape[0]), dim, tokens
 
 
+DVAE_DECODER_DROPPED = ("encoder.",) + DVAE_DROPPED[1:]
+
+
+def convert_dvae_decoder(sd, path, stride=2):
+    """dvae.pth -> the file tts_load_dvae_decoder reads: the decoder's convolutions and codebook.embed under `dvae.`, unchanged, plus dvae.config =
+    (the up-sampling factor,). The encoder, the EMA buffers, the recorded codes and the loss are DROPPED; any other unknown tensor is an error, as is a missing
+    or mis-sized one (--list-expected dvae-decoder). A checkpoint trained with use_transposed_convs=True (decoder.N.0.weight where decoder.N.0.conv.weight
+    is expected) is refused. Returns (up-sampling layers, ResBlocks, innermost channels, codebook dim, tokens)."""
+    sd = {k: v for k, v in sd.items() if not k.startswith(DVAE_DECODER_DROPPED)}
+    nb = 0
+    while "decoder.%d.net.0.weight" % (1 + nb) in sd:
+        nb += 1
+    L = 0
+    while "decoder.%d.0.conv.weight" % (1 + nb + L) in sd:
+        L += 1
+    if "decoder.%d.0.weight" % (1 + nb + L) in sd:
+        raise SystemExit("convert_dvae_decoder: decoder.%d.0.weight is a transposed convolution (use_transposed_convs=True): not supported" % (1 + nb + L))
+    last = "decoder.%d.weight" % (1 + nb + L)
+    if L < 1 or "decoder.0.weight" not in sd or "codebook.embed" not in sd or last not in sd:
+        raise SystemExit("convert_dvae_decoder: no decoder.0.weight, decoder.N.0.conv.weight, %s or codebook.embed (not a DiscreteVAE state dict?)" % last)
+    dim, tokens = (int(v) for v in sd["codebook.embed"].shape)
+    ups = [sd["decoder.%d.0.conv.weight" % (1 + nb + i)] for i in range(L)]
+    up = [int(sd["decoder.0.weight"].shape[0])] + [int(u.shape[0]) for u in ups]
+    exp = dvae_decoder_tensor_shapes(channels=int(sd[last].shape[0]), layers=L, blocks=nb, dim=dim, tokens=tokens, k=int(ups[0].shape[2]), stride=stride, up=up)
+    for k in sorted(sd):
+        if "dvae." + k not in exp:
+            raise SystemExit("convert_dvae_decoder: unexpected tensor '%s'" % k)
+    w = GgmlWriter(path)
+    for name, shape in exp.items():
+        if name == "dvae.config":
+            w.add(name, np.array([stride], np.float32))
+            continue
+        k = name[len("dvae."):]
+        if k not in sd:
+            raise SystemExit("convert_dvae_decoder: tensor '%s' is missing" % k)
+        if tuple(sd[k].shape) != tuple(shape):
+            raise SystemExit("convert_dvae_decoder: tensor '%s' has shape %s, expected %s" % (k, list(sd[k].shape), list(shape)))
+        w.add(name, _np(sd[k]))
+    w.close()
+    return L, nb, up[0], dim, tokens
+
+
 # ---- what each checkpoint is expected to hold (--list-expected) ---------------------------------------------------------------------
 # name -> PyTorch shape as tortoise-tts stores it, for the upstream architecture (or the one given). Written from the loaders' contracts
 # (main.cpp:682-792, 1244-1536, 1808-1923; csrc/extras.hip for the three containers the reference does not have), NOT from a checkpoint:
@@ -602,12 +644,14 @@ def expected_tensors(kind, **arch):
         out.update(random_voice_tensor_shapes(arch.get("dim", 1024), arch.get("layers", 6)))
     elif kind == "dvae":  # dvae.pth: DiscreteVAE's encoder and codebook.embed (the decoder and the EMA buffers are dropped; dvae.config is the converter's)
         out.update({k[len("dvae."):]: v for k, v in dvae_tensor_shapes(config=False, **arch).items()})
+    elif kind == "dvae-decoder":  # dvae.pth: DiscreteVAE's decoder (use_transposed_convs=False) and codebook.embed (the encoder and the EMA buffers are dropped)
+        out.update({k[len("dvae."):]: v for k, v in dvae_decoder_tensor_shapes(config=False, **arch).items()})
     else:
         raise ValueError(kind)
     return out
 
 
-EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan", "classifier", "aligner", "random_voice", "dvae")
+EXPECTED_KINDS = ("ar", "diffusion", "vocoder", "clvp", "conditioning-encoder", "diffusion-conditioning-encoder", "cvvp", "bigvgan", "classifier", "aligner", "random_voice", "dvae", "dvae-decoder")
 
 
 def container_shape(kind, name, shape):
@@ -690,6 +734,8 @@ def main():
     ap.add_argument("--dvae", help="dvae.pth of upstream tortoise-tts (DiscreteVAE) -> ggml-dvae-model.bin (speech codes from audio, tts_load_dvae: the encoder and "
                                    "the codebook; the decoder and the EMA buffers are dropped; not in the reference)")
     ap.add_argument("--dvae-stride", type=int, default=2, help="with --dvae: the strided layers' stride (no shape holds it; upstream: 2)")
+    ap.add_argument("--dvae-decoder", help="dvae.pth of upstream tortoise-tts (DiscreteVAE, use_transposed_convs=False) -> ggml-dvae-decoder-model.bin (speech codes "
+                                           "back to the mel, tts_load_dvae_decoder: the decoder and the codebook; --dvae-stride is its up-sampling factor)")
     ap.add_argument("--out")
     ap.add_argument("--list-expected", nargs="*", metavar="KIND", help="print every tensor name / shape the converter looks for per checkpoint kind (%s; "
                                                                         "default: all, upstream architecture) and exit" % ", ".join(EXPECTED_KINDS))
@@ -766,6 +812,9 @@ def main():
     if a.dvae:
         print("ggml-dvae-model.bin: %d strided layers, %d ResBlocks of %d channels, codebook %d x %d tokens"
               % convert_dvae(load(a.dvae), os.path.join(a.out, "ggml-dvae-model.bin"), a.dvae_stride))
+    if a.dvae_decoder:
+        print("ggml-dvae-decoder-model.bin: %d up-sampling layers, %d ResBlocks of %d channels, codebook %d x %d tokens"
+              % convert_dvae_decoder(load(a.dvae_decoder), os.path.join(a.out, "ggml-dvae-decoder-model.bin"), a.dvae_stride))
     if a.vocoder:
         checked("vocoder", load(a.vocoder), a.vocoder)
         print("ggml-vocoder-model.bin: %d res stacks" % convert_vocoder(load(a.vocoder), os.path.join(a.out, "ggml-vocoder-model.bin")))

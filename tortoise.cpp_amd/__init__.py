@@ -128,6 +128,9 @@ def lib():
         "tts_random_voice": (ci, [vp, vp, ci, vp, vp, vp, vp]), "tts_random_voice_noise": (ci, [vp, C.c_uint64, ci, vp, ci]),
         "tts_load_dvae": (ci, [vp, C.c_char_p]), "tts_dvae_rows": (ci, [ci]), "tts_dvae_tokens": (ci, [vp]), "tts_dvae_dim": (ci, [vp]),
         "tts_dvae_codes": (ci, [vp, vp, vp, ci, vp, vp, ci, vp]), "tts_dvae_codes_audio": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
+        "tts_load_dvae_decoder": (ci, [vp, C.c_char_p]), "tts_dvae_decode_frames": (ci, [vp, ci]), "tts_dvae_decoder_channels": (ci, [vp]),
+        "tts_dvae_decode": (ci, [vp, vp, vp, ci, ci, vp, vp, C.c_int64]), "tts_dvae_reconstruct": (ci, [vp, vp, vp, ci, vp, vp, vp]),
+        "tts_dvae_reconstruct_audio": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, C.c_int64]),
         "tts_ar_latents_for_codes": (ci, [vp, vp, ci, vp, vp, ci, vp, vp]),
         "tts_ar_score_codes": (ci, [vp, vp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp]), "tts_host_ar_score_rows": (ci, [vp, ci, ci, vp, vp, vp]),
         "tts_host_blend_voices": (ci, [vp, vp, ci, ci, vp]), "tts_host_random_voice_fold": (ci, [vp, vp, ci, ci, vp, vp]),
@@ -801,6 +804,67 @@ class Engine:
         self._ck(self.L.tts_dvae_codes_audio(self.h, _ptr(a), _ptr(n), _ptr(r), len(clips), C.addressof(o), _ptr(codes), _ptr(nc), stride,
                                              None if zz is None else _ptr(zz)))
         return self._dvae_split(codes, nc, zz)
+
+    # ---- the DVAE decoder (not in the reference): speech codes back to the mel, and how lossy a recording's codes are ----
+    def load_dvae_decoder(self, path):
+        self._ck(self.L.tts_load_dvae_decoder(self.h, path.encode()))
+
+    def dvae_decode_frames(self, n_codes):
+        """mel frames the loaded decoder makes of n_codes codes (0 before load_dvae_decoder)"""
+        return self._ck(self.L.tts_dvae_decode_frames(self.h, int(n_codes)))
+
+    def _dvae_mels(self, flat, frames):
+        ch, out, o = self.L.tts_dvae_decoder_channels(self.h), [], 0
+        for f in frames:
+            out.append(flat[o:o + ch * int(f)].reshape(ch, int(f)).copy())
+            o += ch * int(f)
+        return out
+
+    def dvae_decode(self, codes_list):
+        """codes_list: int32 code arrays, one per clip. Returns a list of float32 mels [channels, codes * factor^layers], band-major as dvae_codes reads them
+        (tts_dvae_decode: one call for the ragged batch)."""
+        if not len(codes_list):
+            raise TtsError("dvae_decode: no clips")
+        nc = np.array([len(c) for c in codes_list], np.int32)
+        stride = max(1, int(nc.max()))
+        codes = np.zeros((len(nc), stride), np.int32)
+        for i, c in enumerate(codes_list):
+            codes[i, :len(c)] = np.asarray(c, np.int32)
+        frames = np.zeros(len(nc), np.int32)
+        per = max(1, self.L.tts_dvae_decode_frames(self.h, 1)) * self.L.tts_dvae_decoder_channels(self.h)
+        mel = np.zeros(max(1, int(nc.sum()) * per), np.float32)
+        self._ck(self.L.tts_dvae_decode(self.h, _ptr(codes), _ptr(nc), len(nc), stride, _ptr(mel), _ptr(frames), mel.size))
+        return self._dvae_mels(mel, frames)
+
+    def dvae_reconstruct(self, mels, mel_out=False):
+        """mels as dvae_codes takes them -> (l1, mse): float32 [clips], the mean absolute and mean squared reconstruction error of every clip through the
+        encoder and the decoder (tts_dvae_reconstruct: the codes never leave the device); mel_out=True: (l1, mse, list of reconstructed mels)."""
+        if not len(mels):
+            raise TtsError("dvae_reconstruct: no clips")
+        frames = np.array([np.shape(m)[1] for m in mels], np.int32)
+        mel = np.ascontiguousarray(np.concatenate([np.asarray(m, np.float32).reshape(-1) for m in mels]))
+        l1, mse = np.zeros(len(mels), np.float32), np.zeros(len(mels), np.float32)
+        out_frames = [self.dvae_decode_frames(self.dvae_rows(int(f))) for f in frames]
+        rec = np.zeros(max(1, sum(out_frames) * self.L.tts_dvae_decoder_channels(self.h)), np.float32) if mel_out else None
+        self._ck(self.L.tts_dvae_reconstruct(self.h, _ptr(mel), _ptr(frames), len(mels), _ptr(l1), _ptr(mse), None if rec is None else _ptr(rec)))
+        return (l1, mse, self._dvae_mels(rec, out_frames)) if mel_out else (l1, mse)
+
+    def dvae_reconstruct_audio(self, clips, rates, mel_norms=None, mel_out=False):
+        """the same from samples (clips and rates as dvae_codes_audio): (l1, mse, codes per clip[, reconstructed mels]); neither the mel nor the codes leave the device"""
+        rates = [int(rates)] * len(clips) if np.isscalar(rates) else [int(r) for r in rates]
+        if len(rates) != len(clips) or not len(clips):
+            raise TtsError("%d rates for %d clips" % (len(rates), len(clips)))
+        n = np.array([len(c) for c in clips], np.int64)
+        a = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1) for c in clips]))
+        r = np.array(rates, np.int32)
+        o, keep = self._audio_opts(mel_norms, 0, True)
+        frames = [self._ck(self.L.tts_audio_mel(self.h, _ptr(np.ascontiguousarray(c, np.float32)), len(c), rt, 80, C.addressof(o), None, 0)) for c, rt in zip(clips, rates)]
+        out_frames = [self.dvae_decode_frames(self.dvae_rows(f)) for f in frames]
+        l1, mse, nc = np.zeros(len(clips), np.float32), np.zeros(len(clips), np.float32), np.zeros(len(clips), np.int32)
+        rec = np.zeros(max(1, sum(out_frames) * self.L.tts_dvae_decoder_channels(self.h)), np.float32) if mel_out else None
+        self._ck(self.L.tts_dvae_reconstruct_audio(self.h, _ptr(a), _ptr(n), _ptr(r), len(clips), C.addressof(o), _ptr(l1), _ptr(mse), _ptr(nc),
+                                                   None if rec is None else _ptr(rec), 0 if rec is None else rec.size))
+        return (l1, mse, nc, self._dvae_mels(rec, out_frames)) if mel_out else (l1, mse, nc)
 
     def ar_score_codes(self, tokens, voice, codes_list, positions="decode"):
         """Teacher-forced scores of given code sequences under a text and a voice (tts_ar_score_codes): one batched latent pass and one fused head launch, no

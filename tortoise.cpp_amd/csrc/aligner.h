@@ -610,3 +610,4 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
 } // namespace tts
 
 #include "dvae.h" // the DVAE encoder: the same translation unit, the classifier's strided convolution and hfg_conv_kernel
+#include "dvae_dec.h" // the DVAE decoder: the same translation unit, dvae.h's model reader, tables and hfg_conv_kernel launch

@@ -126,6 +126,7 @@ void tts_destroy(tts_ctx *c) {
   if (c->classifier) classifier_free(c->classifier);
   if (c->aligner) aligner_free(c->aligner);
   if (c->dvae) dvae_free(c->dvae);
+  if (c->dvae_dec) dvae_dec_free(c->dvae_dec);
   if (c->rlg) random_voice_free(c->rlg);
   if (c->afe) afe_free(c->afe);
   if (c->fp16_counts) (void)hipFree(c->fp16_counts);
@@ -521,6 +522,27 @@ int tts_dvae_codes_audio(tts_ctx *c, const float *audio, const int64_t *n_sample
                          int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out) {
   NEED_CTX(c);
   return guarded(c, [&] { return afe_dvae_codes_audio(c, audio, n_samples, sample_rate, n_clips, opts, codes_out, n_codes_out, code_stride, z_out); });
+}
+// The DVAE decoder (dvae_dec.h): speech codes -> mel, and the reconstruction error of a recording's own codes. A file of its own, parsed before the device is
+// asked for; the calls are legal while a session is open, as the encoder's.
+int tts_load_dvae_decoder(tts_ctx *c, const char *path) {
+  if (!c) return TTS_ERR_ARG;
+  return guarded(c, [&] { return dvae_dec_load(c, path); });
+}
+int tts_dvae_decode_frames(const tts_ctx *c, int n_codes) { return dvae_dec_frames(c, n_codes); }
+int tts_dvae_decoder_channels(const tts_ctx *c) { return dvae_dec_channels(c); }
+int tts_dvae_decode(tts_ctx *c, const int32_t *codes, const int32_t *n_codes, int n_clips, int code_stride, float *mel_out, int32_t *frames_out, int64_t cap) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return dvae_decode(c, codes, n_codes, n_clips, code_stride, mel_out, frames_out, cap); });
+}
+int tts_dvae_reconstruct(tts_ctx *c, const float *mel80, const int32_t *frames, int n_clips, float *l1_out, float *mse_out, float *mel_out) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return dvae_reconstruct(c, mel80, frames, n_clips, l1_out, mse_out, mel_out); });
+}
+int tts_dvae_reconstruct_audio(tts_ctx *c, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                               float *l1_out, float *mse_out, int32_t *n_codes_out, float *mel_out, int64_t cap) {
+  NEED_CTX(c);
+  return guarded(c, [&] { return afe_dvae_reconstruct_audio(c, audio, n_samples, sample_rate, n_clips, opts, l1_out, mse_out, n_codes_out, mel_out, cap); });
 }
 // tts_ar_begin (one candidate), tts_ar_prefill, tts_host_pad_codes, tts_ar_latents, tts_host_trimmed_rows as one call: the latents of GIVEN codes (a recording's,
 // from tts_dvae_codes) under a text and a voice. No sampling: the context's generator is never touched.

@@ -368,6 +368,31 @@ int afe_dvae_codes_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samp
   return dvae_run(ctx, codes_out, n_codes_out, code_stride, z_out);
 }
 
+// tts_dvae_reconstruct_audio: the same mel written into the encoder's input buffer, then tts_dvae_reconstruct's device half: neither the mel nor the codes
+// touch the host. The bits of tts_dvae_reconstruct on tts_audio_mel(bands 80, full_clips 1) of every clip.
+int afe_dvae_reconstruct_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                               float *l1_out, float *mse_out, int32_t *n_codes_out, float *mel_out, int64_t cap) {
+  const char *fn = "tts_dvae_reconstruct_audio";
+  if (!ctx->dvae) return fail(ctx, TTS_ERR_STATE, "tts_load_dvae not called");
+  if (!ctx->dvae_dec) return fail(ctx, TTS_ERR_STATE, "tts_load_dvae_decoder not called");
+  if (!audio || !n_samples || !sample_rate || !l1_out || !mse_out || n_clips < 1) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", fn);
+  if (dvae_mel_channels(ctx) != 80) return fail(ctx, TTS_ERR_STATE, "%s: the loaded DVAE reads %d mel channels, the audio front end makes 80", fn, dvae_mel_channels(ctx));
+  if (opts && opts->struct_size < sizeof(tts_voice_audio_opts))
+    return fail(ctx, TTS_ERR_ARG, "%s: struct_size %u, version 8 declares %zu bytes (set it to sizeof(tts_voice_audio_opts))", fn, opts->struct_size, sizeof(tts_voice_audio_opts));
+  tts_voice_audio_opts full{};
+  full.struct_size = sizeof(tts_voice_audio_opts);
+  if (opts) full = *opts;
+  full.full_clips = 1; full.crop_offset = 0;
+  AfePlan pl;
+  int rc = afe_plan(ctx, fn, n_samples, sample_rate, n_clips, &full, true, false, pl);
+  if (rc) return rc;
+  float *d80 = nullptr;
+  if ((rc = dvae_recon_begin(ctx, fn, pl.frames80.data(), n_clips, mel_out ? cap : -1, &d80))) return rc; // every check of both models before any device work
+  if ((rc = afe_init(ctx))) return rc;
+  if ((rc = afe_front(ctx, fn, audio, pl, &full, d80, nullptr))) return rc;
+  return dvae_recon_run(ctx, l1_out, mse_out, n_codes_out, mel_out);
+}
+
 int afe_audio_mel(tts_ctx *ctx, const float *audio, int64_t n, int sample_rate, int bands, const tts_voice_audio_opts *opts, float *mel_out, int64_t cap) {
   const char *fn = "tts_audio_mel";
   if (!audio || (bands != 80 && bands != 100)) return fail(ctx, TTS_ERR_ARG, "%s: bad arguments (bands: 80 or 100)", fn);

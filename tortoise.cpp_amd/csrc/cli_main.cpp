@@ -115,6 +115,14 @@
 //   chosen decoder chain (diffusion + vocoder, or --decoder hifigan) -> --output: the recording re-spoken in the other voice. Every voice option works as before.
 //   Usage errors (exit 1, before a model is loaded): --codes-from or --revoice without --dvae, either with --dry-run 1, --revoice with --split-text,
 //   --candidates > 1, several voices, --stream, --clvp / --cvvp, --devices > 1 or --exchange rccl, an unreadable clip, or a clip of more than 500 codes.
+// --dvae-decoder FILE: the DVAE decoder, speech codes back to the 80-band mel (tts_load_dvae_decoder; not in the reference).
+//   --decode-codes FILE --mel-out FILE: FILE holds lines in --codes-out's format; per line "decoded: FILE:line <codes> <frames>" is printed and the mels are
+//   written to --mel-out as raw f32, the clips back to back, each band-major [80][frames] (tts_dvae_decode: one call); no other model is loaded.
+//   --dvae FILE --reconstruct a.wav[,b.wav...] [--mel-out FILE]: per clip "reconstruct: <path> <codes> <frames> <L1> <MSE>", the mean absolute and mean squared
+//   error of the clip's mel through the encoder and the decoder (tts_dvae_reconstruct_audio; --mel-norms as with --codes-from).
+//   Usage errors (exit 1, before a model is loaded): --decode-codes or --reconstruct without --dvae-decoder, both at once, --decode-codes without --mel-out,
+//   --reconstruct without --dvae, --mel-out or --dvae-decoder without either mode, --dry-run 1, a combination with --codes-from, --revoice, --score-audio or
+//   --score-codes, an unreadable clip or codes file, a line that does not hold 1 or more codes of 0 or more.
 // --score-audio a.wav[,b.wav...] (with --dvae FILE) or --score-codes FILE (lines in --codes-out's format), with --message "transcript", any voice source and the
 //   AR model: teacher-forced scores of the clips' codes under the transcript and the voice (tts_ar_score_codes: one batched pass, no sampling; nothing is
 //   synthesised and no other model is loaded). [--score-positions decode|train], default train (upstream forward()'s positions; decode = what the sampler saw).
@@ -239,6 +247,7 @@ int main(int argc, char **argv) {
   bool have_ar_sampler = false, have_ar_sync = false;
   std::string decoder = "diffusion", hifiganPath, vocoder = "univnet", bigvganPath;
   std::string detectClips, classifierPath, alignerPath;
+  std::string dvaeDecPath, decodeCodes, melOut, reconstructFrom;
   std::string dvaePath, codesFrom, codesOut, revoicePath, scoreAudio, scoreCodes, scorePositions;
   bool have_steps = false;
   bool have_temp = false, have_top_k = false, have_top_p = false, have_pen = false, have_scope = false;
@@ -281,6 +290,10 @@ int main(int argc, char **argv) {
     else if (a == "--classifier") classifierPath = argv[i + 1];
     else if (a == "--aligner") alignerPath = argv[i + 1];
     else if (a == "--dvae") dvaePath = argv[i + 1];
+    else if (a == "--dvae-decoder") dvaeDecPath = argv[i + 1];
+    else if (a == "--decode-codes") decodeCodes = argv[i + 1];
+    else if (a == "--mel-out") melOut = argv[i + 1];
+    else if (a == "--reconstruct") reconstructFrom = argv[i + 1];
     else if (a == "--codes-from") codesFrom = argv[i + 1];
     else if (a == "--codes-out") codesOut = argv[i + 1];
     else if (a == "--revoice") revoicePath = argv[i + 1];
@@ -362,6 +375,101 @@ int main(int argc, char **argv) {
     for (size_t c = 0; !rc && c < paths.size(); c++) printf("detect: %s %.9g\n", paths[c].c_str(), (double)prob[c]);
     tts_destroy(dctx);
     return rc;
+  }
+  // --dvae-decoder: speech codes back to the mel; every usage error before a model is loaded
+  if (!dvaeDecPath.empty() || !decodeCodes.empty() || !reconstructFrom.empty() || !melOut.empty()) {
+    const bool dec = !decodeCodes.empty(), rec = !reconstructFrom.empty();
+    if ((dec || rec) && dvaeDecPath.empty()) {
+      fprintf(stderr, "usage: %s needs --dvae-decoder <file> (tools/convert_weights.py --dvae-decoder)\n", dec ? "--decode-codes" : "--reconstruct");
+      return 1;
+    }
+    if (dec && rec) { fprintf(stderr, "usage: --decode-codes and --reconstruct cannot be combined\n"); return 1; }
+    if (!dec && !rec) { fprintf(stderr, "usage: %s needs --decode-codes <file> or --reconstruct <a.wav[,b.wav...]>\n", melOut.empty() ? "--dvae-decoder" : "--mel-out"); return 1; }
+    if (dec && melOut.empty()) { fprintf(stderr, "usage: --decode-codes needs --mel-out <file>\n"); return 1; }
+    if (rec && dvaePath.empty()) { fprintf(stderr, "usage: --reconstruct needs --dvae <file> (tools/convert_weights.py --dvae)\n"); return 1; }
+    if (dry) { fprintf(stderr, "usage: --dvae-decoder runs on the device: it cannot be combined with --dry-run 1\n"); return 1; }
+    const char *bad = !codesFrom.empty() ? "--codes-from" : !revoicePath.empty() ? "--revoice" : !scoreAudio.empty() ? "--score-audio" : !scoreCodes.empty() ? "--score-codes" : nullptr;
+    if (bad) { fprintf(stderr, "usage: %s decodes and exits: it cannot be combined with %s\n", dec ? "--decode-codes" : "--reconstruct", bad); return 1; }
+    std::vector<std::string> names;
+    std::vector<int32_t> codes, nc; // --decode-codes: the lines back to back, then [lines][stride]
+    std::vector<float> samples, norms;
+    std::vector<int64_t> ns;
+    std::vector<int32_t> rates;
+    if (dec) {
+      std::ifstream f(decodeCodes);
+      if (!f) { fprintf(stderr, "usage: --decode-codes %s: cannot be opened\n", decodeCodes.c_str()); return 1; }
+      std::string line;
+      for (int ln = 1; std::getline(f, line); ln++) {
+        std::istringstream is(line);
+        long v;
+        int n = 0;
+        while (is >> v) {
+          if (v < 0 || v > INT32_MAX) { fprintf(stderr, "usage: --decode-codes %s:%d: code %ld\n", decodeCodes.c_str(), ln, v); return 1; }
+          codes.push_back((int32_t)v); n++;
+        }
+        if (!is.eof()) { fprintf(stderr, "usage: --decode-codes %s:%d: a line holds space-separated codes\n", decodeCodes.c_str(), ln); return 1; }
+        if (!n) continue;
+        nc.push_back(n); names.push_back(decodeCodes + ":" + std::to_string(ln));
+      }
+      if (names.empty()) { fprintf(stderr, "usage: --decode-codes %s: no codes\n", decodeCodes.c_str()); return 1; }
+    } else {
+      for (size_t a = 0; a <= reconstructFrom.size();) {
+        const size_t b = std::min(reconstructFrom.find(',', a), reconstructFrom.size());
+        const std::string path = reconstructFrom.substr(a, b - a);
+        a = b + 1;
+        if (path.empty()) continue;
+        int64_t cnt = 0;
+        int32_t rate = 0;
+        if (!read_clip(path, samples, &cnt, &rate)) return 1;
+        names.push_back(path); ns.push_back(cnt); rates.push_back(rate);
+      }
+      if (names.empty()) { fprintf(stderr, "usage: --reconstruct: no clip given\n"); return 1; }
+      if (!read_norms(melNormsPath, norms)) return 1;
+    }
+    const int B = (int)names.size();
+    tts_ctx *dctx = tts_create(device);
+    if (!dctx) { fprintf(stderr, "tts_create(%d) failed: no HIP device (this engine has no CPU path)\n", device); return 1; }
+    auto leave = [&](const char *what) { const int rc = die(dctx, what); tts_destroy(dctx); return rc; };
+    if (tts_load_dvae_decoder(dctx, dvaeDecPath.c_str())) return leave("dvae_decoder_model_load");
+    if (rec && tts_load_dvae(dctx, dvaePath.c_str())) return leave("dvae_model_load");
+    const int ch = tts_dvae_decoder_channels(dctx);
+    std::vector<float> mel, l1(B), mse(B);
+    std::vector<int32_t> frames(B);
+    if (dec) {
+      int stride = 1;
+      int64_t total = 0;
+      for (int n : nc) { stride = std::max(stride, n); total += n; }
+      std::vector<int32_t> padded((size_t)B * stride, 0);
+      for (size_t c = 0, o = 0; c < (size_t)B; o += nc[c], c++) std::copy(codes.begin() + o, codes.begin() + o + nc[c], padded.begin() + c * stride);
+      mel.resize((size_t)total * std::max(1, tts_dvae_decode_frames(dctx, 1)) * ch);
+      if (tts_dvae_decode(dctx, padded.data(), nc.data(), B, stride, mel.data(), frames.data(), (int64_t)mel.size())) return leave("dvae_decode");
+      for (int c = 0; c < B; c++) printf("decoded: %s %d %d\n", names[c].c_str(), nc[c], frames[c]);
+    } else {
+      tts_voice_audio_opts vo;
+      vo.struct_size = sizeof vo;
+      tts_voice_audio_opts_init(&vo);
+      vo.mel_norms80 = norms.empty() ? nullptr : norms.data();
+      nc.assign(B, 0);
+      if (!melOut.empty()) { // a clip's mel frames (samples at 22 050 Hz / 256 + 1) -> its codes -> the decoder's frames
+        int64_t total = 0;
+        for (int c = 0; c < B; c++) total += std::max(0, tts_dvae_decode_frames(dctx, clip_codes(ns[c], rates[c]) + 1));
+        mel.resize((size_t)total * ch);
+      }
+      if (tts_dvae_reconstruct_audio(dctx, samples.data(), ns.data(), rates.data(), B, &vo, l1.data(), mse.data(), nc.data(), mel.empty() ? nullptr : mel.data(), (int64_t)mel.size()))
+        return leave("dvae_reconstruct_audio");
+      for (int c = 0; c < B; c++) {
+        frames[c] = tts_dvae_decode_frames(dctx, nc[c]);
+        printf("reconstruct: %s %d %d %.9g %.9g\n", names[c].c_str(), nc[c], frames[c], (double)l1[c], (double)mse[c]);
+      }
+    }
+    tts_destroy(dctx);
+    if (!melOut.empty()) {
+      size_t used = 0;
+      for (int c = 0; c < B; c++) used += (size_t)frames[c] * ch;
+      FILE *out = fopen(melOut.c_str(), "wb");
+      if (!out || fwrite(mel.data(), 4, used, out) != used || fclose(out)) { fprintf(stderr, "--mel-out %s: write error\n", melOut.c_str()); return 1; }
+    }
+    return 0;
   }
   // --dvae: speech codes from audio
   const bool revoice = !revoicePath.empty();

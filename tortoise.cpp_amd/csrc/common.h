@@ -96,6 +96,7 @@ struct BigvganState;
 struct ClassifierState;
 struct AlignerState;
 struct DvaeState;
+struct DvaeDecState;
 struct RandomVoiceState;
 struct AfeState;
 struct Tokenizer;
@@ -146,6 +147,7 @@ struct tts_ctx {
   tts::ClassifierState *classifier = nullptr; // tortoise-detect: waveform -> probability that the clip is synthesized (classifier.h, part of hifigan.hip's translation unit through bigvgan.h; not in the reference)
   tts::AlignerState *aligner = nullptr; // wav2vec2 CTC aligner: waveform -> one token id per frame, for tts_align_audio / tts_redact_audio (aligner.h, part of hifigan.hip's translation unit through classifier.h; not in the reference)
   tts::DvaeState *dvae = nullptr; // the DVAE encoder: mel -> speech codes, for tts_dvae_codes / tts_dvae_codes_audio (dvae.h, part of hifigan.hip's translation unit through aligner.h; not in the reference)
+  tts::DvaeDecState *dvae_dec = nullptr; // the DVAE decoder: speech codes -> mel, for tts_dvae_decode / tts_dvae_reconstruct (dvae_dec.h, behind dvae.h in hifigan.hip's translation unit; not in the reference)
   tts::RandomVoiceState *rlg = nullptr; // random voices: upstream's RandomLatentConverter, one model per side (random_voice.h, part of extras.hip's translation unit; not in the reference)
   tts::AfeState *afe = nullptr; // audio front-end: its tables and buffers, made at the first tts_voice_from_audio / tts_audio_mel (audio_frontend.hip)
   tts::Tokenizer *tok = nullptr;
@@ -660,6 +662,17 @@ int dvae_run(tts_ctx *ctx, int32_t *codes_out, int32_t *n_codes_out, int code_st
 int dvae_codes(tts_ctx *ctx, const float *mel80, const int32_t *frames, int n_clips, int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out);
 int afe_dvae_codes_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
                          int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out);
+// The DVAE decoder (dvae_dec.h). dvae_recon_begin / dvae_recon_run are tts_dvae_reconstruct in two halves: the audio front end fills *d_mel between them.
+int dvae_dec_load(tts_ctx *ctx, const char *path);
+void dvae_dec_free(DvaeDecState *);
+int dvae_dec_channels(const tts_ctx *ctx);
+int dvae_dec_frames(const tts_ctx *ctx, int n_codes);
+int dvae_decode(tts_ctx *ctx, const int32_t *codes, const int32_t *n_codes, int n_clips, int code_stride, float *mel_out, int32_t *frames_out, int64_t cap);
+int dvae_recon_begin(tts_ctx *ctx, const char *fn, const int32_t *frames, int n_clips, int64_t cap, float **d_mel);
+int dvae_recon_run(tts_ctx *ctx, float *l1_out, float *mse_out, int32_t *n_codes_out, float *mel_out);
+int dvae_reconstruct(tts_ctx *ctx, const float *mel80, const int32_t *frames, int n_clips, float *l1_out, float *mse_out, float *mel_out);
+int afe_dvae_reconstruct_audio(tts_ctx *ctx, const float *audio, const int64_t *n_samples, const int32_t *sample_rate, int n_clips, const tts_voice_audio_opts *opts,
+                               float *l1_out, float *mse_out, int32_t *n_codes_out, float *mel_out, int64_t cap);
 // The host half of alignment and redaction (host_logic.cpp; exported as tts_host_*). Text is UTF-8; a character is a code point. Each returns a count or a
 // negative status and leaves the reason in `err`.
 int ctc_decode(const int32_t *ids, int n_frames, const int32_t *vocab, int n_vocab, int blank, std::vector<int32_t> &out, std::string &err);

@@ -420,8 +420,9 @@ int dvae_begin(tts_ctx *ctx, const char *fn, const int32_t *frames, int n_clips,
   return TTS_OK;
 }
 
-// codes_out [B][code_stride], z_out null or [B][code_stride][dim]: the first n_codes_out[s] entries of a clip are written, the rest is left alone.
-int dvae_run(tts_ctx *ctx, int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out) {
+// The launch sequence of a batch dvae_begin laid out, its mel buffer filled: the codes [R] are left in st->codes and z in st->z (dvae_run downloads them; the
+// decoder, dvae_dec.h, reads the codes where they are)
+int dvae_encode(tts_ctx *ctx) {
   DvaeState *st = ctx->dvae;
   const int B = st->lt.B, L = st->L, D = st->dim;
   const std::vector<int> &max_n = st->lt.max_n;
@@ -466,6 +467,18 @@ int dvae_run(tts_ctx *ctx, int32_t *codes_out, int32_t *n_codes_out, int code_st
     TTS_HIP(ctx, dvae_launch_vq(q, st->codes.as<int>(), nullptr, sm));
   }
   TTS_HIP(ctx, hipGetLastError());
+  return TTS_OK;
+}
+
+// codes_out [B][code_stride], z_out null or [B][code_stride][dim]: the first n_codes_out[s] entries of a clip are written, the rest is left alone.
+int dvae_run(tts_ctx *ctx, int32_t *codes_out, int32_t *n_codes_out, int code_stride, float *z_out) {
+  DvaeState *st = ctx->dvae;
+  const int B = st->lt.B, L = st->L, D = st->dim;
+  const int64_t R = st->lt.rows[L];
+  hipStream_t sm = ctx->stream;
+  const float *z = st->z.as<float>();
+  const int rc = dvae_encode(ctx);
+  if (rc) return rc;
   std::vector<int32_t> codes((size_t)R);
   std::vector<float> zh(z_out ? (size_t)R * D : 0);
   TTS_HIP(ctx, hipMemcpyAsync(codes.data(), st->codes.p, codes.size() * 4, hipMemcpyDeviceToHost, sm));

@@ -894,6 +894,64 @@ def write_dvae(path, seed=1280, **cfg):
     return t
 
 
+def dvae_decoder_tensor_shapes(channels=80, hidden=512, layers=2, blocks=3, dim=512, tokens=8192, k=3, stride=2, config=True, up=None):
+    """{name: PyTorch shape} of a DVAE decoder file (tts_load_dvae_decoder): the decoder and the codebook of upstream's DiscreteVAE state dict
+    (use_transposed_convs=False) under `dvae.` - `decoder.0` the k = 1 convolution dim -> H, ResBlock j `decoder.(1 + j).net.{0,2,4}`, up-sampling layer i
+    `decoder.(1 + blocks + i).0.conv`, the final k = 1 convolution `decoder.(1 + blocks + layers)`, `codebook.embed` [dim][tokens] - plus `dvae.config` =
+    (the up-sampling factor,). up: the channel counts [H, C_1 .. C_layers]; default upstream's, the encoder's reversed with the first repeated
+    (hidden 512, 2 layers: 1024 -> 1024 -> 512). Restated from memory, unpinned against upstream."""
+    if up is None:
+        enc = [hidden * 2 ** i for i in range(layers)][::-1]
+        up = [enc[0]] + enc
+    assert len(up) == layers + 1
+    t = {"dvae.decoder.0.weight": (up[0], dim, 1), "dvae.decoder.0.bias": (up[0],)}
+    for j in range(blocks):
+        p = "dvae.decoder.%d.net." % (1 + j)
+        for q, kk in ((0, k), (2, k), (4, 1)):
+            t[p + "%d.weight" % q] = (up[0], up[0], kk)
+            t[p + "%d.bias" % q] = (up[0],)
+    for i in range(layers):
+        p = "dvae.decoder.%d.0.conv." % (1 + blocks + i)
+        t[p + "weight"] = (up[i + 1], up[i], k)
+        t[p + "bias"] = (up[i + 1],)
+    t["dvae.decoder.%d.weight" % (1 + blocks + layers)] = (channels, up[layers], 1)
+    t["dvae.decoder.%d.bias" % (1 + blocks + layers)] = (channels,)
+    t["dvae.codebook.embed"] = (dim, tokens)
+    if config:
+        t["dvae.config"] = (1,)
+    return t
+
+
+def dvae_decoder_tensors(seed=1290, codebook=None, **cfg):
+    """{name: float32 array}: dvae_tensors' recipe on the decoder's names; the first and the last convolution N(0, 1 / sqrt(fan in)). codebook: the [dim][tokens]
+    array of an encoder file, so that the two files are two halves of one model."""
+    c = dict(DVAE_UPSTREAM, **cfg)
+    g = _Gen(seed)
+    t = {}
+    last = "dvae.decoder.%d.weight" % (1 + c["blocks"] + c["layers"])
+    for name, shape in dvae_decoder_tensor_shapes(**c).items():
+        if name == "dvae.config":
+            t[name] = np.array([c["stride"]], np.float32)
+        elif name == "dvae.codebook.embed":
+            t[name] = g.normal(shape, 1.0) if codebook is None else np.ascontiguousarray(codebook, np.float32)
+        elif name.endswith(".bias"):
+            t[name] = g.normal(shape, 0.05)
+        else:
+            gain = 1.0 if name in (last, "dvae.decoder.0.weight") else 0.25 * np.sqrt(2.0) if ".net.4." in name else np.sqrt(2.0)
+            t[name] = g.lecun(shape, int(np.prod(shape[1:])), gain)
+    return t
+
+
+def write_dvae_decoder(path, seed=1290, codebook=None, **cfg):
+    """ggml-dvae-decoder-model.bin for tts_load_dvae_decoder; every size a parameter (dvae_decoder_tensor_shapes). Returns the tensors."""
+    t = dvae_decoder_tensors(seed, codebook, **cfg)
+    w = GgmlWriter(path)
+    for name, arr in t.items():
+        w.add(name, arr)
+    w.close()
+    return t
+
+
 def write_all(out_dir, ar_layers=30, diff_main=10, diff_tail=3, diff_integ=3, diff_lc=4, seed=1234):
     import os
     os.makedirs(out_dir, exist_ok=True)
