@@ -821,6 +821,15 @@ int tts_aligner_frames(int n_samples_16k);
  * points when vocab_out is not NULL (cap >= V) and the blank id when blank_out is not NULL. TTS_ERR_STATE before tts_load_aligner. */
 int tts_aligner_clip_frames(tts_ctx *ctx, int64_t n_samples, int sample_rate);
 int tts_aligner_vocab(tts_ctx *ctx, int32_t *vocab_out, int cap, int32_t *blank_out);
+/* Option "aligner_precision" (0 default; addition within version 8, no prototype changed): operands of the Linears of the aligner's encoder (feature projection
+ * and, per layer, qkv, out, W1 + GELU, W2: nine tenths of the stage's FLOPs) in tts_aligner_ids, tts_align_audio and tts_redact_audio. 0 = f32 (the f32-input
+ * MFMA, as before), 1 = fp16 operands with f32 accumulation, 2 = activation and weight each as an fp16 hi + lo pair (three products per step, f32
+ * accumulation). Any other value: TTS_ERR_ARG, nothing changes. Set it BEFORE tts_load_aligner: the fp16 planes double the encoder's weight memory (about
+ * +1.2 GB at upstream's size) and are packed only when the option is non-zero at the load (a non-finite weight then fails the load, TTS_ERR_FORMAT); a call in
+ * mode 1 or 2 on a model loaded at 0 returns TTS_ERR_STATE. A model loaded with planes serves all three modes. Every contract of the calls (a clip is the same
+ * bits alone and in a batch, two calls agree) holds within a mode; the bits of two modes differ. On the tests' weights mode 2 is within 5e-5 of the float64
+ * restatement (gate 1e-3, every id the float64 argmax); mode 1 is up to 2.6e-2 from it: it does NOT hold the 1e-3 gate, and an id may differ wherever a frame's
+ * top-two margin is below twice that distance. The extractor, the positional convolution, the attention, the LayerNorms and the CTC head stay f32 in every mode. */
 /* audio: the clips back to back, n_samples[c] mono samples at sample_rate[c] Hz. A clip is resampled to 16 kHz in one stage (the audio front end's
  * polyphase resampler; a clip already at 16 kHz reaches the network bit for bit). ids_out [n_clips][frame_stride]: the argmax of every frame, the lowest
  * index on a tie; n_frames_out [n_clips]; logits_out NULL or [n_clips][frame_stride][V]. Only the first n_frames_out[c] entries of a clip are written.

@@ -9,7 +9,12 @@ For 1 clip and for 16 clips of 147 200 samples at 16 kHz (9.2 s each):
   - with --resources 1 the compiler's resource summary of the new kernels (hipcc -Rpass-analysis=kernel-resource-usage on csrc/hifigan.hip, device code only).
 There is no earlier implementation to compare with, and no time is a pass condition. A run without a GPU fails at Engine(0): nothing falls back.
 
-  python tools/aligner_bench.py [--calls 7] [--warm 2] [--models DIR] [--resources 0|1] [--out profiles/aligner.txt]"""
+--precision M[,M..]: instead, option aligner_precision at each listed value (0 f32, 1 fp16, 2 split fp16 pairs; csrc/w2v_linear_h.h) in ONE process: one engine
+per mode (the option is read at the load), the modes interleaved call by call, --calls timed calls each after --warm; the w2v_conv family's device time and
+TFLOP/s per mode; every mode's largest logit distance from the float64 restatement (synth_weights.aligner_forward) on a --distance-samples clip at full size; the
+resource summary of w2v_linear_h_kernel. Writes profiles/aligner_f16.txt.
+
+  python tools/aligner_bench.py [--calls 7] [--warm 2] [--models DIR] [--resources 0|1] [--precision 0,1,2] [--out FILE]"""
 import argparse
 import os
 import re
@@ -41,7 +46,7 @@ def flops(n, N=7, C=512, k=(), s=(), D=1024, K=128, G=16, depth=24, FF=4096, V=3
 
 
 def resources():
-    """{kernel: resource figures} of the aligner's kernels"""
+    """{kernel: resource figures} of the aligner's kernels (a template's instantiations: the largest of each figure, the smallest occupancy)"""
     src = os.path.join(ROOT, "tortoise.cpp_amd", "csrc", "hifigan.hip")
     with tempfile.TemporaryDirectory() as d:
         r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.dirname(src),
@@ -52,14 +57,66 @@ def resources():
         m = re.search(r"Function Name: \S*?(w2v_\w+?_kernel)", line)
         if m:
             cur = m.group(1)
-            out[cur] = {}
+            out.setdefault(cur, {})
             continue
         if "Function Name:" in line:
             cur = None
         m = re.search(r"remark:\s+(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
         if m and cur:
-            out[cur][m.group(1).split(" [")[0]] = int(m.group(2))
+            key, val = m.group(1).split(" [")[0], int(m.group(2))
+            out[cur][key] = (min if key == "Occupancy" else max)(out[cur].get(key, val), val)
     return out
+
+
+def precision(a, modes, path, say):
+    import numpy as np
+    lin, att, frames = flops(N, **sw.ALIGNER_UPSTREAM)
+    engs = {}
+    for m in modes:
+        engs[m] = pkg.Engine(0)
+        engs[m].set_option("aligner_precision", m)
+        engs[m].load_aligner(path)
+    say("wav2vec2 CTC aligner (tts_aligner_ids), upstream's full size, synthetic weights: option aligner_precision 0 (f32, hfg_conv_kernel) | 1 (fp16 operands) | "
+        "2 (fp16 hi + lo pairs), csrc/w2v_linear_h.h; tools/aligner_bench.py --precision %s" % ",".join(map(str, modes)))
+    say("clip: %d samples at 16 kHz = %d frames; one engine per mode in one process, the modes interleaved call by call, %d timed calls each after %d untimed; "
+        "host clock around the synchronous call" % (N, frames, a.calls, a.warm))
+    for B in (1, 16):
+        clips = [sw.aligner_test_wave(N, 50 + i) for i in range(B)]
+        ts = {m: [] for m in modes}
+        for i in range(a.warm + a.calls):
+            for m in modes:
+                t0 = time.perf_counter()
+                engs[m].aligner_ids(clips, 16000)
+                if i >= a.warm:
+                    ts[m].append((time.perf_counter() - t0) * 1e3)
+        say()
+        for m in modes:
+            say("  %2d clips  aligner_precision %d  tts_aligner_ids  median %8.2f ms  (min %8.2f .. max %8.2f, %d calls)"
+                % (B, m, statistics.median(ts[m]), min(ts[m]), max(ts[m]), len(ts[m])))
+        for m in modes:
+            engs[m].set_option("prof_stride", 1)
+            engs[m].prof_reset(True)
+            engs[m].aligner_ids(clips, 16000)
+            ms, n, work = engs[m].prof_get("w2v_conv")
+            engs[m].prof_reset(False)
+            say("  %2d clips  aligner_precision %d  w2v_conv %8.2f ms on the device, %4d entries, %.1f TFLOP/s" % (B, m, ms, n, work / ms / 1e9))
+    wave = sw.aligner_test_wave(a.distance_samples, 77)
+    want = sw.aligner_forward(sw.read_ggml(path), wave, np.float64)
+    say()
+    say("largest logit distance from float64 (synth_weights.aligner_forward) on a clip of %d samples (%d frames), logits up to %.1f, smallest top-two margin %.4f:"
+        % (len(wave), want.shape[0], np.abs(want).max(), np.diff(np.sort(want, axis=1)[:, -2:], axis=1).min()))
+    for m in modes:
+        ids, lg = engs[m].aligner_ids([wave], 16000, logits=True)
+        say("  aligner_precision %d  %.2e   ids that differ from the float64 argmax: %d of %d" % (m, np.abs(lg[0] - want).max(), int((ids[0] != want.argmax(1)).sum()), len(ids[0])))
+    for e in engs.values():
+        e.close()
+    if a.resources:
+        say()
+        say("compiler resource summary (gfx950, -O3; the largest of the kernel's instantiations):")
+        for k, v in sorted(resources().items()):
+            if k == "w2v_linear_h_kernel":
+                say("  %-24s VGPRs %3d  SGPRs %3d  scratch %d B/lane  occupancy %d waves/SIMD  LDS %d B/workgroup"
+                    % (k, v.get("VGPRs", -1), v.get("TotalSGPRs", -1), v.get("ScratchSize", -1), v.get("Occupancy", -1), v.get("LDS Size", -1)))
 
 
 def main():
@@ -68,8 +125,11 @@ def main():
     ap.add_argument("--warm", type=int, default=2)
     ap.add_argument("--models", default=os.path.join(os.environ.get("TTS_SYNTH_DIR", "/tmp/tts_synth"), "aligner_bench"))
     ap.add_argument("--resources", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "aligner.txt"))
+    ap.add_argument("--precision", default="")
+    ap.add_argument("--distance-samples", type=int, default=32000)
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "aligner_f16.txt" if a.precision else "aligner.txt")
     os.makedirs(a.models, exist_ok=True)
     lines = []
 
@@ -83,6 +143,11 @@ def main():
     if not os.path.exists(cpath + ".done"):
         sw.write_classifier(cpath, seed=1262)
         open(cpath + ".done", "w").write("ok")
+    if a.precision:
+        precision(a, [int(m) for m in a.precision.split(",")], path, say)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     eng = pkg.Engine(0)
     eng.load_aligner(path)
     lin, att, frames = flops(N, **sw.ALIGNER_UPSTREAM)

@@ -10,6 +10,8 @@
 //   h = Linear(C -> D)(LN_C(h))                                                            w2v_ln_kernel, hfg_conv_kernel (k 1)
 //   h = h + GELU(Conv1d(D -> D, K, padding K / 2, groups G)(h))[: frames]                  w2v_pos_kernel
 //   depth x:  h = h + out(attn(qkv(LN(h))));  h = h + W2 GELU(W1 LN(h))                    w2v_ln_kernel, hfg_conv_kernel, cls_attn_kernel<64>, w2v_gelu_kernel
+// Option "aligner_precision" 1 / 2 (set before tts_load_aligner, which then packs the fp16 planes): the Linears above (projection, qkv, out, W1 + GELU, W2) run on
+// w2v_linear_h_kernel (w2v_linear_h.h: fp16 / split-pair operands, 64-row tiles, the GELU in W1's epilogue); everything else stays f32 as it is.
 //   ids = argmax(Linear(D -> V)(LN(h))), the lowest index on a tie                         w2v_ln_kernel, w2v_head_kernel
 //
 // Device layout: time-major f32 rows [row][channels]; clip s owns the rows [start_s, start_s + n_s) of a level, start_s a multiple of 8. Level 0 of the table is
@@ -30,8 +32,6 @@ constexpr int W2V_ROW_TILE = 64;   // rows of a w2v_gelu_kernel workgroup
 constexpr int W2V_PTM = 64;        // output rows of a w2v_pos_kernel workgroup: 2 row halves x 2 column groups of 32 over its 4 waves
 constexpr int W2V_HEAD_ROWS = 8;   // rows of a w2v_head_kernel workgroup: 2 per wave
 constexpr int W2V_MAX_C = 1024, W2V_MAX_V = 1024, W2V_MAX_CONV = 16, W2V_MAX_CLIPS = 256;
-
-__device__ __forceinline__ float w2v_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
 
 // Partial sums of one tile of one clip's samples in double: thread j adds samples j, j + 256, .. of the tile ascending, thread 0 the 256 sums ascending.
 // seq record (level 0): {-, samples, 0, first tile of the clip, first sample of the clip in x}
@@ -422,6 +422,7 @@ struct AlignerState {
   HfgLayer proj_n, enc_n;
   HfgLayer proj, pos, head;
   std::vector<W2vLayer> layers;
+  bool planes = false; // the Linears carry fp16 planes (option "aligner_precision" was non-zero at the load)
   DevWeights dev;
   DevBuf in, wav, part, stat, a, t, h, h2, y, qkv, att, ff, ids, logits;
 };
@@ -442,16 +443,23 @@ int aligner_load(tts_ctx *ctx, const char *path) {
   st->N = h->N; st->C = h->C; st->D = h->D; st->K = h->K; st->cg = h->cg; st->depth = h->depth; st->FF = h->FF; st->V = h->V; st->H = h->H; st->blank = h->blank;
   st->k = h->k; st->s = h->s; st->vocab = h->vocab;
   auto up = [&](const HostLayer &s, HfgLayer &d) { return st->dev.up(ctx, s, d); };
+  // a Linear w2v_linear_h_kernel may run: beside its f32 tensor the fp16 planes, only when the option asks for them now (they double the encoder's weight memory)
+  st->planes = ctx->aligner_precision != 0;
+  auto upl = [&](const HostLayer &s, int cin, int cout, HfgLayer &d) {
+    const int e = up(s, d);
+    return e || !st->planes ? e : st->dev.pack(ctx, "aligner", s.w, 1, cin, cout, d);
+  };
   st->conv.resize(h->N); st->conv_n.resize(h->N); st->layers.resize(h->depth);
   for (int i = 0; i < h->N; i++)
     if ((rc = up(h->conv[i], st->conv[i])) || (rc = up(h->conv_n[i], st->conv_n[i]))) return rc;
-  if ((rc = up(h->proj_n, st->proj_n)) || (rc = up(h->proj, st->proj)) || (rc = up(h->pos, st->pos)) || (rc = up(h->enc_n, st->enc_n)) ||
+  if ((rc = up(h->proj_n, st->proj_n)) || (rc = upl(h->proj, h->C, h->D, st->proj)) || (rc = up(h->pos, st->pos)) || (rc = up(h->enc_n, st->enc_n)) ||
       (rc = up(h->head, st->head)))
     return rc;
   for (int l = 0; l < h->depth; l++) {
     const W2vHostLayer &s = h->layers[l];
     W2vLayer &d = st->layers[l];
-    if ((rc = up(s.n1, d.n1)) || (rc = up(s.n2, d.n2)) || (rc = up(s.qkv, d.qkv)) || (rc = up(s.out, d.out)) || (rc = up(s.w1, d.w1)) || (rc = up(s.w2, d.w2)))
+    if ((rc = up(s.n1, d.n1)) || (rc = up(s.n2, d.n2)) || (rc = upl(s.qkv, h->D, 3 * h->D, d.qkv)) || (rc = upl(s.out, h->D, h->D, d.out)) ||
+        (rc = upl(s.w1, h->D, h->FF, d.w1)) || (rc = upl(s.w2, h->FF, h->D, d.w2)))
       return rc;
   }
   if (ctx->aligner) aligner_free(ctx->aligner);
@@ -496,6 +504,10 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
   if (!st) return fail(ctx, TTS_ERR_STATE, "tts_load_aligner not called");
   if (!audio || !n_samples || !rates || !ids_out || !n_frames_out || !resample || B < 1 || frame_stride < 1) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", fn);
   if (B > W2V_MAX_CLIPS) return fail(ctx, TTS_ERR_LIMIT, "%s: %d clips (at most %d per call)", fn, B, W2V_MAX_CLIPS);
+  const int prec = ctx->aligner_precision;
+  if (!aligner_precision_ok(prec)) return fail(ctx, TTS_ERR_ARG, "%s: aligner_precision %d", fn, prec);
+  if (prec && !st->planes)
+    return fail(ctx, TTS_ERR_STATE, "%s: aligner_precision %d, but the model was loaded with aligner_precision 0 and holds no fp16 planes: set the option before tts_load_aligner", fn, prec);
   const int N = st->N, C = st->C, D = st->D, V = st->V;
   ClipIngest clips;
   std::vector<int> frames(B);
@@ -538,9 +550,22 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
     ProfScope ps(ctx, "w2v_row", (double)rows[l] * ch * 4 * 2);
     w2v_launch_ln(x, out, p.w, p.b, seq(l), ch, gelu, max_n[l], B, sm);
   };
-  auto linear = [&](const float *in, float *out, const float *resid, const HfgLayer &w, int cin, int cout) {
-    ProfScope ps(ctx, "w2v_conv", 2.0 * (double)R * cin * cout);
-    cls_launch_conv(in, out, resid, w.w, w.b, seq(N), cin, cout, 1, max_n[N], B, sm);
+  // aligner_precision 0: hfg_conv_kernel, and w2v_gelu_kernel behind it where `gelu`; 1 / 2: ONE w2v_linear_h_kernel launch, the GELU or the residual in its epilogue
+  bool tiled = true;
+  auto linear = [&](const float *in, float *out, const float *resid, const HfgLayer &w, int cin, int cout, bool gelu = false) {
+    {
+      ProfScope ps(ctx, "w2v_conv", 2.0 * (double)R * cin * cout);
+      if (prec) {
+        const W2vLinearH a{in, out, resid, w.b, seq(N), cin, cout};
+        tiled &= w2v_linear_h_launch(sm, a, w.wh, w.wl, w.ws, prec == 2, gelu ? W2V_EPI_GELU : resid ? W2V_EPI_RESID : W2V_EPI_BIAS, max_n[N], B);
+        return;
+      }
+      cls_launch_conv(in, out, resid, w.w, w.b, seq(N), cin, cout, 1, max_n[N], B, sm);
+    }
+    if (gelu) {
+      ProfScope ps(ctx, "w2v_row", (double)R * cout * 4 * 2);
+      w2v_launch_gelu(out, seq(N), cout, max_n[N], B, sm);
+    }
   };
   {
     ProfScope ps(ctx, "w2v_row", (double)total16 * 4);
@@ -580,11 +605,7 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
     }
     linear(att, h, h, l.out, D, D); // the residual add in the epilogue: an element is read and written by the same thread
     ln(h, y, l.n2, N, D, 0);
-    linear(y, ff, nullptr, l.w1, D, st->FF);
-    {
-      ProfScope ps(ctx, "w2v_row", (double)R * st->FF * 4 * 2);
-      w2v_launch_gelu(ff, seq(N), st->FF, max_n[N], B, sm);
-    }
+    linear(y, ff, nullptr, l.w1, D, st->FF, true);
     linear(ff, h, h, l.w2, st->FF, D);
   }
   ln(h, y, st->enc_n, N, D, 0);
@@ -593,6 +614,7 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
     w2v_launch_head(y, st->head.w, st->head.b, seq(N), D, V, max_n[N], B, st->ids.as<int>(), logits_out ? st->logits.as<float>() : nullptr, sm);
   }
   TTS_HIP(ctx, hipGetLastError());
+  if (!tiled) return fail(ctx, TTS_ERR_LIMIT, "%s: a Linear of the model is outside what w2v_linear_h_kernel tiles (channels a multiple of 64)", fn);
   std::vector<int32_t> ids((size_t)R);
   std::vector<float> lg(logits_out ? (size_t)R * V : 0);
   TTS_HIP(ctx, hipMemcpyAsync(ids.data(), st->ids.p, ids.size() * 4, hipMemcpyDeviceToHost, sm));

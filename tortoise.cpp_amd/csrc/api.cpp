@@ -254,6 +254,10 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     if (!hfg_precision_ok(value)) return fail(c, TTS_ERR_ARG, "hfg_precision: 0 (f32), 1 (fp16) or 2 (split fp16 pairs)");
     c->hfg_precision = (int)value;
   }
+  else if (k == "aligner_precision") { // addition within version 8: operand precision of the aligner's Linears; set before tts_load_aligner, which packs the planes
+    if (!aligner_precision_ok(value)) return fail(c, TTS_ERR_ARG, "aligner_precision: 0 (f32), 1 (fp16) or 2 (split fp16 pairs)");
+    c->aligner_precision = (int)value;
+  }
   else if (k == "prof_eager_every") c->prof_eager_every = value < 1 ? 1 : (int)value;
   else if (k == "stream_cus") {
     // Partition of the chip between two contexts of one process (INTEGRATION.md "two-context pipeline"): value n > 0 re-creates this

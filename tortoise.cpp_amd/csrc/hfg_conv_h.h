@@ -218,3 +218,5 @@ inline void hfg_conv_h_launch(hipStream_t stream, const HfgConv &a, const _Float
 
 } // namespace
 } // namespace tts
+
+#include "w2v_linear_h.h" // w2v_linear_h_kernel: the aligner's Linears on the same operands (option "aligner_precision")
