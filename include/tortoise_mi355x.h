@@ -830,6 +830,12 @@ int tts_aligner_vocab(tts_ctx *ctx, int32_t *vocab_out, int cap, int32_t *blank_
  * bits alone and in a batch, two calls agree) holds within a mode; the bits of two modes differ. On the tests' weights mode 2 is within 5e-5 of the float64
  * restatement (gate 1e-3, every id the float64 argmax); mode 1 is up to 2.6e-2 from it: it does NOT hold the 1e-3 gate, and an id may differ wherever a frame's
  * top-two margin is below twice that distance. The extractor, the positional convolution, the attention, the LayerNorms and the CTC head stay f32 in every mode. */
+/* Option "addon_attn_precision" (0 default; addition within version 8, no prototype changed): the attention of the aligner's encoder (tts_aligner_ids,
+ * tts_align_audio, tts_redact_audio) and of the classifier's attention blocks (tts_classify_audio). 0 = f32 (as before), 1 = fp16 operands, 2 = q, k, v and the
+ * softmax weights each as an fp16 hi + lo pair (three products per step); f32 accumulation and f32 softmax in both. Any other value: TTS_ERR_ARG, nothing changes.
+ * It needs no weights: it is read at call time and may be changed between calls on loaded models; it is independent of "aligner_precision". Within a mode a clip
+ * is the same bits alone and in a batch and two calls agree; the bits of two modes differ. On the tests' weights mode 2 is within 4.5e-5 of the float64
+ * restatement (gate 1e-3, every id the float64 argmax); mode 1 is up to 5.3e-3 from it on the aligner: it does NOT hold the 1e-3 gate. */
 /* audio: the clips back to back, n_samples[c] mono samples at sample_rate[c] Hz. A clip is resampled to 16 kHz in one stage (the audio front end's
  * polyphase resampler; a clip already at 16 kHz reaches the network bit for bit). ids_out [n_clips][frame_stride]: the argmax of every frame, the lowest
  * index on a tie; n_frames_out [n_clips]; logits_out NULL or [n_clips][frame_stride][V]. Only the first n_frames_out[c] entries of a clip are written.

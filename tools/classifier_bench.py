@@ -8,7 +8,11 @@ For 1 clip and for 16 clips of 220 000 samples at 24 kHz (9.17 s each, the crop)
   - the compiler's resource summary of the new kernels (hipcc -Rpass-analysis=kernel-resource-usage on csrc/hifigan.hip, device code only).
 There is no earlier implementation to compare with, and no time is a pass condition. A run without a GPU fails at Engine(0): nothing falls back.
 
-  python tools/classifier_bench.py [--calls 7] [--warm 2] [--models DIR] [--out profiles/classifier.txt]"""
+--attn M[,M..]: instead, option addon_attn_precision at each listed value (0 f32 cls_attn_kernel, 1 fp16, 2 split fp16 pairs; csrc/addon_attn_h.h) on one engine
+(the option is read at call time), the modes interleaved call by call; the cls_attn family's device time per mode and the logits' distance from mode 0. Printed,
+and written where --out names a file (profiles/addon_attn.txt holds it beside the aligner's). Mode 0 must be listed first for the distance.
+
+  python tools/classifier_bench.py [--calls 7] [--warm 2] [--models DIR] [--attn 0,1,2] [--out profiles/classifier.txt]"""
 import argparse
 import os
 import re
@@ -62,12 +66,47 @@ def resources():
     return out
 
 
+def attention(a, modes, eng, say):
+    """option addon_attn_precision (read at call time) on one engine: the modes interleaved call by call"""
+    say("Synthesized-speech classifier (tts_classify_audio), upstream's configuration, synthetic weights: option addon_attn_precision 0 (f32, cls_attn_kernel) | "
+        "1 (fp16 operands) | 2 (fp16 hi + lo pairs), csrc/addon_attn_h.h; tools/classifier_bench.py --attn %s" % ",".join(map(str, modes)))
+    say("clip: %d samples at 24 kHz = %d positions in the attention blocks; one engine, the modes interleaved call by call, %d timed calls each after %d untimed; "
+        "host clock around the synchronous call" % (N, eng.classifier_positions(N), a.calls, a.warm))
+    for B in (1, 16):
+        clips = [sw.classifier_test_wave(N, 50 + i) for i in range(B)]
+        ts = {m: [] for m in modes}
+        for i in range(a.warm + a.calls):
+            for m in modes:
+                eng.set_option("addon_attn_precision", m)
+                t0 = time.perf_counter()
+                eng.classify_audio(clips, 24000)
+                if i >= a.warm:
+                    ts[m].append((time.perf_counter() - t0) * 1e3)
+        say()
+        for m in modes:
+            say("  %2d clips  addon_attn_precision %d  tts_classify_audio  median %8.2f ms  (min %8.2f .. max %8.2f, %d calls)"
+                % (B, m, statistics.median(ts[m]), min(ts[m]), max(ts[m]), len(ts[m])))
+        eng.set_option("prof_stride", 1)
+        logits = {}
+        for m in modes:
+            eng.set_option("addon_attn_precision", m)
+            eng.prof_reset(True)
+            logits[m] = eng.classify_audio(clips, 24000)[1]
+            ms, n, work = eng.prof_get("cls_attn")
+            eng.prof_reset(False)
+            say("  %2d clips  addon_attn_precision %d  cls_attn (GroupNorm, projections and attention of the blocks) %8.2f ms on the device, %4d entries" % (B, m, ms, n))
+        for m in modes:
+            if m:
+                say("  %2d clips  addon_attn_precision %d  largest logit distance from addon_attn_precision 0: %.2e" % (B, m, abs(logits[m] - logits[0]).max()))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=7)
     ap.add_argument("--warm", type=int, default=2)
     ap.add_argument("--models", default=os.path.join(os.environ.get("TTS_SYNTH_DIR", "/tmp/tts_synth"), "classifier_bench"))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "classifier.txt"))
+    ap.add_argument("--out", default="")
+    ap.add_argument("--attn", default="")
     a = ap.parse_args()
     os.makedirs(a.models, exist_ok=True)
     lines = []
@@ -81,6 +120,14 @@ def main():
         open(path + ".done", "w").write("ok")
     eng = pkg.Engine(0)
     eng.load_classifier(path)
+    if a.attn:  # printed; written only where --out names a file (profiles/addon_attn.txt is put together from this and tools/aligner_bench.py --attn)
+        attention(a, [int(m) for m in a.attn.split(",")], eng, say)
+        eng.close()
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
+    a.out = a.out or os.path.join(ROOT, "profiles", "classifier.txt")
     per_clip = conv_flops(N, **sw.CLASSIFIER_UPSTREAM)
     say("Synthesized-speech classifier (tts_classify_audio), upstream's configuration, synthetic weights, tools/classifier_bench.py")
     say("clip: %d samples at 24 kHz = %.2f s = %d positions in the attention blocks; convolutions %.1f GFLOP per clip; %.0f MB of weights; unpinned against upstream, "

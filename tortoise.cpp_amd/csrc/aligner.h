@@ -601,7 +601,7 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
     linear(y, qkv, nullptr, l.qkv, D, 3 * D);
     {
       ProfScope ps(ctx, "w2v_attn", 4.0 * (double)R * max_n[N] * D);
-      cls_launch_attn(qkv, att, seq(N), D, st->H, max_n[N], B, sm);
+      cls_launch_attn_opt(ctx, qkv, att, seq(N), D, st->H, max_n[N], B, sm);
     }
     linear(att, h, h, l.out, D, D); // the residual add in the epilogue: an element is read and written by the same thread
     ln(h, y, l.n2, N, D, 0);

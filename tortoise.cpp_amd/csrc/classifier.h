@@ -28,7 +28,10 @@
 // The attention blocks are f32 throughout (the projections on hfg_conv_kernel's exact-f32 MFMA, scores, softmax and P V in f32 registers), NOT attn_block_run
 // (encoder.h), whose GEMM operands are fp16: with fp16 operands the logits sat 4e-4 .. 1.7e-3 from float64 on an MI355X, outside the 1e-3 gate
 // ("What pins the classifier"). At 215 positions per clip they are under 2 % of the stage's arithmetic either way.
+// Option "addon_attn_precision" 1 / 2 (read at call time; this stage and aligner_run): the attention alone, not the projections, runs on addon_attn_h_kernel
+// (addon_attn_h.h: fp16 operands or fp16 hi + lo pairs on the MFMA, f32 softmax); 0, the default, is cls_attn_kernel below.
 #pragma once
+#include "addon_attn_h.h" // addon_attn_h_kernel: the attention below on the fp16 MFMA (option "addon_attn_precision")
 
 namespace tts {
 
@@ -290,6 +293,26 @@ void cls_launch_attn(const float *qkv, float *out, const int *d_seq, int E, int 
   if (E / heads == 64) cls_attn_kernel<64><<<grid, 256, 0, st>>>(qkv, d_seq, E, out);
   else cls_attn_kernel<128><<<grid, 256, 0, st>>>(qkv, d_seq, E, out);
 }
+// The same attention on addon_attn_h_kernel (option "addon_attn_precision" 1: split false, 2: split true). false: a head dimension that kernel does not tile
+// (64 and 128 only); nothing was launched and the caller takes cls_launch_attn.
+bool cls_launch_attn_h(const float *qkv, float *out, const int *d_seq, int E, int heads, int max_n, int B, bool split, hipStream_t st) {
+  if (!qkv || !out || !d_seq || heads < 1 || heads > 65535 || E < 1 || E % heads || max_n < 1 || B < 1 || B > 65535) return false;
+  const int dh = E / heads;
+  if (dh == 64) {
+    if (split) addon_attn_h_go<64, true>(qkv, out, d_seq, E, heads, max_n, B, st);
+    else addon_attn_h_go<64, false>(qkv, out, d_seq, E, heads, max_n, B, st);
+  } else if (dh == 128) {
+    if (split) addon_attn_h_go<128, true>(qkv, out, d_seq, E, heads, max_n, B, st);
+    else addon_attn_h_go<128, false>(qkv, out, d_seq, E, heads, max_n, B, st);
+  } else return false;
+  return true;
+}
+// the attention of classifier_run and aligner_run: option "addon_attn_precision" 0 (and every head dimension but 64 and 128) is cls_attn_kernel
+void cls_launch_attn_opt(const tts_ctx *ctx, const float *qkv, float *out, const int *d_seq, int E, int heads, int max_n, int B, hipStream_t st) {
+  const int mode = ctx->addon_attn_precision;
+  if (mode && cls_launch_attn_h(qkv, out, d_seq, E, heads, max_n, B, mode == 2, st)) return;
+  cls_launch_attn(qkv, out, d_seq, E, heads, max_n, B, st);
+}
 void cls_launch_down(const ClsDown &a, int max_out, int B, hipStream_t st) {
   const dim3 grid((unsigned)((max_out + CLS_DTM - 1) / CLS_DTM), (unsigned)B, (unsigned)(a.cout / 64));
   cls_down_kernel<<<grid, 256, cls_down_lds(a.taps, a.stride), st>>>(a);
@@ -525,7 +548,7 @@ int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, c
     ProfScope ps(ctx, "cls_attn", 2.0 * (double)rows[depth] * E * (4.0 * E + 2.0 * max_n[depth]));
     cls_launch_gn_silu(x, y, b.n.w, b.n.b, seq(depth), E, max_n[depth], B, part, stat, sm, 0);
     cls_launch_conv(y, qkv, nullptr, b.qkv.w, b.qkv.b, seq(depth), E, 3 * E, 1, max_n[depth], B, sm);
-    cls_launch_attn(qkv, att, seq(depth), E, st->H, max_n[depth], B, sm);
+    cls_launch_attn_opt(ctx, qkv, att, seq(depth), E, st->H, max_n[depth], B, sm);
     cls_launch_conv(att, x, x, b.proj.w, b.proj.b, seq(depth), E, E, 1, max_n[depth], B, sm);
   }
   {
