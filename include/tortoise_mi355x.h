@@ -836,6 +836,7 @@ int tts_aligner_vocab(tts_ctx *ctx, int32_t *vocab_out, int cap, int32_t *blank_
  * It needs no weights: it is read at call time and may be changed between calls on loaded models; it is independent of "aligner_precision". Within a mode a clip
  * is the same bits alone and in a batch and two calls agree; the bits of two modes differ. On the tests' weights mode 2 is within 4.5e-5 of the float64
  * restatement (gate 1e-3, every id the float64 argmax); mode 1 is up to 5.3e-3 from it on the aligner: it does NOT hold the 1e-3 gate. */
+/* Option "addon_conv_precision" (0 default; addition within version 8, no prototype changed): 0 f32 | 1 fp16 operands | 2 fp16 hi + lo pairs for every convolution of tts_classify_audio behind its stem and for the aligner's strided extractor convolutions; set BEFORE tts_load_classifier / tts_load_aligner, which pack the fp16 planes only then (a call in mode 1 or 2 on a model loaded at 0: TTS_ERR_STATE; any other value: TTS_ERR_ARG); independent of the two options above; numbers in profiles/addon_conv.txt. */
 /* audio: the clips back to back, n_samples[c] mono samples at sample_rate[c] Hz. A clip is resampled to 16 kHz in one stage (the audio front end's
  * polyphase resampler; a clip already at 16 kHz reaches the network bit for bit). ids_out [n_clips][frame_stride]: the argmax of every frame, the lowest
  * index on a tie; n_frames_out [n_clips]; logits_out NULL or [n_clips][frame_stride][V]. Only the first n_frames_out[c] entries of a clip are written.

@@ -18,7 +18,12 @@ resource summary of w2v_linear_h_kernel. Writes profiles/aligner_f16.txt.
 loaded with aligner_precision 2 (the option is read at call time), the modes interleaved call by call; the w2v_attn family's device time per mode; every mode's
 largest logit distance from float64. Printed, and written where --out names a file (profiles/addon_attn.txt holds it beside the classifier's).
 
-  python tools/aligner_bench.py [--calls 7] [--warm 2] [--models DIR] [--resources 0|1] [--precision 0,1,2] [--attn 0,1,2] [--out FILE]"""
+--conv-precision M[,M..]: instead, option addon_conv_precision at each listed value (0 f32 cls_down_kernel, 1 fp16, 2 split fp16 pairs; csrc/cls_down_h.h) in ONE
+process: one engine per value, each loaded with it and with aligner_precision 2, and called with addon_attn_precision 2, so the extractor is what moves; the
+values interleaved call by call; the w2v_conv family's device time per value; every value's largest logit distance from float64. Printed, and written where
+--out names a file (profiles/addon_conv.txt holds it beside the classifier's).
+
+  python tools/aligner_bench.py [--calls 7] [--warm 2] [--models DIR] [--resources 0|1] [--precision 0,1,2] [--attn 0,1,2] [--conv-precision 0,1,2] [--out FILE]"""
 import argparse
 import os
 import re
@@ -168,6 +173,53 @@ def attention(a, modes, path, say):
     eng.close()
 
 
+def convolutions(a, modes, path, say):
+    """option addon_conv_precision: one engine per value, each loaded with it and aligner_precision 2 and called with addon_attn_precision 2"""
+    import numpy as np
+    lin, att, frames = flops(N, **sw.ALIGNER_UPSTREAM)
+    engs = {}
+    for m in modes:
+        engs[m] = pkg.Engine(0)
+        engs[m].set_option("aligner_precision", 2)
+        engs[m].set_option("addon_attn_precision", 2)
+        engs[m].set_option("addon_conv_precision", m)
+        engs[m].load_aligner(path)
+    say("wav2vec2 CTC aligner (tts_aligner_ids), upstream's full size, synthetic weights, aligner_precision 2 and addon_attn_precision 2: option addon_conv_precision "
+        "0 (f32, cls_down_kernel) | 1 (fp16 operands) | 2 (fp16 hi + lo pairs), csrc/cls_down_h.h; tools/aligner_bench.py --conv-precision %s" % ",".join(map(str, modes)))
+    say("clip: %d samples at 16 kHz = %d frames; one engine per value in one process, the values interleaved call by call, %d timed calls each after %d untimed; "
+        "host clock around the synchronous call" % (N, frames, a.calls, a.warm))
+    for B in (1, 16):
+        clips = [sw.aligner_test_wave(N, 50 + i) for i in range(B)]
+        ts = {m: [] for m in modes}
+        for i in range(a.warm + a.calls):
+            for m in modes:
+                t0 = time.perf_counter()
+                engs[m].aligner_ids(clips, 16000)
+                if i >= a.warm:
+                    ts[m].append((time.perf_counter() - t0) * 1e3)
+        say()
+        for m in modes:
+            say("  %2d clips  addon_conv_precision %d  tts_aligner_ids  median %8.2f ms  (min %8.2f .. max %8.2f, %d calls)"
+                % (B, m, statistics.median(ts[m]), min(ts[m]), max(ts[m]), len(ts[m])))
+        for m in modes:
+            engs[m].set_option("prof_stride", 1)
+            engs[m].prof_reset(True)
+            engs[m].aligner_ids(clips, 16000)
+            ms, n, work = engs[m].prof_get("w2v_conv")
+            engs[m].prof_reset(False)
+            say("  %2d clips  addon_conv_precision %d  w2v_conv (stem, extractor, Linears, positional convolution, head) %8.2f ms on the device, %4d entries" % (B, m, ms, n))
+    wave = sw.aligner_test_wave(a.distance_samples, 77)
+    want = sw.aligner_forward(sw.read_ggml(path), wave, np.float64)
+    say()
+    say("largest logit distance from float64 (synth_weights.aligner_forward) on a clip of %d samples (%d frames), logits up to %.1f, smallest top-two margin %.4f:"
+        % (len(wave), want.shape[0], np.abs(want).max(), np.diff(np.sort(want, axis=1)[:, -2:], axis=1).min()))
+    for m in modes:
+        ids, lg = engs[m].aligner_ids([wave], 16000, logits=True)
+        say("  addon_conv_precision %d  %.2e   ids that differ from the float64 argmax: %d of %d" % (m, np.abs(lg[0] - want).max(), int((ids[0] != want.argmax(1)).sum()), len(ids[0])))
+    for e in engs.values():
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=7)
@@ -176,10 +228,11 @@ def main():
     ap.add_argument("--resources", type=int, default=1)
     ap.add_argument("--precision", default="")
     ap.add_argument("--attn", default="")
+    ap.add_argument("--conv-precision", default="")
     ap.add_argument("--distance-samples", type=int, default=32000)
     ap.add_argument("--out", default="")
     a = ap.parse_args()
-    if not a.attn:
+    if not a.attn and not a.conv_precision:
         a.out = a.out or os.path.join(ROOT, "profiles", "aligner_f16.txt" if a.precision else "aligner.txt")
     os.makedirs(a.models, exist_ok=True)
     lines = []
@@ -194,6 +247,12 @@ def main():
     if not os.path.exists(cpath + ".done"):
         sw.write_classifier(cpath, seed=1262)
         open(cpath + ".done", "w").write("ok")
+    if a.conv_precision:  # printed; written only where --out names a file (profiles/addon_conv.txt is put together from this and tools/classifier_bench.py --conv-precision)
+        convolutions(a, [int(m) for m in a.conv_precision.split(",")], path, say)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if a.attn:  # printed; written only where --out names a file (profiles/addon_attn.txt is put together from this and tools/classifier_bench.py --attn)
         attention(a, [int(m) for m in a.attn.split(",")], path, say)
         if a.out:

@@ -12,7 +12,12 @@ There is no earlier implementation to compare with, and no time is a pass condit
 (the option is read at call time), the modes interleaved call by call; the cls_attn family's device time per mode and the logits' distance from mode 0. Printed,
 and written where --out names a file (profiles/addon_attn.txt holds it beside the aligner's). Mode 0 must be listed first for the distance.
 
-  python tools/classifier_bench.py [--calls 7] [--warm 2] [--models DIR] [--attn 0,1,2] [--out profiles/classifier.txt]"""
+--conv-precision M[,M..]: instead, option addon_conv_precision at each listed value (0 f32 hfg_conv_kernel / cls_down_kernel, 1 fp16, 2 split fp16 pairs;
+csrc/hfg_conv_h.h, csrc/cls_down_h.h) in ONE process: one engine per value (the option is read at the load, which packs the planes), the values interleaved
+call by call; the cls_conv family's device time per value and the logits' distance from value 0. Printed, and written where --out names a file
+(profiles/addon_conv.txt holds it beside the aligner's). Value 0 must be listed first for the distance.
+
+  python tools/classifier_bench.py [--calls 7] [--warm 2] [--models DIR] [--attn 0,1,2] [--conv-precision 0,1,2] [--out profiles/classifier.txt]"""
 import argparse
 import os
 import re
@@ -100,6 +105,47 @@ def attention(a, modes, eng, say):
                 say("  %2d clips  addon_attn_precision %d  largest logit distance from addon_attn_precision 0: %.2e" % (B, m, abs(logits[m] - logits[0]).max()))
 
 
+def convolutions(a, modes, path, say):
+    """option addon_conv_precision: one engine per value, each loaded with it, the values interleaved call by call"""
+    engs = {}
+    for m in modes:
+        engs[m] = pkg.Engine(0)
+        engs[m].set_option("addon_conv_precision", m)
+        engs[m].load_classifier(path)
+    per_clip = conv_flops(N, **sw.CLASSIFIER_UPSTREAM)
+    say("Synthesized-speech classifier (tts_classify_audio), upstream's configuration, synthetic weights: option addon_conv_precision 0 (f32, hfg_conv_kernel and "
+        "cls_down_kernel) | 1 (fp16 operands) | 2 (fp16 hi + lo pairs), csrc/hfg_conv_h.h and csrc/cls_down_h.h; tools/classifier_bench.py --conv-precision %s"
+        % ",".join(map(str, modes)))
+    say("clip: %d samples at 24 kHz, convolutions %.1f GFLOP per clip; one engine per value in one process, the values interleaved call by call, %d timed calls each "
+        "after %d untimed; host clock around the synchronous call" % (N, per_clip / 1e9, a.calls, a.warm))
+    for B in (1, 16):
+        clips = [sw.classifier_test_wave(N, 50 + i) for i in range(B)]
+        ts = {m: [] for m in modes}
+        for i in range(a.warm + a.calls):
+            for m in modes:
+                t0 = time.perf_counter()
+                engs[m].classify_audio(clips, 24000)
+                if i >= a.warm:
+                    ts[m].append((time.perf_counter() - t0) * 1e3)
+        say()
+        for m in modes:
+            say("  %2d clips  addon_conv_precision %d  tts_classify_audio  median %8.2f ms  (min %8.2f .. max %8.2f, %d calls)"
+                % (B, m, statistics.median(ts[m]), min(ts[m]), max(ts[m]), len(ts[m])))
+        logits = {}
+        for m in modes:
+            engs[m].set_option("prof_stride", 1)
+            engs[m].prof_reset(True)
+            logits[m] = engs[m].classify_audio(clips, 24000)[1]
+            ms, n, work = engs[m].prof_get("cls_conv")
+            engs[m].prof_reset(False)
+            say("  %2d clips  addon_conv_precision %d  cls_conv %8.2f ms on the device, %4d entries, %.1f TFLOP/s" % (B, m, ms, n, work / ms / 1e9))
+        for m in modes:
+            if m:
+                say("  %2d clips  addon_conv_precision %d  largest logit distance from addon_conv_precision 0: %.2e" % (B, m, abs(logits[m] - logits[0]).max()))
+    for e in engs.values():
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=7)
@@ -107,6 +153,7 @@ def main():
     ap.add_argument("--models", default=os.path.join(os.environ.get("TTS_SYNTH_DIR", "/tmp/tts_synth"), "classifier_bench"))
     ap.add_argument("--out", default="")
     ap.add_argument("--attn", default="")
+    ap.add_argument("--conv-precision", default="")
     a = ap.parse_args()
     os.makedirs(a.models, exist_ok=True)
     lines = []
@@ -118,6 +165,12 @@ def main():
     if not os.path.exists(path + ".done"):
         sw.write_classifier(path, seed=1262)
         open(path + ".done", "w").write("ok")
+    if a.conv_precision:  # printed; written only where --out names a file (profiles/addon_conv.txt is put together from this and tools/aligner_bench.py --conv-precision)
+        convolutions(a, [int(m) for m in a.conv_precision.split(",")], path, say)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     eng = pkg.Engine(0)
     eng.load_classifier(path)
     if a.attn:  # printed; written only where --out names a file (profiles/addon_attn.txt is put together from this and tools/aligner_bench.py --attn)

@@ -12,6 +12,8 @@
 //   depth x:  h = h + out(attn(qkv(LN(h))));  h = h + W2 GELU(W1 LN(h))                    w2v_ln_kernel, hfg_conv_kernel, cls_attn_kernel<64>, w2v_gelu_kernel
 // Option "aligner_precision" 1 / 2 (set before tts_load_aligner, which then packs the fp16 planes): the Linears above (projection, qkv, out, W1 + GELU, W2) run on
 // w2v_linear_h_kernel (w2v_linear_h.h: fp16 / split-pair operands, 64-row tiles, the GELU in W1's epilogue); everything else stays f32 as it is.
+// Option "addon_conv_precision" 1 / 2 (set before tts_load_aligner, which then packs the planes of conv[1 .. N - 1]): the extractor's strided convolutions run on
+// cls_down_h_kernel (cls_down_h.h) instead of cls_down_kernel; independent of the two options above.
 //   ids = argmax(Linear(D -> V)(LN(h))), the lowest index on a tie                         w2v_ln_kernel, w2v_head_kernel
 //
 // Device layout: time-major f32 rows [row][channels]; clip s owns the rows [start_s, start_s + n_s) of a level, start_s a multiple of 8. Level 0 of the table is
@@ -423,6 +425,7 @@ struct AlignerState {
   HfgLayer proj, pos, head;
   std::vector<W2vLayer> layers;
   bool planes = false; // the Linears carry fp16 planes (option "aligner_precision" was non-zero at the load)
+  bool conv_planes = false; // conv[1 .. N - 1] carry fp16 planes (option "addon_conv_precision" was non-zero at the load)
   DevWeights dev;
   DevBuf in, wav, part, stat, a, t, h, h2, y, qkv, att, ff, ids, logits;
 };
@@ -450,8 +453,11 @@ int aligner_load(tts_ctx *ctx, const char *path) {
     return e || !st->planes ? e : st->dev.pack(ctx, "aligner", s.w, 1, cin, cout, d);
   };
   st->conv.resize(h->N); st->conv_n.resize(h->N); st->layers.resize(h->depth);
+  st->conv_planes = ctx->addon_conv_precision != 0; // the strided convolutions cls_down_h_kernel may run: the planes of [k_i][C][C], as it lies
   for (int i = 0; i < h->N; i++)
-    if ((rc = up(h->conv[i], st->conv[i])) || (rc = up(h->conv_n[i], st->conv_n[i]))) return rc;
+    if ((rc = up(h->conv[i], st->conv[i])) || (rc = up(h->conv_n[i], st->conv_n[i])) ||
+        (i && st->conv_planes && (rc = st->dev.pack(ctx, "aligner", h->conv[i].w, h->k[i], h->C, h->C, st->conv[i]))))
+      return rc;
   if ((rc = up(h->proj_n, st->proj_n)) || (rc = upl(h->proj, h->C, h->D, st->proj)) || (rc = up(h->pos, st->pos)) || (rc = up(h->enc_n, st->enc_n)) ||
       (rc = up(h->head, st->head)))
     return rc;
@@ -508,6 +514,10 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
   if (!aligner_precision_ok(prec)) return fail(ctx, TTS_ERR_ARG, "%s: aligner_precision %d", fn, prec);
   if (prec && !st->planes)
     return fail(ctx, TTS_ERR_STATE, "%s: aligner_precision %d, but the model was loaded with aligner_precision 0 and holds no fp16 planes: set the option before tts_load_aligner", fn, prec);
+  const int cprec = ctx->addon_conv_precision;
+  if (!addon_conv_precision_ok(cprec)) return fail(ctx, TTS_ERR_ARG, "%s: addon_conv_precision %d", fn, cprec);
+  if (cprec && !st->conv_planes)
+    return fail(ctx, TTS_ERR_STATE, "%s: addon_conv_precision %d, but the model was loaded with addon_conv_precision 0 and holds no fp16 planes: set the option before tts_load_aligner", fn, cprec);
   const int N = st->N, C = st->C, D = st->D, V = st->V;
   ClipIngest clips;
   std::vector<int> frames(B);
@@ -582,7 +592,7 @@ int aligner_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, cons
     d.cin = C; d.cout = C; d.taps = st->k[i]; d.stride = st->s[i]; d.pad = 0;
     {
       ProfScope ps(ctx, "w2v_conv", 2.0 * (double)rows[i + 1] * st->k[i] * C * C);
-      cls_launch_down(d, max_n[i + 1], B, sm);
+      cls_launch_down_opt(cprec, d, st->conv[i], max_n[i + 1], B, sm);
     }
     ln(t, t, st->conv_n[i], i + 1, C, 1);
     std::swap(a, t);

@@ -262,6 +262,10 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     if (!addon_attn_precision_ok(value)) return fail(c, TTS_ERR_ARG, "addon_attn_precision: 0 (f32), 1 (fp16) or 2 (split fp16 pairs)");
     c->addon_attn_precision = (int)value;
   }
+  else if (k == "addon_conv_precision") { // addition within version 8: operand precision of the classifier's convolutions and the aligner's strided convolutions; set before tts_load_classifier / tts_load_aligner, which pack the planes
+    if (!addon_conv_precision_ok(value)) return fail(c, TTS_ERR_ARG, "addon_conv_precision: 0 (f32), 1 (fp16) or 2 (split fp16 pairs)");
+    c->addon_conv_precision = (int)value;
+  }
   else if (k == "prof_eager_every") c->prof_eager_every = value < 1 ? 1 : (int)value;
   else if (k == "stream_cus") {
     // Partition of the chip between two contexts of one process (INTEGRATION.md "two-context pipeline"): value n > 0 re-creates this

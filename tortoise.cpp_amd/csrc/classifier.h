@@ -30,6 +30,8 @@
 // ("What pins the classifier"). At 215 positions per clip they are under 2 % of the stage's arithmetic either way.
 // Option "addon_attn_precision" 1 / 2 (read at call time; this stage and aligner_run): the attention alone, not the projections, runs on addon_attn_h_kernel
 // (addon_attn_h.h: fp16 operands or fp16 hi + lo pairs on the MFMA, f32 softmax); 0, the default, is cls_attn_kernel below.
+// Option "addon_conv_precision" 1 / 2 (set before tts_load_classifier, which then packs the fp16 planes; this stage and aligner_run): every hfg_conv_kernel launch
+// above runs on hfg_conv_h_kernel (hfg_conv_h.h) and cls_down_kernel on cls_down_h_kernel (cls_down_h.h); the stem, GroupNorm, attention and head stay as they are.
 #pragma once
 #include "addon_attn_h.h" // addon_attn_h_kernel: the attention below on the fp16 MFMA (option "addon_attn_precision")
 
@@ -211,6 +213,12 @@ __global__ __launch_bounds__(256) void cls_down_kernel(const ClsDown a) {
   }
 }
 
+} // namespace
+} // namespace tts
+#include "cls_down_h.h" // cls_down_h_kernel: the strided convolution above on the fp16 MFMA (option "addon_conv_precision"); it takes ClsDown
+namespace tts {
+namespace {
+
 // QKVAttentionLegacy of one (clip, head) in f32: out[t] = softmax_s((q[t] c) . (k[s] c)) v[s], c = DH^-1/4 on q and on k as upstream applies it, no mask, no
 // position bias. qkv: rows [row][3 E] = q | k | v, head h at columns h * DH of each (the loader's order). One workgroup = 256 queries; a thread owns one query
 // (q and the output row in registers), the keys stream through LDS 4096 / DH at a time, every lane reading the same key element (a broadcast); the softmax is the
@@ -317,17 +325,34 @@ void cls_launch_down(const ClsDown &a, int max_out, int B, hipStream_t st) {
   const dim3 grid((unsigned)((max_out + CLS_DTM - 1) / CLS_DTM), (unsigned)B, (unsigned)(a.cout / 64));
   cls_down_kernel<<<grid, 256, cls_down_lds(a.taps, a.stride), st>>>(a);
 }
-// a C -> C (or the final k = 1) convolution on hfg_conv_kernel, as bigvgan_run launches it; rate 1
-void cls_launch_conv(const float *in, float *out, const float *resid, const float *w, const float *bias, const int *d_seq, int cin, int cout, int taps, int max_n,
-                     int B, hipStream_t st) {
+// the strided convolution of classifier_run and aligner_run: option "addon_conv_precision" 0 (and every shape cls_down_h_kernel does not tile) is cls_down_kernel;
+// l: the layer, with its fp16 planes where mode is non-zero
+void cls_launch_down_opt(int mode, const ClsDown &a, const HfgLayer &l, int max_out, int B, hipStream_t st) {
+  if (mode && cls_launch_down_h(a, l.wh, l.wl, l.ws, mode == 2, max_out, B, st)) return;
+  cls_launch_down(a, max_out, B, st);
+}
+// the argument of a C -> C (or the final k = 1) convolution: slope 1, rate 1, no conditioning vector, the residual in the epilogue
+HfgConv cls_conv_args(const float *in, float *out, const float *resid, const float *w, const float *bias, const int *d_seq, int cin, int cout, int taps) {
   HfgConv a{};
   a.in = in; a.out = out; a.resid = resid; a.w = w; a.bias = bias; a.cbias = nullptr; a.seq = d_seq;
   a.cin = cin; a.cout = cout; a.taps = taps; a.dil = 1; a.lo = -(taps - 1) / 2; a.phases = 1; a.pad_t = 0; a.rate = 1; a.slope = 1.0f; a.acc_mode = 0;
+  return a;
+}
+// a C -> C (or the final k = 1) convolution on hfg_conv_kernel, as bigvgan_run launches it; rate 1
+void cls_launch_conv(const float *in, float *out, const float *resid, const float *w, const float *bias, const int *d_seq, int cin, int cout, int taps, int max_n,
+                     int B, hipStream_t st) {
+  const HfgConv a = cls_conv_args(in, out, resid, w, bias, d_seq, cin, cout, taps);
   const int nt = cout % 64 == 0 ? 2 : 1;
   const dim3 grid((unsigned)((max_n + HFG_TM - 1) / HFG_TM), (unsigned)B, (unsigned)(cout / (32 * nt)));
   const size_t lds = (size_t)(HFG_TM + taps - 1) * 33 * 4;
   if (nt == 2) hfg_conv_kernel<2><<<grid, 256, lds, st>>>(a);
   else hfg_conv_kernel<1><<<grid, 256, lds, st>>>(a);
+}
+// the same convolution under option "addon_conv_precision": 1 / 2 on hfg_conv_h_kernel with the layer's planes, 0 on hfg_conv_kernel
+void cls_launch_conv_opt(int mode, const float *in, float *out, const float *resid, const HfgLayer &l, const int *d_seq, int cin, int cout, int taps, int max_n, int B,
+                         hipStream_t st) {
+  if (mode) hfg_conv_h_launch(st, cls_conv_args(in, out, resid, l.w, l.b, d_seq, cin, cout, taps), l.wh, l.wl, l.ws, mode == 2, (size_t)max_n, B);
+  else cls_launch_conv(in, out, resid, l.w, l.b, d_seq, cin, cout, taps, max_n, B, st);
 }
 bool cls_pow2_channels(int c) { return c >= 32 && c <= CLS_MAX_C && (c & (c - 1)) == 0; }
 // The tables of classifier_run (and of the test harness): levels 0 .. depth, a Downsample (k 5, stride F, pad 2) between two; every level's records carry
@@ -439,6 +464,7 @@ struct ClassifierState {
   std::vector<ClsRes> res;
   std::vector<HfgLayer> down;
   std::vector<ClsAttn> attn;
+  bool conv_planes = false; // the convolutions carry fp16 planes (option "addon_conv_precision" was non-zero at the load)
   DevWeights dev;
   DevBuf in, wav, h, a, t, part, stat, x, y, qkv, att, out;
 };
@@ -458,16 +484,26 @@ int classifier_load(tts_ctx *ctx, const char *path) {
   std::unique_ptr<ClassifierState> st(new ClassifierState());
   st->b0 = h->b0; st->depth = h->depth; st->K = h->K; st->E = h->E; st->rb = h->rb; st->F = h->F; st->H = h->H;
   auto up = [&](const HostLayer &s, HfgLayer &d) { return st->dev.up(ctx, s, d); };
-  if ((rc = up(h->stem, st->stem)) || (rc = up(h->fin, st->fin)) || (rc = up(h->head, st->head)) || (rc = up(h->fin_n, st->fin_n))) return rc;
+  // a convolution hfg_conv_h_kernel or cls_down_h_kernel may run: beside its f32 tensor the fp16 planes, only when the option asks for them now
+  st->conv_planes = ctx->addon_conv_precision != 0;
+  auto upc = [&](const HostLayer &s, int taps, int cin, int cout, HfgLayer &d) {
+    const int e = up(s, d);
+    return e || !st->conv_planes ? e : st->dev.pack(ctx, "classifier", s.w, taps, cin, cout, d);
+  };
+  const int K = h->K, E = h->E;
+  if ((rc = up(h->stem, st->stem)) || (rc = upc(h->fin, 1, h->b0 << h->depth, E, st->fin)) || (rc = up(h->head, st->head)) || (rc = up(h->fin_n, st->fin_n))) return rc;
   st->res.resize(h->res.size()); st->down.resize(h->down.size()); st->attn.resize(h->attn.size());
-  for (size_t i = 0; i < h->res.size(); i++)
-    if ((rc = up(h->res[i].n1, st->res[i].n1)) || (rc = up(h->res[i].n2, st->res[i].n2)) || (rc = up(h->res[i].ca, st->res[i].ca)) ||
-        (rc = up(h->res[i].cb, st->res[i].cb)))
+  for (size_t i = 0; i < h->res.size(); i++) {
+    const int C = h->b0 << (int)(i / h->rb);
+    if ((rc = up(h->res[i].n1, st->res[i].n1)) || (rc = up(h->res[i].n2, st->res[i].n2)) || (rc = upc(h->res[i].ca, K, C, C, st->res[i].ca)) ||
+        (rc = upc(h->res[i].cb, K, C, C, st->res[i].cb)))
       return rc;
+  }
   for (size_t i = 0; i < h->down.size(); i++)
-    if ((rc = up(h->down[i], st->down[i]))) return rc;
+    if ((rc = upc(h->down[i], 5, h->b0 << (int)i, h->b0 << (int)(i + 1), st->down[i]))) return rc;
   for (size_t i = 0; i < h->attn.size(); i++)
-    if ((rc = up(h->attn[i].n, st->attn[i].n)) || (rc = up(h->attn[i].qkv, st->attn[i].qkv)) || (rc = up(h->attn[i].proj, st->attn[i].proj))) return rc;
+    if ((rc = up(h->attn[i].n, st->attn[i].n)) || (rc = upc(h->attn[i].qkv, 1, E, 3 * E, st->attn[i].qkv)) || (rc = upc(h->attn[i].proj, 1, E, E, st->attn[i].proj)))
+      return rc;
   if (ctx->classifier) classifier_free(ctx->classifier);
   ctx->classifier = st.release();
   return TTS_OK;
@@ -481,6 +517,10 @@ int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, c
   if (!st) return fail(ctx, TTS_ERR_STATE, "tts_load_classifier not called");
   if (!audio || !n_samples || !rates || !prob_out || !resample || B < 1) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", fn);
   if (B > CLS_MAX_CLIPS) return fail(ctx, TTS_ERR_LIMIT, "%s: %d clips (at most %d per call)", fn, B, CLS_MAX_CLIPS);
+  const int cprec = ctx->addon_conv_precision;
+  if (!addon_conv_precision_ok(cprec)) return fail(ctx, TTS_ERR_ARG, "%s: addon_conv_precision %d", fn, cprec);
+  if (cprec && !st->conv_planes)
+    return fail(ctx, TTS_ERR_STATE, "%s: addon_conv_precision %d, but the model was loaded with addon_conv_precision 0 and holds no fp16 planes: set the option before tts_load_classifier", fn, cprec);
   const int depth = st->depth, F = st->F, L = depth + 1;
   ClipIngest clips; // the crop: only TTS_CLS_MAX_SAMPLES of a clip are ever computed
   int rc = clip_ingest(ctx, fn, audio, n_samples, rates, B, 24000, TTS_CLS_MAX_SAMPLES, clips, [](int, int64_t) { return TTS_OK; });
@@ -516,7 +556,7 @@ int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, c
   };
   auto conv = [&](const float *in, float *out, const float *resid, const HfgLayer &w, int l, int cin, int cout, int taps) {
     ProfScope ps(ctx, "cls_conv", 2.0 * (double)rows[l] * taps * cin * cout);
-    cls_launch_conv(in, out, resid, w.w, w.b, seq(l), cin, cout, taps, max_n[l], B, sm);
+    cls_launch_conv_opt(cprec, in, out, resid, w, seq(l), cin, cout, taps, max_n[l], B, sm);
   };
   {
     ProfScope ps(ctx, "cls_conv", 2.0 * (double)rows[0] * 3 * st->b0);
@@ -536,7 +576,7 @@ int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, c
     d.cin = C; d.cout = 2 * C; d.taps = 5; d.stride = F; d.pad = 2;
     {
       ProfScope ps(ctx, "cls_conv", 2.0 * (double)rows[l + 1] * 5 * C * 2 * C);
-      cls_launch_down(d, max_n[l + 1], B, sm);
+      cls_launch_down_opt(cprec, d, st->down[l], max_n[l + 1], B, sm);
     }
     std::swap(h, t);
   }
@@ -547,9 +587,9 @@ int classifier_run(tts_ctx *ctx, const float *audio, const int64_t *n_samples, c
   for (const ClsAttn &b : st->attn) { // one profiler entry per block: GroupNorm, the two projections and the attention between them
     ProfScope ps(ctx, "cls_attn", 2.0 * (double)rows[depth] * E * (4.0 * E + 2.0 * max_n[depth]));
     cls_launch_gn_silu(x, y, b.n.w, b.n.b, seq(depth), E, max_n[depth], B, part, stat, sm, 0);
-    cls_launch_conv(y, qkv, nullptr, b.qkv.w, b.qkv.b, seq(depth), E, 3 * E, 1, max_n[depth], B, sm);
+    cls_launch_conv_opt(cprec, y, qkv, nullptr, b.qkv, seq(depth), E, 3 * E, 1, max_n[depth], B, sm);
     cls_launch_attn_opt(ctx, qkv, att, seq(depth), E, st->H, max_n[depth], B, sm);
-    cls_launch_conv(att, x, x, b.proj.w, b.proj.b, seq(depth), E, E, 1, max_n[depth], B, sm);
+    cls_launch_conv_opt(cprec, att, x, x, b.proj, seq(depth), E, E, 1, max_n[depth], B, sm);
   }
   {
     ProfScope ps(ctx, "cls_attn", 2.0 * (double)B * 2 * E);

@@ -70,6 +70,9 @@
 //   aligner is loaded (f16: fp16 operands, split: fp16 hi + lo pairs; f32 accumulation in both). Another name is a usage error (exit 1, before a model is loaded).
 // --addon-attn-precision f32|f16|split (default f32): the attention of --aligner's encoder and of the classifier, engine option "addon_attn_precision" 0 | 1 | 2
 //   (f16: fp16 operands, split: fp16 hi + lo pairs; f32 accumulation and f32 softmax in both). Another name is a usage error (exit 1, before a model is loaded).
+// --addon-conv-precision f32|f16|split (default f32): the convolutions of the classifier and the strided extractor convolutions of --aligner, engine option
+//   "addon_conv_precision" 0 | 1 | 2, set before either model is loaded (f16: fp16 operands, split: fp16 hi + lo pairs; f32 accumulation in both). Another name is a
+//   usage error (exit 1, before a model is loaded).
 // --stream (with --decoder hifigan; no value) [--stream-stride N, default 16]: one candidate through tts_hifigan_stream. The samples are appended to the WAV as the
 //   callback receives them, while the autoregressive stage is still sampling, and the header's two sizes are fixed at the end: the file is byte for byte the one the
 //   run without --stream writes. --timing 1 prints when the first samples arrived ("[timing] first audio ..."), from the start of the process and from the start of the
@@ -337,6 +340,11 @@ int main(int argc, char **argv) {
       const std::string v = argv[i + 1];
       if (v != "f32" && v != "f16" && v != "split") { fprintf(stderr, "--addon-attn-precision %s: f32, f16 or split\n", v.c_str()); return 1; }
       engine_options.emplace_back("addon_attn_precision", v == "f32" ? 0 : v == "f16" ? 1 : 2);
+    }
+    else if (a == "--addon-conv-precision") {
+      const std::string v = argv[i + 1];
+      if (v != "f32" && v != "f16" && v != "split") { fprintf(stderr, "--addon-conv-precision %s: f32, f16 or split\n", v.c_str()); return 1; }
+      engine_options.emplace_back("addon_conv_precision", v == "f32" ? 0 : v == "f16" ? 1 : 2);
     }
     else if (a == "--diffusion-latent") { diffLatentPath = argv[i + 1]; diffLatentPaths.push_back(diffLatentPath); }
     else if (a == "--split-text") split_ids = std::stoi(argv[i + 1]);
