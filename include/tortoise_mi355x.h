@@ -837,6 +837,7 @@ int tts_aligner_vocab(tts_ctx *ctx, int32_t *vocab_out, int cap, int32_t *blank_
  * is the same bits alone and in a batch and two calls agree; the bits of two modes differ. On the tests' weights mode 2 is within 4.5e-5 of the float64
  * restatement (gate 1e-3, every id the float64 argmax); mode 1 is up to 5.3e-3 from it on the aligner: it does NOT hold the 1e-3 gate. */
 /* Option "addon_conv_precision" (0 default; addition within version 8, no prototype changed): 0 f32 | 1 fp16 operands | 2 fp16 hi + lo pairs for every convolution of tts_classify_audio behind its stem and for the aligner's strided extractor convolutions; set BEFORE tts_load_classifier / tts_load_aligner, which pack the fp16 planes only then (a call in mode 1 or 2 on a model loaded at 0: TTS_ERR_STATE; any other value: TTS_ERR_ARG); independent of the two options above; numbers in profiles/addon_conv.txt. */
+/* Option "dvae_precision" (0 default; addition within version 8, no prototype changed): 0 f32 | 1 fp16 operands | 2 fp16 hi + lo pairs for the DVAE encoder's convolutions behind its stem and for its quantiser (tts_dvae_codes, tts_dvae_codes_audio, tts_dvae_reconstruct*); set BEFORE tts_load_dvae, which packs the fp16 planes only then (a call in mode 1 or 2 on a model loaded at 0: TTS_ERR_STATE; any other value: TTS_ERR_ARG); independent of "addon_conv_precision"; mode 2 keeps the 1e-3 gate on z and float64's codes under a decided-row rule, mode 1 does not hold the gate; numbers in profiles/dvae_f16.txt. */
 /* audio: the clips back to back, n_samples[c] mono samples at sample_rate[c] Hz. A clip is resampled to 16 kHz in one stage (the audio front end's
  * polyphase resampler; a clip already at 16 kHz reaches the network bit for bit). ids_out [n_clips][frame_stride]: the argmax of every frame, the lowest
  * index on a tie; n_frames_out [n_clips]; logits_out NULL or [n_clips][frame_stride][V]. Only the first n_frames_out[c] entries of a clip are written.

@@ -10,8 +10,12 @@ For one 9.2 s clip, 16 such clips, and 64 clips of 20 s (the shape of a fine-tun
   - with --resources 1 the compiler's resource summary of the new kernels (hipcc -Rpass-analysis=kernel-resource-usage on csrc/hifigan.hip, device code only);
     --resources 2 appends that summary alone to --out and needs no GPU.
 There is no earlier implementation to compare with, and no time is a pass condition. A run without a GPU fails at Engine(0): nothing falls back.
+--precision M[,M..]: instead, option dvae_precision at each listed value (0 f32, 1 fp16, 2 split fp16 pairs; csrc/dvae_vq_h.h, csrc/cls_down_h.h,
+csrc/hfg_conv_h.h) in ONE process: one engine per value, each loaded with it, the values interleaved call by call; the families' device time per value; every
+value's z distance from float64 and the codes under the decided-row rule on one 2 s clip at full size (tests/dvae_ref.py, the bound of
+tests/test_dvae_vq_h_gpu.py). Writes profiles/dvae_f16.txt unless --out is given.
 
-  python tools/dvae_bench.py [--calls 7] [--warm 2] [--models DIR] [--resources 0|1|2] [--out profiles/dvae.txt]"""
+  python tools/dvae_bench.py [--calls 7] [--warm 2] [--models DIR] [--resources 0|1|2] [--precision 0,1,2] [--out profiles/dvae.txt]"""
 import argparse
 import os
 import re
@@ -61,9 +65,9 @@ def resources():
                            capture_output=True, text=True, timeout=900)
     out, cur = {}, None
     for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: \S*?(dvae_\w+?_kernel)", line)
+        m = re.search(r"Function Name: \S*?(dvae_\w+?_kernel)(?:ILb([01])E)?", line)
         if m:
-            cur = m.group(1)
+            cur = m.group(1) + ("<SPLIT=%s>" % m.group(2) if m.group(2) else "")
             out[cur] = {}
             continue
         if "Function Name:" in line:
@@ -86,14 +90,67 @@ def resource_lines():
     return lines
 
 
+def precision_run(a, modes, path, say):
+    """option dvae_precision: one engine per value, each loaded with it, the values interleaved call by call"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import dvae_ref as R
+    import test_dvae_vq_h_gpu as K
+    engs = {}
+    for m in modes:
+        engs[m] = pkg.Engine(0)
+        engs[m].set_option("dvae_precision", m)
+        engs[m].load_dvae(path)
+    say("DVAE encoder (tts_dvae_codes_audio), upstream's full size, synthetic weights: option dvae_precision 0 (f32: cls_down_kernel, hfg_conv_kernel, dvae_vq_kernel), "
+        "1 (fp16) and 2 (fp16 hi + lo pairs: cls_down_h_kernel, hfg_conv_h_kernel, dvae_vq_h_kernel), tools/dvae_bench.py --precision")
+    say("one engine per value in one process, the values interleaved call by call; host clock around the synchronous call; %d timed calls after %d untimed" % (a.calls, a.warm))
+    for B, sec in SHAPES:
+        n = int(sec * RATE)
+        clips = [clip(n, 50 + i) for i in range(B)]
+        ts = {m: [] for m in modes}
+        for i in range(a.warm + a.calls):
+            for m in modes:
+                t0 = time.perf_counter()
+                engs[m].dvae_codes_audio(clips, RATE)
+                if i >= a.warm:
+                    ts[m].append((time.perf_counter() - t0) * 1e3)
+        say()
+        for m in modes:
+            say("  %2d clips of %4.1f s  dvae_precision %d  tts_dvae_codes_audio  median %8.2f ms  (min %8.2f .. max %8.2f, %d calls)"
+                % (B, sec, m, statistics.median(ts[m]), min(ts[m]), max(ts[m]), len(ts[m])))
+        for m in modes:
+            engs[m].set_option("prof_stride", 1)
+            engs[m].prof_reset(True)
+            engs[m].dvae_codes_audio(clips, RATE)
+            got = {f: engs[m].prof_get(f) for f in FAMILIES[:2]}
+            engs[m].prof_reset(False)
+            say("  %2d clips of %4.1f s  dvae_precision %d  on the device: " % (B, sec, m)
+                + ",  ".join("%s %8.3f ms (%.1f TFLOP/s)" % (f, got[f][0], got[f][2] / max(got[f][0], 1e-9) / 1e9) for f in FAMILIES[:2]))
+    say()
+    say("distance from float64 on one clip of %d mel frames (%d codes) at full size; decided: the float64 gap exceeds the two codes' kernel bounds" % (R.FULL_FRAMES, R.rows(R.FULL_FRAMES)))
+    t, mel = sw.read_ggml(path), R.mel(R.FULL_FRAMES)
+    ref = R.forward(t, mel)
+    E = t["dvae.codebook.embed"]
+    for m in modes:
+        codes, z = engs[m].dvae_codes([mel], z=True)
+        b = K.bound(ref["z"], E, m) if m else R.vq64(ref["z"], E)[1]
+        fails, out = R.judge_end_to_end(codes[0], z[0], ref["z"], ref["s"], b, E)
+        say("  dvae_precision %d  z max abs %.2e (z up to %.1f)  codes that differ from float64's: %d of %d  decided share %.4f  rows under the end-to-end margin %.4f  rule failures %d"
+            % (m, np.abs(z[0] - ref["z"]).max(), np.abs(ref["z"]).max(), int((codes[0] != ref["codes"]).sum()), len(codes[0]),
+               1.0 - R.judge(ref["codes"], ref["s"], b)[1], out, len(fails)))
+    for e in engs.values():
+        e.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--calls", type=int, default=7)
     ap.add_argument("--warm", type=int, default=2)
     ap.add_argument("--models", default=os.path.join(os.environ.get("TTS_SYNTH_DIR", "/tmp/tts_synth"), "dvae_bench"))
     ap.add_argument("--resources", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dvae.txt"))
+    ap.add_argument("--precision", default="")
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "dvae_f16.txt" if a.precision else "dvae.txt")
     if a.resources == 2:
         with open(a.out, "a") as f:
             f.write("\n".join(resource_lines()) + "\n")
@@ -108,6 +165,11 @@ def main():
     if not os.path.exists(path + ".done"):
         sw.write_dvae(path, seed=1283)
         open(path + ".done", "w").write("ok")
+    if a.precision:
+        precision_run(a, [int(v) for v in a.precision.split(",")], path, say)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return
     eng = pkg.Engine(0)
     eng.load_dvae(path)
     say("DVAE encoder (tts_dvae_codes_audio), upstream's full size, synthetic weights, f32 throughout, tools/dvae_bench.py")

@@ -266,6 +266,10 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
     if (!addon_conv_precision_ok(value)) return fail(c, TTS_ERR_ARG, "addon_conv_precision: 0 (f32), 1 (fp16) or 2 (split fp16 pairs)");
     c->addon_conv_precision = (int)value;
   }
+  else if (k == "dvae_precision") { // addition within version 8: operand precision of the DVAE encoder's convolutions behind its stem and of its quantiser; set before tts_load_dvae, which packs the planes
+    if (!dvae_precision_ok(value)) return fail(c, TTS_ERR_ARG, "dvae_precision: 0 (f32), 1 (fp16) or 2 (split fp16 pairs)");
+    c->dvae_precision = (int)value;
+  }
   else if (k == "prof_eager_every") c->prof_eager_every = value < 1 ? 1 : (int)value;
   else if (k == "stream_cus") {
     // Partition of the chip between two contexts of one process (INTEGRATION.md "two-context pipeline"): value n > 0 re-creates this

@@ -73,6 +73,9 @@
 // --addon-conv-precision f32|f16|split (default f32): the convolutions of the classifier and the strided extractor convolutions of --aligner, engine option
 //   "addon_conv_precision" 0 | 1 | 2, set before either model is loaded (f16: fp16 operands, split: fp16 hi + lo pairs; f32 accumulation in both). Another name is a
 //   usage error (exit 1, before a model is loaded).
+// --dvae-precision f32|f16|split (default f32): the convolutions behind the stem and the quantiser of --dvae's encoder (--codes-from, --revoice), engine option
+//   "dvae_precision" 0 | 1 | 2, set before the model is loaded (f16: fp16 operands, split: fp16 hi + lo pairs; f32 accumulation in both). Another name is a usage
+//   error (exit 1, before a model is loaded).
 // --stream (with --decoder hifigan; no value) [--stream-stride N, default 16]: one candidate through tts_hifigan_stream. The samples are appended to the WAV as the
 //   callback receives them, while the autoregressive stage is still sampling, and the header's two sizes are fixed at the end: the file is byte for byte the one the
 //   run without --stream writes. --timing 1 prints when the first samples arrived ("[timing] first audio ..."), from the start of the process and from the start of the
@@ -346,6 +349,11 @@ int main(int argc, char **argv) {
       if (v != "f32" && v != "f16" && v != "split") { fprintf(stderr, "--addon-conv-precision %s: f32, f16 or split\n", v.c_str()); return 1; }
       engine_options.emplace_back("addon_conv_precision", v == "f32" ? 0 : v == "f16" ? 1 : 2);
     }
+    else if (a == "--dvae-precision") {
+      const std::string v = argv[i + 1];
+      if (v != "f32" && v != "f16" && v != "split") { fprintf(stderr, "--dvae-precision %s: f32, f16 or split\n", v.c_str()); return 1; }
+      engine_options.emplace_back("dvae_precision", v == "f32" ? 0 : v == "f16" ? 1 : 2);
+    }
     else if (a == "--diffusion-latent") { diffLatentPath = argv[i + 1]; diffLatentPaths.push_back(diffLatentPath); }
     else if (a == "--split-text") split_ids = std::stoi(argv[i + 1]);
     else if (a == "--sampler") { sampler = argv[i + 1]; have_sampler = true; }
@@ -453,6 +461,8 @@ int main(int argc, char **argv) {
     if (!dctx) { fprintf(stderr, "tts_create(%d) failed: no HIP device (this engine has no CPU path)\n", device); return 1; }
     auto leave = [&](const char *what) { const int rc = die(dctx, what); tts_destroy(dctx); return rc; };
     if (tts_load_dvae_decoder(dctx, dvaeDecPath.c_str())) return leave("dvae_decoder_model_load");
+    for (const auto &kv : engine_options) // this context is the DVAE's own: --dvae-precision reaches it before the encoder is loaded
+      if (kv.first == "dvae_precision" && tts_set_option(dctx, kv.first.c_str(), kv.second)) return leave("--option");
     if (rec && tts_load_dvae(dctx, dvaePath.c_str())) return leave("dvae_model_load");
     const int ch = tts_dvae_decoder_channels(dctx);
     std::vector<float> mel, l1(B), mse(B);
@@ -538,6 +548,8 @@ int main(int argc, char **argv) {
     if (!read_norms(melNormsPath, norms)) return 1;
     tts_ctx *dctx = tts_create(device);
     if (!dctx) { fprintf(stderr, "tts_create(%d) failed: no HIP device (this engine has no CPU path)\n", device); return 1; }
+    for (const auto &kv : engine_options) // this context is the DVAE's own: --dvae-precision reaches it before the encoder is loaded
+      if (kv.first == "dvae_precision" && tts_set_option(dctx, kv.first.c_str(), kv.second)) { const int rc = die(dctx, "--option"); tts_destroy(dctx); return rc; }
     if (tts_load_dvae(dctx, dvaePath.c_str())) { const int rc = die(dctx, "dvae_model_load"); tts_destroy(dctx); return rc; }
     tts_voice_audio_opts vo;
     vo.struct_size = sizeof vo;

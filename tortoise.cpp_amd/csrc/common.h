@@ -206,6 +206,7 @@ struct tts_ctx {
   int hfg_precision = 0;   // option "hfg_precision": operands of the convolutions of hifigan_run and bigvgan_run: 0 = f32 (hfg_conv_kernel), 1 = fp16, 2 = fp16 hi + lo pairs (hfg_conv_h_kernel)
   int aligner_precision = 0; // option "aligner_precision": operands of the Linears of aligner_run: 0 = f32 (hfg_conv_kernel), 1 = fp16, 2 = fp16 hi + lo pairs (w2v_linear_h_kernel); read by tts_load_aligner too
   int addon_conv_precision = 0; // option "addon_conv_precision": the convolutions of classifier_run and the strided convolutions of aligner_run: 0 = f32 (hfg_conv_kernel, cls_down_kernel), 1 = fp16, 2 = fp16 hi + lo pairs (hfg_conv_h_kernel, cls_down_h_kernel); read by tts_load_classifier and tts_load_aligner too
+  int dvae_precision = 0;  // option "dvae_precision": the DVAE encoder's convolutions behind its stem and its quantiser: 0 = f32 (cls_down_kernel, hfg_conv_kernel, dvae_vq_kernel), 1 = fp16, 2 = fp16 hi + lo pairs (cls_down_h_kernel, hfg_conv_h_kernel, dvae_vq_h_kernel); read by tts_load_dvae too
   int addon_attn_precision = 0; // option "addon_attn_precision": the attention of aligner_run and classifier_run: 0 = f32 (cls_attn_kernel), 1 = fp16, 2 = fp16 hi + lo pairs (addon_attn_h_kernel); read at call time
   int diff_graph = 1;      // option "diff_graph": the diffusion step is captured once per call and replayed (0: every step launched eagerly)
   int prof_eager_every = 8; // while a diff_* family is profiled, every Nth diffusion step runs eagerly with its event pairs; the others replay the graph
@@ -226,6 +227,8 @@ inline bool aligner_precision_ok(double v) { return v == 0 || v == 1 || v == 2; 
 inline bool addon_attn_precision_ok(double v) { return v == 0 || v == 1 || v == 2; }
 // Option "addon_conv_precision": the values tts_set_option stores and classifier_run / aligner_run accept (0 f32, 1 fp16, 2 split fp16 pairs); NaN is none of them
 inline bool addon_conv_precision_ok(double v) { return v == 0 || v == 1 || v == 2; }
+// Option "dvae_precision": the values tts_set_option stores and the DVAE stage accepts (0 f32, 1 fp16, 2 split fp16 pairs); NaN is none of them
+inline bool dvae_precision_ok(double v) { return v == 0 || v == 1 || v == 2; }
 
 // n draws of the context's normal distribution (sample_normal_noise, main.cpp:4695-4701: std::normal_distribution<double> over std::mt19937, values narrowed to float) into
 // dst, leaving generator and distribution in exactly the state n single draws leave them in. Large counts take a two-phase form of the same algorithm (host_logic.cpp).

@@ -15,6 +15,11 @@
 // (band-major, clip s at 80 x the frames before it: what the audio front end writes), level i the output of strided layer i - 1. No kernel reads or writes a row
 // outside the clip it works on and none uses atomics: two runs agree bit for bit, and a clip alone gives the bits of the clip in a batch.
 //
+// Option "dvae_precision" 1 / 2 (set before tts_load_dvae, which then packs the fp16 planes of the convolutions behind the stem and of the codebook; fp16 operands
+// or fp16 hi + lo pairs, f32 accumulation): the strided layers behind the stem run on cls_down_h_kernel (cls_down_h.h; the row ReLU stays behind it), the
+// ResBlocks' convolutions and the final k = 1 on hfg_conv_h_kernel (hfg_conv_h.h) and the quantiser on dvae_vq_h_kernel (dvae_vq_h.h); the stem, the ReLU and
+// the slab reduce stay as they are. 0, the default, launches exactly the f32 kernels above. DESIGN.md, "What pins the DVAE on the fp16 MFMA".
+//
 // What the kernels can tile (dvae_parse refuses everything else, TTS_ERR_FORMAT): 1 .. 128 mel channels; odd kernel sizes up to 7; stride 1 .. 4; every
 // channel count a multiple of 64 up to 4096; codebook dim a multiple of 32 up to 512 (the quantiser keeps 64 rows of it in LDS); tokens a multiple of 32 up to 65536.
 #pragma once
@@ -198,6 +203,12 @@ __global__ __launch_bounds__(256) void dvae_vq_reduce_kernel(const float *__rest
   if (best) best[r] = v;
 }
 
+} // namespace
+} // namespace tts
+#include "dvae_vq_h.h" // dvae_vq_h_kernel: the quantiser above on the fp16 MFMA (option "dvae_precision"); it ends in dvae_vq_reduce_kernel too
+namespace tts {
+namespace {
+
 // ---- the launches, stated once for dvae_run and for the test harness (testlib/dvae_harness.hip) ----
 void dvae_launch_stem(const DvaeStem &a, int max_out, int B, hipStream_t st) {
   const dim3 grid((unsigned)((max_out + DVS_ROWS - 1) / DVS_ROWS), (unsigned)B, (unsigned)((a.cout + 255) / 256));
@@ -211,17 +222,32 @@ void dvae_launch_down(const ClsDown &a, const int *d_seq_out, int max_out, int B
   cls_launch_down(a, max_out, B, st);
   dvae_launch_relu(a.out, d_seq_out, a.cout, max_out, B, st);
 }
-// cls_launch_conv with the input activation: slope 1 = none, slope 0 = a ReLU in hfg_conv_kernel's input stage
-void dvae_launch_conv(const float *in, float *out, const float *resid, const float *w, const float *bias, const int *d_seq, int cin, int cout, int taps, float slope,
-                      int max_n, int B, hipStream_t st) {
+// the same layer under option "dvae_precision" 1 / 2: cls_down_h_kernel with the layer's planes (a shape it does not tile keeps cls_down_kernel), the same ReLU
+void dvae_launch_down_h(const ClsDown &a, const HfgLayer &l, bool split, const int *d_seq_out, int max_out, int B, hipStream_t st) {
+  if (!cls_launch_down_h(a, l.wh, l.wl, l.ws, split, max_out, B, st)) cls_launch_down(a, max_out, B, st);
+  dvae_launch_relu(a.out, d_seq_out, a.cout, max_out, B, st);
+}
+// the argument of a ResBlock convolution or of the final k = 1: rate 1, no conditioning vector, the residual in the epilogue
+HfgConv dvae_conv_args(const float *in, float *out, const float *resid, const float *w, const float *bias, const int *d_seq, int cin, int cout, int taps, float slope) {
   HfgConv a{};
   a.in = in; a.out = out; a.resid = resid; a.w = w; a.bias = bias; a.cbias = nullptr; a.seq = d_seq;
   a.cin = cin; a.cout = cout; a.taps = taps; a.dil = 1; a.lo = -(taps - 1) / 2; a.phases = 1; a.pad_t = 0; a.rate = 1; a.slope = slope; a.acc_mode = 0;
+  return a;
+}
+// cls_launch_conv with the input activation: slope 1 = none, slope 0 = a ReLU in hfg_conv_kernel's input stage
+void dvae_launch_conv(const float *in, float *out, const float *resid, const float *w, const float *bias, const int *d_seq, int cin, int cout, int taps, float slope,
+                      int max_n, int B, hipStream_t st) {
+  const HfgConv a = dvae_conv_args(in, out, resid, w, bias, d_seq, cin, cout, taps, slope);
   const int nt = cout % 64 == 0 ? 2 : 1;
   const dim3 grid((unsigned)((max_n + HFG_TM - 1) / HFG_TM), (unsigned)B, (unsigned)(cout / (32 * nt)));
   const size_t lds = (size_t)(HFG_TM + taps - 1) * 33 * 4;
   if (nt == 2) hfg_conv_kernel<2><<<grid, 256, lds, st>>>(a);
   else hfg_conv_kernel<1><<<grid, 256, lds, st>>>(a);
+}
+// the same convolution under option "dvae_precision" 1 / 2: hfg_conv_h_kernel with the layer's planes; the activation is the one of its input stage too
+void dvae_launch_conv_h(const float *in, float *out, const float *resid, const HfgLayer &l, bool split, const int *d_seq, int cin, int cout, int taps, float slope,
+                        int max_n, int B, hipStream_t st) {
+  hfg_conv_h_launch(st, dvae_conv_args(in, out, resid, l.w, l.b, d_seq, cin, cout, taps, slope), l.wh, l.wl, l.ws, split, (size_t)max_n, B);
 }
 // best: null or [R]
 hipError_t dvae_launch_vq(const DvaeVq &a, int *codes, float *best, hipStream_t st) {
@@ -345,6 +371,8 @@ struct DvaeState {
   std::vector<std::array<DvaeConv, 3>> res;
   DvaeConv head;
   float *E = nullptr, *e2 = nullptr;
+  HfgLayer cb;         // w = E, b = e2 and, with planes, the codebook's fp16 planes and one scale per code (dvae_vq_h_kernel)
+  bool planes = false; // the convolutions behind the stem and the codebook carry fp16 planes (option "dvae_precision" was non-zero at the load)
   DevWeights dev;
   DevBuf mel, tab, a, b, h, z, pv, pi, codes;
   LevelTable lt; // the layout dvae_begin made, for dvae_run (and the source of its asynchronous upload)
@@ -364,17 +392,21 @@ int dvae_load(tts_ctx *ctx, const char *path) {
   (void)hipSetDevice(ctx->device);
   std::unique_ptr<DvaeState> st(new DvaeState());
   st->L = h->L; st->blocks = h->blocks; st->cin = h->cin; st->H = h->H; st->dim = h->dim; st->N = h->N; st->stride = h->stride;
-  auto layer = [&](const DvaeHostConv &s, DvaeConv &d) -> int {
+  st->planes = ctx->dvae_precision != 0; // beside the f32 tensors the fp16 planes, only when the option asks for them now
+  auto layer = [&](const DvaeHostConv &s, DvaeConv &d, bool pack = true) -> int {
     d.cin = s.cin; d.cout = s.cout; d.k = s.k;
-    return st->dev.up(ctx, s, d);
+    const int e = st->dev.up(ctx, s, d);
+    return e || !pack || !st->planes ? e : st->dev.pack(ctx, "DVAE", s.w, s.k, s.cin, s.cout, d);
   };
   st->down.resize(h->L); st->res.resize(h->blocks);
   for (int i = 0; i < h->L; i++)
-    if ((rc = layer(h->down[i], st->down[i]))) return rc;
+    if ((rc = layer(h->down[i], st->down[i], i > 0))) return rc; // the stem stays f32
   for (int j = 0; j < h->blocks; j++)
     for (int q = 0; q < 3; q++)
       if ((rc = layer(h->res[j][q], st->res[j][q]))) return rc;
   if ((rc = layer(h->head, st->head)) || (rc = st->dev.up(ctx, h->E, &st->E)) || (rc = st->dev.up(ctx, h->e2, &st->e2))) return rc;
+  st->cb.w = st->E; st->cb.b = st->e2;
+  if (st->planes && (rc = st->dev.pack(ctx, "DVAE", h->E, 1, h->dim, h->N, st->cb))) return rc; // [dim][tokens] as it lies: one scale per code
   if (ctx->dvae) dvae_free(ctx->dvae);
   ctx->dvae = st.release();
   return TTS_OK;
@@ -390,6 +422,10 @@ int dvae_begin(tts_ctx *ctx, const char *fn, const int32_t *frames, int n_clips,
   DvaeState *st = ctx->dvae;
   if (!st) return fail(ctx, TTS_ERR_STATE, "tts_load_dvae not called");
   if (!frames || n_clips < 1 || code_stride < 1 || !d_mel) return fail(ctx, TTS_ERR_ARG, "%s: bad argument", fn);
+  const int prec = ctx->dvae_precision;
+  if (!dvae_precision_ok(prec)) return fail(ctx, TTS_ERR_ARG, "%s: dvae_precision %d", fn, prec);
+  if (prec && !st->planes)
+    return fail(ctx, TTS_ERR_STATE, "%s: dvae_precision %d, but the model was loaded with dvae_precision 0 and holds no fp16 planes: set the option before tts_load_dvae", fn, prec);
   if (n_clips > DVAE_MAX_CLIPS) return fail(ctx, TTS_ERR_LIMIT, "%s: %d clips (at most %d per call)", fn, n_clips, DVAE_MAX_CLIPS);
   const int B = n_clips, L = st->L;
   for (int s = 0; s < B; s++) {
@@ -425,6 +461,7 @@ int dvae_begin(tts_ctx *ctx, const char *fn, const int32_t *frames, int n_clips,
 int dvae_encode(tts_ctx *ctx) {
   DvaeState *st = ctx->dvae;
   const int B = st->lt.B, L = st->L, D = st->dim;
+  const int prec = st->planes ? ctx->dvae_precision : 0; // dvae_begin refused a non-zero value on a model without planes
   const std::vector<int> &max_n = st->lt.max_n;
   const std::vector<int64_t> &total = st->lt.rows;
   const int64_t R = total[L];
@@ -448,11 +485,13 @@ int dvae_encode(tts_ctx *ctx) {
     d.in = dst(i - 1); d.out = dst(i); d.w = c.w; d.bias = c.b; d.seq_in = seq(i); d.seq_out = seq(i + 1);
     d.cin = c.cin; d.cout = c.cout; d.taps = c.k; d.stride = st->stride; d.pad = (c.k - 1) / 2;
     ProfScope ps(ctx, "dvae_conv", 2.0 * (double)total[i + 1] * c.k * c.cin * c.cout);
-    dvae_launch_down(d, seq(i + 1), max_n[i + 1], B, sm);
+    if (prec) dvae_launch_down_h(d, c, prec == 2, seq(i + 1), max_n[i + 1], B, sm);
+    else dvae_launch_down(d, seq(i + 1), max_n[i + 1], B, sm);
   }
   auto conv = [&](const float *in, float *out, const float *resid, const DvaeConv &c, float slope) {
     ProfScope ps(ctx, "dvae_conv", 2.0 * (double)R * c.k * c.cin * c.cout);
-    dvae_launch_conv(in, out, resid, c.w, c.b, seq(L), c.cin, c.cout, c.k, slope, max_n[L], B, sm);
+    if (prec) dvae_launch_conv_h(in, out, resid, c, prec == 2, seq(L), c.cin, c.cout, c.k, slope, max_n[L], B, sm);
+    else dvae_launch_conv(in, out, resid, c.w, c.b, seq(L), c.cin, c.cout, c.k, slope, max_n[L], B, sm);
   };
   for (const auto &r : st->res) {
     conv(h, a, nullptr, r[0], 1.0f); // no activation on a block's input
@@ -460,7 +499,12 @@ int dvae_encode(tts_ctx *ctx) {
     conv(b, h, h, r[2], 0.0f);       // the skip in the epilogue: an element is read and written by the same thread
   }
   conv(h, z, nullptr, st->head, 1.0f);
-  {
+  if (prec) {
+    DvaeVqH q{};
+    q.z = z; q.eh = st->cb.wh; q.el = st->cb.wl; q.es = st->cb.ws; q.e2 = st->e2; q.pv = st->pv.as<float>(); q.pi = st->pi.as<int>(); q.R = (int)R; q.D = D; q.N = st->N;
+    ProfScope ps(ctx, "dvae_vq", 2.0 * (double)R * D * st->N);
+    TTS_HIP(ctx, dvae_launch_vq_h(q, prec == 2, st->codes.as<int>(), nullptr, sm));
+  } else {
     DvaeVq q{};
     q.z = z; q.E = st->E; q.e2 = st->e2; q.pv = st->pv.as<float>(); q.pi = st->pi.as<int>(); q.R = (int)R; q.D = D; q.N = st->N;
     ProfScope ps(ctx, "dvae_vq", 2.0 * (double)R * D * st->N);

@@ -2,7 +2,7 @@
 // included here whole and unchanged): host arrays in, host arrays out, one launch (the strided layer: cls_down_kernel and its ReLU; the quantiser: its kernel
 // and the slab reduce) per call on a stream of its own, through the dvae_launch_* functions dvae_run itself calls. Built as libtts_dvae_test.so next to the
 // product library (together with csrc/host_logic.cpp, which the host half calls); it is not part of the product (tests/test_dvae_kernels_gpu.py and
-// tests/test_dvae_cpu.py are the only users).
+// tests/test_dvae_cpu.py are the only users). tts_dvae_test_run_vq_h runs a quantiser case on dvae_vq_h_kernel (csrc/dvae_vq_h.h; tests/test_dvae_vq_h_gpu.py).
 //
 // The GPU is shared: a case is validated completely BEFORE any HIP call (the clip tables, every address the chosen kernel reads or writes), and every device
 // buffer carries a canary margin in front and behind, inside the same allocation, that is copied back with the payload; the margins of the input buffers hold NaNs.
@@ -211,5 +211,44 @@ int tts_dvae_test_run(const tts_dvae_case *cp) {
   if (c.kind == TTS_DVAE_TEST_VQ) HT(out2.get_all(c.out2));
   return (int)(e != hipSuccess ? e : es);
 }
+
+// A VQ case on the fp16 MFMA (option "dvae_precision": mode 1 fp16 operands, 2 fp16 hi + lo pairs): the codebook packed by hfg_pack_launch with pt = 1, as
+// dvae_load packs it, then dvae_launch_vq_h (dvae_vq_h_kernel and the slab reduce), as dvae_encode calls it. The case, its checks and its outputs are
+// tts_dvae_test_run's; every address dvae_vq_h_kernel reads or writes lies inside the payloads those checks size (the planes: dim x tokens halves each, the
+// scales 2 x tokens floats). (tests/test_dvae_vq_h_gpu.py)
+int tts_dvae_test_run_vq_h(const tts_dvae_case *cp, int mode) {
+  Plan p;
+  if (!cp || cp->kind != TTS_DVAE_TEST_VQ || !valid(*cp, p) || (mode != 1 && mode != 2)) return (int)hipErrorInvalidValue;
+  const tts_dvae_case &c = *cp;
+  const int R = c.rows, D = c.cin, N = c.cout, slabs = dvae_vq_slabs(N);
+  std::vector<float> e2((size_t)N);
+  if (c.bias) memcpy(e2.data(), c.bias, (size_t)N * 4);
+  else dvae_code_norms(c.w, D, N, e2.data());
+  Dev in, out, out2, w, planes, bias, pv, pi;
+  HT(in.alloc((size_t)R * D * 4, POISON)); HT(in.put(c.in));
+  HT(w.alloc((size_t)D * N * 4, POISON)); HT(w.put(c.w));
+  HT(planes.alloc((size_t)D * N * 4 + (size_t)N * 8, POISON)); // hi | lo | 1 / s, s: DevWeights::pack's one allocation
+  HT(bias.alloc((size_t)N * 4, POISON)); HT(bias.put(e2.data()));
+  HT(pv.alloc((size_t)slabs * R * 4, TTS_DVAE_TEST_SENTINEL)); HT(pi.alloc((size_t)slabs * R * 4, TTS_DVAE_TEST_SENTINEL));
+  HT(out.alloc((size_t)R * 4, TTS_DVAE_TEST_SENTINEL)); HT(out2.alloc((size_t)R * 4, TTS_DVAE_TEST_SENTINEL));
+  HT(hipDeviceSynchronize()); // the fills above ran on the null stream
+  hipStream_t s;
+  HT(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  DvaeVqH q{};
+  _Float16 *eh = (_Float16 *)planes.data(), *el = eh + (size_t)D * N;
+  float *es = (float *)(el + (size_t)D * N);
+  hfg_pack_launch(s, (const float *)w.data(), 1, D, N, eh, el, es);
+  q.z = (const float *)in.data(); q.eh = eh; q.el = el; q.es = es; q.e2 = (const float *)bias.data(); q.pv = (float *)pv.data(); q.pi = (int *)pi.data();
+  q.R = R; q.D = D; q.N = N;
+  hipError_t e = dvae_launch_vq_h(q, mode == 2, (int *)out.data(), (float *)out2.data(), s);
+  if (e == hipSuccess) e = hipGetLastError();
+  const hipError_t es_ = hipStreamSynchronize(s);
+  (void)hipStreamDestroy(s);
+  HT(out.get_all(c.out));
+  HT(out2.get_all(c.out2));
+  return (int)(e != hipSuccess ? e : es_);
+}
+// slabs of a dvae_vq_h_kernel workgroup at R rows and N tokens (host only): the test picks a case on either side of the launcher's threshold
+int tts_dvae_test_vq_h_spw(int rows, int tokens) { return dvae_vq_h_spw(rows, tokens); }
 
 } // extern "C"
