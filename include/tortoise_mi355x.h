@@ -640,7 +640,7 @@ int tts_host_session_first_fit(const uint8_t *busy, int n_slots, int n_cand);
  *   was opened (a 72-byte descriptor: the fields it has).
  * tts_diff_session_open(max_packed_rows, max_requests): every option the diffusion stage reads is read here and holds until tts_diff_session_close, whatever
  *   tts_set_option stores meanwhile: "attn_f32", "share_uncond", "hoist_integrator", "diff_graph", "gn_eps", "ggml_lut", "attn_proj_f16", "proj_dual_b",
- *   "gemm_wreg", "gemm_gn_fuse", "attn_f32_drop", "lc_attn_f32", "attn_q64", "fp16_check", and "diff_sampler" / "ddim_eta" / "cond_free_k" / "diff_temperature" / "cond_free" as tts_diff_request_init's
+ *   "gemm_wreg", "gemm_gn_fuse", "conv3_fp8", "attn_f32_drop", "lc_attn_f32", "attn_q64", "fp16_check", and "diff_sampler" / "ddim_eta" / "cond_free_k" / "diff_temperature" / "cond_free" as tts_diff_request_init's
  *   defaults; the session always runs the batch-path GroupNorm ("latency_mode" is not bit-identical to it by design). With "hoist_integrator" on, every request
  *   is hoisted and owns n_steps x packed rows x 2 KB of device memory until it is collected; a request may then take at most 16384 packed rows (the option's
  *   value, if above 1), else tts_diff_session_admit returns TTS_ERR_LIMIT; a session opened with "hoist_integrator" 0 has no such bound. All activation buffers for max_packed_rows rows are allocated here. A session already open is closed first. TTS_ERR_ARG:
@@ -837,6 +837,12 @@ int tts_aligner_vocab(tts_ctx *ctx, int32_t *vocab_out, int cap, int32_t *blank_
  * is the same bits alone and in a batch and two calls agree; the bits of two modes differ. On the tests' weights mode 2 is within 4.5e-5 of the float64
  * restatement (gate 1e-3, every id the float64 argmax); mode 1 is up to 5.3e-3 from it on the aligner: it does NOT hold the 1e-3 gate. */
 /* Option "addon_conv_precision" (0 default; addition within version 8, no prototype changed): 0 f32 | 1 fp16 operands | 2 fp16 hi + lo pairs for every convolution of tts_classify_audio behind its stem and for the aligner's strided extractor convolutions; set BEFORE tts_load_classifier / tts_load_aligner, which pack the fp16 planes only then (a call in mode 1 or 2 on a model loaded at 0: TTS_ERR_STATE; any other value: TTS_ERR_ARG); independent of the two options above; numbers in profiles/addon_conv.txt. */
+/* Option "conv3_fp8" (0 default; addition within version 8, no prototype changed): 1 runs the k = 3 out_layers convolution of every diffusion ResBlock on the
+ * fp8 matrix instruction (OCP e4m3 operands, f32 accumulation): the activations with one power-of-two scale per sequence, the weights with one per output
+ * channel. Set BEFORE tts_load_diffusion, which packs the fp8 weight images only then (3 MB per ResBlock at 1024 channels); it is read again at call time (and
+ * pinned by tts_diff_session_open): 1 on a model loaded at 0 is TTS_ERR_STATE, 0 on a model loaded at 1 gives the bytes of a context that never set it. Layouts
+ * the fp8 kernel does not take (fewer than 128-row tiles, "latency_mode") keep the fp16 kernels. Values other than 0 and 1: TTS_ERR_ARG. Profiler families
+ * "diff_conv3_f8" and "diff_quant_f8". A throughput mode: it does NOT hold the diffusion parity gates (DESIGN.md "What pins the fp8 convolution"). */
 /* Option "dvae_precision" (0 default; addition within version 8, no prototype changed): 0 f32 | 1 fp16 operands | 2 fp16 hi + lo pairs for the DVAE encoder's convolutions behind its stem and for its quantiser (tts_dvae_codes, tts_dvae_codes_audio, tts_dvae_reconstruct*); set BEFORE tts_load_dvae, which packs the fp16 planes only then (a call in mode 1 or 2 on a model loaded at 0: TTS_ERR_STATE; any other value: TTS_ERR_ARG); independent of "addon_conv_precision"; mode 2 keeps the 1e-3 gate on z and float64's codes under a decided-row rule, mode 1 does not hold the gate; numbers in profiles/dvae_f16.txt. */
 /* audio: the clips back to back, n_samples[c] mono samples at sample_rate[c] Hz. A clip is resampled to 16 kHz in one stage (the audio front end's
  * polyphase resampler; a clip already at 16 kHz reaches the network bit for bit). ids_out [n_clips][frame_stride]: the argmax of every frame, the lowest

@@ -73,6 +73,9 @@
 // --addon-conv-precision f32|f16|split (default f32): the convolutions of the classifier and the strided extractor convolutions of --aligner, engine option
 //   "addon_conv_precision" 0 | 1 | 2, set before either model is loaded (f16: fp16 operands, split: fp16 hi + lo pairs; f32 accumulation in both). Another name is a
 //   usage error (exit 1, before a model is loaded).
+// --conv3-fp8 0|1 (default 0): the k = 3 out_layers convolutions of the diffusion ResBlocks on the fp8 MFMA, engine option "conv3_fp8", set before the diffusion
+//   model is loaded (per-sequence e4m3 activations, per-channel e4m3 weights, f32 accumulation; a throughput mode that does not hold the parity gates). Another
+//   value is a usage error (exit 1, before a model is loaded).
 // --dvae-precision f32|f16|split (default f32): the convolutions behind the stem and the quantiser of --dvae's encoder (--codes-from, --revoice), engine option
 //   "dvae_precision" 0 | 1 | 2, set before the model is loaded (f16: fp16 operands, split: fp16 hi + lo pairs; f32 accumulation in both). Another name is a usage
 //   error (exit 1, before a model is loaded).
@@ -348,6 +351,11 @@ int main(int argc, char **argv) {
       const std::string v = argv[i + 1];
       if (v != "f32" && v != "f16" && v != "split") { fprintf(stderr, "--addon-conv-precision %s: f32, f16 or split\n", v.c_str()); return 1; }
       engine_options.emplace_back("addon_conv_precision", v == "f32" ? 0 : v == "f16" ? 1 : 2);
+    }
+    else if (a == "--conv3-fp8") {
+      const std::string v = argv[i + 1];
+      if (v != "0" && v != "1") { fprintf(stderr, "--conv3-fp8 %s: 0 or 1\n", v.c_str()); return 1; }
+      engine_options.emplace_back("conv3_fp8", v == "1" ? 1 : 0);
     }
     else if (a == "--dvae-precision") {
       const std::string v = argv[i + 1];

@@ -178,6 +178,7 @@ struct tts_ctx {
   int attn_f32 = 0;        // option "attn_f32": the diffusion AttentionBlock in reference precision (F32 QK^T / softmax / PV / proj_out, main.cpp:3848-3875) via split-fp16 MFMA operands; 0 = fp16 operands (throughput mode)
   static constexpr int GEMM_WREG_ALL = 7;
   int gemm_wreg = GEMM_WREG_ALL; // option "gemm_wreg": classes of diffusion GEMMs whose weight operand is streamed into registers from its fragment-major image (bit 0: k = 1 in_layers, bit 1: QKV projection, bit 2: k = 3 out_layers); 0 = the LDS-staged kernels
+  int conv3_fp8 = 0;       // option "conv3_fp8": 1 = the k = 3 out_layers convolutions of the diffusion ResBlocks on the fp8 MFMA (gemm_f8.h: per-sequence e4m3 activations, per-channel e4m3 weights, f32 accumulation) where gemm_f8_conv3_takes admits the layout; read by tts_load_diffusion too, which then packs the fp8 weight images; does not hold the parity gates
   int gemm_gn_fuse = 1;    // option "gemm_gn_fuse": a ResBlock's k = 1 in_layers GEMM and the GroupNorm that consumes it run as one launch (gemm_f16.h: gemm_f16_gn_panel_kernel) where gemm_gn_panel_takes admits the layout (bit-identical); 0 = the pair
   int proj_dual_b = 1;     // option "proj_dual_b" (developer A/B): the split-weight proj_out GEMM stages both weight halves per activation tile (1) or runs two K segments (0)
   int attn_f32_drop = 0;   // option "attn_f32_drop" (developer ablation inside attn_f32 = 1): bit 0 q/k, bit 1 v, bit 2 attention output lose their low halves (= the fp16 rounding of the default mode, one operand at a time)
@@ -227,6 +228,8 @@ inline bool aligner_precision_ok(double v) { return v == 0 || v == 1 || v == 2; 
 inline bool addon_attn_precision_ok(double v) { return v == 0 || v == 1 || v == 2; }
 // Option "addon_conv_precision": the values tts_set_option stores and classifier_run / aligner_run accept (0 f32, 1 fp16, 2 split fp16 pairs); NaN is none of them
 inline bool addon_conv_precision_ok(double v) { return v == 0 || v == 1 || v == 2; }
+// Option "conv3_fp8": the values tts_set_option stores and the diffusion stage accepts (0 the fp16 kernels, 1 the fp8 convolution); NaN is none of them
+inline bool conv3_fp8_ok(double v) { return v == 0 || v == 1; }
 // Option "dvae_precision": the values tts_set_option stores and the DVAE stage accepts (0 f32, 1 fp16, 2 split fp16 pairs); NaN is none of them
 inline bool dvae_precision_ok(double v) { return v == 0 || v == 1 || v == 2; }
 

@@ -17,6 +17,7 @@
 //    host (reference stream) or from a counter-based device generator.
 #include "common.h"
 #include "gemm_f16.h"
+#include "gemm_f8.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -948,7 +949,7 @@ struct AttnDev {
   __half *proj_w_split; // [C][hi(s w) | lo(s w)]: proj_out's F32 weight as a split-precision pair; s = 1 / proj_alpha keeps the low halves normal
   float proj_alpha;     // 1 / s, s = the largest power of two with max|W| s < 30000 (64 for |W| up to 468; round 6: was a fixed 64, whose hi half overflows at |W| > 1023)
 };
-struct ResDev { float *in_g, *in_b, *in_bias, *emb_w, *emb_b, *out_g, *out_b, *out_bias; __half *in_w, *out_w, *in_wf, *out_wf; }; // in_wf: fragment-major image of in_w; out_wf: the per-tap images of out_w (gemm_wfrag3_index)
+struct ResDev { float *in_g, *in_b, *in_bias, *emb_w, *emb_b, *out_g, *out_b, *out_bias; __half *in_w, *out_w, *in_wf, *out_wf; uint8_t *out_w8 = nullptr; float *out_inv_w = nullptr; }; // in_wf: fragment-major image of in_w; out_wf: the per-tap images of out_w (gemm_wfrag3_index); out_w8 / out_inv_w: the e4m3 per-tap images of out_layers' weight and 1 / its per-channel scales (gemm_f8.h; option conv3_fp8 at the load, else null)
 
 // Packed row layout: sequence s occupies rows [start[s], start[s]+len[s]); start % 8 == 0; at least one
 // zero guard row before and after every sequence; total padded to a multiple of 128.
@@ -1034,6 +1035,8 @@ struct Work {
   int rows = 0;
   DevBuf x, hbuf, a16, att16, qk16, vt16, stats;
   DevBuf att16_lo, qk16_lo, vt16_lo; // low halves of the split-precision pairs (option attn_f32)
+  DevBuf a8, inv_a, f8_part;         // option conv3_fp8: the e4m3 operand of the k = 3 convolution (1-row zero halo), 1 / scale per row, the quantiser's partial maxima
+  uint8_t *A8() { return a8.as<uint8_t>() + C; }
   // option latency_mode: fixed-point GroupNorm statistics (gemm_f16.h: fx_add) of the tensor the blocks of this layout work on (X or the code embedding) and of H,
   // left by the epilogue of the GEMM that produced them; nullptr = not available (the batch path reduces them in the GroupNorm kernel)
   long long *st_x = nullptr, *st_h = nullptr;
@@ -1050,6 +1053,11 @@ struct Work {
     TTS_HIP(ctx, reserve_zeroed(qk16, (size_t)(r + 128) * 2048 * 2));
     TTS_HIP(ctx, reserve_zeroed(vt16, (size_t)C * (r + 128) * 2));
     TTS_HIP(ctx, reserve_zeroed(stats, (size_t)ns * 32 * sizeof(float2)));
+    if (ctx->conv3_fp8) {
+      TTS_HIP(ctx, reserve_zeroed(a8, (size_t)(r + 2) * C));
+      TTS_HIP(ctx, reserve_zeroed(inv_a, (size_t)r * 4));
+      TTS_HIP(ctx, reserve_zeroed(f8_part, (size_t)ns * F8_AMAX_PARTS * 4));
+    }
     if (ctx->attn_f32 || split) {
       TTS_HIP(ctx, reserve_zeroed(att16_lo, (size_t)(r + 2) * C * 2));
       TTS_HIP(ctx, reserve_zeroed(qk16_lo, (size_t)(r + 128) * 2048 * 2));
@@ -1162,6 +1170,7 @@ struct DiffState {
   float *inp_bias = nullptr, *integ_bias = nullptr, *outn_g = nullptr, *outn_b = nullptr, *out_bias = nullptr;
   __half *lc_w = nullptr, *inp_w = nullptr, *integ_w = nullptr, *out_w = nullptr;
   std::vector<void *> owned;
+  bool f8_images = false; // the ResBlocks carry the fp8 images of their k = 3 weight (option "conv3_fp8" was 1 at the load)
   // run state
   StepBufs sb;  // the single call's step: layout `sb.lay` of the candidates' sequences and their unconditioned copies
   DiffReq req;  // ... and its one request
@@ -1319,6 +1328,18 @@ struct Loader { // its jobs run on several threads (common.h: run_parallel): `us
     if ((r = f32(p + ".out_layers.0.bias", C, &w.out_b))) return r;
     if ((r = conv16(p + ".out_layers.3.weight", C, C, 3, C, C, &w.out_w, &w.out_wf))) return r;
     if ((r = f32(p + ".out_layers.3.bias", C, &w.out_bias))) return r;
+    if (ctx->conv3_fp8 == 1) { // the same weight as e4m3 per-tap images with one power-of-two scale per output channel (gemm_f8.h)
+      const HostTensor *t = get(p + ".out_layers.3.weight", (int64_t)C * C * 3);
+      if (!t) return TTS_ERR_FORMAT;
+      std::vector<float> wt((size_t)C * 3 * C), inv(C);
+      for (int co = 0; co < C; co++)
+        for (int ci = 0; ci < C; ci++)
+          for (int tap = 0; tap < 3; tap++) wt[((size_t)co * 3 + tap) * C + ci] = t->data[((size_t)co * C + ci) * 3 + tap];
+      std::vector<uint8_t> img(wt.size());
+      gemm_f8_pack_weight(wt.data(), C, C, img.data(), inv.data());
+      if ((r = put(img, &w.out_w8))) return r;
+      if ((r = put(inv, &w.out_inv_w))) return r;
+    }
     return TTS_OK;
   }
 };
@@ -1331,6 +1352,7 @@ int diff_load(tts_ctx *ctx, const char *path) {
   int rc = read_weight_file(path, wf, err);
   if (rc != TTS_OK) return fail(ctx, rc, "diffusion_model_load: %s", err.c_str());
   std::unique_ptr<DiffState> st(new DiffState());
+  st->f8_images = ctx->conv3_fp8 == 1;
   Loader ld{ctx, st.get(), wf, {}};
   while (wf.has("latent_conditioner." + std::to_string(st->n_lc + 1) + ".norm.weight")) st->n_lc++;
   while (wf.has("conditioning_timestep_integrator." + std::to_string(st->n_integ) + ".resblk.in_layers.0.weight")) st->n_integ++;
@@ -1432,6 +1454,14 @@ int diff_fp16_check(tts_ctx *ctx, int64_t counts[2]) {
   }
   counts[0] = dev[0] + ctx->fp16_bad_weights[0];
   counts[1] = dev[1] + ctx->fp16_bad_weights[1];
+  return TTS_OK;
+}
+
+// option conv3_fp8 at call time (the convention of dvae_precision): 1 needs the images tts_load_diffusion packs only when the option is 1 at the load
+static int conv3_fp8_begin(tts_ctx *ctx, const char *fn) {
+  if (!conv3_fp8_ok(ctx->conv3_fp8)) return fail(ctx, TTS_ERR_ARG, "%s: conv3_fp8 %d", fn, ctx->conv3_fp8);
+  if (ctx->conv3_fp8 == 1 && !ctx->diff->f8_images)
+    return fail(ctx, TTS_ERR_STATE, "%s: conv3_fp8 1, but the model was loaded with conv3_fp8 0 and holds no fp8 weight images: set the option before tts_load_diffusion", fn);
   return TTS_OK;
 }
 
@@ -1866,6 +1896,28 @@ static int gemm_gn_panel(tts_ctx *ctx, const Layout &lay, const __half *A, const
   return fp16_check(ctx, y, (size_t)lay.rows * C);
 }
 
+// Option conv3_fp8: the ResBlock's k = 3 convolution as quantise (two launches, family diff_quant_f8) + fp8 convolution (diff_conv3_f8) in place of the fp16 GEMM.
+// a16: the operand the GroupNorm left (A16 or ATT16); X = conv + bias + xin. The launches read and write Work buffers only: capturable in the step graph.
+static int conv3_f8(tts_ctx *ctx, const Layout &lay, Work &wk, const __half *a16, const ResDev &w, const float *xin, float *X) {
+  double mv = 0;
+  for (int l : lay.len) mv += l;
+  QuantF8Args q{};
+  q.A = a16; q.lda = C; q.C = C; q.M = lay.rows; q.ns = lay.ns;
+  q.seq_start = lay.d_start.as<int>(); q.seq_len = lay.d_len.as<int>(); q.row_seq = lay.d_row_seq.as<int>();
+  q.part = wk.f8_part.as<unsigned>(); q.A8 = wk.A8(); q.lda8 = C; q.inv_a = wk.inv_a.as<float>();
+  {
+    ProfScope ps(ctx, "diff_quant_f8", mv * C * 5); // bytes: the fp16 operand read twice, the e4m3 operand written once
+    TTS_HIP(ctx, launch_quant_f8_amax(q, ctx->stream));
+    TTS_HIP(ctx, launch_quant_f8_convert(q, ctx->stream));
+  }
+  GemmF8Args g{};
+  g.A8 = wk.A8(); g.lda = C; g.Wf = w.out_w8; g.inv_a = wk.inv_a.as<float>(); g.inv_w = w.out_inv_w; g.bias = w.out_bias; g.row_seq = lay.d_row_seq.as<int>();
+  g.out = X; g.ldo = C; g.resid = xin; g.M = lay.rows; g.rows_total = lay.rows; g.N = C; g.K = C;
+  ProfScope ps(ctx, "diff_conv3_f8", 2.0 * mv * C * 3 * C);
+  TTS_HIP(ctx, launch_gemm_f8_conv3(g, ctx->stream));
+  return TTS_OK;
+}
+
 // ResBlock: X = Xin + out_layers(in_layers(Xin) with the step's scale/shift); Xin == nullptr: in place on X.
 // ss = this step's [scale | shift] for this block (device, 2048 floats). Hpre: in_layers(Xin) computed earlier (it does
 // not depend on the timestep), nullptr: computed here.
@@ -1885,10 +1937,11 @@ static int res_block(tts_ctx *ctx, DiffState *st, const Layout &lay, Work &wk, f
     // ResBlock, same shape and halo), the k = 3 convolution reads ATT16. The same bits as the pair below.
     CHECK(gn(ctx, st, lay, xin, nullptr, w.in_g, w.in_b, nullptr, 1, wk.A16()));
     CHECK(gemm_gn_panel(ctx, lay, wk.A16(), w.in_wf, w.in_bias, w.out_g, w.out_b, ss, wk.ATT16()));
+    wk.st_x = nullptr;
+    if (gemm_f8_conv3_takes(ctx->conv3_fp8, w.out_w8 != nullptr, false, debug_sums, lay.rows, C, C)) return conv3_f8(ctx, lay, wk, wk.ATT16(), w, xin, X);
     GemmArgs c3 = gemm_base(lay, wk.ATT16(), C, 3, C, w.out_w, C, w.out_bias);
     c3.Wf = w.out_wf; c3.wreg = gemm_wreg_class(ctx, 4);
     c3.mode = GEMM_OUT_F32; c3.outF = X; c3.ldo = C; c3.resid = xin;
-    wk.st_x = nullptr;
     return gemm(ctx, "diff_gemm", c3, lay);
   }
   if (!Hpre) {
@@ -1902,6 +1955,10 @@ static int res_block(tts_ctx *ctx, DiffState *st, const Layout &lay, Work &wk, f
   // the weight the GEMM below will read: the per-tap images where gemm_f16_conv3_wreg_kernel takes it (F32 output, 128-row tiles)
   CHECK(gn(ctx, st, lay, Hpre, lat ? st_h : nullptr, w.out_g, w.out_b, ss, 1, wk.A16(), lat ? w.out_w : gemm_wreg_image(ctx, 4, lay, C, w.out_w, w.out_wf), (size_t)3 * C * C * 2));
   DBG_SUM("res.out gn", wk.A16(), (size_t)lay.rows * C * 2);
+  if (gemm_f8_conv3_takes(ctx->conv3_fp8, w.out_w8 != nullptr, lat, debug_sums, lay.rows, C, C)) {
+    wk.st_x = nullptr;
+    return conv3_f8(ctx, lay, wk, wk.A16(), w, xin, X);
+  }
   GemmArgs c3 = gemm_base(lay, wk.A16(), C, 3, C, w.out_w, C, w.out_bias);
   c3.Wf = w.out_wf; c3.wreg = gemm_wreg_class(ctx, 4);
   long long *st_out = lat ? st->new_stats_slot() : nullptr;
@@ -2322,6 +2379,7 @@ static bool no_graph_env() {
 int diff_forward(tts_ctx *ctx, const float *latents, int L, const float *x_t, int timestep, int cond_free, float *out) {
   DiffState *st = ctx->diff;
   if (!st) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
+  CHECK(conv3_fp8_begin(ctx, "tts_diffusion_forward"));
   if (!latents || !x_t || !out || L < 1) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_forward: bad argument");
   std::vector<int> Ls{L};
   CHECK(setup_batch(ctx, st, latents, Ls, !cond_free, cond_free));
@@ -2551,6 +2609,7 @@ static int diff_sample_with(tts_ctx *ctx, const float *latents, const int32_t *r
 int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, int n_steps, const float *noise, int noise_mode,
                 float *mel_out) {
   if (!ctx->diff) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
+  CHECK(conv3_fp8_begin(ctx, "tts_diffusion"));
   if (!latents || !rows || !mel_out || B < 1 || n_steps < 2) return fail(ctx, TTS_ERR_ARG, "tts_diffusion: bad argument");
   for (int c = 0; c < B; c++) if (rows[c] < 1 || rows[c] > 500) return fail(ctx, TTS_ERR_ARG, "latent rows %d out of range", rows[c]);
   return diff_sample_with(ctx, latents, rows, B, nullptr, 0, nullptr, n_steps, noise, noise_mode, mel_out);
@@ -2558,6 +2617,7 @@ int diff_sample(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, 
 int diff_sample_voices(tts_ctx *ctx, const float *latents, const int32_t *rows, int B, const float *voice_latents, int n_voices, const int32_t *voice_of,
                        int n_steps, const float *noise, int noise_mode, float *mel_out) {
   if (!ctx->diff) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
+  CHECK(conv3_fp8_begin(ctx, "tts_diffusion_multi_voice"));
   if (!latents || !rows || !mel_out || B < 1 || n_steps < 2 || !voice_latents || !voice_of) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_multi_voice: bad argument");
   if (n_voices < 1 || n_voices > (1 << 20)) return fail(ctx, TTS_ERR_ARG, "tts_diffusion_multi_voice: %d voices", n_voices);
   for (int c = 0; c < B; c++) {
@@ -2577,16 +2637,16 @@ int diff_sample_voices(tts_ctx *ctx, const float *latents, const int32_t *rows, 
 // the session's pinned options for the length of one session call: every option the diffusion stage reads between an admission's setup and a step's last kernel
 struct PinnedOptions {
   float gn_eps;
-  int ggml_lut, attn_f32, attn_proj_f16, proj_dual_b, gemm_wreg, attn_f32_drop, lc_attn_f32, attn_q64, fp16_check, hoist_integrator, diff_graph, latency_mode, gemm_gn_fuse;
+  int ggml_lut, attn_f32, attn_proj_f16, proj_dual_b, gemm_wreg, attn_f32_drop, lc_attn_f32, attn_q64, fp16_check, hoist_integrator, diff_graph, latency_mode, gemm_gn_fuse, conv3_fp8;
   bool share_uncond;
   static PinnedOptions of(const tts_ctx *c) {
     return PinnedOptions{c->gn_eps, c->ggml_lut, c->attn_f32, c->attn_proj_f16, c->proj_dual_b, c->gemm_wreg, c->attn_f32_drop, c->lc_attn_f32, c->attn_q64,
-                         c->fp16_check, c->hoist_integrator, c->diff_graph, c->latency_mode, c->gemm_gn_fuse, c->share_uncond};
+                         c->fp16_check, c->hoist_integrator, c->diff_graph, c->latency_mode, c->gemm_gn_fuse, c->conv3_fp8, c->share_uncond};
   }
   void put(tts_ctx *c) const {
     c->gn_eps = gn_eps; c->ggml_lut = ggml_lut; c->attn_f32 = attn_f32; c->attn_proj_f16 = attn_proj_f16; c->proj_dual_b = proj_dual_b; c->gemm_wreg = gemm_wreg;
     c->attn_f32_drop = attn_f32_drop; c->lc_attn_f32 = lc_attn_f32; c->attn_q64 = attn_q64; c->fp16_check = fp16_check; c->hoist_integrator = hoist_integrator;
-    c->diff_graph = diff_graph; c->latency_mode = latency_mode; c->gemm_gn_fuse = gemm_gn_fuse; c->share_uncond = share_uncond;
+    c->diff_graph = diff_graph; c->latency_mode = latency_mode; c->gemm_gn_fuse = gemm_gn_fuse; c->conv3_fp8 = conv3_fp8; c->share_uncond = share_uncond;
   }
 };
 struct DiffSession {
@@ -2635,6 +2695,7 @@ int diff_session_room(const tts_ctx *ctx) {
 int diff_session_open(tts_ctx *ctx, int max_packed_rows, int max_requests) {
   DiffState *st = ctx->diff;
   if (!st) return fail(ctx, TTS_ERR_STATE, "diffusion model not loaded");
+  CHECK(conv3_fp8_begin(ctx, "tts_diff_session_open"));
   diff_session_close(ctx);
   std::unique_ptr<DiffSession> s(new DiffSession());
   s->max_rows = max_packed_rows; s->max_req = max_requests; s->buf_rows = (max_packed_rows + 127) & ~127;
