@@ -197,7 +197,7 @@ int tts_set_option(tts_ctx *c, const char *key, double value) {
   else if (k == "attn_f32") c->attn_f32 = value != 0;
   else if (k == "attn_proj_f16") c->attn_proj_f16 = value != 0;
   else if (k == "proj_dual_b") c->proj_dual_b = value != 0;
-  else if (k == "gemm_wreg") c->gemm_wreg = value == 1 ? tts_ctx::GEMM_WREG_ALL : value == 2 ? 1 : value == 3 ? 2 : value == 4 ? 4 : 0; // 0 the LDS-staged kernels, 1 every class that has a register-streamed kernel, 2 / 3 / 4 in_layers / QKV / k = 3 out_layers only (A/B)
+  else if (k == "gemm_wreg") c->gemm_wreg = value == 1 ? tts_ctx::GEMM_WREG_ALL : value == 2 ? 1 : value == 3 ? 2 : value == 4 ? 4 : value >= 5 && value <= 15 ? (int)value : 0; // 0 the LDS-staged kernels, 1 every class that has a register-streamed kernel and the QKV stores through LDS, 2 / 3 / 4 in_layers / QKV / k = 3 out_layers only (A/B), 5 .. 15 the bit mask of tts_ctx::gemm_wreg itself (7: every class, the QKV tile stored straight from the registers; 15 = 1)
   else if (k == "gemm_gn_fuse") c->gemm_gn_fuse = value != 0;
   else if (k == "conv3_fp8") { // addition within version 8: the k = 3 out_layers convolutions of the diffusion stage on the fp8 MFMA; set before tts_load_diffusion, which packs the weight images
     if (!conv3_fp8_ok(value)) return fail(c, TTS_ERR_ARG, "conv3_fp8: 0 (fp16 kernels) or 1 (fp8 convolution)");

@@ -176,8 +176,8 @@ struct tts_ctx {
   int ar_weights = 0;      // option "ar_weights": 0 = f32 weights in the decode step (reference numerics), 1 = fp16 weights, 2 = OCP fp8 (e4m3) weights with a power-of-two scale per output column (set before tts_load_ar)
   int dec_f32_mfma = 0;    // option "dec_f32_mfma": the decode step's LayerNorm-GEMVs use exact-f32 MFMA products instead of split fp16 (set before tts_load_ar; +1 us per launch)
   int attn_f32 = 0;        // option "attn_f32": the diffusion AttentionBlock in reference precision (F32 QK^T / softmax / PV / proj_out, main.cpp:3848-3875) via split-fp16 MFMA operands; 0 = fp16 operands (throughput mode)
-  static constexpr int GEMM_WREG_ALL = 7;
-  int gemm_wreg = GEMM_WREG_ALL; // option "gemm_wreg": classes of diffusion GEMMs whose weight operand is streamed into registers from its fragment-major image (bit 0: k = 1 in_layers, bit 1: QKV projection, bit 2: k = 3 out_layers); 0 = the LDS-staged kernels
+  static constexpr int GEMM_WREG_ALL = 15;
+  int gemm_wreg = GEMM_WREG_ALL; // option "gemm_wreg": classes of diffusion GEMMs whose weight operand is streamed into registers from its fragment-major image (bit 0: k = 1 in_layers, bit 1: QKV projection, bit 2: k = 3 out_layers); bit 3: the register-streamed QKV projection parks its fp16 tile in LDS and stores whole cache lines; 0 = the LDS-staged kernels
   int conv3_fp8 = 0;       // option "conv3_fp8": 1 = the k = 3 out_layers convolutions of the diffusion ResBlocks on the fp8 MFMA (gemm_f8.h: per-sequence e4m3 activations, per-channel e4m3 weights, f32 accumulation) where gemm_f8_conv3_takes admits the layout; read by tts_load_diffusion too, which then packs the fp8 weight images; does not hold the parity gates
   int gemm_gn_fuse = 1;    // option "gemm_gn_fuse": a ResBlock's k = 1 in_layers GEMM and the GroupNorm that consumes it run as one launch (gemm_f16.h: gemm_f16_gn_panel_kernel) where gemm_gn_panel_takes admits the layout (bit-identical); 0 = the pair
   int proj_dual_b = 1;     // option "proj_dual_b" (developer A/B): the split-weight proj_out GEMM stages both weight halves per activation tile (1) or runs two K segments (0)

@@ -1492,7 +1492,7 @@ static int gemm(tts_ctx *ctx, const char *fam, GemmArgs &g, const Layout &lay, i
 }
 
 // option gemm_wreg (bit 0: k = 1 in_layers, bit 1: QKV projection, bit 2: k = 3 out_layers): does this class stream its weight through registers
-// (gemm_f16_wreg_kernel, gemm_f16_conv3_wreg_kernel)
+// (gemm_f16_wreg_kernel, gemm_f16_conv3_wreg_kernel); bit 3: the register-streamed QKV projection stores its tile through LDS
 static int gemm_wreg_class(const tts_ctx *ctx, int bit) { return (ctx->gemm_wreg & bit) ? 1 : 0; }
 // the image of a weight with a fragment-major copy that the GEMM of this layout will stream (for the GroupNorm's weight touch)
 static const __half *gemm_wreg_image(const tts_ctx *ctx, int bit, const Layout &lay, int N, const __half *w, const __half *wf) {
@@ -1816,7 +1816,7 @@ static int attention_block(tts_ctx *ctx, DiffState *st, const Layout &lay, Work 
   DBG_SUM("attn gn", wk.A16(), (size_t)lay.rows * C * 2);
   GemmArgs g = gemm_base(lay, wk.A16(), C, 1, C, w.qkv_w, 3 * C, w.qkv_b);
   g.mode = f32 ? GEMM_OUT_QKV_SPLIT : GEMM_OUT_QKV;
-  g.Wf = w.qkv_wf; g.wreg = gemm_wreg_class(ctx, 2);
+  g.Wf = w.qkv_wf; g.wreg = gemm_wreg_class(ctx, 2) | (gemm_wreg_class(ctx, 8) << 1); // bit 3 of the option: the fp16 tile leaves through LDS (GemmArgs::wreg bit 1)
   g.outH = wk.qk16.as<__half>(); g.ldh = 2048; g.outVt = wk.vt16.as<__half>(); g.ldvt = wk.rows + 128;
   g.outH2 = wk.qk16_lo.as<__half>(); g.outVt2 = wk.vt16_lo.as<__half>();
   CHECK(gemm(ctx, "diff_gemm", g, lay));

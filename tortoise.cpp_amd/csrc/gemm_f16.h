@@ -23,7 +23,8 @@
 //                             the WEIGHT operand never touches LDS — each wave loads its MFMA fragments from a fragment-major image built at load time, one K tile ahead;
 //                             LDS is a two-slot ring of activation tiles, one raw barrier per K tile. Bit-identical to gemm_f16_vh_kernel. Measured against it in the benchmark
 //                             (profiles/gemm_wreg_same_box_ab.txt): QKV projection 183.0 -> 170.9 us, in_layers 82.2 -> 73.6 us, headline +1.7 %. Adopted for both
-//                             classes (option gemm_wreg); a two-tile distance is not instantiated (see the kernel).
+//                             classes (option gemm_wreg); a two-tile distance is not instantiated (see the kernel). Its fp16 QKV tile leaves through the dead
+//                             activation ring in whole cache lines (gemm_epilogue_wreg_qkv_lds, bit 3 of the option; byte-equal outputs).
 //   gemm_f16_conv3_wreg_kernel the same move for the k = 3 convolution (F32 output with or without residual, 128-row tiles): per-tap fragment-major weight images, waves 1 x 4,
 //                             weight register sets rotating per tap, LDS = a two-slot ring of activation SLABS (34 KB, 4 workgroups per CU), one raw barrier per 64-channel
 //                             chunk. Bit-identical to gemm_f16_conv3_vh_kernel. The dual-B kernel is not ported.
@@ -46,6 +47,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <type_traits>
 
@@ -73,7 +75,8 @@ struct GemmArgs {
   const __half *W;     // [N][ldw]; segment seg starts at column w_off[seg] (defaults: ldw = nseg*kseg, w_off = seg*kseg)
   int ldw_, w_off_[3], custom_w; // set custom_w = 1 to use ldw_/w_off_ (e.g. split-precision: hi|lo halves reused)
   const __half *Wf;    // the fragment-major image of W (one segment: gemm_wfrag_index; the k = 3 convolution: gemm_wfrag3_index), or nullptr
-  int wreg;            // 1 with Wf: stream the weight through registers where gemm_f16_wreg_kernel / gemm_f16_conv3_wreg_kernel takes the shape
+  int wreg;            // bit 0, with Wf: stream the weight through registers where gemm_f16_wreg_kernel / gemm_f16_conv3_wreg_kernel takes the shape
+                       // bit 1: that kernel's GEMM_OUT_QKV tile leaves through LDS in whole cache lines (gemm_epilogue_wreg_qkv_lds) where the outputs are 16-byte aligned
   int M, N;            // multiples of 128 (buffers are padded)
   const float *bias;   // [N] or nullptr
   const int *row_seq;  // [M]: sequence id, <0 for guard/padding rows (output forced to 0); may be null
@@ -693,9 +696,118 @@ __device__ __forceinline__ void gemm_epilogue_wreg(const GemmArgs &g, floatx4 (&
   }
 }
 
+// GEMM_OUT_QKV through LDS (g.wreg bit 1; gemm_plan's qkv_lds). gemm_epilogue_wreg stores a lane's four results as 8 bytes: a wave-level store covers sixteen 32-byte
+// pieces of sixteen rows (Q, K) or channels (V^T). Here the activation ring, dead after the last K tile, takes the fp16 tile first — the SAME pack_half4 values — and
+// the tile leaves in 16-byte stores that cover whole 128-byte lines. The 192 columns of a head are q | k | v of 64, so it is a 64-column HALF of the tile (a wave pair)
+// that lies wholly in Q / K or in V: each pair owns one 16 KB image,
+//   Q / K half  [row 0..127][col 0..63], 128-byte rows, the eight 16-byte chunks of row r at chunk ^ (r >> 1): 8 lanes store one row's line of outH;
+//   V half      [channel 0..63][row 0..127], 256-byte rows (the natural operand order already holds 4 consecutive rows of a channel per lane), the sixteen chunks of
+//               channel c at chunk ^ c: 16 lanes store 256 contiguous bytes of a channel's row of outVt.
+// Banks (64 x 4 bytes), modelled as: a ds_write_b64 is served 32 lanes at a time = 16 rows (channels) x 2 adjacent 8-byte pieces, a ds_read_b128 16 lanes at a time =
+// two rows (one channel); with the swizzles both then touch every bank once (tests/test_gemm_qkv_store_cpu.py evaluates these very functions for every lane). The
+// counters still show 19 conflict cycles per wave (5.4 % of the kernel's LDS-active cycles, profiles/qkv_store.txt): 8 ns of an epilogue of 16 us.
+// Measured against the parent on one box (same file): 166.6 -> 149.9 us per launch (the K loop alone: 133.7), headline 143.6 -> 146.2 audio-s/s.
+struct QkvLdsPos { int r, c; }; // Q / K half: row, first column; V half: channel, first row
+constexpr int qkv_lds_off(bool nat, int r, int c) { // byte offset of element (r, c) in its half's image
+  return nat ? r * 256 + ((((c >> 3) ^ r) & 15) << 4) + (c & 7) * 2 : r * 128 + ((((c >> 3) ^ (r >> 1)) & 7) << 4) + (c & 7) * 2;
+}
+constexpr QkvLdsPos qkv_lds_park(bool nat, int wave, int lane, int i, int j) { // the four values of acc[i][j]: (r, c .. c + 3)
+  const int fr = lane & 15, fq = lane >> 4, cb = (wave & 1) * 32 + j * 16;
+  return nat ? QkvLdsPos{cb + fr, i * 16 + fq * 4} : QkvLdsPos{i * 16 + fr, cb + fq * 4};
+}
+constexpr QkvLdsPos qkv_lds_read(bool nat, int wave, int lane, int p) { // the eight values a lane stores in pass p (0 .. 7): (r, c .. c + 7)
+  const int s = 2 * p + (wave & 1);
+  return nat ? QkvLdsPos{s * 4 + (lane >> 4), (lane & 15) * 8} : QkvLdsPos{s * 8 + (lane >> 3), (lane & 7) * 8};
+}
+// Values, guards and the rows written are those of gemm_epilogue_wreg<GEMM_OUT_QKV>: rows m0 .. m0 + 16 nblk - 1 of every column, guard rows as zeros.
+template <int MI, bool NAT>
+__device__ __forceinline__ void gemm_epilogue_wreg_qkv_lds(const GemmArgs &g, floatx4 (&acc)[MI][2], int m0, int n0, int nblk, int lane, int wave, char *smem) {
+  const int c0 = n0 + wave * 32, fr = lane & 15, fq = lane >> 4;
+  const bool hb = g.bias != nullptr, hs = g.row_seq != nullptr;
+  const float *bp = hb ? g.bias : (const float *)g.W;   // unconditional loads, values selected afterwards (see gemm_epilogue_vh)
+  const int *sp = hs ? g.row_seq : (const int *)g.A[0];
+  char *img = smem + (wave >> 1) * 16384;
+  const int hc = n0 + (wave >> 1) * 64, h = hc / 192, w0 = hc - h * 192; // the half's first column: w0 = 0 (q), 64 (k) or 128 (v)
+  uint2 pk[MI][2];
+  if (NAT) { // acc[i][j][r] = C[m0 + 16 i + 4 fq + r][c0 + 16 j + fr]
+    float bv[2];
+    int4 sq[MI];
+#pragma unroll
+    for (int j = 0; j < 2; j++) bv[j] = bp[c0 + j * 16 + fr];
+#pragma unroll
+    for (int i = 0; i < MI; i++) sq[i] = *(const int4 *)(sp + m0 + min(i, nblk - 1) * 16 + fq * 4);
+#pragma unroll
+    for (int j = 0; j < 2; j++) bv[j] = hb ? bv[j] : 0.f;
+#pragma unroll
+    for (int i = 0; i < MI; i++) sq[i] = hs ? sq[i] : make_int4(0, 0, 0, 0);
+#pragma unroll
+    for (int i = 0; i < MI; i++) {
+      const bool gd[4] = {sq[i].x < 0, sq[i].y < 0, sq[i].z < 0, sq[i].w < 0};
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) v[r] = gd[r] ? 0.f : acc[i][j][r] + bv[j];
+        pk[i][j] = pack_half4(v[0], v[1], v[2], v[3]);
+      }
+    }
+  } else { // acc[i][j][r] = C[m0 + 16 i + fr][c0 + 16 j + 4 fq + r]
+    float4 b4[2];
+    int sq[MI];
+#pragma unroll
+    for (int j = 0; j < 2; j++) b4[j] = *(const float4 *)(bp + c0 + fq * 4 + j * 16);
+#pragma unroll
+    for (int i = 0; i < MI; i++) sq[i] = sp[m0 + min(i, nblk - 1) * 16 + fr];
+#pragma unroll
+    for (int j = 0; j < 2; j++) b4[j] = hb ? b4[j] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int i = 0; i < MI; i++) sq[i] = hs ? sq[i] : 0;
+#pragma unroll
+    for (int i = 0; i < MI; i++)
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        float4 v = make_float4(acc[i][j][0] + b4[j].x, acc[i][j][1] + b4[j].y, acc[i][j][2] + b4[j].z, acc[i][j][3] + b4[j].w);
+        if (sq[i] < 0) v = make_float4(0.f, 0.f, 0.f, 0.f);
+        pk[i][j] = pack_half4(v.x, v.y, v.z, v.w);
+      }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // this wave's fragment reads of the last K tile are complete; no DMA is in flight (the loop's last wait was vmcnt(0))
+  __builtin_amdgcn_s_barrier();                      // ... and so are every other wave's: the ring is free
+#pragma unroll
+  for (int i = 0; i < MI; i++)
+    if (i < nblk) {
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        const QkvLdsPos q = qkv_lds_park(NAT, wave, lane, i, j);
+        *(uint2 *)(img + qkv_lds_off(NAT, q.r, q.c)) = pk[i][j];
+      }
+    }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  constexpr int NP = NAT ? 8 : MI; // V: 4 channels x all rows per pass and wave; Q / K: 8 rows per pass and wave, rows past 16 MI are not the tile's
+  const int rows = nblk * 16;
+  uint4 o[NP];
+#pragma unroll
+  for (int p = 0; p < NP; p++) {
+    const QkvLdsPos q = qkv_lds_read(NAT, wave, lane, p);
+    o[p] = *(const uint4 *)(img + qkv_lds_off(NAT, q.r, q.c));
+  }
+#pragma unroll
+  for (int p = 0; p < NP; p++) {
+    const QkvLdsPos q = qkv_lds_read(NAT, wave, lane, p);
+    if (NAT) {
+      if (q.c < rows) *(uint4 *)(g.outVt + (size_t)(h * 64 + q.r) * g.ldvt + m0 + q.c) = o[p];
+    } else {
+      if (q.r < rows) *(uint4 *)(g.outH + (size_t)(m0 + q.r) * g.ldh + h * 128 + w0 + q.c) = o[p];
+    }
+  }
+}
+
 // NAT: this wave's columns are V columns of a QKV projection (natural operand order). A template parameter of the whole body, not of the K loop alone: with two K loops in one
 // function hipcc spills the weight registers inside both (seen in the ISA)
-template <int MODE, int MI, int D, bool NAT>
+// QLDS (GEMM_OUT_QKV only): the epilogue through LDS, gemm_epilogue_wreg_qkv_lds
+template <int MODE, int MI, int D, bool NAT, bool QLDS>
 __device__ __forceinline__ void gemm_wreg_body(const GemmArgs &g, int m0, int n0, int nblk, int lane, int wave) {
   extern __shared__ __attribute__((aligned(16))) char smem_dyn[]; // ONE LDS object (see gemm_vh_body)
   char *smem = smem_dyn;
@@ -775,29 +887,31 @@ __device__ __forceinline__ void gemm_wreg_body(const GemmArgs &g, int m0, int n0
 #pragma unroll
     for (int j = 0; j < 2; j++) asm volatile("" : "+v"(acc[i][j]));
   kloop();
-  gemm_epilogue_wreg<MODE, MI, NAT>(g, acc, m0, n0, nblk, wave, fr, fq);
+  if constexpr (QLDS) gemm_epilogue_wreg_qkv_lds<MI, NAT>(g, acc, m0, n0, nblk, lane, wave, smem);
+  else gemm_epilogue_wreg<MODE, MI, NAT>(g, acc, m0, n0, nblk, wave, fr, fq);
 }
 
 // D = 1: a two-slot ring, 32 KB, 4 workgroups per CU with 128 registers per wave (126 used, no spill; the loop waits vmcnt(0) once per tile, which is exact at this distance:
 // nothing younger is in flight). D = 2 (three slots, 3 workgroups per CU) compiles to a loop that rotates the weight register sets through v_mov copies — copies of
 // inline-asm load destinations that may not have landed — and is therefore not instantiated.
 static constexpr int GEMM_WREG_D = 1, GEMM_WREG_LDS = (GEMM_WREG_D + 1) * 16384;
-template <int MODE, int D = GEMM_WREG_D>
+template <int MODE, int D = GEMM_WREG_D, bool QLDS = false>
 static __global__ __launch_bounds__(256, 4) void gemm_f16_wreg_kernel(GemmArgs g) {
+  static_assert(!QLDS || MODE == GEMM_OUT_QKV, "the epilogue through LDS is the fp16 QKV one");
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int m0, n0, nblk;
   if (!gemm_vh_tile(g, m0, n0, nblk)) return;
   if (gemm_mode_qkv(MODE) && ((n0 + wave * 32) % 192) >= 128) { // wave-uniform; every body passes the same barriers
-    if (nblk > 4) gemm_wreg_body<MODE, 8, D, true>(g, m0, n0, nblk, lane, wave);
-    else gemm_wreg_body<MODE, 4, D, true>(g, m0, n0, nblk, lane, wave);
+    if (nblk > 4) gemm_wreg_body<MODE, 8, D, true, QLDS>(g, m0, n0, nblk, lane, wave);
+    else gemm_wreg_body<MODE, 4, D, true, QLDS>(g, m0, n0, nblk, lane, wave);
   } else {
-    if (nblk > 4) gemm_wreg_body<MODE, 8, D, false>(g, m0, n0, nblk, lane, wave);
-    else gemm_wreg_body<MODE, 4, D, false>(g, m0, n0, nblk, lane, wave);
+    if (nblk > 4) gemm_wreg_body<MODE, 8, D, false, QLDS>(g, m0, n0, nblk, lane, wave);
+    else gemm_wreg_body<MODE, 4, D, false, QLDS>(g, m0, n0, nblk, lane, wave);
   }
 }
 // the shapes gemm_f16_wreg_kernel takes (gemm_plan has chosen th and ku)
 static inline bool gemm_takes_wreg(const GemmArgs &g, int th, int ku) {
-  return g.wreg > 0 && g.Wf && g.nseg == 1 && !g.custom_w && th == 8 && ku == 1 && (g.kseg >> 6) >= 2 &&
+  return (g.wreg & 1) && g.Wf && g.nseg == 1 && !g.custom_w && th == 8 && ku == 1 && (g.kseg >> 6) >= 2 &&
          (g.mode == GEMM_OUT_F32 || g.mode == GEMM_OUT_QKV || g.mode == GEMM_OUT_QKV_SPLIT);
 }
 
@@ -1265,7 +1379,7 @@ static __global__ __launch_bounds__(256, 4) void gemm_f16_conv3_wreg_kernel(Gemm
 // the shapes gemm_f16_conv3_wreg_kernel takes: g.Wf is then the per-tap image (gemm_wfrag3_index). The STATS and F16 modes, shorter tiles and so the small grids stay
 // with the LDS-staged kernel
 static inline bool gemm_takes_conv3_wreg(const GemmArgs &g, int th) {
-  return g.wreg > 0 && g.Wf && gemm_is_conv3(g) && th == 8 && g.mode == GEMM_OUT_F32;
+  return (g.wreg & 1) && g.Wf && gemm_is_conv3(g) && th == 8 && g.mode == GEMM_OUT_F32;
 }
 
 // tile height (16-row blocks) launch_gemm_f16 chooses for an M x N problem
@@ -1284,6 +1398,7 @@ struct GemmPlan {
   int kernel;     // GEMM_KERNEL_*
   int th, ku, cn; // 16-row blocks per tile, K tiles per barrier pair, column tiles per L2 chunk
   int grid, lds;  // workgroups, dynamic LDS bytes
+  int qkv_lds;    // GEMM_KERNEL_WREG, GEMM_OUT_QKV: the epilogue through LDS (GemmArgs::wreg bit 1)
 };
 static inline GemmPlan gemm_plan(const GemmArgs &g) {
   GemmPlan p = {};
@@ -1325,7 +1440,11 @@ static inline GemmPlan gemm_plan(const GemmArgs &g) {
     mt_max = std::max(mt_max, (b1 - b0 + p.th - 1) / p.th);
   }
   p.grid = 8 * mt_max * NT;
-  if (gemm_takes_wreg(g, p.th, ku)) { p.kernel = GEMM_KERNEL_WREG; p.ku = 1; p.lds = GEMM_WREG_LDS; }
+  if (gemm_takes_wreg(g, p.th, ku)) {
+    p.kernel = GEMM_KERNEL_WREG; p.ku = 1; p.lds = GEMM_WREG_LDS;
+    // 16-byte stores: rows of outH and outVt start at multiples of 8 halves (a tile's first row is a multiple of 16)
+    p.qkv_lds = (g.wreg & 2) && g.mode == GEMM_OUT_QKV && !(g.ldh & 7) && !(g.ldvt & 7) && !((uintptr_t)g.outH & 15) && !((uintptr_t)g.outVt & 15);
+  }
   else if (gemm_takes_conv3_wreg(g, p.th)) { p.kernel = GEMM_KERNEL_CONV3_WREG; p.ku = 1; p.lds = CONV3_WREG_LDS; }
   else if (gemm_is_conv3(g)) { p.kernel = GEMM_KERNEL_CONV3; p.ku = 1; p.lds = CONV3_VH_LDS; }
   else if (g.dual_b) { p.kernel = GEMM_KERNEL_DUALB; p.ku = ku == 2 ? 2 : 1; p.lds = p.ku * GEMM_DUALB_LDS; } // a requested KU of 4 has no dual-B instantiation
@@ -1371,6 +1490,7 @@ static inline void gemm_launch_conv3_wreg(const GemmPlan &p, const GemmArgs &g, 
 }
 static inline void gemm_launch_wreg(const GemmPlan &p, const GemmArgs &g, hipStream_t s) {
   if (g.mode == GEMM_OUT_F32) gemm_launch<gemm_f16_wreg_kernel<GEMM_OUT_F32>>(p, g, s);
+  else if (g.mode == GEMM_OUT_QKV && p.qkv_lds) gemm_launch<gemm_f16_wreg_kernel<GEMM_OUT_QKV, GEMM_WREG_D, true>>(p, g, s);
   else if (g.mode == GEMM_OUT_QKV) gemm_launch<gemm_f16_wreg_kernel<GEMM_OUT_QKV>>(p, g, s);
   else gemm_launch<gemm_f16_wreg_kernel<GEMM_OUT_QKV_SPLIT>>(p, g, s);
 }

@@ -39,6 +39,14 @@ struct tts_gemm_case {
 int tts_gemm_test_margin(void) { return TTS_GEMM_TEST_MARGIN; }
 int tts_gemm_test_auto_th(int M, int N) { return gemm_auto_th(M, N); }
 long long tts_gemm_test_wfrag3_index(int n, int tap, int k, int N, int K) { return (long long)gemm_wfrag3_index(n, tap, k, N, K); } // where the loader puts tap `tap` of W[n][tap * K + k]
+// the LDS maps of gemm_epilogue_wreg_qkv_lds (host evaluation of the kernel's own constexpr functions): the byte offset of the first element a lane parks (read = 0:
+// accumulator a = i, b = j) or stores (read = 1: pass a), and that element's coordinates in its half of the tile
+int tts_gemm_test_qkv_lds(int read, int nat, int wave, int lane, int a, int b, int *r, int *c) {
+  const QkvLdsPos q = read ? qkv_lds_read(nat != 0, wave, lane, a) : qkv_lds_park(nat != 0, wave, lane, a, b);
+  if (r) *r = q.r;
+  if (c) *c = q.c;
+  return qkv_lds_off(nat != 0, q.r, q.c);
+}
 
 } // extern "C"
 
@@ -65,7 +73,7 @@ GemmArgs host_args(const tts_gemm_case &c) { // the fields the dispatcher reads;
 void describe(const GemmArgs &g, char *buf, int cap) {
   static const char *const names[] = {"vh", "dualb", "conv3", "wreg", "conv3w"};
   const GemmPlan p = gemm_plan(g);
-  snprintf(buf, cap, "%s mode=%d th=%d ku=%d cn=%d", names[p.kernel], g.mode, p.th, p.ku, p.cn);
+  snprintf(buf, cap, "%s mode=%d th=%d ku=%d cn=%d%s", names[p.kernel], g.mode, p.th, p.ku, p.cn, p.qkv_lds ? " qkv_lds" : "");
 }
 
 struct Dev { // one device allocation: margin | payload | margin
